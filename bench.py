@@ -28,7 +28,8 @@ Beside it:
 Launch: `python bench.py` (one GPU), or one rank per GPU under torch.distributed.run with --gpus N = WORLD_SIZE (chunks
 are sharded by rank, no collective on the data path), or `python bench.py --gpus N` in ONE process: the library's work
 queue (mrp_queue_*) then drives N devices itself.  Any other combination is refused.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes the last timed step's results for a fixed, seeded sample of
+its chunks as DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
 """
 from __future__ import annotations
 
@@ -44,6 +45,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: the whole dump stays below this
+DUMP_MAX_CHUNKS = 256
+DUMP_SEED = 20240607
 
 
 def parse_args():
@@ -69,6 +73,9 @@ def parse_args():
     ap.add_argument("--sum-chunks", type=int, default=16, help="chunks whose sweeps the log-sum-exp leg replays (0: skip)")
     ap.add_argument("--genome-chunks", type=int, default=3900, help="chunks of the configs[3]/8 leg: one GPU's eighth of a 31 000-chunk genome (0: skip)")
     ap.add_argument("--parity-chunks", type=int, default=16, help="chunks of the timed step whose results are compared with the oracle's (needs the cpu_baseline leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results for a fixed, seeded sample of its chunks as DIR/<name>.npy "
+                         f"(float64 / float32, at most {DUMP_MAX_BYTES >> 20} MB in all)")
     ap.add_argument("--queue-child", action="store_true", help="(internal) run the work queue leg alone and print its runs as one JSON line")
     ap.add_argument("--queue-device", type=int, default=0, help="(internal) device of the queue child")
     return ap.parse_args()
@@ -78,7 +85,6 @@ def queue_child(args):
     """The work queue leg in a process of its own (started by the parent before IT touches the GPU): a caller of the queue holds no
     other family of contexts, and the queue's workers bring contexts, streams, a host pool and allocator caches of their own --
     whichever of the two families of a process comes second runs 3-6 % slower at 1 152 chunks (measured both ways round)."""
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     from margin_amd import capi, sharding, synth
     params = capi.Params.from_reference_names(synth.shipped_phase_params())
     cpu_share = max(1, os.cpu_count() or 8)
@@ -180,6 +186,47 @@ def path_traffic(n_chunks_per_step, workload_sites):
     return float(tj["hbm_bytes_per_batch"]) * n_chunks_per_step / float(tj["chunks"]), tj.get("source")
 
 
+DUMP_SITE_KEYS = {"hap1": "float64", "hap2": "float64", "genotype": "float64", "ancestor": "float64", "support1": "float64",
+                  "support2": "float64", "genotype_probs": "float32", "hap_probs1": "float32", "hap_probs2": "float32"}
+
+
+def dump_sample(chunks):
+    """--dump-outputs: a fixed, seeded sample of the step's chunks (sorted), as many as fit DUMP_MAX_BYTES by a bound taken from
+    the inputs alone (per site: six float64 and three float32 arrays; per read: one float64 in reads1 or reads2; 64 B of scalars)"""
+    import numpy as np
+    idx, total = [], 0
+    for i in np.random.default_rng(DUMP_SEED).permutation(len(chunks))[:DUMP_MAX_CHUNKS]:
+        c = chunks[int(i)]
+        b = 60 * len(c.allele_number) + 8 * len(c.reads) + 64
+        if total + b > DUMP_MAX_BYTES:
+            break
+        idx.append(int(i))
+        total += b
+    return sorted(idx)
+
+
+def write_dump(dirname, idx, results):
+    """--dump-outputs: what mrp_phase_reads_many handed back for the chunks `idx`, one array per result field, concatenated over the
+    chunks in the order of idx.  Per-site fields hold `length` entries per chunk, reads1 / reads2 n_reads1 / n_reads2 entries per chunk
+    (read indices of the chunk's read list).  Integer fields are stored as float64 (exact: all are far below 2^53)."""
+    import numpy as np
+    f64 = lambda xs: np.asarray(xs, dtype=np.float64)
+    cat = lambda k, dt: np.concatenate([np.zeros(0, dt)] + [np.asarray(r[k]).astype(dt) for r in results])
+    arrays = dict(chunk_index=f64(idx), ref_start=f64([r["ref_start"] for r in results]), length=f64([r["length"] for r in results]),
+                  n_reads1=f64([len(r["reads1"]) for r in results]), n_reads2=f64([len(r["reads2"]) for r in results]),
+                  hmm_forward=f64([r["hmm_forward"] for r in results]), hmm_backward=f64([r["hmm_backward"] for r in results]),
+                  n_sweeps=f64([r["n_sweeps"] for r in results]), reads1=cat("reads1", np.float64), reads2=cat("reads2", np.float64))
+    for k, dt in DUMP_SITE_KEYS.items():
+        arrays[k] = cat(k, dt)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"bench.py: the dump of {len(idx)} chunks would take {total} bytes, above {DUMP_MAX_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+    return dict(dir=dirname, chunks=len(idx), files=sorted(arrays), bytes=int(total), sample_seed=DUMP_SEED)
+
+
 def insitu_rooflines(st):
     """Per kernel family IN THE REAL STEP (not the replay): the algorithmic bytes the family is responsible for (SURVEY.md 8d:
     recursion 16 B per cell + 32 B per merge cell + 8 B per column; prune: the 8 B per cell of f and b it ranks; cross product +
@@ -245,10 +292,9 @@ def main():
         sys.exit(f"bench.py: --gpus {n_gpus} but WORLD_SIZE={world}: launch one rank per GPU (torch.distributed.run --nproc-per-node {n_gpus}) "
                  f"or a single process")
     single_process_multi = world == 1 and n_gpus > 1
+    if args.dump_outputs and args.steps < 1:
+        sys.exit("bench.py: --dump-outputs writes the results of the last timed step: it needs --steps 1 or more")
 
-    # torch initialises HIP before libmargin_rphmm.so is loaded: the library's own default (its concurrent batches need more
-    # hardware queues than the runtime's 4, include/margin_rphmm.h) has to be in the environment by then
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     import torch
     dist = None
     if world > 1:
@@ -311,6 +357,9 @@ def main():
     # ---- the timed region: every chunk phased end to end, K times -------------------------------------------------
     # parity stamp: the results of the LAST timed step for the first chunks stay unconverted until the clock has stopped
     n_parity = min(args.parity_chunks, len(chunks)) if (rank == 0 and not args.no_cpu_baseline and n_gpus == 1) else 0
+    # --dump-outputs: the results of the last timed step for a seeded sample of its chunks (rank 0's), kept the same way
+    dump_idx = dump_sample(chunks) if (args.dump_outputs and rank == 0) else []
+    kept = sorted(set(range(n_parity)) | set(dump_idx))
     if single_process_multi:
         queue = capi.Queue(queue_devices)
         descs = capi.chunk_descs(chunks)
@@ -328,13 +377,15 @@ def main():
     st, step_results, step_ms = None, None, []
     for k_ in range(args.steps):
         t_s = time.perf_counter()
-        step_results, st = step(range(n_parity) if k_ + 1 == args.steps else ())
+        step_results, st = step(kept if k_ + 1 == args.steps else ())
         step_ms.append(1e3 * (time.perf_counter() - t_s))
     barrier()
     elapsed, host_cpu = time.perf_counter() - t0, time.process_time() - c0
     elapsed, units_all = sharding.reduce_elapsed_and_units(dist, elapsed, units, device=reduce_dev)
-    gpu_sample = [step_results[i].get() for i in range(n_parity)] if step_results is not None else []
-    step_results = None
+    last = {i: step_results[i].get() for i in kept} if step_results is not None else {}
+    gpu_sample = [last[i] for i in range(n_parity)] if last else []
+    dump_info = write_dump(args.dump_outputs, dump_idx, [last[i] for i in dump_idx]) if dump_idx else None
+    step_results, last = None, None
     # (--steps 0: the counter passes of tools/collect_profiles_r05.sh, which want the replay leg's launches alone in the trace)
     value = units_all * args.steps / elapsed if args.steps > 0 else 0.0
     ms_per_step = 1e3 * elapsed / args.steps if args.steps > 0 else float("nan")
@@ -350,6 +401,8 @@ def main():
     out = dict(metric="het-sites x reads phased/sec (30x ONT synthetic chunks, end to end: every merge level + final sweep)",
                value=value, unit="het-site-reads/s", n_gpus=n_gpus, steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step,
                higher_is_better=True, scaling="weak", vs_baseline=None, dtype="int32", data="synthetic", config=cfg)
+    if dump_info is not None:
+        out["dump_outputs"] = dump_info
     if not single_process_multi and st is not None:
         out["step_detail"] = dict(resident=int(st.resident), fallback_chunks=int(st.fallback_chunks), levels=int(st.levels), hmms=int(st.hmms),
                                   columns=int(st.columns), cells=int(st.cells), merge_cells=int(st.merge_cells), device_ms=float(st.device_ms),

@@ -208,7 +208,7 @@ def load():
         raise FileNotFoundError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
     L = C.CDLL(LIB_PATH)
     L.mrp_runtime_init.restype = C.c_int
-    L.mrp_runtime_init()  # before the first HIP call of this process (hardware queues for the concurrent batches)
+    L.mrp_runtime_init()  # before the first HIP call of this process (as INTEGRATION.md asks of a caller)
     vp, i64, i32, u32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32
     P = C.POINTER
     L.mrp_last_error.restype = C.c_char_p

@@ -277,8 +277,8 @@ struct DevBuf {
 struct mrp_context {
     int device = 0;
     hipStream_t stream = nullptr;
-    /* Streams beyond the main one are made when first asked for: the device's hardware queues (GPU_MAX_HW_QUEUES, 16 after
-     * mrp_runtime_init) are dealt to streams in creation order, and every stream more than that shares a queue with another --
+    /* Streams beyond the main one are made when first asked for: the device's hardware queues (GPU_MAX_HW_QUEUES, as the
+     * environment sets it) are dealt to streams in creation order, and every stream more than that shares a queue with another --
      * whose kernels it then waits for.  A context that is one of several concurrent batches (`grouped`: the siblings of
      * mrp_phase_reads_many, a work queue's contexts) runs its size classes on its main stream (2 streams a batch, 16 for the
      * eight batches of a call); a context on its own runs them side by side on two more. */

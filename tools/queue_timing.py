@@ -1,6 +1,5 @@
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from concurrent.futures import ThreadPoolExecutor
 from margin_amd import capi, sharding, synth
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 1152
