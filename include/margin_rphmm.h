@@ -491,6 +491,62 @@ int mrp_allele_read_supports(mrp_context *ctx, const mrp_pair_hmm *forward_model
                              const uint8_t *read_forward_strand, int64_t expansion, int64_t sv_threshold, float *support,
                              mrp_pairhmm_stats *stats);
 
+/* Haplotagging the filtered reads and phasing the filtered variants: the two pair-HMM loops of margin phase's chunk loop
+ * after the phasing (phase.c:413,432; tools/tagFromPhasedVcf.c:308).  Sites and reads of any number of chunks travel in one
+ * call: they are concatenated, and read indices are global to the call (every per-read array has n_reads entries).
+ * A site is a primary bubble (partition) or a VCF entry (phasing); its entries are the read substrings the reference
+ * lists for it, in the order buildVcfEntryToReadSubstringsMap (bubbleGraph.c:1281-1323) lists them: the order of the
+ * chunk's reads.  Symbols as above; nucleotide emissions only. */
+typedef struct mrp_haptag_sites {
+    int64_t n_sites;
+    const uint8_t *pool; /* symbols of every allele and read substring */
+    int64_t pool_bytes;
+    const int64_t *allele_first; /* n_sites + 1, from 0: site s owns alleles [allele_first[s], allele_first[s + 1]) */
+    const int64_t *allele_off;   /* per allele: its symbols in pool */
+    const int32_t *allele_len;
+    const int32_t *compare;     /* 2 * n_sites: the two alleles compared at site s, indices within the site (hap1 / hap2 allele
+                                 * of the fragment, or gt1 / gt2) */
+    const int64_t *entry_first; /* n_sites + 1, from 0: site s owns entries [entry_first[s], entry_first[s + 1]) */
+    const int64_t *entry_read;  /* per entry: the read, in [0, n_reads) */
+    const int64_t *entry_off;   /* per entry: the read substring in pool */
+    const int32_t *entry_len;
+} mrp_haptag_sites;
+
+/* bubbleGraph_partitionFilteredReadsFromVcfEntries (bubbleGraph.c:1749-1943) and its twin
+ * bubbleGraph_partitionFilteredReadsFromPhasedVcfEntries (:1945-2138), which differ only in where the two compared alleles
+ * come from.  A site whose two compared indices are equal (:1780) or that has no entries is skipped.  At every other
+ * site each read substring is aligned to the two alleles, never anchored (:1832); as in the reference (b->reads is filled
+ * by popping, :1818) the LAST-listed entry with a given substring owns the scores, and its read's strand picks the state
+ * machine for every duplicate.  Supports are rounded to float (:1869); per read, in site order, in fp64:
+ * h1 += s1 - logAddExact(s1, s2), h2 += s2 - logAddExact(s2, s1) (:1879-1888).  Out per read: hap = 1 (h1 > h2), 2
+ * (h2 > h1) or 0 (unclassified, :1913-1925), h1, h2.  A pair whose widest diagonal exceeds 2 048 cells is refused
+ * (MRP_ERR_UNSUPPORTED, as mrp_forward_probabilities) before anything is launched.  stats may be NULL; kernel_ms covers
+ * the pair-HMM and the scoring kernels. */
+int mrp_partition_reads_by_haplotype(mrp_context *ctx, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                                     const mrp_haptag_sites *sites, int64_t n_reads, const uint8_t *read_forward_strand,
+                                     int64_t expansion, int32_t *hap, double *h1, double *h2, mrp_pairhmm_stats *stats);
+
+/* state of a variant after mrp_phase_variants_from_tagged_reads */
+#define MRP_VARIANT_NOT_VISITED 0 /* homozygous (gt1 == gt2, :2174) or no entries (:2186-2192): the reference leaves it alone */
+#define MRP_VARIANT_CIS 1         /* cis > trans: gt1 | gt2 kept */
+#define MRP_VARIANT_TRANS 2       /* trans > cis: gt swapped to gt2 | gt1 */
+#define MRP_VARIANT_TIE 3         /* cis == trans (also: no tagged entry): the reference sets gt to -1 | -1 (:2300-2328) */
+
+/* bubbleGraph_phaseVcfEntriesFromHaplotaggedReads (bubbleGraph.c:2140-2351).  compare holds (gt1, gt2) of every variant.
+ * read_hap: 1 or 2 for reads tagged haplotype 1 / 2, anything else for untagged; resolving the reference's read-name sets
+ * (:2145-2158) is the caller's.  The chunk filter on the root VCF entry's position (:2179) is the caller's too: leave
+ * variants outside the chunk out of the call.  Untagged entries are neither scored nor cached (:2226-2235), so the FIRST
+ * tagged entry with a given substring owns the scores (its strand picks the state machine).  Supports stay fp64; a pair
+ * whose read substring or allele is longer than sv_threshold is banded around its k-mer anchors (:2253-2263, the rule
+ * of mrp_allele_read_supports).  Per variant, in entry order: cis += hap1 ? a - logAddExact(a, b) : b - logAddExact(a, b),
+ * trans the other one (:2280-2287).  Out per variant: state (MRP_VARIANT_*), cis, trans (0 for a variant not visited).
+ * The update of rootVcfEntry->alleleIdxToReads (:2330-2345) follows from read_hap and the state and stays with the
+ * caller.  Errors as mrp_partition_reads_by_haplotype. */
+int mrp_phase_variants_from_tagged_reads(mrp_context *ctx, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                                         const mrp_haptag_sites *variants, int64_t n_reads, const uint8_t *read_forward_strand,
+                                         const int32_t *read_hap, int64_t expansion, int64_t sv_threshold, int32_t *state,
+                                         double *cis, double *trans, mrp_pairhmm_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = [
     "mrp_stitch_chunk", "mrp_stitch_size", "mrp_stitch_lookup", "mrp_phase_sets", "mrp_binomial_p_value", "mrp_binomial_coefficient",
     "mrp_symbols_from_chars", "mrp_pair_hmm_reverse_complement", "mrp_band_diagonals", "mrp_forward_probabilities",
     "mrp_allele_read_supports", "mrp_kmer_alignment_anchors", "mrp_phase_chunks_on_devices", "mrp_queue_plan", "mrp_queue_dry_run", "mrp_queue_create", "mrp_queue_destroy",
-    "mrp_queue_phase_chunks",
+    "mrp_queue_phase_chunks", "mrp_partition_reads_by_haplotype", "mrp_phase_variants_from_tagged_reads",
 ]
 
 
@@ -199,6 +199,15 @@ class PairHmmStats(C.Structure):
     _fields_ = [("pairs_lane", C.c_int64), ("pairs_wave", C.c_int64), ("cells", C.c_int64), ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class HaptagSites(C.Structure):
+    _fields_ = [("n_sites", C.c_int64), ("pool", C.c_void_p), ("pool_bytes", C.c_int64), ("allele_first", C.c_void_p), ("allele_off", C.c_void_p),
+                ("allele_len", C.c_void_p), ("compare", C.c_void_p), ("entry_first", C.c_void_p), ("entry_read", C.c_void_p),
+                ("entry_off", C.c_void_p), ("entry_len", C.c_void_p)]
+
+
+VARIANT_NOT_VISITED, VARIANT_CIS, VARIANT_TRANS, VARIANT_TIE = 0, 1, 2, 3
+
+
 def load():
     """dlopen the in-tree library; raises if it has not been built (no fallback)."""
     global _lib
@@ -277,6 +286,8 @@ def load():
     L.mrp_band_diagonals.argtypes = [vp, i64, i64, i64, i64, vp, vp]
     L.mrp_forward_probabilities.argtypes = [vp, vp, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, P(PairHmmStats)]
     L.mrp_allele_read_supports.argtypes = [vp, P(PairHmm), P(PairHmm), i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, P(PairHmmStats)]
+    L.mrp_partition_reads_by_haplotype.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, i64, vp, vp, vp, P(PairHmmStats)]
+    L.mrp_phase_variants_from_tagged_reads.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, vp, i64, i64, vp, vp, vp, P(PairHmmStats)]
     L.mrp_kmer_alignment_anchors.argtypes = [vp, i64, vp, i64, vp]
     L.mrp_kmer_alignment_anchors.restype = i64
     L.mrp_phase_chunks_on_devices.argtypes = [vp, i32, i64, P(ChunkDesc), P(Params), i64, P(P(PhaseResult)), P(QueueStats)]
@@ -941,3 +952,58 @@ def allele_read_supports(ctx: Context, forward_model: PairHmm, reverse_model: Pa
         out.append(sup[p:p + int(sz)].reshape(int(af[b + 1] - af[b]), int(rf[b + 1] - rf[b])))
         p += int(sz)
     return out, st
+
+
+def _haptag_sites(sites):
+    """sites: list of (alleles, (i, j), entries): alleles a list of uint8 symbol arrays, (i, j) the two compared allele
+    indices, entries a list of (read index, uint8 symbol array) in the order of the chunk's reads.
+    Returns (HaptagSites, the arrays it points into)."""
+    strings, a_first, e_first, a_off, a_len, cmp_, e_read, e_off, e_len, pos = [], [0], [0], [], [], [], [], [], [], 0
+    for alleles, (i, j), entries in sites:
+        for a in alleles:
+            a = np.ascontiguousarray(a, dtype=np.uint8)
+            strings.append(a); a_off.append(pos); a_len.append(len(a)); pos += len(a)
+        for r, sub in entries:
+            sub = np.ascontiguousarray(sub, dtype=np.uint8)
+            strings.append(sub); e_read.append(int(r)); e_off.append(pos); e_len.append(len(sub)); pos += len(sub)
+        cmp_ += [int(i), int(j)]
+        a_first.append(len(a_off))
+        e_first.append(len(e_off))
+    keep = [np.concatenate(strings) if pos else np.zeros(0, dtype=np.uint8), np.array(a_first, dtype=np.int64), np.array(a_off, dtype=np.int64),
+            np.array(a_len, dtype=np.int32), np.array(cmp_, dtype=np.int32), np.array(e_first, dtype=np.int64), np.array(e_read, dtype=np.int64),
+            np.array(e_off, dtype=np.int64), np.array(e_len, dtype=np.int32)]
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data
+    S = HaptagSites(len(sites), ptr(keep[0]), keep[0].size, *[ptr(a) for a in keep[1:]])
+    return S, keep
+
+
+def partition_reads_by_haplotype(ctx: Context, forward_model: PairHmm, reverse_model: PairHmm, sites, n_reads: int, read_forward_strand,
+                                 expansion: int = 4):
+    """bubbleGraph_partitionFilteredReadsFromVcfEntries (bubbleGraph.c:1749-1943) for the sites of any number of chunks; sites as
+    _haptag_sites takes them, (i, j) = (hap1, hap2) allele.  Returns (hap int32 [n_reads]: 1, 2 or 0, h1, h2, PairHmmStats)."""
+    S, keep = _haptag_sites(sites)
+    sd = np.ascontiguousarray(read_forward_strand, dtype=np.uint8).astype(bool).astype(np.uint8)
+    assert sd.size == n_reads
+    hap, h1, h2 = np.zeros(n_reads, dtype=np.int32), np.zeros(n_reads), np.zeros(n_reads)
+    st = PairHmmStats()
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data
+    _check(load().mrp_partition_reads_by_haplotype(ctx.h, C.byref(forward_model), C.byref(reverse_model), C.byref(S), int(n_reads), ptr(sd),
+                                                   int(expansion), ptr(hap), ptr(h1), ptr(h2), C.byref(st)))
+    return hap, h1, h2, st
+
+
+def phase_variants_from_tagged_reads(ctx: Context, forward_model: PairHmm, reverse_model: PairHmm, variants, n_reads: int, read_forward_strand,
+                                     read_hap, expansion: int = 4, sv_threshold: int = 512):
+    """bubbleGraph_phaseVcfEntriesFromHaplotaggedReads (bubbleGraph.c:2140-2351); variants as _haptag_sites takes them, (i, j) = (gt1, gt2);
+    read_hap: 1 / 2 tagged, anything else untagged.  Returns (state int32 [n_variants]: VARIANT_*, cis, trans, PairHmmStats)."""
+    S, keep = _haptag_sites(variants)
+    sd = np.ascontiguousarray(read_forward_strand, dtype=np.uint8).astype(bool).astype(np.uint8)
+    rh = np.ascontiguousarray(read_hap, dtype=np.int32)
+    assert sd.size == n_reads and rh.size == n_reads
+    n = len(variants)
+    state, cis, trans = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n)
+    st = PairHmmStats()
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data
+    _check(load().mrp_phase_variants_from_tagged_reads(ctx.h, C.byref(forward_model), C.byref(reverse_model), C.byref(S), int(n_reads), ptr(sd),
+                                                       ptr(rh), int(expansion), int(sv_threshold), ptr(state), ptr(cis), ptr(trans), C.byref(st)))
+    return state, cis, trans, st

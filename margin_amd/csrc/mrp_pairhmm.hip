@@ -1,7 +1,8 @@
 /*
  * mrp_pairhmm.hip -- read x allele alignment likelihoods: the banded pair-HMM forward probability of the reference
  * (computeForwardProbability, impl/pairwiseAligner.c:849-903) for batches of string pairs, and the alleleReadSupports
- * loop around it (impl/bubbleGraph.c:1421-1464).  gfx950 only; compiled with -ffp-contract=off.
+ * loop around it (impl/bubbleGraph.c:1421-1464), and the filtered-read / filtered-variant loops after the phasing
+ * (:1749-2351: the supports stay on the device, a scoring kernel reduces them).  gfx950 only; compiled with -ffp-contract=off.
  *
  * The recursion (stateMachine3_cellCalculate, impl/stateMachine.c:562-586) gives every dp cell (x, y) three states from
  * its neighbours (x-1, y), (x-1, y-1), (x, y-1); a neighbour outside the band contributes nothing, which is what a
@@ -507,6 +508,353 @@ int64_t kmer_anchors(const uint8_t *sx, int64_t lx, const uint8_t *sy, int64_t l
     return n;
 }
 
+/* The launch half of a pair-HMM batch: what a queued launch reads until its stream has drained (the host sources of its
+ * uploads, its device buffers) and where the log probabilities land (d_out, indexed by pair).  The destructor drains the
+ * stream, so an early return never frees what a queued copy or kernel still reads. */
+struct PhmLaunch {
+    hipStream_t s = nullptr;
+    int64_t cells = 0;
+    std::vector<PhmModelDev> hm;
+    HostVec<PhmLanePair> lane_pairs[4];
+    HostVec<PhmPair> wave_pairs[4];
+    HostVec<int32_t> band;
+    DevBuf<PhmModelDev> d_models;
+    DevBuf<uint8_t> d_pool;
+    DevBuf<int32_t> d_band;
+    DevBuf<double> d_out;
+    DevBuf<PhmLanePair> d_lane[4];
+    DevBuf<PhmPair> d_wave[4];
+    ~PhmLaunch() {
+        if (s) (void) hipStreamSynchronize(s);
+    }
+    void release() {
+        d_models.release(); d_pool.release(); d_band.release(); d_out.release();
+        for (auto &b : d_lane) b.release();
+        for (auto &b : d_wave) b.release();
+    }
+};
+
+/* Classify, upload and queue the kernels of n_pairs > 0 pairs on ctx->stream; ctx->ev[0] is recorded before the first
+ * kernel.  Errors (prefixed with who) are raised on the host, before anything is launched. */
+int phm_launch(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, int32_t n_models, int64_t n_pairs, const uint8_t *pool,
+               int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len, const int64_t *y_off, const int32_t *y_len,
+               const uint8_t *model_index, const int64_t *anchor_off, const int64_t *anchors, int64_t expansion, int ragged_left,
+               int ragged_right, PhmLaunch &L, mrp_pairhmm_stats *stats) {
+    if (n_pairs >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
+    if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
+
+    /* classify.  The pair-per-lane kernel takes the unanchored pairs whose x string fits its LDS row next to the tables;
+     * launch classes by x length (4, 3, 2, 1 waves per workgroup = per CU). */
+    const int table_bytes = (16 + n_models * PHM_ETAB) * (int) sizeof(double);
+    /* (-1: the tables of this many models leave no room for a row, every pair goes to the pair-per-wave kernel) */
+    const int lane_max_x = PHM_LDS_BYTES - table_bytes < PHM_LANE_BYTES_PER_X ? -1 : std::min(PHM_LANE_MAX_X, (PHM_LDS_BYTES - table_bytes) / PHM_LANE_BYTES_PER_X);
+    int lane_cap[4];
+    for (int c = 0; c < 4; c++) lane_cap[c] = std::min(lane_max_x, (PHM_LDS_BYTES - table_bytes) / ((4 - c) * PHM_LANE_BYTES_PER_X));
+    constexpr uint32_t WAVE_KEY = 0xFFFFFFFFu;
+    constexpr int LY_CLIP = 4095;
+    HostVec<uint32_t> key((size_t) n_pairs);
+    std::atomic<int64_t> bad{-1}, cells_atomic{0};
+    mrp_parallel_for((n_pairs + 16383) / 16384, 1, [&](int64_t blk) {
+        int64_t c_local = 0;
+        for (int64_t i = blk * 16384; i < std::min(n_pairs, (blk + 1) * 16384); i++) {
+            const int64_t lx = x_len[i], ly = y_len[i];
+            const int mi = model_index ? model_index[i] : 0;
+            const int64_t na = anchor_off ? anchor_off[i + 1] - anchor_off[i] : 0;
+            if (lx < 0 || ly < 0 || x_off[i] < 0 || y_off[i] < 0 || x_off[i] + lx > pool_bytes || y_off[i] + ly > pool_bytes || mi >= n_models || na < 0 ||
+                (na > 0 && !anchors)) {
+                int64_t expect = -1;
+                bad.compare_exchange_strong(expect, i);
+                key[(size_t) i] = WAVE_KEY;
+                continue;
+            }
+            if (na == 0 && lx <= lane_max_x) {
+                key[(size_t) i] = (uint32_t) (std::min<int64_t>(ly, LY_CLIP) << 7 | lx);
+                c_local += (lx + 1) * (ly + 1);
+            } else {
+                key[(size_t) i] = WAVE_KEY;
+            }
+        }
+        cells_atomic += c_local;
+    });
+    if (bad.load() >= 0)
+        return mrp_set_error(MRP_ERR_ARG, "%s: pair %lld lies outside the symbol pool, names a model >= %d or has bad anchor offsets", who,
+                             (long long) bad.load(), n_models);
+    int64_t cells = cells_atomic.load();
+    /* pairs of similar shape share a wave (counting sort on (y length, x length), longest first so that the tail of a
+     * launch is made of the cheap ones) */
+    HostVec<PhmLanePair> *lane_pairs = L.lane_pairs;
+    int64_t lane_n[4] = {0, 0, 0, 0};
+    {
+        std::vector<int32_t> hist((size_t) (LY_CLIP + 1) << 7, 0);
+        for (int64_t i = 0; i < n_pairs; i++)
+            if (key[(size_t) i] != WAVE_KEY) hist[key[(size_t) i]]++;
+        int cls_of[128];
+        for (int lx = 0; lx < 128; lx++) {
+            int c = 0;
+            while (c < 3 && lx > lane_cap[c]) c++;
+            cls_of[lx] = c;
+        }
+        for (int64_t b = (int64_t) hist.size() - 1; b >= 0; b--) {
+            const int32_t h = hist[(size_t) b];
+            if (!h) continue;
+            const int c = cls_of[b & 127];
+            hist[(size_t) b] = (int32_t) lane_n[c];
+            lane_n[c] += h;
+        }
+        for (int c = 0; c < 4; c++) lane_pairs[c].resize((size_t) lane_n[c]);
+        for (int64_t i = 0; i < n_pairs; i++) {
+            const uint32_t k = key[(size_t) i];
+            if (k == WAVE_KEY) continue;
+            PhmLanePair &q = lane_pairs[cls_of[k & 127]][(size_t) hist[k]++];
+            q.x_off = x_off[i];
+            q.y_off = y_off[i];
+            q.lx = x_len[i];
+            q.ly = y_len[i];
+            q.model = model_index ? model_index[i] : 0;
+            q.out = (int32_t) i;
+        }
+    }
+    HostVec<PhmPair> *wave_pairs = L.wave_pairs;
+    HostVec<int32_t> &band = L.band;
+    std::vector<int32_t> Lb, Rb;
+    for (int64_t i = 0; i < n_pairs; i++) {
+        if (key[(size_t) i] != WAVE_KEY) continue;
+        const int64_t lx = x_len[i], ly = y_len[i];
+        const int64_t na = anchor_off ? anchor_off[i + 1] - anchor_off[i] : 0;
+        PhmPair p;
+        p.x_off = x_off[i];
+        p.y_off = y_off[i];
+        p.band_off = -1;
+        p.lx = (int32_t) lx;
+        p.ly = (int32_t) ly;
+        p.model = model_index ? model_index[i] : 0;
+        p.out = (int32_t) i;
+        int width;
+        if (na == 0) {
+            width = (int) std::min(lx, ly) + 1;
+            cells += (lx + 1) * (ly + 1);
+        } else {
+            if (lx + ly >= (1ll << 30)) return mrp_set_error(MRP_ERR_ARG, "%s: strings too long", who);
+            Lb.resize((size_t) (lx + ly + 1));
+            Rb.resize((size_t) (lx + ly + 1));
+            int64_t c = 0;
+            const int rc = band_closed_form(anchors + 2 * anchor_off[i], na, lx, ly, expansion, Lb.data(), Rb.data(), &c, &width);
+            if (rc != MRP_OK) return mrp_set_error(rc, "%s: pair %lld has invalid anchors (pairwiseAligner.c:206-211)", who, (long long) i);
+            cells += c;
+            p.band_off = (int64_t) band.size() / 2;
+            for (int64_t d = 0; d <= lx + ly; d++) { band.push_back(Lb[(size_t) d]); band.push_back(Rb[(size_t) d]); }
+        }
+        if (width > PHM_WAVE_MAX_WIDTH)
+            return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: pair %lld has a diagonal of %d cells (limit %d)", who, (long long) i, width, PHM_WAVE_MAX_WIDTH);
+        int c = 0;
+        while (width > WAVE_CLASS_CAP[c]) c++;
+        wave_pairs[c].push_back(p);
+    }
+    for (int c = 0; c < 4; c++)
+        std::sort(wave_pairs[c].begin(), wave_pairs[c].end(), [](const PhmPair &a, const PhmPair &b) {
+            const int64_t ca = (int64_t) a.lx * a.ly, cb = (int64_t) b.lx * b.ly;
+            return ca != cb ? ca > cb : a.out < b.out;
+        });
+    L.cells = cells;
+
+    PHM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    L.hm.resize((size_t) n_models);
+    bool has_switch = false;
+    for (int i = 0; i < n_models; i++) {
+        model_to_device(models[i], ragged_left, ragged_right, L.hm[(size_t) i]);
+        if (!(models[i].gap_switch_to_x == -INFINITY && models[i].gap_switch_to_y == -INFINITY)) has_switch = true;
+    }
+    L.d_models.pool = L.d_pool.pool = L.d_band.pool = L.d_out.pool = &ctx->pool;
+    L.s = s; /* from here on the destructor drains the stream */
+    PHM_HIP(L.d_models.upload(L.hm, s));
+    PHM_HIP(L.d_pool.alloc((size_t) pool_bytes));
+    if (pool_bytes) PHM_HIP(hipMemcpyAsync(L.d_pool.p, pool, (size_t) pool_bytes, hipMemcpyHostToDevice, s));
+    PHM_HIP(L.d_band.upload(band, s));
+    PHM_HIP(L.d_out.alloc((size_t) n_pairs));
+    for (int c = 0; c < 4; c++) {
+        L.d_lane[c].pool = L.d_wave[c].pool = &ctx->pool;
+        PHM_HIP(L.d_lane[c].upload(lane_pairs[c], s));
+        PHM_HIP(L.d_wave[c].upload(wave_pairs[c], s));
+    }
+    /* once per device (contexts of several host threads may call concurrently) */
+    static PerDeviceOnce once;
+    const hipError_t configured = once.run([] {
+        hipError_t e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *) phm_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
+        return e;
+    });
+    PHM_HIP(configured);
+    /* kernel_ms must not contain the tail of the uploads (the copy engine finishes them behind the event otherwise) */
+    if (stats) PHM_HIP(hipStreamSynchronize(s));
+    PHM_HIP(hipEventRecord(ctx->ev[0], s));
+    for (int c = 0; c < 4; c++) {
+        const int64_t n = (int64_t) lane_pairs[c].size();
+        if (n == 0) continue;
+        int cap = 1;
+        for (const PhmLanePair &p : lane_pairs[c]) cap = std::max(cap, (int) p.lx);
+        const int row_bytes = cap * PHM_LANE_BYTES_PER_X;
+        const int nw = std::max(1, std::min(4, (PHM_LDS_BYTES - table_bytes) / row_bytes));
+        const size_t lds = (size_t) table_bytes + (size_t) nw * row_bytes;
+        const int64_t per_wg = (int64_t) nw * PHM_WAVE;
+        if (has_switch)
+            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, true>), dim3((unsigned) ((n + per_wg - 1) / per_wg)), dim3((unsigned) per_wg), lds, s, L.d_lane[c].p, n, L.d_pool.p,
+                               L.d_models.p, (int) n_models, cap, L.d_out.p);
+        else
+            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, false>), dim3((unsigned) ((n + per_wg - 1) / per_wg)), dim3((unsigned) per_wg), lds, s, L.d_lane[c].p, n, L.d_pool.p,
+                               L.d_models.p, (int) n_models, cap, L.d_out.p);
+        PHM_HIP(hipGetLastError());
+        if (stats) stats->pairs_lane += n;
+    }
+    for (int c = 0; c < 4; c++) {
+        const int64_t n = (int64_t) wave_pairs[c].size();
+        if (n == 0) continue;
+        const int W = WAVE_CLASS_CAP[c];
+        const size_t lds = (size_t) 9 * W * sizeof(double);
+        hipLaunchKernelGGL(phm_wave_kernel, dim3((unsigned) std::min<int64_t>(n, 16384)), dim3(PHM_WAVE), lds, s, L.d_wave[c].p, n, L.d_pool.p,
+                           L.d_models.p, L.d_band.p, W, L.d_out.p);
+        PHM_HIP(hipGetLastError());
+        if (stats) stats->pairs_wave += n;
+    }
+    return MRP_OK;
+}
+
+/* cachedScores of the reference's bubble loops (bubbleGraph.c:1418,1844,2221, keyed by the substring alone): for every
+ * entry k of every group g (entries [first[g], first[g + 1])), owner[k] = the entry of the group whose scores k takes,
+ * itself if it is scored.  Only entries with may_own[k] != 0 (NULL: all) take part; the others get owner -1 (not scored,
+ * not cached).  last: among the entries of a group with equal substrings the last one owns the scores, else the first. */
+void substring_owners(int64_t n_groups, const int64_t *first, const uint8_t *pool, const int64_t *off, const int32_t *len,
+                      const uint8_t *may_own, bool last, std::vector<int64_t> &owner) {
+    owner.assign((size_t) first[n_groups], -1);
+    mrp_parallel_for(n_groups, 64, [&](int64_t g) {
+        std::vector<int64_t> order;
+        for (int64_t k = first[g]; k < first[g + 1]; k++)
+            if (!may_own || may_own[k]) order.push_back(k);
+        auto same = [&](int64_t a, int64_t c) { return len[a] == len[c] && memcmp(pool + off[a], pool + off[c], (size_t) len[a]) == 0; };
+        std::sort(order.begin(), order.end(), [&](int64_t a, int64_t c) {
+            if (len[a] != len[c]) return len[a] < len[c];
+            const int cmp = memcmp(pool + off[a], pool + off[c], (size_t) len[a]);
+            return cmp != 0 ? cmp < 0 : a < c;
+        });
+        for (size_t i = 0; i < order.size();) {
+            size_t j = i + 1;
+            while (j < order.size() && same(order[i], order[j])) j++;
+            const int64_t o = last ? order[j - 1] : order[i];
+            for (size_t q = i; q < j; q++) owner[(size_t) order[q]] = o;
+            i = j;
+        }
+    });
+}
+
+/* stMath_logAddExact (sonLib), as mrp_kernels.hip and rphmm_frame.c state it */
+static __device__ __forceinline__ double ht_log_add_exact(double x, double y) {
+    if (x == -__builtin_inf()) return y;
+    if (y == -__builtin_inf()) return x;
+    return x > y ? x + log(1.0 + exp(y - x)) : y + log(1.0 + exp(x - y));
+}
+
+struct HtEntry { /* the two log probabilities (indices into the pair-HMM output) of one read at one site */
+    int32_t a, b;
+    int32_t hap1; /* phasing: the read is tagged haplotype 1 (else 2) */
+    int32_t pad;
+};
+
+/* bubbleGraph.c:1876-1925: a lane per read walks the read's sites in order; the supports are floats (:1869, :1881-1882) */
+__global__ void __launch_bounds__(256) ht_partition_kernel(const int64_t *__restrict__ first, const HtEntry *__restrict__ e,
+                                                           const double *__restrict__ lp, int64_t n_reads, int32_t *__restrict__ hap,
+                                                           double *__restrict__ h1, double *__restrict__ h2) {
+    const int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    double t1 = 0.0, t2 = 0.0;
+    for (int64_t i = first[r]; i < first[r + 1]; i++) {
+        const double s1 = (double) (float) lp[e[i].a], s2 = (double) (float) lp[e[i].b];
+        t1 += s1 - ht_log_add_exact(s1, s2);
+        t2 += s2 - ht_log_add_exact(s2, s1);
+    }
+    hap[r] = t1 > t2 ? 1 : (t2 > t1 ? 2 : 0);
+    h1[r] = t1;
+    h2[r] = t2;
+}
+
+/* bubbleGraph.c:2274-2298: a lane per variant walks its tagged entries in order.  Both contributions come from the same
+ * two differences, so equal supports give equal totals (an exact tie). */
+__global__ void __launch_bounds__(256) ht_phase_kernel(const int64_t *__restrict__ first, const uint8_t *__restrict__ visited,
+                                                       const HtEntry *__restrict__ e, const double *__restrict__ lp, int64_t n_variants,
+                                                       int32_t *__restrict__ state, double *__restrict__ cis, double *__restrict__ trans) {
+    const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_variants) return;
+    double c = 0.0, t = 0.0;
+    for (int64_t i = first[v]; i < first[v + 1]; i++) {
+        const double sa = lp[e[i].a], sb = lp[e[i].b];
+        const double l = ht_log_add_exact(sa, sb);
+        const double da = sa - l, db = sb - l;
+        c += e[i].hap1 ? da : db;
+        t += e[i].hap1 ? db : da;
+    }
+    state[v] = !visited[v] ? MRP_VARIANT_NOT_VISITED : (c > t ? MRP_VARIANT_CIS : (t > c ? MRP_VARIANT_TRANS : MRP_VARIANT_TIE));
+    cis[v] = c;
+    trans[v] = t;
+}
+
+/* the checks both haplotagging entries share: MRP_ERR_ARG for malformed sites */
+int ht_check_sites(const char *who, const mrp_haptag_sites *S, int64_t n_reads, const uint8_t *read_forward_strand) {
+    if (!S || n_reads < 0 || S->n_sites < 0 || S->pool_bytes < 0) return mrp_set_error(MRP_ERR_ARG, "%s: bad sizes", who);
+    if (n_reads > 0 && !read_forward_strand) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    if (S->n_sites == 0) return MRP_OK;
+    if (!S->allele_first || !S->allele_off || !S->allele_len || !S->compare || !S->entry_first || (S->pool_bytes > 0 && !S->pool))
+        return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    if (S->allele_first[0] != 0 || S->entry_first[0] != 0) return mrp_set_error(MRP_ERR_ARG, "%s: offsets must start at 0", who);
+    for (int64_t s = 0; s < S->n_sites; s++) {
+        const int64_t na = S->allele_first[s + 1] - S->allele_first[s], ne = S->entry_first[s + 1] - S->entry_first[s];
+        if (na < 0 || ne < 0) return mrp_set_error(MRP_ERR_ARG, "%s: offsets not ascending at site %lld", who, (long long) s);
+        if (S->compare[2 * s] < 0 || S->compare[2 * s] >= na || S->compare[2 * s + 1] < 0 || S->compare[2 * s + 1] >= na)
+            return mrp_set_error(MRP_ERR_ARG, "%s: site %lld compares an allele it does not have", who, (long long) s);
+    }
+    const int64_t n_alleles = S->allele_first[S->n_sites], n_entries = S->entry_first[S->n_sites];
+    if (n_entries > 0 && (!S->entry_read || !S->entry_off || !S->entry_len)) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    for (int64_t j = 0; j < n_alleles; j++)
+        if (S->allele_len[j] < 0 || S->allele_off[j] < 0 || S->allele_off[j] + S->allele_len[j] > S->pool_bytes)
+            return mrp_set_error(MRP_ERR_ARG, "%s: allele %lld lies outside the pool", who, (long long) j);
+    for (int64_t k = 0; k < n_entries; k++) {
+        if (S->entry_len[k] < 0 || S->entry_off[k] < 0 || S->entry_off[k] + S->entry_len[k] > S->pool_bytes)
+            return mrp_set_error(MRP_ERR_ARG, "%s: read substring %lld lies outside the pool", who, (long long) k);
+        if (S->entry_read[k] < 0 || S->entry_read[k] >= n_reads) return mrp_set_error(MRP_ERR_ARG, "%s: entry %lld names read %lld of %lld", who,
+                                                                                       (long long) k, (long long) S->entry_read[k], (long long) n_reads);
+    }
+    return MRP_OK;
+}
+
+/* the pairs of the owning entries: (allele compare[0], entry) and (allele compare[1], entry) for every owner of an active
+ * site; pair_of[k] = index of the first of the two (-1 for entries that own nothing) */
+struct HtPairs {
+    std::vector<int64_t> xo, yo, anchor_off{0}, anchors, pair_of;
+    std::vector<int32_t> xl, yl;
+    std::vector<uint8_t> mi;
+};
+void ht_build_pairs(const mrp_haptag_sites *S, const std::vector<uint8_t> &active, const std::vector<int64_t> &owner,
+                    const uint8_t *read_forward_strand, int64_t sv_threshold, HtPairs &P) {
+    P.pair_of.assign(owner.size(), -1);
+    for (int64_t s = 0; s < S->n_sites; s++) {
+        if (!active[(size_t) s]) continue;
+        for (int64_t k = S->entry_first[s]; k < S->entry_first[s + 1]; k++) {
+            if (owner[(size_t) k] != k) continue;
+            P.pair_of[(size_t) k] = (int64_t) P.xo.size();
+            for (int w = 0; w < 2; w++) {
+                const int64_t j = S->allele_first[s] + S->compare[2 * s + w];
+                P.xo.push_back(S->allele_off[j]);
+                P.xl.push_back(S->allele_len[j]);
+                P.yo.push_back(S->entry_off[k]);
+                P.yl.push_back(S->entry_len[k]);
+                P.mi.push_back(read_forward_strand[S->entry_read[k]] ? 0 : 1);
+                if (S->entry_len[k] > sv_threshold || S->allele_len[j] > sv_threshold) /* bubbleGraph.c:2253-2263 */
+                    kmer_anchors(S->pool + S->allele_off[j], S->allele_len[j], S->pool + S->entry_off[k], S->entry_len[k], P.anchors);
+                P.anchor_off.push_back((int64_t) P.anchors.size() / 2);
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -559,201 +907,21 @@ int mrp_forward_probabilities(mrp_context *ctx, const mrp_pair_hmm *models, int3
     if (n_pairs < 0 || n_models <= 0 || !models || pool_bytes < 0) return fail(MRP_ERR_ARG, "mrp_forward_probabilities: bad sizes");
     if (n_pairs == 0) return MRP_OK;
     if (!x_off || !x_len || !y_off || !y_len || !out || (pool_bytes > 0 && !pool)) return fail(MRP_ERR_ARG, "mrp_forward_probabilities: null argument");
-    if (n_pairs >= (1ll << 31)) return fail(MRP_ERR_ARG, "mrp_forward_probabilities: more than 2^31 pairs in one call");
-    if (expansion < 0 || expansion % 2 != 0) return fail(MRP_ERR_ARG, "mrp_forward_probabilities: diagonalExpansion must be even (pairwiseAligner.c:855)");
-
-    /* classify.  The pair-per-lane kernel takes the unanchored pairs whose x string fits its LDS row next to the tables;
-     * launch classes by x length (4, 3, 2, 1 waves per workgroup = per CU). */
-    const int table_bytes = (16 + n_models * PHM_ETAB) * (int) sizeof(double);
-    /* (-1: the tables of this many models leave no room for a row, every pair goes to the pair-per-wave kernel) */
-    const int lane_max_x = PHM_LDS_BYTES - table_bytes < PHM_LANE_BYTES_PER_X ? -1 : std::min(PHM_LANE_MAX_X, (PHM_LDS_BYTES - table_bytes) / PHM_LANE_BYTES_PER_X);
-    int lane_cap[4];
-    for (int c = 0; c < 4; c++) lane_cap[c] = std::min(lane_max_x, (PHM_LDS_BYTES - table_bytes) / ((4 - c) * PHM_LANE_BYTES_PER_X));
-    constexpr uint32_t WAVE_KEY = 0xFFFFFFFFu;
-    constexpr int LY_CLIP = 4095;
-    HostVec<uint32_t> key((size_t) n_pairs);
-    std::atomic<int64_t> bad{-1}, cells_atomic{0};
-    mrp_parallel_for((n_pairs + 16383) / 16384, 1, [&](int64_t blk) {
-        int64_t c_local = 0;
-        for (int64_t i = blk * 16384; i < std::min(n_pairs, (blk + 1) * 16384); i++) {
-            const int64_t lx = x_len[i], ly = y_len[i];
-            const int mi = model_index ? model_index[i] : 0;
-            const int64_t na = anchor_off ? anchor_off[i + 1] - anchor_off[i] : 0;
-            if (lx < 0 || ly < 0 || x_off[i] < 0 || y_off[i] < 0 || x_off[i] + lx > pool_bytes || y_off[i] + ly > pool_bytes || mi >= n_models || na < 0 ||
-                (na > 0 && !anchors)) {
-                int64_t expect = -1;
-                bad.compare_exchange_strong(expect, i);
-                key[(size_t) i] = WAVE_KEY;
-                continue;
-            }
-            if (na == 0 && lx <= lane_max_x) {
-                key[(size_t) i] = (uint32_t) (std::min<int64_t>(ly, LY_CLIP) << 7 | lx);
-                c_local += (lx + 1) * (ly + 1);
-            } else {
-                key[(size_t) i] = WAVE_KEY;
-            }
-        }
-        cells_atomic += c_local;
-    });
-    if (bad.load() >= 0)
-        return mrp_set_error(MRP_ERR_ARG, "mrp_forward_probabilities: pair %lld lies outside the symbol pool, names a model >= %d or has bad anchor offsets",
-                             (long long) bad.load(), n_models);
-    int64_t cells = cells_atomic.load();
-    /* pairs of similar shape share a wave (counting sort on (y length, x length), longest first so that the tail of a
-     * launch is made of the cheap ones) */
-    HostVec<PhmLanePair> lane_pairs[4];
-    int64_t lane_n[4] = {0, 0, 0, 0};
-    {
-        std::vector<int32_t> hist((size_t) (LY_CLIP + 1) << 7, 0);
-        for (int64_t i = 0; i < n_pairs; i++)
-            if (key[(size_t) i] != WAVE_KEY) hist[key[(size_t) i]]++;
-        int cls_of[128];
-        for (int lx = 0; lx < 128; lx++) {
-            int c = 0;
-            while (c < 3 && lx > lane_cap[c]) c++;
-            cls_of[lx] = c;
-        }
-        for (int64_t b = (int64_t) hist.size() - 1; b >= 0; b--) {
-            const int32_t h = hist[(size_t) b];
-            if (!h) continue;
-            const int c = cls_of[b & 127];
-            hist[(size_t) b] = (int32_t) lane_n[c];
-            lane_n[c] += h;
-        }
-        for (int c = 0; c < 4; c++) lane_pairs[c].resize((size_t) lane_n[c]);
-        for (int64_t i = 0; i < n_pairs; i++) {
-            const uint32_t k = key[(size_t) i];
-            if (k == WAVE_KEY) continue;
-            PhmLanePair &q = lane_pairs[cls_of[k & 127]][(size_t) hist[k]++];
-            q.x_off = x_off[i];
-            q.y_off = y_off[i];
-            q.lx = x_len[i];
-            q.ly = y_len[i];
-            q.model = model_index ? model_index[i] : 0;
-            q.out = (int32_t) i;
-        }
-    }
-    HostVec<PhmPair> wave_pairs[4];
-    HostVec<int32_t> band;
-    std::vector<int32_t> L, R;
-    for (int64_t i = 0; i < n_pairs; i++) {
-        if (key[(size_t) i] != WAVE_KEY) continue;
-        const int64_t lx = x_len[i], ly = y_len[i];
-        const int64_t na = anchor_off ? anchor_off[i + 1] - anchor_off[i] : 0;
-        PhmPair p;
-        p.x_off = x_off[i];
-        p.y_off = y_off[i];
-        p.band_off = -1;
-        p.lx = (int32_t) lx;
-        p.ly = (int32_t) ly;
-        p.model = model_index ? model_index[i] : 0;
-        p.out = (int32_t) i;
-        int width;
-        if (na == 0) {
-            width = (int) std::min(lx, ly) + 1;
-            cells += (lx + 1) * (ly + 1);
-        } else {
-            if (lx + ly >= (1ll << 30)) return fail(MRP_ERR_ARG, "mrp_forward_probabilities: strings too long");
-            L.resize((size_t) (lx + ly + 1));
-            R.resize((size_t) (lx + ly + 1));
-            int64_t c = 0;
-            const int rc = band_closed_form(anchors + 2 * anchor_off[i], na, lx, ly, expansion, L.data(), R.data(), &c, &width);
-            if (rc != MRP_OK) return mrp_set_error(rc, "mrp_forward_probabilities: pair %lld has invalid anchors (pairwiseAligner.c:206-211)", (long long) i);
-            cells += c;
-            p.band_off = (int64_t) band.size() / 2;
-            for (int64_t d = 0; d <= lx + ly; d++) { band.push_back(L[(size_t) d]); band.push_back(R[(size_t) d]); }
-        }
-        if (width > PHM_WAVE_MAX_WIDTH)
-            return mrp_set_error(MRP_ERR_UNSUPPORTED, "mrp_forward_probabilities: pair %lld has a diagonal of %d cells (limit %d)", (long long) i, width, PHM_WAVE_MAX_WIDTH);
-        int c = 0;
-        while (width > WAVE_CLASS_CAP[c]) c++;
-        wave_pairs[c].push_back(p);
-    }
-    for (auto &v : wave_pairs)
-        std::sort(v.begin(), v.end(), [](const PhmPair &a, const PhmPair &b) {
-            const int64_t ca = (int64_t) a.lx * a.ly, cb = (int64_t) b.lx * b.ly;
-            return ca != cb ? ca > cb : a.out < b.out;
-        });
-
-    PHM_HIP(hipSetDevice(ctx->device));
+    PhmLaunch L;
+    const int rc = phm_launch(ctx, "mrp_forward_probabilities", models, n_models, n_pairs, pool, pool_bytes, x_off, x_len, y_off, y_len, model_index,
+                              anchor_off, anchors, expansion, ragged_left, ragged_right, L, stats);
+    if (rc != MRP_OK) return rc;
     hipStream_t s = ctx->stream;
-    std::vector<PhmModelDev> hm((size_t) n_models);
-    bool has_switch = false;
-    for (int i = 0; i < n_models; i++) {
-        model_to_device(models[i], ragged_left, ragged_right, hm[(size_t) i]);
-        if (!(models[i].gap_switch_to_x == -INFINITY && models[i].gap_switch_to_y == -INFINITY)) has_switch = true;
-    }
-    DevBuf<PhmModelDev> d_models;
-    DevBuf<uint8_t> d_pool;
-    DevBuf<int32_t> d_band;
-    DevBuf<double> d_out;
-    DevBuf<PhmLanePair> d_lane[4];
-    DevBuf<PhmPair> d_wave[4];
-    d_models.pool = d_pool.pool = d_band.pool = d_out.pool = &ctx->pool;
-    /* declared after every host vector the queued copies read: an early return drains the stream before they are destroyed */
-    struct Drain { hipStream_t s; ~Drain() { (void) hipStreamSynchronize(s); } } drain{s};
-    PHM_HIP(d_models.upload(hm, s));
-    PHM_HIP(d_pool.alloc((size_t) pool_bytes));
-    if (pool_bytes) PHM_HIP(hipMemcpyAsync(d_pool.p, pool, (size_t) pool_bytes, hipMemcpyHostToDevice, s));
-    PHM_HIP(d_band.upload(band, s));
-    PHM_HIP(d_out.alloc((size_t) n_pairs));
-    for (int c = 0; c < 4; c++) {
-        d_lane[c].pool = d_wave[c].pool = &ctx->pool;
-        PHM_HIP(d_lane[c].upload(lane_pairs[c], s));
-        PHM_HIP(d_wave[c].upload(wave_pairs[c], s));
-    }
-    /* once per device (contexts of several host threads may call concurrently) */
-    static PerDeviceOnce once;
-    const hipError_t configured = once.run([] {
-        hipError_t e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *) phm_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
-        return e;
-    });
-    PHM_HIP(configured);
-    /* kernel_ms must not contain the tail of the uploads (the copy engine finishes them behind the event otherwise) */
-    if (stats) PHM_HIP(hipStreamSynchronize(s));
-    PHM_HIP(hipEventRecord(ctx->ev[0], s));
-    for (int c = 0; c < 4; c++) {
-        const int64_t n = (int64_t) lane_pairs[c].size();
-        if (n == 0) continue;
-        int cap = 1;
-        for (const PhmLanePair &p : lane_pairs[c]) cap = std::max(cap, (int) p.lx);
-        const int row_bytes = cap * PHM_LANE_BYTES_PER_X;
-        const int nw = std::max(1, std::min(4, (PHM_LDS_BYTES - table_bytes) / row_bytes));
-        const size_t lds = (size_t) table_bytes + (size_t) nw * row_bytes;
-        const int64_t per_wg = (int64_t) nw * PHM_WAVE;
-        if (has_switch)
-            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, true>), dim3((unsigned) ((n + per_wg - 1) / per_wg)), dim3((unsigned) per_wg), lds, s, d_lane[c].p, n, d_pool.p,
-                               d_models.p, (int) n_models, cap, d_out.p);
-        else
-            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, false>), dim3((unsigned) ((n + per_wg - 1) / per_wg)), dim3((unsigned) per_wg), lds, s, d_lane[c].p, n, d_pool.p,
-                               d_models.p, (int) n_models, cap, d_out.p);
-        PHM_HIP(hipGetLastError());
-        if (stats) stats->pairs_lane += n;
-    }
-    for (int c = 0; c < 4; c++) {
-        const int64_t n = (int64_t) wave_pairs[c].size();
-        if (n == 0) continue;
-        const int W = WAVE_CLASS_CAP[c];
-        const size_t lds = (size_t) 9 * W * sizeof(double);
-        hipLaunchKernelGGL(phm_wave_kernel, dim3((unsigned) std::min<int64_t>(n, 16384)), dim3(PHM_WAVE), lds, s, d_wave[c].p, n, d_pool.p,
-                           d_models.p, d_band.p, W, d_out.p);
-        PHM_HIP(hipGetLastError());
-        if (stats) stats->pairs_wave += n;
-    }
     PHM_HIP(hipEventRecord(ctx->ev[1], s));
-    PHM_HIP(hipMemcpyAsync(out, d_out.p, (size_t) n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+    PHM_HIP(hipMemcpyAsync(out, L.d_out.p, (size_t) n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
     PHM_HIP(hipStreamSynchronize(s));
     if (stats) {
         float ms = 0.f;
         PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
         stats->kernel_ms = ms;
-        stats->cells = cells;
+        stats->cells = L.cells;
     }
-    d_models.release(); d_pool.release(); d_band.release(); d_out.release();
-    for (auto &b : d_lane) b.release();
-    for (auto &b : d_wave) b.release();
+    L.release();
     ctx->pool.reclaim();
     if (stats) stats->total_ms = now_ms() - t_begin;
     return MRP_OK;
@@ -775,23 +943,8 @@ int mrp_allele_read_supports(mrp_context *ctx, const mrp_pair_hmm *forward_model
     for (int64_t k = 0; k < n_reads_total; k++)
         if (read_len[k] < 0 || read_off[k] < 0 || read_off[k] + read_len[k] > pool_bytes) return fail(MRP_ERR_ARG, "mrp_allele_read_supports: read substring outside the pool");
     /* cachedScores (bubbleGraph.c:1418,1431-1441): the first read of the bubble with a given substring owns the scores */
-    std::vector<int64_t> owner((size_t) n_reads_total);
-    mrp_parallel_for(n_bubbles, 64, [&](int64_t b) {
-        const int64_t r0 = read_first[b], r1 = read_first[b + 1];
-        std::vector<int64_t> order((size_t) (r1 - r0));
-        for (int64_t k = r0; k < r1; k++) order[(size_t) (k - r0)] = k;
-        auto less = [&](int64_t a, int64_t c) {
-            if (read_len[a] != read_len[c]) return read_len[a] < read_len[c];
-            const int cmp = memcmp(pool + read_off[a], pool + read_off[c], (size_t) read_len[a]);
-            return cmp != 0 ? cmp < 0 : a < c;
-        };
-        std::sort(order.begin(), order.end(), less);
-        for (size_t i = 0; i < order.size(); i++) {
-            const int64_t k = order[i];
-            const bool same = i > 0 && read_len[order[i - 1]] == read_len[k] && memcmp(pool + read_off[order[i - 1]], pool + read_off[k], (size_t) read_len[k]) == 0;
-            owner[(size_t) k] = same ? owner[(size_t) order[i - 1]] : k;
-        }
-    });
+    std::vector<int64_t> owner;
+    substring_owners(n_bubbles, read_first, pool, read_off, read_len, nullptr, false, owner);
     const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
     std::vector<int64_t> xo, yo, where, anchor_off, anchors;
     std::vector<int32_t> xl, yl;
@@ -833,6 +986,174 @@ int mrp_allele_read_supports(mrp_context *ctx, const mrp_pair_hmm *forward_model
             for (int64_t j = 0; j < na; j++) support[support_first[(size_t) b] + j * nr + k] = support[support_first[(size_t) b] + j * nr + o];
         }
     }
+    return MRP_OK;
+}
+int mrp_partition_reads_by_haplotype(mrp_context *ctx, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                                     const mrp_haptag_sites *sites, int64_t n_reads, const uint8_t *read_forward_strand, int64_t expansion,
+                                     int32_t *hap, double *h1, double *h2, mrp_pairhmm_stats *stats) {
+    static const char *who = "mrp_partition_reads_by_haplotype";
+    const double t_begin = now_ms();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!ctx) return fail(MRP_ERR_NO_DEVICE, "mrp_partition_reads_by_haplotype: no context (the pair-HMM path has no CPU fallback)");
+    int rc = ht_check_sites(who, sites, n_reads, read_forward_strand);
+    if (rc != MRP_OK) return rc;
+    if (!forward_model || !reverse_model || (n_reads > 0 && (!hap || !h1 || !h2))) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
+    if (n_reads == 0) return MRP_OK;
+    const mrp_haptag_sites &S = *sites;
+    /* heterozygous sites with reads (bubbleGraph.c:1780, :1797-1801) */
+    std::vector<uint8_t> active((size_t) S.n_sites);
+    for (int64_t s = 0; s < S.n_sites; s++) active[(size_t) s] = S.compare[2 * s] != S.compare[2 * s + 1] && S.entry_first[s + 1] > S.entry_first[s];
+    /* b->reads[j] = stList_pop(...) (:1816-1819) reverses the entries, so the cache of :1844-1872 goes to the LAST-listed read
+     * with a given substring, and its strand picks the state machine of every duplicate; never anchored (:1832) */
+    std::vector<int64_t> owner;
+    if (S.n_sites) substring_owners(S.n_sites, S.entry_first, S.pool, S.entry_off, S.entry_len, nullptr, true, owner);
+    HtPairs P;
+    ht_build_pairs(&S, active, owner, read_forward_strand, INT64_MAX, P);
+    const int64_t n_pairs = (int64_t) P.xo.size();
+    if (n_pairs >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
+    /* a read's (site, owner pair) list in site order: counting sort by read, filled in site order */
+    HostVec<int64_t> first((size_t) n_reads + 1, 0);
+    for (int64_t s = 0; s < S.n_sites; s++)
+        if (active[(size_t) s])
+            for (int64_t k = S.entry_first[s]; k < S.entry_first[s + 1]; k++) first[(size_t) S.entry_read[k] + 1]++;
+    for (int64_t r = 0; r < n_reads; r++) first[(size_t) r + 1] += first[(size_t) r];
+    HostVec<HtEntry> ent((size_t) first[(size_t) n_reads]);
+    {
+        std::vector<int64_t> fill(first.begin(), first.end() - 1);
+        for (int64_t s = 0; s < S.n_sites; s++) {
+            if (!active[(size_t) s]) continue;
+            for (int64_t k = S.entry_first[s + 1] - 1; k >= S.entry_first[s]; k--) { /* b->reads order (:1877) */
+                const int64_t p = P.pair_of[(size_t) owner[(size_t) k]];
+                ent[(size_t) fill[(size_t) S.entry_read[k]]++] = HtEntry{(int32_t) p, (int32_t) p + 1, 0, 0};
+            }
+        }
+    }
+    PHM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    DevBuf<int64_t> d_first;
+    DevBuf<HtEntry> d_ent;
+    DevBuf<int32_t> d_hap;
+    DevBuf<double> d_h;
+    d_first.pool = d_ent.pool = d_hap.pool = d_h.pool = &ctx->pool;
+    struct Drain { hipStream_t s; ~Drain() { (void) hipStreamSynchronize(s); } } drain{s};
+    PHM_HIP(d_first.upload(first, s));
+    PHM_HIP(d_ent.upload(ent, s));
+    PHM_HIP(d_hap.alloc((size_t) n_reads));
+    PHM_HIP(d_h.alloc(2 * (size_t) n_reads));
+    const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
+    PhmLaunch L;
+    if (n_pairs > 0) {
+        rc = phm_launch(ctx, who, models, 2, n_pairs, S.pool, S.pool_bytes, P.xo.data(), P.xl.data(), P.yo.data(), P.yl.data(), P.mi.data(), nullptr,
+                        nullptr, expansion, 0, 0, L, stats);
+        if (rc != MRP_OK) return rc;
+    } else {
+        if (stats) PHM_HIP(hipStreamSynchronize(s));
+        PHM_HIP(hipEventRecord(ctx->ev[0], s));
+    }
+    hipLaunchKernelGGL(ht_partition_kernel, dim3((unsigned) ((n_reads + 255) / 256)), dim3(256), 0, s, d_first.p, d_ent.p, L.d_out.p, n_reads, d_hap.p,
+                       d_h.p, d_h.p + n_reads);
+    PHM_HIP(hipGetLastError());
+    PHM_HIP(hipEventRecord(ctx->ev[1], s));
+    PHM_HIP(hipMemcpyAsync(hap, d_hap.p, (size_t) n_reads * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    PHM_HIP(hipMemcpyAsync(h1, d_h.p, (size_t) n_reads * sizeof(double), hipMemcpyDeviceToHost, s));
+    PHM_HIP(hipMemcpyAsync(h2, d_h.p + n_reads, (size_t) n_reads * sizeof(double), hipMemcpyDeviceToHost, s));
+    PHM_HIP(hipStreamSynchronize(s));
+    if (stats) {
+        float ms = 0.f;
+        PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        stats->kernel_ms = ms;
+        stats->cells = L.cells;
+    }
+    L.release();
+    d_first.release(); d_ent.release(); d_hap.release(); d_h.release();
+    ctx->pool.reclaim();
+    if (stats) stats->total_ms = now_ms() - t_begin;
+    return MRP_OK;
+}
+
+int mrp_phase_variants_from_tagged_reads(mrp_context *ctx, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                                         const mrp_haptag_sites *variants, int64_t n_reads, const uint8_t *read_forward_strand,
+                                         const int32_t *read_hap, int64_t expansion, int64_t sv_threshold, int32_t *state, double *cis,
+                                         double *trans, mrp_pairhmm_stats *stats) {
+    static const char *who = "mrp_phase_variants_from_tagged_reads";
+    const double t_begin = now_ms();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!ctx) return fail(MRP_ERR_NO_DEVICE, "mrp_phase_variants_from_tagged_reads: no context (the pair-HMM path has no CPU fallback)");
+    int rc = ht_check_sites(who, variants, n_reads, read_forward_strand);
+    if (rc != MRP_OK) return rc;
+    const int64_t n_var = variants->n_sites;
+    if (!forward_model || !reverse_model || (n_reads > 0 && !read_hap) || (n_var > 0 && (!state || !cis || !trans)))
+        return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
+    if (n_var == 0) return MRP_OK;
+    const mrp_haptag_sites &S = *variants;
+    const int64_t n_entries = S.entry_first[n_var];
+    /* heterozygous variants with reads (bubbleGraph.c:2174, :2186-2192); untagged entries are neither scored nor cached
+     * (:2226-2235), so the FIRST tagged entry with a given substring owns the scores */
+    std::vector<uint8_t> active((size_t) n_var), tagged((size_t) n_entries);
+    for (int64_t v = 0; v < n_var; v++) active[(size_t) v] = S.compare[2 * v] != S.compare[2 * v + 1] && S.entry_first[v + 1] > S.entry_first[v];
+    for (int64_t k = 0; k < n_entries; k++) tagged[(size_t) k] = read_hap[S.entry_read[k]] == 1 || read_hap[S.entry_read[k]] == 2;
+    std::vector<int64_t> owner;
+    substring_owners(n_var, S.entry_first, S.pool, S.entry_off, S.entry_len, tagged.data(), false, owner);
+    HtPairs P;
+    ht_build_pairs(&S, active, owner, read_forward_strand, sv_threshold, P);
+    const int64_t n_pairs = (int64_t) P.xo.size();
+    if (n_pairs >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
+    /* a variant's tagged entries in order */
+    HostVec<int64_t> first((size_t) n_var + 1, 0);
+    HostVec<HtEntry> ent;
+    for (int64_t v = 0; v < n_var; v++) {
+        if (active[(size_t) v])
+            for (int64_t k = S.entry_first[v]; k < S.entry_first[v + 1]; k++) {
+                if (!tagged[(size_t) k]) continue;
+                const int64_t p = P.pair_of[(size_t) owner[(size_t) k]];
+                ent.push_back(HtEntry{(int32_t) p, (int32_t) p + 1, read_hap[S.entry_read[k]] == 1 ? 1 : 0, 0});
+            }
+        first[(size_t) v + 1] = (int64_t) ent.size();
+    }
+    PHM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    DevBuf<int64_t> d_first;
+    DevBuf<uint8_t> d_active;
+    DevBuf<HtEntry> d_ent;
+    DevBuf<int32_t> d_state;
+    DevBuf<double> d_tot;
+    d_first.pool = d_active.pool = d_ent.pool = d_state.pool = d_tot.pool = &ctx->pool;
+    struct Drain { hipStream_t s; ~Drain() { (void) hipStreamSynchronize(s); } } drain{s};
+    PHM_HIP(d_first.upload(first, s));
+    PHM_HIP(d_active.upload(active, s));
+    PHM_HIP(d_ent.upload(ent, s));
+    PHM_HIP(d_state.alloc((size_t) n_var));
+    PHM_HIP(d_tot.alloc(2 * (size_t) n_var));
+    const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
+    PhmLaunch L;
+    if (n_pairs > 0) {
+        rc = phm_launch(ctx, who, models, 2, n_pairs, S.pool, S.pool_bytes, P.xo.data(), P.xl.data(), P.yo.data(), P.yl.data(), P.mi.data(),
+                        P.anchors.empty() ? nullptr : P.anchor_off.data(), P.anchors.empty() ? nullptr : P.anchors.data(), expansion, 0, 0, L, stats);
+        if (rc != MRP_OK) return rc;
+    } else {
+        if (stats) PHM_HIP(hipStreamSynchronize(s));
+        PHM_HIP(hipEventRecord(ctx->ev[0], s));
+    }
+    hipLaunchKernelGGL(ht_phase_kernel, dim3((unsigned) ((n_var + 255) / 256)), dim3(256), 0, s, d_first.p, d_active.p, d_ent.p, L.d_out.p, n_var,
+                       d_state.p, d_tot.p, d_tot.p + n_var);
+    PHM_HIP(hipGetLastError());
+    PHM_HIP(hipEventRecord(ctx->ev[1], s));
+    PHM_HIP(hipMemcpyAsync(state, d_state.p, (size_t) n_var * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    PHM_HIP(hipMemcpyAsync(cis, d_tot.p, (size_t) n_var * sizeof(double), hipMemcpyDeviceToHost, s));
+    PHM_HIP(hipMemcpyAsync(trans, d_tot.p + n_var, (size_t) n_var * sizeof(double), hipMemcpyDeviceToHost, s));
+    PHM_HIP(hipStreamSynchronize(s));
+    if (stats) {
+        float ms = 0.f;
+        PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        stats->kernel_ms = ms;
+        stats->cells = L.cells;
+    }
+    L.release();
+    d_first.release(); d_active.release(); d_ent.release(); d_state.release(); d_tot.release();
+    ctx->pool.reclaim();
+    if (stats) stats->total_ms = now_ms() - t_begin;
     return MRP_OK;
 }
 
