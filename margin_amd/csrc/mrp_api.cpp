@@ -687,8 +687,7 @@ thread_local int t_pool_weight_ns = 0; /* mrp_pool_set_weight: what one index of
  * number before it helps with the others: the loops of a batch's levels run over the same chunks in the same order, so the
  * thread that built a chunk's hmms at one level mostly meets them again at the next (their blocks are in its cache, or its
  * neighbours') instead of wherever a single shared counter sends it. */
-#define MRP_POOL_RANGES 64 /* at most; in use: pool_ranges() */
-static inline int pool_ranges() { const char *e = getenv("MRP_POOL_RANGES"); const int v = e ? atoi(e) : 16; return v < 1 ? 1 : (v > MRP_POOL_RANGES ? MRP_POOL_RANGES : v); } /* development knob */
+#define MRP_POOL_RANGES 16 /* (1, 8 or 32 ranges: the same CPU time per loop family) */
 struct alignas(64) PoolRange { std::atomic<int64_t> next{0}; int64_t end = 0; };
 struct PoolJob {
     void (*fn)(int64_t, void *);
@@ -698,10 +697,9 @@ struct PoolJob {
     PoolRange range[MRP_POOL_RANGES];
     std::atomic<int64_t> done{0};
     std::atomic<int> exhausted{0}; /* ranges that have nothing left to hand out */
-    int n_ranges = 16;
     int active = 0; /* workers currently holding the pointer (under Pool::mu) */
     std::condition_variable cv; /* the posting thread waits here: woken by the last worker to let go of the job, not by every worker of every job */
-    bool has_work() const { return exhausted.load(std::memory_order_relaxed) < n_ranges; }
+    bool has_work() const { return exhausted.load(std::memory_order_relaxed) < MRP_POOL_RANGES; }
 };
 thread_local int t_pool_slot = -1; /* the calling thread's number in its pool: workers 0 .. threads - 2, a posting thread threads - 1 */
 }  // namespace
@@ -728,10 +726,10 @@ struct mrp_host_pool {
             ~Acc() { timespec b; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &b); const long long d = (b.tv_sec - a.tv_sec) * 1000000000ll + (b.tv_nsec - a.tv_nsec);
                      g_pool_task_cpu_ns.fetch_add(d); g_pool_tag_cpu_ns[tag & 15].fetch_add(d); t_pool_task_cpu_ns += d; }
         } acc(j->tag);
-        const int nr = j->n_ranges, home = (t_pool_slot >= 0 ? t_pool_slot : 0) % nr;
+        const int home = (t_pool_slot >= 0 ? t_pool_slot : 0) % MRP_POOL_RANGES;
         int64_t mine = 0; /* booked once: the counter is one cache line shared by every thread of the loop */
-        for (int k = 0; k < nr; k++) {
-            PoolRange &r = j->range[(home + k) % nr];
+        for (int k = 0; k < MRP_POOL_RANGES; k++) {
+            PoolRange &r = j->range[(home + k) % MRP_POOL_RANGES];
             for (;;) {
                 if (r.next.load(std::memory_order_relaxed) >= r.end) break;
                 const int64_t lo = r.next.fetch_add(j->grain);
@@ -809,9 +807,8 @@ extern "C" void mrp_pool_run(int64_t n, int64_t grain, void (*fn)(int64_t, void 
     {   /* ranges of whole grains; the empty ones (a short loop) count as exhausted from the start */
         const int64_t grains = (n + grain - 1) / grain;
         int empty = 0;
-        const int nr = j.n_ranges = pool_ranges();
-        for (int r = 0; r < nr; r++) {
-            const int64_t lo = std::min(n, grains * r / nr * grain), hi = std::min(n, grains * (r + 1) / nr * grain);
+        for (int r = 0; r < MRP_POOL_RANGES; r++) {
+            const int64_t lo = std::min(n, grains * r / MRP_POOL_RANGES * grain), hi = std::min(n, grains * (r + 1) / MRP_POOL_RANGES * grain);
             j.range[r].next.store(lo); j.range[r].end = hi;
             if (lo >= hi) empty++;
         }
@@ -872,7 +869,7 @@ int mrp_context_set_phase_groups(mrp_context *ctx, int groups) {
 }
 int mrp_context_phase_groups(const mrp_context *ctx) { return ctx->phase_groups; }
 int mrp_context_set_test_hooks(mrp_context *ctx, int hooks) {
-    if (!ctx || hooks < 0 || hooks > 15) return fail(MRP_ERR_ARG, "mrp_context_set_test_hooks: bad arguments");
+    if (!ctx || hooks < 0 || hooks > 31) return fail(MRP_ERR_ARG, "mrp_context_set_test_hooks: bad arguments");
     if ((hooks & 4) && ctx->pool.device >= 0) DevPoolRegistry::get().inject_oom[ctx->pool.device].store(1);
     hooks &= ~4;
     ctx->test_hooks = hooks;
@@ -1113,8 +1110,7 @@ int mrp_batch_launch(mrp_batch *b) {
      * 1 152-chunk call: 2 304 on 512 slots), 256 threads -- four to a CU -- get them through sooner: -3 % per call, A/B on one box;
      * a single batch, whose hmms all find a slot, stays at 512 (+4 % with 256). */
     const int64_t chains = 2 * (int64_t) (b->order_wide.size() + b->order_mid.size()) * (int64_t) ctx->concurrent_batches;
-    int t_chain = ctx->concurrent_batches > 1 && chains > 2 * 256 ? 256 : 512; /* (a batch on its own -- the kernel replay of bench.py too: 512, as measured in rounds 1-3) */
-    if (const char *ts = getenv("MRP_SWEEP_T")) { const int v = atoi(ts); if (v == 64 || v == 128 || v == 256 || v == 512) t_chain = v; } /* development */
+    const int t_chain = ctx->concurrent_batches > 1 && chains > 2 * 256 ? 256 : 512; /* (a batch on its own -- the kernel replay of bench.py too: 512, as measured in rounds 1-3) */
     const int t_wide = t_chain, t_mid = t_chain, t_narrow = 64;
     /* workgroup sizes of the recursion kernel's classes (measured; in the
                                                          * concurrent batches of a call 64 to 512 threads for the mid class make no difference) */

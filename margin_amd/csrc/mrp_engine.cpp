@@ -202,9 +202,8 @@ int mrp_engine_create(mrp_context *ctx, const mrp_params *params, mrp_engine **o
     pp.max_p = (int32_t) std::min<int64_t>(params->max_partitions_in_a_column, 1 << 20);
     if (pp.max_p < 0) pp.max_p = 0;
     /* the prune chain on complement pairs (mrp_prune_kernel<..., PAIRS>): every cell has its twin and the limits never cut
-     * a pair.  MRP_PRUNE_PAIRS=0 (development) and test hook bit 3 keep the general chain for A/B parity. */
+     * a pair.  Test hook bit 3 keeps the general chain for A/B parity. */
     pp.pairs = params->include_inverted_partitions && (pp.min_p & 1) == 0 && (pp.max_p & 1) == 0 ? 1 : 0;
-    if (const char *pe = getenv("MRP_PRUNE_PAIRS")) { if (pe[0] == '0') pp.pairs = 0; }
     /* posterior = min(1, exp(s)), s = f + b - total an integer <= 0 (column.c:177-193).  Ranking by the
      * integer is ranking by the double as long as consecutive integers give distinct doubles; from the
      * underflow point of exp down every posterior is 0.0 and they all tie: that is the last bin. */
@@ -466,13 +465,12 @@ static int level_stage(mrp_engine *e, int64_t n, mrp_xhmm *x, bool final_level) 
 
     tm[tmi++] = eng_now();
     /* one array entry per complement pair (MRP_XF_UNITS) where the one-pass cross product + emission kernel writes the level and
-     * the prune reads it by units; MRP_UNITS=0 (development) keeps one entry per cell.  (test hook bit 3: the general prune chain) */
-    L->units = L->fused && e->pp.pairs != 0 && !(ctx->test_hooks & 8) && !(getenv("MRP_UNITS") && getenv("MRP_UNITS")[0] == '0');
+     * the prune reads it by units; test hook bit 4 keeps one entry per cell.  (test hook bit 3: the general prune chain) */
+    L->units = L->fused && e->pp.pairs != 0 && !(ctx->test_hooks & (8 | 16));
     /* hmms whose columns hold at most 64 units and 64 merge units (the static bounds count cells) go through recursion, prune
      * and compaction on ONE wave each (mrp_mini_kernel): the first merge levels, tens of thousands of hmms of a few cells.
-     * They sit at the end of the level's PruneHmm array.  MRP_MINI=0 (development) switches the class off. */
-    const bool mini_on = L->units && !(getenv("MRP_MINI") && getenv("MRP_MINI")[0] == '0');
-    auto is_mini = [&](int64_t i) { return mini_on && x[i].bound_max_cells <= 2 * MRP_MINI_MAX_UNITS && x[i].bound_max_merge <= 2 * MRP_MINI_MAX_UNITS; };
+     * They sit at the end of the level's PruneHmm array; unit levels only. */
+    auto is_mini = [&](int64_t i) { return L->units && x[i].bound_max_cells <= 2 * MRP_MINI_MAX_UNITS && x[i].bound_max_merge <= 2 * MRP_MINI_MAX_UNITS; };
     /* the prune kernel walks one hmm per workgroup, its columns one after the other: longest hmms first */
     L->perm.resize((size_t) n);
     std::vector<int32_t> pos((size_t) n);
@@ -606,7 +604,7 @@ static int level_stage(mrp_engine *e, int64_t n, mrp_xhmm *x, bool final_level) 
     }
     L->frag = false;
     if (final_level && n > 0) { /* genome fragments on the device: every hmm of the stage brings its chunk's reads */
-        bool all = !(getenv("MRP_FRAGMENTS") && getenv("MRP_FRAGMENTS")[0] == '0');
+        bool all = true;
         for (int64_t i = 0; i < n && all; i++) all = x[i].frag_reads && x[i].frag_by_pool && x[i].frag_sites && x[i].frag_reads1 && x[i].frag_reads2 && x[i].frag_n_reads > 0;
         if (all) {
             L->frag_hmms.resize((size_t) n);
@@ -829,17 +827,18 @@ static int level_launch_impl(mrp_engine *e, mrp_engine_level_state *L) {
         ENG_TRY(mrp_launch_layout(L->d_plan.p, L->d_phmm.p, n, total_cols, b->d_chunks.p, e->pp.S,
                                   (e->params.include_inverted_partitions ? MRP_XF_INVERTED : 0u) | (L->units ? MRP_XF_UNITS : 0u), lo, s));
     ENG_TRY(hipMemcpyAsync(L->totals, L->d_totals.p, 48, hipMemcpyDeviceToHost, s));
-    /* Deferred launch (round 5): a small merge level -- its arrays at most MRP_DEFER_MB (1 GB) by the hmms' STATIC bounds, 4 GB of
-     * such levels in flight -- does not wait for its totals: the arrays are sized by the bounds (the layout kernels' offsets stay
-     * inside them: every count is clamped to what the bounds assume), its kernels are queued behind the layout kernels at once and the
-     * level before is ended whenever its event has completed.  A call of one chunk walks eleven levels whose kernels take a
+    /* Deferred launch (round 5): a small merge level -- its arrays at most DEFER_BYTES (1 GB) by the hmms' STATIC bounds, four
+     * times that and at most DEFER_LEVELS levels in flight -- does not wait for its totals: the arrays are sized by the bounds (the
+     * layout kernels' offsets stay inside them: every count is clamped to what the bounds assume), its kernels are queued behind
+     * the layout kernels at once and the level before is ended whenever its event has completed.  A call of one chunk walks eleven levels whose kernels take a
      * millisecond or two each: the wait (totals back, the host awake again, two dozen allocations, a dozen launches) left the device
      * idle for a third of a millisecond per level.  The large levels keep the wait: bounds are loose there (a pruned column of 100
      * cells times another is the bound, a fifth of it the average) and their arrays are what the device's memory goes to. */
-    static const long defer_mb = getenv("MRP_DEFER_MB") ? atol(getenv("MRP_DEFER_MB")) : 1024;
+    static constexpr int64_t DEFER_BYTES = (int64_t) 1024 << 20;
+    static constexpr size_t DEFER_LEVELS = 12;
     const int64_t bound_bytes = 16 * L->bound_cells + 8 * L->bound_merge;
-    const bool defer = L->fused && !L->final_level && defer_mb > 0 && bound_bytes <= ((int64_t) defer_mb << 20) &&
-                       e->inflight_bytes + bound_bytes <= ((int64_t) 4 * defer_mb << 20) && e->inflight.size() < 12;
+    const bool defer = L->fused && !L->final_level && bound_bytes <= DEFER_BYTES &&
+                       e->inflight_bytes + bound_bytes <= 4 * DEFER_BYTES && e->inflight.size() < DEFER_LEVELS;
     int rc;
     int64_t cells, merge, tiles_fast = 0, tiles = 0;
     if (defer) {

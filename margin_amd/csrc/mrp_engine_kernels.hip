@@ -205,9 +205,7 @@ hipError_t mrp_launch_cross(const CrossCol *cols_dev, int64_t n_cols, uint64_t *
  * With inverted partitions cells 2q, 2q+1 are complements and share their cost (hap1 <-> hap2): a lane computes it once.
  * HBM traffic: 8 B written per cell (cost + transitions), nothing read per cell.
  */
-#ifndef XE_WAVES
 #define XE_WAVES 1
-#endif
 /* Table dwords per wave, chosen per launch (dynamic LDS): XE_CAP_NARROW for the levels whose columns all take the table-free path
  * below (200 parent cells x 4 allele slots would still fit: a column that needs the tables after all fills them several times) --
  * 6.4 KB per one-wave workgroup, the registers' 20 waves per CU fit; XE_CAP_WIDE where two pruned columns of 100 cells meet: 8 slots
@@ -215,15 +213,9 @@ hipError_t mrp_launch_cross(const CrossCol *cols_dev, int64_t n_cols, uint64_t *
  * stored), 9.7 KB, 16 waves per CU.  Measured per 96-chunk batch, widest level / the two above it / the three below it:
  * 832 dwords 1.39 / 0.65 + 0.48 / 0.37-0.39 ms; 1 248: 1.24 / 0.64 + 0.49 / 0.39-0.41; 1 664: 1.06 / 0.60 + 0.48 / 0.35-0.44;
  * 2 496: 1.16 / 0.78 + 0.47 / 0.48-0.59; 3 328: 1.26 / 0.84 + 0.58 / 0.54-0.69. */
-#ifndef XE_CAP_NARROW
 #define XE_CAP_NARROW 832
-#endif
-#ifndef XE_CAP_WIDE
 #define XE_CAP_WIDE 1664
-#endif
-#ifndef XE_ROWS
 #define XE_ROWS 16 /* allele slots staged per table fill */
-#endif
 
 typedef unsigned short xe_u16x2 __attribute__((ext_vector_type(2)));
 static __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
@@ -475,18 +467,7 @@ static __device__ __forceinline__ uint32_t xe_narrow_chunk(const uint32_t *__res
 struct __attribute__((packed, aligned(4))) xe_u32x4 { uint32_t x, y, z, w; };
 struct __attribute__((packed, aligned(4))) xe_u32x2 { uint32_t x, y; };
 
-#ifndef XE_MIN_WAVES
 #define XE_MIN_WAVES 1
-#endif
-#ifndef XE_FAST2_ON
-#define XE_FAST2_ON 1 /* (development: 0 keeps the general grid walk for biallelic unit levels) */
-#endif
-#ifndef XE_SLOTS_ON
-#define XE_SLOTS_ON 1 /* (development: 0 keeps a lane per cell for every narrow column) */
-#endif
-#ifndef XE_NARROW_ON
-#define XE_NARROW_ON 1 /* (development: 0 sends every column through the tables) */
-#endif
 /* MODE 1: the narrow columns only (no tables, no LDS, two thirds of the registers: eight waves per SIMD wait for their descriptors and
  * parent cells side by side); MODE 2: the columns that need the tables; a wave that meets a column of the other kind ends behind the
  * column's descriptor.  MODE 0: both kinds in one launch.  The first merge levels, whose hmms are nearly all small, take MODE 1 (and
@@ -534,7 +515,7 @@ __global__ void __launch_bounds__(XE_WAVES * WAVE, MODE == 1 ? 8 : XE_MIN_WAVES)
         const int w4_all = (dc.depth + 15) >> 4;
         const int w4_a = ((int) c.d1 + 15) >> 4, w4_b = (int) c.d1 >> 4;
         /* narrow column: every array entry and every parent cell has a lane of its own */
-        const bool narrow = (C >> ush) <= (uint32_t) WAVE && C1 <= (uint32_t) WAVE && C2 <= (uint32_t) WAVE && XE_NARROW_ON;
+        const bool narrow = (C >> ush) <= (uint32_t) WAVE && C1 <= (uint32_t) WAVE && C2 <= (uint32_t) WAVE;
         if (MODE == 1 ? !narrow : (MODE == 2 && narrow)) continue;
         if (MODE != 2 && narrow) {
             const bool have_a = c.a_part != nullptr, have_b = c.b_part != nullptr;
@@ -571,7 +552,7 @@ __global__ void __launch_bounds__(XE_WAVES * WAVE, MODE == 1 ? 8 : XE_MIN_WAVES)
 #pragma unroll
             for (int w = 0; w < 16; w++) sel[w] = ((uint32_t) ((P >> (4 * w)) & 0xFull) * 0x00204081u) & 0x01010101u;
             uint32_t cost = 0, site0 = 0, sl0 = 0, m1 = 0xFFFFFFFFu, m2 = 0xFFFFFFFFu;
-            if (A_uni == 2u && 2u * U < 2u * (uint32_t) dc.n_sites && XE_SLOTS_ON) { /* few cells, many sites: lanes along the slots */
+            if (A_uni == 2u && 2u * U < 2u * (uint32_t) dc.n_sites) { /* few cells, many sites: lanes along the slots */
                 const uint32_t n_slots = 2u * (uint32_t) dc.n_sites;
                 for (uint32_t s0 = 0; s0 < n_slots; s0 += WAVE) {
                     const uint32_t nsl = min((uint32_t) WAVE, n_slots - s0);
@@ -794,7 +775,7 @@ __global__ void __launch_bounds__(XE_WAVES * WAVE, MODE == 1 ? 8 : XE_MIN_WAVES)
             /* biallelic sites, unit level (the shipped ONT parameters: every level above the first): the cells' loop below takes the
              * slots four at a time without looking at `ends`; the rows' padding up to a multiple of four slots is zeroed (a pad pair
              * then costs 0 + 0) */
-            const bool fast2 = units && a_cells_paired && A_uni == 2u && XE_FAST2_ON;
+            const bool fast2 = units && a_cells_paired && A_uni == 2u;
             if (fast2 && ST > nsl)
                 for (uint32_t i = lane; i < Cs; i += WAVE) {
                     uint32_t *rw = tab + i * ST; /* (side B's rows follow side A's: tb = tab + C1 * ST) */
@@ -967,12 +948,10 @@ hipError_t mrp_launch_cross_emit(const CrossCol *cols_dev, const MrpBatchDev &d,
     int64_t wgs = (d.n_cols + XE_WAVES - 1) / XE_WAVES;
     /* level_max_cells: the level's largest cross product column by the host's static bounds; up to 128 cells (64 array entries of a
      * unit level) every column has a lane per entry */
-    uint32_t cap = level_max_cells > 2 * WAVE && !mostly_narrow ? XE_CAP_WIDE : XE_CAP_NARROW;
-    static const long xe_cap = getenv("MRP_XE_CAP") ? atol(getenv("MRP_XE_CAP")) : 0; /* (development) */
-    if (xe_cap >= 256 && xe_cap <= 8192) cap = (uint32_t) xe_cap & ~3u;
+    const uint32_t cap = level_max_cells > 2 * WAVE && !mostly_narrow ? XE_CAP_WIDE : XE_CAP_NARROW;
     const size_t lds = (size_t) XE_WAVES * (cap + XE_ROWS * 16 + XE_ROWS + 512) * sizeof(uint32_t);
     const dim3 grid((unsigned) (wgs < (1 << 20) ? wgs : (1 << 20)));
-    if (mostly_narrow && XE_NARROW_ON) {
+    if (mostly_narrow) {
         hipLaunchKernelGGL(mrp_cross_emit_kernel<1>, grid, dim3(XE_WAVES * WAVE), 0, stream, cols_dev, d.cols, d.chunks, d.n_cols, d.slot_bytes, d.slot_total,
                            const_cast<uint32_t *>(d.cell_np), d.cell_cost, err, col_hmm_dev, err_hmm, cap);
         /* (a column of at most 64 cells is narrow whatever its parents: they have no more cells than it has) */
@@ -1606,13 +1585,9 @@ __global__ void __launch_bounds__(T, T <= 512 ? 4 : 1) mrp_prune_kernel(PruneIn 
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     /* The four role waves of a workgroup sit on the CU's four SIMDs (wave i on SIMD i mod 4).  Workgroups that share a CU
      * rotate the roles: otherwise every chain wave -- the one wave of a workgroup that is busy all the time -- would issue
-     * from SIMD 0 and the workgroups would take turns on it.  MRP_PRUNE_NO_ROT (development) switches that off. */
+     * from SIMD 0 and the workgroups would take turns on it. */
     const int hw_wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
-#ifdef MRP_PRUNE_NO_ROT
-    const int wave = hw_wave;
-#else
     const int wave = hw_wave < 4 ? ((hw_wave + (int) (blockIdx.x & 3u)) & 3) : hw_wave;
-#endif
     const uint64_t lt_mask = (1ull << lane) - 1ull;
 
     for (int64_t hi_ = blockIdx.x; hi_ < n_hmms; hi_ += gridDim.x) {
@@ -3156,8 +3131,7 @@ hipError_t mrp_launch_prune(const MrpBatchDev &d, const CrossCol *ccols_dev, con
         return e;
     });
     if (configured != hipSuccess) return configured;
-    size_t lds = prune_lds_bytes(p);
-    if (const char *pad = getenv("MRP_PRUNE_LDS_PAD_KB")) lds += (size_t) atol(pad) << 10; /* (development: fewer workgroups per CU) */
+    const size_t lds = prune_lds_bytes(p);
     if (lds > (size_t) MRP_LDS_BUDGET) return hipErrorInvalidValue;
     const dim3 grid((unsigned) (n_hmms < 65536 ? n_hmms : 65536));
     const PruneIn in{d.scols, ccols_dev, d.cell_f32, d.cell_b32, d.merge_f32, d.merge_b32, d.hmm_fb};
@@ -3166,7 +3140,6 @@ hipError_t mrp_launch_prune(const MrpBatchDev &d, const CrossCol *ccols_dev, con
      * 100 x 100 cells of the shipped parameters: half the waves and 77 KB of LDS let two workgroups share a CU where the
      * 1 024-thread variant (two groups of 6 waves x 36 cells, up to 13 824 cells) fills it alone.
      * p.pairs (includeInvertedPartitions and even column limits): the chain runs on complement pairs. */
-    const char *force = getenv("MRP_PRUNE_VARIANT"); /* development: "big" sends mid-sized columns to the 1 024-thread variant */
     const bool pairs = p.pairs != 0;
 #define PRUNE_LAUNCH(T_, CPT_, NGRP_, VEC_)                                                                                               \
     do {                                                                                                                                  \
@@ -3176,12 +3149,13 @@ hipError_t mrp_launch_prune(const MrpBatchDev &d, const CrossCol *ccols_dev, con
     /* what the bin-streaming waves hold per column: cells, or units when the level's arrays hold units (p.pairs == 2) */
     const int held = p.pairs == 2 ? (p.max_cells + 1) / 2 : p.max_cells;
     /* columns of at most 256 entries (the first merge levels: a few reads per hmm): four waves, the table wave writes the bins */
-    if (held <= 4 * WAVE && !(force && force[0] == 's')) PRUNE_LAUNCH(256, 4, 1, 1);
+    if (held <= 4 * WAVE) PRUNE_LAUNCH(256, 4, 1, 1);
     else if (held <= 2 * WAVE * 32) PRUNE_LAUNCH(512, 32, 2, 1);
     /* up to 5 120 entries -- the unit levels of the shipped parameters (100 x 100 cells = 5 000 units): the same four streaming waves as
-     * two groups that alternate over the columns, so that a column's f and b have TWO column times to arrive (MRP_PRUNE_VARIANT=1: one group) */
-    else if (held <= 2 * WAVE * 10 * 4 && !(force && (force[0] == 'b' || force[0] == '1'))) PRUNE_LAUNCH(512, 10, 2, 4);
-    else if (held <= MRP_PRUNE_MID_CELLS && !(force && force[0] == 'b')) PRUNE_LAUNCH(512, 10, 1, 4);
+     * two groups that alternate over the columns, so that a column's f and b have TWO column times to arrive (one group: 1 ms per
+     * step slower) */
+    else if (held <= 2 * WAVE * 10 * 4) PRUNE_LAUNCH(512, 10, 2, 4);
+    else if (held <= MRP_PRUNE_MID_CELLS) PRUNE_LAUNCH(512, 10, 1, 4);
     else PRUNE_LAUNCH(1024, 36, 2, 1);
 #undef PRUNE_LAUNCH
     {
@@ -3919,9 +3893,7 @@ hipError_t mrp_launch_traceback(const MrpBatchDev &d, const PruneHmm *hmms_dev, 
 hipError_t mrp_launch_compact(const MrpBatchDev &d, const CrossCol *ccols_dev, const PruneHmm *hmms_dev, const int32_t *col_hmm_dev, int64_t n_cols,
                               int64_t n_hmms_here, PruneParams p, PruneScratch s, hipStream_t stream) {
     if (n_cols <= 0 || n_hmms_here <= 0) return hipSuccess;
-    int64_t wgs = (n_cols + 3) / 4;
-    static const long cg = getenv("MRP_COMPACT_GRID") ? atol(getenv("MRP_COMPACT_GRID")) : 0; /* (development) */
-    if (cg > 0 && wgs > cg) wgs = cg;
+    const int64_t wgs = (n_cols + 3) / 4;
     hipLaunchKernelGGL(mrp_compact_kernel, dim3((unsigned) (wgs < 65536 ? wgs : 65536)), dim3(256), 0, stream, d, ccols_dev, hmms_dev,
                        col_hmm_dev, n_cols, (int32_t) n_hmms_here, p, s);
     return hipGetLastError();

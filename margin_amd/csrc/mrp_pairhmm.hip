@@ -43,9 +43,7 @@ namespace {
 constexpr int PHM_WAVE = 64;
 constexpr int PHM_LANE_MAX_X = 100;    /* 100 * 1 600 B = 156 KB of the 160 KB, the rest holds the tables */
 constexpr int PHM_LDS_BYTES = 160 * 1024;
-#ifndef PHM_ROWS
 #define PHM_ROWS 2 /* rows a lane of the pair-per-lane kernel advances together (measured: 1 -> 2.49 ms, 2 -> 2.11, 3 -> 2.75, 4 -> 2.61, 6 -> 3.23 for 4.8e5 pairs) */
-#endif
 constexpr int PHM_LANE_BYTES_PER_X = 3 * 64 * 8 + 64; /* LDS per wave and x position: three states per lane + the lane's symbol */
 constexpr int PHM_ETAB = 25 * 6;       /* doubles per model in the emission + transition table */
 constexpr int PHM_WAVE_MAX_WIDTH = 2048; /* 3 diagonals * 2 048 cells * 3 states * 8 B = 144 KB */
@@ -97,29 +95,12 @@ __device__ const float PHM_COEF[16] = {-0.009350833524763f, 0.130659527668286f, 
                                        -0.014532321752540f, 0.139942324101744f, 0.495635523139337f, 0.692140569840976f,
                                        -0.004605031767994f, 0.063427417320019f, 0.695956496475118f, 0.514272634594009f,
                                        -0.000458661602210f, 0.009695946122598f, 0.930734667215156f, 0.168037164329057f};
-/* -DPHM_COEF_SELECT: the coefficients are float literals, select the float's bits (3 v_cndmask each) and widen */
+/* (selecting the float literals' bits, 3 v_cndmask per coefficient, and widening them was 5 % slower: DESIGN.md §9) */
 static __device__ __forceinline__ double phm_lookup_t(double x, const double *coef) {
-#ifdef PHM_COEF_SELECT
-    const bool a = x <= 1.0, b = x <= 2.5, c = x <= 4.5;
-    auto sel = [&](float f0, float f1, float f2, float f3) {
-        uint32_t v = c ? __float_as_uint(f2) : __float_as_uint(f3);
-        v = b ? __float_as_uint(f1) : v;
-        v = a ? __float_as_uint(f0) : v;
-        double d;
-        asm("v_cvt_f64_f32 %0, %1" : "=v"(d) : "v"(v));
-        return d;
-    };
-    const double c3 = sel(-0.009350833524763f, -0.014532321752540f, -0.004605031767994f, -0.000458661602210f);
-    const double c2 = sel(0.130659527668286f, 0.139942324101744f, 0.063427417320019f, 0.009695946122598f);
-    const double c1 = sel(0.498799810682272f, 0.495635523139337f, 0.695956496475118f, 0.930734667215156f);
-    const double c0 = sel(0.693203116424741f, 0.692140569840976f, 0.514272634594009f, 0.168037164329057f);
-    return ((c3 * x + c2) * x + c1) * x + c0;
-#else
     const int idx = (x > 1.0 ? 1 : 0) + (x > 2.5 ? 1 : 0) + (x > 4.5 ? 1 : 0);
     const double2 a = *reinterpret_cast<const double2 *>(coef + idx * 4);
     const double2 b = *reinterpret_cast<const double2 *>(coef + idx * 4 + 2);
     return ((a.x * x + a.y) * x + b.x) * x + b.y;
-#endif
 }
 /* Branch-free on purpose: the interpolation is evaluated for every lane and thrown away where logAdd returns the larger
  * operand (d = inf or NaN then selects a valid table row and produces a value nobody reads).  With the conditional

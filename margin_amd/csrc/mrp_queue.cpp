@@ -59,9 +59,7 @@ QueuePlan plan_queue(int64_t n, const int64_t *cost, int64_t chunks_per_batch, i
      * BASELINE.json configs[1] (60 000 units) as the yardstick the policy was measured on: what a call costs the device and
      * what it keeps there grow with its units, not with its chunks -- 192 chunks of 130 sites would be a call of 9 ms. */
     const int64_t unit_chunk = MRP_QUEUE_UNITS_PER_CHUNK;
-    int64_t short_chunks = MRP_QUEUE_SHORT_CHUNKS;
-    if (const char *ev = getenv("MRP_QUEUE_SHORT_CHUNKS")) { const long v = atol(ev); if (v > 0) short_chunks = v; } /* (development) */
-    const int64_t big = MRP_QUEUE_DEFAULT_BATCH * unit_chunk, short_queue = short_chunks * unit_chunk;
+    const int64_t big = MRP_QUEUE_DEFAULT_BATCH * unit_chunk, short_queue = MRP_QUEUE_SHORT_CHUNKS * unit_chunk;
     auto units = [&](int64_t pos) { return std::max<int64_t>(1, cost[p.order[(size_t) pos]]); };
     int64_t total = 0;
     for (int64_t i = 0; i < n; i++) total += units(i);

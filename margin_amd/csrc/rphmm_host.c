@@ -2393,12 +2393,7 @@ static void *phase_group_main(void *p) {
     const double cpu0 = thread_cpu_ms();
     const long long pool0 = mrp_pool_task_cpu_ns(), mine0 = mrp_pool_task_cpu_ns_this_thread();
     mrp_pool_adopt(g->pool);
-    {   /* batch 0's host loops first: the batches reach their device-heavy levels one after the other.  MRP_POOL_PRIORITY (development):
-         * 0 = no priorities (the oldest loop first), k > 1 = batches in groups of k share a priority */
-        const char *pe = getenv("MRP_POOL_PRIORITY");
-        const int pk = pe ? atoi(pe) : 1;
-        mrp_pool_set_priority(pk <= 0 ? 0 : g->index / pk);
-    }
+    mrp_pool_set_priority(g->index); /* batch 0's host loops first: the batches reach their device-heavy levels one after the other */
     g->rc = phase_many_resident(g->ctx, g->n, g->chunks, g->reads, g->n_reads, g->params, g->out, &g->stats);
     mrp_pool_set_priority(0);
     if (getenv("MRP_TIMING")) {

@@ -618,30 +618,23 @@ def test_bench_shape_configs4_full_size_hifi_chunk_equals_the_oracle(gpu_ctx, or
     dchunk.close()
 
 
-@pytest.mark.parametrize("hooks,env", [(8, {}), (0, {"MRP_UNITS": "0"})], ids=["general_prune_chain", "pairs_chain_on_cell_arrays"])
-def test_prune_variants_agree_with_the_default_path_and_the_oracle(orc, hooks, env):
+@pytest.mark.parametrize("hooks", [8, 16], ids=["general_prune_chain", "pairs_chain_on_cell_arrays"])
+def test_prune_variants_agree_with_the_default_path_and_the_oracle(orc, hooks):
     """The default resident path runs the prune chain on complement pairs over arrays that hold one entry per pair (MRP_XF_UNITS).
     Two variants stay in the product (odd column limits / plain mode take the first, the two-kernel cross product + emission
     path the second): the general chain with one entry per cell (test hook bit 3) and the pair chain over per-cell arrays
-    (MRP_UNITS=0, read at every level).  Both give the default path's results, which are the oracle's."""
+    (test hook bit 4).  Both give the default path's results, which are the oracle's."""
     pd = _params()
     params = capi.Params.from_reference_names(pd)
     chunks = [synth.make_ont_chunk(seed=820 + s, region_bp=120_000 + 40_000 * s, n_sites=240 + 80 * s, coverage=28.0 + 4 * s) for s in range(3)]
-    old = {k: os.environ.get(k) for k in env}
     with capi.Context(0) as ctx:
         dch = [capi.DeviceChunk.from_chunk(ctx, c) for c in chunks]
         ref, st0 = capi.phase_reads_many(ctx, dch, chunks, params)
         try:
-            os.environ.update(env)
             ctx.set_test_hooks(hooks)
             got, st = capi.phase_reads_many(ctx, dch, chunks, params)
         finally:
             ctx.set_test_hooks(0)
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
         assert st.resident == 1 and st.fallback_chunks == 0 and st.cells == st0.cells and st.merge_cells == st0.merge_cells
         for a, b in zip(ref, got):
             for k in PHASE_KEYS:
