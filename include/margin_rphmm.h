@@ -55,7 +55,7 @@ const char *mrp_version(void);
  * mrp_queue_dry_run and mrp_phase_many_stats without one).  A caller built against another header finds out by comparing
  * mrp_abi_version() with the MRP_ABI_VERSION it was compiled with, before it passes a structure in
  * (integration/stRPHmm_forwardBackward_adaptor.c does so when it makes its first context). */
-#define MRP_ABI_VERSION 5
+#define MRP_ABI_VERSION 6
 int mrp_abi_version(void);
 /* Number of visible HIP devices (0 if none / runtime unavailable). */
 int mrp_device_count(void);
@@ -547,6 +547,60 @@ int mrp_phase_variants_from_tagged_reads(mrp_context *ctx, const mrp_pair_hmm *f
                                          const mrp_haptag_sites *variants, int64_t n_reads, const uint8_t *read_forward_strand,
                                          const int32_t *read_hap, int64_t expansion, int64_t sv_threshold, int32_t *state,
                                          double *cis, double *trans, mrp_pairhmm_stats *stats);
+
+/* ---- from read and allele strings to haplotypes and HP tags in one call ---------------------------------------------
+ * The front of margin phase's chunk loop (phase.c:395-401) for n_chunks chunks: the four calls mrp_allele_read_supports ->
+ * mrp_profile_seqs_from_bubbles + mrp_reference_from_bubbles -> mrp_chunk_create + mrp_phase_reads_many ->
+ * mrp_assign_reads_to_haplotypes, with the supports and the profile bytes kept on the device.  One chunk, as the strings
+ * margin phase aligns (bubbleGraph.c:1338-1464): bubble b has alleles [allele_first[b], allele_first[b+1]) (at least one) and
+ * read substrings [sub_first[b], sub_first[b+1]); sub_read names each substring's read (a read at most once per bubble).
+ * Offsets of every chunk start at 0 and ascend; symbols as mrp_symbols_from_chars gives them. */
+typedef struct mrp_string_chunk {
+    int64_t n_bubbles, n_reads;
+    const uint8_t *pool; int64_t pool_bytes;   /* symbols of the alleles and substrings */
+    const int64_t *allele_first;               /* n_bubbles + 1 */
+    const int64_t *allele_off; const int32_t *allele_len;
+    const int64_t *sub_first;                  /* n_bubbles + 1 */
+    const int64_t *sub_off; const int32_t *sub_len;
+    const int32_t *sub_read;                   /* per substring: its read, in [0, n_reads) */
+    const char *const *read_names;             /* n_reads: readId, the hmm tie-break (hmm.c:82-87) */
+    const uint8_t *read_forward_strand;        /* n_reads: nonzero = forward (picks the pair-HMM and mrp_read.forward_strand) */
+} mrp_string_chunk;
+
+/* What the chain's second step returns for one chunk, malloc'd (every array mrp_free): the profile sequences
+ * (mrp_profile_seqs_from_bubbles: seqs, read_of_seq, n_seqs, pool, pool_bytes; seqs[i].name points into the caller's
+ * read_names) and the site tables (mrp_reference_from_bubbles, n_bubbles entries). */
+typedef struct mrp_profile_out {
+    mrp_read *seqs;
+    int32_t *read_of_seq;
+    int64_t n_seqs;
+    uint8_t *pool;
+    int64_t pool_bytes;
+    uint32_t *allele_number;
+    uint16_t *substitution;
+    uint16_t *prior;
+} mrp_profile_out;
+
+typedef struct mrp_string_chunks_stats {
+    mrp_pairhmm_stats pairhmm;   /* the one pair-HMM launch of the call (total_ms: 0) */
+    mrp_phase_many_stats phase;  /* the phasing (mrp_phase_reads_many) */
+    double profile_ms;           /* profile-byte kernel, HIP events */
+    double assign_ms;            /* HP kernel, HIP events */
+    double host_ms;              /* host wall time outside the phasing: checks, owners, pairs, layout, waits */
+    double total_ms;             /* host wall time of the call */
+} mrp_string_chunks_stats;
+
+/* Returns exactly what the four-call chain returns for the same inputs: out[c] as mrp_phase_reads_many gives it, except
+ * that reads1 / reads2 name the CALLER's reads (through read_of_seq); hap_out[c][r] (n_reads entries per chunk) = 1 / 2,
+ * 0 below min_phred, -1 for a read not in the fragment or in no bubble; phred_out (optional) the score of
+ * genomeFragment.c:260, 0 for -1 reads; profiles_out (optional) as above.  A pair whose diagonal exceeds 2 048 cells gives
+ * MRP_ERR_UNSUPPORTED before anything is launched; parameters outside the resident range take mrp_phase_reads_many's
+ * per-chunk path (stats->phase.resident = 0).  Arguments are checked before the context: MRP_ERR_ARG, then
+ * MRP_ERR_NO_DEVICE for a NULL context.  On an error nothing is returned in out / profiles_out. */
+int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model,
+                            const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
+                            const mrp_params *params, int64_t min_phred, mrp_phase_result **out, int8_t *const *hap_out,
+                            double *const *phred_out, mrp_profile_out *profiles_out, mrp_string_chunks_stats *stats);
 
 #ifdef __cplusplus
 }

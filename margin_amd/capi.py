@@ -21,7 +21,7 @@ FLAG_MAX_NOT_SUM = 1
 FLAG_INCLUDE_ANCESTOR_SUB_PROB = 2
 
 #: every symbol include/margin_rphmm.h declares (checked by the CPU test-suite)
-ABI_VERSION = 5  # MRP_ABI_VERSION of include/margin_rphmm.h as transcribed here
+ABI_VERSION = 6  # MRP_ABI_VERSION of include/margin_rphmm.h as transcribed here
 
 EXPORTED_SYMBOLS = [
     "mrp_last_error", "mrp_version", "mrp_abi_version", "mrp_runtime_init", "mrp_device_count", "mrp_context_create", "mrp_context_destroy",
@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = [
     "mrp_stitch_chunk", "mrp_stitch_size", "mrp_stitch_lookup", "mrp_phase_sets", "mrp_binomial_p_value", "mrp_binomial_coefficient",
     "mrp_symbols_from_chars", "mrp_pair_hmm_reverse_complement", "mrp_band_diagonals", "mrp_forward_probabilities",
     "mrp_allele_read_supports", "mrp_kmer_alignment_anchors", "mrp_phase_chunks_on_devices", "mrp_queue_plan", "mrp_queue_dry_run", "mrp_queue_create", "mrp_queue_destroy",
-    "mrp_queue_phase_chunks", "mrp_partition_reads_by_haplotype", "mrp_phase_variants_from_tagged_reads",
+    "mrp_queue_phase_chunks", "mrp_partition_reads_by_haplotype", "mrp_phase_variants_from_tagged_reads", "mrp_phase_string_chunks",
 ]
 
 
@@ -208,6 +208,22 @@ class HaptagSites(C.Structure):
 VARIANT_NOT_VISITED, VARIANT_CIS, VARIANT_TRANS, VARIANT_TIE = 0, 1, 2, 3
 
 
+class StringChunk(C.Structure):
+    _fields_ = [("n_bubbles", C.c_int64), ("n_reads", C.c_int64), ("pool", C.c_void_p), ("pool_bytes", C.c_int64), ("allele_first", C.c_void_p),
+                ("allele_off", C.c_void_p), ("allele_len", C.c_void_p), ("sub_first", C.c_void_p), ("sub_off", C.c_void_p), ("sub_len", C.c_void_p),
+                ("sub_read", C.c_void_p), ("read_names", C.c_void_p), ("read_forward_strand", C.c_void_p)]
+
+
+class ProfileOut(C.Structure):
+    _fields_ = [("seqs", C.POINTER(ReadRec)), ("read_of_seq", C.c_void_p), ("n_seqs", C.c_int64), ("pool", C.c_void_p), ("pool_bytes", C.c_int64),
+                ("allele_number", C.c_void_p), ("substitution", C.c_void_p), ("prior", C.c_void_p)]
+
+
+class StringChunksStats(C.Structure):
+    _fields_ = [("pairhmm", PairHmmStats), ("phase", PhaseManyStats), ("profile_ms", C.c_double), ("assign_ms", C.c_double),
+                ("host_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 def load():
     """dlopen the in-tree library; raises if it has not been built (no fallback)."""
     global _lib
@@ -288,6 +304,8 @@ def load():
     L.mrp_allele_read_supports.argtypes = [vp, P(PairHmm), P(PairHmm), i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, P(PairHmmStats)]
     L.mrp_partition_reads_by_haplotype.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, i64, vp, vp, vp, P(PairHmmStats)]
     L.mrp_phase_variants_from_tagged_reads.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, vp, i64, i64, vp, vp, vp, P(PairHmmStats)]
+    L.mrp_phase_string_chunks.argtypes = [vp, i64, P(StringChunk), P(PairHmm), P(PairHmm), i64, i64, C.c_double, P(Params), i64, P(P(PhaseResult)),
+                                          P(vp), P(vp), P(ProfileOut), P(StringChunksStats)]
     L.mrp_kmer_alignment_anchors.argtypes = [vp, i64, vp, i64, vp]
     L.mrp_kmer_alignment_anchors.restype = i64
     L.mrp_phase_chunks_on_devices.argtypes = [vp, i32, i64, P(ChunkDesc), P(Params), i64, P(P(PhaseResult)), P(QueueStats)]
@@ -1008,3 +1026,165 @@ def phase_variants_from_tagged_reads(ctx: Context, forward_model: PairHmm, rever
     _check(load().mrp_phase_variants_from_tagged_reads(ctx.h, C.byref(forward_model), C.byref(reverse_model), C.byref(S), int(n_reads), ptr(sd),
                                                        ptr(rh), int(expansion), int(sv_threshold), ptr(state), ptr(cis), ptr(trans), C.byref(st)))
     return state, cis, trans, st
+
+
+# ---- from read and allele strings to haplotypes and HP tags (mrp_phase_string_chunks) ----
+
+def string_chunk_struct(chunk):
+    """mrp_string_chunk for a margin_amd.synth.StringChunk; returns (StringChunk, the arrays it points into)"""
+    strings, a_first, a_off, a_len, s_first, s_off, s_len, s_read, pos = [], [0], [], [], [0], [], [], [], 0
+    for alleles, reads, subs in chunk.bubbles:
+        for a in alleles:
+            a = np.ascontiguousarray(a, dtype=np.uint8)
+            strings.append(a); a_off.append(pos); a_len.append(len(a)); pos += len(a)
+        for r, sub in zip(reads, subs):
+            sub = np.ascontiguousarray(sub, dtype=np.uint8)
+            strings.append(sub); s_off.append(pos); s_len.append(len(sub)); s_read.append(int(r)); pos += len(sub)
+        a_first.append(len(a_off))
+        s_first.append(len(s_off))
+    names = [n.encode() for n in chunk.read_names]
+    keep = dict(pool=np.concatenate(strings) if pos else np.zeros(0, np.uint8), allele_first=np.array(a_first, np.int64), allele_off=np.array(a_off, np.int64),
+                allele_len=np.array(a_len, np.int32), sub_first=np.array(s_first, np.int64), sub_off=np.array(s_off, np.int64), sub_len=np.array(s_len, np.int32),
+                sub_read=np.array(s_read, np.int32), strand=np.ascontiguousarray(chunk.read_forward_strand, dtype=np.uint8),
+                names=(C.c_char_p * max(len(names), 1))(*names), name_bytes=names)
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data
+    S = StringChunk(len(chunk.bubbles), len(chunk.read_names), ptr(keep["pool"]), keep["pool"].size, keep["allele_first"].ctypes.data, ptr(keep["allele_off"]),
+                    ptr(keep["allele_len"]), keep["sub_first"].ctypes.data, ptr(keep["sub_off"]), ptr(keep["sub_len"]), ptr(keep["sub_read"]),
+                    C.cast(keep["names"], C.c_void_p) if names else None, ptr(keep["strand"]))
+    return S, keep
+
+
+def _profile_dict(P) -> dict:
+    n = int(P.n_seqs)
+    seqs = [dict(name=P.seqs[i].name.decode(), ref_start=int(P.seqs[i].ref_start), length=int(P.seqs[i].length),
+                 forward_strand=int(P.seqs[i].forward_strand), pool_offset=int(P.seqs[i].pool_offset)) for i in range(n)]
+    return dict(seqs=seqs, read_of_seq=_as_np(P.read_of_seq, n, np.int32), pool=_as_np(P.pool, int(P.pool_bytes), np.uint8))
+
+
+def phase_string_chunks(ctx: Context, chunks, forward_model: PairHmm, reverse_model: PairHmm, params: Params, min_phred: int = 0,
+                        expansion: int = 4, sv_threshold: int = 512, het_substitution_probability: float = 0.0, profiles: bool = False,
+                        structs=None):
+    """mrp_phase_string_chunks -> (list per chunk of dict(result, hap, phred[, profile]), StringChunksStats).  result is the
+    phase result dict with reads1 / reads2 naming the chunk's reads; profile (profiles=True) holds the profile sequences, pool
+    and site tables; structs = [string_chunk_struct(c) for c in chunks] to reuse them (timing loops)."""
+    L = load()
+    n = len(chunks)
+    built = structs if structs is not None else [string_chunk_struct(c) for c in chunks]
+    arr = (StringChunk * max(n, 1))(*[b[0] for b in built])
+    haps = [np.zeros(len(c.read_names), dtype=np.int8) for c in chunks]
+    phreds = [np.zeros(len(c.read_names), dtype=np.float64) for c in chunks]
+    hp = (C.c_void_p * max(n, 1))(*[h.ctypes.data for h in haps])
+    pp = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in phreds])
+    res = (C.POINTER(PhaseResult) * max(n, 1))()
+    prof = (ProfileOut * max(n, 1))() if profiles else None
+    st = StringChunksStats()
+    _check(L.mrp_phase_string_chunks(ctx.h, n, arr, C.byref(forward_model), C.byref(reverse_model), int(expansion), int(sv_threshold),
+                                     float(het_substitution_probability), C.byref(params), int(min_phred), res, hp, pp, prof, C.byref(st)))
+    out = []
+    for i in range(n):
+        d = dict(result=_phase_result_dict(res[i].contents), hap=haps[i], phred=phreds[i])
+        L.mrp_phase_result_destroy(res[i])
+        if profiles:
+            P = prof[i]
+            d["profile"] = _profile_dict(P)
+            nb = len(chunks[i].bubbles)
+            an = _as_np(P.allele_number, nb, np.uint32)
+            A = an.astype(np.int64)
+            d["profile"].update(allele_number=an, sub=_as_np(P.substitution, int((A * A).sum()), np.uint16), prior=_as_np(P.prior, int(A.sum()), np.uint16))
+            for f in ("seqs", "read_of_seq", "pool", "allele_number", "substitution", "prior"):
+                L.mrp_free(C.cast(getattr(P, f), C.c_void_p))
+        out.append(d)
+    return out, st
+
+
+def phase_string_chunks_chain(ctx: Context, chunks, forward_model: PairHmm, reverse_model: PairHmm, params: Params, min_phred: int = 0,
+                              expansion: int = 4, sv_threshold: int = 512, het_substitution_probability: float = 0.0, timing: Optional[dict] = None,
+                              profiles: bool = True):
+    """The same through the four calls an integrator chains by hand (examples/phase_from_strings.c): mrp_allele_read_supports
+    per chunk -> mrp_profile_seqs_from_bubbles + mrp_reference_from_bubbles -> mrp_chunk_create + mrp_phase_reads_many ->
+    mrp_assign_reads_to_haplotypes, read indices translated through read_of_seq.  Same return shape as phase_string_chunks
+    (profile included unless profiles=False).  timing (optional dict) receives the wall ms of the four steps."""
+    import time
+    L = load()
+    t = [time.perf_counter()]
+    prepared = []
+    for c in chunks:
+        S, keep = string_chunk_struct(c)
+        nb = len(c.bubbles)
+        sup_sizes = [len(a) * len(r) for a, r, _ in c.bubbles]
+        sup = np.zeros(max(sum(sup_sizes), 1), dtype=np.float32)
+        ptr = lambda a: None if a.size == 0 else a.ctypes.data
+        strand_of_sub = keep["strand"][keep["sub_read"]] if keep["sub_read"].size else np.zeros(0, np.uint8)
+        strand_of_sub = np.ascontiguousarray(strand_of_sub, dtype=np.uint8)
+        if nb:
+            _check(L.mrp_allele_read_supports(ctx.h, C.byref(forward_model), C.byref(reverse_model), nb, keep["allele_first"].ctypes.data,
+                                              keep["sub_first"].ctypes.data, ptr(keep["pool"]), keep["pool"].size, ptr(keep["allele_off"]), ptr(keep["allele_len"]),
+                                              ptr(keep["sub_off"]), ptr(keep["sub_len"]), ptr(strand_of_sub), int(expansion), int(sv_threshold), sup.ctypes.data, None))
+        prepared.append((S, keep, sup))
+    t.append(time.perf_counter())
+    built = []
+    for c, (S, keep, sup) in zip(chunks, prepared):
+        nb = len(c.bubbles)
+        an = np.diff(keep["allele_first"]).astype(np.uint32)
+        nr = np.diff(keep["sub_first"])
+        sup_off = np.zeros(nb + 1, dtype=np.int64)
+        np.cumsum(an.astype(np.int64) * nr, out=sup_off[1:])
+        b = Bubbles(nb, an.ctypes.data if nb else None, keep["sub_first"].ctypes.data, keep["sub_read"].ctypes.data if keep["sub_read"].size else None,
+                    sup_off.ctypes.data, sup.ctypes.data)
+        fs = keep["strand"].astype(np.int32)
+        seqs = C.POINTER(ReadRec)()
+        read_of, pool = C.c_void_p(), C.c_void_p()
+        n_seqs, pool_bytes = C.c_int64(0), C.c_int64(0)
+        _check(L.mrp_profile_seqs_from_bubbles(C.byref(b), len(c.read_names), C.cast(keep["names"], C.c_void_p), fs.ctypes.data if fs.size else None,
+                                               C.byref(seqs), C.byref(read_of), C.byref(n_seqs), C.byref(pool), C.byref(pool_bytes)))
+        pa, ps, pp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(L.mrp_reference_from_bubbles(C.byref(b), float(het_substitution_probability), C.byref(pa), C.byref(ps), C.byref(pp)))
+        built.append(dict(seqs=seqs, read_of=read_of, n_seqs=n_seqs.value, pool=pool, pool_bytes=pool_bytes.value, an=pa, sub=ps, prior=pp, nb=nb))
+    t.append(time.perf_counter())
+    handles = []
+    for d in built:
+        h = C.c_void_p()
+        _check(L.mrp_chunk_create(ctx.h, d["nb"], d["an"], d["sub"], d["prior"], d["pool"] if d["pool_bytes"] else None, d["pool_bytes"], C.byref(h)))
+        handles.append(h)
+    n = len(chunks)
+    ch = (C.c_void_p * max(n, 1))(*[h.value for h in handles])
+    rd = (C.POINTER(ReadRec) * max(n, 1))(*[d["seqs"] for d in built])
+    nr = (C.c_int64 * max(n, 1))(*[d["n_seqs"] for d in built])
+    res = (C.POINTER(PhaseResult) * max(n, 1))()
+    st = PhaseManyStats()
+    _check(L.mrp_phase_reads_many(ctx.h, n, ch, rd, nr, C.byref(params), res, C.byref(st)))
+    t.append(time.perf_counter())
+    out = []
+    for i, (c, d) in enumerate(zip(chunks, built)):
+        n_reads = len(c.read_names)
+        hap_s = np.zeros(max(d["n_seqs"], 1), dtype=np.int8)
+        phred_s = np.zeros(max(d["n_seqs"], 1), dtype=np.float64)
+        _check(L.mrp_assign_reads_to_haplotypes(d["nb"], d["an"], d["pool"], d["seqs"], d["n_seqs"], res[i], int(min_phred), hap_s.ctypes.data, phred_s.ctypes.data))
+        ro = _as_np(d["read_of"], d["n_seqs"], np.int32)
+        hap = np.full(n_reads, -1, dtype=np.int8)
+        phred = np.zeros(n_reads, dtype=np.float64)
+        hap[ro] = hap_s[:d["n_seqs"]]
+        phred[ro] = phred_s[:d["n_seqs"]]
+        r = _phase_result_dict(res[i].contents)
+        r["reads1"] = [int(ro[q]) for q in r["reads1"]]
+        r["reads2"] = [int(ro[q]) for q in r["reads2"]]
+        L.mrp_phase_result_destroy(res[i])
+        if not profiles:
+            out.append(dict(result=r, hap=hap, phred=phred))
+            continue
+        A = _as_np(d["an"], d["nb"], np.uint32)
+        A64 = A.astype(np.int64)
+        prof = dict(seqs=[dict(name=d["seqs"][q].name.decode(), ref_start=int(d["seqs"][q].ref_start), length=int(d["seqs"][q].length),
+                               forward_strand=int(d["seqs"][q].forward_strand), pool_offset=int(d["seqs"][q].pool_offset)) for q in range(d["n_seqs"])],
+                    read_of_seq=ro, pool=_as_np(d["pool"], d["pool_bytes"], np.uint8), allele_number=A,
+                    sub=_as_np(d["sub"], int((A64 * A64).sum()), np.uint16), prior=_as_np(d["prior"], int(A64.sum()), np.uint16))
+        out.append(dict(result=r, hap=hap, phred=phred, profile=prof))
+    t.append(time.perf_counter())
+    for h in handles:
+        L.mrp_chunk_destroy(h)
+    for d in built:
+        for f in ("seqs", "read_of", "pool", "an", "sub", "prior"):
+            L.mrp_free(C.cast(d[f], C.c_void_p))
+    if timing is not None:
+        timing.update(supports_ms=1e3 * (t[1] - t[0]), profile_ms=1e3 * (t[2] - t[1]), phase_ms=1e3 * (t[3] - t[2]), assign_ms=1e3 * (t[4] - t[3]))
+    return out, st

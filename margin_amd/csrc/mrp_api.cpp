@@ -47,6 +47,7 @@ int fail(int code, const char *fmt, ...) {
 extern "C" {
 
 void mrp_chunk_host_view(const mrp_chunk *chunk, mrp_chunk_host *out) {
+    if (chunk->pool_host_pending.load() && hipEventSynchronize(chunk->pool_host_ready) == hipSuccess) chunk->pool_host_pending.store(false);
     out->n_sites = chunk->n_sites;
     out->allele_number = chunk->allele_number.data();
     out->allele_offset = chunk->allele_offset.data();
@@ -293,7 +294,8 @@ int mrp_chunk_create(mrp_context *ctx, int64_t n_sites, const uint32_t *allele_n
  * one event ends it.  Nothing is waited for here: the first device work that reads a chunk waits for the event on its stream
  * (mrp_engine.cpp) or on the host (mrp_chunk::host_wait).  Per chunk this replaces seven allocations and seven pageable
  * copies (30 ms for 288 chunks) by a share of one. */
-int mrp_chunk_block_create(mrp_context *ctx, int64_t n, const mrp_chunk_desc *const *descs, mrp_chunk **out, mrp_chunk_block *blk, int groups) {
+int mrp_chunk_block_create(mrp_context *ctx, int64_t n, const mrp_chunk_desc *const *descs, mrp_chunk **out, mrp_chunk_block *blk, int groups,
+                           const uint8_t *const *device_pools) {
     if (!ctx || n < 0 || !blk || (n > 0 && (!descs || !out))) return fail(MRP_ERR_ARG, "mrp_chunk_block_create: bad arguments");
     for (int64_t i = 0; i < n; i++) out[i] = nullptr;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -328,7 +330,7 @@ int mrp_chunk_block_create(mrp_context *ctx, int64_t n, const mrp_chunk_desc *co
         const mrp_chunk *ch = out[order[(size_t) k]];
         at_of[(size_t) order[(size_t) k]] = off[(size_t) k];
         off[(size_t) k + 1] = off[(size_t) k] + al(4 * ch->allele_number.size()) + al(4 * ch->allele_offset.size()) + al(4 * ch->sub_offset.size()) +
-                              al(4 * ch->same_until.size()) + al(2 * ch->sub.size()) + al(2 * ch->prior.size()) + al((size_t) ch->pool_bytes);
+                              al(4 * ch->same_until.size()) + al(2 * ch->sub.size()) + al(2 * ch->prior.size()) + (device_pools ? 0 : al((size_t) ch->pool_bytes));
     }
     hipError_t e = hipSuccess;
     if (rc == MRP_OK) {
@@ -358,8 +360,13 @@ int mrp_chunk_block_create(mrp_context *ctx, int64_t n, const mrp_chunk_desc *co
                 ch->dev.same_until = (const int32_t *) put(ch->same_until.data(), 4 * ch->same_until.size());
                 ch->dev.sub = (const uint16_t *) put(ch->sub.data(), 2 * ch->sub.size());
                 ch->dev.prior = (const uint16_t *) put(ch->prior.data(), 2 * ch->prior.size());
-                ch->pool_host = (const uint8_t *) (hb + o);
-                ch->dev.pool = (const uint8_t *) put(descs[i]->profile_pool, (size_t) ch->pool_bytes);
+                if (device_pools) {
+                    ch->pool_host = descs[i]->profile_pool;
+                    ch->dev.pool = device_pools[i];
+                } else {
+                    ch->pool_host = (const uint8_t *) (hb + o);
+                    ch->dev.pool = (const uint8_t *) put(descs[i]->profile_pool, (size_t) ch->pool_bytes);
+                }
             });
             const size_t lo = off[(size_t) group_first[(size_t) g]], hi = off[(size_t) group_first[(size_t) g + 1]];
             if (hi > lo) e = hipMemcpyAsync(db + lo, hb + lo, hi - lo, hipMemcpyHostToDevice, ctx->stream);

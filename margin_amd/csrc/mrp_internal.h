@@ -380,6 +380,10 @@ struct mrp_chunk {
     mutable hipEvent_t ready = nullptr;
     bool owns_ready = true; /* false: the event belongs to the block the chunk was uploaded with (mrp_chunk_block) */
     mutable std::atomic<bool> ready_pending{false};
+    /* a chunk whose profile bytes were written on the device (mrp_phase_string_chunks): pool_host is filled by a download still in
+     * flight, which this event (not owned) ends; mrp_chunk_host_view waits for it before the host code reads a byte */
+    hipEvent_t pool_host_ready = nullptr;
+    mutable std::atomic<bool> pool_host_pending{false};
     hipError_t host_wait() const {
         if (!ready_pending.load()) return hipSuccess;
         const hipError_t e = hipEventSynchronize(ready);
@@ -515,7 +519,10 @@ void mrp_engine_release_context_cache(mrp_context *ctx);
 /* groups > 1: chunk i belongs to group i % groups (the concurrent batches mrp_phase_reads_many will deal the chunks to); the block is
  * laid out and uploaded group by group, and a chunk is ready when its group's copy has ended -- the first batch's kernels need not wait
  * for the last batch's bytes */
-int mrp_chunk_block_create(mrp_context *ctx, int64_t n, const mrp_chunk_desc *const *descs, mrp_chunk **out, mrp_chunk_block *blk, int groups = 1);
+/* device_pools (optional): the profile bytes of chunk i are already on the device at device_pools[i] (with the tail slack
+ * mrp_chunk_create gives a pool) and descs[i]->profile_pool is the caller's host copy of them; only the site tables are staged */
+int mrp_chunk_block_create(mrp_context *ctx, int64_t n, const mrp_chunk_desc *const *descs, mrp_chunk **out, mrp_chunk_block *blk, int groups = 1,
+                           const uint8_t *const *device_pools = nullptr);
 int mrp_host_threads_setting(void); /* what mrp_set_host_threads() was given, 0 if it was never called */
 /* host worker pools (mrp_api.cpp) */
 extern "C" void mrp_batch_last_launch_ms(struct mrp_batch *b, float *pack, float *emission, float *recursion);

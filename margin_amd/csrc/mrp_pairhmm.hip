@@ -28,6 +28,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <string_view>
 #include <unordered_map>
 #include <vector>
@@ -836,6 +837,186 @@ void ht_build_pairs(const mrp_haptag_sites *S, const std::vector<uint8_t> &activ
     }
 }
 
+
+/* ---- mrp_phase_string_chunks: profile bytes and HP tags on the device ------------------------------------------------------
+ *
+ * Exactness of the profile bytes.  The byte of bubbleGraph.c:2429-2435 (rphmm_frame.c mrp_profile_seqs_from_bubbles) is
+ * min(255, (int64) roundf((float) (30 (total - lp)))) with lp the float support and total = logAddExact over the alleles in
+ * allele order.  Everything but total is exact IEEE arithmetic on both sides (the narrowing to float, the fp64 subtraction and
+ * product -- not contracted in this file --, the conversion to float, roundf, and the x86 conversion restated below).  total
+ * takes one exp and one log per allele after the first: the device's (ocml) and glibc's double exp / log are both faithfully
+ * rounded, so total can differ from the host's in its last bit, 2^-52 relative: about 1e-14 absolute for the values here (|total|
+ * below 10^3).  That moves 30 (total - lp) by less than 1e-12, and the byte changes only if the fp64 value lies that close to a
+ * point where its float rounding crosses a half integer; float spacing below 256 is at least 2^-16, so the chance is below
+ * 1e-7 per byte, and the supports are the same floats on both sides.  The tests compare every byte of the chain's pool. */
+static __device__ __forceinline__ int64_t sc_f32_to_i64_x86(float v) { /* (int64_t) of a float as x86-64 converts it (cvttss2si) */
+    if (!(v >= -9223372036854775808.0f && v < 9223372036854775808.0f)) return INT64_MIN;
+    return (int64_t) v;
+}
+
+struct ScByteItem { /* one (bubble, read substring): where its bytes go in the device pool, the first pair of its owner */
+    int64_t dst;
+    int32_t pair;      /* the owner's pair with allele 0 of the bubble; alleles follow */
+    int32_t n_alleles;
+};
+
+/* bubbleGraph.c:2421-2435 over the supports of bubbleGraph.c:1421-1464: a lane per (bubble, substring) */
+__global__ void __launch_bounds__(256) sc_profile_bytes_kernel(const ScByteItem *__restrict__ items, int64_t n_items, const double *__restrict__ lp,
+                                                               uint8_t *__restrict__ pool) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const ScByteItem it = items[i];
+    const double *p = lp + it.pair;
+    double total = -__builtin_inf();
+    for (int32_t k = 0; k < it.n_alleles; k++) total = ht_log_add_exact(total, (double) (float) p[k]); /* the float store of :1464 */
+    uint8_t *dst = pool + it.dst;
+    for (int32_t k = 0; k < it.n_alleles; k++) {
+        const float f = (float) p[k];
+        const int64_t l = sc_f32_to_i64_x86(roundf((float) (30.0 * (total - (double) f))));
+        dst[k] = (uint8_t) (l > 255 ? 255 : l);
+    }
+}
+
+struct ScHapItem { /* one profile sequence of one chunk */
+    int64_t pool;   /* its bytes in the device pool */
+    int64_t aoff;   /* its chunk's allele offsets (n_sites + 1) in the offsets table */
+    int64_t hap;    /* its chunk's haplotype strings: hap1 then hap2, frag_length each */
+    int32_t ref_start, length, frag_start, frag_length;
+    int32_t side;   /* 1 / 2: in reads1 / only in reads2 of the fragment, 0: in neither */
+    int32_t pad;
+};
+
+/* stGenomeFragment_phaseBamChunkReads (genomeFragment.c:234-276) with getLogProbOfReadGivenHaplotype (:71-89) and
+ * getLogProbabilityOfBeingInPartition (:91-100), as mrp_assign_reads_to_haplotypes states them: a lane per sequence.  The
+ * sums of bytes are integers, exact in fp64 in any order; one exp and one log follow (relative error ~1e-16). */
+__global__ void __launch_bounds__(256) sc_assign_kernel(const ScHapItem *__restrict__ items, int64_t n_items, const int64_t *__restrict__ aoff,
+                                                        const uint64_t *__restrict__ haps, const uint8_t *__restrict__ pool, int64_t min_phred,
+                                                        int8_t *__restrict__ hap_out, double *__restrict__ phred_out) {
+    const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_items) return;
+    const ScHapItem it = items[i];
+    if (it.side == 0) { hap_out[i] = -1; phred_out[i] = 0.0; return; }
+    /* :255-259: the first haplotype handed over for a hap1 read is haplotypeString2, i.e. the OTHER one */
+    const uint64_t *mine = haps + it.hap + (it.side == 1 ? 0 : it.frag_length), *other = haps + it.hap + (it.side == 1 ? it.frag_length : 0);
+    const int64_t *ao = aoff + it.aoff + it.ref_start;
+    const uint8_t *bytes = pool + it.pool;
+    int32_t lo = it.frag_start - it.ref_start, hi = it.frag_start + it.frag_length - it.ref_start;
+    if (lo < 0) lo = 0;
+    if (hi > it.length) hi = it.length;
+    double ta = 0.0, tb = 0.0;
+    for (int32_t s = lo; s < hi; s++) {
+        const int64_t o = ao[s] - ao[0], A = ao[s + 1] - ao[s];
+        const int64_t j = (int64_t) s + it.ref_start - it.frag_start;
+        const uint64_t ho = other[j], hm = mine[j];
+        if (ho < (uint64_t) A) ta -= bytes[o + (int64_t) ho]; /* (a haplotype allele is always one of the site's) */
+        if (hm < (uint64_t) A) tb -= bytes[o + (int64_t) hm];
+    }
+    const double a = ta / 30.0, b = tb / 30.0;
+    const double lp = a - ht_log_add_exact(a, b);
+    const double phred = -10 * lp / 2.302585; /* :260 */
+    hap_out[i] = phred < (double) min_phred ? 0 : (int8_t) it.side;
+    phred_out[i] = phred;
+}
+
+/* what the host works out for one chunk beside the pair-HMM kernels: bubbleGraph_getProfileSeqs' layout (bubbleGraph.c:2356-2381)
+ * and bubbleGraph_getReference's tables (:2443-2474), as rphmm_frame.c computes them */
+struct ScLayout {
+    std::vector<mrp_read> seqs;
+    std::vector<int32_t> read_of_seq, seq_of;
+    std::vector<int64_t> aoff; /* n_bubbles + 1 */
+    int64_t pool_bytes = 0;
+    std::vector<uint32_t> an;
+    std::vector<uint16_t> sub, prior;
+};
+
+/* (uint16_t) of a float as gcc/x86-64 converts it (rphmm_frame.c) */
+uint16_t sc_f32_to_u16_x86(float v) {
+    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return 0;
+    return (uint16_t) (uint32_t) (int32_t) v;
+}
+
+/* MRP_ERR_ARG for a malformed chunk; seen: scratch of n_reads entries */
+int sc_check_chunk(int64_t c, const mrp_string_chunk &S, std::vector<int64_t> &seen) {
+    static const char *who = "mrp_phase_string_chunks";
+    if (S.n_bubbles < 0 || S.n_reads < 0 || S.pool_bytes < 0 || S.n_reads >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: bad sizes", who, (long long) c);
+    if (S.n_reads > 0 && (!S.read_names || !S.read_forward_strand)) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null argument", who, (long long) c);
+    for (int64_t r = 0; r < S.n_reads; r++)
+        if (!S.read_names[r]) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: read %lld has no name", who, (long long) c, (long long) r);
+    if (S.n_bubbles == 0) return MRP_OK;
+    if (!S.allele_first || !S.sub_first || (S.pool_bytes > 0 && !S.pool)) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null argument", who, (long long) c);
+    if (S.allele_first[0] != 0 || S.sub_first[0] != 0) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: offsets must start at 0", who, (long long) c);
+    for (int64_t b = 0; b < S.n_bubbles; b++) {
+        const int64_t na = S.allele_first[b + 1] - S.allele_first[b], ns = S.sub_first[b + 1] - S.sub_first[b];
+        if (na < 1 || na > 65535 || ns < 0)
+            return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: offsets not ascending or no allele at bubble %lld", who, (long long) c, (long long) b);
+    }
+    const int64_t n_alleles = S.allele_first[S.n_bubbles], n_subs = S.sub_first[S.n_bubbles];
+    if (!S.allele_off || !S.allele_len || (n_subs > 0 && (!S.sub_off || !S.sub_len || !S.sub_read)))
+        return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null argument", who, (long long) c);
+    for (int64_t j = 0; j < n_alleles; j++)
+        if (S.allele_len[j] < 0 || S.allele_off[j] < 0 || S.allele_off[j] + S.allele_len[j] > S.pool_bytes)
+            return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: allele %lld lies outside the pool", who, (long long) c, (long long) j);
+    seen.assign((size_t) S.n_reads, -1);
+    for (int64_t b = 0; b < S.n_bubbles; b++)
+        for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1]; k++) {
+            if (S.sub_len[k] < 0 || S.sub_off[k] < 0 || S.sub_off[k] + S.sub_len[k] > S.pool_bytes)
+                return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: read substring %lld lies outside the pool", who, (long long) c, (long long) k);
+            const int32_t r = S.sub_read[k];
+            if (r < 0 || r >= S.n_reads)
+                return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: substring %lld names read %d of %lld", who, (long long) c, (long long) k, r, (long long) S.n_reads);
+            if (seen[(size_t) r] == b) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: read %d appears twice in bubble %lld", who, (long long) c, r, (long long) b);
+            seen[(size_t) r] = b;
+        }
+    return MRP_OK;
+}
+
+void sc_layout(const mrp_string_chunk &S, double het_substitution_probability, ScLayout &Lc) {
+    const int64_t nb = S.n_bubbles, n_reads = S.n_reads;
+    std::vector<int64_t> first((size_t) n_reads, -1), last((size_t) n_reads, -1);
+    Lc.seq_of.assign((size_t) n_reads, -1);
+    Lc.read_of_seq.clear();
+    for (int64_t b = 0; b < nb; b++)
+        for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1]; k++) {
+            const int32_t r = S.sub_read[k];
+            if (first[(size_t) r] < 0) { first[(size_t) r] = b; Lc.seq_of[(size_t) r] = (int32_t) Lc.read_of_seq.size(); Lc.read_of_seq.push_back(r); }
+            last[(size_t) r] = b;
+        }
+    Lc.aoff.assign((size_t) nb + 1, 0);
+    Lc.an.resize((size_t) nb);
+    int64_t n_sub = 0;
+    for (int64_t b = 0; b < nb; b++) {
+        const int64_t A = S.allele_first[b + 1] - S.allele_first[b];
+        Lc.an[(size_t) b] = (uint32_t) A;
+        Lc.aoff[(size_t) b + 1] = Lc.aoff[(size_t) b] + A;
+        n_sub += A * A;
+    }
+    const int64_t n_seqs = (int64_t) Lc.read_of_seq.size();
+    Lc.seqs.assign((size_t) n_seqs, mrp_read{});
+    int64_t pool_bytes = 0;
+    for (int64_t q = 0; q < n_seqs; q++) { /* stProfileSeq_constructEmptyProfile profileSeq.c:13-29 */
+        const int32_t r = Lc.read_of_seq[(size_t) q];
+        mrp_read &m = Lc.seqs[(size_t) q];
+        m.name = S.read_names[r];
+        m.ref_start = (int32_t) first[(size_t) r];
+        m.length = (int32_t) (last[(size_t) r] - first[(size_t) r] + 1);
+        m.forward_strand = S.read_forward_strand[r] ? 1 : 0;
+        m.pool_offset = pool_bytes;
+        pool_bytes += Lc.aoff[(size_t) last[(size_t) r] + 1] - Lc.aoff[(size_t) first[(size_t) r]];
+    }
+    Lc.pool_bytes = pool_bytes;
+    /* bubbleGraph.c:2458-2467 */
+    const uint16_t off = sc_f32_to_u16_x86(roundf((float) (-log(het_substitution_probability) * 30.0)));
+    Lc.sub.assign((size_t) n_sub, 0);
+    Lc.prior.assign((size_t) Lc.aoff[(size_t) nb], 0);
+    int64_t o = 0;
+    for (int64_t b = 0; b < nb; b++) {
+        const int64_t A = Lc.an[(size_t) b];
+        for (int64_t j = 0; j < A; j++)
+            for (int64_t k = 0; k < A; k++) Lc.sub[(size_t) (o + j * A + k)] = j == k ? 0 : off;
+        o += A * A;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1135,6 +1316,329 @@ int mrp_phase_variants_from_tagged_reads(mrp_context *ctx, const mrp_pair_hmm *f
     d_first.release(); d_active.release(); d_ent.release(); d_state.release(); d_tot.release();
     ctx->pool.reclaim();
     if (stats) stats->total_ms = now_ms() - t_begin;
+    return MRP_OK;
+}
+
+
+int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model,
+                            const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
+                            const mrp_params *params, int64_t min_phred, mrp_phase_result **out, int8_t *const *hap_out,
+                            double *const *phred_out, mrp_profile_out *profiles_out, mrp_string_chunks_stats *stats) {
+    static const char *who = "mrp_phase_string_chunks";
+    const double t_begin = now_ms();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    /* ---- checks (host only, before the context: a malformed call is refused the same with or without a device) */
+    if (n_chunks < 0 || (n_chunks > 0 && (!chunks || !out || !hap_out)) || !forward_model || !reverse_model || !params)
+        return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
+    if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
+    for (int64_t c = 0; c < n_chunks; c++)
+        if (chunks[c].n_reads > 0 && (!hap_out[c] || (phred_out && !phred_out[c]))) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null output", who, (long long) c);
+    {
+        std::vector<int> rcs((size_t) n_chunks, MRP_OK);
+        std::vector<std::string> msgs((size_t) n_chunks);
+        mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
+            std::vector<int64_t> seen;
+            rcs[(size_t) c] = sc_check_chunk(c, chunks[c], seen);
+            if (rcs[(size_t) c] != MRP_OK) msgs[(size_t) c] = mrp_last_error();
+        });
+        for (int64_t c = 0; c < n_chunks; c++)
+            if (rcs[(size_t) c] != MRP_OK) return mrp_set_error(rcs[(size_t) c], "%s", msgs[(size_t) c].c_str());
+    }
+    if (!ctx) return fail(MRP_ERR_NO_DEVICE, "mrp_phase_string_chunks: no context (the pair-HMM path has no CPU fallback)");
+    for (int64_t c = 0; c < n_chunks; c++) out[c] = nullptr;
+    if (profiles_out) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
+    if (n_chunks == 0) return MRP_OK;
+
+    /* ---- the pairs of every chunk, one symbol pool: bubble b of chunk c is global bubble bubble_base[c] + b */
+    std::vector<int64_t> pool_base((size_t) n_chunks + 1, 0), bubble_base((size_t) n_chunks + 1, 0), sub_base((size_t) n_chunks + 1, 0);
+    for (int64_t c = 0; c < n_chunks; c++) {
+        pool_base[(size_t) c + 1] = pool_base[(size_t) c] + chunks[c].pool_bytes;
+        bubble_base[(size_t) c + 1] = bubble_base[(size_t) c] + chunks[c].n_bubbles;
+        sub_base[(size_t) c + 1] = sub_base[(size_t) c] + (chunks[c].n_bubbles ? chunks[c].sub_first[chunks[c].n_bubbles] : 0);
+    }
+    const int64_t n_bub = bubble_base[(size_t) n_chunks], n_subs = sub_base[(size_t) n_chunks];
+    HostVec<uint8_t> gpool((size_t) pool_base[(size_t) n_chunks]);
+    std::vector<int64_t> g_sub_first((size_t) n_bub + 1, 0), g_sub_off((size_t) n_subs);
+    std::vector<int32_t> g_sub_len((size_t) n_subs);
+    mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
+        const mrp_string_chunk &S = chunks[c];
+        if (S.pool_bytes) memcpy(gpool.data() + pool_base[(size_t) c], S.pool, (size_t) S.pool_bytes);
+        for (int64_t b = 0; b < S.n_bubbles; b++) g_sub_first[(size_t) (bubble_base[(size_t) c] + b + 1)] = sub_base[(size_t) c] + S.sub_first[b + 1];
+        const int64_t ns = sub_base[(size_t) c + 1] - sub_base[(size_t) c];
+        for (int64_t k = 0; k < ns; k++) {
+            g_sub_off[(size_t) (sub_base[(size_t) c] + k)] = pool_base[(size_t) c] + S.sub_off[k];
+            g_sub_len[(size_t) (sub_base[(size_t) c] + k)] = S.sub_len[k];
+        }
+    });
+    /* cachedScores (bubbleGraph.c:1418,1431-1441): the first substring of the bubble with given symbols owns the scores */
+    std::vector<int64_t> owner;
+    substring_owners(n_bub, g_sub_first.data(), gpool.data(), g_sub_off.data(), g_sub_len.data(), nullptr, false, owner);
+    /* the owners' pairs, chunk by chunk in parallel: pair_first[k] = the pair of owner k with the bubble's allele 0 */
+    std::vector<int64_t> pair_base((size_t) n_chunks + 1, 0), pair_first((size_t) n_subs, -1);
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const mrp_string_chunk &S = chunks[c];
+        int64_t np = 0;
+        for (int64_t b = 0; b < S.n_bubbles; b++)
+            for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1]; k++)
+                if (owner[(size_t) (sub_base[(size_t) c] + k)] == sub_base[(size_t) c] + k) np += S.allele_first[b + 1] - S.allele_first[b];
+        pair_base[(size_t) c + 1] = pair_base[(size_t) c] + np;
+    }
+    const int64_t n_pairs = pair_base[(size_t) n_chunks];
+    if (n_pairs >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
+    std::vector<int64_t> xo((size_t) n_pairs), yo((size_t) n_pairs), anchor_off((size_t) n_pairs + 1, 0);
+    std::vector<int32_t> xl((size_t) n_pairs), yl((size_t) n_pairs);
+    std::vector<uint8_t> mi((size_t) n_pairs);
+    std::vector<std::vector<int64_t>> chunk_anchors((size_t) n_chunks);
+    mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
+        const mrp_string_chunk &S = chunks[c];
+        const int64_t pb = pool_base[(size_t) c], sb = sub_base[(size_t) c];
+        int64_t p = pair_base[(size_t) c];
+        std::vector<int64_t> &anc = chunk_anchors[(size_t) c];
+        for (int64_t b = 0; b < S.n_bubbles; b++)
+            for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1]; k++) {
+                if (owner[(size_t) (sb + k)] != sb + k) continue;
+                pair_first[(size_t) (sb + k)] = p;
+                for (int64_t j = S.allele_first[b]; j < S.allele_first[b + 1]; j++, p++) {
+                    xo[(size_t) p] = pb + S.allele_off[j];
+                    xl[(size_t) p] = S.allele_len[j];
+                    yo[(size_t) p] = pb + S.sub_off[k];
+                    yl[(size_t) p] = S.sub_len[k];
+                    mi[(size_t) p] = S.read_forward_strand[S.sub_read[k]] ? 0 : 1;
+                    const size_t before = anc.size();
+                    if (S.sub_len[k] > sv_threshold || S.allele_len[j] > sv_threshold) /* bubbleGraph.c:1448-1451 */
+                        kmer_anchors(S.pool + S.allele_off[j], S.allele_len[j], S.pool + S.sub_off[k], S.sub_len[k], anc);
+                    anchor_off[(size_t) p + 1] = (int64_t) (anc.size() - before) / 2; /* a count for now */
+                }
+            }
+    });
+    std::vector<int64_t> anchors;
+    for (int64_t p = 0; p < n_pairs; p++) anchor_off[(size_t) p + 1] += anchor_off[(size_t) p];
+    for (auto &v : chunk_anchors) anchors.insert(anchors.end(), v.begin(), v.end());
+    for (int64_t k = 0; k < n_subs; k++) /* duplicates read their owner's pairs */
+        if (owner[(size_t) k] != k) pair_first[(size_t) k] = pair_first[(size_t) owner[(size_t) k]];
+
+    PHM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
+    /* device buffers first: they are released after the stream has drained (Drain below runs before their destructors) */
+    DevBuf<ScByteItem> d_items;
+    DevBuf<uint8_t> d_pool;
+    DevBuf<int64_t> d_aoff;
+    DevBuf<uint64_t> d_haps;
+    DevBuf<ScHapItem> d_hitems;
+    DevBuf<int8_t> d_hap;
+    DevBuf<double> d_phred;
+    d_items.pool = d_pool.pool = d_aoff.pool = d_haps.pool = d_hitems.pool = d_hap.pool = d_phred.pool = &ctx->pool;
+    PinnedBuf h_pool, h_res;
+    struct Events {
+        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Events() { for (hipEvent_t x : e) if (x) (void) hipEventDestroy(x); }
+    } ev;
+    mrp_chunk_block blk;
+    std::vector<mrp_chunk *> dch((size_t) n_chunks, nullptr);
+    std::vector<mrp_phase_result *> res((size_t) n_chunks, nullptr);
+    struct Cleanup {
+        hipStream_t s;
+        std::vector<mrp_chunk *> &dch;
+        std::vector<mrp_phase_result *> &res;
+        ~Cleanup() {
+            (void) hipStreamSynchronize(s);
+            for (mrp_chunk *ch : dch) delete ch;
+            for (mrp_phase_result *r : res) mrp_phase_result_destroy(r);
+        }
+    } cleanup{s, dch, res};
+    for (hipEvent_t &x : ev.e) PHM_HIP(hipEventCreate(&x));
+    PhmLaunch L;
+    if (n_pairs > 0) {
+        const int rc = phm_launch(ctx, who, models, 2, n_pairs, gpool.data(), (int64_t) gpool.size(), xo.data(), xl.data(), yo.data(), yl.data(), mi.data(),
+                                  anchors.empty() ? nullptr : anchor_off.data(), anchors.empty() ? nullptr : anchors.data(), expansion, 0, 0, L,
+                                  stats ? &stats->pairhmm : nullptr);
+        if (rc != MRP_OK) return rc;
+    } else {
+        PHM_HIP(hipEventRecord(ctx->ev[0], s));
+    }
+    PHM_HIP(hipEventRecord(ev.e[0], s)); /* end of the pair-HMM kernels */
+
+    /* ---- beside the kernels: the layout of every chunk (the index arrays only) */
+    std::vector<ScLayout> lay((size_t) n_chunks);
+    mrp_parallel_for(n_chunks, 1, [&](int64_t c) { sc_layout(chunks[c], het_substitution_probability, lay[(size_t) c]); });
+    /* every chunk's pool in one device buffer, with mrp_chunk_create's tail slack (mrp_pack_kernel reads a read's last bytes a
+     * dword at a time) and 256-byte alignment */
+    std::vector<int64_t> dpool_base((size_t) n_chunks + 1, 0), aoff_base((size_t) n_chunks + 1, 0), seq_base((size_t) n_chunks + 1, 0);
+    for (int64_t c = 0; c < n_chunks; c++) {
+        dpool_base[(size_t) c + 1] = (dpool_base[(size_t) c] + lay[(size_t) c].pool_bytes + 16 + 255) & ~(int64_t) 255;
+        aoff_base[(size_t) c + 1] = aoff_base[(size_t) c] + chunks[c].n_bubbles + 1;
+        seq_base[(size_t) c + 1] = seq_base[(size_t) c] + (int64_t) lay[(size_t) c].seqs.size();
+    }
+    const int64_t dpool_bytes = dpool_base[(size_t) n_chunks], n_seqs_all = seq_base[(size_t) n_chunks];
+    HostVec<ScByteItem> items((size_t) n_subs);
+    HostVec<int64_t> aoff_all((size_t) aoff_base[(size_t) n_chunks]);
+    mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
+        const mrp_string_chunk &S = chunks[c];
+        const ScLayout &Lc = lay[(size_t) c];
+        const int64_t sb = sub_base[(size_t) c];
+        for (int64_t b = 0; b < S.n_bubbles; b++)
+            for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1]; k++) {
+                const mrp_read &q = Lc.seqs[(size_t) Lc.seq_of[(size_t) S.sub_read[k]]];
+                ScByteItem &it = items[(size_t) (sb + k)];
+                it.dst = dpool_base[(size_t) c] + q.pool_offset + (Lc.aoff[(size_t) b] - Lc.aoff[(size_t) q.ref_start]);
+                it.pair = (int32_t) pair_first[(size_t) (sb + k)];
+                it.n_alleles = (int32_t) Lc.an[(size_t) b];
+            }
+        std::copy(Lc.aoff.begin(), Lc.aoff.end(), aoff_all.begin() + aoff_base[(size_t) c]);
+    });
+
+    /* ---- the profile bytes, written into the chunks' device pool; the host copy comes back behind them */
+    PHM_HIP(d_items.upload(items, s));
+    PHM_HIP(d_aoff.upload(aoff_all, s));
+    PHM_HIP(d_pool.alloc((size_t) dpool_bytes));
+    PHM_HIP(hipMemsetAsync(d_pool.p, 0, (size_t) dpool_bytes, s)); /* sites a read skips stay 0 */
+    PHM_HIP(h_pool.reserve((size_t) dpool_bytes));
+    PHM_HIP(hipEventRecord(ev.e[1], s));
+    if (n_subs > 0) {
+        hipLaunchKernelGGL(sc_profile_bytes_kernel, dim3((unsigned) ((n_subs + 255) / 256)), dim3(256), 0, s, d_items.p, n_subs, L.d_out.p, d_pool.p);
+        PHM_HIP(hipGetLastError());
+    }
+    PHM_HIP(hipEventRecord(ev.e[2], s));
+    PHM_HIP(hipMemcpyAsync(h_pool.p, d_pool.p, (size_t) dpool_bytes, hipMemcpyDeviceToHost, s));
+    PHM_HIP(hipEventRecord(ev.e[3], s)); /* the host copy is complete */
+
+    /* ---- chunks over that pool (site tables staged and uploaded behind the download), then the phasing as it stands */
+    std::vector<mrp_chunk_desc> descs((size_t) n_chunks);
+    std::vector<const mrp_chunk_desc *> desc_ptr((size_t) n_chunks);
+    std::vector<const uint8_t *> dev_pools((size_t) n_chunks);
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const ScLayout &Lc = lay[(size_t) c];
+        mrp_chunk_desc &d = descs[(size_t) c];
+        d.n_sites = chunks[c].n_bubbles;
+        d.allele_number = Lc.an.data();
+        d.substitution_log_probs = Lc.sub.data();
+        d.allele_prior_log_probs = Lc.prior.data();
+        d.profile_pool = (const uint8_t *) h_pool.p + dpool_base[(size_t) c];
+        d.pool_bytes = Lc.pool_bytes;
+        d.reads = Lc.seqs.data();
+        d.n_reads = (int64_t) Lc.seqs.size();
+        desc_ptr[(size_t) c] = &d;
+        dev_pools[(size_t) c] = d_pool.p + dpool_base[(size_t) c];
+    }
+    int rc = mrp_chunk_block_create(ctx, n_chunks, desc_ptr.data(), dch.data(), &blk, 1, dev_pools.data());
+    if (rc != MRP_OK) return rc;
+    for (mrp_chunk *ch : dch) { ch->pool_host_ready = ev.e[3]; ch->pool_host_pending.store(true); }
+    std::vector<const mrp_chunk *> cptr(dch.begin(), dch.end());
+    std::vector<const mrp_read *> rptr((size_t) n_chunks);
+    std::vector<int64_t> nr((size_t) n_chunks);
+    for (int64_t c = 0; c < n_chunks; c++) { rptr[(size_t) c] = lay[(size_t) c].seqs.data(); nr[(size_t) c] = (int64_t) lay[(size_t) c].seqs.size(); }
+    const double t_phase0 = now_ms();
+    rc = mrp_phase_reads_many(ctx, n_chunks, cptr.data(), rptr.data(), nr.data(), params, res.data(), stats ? &stats->phase : nullptr);
+    const double t_phase1 = now_ms();
+    if (rc != MRP_OK) return rc;
+
+    /* ---- HP tags over the same device pool: the fragments' haplotype strings go up, one lane per sequence */
+    std::vector<int64_t> hap_base((size_t) n_chunks + 1, 0);
+    for (int64_t c = 0; c < n_chunks; c++) hap_base[(size_t) c + 1] = hap_base[(size_t) c] + 2 * (int64_t) res[(size_t) c]->length;
+    HostVec<uint64_t> haps((size_t) hap_base[(size_t) n_chunks]);
+    HostVec<ScHapItem> hitems((size_t) n_seqs_all);
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const mrp_phase_result *g = res[(size_t) c];
+        const ScLayout &Lc = lay[(size_t) c];
+        const int64_t ns = (int64_t) Lc.seqs.size();
+        if (g->length > 0) {
+            std::copy(g->haplotype_string1, g->haplotype_string1 + g->length, haps.begin() + hap_base[(size_t) c]);
+            std::copy(g->haplotype_string2, g->haplotype_string2 + g->length, haps.begin() + hap_base[(size_t) c] + g->length);
+        }
+        std::vector<int32_t> side((size_t) ns, 0);
+        for (int64_t q = 0; q < g->n_reads2; q++) /* a read found in both sets counts as hap1 (genomeFragment.c:253) */
+            if (g->reads2[q] >= 0 && g->reads2[q] < ns) side[(size_t) g->reads2[q]] = 2;
+        for (int64_t q = 0; q < g->n_reads1; q++)
+            if (g->reads1[q] >= 0 && g->reads1[q] < ns) side[(size_t) g->reads1[q]] = 1;
+        for (int64_t q = 0; q < ns; q++) {
+            ScHapItem &it = hitems[(size_t) (seq_base[(size_t) c] + q)];
+            it.pool = dpool_base[(size_t) c] + Lc.seqs[(size_t) q].pool_offset;
+            it.aoff = aoff_base[(size_t) c];
+            it.hap = hap_base[(size_t) c];
+            it.ref_start = Lc.seqs[(size_t) q].ref_start;
+            it.length = Lc.seqs[(size_t) q].length;
+            it.frag_start = g->ref_start;
+            it.frag_length = g->length;
+            it.side = side[(size_t) q];
+            it.pad = 0;
+        }
+    }
+    PHM_HIP(d_haps.upload(haps, s));
+    PHM_HIP(d_hitems.upload(hitems, s));
+    PHM_HIP(d_hap.alloc((size_t) n_seqs_all));
+    PHM_HIP(d_phred.alloc((size_t) n_seqs_all));
+    PHM_HIP(h_res.reserve((size_t) n_seqs_all * 9 + 16));
+    int8_t *h_hap = (int8_t *) h_res.p;
+    double *h_phred = (double *) ((char *) h_res.p + (((size_t) n_seqs_all + 7) & ~(size_t) 7));
+    PHM_HIP(hipEventRecord(ev.e[4], s));
+    if (n_seqs_all > 0) {
+        hipLaunchKernelGGL(sc_assign_kernel, dim3((unsigned) ((n_seqs_all + 255) / 256)), dim3(256), 0, s, d_hitems.p, n_seqs_all, d_aoff.p, d_haps.p,
+                           d_pool.p, min_phred, d_hap.p, d_phred.p);
+        PHM_HIP(hipGetLastError());
+    }
+    PHM_HIP(hipEventRecord(ctx->ev[1], s));
+    if (n_seqs_all > 0) {
+        PHM_HIP(hipMemcpyAsync(h_hap, d_hap.p, (size_t) n_seqs_all, hipMemcpyDeviceToHost, s));
+        PHM_HIP(hipMemcpyAsync(h_phred, d_phred.p, (size_t) n_seqs_all * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    PHM_HIP(hipStreamSynchronize(s));
+
+    /* ---- back to the caller's reads */
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const ScLayout &Lc = lay[(size_t) c];
+        mrp_phase_result *g = res[(size_t) c];
+        for (int64_t r = 0; r < chunks[c].n_reads; r++) {
+            hap_out[c][r] = -1;
+            if (phred_out) phred_out[c][r] = 0.0;
+        }
+        for (size_t q = 0; q < Lc.seqs.size(); q++) {
+            const int32_t r = Lc.read_of_seq[q];
+            hap_out[c][r] = h_hap[seq_base[(size_t) c] + (int64_t) q];
+            if (phred_out) phred_out[c][r] = h_phred[seq_base[(size_t) c] + (int64_t) q];
+        }
+        for (int64_t q = 0; q < g->n_reads1; q++) g->reads1[q] = Lc.read_of_seq[(size_t) g->reads1[q]];
+        for (int64_t q = 0; q < g->n_reads2; q++) g->reads2[q] = Lc.read_of_seq[(size_t) g->reads2[q]];
+    }
+    if (profiles_out)
+        for (int64_t c = 0; c < n_chunks; c++) {
+            const ScLayout &Lc = lay[(size_t) c];
+            mrp_profile_out &P = profiles_out[c];
+            auto dup = [](const void *src, size_t bytes) { void *p = malloc(bytes ? bytes : 1); if (p && bytes) memcpy(p, src, bytes); return p; };
+            P.n_seqs = (int64_t) Lc.seqs.size();
+            P.pool_bytes = Lc.pool_bytes;
+            P.seqs = (mrp_read *) dup(Lc.seqs.data(), sizeof(mrp_read) * Lc.seqs.size());
+            P.read_of_seq = (int32_t *) dup(Lc.read_of_seq.data(), sizeof(int32_t) * Lc.read_of_seq.size());
+            P.pool = (uint8_t *) dup((const uint8_t *) h_pool.p + dpool_base[(size_t) c], (size_t) Lc.pool_bytes);
+            P.allele_number = (uint32_t *) dup(Lc.an.data(), sizeof(uint32_t) * Lc.an.size());
+            P.substitution = (uint16_t *) dup(Lc.sub.data(), sizeof(uint16_t) * Lc.sub.size());
+            P.prior = (uint16_t *) dup(Lc.prior.data(), sizeof(uint16_t) * Lc.prior.size());
+            if (!P.seqs || !P.read_of_seq || !P.pool || !P.allele_number || !P.substitution || !P.prior) {
+                for (int64_t q = 0; q <= c; q++) {
+                    mrp_profile_out &X = profiles_out[q];
+                    free(X.seqs); free(X.read_of_seq); free(X.pool); free(X.allele_number); free(X.substitution); free(X.prior);
+                    memset(&X, 0, sizeof(X));
+                }
+                return fail(MRP_ERR_NOMEM, "mrp_phase_string_chunks: out of host memory");
+            }
+        }
+    if (stats) {
+        float ms = 0.f;
+        if (n_pairs > 0) { PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ev.e[0])); stats->pairhmm.kernel_ms = ms; stats->pairhmm.cells = L.cells; }
+        PHM_HIP(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
+        stats->profile_ms = ms;
+        PHM_HIP(hipEventElapsedTime(&ms, ev.e[4], ctx->ev[1]));
+        stats->assign_ms = ms;
+    }
+    for (int64_t c = 0; c < n_chunks; c++) { out[c] = res[(size_t) c]; res[(size_t) c] = nullptr; }
+    L.release();
+    d_items.release(); d_pool.release(); d_aoff.release(); d_haps.release(); d_hitems.release(); d_hap.release(); d_phred.release();
+    for (mrp_chunk *&ch : dch) { delete ch; ch = nullptr; }
+    ctx->pool.reclaim();
+    if (stats) {
+        stats->total_ms = now_ms() - t_begin;
+        stats->host_ms = stats->total_ms - (t_phase1 - t_phase0);
+    }
     return MRP_OK;
 }
 

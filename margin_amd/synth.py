@@ -1,6 +1,6 @@
 """Seeded synthetic chunks for the stRPHmm hot path (inputs only -- no algorithm lives here).
 
-Two generators:
+Generators of profile-byte chunks:
 
 * :func:`make_ont_chunk` -- BASELINE.json config 2 as restated in SURVEY.md section 8(d): a region
   with biallelic het sites at uniform positions, 30x log-normal reads, 50/50 strand and
@@ -229,3 +229,91 @@ def pairs_from_bubbles(bubbles):
     pool = np.concatenate(strings) if strings else np.zeros(0, dtype=np.uint8)
     return (pool, np.array(xo, dtype=np.int64), np.array(xl, dtype=np.int32), np.array(yo, dtype=np.int64), np.array(yl, dtype=np.int32),
             np.array(mi, dtype=np.uint8))
+
+
+# ---- chunks as the strings margin phase aligns (input of mrp_phase_string_chunks) ----
+
+@dataclass
+class StringChunk:
+    """One chunk before the alignment: per bubble (alleles, reads, substrings) with alleles / substrings uint8 symbol arrays and
+    reads the index of each substring's read; per read its name and strand.  hap / truth are for scoring only."""
+    bubbles: list
+    read_names: List[str]
+    read_forward_strand: np.ndarray  # uint8 [n_reads]
+    hap: np.ndarray                  # int [n_reads]: the haplotype each read was drawn from
+    truth: List[int]                 # per bubble: the allele of haplotype 0
+
+
+def _noisy_copy(rng, s: np.ndarray, sub: float, ins: float, dele: float) -> np.ndarray:
+    """evolve_sequence's three error kinds in one vectorised pass (at most one inserted symbol after a position)"""
+    n = len(s)
+    r = rng.random(n)
+    base = rng.integers(0, 4, size=2 * n).astype(np.uint8)
+    out = np.where(r < dele + sub, base[:n], s).astype(np.uint8)
+    ins_after = rng.random(n) < ins
+    keep = r >= dele
+    pieces = np.stack([out, base[n:]], axis=1).reshape(-1)
+    mask = np.stack([keep, ins_after], axis=1).reshape(-1)
+    return np.ascontiguousarray(pieces[mask], dtype=np.uint8)
+
+
+def make_string_chunk(seed: int, n_sites: int = 130, coverage: int = 30, allele_len: int = 25, span=(4, 40), multi_allelic: float = 0.0,
+                      duplicate_rate: float = 0.0, sv_sites: int = 0, sv_len: int = 600, orphan_reads: int = 0, empty_bubbles: int = 0,
+                      error=(0.04, 0.02, 0.02), name_prefix: str = "read") -> StringChunk:
+    """Spanning reads over consecutive het sites: each read carries one haplotype and one strand over a run of `span` sites and
+    appears in every bubble of that run with a noisy copy of its haplotype's allele.  Options: a share of multi-allelic sites
+    (3-4 alleles: every allele a substitution of the reference window at its own position), substrings copied verbatim from
+    another read of the bubble (duplicate_rate), sv_sites bubbles whose second allele inserts sv_len symbols (longer than the
+    shipped sv_threshold of 512: the pair-HMM anchors them), orphan_reads reads listed in no bubble, and empty_bubbles bubbles
+    (placed at random) that list no substring.  Deterministic per seed."""
+    rng = np.random.default_rng([seed, 11])
+    n_reads = max(1, int(round(coverage * n_sites / ((span[0] + span[1]) / 2))))
+    hap = rng.integers(0, 2, size=n_reads)
+    strand = rng.integers(0, 2, size=n_reads).astype(np.uint8)
+    spans = []
+    for _ in range(n_reads):
+        ln = int(rng.integers(span[0], span[1] + 1))
+        a = int(rng.integers(-ln + 1, n_sites))
+        spans.append((max(a, 0), min(a + ln, n_sites) - 1))
+    empty = set(rng.choice(n_sites, size=min(empty_bubbles, n_sites), replace=False).tolist()) if empty_bubbles else set()
+    sv = set(rng.choice(n_sites, size=min(sv_sites, n_sites), replace=False).tolist()) if sv_sites else set()
+    bubbles, truth = [], []
+    mid = allele_len // 2
+    for i in range(n_sites):
+        ref = random_sequence(rng, allele_len)
+        if i in sv:
+            alleles = [ref, np.concatenate([ref[:mid], random_sequence(rng, sv_len), ref[mid:]])]
+        else:
+            n_all = int(rng.integers(3, 5)) if rng.random() < multi_allelic else 2
+            alleles = [ref]
+            for k in range(1, n_all):
+                alt = ref.copy()
+                p = (mid + 2 * (k - 1)) % allele_len
+                alt[p] = (alt[p] + k) % 4
+                alleles.append(alt)
+        t0 = int(rng.integers(0, len(alleles)))
+        t1 = (t0 + 1 + int(rng.integers(0, len(alleles) - 1))) % len(alleles)
+        truth.append(t0)
+        reads, subs = [], []
+        if i not in empty:
+            for r in range(n_reads):
+                a, b = spans[r]
+                if not a <= i <= b:
+                    continue
+                if subs and rng.random() < duplicate_rate:
+                    subs.append(subs[int(rng.integers(0, len(subs)))].copy())
+                else:
+                    subs.append(_noisy_copy(rng, alleles[t0 if hap[r] == 0 else t1], *error))
+                reads.append(r)
+        bubbles.append((alleles, reads, subs))
+    names = [f"{name_prefix}_{seed}_{r:05d}" for r in range(n_reads + orphan_reads)]
+    hap = np.concatenate([hap, rng.integers(0, 2, size=orphan_reads)]) if orphan_reads else hap
+    strand = np.concatenate([strand, rng.integers(0, 2, size=orphan_reads).astype(np.uint8)]) if orphan_reads else strand
+    if orphan_reads:  # the orphans take random positions among the reads
+        perm = rng.permutation(len(names))
+        inv = np.empty_like(perm)
+        inv[perm] = np.arange(len(perm))
+        bubbles = [(al, [int(inv[r]) for r in rs], sb) for al, rs, sb in bubbles]
+        names = [names[int(p)] for p in perm]
+        hap, strand = hap[perm], strand[perm]
+    return StringChunk(bubbles=bubbles, read_names=names, read_forward_strand=np.ascontiguousarray(strand, dtype=np.uint8), hap=np.asarray(hap), truth=truth)
