@@ -602,6 +602,96 @@ int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string
                             const mrp_params *params, int64_t min_phred, mrp_phase_result **out, int8_t *const *hap_out,
                             double *const *phred_out, mrp_profile_out *profiles_out, mrp_string_chunks_stats *stats);
 
+/* ---- from alignments to read substrings at variant sites --------------------------------------------------------------
+ * The step of margin phase's chunk loop that makes the strings above (phase.c:337-357): updateVcfEntriesWithSubstringsAndPositions
+ * (impl/vcf.c:476-486, getAlleleSubstrings2 :394-462) and extractReadSubstringsAtVariantPositions (impl/htsIntegration.c:1722-1989)
+ * with indelSizeForSVHandling = 0.  One chunk's inputs in the layout htslib holds them; coordinates are 0-based genome
+ * positions (bamChunk's chunkOverlapStart / chunkOverlapEnd / chunkStart / chunkEnd). */
+#define MRP_READ_DROPPED 0  /* not listed: filtered out (:1816-1842) or no variant at or after its start (:1855) */
+#define MRP_READ_KEPT 1     /* in `reads` */
+#define MRP_READ_FILTERED 2 /* in `filteredReads`: mapq below min_mapq (:1825-1828) */
+
+typedef struct mrp_aligned_chunk {
+    int64_t overlap_start, overlap_end, chunk_start, chunk_end;
+    const char *reference; int64_t reference_len; /* the overlap slice: reference_len == overlap_end - overlap_start */
+    int64_t n_variants;
+    const int64_t *variant_pos;   /* 0-based genome position, ascending, inside [overlap_start, overlap_end) (vcf.c:284-289) */
+    const int64_t *allele_first;  /* n_variants + 1, from 0: variant v owns alleles [allele_first[v], allele_first[v+1]), at least one */
+    const int64_t *allele_off;    /* per allele: its chars in allele_chars; allele 0 = REF */
+    const int32_t *allele_len;
+    const char *allele_chars; int64_t allele_bytes;
+    const uint8_t *is_sv;         /* n_variants: nonzero selects expansion_sv (isStructuralVariant, vcf.c:405-410) */
+    int64_t n_reads;
+    const int64_t *pos;           /* bam1_core_t.pos */
+    const uint16_t *flag;         /* bam1_core_t.flag */
+    const uint8_t *mapq;          /* bam1_core_t.qual */
+    const int32_t *l_qseq;        /* bam1_core_t.l_qseq */
+    const int64_t *cigar_first;   /* n_reads + 1, from 0: read r's CIGAR is cigar[cigar_first[r] .. cigar_first[r+1]) */
+    const uint32_t *cigar;        /* bam_get_cigar words */
+    const int64_t *seq_first;     /* n_reads + 1, from 0: read r's packed bases are seq[seq_first[r] ..), (l_qseq + 1) / 2 bytes at least */
+    const uint8_t *seq;           /* bam_get_seq bytes (4-bit codes, high nibble first) */
+} mrp_aligned_chunk;
+
+typedef struct mrp_extract_options {
+    int64_t expansion_small;         /* referenceExpansionForSmallVariants (12 shipped) */
+    int64_t expansion_sv;            /* referenceExpansionForStructuralVariants (512 shipped) */
+    int64_t min_mapq;                /* filterAlignmentsWithMapQBelowThisThreshold (5 shipped) */
+    int32_t include_secondary;       /* includeSecondaryAlignments (0 shipped) */
+    int32_t include_supplementary;   /* includeSupplementaryAlignments (0 shipped) */
+    int32_t indel_size_for_sv_handling; /* indelSizeForSVHandling: only 0 (shipped) is supported (:1724-1755) */
+    int32_t use_run_length_encoding; /* useRunLengthEncoding: only 0 (shipped) is supported */
+} mrp_extract_options;
+
+/* What the extraction gives for one chunk.  Windows are 0-based in the overlap slice (putRefPosInPOASpace = FALSE).  Variant v
+ * owns alleles [allele_first[v], allele_first[v+1]) (prefix + allele + suffix of getAlleleSubstrings2) and entries
+ * [entry_first[v], entry_first[v+1]), one per read that saved a substring for it, in ascending read order (the order
+ * buildVcfEntryToReadSubstringsMap, bubbleGraph.c:1281-1323, sees).  Symbols as mrp_symbols_from_chars gives them, read
+ * bases decoded through seq_nt16_str (IUPAC codes and '=' become 4); alleles first, then the substrings, in one pool.  Every
+ * array is malloc'd: release each with mrp_free, then the array of chunks itself. */
+typedef struct mrp_extracted_chunk {
+    int64_t n_variants, n_reads;
+    int64_t *ref_aln_start, *ref_aln_stop_incl; /* n_variants: refAlnStart / refAlnStopIncl */
+    int64_t *allele_first;                      /* n_variants + 1 */
+    int64_t *allele_off; int32_t *allele_len;
+    uint8_t *read_status;                       /* n_reads: MRP_READ_* */
+    int32_t *read_n_substrings;                 /* n_reads */
+    int64_t *entry_first;                       /* n_variants + 1 */
+    int32_t *entry_read;                        /* the chunk's read index */
+    int64_t *entry_off; int32_t *entry_len;
+    uint8_t *pool; int64_t pool_bytes;
+} mrp_extracted_chunk;
+
+typedef struct mrp_extract_stats {
+    int64_t reads, cigar_ops, aligned_bases, entries; /* over the call: reads, CIGAR ops, M/=/X/I bases of reads with bases and a CIGAR, substrings */
+    double kernel_ms;       /* HIP events around the launches */
+    int64_t bytes_uploaded;
+    double host_ms;         /* host wall time outside the device work: checks, windows and alleles, staging, output */
+    double total_ms;        /* host wall time of the call */
+} mrp_extract_stats;
+
+/* extractReadSubstringsAtVariantPositions for n_chunks chunks, all device work in one set of launches.  The reference's
+ * quirks are kept: an entry starts no earlier than every entry listed before it (:1589-1607), a
+ * window with no read base is dropped, a window open at the end of the read is kept unless the walk ended before the
+ * variant's position (:1640), and the walk stops after alnReadLength + 1 reference steps, alnReadLength leaving N ops out
+ * (:1901, :113-120).  *out receives a malloc'd array of n_chunks.  MRP_ERR_ARG (checked before the context, then
+ * MRP_ERR_NO_DEVICE for a NULL context): a NULL or badly sized array, variants not ascending or outside the overlap, a
+ * variant without alleles, a REF allele that disagrees with an A/C/G/T reference base (vcf.c:423), a reference slice of the
+ * wrong length, a CIGAR op code above 8, and for a read with bases and a CIGAR: an M/I/D/N/=/X op of length 0 (the
+ * reference's walk never leaves it) or a CIGAR whose query length is not l_qseq.  MRP_ERR_UNSUPPORTED for the SV split
+ * mode or run-length encoding.  Nothing is returned on error.  stats may be NULL. */
+int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_extract_options *options,
+                                mrp_extracted_chunk **out, mrp_extract_stats *stats);
+
+/* bubbleGraph_constructFromVCFAndBamChunkReadVcfEntrySubstrings (bubbleGraph.c:1338-1400), host only: the mrp_string_chunk
+ * of one extracted chunk over its MRP_READ_KEPT reads r with keep[r] set (keep NULL: all; the seam for the caller's
+ * downsampling, downsampleBamChunkReadWithVcfEntrySubstringsViaFullReadLengthLikelihood).  A variant left without
+ * substrings makes no bubble (:1366-1371); a bubble's substrings are listed in popped, i.e. descending read order
+ * (:1391-1393).  Read indices are the extracted chunk's, n_reads = x->n_reads; read_names and read_forward_strand are
+ * the caller's and only stored.  out->pool is x->pool (borrowed); the other arrays of out and bubble_variant
+ * (vcfEntriesToBubbleIdx: the variant of each bubble) live in one block, released by mrp_free((void *) out->allele_first). */
+int mrp_string_chunk_from_extracted(const mrp_extracted_chunk *x, const uint8_t *keep, const char *const *read_names,
+                                    const uint8_t *read_forward_strand, mrp_string_chunk *out, int64_t **bubble_variant);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "mrp_symbols_from_chars", "mrp_pair_hmm_reverse_complement", "mrp_band_diagonals", "mrp_forward_probabilities",
     "mrp_allele_read_supports", "mrp_kmer_alignment_anchors", "mrp_phase_chunks_on_devices", "mrp_queue_plan", "mrp_queue_dry_run", "mrp_queue_create", "mrp_queue_destroy",
     "mrp_queue_phase_chunks", "mrp_partition_reads_by_haplotype", "mrp_phase_variants_from_tagged_reads", "mrp_phase_string_chunks",
+    "mrp_extract_read_substrings", "mrp_string_chunk_from_extracted",
 ]
 
 
@@ -224,6 +225,46 @@ class StringChunksStats(C.Structure):
                 ("host_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+READ_DROPPED, READ_KEPT, READ_FILTERED = 0, 1, 2
+
+
+class AlignedChunk(C.Structure):
+    _fields_ = [("overlap_start", C.c_int64), ("overlap_end", C.c_int64), ("chunk_start", C.c_int64), ("chunk_end", C.c_int64),
+                ("reference", C.c_void_p), ("reference_len", C.c_int64), ("n_variants", C.c_int64), ("variant_pos", C.c_void_p),
+                ("allele_first", C.c_void_p), ("allele_off", C.c_void_p), ("allele_len", C.c_void_p), ("allele_chars", C.c_void_p),
+                ("allele_bytes", C.c_int64), ("is_sv", C.c_void_p), ("n_reads", C.c_int64), ("pos", C.c_void_p), ("flag", C.c_void_p),
+                ("mapq", C.c_void_p), ("l_qseq", C.c_void_p), ("cigar_first", C.c_void_p), ("cigar", C.c_void_p), ("seq_first", C.c_void_p),
+                ("seq", C.c_void_p)]
+
+
+class ExtractOptions(C.Structure):
+    _fields_ = [("expansion_small", C.c_int64), ("expansion_sv", C.c_int64), ("min_mapq", C.c_int64), ("include_secondary", C.c_int32),
+                ("include_supplementary", C.c_int32), ("indel_size_for_sv_handling", C.c_int32), ("use_run_length_encoding", C.c_int32)]
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "ExtractOptions":
+        return cls(int(d["expansion_small"]), int(d["expansion_sv"]), int(d["min_mapq"]), int(d["include_secondary"]),
+                   int(d["include_supplementary"]), int(d.get("indel_size_for_sv_handling", 0)), int(d.get("use_run_length_encoding", 0)))
+
+
+def shipped_extract_options() -> dict:
+    """params/base_params.json: referenceExpansionForSmallVariants 12, ...StructuralVariants 512, filterAlignmentsWithMapQBelowThisThreshold
+    5, includeSecondaryAlignments / includeSupplementaryAlignments false"""
+    return dict(expansion_small=12, expansion_sv=512, min_mapq=5, include_secondary=0, include_supplementary=0)
+
+
+class ExtractedChunk(C.Structure):
+    _fields_ = [("n_variants", C.c_int64), ("n_reads", C.c_int64), ("ref_aln_start", C.c_void_p), ("ref_aln_stop_incl", C.c_void_p),
+                ("allele_first", C.c_void_p), ("allele_off", C.c_void_p), ("allele_len", C.c_void_p), ("read_status", C.c_void_p),
+                ("read_n_substrings", C.c_void_p), ("entry_first", C.c_void_p), ("entry_read", C.c_void_p), ("entry_off", C.c_void_p),
+                ("entry_len", C.c_void_p), ("pool", C.c_void_p), ("pool_bytes", C.c_int64)]
+
+
+class ExtractStats(C.Structure):
+    _fields_ = [("reads", C.c_int64), ("cigar_ops", C.c_int64), ("aligned_bases", C.c_int64), ("entries", C.c_int64), ("kernel_ms", C.c_double),
+                ("bytes_uploaded", C.c_int64), ("host_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 def load():
     """dlopen the in-tree library; raises if it has not been built (no fallback)."""
     global _lib
@@ -306,6 +347,8 @@ def load():
     L.mrp_phase_variants_from_tagged_reads.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, vp, i64, i64, vp, vp, vp, P(PairHmmStats)]
     L.mrp_phase_string_chunks.argtypes = [vp, i64, P(StringChunk), P(PairHmm), P(PairHmm), i64, i64, C.c_double, P(Params), i64, P(P(PhaseResult)),
                                           P(vp), P(vp), P(ProfileOut), P(StringChunksStats)]
+    L.mrp_extract_read_substrings.argtypes = [vp, i64, P(AlignedChunk), P(ExtractOptions), P(P(ExtractedChunk)), P(ExtractStats)]
+    L.mrp_string_chunk_from_extracted.argtypes = [P(ExtractedChunk), vp, vp, vp, P(StringChunk), P(P(C.c_int64))]
     L.mrp_kmer_alignment_anchors.argtypes = [vp, i64, vp, i64, vp]
     L.mrp_kmer_alignment_anchors.restype = i64
     L.mrp_phase_chunks_on_devices.argtypes = [vp, i32, i64, P(ChunkDesc), P(Params), i64, P(P(PhaseResult)), P(QueueStats)]
@@ -1188,3 +1231,103 @@ def phase_string_chunks_chain(ctx: Context, chunks, forward_model: PairHmm, reve
     if timing is not None:
         timing.update(supports_ms=1e3 * (t[1] - t[0]), profile_ms=1e3 * (t[2] - t[1]), phase_ms=1e3 * (t[3] - t[2]), assign_ms=1e3 * (t[4] - t[3]))
     return out, st
+
+
+# ---- read substrings at variant sites from alignments (mrp_extract_read_substrings) ----
+
+_EXTRACTED_ARRAYS = (("ref_aln_start", np.int64, "v"), ("ref_aln_stop_incl", np.int64, "v"), ("allele_first", np.int64, "v1"),
+                     ("allele_off", np.int64, "a"), ("allele_len", np.int32, "a"), ("read_status", np.uint8, "r"),
+                     ("read_n_substrings", np.int32, "r"), ("entry_first", np.int64, "v1"), ("entry_read", np.int32, "e"),
+                     ("entry_off", np.int64, "e"), ("entry_len", np.int32, "e"), ("pool", np.uint8, "p"))
+
+
+def aligned_chunk_struct(chunk):
+    """mrp_aligned_chunk for a margin_amd.synth.AlignedChunk; returns (AlignedChunk, the arrays it points into)"""
+    chars = [a.encode() for al in chunk.alleles for a in al]
+    a_first = np.zeros(len(chunk.alleles) + 1, np.int64)
+    np.cumsum([len(al) for al in chunk.alleles], out=a_first[1:])
+    a_len = np.array([len(c) for c in chars], np.int32)
+    a_off = np.zeros(len(chars), np.int64)
+    if len(chars):
+        a_off[1:] = np.cumsum(a_len[:-1])
+    keep = dict(reference=chunk.reference.encode(), allele_chars=b"".join(chars), variant_pos=np.ascontiguousarray(chunk.variant_pos, np.int64),
+                allele_first=a_first, allele_off=a_off, allele_len=a_len, is_sv=np.ascontiguousarray(chunk.is_sv, np.uint8),
+                pos=np.ascontiguousarray(chunk.read_pos, np.int64), flag=np.ascontiguousarray(chunk.flag, np.uint16),
+                mapq=np.ascontiguousarray(chunk.mapq, np.uint8), l_qseq=np.ascontiguousarray(chunk.l_qseq, np.int32),
+                cigar_first=np.ascontiguousarray(chunk.cigar_first, np.int64), cigar=np.ascontiguousarray(chunk.cigar, np.uint32),
+                seq_first=np.ascontiguousarray(chunk.seq_first, np.int64), seq=np.ascontiguousarray(chunk.seq, np.uint8))
+    keep["ref_buf"] = C.create_string_buffer(keep["reference"], max(len(keep["reference"]), 1))
+    keep["chars_buf"] = C.create_string_buffer(keep["allele_chars"], max(len(keep["allele_chars"]), 1))
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data
+    S = AlignedChunk(int(chunk.overlap_start), int(chunk.overlap_end), int(chunk.chunk_start), int(chunk.chunk_end), C.addressof(keep["ref_buf"]),
+                     len(keep["reference"]), len(chunk.alleles), ptr(keep["variant_pos"]), keep["allele_first"].ctypes.data, ptr(keep["allele_off"]),
+                     ptr(keep["allele_len"]), C.addressof(keep["chars_buf"]), len(keep["allele_chars"]), ptr(keep["is_sv"]), len(keep["pos"]),
+                     ptr(keep["pos"]), ptr(keep["flag"]), ptr(keep["mapq"]), ptr(keep["l_qseq"]), keep["cigar_first"].ctypes.data,
+                     ptr(keep["cigar"]), keep["seq_first"].ctypes.data, ptr(keep["seq"]))
+    return S, keep
+
+
+def extract_read_substrings(ctx: Optional[Context], chunks, options: Optional[dict] = None, structs=None):
+    """mrp_extract_read_substrings -> (list per chunk of dict of the mrp_extracted_chunk arrays as numpy, ExtractStats).
+    ctx None passes a NULL context (MRP_ERR_NO_DEVICE); structs = [aligned_chunk_struct(c) ...] to reuse them."""
+    L = load()
+    n = len(chunks)
+    built = structs if structs is not None else [aligned_chunk_struct(c) for c in chunks]
+    arr = (AlignedChunk * max(n, 1))(*[b[0] for b in built])
+    opt = ExtractOptions.from_dict(options or shipped_extract_options())
+    out = C.POINTER(ExtractedChunk)()
+    st = ExtractStats()
+    _check(L.mrp_extract_read_substrings(ctx.h if ctx else None, n, arr, C.byref(opt), C.byref(out), C.byref(st)))
+    res = []
+    for i in range(n):
+        X = out[i]
+        nv, nr = int(X.n_variants), int(X.n_reads)
+        af = _as_np(X.allele_first, nv + 1, np.int64)
+        ef = _as_np(X.entry_first, nv + 1, np.int64)
+        size = dict(v=nv, v1=nv + 1, a=int(af[nv]), r=nr, e=int(ef[nv]), p=int(X.pool_bytes))
+        d = {f: _as_np(getattr(X, f), size[k], t) for f, t, k in _EXTRACTED_ARRAYS}
+        for f, _, _ in _EXTRACTED_ARRAYS:
+            L.mrp_free(C.cast(getattr(X, f), C.c_void_p))
+        res.append(d)
+    L.mrp_free(C.cast(out, C.c_void_p))
+    return res, st
+
+
+def extracted_struct(x: dict):
+    """mrp_extracted_chunk over the numpy arrays of one extract_read_substrings result; returns (ExtractedChunk, arrays)"""
+    keep = {f: np.ascontiguousarray(x[f], t) for f, t, _ in _EXTRACTED_ARRAYS}
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data
+    X = ExtractedChunk(len(keep["ref_aln_start"]), len(keep["read_status"]), *[ptr(keep[f]) for f, _, _ in _EXTRACTED_ARRAYS], keep["pool"].size)
+    return X, keep
+
+
+def string_chunk_from_extracted(x: dict, read_names, read_forward_strand, keep=None):
+    """mrp_string_chunk_from_extracted -> (margin_amd.synth.StringChunk, bubble -> variant int64 array, the raw arrays)"""
+    from margin_amd import synth
+    L = load()
+    X, hold = extracted_struct(x)
+    names = [n.encode() for n in read_names]
+    name_arr = (C.c_char_p * max(len(names), 1))(*names)
+    strand = np.ascontiguousarray(read_forward_strand, np.uint8)
+    km = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+    S = StringChunk()
+    bv = C.POINTER(C.c_int64)()
+    _check(L.mrp_string_chunk_from_extracted(C.byref(X), None if km is None else km.ctypes.data, C.cast(name_arr, C.c_void_p),
+                                             strand.ctypes.data if strand.size else None, C.byref(S), C.byref(bv)))
+    nb = int(S.n_bubbles)
+    a_first = _as_np(S.allele_first, nb + 1, np.int64)
+    s_first = _as_np(S.sub_first, nb + 1, np.int64)
+    raw = dict(allele_first=a_first, allele_off=_as_np(S.allele_off, int(a_first[nb]), np.int64), allele_len=_as_np(S.allele_len, int(a_first[nb]), np.int32),
+               sub_first=s_first, sub_off=_as_np(S.sub_off, int(s_first[nb]), np.int64), sub_len=_as_np(S.sub_len, int(s_first[nb]), np.int32),
+               sub_read=_as_np(S.sub_read, int(s_first[nb]), np.int32), bubble_variant=_as_np(C.cast(bv, C.c_void_p), nb, np.int64))
+    assert S.pool == (hold["pool"].ctypes.data if hold["pool"].size else None) and S.n_reads == len(hold["read_status"])
+    L.mrp_free(C.cast(S.allele_first, C.c_void_p))
+    pool = hold["pool"]
+    bubbles = []
+    for b in range(nb):
+        al = [pool[o:o + l].copy() for o, l in zip(raw["allele_off"][a_first[b]:a_first[b + 1]], raw["allele_len"][a_first[b]:a_first[b + 1]])]
+        ks = range(int(s_first[b]), int(s_first[b + 1]))
+        bubbles.append((al, [int(raw["sub_read"][k]) for k in ks], [pool[raw["sub_off"][k]:raw["sub_off"][k] + raw["sub_len"][k]].copy() for k in ks]))
+    sc = synth.StringChunk(bubbles=bubbles, read_names=list(read_names), read_forward_strand=strand, hap=np.zeros(len(names), np.int64),
+                           truth=[0] * nb)
+    return sc, raw["bubble_variant"], raw

@@ -317,3 +317,227 @@ def make_string_chunk(seed: int, n_sites: int = 130, coverage: int = 30, allele_
         names = [names[int(p)] for p in perm]
         hap, strand = hap[perm], strand[perm]
     return StringChunk(bubbles=bubbles, read_names=names, read_forward_strand=np.ascontiguousarray(strand, dtype=np.uint8), hap=np.asarray(hap), truth=truth)
+
+
+# ---- alignments before the extraction of read substrings at variant sites ----
+
+@dataclass
+class AlignedChunk:
+    """One chunk as htslib holds it (the fields of mrp_aligned_chunk): coordinates (0-based genome), the overlap slice of the
+    reference, variants ascending by position with their alleles as strings (allele 0 = REF) and an SV flag, and reads as
+    bam1_t fields: pos, flag, mapq, l_qseq, the CIGAR as BAM uint32 words and the sequence in bam_get_seq's 4-bit packing
+    (both in CSR).  read_names / read_forward_strand are for the string chunk that follows."""
+    overlap_start: int
+    overlap_end: int
+    chunk_start: int
+    chunk_end: int
+    reference: str
+    variant_pos: np.ndarray   # int64
+    alleles: list             # per variant: list of str
+    is_sv: np.ndarray         # uint8
+    read_pos: np.ndarray      # int64
+    flag: np.ndarray          # uint16
+    mapq: np.ndarray          # uint8
+    l_qseq: np.ndarray        # int32
+    cigar_first: np.ndarray   # int64 [n_reads + 1]
+    cigar: np.ndarray         # uint32
+    seq_first: np.ndarray     # int64 [n_reads + 1]
+    seq: np.ndarray           # uint8
+    read_names: List[str] = field(default_factory=list)
+
+    @property
+    def read_forward_strand(self) -> np.ndarray:
+        return np.ascontiguousarray((self.flag & 0x10) == 0, dtype=np.uint8)
+
+
+_NT16 = {c: k for k, c in enumerate("=ACMGRSVTWYHKDBN")}
+
+
+def pack_seq(codes: Sequence[int]) -> np.ndarray:
+    """4-bit codes (seq_nt16_table values) -> bam_get_seq's layout, high nibble first"""
+    c = np.asarray(codes, dtype=np.uint8)
+    if len(c) % 2:
+        c = np.concatenate([c, np.zeros(1, np.uint8)])
+    return np.ascontiguousarray((c[0::2] << 4) | c[1::2], dtype=np.uint8)
+
+
+def _run_length(ops: Sequence[int]) -> List[int]:
+    words, k = [], 0
+    while k < len(ops):
+        j = k
+        while j < len(ops) and ops[j] == ops[k]:
+            j += 1
+        words.append(((j - k) << 4) | ops[k])
+        k = j
+    return words
+
+
+def make_aligned_chunk(seed: int, overlap_bp: int = 12_000, margin_bp: int = 1_000, coverage: float = 12.0, read_len=(600, 4000),
+                       variant_every: int = 150, sv_share: float = 0.08, sv_len=(60, 400), error=(0.04, 0.03, 0.03),
+                       oddities: bool = True, genome_start: Optional[int] = None) -> AlignedChunk:
+    """Haplotype reads aligned to a random reference, base by base: ONT-like substitutions, insertions and deletions, the
+    het variants of the read's haplotype (SNPs, indels, multi-allelic sites, SV-flagged long insertions / deletions, some
+    sites a few bases apart and some at the same position), soft and hard clips, M or =/X CIGARs, N ops, IUPAC and '='
+    bases, windows deleted whole in some reads, reads crossing the chunk and overlap edges.  With oddities, also low-mapq,
+    secondary, supplementary and unmapped records, a read without CIGAR and a secondary without sequence.  Deterministic
+    per seed; the other generators' outputs are untouched (own generator stream)."""
+    rng = np.random.default_rng([seed, 29])
+    g0 = int(genome_start if genome_start is not None else 1_000_000 + 7_919 * (seed % 1000))
+    pad = read_len[1] + 2 * sv_len[1]
+    genome = "".join(rng.choice(list("ACGT"), size=overlap_bp + 2 * pad))  # genome[k] is position g0 - pad + k
+    low = rng.random(len(genome)) < 0.05
+    genome = "".join(c.lower() if m else c for c, m in zip(genome, low))
+    genome = "".join("N" if rng.random() < 0.002 else c for c in genome)
+    base = g0 - pad
+    ovl_s, ovl_e = g0, g0 + overlap_bp
+    ch_s, ch_e = ovl_s + margin_bp, ovl_e - margin_bp
+    ref = genome[ovl_s - base:ovl_e - base]
+
+    # variants (REF taken from the reference)
+    vpos, valleles, vsv = [], [], []
+    p = ovl_s + int(rng.integers(0, 20))
+    while p < ovl_e - 2:
+        r = rng.random()
+        g = genome[p - base]
+        if r < sv_share:
+            ln = int(rng.integers(sv_len[0], sv_len[1] + 1))
+            if rng.random() < 0.5:
+                alleles = [g, g + "".join(rng.choice(list("ACGT"), size=ln))]
+            else:
+                ln = min(ln, ovl_e - p - 1)
+                alleles = [genome[p - base:p - base + ln + 1], g]
+            vsv.append(1)
+        else:
+            kind = rng.random()
+            if kind < 0.55:
+                alleles = [g, "ACGT"[("ACGT".find(g.upper()) + 1) % 4]]
+            elif kind < 0.7:
+                alleles = [g] + ["ACGT"[("ACGT".find(g.upper()) + k) % 4] for k in (1, 2)]
+            elif kind < 0.85:
+                alleles = [g, g + "".join(rng.choice(list("ACGT"), size=int(rng.integers(1, 6))))]
+            else:
+                ln = int(rng.integers(1, 6))
+                alleles = [genome[p - base:p - base + ln + 1], g]
+            vsv.append(0)
+        vpos.append(p)
+        valleles.append(alleles)
+        q = rng.random()
+        p += 0 if q < 0.03 else int(rng.integers(1, 8)) if q < 0.15 else int(rng.integers(variant_every // 2, 2 * variant_every))
+    hap_alt = [[int(rng.integers(1, len(a))) if rng.random() < 0.85 else 0, 0] for a in valleles]  # hap 0 alt, hap 1 REF mostly
+    for h in hap_alt:
+        if rng.random() < 0.5:
+            h.reverse()
+
+    # reads
+    n_reads = max(1, int(coverage * (overlap_bp + read_len[1]) / ((read_len[0] + read_len[1]) / 2)))
+    pos_l, flag_l, mapq_l, lq_l, cig_l, seq_l, names = [], [], [], [], [], [], []
+    var_at = {}
+    for k, q in enumerate(vpos):
+        var_at.setdefault(q, k)
+    sub, ins, dele = error
+    for r in range(n_reads):
+        hap = int(rng.integers(0, 2))
+        start = int(rng.integers(ovl_s - read_len[1], ovl_e))
+        length = int(rng.integers(read_len[0], read_len[1] + 1))
+        eq_style = rng.random() < 0.3
+        ops, codes = [], []
+        g = start
+        wipe = rng.random() < 0.3
+        while g < start + length and g - base < len(genome) - pad // 2:
+            v = var_at.get(g)
+            if v is not None and hap_alt[v][hap] != 0 and g > start:
+                a_ref, a_alt = valleles[v][0], valleles[v][hap_alt[v][hap]]
+                common = 0
+                while common < min(len(a_ref), len(a_alt)) and a_ref[common].upper() == a_alt[common].upper():
+                    common += 1
+                for t in range(min(len(a_ref), len(a_alt))):
+                    c = a_alt[t]
+                    same = c.upper() == genome[g - base + t].upper()
+                    ops.append((7 if same else 8) if eq_style else 0)
+                    codes.append(_NT16[c.upper()])
+                if len(a_alt) > len(a_ref):
+                    ops += [1] * (len(a_alt) - len(a_ref))
+                    codes += [_NT16[c.upper()] for c in a_alt[len(a_ref):]]
+                elif len(a_ref) > len(a_alt):
+                    ops += [2] * (len(a_ref) - len(a_alt))
+                g += len(a_ref)
+                continue
+            if v is not None and wipe and rng.random() < 0.1 and g > start:  # a deletion over a whole small window
+                ln = int(rng.integers(20, 40))
+                ops += [3 if rng.random() < 0.3 else 2] * ln
+                g += ln
+                continue
+            x = rng.random()
+            if x < dele:
+                ops.append(2)
+                g += 1
+                continue
+            c = genome[g - base].upper()
+            if x < dele + sub:
+                c = "ACGT"[int(rng.integers(0, 4))]
+            code = _NT16.get(c, 15)
+            if rng.random() < 0.003:
+                code = int(rng.choice([0, 3, 5, 6, 9, 15]))  # '=', M, R, S, W, N
+            same = c == genome[g - base].upper() and code in (1, 2, 4, 8)
+            ops.append((7 if same else 8) if eq_style else 0)
+            codes.append(code)
+            g += 1
+            while rng.random() < ins:
+                ops.append(1)
+                codes.append([1, 2, 4, 8][int(rng.integers(0, 4))])
+        if rng.random() < 0.05:  # an N run inside the read (spliced-looking)
+            cut = int(rng.integers(1, max(2, len(ops) - 1)))
+            if ops[cut - 1] not in (1,) and ops[cut] not in (1,):
+                ops = ops[:cut] + [3] * int(rng.integers(5, 60)) + ops[cut:]
+        while ops and ops[0] in (2, 3):  # an alignment starts and ends on a base
+            ops.pop(0)
+            start += 1
+        while ops and ops[-1] in (2, 3):
+            ops.pop()
+        if not ops:
+            continue
+        words = _run_length(ops)
+        lead = [1, 2, 4, 8]
+        sc0 = int(rng.integers(1, 200)) if rng.random() < 0.4 else 0
+        sc1 = int(rng.integers(1, 200)) if rng.random() < 0.4 else 0
+        if sc0:
+            words = [(sc0 << 4) | 4] + words
+            codes = [lead[int(rng.integers(0, 4))] for _ in range(sc0)] + codes
+        if sc1:
+            words = words + [(sc1 << 4) | 4]
+            codes = codes + [lead[int(rng.integers(0, 4))] for _ in range(sc1)]
+        if rng.random() < 0.15:
+            words = [(int(rng.integers(1, 500)) << 4) | 5] + words
+        if rng.random() < 0.15:
+            words = words + [(int(rng.integers(1, 500)) << 4) | 5]
+        flag = 0x10 if rng.random() < 0.5 else 0
+        mapq = 60 if rng.random() < 0.85 else int(rng.integers(0, 12))
+        if oddities:
+            o = rng.random()
+            flag |= 0x100 if o < 0.04 else 0x800 if o < 0.08 else 0x4 if o < 0.1 else 0
+        pos_l.append(start)
+        flag_l.append(flag)
+        mapq_l.append(mapq)
+        lq_l.append(len(codes))
+        cig_l.append(np.array(words, np.uint32))
+        seq_l.append(pack_seq(codes))
+        names.append(f"aln_{seed}_{r:05d}")
+    if oddities:  # a mapped read without CIGAR, a secondary without sequence (SEQ '*')
+        for w, lq in (([], 40), ([(40 << 4) | 0], 0)):
+            pos_l.append(ch_s + int(rng.integers(0, 100)))
+            flag_l.append(0 if lq else 0x100)
+            mapq_l.append(60)
+            lq_l.append(lq)
+            cig_l.append(np.array(w, np.uint32))
+            seq_l.append(pack_seq([1] * lq))
+            names.append(f"aln_{seed}_odd{len(names)}")
+    cf = np.zeros(len(cig_l) + 1, np.int64)
+    np.cumsum([len(c) for c in cig_l], out=cf[1:])
+    sf = np.zeros(len(seq_l) + 1, np.int64)
+    np.cumsum([len(s) for s in seq_l], out=sf[1:])
+    return AlignedChunk(overlap_start=ovl_s, overlap_end=ovl_e, chunk_start=ch_s, chunk_end=ch_e, reference=ref,
+                        variant_pos=np.array(vpos, np.int64), alleles=valleles, is_sv=np.array(vsv, np.uint8),
+                        read_pos=np.array(pos_l, np.int64), flag=np.array(flag_l, np.uint16), mapq=np.array(mapq_l, np.uint8),
+                        l_qseq=np.array(lq_l, np.int32), cigar_first=cf,
+                        cigar=np.concatenate(cig_l) if cig_l else np.zeros(0, np.uint32), seq_first=sf,
+                        seq=np.concatenate(seq_l) if seq_l else np.zeros(0, np.uint8), read_names=names)
