@@ -16,12 +16,18 @@ Beside it:
                 `traffic` = HBM bytes that really cross the interface per step, from the committed rocprofv3 PMC passes over every
                 kernel of a 96-chunk batch in situ (profiles/r05/path_traffic.json, stamped with the kernel sources' hash);
                 `insitu` = the same arithmetic per kernel family with the family's summed device time (HIP events of the step);
-                `replay` = kernel evidence only: the recursion kernel over ALL sweeps of 96 chunks as one dependency-free batch.
+                `replay` (--full) = kernel evidence only: the recursion kernel over ALL sweeps of 96 chunks as one dependency-free batch.
+  step_detail   the device time of the last timed step by kernel family, from the library's counters
+
+A plain run gives the headline and these two, which come from the timed steps themselves.  Every other leg takes runs of its own
+and comes only with `--full`:
   parity        the results of the LAST timed step for 16 of its chunks against the oracle's results for the same chunks (the
                 cpu_baseline leg computes them anyway); the shape legs sample 8 chunks each the same way
   queue         the same chunks through the host work queue from HOST memory (upload included, PCIe-inclusive rate)
   shapes        the chunk shapes of BASELINE.json configs[2] (640 x ~130 sites), configs[4] (HiFi, 2-4 alleles) through the same call, and
                 configs[3]/8: one GPU's share of a whole genome (3 900 chunks of ~130 sites) from HOST memory through the work queue
+  latency       one call over 1 and over 8 of the chunks
+  sum_mode      the log-sum-exp sweeps of a few chunks replayed as one batch
   alignment     the pair-HMM kernel family that produces the profile bytes
   cpu_baseline  the oracle (CPU restatement of the reference) on a bounded sample of the same chunks, N = 1 only
 
@@ -50,7 +56,7 @@ DUMP_MAX_CHUNKS = 256
 DUMP_SEED = 20240607
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -61,6 +67,9 @@ def parse_args():
     ap.add_argument("--threads", type=int, default=int(os.environ.get("MRP_BENCH_THREADS", "0")))
     ap.add_argument("--phase-groups", type=int, default=0,
                     help="concurrent batches inside mrp_phase_reads_many (0: the library's choice, one per 12 chunks up to 4, eight from 192 chunks on)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (latency, queue, shapes, kernel replay, sum mode, alignment, cpu_baseline and "
+                         "parity); the options below that select or size those legs apply to a --full run only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the kernel replay leg (it needs ~20 s of host work to record the sweeps)")
     ap.add_argument("--roofline-steps", type=int, default=20)
@@ -78,7 +87,24 @@ def parse_args():
                          f"(float64 / float32, at most {DUMP_MAX_BYTES >> 20} MB in all)")
     ap.add_argument("--queue-child", action="store_true", help="(internal) run the work queue leg alone and print its runs as one JSON line")
     ap.add_argument("--queue-device", type=int, default=0, help="(internal) device of the queue child")
-    return ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def make_chunks(seeds, n_workers, **kw):
+    """synth.make_ont_chunk(seed, **kw) for every seed, in order, with each chunk's read records (capi.read_records) built as it
+    arrives.  The generator is bound by the interpreter, so the chunks are made in a pool of fresh processes rather than threads
+    (1 152 chunks of the headline: 4.0-4.5 s on 16 processes, 52 s on 16 threads)."""
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    from functools import partial
+    from margin_amd import capi, synth
+    n_workers = max(1, min(n_workers, len(seeds)))
+    chunks = []
+    with ProcessPoolExecutor(max_workers=n_workers, mp_context=multiprocessing.get_context("spawn")) as ex:
+        for c in ex.map(partial(synth.make_ont_chunk, **kw), seeds, chunksize=max(1, min(8, len(seeds) // (4 * n_workers)))):
+            capi.read_records(c)
+            chunks.append(c)
+    return chunks
 
 
 def queue_child(args):
@@ -90,11 +116,7 @@ def queue_child(args):
     cpu_share = max(1, os.cpu_count() or 8)
     capi.load().mrp_set_host_threads(max(1, min(int(os.environ.get("MRP_BENCH_HOST_THREADS", "32")), cpu_share)))
     n_threads = args.threads or min(16, cpu_share, args.chunks)
-    seeds = sharding.chunk_seeds(0, args.chunks)
-    with ThreadPoolExecutor(max_workers=n_threads) as ex:
-        chunks = list(ex.map(lambda sd: synth.make_ont_chunk(seed=sd, region_bp=args.sites * 500, n_sites=args.sites, coverage=args.coverage), seeds))
-    for c in chunks:
-        capi.read_records(c)
+    chunks = make_chunks(sharding.chunk_seeds(0, args.chunks), n_threads, region_bp=args.sites * 500, n_sites=args.sites, coverage=args.coverage)
     descs = capi.chunk_descs(chunks)
     q = capi.Queue([args.queue_device])
     for _ in range(2):
@@ -285,7 +307,7 @@ def main():
     # the work queue leg in a fresh process, BEFORE this one touches the GPU (a process that has initialised the GPU must not start
     # another program); one rank only: the ranks of a multi-GPU launch keep the in-process leg, whose runs they can bracket by barriers
     fresh_queue, queue_process = None, "in-process"
-    if world == 1 and n_gpus == 1 and args.queue_runs > 0 and args.steps > 0 and "MRP_BENCH_DEVICES" not in os.environ:
+    if args.full and world == 1 and n_gpus == 1 and args.queue_runs > 0 and args.steps > 0 and "MRP_BENCH_DEVICES" not in os.environ:
         fresh_queue, queue_process = run_queue_child(args, local_rank)
     # one rank per GPU (the driver's launch), or one process that drives the N devices through the library's queue
     if world != 1 and world != n_gpus:
@@ -294,6 +316,16 @@ def main():
     single_process_multi = world == 1 and n_gpus > 1
     if args.dump_outputs and args.steps < 1:
         sys.exit("bench.py: --dump-outputs writes the results of the last timed step: it needs --steps 1 or more")
+
+    # the chunks, made by fresh processes before this one touches the GPU (as the queue child above)
+    from margin_amd import sharding
+    n_chunks = args.chunks * (n_gpus if single_process_multi else 1)
+    cpu_share = max(1, (os.cpu_count() or 8) // max(1, world))
+    n_threads = args.threads or min(16, cpu_share, n_chunks)
+    t0 = time.time()
+    chunks = make_chunks(sharding.chunk_seeds(rank, n_chunks), n_threads, region_bp=args.sites * 500, n_sites=args.sites, coverage=args.coverage)
+    t_synth = time.time() - t0
+    units = float(sum(c.units for c in chunks))
 
     import torch
     dist = None
@@ -319,7 +351,7 @@ def main():
         cpu_binding = bind_near_device(local_rank)
 
     import numpy as np
-    from margin_amd import capi, sharding, synth
+    from margin_amd import capi, synth
 
     # rehearsal knob: the single-process path over an explicit device list (e.g. "0,0": two queue workers sharing one card)
     queue_devices = [int(x) for x in os.environ["MRP_BENCH_DEVICES"].split(",")] if os.environ.get("MRP_BENCH_DEVICES") else list(range(n_gpus))
@@ -328,24 +360,12 @@ def main():
 
     params_dict = synth.shipped_phase_params()
     params = capi.Params.from_reference_names(params_dict)
-    n_chunks = args.chunks * (n_gpus if single_process_multi else 1)
-    cpu_share = max(1, (os.cpu_count() or 8) // max(1, world))
-    n_threads = args.threads or min(16, cpu_share, n_chunks)
     # the library's worker pool: this rank's share of the node's cores, at most 32 per device (a work queue gives every
     # device its own pool of this size).  Round 5: 32 instead of 16 -- the GPU hosts of this pool have 256 hardware threads for eight
     # devices, and the host-bound head of a call (the first merge levels' tiling paths) shrinks with the pool: 157 -> 153 ms per step
     # at 32 threads, 152 at 48 (tools/step_probe.py); the pool's threads sleep outside their loops
     host_threads = max(1, min(int(os.environ.get("MRP_BENCH_HOST_THREADS", "32")), cpu_share // (n_gpus if single_process_multi else 1)))
     capi.load().mrp_set_host_threads(host_threads)
-    seeds = sharding.chunk_seeds(rank, n_chunks)
-
-    t0 = time.time()
-    with ThreadPoolExecutor(max_workers=n_threads) as ex:
-        chunks = list(ex.map(lambda s: synth.make_ont_chunk(seed=s, region_bp=args.sites * 500, n_sites=args.sites, coverage=args.coverage), seeds))
-    t_synth = time.time() - t0
-    units = float(sum(c.units for c in chunks))
-    for c in chunks:
-        capi.read_records(c)
 
     def barrier():
         if dist is not None:
@@ -355,7 +375,8 @@ def main():
     reduce_dev = "cuda" if (dist is not None and dist.get_backend() == "nccl") else None
 
     # ---- the timed region: every chunk phased end to end, K times -------------------------------------------------
-    # parity stamp: the results of the LAST timed step for the first chunks stay unconverted until the clock has stopped
+    # parity stamp: the results of the LAST timed step for the first chunks stay unconverted until the clock has stopped (in a plain
+    # run too, where nothing compares them: the timed steps are the same with and without --full)
     n_parity = min(args.parity_chunks, len(chunks)) if (rank == 0 and not args.no_cpu_baseline and n_gpus == 1) else 0
     # --dump-outputs: the results of the last timed step for a seeded sample of its chunks (rank 0's), kept the same way
     dump_idx = dump_sample(chunks) if (args.dump_outputs and rank == 0) else []
@@ -397,7 +418,7 @@ def main():
                chunks_per_gpu=args.chunks, units_per_gpu=int(units) // (n_gpus if single_process_multi else 1),
                parallelism=(f"1 process, {n_gpus} devices, host work queue (mrp_queue_phase_chunks), no collectives" if single_process_multi else
                             f"{world} process(es), one per GPU, chunks sharded by rank, no collectives"),
-               host_threads=host_threads, host_cpu_s_per_step=host_cpu / max(1, args.steps), synth_s=t_synth, cpu_binding=cpu_binding)
+               host_threads=host_threads, host_cpu_s_per_step=host_cpu / max(1, args.steps), synth_s=t_synth, cpu_binding=cpu_binding, full=args.full)
     out = dict(metric="het-sites x reads phased/sec (30x ONT synthetic chunks, end to end: every merge level + final sweep)",
                value=value, unit="het-site-reads/s", n_gpus=n_gpus, steps=args.steps, warmup=args.warmup, ms_per_step=ms_per_step,
                higher_is_better=True, scaling="weak", vs_baseline=None, dtype="int32", data="synthetic", config=cfg)
@@ -439,7 +460,7 @@ def main():
 
     # ---- latency: what ONE chunk and EIGHT chunks of the headline workload cost end to end (BASELINE.json configs[1] is literally
     # "a single 1 Mb chunk, one sweep": a caller with few chunks in hand sees this, not the many-chunk rate) ----------------
-    if not single_process_multi and rank == 0:
+    if args.full and not single_process_multi and rank == 0:
         lat = {}
         for m in (1, 8):
             if m > len(dchunks):
@@ -456,7 +477,7 @@ def main():
         dist.barrier()
 
     # ---- the same chunks from HOST memory through the work queue (PCIe-inclusive) --------------------------------
-    if args.queue_runs > 0 and not single_process_multi:
+    if args.full and args.queue_runs > 0 and not single_process_multi:
         # the queue's workers have contexts, streams and allocator caches of their own: the resident leg's go first (a caller of
         # the queue holds no second family of contexts whose streams would share the device's hardware queues with the queue's)
         for d_ in dchunks:
@@ -502,9 +523,9 @@ def main():
         dchunks = []
 
     # ---- the shapes of BASELINE.json configs[2] and configs[4] on one GPU (same call, other chunks) ---------------
-    if not single_process_multi:
+    if args.full and not single_process_multi:
         ctx.trim()
-    if args.shape_runs > 0 and not single_process_multi:
+    if args.full and args.shape_runs > 0 and not single_process_multi:
         do_parity = rank == 0 and not args.no_cpu_baseline and n_gpus == 1
 
         def parity_of(cs, got, idx):
@@ -611,7 +632,7 @@ def main():
             gq.close()
 
     # ---- kernel evidence: all sweeps of the same chunks replayed as one batch (rank 0) ---------------------------
-    if not args.no_roofline and rank == 0 and not single_process_multi:
+    if args.full and not args.no_roofline and rank == 0 and not single_process_multi:
         rctx = capi.Context(local_rank)
         big = capi.Batch(rctx)
         tls_ctx = {}
@@ -691,7 +712,7 @@ def main():
     if dist is not None:
         dist.barrier()
 
-    if args.sum_chunks > 0 and rank == 0 and not single_process_multi:
+    if args.full and args.sum_chunks > 0 and rank == 0 and not single_process_multi:
         # Sum mode (logAddP with maxNotSumTransitions false, hmm.c:15-20): the sweeps of a few chunks phased by the hashing path
         # with log-sum-exp transitions, replayed as one batch: mrp_sweep_lse_kernel (merge column in LDS, reproducible sums).
         sctx = capi.Context(local_rank)
@@ -719,7 +740,7 @@ def main():
         for d_ in skeep:
             d_.close()
 
-    if args.align_chunks > 0 and not single_process_multi:
+    if args.full and args.align_chunks > 0 and not single_process_multi:
         # Alignment leg: the banded pair-HMM forward probability of every read substring against every
         # allele of every site (bubbleGraph.c:1421-1464), the numbers that become the profile bytes the sweeps read.
         t_hmm, t_tr, t_em = synth.margin_phase_pair_hmm_arrays()
@@ -772,7 +793,7 @@ def main():
                                                     identical_to_gpu=bool(same))
         actx.close()
 
-    if rank == 0 and not args.no_cpu_baseline and n_gpus == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and n_gpus == 1:
         # CPU baseline: the oracle (C restatement of the reference's linked-list/hash implementation, -O3 -mpopcnt) phasing
         # one chunk per thread -- the reference's own parallel axis (phase.c:276) -- on a bounded sample of the same chunks,
         # end to end like the GPU value (tiling paths, every merge level with prune, final sweep, trace back, fragments).

@@ -4,9 +4,9 @@
 set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --threads 2 --no-cpu-baseline --align-chunks 0 --queue-runs 0 --sum-chunks 0"
-# 1. the default bench line
-( cd $R && timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) || exit 1
+BENCH="python3 $R/bench.py --full --threads 2 --no-cpu-baseline --align-chunks 0 --queue-runs 0 --sum-chunks 0"
+# 1. the bench line with every leg
+( cd $R && timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) || exit 1
 # 2. kernel trace + stats of the bench command (end-to-end steps and the replay leg)
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/t_stats -o t -- $BENCH --steps 5 --warmup 1 > $O/bench_under_trace.json 2> $O/bench_under_trace.err || exit 1
 python3 $R/tools/r02_summary.py stats $O/t_stats > $O/bench_kernel_stats.txt
