@@ -532,7 +532,7 @@ def emissions(ctx: Context, dchunk: DeviceChunk, first_site: int, n_sites: int, 
     return out[:part.shape[0]]
 
 
-# ---- host pipeline (rphmm_host.c) -----------------------------------------------------------
+# ---- host pipeline (rphmm_chunk.c, rphmm_host.c, rphmm_many.c) -------------------------------
 
 def read_records(chunk):
     """mrp_read[] for a margin_amd.synth.Chunk; returns (ctypes array, keep-alive list).  Cached on the chunk."""

@@ -1,47 +1,30 @@
 /*
- * rphmm_host.c -- host pipeline of libmargin_rphmm.so, in C as the reference's host code is.
+ * rphmm_host.c -- the device-resident host path of libmargin_rphmm.so: the code behind mrp_phase_reads_many's headline.
  *
- * The structural stRPHmm operations of impl/hmm.c, column.c, mergeColumn.c, coordination.c,
- * genomeFragment.c and the phasing driver bubbleGraph.c:2673-2801, re-designed around ONE flat
- * structure-of-arrays hmm (struct mrp_hmm) whose arrays are exactly the arrays of mrp_hmm_job:
- * cells are rows of (partition, next, prev), merge cells rows of (from, to), transitions are
- * indices instead of hash lookups.  Nothing is flattened before a sweep; the device batch is a
- * memcpy of these arrays.  Every forward/backward sweep runs on the GPU via mrp_fb_run /
- * mrp_batch_*; there is no CPU sweep in this file.
+ * The recursion of mergeTilingPaths (coordination.c:263-409) for any number of chunks at once, with the hmms never
+ * leaving HBM.  The host keeps a compact "shadow" of every hmm (struct rhmm: interval, reads, column boundaries, where
+ * its pruned form will be on the device) and decides WHICH hmms are merged and where the merged columns begin
+ * (r_prepare_merge, r_cross_build); everything else -- cells, connectors, sweep, prune, trace back, genome fragment --
+ * is the engine's (mrp_engine.cpp), one batch of kernels per recursion level (r_run_tree).  phase_many_resident is one
+ * batch of chunks from reads to results; rphmm_many.c splits a call into such batches.
  *
- * Order conventions (DESIGN.md "Order semantics"): cell order is the reference's list order;
- * merge cells keep creation order; stList_sort2 is taken to be stable; stHash/stSet iteration
- * (address dependent in the reference) is creation order.
+ * The hot loops run some 10^5 times per call on 16 threads, so two private allocators live here beside their only
+ * users: the thread's scratch arena (with the arena-aware xmalloc / xcalloc / xrealloc and this file's free()) and
+ * the shadow block pool.  The flat hmm and the per-job view are in rphmm_common.h, results are built in
+ * rphmm_result.c, the per-chunk path a chunk falls back to is rphmm_chunk.c.
  */
 #define _GNU_SOURCE
-#include "rphmm_host.h"
+#define RPHMM_ARENA_ALLOC /* this file supplies xmalloc / xcalloc / xrealloc */
+#include "rphmm_common.h"
 
-#include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
-
-static double now_ms(void) {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return 1e3 * (double) ts.tv_sec + 1e-6 * (double) ts.tv_nsec;
-}
-
-/* host worker threads: the structural code is independent per chunk / per merge node */
-#include <pthread.h>
-typedef void (*par_fn)(int64_t i, void *arg);
-static void parallel_for(int64_t n, par_fn fn, void *arg) { mrp_pool_run(n, 1, fn, arg); } /* persistent pool, mrp_api.cpp */
-
-/* ------------------------------------------------------------------------------------------ */
-/* helpers                                                                                     */
-/* ------------------------------------------------------------------------------------------ */
 /* Scratch arena of the calling thread.  One merge of the resident pipeline (r_prepare_merge) makes some thirty small
  * allocations that all die before it returns -- component lists, tiling paths, piece lists -- and a call makes 10^5 merges on
  * 16 threads: a quarter of the host CPU time of a call went into malloc/free.  While the arena is switched on, xmalloc /
  * xcalloc / xrealloc (hence VEC_PUSH) bump-allocate from it; free() of such a pointer is a no-op (this file's free() checks
  * the range), the arena is rewound when the merge is done.  What outlives the merge (shadows, the result path, the garbage
- * list) is allocated with the arena switched off.  A block never changes threads while the arena owns it. */
+ * list) is allocated with the arena switched off.  A block never changes threads while the arena owns it.
+ * The arena is only ever on inside r_prepare_merge: flat hmms and results (rphmm_result.c, whose free() is the heap's) never
+ * come from it.  Its state exists once in the library, in this file. */
 typedef struct { char *base; size_t cap, used; int active; } tl_arena;
 static __thread tl_arena t_ar;
 static pthread_key_t ar_key;
@@ -93,68 +76,8 @@ static void *xrealloc(void *q, size_t n) {
     if (!p) { fprintf(stderr, "margin_rphmm: out of host memory\n"); abort(); }
     return p;
 }
-void mrp_free(void *p) { free(p); }
 static inline void tl_free(void *p) { if (p && !ar_owns(p)) free(p); }
 #define free(p) tl_free(p) /* from here on: a block of the thread's scratch arena is not given to the heap */
-
-#define VEC(T) struct { T *a; int64_t n, cap; }
-#define VEC_PUSH(v, x)                                                                        \
-    do {                                                                                      \
-        if ((v).n == (v).cap) {                                                               \
-            (v).cap = (v).cap ? (v).cap * 2 : 16;                                             \
-            (v).a = xrealloc((v).a, sizeof(*(v).a) * (size_t) (v).cap);                       \
-        }                                                                                     \
-        (v).a[(v).n++] = (x);                                                                 \
-    } while (0)
-#define VEC_RESERVE(v, extra)                                                                 \
-    do {                                                                                      \
-        if ((v).n + (int64_t) (extra) > (v).cap) {                                            \
-            while ((v).n + (int64_t) (extra) > (v).cap) (v).cap = (v).cap ? (v).cap * 2 : 16; \
-            (v).a = xrealloc((v).a, sizeof(*(v).a) * (size_t) (v).cap);                       \
-        }                                                                                     \
-    } while (0)
-
-static inline uint64_t mix64(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return x;
-}
-/* uint64 -> uint32 open-addressing map (stands in for the stHash of mergeColumn.c:27-31) */
-typedef struct { uint64_t *k; uint32_t *v; uint64_t mask; } u64map;
-#define U64MAP_EMPTY 0xFFFFFFFFu
-static void u64map_init(u64map *m, int64_t expect) {
-    uint64_t cap = 16;
-    while (cap < (uint64_t) expect * 2) cap *= 2;
-    m->mask = cap - 1;
-    m->k = xmalloc(sizeof(uint64_t) * cap);
-    m->v = xmalloc(sizeof(uint32_t) * cap);
-    memset(m->v, 0xFF, sizeof(uint32_t) * cap);
-}
-static void u64map_free(u64map *m) { free(m->k); free(m->v); m->k = NULL; m->v = NULL; }
-static inline uint32_t u64map_get(const u64map *m, uint64_t key) {
-    uint64_t i = mix64(key) & m->mask;
-    while (m->v[i] != U64MAP_EMPTY) {
-        if (m->k[i] == key) return m->v[i];
-        i = (i + 1) & m->mask;
-    }
-    return U64MAP_EMPTY;
-}
-static inline void u64map_put(u64map *m, uint64_t key, uint32_t val) { /* caller sized the map */
-    uint64_t i = mix64(key) & m->mask;
-    while (m->v[i] != U64MAP_EMPTY) {
-        if (m->k[i] == key) { m->v[i] = val; return; }
-        i = (i + 1) & m->mask;
-    }
-    m->k[i] = key; m->v[i] = val;
-}
-
-/* partitions.c */
-static inline uint64_t accept_mask(int64_t depth) { /* :13-19 */
-    return depth < 64 ? ~(0xFFFFFFFFFFFFFFFFULL << depth) : 0xFFFFFFFFFFFFFFFFULL;
-}
-static inline uint64_t merge_bits(uint64_t p1, uint64_t p2, int64_t d1) { /* :21-28 */
-    return d1 < 64 ? ((p2 << d1) | p1) : p1;
-}
-static inline uint64_t invert_partition(uint64_t p, int64_t depth) { return accept_mask(depth) & ~p; } /* :37-42 */
 
 /* Blocks of the shadow hmms of the device-resident merge: tens of thousands per call, a few hundred bytes to a few hundred
  * kilobytes each, all dead by the end of the call.  Through malloc the large ones are mapped and unmapped one by one (and
@@ -231,1147 +154,10 @@ static void shadow_release(void *p, int cls) {
 }
 
 /* ------------------------------------------------------------------------------------------ */
-/* the flat hmm                                                                                */
-/* ------------------------------------------------------------------------------------------ */
-struct mrp_hmm {
-    int32_t ref_start, ref_length; /* stRPHmm.refStart / refLength */
-    int32_t max_depth;
-    VEC(int32_t) reads;            /* stRPHmm.profileSeqs (read indices) */
-    /* columns */
-    VEC(int32_t) col_start, col_len, col_depth;
-    VEC(int64_t) cell_off, read_off;   /* K+1 */
-    VEC(int32_t) col_reads;            /* per column, bit order */
-    VEC(int64_t) read_byte_off;        /* per column per read: offset of column->seqs[i] in the pool */
-    /* cells */
-    VEC(uint64_t) part;
-    VEC(uint32_t) next, prev;
-    /* merge columns */
-    VEC(uint64_t) mask_from, mask_to;  /* K-1 */
-    VEC(int64_t) mcell_off;            /* K (first entry 0) */
-    VEC(uint64_t) mfrom, mto;
-    /* results of the last sweep */
-    double *f, *b, *mf, *mb, *total;
-    double fwd, bwd;
-    int has_results;
-};
-
-static int64_t hmm_K(const mrp_hmm *h) { return h->col_start.n; }
-
-static mrp_hmm *hmm_new(void) {
-    mrp_hmm *h = xcalloc(1, sizeof(*h));
-    VEC_PUSH(h->cell_off, 0);
-    VEC_PUSH(h->read_off, 0);
-    VEC_PUSH(h->mcell_off, 0);
-    return h;
-}
-static void hmm_free_results(mrp_hmm *h) {
-    free(h->f); free(h->b); free(h->mf); free(h->mb); free(h->total);
-    h->f = h->b = h->mf = h->mb = h->total = NULL;
-    h->has_results = 0;
-}
-static void hmm_free_array(const mrp_hmm *h, void *p) { (void) h; free(p); }
-void mrp_hmm_destroy(mrp_hmm *h) {
-    if (!h) return;
-    void *arrays[] = {h->reads.a, h->col_start.a, h->col_len.a, h->col_depth.a, h->cell_off.a, h->read_off.a, h->col_reads.a,
-                      h->read_byte_off.a, h->part.a, h->next.a, h->prev.a, h->mask_from.a, h->mask_to.a, h->mcell_off.a,
-                      h->mfrom.a, h->mto.a};
-    for (size_t i = 0; i < sizeof(arrays) / sizeof(arrays[0]); i++) hmm_free_array(h, arrays[i]);
-    hmm_free_results(h);
-    free(h);
-}
-
-/* per-job view of the reads + chunk the structural code works against */
-typedef struct {
-    const mrp_chunk *chunk;
-    mrp_chunk_host ch;
-    const mrp_read *reads;
-    int64_t n_reads;
-    mrp_context *ctx;
-    mrp_batch *record;
-    int64_t n_sweeps;
-    uint32_t max_alleles;
-    int failed; /* resident path: a kernel asked for this chunk to be redone on the hashing path */
-} world;
-
-static int64_t read_byte_offset(const world *w, int32_t read, int32_t site) { /* profileSeq.c:41-47 */
-    const mrp_read *r = &w->reads[read];
-    return r->pool_offset + (int64_t) (w->ch.allele_offset[site] - w->ch.allele_offset[r->ref_start]);
-}
-
-/* begin a column; cells are appended afterwards */
-static void hmm_begin_column(mrp_hmm *h, const world *w, int32_t start, int32_t len, int32_t depth,
-                             const int32_t *col_reads) {
-    VEC_PUSH(h->col_start, start);
-    VEC_PUSH(h->col_len, len);
-    VEC_PUSH(h->col_depth, depth);
-    for (int32_t i = 0; i < depth; i++) {
-        VEC_PUSH(h->col_reads, col_reads[i]);
-        VEC_PUSH(h->read_byte_off, read_byte_offset(w, col_reads[i], start));
-    }
-    if (depth > h->max_depth) h->max_depth = depth;
-}
-static void hmm_end_column(mrp_hmm *h) {
-    VEC_PUSH(h->cell_off, h->part.n);
-    VEC_PUSH(h->read_off, h->col_reads.n);
-}
-static inline void hmm_add_cell(mrp_hmm *h, uint64_t p, uint32_t prev) {
-    VEC_PUSH(h->part, p);
-    VEC_PUSH(h->prev, prev);
-    VEC_PUSH(h->next, 0u);
-}
-static void hmm_begin_merge(mrp_hmm *h, uint64_t mask_from, uint64_t mask_to) {
-    VEC_PUSH(h->mask_from, mask_from);
-    VEC_PUSH(h->mask_to, mask_to);
-}
-static void hmm_end_merge(mrp_hmm *h) { VEC_PUSH(h->mcell_off, h->mfrom.n); }
-
-/* stRPHmm_construct hmm.c:97-133: one column, cells {1, 0} */
-static mrp_hmm *hmm_from_read(const world *w, int32_t read) {
-    mrp_hmm *h = hmm_new();
-    const mrp_read *r = &w->reads[read];
-    h->ref_start = r->ref_start;
-    h->ref_length = r->length;
-    VEC_PUSH(h->reads, read);
-    hmm_begin_column(h, w, r->ref_start, r->length, 1, &read);
-    hmm_add_cell(h, 1, 0);
-    hmm_add_cell(h, 0, 0);
-    hmm_end_column(h);
-    return h;
-}
-
-#define HMM_T mrp_hmm
-#define PFX(x) x
-#define H_NAME_READ(h) ((h)->reads.n > 0 ? (h)->reads.a[0] : -1)
-#include "rphmm_paths.inc"
-#undef HMM_T
-#undef PFX
-#undef H_NAME_READ
-
-/* ------------------------------------------------------------------------------------------ */
-/* fuse + align + cross product in one pass                                                    */
-/* ------------------------------------------------------------------------------------------ */
-/* A piece is a column of a source hmm (or a gap) restricted to a site interval; a connector is
- * the merge column that leads out of it.  stRPHmm_fuse (hmm.c:283-372) contributes ZERO
- * connectors and gap pieces, stRPHmm_alignColumns (hmm.c:374-507) the prefix/suffix gaps and,
- * through stRPColumn_split (column.c:70-130), the IDENT connectors. */
-typedef enum { CONN_NONE = 0, CONN_REAL, CONN_ZERO, CONN_IDENT } conn_kind;
-typedef struct {
-    const mrp_hmm *h; /* NULL = gap column (depth 0, one cell, partition 0) */
-    int32_t k;        /* column in h */
-    int32_t start, len;
-    conn_kind out;    /* connector to the next piece */
-} piece;
-typedef VEC(piece) piece_vec;
-
-static void pieces_of_path(const hmm_vec *tp, int32_t S, int32_t E, piece_vec *out) {
-    int32_t pos = S;
-    for (int64_t i = 0; i < tp->n; i++) {
-        const mrp_hmm *h = tp->a[i];
-        if (h->ref_start > pos) { /* gap (hmm.c:335-359, :396-424) */
-            piece g = {NULL, 0, pos, h->ref_start - pos, CONN_ZERO};
-            VEC_PUSH(*out, g);
-        }
-        const int64_t K = hmm_K(h);
-        for (int64_t k = 0; k < K; k++) {
-            piece p = {h, (int32_t) k, h->col_start.a[k], h->col_len.a[k], k + 1 < K ? CONN_REAL : CONN_ZERO};
-            VEC_PUSH(*out, p);
-        }
-        pos = h->ref_start + h->ref_length;
-    }
-    if (pos < E) { /* suffix gap (hmm.c:435-462) */
-        piece g = {NULL, 0, pos, E - pos, CONN_ZERO};
-        VEC_PUSH(*out, g);
-    }
-    out->a[out->n - 1].out = CONN_NONE;
-}
-/* cut both piece lists at the union of their boundaries (hmm.c:476-504) */
-static void align_pieces(const piece_vec *a, const piece_vec *b, piece_vec *oa, piece_vec *ob) {
-    int64_t i = 0, j = 0;
-    piece pa = a->a[0], pb = b->a[0];
-    while (1) {
-        const int32_t len = pa.len < pb.len ? pa.len : pb.len;
-        piece ca = pa, cb = pb;
-        ca.len = len; cb.len = len;
-        if (pa.len > len) ca.out = CONN_IDENT;
-        if (pb.len > len) cb.out = CONN_IDENT;
-        VEC_PUSH(*oa, ca);
-        VEC_PUSH(*ob, cb);
-        if (pa.len > len) { pa.start += len; pa.len -= len; } else { i++; if (i < a->n) pa = a->a[i]; }
-        if (pb.len > len) { pb.start += len; pb.len -= len; } else { j++; if (j < b->n) pb = b->a[j]; }
-        if (i >= a->n || j >= b->n) break;
-    }
-}
-
-static const uint64_t ZERO_PART[1] = {0};
-static inline int64_t piece_cells(const piece *p) { return p->h ? p->h->cell_off.a[p->k + 1] - p->h->cell_off.a[p->k] : 1; }
-static inline const uint64_t *piece_parts(const piece *p) { return p->h ? p->h->part.a + p->h->cell_off.a[p->k] : ZERO_PART; }
-static inline int32_t piece_depth(const piece *p) { return p->h ? p->h->col_depth.a[p->k] : 0; }
-static inline const int32_t *piece_reads(const piece *p) { return p->h ? p->h->col_reads.a + p->h->read_off.a[p->k] : NULL; }
-
-/* connector accessors */
-typedef struct {
-    uint64_t mask_from, mask_to;
-    int64_t M;
-    const uint64_t *from, *to;
-} conn_view;
-static void conn_of(const piece *p, conn_view *c) {
-    switch (p->out) {
-        case CONN_REAL: {
-            const mrp_hmm *h = p->h;
-            c->mask_from = h->mask_from.a[p->k]; c->mask_to = h->mask_to.a[p->k];
-            c->M = h->mcell_off.a[p->k + 1] - h->mcell_off.a[p->k];
-            c->from = h->mfrom.a + h->mcell_off.a[p->k]; c->to = h->mto.a + h->mcell_off.a[p->k];
-            break;
-        }
-        case CONN_IDENT: { /* column.c:86-101 */
-            c->mask_from = c->mask_to = accept_mask(piece_depth(p));
-            c->M = piece_cells(p);
-            c->from = c->to = piece_parts(p);
-            break;
-        }
-        default: /* ZERO: hmm.c:324-331 */
-            c->mask_from = c->mask_to = 0; c->M = 1; c->from = c->to = ZERO_PART;
-    }
-}
-
-/* stRPHmm_createCrossProductOfTwoAlignedHmm hmm.c:534-750 over two aligned piece lists */
-static mrp_hmm *cross_product(const world *w, const piece_vec *A, const piece_vec *B, const hmm_vec *tpA,
-                              const hmm_vec *tpB, const mrp_params *params, int32_t S, int32_t E) {
-    mrp_hmm *h = hmm_new();
-    h->ref_start = S; h->ref_length = E - S;
-    for (int64_t i = 0; i < tpA->n; i++) for (int64_t r = 0; r < tpA->a[i]->reads.n; r++) VEC_PUSH(h->reads, tpA->a[i]->reads.a[r]);
-    for (int64_t i = 0; i < tpB->n; i++) for (int64_t r = 0; r < tpB->a[i]->reads.n; r++) VEC_PUSH(h->reads, tpB->a[i]->reads.a[r]);
-    const int inv = params->include_inverted_partitions != 0;
-    const int64_t n = A->n;
-    u64map prev_to = {0}; /* toPartition -> merge index of the merge column before the current column */
-    int have_prev = 0;
-    uint64_t prev_mask_to = 0;
-    int32_t colreads[MRP_MAX_READ_PARTITIONING_DEPTH];
-    for (int64_t s = 0; s < n; s++) {
-        const piece *pa = &A->a[s], *pb = &B->a[s];
-        const int32_t d1 = piece_depth(pa), d2 = piece_depth(pb), depth = d1 + d2;
-        if (depth > MRP_MAX_READ_PARTITIONING_DEPTH) {
-            mrp_hmm_destroy(h); u64map_free(&prev_to);
-            mrp_set_error(MRP_ERR_ARG, "cross product column depth %d exceeds %d", depth, MRP_MAX_READ_PARTITIONING_DEPTH);
-            return NULL;
-        }
-        if (d1) memcpy(colreads, piece_reads(pa), sizeof(int32_t) * (size_t) d1);
-        if (d2) memcpy(colreads + d1, piece_reads(pb), sizeof(int32_t) * (size_t) d2);
-        hmm_begin_column(h, w, pa->start, pa->len, depth, colreads);
-        const int64_t C1 = piece_cells(pa), C2 = piece_cells(pb);
-        const uint64_t *P1 = piece_parts(pa), *P2 = piece_parts(pb);
-        const int64_t cell0 = h->part.n;
-        VEC_RESERVE(h->part, 2 * C1 * C2); VEC_RESERVE(h->prev, 2 * C1 * C2); VEC_RESERVE(h->next, 2 * C1 * C2);
-        if (inv) { /* hmm.c:627-655 */
-            u64map seen; u64map_init(&seen, 2 * C1 * C2);
-            for (int64_t c1 = 0; c1 < C1; c1++)
-                for (int64_t c2 = 0; c2 < C2; c2++) {
-                    const uint64_t p = merge_bits(P1[c1], P2[c2], d1);
-                    if (u64map_get(&seen, p) == U64MAP_EMPTY) {
-                        u64map_put(&seen, p, 1);
-                        hmm_add_cell(h, p, 0);
-                        if (depth > 0) {
-                            const uint64_t ip = invert_partition(p, depth);
-                            u64map_put(&seen, ip, 1);
-                            hmm_add_cell(h, ip, 0);
-                        }
-                    }
-                }
-            u64map_free(&seen);
-        } else { /* hmm.c:657-668 */
-            for (int64_t c1 = 0; c1 < C1; c1++)
-                for (int64_t c2 = 0; c2 < C2; c2++) hmm_add_cell(h, merge_bits(P1[c1], P2[c2], d1), 0);
-        }
-        hmm_end_column(h);
-        const int64_t nC = h->part.n - cell0;
-        /* link to the previous merge column (mergeColumn.c:72-79) */
-        if (have_prev) {
-            for (int64_t c = 0; c < nC; c++) {
-                const uint32_t m = u64map_get(&prev_to, h->part.a[cell0 + c] & prev_mask_to);
-                if (m == U64MAP_EMPTY) {
-                    mrp_hmm_destroy(h); u64map_free(&prev_to);
-                    mrp_set_error(MRP_ERR_LOOKUP, "cross product: cell without previous merge cell");
-                    return NULL;
-                }
-                h->prev.a[cell0 + c] = m;
-            }
-            u64map_free(&prev_to);
-            have_prev = 0;
-        }
-        if (s + 1 == n) break;
-        /* merge column hmm.c:686-740 */
-        conn_view ca, cb;
-        conn_of(pa, &ca); conn_of(pb, &cb);
-        const int32_t d1n = piece_depth(&A->a[s + 1]), d2n = piece_depth(&B->a[s + 1]);
-        const uint64_t from_mask = merge_bits(ca.mask_from, cb.mask_from, d1);
-        const uint64_t to_mask = merge_bits(ca.mask_to, cb.mask_to, d1n);
-        hmm_begin_merge(h, from_mask, to_mask);
-        const int64_t m0 = h->mfrom.n;
-        u64map from_map; u64map_init(&from_map, 2 * ca.M * cb.M);
-        u64map_init(&prev_to, 2 * ca.M * cb.M);
-        for (int64_t i = 0; i < ca.M; i++)
-            for (int64_t j = 0; j < cb.M; j++) {
-                const uint64_t from = merge_bits(ca.from[i], cb.from[j], d1);
-                const uint64_t to = merge_bits(ca.to[i], cb.to[j], d1n);
-                if (inv) {
-                    if (u64map_get(&from_map, from) == U64MAP_EMPTY) {
-                        u64map_put(&from_map, from, (uint32_t) (h->mfrom.n - m0));
-                        u64map_put(&prev_to, to, (uint32_t) (h->mfrom.n - m0));
-                        VEC_PUSH(h->mfrom, from); VEC_PUSH(h->mto, to);
-                        if (__builtin_popcountll(from_mask) > 0) {
-                            const uint64_t ifrom = from_mask & invert_partition(from, d1 + d2);
-                            const uint64_t ito = to_mask & invert_partition(to, d1n + d2n);
-                            u64map_put(&from_map, ifrom, (uint32_t) (h->mfrom.n - m0));
-                            u64map_put(&prev_to, ito, (uint32_t) (h->mfrom.n - m0));
-                            VEC_PUSH(h->mfrom, ifrom); VEC_PUSH(h->mto, ito);
-                        }
-                    }
-                } else {
-                    u64map_put(&from_map, from, (uint32_t) (h->mfrom.n - m0));
-                    u64map_put(&prev_to, to, (uint32_t) (h->mfrom.n - m0));
-                    VEC_PUSH(h->mfrom, from); VEC_PUSH(h->mto, to);
-                }
-            }
-        hmm_end_merge(h);
-        /* link this column's cells to it (mergeColumn.c:63-70) */
-        for (int64_t c = 0; c < nC; c++) {
-            const uint32_t m = u64map_get(&from_map, h->part.a[cell0 + c] & from_mask);
-            if (m == U64MAP_EMPTY) {
-                mrp_hmm_destroy(h); u64map_free(&from_map); u64map_free(&prev_to);
-                mrp_set_error(MRP_ERR_LOOKUP, "cross product: cell without next merge cell");
-                return NULL;
-            }
-            h->next.a[cell0 + c] = m;
-        }
-        u64map_free(&from_map);
-        have_prev = 1;
-        prev_mask_to = to_mask;
-    }
-    return h;
-}
-
-/* fuseTilingPath coordination.c:244-261 without a partner: concatenate hmms with ZERO connectors
- * and gap columns (hmm.c:283-372). */
-static mrp_hmm *fuse_path(const world *w, const hmm_vec *tp) {
-    if (tp->n == 1) return tp->a[0];
-    mrp_hmm *h = hmm_new();
-    h->ref_start = tp->a[0]->ref_start;
-    h->ref_length = tp->a[tp->n - 1]->ref_start + tp->a[tp->n - 1]->ref_length - h->ref_start;
-    piece_vec ps = {0};
-    pieces_of_path(tp, h->ref_start, h->ref_start + h->ref_length, &ps);
-    for (int64_t i = 0; i < tp->n; i++) for (int64_t r = 0; r < tp->a[i]->reads.n; r++) VEC_PUSH(h->reads, tp->a[i]->reads.a[r]);
-    for (int64_t s = 0; s < ps.n; s++) {
-        const piece *p = &ps.a[s];
-        hmm_begin_column(h, w, p->start, p->len, piece_depth(p), piece_reads(p));
-        const int64_t C = piece_cells(p);
-        const uint64_t *P = piece_parts(p);
-        const int real_prev = s > 0 && ps.a[s - 1].out == CONN_REAL;
-        const int real_next = p->out == CONN_REAL;
-        for (int64_t c = 0; c < C; c++) {
-            hmm_add_cell(h, P[c], real_prev ? p->h->prev.a[p->h->cell_off.a[p->k] + c] : 0);
-            h->next.a[h->next.n - 1] = real_next ? p->h->next.a[p->h->cell_off.a[p->k] + c] : 0;
-        }
-        hmm_end_column(h);
-        if (p->out == CONN_NONE) break;
-        conn_view cv; conn_of(p, &cv);
-        hmm_begin_merge(h, cv.mask_from, cv.mask_to);
-        for (int64_t m = 0; m < cv.M; m++) { VEC_PUSH(h->mfrom, cv.from[m]); VEC_PUSH(h->mto, cv.to[m]); }
-        hmm_end_merge(h);
-    }
-    free(ps.a);
-    for (int64_t i = 0; i < tp->n; i++) mrp_hmm_destroy(tp->a[i]);
-    return h;
-}
-
-/* ------------------------------------------------------------------------------------------ */
-/* sweeps on the device                                                                        */
-/* ------------------------------------------------------------------------------------------ */
-static uint32_t sweep_flags(const mrp_params *p) {
-    return (p->max_not_sum_transitions ? MRP_FLAG_MAX_NOT_SUM : 0u) |
-           (p->include_ancestor_sub_prob ? MRP_FLAG_INCLUDE_ANCESTOR_SUB_PROB : 0u);
-}
-static void hmm_alloc_results(mrp_hmm *h) {
-    hmm_free_results(h);
-    const int64_t K = hmm_K(h);
-    h->f = xmalloc(sizeof(double) * (size_t) h->part.n);
-    h->b = xmalloc(sizeof(double) * (size_t) h->part.n);
-    h->mf = xmalloc(sizeof(double) * (size_t) (h->mfrom.n + 1));
-    h->mb = xmalloc(sizeof(double) * (size_t) (h->mfrom.n + 1));
-    h->total = xmalloc(sizeof(double) * (size_t) K);
-    h->has_results = 1;
-}
-static void hmm_job(const world *w, mrp_hmm *h, uint32_t flags, mrp_hmm_job *j, int with_outputs) {
-    memset(j, 0, sizeof(*j));
-    j->chunk = w->chunk;
-    j->n_columns = (int32_t) hmm_K(h);
-    j->flags = flags;
-    j->col_ref_start = h->col_start.a; j->col_length = h->col_len.a; j->col_depth = h->col_depth.a;
-    j->col_cell_off = h->cell_off.a; j->col_read_off = h->read_off.a; j->read_byte_off = h->read_byte_off.a;
-    j->partition = h->part.a; j->mask_from = h->mask_from.a; j->mask_to = h->mask_to.a;
-    j->mcol_cell_off = h->mcell_off.a; j->merge_from = h->mfrom.a; j->merge_to = h->mto.a;
-    j->cell_next = h->next.a; j->cell_prev = h->prev.a;
-    if (with_outputs) {
-        j->cell_forward = h->f; j->cell_backward = h->b; j->merge_forward = h->mf; j->merge_backward = h->mb;
-        j->col_total = h->total; j->hmm_forward = &h->fwd; j->hmm_backward = &h->bwd;
-    }
-}
-/* stRPHmm_forwardBackward for a set of independent hmms: one device batch */
-static int sweep_many(world *w, mrp_hmm **hmms, int64_t n, const mrp_params *params) {
-    if (n == 0) return MRP_OK;
-    const uint32_t flags = sweep_flags(params);
-    mrp_hmm_job *jobs = xcalloc((size_t) n, sizeof(*jobs));
-    for (int64_t i = 0; i < n; i++) {
-        hmm_alloc_results(hmms[i]);
-        hmm_job(w, hmms[i], flags, &jobs[i], 1);
-    }
-    int rc = mrp_fb_run(w->ctx, n, jobs);
-    if (rc == MRP_OK && w->record) {
-        for (int64_t i = 0; rc == MRP_OK && i < n; i++) {
-            mrp_hmm_job dj;
-            hmm_job(w, hmms[i], flags, &dj, 0);
-            rc = mrp_batch_add(w->record, &dj);
-        }
-    }
-    w->n_sweeps += n;
-    free(jobs);
-    return rc;
-}
-
-/* ------------------------------------------------------------------------------------------ */
-/* prune (hmm.c:944-1163)                                                                      */
-/* ------------------------------------------------------------------------------------------ */
-typedef struct { int64_t idx; double key; } keyed;
-static void keyed_sort_desc(keyed *a, int64_t n, keyed *tmp) { /* stable, descending */
-    for (int64_t wdt = 1; wdt < n; wdt *= 2) {
-        for (int64_t lo = 0; lo < n; lo += 2 * wdt) {
-            const int64_t mid = lo + wdt < n ? lo + wdt : n, hi = lo + 2 * wdt < n ? lo + 2 * wdt : n;
-            int64_t i = lo, j = mid, o = lo;
-            while (i < mid && j < hi) { if (a[j].key > a[i].key) tmp[o++] = a[j++]; else tmp[o++] = a[i++]; }
-            while (i < mid) tmp[o++] = a[i++];
-            while (j < hi) tmp[o++] = a[j++];
-        }
-        memcpy(a, tmp, sizeof(keyed) * (size_t) n);
-    }
-}
-static int posterior(double f, double b, double total, double limit, double *out) { /* column.c:177-193, mergeColumn.c:129-146 */
-    const double p = exp(f + b - total);
-    if (p > limit || p < 0.0) return mrp_set_error(MRP_ERR_ARG, "ERROR: invalid prob %f", p);
-    *out = p > 1.0 ? 1.0 : p;
-    return MRP_OK;
-}
-
-int mrp_hmm_prune(mrp_hmm *h, const mrp_params *P) {
-    if (!h || !P) return mrp_set_error(MRP_ERR_ARG, "mrp_hmm_prune: NULL argument");
-    if (!h->has_results) return mrp_set_error(MRP_ERR_ARG, "mrp_hmm_prune before a forward/backward sweep");
-    const int64_t K = hmm_K(h);
-    int64_t max_c = 1, max_m = 1;
-    for (int64_t k = 0; k < K; k++) {
-        const int64_t c = h->cell_off.a[k + 1] - h->cell_off.a[k];
-        if (c > max_c) max_c = c;
-        if (k + 1 < K) { const int64_t m = h->mcell_off.a[k + 1] - h->mcell_off.a[k]; if (m > max_m) max_m = m; }
-    }
-    /* kept cells per column (old cell indices, new order) and kept-flag per merge cell */
-    int64_t *keep_off = xmalloc(sizeof(int64_t) * (size_t) (K + 1));
-    int64_t *keep_idx = xmalloc(sizeof(int64_t) * (size_t) (h->part.n + 1));
-    uint8_t *keep_m = xcalloc((size_t) (h->mfrom.n + 1), 1);
-    keyed *ka = xmalloc(sizeof(keyed) * (size_t) (max_c > max_m ? max_c : max_m));
-    keyed *kt = xmalloc(sizeof(keyed) * (size_t) (max_c > max_m ? max_c : max_m));
-    uint8_t *chosen = xmalloc((size_t) max_m);
-    int rc = MRP_OK;
-    /* stRPHmm_pruneForwards hmm.c:1049-1109 */
-    keep_off[0] = 0;
-    for (int64_t k = 0; k < K && rc == MRP_OK; k++) {
-        const int64_t c0 = h->cell_off.a[k], nc = h->cell_off.a[k + 1] - c0;
-        int64_t n = 0;
-        for (int64_t c = 0; c < nc; c++) { /* getLinkedCells :1021-1047 */
-            if (k > 0 && !keep_m[h->mcell_off.a[k - 1] + h->prev.a[c0 + c]]) continue;
-            ka[n].idx = c;
-            rc = posterior(h->f[c0 + c], h->b[c0 + c], h->total[k], 1.1, &ka[n].key);
-            if (rc != MRP_OK) break;
-            n++;
-        }
-        if (rc != MRP_OK) break;
-        keyed_sort_desc(ka, n, kt);
-        while (n > P->min_partitions_in_a_column &&
-               (n > P->max_partitions_in_a_column || ka[n - 1].key < P->min_posterior_probability_for_partition))
-            n--;
-        for (int64_t i = 0; i < n; i++) keep_idx[keep_off[k] + i] = ka[i].idx;
-        keep_off[k + 1] = keep_off[k] + n;
-        if (k + 1 == K) break;
-        /* getLinkedMergeCells :989-1004, sort + shrink :1088-1101 */
-        const int64_t m0 = h->mcell_off.a[k], nm = h->mcell_off.a[k + 1] - m0;
-        memset(chosen, 0, (size_t) nm);
-        int64_t mn = 0;
-        for (int64_t i = 0; i < n; i++) {
-            const uint32_t m = h->next.a[c0 + keep_idx[keep_off[k] + i]];
-            if (!chosen[m]) {
-                chosen[m] = 1;
-                ka[mn].idx = m;
-                rc = posterior(h->mf[m0 + m], h->mb[m0 + m], h->total[k + 1], 1.001, &ka[mn].key);
-                if (rc != MRP_OK) break;
-                mn++;
-            }
-        }
-        if (rc != MRP_OK) break;
-        keyed_sort_desc(ka, mn, kt);
-        while (mn > P->min_partitions_in_a_column &&
-               (mn > P->max_partitions_in_a_column || ka[mn - 1].key < P->min_posterior_probability_for_partition))
-            mn--;
-        for (int64_t i = 0; i < mn; i++) keep_m[m0 + ka[i].idx] = 1;
-    }
-    /* stRPHmm_pruneBackwards hmm.c:1111-1158 */
-    for (int64_t k = K - 1; k >= 0 && rc == MRP_OK; k--) {
-        const int64_t c0 = h->cell_off.a[k];
-        int64_t n = 0;
-        for (int64_t i = keep_off[k]; i < keep_off[k + 1]; i++) {
-            const int64_t c = keep_idx[i];
-            if (k + 1 < K && !keep_m[h->mcell_off.a[k] + h->next.a[c0 + c]]) continue;
-            keep_idx[keep_off[k] + n++] = c; /* order kept: the re-sort of an already sorted list is a no-op */
-        }
-        /* entries past the new length are marked unused */
-        for (int64_t i = keep_off[k] + n; i < keep_off[k + 1]; i++) keep_idx[i] = -1;
-        if (k == 0) break;
-        const int64_t m0 = h->mcell_off.a[k - 1], nm = h->mcell_off.a[k] - m0;
-        memset(chosen, 0, (size_t) nm);
-        for (int64_t i = 0; i < n; i++) chosen[h->prev.a[c0 + keep_idx[keep_off[k] + i]]] = 1;
-        for (int64_t m = 0; m < nm; m++) keep_m[m0 + m] = keep_m[m0 + m] && chosen[m];
-    }
-    if (rc == MRP_OK) {
-        /* rebuild compactly: merge cells keep their relative order (filterMergeCells :964-987),
-         * cells are relinked in sorted order (relinkCells :1006-1019) */
-        uint32_t *remap = xmalloc(sizeof(uint32_t) * (size_t) (h->mfrom.n + 1));
-        int64_t nm_new = 0;
-        int64_t *new_moff = xmalloc(sizeof(int64_t) * (size_t) K);
-        new_moff[0] = 0;
-        for (int64_t k = 0; k + 1 < K; k++) {
-            const int64_t m0 = h->mcell_off.a[k], nm = h->mcell_off.a[k + 1] - m0;
-            uint32_t local = 0;
-            for (int64_t m = 0; m < nm; m++) {
-                if (keep_m[m0 + m]) {
-                    remap[m0 + m] = local++;
-                    h->mfrom.a[nm_new] = h->mfrom.a[m0 + m];
-                    h->mto.a[nm_new] = h->mto.a[m0 + m];
-                    h->mf[nm_new] = h->mf[m0 + m];
-                    h->mb[nm_new] = h->mb[m0 + m];
-                    nm_new++;
-                } else remap[m0 + m] = U64MAP_EMPTY;
-            }
-            new_moff[k + 1] = nm_new;
-        }
-        const int64_t nC_old = h->part.n;
-        uint64_t *np = xmalloc(sizeof(uint64_t) * (size_t) (nC_old + 1));
-        uint32_t *nn = xmalloc(sizeof(uint32_t) * (size_t) (nC_old + 1)), *npv = xmalloc(sizeof(uint32_t) * (size_t) (nC_old + 1));
-        double *nf = xmalloc(sizeof(double) * (size_t) (nC_old + 1)), *nb = xmalloc(sizeof(double) * (size_t) (nC_old + 1));
-        int64_t o = 0;
-        int64_t *new_coff = xmalloc(sizeof(int64_t) * (size_t) (K + 1));
-        new_coff[0] = 0;
-        for (int64_t k = 0; k < K; k++) {
-            const int64_t c0 = h->cell_off.a[k];
-            for (int64_t i = keep_off[k]; i < keep_off[k + 1]; i++) {
-                const int64_t c = keep_idx[i];
-                if (c < 0) break;
-                np[o] = h->part.a[c0 + c];
-                nn[o] = k + 1 < K ? remap[h->mcell_off.a[k] + h->next.a[c0 + c]] : 0;
-                npv[o] = k > 0 ? remap[h->mcell_off.a[k - 1] + h->prev.a[c0 + c]] : 0;
-                nf[o] = h->f[c0 + c]; nb[o] = h->b[c0 + c];
-                o++;
-            }
-            new_coff[k + 1] = o;
-        }
-        memcpy(h->part.a, np, sizeof(uint64_t) * (size_t) o);
-        memcpy(h->next.a, nn, sizeof(uint32_t) * (size_t) o);
-        memcpy(h->prev.a, npv, sizeof(uint32_t) * (size_t) o);
-        memcpy(h->f, nf, sizeof(double) * (size_t) o);
-        memcpy(h->b, nb, sizeof(double) * (size_t) o);
-        h->part.n = h->next.n = h->prev.n = o;
-        h->mfrom.n = h->mto.n = nm_new;
-        memcpy(h->cell_off.a, new_coff, sizeof(int64_t) * (size_t) (K + 1));
-        memcpy(h->mcell_off.a, new_moff, sizeof(int64_t) * (size_t) K);
-        free(remap); free(new_moff); free(np); free(nn); free(npv); free(nf); free(nb); free(new_coff);
-    }
-    free(keep_off); free(keep_idx); free(keep_m); free(ka); free(kt); free(chosen);
-    return rc;
-}
-
-/* ------------------------------------------------------------------------------------------ */
-/* coordination.c                                                                              */
-/* ------------------------------------------------------------------------------------------ */
-/* mergeTwoTilingPaths coordination.c:263-339.  All cross products of the call are swept in one
- * device batch (the components are independent), then pruned. */
-static int merge_two_tiling_paths(world *w, hmm_vec *tp1, hmm_vec *tp2, const mrp_params *params, hmm_vec **out) {
-    comp_vec comps = overlapping_components(w, tp1, tp2);
-    free(tp1->a); free(tp1); free(tp2->a); free(tp2);
-    hmm_vec *res = xcalloc(1, sizeof(*res));
-    hmm_vec crossed = {0};
-    int rc = MRP_OK;
-    for (int64_t i = 0; i < comps.n; i++) {
-        component *comp = comps.a[i];
-        if (rc == MRP_OK) {
-            path_vec sub = tiling_paths_from(w, comp->members.a, comp->members.n);
-            if (sub.n == 2) {
-                hmm_vec *a = sub.a[0], *b = sub.a[1];
-                int32_t S = a->a[0]->ref_start < b->a[0]->ref_start ? a->a[0]->ref_start : b->a[0]->ref_start;
-                int32_t Ea = a->a[a->n - 1]->ref_start + a->a[a->n - 1]->ref_length;
-                int32_t Eb = b->a[b->n - 1]->ref_start + b->a[b->n - 1]->ref_length;
-                int32_t E = Ea > Eb ? Ea : Eb;
-                piece_vec pa = {0}, pb = {0}, qa = {0}, qb = {0};
-                pieces_of_path(a, S, E, &pa);
-                pieces_of_path(b, S, E, &pb);
-                align_pieces(&pa, &pb, &qa, &qb);
-                mrp_hmm *x = cross_product(w, &qa, &qb, a, b, params, S, E);
-                free(pa.a); free(pb.a); free(qa.a); free(qb.a);
-                for (int64_t t = 0; t < a->n; t++) mrp_hmm_destroy(a->a[t]);
-                for (int64_t t = 0; t < b->n; t++) mrp_hmm_destroy(b->a[t]);
-                if (x) { VEC_PUSH(crossed, x); VEC_PUSH(*res, x); } else rc = MRP_ERR_ARG;
-            } else if (sub.n == 1 && sub.a[0]->n == 1) {
-                VEC_PUSH(*res, sub.a[0]->a[0]);
-            } else {
-                rc = mrp_set_error(MRP_ERR_ARG, "overlap component with %lld tiling paths", (long long) sub.n);
-            }
-            for (int64_t t = 0; t < sub.n; t++) { free(sub.a[t]->a); free(sub.a[t]); }
-            free(sub.a);
-        }
-        free(comp->members.a); free(comp);
-    }
-    free(comps.a);
-    if (rc == MRP_OK) rc = sweep_many(w, crossed.a, crossed.n, params);       /* coordination.c:312 */
-    for (int64_t i = 0; rc == MRP_OK && i < crossed.n; i++) rc = mrp_hmm_prune(crossed.a[i], params); /* :313 */
-    free(crossed.a);
-    if (rc == MRP_OK) sort_hmms(w, res->a, res->n);                           /* :336 */
-    *out = res;
-    return rc;
-}
-
-static void free_path(hmm_vec *tp, int destroy_hmms) {
-    if (!tp) return;
-    if (destroy_hmms) for (int64_t i = 0; i < tp->n; i++) mrp_hmm_destroy(tp->a[i]);
-    free(tp->a); free(tp);
-}
-
-/* mergeTilingPaths coordination.c:341-409 */
-static int merge_tiling_paths(world *w, hmm_vec **paths, int64_t n, const mrp_params *params, hmm_vec **out) {
-    if (n == 0) { *out = xcalloc(1, sizeof(hmm_vec)); return MRP_OK; }
-    if (n == 1) { *out = paths[0]; return MRP_OK; }
-    hmm_vec *tp1 = NULL, *tp2 = NULL;
-    int rc = MRP_OK;
-    if (n > 2) {
-        rc = merge_tiling_paths(w, paths, n / 2, params, &tp1);
-        if (rc == MRP_OK) rc = merge_tiling_paths(w, paths + n / 2, n - n / 2, params, &tp2);
-        else for (int64_t i = n / 2; i < n; i++) free_path(paths[i], 1);
-        if (rc != MRP_OK) { free_path(tp1, 1); free_path(tp2, 1); *out = NULL; return rc; }
-    } else {
-        tp1 = paths[0]; tp2 = paths[1];
-    }
-    return merge_two_tiling_paths(w, tp1, tp2, params, out);
-}
-
-static path_vec tiling_paths2(const world *w, const int32_t *read_index, int64_t n) { /* coordination.c:224-242 */
-    mrp_hmm **hmms = xmalloc(sizeof(*hmms) * (size_t) (n + 1));
-    for (int64_t i = 0; i < n; i++) hmms[i] = hmm_from_read(w, read_index[i]);
-    path_vec paths = tiling_paths_from(w, hmms, n);
-    free(hmms);
-    return paths;
-}
-
-static int get_rp_hmms(world *w, const int32_t *read_index, int64_t n, const mrp_params *params, hmm_vec **out) {
-    path_vec paths = tiling_paths2(w, read_index, n); /* coordination.c:498 */
-    if (paths.n > MRP_MAX_READ_PARTITIONING_DEPTH || paths.n > params->max_coverage_depth) { /* :500-504 */
-        for (int64_t i = 0; i < paths.n; i++) free_path(paths.a[i], 1);
-        const int64_t np = paths.n;
-        free(paths.a);
-        *out = NULL;
-        return mrp_set_error(MRP_ERR_ARG,
-                             "Coverage depth: read depth of %lld exceeds hard maximum of %d with configured maximum of %lld",
-                             (long long) np, MRP_MAX_READ_PARTITIONING_DEPTH, (long long) params->max_coverage_depth);
-    }
-    int rc = merge_tiling_paths(w, paths.a, paths.n, params, out);
-    free(paths.a);
-    return rc;
-}
-
-static int check_reads(const world *w, const mrp_read *reads, int64_t n) {
-    for (int64_t i = 0; i < n; i++) {
-        const mrp_read *r = &reads[i];
-        if (!r->name || r->length < 1 || r->ref_start < 0 || (int64_t) r->ref_start + r->length > w->ch.n_sites)
-            return mrp_set_error(MRP_ERR_ARG, "read %lld: bad interval [%d,+%d)", (long long) i, r->ref_start, r->length);
-        const int64_t nb = w->ch.allele_offset[r->ref_start + r->length] - w->ch.allele_offset[r->ref_start];
-        if (r->pool_offset < 0 || r->pool_offset + nb > w->ch.pool_bytes)
-            return mrp_set_error(MRP_ERR_ARG, "read %lld: profile bytes outside the pool", (long long) i);
-    }
-    return MRP_OK;
-}
-static int world_init(world *w, mrp_context *ctx, const mrp_chunk *chunk, const mrp_read *reads, int64_t n_reads,
-                      mrp_batch *record) {
-    if (!ctx || !chunk || (n_reads > 0 && !reads)) return mrp_set_error(MRP_ERR_ARG, "NULL argument");
-    if (mrp_context_device(mrp_chunk_context(chunk)) != mrp_context_device(ctx)) return mrp_set_error(MRP_ERR_ARG, "chunk lives on a different device");
-    memset(w, 0, sizeof(*w));
-    w->chunk = chunk; w->reads = reads; w->n_reads = n_reads; w->ctx = ctx; w->record = record;
-    mrp_chunk_host_view(chunk, &w->ch);
-    w->max_alleles = 1;
-    for (int64_t i = 0; i < w->ch.n_sites; i++) if (w->ch.allele_number[i] > w->max_alleles) w->max_alleles = w->ch.allele_number[i];
-    return check_reads(w, reads, n_reads);
-}
-
-int mrp_get_rp_hmms(mrp_context *ctx, const mrp_chunk *chunk, const mrp_read *reads, const int32_t *read_index,
-                    int64_t n, const mrp_params *params, mrp_batch *record, mrp_hmm ***hmms_out, int64_t *n_out) {
-    if (!params || !hmms_out || !n_out || n < 0 || (n > 0 && !read_index)) return mrp_set_error(MRP_ERR_ARG, "mrp_get_rp_hmms: bad arguments");
-    int64_t max_idx = -1;
-    for (int64_t i = 0; i < n; i++) { if (read_index[i] < 0) return mrp_set_error(MRP_ERR_ARG, "negative read index"); if (read_index[i] > max_idx) max_idx = read_index[i]; }
-    world w;
-    int rc = world_init(&w, ctx, chunk, reads, max_idx + 1, record);
-    if (rc != MRP_OK) return rc;
-    hmm_vec *tp = NULL;
-    rc = get_rp_hmms(&w, read_index, n, params, &tp);
-    if (rc != MRP_OK) { free_path(tp, 1); return rc; }
-    *n_out = tp->n;
-    *hmms_out = tp->a ? tp->a : xmalloc(sizeof(mrp_hmm *));
-    free(tp);
-    return MRP_OK;
-}
-
-int mrp_hmm_view(const mrp_hmm *hmm, mrp_hmm_job *view, const int32_t **col_reads_out, int32_t *ref_start,
-                 int32_t *ref_length) {
-    if (!hmm || !view) return mrp_set_error(MRP_ERR_ARG, "mrp_hmm_view: NULL argument");
-    world w; memset(&w, 0, sizeof(w));
-    hmm_job(&w, (mrp_hmm *) hmm, 0, view, hmm->has_results);
-    if (col_reads_out) *col_reads_out = hmm->col_reads.a;
-    if (ref_start) *ref_start = hmm->ref_start;
-    if (ref_length) *ref_length = hmm->ref_length;
-    return MRP_OK;
-}
-
-int mrp_hmm_forward_backward(mrp_context *ctx, const mrp_chunk *chunk, mrp_hmm *hmm, const mrp_params *params,
-                             mrp_batch *record) {
-    if (!hmm || !params) return mrp_set_error(MRP_ERR_ARG, "mrp_hmm_forward_backward: NULL argument");
-    world w;
-    int rc = world_init(&w, ctx, chunk, NULL, 0, record);
-    if (rc != MRP_OK) return rc;
-    return sweep_many(&w, &hmm, 1, params);
-}
-
-/* stRPHmm_forwardTraceBack hmm.c:165-219 */
-int mrp_hmm_forward_trace_back(const mrp_hmm *h, int32_t *path) {
-    if (!h || !path) return mrp_set_error(MRP_ERR_ARG, "mrp_hmm_forward_trace_back: NULL argument");
-    if (!h->has_results) return mrp_set_error(MRP_ERR_ARG, "trace back before a forward/backward sweep");
-    const int64_t K = hmm_K(h);
-    int64_t c0 = h->cell_off.a[K - 1], nc = h->cell_off.a[K] - c0;
-    int64_t best = 0;
-    double max_prob = h->f[c0];
-    for (int64_t c = 1; c < nc; c++) if (h->f[c0 + c] > max_prob) { max_prob = h->f[c0 + c]; best = c; }
-    path[K - 1] = (int32_t) best;
-    for (int64_t k = K - 1; k > 0; k--) {
-        const uint32_t m = h->prev.a[h->cell_off.a[k] + path[k]];
-        c0 = h->cell_off.a[k - 1]; nc = h->cell_off.a[k] - c0;
-        best = -1; max_prob = -INFINITY;
-        for (int64_t c = 0; c < nc; c++)
-            if (h->next.a[c0 + c] == m && h->f[c0 + c] > max_prob) { max_prob = h->f[c0 + c]; best = c; }
-        if (best < 0) return mrp_set_error(MRP_ERR_LOOKUP, "trace back: no cell feeds the chosen merge cell in column %lld", (long long) (k - 1));
-        path[k - 1] = (int32_t) best;
-    }
-    return MRP_OK;
-}
-
-/* ------------------------------------------------------------------------------------------ */
-/* split (hmm.c:1192-1383)                                                                      */
-/* ------------------------------------------------------------------------------------------ */
-/* columns [k0, k1) of src appended to dst; the first one may start later, the last one end earlier (stRPColumn_split
- * column.c:86-101 leaves both halves with the same cells and reads) */
-static void hmm_append_columns(const world *w, mrp_hmm *dst, const mrp_hmm *src, int64_t k0, int64_t k1, int32_t first_start,
-                               int32_t last_end) {
-    for (int64_t k = k0; k < k1; k++) {
-        int32_t start = src->col_start.a[k], end = start + src->col_len.a[k];
-        if (k == k0 && first_start > start) start = first_start;
-        if (k == k1 - 1 && last_end < end) end = last_end;
-        hmm_begin_column(dst, w, start, end - start, src->col_depth.a[k], src->col_reads.a + src->read_off.a[k]);
-        for (int64_t c = src->cell_off.a[k]; c < src->cell_off.a[k + 1]; c++) {
-            hmm_add_cell(dst, src->part.a[c], k == k0 ? 0u : src->prev.a[c]);
-            dst->next.a[dst->next.n - 1] = k == k1 - 1 ? 0u : src->next.a[c];
-        }
-        hmm_end_column(dst);
-        if (k + 1 < k1) {
-            hmm_begin_merge(dst, src->mask_from.a[k], src->mask_to.a[k]);
-            for (int64_t m = src->mcell_off.a[k]; m < src->mcell_off.a[k + 1]; m++) { VEC_PUSH(dst->mfrom, src->mfrom.a[m]); VEC_PUSH(dst->mto, src->mto.a[m]); }
-            hmm_end_merge(dst);
-        }
-    }
-}
-/* h takes the arrays of `from` (which is consumed); h's own bookkeeping as an allocation stays */
-static void hmm_take(mrp_hmm *h, mrp_hmm *from) {
-    void *arrays[] = {h->reads.a, h->col_start.a, h->col_len.a, h->col_depth.a, h->cell_off.a, h->read_off.a, h->col_reads.a,
-                      h->read_byte_off.a, h->part.a, h->next.a, h->prev.a, h->mask_from.a, h->mask_to.a, h->mcell_off.a,
-                      h->mfrom.a, h->mto.a};
-    for (size_t i = 0; i < sizeof(arrays) / sizeof(arrays[0]); i++) hmm_free_array(h, arrays[i]);
-    hmm_free_results(h);
-    h->ref_start = from->ref_start; h->ref_length = from->ref_length; h->max_depth = from->max_depth;
-    h->reads = from->reads; h->col_start = from->col_start; h->col_len = from->col_len; h->col_depth = from->col_depth;
-    h->cell_off = from->cell_off; h->read_off = from->read_off; h->col_reads = from->col_reads; h->read_byte_off = from->read_byte_off;
-    h->part = from->part; h->next = from->next; h->prev = from->prev; h->mask_from = from->mask_from; h->mask_to = from->mask_to;
-    h->mcell_off = from->mcell_off; h->mfrom = from->mfrom; h->mto = from->mto;
-    free(from);
-}
-/* stRPHmm_split hmm.c:1231-1300: h keeps [refStart, split_point), the returned hmm holds the rest.  The column that
- * contains the split point is cut in two (both halves keep its cells); the merge column in front of the suffix goes. */
-static mrp_hmm *hmm_split(const world *w, mrp_hmm *h, int32_t sp) {
-    const int64_t K = hmm_K(h);
-    int64_t ks = 0; /* getColumn :1192-1209 */
-    while (ks < K && sp >= h->col_start.a[ks] + h->col_len.a[ks]) ks++;
-    const int inside = sp > h->col_start.a[ks];
-    mrp_hmm *L = hmm_new(), *R = hmm_new();
-    for (int64_t i = 0; i < h->reads.n; i++) { /* :1247-1262 */
-        const mrp_read *r = &w->reads[h->reads.a[i]];
-        if (r->ref_start < sp) VEC_PUSH(L->reads, h->reads.a[i]);
-        if (r->ref_start + r->length > sp) VEC_PUSH(R->reads, h->reads.a[i]);
-    }
-    hmm_append_columns(w, L, h, 0, inside ? ks + 1 : ks, h->col_start.a[0], sp);
-    hmm_append_columns(w, R, h, ks, K, sp, h->col_start.a[K - 1] + h->col_len.a[K - 1]);
-    L->ref_start = h->ref_start; L->ref_length = sp - h->ref_start;
-    R->ref_start = sp; R->ref_length = h->ref_start + h->ref_length - sp;
-    hmm_take(h, L);
-    return R;
-}
-static int world_host(world *w, const mrp_chunk *chunk, const mrp_read *reads, int64_t n_reads) {
-    if (!chunk || (n_reads > 0 && !reads)) return mrp_set_error(MRP_ERR_ARG, "NULL argument");
-    memset(w, 0, sizeof(*w));
-    w->chunk = chunk; w->reads = reads; w->n_reads = n_reads;
-    mrp_chunk_host_view(chunk, &w->ch);
-    return check_reads(w, reads, n_reads);
-}
-static int hmm_reads_known(const mrp_hmm *h, int64_t n_reads) {
-    for (int64_t i = 0; i < h->reads.n; i++) if (h->reads.a[i] < 0 || h->reads.a[i] >= n_reads) return 0;
-    return 1;
-}
-int mrp_hmm_split(const mrp_chunk *chunk, const mrp_read *reads, int64_t n_reads, mrp_hmm *hmm, int32_t split_point,
-                  mrp_hmm **suffix_out) {
-    if (!hmm || !suffix_out) return mrp_set_error(MRP_ERR_ARG, "mrp_hmm_split: bad arguments");
-    if (split_point <= hmm->ref_start) return mrp_set_error(MRP_ERR_ARG, "The split point is at or before the start of the reference interval");
-    if (split_point >= hmm->ref_start + hmm->ref_length) return mrp_set_error(MRP_ERR_ARG, "The split point is after the last position of the reference interval");
-    world w;
-    int rc = world_host(&w, chunk, reads, n_reads);
-    if (rc != MRP_OK) return rc;
-    if (!hmm_reads_known(hmm, n_reads)) return mrp_set_error(MRP_ERR_ARG, "mrp_hmm_split: the hmm names reads beyond n_reads");
-    *suffix_out = hmm_split(&w, hmm, split_point);
-    return MRP_OK;
-}
-
-static void genome_fragment(const world *w, mrp_phase_result *g, const mrp_hmm *h, const uint64_t *chosen, int64_t max_iterations);
-static mrp_phase_result *result_new(int32_t ref_start, int32_t length, int64_t n_reads);
-/* sitesLinkageIsWellSupported hmm.c:1302-1320: reads shared by the columns that hold the two sites */
-static int sites_linkage_well_supported(const mrp_hmm *h, const mrp_params *params, int32_t left, int32_t right) {
-    const int64_t K = hmm_K(h);
-    int64_t kl = 0, kr;
-    while (kl < K - 1 && left >= h->col_start.a[kl] + h->col_len.a[kl]) kl++;
-    kr = kl;
-    while (kr < K - 1 && right >= h->col_start.a[kr] + h->col_len.a[kr]) kr++;
-    const int32_t *a = h->col_reads.a + h->read_off.a[kl], *b = h->col_reads.a + h->read_off.a[kr];
-    int64_t common = 0;
-    for (int32_t i = 0; i < h->col_depth.a[kl]; i++)
-        for (int32_t j = 0; j < h->col_depth.a[kr]; j++)
-            if (a[i] == b[j]) { common++; break; }
-    return common >= params->min_read_coverage_to_support_phasing_between_heterozygous_sites;
-}
-/* stRPHMM_splitWherePhasingIsUncertain hmm.c:1322-1383: sweep, trace back, predicted haplotypes; between two consecutive
- * heterozygous sites that too few reads span, the hmm is cut half way.  The input hmm becomes the first of the list. */
-int mrp_hmm_split_where_phasing_is_uncertain(mrp_context *ctx, const mrp_chunk *chunk, const mrp_read *reads, int64_t n_reads,
-                                             mrp_hmm *hmm, const mrp_params *params, mrp_hmm ***hmms_out, int64_t *n_out) {
-    if (!hmm || !params || !hmms_out || !n_out) return mrp_set_error(MRP_ERR_ARG, "mrp_hmm_split_where_phasing_is_uncertain: bad arguments");
-    world w;
-    int rc = world_init(&w, ctx, chunk, reads, n_reads, NULL);
-    if (rc != MRP_OK) return rc;
-    if (!hmm_reads_known(hmm, n_reads)) return mrp_set_error(MRP_ERR_ARG, "the hmm names reads beyond n_reads");
-    mrp_hmm *one = hmm;
-    rc = sweep_many(&w, &one, 1, params);
-    if (rc != MRP_OK) return rc;
-    const int64_t K = hmm_K(hmm);
-    int32_t *path = xmalloc(sizeof(int32_t) * (size_t) K);
-    rc = mrp_hmm_forward_trace_back(hmm, path);
-    if (rc != MRP_OK) { free(path); return rc; }
-    uint64_t *chosen = xmalloc(sizeof(uint64_t) * (size_t) K);
-    for (int64_t k = 0; k < K; k++) chosen[k] = hmm->part.a[hmm->cell_off.a[k] + path[k]];
-    mrp_phase_result *g = result_new(hmm->ref_start, hmm->ref_length, n_reads);
-    genome_fragment(&w, g, hmm, chosen, 0); /* stGenomeFragment_construct only, :1330 */
-    hmm_vec out = {0};
-    int32_t prev_het = -1;
-    for (int32_t i = 0; i < g->length; i++) {
-        if (g->haplotype_string1[i] == g->haplotype_string2[i]) continue;
-        const int32_t site = g->ref_start + i;
-        if (prev_het >= 0 && !sites_linkage_well_supported(hmm, params, prev_het, site)) {
-            mrp_hmm *right = hmm_split(&w, hmm, prev_het + (site - prev_het + 1) / 2); /* :1361 */
-            VEC_PUSH(out, hmm);
-            hmm = right;
-        }
-        prev_het = site;
-    }
-    VEC_PUSH(out, hmm);
-    free(path); free(chosen); mrp_phase_result_destroy(g);
-    *hmms_out = out.a;
-    *n_out = out.n;
-    return MRP_OK;
-}
-
-/* ------------------------------------------------------------------------------------------ */
-/* genome fragment (emissions.c:246-343, genomeFragment.c)                                     */
-/* ------------------------------------------------------------------------------------------ */
-static mrp_phase_result *result_new(int32_t ref_start, int32_t length, int64_t n_reads) {
-    mrp_phase_result *r = xcalloc(1, sizeof(*r));
-    r->ref_start = ref_start; r->length = length;
-    const size_t n = (size_t) length;
-    r->genotype_string = xcalloc(n, sizeof(uint64_t)); r->haplotype_string1 = xcalloc(n, sizeof(uint64_t));
-    r->haplotype_string2 = xcalloc(n, sizeof(uint64_t)); r->ancestor_string = xcalloc(n, sizeof(uint64_t));
-    r->reads_supporting_haplotype1 = xcalloc(n, sizeof(uint64_t)); r->reads_supporting_haplotype2 = xcalloc(n, sizeof(uint64_t));
-    r->genotype_probs = xcalloc(n, sizeof(float)); r->haplotype_probs1 = xcalloc(n, sizeof(float));
-    r->haplotype_probs2 = xcalloc(n, sizeof(float));
-    /* (a read that inconsistent columns put on both sides sits in both lists and may be moved into a list that already holds it) */
-    r->reads1 = xcalloc(2 * (size_t) n_reads + 2, sizeof(int32_t)); r->reads2 = xcalloc(2 * (size_t) n_reads + 2, sizeof(int32_t));
-    return r;
-}
-void mrp_phase_result_destroy(mrp_phase_result *r) {
-    if (!r) return;
-    free(r->genotype_string); free(r->haplotype_string1); free(r->haplotype_string2); free(r->ancestor_string);
-    free(r->reads_supporting_haplotype1); free(r->reads_supporting_haplotype2); free(r->genotype_probs);
-    free(r->haplotype_probs1); free(r->haplotype_probs2); free(r->reads1); free(r->reads2);
-    free(r);
-}
-/* fillInPredictedGenome emissions.c:323-343 for column k with the given partition.  The allele
- * costs are the same integers getLogProbOfAllele returns (sum of the bytes of the reads in the
- * partition), summed directly. */
-static void fill_in_predicted_genome(const world *w, mrp_phase_result *g, const mrp_hmm *h, int64_t k, uint64_t partition, uint64_t *scratch) {
-    const int32_t depth = h->col_depth.a[k];
-    const int64_t *off = h->read_byte_off.a + h->read_off.a[k];
-    const int32_t start = h->col_start.a[k];
-    const uint32_t first_allele = w->ch.allele_offset[start];
-    uint64_t *h1 = scratch, *h2 = h1 + w->max_alleles, *a1 = h2 + w->max_alleles, *a2 = a1 + w->max_alleles; /* [4 * max_alleles] */
-    for (int32_t s = 0; s < h->col_len.a[k]; s++) {
-        const int32_t site = start + s;
-        const uint32_t A = w->ch.allele_number[site], so = w->ch.allele_offset[site] - first_allele;
-        const uint16_t *sub = w->ch.sub + w->ch.sub_offset[site], *prior = w->ch.prior + w->ch.allele_offset[site];
-        if (A == 2) { /* the common case: both bytes of a read together, no branch on the partition bit */
-            uint64_t t0 = 0, t1 = 0, x0 = 0, x1 = 0; /* totals over the column's reads, and over those in the partition */
-            for (int32_t i = 0; i < depth; i++) {
-                const uint8_t *b = w->ch.pool + off[i] + so;
-                const uint64_t in = 0 - ((partition >> i) & 1);
-                t0 += b[0]; t1 += b[1];
-                x0 += b[0] & in; x1 += b[1] & in;
-            }
-            h1[0] = x0; h1[1] = x1; h2[0] = t0 - x0; h2[1] = t1 - x1;
-        } else {
-            for (uint32_t a = 0; a < A; a++) { h1[a] = 0; h2[a] = 0; }
-            for (int32_t i = 0; i < depth; i++) {
-                const uint8_t *b = w->ch.pool + off[i] + so;
-                uint64_t *dst = ((partition >> i) & 1) ? h1 : h2;
-                for (uint32_t a = 0; a < A; a++) dst[a] += b[a];
-            }
-        }
-        for (uint32_t i = 0; i < A; i++) { /* ancestorHapProbabilities emissions.c:156-172 */
-            uint64_t x = h1[0] + sub[i * A], y = h2[0] + sub[i * A];
-            for (uint32_t q = 1; q < A; q++) {
-                if (h1[q] + sub[i * A + q] < x) x = h1[q] + sub[i * A + q];
-                if (h2[q] + sub[i * A + q] < y) y = h2[q] + sub[i * A + q];
-            }
-            a1[i] = x; a2[i] = y;
-        }
-        uint64_t best = a1[0] + a2[0] + prior[0], anc = 0; /* :283-292 */
-        for (uint32_t i = 1; i < A; i++) {
-            const uint64_t j = a1[i] + a2[i] + prior[i];
-            if (j < best) { best = j; anc = i; }
-        }
-        uint64_t hap1 = 0, hap2 = 0, m1 = h1[0] + sub[anc * A], m2 = h2[0] + sub[anc * A]; /* getMLAllele :246-261 */
-        for (uint32_t i = 1; i < A; i++) {
-            if (h1[i] + sub[anc * A + i] < m1) { m1 = h1[i] + sub[anc * A + i]; hap1 = i; }
-            if (h2[i] + sub[anc * A + i] < m2) { m2 = h2[i] + sub[anc * A + i]; hap2 = i; }
-        }
-        const int64_t q = site - g->ref_start;
-        g->ancestor_string[q] = anc;
-        g->haplotype_string1[q] = hap1;
-        g->haplotype_string2[q] = hap2;
-        g->genotype_string[q] = hap1 < hap2 ? hap1 * A + hap2 : hap2 * A + hap1;
-        g->genotype_probs[q] = -((float) best);
-        g->haplotype_probs1[q] = -(float) h1[hap1];
-        g->haplotype_probs2[q] = -(float) h2[hap2];
-        g->reads_supporting_haplotype1[q] = (uint64_t) __builtin_popcountll(partition);
-        g->reads_supporting_haplotype2[q] = (uint64_t) depth - (uint64_t) __builtin_popcountll(partition);
-    }
-}
-/* getLogProbOfReadGivenHaplotype genomeFragment.c:71-89, for both haplotypes in one walk over the read's sites: *x for hap1,
- * *y for hap2 (each sum in site order, then divided by PROFILE_PROB_SCALAR inc/margin.h:189) */
-static void read_log_prob2(const world *w, const uint64_t *hap1, const uint64_t *hap2, int32_t start, int32_t length, int32_t read, double *x, double *y) {
-    const mrp_read *r = &w->reads[read];
-    double t1 = 0.0, t2 = 0.0;
-    const uint32_t first = w->ch.allele_offset[r->ref_start];
-    int32_t lo = start - r->ref_start, hi = start + length - r->ref_start;
-    if (lo < 0) lo = 0;
-    if (hi > r->length) hi = r->length;
-    const uint8_t *pool = w->ch.pool + r->pool_offset;
-    const uint32_t *ao = w->ch.allele_offset + r->ref_start;
-    const uint64_t *a1 = hap1 + (r->ref_start - start), *a2 = hap2 + (r->ref_start - start);
-    for (int32_t i = lo; i < hi; i++) {
-        const uint32_t o = ao[i] - first;
-        t1 -= pool[o + a1[i]];
-        t2 -= pool[o + a2[i]];
-    }
-    *x = t1 / 30.0; *y = t2 / 30.0;
-}
-
-/* stGenomeFragment_construct genomeFragment.c:40-69 (+ hmm.c:221-248) then
- * stGenomeFragment_refineGenomeFragment genomeFragment.c:165-232 */
-static void genome_fragment(const world *w, mrp_phase_result *g, const mrp_hmm *h, const uint64_t *chosen,
-                            int64_t max_iterations) {
-    const int64_t K = hmm_K(h);
-    /* side[read]: 0 = unseen, 1 = reads1, 2 = reads2; first sighting along the path wins per set
-     * (a read can be put in both sets by inconsistent columns; set semantics as in the reference) */
-    uint8_t *in1 = xcalloc((size_t) w->n_reads + 1, 1), *in2 = xcalloc((size_t) w->n_reads + 1, 1);
-    uint64_t *p = xmalloc(sizeof(uint64_t) * (size_t) K);
-    uint64_t *scratch = xmalloc(sizeof(uint64_t) * 4 * (size_t) w->max_alleles);
-    for (int64_t k = 0; k < K; k++) {
-        p[k] = chosen[k]; /* partition of the traced-back cell of column k */
-        const int32_t *cr = h->col_reads.a + h->read_off.a[k];
-        for (int32_t i = 0; i < h->col_depth.a[k]; i++) {
-            if ((p[k] >> i) & 1) { if (!in1[cr[i]]) { in1[cr[i]] = 1; g->reads1[g->n_reads1++] = cr[i]; } }
-            else { if (!in2[cr[i]]) { in2[cr[i]] = 1; g->reads2[g->n_reads2++] = cr[i]; } }
-        }
-        fill_in_predicted_genome(w, g, h, k, p[k], scratch);
-    }
-    int64_t iteration = 0;
-    uint8_t *m12 = xcalloc((size_t) w->n_reads + 1, 1), *m21 = xcalloc((size_t) w->n_reads + 1, 1);
-    int32_t *n1 = xmalloc(sizeof(int32_t) * (size_t) (2 * w->n_reads + 2)), *n2 = xmalloc(sizeof(int32_t) * (size_t) (2 * w->n_reads + 2));
-    while (iteration++ < max_iterations) {
-        int64_t c12 = 0, c21 = 0;
-        memset(m12, 0, (size_t) w->n_reads + 1); memset(m21, 0, (size_t) w->n_reads + 1);
-        for (int64_t i = 0; i < g->n_reads1; i++) { /* :126-151 */
-            const int32_t r = g->reads1[i];
-            double x, y;
-            read_log_prob2(w, g->haplotype_string1, g->haplotype_string2, g->ref_start, g->length, r, &x, &y);
-            if (x < y) { m12[r] = 1; c12++; }
-        }
-        for (int64_t i = 0; i < g->n_reads2; i++) {
-            const int32_t r = g->reads2[i];
-            double x, y;
-            read_log_prob2(w, g->haplotype_string1, g->haplotype_string2, g->ref_start, g->length, r, &x, &y);
-            if (y < x) { m21[r] = 1; c21++; }
-        }
-        if (c12 + c21 == 0) break;
-        int64_t a = 0, b = 0;
-        for (int64_t i = 0; i < g->n_reads1; i++) if (!m12[g->reads1[i]]) n1[a++] = g->reads1[i];
-        for (int64_t i = 0; i < g->n_reads2; i++) if (!m21[g->reads2[i]]) n2[b++] = g->reads2[i];
-        for (int64_t i = 0; i < g->n_reads2; i++) if (m21[g->reads2[i]]) n1[a++] = g->reads2[i];
-        for (int64_t i = 0; i < g->n_reads1; i++) if (m12[g->reads1[i]]) n2[b++] = g->reads1[i];
-        memcpy(g->reads1, n1, sizeof(int32_t) * (size_t) a); memcpy(g->reads2, n2, sizeof(int32_t) * (size_t) b);
-        g->n_reads1 = a; g->n_reads2 = b;
-        for (int64_t k = 0; k < K; k++) { /* :211-226 */
-            const int32_t *cr = h->col_reads.a + h->read_off.a[k];
-            uint64_t flip = 0; /* (a read moved both ways -- it sat in both lists -- is flipped twice: not at all) */
-            for (int32_t i = 0; i < h->col_depth.a[k]; i++) flip |= (uint64_t) (m12[cr[i]] ^ m21[cr[i]]) << i;
-            if (!flip) continue; /* fillInPredictedGenome is a function of the column and its partition: unchanged */
-            p[k] ^= flip;
-            fill_in_predicted_genome(w, g, h, k, p[k], scratch);
-        }
-    }
-    free(in1); free(in2); free(p); free(m12); free(m21); free(n1); free(n2); free(scratch);
-}
-
-/* filterReadsByCoverageDepth coordination.c:443-488 */
-static void filter_reads_by_coverage_depth(const world *w, const mrp_params *params, int32_t *filtered, int64_t *nf,
-                                           int32_t *discarded, int64_t *nd) {
-    int32_t *all = xmalloc(sizeof(int32_t) * (size_t) (w->n_reads + 1));
-    for (int64_t i = 0; i < w->n_reads; i++) all[i] = (int32_t) i;
-    path_vec paths = tiling_paths2(w, all, w->n_reads);
-    free(all);
-    keyed *a = xmalloc(sizeof(keyed) * (size_t) (paths.n + 1)), *t = xmalloc(sizeof(keyed) * (size_t) (paths.n + 1));
-    for (int64_t i = 0; i < paths.n; i++) {
-        int64_t total = 0;
-        for (int64_t j = 0; j < paths.a[i]->n; j++) total += w->reads[paths.a[i]->a[j]->reads.a[0]].length;
-        a[i].idx = i; a[i].key = (double) total;
-    }
-    keyed_sort_desc(a, paths.n, t);
-    int64_t np = paths.n;
-    *nf = 0; *nd = 0;
-    while (np > params->max_coverage_depth) {
-        hmm_vec *tp = paths.a[a[--np].idx];
-        for (int64_t j = tp->n - 1; j >= 0; j--) discarded[(*nd)++] = tp->a[j]->reads.a[0];
-    }
-    while (np > 0) {
-        hmm_vec *tp = paths.a[a[--np].idx];
-        for (int64_t j = tp->n - 1; j >= 0; j--) filtered[(*nf)++] = tp->a[j]->reads.a[0];
-    }
-    for (int64_t i = 0; i < paths.n; i++) free_path(paths.a[i], 1);
-    free(paths.a); free(a); free(t);
-}
-
-/* bubbleGraph.c:2761-2779: genome fragment from the traced-back partitions, refinement, re-adding the filtered reads */
-static void finish_phase_parts(world *w, const mrp_hmm *hmm, const uint64_t *chosen, double fwd, double bwd, const mrp_params *params,
-                               const int32_t *discarded, int64_t nd, mrp_phase_result **out) {
-    mrp_phase_result *g = result_new(hmm->ref_start, hmm->ref_length, w->n_reads);
-    genome_fragment(w, g, hmm, chosen, params->rounds_of_iterative_refinement); /* :2761-2764 */
-    for (int64_t i = 0; i < nd; i++) { /* :2772-2779 */
-        double x, y;
-        read_log_prob2(w, g->haplotype_string1, g->haplotype_string2, g->ref_start, g->length, discarded[i], &x, &y);
-        if (x < y) g->reads2[g->n_reads2++] = discarded[i]; else g->reads1[g->n_reads1++] = discarded[i];
-    }
-    g->hmm_forward = fwd; g->hmm_backward = bwd; g->n_sweeps = w->n_sweeps;
-    *out = g;
-}
-/* bubbleGraph.c:2755-2779 on a swept host hmm */
-static int finish_phase(world *w, mrp_hmm *hmm, const mrp_params *params, const int32_t *discarded, int64_t nd,
-                        mrp_phase_result **out) {
-    const int64_t K = hmm_K(hmm);
-    int32_t *path = xmalloc(sizeof(int32_t) * (size_t) K);
-    int rc = mrp_hmm_forward_trace_back(hmm, path); /* :2755 */
-    if (rc == MRP_OK) {
-        uint64_t *chosen = xmalloc(sizeof(uint64_t) * (size_t) K);
-        for (int64_t k = 0; k < K; k++) chosen[k] = hmm->part.a[hmm->cell_off.a[k] + path[k]];
-        finish_phase_parts(w, hmm, chosen, hmm->fwd, hmm->bwd, params, discarded, nd, out);
-        free(chosen);
-    }
-    free(path);
-    return rc;
-}
-
-/* bubbleGraph_phaseBubbleGraph bubbleGraph.c:2673-2801 */
-int mrp_phase_reads(mrp_context *ctx, const mrp_chunk *chunk, const mrp_read *reads, int64_t n_reads,
-                    const mrp_params *params, mrp_batch *record, mrp_phase_result **out) {
-    if (!params || !out || n_reads < 0) return mrp_set_error(MRP_ERR_ARG, "mrp_phase_reads: bad arguments");
-    *out = NULL;
-    world w;
-    int rc = world_init(&w, ctx, chunk, reads, n_reads, record);
-    if (rc != MRP_OK) return rc;
-    if (n_reads == 0) { *out = result_new(0, 0, 0); return MRP_OK; } /* :2719-2728 */
-    int32_t *filtered = xmalloc(sizeof(int32_t) * (size_t) n_reads), *discarded = xmalloc(sizeof(int32_t) * (size_t) n_reads);
-    int64_t nf, nd;
-    filter_reads_by_coverage_depth(&w, params, filtered, &nf, discarded, &nd); /* :2699 */
-    uint8_t *is_disc = xcalloc((size_t) n_reads, 1);
-    for (int64_t i = 0; i < nd; i++) is_disc[discarded[i]] = 1;
-    int32_t *fwd = xmalloc(sizeof(int32_t) * (size_t) n_reads), *rev = xmalloc(sizeof(int32_t) * (size_t) n_reads);
-    int64_t nfwd = 0, nrev = 0;
-    for (int64_t i = 0; i < n_reads; i++) { /* :2705-2716 */
-        if (is_disc[i]) continue;
-        if (reads[i].forward_strand) fwd[nfwd++] = (int32_t) i; else rev[nrev++] = (int32_t) i;
-    }
-    mrp_params pc = *params;
-    pc.include_ancestor_sub_prob = 0; /* :2733 */
-    hmm_vec *tpF = NULL, *tpR = NULL, *joined = NULL;
-    mrp_hmm *hmm = NULL;
-    rc = get_rp_hmms(&w, fwd, nfwd, &pc, &tpF);                  /* :2736 */
-    if (rc == MRP_OK) rc = get_rp_hmms(&w, rev, nrev, &pc, &tpR); /* :2740 */
-    if (rc == MRP_OK) { rc = merge_two_tiling_paths(&w, tpF, tpR, &pc, &joined); tpF = tpR = NULL; } /* :2745 */
-    if (rc == MRP_OK && joined->n > 0) {
-        hmm = fuse_path(&w, joined);
-        free(joined->a); free(joined); joined = NULL;
-        pc.include_ancestor_sub_prob = 1; /* :2748 */
-        rc = sweep_many(&w, &hmm, 1, &pc); /* :2749 */
-        if (rc == MRP_OK) rc = finish_phase(&w, hmm, params, discarded, nd, out);
-    } else if (rc == MRP_OK) {
-        *out = result_new(0, 0, n_reads);
-    }
-    free_path(tpF, 1); free_path(tpR, 1); free_path(joined, 1);
-    mrp_hmm_destroy(hmm);
-    free(filtered); free(discarded); free(is_disc); free(fwd); free(rev);
-    return rc;
-}
-
-/* ------------------------------------------------------------------------------------------ */
 /* device-resident merge                                                     */
 /*                                                                                             */
-/* The same recursion as merge_tiling_paths / merge_two_tiling_paths above, but the hmms never  */
-/* leave HBM.  The structural decisions depend on read intervals only and are split in two:     */
+/* The same recursion as merge_tiling_paths / merge_two_tiling_paths of rphmm_chunk.c, but the  */
+/* hmms never leave HBM.  The structural decisions depend on read intervals only, split in two: */
 /*   host    WHICH hmms are merged -- tiling paths, overlap components (coordination.c:69-339):   */
 /*           a few hundred intervals per chunk and level -- and the merged column BOUNDARIES of   */
 /*           every cross product (two sorted lists per hmm: 8 bytes per column);                 */
@@ -2224,7 +1010,7 @@ static void many_finish(int64_t c, void *arg) {
     else ctl->out[c] = result_new(0, 0, ctl->n_reads[c]);
 }
 
-static int phase_many_resident(mrp_context *ctx, int64_t n_chunks, const mrp_chunk *const *chunks, const mrp_read *const *reads,
+int phase_many_resident(mrp_context *ctx, int64_t n_chunks, const mrp_chunk *const *chunks, const mrp_read *const *reads,
                                const int64_t *n_reads, const mrp_params *params, mrp_phase_result **out,
                                mrp_phase_many_stats *stats) {
     mrp_params pc = *params;
@@ -2348,286 +1134,4 @@ static int phase_many_resident(mrp_context *ctx, int64_t n_chunks, const mrp_chu
     return rc;
 }
 
-
-/* one concurrent batch of mrp_phase_reads_many: while its levels wait for the device, the other batch's host work runs */
-typedef struct {
-    mrp_context *ctx;
-    int64_t n;
-    const mrp_chunk **chunks;
-    const mrp_read **reads;
-    int64_t *n_reads;
-    const mrp_params *params;
-    mrp_phase_result **out;
-    mrp_phase_many_stats stats;
-    int rc, index;
-    void *pool; /* the caller's host worker pool */
-    char err[256];
-} phase_group;
-long long mrp_pool_task_cpu_ns(void);
-long long mrp_pool_task_cpu_ns_this_thread(void);
-static double thread_cpu_ms(void) { struct timespec t; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &t); return 1e3 * t.tv_sec + 1e-6 * t.tv_nsec; }
-/* The batch (0 .. G - 1) every chunk of a call goes to: a repeating pattern that gives batch g the share w_g / sum w of the chunks.
- * For calls of large chunks the first batches are the smaller ones (shares 2 : 3 : 4 : 5 : 5 ...): every batch starts with merge levels
- * that cost the host more than the device, the batches leave them one after the other (the pool serves batch 0 first), and the device
- * waits for the first batch to reach its large levels -- a small first batch gets there sooner, the later ones are prepared beside its
- * kernels (-1 to -2 % per call of 1 152 configs[1] chunks, A/B on three boxes).  Chunks of a few hundred sites keep equal shares: their
- * calls are the host's time throughout, and a larger last batch only lengthens them (640 chunks of 130 sites: 16.2 ms with equal shares,
- * 17.6 with graded ones).  MRP_GROUP_WEIGHTS=w0:w1:... (development) sets the shares.  A work queue's chunk block is uploaded in the
- * same groups (mrp_chunk_block_create): a batch waits for its own group's copy only. */
-void mrp_phase_group_assign(int64_t n_chunks, int G, int64_t total_sites, uint8_t *group_of) {
-    int w[16], W = 0, pat[256], np = 0;
-    if (G < 1) G = 1;
-    if (G > 16) G = 16;
-    const int graded = G >= 4 && n_chunks >= 16 * (int64_t) G && total_sites >= 500 * n_chunks;
-    for (int g = 0; g < G; g++) w[g] = graded ? (g + 2 < 5 ? g + 2 : 5) : 1;
-    const char *we = getenv("MRP_GROUP_WEIGHTS");
-    if (we) { int g = 0; for (const char *c = we; *c && g < G; g++) { w[g] = atoi(c); if (w[g] < 1) w[g] = 1; if (w[g] > 8) w[g] = 8; while (*c >= '0' && *c <= '9') c++; if (*c) c++; /* (any separator) */ } }
-    for (int g = 0; g < G; g++) W += w[g];
-    /* the pattern: round by round, every batch that still has weight left takes one place */
-    for (int round = 0; np < W; round++) for (int g = 0; g < G && np < W; g++) if (w[g] > round) pat[np++] = g;
-    for (int64_t i = 0; i < n_chunks; i++) group_of[i] = (uint8_t) pat[i % W];
-}
-
-static void *phase_group_main(void *p) {
-    phase_group *g = p;
-    const double cpu0 = thread_cpu_ms();
-    const long long pool0 = mrp_pool_task_cpu_ns(), mine0 = mrp_pool_task_cpu_ns_this_thread();
-    mrp_pool_adopt(g->pool);
-    mrp_pool_set_priority(g->index); /* batch 0's host loops first: the batches reach their device-heavy levels one after the other */
-    g->rc = phase_many_resident(g->ctx, g->n, g->chunks, g->reads, g->n_reads, g->params, g->out, &g->stats);
-    mrp_pool_set_priority(0);
-    if (getenv("MRP_TIMING")) {
-        fprintf(stderr, "  batch %d: cpu of its own thread %.1f ms (%.1f of it pool tasks it ran itself); pool tasks (all batches, while it ran) %.1f ms; cumulative by loop:", g->index,
-                thread_cpu_ms() - cpu0, (mrp_pool_task_cpu_ns_this_thread() - mine0) * 1e-6, (mrp_pool_task_cpu_ns() - pool0) * 1e-6);
-        for (int t = 0; t < 12; t++) fprintf(stderr, " %d:%.0f", t, mrp_pool_tag_cpu_ns(t) * 1e-6);
-        fprintf(stderr, "\n");
-    }
-    if (g->rc != MRP_OK) snprintf(g->err, sizeof(g->err), "%s", mrp_last_error());
-    return NULL;
-}
-
-/* the chunks of a call that cannot take the resident path, pulled one at a time by up to eight host threads */
-typedef struct {
-    mrp_context *ctx;
-    const mrp_chunk *const *chunks;
-    const mrp_read *const *reads;
-    const int64_t *n_reads;
-    const mrp_params *params;
-    mrp_phase_result **out;
-    int64_t next;
-    int rc;
-    char err[256];
-    int threads;
-    int64_t n;
-} hashing_ctl;
-typedef struct { hashing_ctl *ctl; mrp_context *ctx; } hashing_arg;
-static void *hashing_main(void *p) {
-    hashing_arg *a = p;
-    hashing_ctl *hc = a->ctl;
-    for (;;) {
-        const int64_t c = __atomic_fetch_add(&hc->next, 1, __ATOMIC_RELAXED);
-        if (c >= hc->n || __atomic_load_n(&hc->rc, __ATOMIC_RELAXED) != MRP_OK) return NULL;
-        const int rc = mrp_phase_reads(a->ctx, hc->chunks[c], hc->reads[c], hc->n_reads[c], hc->params, NULL, &hc->out[c]);
-        if (rc != MRP_OK) {
-            int expect = MRP_OK;
-            if (__atomic_compare_exchange_n(&hc->rc, &expect, rc, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) snprintf(hc->err, sizeof(hc->err), "%s", mrp_last_error());
-            return NULL;
-        }
-    }
-}
-
-/* the concurrent batches a call over n_chunks chunks is split into (chunk i goes to batch i % G) */
-int mrp_phase_groups_for(const mrp_context *ctx, int64_t n_chunks) {
-    int G = mrp_context_phase_groups(ctx); /* mrp_context_set_phase_groups; 0 (default): by batch size */
-    if (G <= 0) G = n_chunks < 192 ? (int) (n_chunks / 12 > 4 ? 4 : n_chunks / 12) : 8;
-    if (G < 1) G = 1;
-    if (G > 16) G = 16;
-    if (n_chunks < 4 * G) G = 1;
-    return G;
-}
-
-static int phase_many_once(mrp_context *ctx, int64_t n_chunks, const mrp_chunk *const *chunks, const mrp_read *const *reads,
-                           const int64_t *n_reads, const mrp_params *params, mrp_phase_result **out, mrp_phase_many_stats *stats);
-
-static void stats_add(mrp_phase_many_stats *stats, const mrp_phase_many_stats *st, int first) {
-    if (first) { *stats = *st; return; }
-    stats->resident = stats->resident && st->resident; stats->fallback_chunks += st->fallback_chunks;
-    if (st->levels > stats->levels) stats->levels = st->levels;
-    stats->hmms += st->hmms; stats->columns += st->columns; stats->cells += st->cells; stats->merge_cells += st->merge_cells;
-    stats->device_ms += st->device_ms; stats->cross_ms += st->cross_ms; stats->sweep_ms += st->sweep_ms; stats->prune_ms += st->prune_ms;
-    stats->pack_ms += st->pack_ms; stats->cross_emit_ms += st->cross_emit_ms; stats->recursion_ms += st->recursion_ms; stats->prune_kernel_ms += st->prune_kernel_ms; stats->compact_ms += st->compact_ms;
-    if (st->note[0] && !stats->note[0]) memcpy(stats->note, st->note, sizeof(stats->note));
-}
-
-/* A call of at most `cap` (read, site) units at a time: what a call keeps on the device grows with its units (measured 214 GB
- * for 1 152 chunks of 60 000 units, ~3.1 KB per unit: the cells of the widest merge level of every concurrent batch), so a call
- * beyond the device's budget runs as consecutive slices that fit.  The estimate is only that: when the driver still refuses
- * an allocation (memory held by another process, a pool grown by best-fit reuse) the slice is redone as two halves after
- * every cache of the context has been given back -- down to single chunks -- instead of failing the call. */
-static int phase_many_capped(mrp_context *ctx, int64_t n_chunks, const mrp_chunk *const *chunks, const mrp_read *const *reads,
-                             const int64_t *n_reads, const mrp_params *params, mrp_phase_result **out, mrp_phase_many_stats *stats,
-                             int64_t cap, int depth) {
-    int64_t total = 0;
-    for (int64_t c = 0; c < n_chunks; c++)
-        for (int64_t r = 0; r < n_reads[c]; r++) total += reads[c][r].length;
-    if (total <= cap || n_chunks <= 1) {
-        const uint64_t oom0 = mrp_context_oom_events(ctx);
-        int rc = phase_many_once(ctx, n_chunks, chunks, reads, n_reads, params, out, stats);
-        if (rc == MRP_ERR_HIP && n_chunks > 1 && depth < 8 && mrp_context_oom_events(ctx) != oom0) {
-            static int warned;
-            if (!__atomic_exchange_n(&warned, 1, __ATOMIC_RELAXED) && !getenv("MRP_QUIET"))
-                fprintf(stderr, "margin_rphmm: the device refused memory for a call of %lld chunks (%lld units): redone in two halves\n",
-                        (long long) n_chunks, (long long) total);
-            for (int64_t c = 0; c < n_chunks; c++) { mrp_phase_result_destroy(out[c]); out[c] = NULL; }
-            mrp_context_trim(ctx);
-            return phase_many_capped(ctx, n_chunks, chunks, reads, n_reads, params, out, stats, total / 2 + 1, depth + 1);
-        }
-        return rc;
-    }
-    int rc = MRP_OK;
-    int64_t c0 = 0;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    while (c0 < n_chunks && rc == MRP_OK) {
-        int64_t c1 = c0, u = 0;
-        while (c1 < n_chunks) {
-            int64_t uc = 0;
-            for (int64_t r = 0; r < n_reads[c1]; r++) uc += reads[c1][r].length;
-            if (c1 > c0 && u + uc > cap) break;
-            u += uc; c1++;
-        }
-        mrp_phase_many_stats st;
-        rc = phase_many_capped(ctx, c1 - c0, chunks + c0, reads + c0, n_reads + c0, params, out + c0, &st, cap, depth);
-        if (stats && rc == MRP_OK) stats_add(stats, &st, c0 == 0);
-        c0 = c1;
-    }
-    if (rc != MRP_OK)
-        for (int64_t c = 0; c < n_chunks; c++) { mrp_phase_result_destroy(out[c]); out[c] = NULL; }
-    return rc;
-}
-
-int mrp_phase_reads_many(mrp_context *ctx, int64_t n_chunks, const mrp_chunk *const *chunks, const mrp_read *const *reads,
-                         const int64_t *n_reads, const mrp_params *params, mrp_phase_result **out,
-                         mrp_phase_many_stats *stats) {
-    if (!ctx || n_chunks < 0 || !params || (n_chunks > 0 && (!chunks || !reads || !n_reads || !out)))
-        return mrp_set_error(MRP_ERR_ARG, "mrp_phase_reads_many: bad arguments");
-    if (params->reserved != 0) return mrp_set_error(MRP_ERR_ARG, "mrp_params.reserved must be 0");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    for (int64_t c = 0; c < n_chunks; c++) out[c] = NULL;
-    /* the slice size from the device's budget (free memory when the process's first pool asked, mrp_internal.h); MRP_CALL_UNITS
-     * overrides it (tests) */
-    const int64_t budget = mrp_context_device_budget(ctx);
-    int64_t cap = budget > 0 ? budget / 3400 : (int64_t) 7e7;
-    const char *ce = getenv("MRP_CALL_UNITS");
-    if (ce && atoll(ce) > 0) cap = atoll(ce);
-    return phase_many_capped(ctx, n_chunks, chunks, reads, n_reads, params, out, stats, cap, 0);
-}
-
-static int phase_many_once(mrp_context *ctx, int64_t n_chunks, const mrp_chunk *const *chunks, const mrp_read *const *reads,
-                           const int64_t *n_reads, const mrp_params *params, mrp_phase_result **out, mrp_phase_many_stats *stats) {
-    if (stats) memset(stats, 0, sizeof(*stats));
-    for (int64_t c = 0; c < n_chunks; c++) out[c] = NULL;
-    /* the levels of a batch alternate host work (structure, descriptors) and device work; two interleaved halves of the
-     * chunks, each with its own context and host thread, keep both busy */
-    int G = mrp_phase_groups_for(ctx, n_chunks);
-    /* measured on MI355X (bench.py --chunks N --phase-groups G, two streams a batch): 48 chunks 45.3 ms with 2 batches, 42.5
-     * with 4; 96: 52.3 with 4, 54.8 with 8; 144: 66.4 / 68.0; 192: 80.2 / 78.6; 288: 104.5 / 96.9; 432: 139.9 with 6, 130.5
-     * with 8; 576 with 8: 169.5 (2.04e8 units/s, the best rate; 768: 243 ms).  More than 8 would share hardware queues. */
-    int rc = MRP_OK;
-    if (G == 1) {
-        rc = phase_many_resident(ctx, n_chunks, chunks, reads, n_reads, params, out, stats);
-    } else {
-        phase_group *grp = xcalloc((size_t) G, sizeof(*grp));
-        pthread_t th[16];
-        int started[16] = {0};
-        /* which batch a chunk goes to (mrp_phase_group_assign: graded shares for calls of large chunks) */
-        uint8_t *group_of = xmalloc((size_t) n_chunks + 1);
-        {
-            int64_t sites = 0;
-            for (int64_t i = 0; i < n_chunks; i++) { mrp_chunk_host hv; mrp_chunk_host_view(chunks[i], &hv); sites += hv.n_sites; }
-            mrp_phase_group_assign(n_chunks, G, sites, group_of);
-        }
-        for (int g = 0; g < G; g++) {
-            phase_group *q = &grp[g];
-            q->index = g;
-            q->pool = mrp_pool_current();
-            q->ctx = g == 0 ? ctx : mrp_context_sibling(ctx, g - 1);
-            q->params = params;
-            q->n = 0;
-            for (int64_t i = 0; i < n_chunks; i++) if (group_of[i] == g) q->n++;
-            q->chunks = xmalloc(sizeof(*q->chunks) * (size_t) (q->n + 1));
-            q->reads = xmalloc(sizeof(*q->reads) * (size_t) (q->n + 1));
-            q->n_reads = xmalloc(sizeof(*q->n_reads) * (size_t) (q->n + 1));
-            q->out = xcalloc((size_t) q->n + 1, sizeof(*q->out));
-            q->n = 0;
-            for (int64_t i = 0; i < n_chunks; i++)
-                if (group_of[i] == g) { q->chunks[q->n] = chunks[i]; q->reads[q->n] = reads[i]; q->n_reads[q->n] = n_reads[i]; q->n++; }
-            if (!q->ctx) { q->rc = MRP_ERR_HIP; snprintf(q->err, sizeof(q->err), "%s", mrp_last_error()); }
-        }
-        const int was_grouped = mrp_context_set_grouped(ctx, 1); /* (the siblings always are) */
-        for (int g = 0; g < G; g++) if (grp[g].ctx) mrp_context_set_concurrent_batches(grp[g].ctx, G * mrp_context_calls_sharing_device(ctx));
-        mrp_warn_hw_queues_once(G);
-        for (int g = 1; g < G; g++)
-            if (grp[g].ctx && pthread_create(&th[g], NULL, phase_group_main, &grp[g]) == 0) started[g] = 1;
-        if (grp[0].ctx) phase_group_main(&grp[0]);
-        for (int g = 1; g < G; g++) {
-            if (started[g]) pthread_join(th[g], NULL);
-            else if (grp[g].ctx) phase_group_main(&grp[g]); /* thread creation failed: run it here */
-        }
-        mrp_context_set_grouped(ctx, was_grouped);
-        for (int g = 0; g < G; g++) if (grp[g].ctx) mrp_context_set_concurrent_batches(grp[g].ctx, 1);
-        for (int g = 0; g < G; g++) {
-            phase_group *q = &grp[g];
-            if (q->rc != MRP_OK && (rc == MRP_OK || rc == MRP_ERR_UNSUPPORTED)) rc = mrp_set_error(q->rc, "%s", q->err);
-            { int64_t k = 0; for (int64_t i = 0; i < n_chunks; i++) if (group_of[i] == g) out[i] = q->out[k++]; }
-            if (stats && q->rc == MRP_OK) {
-                stats->resident = 1;
-                stats->fallback_chunks += q->stats.fallback_chunks;
-                stats->levels = q->stats.levels > stats->levels ? q->stats.levels : stats->levels;
-                stats->hmms += q->stats.hmms; stats->columns += q->stats.columns; stats->cells += q->stats.cells;
-                stats->merge_cells += q->stats.merge_cells;
-                stats->device_ms += q->stats.device_ms; stats->cross_ms += q->stats.cross_ms; stats->sweep_ms += q->stats.sweep_ms;
-                stats->prune_ms += q->stats.prune_ms;
-                stats->pack_ms += q->stats.pack_ms; stats->cross_emit_ms += q->stats.cross_emit_ms; stats->recursion_ms += q->stats.recursion_ms;
-                stats->prune_kernel_ms += q->stats.prune_kernel_ms; stats->compact_ms += q->stats.compact_ms;
-            }
-            free(q->chunks); free(q->reads); free(q->n_reads); free(q->out);
-        }
-        free(grp);
-        free(group_of);
-    }
-    if (rc == MRP_ERR_UNSUPPORTED) {
-        /* Parameters or hmm shapes outside the resident path: the hashing path (mrp_phase_reads), one chunk per host thread,
-         * each thread with a context of its own.  Said loudly: this is two orders of magnitude slower than the resident path. */
-        char why[160];
-        snprintf(why, sizeof(why), "%s", mrp_last_error());
-        if (stats) { memset(stats, 0, sizeof(*stats)); snprintf(stats->note, sizeof(stats->note), "%s", why); }
-        static int warned;
-        if (!__atomic_exchange_n(&warned, 1, __ATOMIC_RELAXED) && !getenv("MRP_QUIET"))
-            fprintf(stderr, "margin_rphmm: mrp_phase_reads_many leaves the device-resident path (%s): %lld chunk(s) take the per-chunk hashing path, "
-                            "about 100x slower per chunk\n", why, (long long) n_chunks);
-        rc = MRP_OK;
-        for (int64_t c = 0; c < n_chunks; c++) { mrp_phase_result_destroy(out[c]); out[c] = NULL; }
-        int T = mrp_host_threads();
-        if (T > 8) T = 8;
-        if (T > n_chunks) T = (int) n_chunks;
-        if (T < 1) T = 1;
-        hashing_ctl hc = {ctx, chunks, reads, n_reads, params, out, 0, MRP_OK, {0}, T, 0};
-        for (int t = 1; t < T && rc == MRP_OK; t++)
-            if (!mrp_context_sibling(ctx, t - 1)) rc = MRP_ERR_HIP; /* all contexts before the first thread (allocator peers) */
-        if (rc == MRP_OK) {
-            hc.n = n_chunks;
-            pthread_t th[8];
-            int started[8] = {0};
-            hashing_arg ha[8];
-            for (int t = 0; t < T; t++) { ha[t].ctl = &hc; ha[t].ctx = t == 0 ? ctx : mrp_context_sibling(ctx, t - 1); }
-            for (int t = 1; t < T; t++) started[t] = pthread_create(&th[t], NULL, hashing_main, &ha[t]) == 0;
-            hashing_main(&ha[0]);
-            for (int t = 1; t < T; t++) if (started[t]) pthread_join(th[t], NULL);
-            rc = hc.rc;
-            if (rc != MRP_OK) mrp_set_error(rc, "%s", hc.err);
-        }
-    }
-    if (rc != MRP_OK)
-        for (int64_t c = 0; c < n_chunks; c++) { mrp_phase_result_destroy(out[c]); out[c] = NULL; }
-    return rc;
-}
+#undef free /* (a file that includes this one -- tools/hostbench -- holds no arena pointers) */

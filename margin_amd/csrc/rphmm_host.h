@@ -1,5 +1,5 @@
 /*
- * rphmm_host.h -- internal interface between the C host pipeline (rphmm_host.c) and the HIP side
+ * rphmm_host.h -- internal interface between the C host pipeline (rphmm_*.c) and the HIP side
  * of libmargin_rphmm.so (mrp_api.cpp).  Public declarations live in include/margin_rphmm.h.
  */
 #ifndef RPHMM_HOST_H_
@@ -27,7 +27,7 @@ typedef struct mrp_chunk_host {
 
 void mrp_chunk_host_view(const mrp_chunk *chunk, mrp_chunk_host *out);
 mrp_context *mrp_chunk_context(const mrp_chunk *chunk);
-/* the concurrent batch (0 .. G - 1) of every chunk of an mrp_phase_reads_many call (rphmm_host.c) */
+/* the concurrent batch (0 .. G - 1) of every chunk of an mrp_phase_reads_many call (rphmm_many.c) */
 void mrp_phase_group_assign(int64_t n_chunks, int G, int64_t total_sites, uint8_t *group_of);
 int mrp_context_device(const mrp_context *ctx);
 /* the context is one of several concurrent batches of its device: no side streams (mrp_internal.h) */

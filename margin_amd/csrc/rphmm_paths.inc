@@ -1,7 +1,7 @@
 /*
  * rphmm_paths.inc -- the interval logic of coordination.c (stRPHmm_cmpFn, getTilingPaths, getOverlappingComponents) over
- * any hmm type that has ref_start and ref_length; included by rphmm_host.c once for the flat host hmm (struct mrp_hmm) and
- * once for the compact shadows of the device-resident merge (struct rhmm).  Parameters:
+ * any hmm type that has ref_start and ref_length; included by rphmm_chunk.c for the flat host hmm (struct mrp_hmm) and by
+ * rphmm_host.c for the compact shadows of the device-resident merge (struct rhmm).  Parameters:
  *     HMM_T            the hmm type
  *     PFX(name)        prefix of the generated names
  *     H_NAME_READ(h)   index of the read whose name breaks ties (first read of the hmm), -1 if it has none

@@ -106,7 +106,7 @@ def test_host_worker_pool_runs_every_index_once():
 
 
 def test_batch_shares_of_a_call(monkeypatch):
-    """mrp_phase_group_assign (rphmm_host.c): which concurrent batch every chunk of an mrp_phase_reads_many call goes to -- and, the
+    """mrp_phase_group_assign (rphmm_many.c): which concurrent batch every chunk of an mrp_phase_reads_many call goes to -- and, the
     same function, in which group a work queue uploads it.  Equal shares for small calls and small chunks, graded ones
     (2 : 3 : 4 : 5 : 5 ...) for many large chunks, MRP_GROUP_WEIGHTS on request; every chunk gets a batch below G."""
     lib = capi.load()

@@ -704,7 +704,7 @@ def test_results_do_not_depend_on_the_host_threads(gpu_ctx, orc):
 
 def test_results_do_not_depend_on_the_batches_shares(gpu_ctx, orc, monkeypatch):
     """A call of many large chunks deals them to its concurrent batches in graded shares (2 : 3 : 4 : 5 : 5 ..., the first batch the
-    smallest, rphmm_host.c), small chunks in equal shares; MRP_GROUP_WEIGHTS sets the shares.  Size-independent property: 160 small
+    smallest, rphmm_many.c), small chunks in equal shares; MRP_GROUP_WEIGHTS sets the shares.  Size-independent property: 160 small
     chunks in eight batches give the same results, chunk for chunk, with equal shares, with the graded ones and with reversed ones;
     a sample against the oracle."""
     chunks = [synth.make_ont_chunk(seed=9100 + s, region_bp=40_000, n_sites=80, coverage=30.0) for s in range(160)]

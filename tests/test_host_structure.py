@@ -1,4 +1,4 @@
-"""The host side of the device-resident pipeline without a device (tools/hostbench): rphmm_host.c compiled with the engine
+"""The host side of the device-resident pipeline without a device (tools/hostbench): rphmm_host.c and rphmm_result.c compiled with the engine
 replaced by stubs that only hand out segment numbers.  Tiling paths, overlap components, the merged column boundaries of every
 cross product (r_cross_build), the final shadows and their expansion into per-column read lists (r_expand checks the column
 depths against the reads' intervals) run for whole chunks; any inconsistency makes the call fail."""

@@ -1,6 +1,6 @@
-/* hostbench.c -- CPU-only profile of the HOST side of the device-resident pipeline (rphmm_host.c): the engine is replaced by
- * stubs that only hand out segment numbers, so that tiling paths, overlap components, column boundaries, final shadows and
- * genome fragments can be timed (gprof) without a GPU.  Development tool; build: make -C tools/hostbench. */
+/* hostbench.c -- CPU-only profile of the HOST side of the device-resident pipeline (rphmm_host.c, with rphmm_result.c beside it):
+ * the engine is replaced by stubs that only hand out segment numbers, so that tiling paths, overlap components, column boundaries,
+ * final shadows and genome fragments can be timed (gprof) without a GPU.  Development tool; build: make -C tools/hostbench. */
 #define _GNU_SOURCE
 #include <stdarg.h>
 #include <pthread.h>
@@ -14,28 +14,12 @@ static __thread char g_err[512];
 void mrp_chunk_host_view(const mrp_chunk *chunk, mrp_chunk_host *out) { *out = chunk->h; }
 mrp_context *mrp_chunk_context(const mrp_chunk *chunk) { (void) chunk; return (mrp_context *) 8; }
 int mrp_context_device(const mrp_context *ctx) { (void) ctx; return 0; }
-int mrp_context_set_grouped(mrp_context *ctx, int grouped) { (void) ctx; (void) grouped; return 0; }
-void mrp_context_set_concurrent_batches(mrp_context *ctx, int n) { (void) ctx; (void) n; }
-int mrp_context_calls_sharing_device(const mrp_context *ctx) { (void) ctx; return 1; }
-int64_t mrp_context_device_budget(mrp_context *ctx) { (void) ctx; return 0; }
-uint64_t mrp_context_oom_events(mrp_context *ctx) { (void) ctx; return 0; }
-void mrp_warn_hw_queues_once(int n) { (void) n; }
-int mrp_context_trim(mrp_context *ctx) { (void) ctx; return 0; }
 void mrp_context_pool_bytes(mrp_context *ctx, int64_t *cached, int64_t *device_held) { (void) ctx; *cached = 0; *device_held = 0; }
-mrp_context *mrp_context_sibling(mrp_context *ctx, int i) { (void) i; return ctx; }
 int mrp_set_error(int code, const char *fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap); return code; }
 const char *mrp_last_error(void) { return g_err; }
 static int g_threads = 1;
-int mrp_host_threads(void) { return g_threads; }
-int mrp_context_phase_groups(const mrp_context *ctx) { (void) ctx; return 1; }
-void mrp_pool_set_priority(int p) { (void) p; }
 void mrp_pool_set_tag(int t) { (void) t; }
 void mrp_pool_set_weight(int ns) { (void) ns; }
-long long mrp_pool_tag_cpu_ns(int tag) { (void) tag; return 0; }
-long long mrp_pool_task_cpu_ns(void) { return 0; }
-long long mrp_pool_task_cpu_ns_this_thread(void) { return 0; }
-void mrp_pool_adopt(void *p) { (void) p; }
-void *mrp_pool_current(void) { return NULL; }
 typedef struct { int64_t n, grain; void (*fn)(int64_t, void *); void *arg; int64_t next; } pjob;
 static void *pworker(void *a) { pjob *j = a; for (;;) { int64_t lo = __atomic_fetch_add(&j->next, j->grain, __ATOMIC_RELAXED); if (lo >= j->n) return NULL;
     int64_t hi = lo + j->grain < j->n ? lo + j->grain : j->n; for (int64_t i = lo; i < hi; i++) j->fn(i, j->arg); } }
@@ -47,10 +31,10 @@ void mrp_pool_run(int64_t n, int64_t grain, void (*fn)(int64_t, void *), void *a
     pworker(&j);
     for (int t = 1; t < g_threads; t++) pthread_join(th[t], NULL);
 }
-int mrp_fb_run(mrp_context *ctx, int64_t n, const mrp_hmm_job *jobs) { (void) ctx; (void) n; (void) jobs; return MRP_ERR_NO_DEVICE; }
-int mrp_batch_add(mrp_batch *b, const mrp_hmm_job *job) { (void) b; (void) job; return MRP_ERR_NO_DEVICE; }
+/* (the per-chunk path a chunk falls back to when a kernel gives it up: the stub engine never does) */
+int mrp_phase_reads(mrp_context *ctx, const mrp_chunk *chunk, const mrp_read *reads, int64_t n_reads, const mrp_params *params, mrp_batch *record, mrp_phase_result **out) { (void) ctx; (void) chunk; (void) reads; (void) n_reads; (void) params; (void) record; (void) out; return MRP_ERR_NO_DEVICE; }
 int mrp_engine_create(mrp_context *ctx, const mrp_params *params, mrp_engine **out) { (void) ctx; (void) params; *out = calloc(1, sizeof(mrp_engine)); return MRP_OK; }
-void mrp_engine_destroy(mrp_engine *e) { g_hash = e->hash; (free)(e); }
+void mrp_engine_destroy(mrp_engine *e) { g_hash = e->hash; free(e); }
 int32_t mrp_engine_stride(const mrp_engine *e) { (void) e; return 100; }
 int mrp_engine_locate(const mrp_engine *e, int32_t seg, int64_t col0, const uint64_t **a, const uint32_t **b, const int32_t **c, const int32_t **d) { (void) e; (void) seg; (void) col0; *a = NULL; *b = NULL; *c = NULL; *d = NULL; return MRP_OK; }
 static int stage(mrp_engine *e, int64_t n, mrp_xhmm *x, int final) {
