@@ -602,6 +602,36 @@ int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string
                             const mrp_params *params, int64_t min_phred, mrp_phase_result **out, int8_t *const *hap_out,
                             double *const *phred_out, mrp_profile_out *profiles_out, mrp_string_chunks_stats *stats);
 
+/* ---- the same for a node's worth of chunks over its GPUs --------------------------------------------------------------
+ * The chunk loop of phase.c around that front (:395-401), with its ordering (:257-263: largest first) and its schedule
+ * (:276-279: schedule(dynamic,1)) as the work queue above gives them: mrp_queue_phase_string_chunks is mrp_phase_string_chunks
+ * for n_chunks chunks spread over the queue's devices.  The chunks are ordered by their (read, bubble) units
+ * (mrp_string_chunk_units: sub_first[n_bubbles], the unit MRP_QUEUE_UNITS_PER_CHUNK counts), largest first, ties in input
+ * order, and cut into batches by the rules of mrp_queue_phase_chunks (chunks_per_batch = 0: the library's cut by units, one
+ * batch per device for a short queue).  A lane phases a batch as one mrp_phase_string_chunks call on its own context and its
+ * device's host pool; while the batch is on the device, the host front of the lane's NEXT batch (symbol pool, substring
+ * owners, pair list, k-mer anchors, launch classes) is made on a thread beside it.
+ *   Results: out[c], hap_out[c], phred_out[c], profiles_out[c] are, at the chunk's own position, bit for bit what one
+ * mrp_phase_string_chunks call over all chunks returns, whatever the batch size, the lanes, the devices or the hand-out.
+ *   Errors: every chunk is checked on the caller's thread before a lane starts, in that call's order -- MRP_ERR_ARG, then
+ * MRP_ERR_NO_DEVICE for a NULL queue, then MRP_ERR_UNSUPPORTED for a pair of ANY chunk whose diagonal exceeds 2 048 cells.
+ * An error inside a lane (HIP, out of memory) stops the queue as in mrp_queue_phase_chunks: the remaining batches are
+ * dropped, the workers joined, every result already made destroyed, out[] / profiles_out[] left NULL / zeroed, the first
+ * error returned (mrp_last_error); the queue stays usable.
+ *   Parameters outside the resident range take the per-chunk path as in the one call (stats->fallback_chunks counts them).
+ * stats as for profile chunks, units_per_device in mrp_string_chunk_units. */
+int mrp_string_chunk_units(const mrp_string_chunk *chunk, int64_t *units_out); /* host only, no device needed */
+int mrp_queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model,
+                                  const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
+                                  const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out,
+                                  double *const *phred_out, mrp_profile_out *profiles_out, mrp_queue_stats *stats);
+/* create a queue, run the call above, destroy it: the string twin of mrp_phase_chunks_on_devices */
+int mrp_phase_string_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_string_chunk *chunks,
+                                       const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                       double het_substitution_probability, const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch,
+                                       mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                                       mrp_queue_stats *stats);
+
 /* ---- from alignments to read substrings at variant sites --------------------------------------------------------------
  * The step of margin phase's chunk loop that makes the strings above (phase.c:337-357): updateVcfEntriesWithSubstringsAndPositions
  * (impl/vcf.c:476-486, getAlleleSubstrings2 :394-462) and extractReadSubstringsAtVariantPositions (impl/htsIntegration.c:1722-1989)

@@ -35,7 +35,8 @@ EXPORTED_SYMBOLS = [
     "mrp_symbols_from_chars", "mrp_pair_hmm_reverse_complement", "mrp_band_diagonals", "mrp_forward_probabilities",
     "mrp_allele_read_supports", "mrp_kmer_alignment_anchors", "mrp_phase_chunks_on_devices", "mrp_queue_plan", "mrp_queue_dry_run", "mrp_queue_create", "mrp_queue_destroy",
     "mrp_queue_phase_chunks", "mrp_partition_reads_by_haplotype", "mrp_phase_variants_from_tagged_reads", "mrp_phase_string_chunks",
-    "mrp_extract_read_substrings", "mrp_string_chunk_from_extracted",
+    "mrp_extract_read_substrings", "mrp_string_chunk_from_extracted", "mrp_string_chunk_units", "mrp_queue_phase_string_chunks",
+    "mrp_phase_string_chunks_on_devices",
 ]
 
 
@@ -347,6 +348,10 @@ def load():
     L.mrp_phase_variants_from_tagged_reads.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, vp, i64, i64, vp, vp, vp, P(PairHmmStats)]
     L.mrp_phase_string_chunks.argtypes = [vp, i64, P(StringChunk), P(PairHmm), P(PairHmm), i64, i64, C.c_double, P(Params), i64, P(P(PhaseResult)),
                                           P(vp), P(vp), P(ProfileOut), P(StringChunksStats)]
+    L.mrp_string_chunk_units.argtypes = [P(StringChunk), P(i64)]
+    L.mrp_queue_phase_string_chunks.argtypes = [vp, i64, P(StringChunk), P(PairHmm), P(PairHmm), i64, i64, C.c_double, P(Params), i64, i64,
+                                                P(P(PhaseResult)), P(vp), P(vp), P(ProfileOut), P(QueueStats)]
+    L.mrp_phase_string_chunks_on_devices.argtypes = [vp, i32] + L.mrp_queue_phase_string_chunks.argtypes[1:]
     L.mrp_extract_read_substrings.argtypes = [vp, i64, P(AlignedChunk), P(ExtractOptions), P(P(ExtractedChunk)), P(ExtractStats)]
     L.mrp_string_chunk_from_extracted.argtypes = [P(ExtractedChunk), vp, vp, vp, P(StringChunk), P(P(C.c_int64))]
     L.mrp_kmer_alignment_anchors.argtypes = [vp, i64, vp, i64, vp]
@@ -788,6 +793,13 @@ class Queue:
             L.mrp_phase_result_destroy(res[i])
         return out, st
 
+    def phase_string_chunks(self, chunks, forward_model: "PairHmm", reverse_model: "PairHmm", params: Params, min_phred: int = 0,
+                            chunks_per_batch: int = 0, expansion: int = 4, sv_threshold: int = 512, het_substitution_probability: float = 0.0,
+                            profiles: bool = False, structs=None):
+        """mrp_queue_phase_string_chunks -> (phase_string_chunks' list of dicts in input order, QueueStats)"""
+        return _queue_phase_string_chunks(self.h, chunks, forward_model, reverse_model, params, min_phred, chunks_per_batch, expansion, sv_threshold,
+                                          het_substitution_probability, profiles, structs)
+
     def close(self):
         if self.h:
             load().mrp_queue_destroy(self.h)
@@ -1104,6 +1116,40 @@ def _profile_dict(P) -> dict:
     return dict(seqs=seqs, read_of_seq=_as_np(P.read_of_seq, n, np.int32), pool=_as_np(P.pool, int(P.pool_bytes), np.uint8))
 
 
+class StringChunkArgs:
+    """the arrays a string-chunk call takes and fills (mrp_phase_string_chunks, mrp_queue_phase_string_chunks), and its results as dicts"""
+
+    def __init__(self, chunks, profiles: bool, structs=None):
+        self.chunks, self.n, self.profiles = chunks, len(chunks), profiles
+        n = self.n
+        self.built = structs if structs is not None else [string_chunk_struct(c) for c in chunks]
+        self.arr = (StringChunk * max(n, 1))(*[b[0] for b in self.built])
+        self.haps = [np.zeros(len(c.read_names), dtype=np.int8) for c in chunks]
+        self.phreds = [np.zeros(len(c.read_names), dtype=np.float64) for c in chunks]
+        self.hp = (C.c_void_p * max(n, 1))(*[h.ctypes.data for h in self.haps])
+        self.pp = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in self.phreds])
+        self.res = (C.POINTER(PhaseResult) * max(n, 1))()
+        self.prof = (ProfileOut * max(n, 1))() if profiles else None
+
+    def results(self):
+        L = load()
+        out = []
+        for i in range(self.n):
+            d = dict(result=_phase_result_dict(self.res[i].contents), hap=self.haps[i], phred=self.phreds[i])
+            L.mrp_phase_result_destroy(self.res[i])
+            if self.profiles:
+                P = self.prof[i]
+                d["profile"] = _profile_dict(P)
+                nb = len(self.chunks[i].bubbles)
+                an = _as_np(P.allele_number, nb, np.uint32)
+                A = an.astype(np.int64)
+                d["profile"].update(allele_number=an, sub=_as_np(P.substitution, int((A * A).sum()), np.uint16), prior=_as_np(P.prior, int(A.sum()), np.uint16))
+                for f in ("seqs", "read_of_seq", "pool", "allele_number", "substitution", "prior"):
+                    L.mrp_free(C.cast(getattr(P, f), C.c_void_p))
+            out.append(d)
+        return out
+
+
 def phase_string_chunks(ctx: Context, chunks, forward_model: PairHmm, reverse_model: PairHmm, params: Params, min_phred: int = 0,
                         expansion: int = 4, sv_threshold: int = 512, het_substitution_probability: float = 0.0, profiles: bool = False,
                         structs=None):
@@ -1111,33 +1157,42 @@ def phase_string_chunks(ctx: Context, chunks, forward_model: PairHmm, reverse_mo
     phase result dict with reads1 / reads2 naming the chunk's reads; profile (profiles=True) holds the profile sequences, pool
     and site tables; structs = [string_chunk_struct(c) for c in chunks] to reuse them (timing loops)."""
     L = load()
-    n = len(chunks)
-    built = structs if structs is not None else [string_chunk_struct(c) for c in chunks]
-    arr = (StringChunk * max(n, 1))(*[b[0] for b in built])
-    haps = [np.zeros(len(c.read_names), dtype=np.int8) for c in chunks]
-    phreds = [np.zeros(len(c.read_names), dtype=np.float64) for c in chunks]
-    hp = (C.c_void_p * max(n, 1))(*[h.ctypes.data for h in haps])
-    pp = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in phreds])
-    res = (C.POINTER(PhaseResult) * max(n, 1))()
-    prof = (ProfileOut * max(n, 1))() if profiles else None
+    a = StringChunkArgs(chunks, profiles, structs)
     st = StringChunksStats()
-    _check(L.mrp_phase_string_chunks(ctx.h, n, arr, C.byref(forward_model), C.byref(reverse_model), int(expansion), int(sv_threshold),
-                                     float(het_substitution_probability), C.byref(params), int(min_phred), res, hp, pp, prof, C.byref(st)))
-    out = []
-    for i in range(n):
-        d = dict(result=_phase_result_dict(res[i].contents), hap=haps[i], phred=phreds[i])
-        L.mrp_phase_result_destroy(res[i])
-        if profiles:
-            P = prof[i]
-            d["profile"] = _profile_dict(P)
-            nb = len(chunks[i].bubbles)
-            an = _as_np(P.allele_number, nb, np.uint32)
-            A = an.astype(np.int64)
-            d["profile"].update(allele_number=an, sub=_as_np(P.substitution, int((A * A).sum()), np.uint16), prior=_as_np(P.prior, int(A.sum()), np.uint16))
-            for f in ("seqs", "read_of_seq", "pool", "allele_number", "substitution", "prior"):
-                L.mrp_free(C.cast(getattr(P, f), C.c_void_p))
-        out.append(d)
-    return out, st
+    _check(L.mrp_phase_string_chunks(ctx.h, a.n, a.arr, C.byref(forward_model), C.byref(reverse_model), int(expansion), int(sv_threshold),
+                                     float(het_substitution_probability), C.byref(params), int(min_phred), a.res, a.hp, a.pp, a.prof, C.byref(st)))
+    return a.results(), st
+
+
+def string_chunk_units(chunk, struct=None) -> int:
+    """mrp_string_chunk_units: the (read, bubble) units of one chunk, what the work queue orders and cuts its batches by"""
+    S = struct if struct is not None else string_chunk_struct(chunk)
+    u = C.c_int64(-1)
+    _check(load().mrp_string_chunk_units(C.byref(S[0]), C.byref(u)))
+    return int(u.value)
+
+
+def _queue_phase_string_chunks(q, chunks, forward_model, reverse_model, params, min_phred, chunks_per_batch, expansion, sv_threshold,
+                               het_substitution_probability, profiles, structs):
+    a = StringChunkArgs(chunks, profiles, structs)
+    st = QueueStats()
+    _check(load().mrp_queue_phase_string_chunks(q, a.n, a.arr, C.byref(forward_model), C.byref(reverse_model), int(expansion), int(sv_threshold),
+                                                float(het_substitution_probability), C.byref(params), int(min_phred), int(chunks_per_batch), a.res,
+                                                a.hp, a.pp, a.prof, C.byref(st)))
+    return a.results(), st
+
+
+def phase_string_chunks_on_devices(devices, chunks, forward_model: PairHmm, reverse_model: PairHmm, params: Params, min_phred: int = 0,
+                                   chunks_per_batch: int = 0, expansion: int = 4, sv_threshold: int = 512, het_substitution_probability: float = 0.0,
+                                   profiles: bool = False, structs=None):
+    """mrp_phase_string_chunks_on_devices -> (phase_string_chunks' list of dicts in input order, QueueStats)"""
+    a = StringChunkArgs(chunks, profiles, structs)
+    dev = (C.c_int32 * len(devices))(*devices)
+    st = QueueStats()
+    _check(load().mrp_phase_string_chunks_on_devices(C.cast(dev, C.c_void_p), len(devices), a.n, a.arr, C.byref(forward_model), C.byref(reverse_model),
+                                                     int(expansion), int(sv_threshold), float(het_substitution_probability), C.byref(params),
+                                                     int(min_phred), int(chunks_per_batch), a.res, a.hp, a.pp, a.prof, C.byref(st)))
+    return a.results(), st
 
 
 def phase_string_chunks_chain(ctx: Context, chunks, forward_model: PairHmm, reverse_model: PairHmm, params: Params, min_phred: int = 0,

@@ -523,6 +523,23 @@ void mrp_engine_release_context_cache(mrp_context *ctx);
  * mrp_chunk_create gives a pool) and descs[i]->profile_pool is the caller's host copy of them; only the site tables are staged */
 int mrp_chunk_block_create(mrp_context *ctx, int64_t n, const mrp_chunk_desc *const *descs, mrp_chunk **out, mrp_chunk_block *blk, int groups = 1,
                            const uint8_t *const *device_pools = nullptr);
+/* mrp_phase_string_chunks in three steps (mrp_pairhmm.hip), so that a work queue can check every chunk before its first lane
+ * starts and a lane can make the front of its next batch while the current one is on the device:
+ *   check        MRP_ERR_ARG for malformed arguments (host only, the one call's own checks);
+ *   check_pairs  MRP_ERR_UNSUPPORTED for a pair whose diagonal exceeds the pair-per-wave kernel's limit (host only);
+ *   front        symbol pool, substring owners, pair list, anchors, launch classes (host only, no context; any thread);
+ *   run          uploads, kernels, phasing, HP tags, results -- on the thread of ctx; a front is run once.
+ * The front keeps pointers into chunks[]: the array lives until the run has returned. */
+struct mrp_string_front;
+int mrp_string_chunks_check(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                            int64_t expansion, const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out);
+int mrp_string_chunks_check_pairs(int64_t n_chunks, const mrp_string_chunk *chunks, int64_t expansion, int64_t sv_threshold);
+int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                            int64_t expansion, int64_t sv_threshold, mrp_string_front **front_out);
+void mrp_string_front_destroy(mrp_string_front *front);
+int mrp_string_front_run(mrp_context *ctx, mrp_string_front *front, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                         mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                         mrp_string_chunks_stats *stats);
 int mrp_host_threads_setting(void); /* what mrp_set_host_threads() was given, 0 if it was never called */
 /* host worker pools (mrp_api.cpp) */
 extern "C" void mrp_batch_last_launch_ms(struct mrp_batch *b, float *pack, float *emission, float *recursion);

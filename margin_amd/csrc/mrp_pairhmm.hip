@@ -496,10 +496,13 @@ int64_t kmer_anchors(const uint8_t *sx, int64_t lx, const uint8_t *sy, int64_t l
 struct PhmLaunch {
     hipStream_t s = nullptr;
     int64_t cells = 0;
+    int n_models = 0, table_bytes = 0; /* phm_classify: what phm_enqueue sizes the launches by */
+    bool has_switch = false;
     std::vector<PhmModelDev> hm;
     HostVec<PhmLanePair> lane_pairs[4];
     HostVec<PhmPair> wave_pairs[4];
     HostVec<int32_t> band;
+    HostVec<uint32_t> key; /* phm_classify's sort keys (released with the launch, not between its two halves) */
     DevBuf<PhmModelDev> d_models;
     DevBuf<uint8_t> d_pool;
     DevBuf<int32_t> d_band;
@@ -516,12 +519,12 @@ struct PhmLaunch {
     }
 };
 
-/* Classify, upload and queue the kernels of n_pairs > 0 pairs on ctx->stream; ctx->ev[0] is recorded before the first
- * kernel.  Errors (prefixed with who) are raised on the host, before anything is launched. */
-int phm_launch(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, int32_t n_models, int64_t n_pairs, const uint8_t *pool,
-               int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len, const int64_t *y_off, const int32_t *y_len,
-               const uint8_t *model_index, const int64_t *anchor_off, const int64_t *anchors, int64_t expansion, int ragged_left,
-               int ragged_right, PhmLaunch &L, mrp_pairhmm_stats *stats) {
+/* The host half of a pair-HMM batch of n_pairs > 0 pairs, no device needed: the pairs sorted into the launch classes of
+ * the two kernels, the bands of the anchored ones, the models as the kernels read them.  Every error of the batch (prefixed
+ * with who) is raised here, MRP_ERR_UNSUPPORTED for a diagonal beyond PHM_WAVE_MAX_WIDTH cells among them. */
+int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, int64_t n_pairs, int64_t pool_bytes, const int64_t *x_off,
+                 const int32_t *x_len, const int64_t *y_off, const int32_t *y_len, const uint8_t *model_index, const int64_t *anchor_off,
+                 const int64_t *anchors, int64_t expansion, int ragged_left, int ragged_right, PhmLaunch &L) {
     if (n_pairs >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
     if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
 
@@ -534,7 +537,8 @@ int phm_launch(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, in
     for (int c = 0; c < 4; c++) lane_cap[c] = std::min(lane_max_x, (PHM_LDS_BYTES - table_bytes) / ((4 - c) * PHM_LANE_BYTES_PER_X));
     constexpr uint32_t WAVE_KEY = 0xFFFFFFFFu;
     constexpr int LY_CLIP = 4095;
-    HostVec<uint32_t> key((size_t) n_pairs);
+    HostVec<uint32_t> &key = L.key;
+    key.resize((size_t) n_pairs);
     std::atomic<int64_t> bad{-1}, cells_atomic{0};
     mrp_parallel_for((n_pairs + 16383) / 16384, 1, [&](int64_t blk) {
         int64_t c_local = 0;
@@ -638,15 +642,27 @@ int phm_launch(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, in
             return ca != cb ? ca > cb : a.out < b.out;
         });
     L.cells = cells;
-
-    PHM_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
+    L.n_models = n_models;
+    L.table_bytes = table_bytes;
     L.hm.resize((size_t) n_models);
-    bool has_switch = false;
+    L.has_switch = false;
     for (int i = 0; i < n_models; i++) {
         model_to_device(models[i], ragged_left, ragged_right, L.hm[(size_t) i]);
-        if (!(models[i].gap_switch_to_x == -INFINITY && models[i].gap_switch_to_y == -INFINITY)) has_switch = true;
+        if (!(models[i].gap_switch_to_x == -INFINITY && models[i].gap_switch_to_y == -INFINITY)) L.has_switch = true;
     }
+    return MRP_OK;
+}
+
+/* The device half: uploads what phm_classify made of n_pairs pairs over pool and queues the kernels on ctx->stream;
+ * ctx->ev[0] is recorded before the first kernel. */
+int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64_t n_pairs, PhmLaunch &L, mrp_pairhmm_stats *stats) {
+    const int n_models = L.n_models, table_bytes = L.table_bytes;
+    const bool has_switch = L.has_switch;
+    HostVec<PhmLanePair> *lane_pairs = L.lane_pairs;
+    HostVec<PhmPair> *wave_pairs = L.wave_pairs;
+    HostVec<int32_t> &band = L.band;
+    PHM_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
     L.d_models.pool = L.d_pool.pool = L.d_band.pool = L.d_out.pool = &ctx->pool;
     L.s = s; /* from here on the destructor drains the stream */
     PHM_HIP(L.d_models.upload(L.hm, s));
@@ -700,6 +716,16 @@ int phm_launch(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, in
         if (stats) stats->pairs_wave += n;
     }
     return MRP_OK;
+}
+
+/* Classify, upload and queue the kernels of n_pairs > 0 pairs: errors are raised on the host, before anything is launched. */
+int phm_launch(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, int32_t n_models, int64_t n_pairs, const uint8_t *pool,
+               int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len, const int64_t *y_off, const int32_t *y_len,
+               const uint8_t *model_index, const int64_t *anchor_off, const int64_t *anchors, int64_t expansion, int ragged_left,
+               int ragged_right, PhmLaunch &L, mrp_pairhmm_stats *stats) {
+    const int rc = phm_classify(who, models, n_models, n_pairs, pool_bytes, x_off, x_len, y_off, y_len, model_index, anchor_off, anchors, expansion,
+                                ragged_left, ragged_right, L);
+    return rc != MRP_OK ? rc : phm_enqueue(ctx, pool, pool_bytes, n_pairs, L, stats);
 }
 
 /* cachedScores of the reference's bubble loops (bubbleGraph.c:1418,1844,2221, keyed by the substring alone): for every
@@ -1319,15 +1345,33 @@ int mrp_phase_variants_from_tagged_reads(mrp_context *ctx, const mrp_pair_hmm *f
     return MRP_OK;
 }
 
+}  // extern "C"
 
-int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model,
-                            const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
-                            const mrp_params *params, int64_t min_phred, mrp_phase_result **out, int8_t *const *hap_out,
-                            double *const *phred_out, mrp_profile_out *profiles_out, mrp_string_chunks_stats *stats) {
+/* ---- mrp_phase_string_chunks in three steps (mrp_internal.h): its own body below, and what a lane of the work queue runs per
+ * batch (mrp_queue.cpp) -- the checks of every chunk first, the front of batch n + 1 beside the device work of batch n. */
+
+struct mrp_string_front {
+    int64_t n_chunks = 0, n_subs = 0, n_pairs = 0;
+    const mrp_string_chunk *chunks = nullptr;          /* the caller's, alive until the run has returned */
+    std::vector<int64_t> pool_base, sub_base;          /* n_chunks + 1: chunk c's symbols and substrings in the call's arrays */
+    HostVec<uint8_t> gpool;                            /* every chunk's symbols: what the pair-HMM kernels read */
+    std::vector<int64_t> pair_first;                   /* per substring: the pair of its owner with the bubble's allele 0 */
+    PhmLaunch L;                                       /* the pairs as phm_classify sorted them; the run adds the device half */
+    /* what only the front itself reads, kept until the front is destroyed: released between front and run, these ~100 bytes per
+     * pair go back to the system and the run's own arrays fault fresh pages in (12 chunks of 2 000 sites: a call of 68-77 ms
+     * instead of 56-61) */
+    struct Scratch {
+        std::vector<int64_t> g_sub_first, g_sub_off, owner, xo, yo, anchor_off, anchors;
+        std::vector<int32_t> g_sub_len, xl, yl;
+        std::vector<uint8_t> mi;
+        std::vector<std::vector<int64_t>> chunk_anchors;
+    } scratch;
+    double front_ms = 0;                               /* host wall time of the front (the one call adds its checks) */
+};
+
+int mrp_string_chunks_check(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                            int64_t expansion, const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out) {
     static const char *who = "mrp_phase_string_chunks";
-    const double t_begin = now_ms();
-    if (stats) memset(stats, 0, sizeof(*stats));
-    /* ---- checks (host only, before the context: a malformed call is refused the same with or without a device) */
     if (n_chunks < 0 || (n_chunks > 0 && (!chunks || !out || !hap_out)) || !forward_model || !reverse_model || !params)
         return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
     if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
@@ -1344,22 +1388,80 @@ int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string
         for (int64_t c = 0; c < n_chunks; c++)
             if (rcs[(size_t) c] != MRP_OK) return mrp_set_error(rcs[(size_t) c], "%s", msgs[(size_t) c].c_str());
     }
-    if (!ctx) return fail(MRP_ERR_NO_DEVICE, "mrp_phase_string_chunks: no context (the pair-HMM path has no CPU fallback)");
-    for (int64_t c = 0; c < n_chunks; c++) out[c] = nullptr;
-    if (profiles_out) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
-    if (n_chunks == 0) return MRP_OK;
+    return MRP_OK;
+}
 
+/* MRP_ERR_UNSUPPORTED as phm_classify raises it, from the strings alone -- without the owners, the pair list or the sort (a
+ * duplicate substring has its owner's strings, so looking at every substring changes nothing).  A diagonal of a pair holds at
+ * most min(lx, ly) + 1 cells, band or not: only pairs with BOTH strings at the limit are looked at, their anchors (above
+ * sv_threshold, bubbleGraph.c:1448-1451) and bands made as the front makes them. */
+int mrp_string_chunks_check_pairs(int64_t n_chunks, const mrp_string_chunk *chunks, int64_t expansion, int64_t sv_threshold) {
+    static const char *who = "mrp_phase_string_chunks";
+    std::vector<int> rcs((size_t) n_chunks, MRP_OK);
+    std::vector<std::string> msgs((size_t) n_chunks);
+    mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
+        const mrp_string_chunk &S = chunks[c];
+        std::vector<int64_t> anc;
+        std::vector<int32_t> Lb, Rb;
+        for (int64_t b = 0; b < S.n_bubbles && rcs[(size_t) c] == MRP_OK; b++)
+            for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1] && rcs[(size_t) c] == MRP_OK; k++)
+                for (int64_t j = S.allele_first[b]; j < S.allele_first[b + 1]; j++) {
+                    const int64_t lx = S.allele_len[j], ly = S.sub_len[k];
+                    if (std::min(lx, ly) < PHM_WAVE_MAX_WIDTH) continue;
+                    const bool anchored = ly > sv_threshold || lx > sv_threshold;
+                    anc.clear();
+                    if (anchored) kmer_anchors(S.pool + S.allele_off[j], lx, S.pool + S.sub_off[k], ly, anc);
+                    int width = (int) std::min<int64_t>(std::min(lx, ly) + 1, INT32_MAX);
+                    if (!anc.empty()) {
+                        if (lx + ly >= (1ll << 30)) { rcs[(size_t) c] = mrp_set_error(MRP_ERR_ARG, "%s: strings too long", who); break; }
+                        Lb.resize((size_t) (lx + ly + 1));
+                        Rb.resize((size_t) (lx + ly + 1));
+                        const int rc = band_closed_form(anc.data(), (int64_t) anc.size() / 2, lx, ly, expansion, Lb.data(), Rb.data(), nullptr, &width);
+                        if (rc != MRP_OK) { rcs[(size_t) c] = mrp_set_error(rc, "%s: chunk %lld: a pair of bubble %lld has invalid anchors (pairwiseAligner.c:206-211)", who, (long long) c, (long long) b); break; }
+                    }
+                    if (width > PHM_WAVE_MAX_WIDTH) {
+                        rcs[(size_t) c] = mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: chunk %lld: a pair of bubble %lld has a diagonal of %d cells (limit %d)", who,
+                                                        (long long) c, (long long) b, width, PHM_WAVE_MAX_WIDTH);
+                        break;
+                    }
+                }
+        if (rcs[(size_t) c] != MRP_OK) msgs[(size_t) c] = mrp_last_error();
+    });
+    for (int64_t c = 0; c < n_chunks; c++)
+        if (rcs[(size_t) c] != MRP_OK) return mrp_set_error(rcs[(size_t) c], "%s", msgs[(size_t) c].c_str());
+    return MRP_OK;
+}
+
+void mrp_string_front_destroy(mrp_string_front *F) { delete F; }
+
+int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                            int64_t expansion, int64_t sv_threshold, mrp_string_front **front_out) {
+    static const char *who = "mrp_phase_string_chunks";
+    const double t_begin = now_ms();
+    *front_out = nullptr;
+    mrp_string_front *F = new (std::nothrow) mrp_string_front();
+    if (!F) return fail(MRP_ERR_NOMEM, "mrp_phase_string_chunks: out of host memory");
+    struct Drop { mrp_string_front *f; ~Drop() { delete f; } } drop{F}; /* (an early return) */
+    F->n_chunks = n_chunks;
+    F->chunks = chunks;
     /* ---- the pairs of every chunk, one symbol pool: bubble b of chunk c is global bubble bubble_base[c] + b */
-    std::vector<int64_t> pool_base((size_t) n_chunks + 1, 0), bubble_base((size_t) n_chunks + 1, 0), sub_base((size_t) n_chunks + 1, 0);
+    std::vector<int64_t> &pool_base = F->pool_base, &sub_base = F->sub_base, bubble_base((size_t) n_chunks + 1, 0);
+    pool_base.assign((size_t) n_chunks + 1, 0);
+    sub_base.assign((size_t) n_chunks + 1, 0);
     for (int64_t c = 0; c < n_chunks; c++) {
         pool_base[(size_t) c + 1] = pool_base[(size_t) c] + chunks[c].pool_bytes;
         bubble_base[(size_t) c + 1] = bubble_base[(size_t) c] + chunks[c].n_bubbles;
         sub_base[(size_t) c + 1] = sub_base[(size_t) c] + (chunks[c].n_bubbles ? chunks[c].sub_first[chunks[c].n_bubbles] : 0);
     }
     const int64_t n_bub = bubble_base[(size_t) n_chunks], n_subs = sub_base[(size_t) n_chunks];
-    HostVec<uint8_t> gpool((size_t) pool_base[(size_t) n_chunks]);
-    std::vector<int64_t> g_sub_first((size_t) n_bub + 1, 0), g_sub_off((size_t) n_subs);
-    std::vector<int32_t> g_sub_len((size_t) n_subs);
+    HostVec<uint8_t> &gpool = F->gpool;
+    gpool.resize((size_t) pool_base[(size_t) n_chunks]);
+    mrp_string_front::Scratch &X = F->scratch;
+    std::vector<int64_t> &g_sub_first = X.g_sub_first, &g_sub_off = X.g_sub_off;
+    std::vector<int32_t> &g_sub_len = X.g_sub_len;
+    g_sub_first.assign((size_t) n_bub + 1, 0);
+    g_sub_off.resize((size_t) n_subs);
+    g_sub_len.resize((size_t) n_subs);
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
         const mrp_string_chunk &S = chunks[c];
         if (S.pool_bytes) memcpy(gpool.data() + pool_base[(size_t) c], S.pool, (size_t) S.pool_bytes);
@@ -1371,10 +1473,11 @@ int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string
         }
     });
     /* cachedScores (bubbleGraph.c:1418,1431-1441): the first substring of the bubble with given symbols owns the scores */
-    std::vector<int64_t> owner;
+    std::vector<int64_t> &owner = X.owner;
     substring_owners(n_bub, g_sub_first.data(), gpool.data(), g_sub_off.data(), g_sub_len.data(), nullptr, false, owner);
     /* the owners' pairs, chunk by chunk in parallel: pair_first[k] = the pair of owner k with the bubble's allele 0 */
-    std::vector<int64_t> pair_base((size_t) n_chunks + 1, 0), pair_first((size_t) n_subs, -1);
+    std::vector<int64_t> pair_base((size_t) n_chunks + 1, 0), &pair_first = F->pair_first;
+    pair_first.assign((size_t) n_subs, -1);
     for (int64_t c = 0; c < n_chunks; c++) {
         const mrp_string_chunk &S = chunks[c];
         int64_t np = 0;
@@ -1385,10 +1488,13 @@ int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string
     }
     const int64_t n_pairs = pair_base[(size_t) n_chunks];
     if (n_pairs >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
-    std::vector<int64_t> xo((size_t) n_pairs), yo((size_t) n_pairs), anchor_off((size_t) n_pairs + 1, 0);
-    std::vector<int32_t> xl((size_t) n_pairs), yl((size_t) n_pairs);
-    std::vector<uint8_t> mi((size_t) n_pairs);
-    std::vector<std::vector<int64_t>> chunk_anchors((size_t) n_chunks);
+    std::vector<int64_t> &xo = X.xo, &yo = X.yo, &anchor_off = X.anchor_off;
+    std::vector<int32_t> &xl = X.xl, &yl = X.yl;
+    std::vector<uint8_t> &mi = X.mi;
+    std::vector<std::vector<int64_t>> &chunk_anchors = X.chunk_anchors;
+    xo.resize((size_t) n_pairs); yo.resize((size_t) n_pairs); xl.resize((size_t) n_pairs); yl.resize((size_t) n_pairs); mi.resize((size_t) n_pairs);
+    anchor_off.assign((size_t) n_pairs + 1, 0);
+    chunk_anchors.resize((size_t) n_chunks);
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
         const mrp_string_chunk &S = chunks[c];
         const int64_t pb = pool_base[(size_t) c], sb = sub_base[(size_t) c];
@@ -1411,15 +1517,36 @@ int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string
                 }
             }
     });
-    std::vector<int64_t> anchors;
+    std::vector<int64_t> &anchors = X.anchors;
     for (int64_t p = 0; p < n_pairs; p++) anchor_off[(size_t) p + 1] += anchor_off[(size_t) p];
     for (auto &v : chunk_anchors) anchors.insert(anchors.end(), v.begin(), v.end());
     for (int64_t k = 0; k < n_subs; k++) /* duplicates read their owner's pairs */
         if (owner[(size_t) k] != k) pair_first[(size_t) k] = pair_first[(size_t) owner[(size_t) k]];
 
+    F->n_subs = n_subs;
+    F->n_pairs = n_pairs;
+    if (n_pairs > 0) {
+        const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
+        const int rc = phm_classify(who, models, 2, n_pairs, (int64_t) gpool.size(), xo.data(), xl.data(), yo.data(), yl.data(), mi.data(),
+                                    anchors.empty() ? nullptr : anchor_off.data(), anchors.empty() ? nullptr : anchors.data(), expansion, 0, 0, F->L);
+        if (rc != MRP_OK) return rc;
+    }
+    F->front_ms = now_ms() - t_begin;
+    drop.f = nullptr;
+    *front_out = F;
+    return MRP_OK;
+}
+
+int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                         mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                         mrp_string_chunks_stats *stats) {
+    const double t_begin = now_ms();
+    const int64_t n_chunks = F->n_chunks, n_subs = F->n_subs, n_pairs = F->n_pairs;
+    const mrp_string_chunk *chunks = F->chunks;
+    const std::vector<int64_t> &sub_base = F->sub_base, &pair_first = F->pair_first;
+    const HostVec<uint8_t> &gpool = F->gpool;
     PHM_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
     /* device buffers first: they are released after the stream has drained (Drain below runs before their destructors) */
     DevBuf<ScByteItem> d_items;
     DevBuf<uint8_t> d_pool;
@@ -1448,11 +1575,9 @@ int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string
         }
     } cleanup{s, dch, res};
     for (hipEvent_t &x : ev.e) PHM_HIP(hipEventCreate(&x));
-    PhmLaunch L;
+    PhmLaunch &L = F->L;
     if (n_pairs > 0) {
-        const int rc = phm_launch(ctx, who, models, 2, n_pairs, gpool.data(), (int64_t) gpool.size(), xo.data(), xl.data(), yo.data(), yl.data(), mi.data(),
-                                  anchors.empty() ? nullptr : anchor_off.data(), anchors.empty() ? nullptr : anchors.data(), expansion, 0, 0, L,
-                                  stats ? &stats->pairhmm : nullptr);
+        const int rc = phm_enqueue(ctx, gpool.data(), (int64_t) gpool.size(), n_pairs, L, stats ? &stats->pairhmm : nullptr);
         if (rc != MRP_OK) return rc;
     } else {
         PHM_HIP(hipEventRecord(ctx->ev[0], s));
@@ -1636,10 +1761,41 @@ int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string
     for (mrp_chunk *&ch : dch) { delete ch; ch = nullptr; }
     ctx->pool.reclaim();
     if (stats) {
-        stats->total_ms = now_ms() - t_begin;
+        stats->total_ms = F->front_ms + (now_ms() - t_begin);
         stats->host_ms = stats->total_ms - (t_phase1 - t_phase0);
     }
     return MRP_OK;
+}
+
+extern "C" {
+
+int mrp_string_chunk_units(const mrp_string_chunk *chunk, int64_t *units_out) {
+    if (!chunk || !units_out || chunk->n_bubbles < 0 || (chunk->n_bubbles > 0 && !chunk->sub_first))
+        return mrp_set_error(MRP_ERR_ARG, "mrp_string_chunk_units: null argument or bad sizes");
+    *units_out = chunk->n_bubbles ? chunk->sub_first[chunk->n_bubbles] : 0;
+    return MRP_OK;
+}
+
+int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model,
+                            const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
+                            const mrp_params *params, int64_t min_phred, mrp_phase_result **out, int8_t *const *hap_out,
+                            double *const *phred_out, mrp_profile_out *profiles_out, mrp_string_chunks_stats *stats) {
+    const double t_begin = now_ms();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    /* ---- checks (host only, before the context: a malformed call is refused the same with or without a device) */
+    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out);
+    if (rc != MRP_OK) return rc;
+    if (!ctx) return fail(MRP_ERR_NO_DEVICE, "mrp_phase_string_chunks: no context (the pair-HMM path has no CPU fallback)");
+    for (int64_t c = 0; c < n_chunks; c++) out[c] = nullptr;
+    if (profiles_out) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
+    if (n_chunks == 0) return MRP_OK;
+    mrp_string_front *F = nullptr;
+    rc = mrp_string_front_create(n_chunks, chunks, forward_model, reverse_model, expansion, sv_threshold, &F);
+    if (rc != MRP_OK) return rc;
+    F->front_ms = now_ms() - t_begin;
+    rc = mrp_string_front_run(ctx, F, het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, stats);
+    mrp_string_front_destroy(F);
+    return rc;
 }
 
 }  // extern "C"

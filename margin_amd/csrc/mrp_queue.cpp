@@ -8,6 +8,8 @@
  * what one mrp_phase_reads_many call phases; its chunks share kernel launches), upload them, phase them and write the
  * results at the chunks' positions of the caller's array.  No collective, no device-to-device traffic.  The uploads of a
  * worker's next batch run on a second stream while the current batch is phased; every worker has its own host thread pool.
+ * The same queue takes the chunks as read and allele strings (mrp_queue_phase_string_chunks): a batch is then what one
+ * mrp_phase_string_chunks call phases, and what runs beside the current batch is the host front of the next one.
  */
 #include <hip/hip_runtime.h>
 
@@ -304,13 +306,93 @@ static bool device_cpuset(int device, cpu_set_t *set) {
     return n > 0;
 }
 
+/* What one call of the queue keeps beside its batches, whichever input they are made of (profile bytes: mrp_queue_phase_chunks,
+ * strings: mrp_queue_phase_string_chunks): the lanes' contexts and pools, one error text per lane and ROLE (the call and the work
+ * for the next batch run on two threads at a time), what each lane did. */
+struct QueueCall {
+    struct PerLane { int64_t chunks = 0, units = 0, fallback = 0; double busy_ms = 0; };
+    mrp_queue *q;
+    int64_t n_batches;
+    int active_lanes;
+    std::vector<std::string> errs, stage_errs;
+    std::vector<PerLane> per;
+    std::vector<void *> caller_pool; /* (lane 0 may run on the caller's thread: its pool comes back at the end) */
+    std::mutex pool_mu;
+    std::chrono::steady_clock::time_point t_call = std::chrono::steady_clock::now();
+    const bool timing = getenv("MRP_TIMING") != nullptr;
+
+    QueueCall(mrp_queue *queue, int64_t batches, int lanes_in_use)
+        : q(queue), n_batches(batches), active_lanes(lanes_in_use), errs(queue->ctx.size()), stage_errs(queue->ctx.size()), per(queue->ctx.size()),
+          caller_pool(queue->ctx.size(), nullptr) {}
+    double since() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); }
+
+    /* the lane's context (and, for uploads beside the call, a second one on the same device) and its device's host pool, made
+     * on first use and kept between calls */
+    int lane_begin(int w, bool with_stage_ctx) {
+        const int lanes = q->lanes, d = w / lanes; /* the device this lane works for */
+        const int n_devices = (int) q->devices.size();
+        int r = MRP_OK;
+        if (!q->ctx[(size_t) w]) r = mrp_context_create(q->devices[(size_t) d], &q->ctx[(size_t) w]);
+        if (r == MRP_OK && with_stage_ctx && !q->stage_ctx[(size_t) w]) r = mrp_context_create(q->devices[(size_t) d], &q->stage_ctx[(size_t) w]);
+        if (r == MRP_OK) {
+            std::lock_guard<std::mutex> lk(pool_mu);
+            if (!q->pools[(size_t) d]) {
+                q->pools[(size_t) d] = mrp_host_pool_create(q->threads_per_device);
+                if (!q->pools[(size_t) d]) r = mrp_set_error(MRP_ERR_NOMEM, "out of host memory");
+            }
+        }
+        if (r != MRP_OK) { errs[(size_t) w] = mrp_last_error(); return r; }
+        if (lanes > 1) (void) mrp_context_set_grouped(q->ctx[(size_t) w], 1); /* the lanes of a device are concurrent batches of it */
+        q->ctx[(size_t) w]->calls_sharing_device = n_batches > (int64_t) n_devices ? active_lanes : 1;
+        caller_pool[(size_t) w] = mrp_pool_current();
+        mrp_pool_adopt(q->pools[(size_t) d]);
+        /* the lanes of a device share it: a call of a long queue runs 8 / lanes concurrent batches, the one call of a short
+         * queue as many as its size asks for */
+        (void) mrp_context_set_phase_groups(q->ctx[(size_t) w], n_batches > (int64_t) n_devices ? std::max(1, 8 / active_lanes) : 0);
+        return (int) MRP_OK;
+    }
+    void lane_end(int w) { mrp_pool_adopt(caller_pool[(size_t) w]); }
+
+    /* runs the lanes; when the queue drives more than one device, each on the CPUs next to its device */
+    int run(const LaneHooks &hk) {
+        const int n_devices = (int) q->devices.size(), lanes = q->lanes;
+        const char *aff_env = getenv("MRP_QUEUE_AFFINITY");
+        const bool bind = n_devices > 1 && !(aff_env && aff_env[0] == '0');
+        /* before the first thread of a worker is created (they inherit it): the CPUs next to its device */
+        std::function<void(int)> on_start;
+        if (bind) on_start = [this, lanes](int w) {
+            cpu_set_t set;
+            if (device_cpuset(q->devices[(size_t) (w / lanes)], &set)) (void) pthread_setaffinity_np(pthread_self(), sizeof(set), &set);
+        };
+        const int rc = run_lanes(n_devices, lanes, active_lanes, n_batches, hk, /* the caller's own affinity is left alone */ bind, on_start);
+        if (timing) fprintf(stderr, "  [%7.1f] queue: workers joined\n", since());
+        return rc;
+    }
+    void fill(mrp_queue_stats *stats) const {
+        if (!stats) return;
+        for (size_t w = 0; w < per.size(); w++) {
+            const size_t d = w / (size_t) q->lanes;
+            stats->chunks_per_device[d] += per[w].chunks;
+            stats->units_per_device[d] += per[w].units;
+            stats->busy_ms_per_device[d] = std::max(stats->busy_ms_per_device[d], per[w].busy_ms);
+            stats->fallback_chunks += per[w].fallback;
+        }
+    }
+    int error(int rc) const { /* the first error text: the calls' before the staging threads' */
+        for (auto &e : errs)
+            if (!e.empty()) return mrp_set_error(rc, "%s", e.c_str());
+        for (auto &e : stage_errs)
+            if (!e.empty()) return mrp_set_error(rc, "%s", e.c_str());
+        return mrp_set_error(rc, "work queue stopped");
+    }
+};
+
 extern "C" {
 
 int mrp_queue_phase_chunks(mrp_queue *q, int64_t n_chunks, const mrp_chunk_desc *chunks, const mrp_params *params, int64_t chunks_per_batch,
                            mrp_phase_result **out, mrp_queue_stats *stats) {
     if (!q || n_chunks < 0 || !params || (n_chunks > 0 && (!chunks || !out))) return mrp_set_error(MRP_ERR_ARG, "mrp_queue_phase_chunks: bad arguments");
     const int n_devices = (int) q->devices.size();
-    const int32_t *devices = q->devices.data();
     if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = n_devices; }
     for (int64_t i = 0; i < n_chunks; i++) out[i] = nullptr;
     if (n_chunks == 0) return MRP_OK;
@@ -327,14 +409,9 @@ int mrp_queue_phase_chunks(mrp_queue *q, int64_t n_chunks, const mrp_chunk_desc 
     const int64_t n_batches = (int64_t) plan.batch_off.size() - 1;
     if (stats) stats->batches = n_batches;
 
-    /* one error text per lane and ROLE: the call (phase) and the upload of the next batch (prefetch) run on two threads at a time */
-    std::vector<std::string> errs((size_t) n_workers), stage_errs((size_t) n_workers);
-    struct PerDev { int64_t chunks = 0, units = 0, fallback = 0; double busy_ms = 0, stage_wait_ms = 0; };
-    std::vector<PerDev> per((size_t) n_workers);
-    std::mutex pool_mu;
-    const int active_lanes = active_lanes_of(plan, cost.data(), n_devices, lanes);
-    const char *aff_env = getenv("MRP_QUEUE_AFFINITY");
-    const bool bind = n_devices > 1 && !(aff_env && aff_env[0] == '0');
+    QueueCall call(q, n_batches, active_lanes_of(plan, cost.data(), n_devices, lanes));
+    std::vector<std::string> &errs = call.errs, &stage_errs = call.stage_errs;
+    std::vector<QueueCall::PerLane> &per = call.per;
 
     /* the chunks of one batch on the device (uploads queued on the staging context's stream; the chunks carry the event that
      * ends the upload, the first device work that reads one waits for it) */
@@ -343,11 +420,10 @@ int mrp_queue_phase_chunks(mrp_queue *q, int64_t n_chunks, const mrp_chunk_desc 
         int64_t first = 0, count = 0;
         std::vector<mrp_chunk *> dch;
     };
-    struct Lane { Staged st[2]; int n_staged = 0; void *caller_pool = nullptr; };
+    struct Lane { Staged st[2]; int n_staged = 0; };
     std::vector<Lane> lane_state((size_t) n_workers);
-    const bool timing = getenv("MRP_TIMING") != nullptr;
-    const auto t_call = std::chrono::steady_clock::now();
-    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); };
+    const bool timing = call.timing;
+    auto since = [&]() { return call.since(); };
     auto drop = [&](Staged *st) { /* (a thousand chunks of a one-call queue: on the lane's pool, not one after the other) */
         mrp_parallel_for((int64_t) st->dch.size(), 8, [&](int64_t i) { if (st->dch[(size_t) i]) mrp_chunk_destroy(st->dch[(size_t) i]); });
         st->dch.clear();
@@ -358,28 +434,7 @@ int mrp_queue_phase_chunks(mrp_queue *q, int64_t n_chunks, const mrp_chunk_desc 
         return L.st[0].batch.load() == b ? &L.st[0] : (L.st[1].batch.load() == b ? &L.st[1] : nullptr);
     };
     LaneHooks hk;
-    hk.begin = [&](int w) {
-        const int d = w / lanes; /* the device this lane works for */
-        int r = MRP_OK;
-        if (!q->ctx[(size_t) w]) r = mrp_context_create(devices[d], &q->ctx[(size_t) w]);
-        if (r == MRP_OK && !q->stage_ctx[(size_t) w]) r = mrp_context_create(devices[d], &q->stage_ctx[(size_t) w]);
-        if (r == MRP_OK) {
-            std::lock_guard<std::mutex> lk(pool_mu);
-            if (!q->pools[(size_t) d]) {
-                q->pools[(size_t) d] = mrp_host_pool_create(q->threads_per_device);
-                if (!q->pools[(size_t) d]) r = mrp_set_error(MRP_ERR_NOMEM, "out of host memory");
-            }
-        }
-        if (r != MRP_OK) { errs[(size_t) w] = mrp_last_error(); return r; }
-        if (lanes > 1) (void) mrp_context_set_grouped(q->ctx[(size_t) w], 1); /* the lanes of a device are concurrent batches of it */
-        q->ctx[(size_t) w]->calls_sharing_device = n_batches > (int64_t) n_devices ? active_lanes : 1;
-        lane_state[(size_t) w].caller_pool = mrp_pool_current(); /* (lane 0 may run on the caller's thread: its pool comes back at the end) */
-        mrp_pool_adopt(q->pools[(size_t) d]);
-        /* the lanes of a device share it: a call of a long queue runs 8 / lanes concurrent batches, the one call of a short
-         * queue as many as its size asks for */
-        (void) mrp_context_set_phase_groups(q->ctx[(size_t) w], n_batches > (int64_t) n_devices ? std::max(1, 8 / active_lanes) : 0);
-        return (int) MRP_OK;
-    };
+    hk.begin = [&](int w) { return call.lane_begin(w, true); };
     hk.prefetch = [&](int w, int64_t b) { /* (the first batch on the lane's thread, the later ones on a thread beside the call) */
         const auto ts0 = std::chrono::steady_clock::now();
         const int d = w / lanes;
@@ -438,30 +493,12 @@ int mrp_queue_phase_chunks(mrp_queue *q, int64_t n_chunks, const mrp_chunk_desc 
         if (Staged *st = staged_of(w, b)) drop(st);
         per[(size_t) w].busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     };
-    hk.end = [&](int w) { mrp_pool_adopt(lane_state[(size_t) w].caller_pool); };
-    /* before the first thread of a worker is created (they inherit it): the CPUs next to its device */
-    std::function<void(int)> on_start;
-    if (bind) on_start = [&](int w) {
-        cpu_set_t set;
-        if (device_cpuset(devices[w / lanes], &set)) (void) pthread_setaffinity_np(pthread_self(), sizeof(set), &set);
-    };
-    int rc = run_lanes(n_devices, lanes, active_lanes, n_batches, hk, /* the caller's own affinity is left alone */ bind, on_start);
-    if (timing) fprintf(stderr, "  [%7.1f] queue: workers joined\n", since());
-    if (stats)
-        for (int w = 0; w < n_workers; w++) {
-            const int d = w / lanes;
-            stats->chunks_per_device[d] += per[(size_t) w].chunks;
-            stats->units_per_device[d] += per[(size_t) w].units;
-            stats->busy_ms_per_device[d] = std::max(stats->busy_ms_per_device[d], per[(size_t) w].busy_ms);
-            stats->fallback_chunks += per[(size_t) w].fallback;
-        }
+    hk.end = [&](int w) { call.lane_end(w); };
+    const int rc = call.run(hk);
+    call.fill(stats);
     if (rc != MRP_OK) {
         for (int64_t i = 0; i < n_chunks; i++) { mrp_phase_result_destroy(out[i]); out[i] = nullptr; }
-        for (auto &e : errs)
-            if (!e.empty()) return mrp_set_error(rc, "%s", e.c_str());
-        for (auto &e : stage_errs)
-            if (!e.empty()) return mrp_set_error(rc, "%s", e.c_str());
-        return mrp_set_error(rc, "work queue stopped");
+        return call.error(rc);
     }
     return MRP_OK;
 }
@@ -471,6 +508,136 @@ int mrp_phase_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64
     mrp_queue *q = nullptr;
     int rc = mrp_queue_create(devices, n_devices, &q);
     if (rc == MRP_OK) rc = mrp_queue_phase_chunks(q, n_chunks, chunks, params, chunks_per_batch, out, stats);
+    mrp_queue_destroy(q);
+    return rc;
+}
+
+int mrp_queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model,
+                                  const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
+                                  const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out,
+                                  double *const *phred_out, mrp_profile_out *profiles_out, mrp_queue_stats *stats) {
+    /* ---- every chunk's checks first, on the caller's thread and in the one call's order: no lane starts on a call that would be refused */
+    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out);
+    if (rc != MRP_OK) return rc;
+    if (!q) return mrp_set_error(MRP_ERR_NO_DEVICE, "mrp_queue_phase_string_chunks: no queue (the pair-HMM path has no CPU fallback)");
+    const int n_devices = (int) q->devices.size();
+    if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = n_devices; }
+    for (int64_t i = 0; i < n_chunks; i++) out[i] = nullptr;
+    if (profiles_out) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
+    rc = mrp_string_chunks_check_pairs(n_chunks, chunks, expansion, sv_threshold);
+    if (rc != MRP_OK) return rc;
+    if (n_chunks == 0) return MRP_OK;
+    /* phase.c:257-263 orders by estimated depth; here a chunk costs its (read, bubble) units, the unit the batches are cut by */
+    std::vector<int64_t> cost((size_t) n_chunks, 0);
+    for (int64_t i = 0; i < n_chunks; i++) (void) mrp_string_chunk_units(&chunks[i], &cost[(size_t) i]);
+    const int lanes = q->lanes, n_workers = n_devices * lanes;
+    const QueuePlan plan = plan_queue(n_chunks, cost.data(), chunks_per_batch, n_workers, n_devices);
+    const int64_t n_batches = (int64_t) plan.batch_off.size() - 1;
+    if (stats) stats->batches = n_batches;
+    QueueCall call(q, n_batches, active_lanes_of(plan, cost.data(), n_devices, lanes));
+
+    /* a batch as one mrp_phase_string_chunks call sees it: its chunks side by side, and the host front made of them (prefetch:
+     * beside the device work of the lane's current batch; the uploads follow on the lane's own stream when the batch is run) */
+    struct Staged {
+        std::atomic<int64_t> batch{-1}; /* (the call's thread looks its batch up while the stager fills the lane's OTHER slot) */
+        int64_t first = 0, count = 0;
+        std::vector<mrp_string_chunk> sc;
+        mrp_string_front *front = nullptr;
+    };
+    struct Lane { Staged st[2]; int n_staged = 0; };
+    std::vector<Lane> lane_state((size_t) n_workers);
+    auto staged_of = [&](int w, int64_t b) -> Staged * {
+        Lane &L = lane_state[(size_t) w];
+        return L.st[0].batch.load() == b ? &L.st[0] : (L.st[1].batch.load() == b ? &L.st[1] : nullptr);
+    };
+    auto drop = [&](Staged *st) { mrp_string_front_destroy(st->front); st->front = nullptr; st->batch = -1; };
+    auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    LaneHooks hk;
+    hk.begin = [&](int w) { return call.lane_begin(w, false); };
+    hk.prefetch = [&](int w, int64_t b) {
+        const auto t0 = std::chrono::steady_clock::now();
+        mrp_pool_adopt(q->pools[(size_t) (w / lanes)]);
+        Lane &L = lane_state[(size_t) w];
+        Staged *st = &L.st[L.n_staged++ & 1];
+        st->first = plan.batch_off[(size_t) b]; st->count = plan.batch_off[(size_t) b + 1] - st->first;
+        st->sc.resize((size_t) st->count);
+        for (int64_t i = 0; i < st->count; i++) st->sc[(size_t) i] = chunks[plan.order[(size_t) (st->first + i)]];
+        st->batch.store(b);
+        const int r = mrp_string_front_create(st->count, st->sc.data(), forward_model, reverse_model, expansion, sv_threshold, &st->front);
+        if (r != MRP_OK) call.stage_errs[(size_t) w] = mrp_last_error();
+        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: front of batch %lld (%lld chunks) in %.1f ms\n", call.since(), w, (long long) b, (long long) st->count, ms_since(t0));
+        return r;
+    };
+    hk.discard = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
+    hk.phase = [&](int w, int64_t b) {
+        Staged *cur = staged_of(w, b);
+        if (!cur || !cur->front) { call.errs[(size_t) w] = "work queue: batch has no front"; return (int) MRP_ERR_ARG; }
+        const auto t0 = std::chrono::steady_clock::now();
+        const int64_t count = cur->count;
+        std::vector<mrp_phase_result *> res((size_t) count, nullptr);
+        std::vector<int8_t *> hap((size_t) count);
+        std::vector<double *> phred((size_t) count);
+        std::vector<mrp_profile_out> prof(profiles_out ? (size_t) count : 0);
+        if (profiles_out) memset(prof.data(), 0, sizeof(mrp_profile_out) * prof.size());
+        for (int64_t i = 0; i < count; i++) {
+            const int64_t chunk = plan.order[(size_t) (cur->first + i)];
+            hap[(size_t) i] = hap_out[chunk];
+            if (phred_out) phred[(size_t) i] = phred_out[chunk];
+        }
+        mrp_string_chunks_stats ss;
+        memset(&ss, 0, sizeof(ss));
+        const int r = mrp_string_front_run(q->ctx[(size_t) w], cur->front, het_substitution_probability, params, min_phred, res.data(), hap.data(),
+                                           phred_out ? phred.data() : nullptr, profiles_out ? prof.data() : nullptr, &ss);
+        QueueCall::PerLane &me = call.per[(size_t) w];
+        if (r != MRP_OK) call.errs[(size_t) w] = mrp_last_error();
+        else {
+            for (int64_t i = 0; i < count; i++) {
+                const int64_t chunk = plan.order[(size_t) (cur->first + i)];
+                out[chunk] = res[(size_t) i];
+                if (profiles_out) profiles_out[chunk] = prof[(size_t) i];
+                me.units += cost[(size_t) chunk];
+            }
+            me.chunks += count;
+            me.fallback += ss.phase.resident ? ss.phase.fallback_chunks : count;
+        }
+        const double run_ms = ms_since(t0);
+        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld run in %.1f ms, its front took %.1f ms\n", call.since(), w, (long long) b, run_ms,
+                                 ss.total_ms - run_ms);
+        me.busy_ms += run_ms;
+        return r;
+    };
+    hk.retire = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
+    hk.end = [&](int w) { call.lane_end(w); };
+    rc = call.run(hk);
+    call.fill(stats);
+    if (rc != MRP_OK) {
+        for (int64_t i = 0; i < n_chunks; i++) {
+            mrp_phase_result_destroy(out[i]);
+            out[i] = nullptr;
+            if (profiles_out) {
+                mrp_profile_out &P = profiles_out[i];
+                mrp_free(P.seqs); mrp_free(P.read_of_seq); mrp_free(P.pool); mrp_free(P.allele_number); mrp_free(P.substitution); mrp_free(P.prior);
+                memset(&P, 0, sizeof(P));
+            }
+        }
+        return call.error(rc);
+    }
+    return MRP_OK;
+}
+
+int mrp_phase_string_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_string_chunk *chunks,
+                                       const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                       double het_substitution_probability, const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch,
+                                       mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                                       mrp_queue_stats *stats) {
+    /* (the queue's own order of errors: a malformed call is MRP_ERR_ARG with or without a device) */
+    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out);
+    if (rc != MRP_OK) return rc;
+    mrp_queue *q = nullptr;
+    rc = mrp_queue_create(devices, n_devices, &q);
+    if (rc == MRP_OK)
+        rc = mrp_queue_phase_string_chunks(q, n_chunks, chunks, forward_model, reverse_model, expansion, sv_threshold, het_substitution_probability, params,
+                                           min_phred, chunks_per_batch, out, hap_out, phred_out, profiles_out, stats);
     mrp_queue_destroy(q);
     return rc;
 }

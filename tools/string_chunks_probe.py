@@ -4,11 +4,26 @@ arguments or converts results is outside); the chain's steps are timed one by on
 writes them all to --out.
 
     python tools/string_chunks_probe.py [--small 96] [--large 12] [--reps 3] [--out profiles/string_chunks/probe.json]
+
+--queue measures the work queue over string chunks instead (mrp_queue_phase_string_chunks) on the same two shapes and on a long
+queue (the first shape repeated to --long chunks), three ways on device 0: (a) ONE mrp_phase_string_chunks call over all chunks,
+the yardstick -- of the library given with --yardstick-lib (a libmargin_rphmm.so built from the commit before the queue took
+strings), else of this build; (b) the queue with MRP_QUEUE_LANES=1; (c) the queue with its default lanes -- both with the
+library's own batches (chunks_per_batch = 0), which for queues of these sizes are ONE batch, so that no second lane starts; and
+therefore (d) the default lanes with batches of --lane-batch chunks, where the lanes and the front made ahead do run.  Each leg is a process
+of its own, one after the other (the lane count is read when a queue is made, a second library needs its own process): a
+warm-up call, then --reps timed calls, host wall time around the C call alone; the legs are run --rounds times in turn and a
+leg's figure is the median over the timed calls of all its processes, its spread (max - min) / median over the same calls; the
+legs' outputs are compared through a digest taken outside the timed region.  Prints one JSON line and writes it to --out (default profiles/string_chunks/queue.json).
+
+    python tools/string_chunks_probe.py --queue [--yardstick-lib PATH] [--long 1536] [--lane-batch 192] [--reps 3]
 """
 import argparse
 import ctypes as C
+import hashlib
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -122,19 +137,179 @@ def run_shape(ctx, name, chunks, reps, f, r, params):
                 speedup=round(wc / wn, 3), hp_coverage_matches=bool(parity))
 
 
+def probe_shapes(small, large, long_n=0):
+    shapes = [("config2_130_sites", [synth.make_string_chunk(seed=1000 + i, n_sites=130, coverage=30, allele_len=25) for i in range(small)]),
+              ("2000_sites", [synth.make_string_chunk(seed=2000 + i, n_sites=2000, coverage=30, allele_len=25, span=(10, 60)) for i in range(large)])]
+    if long_n:
+        shapes.append(("config2_130_sites_long", [shapes[0][1][i % small] for i in range(long_n)]))
+    return shapes
+
+
+def digest(rows):
+    """every output of every chunk, in input order"""
+    h = hashlib.sha256()
+    for d in rows:
+        g = d["result"]
+        for k in sorted(g):
+            v = g[k]
+            h.update(np.ascontiguousarray(v).tobytes() if isinstance(v, np.ndarray) else repr(v).encode())
+        h.update(d["hap"].tobytes())
+        h.update(d["phred"].tobytes())
+    return h.hexdigest()
+
+
+def queue_leg(a):
+    """one leg in this process: per shape a warm-up and a.reps timed C calls -> JSON file a.leg_out"""
+    t, tr, em = synth.margin_phase_pair_hmm_arrays()
+    f = capi.PairHmm.from_margin_hmm(t, tr, em)
+    r = f.reverse_complement()
+    params = capi.Params.from_reference_names(synth.shipped_phase_params())
+    L = capi.load()
+    if a.host_threads:
+        capi._check(L.mrp_set_host_threads(a.host_threads))
+    ctx = q = None
+    if a.queue_leg == "a":
+        Y = L
+        if a.yardstick_lib:  # the yardstick's own library beside this build's (which serves the host-only helpers above)
+            Y = C.CDLL(a.yardstick_lib)
+            Y.mrp_runtime_init()
+            Y.mrp_context_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+            Y.mrp_context_destroy.argtypes = [C.c_void_p]
+            Y.mrp_context_destroy.restype = None
+            Y.mrp_phase_string_chunks.argtypes = L.mrp_phase_string_chunks.argtypes
+            Y.mrp_phase_result_destroy.argtypes = L.mrp_phase_result_destroy.argtypes
+            Y.mrp_phase_result_destroy.restype = None
+            Y.mrp_last_error.restype = C.c_char_p
+        ctx = C.c_void_p()
+        if Y.mrp_context_create(0, C.byref(ctx)) != capi.MRP_OK:
+            raise RuntimeError(Y.mrp_last_error().decode())
+    else:
+        q = capi.Queue([0])
+    rows = []
+    per_batch = a.lane_batch if a.queue_leg == "d" else 0
+    for name, chunks in probe_shapes(a.small, a.large, a.long):
+        built = {id(c): capi.string_chunk_struct(c) for c in chunks}
+        structs = [built[id(c)] for c in chunks]
+        units = sum(capi.string_chunk_units(c, struct=built[id(c)]) for c in chunks)
+        times, extra, dig = [], {}, None
+        for rep in range(a.reps + 1):
+            args = capi.StringChunkArgs(chunks, False, structs)
+            if ctx is not None:
+                st = capi.StringChunksStats()
+                t0 = time.perf_counter()
+                rc = Y.mrp_phase_string_chunks(ctx, args.n, args.arr, C.byref(f), C.byref(r), 4, 512, 0.0, C.byref(params), 0, args.res, args.hp, args.pp, None,
+                                               C.byref(st))
+                ms = 1e3 * (time.perf_counter() - t0)
+                if rc != capi.MRP_OK:
+                    raise RuntimeError(Y.mrp_last_error().decode())
+                info = dict(host_ms=round(st.host_ms, 2), phase_ms=round(st.total_ms - st.host_ms, 2), pairhmm_kernel_ms=round(st.pairhmm.kernel_ms, 2))
+            else:
+                st = capi.QueueStats()
+                t0 = time.perf_counter()
+                rc = L.mrp_queue_phase_string_chunks(q.h, args.n, args.arr, C.byref(f), C.byref(r), 4, 512, 0.0, C.byref(params), 0, per_batch, args.res, args.hp, args.pp,
+                                                     None, C.byref(st))
+                ms = 1e3 * (time.perf_counter() - t0)
+                capi._check(rc)
+                info = dict(batches=int(st.batches), busy_ms_device0=round(st.busy_ms_per_device[0], 2), fallback_chunks=int(st.fallback_chunks))
+            if rep == 0:  # the warm-up call: its outputs are the ones compared (read through this build's binding either way)
+                dig = digest(args.results())
+            else:
+                for i in range(args.n):
+                    (Y if ctx is not None else L).mrp_phase_result_destroy(args.res[i])
+                times.append(ms)
+                extra[ms] = info
+        med = sorted(times)[len(times) // 2]
+        rows.append(dict(shape=name, chunks=len(chunks), units=int(units), reps_ms=[round(x, 2) for x in times], median_ms=round(med, 2),
+                         spread_pct=round(100.0 * (max(times) - min(times)) / med, 1), digest=dig, **extra[med]))
+        print(f"leg {a.queue_leg} {name}: {rows[-1]['reps_ms']} ms", file=sys.stderr, flush=True)
+    if ctx is not None:
+        Y.mrp_context_destroy(ctx)
+    else:
+        q.close()
+    with open(a.leg_out, "w") as fh:
+        json.dump(rows, fh)
+
+
+def cpu_model():
+    try:
+        with open("/proc/cpuinfo") as fh:
+            for line in fh:
+                if line.startswith("model name"):
+                    return line.split(":", 1)[1].strip()
+    except OSError:
+        pass
+    return "unknown"
+
+
+def queue_probe(a):
+    out = a.out or os.path.join(ROOT, "profiles", "string_chunks", "queue.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    runs = {}
+    for leg, env_extra in [("a", {}), ("b", {"MRP_QUEUE_LANES": "1"}), ("c", {}), ("d", {})] * a.rounds:
+        env = {k: v for k, v in os.environ.items() if k != "MRP_QUEUE_LANES"}
+        env.update(env_extra)
+        path = f"{out}.leg_{leg}"
+        cmd = [sys.executable, os.path.abspath(__file__), "--queue-leg", leg, "--leg-out", path, "--small", str(a.small), "--large", str(a.large),
+               "--long", str(a.long), "--lane-batch", str(a.lane_batch), "--reps", str(a.reps), "--host-threads", str(a.host_threads)]
+        if leg == "a" and a.yardstick_lib:
+            cmd += ["--yardstick-lib", os.path.abspath(a.yardstick_lib)]
+        subprocess.run(cmd, check=True, env=env, timeout=a.leg_timeout, cwd=ROOT)  # one GPU process at a time; a failed leg ends the probe
+        with open(path) as fh:
+            runs.setdefault(leg, []).append(json.load(fh))
+        os.remove(path)
+    legs = {}
+    for leg, per_process in runs.items():  # a leg's processes as one sample: the median and the spread over all their timed calls
+        legs[leg] = []
+        for rows in zip(*per_process):
+            times = sorted(t for r in rows for t in r["reps_ms"])
+            med = times[len(times) // 2]
+            at_median = min(rows, key=lambda r: abs(r["median_ms"] - med))
+            row = dict(at_median, reps_ms=[r["reps_ms"] for r in rows], process_medians_ms=[r["median_ms"] for r in rows], median_ms=med,
+                       spread_pct=round(100.0 * (times[-1] - times[0]) / med, 1), digest=rows[0]["digest"] if len({r["digest"] for r in rows}) == 1 else None)
+            legs[leg].append(row)
+    shapes = []
+    strip = lambda d: {k: v for k, v in d.items() if k not in ("shape", "chunks", "units", "digest")}
+    for ra, rb, rc, rd in zip(legs["a"], legs["b"], legs["c"], legs["d"]):
+        shapes.append(dict(shape=ra["shape"], chunks=ra["chunks"], units=ra["units"], one_call=strip(ra), queue_1_lane=strip(rb), queue_default_lanes=strip(rc),
+                           queue_default_lanes_caller_batches=strip(rd), queue_caller_batches_over_one_call=round(rd["median_ms"] / ra["median_ms"], 3),
+                           queue_1_lane_over_one_call=round(rb["median_ms"] / ra["median_ms"], 3),
+                           queue_default_lanes_over_one_call=round(rc["median_ms"] / ra["median_ms"], 3),
+                           outputs_equal=bool(ra["digest"] is not None and ra["digest"] == rb["digest"] == rc["digest"] == rd["digest"])))
+    row = dict(probe="string_chunks_queue", device=0, cpu=cpu_model(), reps=a.reps, processes_per_leg=a.rounds, caller_batch=a.lane_batch, host_threads=a.host_threads or "library default",
+               yardstick="mrp_phase_string_chunks of " + ("the library given as --yardstick-lib" if a.yardstick_lib else "this build"), shapes=shapes)
+    print(json.dumps(row), flush=True)
+    with open(out, "w") as fh:
+        fh.write(json.dumps(row) + "\n")
+    if not all(s["outputs_equal"] for s in shapes):
+        raise SystemExit("the legs' outputs differ")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--small", type=int, default=96, help="chunks of the config-2 shape")
     ap.add_argument("--large", type=int, default=12, help="chunks of 2 000 sites")
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "string_chunks", "probe.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/string_chunks/probe.json, with --queue profiles/string_chunks/queue.json")
+    ap.add_argument("--queue", action="store_true", help="the work queue over string chunks against the one call (see above)")
+    ap.add_argument("--long", type=int, default=1536, help="--queue: chunks of the long queue (the first shape repeated)")
+    ap.add_argument("--yardstick-lib", default=None, help="--queue: the library whose one call is leg (a)")
+    ap.add_argument("--leg-timeout", type=int, default=400, help="--queue: seconds a leg's process may take")
+    ap.add_argument("--lane-batch", type=int, default=192, help="--queue: chunks per batch of leg (d)")
+    ap.add_argument("--rounds", type=int, default=2, help="--queue: processes per leg, run in turn (a b c d a b c d): timings of one shape differ more between processes than within one")
+    ap.add_argument("--host-threads", type=int, default=0, help="--queue: mrp_set_host_threads before the legs (the queue: per device); 0 = the library's choice")
+    ap.add_argument("--queue-leg", choices=("a", "b", "c", "d"), default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--leg-out", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.queue_leg:
+        return queue_leg(a)
+    if a.queue:
+        return queue_probe(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "string_chunks", "probe.json")
     t, tr, em = synth.margin_phase_pair_hmm_arrays()
     f = capi.PairHmm.from_margin_hmm(t, tr, em)
     r = f.reverse_complement()
     params = capi.Params.from_reference_names(synth.shipped_phase_params())
-    shapes = [("config2_130_sites", [synth.make_string_chunk(seed=1000 + i, n_sites=130, coverage=30, allele_len=25) for i in range(a.small)]),
-              ("2000_sites", [synth.make_string_chunk(seed=2000 + i, n_sites=2000, coverage=30, allele_len=25, span=(10, 60)) for i in range(a.large)])]
+    shapes = probe_shapes(a.small, a.large)
     rows = []
     with capi.Context(0) as ctx:
         for name, chunks in shapes:
