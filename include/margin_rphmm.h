@@ -632,6 +632,88 @@ int mrp_phase_string_chunks_on_devices(const int32_t *devices, int32_t n_devices
                                        mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
                                        mrp_queue_stats *stats);
 
+/* ---- the same with the back half of the chunk loop: filtered variants phased, filtered reads tagged, in the call ---------
+ * What margin phase does with a chunk after its phasing (phase.c:410-436): the filtered variants are phased with the tagged
+ * primary reads (mrp_phase_variants_from_tagged_reads), then the filtered reads together with the primary reads the phasing
+ * left untagged are haplotagged against the fragment's alleles (mrp_partition_reads_by_haplotype).  Nothing the pair-HMM scores
+ * for this depends on the phasing, so every pair some outcome could read joins the front's one pair-HMM launch and the back
+ * half is three small kernels behind the HP kernel.
+ *   One rest per chunk, beside its mrp_string_chunk; the symbol alphabet is the chunk's, the offsets are into the rest's own
+ * pool (which may be the chunk's pool: same pointer, same size).  The rest's n_filtered filtered reads (filteredReads of
+ * phase.c:349,365, in list order) are reads n_reads .. n_reads + n_filtered - 1 of the chunk in this call.  A rest with
+ * n_filtered == 0 and n_variants == 0 is empty (every pointer may be NULL): the chunk then takes no part in the back half. */
+typedef struct mrp_string_chunk_rest {
+    int64_t n_filtered;
+    const uint8_t *forward_strand;            /* n_filtered: nonzero = forward */
+    const uint8_t *pool; int64_t pool_bytes;  /* symbols of the filtered substrings, the variants' alleles and entries */
+    /* per primary bubble the filtered reads' substrings */
+    const int64_t *fsub_first;                /* n_bubbles + 1, from 0 (NULL when n_filtered == 0: none) */
+    const int64_t *fsub_off; const int32_t *fsub_len;
+    const int32_t *fsub_read;                 /* a filtered read, in [0, n_filtered); at most once per bubble, ascending within a bubble */
+    /* the filtered variants inside the chunk (the filter of bubbleGraph.c:2179 is the caller's) */
+    int64_t n_variants;
+    const int64_t *valle_first;               /* n_variants + 1, from 0 */
+    const int64_t *valle_off; const int32_t *valle_len;
+    const int32_t *gt;                        /* 2 * n_variants: gt1, gt2, allele indices within the variant */
+    const int64_t *ventry_first;              /* n_variants + 1, from 0; entries in the order buildVcfEntryToReadSubstringsMap lists them */
+    const int32_t *ventry_read;               /* a primary read [0, n_reads) or a filtered one [n_reads, n_reads + n_filtered) */
+    const int64_t *ventry_off; const int32_t *ventry_len;
+} mrp_string_chunk_rest;
+
+/* The back half's results of one chunk, malloc'd (every array mrp_free).  read_hap / h1 / h2 (n_reads = the chunk's n_reads +
+ * n_filtered entries): for a read that took part in the partition what mrp_partition_reads_by_haplotype gives (1 / 2 / 0 and the
+ * two totals), for a primary read the phasing tagged its tag and 0 / 0; for a chunk with an empty rest the tags (0 for an
+ * untagged read) and 0 / 0.  variant_state / cis / trans (n_variants): what mrp_phase_variants_from_tagged_reads gives. */
+typedef struct mrp_filtered_out {
+    int64_t n_reads;
+    int32_t *read_hap;
+    double *h1, *h2;
+    int64_t n_variants;
+    int32_t *variant_state;
+    double *cis, *trans;
+} mrp_filtered_out;
+
+typedef struct mrp_string_filtered_stats {
+    mrp_string_chunks_stats chunks;  /* as mrp_phase_string_chunks fills it; pairhmm covers every pair of the call */
+    int64_t pairs_scored;            /* pairs in the one pair-HMM launch: the front's own and the speculative ones */
+    int64_t pairs_speculative;       /* of those: the ones only the back half can read */
+    int64_t pairs_read_by_results;   /* speculative pairs some live record of the back half used */
+    double filtered_ms;              /* the back half's kernels, HIP events */
+} mrp_string_filtered_stats;
+
+/* mrp_phase_string_chunks with rest[n_chunks] beside chunks[n_chunks]: everything that call returns, unchanged, plus
+ * filtered_out[n_chunks].  Semantics, as the two calls above state them:
+ *   variants first (phase.c:413): a read is tagged when it is a primary read with hap_out 1 / 2.  Untagged entries neither score
+ * nor cache; the FIRST tagged entry of a group of equal substrings owns the scores and its read's strand picks the state machine;
+ * a pair with a string longer than sv_threshold is anchored; supports stay fp64.
+ *   then the reads (phase.c:419-436): the participants are the filtered reads in index order followed by the primary reads with
+ * hap_out not 1 or 2, in index order.  Sites are the fragment's bubbles ref_start .. ref_start + length - 1 whose hap1 and hap2
+ * alleles differ; the compared alleles are the fragment's; never anchored; the LAST-listed participating entry of a group of
+ * equal substrings owns the scores; supports are rounded to float; a read's sums run in bubble order.
+ * Checks in the existing order: MRP_ERR_ARG (the rest's included: NULL arrays, offsets not ascending, a read index out of range,
+ * a filtered read twice in a bubble or not ascending, gt naming an allele the variant lacks) before the context, then
+ * MRP_ERR_NO_DEVICE, then MRP_ERR_UNSUPPORTED for a pair -- the back half's included: with a rest every substring of a bubble
+ * may be aligned unanchored -- beyond the 2 048-cell diagonal.  On an error filtered_out is left zeroed.  stats may be NULL. */
+int mrp_phase_string_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest,
+                                          const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                          double het_substitution_probability, const mrp_params *params, int64_t min_phred, mrp_phase_result **out,
+                                          int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out, mrp_filtered_out *filtered_out,
+                                          mrp_string_filtered_stats *stats);
+/* The queue twins: mrp_queue_phase_string_chunks / mrp_phase_string_chunks_on_devices with the rest travelling with its chunk.
+ * The order of the queue is by mrp_string_chunk_units plus the rest's (read, site) entries (fsub_first[n_bubbles] +
+ * ventry_first[n_variants]); results, errors and stats as there, filtered_out[] zeroed on an error. */
+int mrp_queue_phase_string_chunks_with_filtered(mrp_queue *q, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest,
+                                                const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                                                int64_t sv_threshold, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                mrp_profile_out *profiles_out, mrp_filtered_out *filtered_out, mrp_queue_stats *stats);
+int mrp_phase_string_chunks_with_filtered_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_string_chunk *chunks,
+                                                     const mrp_string_chunk_rest *rest, const mrp_pair_hmm *forward_model,
+                                                     const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                                     double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                     int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                     mrp_profile_out *profiles_out, mrp_filtered_out *filtered_out, mrp_queue_stats *stats);
+
 /* ---- from alignments to read substrings at variant sites --------------------------------------------------------------
  * The step of margin phase's chunk loop that makes the strings above (phase.c:337-357): updateVcfEntriesWithSubstringsAndPositions
  * (impl/vcf.c:476-486, getAlleleSubstrings2 :394-462) and extractReadSubstringsAtVariantPositions (impl/htsIntegration.c:1722-1989)

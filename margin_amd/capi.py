@@ -36,7 +36,8 @@ EXPORTED_SYMBOLS = [
     "mrp_allele_read_supports", "mrp_kmer_alignment_anchors", "mrp_phase_chunks_on_devices", "mrp_queue_plan", "mrp_queue_dry_run", "mrp_queue_create", "mrp_queue_destroy",
     "mrp_queue_phase_chunks", "mrp_partition_reads_by_haplotype", "mrp_phase_variants_from_tagged_reads", "mrp_phase_string_chunks",
     "mrp_extract_read_substrings", "mrp_string_chunk_from_extracted", "mrp_string_chunk_units", "mrp_queue_phase_string_chunks",
-    "mrp_phase_string_chunks_on_devices",
+    "mrp_phase_string_chunks_on_devices", "mrp_phase_string_chunks_with_filtered", "mrp_queue_phase_string_chunks_with_filtered",
+    "mrp_phase_string_chunks_with_filtered_on_devices",
 ]
 
 
@@ -226,6 +227,23 @@ class StringChunksStats(C.Structure):
                 ("host_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class StringChunkRest(C.Structure):
+    _fields_ = [("n_filtered", C.c_int64), ("forward_strand", C.c_void_p), ("pool", C.c_void_p), ("pool_bytes", C.c_int64), ("fsub_first", C.c_void_p),
+                ("fsub_off", C.c_void_p), ("fsub_len", C.c_void_p), ("fsub_read", C.c_void_p), ("n_variants", C.c_int64), ("valle_first", C.c_void_p),
+                ("valle_off", C.c_void_p), ("valle_len", C.c_void_p), ("gt", C.c_void_p), ("ventry_first", C.c_void_p), ("ventry_read", C.c_void_p),
+                ("ventry_off", C.c_void_p), ("ventry_len", C.c_void_p)]
+
+
+class FilteredOut(C.Structure):
+    _fields_ = [("n_reads", C.c_int64), ("read_hap", C.c_void_p), ("h1", C.c_void_p), ("h2", C.c_void_p), ("n_variants", C.c_int64),
+                ("variant_state", C.c_void_p), ("cis", C.c_void_p), ("trans", C.c_void_p)]
+
+
+class StringFilteredStats(C.Structure):
+    _fields_ = [("chunks", StringChunksStats), ("pairs_scored", C.c_int64), ("pairs_speculative", C.c_int64), ("pairs_read_by_results", C.c_int64),
+                ("filtered_ms", C.c_double)]
+
+
 READ_DROPPED, READ_KEPT, READ_FILTERED = 0, 1, 2
 
 
@@ -352,6 +370,11 @@ def load():
     L.mrp_queue_phase_string_chunks.argtypes = [vp, i64, P(StringChunk), P(PairHmm), P(PairHmm), i64, i64, C.c_double, P(Params), i64, i64,
                                                 P(P(PhaseResult)), P(vp), P(vp), P(ProfileOut), P(QueueStats)]
     L.mrp_phase_string_chunks_on_devices.argtypes = [vp, i32] + L.mrp_queue_phase_string_chunks.argtypes[1:]
+    L.mrp_phase_string_chunks_with_filtered.argtypes = [vp, i64, P(StringChunk), P(StringChunkRest), P(PairHmm), P(PairHmm), i64, i64, C.c_double, P(Params),
+                                                        i64, P(P(PhaseResult)), P(vp), P(vp), P(ProfileOut), P(FilteredOut), P(StringFilteredStats)]
+    L.mrp_queue_phase_string_chunks_with_filtered.argtypes = [vp, i64, P(StringChunk), P(StringChunkRest), P(PairHmm), P(PairHmm), i64, i64, C.c_double,
+                                                              P(Params), i64, i64, P(P(PhaseResult)), P(vp), P(vp), P(ProfileOut), P(FilteredOut), P(QueueStats)]
+    L.mrp_phase_string_chunks_with_filtered_on_devices.argtypes = [vp, i32] + L.mrp_queue_phase_string_chunks_with_filtered.argtypes[1:]
     L.mrp_extract_read_substrings.argtypes = [vp, i64, P(AlignedChunk), P(ExtractOptions), P(P(ExtractedChunk)), P(ExtractStats)]
     L.mrp_string_chunk_from_extracted.argtypes = [P(ExtractedChunk), vp, vp, vp, P(StringChunk), P(P(C.c_int64))]
     L.mrp_kmer_alignment_anchors.argtypes = [vp, i64, vp, i64, vp]
@@ -1192,6 +1215,110 @@ def phase_string_chunks_on_devices(devices, chunks, forward_model: PairHmm, reve
     _check(load().mrp_phase_string_chunks_on_devices(C.cast(dev, C.c_void_p), len(devices), a.n, a.arr, C.byref(forward_model), C.byref(reverse_model),
                                                      int(expansion), int(sv_threshold), float(het_substitution_probability), C.byref(params),
                                                      int(min_phred), int(chunks_per_batch), a.res, a.hp, a.pp, a.prof, C.byref(st)))
+    return a.results(), st
+
+
+# ---- the same with the back half: filtered variants phased, filtered reads tagged (mrp_phase_string_chunks_with_filtered) ----
+
+def string_chunk_rest_struct(chunk, rest):
+    """mrp_string_chunk_rest beside chunk (a synth.StringChunk).  rest: None (an empty rest) or a dict with
+    forward_strand (per filtered read), fsubs (per bubble of the chunk a list of (filtered read, symbols), ascending reads),
+    variants (a list of (alleles, (gt1, gt2), entries), entries a list of (read of the chunk, primary or n_reads + filtered, symbols)).
+    Returns (StringChunkRest, the arrays it points into)."""
+    if rest is None:
+        return StringChunkRest(), {}
+    strings, pos = [], 0
+    f_first, f_off, f_len, f_read = [0], [], [], []
+    fsubs = rest.get("fsubs") or [[] for _ in chunk.bubbles]
+    assert len(fsubs) == len(chunk.bubbles)
+    for subs in fsubs:
+        for r, sub in subs:
+            sub = np.ascontiguousarray(sub, dtype=np.uint8)
+            strings.append(sub); f_off.append(pos); f_len.append(len(sub)); f_read.append(int(r)); pos += len(sub)
+        f_first.append(len(f_off))
+    a_first, a_off, a_len, gt, e_first, e_read, e_off, e_len = [0], [], [], [], [0], [], [], []
+    for alleles, g, entries in rest.get("variants", []):
+        for a in alleles:
+            a = np.ascontiguousarray(a, dtype=np.uint8)
+            strings.append(a); a_off.append(pos); a_len.append(len(a)); pos += len(a)
+        for r, sub in entries:
+            sub = np.ascontiguousarray(sub, dtype=np.uint8)
+            strings.append(sub); e_read.append(int(r)); e_off.append(pos); e_len.append(len(sub)); pos += len(sub)
+        gt += [int(g[0]), int(g[1])]
+        a_first.append(len(a_off))
+        e_first.append(len(e_off))
+    keep = dict(strand=np.ascontiguousarray(rest["forward_strand"], dtype=np.uint8), pool=np.concatenate(strings) if pos else np.zeros(0, np.uint8),
+                fsub_first=np.array(f_first, np.int64), fsub_off=np.array(f_off, np.int64), fsub_len=np.array(f_len, np.int32),
+                fsub_read=np.array(f_read, np.int32), valle_first=np.array(a_first, np.int64), valle_off=np.array(a_off, np.int64),
+                valle_len=np.array(a_len, np.int32), gt=np.array(gt, np.int32), ventry_first=np.array(e_first, np.int64),
+                ventry_read=np.array(e_read, np.int32), ventry_off=np.array(e_off, np.int64), ventry_len=np.array(e_len, np.int32))
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data
+    R = StringChunkRest(keep["strand"].size, ptr(keep["strand"]), ptr(keep["pool"]), keep["pool"].size, keep["fsub_first"].ctypes.data, ptr(keep["fsub_off"]),
+                        ptr(keep["fsub_len"]), ptr(keep["fsub_read"]), len(rest.get("variants", [])), keep["valle_first"].ctypes.data, ptr(keep["valle_off"]),
+                        ptr(keep["valle_len"]), ptr(keep["gt"]), keep["ventry_first"].ctypes.data, ptr(keep["ventry_read"]), ptr(keep["ventry_off"]),
+                        ptr(keep["ventry_len"]))
+    return R, keep
+
+
+class StringFilteredArgs(StringChunkArgs):
+    """StringChunkArgs with the rests and the back half's results"""
+
+    def __init__(self, chunks, rests, profiles: bool, structs=None, rest_structs=None):
+        super().__init__(chunks, profiles, structs)
+        assert len(rests) == self.n
+        self.rbuilt = rest_structs if rest_structs is not None else [string_chunk_rest_struct(c, r) for c, r in zip(chunks, rests)]
+        self.rarr = (StringChunkRest * max(self.n, 1))(*[b[0] for b in self.rbuilt])
+        self.fout = (FilteredOut * max(self.n, 1))()
+
+    def results(self):
+        L = load()
+        out = super().results()
+        for i, d in enumerate(out):
+            O = self.fout[i]
+            nr, nv = int(O.n_reads), int(O.n_variants)
+            d["filtered"] = dict(read_hap=_as_np(O.read_hap, nr, np.int32), h1=_as_np(O.h1, nr, np.float64), h2=_as_np(O.h2, nr, np.float64),
+                                 variant_state=_as_np(O.variant_state, nv, np.int32), cis=_as_np(O.cis, nv, np.float64), trans=_as_np(O.trans, nv, np.float64))
+            for f in ("read_hap", "h1", "h2", "variant_state", "cis", "trans"):
+                L.mrp_free(C.cast(getattr(O, f), C.c_void_p))
+        return out
+
+
+def phase_string_chunks_with_filtered(ctx: Context, chunks, rests, forward_model: PairHmm, reverse_model: PairHmm, params: Params, min_phred: int = 0,
+                                      expansion: int = 4, sv_threshold: int = 512, het_substitution_probability: float = 0.0, profiles: bool = False,
+                                      structs=None, rest_structs=None):
+    """mrp_phase_string_chunks_with_filtered -> (phase_string_chunks' list of dicts, each with "filtered": dict(read_hap, h1, h2 over the
+    chunk's primary then filtered reads, variant_state, cis, trans), StringFilteredStats).  rests as string_chunk_rest_struct takes them."""
+    a = StringFilteredArgs(chunks, rests, profiles, structs, rest_structs)
+    st = StringFilteredStats()
+    _check(load().mrp_phase_string_chunks_with_filtered(ctx.h, a.n, a.arr, a.rarr, C.byref(forward_model), C.byref(reverse_model), int(expansion),
+                                                        int(sv_threshold), float(het_substitution_probability), C.byref(params), int(min_phred), a.res,
+                                                        a.hp, a.pp, a.prof, a.fout, C.byref(st)))
+    return a.results(), st
+
+
+def queue_phase_string_chunks_with_filtered(q, chunks, rests, forward_model: PairHmm, reverse_model: PairHmm, params: Params, min_phred: int = 0,
+                                            chunks_per_batch: int = 0, expansion: int = 4, sv_threshold: int = 512,
+                                            het_substitution_probability: float = 0.0, profiles: bool = False, structs=None, rest_structs=None):
+    """mrp_queue_phase_string_chunks_with_filtered on a Queue -> (list of dicts in input order, QueueStats)"""
+    a = StringFilteredArgs(chunks, rests, profiles, structs, rest_structs)
+    st = QueueStats()
+    _check(load().mrp_queue_phase_string_chunks_with_filtered(q.h, a.n, a.arr, a.rarr, C.byref(forward_model), C.byref(reverse_model), int(expansion),
+                                                              int(sv_threshold), float(het_substitution_probability), C.byref(params), int(min_phred),
+                                                              int(chunks_per_batch), a.res, a.hp, a.pp, a.prof, a.fout, C.byref(st)))
+    return a.results(), st
+
+
+def phase_string_chunks_with_filtered_on_devices(devices, chunks, rests, forward_model: PairHmm, reverse_model: PairHmm, params: Params, min_phred: int = 0,
+                                                 chunks_per_batch: int = 0, expansion: int = 4, sv_threshold: int = 512,
+                                                 het_substitution_probability: float = 0.0, profiles: bool = False):
+    """mrp_phase_string_chunks_with_filtered_on_devices -> (list of dicts in input order, QueueStats)"""
+    a = StringFilteredArgs(chunks, rests, profiles)
+    dev = (C.c_int32 * len(devices))(*devices)
+    st = QueueStats()
+    _check(load().mrp_phase_string_chunks_with_filtered_on_devices(C.cast(dev, C.c_void_p), len(devices), a.n, a.arr, a.rarr, C.byref(forward_model),
+                                                                   C.byref(reverse_model), int(expansion), int(sv_threshold),
+                                                                   float(het_substitution_probability), C.byref(params), int(min_phred),
+                                                                   int(chunks_per_batch), a.res, a.hp, a.pp, a.prof, a.fout, C.byref(st)))
     return a.results(), st
 
 

@@ -531,15 +531,20 @@ int mrp_chunk_block_create(mrp_context *ctx, int64_t n, const mrp_chunk_desc *co
  *   run          uploads, kernels, phasing, HP tags, results -- on the thread of ctx; a front is run once.
  * The front keeps pointers into chunks[]: the array lives until the run has returned. */
 struct mrp_string_front;
+/* rest (NULL, or one mrp_string_chunk_rest per chunk): the back half of mrp_phase_string_chunks_with_filtered travels with its chunk
+ * through the same three steps; filtered_out (zeroed by the caller) and filtered_stats (added to) are filled when the front was made
+ * with a rest.  who: the entry the caller called, the prefix of every message. */
 int mrp_string_chunks_check(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
-                            int64_t expansion, const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out);
-int mrp_string_chunks_check_pairs(int64_t n_chunks, const mrp_string_chunk *chunks, int64_t expansion, int64_t sv_threshold);
-int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
-                            int64_t expansion, int64_t sv_threshold, mrp_string_front **front_out);
+                            int64_t expansion, const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                            const mrp_string_chunk_rest *rest, const char *who);
+int mrp_string_chunks_check_pairs(int64_t n_chunks, const mrp_string_chunk *chunks, int64_t expansion, int64_t sv_threshold, const mrp_string_chunk_rest *rest,
+                                  const char *who);
+int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest, const mrp_pair_hmm *forward_model,
+                            const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, mrp_string_front **front_out);
 void mrp_string_front_destroy(mrp_string_front *front);
 int mrp_string_front_run(mrp_context *ctx, mrp_string_front *front, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
                          mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
-                         mrp_string_chunks_stats *stats);
+                         mrp_string_chunks_stats *stats, mrp_filtered_out *filtered_out, mrp_string_filtered_stats *filtered_stats);
 int mrp_host_threads_setting(void); /* what mrp_set_host_threads() was given, 0 if it was never called */
 /* host worker pools (mrp_api.cpp) */
 extern "C" void mrp_batch_last_launch_ms(struct mrp_batch *b, float *pack, float *emission, float *recursion);

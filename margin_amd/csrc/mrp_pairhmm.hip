@@ -765,7 +765,7 @@ static __device__ __forceinline__ double ht_log_add_exact(double x, double y) {
 struct HtEntry { /* the two log probabilities (indices into the pair-HMM output) of one read at one site */
     int32_t a, b;
     int32_t hap1; /* phasing: the read is tagged haplotype 1 (else 2) */
-    int32_t pad;
+    int32_t live; /* the back half in the string-chunk call (fs_* kernels): the record counts; the ht_* kernels do not read it */
 };
 
 /* bubbleGraph.c:1876-1925: a lane per read walks the read's sites in order; the supports are floats (:1869, :1881-1882) */
@@ -962,8 +962,7 @@ uint16_t sc_f32_to_u16_x86(float v) {
 }
 
 /* MRP_ERR_ARG for a malformed chunk; seen: scratch of n_reads entries */
-int sc_check_chunk(int64_t c, const mrp_string_chunk &S, std::vector<int64_t> &seen) {
-    static const char *who = "mrp_phase_string_chunks";
+int sc_check_chunk(const char *who, int64_t c, const mrp_string_chunk &S, std::vector<int64_t> &seen) {
     if (S.n_bubbles < 0 || S.n_reads < 0 || S.pool_bytes < 0 || S.n_reads >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: bad sizes", who, (long long) c);
     if (S.n_reads > 0 && (!S.read_names || !S.read_forward_strand)) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null argument", who, (long long) c);
     for (int64_t r = 0; r < S.n_reads; r++)
@@ -1041,6 +1040,195 @@ void sc_layout(const mrp_string_chunk &S, double het_substitution_probability, S
             for (int64_t k = 0; k < A; k++) Lc.sub[(size_t) (o + j * A + k)] = j == k ? 0 : off;
         o += A * A;
     }
+}
+
+/* ---- the back half in the string-chunk call (mrp_phase_string_chunks_with_filtered) ------------------------------
+ * A "site" is a primary bubble of a chunk with a rest (its entries: the bubble's primary substrings and the filtered reads') or a
+ * filtered variant (its entries as listed).  The front groups a site's entries into classes of equal substrings and scores, for
+ * every class and every strand that occurs in it, the pairs some outcome of the phasing could read: cbase[2 * class + reverse] is
+ * the block of that (class, strand) in pidx, pidx[block + allele] (bubbles) / pidx[block + 0 / 1] (variants: gt1, gt2) the pair. */
+struct FsEntry {
+    int32_t cls;   /* class within the site */
+    int32_t read;  /* the call's read index (primary reads of a chunk first, then its filtered reads) */
+    int32_t key;   /* position in the site's listing order: the owner of a class is the max (bubbles) / min (variants) over its
+                    * participating entries */
+    int32_t flags; /* 1: reverse strand, 2: a filtered read */
+};
+struct FsSite {
+    int64_t entry_first, cls_first;
+    int32_t n_entries, n_classes;
+    int32_t chunk, bubble; /* bubble < 0: a variant */
+    int32_t n_alleles, visited; /* variants: gt1 != gt2 and entries (bubbleGraph.c:2174, :2186-2192) */
+};
+struct FsChunk { /* what the phasing decided for a chunk: where its haplotype strings are (hap1 then hap2, frag_length each) */
+    int64_t hap;
+    int32_t frag_start, frag_length;
+};
+constexpr int FS_TILE = 256; /* classes per pass of the LDS owner table */
+
+/* the tag of a read where the HP kernel wrote it: read_seq = its profile sequence, -1 a primary read in no bubble, -2 a filtered read */
+static __device__ __forceinline__ int fs_tag(const int32_t *__restrict__ read_seq, const int8_t *__restrict__ tags, int32_t read) {
+    const int32_t q = read_seq[read];
+    return q >= 0 ? (int) tags[q] : -1;
+}
+
+/* A wave per site, behind sc_assign_kernel.  Decides the site's activity and its two alleles (bubbles: the fragment's hap1 / hap2
+ * allele, bubbleGraph.c:1780; variants: gt1 / gt2), each entry's participation (bubbles: filtered reads and untagged primary
+ * reads; variants: tagged primary reads, :2226-2235), per class the owning entry (bubbles: the last-listed participant, :1816-1819;
+ * variants: the first, :2221) and from the owner's strand the two pairs.  One record per entry, live or not. */
+__global__ void __launch_bounds__(64) sc_filtered_sites_kernel(const FsSite *__restrict__ sites, const FsEntry *__restrict__ ent,
+                                                               const int32_t *__restrict__ cbase, const int32_t *__restrict__ pidx,
+                                                               const int32_t *__restrict__ read_seq, const int8_t *__restrict__ tags,
+                                                               const FsChunk *__restrict__ chunks, const uint64_t *__restrict__ haps,
+                                                               HtEntry *__restrict__ rec, uint8_t *__restrict__ used) {
+    __shared__ int32_t tab[FS_TILE];
+    const FsSite st = sites[blockIdx.x];
+    const int lane = (int) threadIdx.x;
+    const bool variant = st.bubble < 0;
+    bool active = st.visited != 0;
+    int32_t a1 = 0, a2 = 1;
+    if (!variant) {
+        const FsChunk ch = chunks[st.chunk];
+        const int32_t j = st.bubble - ch.frag_start;
+        active = j >= 0 && j < ch.frag_length;
+        if (active) {
+            const uint64_t h1 = haps[ch.hap + j], h2 = haps[ch.hap + ch.frag_length + j];
+            active = h1 != h2 && h1 < (uint64_t) st.n_alleles && h2 < (uint64_t) st.n_alleles;
+            a1 = (int32_t) h1;
+            a2 = (int32_t) h2;
+        }
+    }
+    const FsEntry *e = ent + st.entry_first;
+    HtEntry *out = rec + st.entry_first;
+    for (int32_t i = lane; i < st.n_entries; i += 64) out[i] = HtEntry{0, 0, 0, 0};
+    if (!active) return; /* (the same for every lane of the block) */
+    for (int32_t t0 = 0; t0 < st.n_classes; t0 += FS_TILE) {
+        for (int i = lane; i < FS_TILE; i += 64) tab[i] = variant ? INT32_MAX : -1;
+        __syncthreads();
+        for (int32_t i = lane; i < st.n_entries; i += 64) {
+            const FsEntry x = e[i];
+            const int tag = fs_tag(read_seq, tags, x.read);
+            const bool tagged = !(x.flags & 2) && (tag == 1 || tag == 2);
+            const bool takes_part = variant ? tagged : !tagged;
+            if (!takes_part || x.cls < t0 || x.cls >= t0 + FS_TILE) continue;
+            const int32_t v = x.key * 2 + (x.flags & 1);
+            if (variant) atomicMin(&tab[x.cls - t0], v);
+            else atomicMax(&tab[x.cls - t0], v);
+        }
+        __syncthreads();
+        for (int32_t i = lane; i < st.n_entries; i += 64) {
+            const FsEntry x = e[i];
+            const int tag = fs_tag(read_seq, tags, x.read);
+            const bool tagged = !(x.flags & 2) && (tag == 1 || tag == 2);
+            const bool takes_part = variant ? tagged : !tagged;
+            if (!takes_part || x.cls < t0 || x.cls >= t0 + FS_TILE) continue;
+            const int32_t owner = tab[x.cls - t0];
+            const int32_t block = cbase[2 * (st.cls_first + x.cls) + (owner & 1)];
+            const int32_t pa = pidx[block + a1], pb = pidx[block + a2];
+            out[i] = HtEntry{pa, pb, tag == 1 ? 1 : 0, 1};
+            if (used) { used[pa] = 1; used[pb] = 1; }
+        }
+        __syncthreads();
+    }
+}
+
+/* ht_partition_kernel over a read's static candidate list (its entries at bubbles, in bubble order): records that are not live
+ * are skipped.  A primary read the phasing tagged keeps its tag. */
+__global__ void __launch_bounds__(256) fs_partition_kernel(const int64_t *__restrict__ first, const int32_t *__restrict__ cand,
+                                                           const HtEntry *__restrict__ e, const double *__restrict__ lp,
+                                                           const int32_t *__restrict__ read_seq, const int8_t *__restrict__ tags, int64_t n_reads,
+                                                           int32_t *__restrict__ hap, double *__restrict__ h1, double *__restrict__ h2) {
+    const int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    const int tag = fs_tag(read_seq, tags, (int32_t) r);
+    if (read_seq[r] != -2 && (tag == 1 || tag == 2)) { hap[r] = tag; h1[r] = 0.0; h2[r] = 0.0; return; }
+    double t1 = 0.0, t2 = 0.0;
+    for (int64_t i = first[r]; i < first[r + 1]; i++) {
+        const HtEntry x = e[cand[i]];
+        if (!x.live) continue;
+        const double s1 = (double) (float) lp[x.a], s2 = (double) (float) lp[x.b];
+        t1 += s1 - ht_log_add_exact(s1, s2);
+        t2 += s2 - ht_log_add_exact(s2, s1);
+    }
+    hap[r] = t1 > t2 ? 1 : (t2 > t1 ? 2 : 0);
+    h1[r] = t1;
+    h2[r] = t2;
+}
+
+/* ht_phase_kernel over a variant's entries in order, the records that are not live skipped */
+__global__ void __launch_bounds__(256) fs_phase_kernel(const FsSite *__restrict__ sites, const HtEntry *__restrict__ e, const double *__restrict__ lp,
+                                                       int64_t n_variants, int32_t *__restrict__ state, double *__restrict__ cis,
+                                                       double *__restrict__ trans) {
+    const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_variants) return;
+    const FsSite st = sites[v];
+    double c = 0.0, t = 0.0;
+    for (int64_t i = st.entry_first; i < st.entry_first + st.n_entries; i++) {
+        const HtEntry x = e[i];
+        if (!x.live) continue;
+        const double sa = lp[x.a], sb = lp[x.b];
+        const double l = ht_log_add_exact(sa, sb);
+        const double da = sa - l, db = sb - l;
+        c += x.hap1 ? da : db;
+        t += x.hap1 ? db : da;
+    }
+    state[v] = !st.visited ? MRP_VARIANT_NOT_VISITED : (c > t ? MRP_VARIANT_CIS : (t > c ? MRP_VARIANT_TRANS : MRP_VARIANT_TIE));
+    cis[v] = c;
+    trans[v] = t;
+}
+
+bool sc_rest_empty(const mrp_string_chunk_rest &R) { return R.n_filtered == 0 && R.n_variants == 0; }
+
+/* MRP_ERR_ARG for a malformed rest of chunk c (the chunk itself has passed sc_check_chunk) */
+int sc_check_rest(const char *who, int64_t c, const mrp_string_chunk &S, const mrp_string_chunk_rest &R) {
+    const long long cc = (long long) c;
+    if (R.n_filtered < 0 || R.n_variants < 0 || R.pool_bytes < 0 || S.n_reads + R.n_filtered >= (1ll << 30))
+        return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: bad sizes of the rest", who, cc);
+    if ((R.n_filtered > 0 && !R.forward_strand) || (R.pool_bytes > 0 && !R.pool)) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null argument in the rest", who, cc);
+    if (R.n_filtered > 0 && S.n_bubbles > 0 && !R.fsub_first) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null argument in the rest (fsub_first)", who, cc);
+    if (R.fsub_first && S.n_bubbles > 0) {
+        if (R.fsub_first[0] != 0) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: offsets of the rest must start at 0", who, cc);
+        for (int64_t b = 0; b < S.n_bubbles; b++)
+            if (R.fsub_first[b + 1] < R.fsub_first[b])
+                return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: filtered substring offsets not ascending at bubble %lld", who, cc, (long long) b);
+        const int64_t n = R.fsub_first[S.n_bubbles];
+        if (n > 0 && (!R.fsub_off || !R.fsub_len || !R.fsub_read)) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null argument in the rest", who, cc);
+        for (int64_t b = 0; b < S.n_bubbles; b++)
+            for (int64_t k = R.fsub_first[b]; k < R.fsub_first[b + 1]; k++) {
+                if (R.fsub_len[k] < 0 || R.fsub_off[k] < 0 || R.fsub_off[k] + R.fsub_len[k] > R.pool_bytes)
+                    return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: filtered substring %lld lies outside the pool", who, cc, (long long) k);
+                const int32_t r = R.fsub_read[k];
+                if (r < 0 || r >= R.n_filtered)
+                    return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: filtered substring %lld names read %d of %lld", who, cc, (long long) k, r, (long long) R.n_filtered);
+                if (k > R.fsub_first[b] && R.fsub_read[k - 1] == r)
+                    return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: filtered read %d appears twice in bubble %lld", who, cc, r, (long long) b);
+                if (k > R.fsub_first[b] && R.fsub_read[k - 1] > r)
+                    return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: filtered reads of bubble %lld are not in ascending order", who, cc, (long long) b);
+            }
+    }
+    if (R.n_variants == 0) return MRP_OK;
+    if (!R.valle_first || !R.ventry_first || !R.gt) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null argument in the rest", who, cc);
+    if (R.valle_first[0] != 0 || R.ventry_first[0] != 0) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: offsets of the rest must start at 0", who, cc);
+    for (int64_t v = 0; v < R.n_variants; v++) {
+        const int64_t na = R.valle_first[v + 1] - R.valle_first[v], ne = R.ventry_first[v + 1] - R.ventry_first[v];
+        if (na < 0 || ne < 0 || ne >= (1ll << 30)) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: offsets not ascending at variant %lld", who, cc, (long long) v);
+        if (R.gt[2 * v] < 0 || R.gt[2 * v] >= na || R.gt[2 * v + 1] < 0 || R.gt[2 * v + 1] >= na)
+            return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: variant %lld has a genotype allele it does not have", who, cc, (long long) v);
+    }
+    const int64_t n_alleles = R.valle_first[R.n_variants], n_entries = R.ventry_first[R.n_variants];
+    if ((n_alleles > 0 && (!R.valle_off || !R.valle_len)) || (n_entries > 0 && (!R.ventry_read || !R.ventry_off || !R.ventry_len)))
+        return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null argument in the rest", who, cc);
+    for (int64_t j = 0; j < n_alleles; j++)
+        if (R.valle_len[j] < 0 || R.valle_off[j] < 0 || R.valle_off[j] + R.valle_len[j] > R.pool_bytes)
+            return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: variant allele %lld lies outside the pool", who, cc, (long long) j);
+    for (int64_t k = 0; k < n_entries; k++) {
+        if (R.ventry_len[k] < 0 || R.ventry_off[k] < 0 || R.ventry_off[k] + R.ventry_len[k] > R.pool_bytes)
+            return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: variant entry %lld lies outside the pool", who, cc, (long long) k);
+        if (R.ventry_read[k] < 0 || R.ventry_read[k] >= S.n_reads + R.n_filtered)
+            return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: variant entry %lld names read %d of %lld", who, cc, (long long) k, R.ventry_read[k],
+                                 (long long) (S.n_reads + R.n_filtered));
+    }
+    return MRP_OK;
 }
 
 }  // namespace
@@ -1367,11 +1555,24 @@ struct mrp_string_front {
         std::vector<std::vector<int64_t>> chunk_anchors;
     } scratch;
     double front_ms = 0;                               /* host wall time of the front (the one call adds its checks) */
+    /* the back half (a call with rests): the static part of its sites, made with the pairs.  Sites: the bubbles of the chunks
+     * with a rest, chunk by chunk, then the variants, chunk by chunk. */
+    struct Filtered {
+        bool on = false;
+        const mrp_string_chunk_rest *rest = nullptr;   /* the caller's, as chunks */
+        std::vector<int64_t> read_base, var_base;      /* n_chunks + 1: chunk c's reads (primary, then filtered) and variants in the call */
+        int64_t n_bsites = 0, n_primary_pairs = 0;
+        HostVec<FsEntry> entries;
+        HostVec<FsSite> sites;
+        HostVec<int32_t> cbase, pidx;
+        HostVec<int64_t> cand_first;                   /* per read of the call: its entries at bubbles, in bubble order */
+        HostVec<int32_t> cand;
+    } fil;
 };
 
 int mrp_string_chunks_check(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
-                            int64_t expansion, const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out) {
-    static const char *who = "mrp_phase_string_chunks";
+                            int64_t expansion, const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                            const mrp_string_chunk_rest *rest, const char *who) {
     if (n_chunks < 0 || (n_chunks > 0 && (!chunks || !out || !hap_out)) || !forward_model || !reverse_model || !params)
         return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
     if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
@@ -1382,7 +1583,8 @@ int mrp_string_chunks_check(int64_t n_chunks, const mrp_string_chunk *chunks, co
         std::vector<std::string> msgs((size_t) n_chunks);
         mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
             std::vector<int64_t> seen;
-            rcs[(size_t) c] = sc_check_chunk(c, chunks[c], seen);
+            rcs[(size_t) c] = sc_check_chunk(who, c, chunks[c], seen);
+            if (rcs[(size_t) c] == MRP_OK && rest) rcs[(size_t) c] = sc_check_rest(who, c, chunks[c], rest[c]);
             if (rcs[(size_t) c] != MRP_OK) msgs[(size_t) c] = mrp_last_error();
         });
         for (int64_t c = 0; c < n_chunks; c++)
@@ -1395,37 +1597,64 @@ int mrp_string_chunks_check(int64_t n_chunks, const mrp_string_chunk *chunks, co
  * duplicate substring has its owner's strings, so looking at every substring changes nothing).  A diagonal of a pair holds at
  * most min(lx, ly) + 1 cells, band or not: only pairs with BOTH strings at the limit are looked at, their anchors (above
  * sv_threshold, bubbleGraph.c:1448-1451) and bands made as the front makes them. */
-int mrp_string_chunks_check_pairs(int64_t n_chunks, const mrp_string_chunk *chunks, int64_t expansion, int64_t sv_threshold) {
-    static const char *who = "mrp_phase_string_chunks";
+int mrp_string_chunks_check_pairs(int64_t n_chunks, const mrp_string_chunk *chunks, int64_t expansion, int64_t sv_threshold,
+                                  const mrp_string_chunk_rest *rest, const char *who) {
     std::vector<int> rcs((size_t) n_chunks, MRP_OK);
     std::vector<std::string> msgs((size_t) n_chunks);
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
         const mrp_string_chunk &S = chunks[c];
         std::vector<int64_t> anc;
         std::vector<int32_t> Lb, Rb;
-        for (int64_t b = 0; b < S.n_bubbles && rcs[(size_t) c] == MRP_OK; b++)
-            for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1] && rcs[(size_t) c] == MRP_OK; k++)
-                for (int64_t j = S.allele_first[b]; j < S.allele_first[b + 1]; j++) {
-                    const int64_t lx = S.allele_len[j], ly = S.sub_len[k];
-                    if (std::min(lx, ly) < PHM_WAVE_MAX_WIDTH) continue;
-                    const bool anchored = ly > sv_threshold || lx > sv_threshold;
-                    anc.clear();
-                    if (anchored) kmer_anchors(S.pool + S.allele_off[j], lx, S.pool + S.sub_off[k], ly, anc);
-                    int width = (int) std::min<int64_t>(std::min(lx, ly) + 1, INT32_MAX);
-                    if (!anc.empty()) {
-                        if (lx + ly >= (1ll << 30)) { rcs[(size_t) c] = mrp_set_error(MRP_ERR_ARG, "%s: strings too long", who); break; }
-                        Lb.resize((size_t) (lx + ly + 1));
-                        Rb.resize((size_t) (lx + ly + 1));
-                        const int rc = band_closed_form(anc.data(), (int64_t) anc.size() / 2, lx, ly, expansion, Lb.data(), Rb.data(), nullptr, &width);
-                        if (rc != MRP_OK) { rcs[(size_t) c] = mrp_set_error(rc, "%s: chunk %lld: a pair of bubble %lld has invalid anchors (pairwiseAligner.c:206-211)", who, (long long) c, (long long) b); break; }
-                    }
-                    if (width > PHM_WAVE_MAX_WIDTH) {
-                        rcs[(size_t) c] = mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: chunk %lld: a pair of bubble %lld has a diagonal of %d cells (limit %d)", who,
-                                                        (long long) c, (long long) b, width, PHM_WAVE_MAX_WIDTH);
-                        break;
+        int &rcc = rcs[(size_t) c];
+        /* one pair: x = allele, y = substring; what: "bubble" / "variant" and its index.  Leaves rcc set on a refusal. */
+        auto pair = [&](const uint8_t *x, int64_t lx, const uint8_t *y, int64_t ly, bool anchored, const char *what, int64_t idx) {
+            if (std::min(lx, ly) < PHM_WAVE_MAX_WIDTH) return;
+            anc.clear();
+            if (anchored) kmer_anchors(x, lx, y, ly, anc);
+            int width = (int) std::min<int64_t>(std::min(lx, ly) + 1, INT32_MAX);
+            if (!anc.empty()) {
+                if (lx + ly >= (1ll << 30)) { rcc = mrp_set_error(MRP_ERR_ARG, "%s: strings too long", who); return; }
+                Lb.resize((size_t) (lx + ly + 1));
+                Rb.resize((size_t) (lx + ly + 1));
+                const int rc = band_closed_form(anc.data(), (int64_t) anc.size() / 2, lx, ly, expansion, Lb.data(), Rb.data(), nullptr, &width);
+                if (rc != MRP_OK) {
+                    rcc = mrp_set_error(rc, "%s: chunk %lld: a pair of %s %lld has invalid anchors (pairwiseAligner.c:206-211)", who, (long long) c, what, (long long) idx);
+                    return;
+                }
+            }
+            if (width > PHM_WAVE_MAX_WIDTH)
+                rcc = mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: chunk %lld: a pair of %s %lld has a diagonal of %d cells (limit %d)", who, (long long) c, what,
+                                    (long long) idx, width, PHM_WAVE_MAX_WIDTH);
+        };
+        for (int64_t b = 0; b < S.n_bubbles && rcc == MRP_OK; b++)
+            for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1] && rcc == MRP_OK; k++)
+                for (int64_t j = S.allele_first[b]; j < S.allele_first[b + 1] && rcc == MRP_OK; j++)
+                    pair(S.pool + S.allele_off[j], S.allele_len[j], S.pool + S.sub_off[k], S.sub_len[k], S.sub_len[k] > sv_threshold || S.allele_len[j] > sv_threshold,
+                         "bubble", b);
+        if (rest && !sc_rest_empty(rest[c])) {
+            /* the back half's pairs: every substring of a bubble, primary or filtered, against every allele without anchors (the
+             * partition never anchors, bubbleGraph.c:1832); a variant's entries of primary reads against its two gt alleles */
+            const mrp_string_chunk_rest &R = rest[c];
+            for (int64_t b = 0; b < S.n_bubbles && rcc == MRP_OK; b++)
+                for (int64_t j = S.allele_first[b]; j < S.allele_first[b + 1] && rcc == MRP_OK; j++) {
+                    for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1] && rcc == MRP_OK; k++)
+                        pair(S.pool + S.allele_off[j], S.allele_len[j], S.pool + S.sub_off[k], S.sub_len[k], false, "bubble", b);
+                    for (int64_t k = R.fsub_first ? R.fsub_first[b] : 0; k < (R.fsub_first ? R.fsub_first[b + 1] : 0) && rcc == MRP_OK; k++)
+                        pair(S.pool + S.allele_off[j], S.allele_len[j], R.pool + R.fsub_off[k], R.fsub_len[k], false, "bubble", b);
+                }
+            for (int64_t v = 0; v < R.n_variants && rcc == MRP_OK; v++) {
+                if (R.gt[2 * v] == R.gt[2 * v + 1]) continue;
+                for (int64_t k = R.ventry_first[v]; k < R.ventry_first[v + 1] && rcc == MRP_OK; k++) {
+                    if (R.ventry_read[k] >= S.n_reads) continue;
+                    for (int w = 0; w < 2 && rcc == MRP_OK; w++) {
+                        const int64_t j = R.valle_first[v] + R.gt[2 * v + w];
+                        pair(R.pool + R.valle_off[j], R.valle_len[j], R.pool + R.ventry_off[k], R.ventry_len[k],
+                             R.ventry_len[k] > sv_threshold || R.valle_len[j] > sv_threshold, "variant", v);
                     }
                 }
-        if (rcs[(size_t) c] != MRP_OK) msgs[(size_t) c] = mrp_last_error();
+            }
+        }
+        if (rcc != MRP_OK) msgs[(size_t) c] = mrp_last_error();
     });
     for (int64_t c = 0; c < n_chunks; c++)
         if (rcs[(size_t) c] != MRP_OK) return mrp_set_error(rcs[(size_t) c], "%s", msgs[(size_t) c].c_str());
@@ -1434,9 +1663,214 @@ int mrp_string_chunks_check_pairs(int64_t n_chunks, const mrp_string_chunk *chun
 
 void mrp_string_front_destroy(mrp_string_front *F) { delete F; }
 
-int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
-                            int64_t expansion, int64_t sv_threshold, mrp_string_front **front_out) {
-    static const char *who = "mrp_phase_string_chunks";
+/* The static half of the back half, made with the front (host only): per chunk with a rest its sites (bubbles, then variants), their
+ * entries grouped into classes of equal substrings (the sort of substring_owners), and one pair per (class, strand that occurs in
+ * the class, allele) some outcome of the phasing could read -- for a bubble every allele, never anchored; for a variant its two gt
+ * alleles, anchored past sv_threshold, and only classes and strands of primary reads (a filtered read is never tagged).  A pair
+ * the front already scores (same substring, same strand's model, not anchored) is referred to, not added.  The new pairs go behind
+ * the front's own in its pair list. */
+static int sc_filtered_front(mrp_string_front *F, const mrp_string_chunk_rest *rest, int64_t sv_threshold, const std::vector<int64_t> &rpool_base) {
+    static const char *who = "mrp_phase_string_chunks_with_filtered";
+    const int64_t n_chunks = F->n_chunks;
+    const mrp_string_chunk *chunks = F->chunks;
+    mrp_string_front::Filtered &Q = F->fil;
+    mrp_string_front::Scratch &X = F->scratch;
+    const uint8_t *gpool = F->gpool.data();
+    Q.on = true;
+    Q.rest = rest;
+    Q.n_primary_pairs = F->n_pairs;
+    Q.read_base.assign((size_t) n_chunks + 1, 0);
+    Q.var_base.assign((size_t) n_chunks + 1, 0);
+    for (int64_t c = 0; c < n_chunks; c++) {
+        Q.read_base[(size_t) c + 1] = Q.read_base[(size_t) c] + chunks[c].n_reads + rest[c].n_filtered;
+        Q.var_base[(size_t) c + 1] = Q.var_base[(size_t) c] + rest[c].n_variants;
+    }
+    if (Q.read_base[(size_t) n_chunks] >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 reads in one call", who);
+    struct Local { /* one task's share; pidx: a pair of the front (>= 0) or ~(index among the task's new pairs) */
+        std::vector<FsEntry> entries;
+        std::vector<FsSite> bsites, vsites;
+        std::vector<int32_t> cbase;
+        std::vector<int64_t> pidx, xo, yo, anc, anc_n;
+        std::vector<int32_t> xl, yl;
+        std::vector<uint8_t> mi;
+    };
+    /* a task: a run of bubbles or of variants of one chunk (a chunk of 2 000 sites is sixteen tasks, not one) */
+    struct Task { int64_t c; bool variants; int64_t lo, hi; };
+    std::vector<Task> tasks;
+    constexpr int64_t TASK_SITES = 128;
+    for (int64_t c = 0; c < n_chunks; c++) {
+        if (sc_rest_empty(rest[c])) continue;
+        for (int64_t lo = 0; lo < chunks[c].n_bubbles; lo += TASK_SITES) tasks.push_back(Task{c, false, lo, std::min(chunks[c].n_bubbles, lo + TASK_SITES)});
+        for (int64_t lo = 0; lo < rest[c].n_variants; lo += TASK_SITES) tasks.push_back(Task{c, true, lo, std::min(rest[c].n_variants, lo + TASK_SITES)});
+    }
+    std::vector<Local> loc(tasks.size());
+    mrp_parallel_for((int64_t) tasks.size(), 1, [&](int64_t ti) {
+        const Task &T = tasks[(size_t) ti];
+        const int64_t c = T.c;
+        const mrp_string_chunk &S = chunks[c];
+        const mrp_string_chunk_rest &R = rest[c];
+        Local &Lc = loc[(size_t) ti];
+        const int64_t pb = F->pool_base[(size_t) c], rb = rpool_base[(size_t) c], sb = F->sub_base[(size_t) c];
+        struct Item { int64_t off; int32_t len; int64_t prim_sub; bool may_own; };
+        std::vector<Item> items;
+        std::vector<int32_t> order;
+        auto same = [&](int32_t a, int32_t d) { return items[(size_t) a].len == items[(size_t) d].len && memcmp(gpool + items[(size_t) a].off, gpool + items[(size_t) d].off, (size_t) items[(size_t) a].len) == 0; };
+        /* classes of the items that may own (entries [e0, e0 + items.size()) of Lc.entries); per class and strand block(cls, rev, rep):
+         * adds the (class, strand)'s pairs and returns where its block starts in Lc.pidx */
+        auto classes = [&](size_t e0, FsSite &st, auto block) {
+            order.clear();
+            for (size_t i = 0; i < items.size(); i++)
+                if (items[i].may_own) order.push_back((int32_t) i);
+            std::sort(order.begin(), order.end(), [&](int32_t a, int32_t d) {
+                const Item &x = items[(size_t) a], &y = items[(size_t) d];
+                if (x.len != y.len) return x.len < y.len;
+                const int cmp = memcmp(gpool + x.off, gpool + y.off, (size_t) x.len);
+                return cmp != 0 ? cmp < 0 : a < d;
+            });
+            st.cls_first = (int64_t) Lc.cbase.size() / 2;
+            int32_t n_cls = 0;
+            for (size_t i = 0; i < order.size(); n_cls++) {
+                size_t j = i + 1;
+                while (j < order.size() && same(order[i], order[j])) j++;
+                int64_t prim = -1;
+                bool has[2] = {false, false};
+                for (size_t q = i; q < j; q++) {
+                    FsEntry &e = Lc.entries[e0 + (size_t) order[q]];
+                    e.cls = n_cls;
+                    has[e.flags & 1] = true;
+                    if (prim < 0) prim = items[(size_t) order[q]].prim_sub;
+                }
+                for (int rev = 0; rev < 2; rev++) Lc.cbase.push_back(has[rev] ? (int32_t) block(rev, items[(size_t) order[i]], prim) : -1);
+                i = j;
+            }
+            st.n_classes = n_cls;
+        };
+        auto new_pair = [&](int64_t xo, int32_t xl, int64_t yo, int32_t yl, int rev, bool anchored) {
+            Lc.pidx.push_back(~(int64_t) Lc.xo.size());
+            Lc.xo.push_back(xo); Lc.xl.push_back(xl); Lc.yo.push_back(yo); Lc.yl.push_back(yl); Lc.mi.push_back((uint8_t) rev);
+            const size_t before = Lc.anc.size();
+            if (anchored) kmer_anchors(gpool + xo, xl, gpool + yo, yl, Lc.anc);
+            Lc.anc_n.push_back((int64_t) (Lc.anc.size() - before) / 2);
+        };
+        for (int64_t b = T.variants ? T.hi : T.lo; b < T.hi; b++) {
+            FsSite st{};
+            st.entry_first = (int64_t) Lc.entries.size();
+            st.chunk = (int32_t) c;
+            st.bubble = (int32_t) b;
+            st.n_alleles = (int32_t) (S.allele_first[b + 1] - S.allele_first[b]);
+            st.visited = 1;
+            items.clear();
+            /* listing order of the partition: the filtered reads in index order, then the primary reads in index order */
+            for (int64_t k = R.fsub_first ? R.fsub_first[b] : 0; k < (R.fsub_first ? R.fsub_first[b + 1] : 0); k++) {
+                const int32_t fr = R.fsub_read[k];
+                Lc.entries.push_back(FsEntry{0, (int32_t) (S.n_reads + fr), fr, (R.forward_strand[fr] ? 0 : 1) | 2});
+                items.push_back(Item{rb + R.fsub_off[k], R.fsub_len[k], -1, true});
+            }
+            for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1]; k++) {
+                const int32_t r = S.sub_read[k];
+                Lc.entries.push_back(FsEntry{0, r, (int32_t) (R.n_filtered + r), S.read_forward_strand[r] ? 0 : 1});
+                items.push_back(Item{pb + S.sub_off[k], S.sub_len[k], sb + k, true});
+            }
+            st.n_entries = (int32_t) items.size();
+            classes((size_t) st.entry_first, st, [&](int rev, const Item &rep, int64_t prim) {
+                const int64_t at = (int64_t) Lc.pidx.size();
+                /* the front's own pairs of this substring: its owner's strand, anchored past sv_threshold (bubbleGraph.c:1448-1451) */
+                int prim_rev = -1;
+                if (prim >= 0) {
+                    const int64_t po = X.owner[(size_t) prim] - sb;
+                    prim_rev = S.read_forward_strand[S.sub_read[po]] ? 0 : 1;
+                }
+                for (int64_t j = S.allele_first[b]; j < S.allele_first[b + 1]; j++) {
+                    if (prim_rev == rev && !(rep.len > sv_threshold || S.allele_len[j] > sv_threshold))
+                        Lc.pidx.push_back(F->pair_first[(size_t) prim] + (j - S.allele_first[b]));
+                    else
+                        new_pair(pb + S.allele_off[j], S.allele_len[j], rep.off, rep.len, rev, false);
+                }
+                return at;
+            });
+            Lc.bsites.push_back(st);
+        }
+        for (int64_t v = T.variants ? T.lo : T.hi; v < T.hi; v++) {
+            FsSite st{};
+            st.entry_first = (int64_t) Lc.entries.size();
+            st.chunk = (int32_t) c;
+            st.bubble = -1;
+            st.n_alleles = 2;
+            st.n_entries = (int32_t) (R.ventry_first[v + 1] - R.ventry_first[v]);
+            st.visited = R.gt[2 * v] != R.gt[2 * v + 1] && st.n_entries > 0;
+            items.clear();
+            for (int64_t k = R.ventry_first[v]; k < R.ventry_first[v + 1]; k++) {
+                const int32_t r = R.ventry_read[k];
+                const bool filtered = r >= S.n_reads;
+                const bool fwd = filtered ? R.forward_strand[r - S.n_reads] != 0 : S.read_forward_strand[r] != 0;
+                Lc.entries.push_back(FsEntry{0, r, (int32_t) (k - R.ventry_first[v]), (fwd ? 0 : 1) | (filtered ? 2 : 0)});
+                items.push_back(Item{rb + R.ventry_off[k], R.ventry_len[k], -1, st.visited && !filtered});
+            }
+            classes((size_t) st.entry_first, st, [&](int rev, const Item &rep, int64_t) {
+                const int64_t at = (int64_t) Lc.pidx.size();
+                for (int w = 0; w < 2; w++) {
+                    const int64_t j = R.valle_first[v] + R.gt[2 * v + w];
+                    new_pair(rb + R.valle_off[j], R.valle_len[j], rep.off, rep.len, rev, rep.len > sv_threshold || R.valle_len[j] > sv_threshold); /* bubbleGraph.c:2253-2263 */
+                }
+                return at;
+            });
+            Lc.vsites.push_back(st);
+        }
+    });
+    /* ---- side by side: entries, class tables and blocks task by task; the sites as bubbles of every chunk, then variants */
+    int64_t n_entries = 0, n_cbase = 0, n_pidx = 0, n_new = 0, n_b = 0, n_v = 0;
+    for (const Local &Lc : loc) {
+        n_entries += (int64_t) Lc.entries.size(); n_cbase += (int64_t) Lc.cbase.size(); n_pidx += (int64_t) Lc.pidx.size(); n_new += (int64_t) Lc.xo.size();
+        n_b += (int64_t) Lc.bsites.size(); n_v += (int64_t) Lc.vsites.size();
+    }
+    if (F->n_pairs + n_new >= (1ll << 31) || n_entries >= (1ll << 31) || n_pidx >= (1ll << 31) || n_cbase >= (1ll << 31) || n_b + n_v >= (1ll << 31))
+        return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs or entries in one call", who);
+    Q.entries.resize((size_t) n_entries);
+    Q.cbase.resize((size_t) n_cbase);
+    Q.pidx.resize((size_t) n_pidx);
+    Q.sites.resize((size_t) (n_b + n_v));
+    Q.n_bsites = n_b;
+    int64_t e0 = 0, c0 = 0, p0 = 0, b0 = 0, v0 = n_b, pair0 = F->n_pairs;
+    for (size_t ti = 0; ti < tasks.size(); ti++) {
+        const Local &Lc = loc[ti];
+        const int64_t c = tasks[ti].c;
+        for (size_t i = 0; i < Lc.entries.size(); i++) {
+            FsEntry e = Lc.entries[i];
+            e.read += (int32_t) Q.read_base[(size_t) c];
+            Q.entries[(size_t) e0 + i] = e;
+        }
+        for (size_t i = 0; i < Lc.cbase.size(); i++) Q.cbase[(size_t) c0 + i] = Lc.cbase[i] < 0 ? -1 : Lc.cbase[i] + (int32_t) p0;
+        for (size_t i = 0; i < Lc.pidx.size(); i++) Q.pidx[(size_t) p0 + i] = (int32_t) (Lc.pidx[i] >= 0 ? Lc.pidx[i] : pair0 + ~Lc.pidx[i]);
+        for (const FsSite &st : Lc.bsites) { FsSite g = st; g.entry_first += e0; g.cls_first += c0 / 2; Q.sites[(size_t) b0++] = g; }
+        for (const FsSite &st : Lc.vsites) { FsSite g = st; g.entry_first += e0; g.cls_first += c0 / 2; Q.sites[(size_t) v0++] = g; }
+        X.xo.insert(X.xo.end(), Lc.xo.begin(), Lc.xo.end());
+        X.yo.insert(X.yo.end(), Lc.yo.begin(), Lc.yo.end());
+        X.xl.insert(X.xl.end(), Lc.xl.begin(), Lc.xl.end());
+        X.yl.insert(X.yl.end(), Lc.yl.begin(), Lc.yl.end());
+        X.mi.insert(X.mi.end(), Lc.mi.begin(), Lc.mi.end());
+        for (int64_t n : Lc.anc_n) X.anchor_off.push_back(X.anchor_off.back() + n);
+        X.anchors.insert(X.anchors.end(), Lc.anc.begin(), Lc.anc.end());
+        e0 += (int64_t) Lc.entries.size(); c0 += (int64_t) Lc.cbase.size(); p0 += (int64_t) Lc.pidx.size(); pair0 += (int64_t) Lc.xo.size();
+    }
+    F->n_pairs = pair0;
+    /* a read's entries at bubbles in bubble order (a counting sort by read, filled in site order) */
+    const int64_t n_reads_all = Q.read_base[(size_t) n_chunks];
+    Q.cand_first.assign((size_t) n_reads_all + 1, 0);
+    for (int64_t s = 0; s < n_b; s++)
+        for (int64_t i = Q.sites[(size_t) s].entry_first; i < Q.sites[(size_t) s].entry_first + Q.sites[(size_t) s].n_entries; i++)
+            Q.cand_first[(size_t) Q.entries[(size_t) i].read + 1]++;
+    for (int64_t r = 0; r < n_reads_all; r++) Q.cand_first[(size_t) r + 1] += Q.cand_first[(size_t) r];
+    Q.cand.resize((size_t) Q.cand_first[(size_t) n_reads_all]);
+    std::vector<int64_t> fill(Q.cand_first.begin(), Q.cand_first.end() - 1);
+    for (int64_t s = 0; s < n_b; s++)
+        for (int64_t i = Q.sites[(size_t) s].entry_first; i < Q.sites[(size_t) s].entry_first + Q.sites[(size_t) s].n_entries; i++)
+            Q.cand[(size_t) fill[(size_t) Q.entries[(size_t) i].read]++] = (int32_t) i;
+    return MRP_OK;
+}
+
+int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest, const mrp_pair_hmm *forward_model,
+                            const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, mrp_string_front **front_out) {
+    const char *who = rest ? "mrp_phase_string_chunks_with_filtered" : "mrp_phase_string_chunks";
     const double t_begin = now_ms();
     *front_out = nullptr;
     mrp_string_front *F = new (std::nothrow) mrp_string_front();
@@ -1455,7 +1889,18 @@ int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, co
     }
     const int64_t n_bub = bubble_base[(size_t) n_chunks], n_subs = sub_base[(size_t) n_chunks];
     HostVec<uint8_t> &gpool = F->gpool;
-    gpool.resize((size_t) pool_base[(size_t) n_chunks]);
+    /* the rests' symbols behind the chunks' (a rest that points at its chunk's pool reads it there) */
+    std::vector<int64_t> rpool_base((size_t) n_chunks, 0);
+    int64_t gpool_bytes = pool_base[(size_t) n_chunks];
+    auto rest_has_own_pool = [&](int64_t c) { return !(rest[c].pool == chunks[c].pool && rest[c].pool_bytes == chunks[c].pool_bytes); };
+    if (rest)
+        for (int64_t c = 0; c < n_chunks; c++) {
+            rpool_base[(size_t) c] = pool_base[(size_t) c];
+            if (sc_rest_empty(rest[c]) || !rest_has_own_pool(c)) continue;
+            rpool_base[(size_t) c] = gpool_bytes;
+            gpool_bytes += rest[c].pool_bytes;
+        }
+    gpool.resize((size_t) gpool_bytes);
     mrp_string_front::Scratch &X = F->scratch;
     std::vector<int64_t> &g_sub_first = X.g_sub_first, &g_sub_off = X.g_sub_off;
     std::vector<int32_t> &g_sub_len = X.g_sub_len;
@@ -1465,6 +1910,8 @@ int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, co
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
         const mrp_string_chunk &S = chunks[c];
         if (S.pool_bytes) memcpy(gpool.data() + pool_base[(size_t) c], S.pool, (size_t) S.pool_bytes);
+        if (rest && !sc_rest_empty(rest[c]) && rest_has_own_pool(c) && rest[c].pool_bytes)
+            memcpy(gpool.data() + rpool_base[(size_t) c], rest[c].pool, (size_t) rest[c].pool_bytes);
         for (int64_t b = 0; b < S.n_bubbles; b++) g_sub_first[(size_t) (bubble_base[(size_t) c] + b + 1)] = sub_base[(size_t) c] + S.sub_first[b + 1];
         const int64_t ns = sub_base[(size_t) c + 1] - sub_base[(size_t) c];
         for (int64_t k = 0; k < ns; k++) {
@@ -1525,9 +1972,13 @@ int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, co
 
     F->n_subs = n_subs;
     F->n_pairs = n_pairs;
-    if (n_pairs > 0) {
+    if (rest) { /* the back half's sites; its speculative pairs join the list behind the front's own */
+        const int rc = sc_filtered_front(F, rest, sv_threshold, rpool_base);
+        if (rc != MRP_OK) return rc;
+    }
+    if (F->n_pairs > 0) {
         const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
-        const int rc = phm_classify(who, models, 2, n_pairs, (int64_t) gpool.size(), xo.data(), xl.data(), yo.data(), yl.data(), mi.data(),
+        const int rc = phm_classify(who, models, 2, F->n_pairs, (int64_t) gpool.size(), xo.data(), xl.data(), yo.data(), yl.data(), mi.data(),
                                     anchors.empty() ? nullptr : anchor_off.data(), anchors.empty() ? nullptr : anchors.data(), expansion, 0, 0, F->L);
         if (rc != MRP_OK) return rc;
     }
@@ -1539,9 +1990,11 @@ int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, co
 
 int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
                          mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
-                         mrp_string_chunks_stats *stats) {
+                         mrp_string_chunks_stats *stats, mrp_filtered_out *filtered_out, mrp_string_filtered_stats *filtered_stats) {
     const double t_begin = now_ms();
     const int64_t n_chunks = F->n_chunks, n_subs = F->n_subs, n_pairs = F->n_pairs;
+    const mrp_string_front::Filtered &Q = F->fil;
+    const bool back_half = Q.on && filtered_out != nullptr;
     const mrp_string_chunk *chunks = F->chunks;
     const std::vector<int64_t> &sub_base = F->sub_base, &pair_first = F->pair_first;
     const HostVec<uint8_t> &gpool = F->gpool;
@@ -1556,9 +2009,22 @@ int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_subst
     DevBuf<int8_t> d_hap;
     DevBuf<double> d_phred;
     d_items.pool = d_pool.pool = d_aoff.pool = d_haps.pool = d_hitems.pool = d_hap.pool = d_phred.pool = &ctx->pool;
-    PinnedBuf h_pool, h_res;
+    /* the back half: its static tables, what the phasing decided per chunk, a record per entry, the results */
+    DevBuf<FsEntry> d_fent;
+    DevBuf<FsSite> d_fsites;
+    DevBuf<FsChunk> d_fchunks;
+    DevBuf<int32_t> d_cbase, d_pidx, d_cand, d_read_seq, d_fhap;
+    DevBuf<int64_t> d_cand_first;
+    DevBuf<HtEntry> d_rec;
+    DevBuf<double> d_ftot;
+    DevBuf<uint8_t> d_used;
+    d_fent.pool = d_fsites.pool = d_fchunks.pool = d_cbase.pool = d_pidx.pool = d_cand.pool = d_read_seq.pool = d_fhap.pool = d_cand_first.pool =
+        d_rec.pool = d_ftot.pool = d_used.pool = &ctx->pool;
+    HostVec<int32_t> read_seq;
+    HostVec<FsChunk> fchunks;
+    PinnedBuf h_pool, h_res, h_fres;
     struct Events {
-        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         ~Events() { for (hipEvent_t x : e) if (x) (void) hipEventDestroy(x); }
     } ev;
     mrp_chunk_block blk;
@@ -1616,6 +2082,25 @@ int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_subst
     /* ---- the profile bytes, written into the chunks' device pool; the host copy comes back behind them */
     PHM_HIP(d_items.upload(items, s));
     PHM_HIP(d_aoff.upload(aoff_all, s));
+    const int64_t n_freads = back_half ? Q.read_base[(size_t) n_chunks] : 0, n_fvars = back_half ? Q.var_base[(size_t) n_chunks] : 0;
+    if (back_half) { /* the static tables of the back half go up with the rest; a read's tag is its sequence's */
+        read_seq.resize((size_t) n_freads);
+        for (int64_t c = 0; c < n_chunks; c++) {
+            const int64_t rb = Q.read_base[(size_t) c];
+            for (int64_t r = 0; r < chunks[c].n_reads; r++) {
+                const int32_t q = lay[(size_t) c].seq_of[(size_t) r];
+                read_seq[(size_t) (rb + r)] = q < 0 ? -1 : (int32_t) (seq_base[(size_t) c] + q);
+            }
+            for (int64_t r = 0; r < Q.rest[c].n_filtered; r++) read_seq[(size_t) (rb + chunks[c].n_reads + r)] = -2;
+        }
+        PHM_HIP(d_fent.upload(Q.entries, s));
+        PHM_HIP(d_fsites.upload(Q.sites, s));
+        PHM_HIP(d_cbase.upload(Q.cbase, s));
+        PHM_HIP(d_pidx.upload(Q.pidx, s));
+        PHM_HIP(d_cand_first.upload(Q.cand_first, s));
+        PHM_HIP(d_cand.upload(Q.cand, s));
+        PHM_HIP(d_read_seq.upload(read_seq, s));
+    }
     PHM_HIP(d_pool.alloc((size_t) dpool_bytes));
     PHM_HIP(hipMemsetAsync(d_pool.p, 0, (size_t) dpool_bytes, s)); /* sites a read skips stay 0 */
     PHM_HIP(h_pool.reserve((size_t) dpool_bytes));
@@ -1691,11 +2176,35 @@ int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_subst
     }
     PHM_HIP(d_haps.upload(haps, s));
     PHM_HIP(d_hitems.upload(hitems, s));
+    if (back_half) {
+        fchunks.resize((size_t) n_chunks);
+        for (int64_t c = 0; c < n_chunks; c++) fchunks[(size_t) c] = FsChunk{hap_base[(size_t) c], (int32_t) res[(size_t) c]->ref_start, (int32_t) res[(size_t) c]->length};
+        PHM_HIP(d_fchunks.upload(fchunks, s));
+    }
     PHM_HIP(d_hap.alloc((size_t) n_seqs_all));
     PHM_HIP(d_phred.alloc((size_t) n_seqs_all));
     PHM_HIP(h_res.reserve((size_t) n_seqs_all * 9 + 16));
     int8_t *h_hap = (int8_t *) h_res.p;
     double *h_phred = (double *) ((char *) h_res.p + (((size_t) n_seqs_all + 7) & ~(size_t) 7));
+    /* the back half's buffers, device and pinned, before the HP kernel is queued: no allocation between it and the back half */
+    double *h_ftot = nullptr;
+    int32_t *h_fhap = nullptr;
+    uint8_t *h_used = nullptr;
+    const bool count_used = back_half && filtered_stats != nullptr;
+    const size_t n_tot = 2 * (size_t) (n_freads + n_fvars), n_i32 = (size_t) (n_freads + n_fvars);
+    if (back_half) {
+        PHM_HIP(d_rec.alloc(Q.entries.size()));
+        PHM_HIP(d_ftot.alloc(n_tot));
+        PHM_HIP(d_fhap.alloc(n_i32));
+        PHM_HIP(h_fres.reserve(n_tot * sizeof(double) + n_i32 * sizeof(int32_t) + (count_used ? (size_t) n_pairs : 0) + 16));
+        h_ftot = (double *) h_fres.p;
+        h_fhap = (int32_t *) (h_ftot + n_tot);
+        h_used = (uint8_t *) (h_fhap + n_i32);
+        if (count_used) {
+            PHM_HIP(d_used.alloc((size_t) n_pairs));
+            PHM_HIP(hipMemsetAsync(d_used.p, 0, (size_t) std::max<int64_t>(n_pairs, 1), s));
+        }
+    }
     PHM_HIP(hipEventRecord(ev.e[4], s));
     if (n_seqs_all > 0) {
         hipLaunchKernelGGL(sc_assign_kernel, dim3((unsigned) ((n_seqs_all + 255) / 256)), dim3(256), 0, s, d_hitems.p, n_seqs_all, d_aoff.p, d_haps.p,
@@ -1707,7 +2216,37 @@ int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_subst
         PHM_HIP(hipMemcpyAsync(h_hap, d_hap.p, (size_t) n_seqs_all, hipMemcpyDeviceToHost, s));
         PHM_HIP(hipMemcpyAsync(h_phred, d_phred.p, (size_t) n_seqs_all * sizeof(double), hipMemcpyDeviceToHost, s));
     }
+    /* ---- the back half behind the HP kernel on the same stream: the tags and the haplotype strings are read where they are */
+    if (back_half) {
+        const int64_t n_fsites = (int64_t) Q.sites.size();
+        PHM_HIP(hipEventRecord(ev.e[5], s));
+        if (n_fsites > 0) {
+            hipLaunchKernelGGL(sc_filtered_sites_kernel, dim3((unsigned) n_fsites), dim3(64), 0, s, d_fsites.p, d_fent.p, d_cbase.p, d_pidx.p, d_read_seq.p,
+                               d_hap.p, d_fchunks.p, d_haps.p, d_rec.p, count_used ? d_used.p : nullptr);
+            PHM_HIP(hipGetLastError());
+        }
+        /* totals: h1 | h2 of the reads, then cis | trans of the variants; decisions: the reads', then the variants' */
+        double *d_h1 = d_ftot.p, *d_h2 = d_ftot.p + n_freads, *d_cis = d_ftot.p + 2 * n_freads, *d_trans = d_cis + n_fvars;
+        if (n_freads > 0) {
+            hipLaunchKernelGGL(fs_partition_kernel, dim3((unsigned) ((n_freads + 255) / 256)), dim3(256), 0, s, d_cand_first.p, d_cand.p, d_rec.p, L.d_out.p,
+                               d_read_seq.p, d_hap.p, n_freads, d_fhap.p, d_h1, d_h2);
+            PHM_HIP(hipGetLastError());
+        }
+        if (n_fvars > 0) {
+            hipLaunchKernelGGL(fs_phase_kernel, dim3((unsigned) ((n_fvars + 255) / 256)), dim3(256), 0, s, d_fsites.p + Q.n_bsites, d_rec.p, L.d_out.p, n_fvars,
+                               d_fhap.p + n_freads, d_cis, d_trans);
+            PHM_HIP(hipGetLastError());
+        }
+        PHM_HIP(hipEventRecord(ev.e[6], s));
+        if (n_tot > 0) {
+            PHM_HIP(hipMemcpyAsync(h_ftot, d_ftot.p, n_tot * sizeof(double), hipMemcpyDeviceToHost, s));
+            PHM_HIP(hipMemcpyAsync(h_fhap, d_fhap.p, n_i32 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        }
+        if (count_used && n_pairs > 0) PHM_HIP(hipMemcpyAsync(h_used, d_used.p, (size_t) n_pairs, hipMemcpyDeviceToHost, s));
+    }
     PHM_HIP(hipStreamSynchronize(s));
+    float filtered_ms = 0.f; /* (read before anything is handed over: an error leaves profiles_out / filtered_out zeroed) */
+    if (back_half && filtered_stats) PHM_HIP(hipEventElapsedTime(&filtered_ms, ev.e[5], ev.e[6]));
 
     /* ---- back to the caller's reads */
     for (int64_t c = 0; c < n_chunks; c++) {
@@ -1747,6 +2286,43 @@ int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_subst
                 return fail(MRP_ERR_NOMEM, "mrp_phase_string_chunks: out of host memory");
             }
         }
+    if (back_half) {
+        const double *h_h1 = h_ftot, *h_h2 = h_ftot + n_freads, *h_cis = h_ftot + 2 * n_freads, *h_trans = h_cis + n_fvars;
+        bool ok = true;
+        for (int64_t c = 0; c < n_chunks && ok; c++) {
+            mrp_filtered_out &O = filtered_out[c];
+            const int64_t rb = Q.read_base[(size_t) c], nr = Q.read_base[(size_t) c + 1] - rb, vb = Q.var_base[(size_t) c], nv = Q.var_base[(size_t) c + 1] - vb;
+            auto dup = [](const void *src, size_t bytes) { void *p = malloc(bytes ? bytes : 1); if (p && bytes) memcpy(p, src, bytes); return p; };
+            O.n_reads = nr;
+            O.n_variants = nv;
+            O.read_hap = (int32_t *) dup(h_fhap + rb, sizeof(int32_t) * (size_t) nr);
+            O.h1 = (double *) dup(h_h1 + rb, sizeof(double) * (size_t) nr);
+            O.h2 = (double *) dup(h_h2 + rb, sizeof(double) * (size_t) nr);
+            O.variant_state = (int32_t *) dup(h_fhap + n_freads + vb, sizeof(int32_t) * (size_t) nv);
+            O.cis = (double *) dup(h_cis + vb, sizeof(double) * (size_t) nv);
+            O.trans = (double *) dup(h_trans + vb, sizeof(double) * (size_t) nv);
+            ok = O.read_hap && O.h1 && O.h2 && O.variant_state && O.cis && O.trans;
+        }
+        if (!ok) {
+            for (int64_t c = 0; c < n_chunks; c++) {
+                mrp_filtered_out &O = filtered_out[c];
+                free(O.read_hap); free(O.h1); free(O.h2); free(O.variant_state); free(O.cis); free(O.trans);
+                memset(&O, 0, sizeof(O));
+                if (profiles_out) {
+                    mrp_profile_out &X = profiles_out[c];
+                    free(X.seqs); free(X.read_of_seq); free(X.pool); free(X.allele_number); free(X.substitution); free(X.prior);
+                    memset(&X, 0, sizeof(X));
+                }
+            }
+            return fail(MRP_ERR_NOMEM, "mrp_phase_string_chunks_with_filtered: out of host memory");
+        }
+        if (filtered_stats) {
+            filtered_stats->filtered_ms += filtered_ms;
+            filtered_stats->pairs_scored += n_pairs;
+            filtered_stats->pairs_speculative += n_pairs - Q.n_primary_pairs;
+            for (int64_t p = Q.n_primary_pairs; p < n_pairs; p++) filtered_stats->pairs_read_by_results += h_used[p] ? 1 : 0;
+        }
+    }
     if (stats) {
         float ms = 0.f;
         if (n_pairs > 0) { PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ev.e[0])); stats->pairhmm.kernel_ms = ms; stats->pairhmm.cells = L.cells; }
@@ -1758,6 +2334,8 @@ int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_subst
     for (int64_t c = 0; c < n_chunks; c++) { out[c] = res[(size_t) c]; res[(size_t) c] = nullptr; }
     L.release();
     d_items.release(); d_pool.release(); d_aoff.release(); d_haps.release(); d_hitems.release(); d_hap.release(); d_phred.release();
+    d_fent.release(); d_fsites.release(); d_fchunks.release(); d_cbase.release(); d_pidx.release(); d_cand.release(); d_read_seq.release(); d_fhap.release();
+    d_cand_first.release(); d_rec.release(); d_ftot.release(); d_used.release();
     for (mrp_chunk *&ch : dch) { delete ch; ch = nullptr; }
     ctx->pool.reclaim();
     if (stats) {
@@ -1783,17 +2361,42 @@ int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string
     const double t_begin = now_ms();
     if (stats) memset(stats, 0, sizeof(*stats));
     /* ---- checks (host only, before the context: a malformed call is refused the same with or without a device) */
-    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out);
+    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out, nullptr, "mrp_phase_string_chunks");
     if (rc != MRP_OK) return rc;
     if (!ctx) return fail(MRP_ERR_NO_DEVICE, "mrp_phase_string_chunks: no context (the pair-HMM path has no CPU fallback)");
     for (int64_t c = 0; c < n_chunks; c++) out[c] = nullptr;
     if (profiles_out) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
     if (n_chunks == 0) return MRP_OK;
     mrp_string_front *F = nullptr;
-    rc = mrp_string_front_create(n_chunks, chunks, forward_model, reverse_model, expansion, sv_threshold, &F);
+    rc = mrp_string_front_create(n_chunks, chunks, nullptr, forward_model, reverse_model, expansion, sv_threshold, &F);
     if (rc != MRP_OK) return rc;
     F->front_ms = now_ms() - t_begin;
-    rc = mrp_string_front_run(ctx, F, het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, stats);
+    rc = mrp_string_front_run(ctx, F, het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, stats, nullptr, nullptr);
+    mrp_string_front_destroy(F);
+    return rc;
+}
+
+int mrp_phase_string_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest,
+                                          const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                          double het_substitution_probability, const mrp_params *params, int64_t min_phred, mrp_phase_result **out,
+                                          int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out, mrp_filtered_out *filtered_out,
+                                          mrp_string_filtered_stats *stats) {
+    const double t_begin = now_ms();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_chunks > 0 && (!rest || !filtered_out)) return fail(MRP_ERR_ARG, "mrp_phase_string_chunks_with_filtered: null argument or bad sizes");
+    if (filtered_out && n_chunks > 0) memset(filtered_out, 0, sizeof(*filtered_out) * (size_t) n_chunks);
+    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out, rest, "mrp_phase_string_chunks_with_filtered");
+    if (rc != MRP_OK) return rc;
+    if (!ctx) return fail(MRP_ERR_NO_DEVICE, "mrp_phase_string_chunks_with_filtered: no context (the pair-HMM path has no CPU fallback)");
+    for (int64_t c = 0; c < n_chunks; c++) out[c] = nullptr;
+    if (profiles_out) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
+    if (n_chunks == 0) return MRP_OK;
+    mrp_string_front *F = nullptr;
+    rc = mrp_string_front_create(n_chunks, chunks, rest, forward_model, reverse_model, expansion, sv_threshold, &F);
+    if (rc != MRP_OK) return rc;
+    F->front_ms = now_ms() - t_begin;
+    rc = mrp_string_front_run(ctx, F, het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, stats ? &stats->chunks : nullptr,
+                              filtered_out, stats);
     mrp_string_front_destroy(F);
     return rc;
 }

@@ -512,24 +512,41 @@ int mrp_phase_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64
     return rc;
 }
 
-int mrp_queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model,
-                                  const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
-                                  const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out,
-                                  double *const *phred_out, mrp_profile_out *profiles_out, mrp_queue_stats *stats) {
+}  /* extern "C" */
+
+static void free_filtered_out(mrp_filtered_out &O) {
+    mrp_free(O.read_hap); mrp_free(O.h1); mrp_free(O.h2); mrp_free(O.variant_state); mrp_free(O.cis); mrp_free(O.trans);
+    memset(&O, 0, sizeof(O));
+}
+
+/* mrp_queue_phase_string_chunks (rest == NULL) and mrp_queue_phase_string_chunks_with_filtered: the rest travels with its chunk */
+static int queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest,
+                                     const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                     double het_substitution_probability, const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch,
+                                     mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                                     mrp_filtered_out *filtered_out, mrp_queue_stats *stats) {
+    /* (messages carry the name of the one call a batch makes, as they did before the rest existed, or the entry's own) */
+    const char *who = rest ? "mrp_queue_phase_string_chunks_with_filtered" : "mrp_phase_string_chunks";
     /* ---- every chunk's checks first, on the caller's thread and in the one call's order: no lane starts on a call that would be refused */
-    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out);
+    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out, rest, who);
     if (rc != MRP_OK) return rc;
-    if (!q) return mrp_set_error(MRP_ERR_NO_DEVICE, "mrp_queue_phase_string_chunks: no queue (the pair-HMM path has no CPU fallback)");
+    if (!q) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no queue (the pair-HMM path has no CPU fallback)", rest ? who : "mrp_queue_phase_string_chunks");
     const int n_devices = (int) q->devices.size();
     if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = n_devices; }
     for (int64_t i = 0; i < n_chunks; i++) out[i] = nullptr;
     if (profiles_out) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
-    rc = mrp_string_chunks_check_pairs(n_chunks, chunks, expansion, sv_threshold);
+    rc = mrp_string_chunks_check_pairs(n_chunks, chunks, expansion, sv_threshold, rest, who);
     if (rc != MRP_OK) return rc;
     if (n_chunks == 0) return MRP_OK;
-    /* phase.c:257-263 orders by estimated depth; here a chunk costs its (read, bubble) units, the unit the batches are cut by */
+    /* phase.c:257-263 orders by estimated depth; here a chunk costs its (read, bubble) units, the unit the batches are cut by, and
+     * with a rest that rest's (read, site) entries as well */
     std::vector<int64_t> cost((size_t) n_chunks, 0);
-    for (int64_t i = 0; i < n_chunks; i++) (void) mrp_string_chunk_units(&chunks[i], &cost[(size_t) i]);
+    for (int64_t i = 0; i < n_chunks; i++) {
+        (void) mrp_string_chunk_units(&chunks[i], &cost[(size_t) i]);
+        if (!rest) continue;
+        if (rest[i].fsub_first && chunks[i].n_bubbles > 0) cost[(size_t) i] += rest[i].fsub_first[chunks[i].n_bubbles];
+        if (rest[i].n_variants > 0) cost[(size_t) i] += rest[i].ventry_first[rest[i].n_variants];
+    }
     const int lanes = q->lanes, n_workers = n_devices * lanes;
     const QueuePlan plan = plan_queue(n_chunks, cost.data(), chunks_per_batch, n_workers, n_devices);
     const int64_t n_batches = (int64_t) plan.batch_off.size() - 1;
@@ -542,6 +559,7 @@ int mrp_queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_stri
         std::atomic<int64_t> batch{-1}; /* (the call's thread looks its batch up while the stager fills the lane's OTHER slot) */
         int64_t first = 0, count = 0;
         std::vector<mrp_string_chunk> sc;
+        std::vector<mrp_string_chunk_rest> sr;
         mrp_string_front *front = nullptr;
     };
     struct Lane { Staged st[2]; int n_staged = 0; };
@@ -562,8 +580,11 @@ int mrp_queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_stri
         st->first = plan.batch_off[(size_t) b]; st->count = plan.batch_off[(size_t) b + 1] - st->first;
         st->sc.resize((size_t) st->count);
         for (int64_t i = 0; i < st->count; i++) st->sc[(size_t) i] = chunks[plan.order[(size_t) (st->first + i)]];
+        st->sr.resize(rest ? (size_t) st->count : 0);
+        for (int64_t i = 0; rest && i < st->count; i++) st->sr[(size_t) i] = rest[plan.order[(size_t) (st->first + i)]];
         st->batch.store(b);
-        const int r = mrp_string_front_create(st->count, st->sc.data(), forward_model, reverse_model, expansion, sv_threshold, &st->front);
+        const int r = mrp_string_front_create(st->count, st->sc.data(), rest ? st->sr.data() : nullptr, forward_model, reverse_model, expansion, sv_threshold,
+                                              &st->front);
         if (r != MRP_OK) call.stage_errs[(size_t) w] = mrp_last_error();
         if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: front of batch %lld (%lld chunks) in %.1f ms\n", call.since(), w, (long long) b, (long long) st->count, ms_since(t0));
         return r;
@@ -584,10 +605,12 @@ int mrp_queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_stri
             hap[(size_t) i] = hap_out[chunk];
             if (phred_out) phred[(size_t) i] = phred_out[chunk];
         }
+        std::vector<mrp_filtered_out> fo(rest ? (size_t) count : 0);
+        if (rest) memset(fo.data(), 0, sizeof(mrp_filtered_out) * fo.size());
         mrp_string_chunks_stats ss;
         memset(&ss, 0, sizeof(ss));
         const int r = mrp_string_front_run(q->ctx[(size_t) w], cur->front, het_substitution_probability, params, min_phred, res.data(), hap.data(),
-                                           phred_out ? phred.data() : nullptr, profiles_out ? prof.data() : nullptr, &ss);
+                                           phred_out ? phred.data() : nullptr, profiles_out ? prof.data() : nullptr, &ss, rest ? fo.data() : nullptr, nullptr);
         QueueCall::PerLane &me = call.per[(size_t) w];
         if (r != MRP_OK) call.errs[(size_t) w] = mrp_last_error();
         else {
@@ -595,6 +618,7 @@ int mrp_queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_stri
                 const int64_t chunk = plan.order[(size_t) (cur->first + i)];
                 out[chunk] = res[(size_t) i];
                 if (profiles_out) profiles_out[chunk] = prof[(size_t) i];
+                if (rest) filtered_out[chunk] = fo[(size_t) i];
                 me.units += cost[(size_t) chunk];
             }
             me.chunks += count;
@@ -619,10 +643,52 @@ int mrp_queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_stri
                 mrp_free(P.seqs); mrp_free(P.read_of_seq); mrp_free(P.pool); mrp_free(P.allele_number); mrp_free(P.substitution); mrp_free(P.prior);
                 memset(&P, 0, sizeof(P));
             }
+            if (rest) free_filtered_out(filtered_out[i]);
         }
         return call.error(rc);
     }
     return MRP_OK;
+}
+
+extern "C" {
+
+int mrp_queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model,
+                                  const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
+                                  const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out,
+                                  double *const *phred_out, mrp_profile_out *profiles_out, mrp_queue_stats *stats) {
+    return queue_phase_string_chunks(q, n_chunks, chunks, nullptr, forward_model, reverse_model, expansion, sv_threshold, het_substitution_probability, params,
+                                     min_phred, chunks_per_batch, out, hap_out, phred_out, profiles_out, nullptr, stats);
+}
+
+int mrp_queue_phase_string_chunks_with_filtered(mrp_queue *q, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest,
+                                                const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                                                int64_t sv_threshold, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                mrp_profile_out *profiles_out, mrp_filtered_out *filtered_out, mrp_queue_stats *stats) {
+    if (n_chunks > 0 && (!rest || !filtered_out)) return mrp_set_error(MRP_ERR_ARG, "mrp_queue_phase_string_chunks_with_filtered: null argument or bad sizes");
+    if (filtered_out && n_chunks > 0) memset(filtered_out, 0, sizeof(*filtered_out) * (size_t) n_chunks);
+    return queue_phase_string_chunks(q, n_chunks, chunks, rest, forward_model, reverse_model, expansion, sv_threshold, het_substitution_probability, params,
+                                     min_phred, chunks_per_batch, out, hap_out, phred_out, profiles_out, filtered_out, stats);
+}
+
+int mrp_phase_string_chunks_with_filtered_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_string_chunk *chunks,
+                                                     const mrp_string_chunk_rest *rest, const mrp_pair_hmm *forward_model,
+                                                     const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                                     double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                     int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                     mrp_profile_out *profiles_out, mrp_filtered_out *filtered_out, mrp_queue_stats *stats) {
+    if (n_chunks > 0 && (!rest || !filtered_out)) return mrp_set_error(MRP_ERR_ARG, "mrp_phase_string_chunks_with_filtered_on_devices: null argument or bad sizes");
+    if (filtered_out && n_chunks > 0) memset(filtered_out, 0, sizeof(*filtered_out) * (size_t) n_chunks);
+    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out, rest, "mrp_phase_string_chunks_with_filtered_on_devices");
+    if (rc != MRP_OK) return rc;
+    mrp_queue *q = nullptr;
+    rc = mrp_queue_create(devices, n_devices, &q);
+    if (rc == MRP_OK)
+        rc = mrp_queue_phase_string_chunks_with_filtered(q, n_chunks, chunks, rest, forward_model, reverse_model, expansion, sv_threshold,
+                                                         het_substitution_probability, params, min_phred, chunks_per_batch, out, hap_out, phred_out, profiles_out,
+                                                         filtered_out, stats);
+    mrp_queue_destroy(q);
+    return rc;
 }
 
 int mrp_phase_string_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_string_chunk *chunks,
@@ -631,7 +697,7 @@ int mrp_phase_string_chunks_on_devices(const int32_t *devices, int32_t n_devices
                                        mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
                                        mrp_queue_stats *stats) {
     /* (the queue's own order of errors: a malformed call is MRP_ERR_ARG with or without a device) */
-    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out);
+    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out, nullptr, "mrp_phase_string_chunks");
     if (rc != MRP_OK) return rc;
     mrp_queue *q = nullptr;
     rc = mrp_queue_create(devices, n_devices, &q);

@@ -319,6 +319,42 @@ def make_string_chunk(seed: int, n_sites: int = 130, coverage: int = 30, allele_
     return StringChunk(bubbles=bubbles, read_names=names, read_forward_strand=np.ascontiguousarray(strand, dtype=np.uint8), hap=np.asarray(hap), truth=truth)
 
 
+def split_filtered(full: StringChunk, seed: int, filtered_share: float = 0.5, variant_share: float = 0.1):
+    """A chunk as margin phase sees it after downsampling (polish.maxDepth): a share of the reads of `full` become filtered reads,
+    the others stay primary, and variant_share * n_bubbles filtered variants (three alleles, a heterozygous genotype along the two
+    haplotypes, an entry per read of a random bubble) are added.  Returns (StringChunk of the primary reads, rest): rest a dict with
+    forward_strand (per filtered read), fsubs (per bubble a list of (filtered read, symbols), ascending reads) and variants (a list
+    of (alleles, (gt1, gt2), entries), entries (read, symbols) with filtered reads numbered behind the primary ones) -- what
+    capi.string_chunk_rest_struct takes.  Deterministic per seed."""
+    rng = np.random.default_rng([seed, 29])
+    n = len(full.read_names)
+    is_f = rng.random(n) < filtered_share
+    idx = np.zeros(n, dtype=np.int64)
+    idx[~is_f] = np.arange(int((~is_f).sum()))
+    idx[is_f] = np.arange(int(is_f.sum()))
+    n_primary = int((~is_f).sum())
+    bubbles, fsubs = [], []
+    for alleles, reads, subs in full.bubbles:
+        bubbles.append((alleles, [int(idx[r]) for r in reads if not is_f[r]], [s for r, s in zip(reads, subs) if not is_f[r]]))
+        fsubs.append(sorted(((int(idx[r]), s) for r, s in zip(reads, subs) if is_f[r]), key=lambda x: x[0]))
+    primary = StringChunk(bubbles=bubbles, read_names=[nm for nm, f in zip(full.read_names, is_f) if not f],
+                          read_forward_strand=np.ascontiguousarray(full.read_forward_strand[~is_f]), hap=full.hap[~is_f], truth=full.truth)
+    variants = []
+    with_reads = [b for b in range(len(full.bubbles)) if full.bubbles[b][1]]
+    for _ in range(int(round(variant_share * len(full.bubbles))) if with_reads else 0):
+        b = with_reads[int(rng.integers(0, len(with_reads)))]
+        ref = random_sequence(rng, 25)
+        alleles = [ref]
+        for k in (1, 2):
+            alt = ref.copy()
+            alt[10 + 3 * k] = (alt[10 + 3 * k] + k) % 4
+            alleles.append(alt)
+        g = rng.choice(3, size=2, replace=False).tolist()
+        entries = [(int(idx[r]) + (n_primary if is_f[r] else 0), _noisy_copy(rng, alleles[g[int(full.hap[r])]], 0.04, 0.02, 0.02)) for r in full.bubbles[b][1]]
+        variants.append((alleles, (int(g[0]), int(g[1])), entries))
+    return primary, dict(forward_strand=np.ascontiguousarray(full.read_forward_strand[is_f]), fsubs=fsubs, variants=variants)
+
+
 # ---- alignments before the extraction of read substrings at variant sites ----
 
 @dataclass

@@ -17,6 +17,18 @@ leg's figure is the median over the timed calls of all its processes, its spread
 legs' outputs are compared through a digest taken outside the timed region.  Prints one JSON line and writes it to --out (default profiles/string_chunks/queue.json).
 
     python tools/string_chunks_probe.py --queue [--yardstick-lib PATH] [--long 1536] [--lane-batch 192] [--reps 3]
+
+--filtered measures the back half inside the string-chunk call (mrp_phase_string_chunks_with_filtered) on the same two
+shapes at 60x with half of each chunk's reads filtered and 10 % as many filtered variants as bubbles, two ways on device 0:
+(a) the chain of the existing calls -- ONE mrp_phase_string_chunks over the primary reads, then the sites of every chunk in ONE
+mrp_phase_variants_from_tagged_reads and ONE mrp_partition_reads_by_haplotype -- of the library given with --yardstick-lib (built
+from the commit before the new call), else of this build; (b) the new call.  Timed is the host wall time around the C calls alone:
+the chain's two host assemblies of mrp_haptag_sites are made once, outside the timed region (a caller in C pays for them; here
+they are Python), so leg (a) is shown at its best.  Processes of their own, in turn a b a b a b (--rounds 3): a warm-up call, then
+--reps timed calls; median and min-max over all timed calls of a leg.  The legs' outputs are compared.  Writes
+profiles/string_chunks/filtered.json.
+
+    python tools/string_chunks_probe.py --filtered [--yardstick-lib PATH] [--small 96] [--large 12] [--reps 3] [--rounds 3]
 """
 import argparse
 import ctypes as C
@@ -230,6 +242,192 @@ def queue_leg(a):
         json.dump(rows, fh)
 
 
+def filtered_shapes(small, large):
+    out = []
+    for name, chunks in (("config2_130_sites_60x", [synth.make_string_chunk(seed=3000 + i, n_sites=130, coverage=60, allele_len=25) for i in range(small)]),
+                         ("2000_sites_60x", [synth.make_string_chunk(seed=4000 + i, n_sites=2000, coverage=60, allele_len=25, span=(10, 60)) for i in range(large)])):
+        pairs = [synth.split_filtered(c, seed=7000 + i) for i, c in enumerate(chunks)]
+        out.append((name, [p[0] for p in pairs], [p[1] for p in pairs]))
+    return out
+
+
+def chain_sites(chunks, rests, front):
+    """the chain's two host assemblies over every chunk of the call, read indices global to the call: (variants, partition sites,
+    strands, primary tags) as capi._haptag_sites takes them (tests/string_filtered_cases.py states the rules)"""
+    variants, psites, strands, tags_all, base = [], [], [], [], 0
+    for c, rest, g in zip(chunks, rests, front):
+        n_primary, n_f = len(c.read_names), len(rest["forward_strand"])
+        tags = np.where((g["hap"] == 1) | (g["hap"] == 2), g["hap"], 0).astype(np.int32)
+        strands += [c.read_forward_strand, rest["forward_strand"]]
+        tags_all += [tags, np.zeros(n_f, np.int32)]
+        for alleles, gt, entries in rest["variants"]:
+            variants.append((alleles, gt, [(base + q, sub) for q, sub in entries]))
+        res = g["result"]
+        for j in range(int(res["length"])):
+            b = int(res["ref_start"]) + j
+            alleles, reads, subs = c.bubbles[b]
+            entries = [(base + n_primary + fr, sub) for fr, sub in rest["fsubs"][b]]
+            entries += [(base + q, sub) for q, sub in sorted(zip(reads, subs), key=lambda x: x[0]) if tags[q] == 0]
+            psites.append((alleles, (int(res["hap1"][j]), int(res["hap2"][j])), entries))
+        base += n_primary + n_f
+    return variants, psites, np.concatenate(strands).astype(np.uint8), np.concatenate(tags_all), base
+
+
+def filtered_leg(a):
+    """one leg in this process: per shape a warm-up and a.reps timed calls -> JSON file a.leg_out"""
+    import pickle
+    t, tr, em = synth.margin_phase_pair_hmm_arrays()
+    f = capi.PairHmm.from_margin_hmm(t, tr, em)
+    r = f.reverse_complement()
+    params = capi.Params.from_reference_names(synth.shipped_phase_params())
+    L = capi.load()
+    with open(a.inputs, "rb") as fh:
+        shapes = pickle.load(fh)
+    Y, ctx = L, None
+    if a.filtered_leg == "a":
+        if a.yardstick_lib:
+            Y = C.CDLL(a.yardstick_lib)
+            Y.mrp_runtime_init()
+            for fn in ("mrp_context_create", "mrp_context_destroy", "mrp_phase_string_chunks", "mrp_phase_result_destroy", "mrp_last_error",
+                       "mrp_phase_variants_from_tagged_reads", "mrp_partition_reads_by_haplotype"):
+                getattr(Y, fn).argtypes = getattr(L, fn).argtypes
+                getattr(Y, fn).restype = getattr(L, fn).restype
+        ctx = C.c_void_p()
+        if Y.mrp_context_create(0, C.byref(ctx)) != capi.MRP_OK:
+            raise RuntimeError(Y.mrp_last_error().decode())
+    else:
+        gctx = capi.Context(0)
+    ok = lambda rc: None if rc == capi.MRP_OK else (_ for _ in ()).throw(RuntimeError(Y.mrp_last_error().decode()))
+    ptr = lambda x: None if x.size == 0 else x.ctypes.data
+    rows = []
+    for name, chunks, rests in shapes:
+        structs = [capi.string_chunk_struct(c) for c in chunks]
+        times, info_at, dig = [], {}, None
+        if a.filtered_leg == "a":
+            assembled = None
+            for rep in range(a.reps + 1):
+                args = capi.StringChunkArgs(chunks, False, structs)
+                st = capi.StringChunksStats()
+                t0 = time.perf_counter()
+                ok(Y.mrp_phase_string_chunks(ctx, args.n, args.arr, C.byref(f), C.byref(r), 4, 512, 0.0, C.byref(params), 0, args.res, args.hp, args.pp, None, C.byref(st)))
+                ms = 1e3 * (time.perf_counter() - t0)
+                if assembled is None:  # the warm-up call: the two host assemblies, once (the tags are the same in every call)
+                    front = args.results()
+                    variants, psites, strands, tags, n_all = chain_sites(chunks, rests, front)
+                    V, vkeep = capi._haptag_sites(variants)
+                    P, pkeep = capi._haptag_sites(psites)
+                    assembled = True
+                else:
+                    for i in range(args.n):
+                        Y.mrp_phase_result_destroy(args.res[i])
+                state, cis, trans = np.zeros(len(variants), np.int32), np.zeros(len(variants)), np.zeros(len(variants))
+                hap, h1, h2 = np.zeros(n_all, np.int32), np.zeros(n_all), np.zeros(n_all)
+                sv, sp = capi.PairHmmStats(), capi.PairHmmStats()
+                t0 = time.perf_counter()
+                ok(Y.mrp_phase_variants_from_tagged_reads(ctx, C.byref(f), C.byref(r), C.byref(V), n_all, ptr(strands), ptr(tags), 4, 512, ptr(state), ptr(cis), ptr(trans),
+                                                          C.byref(sv)))
+                ok(Y.mrp_partition_reads_by_haplotype(ctx, C.byref(f), C.byref(r), C.byref(P), n_all, ptr(strands), 4, ptr(hap), ptr(h1), ptr(h2), C.byref(sp)))
+                ms += 1e3 * (time.perf_counter() - t0)
+                pairs = [int(x.pairs_lane + x.pairs_wave) for x in (st.pairhmm, sv, sp)]
+                info = dict(pairs_front=pairs[0], pairs_variants=pairs[1], pairs_partition=pairs[2], pairs=sum(pairs), front_ms=round(st.total_ms, 2),
+                            variants_ms=round(sv.total_ms, 2), partition_ms=round(sp.total_ms, 2),
+                            pairhmm_kernel_ms=round(st.pairhmm.kernel_ms + sv.kernel_ms + sp.kernel_ms, 2))
+                if rep == 0:
+                    tagged = tags != 0
+                    dig = hashlib.sha256(b"".join(x.tobytes() for x in (np.where(tagged, tags, hap), np.where(tagged, 0.0, h1), np.where(tagged, 0.0, h2), state, cis, trans))).hexdigest()
+                else:
+                    times.append(ms)
+                    info_at[ms] = info
+        else:
+            rstructs = [capi.string_chunk_rest_struct(c, x) for c, x in zip(chunks, rests)]
+            for rep in range(a.reps + 1):
+                args = capi.StringFilteredArgs(chunks, rests, False, structs, rstructs)
+                st = capi.StringFilteredStats()
+                t0 = time.perf_counter()
+                capi._check(L.mrp_phase_string_chunks_with_filtered(gctx.h, args.n, args.arr, args.rarr, C.byref(f), C.byref(r), 4, 512, 0.0, C.byref(params), 0, args.res,
+                                                                    args.hp, args.pp, None, args.fout, C.byref(st)))
+                ms = 1e3 * (time.perf_counter() - t0)
+                out = args.results()
+                info = dict(pairs=int(st.pairs_scored), pairs_speculative=int(st.pairs_speculative), pairs_read_by_results=int(st.pairs_read_by_results),
+                            filtered_kernels_ms=round(st.filtered_ms, 3), pairhmm_kernel_ms=round(st.chunks.pairhmm.kernel_ms, 2), host_ms=round(st.chunks.host_ms, 2),
+                            phase_ms=round(st.chunks.total_ms - st.chunks.host_ms, 2))
+                if rep == 0:
+                    cat = lambda k: np.concatenate([o["filtered"][k] for o in out])
+                    dig = hashlib.sha256(b"".join(cat(k).tobytes() for k in ("read_hap", "h1", "h2", "variant_state", "cis", "trans"))).hexdigest()
+                else:
+                    times.append(ms)
+                    info_at[ms] = info
+        med = sorted(times)[len(times) // 2]
+        rows.append(dict(shape=name, chunks=len(chunks), reps_ms=[round(x, 2) for x in times], median_ms=round(med, 2), digest=dig, **info_at[med]))
+        print(f"leg {a.filtered_leg} {name}: {rows[-1]['reps_ms']} ms", file=sys.stderr, flush=True)
+    if ctx is not None:
+        Y.mrp_context_destroy(ctx)
+    else:
+        gctx.close()
+    with open(a.leg_out, "w") as fh:
+        json.dump(rows, fh)
+
+
+def filtered_probe(a):
+    import pickle
+    out = a.out or os.path.join(ROOT, "profiles", "string_chunks", "filtered.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    import tempfile
+    shapes = filtered_shapes(a.small, a.large)
+    fd, inputs = tempfile.mkstemp(suffix=".pkl")  # the legs read the same inputs; removed whatever happens
+    try:
+        with os.fdopen(fd, "wb") as fh:
+            pickle.dump(shapes, fh, protocol=4)
+        print("inputs written", file=sys.stderr, flush=True)
+        runs = filtered_legs(a, out, inputs)
+    finally:
+        os.remove(inputs)
+    filtered_report(a, out, shapes, runs)
+
+
+def filtered_legs(a, out, inputs):
+    runs = {"a": [], "b": []}
+    for leg in ["a", "b"] * a.rounds:
+        path = f"{out}.leg_{leg}"
+        cmd = [sys.executable, os.path.abspath(__file__), "--filtered-leg", leg, "--leg-out", path, "--inputs", inputs, "--reps", str(a.reps)]
+        if leg == "a" and a.yardstick_lib:
+            cmd += ["--yardstick-lib", os.path.abspath(a.yardstick_lib)]
+        subprocess.run(cmd, check=True, timeout=a.leg_timeout, cwd=ROOT)  # one GPU process at a time; a failed leg ends the probe
+        with open(path) as fh:
+            runs[leg].append(json.load(fh))
+        os.remove(path)
+    return runs
+
+
+def filtered_report(a, out, shapes, runs):
+    rows = []
+    for i, (name, chunks, rests) in enumerate(shapes):
+        legs = {}
+        for leg in ("a", "b"):
+            per = [p[i] for p in runs[leg]]
+            times = sorted(t for r in per for t in r["reps_ms"])
+            med = times[len(times) // 2]
+            at = min(per, key=lambda r: abs(r["median_ms"] - med))
+            legs[leg] = dict({k: v for k, v in at.items() if k not in ("shape", "chunks", "reps_ms", "median_ms", "digest")}, reps_ms=[r["reps_ms"] for r in per],
+                             median_ms=med, min_ms=times[0], max_ms=times[-1], digest=per[0]["digest"] if len({r["digest"] for r in per}) == 1 else None)
+        ca, nb = legs["a"], legs["b"]
+        bound = ca["median_ms"] + (ca["max_ms"] - ca["min_ms"])
+        rows.append(dict(shape=name, chunks=len(chunks), sites=sum(len(c.bubbles) for c in chunks), primary_reads=sum(len(c.read_names) for c in chunks),
+                         filtered_reads=sum(len(x["forward_strand"]) for x in rests), filtered_variants=sum(len(x["variants"]) for x in rests),
+                         chain=ca, one_call=nb, one_call_over_chain=round(nb["median_ms"] / ca["median_ms"], 3),
+                         condition="one call's median <= chain's median + chain's (max - min)", bound_ms=round(bound, 2), condition_met=bool(nb["median_ms"] <= bound),
+                         pairs_one_call_over_chain=round(nb["pairs"] / max(ca["pairs"], 1), 3),
+                         pairs_scored_over_read_by_results=round(nb["pairs"] / max(nb["pairs"] - nb["pairs_speculative"] + nb["pairs_read_by_results"], 1), 3),
+                         outputs_equal=bool(ca["digest"] is not None and ca["digest"] == nb["digest"])))
+    row = dict(probe="string_chunks_filtered", device=0, cpu=cpu_model(), reps=a.reps, processes_per_leg=a.rounds,
+               yardstick="the chain of existing calls of " + ("the library given as --yardstick-lib" if a.yardstick_lib else "this build"), shapes=rows)
+    print(json.dumps(row), flush=True)
+    with open(out, "w") as fh:
+        fh.write(json.dumps(row, indent=1) + "\n")
+    if not all(s_["outputs_equal"] for s_ in rows):
+        raise SystemExit("the legs' outputs differ")
+
+
 def cpu_model():
     try:
         with open("/proc/cpuinfo") as fh:
@@ -297,9 +495,18 @@ def main():
     ap.add_argument("--lane-batch", type=int, default=192, help="--queue: chunks per batch of leg (d)")
     ap.add_argument("--rounds", type=int, default=2, help="--queue: processes per leg, run in turn (a b c d a b c d): timings of one shape differ more between processes than within one")
     ap.add_argument("--host-threads", type=int, default=0, help="--queue: mrp_set_host_threads before the legs (the queue: per device); 0 = the library's choice")
+    ap.add_argument("--filtered", action="store_true", help="the back half inside the call against the chain of existing calls (see above)")
+    ap.add_argument("--filtered-leg", choices=("a", "b"), default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--inputs", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--queue-leg", choices=("a", "b", "c", "d"), default=None, help=argparse.SUPPRESS)
     ap.add_argument("--leg-out", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.filtered_leg:
+        return filtered_leg(a)
+    if a.filtered:
+        if a.rounds == 2:
+            a.rounds = 3  # (a b a b a b unless asked otherwise)
+        return filtered_probe(a)
     if a.queue_leg:
         return queue_leg(a)
     if a.queue:
