@@ -545,6 +545,15 @@ void mrp_string_front_destroy(mrp_string_front *front);
 int mrp_string_front_run(mrp_context *ctx, mrp_string_front *front, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
                          mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
                          mrp_string_chunks_stats *stats, mrp_filtered_out *filtered_out, mrp_string_filtered_stats *filtered_stats);
+/* frees every array of a result the string-chunk calls filled (mrp_free is free) and zeroes the struct */
+static inline void mrp_profile_out_clear(mrp_profile_out *P) {
+    free(P->seqs); free(P->read_of_seq); free(P->pool); free(P->allele_number); free(P->substitution); free(P->prior);
+    memset(P, 0, sizeof(*P));
+}
+static inline void mrp_filtered_out_clear(mrp_filtered_out *O) {
+    free(O->read_hap); free(O->h1); free(O->h2); free(O->variant_state); free(O->cis); free(O->trans);
+    memset(O, 0, sizeof(*O));
+}
 int mrp_host_threads_setting(void); /* what mrp_set_host_threads() was given, 0 if it was never called */
 /* host worker pools (mrp_api.cpp) */
 extern "C" void mrp_batch_last_launch_ms(struct mrp_batch *b, float *pack, float *emission, float *recursion);

@@ -490,11 +490,64 @@ int64_t kmer_anchors(const uint8_t *sx, int64_t lx, const uint8_t *sy, int64_t l
     return n;
 }
 
-/* The launch half of a pair-HMM batch: what a queued launch reads until its stream has drained (the host sources of its
- * uploads, its device buffers) and where the log probabilities land (d_out, indexed by pair).  The destructor drains the
- * stream, so an early return never frees what a queued copy or kernel still reads. */
+/* A batch's pairs as phm_classify reads them, in the order of the output: pair i aligns x (an allele) to y (a read substring), both
+ * in one symbol pool, with model model[i] (NULL: model 0), inside the band of the anchors (x, y) anchors[2 * anchor_off[i]] up to
+ * anchors[2 * anchor_off[i + 1]] (NULL: no pair is anchored).  The arrays are a PhmPairList's or a caller's. */
+struct PhmPairs {
+    int64_t n;
+    const int64_t *x_off;
+    const int32_t *x_len;
+    const int64_t *y_off;
+    const int32_t *y_len;
+    const uint8_t *model;
+    const int64_t *anchor_off, *anchors;
+};
+
+/* The pairs of a batch as the host makes them, one after the other (add) or side by side (resize, set, counts_to_offsets) */
+struct PhmPairList {
+    std::vector<int64_t> x_off, y_off, anchor_off{0}, anchors;
+    std::vector<int32_t> x_len, y_len;
+    std::vector<uint8_t> model;
+    int64_t size() const { return (int64_t) x_off.size(); }
+    /* pool: the symbols, for a pair that gets k-mer anchors; NULL for an unanchored one */
+    void add(int64_t xo, int32_t xl, int64_t yo, int32_t yl, int mi, const uint8_t *pool) {
+        x_off.push_back(xo); x_len.push_back(xl); y_off.push_back(yo); y_len.push_back(yl); model.push_back((uint8_t) mi);
+        if (pool) kmer_anchors(pool + xo, xl, pool + yo, yl, anchors);
+        anchor_off.push_back((int64_t) anchors.size() / 2);
+    }
+    void resize(int64_t n) {
+        x_off.resize((size_t) n); x_len.resize((size_t) n); y_off.resize((size_t) n); y_len.resize((size_t) n); model.resize((size_t) n);
+        anchor_off.assign((size_t) n + 1, 0);
+    }
+    /* n_anchors: a count for now; the caller appends the anchors themselves in pair order and calls counts_to_offsets() */
+    void set(int64_t i, int64_t xo, int32_t xl, int64_t yo, int32_t yl, int mi, int64_t n_anchors) {
+        x_off[(size_t) i] = xo; x_len[(size_t) i] = xl; y_off[(size_t) i] = yo; y_len[(size_t) i] = yl; model[(size_t) i] = (uint8_t) mi;
+        anchor_off[(size_t) i + 1] = n_anchors;
+    }
+    void counts_to_offsets() {
+        for (size_t i = 1; i < anchor_off.size(); i++) anchor_off[i] += anchor_off[i - 1];
+    }
+    void append(const PhmPairList &o) {
+        x_off.insert(x_off.end(), o.x_off.begin(), o.x_off.end());
+        x_len.insert(x_len.end(), o.x_len.begin(), o.x_len.end());
+        y_off.insert(y_off.end(), o.y_off.begin(), o.y_off.end());
+        y_len.insert(y_len.end(), o.y_len.begin(), o.y_len.end());
+        model.insert(model.end(), o.model.begin(), o.model.end());
+        for (size_t i = 1; i < o.anchor_off.size(); i++) anchor_off.push_back(anchor_off.back() + (o.anchor_off[i] - o.anchor_off[i - 1]));
+        anchors.insert(anchors.end(), o.anchors.begin(), o.anchors.end());
+    }
+    PhmPairs view() const {
+        const bool anchored = !anchors.empty();
+        return PhmPairs{size(), x_off.data(), x_len.data(), y_off.data(), y_len.data(), model.data(), anchored ? anchor_off.data() : nullptr,
+                        anchored ? anchors.data() : nullptr};
+    }
+};
+
+/* A pair-HMM batch in two halves.  PhmLaunch, the host half (phm_classify): the pairs sorted into launch classes, the bands, the
+ * models -- the sources of the uploads, so it outlives the device half.  PhmDev, the device half (phm_enqueue): the buffers of a
+ * queued launch and where the log probabilities land (d_out, indexed by pair).  Its destructor drains the stream before the buffers
+ * go back to their pool, so an early return never frees what a queued copy or kernel still reads. */
 struct PhmLaunch {
-    hipStream_t s = nullptr;
     int64_t cells = 0;
     int n_models = 0, table_bytes = 0; /* phm_classify: what phm_enqueue sizes the launches by */
     bool has_switch = false;
@@ -503,28 +556,29 @@ struct PhmLaunch {
     HostVec<PhmPair> wave_pairs[4];
     HostVec<int32_t> band;
     HostVec<uint32_t> key; /* phm_classify's sort keys (released with the launch, not between its two halves) */
+};
+struct PhmDev {
+    hipStream_t s = nullptr;
     DevBuf<PhmModelDev> d_models;
     DevBuf<uint8_t> d_pool;
     DevBuf<int32_t> d_band;
     DevBuf<double> d_out;
     DevBuf<PhmLanePair> d_lane[4];
     DevBuf<PhmPair> d_wave[4];
-    ~PhmLaunch() {
+    ~PhmDev() {
         if (s) (void) hipStreamSynchronize(s);
-    }
-    void release() {
-        d_models.release(); d_pool.release(); d_band.release(); d_out.release();
-        for (auto &b : d_lane) b.release();
-        for (auto &b : d_wave) b.release();
     }
 };
 
 /* The host half of a pair-HMM batch of n_pairs > 0 pairs, no device needed: the pairs sorted into the launch classes of
  * the two kernels, the bands of the anchored ones, the models as the kernels read them.  Every error of the batch (prefixed
  * with who) is raised here, MRP_ERR_UNSUPPORTED for a diagonal beyond PHM_WAVE_MAX_WIDTH cells among them. */
-int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, int64_t n_pairs, int64_t pool_bytes, const int64_t *x_off,
-                 const int32_t *x_len, const int64_t *y_off, const int32_t *y_len, const uint8_t *model_index, const int64_t *anchor_off,
-                 const int64_t *anchors, int64_t expansion, int ragged_left, int ragged_right, PhmLaunch &L) {
+int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, int64_t pool_bytes, const PhmPairs &P, int64_t expansion,
+                 int ragged_left, int ragged_right, PhmLaunch &L) {
+    const int64_t n_pairs = P.n;
+    const int64_t *x_off = P.x_off, *y_off = P.y_off, *anchor_off = P.anchor_off, *anchors = P.anchors;
+    const int32_t *x_len = P.x_len, *y_len = P.y_len;
+    const uint8_t *model_index = P.model;
     if (n_pairs >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
     if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
 
@@ -655,17 +709,17 @@ int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, 
 
 /* The device half: uploads what phm_classify made of n_pairs pairs over pool and queues the kernels on ctx->stream;
  * ctx->ev[0] is recorded before the first kernel. */
-int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64_t n_pairs, PhmLaunch &L, mrp_pairhmm_stats *stats) {
-    const int n_models = L.n_models, table_bytes = L.table_bytes;
-    const bool has_switch = L.has_switch;
-    HostVec<PhmLanePair> *lane_pairs = L.lane_pairs;
-    HostVec<PhmPair> *wave_pairs = L.wave_pairs;
-    HostVec<int32_t> &band = L.band;
+int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64_t n_pairs, const PhmLaunch &H, PhmDev &L, mrp_pairhmm_stats *stats) {
+    const int n_models = H.n_models, table_bytes = H.table_bytes;
+    const bool has_switch = H.has_switch;
+    const HostVec<PhmLanePair> *lane_pairs = H.lane_pairs;
+    const HostVec<PhmPair> *wave_pairs = H.wave_pairs;
+    const HostVec<int32_t> &band = H.band;
     PHM_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     L.d_models.pool = L.d_pool.pool = L.d_band.pool = L.d_out.pool = &ctx->pool;
     L.s = s; /* from here on the destructor drains the stream */
-    PHM_HIP(L.d_models.upload(L.hm, s));
+    PHM_HIP(L.d_models.upload(H.hm, s));
     PHM_HIP(L.d_pool.alloc((size_t) pool_bytes));
     if (pool_bytes) PHM_HIP(hipMemcpyAsync(L.d_pool.p, pool, (size_t) pool_bytes, hipMemcpyHostToDevice, s));
     PHM_HIP(L.d_band.upload(band, s));
@@ -718,14 +772,43 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
     return MRP_OK;
 }
 
-/* Classify, upload and queue the kernels of n_pairs > 0 pairs: errors are raised on the host, before anything is launched. */
-int phm_launch(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, int32_t n_models, int64_t n_pairs, const uint8_t *pool,
-               int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len, const int64_t *y_off, const int32_t *y_len,
-               const uint8_t *model_index, const int64_t *anchor_off, const int64_t *anchors, int64_t expansion, int ragged_left,
-               int ragged_right, PhmLaunch &L, mrp_pairhmm_stats *stats) {
-    const int rc = phm_classify(who, models, n_models, n_pairs, pool_bytes, x_off, x_len, y_off, y_len, model_index, anchor_off, anchors, expansion,
-                                ragged_left, ragged_right, L);
-    return rc != MRP_OK ? rc : phm_enqueue(ctx, pool, pool_bytes, n_pairs, L, stats);
+/* What the small entries share.  On ctx->stream: the pair-HMM kernels over P (classified first: every error of the batch is raised
+ * on the host, before anything is launched) with ctx->ev[0] in front of them -- or, with no pairs, the event alone; then reduce(s, lp),
+ * which uploads the entry's tables, launches its reduction over the log probabilities lp (indexed by pair; NULL with no pairs),
+ * records ctx->ev[1] and queues its downloads.  Then the stream is drained, stats filled and the pool reclaimed.  reduce may keep its
+ * device buffers as locals bound to ctx->pool: a block that went back to the pool is handed out again only after a reclaim().
+ * The entry's tables are allocated and copied between the two events, so kernel_ms of the haplotagging entries covers those small
+ * copies (and, on a cold pool, their hipMalloc) beside the kernels. */
+template <class Reduce>
+int phm_call(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, int32_t n_models, const uint8_t *pool, int64_t pool_bytes,
+             const PhmPairs &P, int64_t expansion, int ragged_left, int ragged_right, mrp_pairhmm_stats *stats, double t_begin, Reduce reduce) {
+    hipStream_t s = ctx->stream;
+    {
+        PhmLaunch H;
+        PhmDev L;
+        if (P.n > 0) { /* (the host's errors first, then the device: phm_enqueue makes it current) */
+            int rc = phm_classify(who, models, n_models, pool_bytes, P, expansion, ragged_left, ragged_right, H);
+            if (rc == MRP_OK) rc = phm_enqueue(ctx, pool, pool_bytes, P.n, H, L, stats);
+            if (rc != MRP_OK) return rc;
+        } else {
+            PHM_HIP(hipSetDevice(ctx->device));
+            if (stats) PHM_HIP(hipStreamSynchronize(s));
+            PHM_HIP(hipEventRecord(ctx->ev[0], s));
+        }
+        L.s = s; /* (whatever reduce has queued when it fails is drained as well) */
+        const int rc = reduce(s, L.d_out.p);
+        if (rc != MRP_OK) return rc;
+        PHM_HIP(hipStreamSynchronize(s));
+        if (stats) {
+            float ms = 0.f;
+            PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+            stats->kernel_ms = ms;
+            stats->cells = H.cells;
+        }
+    }
+    ctx->pool.reclaim();
+    if (stats) stats->total_ms = now_ms() - t_begin;
+    return MRP_OK;
 }
 
 /* cachedScores of the reference's bubble loops (bubbleGraph.c:1418,1844,2221, keyed by the substring alone): for every
@@ -768,39 +851,49 @@ struct HtEntry { /* the two log probabilities (indices into the pair-HMM output)
     int32_t live; /* the back half in the string-chunk call (fs_* kernels): the record counts; the ht_* kernels do not read it */
 };
 
-/* bubbleGraph.c:1876-1925: a lane per read walks the read's sites in order; the supports are floats (:1869, :1881-1882) */
+/* One entry's share of a read's two totals, bubbleGraph.c:1881-1884: the supports are floats (:1869, :1881-1882) */
+static __device__ __forceinline__ void ht_partition_term(const double *__restrict__ lp, const HtEntry &x, double &t1, double &t2) {
+    const double s1 = (double) (float) lp[x.a], s2 = (double) (float) lp[x.b];
+    t1 += s1 - ht_log_add_exact(s1, s2);
+    t2 += s2 - ht_log_add_exact(s2, s1);
+}
+static __device__ __forceinline__ int32_t ht_hap(double t1, double t2) { return t1 > t2 ? 1 : (t2 > t1 ? 2 : 0); }
+
+/* One tagged entry's share of a variant's two totals, bubbleGraph.c:2274-2298 (the supports stay doubles here).  Both contributions
+ * come from the same two differences, so equal supports give equal totals (an exact tie). */
+static __device__ __forceinline__ void ht_phase_term(const double *__restrict__ lp, const HtEntry &x, double &c, double &t) {
+    const double sa = lp[x.a], sb = lp[x.b];
+    const double l = ht_log_add_exact(sa, sb);
+    const double da = sa - l, db = sb - l;
+    c += x.hap1 ? da : db;
+    t += x.hap1 ? db : da;
+}
+static __device__ __forceinline__ int32_t ht_state(bool visited, double c, double t) {
+    return !visited ? MRP_VARIANT_NOT_VISITED : (c > t ? MRP_VARIANT_CIS : (t > c ? MRP_VARIANT_TRANS : MRP_VARIANT_TIE));
+}
+
+/* bubbleGraph.c:1876-1925: a lane per read walks the read's sites in order */
 __global__ void __launch_bounds__(256) ht_partition_kernel(const int64_t *__restrict__ first, const HtEntry *__restrict__ e,
                                                            const double *__restrict__ lp, int64_t n_reads, int32_t *__restrict__ hap,
                                                            double *__restrict__ h1, double *__restrict__ h2) {
     const int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_reads) return;
     double t1 = 0.0, t2 = 0.0;
-    for (int64_t i = first[r]; i < first[r + 1]; i++) {
-        const double s1 = (double) (float) lp[e[i].a], s2 = (double) (float) lp[e[i].b];
-        t1 += s1 - ht_log_add_exact(s1, s2);
-        t2 += s2 - ht_log_add_exact(s2, s1);
-    }
-    hap[r] = t1 > t2 ? 1 : (t2 > t1 ? 2 : 0);
+    for (int64_t i = first[r]; i < first[r + 1]; i++) ht_partition_term(lp, e[i], t1, t2);
+    hap[r] = ht_hap(t1, t2);
     h1[r] = t1;
     h2[r] = t2;
 }
 
-/* bubbleGraph.c:2274-2298: a lane per variant walks its tagged entries in order.  Both contributions come from the same
- * two differences, so equal supports give equal totals (an exact tie). */
+/* bubbleGraph.c:2274-2298: a lane per variant walks its tagged entries in order */
 __global__ void __launch_bounds__(256) ht_phase_kernel(const int64_t *__restrict__ first, const uint8_t *__restrict__ visited,
                                                        const HtEntry *__restrict__ e, const double *__restrict__ lp, int64_t n_variants,
                                                        int32_t *__restrict__ state, double *__restrict__ cis, double *__restrict__ trans) {
     const int64_t v = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n_variants) return;
     double c = 0.0, t = 0.0;
-    for (int64_t i = first[v]; i < first[v + 1]; i++) {
-        const double sa = lp[e[i].a], sb = lp[e[i].b];
-        const double l = ht_log_add_exact(sa, sb);
-        const double da = sa - l, db = sb - l;
-        c += e[i].hap1 ? da : db;
-        t += e[i].hap1 ? db : da;
-    }
-    state[v] = !visited[v] ? MRP_VARIANT_NOT_VISITED : (c > t ? MRP_VARIANT_CIS : (t > c ? MRP_VARIANT_TRANS : MRP_VARIANT_TIE));
+    for (int64_t i = first[v]; i < first[v + 1]; i++) ht_phase_term(lp, e[i], c, t);
+    state[v] = ht_state(visited[v] != 0, c, t);
     cis[v] = c;
     trans[v] = t;
 }
@@ -836,9 +929,8 @@ int ht_check_sites(const char *who, const mrp_haptag_sites *S, int64_t n_reads, 
 /* the pairs of the owning entries: (allele compare[0], entry) and (allele compare[1], entry) for every owner of an active
  * site; pair_of[k] = index of the first of the two (-1 for entries that own nothing) */
 struct HtPairs {
-    std::vector<int64_t> xo, yo, anchor_off{0}, anchors, pair_of;
-    std::vector<int32_t> xl, yl;
-    std::vector<uint8_t> mi;
+    PhmPairList list;
+    std::vector<int64_t> pair_of;
 };
 void ht_build_pairs(const mrp_haptag_sites *S, const std::vector<uint8_t> &active, const std::vector<int64_t> &owner,
                     const uint8_t *read_forward_strand, int64_t sv_threshold, HtPairs &P) {
@@ -847,17 +939,12 @@ void ht_build_pairs(const mrp_haptag_sites *S, const std::vector<uint8_t> &activ
         if (!active[(size_t) s]) continue;
         for (int64_t k = S->entry_first[s]; k < S->entry_first[s + 1]; k++) {
             if (owner[(size_t) k] != k) continue;
-            P.pair_of[(size_t) k] = (int64_t) P.xo.size();
+            P.pair_of[(size_t) k] = P.list.size();
             for (int w = 0; w < 2; w++) {
                 const int64_t j = S->allele_first[s] + S->compare[2 * s + w];
-                P.xo.push_back(S->allele_off[j]);
-                P.xl.push_back(S->allele_len[j]);
-                P.yo.push_back(S->entry_off[k]);
-                P.yl.push_back(S->entry_len[k]);
-                P.mi.push_back(read_forward_strand[S->entry_read[k]] ? 0 : 1);
-                if (S->entry_len[k] > sv_threshold || S->allele_len[j] > sv_threshold) /* bubbleGraph.c:2253-2263 */
-                    kmer_anchors(S->pool + S->allele_off[j], S->allele_len[j], S->pool + S->entry_off[k], S->entry_len[k], P.anchors);
-                P.anchor_off.push_back((int64_t) P.anchors.size() / 2);
+                const bool anchored = S->entry_len[k] > sv_threshold || S->allele_len[j] > sv_threshold; /* bubbleGraph.c:2253-2263 */
+                P.list.add(S->allele_off[j], S->allele_len[j], S->entry_off[k], S->entry_len[k], read_forward_strand[S->entry_read[k]] ? 0 : 1,
+                           anchored ? S->pool : nullptr);
             }
         }
     }
@@ -1145,12 +1232,9 @@ __global__ void __launch_bounds__(256) fs_partition_kernel(const int64_t *__rest
     double t1 = 0.0, t2 = 0.0;
     for (int64_t i = first[r]; i < first[r + 1]; i++) {
         const HtEntry x = e[cand[i]];
-        if (!x.live) continue;
-        const double s1 = (double) (float) lp[x.a], s2 = (double) (float) lp[x.b];
-        t1 += s1 - ht_log_add_exact(s1, s2);
-        t2 += s2 - ht_log_add_exact(s2, s1);
+        if (x.live) ht_partition_term(lp, x, t1, t2);
     }
-    hap[r] = t1 > t2 ? 1 : (t2 > t1 ? 2 : 0);
+    hap[r] = ht_hap(t1, t2);
     h1[r] = t1;
     h2[r] = t2;
 }
@@ -1165,14 +1249,9 @@ __global__ void __launch_bounds__(256) fs_phase_kernel(const FsSite *__restrict_
     double c = 0.0, t = 0.0;
     for (int64_t i = st.entry_first; i < st.entry_first + st.n_entries; i++) {
         const HtEntry x = e[i];
-        if (!x.live) continue;
-        const double sa = lp[x.a], sb = lp[x.b];
-        const double l = ht_log_add_exact(sa, sb);
-        const double da = sa - l, db = sb - l;
-        c += x.hap1 ? da : db;
-        t += x.hap1 ? db : da;
+        if (x.live) ht_phase_term(lp, x, c, t);
     }
-    state[v] = !st.visited ? MRP_VARIANT_NOT_VISITED : (c > t ? MRP_VARIANT_CIS : (t > c ? MRP_VARIANT_TRANS : MRP_VARIANT_TIE));
+    state[v] = ht_state(st.visited != 0, c, t);
     cis[v] = c;
     trans[v] = t;
 }
@@ -1283,24 +1362,13 @@ int mrp_forward_probabilities(mrp_context *ctx, const mrp_pair_hmm *models, int3
     if (n_pairs < 0 || n_models <= 0 || !models || pool_bytes < 0) return fail(MRP_ERR_ARG, "mrp_forward_probabilities: bad sizes");
     if (n_pairs == 0) return MRP_OK;
     if (!x_off || !x_len || !y_off || !y_len || !out || (pool_bytes > 0 && !pool)) return fail(MRP_ERR_ARG, "mrp_forward_probabilities: null argument");
-    PhmLaunch L;
-    const int rc = phm_launch(ctx, "mrp_forward_probabilities", models, n_models, n_pairs, pool, pool_bytes, x_off, x_len, y_off, y_len, model_index,
-                              anchor_off, anchors, expansion, ragged_left, ragged_right, L, stats);
-    if (rc != MRP_OK) return rc;
-    hipStream_t s = ctx->stream;
-    PHM_HIP(hipEventRecord(ctx->ev[1], s));
-    PHM_HIP(hipMemcpyAsync(out, L.d_out.p, (size_t) n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
-    PHM_HIP(hipStreamSynchronize(s));
-    if (stats) {
-        float ms = 0.f;
-        PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        stats->kernel_ms = ms;
-        stats->cells = L.cells;
-    }
-    L.release();
-    ctx->pool.reclaim();
-    if (stats) stats->total_ms = now_ms() - t_begin;
-    return MRP_OK;
+    const PhmPairs P{n_pairs, x_off, x_len, y_off, y_len, model_index, anchor_off, anchors};
+    return phm_call(ctx, "mrp_forward_probabilities", models, n_models, pool, pool_bytes, P, expansion, ragged_left, ragged_right, stats, t_begin,
+                    [&](hipStream_t s, const double *lp) {
+                        PHM_HIP(hipEventRecord(ctx->ev[1], s));
+                        PHM_HIP(hipMemcpyAsync(out, lp, (size_t) n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+                        return (int) MRP_OK;
+                    });
 }
 
 int mrp_allele_read_supports(mrp_context *ctx, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t n_bubbles,
@@ -1322,10 +1390,8 @@ int mrp_allele_read_supports(mrp_context *ctx, const mrp_pair_hmm *forward_model
     std::vector<int64_t> owner;
     substring_owners(n_bubbles, read_first, pool, read_off, read_len, nullptr, false, owner);
     const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
-    std::vector<int64_t> xo, yo, where, anchor_off, anchors;
-    std::vector<int32_t> xl, yl;
-    std::vector<uint8_t> mi;
-    anchor_off.push_back(0);
+    PhmPairList pairs;
+    std::vector<int64_t> where;
     std::vector<int64_t> support_first((size_t) n_bubbles + 1, 0);
     for (int64_t b = 0; b < n_bubbles; b++) {
         const int64_t na = allele_first[b + 1] - allele_first[b], nr = read_first[b + 1] - read_first[b];
@@ -1334,24 +1400,18 @@ int mrp_allele_read_supports(mrp_context *ctx, const mrp_pair_hmm *forward_model
         for (int64_t k = read_first[b]; k < read_first[b + 1]; k++) {
             if (owner[(size_t) k] != k) continue;
             for (int64_t j = allele_first[b]; j < allele_first[b + 1]; j++) {
-                xo.push_back(allele_off[j]);
-                xl.push_back(allele_len[j]);
-                yo.push_back(read_off[k]);
-                yl.push_back(read_len[k]);
-                mi.push_back(read_forward_strand[k] ? 0 : 1);
                 where.push_back(support_first[(size_t) b] + (j - allele_first[b]) * nr + (k - read_first[b]));
-                if (read_len[k] > sv_threshold || allele_len[j] > sv_threshold) { /* bubbleGraph.c:1448-1451 */
-                    if (allele_len[j] < 0 || allele_off[j] < 0 || allele_off[j] + allele_len[j] > pool_bytes)
-                        return fail(MRP_ERR_ARG, "mrp_allele_read_supports: allele outside the pool");
-                    kmer_anchors(pool + allele_off[j], allele_len[j], pool + read_off[k], read_len[k], anchors);
-                }
-                anchor_off.push_back((int64_t) anchors.size() / 2);
+                const bool anchored = read_len[k] > sv_threshold || allele_len[j] > sv_threshold; /* bubbleGraph.c:1448-1451 */
+                if (anchored && (allele_len[j] < 0 || allele_off[j] < 0 || allele_off[j] + allele_len[j] > pool_bytes))
+                    return fail(MRP_ERR_ARG, "mrp_allele_read_supports: allele outside the pool");
+                pairs.add(allele_off[j], allele_len[j], read_off[k], read_len[k], read_forward_strand[k] ? 0 : 1, anchored ? pool : nullptr);
             }
         }
     }
-    std::vector<double> lp(xo.size());
-    const int rc = mrp_forward_probabilities(ctx, models, 2, (int64_t) xo.size(), pool, pool_bytes, xo.data(), xl.data(), yo.data(), yl.data(), mi.data(),
-                                             anchors.empty() ? nullptr : anchor_off.data(), anchors.empty() ? nullptr : anchors.data(), expansion, 0, 0, lp.data(), stats);
+    std::vector<double> lp((size_t) pairs.size());
+    const PhmPairs P = pairs.view();
+    const int rc = mrp_forward_probabilities(ctx, models, 2, P.n, pool, pool_bytes, P.x_off, P.x_len, P.y_off, P.y_len, P.model, P.anchor_off, P.anchors, expansion,
+                                             0, 0, lp.data(), stats);
     if (rc != MRP_OK) return rc;
     for (size_t i = 0; i < lp.size(); i++) support[where[i]] = (float) lp[i];
     for (int64_t b = 0; b < n_bubbles; b++) {
@@ -1386,8 +1446,7 @@ int mrp_partition_reads_by_haplotype(mrp_context *ctx, const mrp_pair_hmm *forwa
     if (S.n_sites) substring_owners(S.n_sites, S.entry_first, S.pool, S.entry_off, S.entry_len, nullptr, true, owner);
     HtPairs P;
     ht_build_pairs(&S, active, owner, read_forward_strand, INT64_MAX, P);
-    const int64_t n_pairs = (int64_t) P.xo.size();
-    if (n_pairs >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
+    if (P.list.size() >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
     /* a read's (site, owner pair) list in site order: counting sort by read, filled in site order */
     HostVec<int64_t> first((size_t) n_reads + 1, 0);
     for (int64_t s = 0; s < S.n_sites; s++)
@@ -1405,47 +1464,26 @@ int mrp_partition_reads_by_haplotype(mrp_context *ctx, const mrp_pair_hmm *forwa
             }
         }
     }
-    PHM_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    DevBuf<int64_t> d_first;
-    DevBuf<HtEntry> d_ent;
-    DevBuf<int32_t> d_hap;
-    DevBuf<double> d_h;
-    d_first.pool = d_ent.pool = d_hap.pool = d_h.pool = &ctx->pool;
-    struct Drain { hipStream_t s; ~Drain() { (void) hipStreamSynchronize(s); } } drain{s};
-    PHM_HIP(d_first.upload(first, s));
-    PHM_HIP(d_ent.upload(ent, s));
-    PHM_HIP(d_hap.alloc((size_t) n_reads));
-    PHM_HIP(d_h.alloc(2 * (size_t) n_reads));
     const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
-    PhmLaunch L;
-    if (n_pairs > 0) {
-        rc = phm_launch(ctx, who, models, 2, n_pairs, S.pool, S.pool_bytes, P.xo.data(), P.xl.data(), P.yo.data(), P.yl.data(), P.mi.data(), nullptr,
-                        nullptr, expansion, 0, 0, L, stats);
-        if (rc != MRP_OK) return rc;
-    } else {
-        if (stats) PHM_HIP(hipStreamSynchronize(s));
-        PHM_HIP(hipEventRecord(ctx->ev[0], s));
-    }
-    hipLaunchKernelGGL(ht_partition_kernel, dim3((unsigned) ((n_reads + 255) / 256)), dim3(256), 0, s, d_first.p, d_ent.p, L.d_out.p, n_reads, d_hap.p,
-                       d_h.p, d_h.p + n_reads);
-    PHM_HIP(hipGetLastError());
-    PHM_HIP(hipEventRecord(ctx->ev[1], s));
-    PHM_HIP(hipMemcpyAsync(hap, d_hap.p, (size_t) n_reads * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    PHM_HIP(hipMemcpyAsync(h1, d_h.p, (size_t) n_reads * sizeof(double), hipMemcpyDeviceToHost, s));
-    PHM_HIP(hipMemcpyAsync(h2, d_h.p + n_reads, (size_t) n_reads * sizeof(double), hipMemcpyDeviceToHost, s));
-    PHM_HIP(hipStreamSynchronize(s));
-    if (stats) {
-        float ms = 0.f;
-        PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        stats->kernel_ms = ms;
-        stats->cells = L.cells;
-    }
-    L.release();
-    d_first.release(); d_ent.release(); d_hap.release(); d_h.release();
-    ctx->pool.reclaim();
-    if (stats) stats->total_ms = now_ms() - t_begin;
-    return MRP_OK;
+    return phm_call(ctx, who, models, 2, S.pool, S.pool_bytes, P.list.view(), expansion, 0, 0, stats, t_begin, [&](hipStream_t s, const double *lp) {
+        DevBuf<int64_t> d_first;
+        DevBuf<HtEntry> d_ent;
+        DevBuf<int32_t> d_hap;
+        DevBuf<double> d_h;
+        d_first.pool = d_ent.pool = d_hap.pool = d_h.pool = &ctx->pool;
+        PHM_HIP(d_first.upload(first, s));
+        PHM_HIP(d_ent.upload(ent, s));
+        PHM_HIP(d_hap.alloc((size_t) n_reads));
+        PHM_HIP(d_h.alloc(2 * (size_t) n_reads));
+        hipLaunchKernelGGL(ht_partition_kernel, dim3((unsigned) ((n_reads + 255) / 256)), dim3(256), 0, s, d_first.p, d_ent.p, lp, n_reads, d_hap.p, d_h.p,
+                           d_h.p + n_reads);
+        PHM_HIP(hipGetLastError());
+        PHM_HIP(hipEventRecord(ctx->ev[1], s));
+        PHM_HIP(hipMemcpyAsync(hap, d_hap.p, (size_t) n_reads * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        PHM_HIP(hipMemcpyAsync(h1, d_h.p, (size_t) n_reads * sizeof(double), hipMemcpyDeviceToHost, s));
+        PHM_HIP(hipMemcpyAsync(h2, d_h.p + n_reads, (size_t) n_reads * sizeof(double), hipMemcpyDeviceToHost, s));
+        return (int) MRP_OK;
+    });
 }
 
 int mrp_phase_variants_from_tagged_reads(mrp_context *ctx, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
@@ -1474,8 +1512,7 @@ int mrp_phase_variants_from_tagged_reads(mrp_context *ctx, const mrp_pair_hmm *f
     substring_owners(n_var, S.entry_first, S.pool, S.entry_off, S.entry_len, tagged.data(), false, owner);
     HtPairs P;
     ht_build_pairs(&S, active, owner, read_forward_strand, sv_threshold, P);
-    const int64_t n_pairs = (int64_t) P.xo.size();
-    if (n_pairs >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
+    if (P.list.size() >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
     /* a variant's tagged entries in order */
     HostVec<int64_t> first((size_t) n_var + 1, 0);
     HostVec<HtEntry> ent;
@@ -1488,49 +1525,28 @@ int mrp_phase_variants_from_tagged_reads(mrp_context *ctx, const mrp_pair_hmm *f
             }
         first[(size_t) v + 1] = (int64_t) ent.size();
     }
-    PHM_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    DevBuf<int64_t> d_first;
-    DevBuf<uint8_t> d_active;
-    DevBuf<HtEntry> d_ent;
-    DevBuf<int32_t> d_state;
-    DevBuf<double> d_tot;
-    d_first.pool = d_active.pool = d_ent.pool = d_state.pool = d_tot.pool = &ctx->pool;
-    struct Drain { hipStream_t s; ~Drain() { (void) hipStreamSynchronize(s); } } drain{s};
-    PHM_HIP(d_first.upload(first, s));
-    PHM_HIP(d_active.upload(active, s));
-    PHM_HIP(d_ent.upload(ent, s));
-    PHM_HIP(d_state.alloc((size_t) n_var));
-    PHM_HIP(d_tot.alloc(2 * (size_t) n_var));
     const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
-    PhmLaunch L;
-    if (n_pairs > 0) {
-        rc = phm_launch(ctx, who, models, 2, n_pairs, S.pool, S.pool_bytes, P.xo.data(), P.xl.data(), P.yo.data(), P.yl.data(), P.mi.data(),
-                        P.anchors.empty() ? nullptr : P.anchor_off.data(), P.anchors.empty() ? nullptr : P.anchors.data(), expansion, 0, 0, L, stats);
-        if (rc != MRP_OK) return rc;
-    } else {
-        if (stats) PHM_HIP(hipStreamSynchronize(s));
-        PHM_HIP(hipEventRecord(ctx->ev[0], s));
-    }
-    hipLaunchKernelGGL(ht_phase_kernel, dim3((unsigned) ((n_var + 255) / 256)), dim3(256), 0, s, d_first.p, d_active.p, d_ent.p, L.d_out.p, n_var,
-                       d_state.p, d_tot.p, d_tot.p + n_var);
-    PHM_HIP(hipGetLastError());
-    PHM_HIP(hipEventRecord(ctx->ev[1], s));
-    PHM_HIP(hipMemcpyAsync(state, d_state.p, (size_t) n_var * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    PHM_HIP(hipMemcpyAsync(cis, d_tot.p, (size_t) n_var * sizeof(double), hipMemcpyDeviceToHost, s));
-    PHM_HIP(hipMemcpyAsync(trans, d_tot.p + n_var, (size_t) n_var * sizeof(double), hipMemcpyDeviceToHost, s));
-    PHM_HIP(hipStreamSynchronize(s));
-    if (stats) {
-        float ms = 0.f;
-        PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        stats->kernel_ms = ms;
-        stats->cells = L.cells;
-    }
-    L.release();
-    d_first.release(); d_active.release(); d_ent.release(); d_state.release(); d_tot.release();
-    ctx->pool.reclaim();
-    if (stats) stats->total_ms = now_ms() - t_begin;
-    return MRP_OK;
+    return phm_call(ctx, who, models, 2, S.pool, S.pool_bytes, P.list.view(), expansion, 0, 0, stats, t_begin, [&](hipStream_t s, const double *lp) {
+        DevBuf<int64_t> d_first;
+        DevBuf<uint8_t> d_active;
+        DevBuf<HtEntry> d_ent;
+        DevBuf<int32_t> d_state;
+        DevBuf<double> d_tot;
+        d_first.pool = d_active.pool = d_ent.pool = d_state.pool = d_tot.pool = &ctx->pool;
+        PHM_HIP(d_first.upload(first, s));
+        PHM_HIP(d_active.upload(active, s));
+        PHM_HIP(d_ent.upload(ent, s));
+        PHM_HIP(d_state.alloc((size_t) n_var));
+        PHM_HIP(d_tot.alloc(2 * (size_t) n_var));
+        hipLaunchKernelGGL(ht_phase_kernel, dim3((unsigned) ((n_var + 255) / 256)), dim3(256), 0, s, d_first.p, d_active.p, d_ent.p, lp, n_var, d_state.p,
+                           d_tot.p, d_tot.p + n_var);
+        PHM_HIP(hipGetLastError());
+        PHM_HIP(hipEventRecord(ctx->ev[1], s));
+        PHM_HIP(hipMemcpyAsync(state, d_state.p, (size_t) n_var * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        PHM_HIP(hipMemcpyAsync(cis, d_tot.p, (size_t) n_var * sizeof(double), hipMemcpyDeviceToHost, s));
+        PHM_HIP(hipMemcpyAsync(trans, d_tot.p + n_var, (size_t) n_var * sizeof(double), hipMemcpyDeviceToHost, s));
+        return (int) MRP_OK;
+    });
 }
 
 }  // extern "C"
@@ -1544,14 +1560,14 @@ struct mrp_string_front {
     std::vector<int64_t> pool_base, sub_base;          /* n_chunks + 1: chunk c's symbols and substrings in the call's arrays */
     HostVec<uint8_t> gpool;                            /* every chunk's symbols: what the pair-HMM kernels read */
     std::vector<int64_t> pair_first;                   /* per substring: the pair of its owner with the bubble's allele 0 */
-    PhmLaunch L;                                       /* the pairs as phm_classify sorted them; the run adds the device half */
+    PhmLaunch L;                                       /* the pairs as phm_classify sorted them; the run adds the device half (PhmDev) */
     /* what only the front itself reads, kept until the front is destroyed: released between front and run, these ~100 bytes per
      * pair go back to the system and the run's own arrays fault fresh pages in (12 chunks of 2 000 sites: a call of 68-77 ms
      * instead of 56-61) */
     struct Scratch {
-        std::vector<int64_t> g_sub_first, g_sub_off, owner, xo, yo, anchor_off, anchors;
-        std::vector<int32_t> g_sub_len, xl, yl;
-        std::vector<uint8_t> mi;
+        std::vector<int64_t> g_sub_first, g_sub_off, owner;
+        std::vector<int32_t> g_sub_len;
+        PhmPairList pairs;                             /* the front's own, then the back half's speculative ones */
         std::vector<std::vector<int64_t>> chunk_anchors;
     } scratch;
     double front_ms = 0;                               /* host wall time of the front (the one call adds its checks) */
@@ -1669,13 +1685,134 @@ void mrp_string_front_destroy(mrp_string_front *F) { delete F; }
  * alleles, anchored past sv_threshold, and only classes and strands of primary reads (a filtered read is never tagged).  A pair
  * the front already scores (same substring, same strand's model, not anchored) is referred to, not added.  The new pairs go behind
  * the front's own in its pair list. */
+struct FsLocal { /* one task's share; pidx: a pair of the front (>= 0) or ~(index among the task's new pairs) */
+    std::vector<FsEntry> entries;
+    std::vector<FsSite> bsites, vsites;
+    std::vector<int32_t> cbase;
+    std::vector<int64_t> pidx;
+    PhmPairList pairs;
+};
+/* a task: a run of bubbles or of variants of one chunk (a chunk of 2 000 sites is sixteen tasks, not one) */
+struct FsTask { int64_t c; bool variants; int64_t lo, hi; };
+
+static void sc_filtered_task(const mrp_string_front *F, const mrp_string_chunk_rest *rest, int64_t sv_threshold, const std::vector<int64_t> &rpool_base,
+                             const FsTask &T, FsLocal &Lc) {
+    const mrp_string_front::Scratch &X = F->scratch;
+    const uint8_t *gpool = F->gpool.data();
+    const int64_t c = T.c;
+    const mrp_string_chunk &S = F->chunks[c];
+    const mrp_string_chunk_rest &R = rest[c];
+    const int64_t pb = F->pool_base[(size_t) c], rb = rpool_base[(size_t) c], sb = F->sub_base[(size_t) c];
+    struct Item { int64_t off; int32_t len; int64_t prim_sub; bool may_own; };
+    std::vector<Item> items;
+    std::vector<int32_t> order;
+    auto same = [&](int32_t a, int32_t d) { return items[(size_t) a].len == items[(size_t) d].len && memcmp(gpool + items[(size_t) a].off, gpool + items[(size_t) d].off, (size_t) items[(size_t) a].len) == 0; };
+    /* classes of the items that may own (entries [e0, e0 + items.size()) of Lc.entries); per class and strand block(cls, rev, rep):
+     * adds the (class, strand)'s pairs and returns where its block starts in Lc.pidx */
+    auto classes = [&](size_t e0, FsSite &st, auto block) {
+        order.clear();
+        for (size_t i = 0; i < items.size(); i++)
+            if (items[i].may_own) order.push_back((int32_t) i);
+        std::sort(order.begin(), order.end(), [&](int32_t a, int32_t d) {
+            const Item &x = items[(size_t) a], &y = items[(size_t) d];
+            if (x.len != y.len) return x.len < y.len;
+            const int cmp = memcmp(gpool + x.off, gpool + y.off, (size_t) x.len);
+            return cmp != 0 ? cmp < 0 : a < d;
+        });
+        st.cls_first = (int64_t) Lc.cbase.size() / 2;
+        int32_t n_cls = 0;
+        for (size_t i = 0; i < order.size(); n_cls++) {
+            size_t j = i + 1;
+            while (j < order.size() && same(order[i], order[j])) j++;
+            int64_t prim = -1;
+            bool has[2] = {false, false};
+            for (size_t q = i; q < j; q++) {
+                FsEntry &e = Lc.entries[e0 + (size_t) order[q]];
+                e.cls = n_cls;
+                has[e.flags & 1] = true;
+                if (prim < 0) prim = items[(size_t) order[q]].prim_sub;
+            }
+            for (int rev = 0; rev < 2; rev++) Lc.cbase.push_back(has[rev] ? (int32_t) block(rev, items[(size_t) order[i]], prim) : -1);
+            i = j;
+        }
+        st.n_classes = n_cls;
+    };
+    auto new_pair = [&](int64_t xo, int32_t xl, int64_t yo, int32_t yl, int rev, bool anchored) {
+        Lc.pidx.push_back(~Lc.pairs.size());
+        Lc.pairs.add(xo, xl, yo, yl, rev, anchored ? gpool : nullptr);
+    };
+    for (int64_t b = T.variants ? T.hi : T.lo; b < T.hi; b++) {
+        FsSite st{};
+        st.entry_first = (int64_t) Lc.entries.size();
+        st.chunk = (int32_t) c;
+        st.bubble = (int32_t) b;
+        st.n_alleles = (int32_t) (S.allele_first[b + 1] - S.allele_first[b]);
+        st.visited = 1;
+        items.clear();
+        /* listing order of the partition: the filtered reads in index order, then the primary reads in index order */
+        for (int64_t k = R.fsub_first ? R.fsub_first[b] : 0; k < (R.fsub_first ? R.fsub_first[b + 1] : 0); k++) {
+            const int32_t fr = R.fsub_read[k];
+            Lc.entries.push_back(FsEntry{0, (int32_t) (S.n_reads + fr), fr, (R.forward_strand[fr] ? 0 : 1) | 2});
+            items.push_back(Item{rb + R.fsub_off[k], R.fsub_len[k], -1, true});
+        }
+        for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1]; k++) {
+            const int32_t r = S.sub_read[k];
+            Lc.entries.push_back(FsEntry{0, r, (int32_t) (R.n_filtered + r), S.read_forward_strand[r] ? 0 : 1});
+            items.push_back(Item{pb + S.sub_off[k], S.sub_len[k], sb + k, true});
+        }
+        st.n_entries = (int32_t) items.size();
+        classes((size_t) st.entry_first, st, [&](int rev, const Item &rep, int64_t prim) {
+            const int64_t at = (int64_t) Lc.pidx.size();
+            /* the front's own pairs of this substring: its owner's strand, anchored past sv_threshold (bubbleGraph.c:1448-1451) */
+            int prim_rev = -1;
+            if (prim >= 0) {
+                const int64_t po = X.owner[(size_t) prim] - sb;
+                prim_rev = S.read_forward_strand[S.sub_read[po]] ? 0 : 1;
+            }
+            for (int64_t j = S.allele_first[b]; j < S.allele_first[b + 1]; j++) {
+                if (prim_rev == rev && !(rep.len > sv_threshold || S.allele_len[j] > sv_threshold))
+                    Lc.pidx.push_back(F->pair_first[(size_t) prim] + (j - S.allele_first[b]));
+                else
+                    new_pair(pb + S.allele_off[j], S.allele_len[j], rep.off, rep.len, rev, false);
+            }
+            return at;
+        });
+        Lc.bsites.push_back(st);
+    }
+    for (int64_t v = T.variants ? T.lo : T.hi; v < T.hi; v++) {
+        FsSite st{};
+        st.entry_first = (int64_t) Lc.entries.size();
+        st.chunk = (int32_t) c;
+        st.bubble = -1;
+        st.n_alleles = 2;
+        st.n_entries = (int32_t) (R.ventry_first[v + 1] - R.ventry_first[v]);
+        st.visited = R.gt[2 * v] != R.gt[2 * v + 1] && st.n_entries > 0;
+        items.clear();
+        for (int64_t k = R.ventry_first[v]; k < R.ventry_first[v + 1]; k++) {
+            const int32_t r = R.ventry_read[k];
+            const bool filtered = r >= S.n_reads;
+            const bool fwd = filtered ? R.forward_strand[r - S.n_reads] != 0 : S.read_forward_strand[r] != 0;
+            Lc.entries.push_back(FsEntry{0, r, (int32_t) (k - R.ventry_first[v]), (fwd ? 0 : 1) | (filtered ? 2 : 0)});
+            items.push_back(Item{rb + R.ventry_off[k], R.ventry_len[k], -1, st.visited && !filtered});
+        }
+        classes((size_t) st.entry_first, st, [&](int rev, const Item &rep, int64_t) {
+            const int64_t at = (int64_t) Lc.pidx.size();
+            for (int w = 0; w < 2; w++) {
+                const int64_t j = R.valle_first[v] + R.gt[2 * v + w];
+                new_pair(rb + R.valle_off[j], R.valle_len[j], rep.off, rep.len, rev, rep.len > sv_threshold || R.valle_len[j] > sv_threshold); /* bubbleGraph.c:2253-2263 */
+            }
+            return at;
+        });
+        Lc.vsites.push_back(st);
+    }
+}
+
 static int sc_filtered_front(mrp_string_front *F, const mrp_string_chunk_rest *rest, int64_t sv_threshold, const std::vector<int64_t> &rpool_base) {
     static const char *who = "mrp_phase_string_chunks_with_filtered";
     const int64_t n_chunks = F->n_chunks;
     const mrp_string_chunk *chunks = F->chunks;
     mrp_string_front::Filtered &Q = F->fil;
     mrp_string_front::Scratch &X = F->scratch;
-    const uint8_t *gpool = F->gpool.data();
     Q.on = true;
     Q.rest = rest;
     Q.n_primary_pairs = F->n_pairs;
@@ -1686,141 +1823,19 @@ static int sc_filtered_front(mrp_string_front *F, const mrp_string_chunk_rest *r
         Q.var_base[(size_t) c + 1] = Q.var_base[(size_t) c] + rest[c].n_variants;
     }
     if (Q.read_base[(size_t) n_chunks] >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 reads in one call", who);
-    struct Local { /* one task's share; pidx: a pair of the front (>= 0) or ~(index among the task's new pairs) */
-        std::vector<FsEntry> entries;
-        std::vector<FsSite> bsites, vsites;
-        std::vector<int32_t> cbase;
-        std::vector<int64_t> pidx, xo, yo, anc, anc_n;
-        std::vector<int32_t> xl, yl;
-        std::vector<uint8_t> mi;
-    };
-    /* a task: a run of bubbles or of variants of one chunk (a chunk of 2 000 sites is sixteen tasks, not one) */
-    struct Task { int64_t c; bool variants; int64_t lo, hi; };
-    std::vector<Task> tasks;
+    std::vector<FsTask> tasks;
     constexpr int64_t TASK_SITES = 128;
     for (int64_t c = 0; c < n_chunks; c++) {
         if (sc_rest_empty(rest[c])) continue;
-        for (int64_t lo = 0; lo < chunks[c].n_bubbles; lo += TASK_SITES) tasks.push_back(Task{c, false, lo, std::min(chunks[c].n_bubbles, lo + TASK_SITES)});
-        for (int64_t lo = 0; lo < rest[c].n_variants; lo += TASK_SITES) tasks.push_back(Task{c, true, lo, std::min(rest[c].n_variants, lo + TASK_SITES)});
+        for (int64_t lo = 0; lo < chunks[c].n_bubbles; lo += TASK_SITES) tasks.push_back(FsTask{c, false, lo, std::min(chunks[c].n_bubbles, lo + TASK_SITES)});
+        for (int64_t lo = 0; lo < rest[c].n_variants; lo += TASK_SITES) tasks.push_back(FsTask{c, true, lo, std::min(rest[c].n_variants, lo + TASK_SITES)});
     }
-    std::vector<Local> loc(tasks.size());
-    mrp_parallel_for((int64_t) tasks.size(), 1, [&](int64_t ti) {
-        const Task &T = tasks[(size_t) ti];
-        const int64_t c = T.c;
-        const mrp_string_chunk &S = chunks[c];
-        const mrp_string_chunk_rest &R = rest[c];
-        Local &Lc = loc[(size_t) ti];
-        const int64_t pb = F->pool_base[(size_t) c], rb = rpool_base[(size_t) c], sb = F->sub_base[(size_t) c];
-        struct Item { int64_t off; int32_t len; int64_t prim_sub; bool may_own; };
-        std::vector<Item> items;
-        std::vector<int32_t> order;
-        auto same = [&](int32_t a, int32_t d) { return items[(size_t) a].len == items[(size_t) d].len && memcmp(gpool + items[(size_t) a].off, gpool + items[(size_t) d].off, (size_t) items[(size_t) a].len) == 0; };
-        /* classes of the items that may own (entries [e0, e0 + items.size()) of Lc.entries); per class and strand block(cls, rev, rep):
-         * adds the (class, strand)'s pairs and returns where its block starts in Lc.pidx */
-        auto classes = [&](size_t e0, FsSite &st, auto block) {
-            order.clear();
-            for (size_t i = 0; i < items.size(); i++)
-                if (items[i].may_own) order.push_back((int32_t) i);
-            std::sort(order.begin(), order.end(), [&](int32_t a, int32_t d) {
-                const Item &x = items[(size_t) a], &y = items[(size_t) d];
-                if (x.len != y.len) return x.len < y.len;
-                const int cmp = memcmp(gpool + x.off, gpool + y.off, (size_t) x.len);
-                return cmp != 0 ? cmp < 0 : a < d;
-            });
-            st.cls_first = (int64_t) Lc.cbase.size() / 2;
-            int32_t n_cls = 0;
-            for (size_t i = 0; i < order.size(); n_cls++) {
-                size_t j = i + 1;
-                while (j < order.size() && same(order[i], order[j])) j++;
-                int64_t prim = -1;
-                bool has[2] = {false, false};
-                for (size_t q = i; q < j; q++) {
-                    FsEntry &e = Lc.entries[e0 + (size_t) order[q]];
-                    e.cls = n_cls;
-                    has[e.flags & 1] = true;
-                    if (prim < 0) prim = items[(size_t) order[q]].prim_sub;
-                }
-                for (int rev = 0; rev < 2; rev++) Lc.cbase.push_back(has[rev] ? (int32_t) block(rev, items[(size_t) order[i]], prim) : -1);
-                i = j;
-            }
-            st.n_classes = n_cls;
-        };
-        auto new_pair = [&](int64_t xo, int32_t xl, int64_t yo, int32_t yl, int rev, bool anchored) {
-            Lc.pidx.push_back(~(int64_t) Lc.xo.size());
-            Lc.xo.push_back(xo); Lc.xl.push_back(xl); Lc.yo.push_back(yo); Lc.yl.push_back(yl); Lc.mi.push_back((uint8_t) rev);
-            const size_t before = Lc.anc.size();
-            if (anchored) kmer_anchors(gpool + xo, xl, gpool + yo, yl, Lc.anc);
-            Lc.anc_n.push_back((int64_t) (Lc.anc.size() - before) / 2);
-        };
-        for (int64_t b = T.variants ? T.hi : T.lo; b < T.hi; b++) {
-            FsSite st{};
-            st.entry_first = (int64_t) Lc.entries.size();
-            st.chunk = (int32_t) c;
-            st.bubble = (int32_t) b;
-            st.n_alleles = (int32_t) (S.allele_first[b + 1] - S.allele_first[b]);
-            st.visited = 1;
-            items.clear();
-            /* listing order of the partition: the filtered reads in index order, then the primary reads in index order */
-            for (int64_t k = R.fsub_first ? R.fsub_first[b] : 0; k < (R.fsub_first ? R.fsub_first[b + 1] : 0); k++) {
-                const int32_t fr = R.fsub_read[k];
-                Lc.entries.push_back(FsEntry{0, (int32_t) (S.n_reads + fr), fr, (R.forward_strand[fr] ? 0 : 1) | 2});
-                items.push_back(Item{rb + R.fsub_off[k], R.fsub_len[k], -1, true});
-            }
-            for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1]; k++) {
-                const int32_t r = S.sub_read[k];
-                Lc.entries.push_back(FsEntry{0, r, (int32_t) (R.n_filtered + r), S.read_forward_strand[r] ? 0 : 1});
-                items.push_back(Item{pb + S.sub_off[k], S.sub_len[k], sb + k, true});
-            }
-            st.n_entries = (int32_t) items.size();
-            classes((size_t) st.entry_first, st, [&](int rev, const Item &rep, int64_t prim) {
-                const int64_t at = (int64_t) Lc.pidx.size();
-                /* the front's own pairs of this substring: its owner's strand, anchored past sv_threshold (bubbleGraph.c:1448-1451) */
-                int prim_rev = -1;
-                if (prim >= 0) {
-                    const int64_t po = X.owner[(size_t) prim] - sb;
-                    prim_rev = S.read_forward_strand[S.sub_read[po]] ? 0 : 1;
-                }
-                for (int64_t j = S.allele_first[b]; j < S.allele_first[b + 1]; j++) {
-                    if (prim_rev == rev && !(rep.len > sv_threshold || S.allele_len[j] > sv_threshold))
-                        Lc.pidx.push_back(F->pair_first[(size_t) prim] + (j - S.allele_first[b]));
-                    else
-                        new_pair(pb + S.allele_off[j], S.allele_len[j], rep.off, rep.len, rev, false);
-                }
-                return at;
-            });
-            Lc.bsites.push_back(st);
-        }
-        for (int64_t v = T.variants ? T.lo : T.hi; v < T.hi; v++) {
-            FsSite st{};
-            st.entry_first = (int64_t) Lc.entries.size();
-            st.chunk = (int32_t) c;
-            st.bubble = -1;
-            st.n_alleles = 2;
-            st.n_entries = (int32_t) (R.ventry_first[v + 1] - R.ventry_first[v]);
-            st.visited = R.gt[2 * v] != R.gt[2 * v + 1] && st.n_entries > 0;
-            items.clear();
-            for (int64_t k = R.ventry_first[v]; k < R.ventry_first[v + 1]; k++) {
-                const int32_t r = R.ventry_read[k];
-                const bool filtered = r >= S.n_reads;
-                const bool fwd = filtered ? R.forward_strand[r - S.n_reads] != 0 : S.read_forward_strand[r] != 0;
-                Lc.entries.push_back(FsEntry{0, r, (int32_t) (k - R.ventry_first[v]), (fwd ? 0 : 1) | (filtered ? 2 : 0)});
-                items.push_back(Item{rb + R.ventry_off[k], R.ventry_len[k], -1, st.visited && !filtered});
-            }
-            classes((size_t) st.entry_first, st, [&](int rev, const Item &rep, int64_t) {
-                const int64_t at = (int64_t) Lc.pidx.size();
-                for (int w = 0; w < 2; w++) {
-                    const int64_t j = R.valle_first[v] + R.gt[2 * v + w];
-                    new_pair(rb + R.valle_off[j], R.valle_len[j], rep.off, rep.len, rev, rep.len > sv_threshold || R.valle_len[j] > sv_threshold); /* bubbleGraph.c:2253-2263 */
-                }
-                return at;
-            });
-            Lc.vsites.push_back(st);
-        }
-    });
+    std::vector<FsLocal> loc(tasks.size());
+    mrp_parallel_for((int64_t) tasks.size(), 1, [&](int64_t ti) { sc_filtered_task(F, rest, sv_threshold, rpool_base, tasks[(size_t) ti], loc[(size_t) ti]); });
     /* ---- side by side: entries, class tables and blocks task by task; the sites as bubbles of every chunk, then variants */
     int64_t n_entries = 0, n_cbase = 0, n_pidx = 0, n_new = 0, n_b = 0, n_v = 0;
-    for (const Local &Lc : loc) {
-        n_entries += (int64_t) Lc.entries.size(); n_cbase += (int64_t) Lc.cbase.size(); n_pidx += (int64_t) Lc.pidx.size(); n_new += (int64_t) Lc.xo.size();
+    for (const FsLocal &Lc : loc) {
+        n_entries += (int64_t) Lc.entries.size(); n_cbase += (int64_t) Lc.cbase.size(); n_pidx += (int64_t) Lc.pidx.size(); n_new += Lc.pairs.size();
         n_b += (int64_t) Lc.bsites.size(); n_v += (int64_t) Lc.vsites.size();
     }
     if (F->n_pairs + n_new >= (1ll << 31) || n_entries >= (1ll << 31) || n_pidx >= (1ll << 31) || n_cbase >= (1ll << 31) || n_b + n_v >= (1ll << 31))
@@ -1832,7 +1847,7 @@ static int sc_filtered_front(mrp_string_front *F, const mrp_string_chunk_rest *r
     Q.n_bsites = n_b;
     int64_t e0 = 0, c0 = 0, p0 = 0, b0 = 0, v0 = n_b, pair0 = F->n_pairs;
     for (size_t ti = 0; ti < tasks.size(); ti++) {
-        const Local &Lc = loc[ti];
+        const FsLocal &Lc = loc[ti];
         const int64_t c = tasks[ti].c;
         for (size_t i = 0; i < Lc.entries.size(); i++) {
             FsEntry e = Lc.entries[i];
@@ -1843,14 +1858,8 @@ static int sc_filtered_front(mrp_string_front *F, const mrp_string_chunk_rest *r
         for (size_t i = 0; i < Lc.pidx.size(); i++) Q.pidx[(size_t) p0 + i] = (int32_t) (Lc.pidx[i] >= 0 ? Lc.pidx[i] : pair0 + ~Lc.pidx[i]);
         for (const FsSite &st : Lc.bsites) { FsSite g = st; g.entry_first += e0; g.cls_first += c0 / 2; Q.sites[(size_t) b0++] = g; }
         for (const FsSite &st : Lc.vsites) { FsSite g = st; g.entry_first += e0; g.cls_first += c0 / 2; Q.sites[(size_t) v0++] = g; }
-        X.xo.insert(X.xo.end(), Lc.xo.begin(), Lc.xo.end());
-        X.yo.insert(X.yo.end(), Lc.yo.begin(), Lc.yo.end());
-        X.xl.insert(X.xl.end(), Lc.xl.begin(), Lc.xl.end());
-        X.yl.insert(X.yl.end(), Lc.yl.begin(), Lc.yl.end());
-        X.mi.insert(X.mi.end(), Lc.mi.begin(), Lc.mi.end());
-        for (int64_t n : Lc.anc_n) X.anchor_off.push_back(X.anchor_off.back() + n);
-        X.anchors.insert(X.anchors.end(), Lc.anc.begin(), Lc.anc.end());
-        e0 += (int64_t) Lc.entries.size(); c0 += (int64_t) Lc.cbase.size(); p0 += (int64_t) Lc.pidx.size(); pair0 += (int64_t) Lc.xo.size();
+        X.pairs.append(Lc.pairs);
+        e0 += (int64_t) Lc.entries.size(); c0 += (int64_t) Lc.cbase.size(); p0 += (int64_t) Lc.pidx.size(); pair0 += Lc.pairs.size();
     }
     F->n_pairs = pair0;
     /* a read's entries at bubbles in bubble order (a counting sort by read, filled in site order) */
@@ -1935,12 +1944,9 @@ int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, co
     }
     const int64_t n_pairs = pair_base[(size_t) n_chunks];
     if (n_pairs >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
-    std::vector<int64_t> &xo = X.xo, &yo = X.yo, &anchor_off = X.anchor_off;
-    std::vector<int32_t> &xl = X.xl, &yl = X.yl;
-    std::vector<uint8_t> &mi = X.mi;
+    PhmPairList &pairs = X.pairs;
     std::vector<std::vector<int64_t>> &chunk_anchors = X.chunk_anchors;
-    xo.resize((size_t) n_pairs); yo.resize((size_t) n_pairs); xl.resize((size_t) n_pairs); yl.resize((size_t) n_pairs); mi.resize((size_t) n_pairs);
-    anchor_off.assign((size_t) n_pairs + 1, 0);
+    pairs.resize(n_pairs);
     chunk_anchors.resize((size_t) n_chunks);
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
         const mrp_string_chunk &S = chunks[c];
@@ -1952,21 +1958,16 @@ int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, co
                 if (owner[(size_t) (sb + k)] != sb + k) continue;
                 pair_first[(size_t) (sb + k)] = p;
                 for (int64_t j = S.allele_first[b]; j < S.allele_first[b + 1]; j++, p++) {
-                    xo[(size_t) p] = pb + S.allele_off[j];
-                    xl[(size_t) p] = S.allele_len[j];
-                    yo[(size_t) p] = pb + S.sub_off[k];
-                    yl[(size_t) p] = S.sub_len[k];
-                    mi[(size_t) p] = S.read_forward_strand[S.sub_read[k]] ? 0 : 1;
                     const size_t before = anc.size();
                     if (S.sub_len[k] > sv_threshold || S.allele_len[j] > sv_threshold) /* bubbleGraph.c:1448-1451 */
                         kmer_anchors(S.pool + S.allele_off[j], S.allele_len[j], S.pool + S.sub_off[k], S.sub_len[k], anc);
-                    anchor_off[(size_t) p + 1] = (int64_t) (anc.size() - before) / 2; /* a count for now */
+                    pairs.set(p, pb + S.allele_off[j], S.allele_len[j], pb + S.sub_off[k], S.sub_len[k], S.read_forward_strand[S.sub_read[k]] ? 0 : 1,
+                              (int64_t) (anc.size() - before) / 2);
                 }
             }
     });
-    std::vector<int64_t> &anchors = X.anchors;
-    for (int64_t p = 0; p < n_pairs; p++) anchor_off[(size_t) p + 1] += anchor_off[(size_t) p];
-    for (auto &v : chunk_anchors) anchors.insert(anchors.end(), v.begin(), v.end());
+    pairs.counts_to_offsets();
+    for (auto &v : chunk_anchors) pairs.anchors.insert(pairs.anchors.end(), v.begin(), v.end());
     for (int64_t k = 0; k < n_subs; k++) /* duplicates read their owner's pairs */
         if (owner[(size_t) k] != k) pair_first[(size_t) k] = pair_first[(size_t) owner[(size_t) k]];
 
@@ -1978,8 +1979,7 @@ int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, co
     }
     if (F->n_pairs > 0) {
         const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
-        const int rc = phm_classify(who, models, 2, F->n_pairs, (int64_t) gpool.size(), xo.data(), xl.data(), yo.data(), yl.data(), mi.data(),
-                                    anchors.empty() ? nullptr : anchor_off.data(), anchors.empty() ? nullptr : anchors.data(), expansion, 0, 0, F->L);
+        const int rc = phm_classify(who, models, 2, (int64_t) gpool.size(), pairs.view(), expansion, 0, 0, F->L);
         if (rc != MRP_OK) return rc;
     }
     F->front_ms = now_ms() - t_begin;
@@ -1988,19 +1988,30 @@ int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, co
     return MRP_OK;
 }
 
-int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
-                         mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
-                         mrp_string_chunks_stats *stats, mrp_filtered_out *filtered_out, mrp_string_filtered_stats *filtered_stats) {
-    const double t_begin = now_ms();
-    const int64_t n_chunks = F->n_chunks, n_subs = F->n_subs, n_pairs = F->n_pairs;
-    const mrp_string_front::Filtered &Q = F->fil;
-    const bool back_half = Q.on && filtered_out != nullptr;
-    const mrp_string_chunk *chunks = F->chunks;
-    const std::vector<int64_t> &sub_base = F->sub_base, &pair_first = F->pair_first;
-    const HostVec<uint8_t> &gpool = F->gpool;
-    PHM_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    /* device buffers first: they are released after the stream has drained (Drain below runs before their destructors) */
+namespace {
+
+static void *sc_dup(const void *src, size_t bytes) { /* a result array the caller frees with mrp_free */
+    void *p = malloc(bytes ? bytes : 1);
+    if (p && bytes) memcpy(p, src, bytes);
+    return p;
+}
+
+/* One run of a front: everything the queued work reads or writes until the stream has drained -- the stream, the device and pinned
+ * buffers, the host sources of the uploads, the events, the layouts -- and the chunks and results that are the run's until it hands
+ * them over.  The destructor drains the stream first, then deletes the chunks and whatever was not handed over; the buffers' own
+ * destructors follow, so mrp_string_front_run reclaims the pool once the ScRun is gone and no block can be forgotten.
+ * The steps run in the order mrp_string_front_run lists them; each queues its work on ctx->stream in the order written. */
+struct ScRun {
+    mrp_context *const ctx;
+    mrp_string_front *const F;
+    mrp_string_chunks_stats *const stats;
+    mrp_string_filtered_stats *const filtered_stats;
+    const int64_t n_chunks, n_subs, n_pairs;
+    const mrp_string_chunk *const chunks;
+    hipStream_t s = nullptr; /* set once the device is current: from then on the destructor drains it */
+    enum { EV_PAIRS_END, EV_BYTES_BEGIN, EV_BYTES_END, EV_POOL_HOME, EV_TAGS_BEGIN, EV_BACK_BEGIN, EV_BACK_END, N_EV };
+    hipEvent_t ev[N_EV] = {};
+    PhmDev D; /* the pair-HMM's device half: D.d_out holds the log probabilities every later kernel reads */
     DevBuf<ScByteItem> d_items;
     DevBuf<uint8_t> d_pool;
     DevBuf<int64_t> d_aoff;
@@ -2008,115 +2019,160 @@ int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_subst
     DevBuf<ScHapItem> d_hitems;
     DevBuf<int8_t> d_hap;
     DevBuf<double> d_phred;
-    d_items.pool = d_pool.pool = d_aoff.pool = d_haps.pool = d_hitems.pool = d_hap.pool = d_phred.pool = &ctx->pool;
-    /* the back half: its static tables, what the phasing decided per chunk, a record per entry, the results */
-    DevBuf<FsEntry> d_fent;
-    DevBuf<FsSite> d_fsites;
-    DevBuf<FsChunk> d_fchunks;
-    DevBuf<int32_t> d_cbase, d_pidx, d_cand, d_read_seq, d_fhap;
-    DevBuf<int64_t> d_cand_first;
-    DevBuf<HtEntry> d_rec;
-    DevBuf<double> d_ftot;
-    DevBuf<uint8_t> d_used;
-    d_fent.pool = d_fsites.pool = d_fchunks.pool = d_cbase.pool = d_pidx.pool = d_cand.pool = d_read_seq.pool = d_fhap.pool = d_cand_first.pool =
-        d_rec.pool = d_ftot.pool = d_used.pool = &ctx->pool;
-    HostVec<int32_t> read_seq;
-    HostVec<FsChunk> fchunks;
-    PinnedBuf h_pool, h_res, h_fres;
-    struct Events {
-        hipEvent_t e[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() { for (hipEvent_t x : e) if (x) (void) hipEventDestroy(x); }
-    } ev;
+    PinnedBuf h_pool, h_res;
+    int8_t *h_hap = nullptr;
+    double *h_phred = nullptr;
+    std::vector<ScLayout> lay;
+    std::vector<int64_t> dpool_base, aoff_base, seq_base, hap_base; /* n_chunks + 1: chunk c's share of the call's arrays */
+    int64_t dpool_bytes = 0, n_seqs_all = 0;
+    HostVec<ScByteItem> items;
+    HostVec<int64_t> aoff_all;
+    HostVec<uint64_t> haps;
+    HostVec<ScHapItem> hitems;
     mrp_chunk_block blk;
-    std::vector<mrp_chunk *> dch((size_t) n_chunks, nullptr);
-    std::vector<mrp_phase_result *> res((size_t) n_chunks, nullptr);
-    struct Cleanup {
-        hipStream_t s;
-        std::vector<mrp_chunk *> &dch;
-        std::vector<mrp_phase_result *> &res;
-        ~Cleanup() {
-            (void) hipStreamSynchronize(s);
-            for (mrp_chunk *ch : dch) delete ch;
-            for (mrp_phase_result *r : res) mrp_phase_result_destroy(r);
+    std::vector<mrp_chunk *> dch;
+    std::vector<mrp_phase_result *> res;
+    double phase_ms = 0; /* host wall time inside mrp_phase_reads_many */
+
+    /* The back half's share: its static tables, what the phasing decided per chunk, a record per entry, the results.
+     * Its four methods are called where the run has the matching step of its own; `on` false makes each a no-op. */
+    struct Back {
+        const mrp_string_front::Filtered &Q;
+        mrp_filtered_out *const out;
+        const bool on, count_used;
+        int64_t n_reads = 0, n_vars = 0;
+        size_t n_tot = 0, n_i32 = 0;
+        DevBuf<FsEntry> d_ent;
+        DevBuf<FsSite> d_sites;
+        DevBuf<FsChunk> d_chunks;
+        DevBuf<int32_t> d_cbase, d_pidx, d_cand, d_read_seq, d_hap;
+        DevBuf<int64_t> d_cand_first;
+        DevBuf<HtEntry> d_rec;
+        DevBuf<double> d_tot;
+        DevBuf<uint8_t> d_used;
+        HostVec<int32_t> read_seq;
+        HostVec<FsChunk> fchunks;
+        PinnedBuf h_res;
+        double *h_tot = nullptr;
+        int32_t *h_hap = nullptr;
+        uint8_t *h_used = nullptr;
+        float ms = 0.f;
+        Back(const mrp_string_front::Filtered &q, mrp_filtered_out *o, bool stats) : Q(q), out(o), on(q.on && o != nullptr), count_used(on && stats) {}
+        void bind(DevPool *pl) {
+            d_ent.pool = d_sites.pool = d_chunks.pool = d_cbase.pool = d_pidx.pool = d_cand.pool = d_read_seq.pool = d_hap.pool = d_cand_first.pool =
+                d_rec.pool = d_tot.pool = d_used.pool = pl;
         }
-    } cleanup{s, dch, res};
-    for (hipEvent_t &x : ev.e) PHM_HIP(hipEventCreate(&x));
-    PhmLaunch &L = F->L;
+        int upload_static(ScRun &R);
+        int alloc_results(ScRun &R);
+        int launch(ScRun &R);
+        int hand_over(ScRun &R, mrp_profile_out *profiles_out);
+    } back;
+
+    ScRun(mrp_context *c, mrp_string_front *f, mrp_string_chunks_stats *st, mrp_filtered_out *filtered_out, mrp_string_filtered_stats *fst)
+        : ctx(c), F(f), stats(st), filtered_stats(fst), n_chunks(f->n_chunks), n_subs(f->n_subs), n_pairs(f->n_pairs), chunks(f->chunks),
+          dch((size_t) f->n_chunks, nullptr), res((size_t) f->n_chunks, nullptr), back(f->fil, filtered_out, fst != nullptr) {
+        /* the one place that binds the run's device buffers to the context's pool (D: phm_enqueue) */
+        d_items.pool = d_pool.pool = d_aoff.pool = d_haps.pool = d_hitems.pool = d_hap.pool = d_phred.pool = &ctx->pool;
+        back.bind(&ctx->pool);
+    }
+    ~ScRun() {
+        if (s) (void) hipStreamSynchronize(s);
+        for (mrp_chunk *ch : dch) delete ch;
+        for (mrp_phase_result *r : res) mrp_phase_result_destroy(r);
+        for (hipEvent_t x : ev)
+            if (x) (void) hipEventDestroy(x);
+    }
+    int begin();
+    int enqueue_pairhmm();
+    int layout_and_items(double het_substitution_probability);
+    int profile_bytes();
+    int chunks_and_phase(const mrp_params *params);
+    int hp_tags(int64_t min_phred);
+    int download();
+    int hand_over(mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out);
+};
+
+int ScRun::begin() {
+    PHM_HIP(hipSetDevice(ctx->device));
+    s = ctx->stream;
+    for (hipEvent_t &x : ev) PHM_HIP(hipEventCreate(&x));
+    return MRP_OK;
+}
+
+/* the pair-HMM kernels over the front's launch classes; EV_PAIRS_END behind them */
+int ScRun::enqueue_pairhmm() {
     if (n_pairs > 0) {
-        const int rc = phm_enqueue(ctx, gpool.data(), (int64_t) gpool.size(), n_pairs, L, stats ? &stats->pairhmm : nullptr);
+        const int rc = phm_enqueue(ctx, F->gpool.data(), (int64_t) F->gpool.size(), n_pairs, F->L, D, stats ? &stats->pairhmm : nullptr);
         if (rc != MRP_OK) return rc;
     } else {
         PHM_HIP(hipEventRecord(ctx->ev[0], s));
     }
-    PHM_HIP(hipEventRecord(ev.e[0], s)); /* end of the pair-HMM kernels */
+    PHM_HIP(hipEventRecord(ev[EV_PAIRS_END], s));
+    return MRP_OK;
+}
 
-    /* ---- beside the kernels: the layout of every chunk (the index arrays only) */
-    std::vector<ScLayout> lay((size_t) n_chunks);
+/* on the host, beside the pair-HMM kernels: the layout of every chunk (the index arrays only) and where each (bubble, substring)'s
+ * bytes go.  Every chunk's pool lies in one device buffer, with mrp_chunk_create's tail slack (mrp_pack_kernel reads a read's last
+ * bytes a dword at a time) and 256-byte alignment. */
+int ScRun::layout_and_items(double het_substitution_probability) {
+    lay.resize((size_t) n_chunks);
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) { sc_layout(chunks[c], het_substitution_probability, lay[(size_t) c]); });
-    /* every chunk's pool in one device buffer, with mrp_chunk_create's tail slack (mrp_pack_kernel reads a read's last bytes a
-     * dword at a time) and 256-byte alignment */
-    std::vector<int64_t> dpool_base((size_t) n_chunks + 1, 0), aoff_base((size_t) n_chunks + 1, 0), seq_base((size_t) n_chunks + 1, 0);
+    dpool_base.assign((size_t) n_chunks + 1, 0);
+    aoff_base.assign((size_t) n_chunks + 1, 0);
+    seq_base.assign((size_t) n_chunks + 1, 0);
     for (int64_t c = 0; c < n_chunks; c++) {
         dpool_base[(size_t) c + 1] = (dpool_base[(size_t) c] + lay[(size_t) c].pool_bytes + 16 + 255) & ~(int64_t) 255;
         aoff_base[(size_t) c + 1] = aoff_base[(size_t) c] + chunks[c].n_bubbles + 1;
         seq_base[(size_t) c + 1] = seq_base[(size_t) c] + (int64_t) lay[(size_t) c].seqs.size();
     }
-    const int64_t dpool_bytes = dpool_base[(size_t) n_chunks], n_seqs_all = seq_base[(size_t) n_chunks];
-    HostVec<ScByteItem> items((size_t) n_subs);
-    HostVec<int64_t> aoff_all((size_t) aoff_base[(size_t) n_chunks]);
+    dpool_bytes = dpool_base[(size_t) n_chunks];
+    n_seqs_all = seq_base[(size_t) n_chunks];
+    items.resize((size_t) n_subs);
+    aoff_all.resize((size_t) aoff_base[(size_t) n_chunks]);
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
         const mrp_string_chunk &S = chunks[c];
         const ScLayout &Lc = lay[(size_t) c];
-        const int64_t sb = sub_base[(size_t) c];
+        const int64_t sb = F->sub_base[(size_t) c];
         for (int64_t b = 0; b < S.n_bubbles; b++)
             for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1]; k++) {
                 const mrp_read &q = Lc.seqs[(size_t) Lc.seq_of[(size_t) S.sub_read[k]]];
                 ScByteItem &it = items[(size_t) (sb + k)];
                 it.dst = dpool_base[(size_t) c] + q.pool_offset + (Lc.aoff[(size_t) b] - Lc.aoff[(size_t) q.ref_start]);
-                it.pair = (int32_t) pair_first[(size_t) (sb + k)];
+                it.pair = (int32_t) F->pair_first[(size_t) (sb + k)];
                 it.n_alleles = (int32_t) Lc.an[(size_t) b];
             }
         std::copy(Lc.aoff.begin(), Lc.aoff.end(), aoff_all.begin() + aoff_base[(size_t) c]);
     });
+    return MRP_OK;
+}
 
-    /* ---- the profile bytes, written into the chunks' device pool; the host copy comes back behind them */
+/* the profile bytes, written into the chunks' device pool; the host copy comes back behind them (EV_POOL_HOME) */
+int ScRun::profile_bytes() {
     PHM_HIP(d_items.upload(items, s));
     PHM_HIP(d_aoff.upload(aoff_all, s));
-    const int64_t n_freads = back_half ? Q.read_base[(size_t) n_chunks] : 0, n_fvars = back_half ? Q.var_base[(size_t) n_chunks] : 0;
-    if (back_half) { /* the static tables of the back half go up with the rest; a read's tag is its sequence's */
-        read_seq.resize((size_t) n_freads);
-        for (int64_t c = 0; c < n_chunks; c++) {
-            const int64_t rb = Q.read_base[(size_t) c];
-            for (int64_t r = 0; r < chunks[c].n_reads; r++) {
-                const int32_t q = lay[(size_t) c].seq_of[(size_t) r];
-                read_seq[(size_t) (rb + r)] = q < 0 ? -1 : (int32_t) (seq_base[(size_t) c] + q);
-            }
-            for (int64_t r = 0; r < Q.rest[c].n_filtered; r++) read_seq[(size_t) (rb + chunks[c].n_reads + r)] = -2;
-        }
-        PHM_HIP(d_fent.upload(Q.entries, s));
-        PHM_HIP(d_fsites.upload(Q.sites, s));
-        PHM_HIP(d_cbase.upload(Q.cbase, s));
-        PHM_HIP(d_pidx.upload(Q.pidx, s));
-        PHM_HIP(d_cand_first.upload(Q.cand_first, s));
-        PHM_HIP(d_cand.upload(Q.cand, s));
-        PHM_HIP(d_read_seq.upload(read_seq, s));
-    }
+    const int rc = back.upload_static(*this); /* the static tables of the back half go up with the rest */
+    if (rc != MRP_OK) return rc;
     PHM_HIP(d_pool.alloc((size_t) dpool_bytes));
     PHM_HIP(hipMemsetAsync(d_pool.p, 0, (size_t) dpool_bytes, s)); /* sites a read skips stay 0 */
     PHM_HIP(h_pool.reserve((size_t) dpool_bytes));
-    PHM_HIP(hipEventRecord(ev.e[1], s));
+    PHM_HIP(hipEventRecord(ev[EV_BYTES_BEGIN], s));
     if (n_subs > 0) {
-        hipLaunchKernelGGL(sc_profile_bytes_kernel, dim3((unsigned) ((n_subs + 255) / 256)), dim3(256), 0, s, d_items.p, n_subs, L.d_out.p, d_pool.p);
+        hipLaunchKernelGGL(sc_profile_bytes_kernel, dim3((unsigned) ((n_subs + 255) / 256)), dim3(256), 0, s, d_items.p, n_subs, D.d_out.p, d_pool.p);
         PHM_HIP(hipGetLastError());
     }
-    PHM_HIP(hipEventRecord(ev.e[2], s));
+    PHM_HIP(hipEventRecord(ev[EV_BYTES_END], s));
     PHM_HIP(hipMemcpyAsync(h_pool.p, d_pool.p, (size_t) dpool_bytes, hipMemcpyDeviceToHost, s));
-    PHM_HIP(hipEventRecord(ev.e[3], s)); /* the host copy is complete */
+    PHM_HIP(hipEventRecord(ev[EV_POOL_HOME], s)); /* the host copy is complete */
+    return MRP_OK;
+}
 
-    /* ---- chunks over that pool (site tables staged and uploaded behind the download), then the phasing as it stands */
+/* chunks over that pool (site tables staged and uploaded behind the download), then the phasing as it stands */
+int ScRun::chunks_and_phase(const mrp_params *params) {
     std::vector<mrp_chunk_desc> descs((size_t) n_chunks);
     std::vector<const mrp_chunk_desc *> desc_ptr((size_t) n_chunks);
     std::vector<const uint8_t *> dev_pools((size_t) n_chunks);
+    std::vector<const mrp_read *> rptr((size_t) n_chunks);
+    std::vector<int64_t> nr((size_t) n_chunks);
     for (int64_t c = 0; c < n_chunks; c++) {
         const ScLayout &Lc = lay[(size_t) c];
         mrp_chunk_desc &d = descs[(size_t) c];
@@ -2130,24 +2186,26 @@ int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_subst
         d.n_reads = (int64_t) Lc.seqs.size();
         desc_ptr[(size_t) c] = &d;
         dev_pools[(size_t) c] = d_pool.p + dpool_base[(size_t) c];
+        rptr[(size_t) c] = Lc.seqs.data();
+        nr[(size_t) c] = (int64_t) Lc.seqs.size();
     }
     int rc = mrp_chunk_block_create(ctx, n_chunks, desc_ptr.data(), dch.data(), &blk, 1, dev_pools.data());
     if (rc != MRP_OK) return rc;
-    for (mrp_chunk *ch : dch) { ch->pool_host_ready = ev.e[3]; ch->pool_host_pending.store(true); }
+    for (mrp_chunk *ch : dch) { ch->pool_host_ready = ev[EV_POOL_HOME]; ch->pool_host_pending.store(true); }
     std::vector<const mrp_chunk *> cptr(dch.begin(), dch.end());
-    std::vector<const mrp_read *> rptr((size_t) n_chunks);
-    std::vector<int64_t> nr((size_t) n_chunks);
-    for (int64_t c = 0; c < n_chunks; c++) { rptr[(size_t) c] = lay[(size_t) c].seqs.data(); nr[(size_t) c] = (int64_t) lay[(size_t) c].seqs.size(); }
-    const double t_phase0 = now_ms();
+    const double t0 = now_ms();
     rc = mrp_phase_reads_many(ctx, n_chunks, cptr.data(), rptr.data(), nr.data(), params, res.data(), stats ? &stats->phase : nullptr);
-    const double t_phase1 = now_ms();
-    if (rc != MRP_OK) return rc;
+    phase_ms = now_ms() - t0;
+    return rc;
+}
 
-    /* ---- HP tags over the same device pool: the fragments' haplotype strings go up, one lane per sequence */
-    std::vector<int64_t> hap_base((size_t) n_chunks + 1, 0);
+/* HP tags over the same device pool: the fragments' haplotype strings go up, one lane per sequence; the back half follows the HP
+ * kernel on the same stream and reads the tags and the haplotype strings where they are */
+int ScRun::hp_tags(int64_t min_phred) {
+    hap_base.assign((size_t) n_chunks + 1, 0);
     for (int64_t c = 0; c < n_chunks; c++) hap_base[(size_t) c + 1] = hap_base[(size_t) c] + 2 * (int64_t) res[(size_t) c]->length;
-    HostVec<uint64_t> haps((size_t) hap_base[(size_t) n_chunks]);
-    HostVec<ScHapItem> hitems((size_t) n_seqs_all);
+    haps.resize((size_t) hap_base[(size_t) n_chunks]);
+    hitems.resize((size_t) n_seqs_all);
     for (int64_t c = 0; c < n_chunks; c++) {
         const mrp_phase_result *g = res[(size_t) c];
         const ScLayout &Lc = lay[(size_t) c];
@@ -2176,36 +2234,15 @@ int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_subst
     }
     PHM_HIP(d_haps.upload(haps, s));
     PHM_HIP(d_hitems.upload(hitems, s));
-    if (back_half) {
-        fchunks.resize((size_t) n_chunks);
-        for (int64_t c = 0; c < n_chunks; c++) fchunks[(size_t) c] = FsChunk{hap_base[(size_t) c], (int32_t) res[(size_t) c]->ref_start, (int32_t) res[(size_t) c]->length};
-        PHM_HIP(d_fchunks.upload(fchunks, s));
-    }
     PHM_HIP(d_hap.alloc((size_t) n_seqs_all));
     PHM_HIP(d_phred.alloc((size_t) n_seqs_all));
     PHM_HIP(h_res.reserve((size_t) n_seqs_all * 9 + 16));
-    int8_t *h_hap = (int8_t *) h_res.p;
-    double *h_phred = (double *) ((char *) h_res.p + (((size_t) n_seqs_all + 7) & ~(size_t) 7));
+    h_hap = (int8_t *) h_res.p;
+    h_phred = (double *) ((char *) h_res.p + (((size_t) n_seqs_all + 7) & ~(size_t) 7));
     /* the back half's buffers, device and pinned, before the HP kernel is queued: no allocation between it and the back half */
-    double *h_ftot = nullptr;
-    int32_t *h_fhap = nullptr;
-    uint8_t *h_used = nullptr;
-    const bool count_used = back_half && filtered_stats != nullptr;
-    const size_t n_tot = 2 * (size_t) (n_freads + n_fvars), n_i32 = (size_t) (n_freads + n_fvars);
-    if (back_half) {
-        PHM_HIP(d_rec.alloc(Q.entries.size()));
-        PHM_HIP(d_ftot.alloc(n_tot));
-        PHM_HIP(d_fhap.alloc(n_i32));
-        PHM_HIP(h_fres.reserve(n_tot * sizeof(double) + n_i32 * sizeof(int32_t) + (count_used ? (size_t) n_pairs : 0) + 16));
-        h_ftot = (double *) h_fres.p;
-        h_fhap = (int32_t *) (h_ftot + n_tot);
-        h_used = (uint8_t *) (h_fhap + n_i32);
-        if (count_used) {
-            PHM_HIP(d_used.alloc((size_t) n_pairs));
-            PHM_HIP(hipMemsetAsync(d_used.p, 0, (size_t) std::max<int64_t>(n_pairs, 1), s));
-        }
-    }
-    PHM_HIP(hipEventRecord(ev.e[4], s));
+    int rc = back.alloc_results(*this);
+    if (rc != MRP_OK) return rc;
+    PHM_HIP(hipEventRecord(ev[EV_TAGS_BEGIN], s));
     if (n_seqs_all > 0) {
         hipLaunchKernelGGL(sc_assign_kernel, dim3((unsigned) ((n_seqs_all + 255) / 256)), dim3(256), 0, s, d_hitems.p, n_seqs_all, d_aoff.p, d_haps.p,
                            d_pool.p, min_phred, d_hap.p, d_phred.p);
@@ -2216,39 +2253,19 @@ int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_subst
         PHM_HIP(hipMemcpyAsync(h_hap, d_hap.p, (size_t) n_seqs_all, hipMemcpyDeviceToHost, s));
         PHM_HIP(hipMemcpyAsync(h_phred, d_phred.p, (size_t) n_seqs_all * sizeof(double), hipMemcpyDeviceToHost, s));
     }
-    /* ---- the back half behind the HP kernel on the same stream: the tags and the haplotype strings are read where they are */
-    if (back_half) {
-        const int64_t n_fsites = (int64_t) Q.sites.size();
-        PHM_HIP(hipEventRecord(ev.e[5], s));
-        if (n_fsites > 0) {
-            hipLaunchKernelGGL(sc_filtered_sites_kernel, dim3((unsigned) n_fsites), dim3(64), 0, s, d_fsites.p, d_fent.p, d_cbase.p, d_pidx.p, d_read_seq.p,
-                               d_hap.p, d_fchunks.p, d_haps.p, d_rec.p, count_used ? d_used.p : nullptr);
-            PHM_HIP(hipGetLastError());
-        }
-        /* totals: h1 | h2 of the reads, then cis | trans of the variants; decisions: the reads', then the variants' */
-        double *d_h1 = d_ftot.p, *d_h2 = d_ftot.p + n_freads, *d_cis = d_ftot.p + 2 * n_freads, *d_trans = d_cis + n_fvars;
-        if (n_freads > 0) {
-            hipLaunchKernelGGL(fs_partition_kernel, dim3((unsigned) ((n_freads + 255) / 256)), dim3(256), 0, s, d_cand_first.p, d_cand.p, d_rec.p, L.d_out.p,
-                               d_read_seq.p, d_hap.p, n_freads, d_fhap.p, d_h1, d_h2);
-            PHM_HIP(hipGetLastError());
-        }
-        if (n_fvars > 0) {
-            hipLaunchKernelGGL(fs_phase_kernel, dim3((unsigned) ((n_fvars + 255) / 256)), dim3(256), 0, s, d_fsites.p + Q.n_bsites, d_rec.p, L.d_out.p, n_fvars,
-                               d_fhap.p + n_freads, d_cis, d_trans);
-            PHM_HIP(hipGetLastError());
-        }
-        PHM_HIP(hipEventRecord(ev.e[6], s));
-        if (n_tot > 0) {
-            PHM_HIP(hipMemcpyAsync(h_ftot, d_ftot.p, n_tot * sizeof(double), hipMemcpyDeviceToHost, s));
-            PHM_HIP(hipMemcpyAsync(h_fhap, d_fhap.p, n_i32 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        }
-        if (count_used && n_pairs > 0) PHM_HIP(hipMemcpyAsync(h_used, d_used.p, (size_t) n_pairs, hipMemcpyDeviceToHost, s));
-    }
-    PHM_HIP(hipStreamSynchronize(s));
-    float filtered_ms = 0.f; /* (read before anything is handed over: an error leaves profiles_out / filtered_out zeroed) */
-    if (back_half && filtered_stats) PHM_HIP(hipEventElapsedTime(&filtered_ms, ev.e[5], ev.e[6]));
+    return back.launch(*this);
+}
 
-    /* ---- back to the caller's reads */
+/* the downloads queued behind their kernels have landed once the stream has drained */
+int ScRun::download() {
+    PHM_HIP(hipStreamSynchronize(s));
+    /* (read before anything is handed over: an error leaves profiles_out / filtered_out zeroed) */
+    if (back.on && filtered_stats) PHM_HIP(hipEventElapsedTime(&back.ms, ev[EV_BACK_BEGIN], ev[EV_BACK_END]));
+    return MRP_OK;
+}
+
+/* back to the caller's reads; the results are the caller's from the last line on */
+int ScRun::hand_over(mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out) {
     for (int64_t c = 0; c < n_chunks; c++) {
         const ScLayout &Lc = lay[(size_t) c];
         mrp_phase_result *g = res[(size_t) c];
@@ -2268,81 +2285,174 @@ int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_subst
         for (int64_t c = 0; c < n_chunks; c++) {
             const ScLayout &Lc = lay[(size_t) c];
             mrp_profile_out &P = profiles_out[c];
-            auto dup = [](const void *src, size_t bytes) { void *p = malloc(bytes ? bytes : 1); if (p && bytes) memcpy(p, src, bytes); return p; };
             P.n_seqs = (int64_t) Lc.seqs.size();
             P.pool_bytes = Lc.pool_bytes;
-            P.seqs = (mrp_read *) dup(Lc.seqs.data(), sizeof(mrp_read) * Lc.seqs.size());
-            P.read_of_seq = (int32_t *) dup(Lc.read_of_seq.data(), sizeof(int32_t) * Lc.read_of_seq.size());
-            P.pool = (uint8_t *) dup((const uint8_t *) h_pool.p + dpool_base[(size_t) c], (size_t) Lc.pool_bytes);
-            P.allele_number = (uint32_t *) dup(Lc.an.data(), sizeof(uint32_t) * Lc.an.size());
-            P.substitution = (uint16_t *) dup(Lc.sub.data(), sizeof(uint16_t) * Lc.sub.size());
-            P.prior = (uint16_t *) dup(Lc.prior.data(), sizeof(uint16_t) * Lc.prior.size());
+            P.seqs = (mrp_read *) sc_dup(Lc.seqs.data(), sizeof(mrp_read) * Lc.seqs.size());
+            P.read_of_seq = (int32_t *) sc_dup(Lc.read_of_seq.data(), sizeof(int32_t) * Lc.read_of_seq.size());
+            P.pool = (uint8_t *) sc_dup((const uint8_t *) h_pool.p + dpool_base[(size_t) c], (size_t) Lc.pool_bytes);
+            P.allele_number = (uint32_t *) sc_dup(Lc.an.data(), sizeof(uint32_t) * Lc.an.size());
+            P.substitution = (uint16_t *) sc_dup(Lc.sub.data(), sizeof(uint16_t) * Lc.sub.size());
+            P.prior = (uint16_t *) sc_dup(Lc.prior.data(), sizeof(uint16_t) * Lc.prior.size());
             if (!P.seqs || !P.read_of_seq || !P.pool || !P.allele_number || !P.substitution || !P.prior) {
-                for (int64_t q = 0; q <= c; q++) {
-                    mrp_profile_out &X = profiles_out[q];
-                    free(X.seqs); free(X.read_of_seq); free(X.pool); free(X.allele_number); free(X.substitution); free(X.prior);
-                    memset(&X, 0, sizeof(X));
-                }
+                for (int64_t q = 0; q <= c; q++) mrp_profile_out_clear(&profiles_out[q]);
                 return fail(MRP_ERR_NOMEM, "mrp_phase_string_chunks: out of host memory");
             }
         }
-    if (back_half) {
-        const double *h_h1 = h_ftot, *h_h2 = h_ftot + n_freads, *h_cis = h_ftot + 2 * n_freads, *h_trans = h_cis + n_fvars;
-        bool ok = true;
-        for (int64_t c = 0; c < n_chunks && ok; c++) {
-            mrp_filtered_out &O = filtered_out[c];
-            const int64_t rb = Q.read_base[(size_t) c], nr = Q.read_base[(size_t) c + 1] - rb, vb = Q.var_base[(size_t) c], nv = Q.var_base[(size_t) c + 1] - vb;
-            auto dup = [](const void *src, size_t bytes) { void *p = malloc(bytes ? bytes : 1); if (p && bytes) memcpy(p, src, bytes); return p; };
-            O.n_reads = nr;
-            O.n_variants = nv;
-            O.read_hap = (int32_t *) dup(h_fhap + rb, sizeof(int32_t) * (size_t) nr);
-            O.h1 = (double *) dup(h_h1 + rb, sizeof(double) * (size_t) nr);
-            O.h2 = (double *) dup(h_h2 + rb, sizeof(double) * (size_t) nr);
-            O.variant_state = (int32_t *) dup(h_fhap + n_freads + vb, sizeof(int32_t) * (size_t) nv);
-            O.cis = (double *) dup(h_cis + vb, sizeof(double) * (size_t) nv);
-            O.trans = (double *) dup(h_trans + vb, sizeof(double) * (size_t) nv);
-            ok = O.read_hap && O.h1 && O.h2 && O.variant_state && O.cis && O.trans;
-        }
-        if (!ok) {
-            for (int64_t c = 0; c < n_chunks; c++) {
-                mrp_filtered_out &O = filtered_out[c];
-                free(O.read_hap); free(O.h1); free(O.h2); free(O.variant_state); free(O.cis); free(O.trans);
-                memset(&O, 0, sizeof(O));
-                if (profiles_out) {
-                    mrp_profile_out &X = profiles_out[c];
-                    free(X.seqs); free(X.read_of_seq); free(X.pool); free(X.allele_number); free(X.substitution); free(X.prior);
-                    memset(&X, 0, sizeof(X));
-                }
-            }
-            return fail(MRP_ERR_NOMEM, "mrp_phase_string_chunks_with_filtered: out of host memory");
-        }
-        if (filtered_stats) {
-            filtered_stats->filtered_ms += filtered_ms;
-            filtered_stats->pairs_scored += n_pairs;
-            filtered_stats->pairs_speculative += n_pairs - Q.n_primary_pairs;
-            for (int64_t p = Q.n_primary_pairs; p < n_pairs; p++) filtered_stats->pairs_read_by_results += h_used[p] ? 1 : 0;
-        }
-    }
+    const int rc = back.hand_over(*this, profiles_out);
+    if (rc != MRP_OK) return rc;
     if (stats) {
         float ms = 0.f;
-        if (n_pairs > 0) { PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ev.e[0])); stats->pairhmm.kernel_ms = ms; stats->pairhmm.cells = L.cells; }
-        PHM_HIP(hipEventElapsedTime(&ms, ev.e[1], ev.e[2]));
+        if (n_pairs > 0) { PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ev[EV_PAIRS_END])); stats->pairhmm.kernel_ms = ms; stats->pairhmm.cells = F->L.cells; }
+        PHM_HIP(hipEventElapsedTime(&ms, ev[EV_BYTES_BEGIN], ev[EV_BYTES_END]));
         stats->profile_ms = ms;
-        PHM_HIP(hipEventElapsedTime(&ms, ev.e[4], ctx->ev[1]));
+        PHM_HIP(hipEventElapsedTime(&ms, ev[EV_TAGS_BEGIN], ctx->ev[1]));
         stats->assign_ms = ms;
     }
     for (int64_t c = 0; c < n_chunks; c++) { out[c] = res[(size_t) c]; res[(size_t) c] = nullptr; }
-    L.release();
-    d_items.release(); d_pool.release(); d_aoff.release(); d_haps.release(); d_hitems.release(); d_hap.release(); d_phred.release();
-    d_fent.release(); d_fsites.release(); d_fchunks.release(); d_cbase.release(); d_pidx.release(); d_cand.release(); d_read_seq.release(); d_fhap.release();
-    d_cand_first.release(); d_rec.release(); d_ftot.release(); d_used.release();
-    for (mrp_chunk *&ch : dch) { delete ch; ch = nullptr; }
-    ctx->pool.reclaim();
-    if (stats) {
-        stats->total_ms = F->front_ms + (now_ms() - t_begin);
-        stats->host_ms = stats->total_ms - (t_phase1 - t_phase0);
+    return MRP_OK;
+}
+
+/* the static tables; a read's tag is its sequence's (read_seq: -1 a primary read in no bubble, -2 a filtered read) */
+int ScRun::Back::upload_static(ScRun &R) {
+    if (!on) return MRP_OK;
+    hipStream_t s = R.s;
+    n_reads = Q.read_base[(size_t) R.n_chunks];
+    n_vars = Q.var_base[(size_t) R.n_chunks];
+    n_tot = 2 * (size_t) (n_reads + n_vars);
+    n_i32 = (size_t) (n_reads + n_vars);
+    read_seq.resize((size_t) n_reads);
+    for (int64_t c = 0; c < R.n_chunks; c++) {
+        const int64_t rb = Q.read_base[(size_t) c];
+        for (int64_t r = 0; r < R.chunks[c].n_reads; r++) {
+            const int32_t q = R.lay[(size_t) c].seq_of[(size_t) r];
+            read_seq[(size_t) (rb + r)] = q < 0 ? -1 : (int32_t) (R.seq_base[(size_t) c] + q);
+        }
+        for (int64_t r = 0; r < Q.rest[c].n_filtered; r++) read_seq[(size_t) (rb + R.chunks[c].n_reads + r)] = -2;
+    }
+    PHM_HIP(d_ent.upload(Q.entries, s));
+    PHM_HIP(d_sites.upload(Q.sites, s));
+    PHM_HIP(d_cbase.upload(Q.cbase, s));
+    PHM_HIP(d_pidx.upload(Q.pidx, s));
+    PHM_HIP(d_cand_first.upload(Q.cand_first, s));
+    PHM_HIP(d_cand.upload(Q.cand, s));
+    PHM_HIP(d_read_seq.upload(read_seq, s));
+    return MRP_OK;
+}
+
+/* what the phasing decided per chunk goes up; then every buffer of the results.  Totals: h1 | h2 of the reads, then cis | trans of
+ * the variants; decisions: the reads', then the variants'. */
+int ScRun::Back::alloc_results(ScRun &R) {
+    if (!on) return MRP_OK;
+    hipStream_t s = R.s;
+    fchunks.resize((size_t) R.n_chunks);
+    for (int64_t c = 0; c < R.n_chunks; c++)
+        fchunks[(size_t) c] = FsChunk{R.hap_base[(size_t) c], (int32_t) R.res[(size_t) c]->ref_start, (int32_t) R.res[(size_t) c]->length};
+    PHM_HIP(d_chunks.upload(fchunks, s));
+    PHM_HIP(d_rec.alloc(Q.entries.size()));
+    PHM_HIP(d_tot.alloc(n_tot));
+    PHM_HIP(d_hap.alloc(n_i32));
+    PHM_HIP(h_res.reserve(n_tot * sizeof(double) + n_i32 * sizeof(int32_t) + (count_used ? (size_t) R.n_pairs : 0) + 16));
+    h_tot = (double *) h_res.p;
+    h_hap = (int32_t *) (h_tot + n_tot);
+    h_used = (uint8_t *) (h_hap + n_i32);
+    if (count_used) {
+        PHM_HIP(d_used.alloc((size_t) R.n_pairs));
+        PHM_HIP(hipMemsetAsync(d_used.p, 0, (size_t) std::max<int64_t>(R.n_pairs, 1), s));
     }
     return MRP_OK;
+}
+
+int ScRun::Back::launch(ScRun &R) {
+    if (!on) return MRP_OK;
+    hipStream_t s = R.s;
+    const int64_t n_sites = (int64_t) Q.sites.size();
+    PHM_HIP(hipEventRecord(R.ev[EV_BACK_BEGIN], s));
+    if (n_sites > 0) {
+        hipLaunchKernelGGL(sc_filtered_sites_kernel, dim3((unsigned) n_sites), dim3(64), 0, s, d_sites.p, d_ent.p, d_cbase.p, d_pidx.p, d_read_seq.p,
+                           R.d_hap.p, d_chunks.p, R.d_haps.p, d_rec.p, count_used ? d_used.p : nullptr);
+        PHM_HIP(hipGetLastError());
+    }
+    double *d_h1 = d_tot.p, *d_h2 = d_tot.p + n_reads, *d_cis = d_tot.p + 2 * n_reads, *d_trans = d_cis + n_vars;
+    if (n_reads > 0) {
+        hipLaunchKernelGGL(fs_partition_kernel, dim3((unsigned) ((n_reads + 255) / 256)), dim3(256), 0, s, d_cand_first.p, d_cand.p, d_rec.p, R.D.d_out.p,
+                           d_read_seq.p, R.d_hap.p, n_reads, d_hap.p, d_h1, d_h2);
+        PHM_HIP(hipGetLastError());
+    }
+    if (n_vars > 0) {
+        hipLaunchKernelGGL(fs_phase_kernel, dim3((unsigned) ((n_vars + 255) / 256)), dim3(256), 0, s, d_sites.p + Q.n_bsites, d_rec.p, R.D.d_out.p, n_vars,
+                           d_hap.p + n_reads, d_cis, d_trans);
+        PHM_HIP(hipGetLastError());
+    }
+    PHM_HIP(hipEventRecord(R.ev[EV_BACK_END], s));
+    if (n_tot > 0) {
+        PHM_HIP(hipMemcpyAsync(h_tot, d_tot.p, n_tot * sizeof(double), hipMemcpyDeviceToHost, s));
+        PHM_HIP(hipMemcpyAsync(h_hap, d_hap.p, n_i32 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    if (count_used && R.n_pairs > 0) PHM_HIP(hipMemcpyAsync(h_used, d_used.p, (size_t) R.n_pairs, hipMemcpyDeviceToHost, s));
+    return MRP_OK;
+}
+
+int ScRun::Back::hand_over(ScRun &R, mrp_profile_out *profiles_out) {
+    if (!on) return MRP_OK;
+    const double *h_h1 = h_tot, *h_h2 = h_tot + n_reads, *h_cis = h_tot + 2 * n_reads, *h_trans = h_cis + n_vars;
+    bool ok = true;
+    for (int64_t c = 0; c < R.n_chunks && ok; c++) {
+        mrp_filtered_out &O = out[c];
+        const int64_t rb = Q.read_base[(size_t) c], nr = Q.read_base[(size_t) c + 1] - rb, vb = Q.var_base[(size_t) c], nv = Q.var_base[(size_t) c + 1] - vb;
+        O.n_reads = nr;
+        O.n_variants = nv;
+        O.read_hap = (int32_t *) sc_dup(h_hap + rb, sizeof(int32_t) * (size_t) nr);
+        O.h1 = (double *) sc_dup(h_h1 + rb, sizeof(double) * (size_t) nr);
+        O.h2 = (double *) sc_dup(h_h2 + rb, sizeof(double) * (size_t) nr);
+        O.variant_state = (int32_t *) sc_dup(h_hap + n_reads + vb, sizeof(int32_t) * (size_t) nv);
+        O.cis = (double *) sc_dup(h_cis + vb, sizeof(double) * (size_t) nv);
+        O.trans = (double *) sc_dup(h_trans + vb, sizeof(double) * (size_t) nv);
+        ok = O.read_hap && O.h1 && O.h2 && O.variant_state && O.cis && O.trans;
+    }
+    if (!ok) {
+        for (int64_t c = 0; c < R.n_chunks; c++) {
+            mrp_filtered_out_clear(&out[c]);
+            if (profiles_out) mrp_profile_out_clear(&profiles_out[c]);
+        }
+        return fail(MRP_ERR_NOMEM, "mrp_phase_string_chunks_with_filtered: out of host memory");
+    }
+    if (R.filtered_stats) {
+        mrp_string_filtered_stats &T = *R.filtered_stats;
+        T.filtered_ms += ms;
+        T.pairs_scored += R.n_pairs;
+        T.pairs_speculative += R.n_pairs - Q.n_primary_pairs;
+        for (int64_t p = Q.n_primary_pairs; p < R.n_pairs; p++) T.pairs_read_by_results += h_used[p] ? 1 : 0;
+    }
+    return MRP_OK;
+}
+
+}  // namespace
+
+int mrp_string_front_run(mrp_context *ctx, mrp_string_front *F, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                         mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                         mrp_string_chunks_stats *stats, mrp_filtered_out *filtered_out, mrp_string_filtered_stats *filtered_stats) {
+    const double t_begin = now_ms();
+    int rc;
+    double phase_ms;
+    {
+        ScRun R(ctx, F, stats, filtered_out, filtered_stats);
+        rc = R.begin();
+        if (rc == MRP_OK) rc = R.enqueue_pairhmm();
+        if (rc == MRP_OK) rc = R.layout_and_items(het_substitution_probability);
+        if (rc == MRP_OK) rc = R.profile_bytes();
+        if (rc == MRP_OK) rc = R.chunks_and_phase(params);
+        if (rc == MRP_OK) rc = R.hp_tags(min_phred);
+        if (rc == MRP_OK) rc = R.download();
+        if (rc == MRP_OK) rc = R.hand_over(out, hap_out, phred_out, profiles_out);
+        phase_ms = R.phase_ms;
+    }
+    /* the stream has drained and every buffer of the run is back in the pool (after a refused run as well) */
+    ctx->pool.reclaim();
+    if (rc == MRP_OK && stats) { /* the whole call, its teardown included */
+        stats->total_ms = F->front_ms + (now_ms() - t_begin);
+        stats->host_ms = stats->total_ms - phase_ms;
+    }
+    return rc;
 }
 
 extern "C" {

@@ -514,11 +514,6 @@ int mrp_phase_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64
 
 }  /* extern "C" */
 
-static void free_filtered_out(mrp_filtered_out &O) {
-    mrp_free(O.read_hap); mrp_free(O.h1); mrp_free(O.h2); mrp_free(O.variant_state); mrp_free(O.cis); mrp_free(O.trans);
-    memset(&O, 0, sizeof(O));
-}
-
 /* mrp_queue_phase_string_chunks (rest == NULL) and mrp_queue_phase_string_chunks_with_filtered: the rest travels with its chunk */
 static int queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest,
                                      const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
@@ -638,12 +633,8 @@ static int queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_s
         for (int64_t i = 0; i < n_chunks; i++) {
             mrp_phase_result_destroy(out[i]);
             out[i] = nullptr;
-            if (profiles_out) {
-                mrp_profile_out &P = profiles_out[i];
-                mrp_free(P.seqs); mrp_free(P.read_of_seq); mrp_free(P.pool); mrp_free(P.allele_number); mrp_free(P.substitution); mrp_free(P.prior);
-                memset(&P, 0, sizeof(P));
-            }
-            if (rest) free_filtered_out(filtered_out[i]);
+            if (profiles_out) mrp_profile_out_clear(&profiles_out[i]);
+            if (rest) mrp_filtered_out_clear(&filtered_out[i]);
         }
         return call.error(rc);
     }

@@ -90,6 +90,15 @@ def filtered_chunks(n=26):
     return chunks, rests
 
 
+def no_pair_chunks():
+    """a chunk of 3 reads and no bubble, a chunk of 2 bubbles without a substring: no pair, no profile sequence in the whole call"""
+    rng = np.random.default_rng(12)
+    lonely = synth.StringChunk(bubbles=[], read_names=["a0", "a1", "a2"], read_forward_strand=np.array([1, 0, 1], np.uint8), hap=np.zeros(3, int), truth=[])
+    bubbles = [([synth.random_sequence(rng, 25), synth.random_sequence(rng, 25)], [], []) for _ in range(2)]
+    bare = synth.StringChunk(bubbles=bubbles, read_names=["b0", "b1"], read_forward_strand=np.array([1, 0], np.uint8), hap=np.zeros(2, int), truth=[0, 0])
+    return [lonely, bare]
+
+
 def chain(ctx, chunks, rests, f, r, p, min_phred=MIN_PHRED, expansion=4, sv_threshold=512):
     """The yardstick.  Returns (front: phase_string_chunks' list, back: per chunk dict(read_hap, h1, h2, variant_state, cis, trans,
     psites, tagged) -- psites the partition's sites, for the checks on the inputs)."""

@@ -1,6 +1,8 @@
 """GPU parity of the filtered-read haplotagging and filtered-variant phasing (mrp_partition_reads_by_haplotype,
 mrp_phase_variants_from_tagged_reads) against tests/haptag_oracle.py: decisions and states identical, totals within
 1e-9 * max(1, |oracle|) (device log / exp are not glibc's; the pair-HMM values themselves are bit-identical)."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -173,6 +175,48 @@ def test_phase_variants_duplicates_across_strands(gpu_ctx):
     assert (cis0 == cis).all() and (trans0 == trans).all()
     _, cis1, _, _ = capi.phase_variants_from_tagged_reads(gpu_ctx, f, r, variants, 4, [True, True, True, False], read_hap)
     assert (cis1 != cis).sum() > len(variants) // 2
+
+
+def raw_call(fn, ctx, f, r, sites, strands, read_hap, n_out):
+    """the C entry with its outputs pre-filled, so that a result the call did not write shows: (decision, total a, total b, stats)"""
+    S, keep = capi._haptag_sites(sites)
+    sd = np.ascontiguousarray(strands, dtype=np.uint8)
+    dec, a, b = np.full(n_out, 99, np.int32), np.full(n_out, 9.0), np.full(n_out, 9.0)
+    st = capi.PairHmmStats()
+    if read_hap is None:
+        rc = fn(ctx.h, C.byref(f), C.byref(r), C.byref(S), sd.size, sd.ctypes.data, 4, dec.ctypes.data, a.ctypes.data, b.ctypes.data, C.byref(st))
+    else:
+        rh = np.ascontiguousarray(read_hap, dtype=np.int32)
+        rc = fn(ctx.h, C.byref(f), C.byref(r), C.byref(S), sd.size, sd.ctypes.data, rh.ctypes.data, 4, 512, dec.ctypes.data, a.ctypes.data, b.ctypes.data,
+                C.byref(st))
+    capi._check(rc)
+    return dec, a, b, st
+
+
+def test_partition_without_an_active_site(gpu_ctx):
+    """the one site compares an allele with itself: no pair is scored, the reduction runs over nothing"""
+    rng = np.random.default_rng(3)
+    f, r, of, orv = models()
+    alleles = snp_alleles(rng)
+    sites = [(alleles, (1, 1), [(0, alleles[1].copy()), (1, alleles[0].copy())])]
+    rhap, rh1, rh2 = ho.partition_filtered_reads(of, orv, sites, 2, [True, False])
+    assert list(rhap) == [0, 0] and list(rh1) == [0.0, 0.0] and list(rh2) == [0.0, 0.0]
+    hap, h1, h2, st = raw_call(capi.load().mrp_partition_reads_by_haplotype, gpu_ctx, f, r, sites, [1, 0], None, 2)
+    assert st.pairs_lane + st.pairs_wave == 0 and st.cells == 0
+    assert hap.tolist() == [0, 0] and h1.tolist() == [0.0, 0.0] and h2.tolist() == [0.0, 0.0]
+
+
+def test_phase_variants_without_a_tagged_entry(gpu_ctx):
+    """a heterozygous variant whose only entry is an untagged read: visited, but nothing is scored -- a tie of two empty sums"""
+    rng = np.random.default_rng(4)
+    f, r, of, orv = models()
+    alleles = snp_alleles(rng)
+    variants = [(alleles, (0, 1), [(0, alleles[1].copy())])]
+    rstate, rcis, rtrans = ho.phase_filtered_variants(of, orv, variants, 1, [True], [0])
+    assert list(rstate) == [ho.TIE] and list(rcis) == [0.0] and list(rtrans) == [0.0]
+    state, cis, trans, st = raw_call(capi.load().mrp_phase_variants_from_tagged_reads, gpu_ctx, f, r, variants, [1], [0], 1)
+    assert st.pairs_lane + st.pairs_wave == 0 and st.cells == 0
+    assert state.tolist() == [ho.TIE] and cis.tolist() == [0.0] and trans.tolist() == [0.0]
 
 
 def test_end_to_end_chunk_loop(gpu_ctx, orc):

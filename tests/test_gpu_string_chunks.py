@@ -11,6 +11,7 @@ import pytest
 
 from margin_amd import capi, synth
 from oracle import pairhmm as ph
+from tests import string_filtered_cases as sf
 from tests.test_pairhmm import omodel
 
 pytestmark = pytest.mark.gpu
@@ -84,6 +85,25 @@ def test_mixed_chunks_against_the_chain(gpu_ctx):
     assert (np.concatenate([g["hap"] for g in got]) == -1).sum() >= 10
     tagged = np.concatenate([g["hap"] for g in got])
     assert ((tagged == 1) | (tagged == 2)).sum() > 0.8 * len(tagged)
+
+
+def test_a_call_without_pairs(gpu_ctx, monkeypatch):
+    """the pair-HMM launch, the profile-byte kernel and the HP kernel are all skipped: the call still equals the chain"""
+    # the chain helper hands NULL for an empty array, which mrp_allele_read_supports refuses even when no bubble has a substring:
+    # give it the empty read arrays a caller in C would pass (arguments 10-12: read_off, read_len, read_forward_strand)
+    L = capi.load()
+    supports, nothing = L.mrp_allele_read_supports, np.zeros(1, np.int64)
+    monkeypatch.setattr(L, "mrp_allele_read_supports",
+                        lambda *a: supports(*[nothing.ctypes.data if x is None and 10 <= i <= 12 else x for i, x in enumerate(a)]))
+    f, r = models()
+    chunks = sf.no_pair_chunks()
+    p = params()
+    got, st = capi.phase_string_chunks(gpu_ctx, chunks, f, r, p, min_phred=3, profiles=True)
+    ref, _ = capi.phase_string_chunks_chain(gpu_ctx, chunks, f, r, p, min_phred=3)
+    assert st.pairhmm.pairs_lane + st.pairhmm.pairs_wave == 0 and st.pairhmm.cells == 0
+    assert all(len(g["profile"]["seqs"]) == 0 for g in got)
+    assert all(g["hap"].shape == (len(c.read_names),) and (g["hap"] == -1).all() and (g["phred"] == 0).all() for g, c in zip(got, chunks))
+    assert_same(got, ref, chunks)
 
 
 def test_one_chunk_against_the_oracles(gpu_ctx, orc):

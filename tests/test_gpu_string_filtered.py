@@ -158,6 +158,29 @@ def test_a_lane_error_leaves_the_outputs_zeroed_and_the_queue_usable(gpu_ctx, ca
         q.close()
 
 
+def test_a_call_without_pairs(gpu_ctx):
+    """no substring at any bubble and the one filtered variant homozygous: nothing is scored, the back half's kernels run over
+    records that are all dead -- the filtered read stays untagged, the variant is not visited, as in the chain"""
+    from margin_amd import synth
+    f, r = models()
+    p = params()
+    chunks = sf.no_pair_chunks()
+    rng = np.random.default_rng(13)
+    allele = synth.random_sequence(rng, 25)
+    filtered_read = len(chunks[1].read_names)  # the rest's only read, behind the chunk's primary ones
+    rest = dict(forward_strand=np.ones(1, np.uint8), fsubs=[[], []], variants=[([allele, allele[::-1].copy()], (1, 1), [(filtered_read, allele.copy())])])
+    rests = [None, rest]
+    got, st = capi.phase_string_chunks_with_filtered(gpu_ctx, chunks, rests, f, r, p, min_phred=sf.MIN_PHRED, profiles=True)
+    front, back = sf.chain(gpu_ctx, chunks, rests, f, r, p)
+    assert st.pairs_scored == 0 and st.pairs_speculative == 0 and st.pairs_read_by_results == 0
+    assert all((g["hap"] == -1).all() for g in got)
+    assert_identical(got, front, chunks)
+    sf.assert_back_identical(got, back)
+    o = got[1]["filtered"]
+    assert o["read_hap"].tolist() == [0, 0, 0] and (o["h1"] == 0).all() and (o["h2"] == 0).all()
+    assert o["variant_state"].tolist() == [ho.NOT_VISITED] and o["cis"].tolist() == [0.0] and o["trans"].tolist() == [0.0]
+
+
 def test_oversize_unanchored_pair_of_the_back_half_is_refused(gpu_ctx):
     """a primary substring and an allele beyond the diagonal limit, anchored by the front: with a rest the partition may align them
     unanchored, so the call refuses; with an empty rest it goes through"""
