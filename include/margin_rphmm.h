@@ -87,7 +87,8 @@ int mrp_context_set_phase_groups(mrp_context *ctx, int groups);
  * cleared when it fires): the next device allocation of at least 1 MB on the context's device is refused as out of memory, which
  * a resident call must survive by redoing itself in two halves.  Bit 3: the prune kernel's general chain (one entry per cell) instead
  * of the chain on complement pairs that includeInvertedPartitions with even column limits selects, for A/B parity.  Bit 4: one
- * array entry per cell on unit levels (the chain on complement pairs over per-cell arrays) instead of one per complement pair. */
+ * array entry per cell on unit levels (the chain on complement pairs over per-cell arrays) instead of one per complement pair.
+ * Bit 5: no merge level is launched deferred -- every launch waits for its totals, as the large levels' do. */
 int mrp_context_set_test_hooks(mrp_context *ctx, int hooks);
 /* size of the host worker pool (structure of the merge levels, descriptors, classification of alignment pairs): the
  * process-wide pool of contexts used directly, and EACH worker's own pool of a work queue (mrp_queue_*: one pool per device).

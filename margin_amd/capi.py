@@ -413,7 +413,7 @@ class Context:
 
     def set_test_hooks(self, hooks: int):
         """test suite only: bit 0 fault injection, bit 1 separate cross product / emission kernels, bit 2 one refused device
-        allocation, bit 3 general prune chain, bit 4 one array entry per cell on unit levels (include/margin_rphmm.h)"""
+        allocation, bit 3 general prune chain, bit 4 one array entry per cell on unit levels, bit 5 no level is launched deferred (include/margin_rphmm.h)"""
         _check(load().mrp_context_set_test_hooks(self.h, hooks))
 
     def close(self):

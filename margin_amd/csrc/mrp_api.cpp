@@ -158,10 +158,8 @@ void mrp_context_destroy(mrp_context *ctx) {
     ctx->siblings.clear();
     (void) hipSetDevice(ctx->device);
     mrp_engine_release_context_cache(ctx);
-    if (ctx->spare_batch) { mrp_batch_destroy(ctx->spare_batch); ctx->spare_batch = nullptr; }
     (void) hipDeviceSynchronize(); /* the auxiliary and copy streams too */
     ctx->pool.destroy();
-    if (ctx->pinned) (void) hipHostFree(ctx->pinned);
     for (auto &e : ctx->ev)
         if (e) (void) hipEventDestroy(e);
     if (ctx->fork) (void) hipEventDestroy(ctx->fork);
@@ -876,7 +874,7 @@ int mrp_context_set_phase_groups(mrp_context *ctx, int groups) {
 }
 int mrp_context_phase_groups(const mrp_context *ctx) { return ctx->phase_groups; }
 int mrp_context_set_test_hooks(mrp_context *ctx, int hooks) {
-    if (!ctx || hooks < 0 || hooks > 31) return fail(MRP_ERR_ARG, "mrp_context_set_test_hooks: bad arguments");
+    if (!ctx || hooks < 0 || hooks > 63) return fail(MRP_ERR_ARG, "mrp_context_set_test_hooks: bad arguments");
     if ((hooks & 4) && ctx->pool.device >= 0) DevPoolRegistry::get().inject_oom[ctx->pool.device].store(1);
     hooks &= ~4;
     ctx->test_hooks = hooks;

@@ -203,7 +203,11 @@ struct DevPool {
         std::lock_guard<std::mutex> lock(mu);
         pending.emplace_back(cls, p);
     }
-    void reclaim() { /* only after the context's streams were synchronized */
+    /* Only when nothing queued can still touch a pending block.  Either the context's streams were synchronized, or -- the resident
+     * engine's level_retire(complete = true), with later levels in flight -- every pending block belongs to a level whose `done`
+     * event has completed: a level's arrays are empty when it is staged and no array of a level in flight is ever allocated
+     * again, so a level in flight releases nothing. */
+    void reclaim() {
         std::lock_guard<std::mutex> lock(mu);
         for (auto &b : pending) {
             free_blocks.emplace(b.first, b.second);
@@ -237,12 +241,29 @@ inline void DevPoolRegistry::trim_device(int device, DevPool *but) {
         if (q != but && q->device == device) q->trim();
 }
 
+/* The device arrays of one owner (a batch, a level of the resident engine): an array declared with the group -- DevBuf<T> a{arrays}; --
+ * is bound to a pool and released with all the others, so a new array is one declaration.  The entries point at the owner's members:
+ * owners are heap objects that are never copied or moved. */
+struct DevBufGroup {
+    struct Member { void *buf; void (*release)(void *); void (*bind)(void *, DevPool *); };
+    std::vector<Member> members;
+    DevBufGroup() = default;
+    DevBufGroup(const DevBufGroup &) = delete;
+    DevBufGroup &operator=(const DevBufGroup &) = delete;
+    void bind(DevPool *pl) { for (Member &m : members) m.bind(m.buf, pl); }
+    void release() { for (Member &m : members) m.release(m.buf); }
+};
+
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
     DevPool *pool = nullptr; /* NULL: plain hipMalloc / hipFree */
     size_t cls = 0;
+    DevBuf() = default;
+    explicit DevBuf(DevBufGroup &g) {
+        g.members.push_back({this, [](void *b) { static_cast<DevBuf *>(b)->release(); }, [](void *b, DevPool *pl) { static_cast<DevBuf *>(b)->pool = pl; }});
+    }
     ~DevBuf() { release(); }
     void release() {
         if (p) {
@@ -338,26 +359,11 @@ struct mrp_context {
     int phase_groups = 0; /* concurrent batches of mrp_phase_reads_many (mrp_context_set_phase_groups); 0: chosen by batch size */
     std::vector<mrp_context *> siblings; /* further contexts on the same device (concurrent batches of mrp_phase_reads_many) */
     std::mutex sibling_mu;
-    /* the emptied batch object of the last resident engine on this context: its host arrays keep their capacity (and their
-     * mapped pages) from one mrp_phase_reads_many call to the next */
-    struct mrp_batch *spare_batch = nullptr;
-    /* and its level objects (page-locked staging blocks, events) with a second emptied batch: kept from call to call, allocating
+    /* the emptied batch objects of the last resident engine on this context (their host arrays keep their capacity and their mapped
+     * pages from one mrp_phase_reads_many call to the next) and its level objects (page-locked staging blocks, events): allocating
      * page-locked memory takes milliseconds and synchronizes the device (owned here, managed by mrp_engine.cpp) */
     std::vector<struct mrp_engine_level_state *> spare_levels;
     std::vector<struct mrp_batch *> spare_batches;
-    /* page-locked host staging for the small per-level results of the resident engine (grow-only) */
-    void *pinned = nullptr;
-    size_t pinned_bytes = 0;
-    hipError_t pinned_reserve(size_t bytes) {
-        if (bytes <= pinned_bytes) return hipSuccess;
-        if (pinned) (void) hipHostFree(pinned);
-        pinned = nullptr;
-        pinned_bytes = 0;
-        const size_t want = std::max<size_t>(bytes + bytes / 2, (size_t) 1 << 20);
-        hipError_t e = hipHostMalloc(&pinned, want, hipHostMallocDefault);
-        if (e == hipSuccess) pinned_bytes = want;
-        return e;
-    }
 };
 
 struct mrp_chunk {
@@ -448,7 +454,8 @@ struct mrp_batch {
     /* resident merge levels: launched between the byte packing and the recursion kernels, in place of the emission kernel
      * (cross product + emission in one pass, mrp_launch_cross_emit) */
     std::function<hipError_t(hipStream_t)> pre_sweep;
-    DevBuf<TileCol> d_tilecols;
+    DevBufGroup arrays; /* every device array of the batch */
+    DevBuf<TileCol> d_tilecols{arrays};
     bool need_wide = false;
     std::vector<JobOut> outs;
     int64_t n_merge = 0, n_slots = 0;
@@ -464,27 +471,24 @@ struct mrp_batch {
     static constexpr int EV_RING = 32;
     std::vector<std::array<hipEvent_t, 5>> ev_ring;
     int64_t n_launches = 0, stats_mark = 0; /* stats_mark: launches already reported by an earlier mrp_batch_stats */
-    DevBuf<DevHmm> d_hmms;
-    DevBuf<DevCol> d_cols;
-    DevBuf<DevChunk> d_chunks;
-    DevBuf<int64_t> d_read_byte_off;
-    DevBuf<uint64_t> d_partition, d_planes;
-    DevBuf<SweepCol> d_scols;
-    DevBuf<PlaneCol> d_pcols;
-    DevBuf<uint32_t> d_next, d_prev, d_np, d_slot_total, d_slot_bytes, d_cost;
-    DevBuf<double> d_f, d_b, d_mf, d_mb, d_total, d_hmm_fb;
-    DevBuf<int32_t> d_f32, d_b32, d_mf32, d_mb32;
-    DevBuf<int32_t> d_order_wide, d_order_mid, d_order_narrow, d_order_f64, d_order_lse, d_order_lse_big, d_pack_list, d_plane_list;
-    DevBuf<EmitTile> d_tiles;
+    DevBuf<DevHmm> d_hmms{arrays};
+    DevBuf<DevCol> d_cols{arrays};
+    DevBuf<DevChunk> d_chunks{arrays};
+    DevBuf<int64_t> d_read_byte_off{arrays};
+    DevBuf<uint64_t> d_partition{arrays}, d_planes{arrays};
+    DevBuf<SweepCol> d_scols{arrays};
+    DevBuf<PlaneCol> d_pcols{arrays};
+    DevBuf<uint32_t> d_next{arrays}, d_prev{arrays}, d_np{arrays}, d_slot_total{arrays}, d_slot_bytes{arrays}, d_cost{arrays};
+    DevBuf<double> d_f{arrays}, d_b{arrays}, d_mf{arrays}, d_mb{arrays}, d_total{arrays}, d_hmm_fb{arrays};
+    DevBuf<int32_t> d_f32{arrays}, d_b32{arrays}, d_mf32{arrays}, d_mb32{arrays};
+    DevBuf<int32_t> d_order_wide{arrays}, d_order_mid{arrays}, d_order_narrow{arrays}, d_order_f64{arrays}, d_order_lse{arrays}, d_order_lse_big{arrays},
+        d_pack_list{arrays}, d_plane_list{arrays};
+    DevBuf<EmitTile> d_tiles{arrays};
     MrpBatchDev dev{};
     /* back to the empty state, keeping the capacity of the host arrays (the resident engine reuses one batch object for
      * all levels of a run: their descriptor arrays are tens of megabytes).  Only after the stream was synchronized. */
     void recycle() {
-        d_hmms.release(); d_cols.release(); d_chunks.release(); d_read_byte_off.release(); d_partition.release(); d_planes.release();
-        d_scols.release(); d_pcols.release(); d_next.release(); d_prev.release(); d_np.release(); d_slot_total.release();
-        d_slot_bytes.release(); d_cost.release(); d_f.release(); d_b.release(); d_mf.release(); d_mb.release(); d_total.release();
-        d_hmm_fb.release(); d_f32.release(); d_b32.release(); d_mf32.release(); d_mb32.release(); d_order_wide.release();
-        d_order_mid.release(); d_order_narrow.release(); d_order_f64.release(); d_order_lse.release(); d_order_lse_big.release(); d_tiles.release(); d_pack_list.release(); d_plane_list.release(); d_tilecols.release();
+        arrays.release();
         chunks.clear(); hmms.clear(); cols.clear(); read_byte_off.clear(); partition.clear(); scols.clear(); pcols.clear();
         cell_next.clear(); cell_prev.clear(); cell_np.clear(); tiles.clear(); tilecols.clear(); outs.clear();
         order_wide.clear(); order_mid.clear(); order_narrow.clear(); order_f64.clear(); order_lse.clear(); order_lse_big.clear(); order_gen.clear();
@@ -495,13 +499,7 @@ struct mrp_batch {
         n_launches = 0; stats_mark = 0; /* (the events stay: every launch of the emptied batch has been waited for) */
         dev = MrpBatchDev{};
     }
-    void bind_pool(DevPool *pl) {
-        d_hmms.pool = pl; d_cols.pool = pl; d_chunks.pool = pl; d_read_byte_off.pool = pl; d_partition.pool = pl; d_planes.pool = pl;
-        d_scols.pool = pl; d_pcols.pool = pl; d_next.pool = pl; d_prev.pool = pl; d_np.pool = pl; d_slot_total.pool = pl;
-        d_slot_bytes.pool = pl; d_cost.pool = pl; d_f.pool = pl; d_b.pool = pl; d_mf.pool = pl; d_mb.pool = pl; d_total.pool = pl;
-        d_hmm_fb.pool = pl; d_f32.pool = pl; d_b32.pool = pl; d_mf32.pool = pl; d_mb32.pool = pl; d_order_wide.pool = pl;
-        d_order_mid.pool = pl; d_order_narrow.pool = pl; d_order_f64.pool = pl; d_order_lse.pool = pl; d_order_lse_big.pool = pl; d_tiles.pool = pl; d_pack_list.pool = pl; d_plane_list.pool = pl; d_tilecols.pool = pl;
-    }
+    void bind_pool(DevPool *pl) { arrays.bind(pl); }
 };
 
 

@@ -95,7 +95,7 @@ typedef struct mrp_xhmm {
     /* results, known as soon as the level is staged: where the pruned hmm will be */
     int32_t seg;
     int64_t col0;
-    /* mrp_engine_final instead: n_cells[k] = index of the traced-back cell of column k, path_part[k] its
+    /* mrp_engine_final_stage instead: n_cells[k] = index of the traced-back cell of column k, path_part[k] its
      * partition (host, caller-allocated), and the totals of the final sweep */
     int32_t *n_cells;
     uint64_t *path_part;
@@ -153,14 +153,9 @@ int mrp_engine_level_end(mrp_engine *e);
  * they end in order, by a later launch or by mrp_engine_level_end, which ends them all).  The number of levels ended so far: the k-th
  * level launched has ended -- its x[i].err are set, x may go -- once this is at least k. */
 int64_t mrp_engine_levels_ended(const mrp_engine *e);
-/* stage + launch */
-int mrp_engine_level_begin(mrp_engine *e, int64_t n, mrp_xhmm *x);
-/* stage + launch + end */
-int mrp_engine_level(mrp_engine *e, int64_t n, mrp_xhmm *x);
 /* the last step of bubbleGraph_phaseBubbleGraph (bubbleGraph.c:2745-2755) for n fused hmms: cross product with
  * nothing (= stRPHmm_fuse with its gap columns), forward/backward with the flags given, stRPHmm_forwardTraceBack */
 int mrp_engine_final_stage(mrp_engine *e, int64_t n, mrp_xhmm *x);
-int mrp_engine_final(mrp_engine *e, int64_t n, mrp_xhmm *x);
 /* device -> host copy of resident arrays (queued), and the wait for all queued copies */
 int mrp_engine_fetch(mrp_engine *e, void *dst, const void *src_dev, int64_t bytes);
 int mrp_engine_sync(mrp_engine *e);

@@ -437,16 +437,19 @@ def test_resident_pair_order_violation_sends_only_that_chunk_to_the_hashing_path
         d.close()
 
 
-def test_resident_merge_check_failure_sends_only_that_chunk_to_the_hashing_path(gpu_ctx, orc):
+@pytest.mark.parametrize("hooks", [1, 33], ids=["levels_in_flight_behind_it", "no_level_deferred"])
+def test_resident_merge_check_failure_sends_only_that_chunk_to_the_hashing_path(gpu_ctx, orc, hooks):
     """MRP_ENGINE_ERR_MERGE -- "a merge cell the kept cells lead to would itself be pruned" (hmm.c:1090-1100) -- cannot be
     produced by an input in max-plus mode (a merge cell's posterior is at least that of every cell leading to it, so
     whenever more than minPartitionsInAColumn cells are kept they and their merge cells all pass the threshold); the
     kernel checks it all the same.  The check's way out is exercised by fault injection (mrp_context_set_test_hooks bit 0: one
     hmm of the second level reports the error): that hmm's chunk, and only it, is redone on the hashing path; results are
-    the oracle's."""
+    the oracle's.  By default the levels behind the failing one are in flight when its flags arrive; with test hook bit 5 (no level
+    is launched deferred) the failing level has ended before the next is launched: both orders of "the chunk is discarded" against
+    "the next level runs"."""
     pd = _params()
     params = capi.Params.from_reference_names(pd)
-    gpu_ctx.set_test_hooks(1)
+    gpu_ctx.set_test_hooks(hooks)
     chunks = [synth.make_ont_chunk(seed=91 + i, region_bp=50_000, n_sites=100, coverage=20 + 4 * i) for i in range(4)]
     dchunks = [capi.DeviceChunk.from_chunk(gpu_ctx, c) for c in chunks]
     got, st = capi.phase_reads_many(gpu_ctx, dchunks, chunks, params)
@@ -618,12 +621,13 @@ def test_bench_shape_configs4_full_size_hifi_chunk_equals_the_oracle(gpu_ctx, or
     dchunk.close()
 
 
-@pytest.mark.parametrize("hooks", [8, 16], ids=["general_prune_chain", "pairs_chain_on_cell_arrays"])
+@pytest.mark.parametrize("hooks", [8, 16, 32], ids=["general_prune_chain", "pairs_chain_on_cell_arrays", "no_level_deferred"])
 def test_prune_variants_agree_with_the_default_path_and_the_oracle(orc, hooks):
     """The default resident path runs the prune chain on complement pairs over arrays that hold one entry per pair (MRP_XF_UNITS).
     Two variants stay in the product (odd column limits / plain mode take the first, the two-kernel cross product + emission
     path the second): the general chain with one entry per cell (test hook bit 3) and the pair chain over per-cell arrays
-    (test hook bit 4).  Both give the default path's results, which are the oracle's."""
+    (test hook bit 4).  Both give the default path's results, which are the oracle's.  So does the waiting launch of every merge level
+    (test hook bit 5: no level is deferred, as at sizes beyond the deferral bound; by default all levels of these chunks are)."""
     pd = _params()
     params = capi.Params.from_reference_names(pd)
     chunks = [synth.make_ont_chunk(seed=820 + s, region_bp=120_000 + 40_000 * s, n_sites=240 + 80 * s, coverage=28.0 + 4 * s) for s in range(3)]

@@ -1,0 +1,17 @@
+"""The host arithmetic of staging a resident level (margin_amd/csrc/mrp_level_order.h) without a device: tests/level_order_check.cpp,
+a stand-alone program built with the address and undefined-behaviour sanitizers.  It checks the order of a level's hmms and their
+launch classes on seeded random levels (n in {0, 1, 2, 63, 4 096, 4 097, 6 000}; few distinct column counts and bounds, so ties are
+common; bounds on both sides of every threshold; unit and cell levels) against a plain restatement, and the block carver's sizing
+pass against its pointer pass (64-byte aligned, inside the block, disjoint regions; a zero count takes nothing)."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_level_order_classes_and_block_carver(tmp_path):
+    exe = str(tmp_path / "level_order_check")
+    subprocess.check_call(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__",
+                           "-I/opt/rocm/include", "-o", exe, os.path.join(ROOT, "tests", "level_order_check.cpp")])
+    out = subprocess.check_output([exe], text=True)
+    assert out.strip() == "level order ok", out
