@@ -926,14 +926,10 @@ static int launch_size_batch(mrp_engine_level_state *L, int64_t cells, int64_t m
     ENG_TRY(b->d_slot_bytes.alloc((size_t) n_slots * 16));
     ENG_TRY(b->d_total.alloc((size_t) total_cols)); ENG_TRY(b->d_hmm_fb.alloc(2 * (size_t) n));
     MrpBatchDev &d = b->dev;
-    d = MrpBatchDev{};
-    d.hmms = b->d_hmms.p; d.cols = b->d_cols.p; d.chunks = b->d_chunks.p; d.read_byte_off = L->seg->rbo.p;
-    d.partition = b->d_partition.p; d.scols = b->d_scols.p; d.pcols = b->d_pcols.p;
+    d = b->view(); /* (the fp64 arrays, the wide transitions and the lists were never allocated: NULL) */
+    d.read_byte_off = L->seg->rbo.p;
     d.pack_list = nullptr; d.plane_list = nullptr; d.list_filter = 1; /* every column, filtered by PlaneCol.need_planes */
     d.n_pack_list = L->any_pack ? total_cols : 0; d.n_plane_list = L->any_planes ? total_cols : 0;
-    d.cell_np = b->d_np.p; d.planes = b->d_planes.p; d.slot_total = b->d_slot_total.p; d.slot_bytes = b->d_slot_bytes.p;
-    d.cell_cost = b->d_cost.p; d.cell_f32 = b->d_f32.p; d.cell_b32 = b->d_b32.p; d.merge_f32 = b->d_mf32.p; d.merge_b32 = b->d_mb32.p;
-    d.col_total = b->d_total.p; d.hmm_fb = b->d_hmm_fb.p;
     d.n_hmms = n; d.n_cols = total_cols; d.n_cells = cells; d.n_merge = merge; d.n_slots = n_slots;
     b->uploaded = true;
     b->outs.clear(); /* device-only */

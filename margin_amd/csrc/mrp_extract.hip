@@ -516,7 +516,7 @@ int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_al
         hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
         ~Events() { for (hipEvent_t x : e) if (x) (void) hipEventDestroy(x); }
     } ev;
-    struct Drain { hipStream_t s; ~Drain() { (void) hipStreamSynchronize(s); } } drain{s}; /* before the buffers go back to the pool */
+    Drain drain{s}; /* before the buffers go back to the pool */
     for (hipEvent_t &x : ev.e) EX_HIP(hipEventCreate(&x));
 
     EX_HIP(h_in.reserve(std::max<size_t>(in_bytes, 1)));

@@ -1,6 +1,6 @@
 /*
- * mrp_internal.h -- host-side objects behind the opaque handles of include/margin_rphmm.h, shared by
- * mrp_api.cpp (forward/backward seam) and mrp_engine.cpp (device-resident merge levels).
+ * mrp_internal.h -- host-side objects behind the opaque handles of include/margin_rphmm.h, shared by mrp_context.cpp,
+ * mrp_chunk.cpp, mrp_batch.cpp (forward/backward seam) and mrp_engine.cpp (device-resident merge levels).
  */
 #ifndef MRP_INTERNAL_H_
 #define MRP_INTERNAL_H_
@@ -21,13 +21,24 @@
 #include <new>
 #include <type_traits>
 #include <mutex>
+#include <thread>
 #include <utility>
 #include <vector>
 
 #include "../../include/margin_rphmm.h"
 #include "mrp_device.h"
+#include "mrp_host_pool.h"
 #include "mrp_kernels.h"
 #include "rphmm_host.h"
+
+#define HIP_TRY(expr)                                                                                          \
+    do {                                                                                                       \
+        hipError_t e_ = (expr);                                                                                \
+        if (e_ != hipSuccess) return mrp_set_error(MRP_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+/* Declared after the host staging vectors and scratch buffers of a function that queues work on s: whatever way the function
+ * is left, the stream is drained before they go. */
+struct Drain { hipStream_t s; ~Drain() { (void) hipStreamSynchronize(s); } };
 
 /* A kernel attribute (the opt-in to more than 64 KB of dynamic LDS) belongs to the function ON A DEVICE: set once per device,
  * by whichever context of that device launches first (the C-ABI lets one process hold contexts on several devices). */
@@ -375,10 +386,11 @@ struct mrp_chunk {
     std::vector<uint8_t> pool;
     const uint8_t *pool_host = nullptr; /* the profile bytes on the host: pool.data(), or the copy in the page-locked block of a work queue's batch */
     uint32_t max_sub = 0, max_prior = 0, max_alleles = 1;
-    DevBuf<uint32_t> d_allele_number, d_allele_offset, d_sub_offset;
-    DevBuf<int32_t> d_same_until;
-    DevBuf<uint16_t> d_sub, d_prior;
-    DevBuf<uint8_t> d_pool;
+    DevBufGroup arrays; /* mrp_chunk_create: the chunk's own device arrays (a chunk of a block has none) */
+    DevBuf<uint32_t> d_allele_number{arrays}, d_allele_offset{arrays}, d_sub_offset{arrays};
+    DevBuf<int32_t> d_same_until{arrays};
+    DevBuf<uint16_t> d_sub{arrays}, d_prior{arrays};
+    DevBuf<uint8_t> d_pool{arrays};
     DevChunk dev{};
     /* a chunk whose uploads were queued but not waited for (a work queue uploads its next batch beside the current one): the
      * event ends them.  Device work that reads the chunk waits for it on its stream (mrp_engine.cpp) or on the host
@@ -449,8 +461,7 @@ struct mrp_batch {
     HostVec<uint32_t> cell_next, cell_prev, cell_np;
     HostVec<EmitTile> tiles;
     int64_t n_fast_tiles = 0;
-    HostVec<TileCol> tilecols; /* resident batches: the tiles are written on the device from these */
-    int64_t n_tiles_dev = 0;   /* their number (tiles stays empty) */
+    int64_t n_tiles_dev = 0;   /* tiles on the device (a resident batch's are written there from d_tilecols: tiles stays empty) */
     /* resident merge levels: launched between the byte packing and the recursion kernels, in place of the emission kernel
      * (cross product + emission in one pass, mrp_launch_cross_emit) */
     std::function<hipError_t(hipStream_t)> pre_sweep;
@@ -490,7 +501,7 @@ struct mrp_batch {
     void recycle() {
         arrays.release();
         chunks.clear(); hmms.clear(); cols.clear(); read_byte_off.clear(); partition.clear(); scols.clear(); pcols.clear();
-        cell_next.clear(); cell_prev.clear(); cell_np.clear(); tiles.clear(); tilecols.clear(); outs.clear();
+        cell_next.clear(); cell_prev.clear(); cell_np.clear(); tiles.clear(); outs.clear();
         order_wide.clear(); order_mid.clear(); order_narrow.clear(); order_f64.clear(); order_lse.clear(); order_lse_big.clear(); order_gen.clear();
         n_fast_tiles = 0; n_tiles_dev = 0; need_wide = false; n_merge = 0; n_slots = 0; n_cells_total = 0; resident = false;
         stats = mrp_launch_stats{};
@@ -500,25 +511,28 @@ struct mrp_batch {
         dev = MrpBatchDev{};
     }
     void bind_pool(DevPool *pl) { arrays.bind(pl); }
+    /* The device view of the batch: every pointer from its DevBuf (NULL for an array that was never allocated or was released) and
+     * the counts the batch knows.  The resident engine overrides what is its own (launch_size_batch). */
+    MrpBatchDev view() const {
+        MrpBatchDev d{};
+        d.hmms = d_hmms.p; d.cols = d_cols.p; d.scols = d_scols.p; d.pcols = d_pcols.p; d.chunks = d_chunks.p; d.read_byte_off = d_read_byte_off.p;
+        d.pack_list = d_pack_list.p; d.plane_list = d_plane_list.p; d.n_pack_list = (int64_t) d_pack_list.n; d.n_plane_list = (int64_t) d_plane_list.n;
+        d.partition = d_partition.p; d.cell_np = d_np.p; d.cell_next = d_next.p; d.cell_prev = d_prev.p;
+        d.planes = d_planes.p; d.slot_total = d_slot_total.p; d.slot_bytes = d_slot_bytes.p; d.cell_cost = d_cost.p;
+        d.cell_f32 = d_f32.p; d.cell_b32 = d_b32.p; d.merge_f32 = d_mf32.p; d.merge_b32 = d_mb32.p;
+        d.cell_f = d_f.p; d.cell_b = d_b.p; d.merge_f = d_mf.p; d.merge_b = d_mb.p; d.col_total = d_total.p; d.hmm_fb = d_hmm_fb.p;
+        d.n_hmms = (int64_t) hmms.size(); d.n_cols = (int64_t) cols.size(); d.n_cells = n_cells_total; d.n_merge = n_merge; d.n_slots = n_slots;
+        return d;
+    }
 };
 
-
-/* appends one hmm to a batch.  resident = the cell arrays (partition, transitions) are produced on
- * the device (mrp_engine.cpp): only the column structure is taken from the job. */
-int mrp_batch_add_impl(mrp_batch *b, const mrp_hmm_job *job, bool resident, int64_t *cell0_out, int64_t *mcell0_out,
-                       int64_t *col0_out);
-
-
-#include <atomic>
-#include <thread>
-extern "C" void mrp_pool_run(int64_t n, int64_t grain, void (*fn)(int64_t, void *), void *arg);
 /* releases what mrp_engine.cpp parked in the context (mrp_context_destroy) */
 void mrp_engine_release_context_cache(mrp_context *ctx);
 /* groups > 1: chunk i belongs to group i % groups (the concurrent batches mrp_phase_reads_many will deal the chunks to); the block is
  * laid out and uploaded group by group, and a chunk is ready when its group's copy has ended -- the first batch's kernels need not wait
  * for the last batch's bytes */
-/* device_pools (optional): the profile bytes of chunk i are already on the device at device_pools[i] (with the tail slack
- * mrp_chunk_create gives a pool) and descs[i]->profile_pool is the caller's host copy of them; only the site tables are staged */
+/* device_pools (optional): the profile bytes of chunk i are already on the device at device_pools[i] (followed by
+ * MRP_POOL_TAIL_PAD bytes of the allocation) and descs[i]->profile_pool is the caller's host copy of them; only the site tables are staged */
 int mrp_chunk_block_create(mrp_context *ctx, int64_t n, const mrp_chunk_desc *const *descs, mrp_chunk **out, mrp_chunk_block *blk, int groups = 1,
                            const uint8_t *const *device_pools = nullptr);
 /* mrp_phase_string_chunks in three steps (mrp_pairhmm.hip), so that a work queue can check every chunk before its first lane
@@ -552,17 +566,7 @@ static inline void mrp_filtered_out_clear(mrp_filtered_out *O) {
     free(O->read_hap); free(O->h1); free(O->h2); free(O->variant_state); free(O->cis); free(O->trans);
     memset(O, 0, sizeof(*O));
 }
-int mrp_host_threads_setting(void); /* what mrp_set_host_threads() was given, 0 if it was never called */
-/* host worker pools (mrp_api.cpp) */
 extern "C" void mrp_batch_last_launch_ms(struct mrp_batch *b, float *pack, float *emission, float *recursion);
-struct mrp_host_pool;
-mrp_host_pool *mrp_host_pool_create(int threads);
-void mrp_host_pool_destroy(mrp_host_pool *p);
-template <class F>
-static inline void mrp_parallel_for(int64_t n, int64_t grain, F f) {
-    mrp_pool_run(n, grain, [](int64_t i, void *a) { (*static_cast<F *>(a))(i); }, &f);
-}
-
 
 /* development: MRP_DUP=<letters> launches the named kernel families of a resident level TWICE (they are idempotent) -- the slow-down of a
  * step is that family's marginal cost in situ: p packing, x cross product + emission, s recursion, r prune, c compaction, l layout,

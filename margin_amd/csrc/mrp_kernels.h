@@ -48,6 +48,9 @@ struct MrpBatchDev {
 /* usable dynamic LDS per workgroup for the sweep kernels, bytes */
 #define MRP_LDS_BUDGET (160 * 1024 - 1024)
 
+/* mrp_pack_kernel reads a read's profile bytes of a column one unaligned dword (four slots) at a time, so the last load of a run
+ * reaches up to three bytes past it: whoever lays out a profile pool keeps this many bytes behind it inside the allocation */
+#define MRP_POOL_TAIL_PAD 16
 hipError_t mrp_launch_planes(const MrpBatchDev &d, hipStream_t stream);
 /* MRP_EMIT_TILE cells per tile */
 #define MRP_EMIT_TILE 512

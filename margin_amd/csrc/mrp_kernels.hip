@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(256) mrp_planes_kernel(const PlaneCol *__restr
  * words, and the four byte sums travel through the 16-lane reduction two to a register.  A byte load per read and slot (round 1) made
  * a column of the first merge levels -- two to four reads over sixty slots -- sixty dependent trips to memory per lane: the kernel
  * waited 80 % of its cycles and a step paid 12 ms for it (marginal cost, MRP_DUP=p).  The last dword of a read's run may reach up to
- * three bytes past it: into the next read's bytes or the padding behind the pool (mrp_chunk_create / mrp_chunk_block_create). */
+ * three bytes past it: into the next read's bytes or the MRP_POOL_TAIL_PAD bytes every pool is followed by (mrp_kernels.h). */
 struct __attribute__((packed, aligned(1))) pack_u32 { uint32_t v; };
 __global__ void __launch_bounds__(256) mrp_pack_kernel(const PlaneCol *__restrict__ pcols, const int32_t *__restrict__ list,
                                                        int64_t n_list, const int64_t *__restrict__ read_byte_off,

@@ -1,6 +1,7 @@
 /*
  * mrp_level_order.h -- what staging a resident level (mrp_engine.cpp) decides by host arithmetic alone: the order of the level's
- * hmms, their launch classes, and the layout of its page-locked blocks.  No HIP call: tests/level_order_check.cpp runs it on the CPU.
+ * hmms, their launch classes, and the layout of its page-locked blocks; also the layout of a work queue's chunk block
+ * (mrp_chunk.cpp).  No HIP call: tests/level_order_check.cpp runs it on the CPU.
  */
 #ifndef MRP_LEVEL_ORDER_H_
 #define MRP_LEVEL_ORDER_H_
@@ -14,18 +15,35 @@
 #include "mrp_engine.h" /* MRP_MINI_MAX_UNITS */
 #include "rphmm_host.h" /* mrp_xhmm */
 
-/* Hands out consecutive 64-byte aligned regions of one block.  Run the same code twice: without a base, `used` is the size to
- * reserve; with the block's address, take() returns the regions. */
+/* Hands out consecutive aligned regions of one block (64 bytes unless told otherwise; a power of two).  Run the same code twice:
+ * without a base, `used` is the size to reserve; with the block's address, take() returns the regions. */
 struct BlockCarver {
     char *base;
-    size_t used = 0;
-    explicit BlockCarver(void *block = nullptr) : base(static_cast<char *>(block)) {}
+    size_t align, used = 0;
+    explicit BlockCarver(void *block = nullptr, size_t alignment = 64) : base(static_cast<char *>(block)), align(alignment) {}
     template <class T> T *take(size_t count) {
         T *p = base ? reinterpret_cast<T *>(base + used) : nullptr;
-        used += (count * sizeof(T) + 63) & ~(size_t) 63;
+        used += (count * sizeof(T) + align - 1) & ~(align - 1);
         return p;
     }
 };
+
+/* One chunk's share of the block that holds the chunks of a work queue's batch: the six site tables, then the profile bytes
+ * unless they are on the device already (with_pool = false: pool stays NULL and takes nothing).  Every slice starts on a
+ * multiple of MRP_CHUNK_BLOCK_ALIGN bytes.  The block is reserved MRP_CHUNK_BLOCK_SLACK bytes larger than the slices need, which
+ * covers the packing kernel's reach behind the last chunk's profile bytes (MRP_POOL_TAIL_PAD, mrp_kernels.h). */
+#define MRP_CHUNK_BLOCK_ALIGN 256
+#define MRP_CHUNK_BLOCK_SLACK 256
+static_assert(MRP_CHUNK_BLOCK_SLACK >= MRP_POOL_TAIL_PAD, "the chunk block ends too close behind its last profile pool");
+static inline size_t chunk_block_bytes(size_t carved) { return carved + MRP_CHUNK_BLOCK_SLACK; }
+struct ChunkSlices { uint32_t *allele_number, *allele_offset, *sub_offset; int32_t *same_until; uint16_t *sub, *prior; uint8_t *pool; };
+static inline ChunkSlices carve_chunk(BlockCarver &c, size_t n_sites, size_t n_alleles, size_t n_sub, size_t pool_bytes, bool with_pool) {
+    ChunkSlices s{};
+    s.allele_number = c.take<uint32_t>(n_sites); s.allele_offset = c.take<uint32_t>(n_sites + 1); s.sub_offset = c.take<uint32_t>(n_sites + 1);
+    s.same_until = c.take<int32_t>(n_sites); s.sub = c.take<uint16_t>(n_sub); s.prior = c.take<uint16_t>(n_alleles);
+    if (with_pool) s.pool = c.take<uint8_t>(pool_bytes);
+    return s;
+}
 
 struct LevelClass {
     std::vector<int32_t> order; /* indices into x */
@@ -67,6 +85,13 @@ static inline void level_sort(const mrp_xhmm *x, int64_t n, bool units, LevelOrd
     for (int64_t j = 0; j < n; j++) o.pos[(size_t) o.perm[(size_t) j]] = (int32_t) j;
 }
 
+/* The launch class of the recursion kernel for an hmm, by its largest column and largest merge column: the rule of the resident
+ * levels (level_classes, from the static bounds) and of the host-fed batch's int32 plan (mrp_batch_upload). */
+enum SweepClass { SWEEP_NARROW, SWEEP_MID, SWEEP_WIDE };
+static inline SweepClass sweep_class(int64_t max_cells, int64_t max_merge) {
+    return max_cells <= 256 ? SWEEP_NARROW : max_merge <= 4096 ? SWEEP_MID : SWEEP_WIDE;
+}
+
 /* the launch classes, from the static bounds; largest first inside a class.  Also the level's maxima and bound sums. */
 static inline void level_classes(const mrp_xhmm *x, int64_t n, bool units, LevelOrder &o) {
     o.wide.order.clear(); o.mid.order.clear(); o.narrow.order.clear();
@@ -79,7 +104,8 @@ static inline void level_classes(const mrp_xhmm *x, int64_t n, bool units, Level
         o.bound_cells += (q.bound_cells + 3) & ~3ll;
         o.bound_merge += q.bound_merge;
         if (level_is_mini(q, units)) continue; /* swept by the single-wave kernel */
-        LevelClass &c = q.bound_max_cells <= 256 ? o.narrow : q.bound_max_merge <= 4096 ? o.mid : o.wide;
+        const SweepClass k = sweep_class(q.bound_max_cells, q.bound_max_merge);
+        LevelClass &c = k == SWEEP_NARROW ? o.narrow : k == SWEEP_MID ? o.mid : o.wide;
         c.order.push_back((int32_t) i);
     }
     for (LevelClass *c : {&o.wide, &o.mid, &o.narrow}) {

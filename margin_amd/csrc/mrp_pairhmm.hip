@@ -2121,7 +2121,7 @@ int ScRun::layout_and_items(double het_substitution_probability) {
     aoff_base.assign((size_t) n_chunks + 1, 0);
     seq_base.assign((size_t) n_chunks + 1, 0);
     for (int64_t c = 0; c < n_chunks; c++) {
-        dpool_base[(size_t) c + 1] = (dpool_base[(size_t) c] + lay[(size_t) c].pool_bytes + 16 + 255) & ~(int64_t) 255;
+        dpool_base[(size_t) c + 1] = (dpool_base[(size_t) c] + lay[(size_t) c].pool_bytes + MRP_POOL_TAIL_PAD + 255) & ~(int64_t) 255;
         aoff_base[(size_t) c + 1] = aoff_base[(size_t) c] + chunks[c].n_bubbles + 1;
         seq_base[(size_t) c + 1] = seq_base[(size_t) c] + (int64_t) lay[(size_t) c].seqs.size();
     }

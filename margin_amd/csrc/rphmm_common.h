@@ -28,7 +28,7 @@ static inline double now_ms(void) {
 
 /* host worker threads: the structural code is independent per chunk / per merge node */
 typedef void (*par_fn)(int64_t i, void *arg);
-static inline void parallel_for(int64_t n, par_fn fn, void *arg) { mrp_pool_run(n, 1, fn, arg); } /* persistent pool, mrp_api.cpp */
+static inline void parallel_for(int64_t n, par_fn fn, void *arg) { mrp_pool_run(n, 1, fn, arg); } /* persistent pool, mrp_host_pool.cpp */
 
 /* Allocation: out of memory is fatal, like st_malloc.  Every translation unit has the three functions under these names.  The
  * plain ones are defined here; rphmm_host.c defines RPHMM_ARENA_ALLOC before it includes this header and supplies its own,

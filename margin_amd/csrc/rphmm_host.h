@@ -1,6 +1,6 @@
 /*
  * rphmm_host.h -- internal interface between the C host pipeline (rphmm_*.c) and the HIP side
- * of libmargin_rphmm.so (mrp_api.cpp).  Public declarations live in include/margin_rphmm.h.
+ * of libmargin_rphmm.so (mrp_context.cpp, mrp_chunk.cpp, mrp_batch.cpp, mrp_host_pool.cpp, mrp_engine.cpp).  Public declarations live in include/margin_rphmm.h.
  */
 #ifndef RPHMM_HOST_H_
 #define RPHMM_HOST_H_
@@ -54,7 +54,7 @@ void mrp_pool_set_tag(int t);
 void *mrp_pool_current(void);
 void mrp_pool_adopt(void *pool);
 long long mrp_pool_tag_cpu_ns(int tag);
-/* fn(i, arg) for every i in [0, n), grain indices at a time, on the caller and the persistent worker pool (mrp_api.cpp) */
+/* fn(i, arg) for every i in [0, n), grain indices at a time, on the caller and the persistent worker pool (mrp_host_pool.cpp) */
 void mrp_pool_run(int64_t n, int64_t grain, void (*fn)(int64_t, void *), void *arg);
 /* rough cost of one index of the calling thread's next loops, nanoseconds (0: unknown): short loops run on the caller, longer ones wake only
  * as many workers as they can keep busy */

@@ -1,11 +1,13 @@
 /*
  * level_order_check.cpp -- the host arithmetic of staging a resident level (margin_amd/csrc/mrp_level_order.h) without a device:
- * the order and launch classes of random levels against a plain restatement, and the block carver's two passes against each other.
+ * the order and launch classes of random levels against a plain restatement, the block carver's two passes against each other, and
+ * the layout of a work queue's chunk block.
  * Built and run by tests/test_level_order.py with the address and undefined-behaviour sanitizers; prints "level order ok".
  */
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 
@@ -130,6 +132,45 @@ static void check_carver(std::mt19937 &rng) {
     free(block);
 }
 
+/* the chunk block of a work queue's batch (mrp_chunk_block_create): a few chunks carved one behind the other, sized first, then placed */
+static void check_chunk_block(const std::vector<int> &n_sites, const std::vector<size_t> &pool_bytes, bool with_pool) {
+    static const uint32_t ALLELES[] = {3, 2, 5, 1, 2}; /* slot totals 3, 5, 10, 11, 13: none divisible by 4 */
+    const size_t n = n_sites.size();
+    std::vector<size_t> alleles(n, 0), subs(n, 0), at(n + 1, 0);
+    BlockCarver sizes(nullptr, MRP_CHUNK_BLOCK_ALIGN);
+    for (size_t k = 0; k < n; k++) {
+        for (int i = 0; i < n_sites[k]; i++) { alleles[k] += ALLELES[i]; subs[k] += ALLELES[i] * ALLELES[i]; }
+        CHECK(n_sites[k] == 0 || alleles[k] % 4 != 0);
+        const ChunkSlices z = carve_chunk(sizes, (size_t) n_sites[k], alleles[k], subs[k], pool_bytes[k], with_pool);
+        CHECK(!z.allele_number && !z.allele_offset && !z.sub_offset && !z.same_until && !z.sub && !z.prior && !z.pool);
+        at[k + 1] = sizes.used;
+    }
+    const size_t reserved = chunk_block_bytes(sizes.used);
+    char *block = (char *) aligned_alloc(MRP_CHUNK_BLOCK_ALIGN, (reserved + MRP_CHUNK_BLOCK_ALIGN - 1) / MRP_CHUNK_BLOCK_ALIGN * MRP_CHUNK_BLOCK_ALIGN);
+    CHECK(block != nullptr);
+    char *end_before = block;
+    for (size_t k = 0; k < n; k++) {
+        BlockCarver c(block + at[k], MRP_CHUNK_BLOCK_ALIGN); /* as the second pass does: every chunk from its own offset */
+        const ChunkSlices z = carve_chunk(c, (size_t) n_sites[k], alleles[k], subs[k], pool_bytes[k], with_pool);
+        CHECK(at[k] + c.used == at[k + 1]); /* the sizing pass equals the pointer pass */
+        const size_t ns = (size_t) n_sites[k];
+        char *const p[7] = {(char *) z.allele_number, (char *) z.allele_offset, (char *) z.sub_offset, (char *) z.same_until, (char *) z.sub, (char *) z.prior, (char *) z.pool};
+        const size_t bytes[7] = {4 * ns, 4 * (ns + 1), 4 * (ns + 1), 4 * ns, 2 * subs[k], 2 * alleles[k], pool_bytes[k]};
+        CHECK((z.pool != nullptr) == with_pool);
+        for (int q = 0; q < (with_pool ? 7 : 6); q++) {
+            CHECK(((uintptr_t) p[q] & (MRP_CHUNK_BLOCK_ALIGN - 1)) == 0);
+            CHECK(p[q] >= end_before && p[q] + bytes[q] <= block + sizes.used); /* inside the block, behind every slice before it */
+            if (q > 0 && bytes[q - 1] == 0) CHECK(p[q] == p[q - 1]);             /* a zero-length slice takes nothing */
+            CHECK(p[q] - end_before < MRP_CHUNK_BLOCK_ALIGN);                    /* nothing but the rounding between two slices */
+            memset(p[q], (int) q, bytes[q]);                                     /* (the sanitizer watches the writes) */
+            end_before = p[q] + bytes[q];
+        }
+        /* the packing kernel's reach behind a pool stays inside the allocation, behind the last pool of the block too */
+        if (with_pool) CHECK((char *) z.pool + pool_bytes[k] + MRP_POOL_TAIL_PAD <= block + reserved);
+    }
+    free(block);
+}
+
 int main() {
     std::mt19937 rng(20240611);
     for (int64_t n : {0, 1, 2, 63, 4096, 4097, 6000})
@@ -137,6 +178,13 @@ int main() {
             for (int units = 0; units < 2; units++)
                 for (int rep = 0; rep < (n <= 63 ? 20 : 2); rep++) check_level(random_level(rng, n, mode), units != 0);
     for (int rep = 0; rep < 2000; rep++) check_carver(rng);
+    for (int with_pool = 0; with_pool < 2; with_pool++)
+        for (size_t last_pool : {0, 1, 255, 256, 257})
+            for (int last_sites : {0, 1, 5}) {
+                check_chunk_block({last_sites}, {last_pool}, with_pool != 0);
+                check_chunk_block({5, 0, 1, last_sites}, {257, 0, 255, last_pool}, with_pool != 0);
+                check_chunk_block({last_sites, 1, 5}, {last_pool, 256, 1}, with_pool != 0);
+            }
     printf("level order ok\n");
     return 0;
 }

@@ -296,7 +296,7 @@ def _run_one_job(gpu_ctx, chunk, flat):
 
 def test_sum_mode_column_of_2_to_the_14_cells_takes_the_generic_kernel(gpu_ctx):
     """The log-sum-exp kernel with the merge column in LDS accumulates in 64-bit fixed point, 2^50 units per term: a column of
-    2^14 equal-valued cells would wrap its accumulator.  Such an hmm goes to the generic fp64 kernel (mrp_api.cpp launch plan)
+    2^14 equal-valued cells would wrap its accumulator.  Such an hmm goes to the generic fp64 kernel (mrp_batch.cpp launch plan)
     and its sums are the sequential logAddP of hmm.c:15-20 within 1e-9 (checked against the naive evaluation)."""
     from tests import bruteforce
     chunk = synth.make_ont_chunk(seed=21, region_bp=2_000, n_sites=4, coverage=40)

@@ -2,7 +2,10 @@
 a stand-alone program built with the address and undefined-behaviour sanitizers.  It checks the order of a level's hmms and their
 launch classes on seeded random levels (n in {0, 1, 2, 63, 4 096, 4 097, 6 000}; few distinct column counts and bounds, so ties are
 common; bounds on both sides of every threshold; unit and cell levels) against a plain restatement, and the block carver's sizing
-pass against its pointer pass (64-byte aligned, inside the block, disjoint regions; a zero count takes nothing)."""
+pass against its pointer pass (64-byte aligned, inside the block, disjoint regions; a zero count takes nothing), and the chunk block of
+a work queue's batch (chunks of 0, 1 and 5 sites with slot totals not divisible by 4, profile pools of 0, 1, 255, 256 and 257 bytes, with
+and without the pools in the block): sizing pass equal to pointer pass, every slice 256-byte aligned, inside the block and disjoint,
+a zero-length slice takes nothing, and every pool -- the last one too -- ends MRP_POOL_TAIL_PAD bytes or more before the reserved size."""
 import os
 import subprocess
 
