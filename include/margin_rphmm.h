@@ -805,6 +805,55 @@ int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_al
 int mrp_string_chunk_from_extracted(const mrp_extracted_chunk *x, const uint8_t *keep, const char *const *read_names,
                                     const uint8_t *read_forward_strand, mrp_string_chunk *out, int64_t **bubble_variant);
 
+/* ---- from alignments and a phased VCF to haplotype tags ---------------------------------------------------------------
+ * The chunk loop of tools/tagFromPhasedVcf.c (:284-309): updateVcfEntriesWithSubstringsAndPositions,
+ * extractReadSubstringsAtVariantPositions with filteredReads = NULL, bubbleGraph_partitionFilteredReadsFromPhasedVcfEntries
+ * (bubbleGraph.c:1945-2138).
+ *
+ * mrp_haptag_sites_from_extracted, host only: the sites mrp_partition_reads_by_haplotype takes, for n_chunks extracted chunks.
+ * A site is a variant, in chunk order then variant order (a variant without entries is listed too: the partition skips it
+ * itself); compare = (gt[c][2v], gt[c][2v+1]), the phased genotype of variant v of chunk c (allele indices within the variant;
+ * gt[c] may be NULL for a chunk without variants); the entries are those of the MRP_READ_KEPT reads, in ascending read order
+ * (with filteredReads == NULL the reference skips low-mapq reads, htsIntegration.c:1825).  Read indices are global:
+ * read_first[c] + r, read_first (n_chunks + 1 entries, written) ending in the n_reads to pass on.  The pool is the chunks'
+ * pools one after the other, offsets moved by each chunk's base.  Every array of out lives in one block, released by
+ * mrp_free((void *) out->allele_first).  MRP_ERR_ARG for a NULL argument or a genotype outside [0, alleles of the variant); the
+ * message names chunk and variant. */
+int mrp_haptag_sites_from_extracted(int64_t n_chunks, const mrp_extracted_chunk *x, const int32_t *const *gt,
+                                    mrp_haptag_sites *out, int64_t *read_first /* n_chunks + 1 */);
+
+typedef struct mrp_haplotag_aligned_stats {
+    mrp_extract_stats extract;  /* the extraction's half; total_ms and host_ms end where its second half has been queued */
+    mrp_pairhmm_stats pairhmm;  /* the pair-HMM launch and the scoring kernel (total_ms: 0) */
+    int64_t sites;              /* variants of the call */
+    int64_t active_sites;       /* heterozygous, with an entry of a kept read */
+    int64_t entries;            /* entries of kept reads at active sites: what is scored or copies a score */
+    int64_t owners;             /* of these, the ones that are scored (two pairs each) */
+    int64_t bytes_downloaded;   /* everything that came back from the device during the call */
+    double owners_ms;           /* HIP events around the kernel that finds the owners of equal substrings */
+    double total_ms;            /* host wall time of the call */
+} mrp_haplotag_aligned_stats;
+
+/* The three steps above in one call: mrp_extract_read_substrings (same options, quirks and refusals), the sites over its
+ * result where it lies on the device, mrp_partition_reads_by_haplotype's scoring.  A read's strand is its flag (0x10 clear:
+ * forward).  The MRP_READ_KEPT reads take part; MRP_READ_FILTERED reads are not scored and never own a cache entry.  A
+ * site is active if gt1 != gt2 (:1975) and a kept read has an entry for it (:1989); among a site's entries of kept reads with equal
+ * substrings the LAST listed (highest read index; b->reads is filled by popping, :2012-2014) owns the scores and its strand picks
+ * the state machine (:2047-2061); pairs are never anchored (:2027); scoring as mrp_partition_reads_by_haplotype.  The substrings'
+ * symbols never leave the device: the owners are found there, and what comes back is per entry its read, length and owner, per
+ * read its status, and the results.  hap_out[c][r], for every read of chunk c: 1, 2, 0 (kept but unclassified) or -1 (not in
+ * `reads`: dropped or low mapq); h1_out / h2_out (NULL, or one array per chunk) the totals, 0 for reads that are not kept.
+ * Outputs are written only on success.  Errors, in this order: MRP_ERR_ARG (the extraction's own checks, a NULL model or output,
+ * a NULL gt[c] for a chunk with variants, a genotype outside the variant's alleles, an odd or negative expansion) before the
+ * context is looked at; MRP_ERR_UNSUPPORTED for the SV split mode or run-length encoding, as the extraction reports them:
+ * without a context too; MRP_ERR_NO_DEVICE for a NULL context; MRP_ERR_UNSUPPORTED for a pair whose widest diagonal exceeds
+ * 2 048 cells, known once the extraction's device half has given the lengths and raised before any pair-HMM kernel is launched.
+ * stats may be NULL. */
+int mrp_haplotag_aligned_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const int32_t *const *gt,
+                                const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                                int64_t expansion, int8_t *const *hap_out, double *const *h1_out, double *const *h2_out,
+                                mrp_haplotag_aligned_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

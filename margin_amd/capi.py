@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = [
     "mrp_queue_phase_chunks", "mrp_partition_reads_by_haplotype", "mrp_phase_variants_from_tagged_reads", "mrp_phase_string_chunks",
     "mrp_extract_read_substrings", "mrp_string_chunk_from_extracted", "mrp_string_chunk_units", "mrp_queue_phase_string_chunks",
     "mrp_phase_string_chunks_on_devices", "mrp_phase_string_chunks_with_filtered", "mrp_queue_phase_string_chunks_with_filtered",
-    "mrp_phase_string_chunks_with_filtered_on_devices",
+    "mrp_phase_string_chunks_with_filtered_on_devices", "mrp_haptag_sites_from_extracted", "mrp_haplotag_aligned_chunks",
 ]
 
 
@@ -284,6 +284,11 @@ class ExtractStats(C.Structure):
                 ("bytes_uploaded", C.c_int64), ("host_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class HaplotagAlignedStats(C.Structure):
+    _fields_ = [("extract", ExtractStats), ("pairhmm", PairHmmStats), ("sites", C.c_int64), ("active_sites", C.c_int64), ("entries", C.c_int64),
+                ("owners", C.c_int64), ("bytes_downloaded", C.c_int64), ("owners_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 def load():
     """dlopen the in-tree library; raises if it has not been built (no fallback)."""
     global _lib
@@ -377,6 +382,9 @@ def load():
     L.mrp_phase_string_chunks_with_filtered_on_devices.argtypes = [vp, i32] + L.mrp_queue_phase_string_chunks_with_filtered.argtypes[1:]
     L.mrp_extract_read_substrings.argtypes = [vp, i64, P(AlignedChunk), P(ExtractOptions), P(P(ExtractedChunk)), P(ExtractStats)]
     L.mrp_string_chunk_from_extracted.argtypes = [P(ExtractedChunk), vp, vp, vp, P(StringChunk), P(P(C.c_int64))]
+    L.mrp_haptag_sites_from_extracted.argtypes = [i64, P(ExtractedChunk), P(vp), P(HaptagSites), vp]
+    L.mrp_haplotag_aligned_chunks.argtypes = [vp, i64, P(AlignedChunk), P(vp), P(ExtractOptions), P(PairHmm), P(PairHmm), i64, P(vp), P(vp), P(vp),
+                                              P(HaplotagAlignedStats)]
     L.mrp_kmer_alignment_anchors.argtypes = [vp, i64, vp, i64, vp]
     L.mrp_kmer_alignment_anchors.restype = i64
     L.mrp_phase_chunks_on_devices.argtypes = [vp, i32, i64, P(ChunkDesc), P(Params), i64, P(P(PhaseResult)), P(QueueStats)]
@@ -1079,6 +1087,10 @@ def partition_reads_by_haplotype(ctx: Context, forward_model: PairHmm, reverse_m
     """bubbleGraph_partitionFilteredReadsFromVcfEntries (bubbleGraph.c:1749-1943) for the sites of any number of chunks; sites as
     _haptag_sites takes them, (i, j) = (hap1, hap2) allele.  Returns (hap int32 [n_reads]: 1, 2 or 0, h1, h2, PairHmmStats)."""
     S, keep = _haptag_sites(sites)
+    return _partition_reads(ctx, forward_model, reverse_model, S, n_reads, read_forward_strand, expansion)
+
+
+def _partition_reads(ctx, forward_model, reverse_model, S: HaptagSites, n_reads: int, read_forward_strand, expansion: int):
     sd = np.ascontiguousarray(read_forward_strand, dtype=np.uint8).astype(bool).astype(np.uint8)
     assert sd.size == n_reads
     hap, h1, h2 = np.zeros(n_reads, dtype=np.int32), np.zeros(n_reads), np.zeros(n_reads)
@@ -1513,3 +1525,72 @@ def string_chunk_from_extracted(x: dict, read_names, read_forward_strand, keep=N
     sc = synth.StringChunk(bubbles=bubbles, read_names=list(read_names), read_forward_strand=strand, hap=np.zeros(len(names), np.int64),
                            truth=[0] * nb)
     return sc, raw["bubble_variant"], raw
+
+
+# ---- haplotagging aligned reads from a phased VCF (mrp_haptag_sites_from_extracted, mrp_haplotag_aligned_chunks) ----
+
+_HAPTAG_SITE_ARRAYS = (("allele_first", np.int64, "s1"), ("allele_off", np.int64, "a"), ("allele_len", np.int32, "a"), ("compare", np.int32, "s2"),
+                       ("entry_first", np.int64, "s1"), ("entry_read", np.int64, "e"), ("entry_off", np.int64, "e"), ("entry_len", np.int32, "e"))
+
+
+def _genotype_arrays(gts):
+    """per chunk an int32 [2 * n_variants] array (None stays NULL) -> (the void* array the C-ABI takes, the arrays it points into)"""
+    keep = [None if g is None else np.ascontiguousarray(g, np.int32).reshape(-1) for g in gts]
+    arr = (C.c_void_p * max(len(keep), 1))(*[None if g is None or g.size == 0 else g.ctypes.data for g in keep])
+    return arr, keep
+
+
+def haptag_sites_from_extracted(xs, gts, null_gt=False):
+    """mrp_haptag_sites_from_extracted over the dicts extract_read_substrings returns (or tests.extract_oracle.as_arrays makes); gts: per
+    chunk the phased genotypes, int32 [n_variants, 2].  Returns (dict of the mrp_haptag_sites arrays as numpy copies, with n_sites and
+    pool; read_first int64 [n_chunks + 1]).  null_gt passes a NULL genotype table (for the argument checks)."""
+    L = load()
+    n = len(xs)
+    built = [extracted_struct(x) for x in xs]
+    arr = (ExtractedChunk * max(n, 1))(*[b[0] for b in built])
+    garr, gkeep = _genotype_arrays(gts)
+    S = HaptagSites()
+    read_first = np.zeros(n + 1, np.int64)
+    _check(L.mrp_haptag_sites_from_extracted(n, arr, None if null_gt else garr, C.byref(S), read_first.ctypes.data))
+    ns = int(S.n_sites)
+    a_first = _as_np(S.allele_first, ns + 1, np.int64)
+    e_first = _as_np(S.entry_first, ns + 1, np.int64)
+    size = dict(s1=ns + 1, s2=2 * ns, a=int(a_first[ns]), e=int(e_first[ns]))
+    out = {f: _as_np(getattr(S, f), size[k], t) for f, t, k in _HAPTAG_SITE_ARRAYS}
+    out["pool"] = _as_np(S.pool, int(S.pool_bytes), np.uint8)
+    out["n_sites"] = ns
+    L.mrp_free(S.allele_first)
+    return out, read_first
+
+
+def partition_reads_from_site_arrays(ctx: Context, forward_model: PairHmm, reverse_model: PairHmm, sites: dict, n_reads: int, read_forward_strand,
+                                     expansion: int = 4):
+    """mrp_partition_reads_by_haplotype over the arrays haptag_sites_from_extracted returns -> (hap, h1, h2, PairHmmStats)"""
+    keep = {f: np.ascontiguousarray(sites[f], t) for f, t, _ in _HAPTAG_SITE_ARRAYS}
+    pool = np.ascontiguousarray(sites["pool"], np.uint8)
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data
+    S = HaptagSites(int(sites["n_sites"]), ptr(pool), pool.size, *[ptr(keep[f]) for f, _, _ in _HAPTAG_SITE_ARRAYS])
+    return _partition_reads(ctx, forward_model, reverse_model, S, n_reads, read_forward_strand, expansion)
+
+
+def haplotag_aligned_chunks(ctx: Optional[Context], chunks, gts, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm],
+                            options: Optional[dict] = None, expansion: int = 4, totals: bool = True, structs=None, null_options: bool = False):
+    """mrp_haplotag_aligned_chunks -> (per chunk dict(hap int8 [n_reads]: 1 / 2 / 0 / -1, h1, h2 float64 (None without totals)),
+    HaplotagAlignedStats).  gts: per chunk int32 [n_variants, 2] (None: NULL).  ctx / a model None pass NULL; structs as
+    extract_read_substrings takes them."""
+    L = load()
+    n = len(chunks)
+    built = structs if structs is not None else [aligned_chunk_struct(c) for c in chunks]
+    arr = (AlignedChunk * max(n, 1))(*[b[0] for b in built])
+    garr, gkeep = _genotype_arrays(gts)
+    opt = ExtractOptions.from_dict(options or shipped_extract_options())
+    nr = [int(b[0].n_reads) for b in built]
+    hap = [np.full(k, 99, np.int8) for k in nr]
+    h1 = [np.full(k, np.nan) for k in nr]
+    h2 = [np.full(k, np.nan) for k in nr]
+    ptrs = lambda arrays: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrays])
+    st = HaplotagAlignedStats()
+    by = lambda m: None if m is None else C.byref(m)
+    _check(L.mrp_haplotag_aligned_chunks(ctx.h if ctx else None, n, arr, garr, None if null_options else C.byref(opt), by(forward_model), by(reverse_model),
+                                         int(expansion), ptrs(hap), ptrs(h1) if totals else None, ptrs(h2) if totals else None, C.byref(st)))
+    return [dict(hap=hap[c], h1=h1[c] if totals else None, h2=h2[c] if totals else None) for c in range(n)], st

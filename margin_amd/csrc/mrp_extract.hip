@@ -21,6 +21,10 @@
  *
  * The windows are computed on the host while checking the arguments; the allele strings on the worker pool while the
  * device runs.  One total (the substrings and their bases) comes back between the two halves to size the buffers.
+ *
+ * The call is one mrp_extract_run taken through steps (mrp_internal.h): check, stage and upload, first half, totals, second
+ * half, download.  mrp_extract_read_substrings is all of them; mrp_haplotag_aligned_chunks (mrp_pairhmm.hip) stops before the
+ * download and reads the result in HBM.
  */
 #include <hip/hip_runtime.h>
 
@@ -329,12 +333,12 @@ __global__ __launch_bounds__(64) void ex_rank_kernel(const int64_t *__restrict__
 
 __global__ __launch_bounds__(64) void ex_gather_kernel(const int32_t *__restrict__ order, int64_t n, const ExEntry *__restrict__ e,
                                                        const int64_t *__restrict__ off, const uint8_t *__restrict__ seq, uint8_t *__restrict__ pool,
-                                                       int32_t *__restrict__ read) {
+                                                       int64_t base, int32_t *__restrict__ read) {
     const int lane = threadIdx.x;
     for (int64_t p = blockIdx.x; p < n; p += gridDim.x) {
         const ExEntry x = e[order[p]];
         if (lane == 0) read[p] = x.read;
-        uint8_t *dst = pool + off[p];
+        uint8_t *dst = pool + base + off[p]; /* base: where the call's substrings begin in pool */
         for (int t = lane; t < x.len; t += EX_WAVE) {
             const int64_t i = x.src + t;
             const uint32_t code = (seq[i >> 1] >> ((~i & 1) << 2)) & 15u;
@@ -450,53 +454,37 @@ int ex_check_chunk(const mrp_aligned_chunk &C, const mrp_extract_options &o, std
 
 template <class T> size_t ex_align(size_t x) { return (x + alignof(T) - 1) / alignof(T) * alignof(T); }
 
+void ex_free_chunks(mrp_extracted_chunk *res, int64_t n_chunks) {
+    if (!res) return;
+    for (int64_t c = 0; c < n_chunks; c++) {
+        mrp_extracted_chunk &X = res[c];
+        void *ps[] = {X.ref_aln_start, X.ref_aln_stop_incl, X.allele_first, X.allele_off, X.allele_len, X.read_status,
+                      X.read_n_substrings, X.entry_first, X.entry_read, X.entry_off, X.entry_len, X.pool};
+        for (void *p : ps) free(p);
+    }
+    free(res);
+}
+
 }  // namespace
 
-extern "C" {
-
-int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_extract_options *options,
-                                mrp_extracted_chunk **out, mrp_extract_stats *stats) {
-    static const char *who = "mrp_extract_read_substrings";
-    const double t_begin = ex_now_ms();
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (n_chunks < 0 || (n_chunks > 0 && !chunks) || !options || !out) return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
-    const mrp_extract_options o = *options;
-    if (o.expansion_small < 0 || o.expansion_sv < 0) return mrp_set_error(MRP_ERR_ARG, "%s: negative reference expansion", who);
-    if (o.indel_size_for_sv_handling != 0) return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: indelSizeForSVHandling > 0 (htsIntegration.c:1724-1755) is not supported", who);
-    if (o.use_run_length_encoding != 0) return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: run-length encoding is not supported", who);
-    std::vector<std::vector<ExWindow>> win((size_t) n_chunks);
-    std::vector<int64_t> aligned((size_t) n_chunks, 0);
-    {
-        std::vector<int> rcs((size_t) n_chunks, MRP_OK);
-        std::vector<std::string> msgs((size_t) n_chunks);
-        mrp_parallel_for(n_chunks, 1, [&](int64_t c) { rcs[(size_t) c] = ex_check_chunk(chunks[c], o, win[(size_t) c], aligned[(size_t) c], msgs[(size_t) c]); });
-        for (int64_t c = 0; c < n_chunks; c++)
-            if (rcs[(size_t) c] != MRP_OK) return mrp_set_error(rcs[(size_t) c], "%s: chunk %lld: %s", who, (long long) c, msgs[(size_t) c].c_str());
-    }
-    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction has no CPU fallback)", who);
-    *out = nullptr;
-
-    /* ---- the call's reads, ops, bases and variants, one staging buffer */
-    std::vector<int64_t> rb((size_t) n_chunks + 1, 0), vb((size_t) n_chunks + 1, 0), cb((size_t) n_chunks + 1, 0), sb((size_t) n_chunks + 1, 0);
-    for (int64_t c = 0; c < n_chunks; c++) {
-        const mrp_aligned_chunk &C = chunks[c];
-        rb[(size_t) c + 1] = rb[(size_t) c] + C.n_reads;
-        vb[(size_t) c + 1] = vb[(size_t) c] + C.n_variants;
-        cb[(size_t) c + 1] = cb[(size_t) c] + (C.n_reads ? C.cigar_first[C.n_reads] : 0);
-        sb[(size_t) c + 1] = sb[(size_t) c] + (C.n_reads ? C.seq_first[C.n_reads] : 0);
-    }
-    const int64_t n_reads = rb[(size_t) n_chunks], n_var = vb[(size_t) n_chunks], n_ops = cb[(size_t) n_chunks], n_seq = sb[(size_t) n_chunks];
-    if (n_reads >= (1ll << 31) || n_var >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 reads or variants in one call", who);
-    size_t at = 0;
-    const size_t o_cig = at; at = ex_align<ExRead>(at + sizeof(uint32_t) * (size_t) n_ops);
-    const size_t o_read = at; at = ex_align<ExChunk>(at + sizeof(ExRead) * (size_t) n_reads);
-    const size_t o_chunk = at; at = ex_align<ExVar>(at + sizeof(ExChunk) * (size_t) n_chunks);
-    const size_t o_var = at; at += sizeof(ExVar) * (size_t) n_var;
-    const size_t o_seq = at; at += (size_t) n_seq;
-    const size_t in_bytes = at;
-
-    EX_HIP(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
+/* One extraction taken through steps (mrp_internal.h): everything the queued work reads or writes until the stream has drained -- the
+ * windows, the staging block, the device arrays, the events -- and the allele strings made beside the first half.  The destructor
+ * drains the stream before the buffers go back to the pool; whoever ran it reclaims the pool afterwards. */
+struct mrp_extract_run {
+    const char *const who;
+    const int64_t n_chunks;
+    const mrp_aligned_chunk *const chunks;
+    const mrp_extract_options *const options;
+    mrp_extract_stats *const stats;
+    const double t_begin;
+    mrp_extract_options o{};
+    std::vector<std::vector<ExWindow>> win;
+    std::vector<int64_t> aligned;
+    std::vector<int64_t> rb, vb, cb, sb; /* n_chunks + 1: chunk c's share of the call's reads, variants, CIGAR words, packed bases */
+    int64_t n_reads = 0, n_var = 0, n_ops = 0, n_seq = 0, n_ent = 0, n_bases = 0;
+    size_t o_cig = 0, o_read = 0, o_chunk = 0, o_var = 0, o_seq = 0, in_bytes = 0;
+    mrp_context *ctx = nullptr;
+    hipStream_t s = nullptr; /* set once the device is current: from then on the destructor drains it */
     DevBuf<uint8_t> d_in, d_status, d_pool;
     DevBuf<ExOp> d_ops;
     DevBuf<ExState> d_state;
@@ -504,24 +492,103 @@ int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_al
     DevBuf<unsigned long long> d_tot;
     DevBuf<ExEntry> d_entries;
     DevBuf<int32_t> d_bucket, d_order, d_fread;
-    d_in.pool = d_status.pool = d_pool.pool = &ctx->pool;
-    d_ops.pool = &ctx->pool;
-    d_state.pool = &ctx->pool;
-    d_count.pool = d_eoff.pool = d_vcnt.pool = d_vfirst.pool = d_vfill.pool = d_flen.pool = d_foff.pool = &ctx->pool;
-    d_tot.pool = &ctx->pool;
-    d_entries.pool = &ctx->pool;
-    d_bucket.pool = d_order.pool = d_fread.pool = &ctx->pool;
+    uint8_t *g_pool = nullptr; /* where the gather wrote: d_pool, or the caller's pool + its base */
     PinnedBuf h_in, h_back;
-    struct Events {
-        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-        ~Events() { for (hipEvent_t x : e) if (x) (void) hipEventDestroy(x); }
-    } ev;
-    Drain drain{s}; /* before the buffers go back to the pool */
-    for (hipEvent_t &x : ev.e) EX_HIP(hipEventCreate(&x));
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double t_dev0 = 0, t_dev2 = 0, t_end = 0;
+    /* the allele strings (prefix + allele + suffix), symbols, per chunk */
+    std::vector<HostVec<uint8_t>> apool;
+    std::vector<std::vector<int64_t>> aoff;
 
-    EX_HIP(h_in.reserve(std::max<size_t>(in_bytes, 1)));
-    uint8_t *hin = (uint8_t *) h_in.p;
+    mrp_extract_run(const char *w, int64_t n, const mrp_aligned_chunk *c, const mrp_extract_options *op, mrp_extract_stats *st)
+        : who(w), n_chunks(n), chunks(c), options(op), stats(st), t_begin(ex_now_ms()) {
+        if (stats) memset(stats, 0, sizeof(*stats));
+    }
+    ~mrp_extract_run() {
+        if (s) (void) hipStreamSynchronize(s);
+        for (hipEvent_t x : ev)
+            if (x) (void) hipEventDestroy(x);
+    }
+    void bind(DevPool *pl) {
+        d_in.pool = d_status.pool = d_pool.pool = pl;
+        d_ops.pool = pl;
+        d_state.pool = pl;
+        d_count.pool = d_eoff.pool = d_vcnt.pool = d_vfirst.pool = d_vfill.pool = d_flen.pool = d_foff.pool = pl;
+        d_tot.pool = pl;
+        d_entries.pool = pl;
+        d_bucket.pool = d_order.pool = d_fread.pool = pl;
+    }
+};
+
+mrp_extract_run *mrp_extract_run_create(const char *who, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_extract_options *options,
+                                        mrp_extract_stats *stats) {
+    return new (std::nothrow) mrp_extract_run(who, n_chunks, chunks, options, stats);
+}
+
+void mrp_extract_run_destroy(mrp_extract_run *R) { delete R; }
+
+int mrp_extract_run_check_args(mrp_extract_run *R, bool have_out) {
+    if (R->n_chunks < 0 || (R->n_chunks > 0 && !R->chunks) || !R->options || !have_out) return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", R->who);
+    R->o = *R->options;
+    if (R->o.expansion_small < 0 || R->o.expansion_sv < 0) return mrp_set_error(MRP_ERR_ARG, "%s: negative reference expansion", R->who);
+    return MRP_OK;
+}
+
+int mrp_extract_run_check_modes(mrp_extract_run *R) {
+    if (R->o.indel_size_for_sv_handling != 0)
+        return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: indelSizeForSVHandling > 0 (htsIntegration.c:1724-1755) is not supported", R->who);
+    if (R->o.use_run_length_encoding != 0) return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: run-length encoding is not supported", R->who);
+    return MRP_OK;
+}
+
+/* the chunks' own checks, and the windows */
+int mrp_extract_run_check_chunks(mrp_extract_run *R) {
+    const int64_t n_chunks = R->n_chunks;
+    R->win.resize((size_t) n_chunks);
+    R->aligned.assign((size_t) n_chunks, 0);
+    std::vector<int> rcs((size_t) n_chunks, MRP_OK);
+    std::vector<std::string> msgs((size_t) n_chunks);
+    mrp_parallel_for(n_chunks, 1, [&](int64_t c) { rcs[(size_t) c] = ex_check_chunk(R->chunks[c], R->o, R->win[(size_t) c], R->aligned[(size_t) c], msgs[(size_t) c]); });
+    for (int64_t c = 0; c < n_chunks; c++)
+        if (rcs[(size_t) c] != MRP_OK) return mrp_set_error(rcs[(size_t) c], "%s: chunk %lld: %s", R->who, (long long) c, msgs[(size_t) c].c_str());
+    return MRP_OK;
+}
+
+/* the call's reads, ops, bases and variants in one staging buffer, and its upload */
+int mrp_extract_run_stage(mrp_extract_run *R, mrp_context *ctx) {
+    const char *who = R->who;
+    const int64_t n_chunks = R->n_chunks;
+    const mrp_aligned_chunk *chunks = R->chunks;
+    std::vector<int64_t> &rb = R->rb, &vb = R->vb, &cb = R->cb, &sb = R->sb;
+    rb.assign((size_t) n_chunks + 1, 0); vb.assign((size_t) n_chunks + 1, 0); cb.assign((size_t) n_chunks + 1, 0); sb.assign((size_t) n_chunks + 1, 0);
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const mrp_aligned_chunk &C = chunks[c];
+        rb[(size_t) c + 1] = rb[(size_t) c] + C.n_reads;
+        vb[(size_t) c + 1] = vb[(size_t) c] + C.n_variants;
+        cb[(size_t) c + 1] = cb[(size_t) c] + (C.n_reads ? C.cigar_first[C.n_reads] : 0);
+        sb[(size_t) c + 1] = sb[(size_t) c] + (C.n_reads ? C.seq_first[C.n_reads] : 0);
+    }
+    const int64_t n_reads = R->n_reads = rb[(size_t) n_chunks], n_var = R->n_var = vb[(size_t) n_chunks], n_ops = R->n_ops = cb[(size_t) n_chunks],
+                  n_seq = R->n_seq = sb[(size_t) n_chunks];
+    if (n_reads >= (1ll << 31) || n_var >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 reads or variants in one call", who);
+    size_t at = 0;
+    const size_t o_cig = R->o_cig = at; at = ex_align<ExRead>(at + sizeof(uint32_t) * (size_t) n_ops);
+    const size_t o_read = R->o_read = at; at = ex_align<ExChunk>(at + sizeof(ExRead) * (size_t) n_reads);
+    const size_t o_chunk = R->o_chunk = at; at = ex_align<ExVar>(at + sizeof(ExChunk) * (size_t) n_chunks);
+    const size_t o_var = R->o_var = at; at += sizeof(ExVar) * (size_t) n_var;
+    const size_t o_seq = R->o_seq = at; at += (size_t) n_seq;
+    const size_t in_bytes = R->in_bytes = at;
+
+    EX_HIP(hipSetDevice(ctx->device));
+    R->ctx = ctx;
+    R->bind(&ctx->pool);
+    hipStream_t s = R->s = ctx->stream;
+    for (hipEvent_t &x : R->ev) EX_HIP(hipEventCreate(&x));
+
+    EX_HIP(R->h_in.reserve(std::max<size_t>(in_bytes, 1)));
+    uint8_t *hin = (uint8_t *) R->h_in.p;
     ExChunk *hch = (ExChunk *) (hin + o_chunk);
+    const std::vector<std::vector<ExWindow>> &win = R->win;
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
         const mrp_aligned_chunk &C = chunks[c];
         hch[c] = ExChunk{C.overlap_start, C.chunk_start, C.chunk_end, vb[(size_t) c], C.n_variants};
@@ -545,58 +612,68 @@ int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_al
             if (C.seq_first[C.n_reads]) memcpy(hin + o_seq + (size_t) sb[(size_t) c], C.seq, (size_t) C.seq_first[C.n_reads]);
         }
     });
-    EX_HIP(d_in.alloc(in_bytes));
-    if (in_bytes) EX_HIP(hipMemcpyAsync(d_in.p, hin, in_bytes, hipMemcpyHostToDevice, s));
-    const uint32_t *g_cig = (const uint32_t *) (d_in.p + o_cig);
-    const ExRead *g_read = (const ExRead *) (d_in.p + o_read);
-    const ExChunk *g_chunk = (const ExChunk *) (d_in.p + o_chunk);
-    const ExVar *g_var = (const ExVar *) (d_in.p + o_var);
-    const uint8_t *g_seq = d_in.p + o_seq;
-    if (stats) EX_HIP(hipStreamSynchronize(s)); /* kernel_ms must not contain the tail of the upload */
-    const double t_dev0 = ex_now_ms();
+    EX_HIP(R->d_in.alloc(in_bytes));
+    if (in_bytes) EX_HIP(hipMemcpyAsync(R->d_in.p, hin, in_bytes, hipMemcpyHostToDevice, s));
+    if (R->stats) EX_HIP(hipStreamSynchronize(s)); /* kernel_ms must not contain the tail of the upload */
+    R->t_dev0 = ex_now_ms();
+    return MRP_OK;
+}
 
-    /* ---- first half: scan, count, scan of the counts; one total back */
-    const ExOpt eo{o.min_mapq, o.include_secondary, o.include_supplementary};
-    EX_HIP(d_status.alloc((size_t) n_reads));
-    EX_HIP(d_ops.alloc((size_t) n_ops));
-    EX_HIP(d_state.alloc((size_t) n_reads));
-    EX_HIP(d_count.alloc((size_t) n_reads));
-    EX_HIP(d_eoff.alloc((size_t) n_reads + 1));
-    EX_HIP(d_tot.alloc(1));
-    EX_HIP(h_back.reserve(64));
-    EX_HIP(hipEventRecord(ev.e[0], s));
-    EX_HIP(hipMemsetAsync(d_tot.p, 0, sizeof(unsigned long long), s));
+/* first half: scan, count, scan of the counts; one total (the substrings and their bases) starts on its way back */
+int mrp_extract_run_first_half(mrp_extract_run *R) {
+    hipStream_t s = R->s;
+    const int64_t n_reads = R->n_reads;
+    const uint32_t *g_cig = (const uint32_t *) (R->d_in.p + R->o_cig);
+    const ExRead *g_read = (const ExRead *) (R->d_in.p + R->o_read);
+    const ExChunk *g_chunk = (const ExChunk *) (R->d_in.p + R->o_chunk);
+    const ExVar *g_var = (const ExVar *) (R->d_in.p + R->o_var);
+    const ExOpt eo{R->o.min_mapq, R->o.include_secondary, R->o.include_supplementary};
+    EX_HIP(R->d_status.alloc((size_t) n_reads));
+    EX_HIP(R->d_ops.alloc((size_t) R->n_ops));
+    EX_HIP(R->d_state.alloc((size_t) n_reads));
+    EX_HIP(R->d_count.alloc((size_t) n_reads));
+    EX_HIP(R->d_eoff.alloc((size_t) n_reads + 1));
+    EX_HIP(R->d_tot.alloc(1));
+    EX_HIP(R->h_back.reserve(64));
+    EX_HIP(hipEventRecord(R->ev[0], s));
+    EX_HIP(hipMemsetAsync(R->d_tot.p, 0, sizeof(unsigned long long), s));
     if (n_reads > 0) {
-        hipLaunchKernelGGL(ex_scan_kernel, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, g_cig, g_chunk, g_var, eo, d_ops.p, d_state.p, d_status.p);
+        hipLaunchKernelGGL(ex_scan_kernel, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, g_cig, g_chunk, g_var, eo, R->d_ops.p, R->d_state.p, R->d_status.p);
         EX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ex_locate_kernel<false>, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, d_status.p, d_state.p, d_ops.p, g_chunk, g_var,
-                           d_count.p, d_tot.p, (const int64_t *) nullptr, (ExEntry *) nullptr);
+        hipLaunchKernelGGL(ex_locate_kernel<false>, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, R->d_status.p, R->d_state.p, R->d_ops.p, g_chunk, g_var,
+                           R->d_count.p, R->d_tot.p, (const int64_t *) nullptr, (ExEntry *) nullptr);
         EX_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(ex_scan_i64, dim3(1), dim3(1024), 0, s, d_count.p, n_reads, d_eoff.p);
+    hipLaunchKernelGGL(ex_scan_i64, dim3(1), dim3(1024), 0, s, R->d_count.p, n_reads, R->d_eoff.p);
     EX_HIP(hipGetLastError());
-    EX_HIP(hipEventRecord(ev.e[1], s));
-    int64_t *hb = (int64_t *) h_back.p;
-    EX_HIP(hipMemcpyAsync(hb, d_eoff.p + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    EX_HIP(hipMemcpyAsync(hb + 1, d_tot.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    EX_HIP(hipEventRecord(R->ev[1], s));
+    int64_t *hb = (int64_t *) R->h_back.p;
+    EX_HIP(hipMemcpyAsync(hb, R->d_eoff.p + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    EX_HIP(hipMemcpyAsync(hb + 1, R->d_tot.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    return MRP_OK;
+}
 
-    /* meanwhile: the allele strings (prefix + allele + suffix), symbols, per chunk */
-    std::vector<HostVec<uint8_t>> apool((size_t) n_chunks);
-    std::vector<std::vector<int64_t>> aoff((size_t) n_chunks);
+/* beside the first half: the allele strings on the worker pool; then the total the second half is sized by */
+int mrp_extract_run_totals(mrp_extract_run *R, int64_t *n_entries, int64_t *n_bases) {
+    const int64_t n_chunks = R->n_chunks;
+    const mrp_aligned_chunk *chunks = R->chunks;
+    R->apool.resize((size_t) n_chunks);
+    R->aoff.resize((size_t) n_chunks);
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
         const mrp_aligned_chunk &C = chunks[c];
+        const std::vector<ExWindow> &win = R->win[(size_t) c];
         const int64_t na = C.n_variants ? C.allele_first[C.n_variants] : 0;
-        std::vector<int64_t> &off = aoff[(size_t) c];
+        std::vector<int64_t> &off = R->aoff[(size_t) c];
         off.assign((size_t) na + 1, 0);
         for (int64_t v = 0; v < C.n_variants; v++) {
-            const ExWindow &w = win[(size_t) c][(size_t) v];
+            const ExWindow &w = win[(size_t) v];
             for (int64_t a = C.allele_first[v]; a < C.allele_first[v + 1]; a++) off[(size_t) a + 1] = w.pre_len + C.allele_len[a] + w.suf_len;
         }
         for (int64_t a = 0; a < na; a++) off[(size_t) a + 1] += off[(size_t) a];
-        HostVec<uint8_t> &p = apool[(size_t) c];
+        HostVec<uint8_t> &p = R->apool[(size_t) c];
         p.resize((size_t) off[(size_t) na]);
         for (int64_t v = 0; v < C.n_variants; v++) {
-            const ExWindow &w = win[(size_t) c][(size_t) v];
+            const ExWindow &w = win[(size_t) v];
             for (int64_t a = C.allele_first[v]; a < C.allele_first[v + 1]; a++) {
                 uint8_t *d = p.data() + off[(size_t) a];
                 for (int64_t i = 0; i < w.pre_len; i++) *d++ = ex_symbol(C.reference[w.pre_at + i]);
@@ -605,86 +682,171 @@ int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_al
             }
         }
     });
-    EX_HIP(hipStreamSynchronize(s));
-    const int64_t n_ent = hb[0], n_bases = hb[1];
-    if (n_ent >= (1ll << 31)) return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: more than 2^31 substrings in one call", who);
-    const double t_dev1 = ex_now_ms();
+    EX_HIP(hipStreamSynchronize(R->s));
+    const int64_t *hb = (const int64_t *) R->h_back.p;
+    R->n_ent = hb[0];
+    R->n_bases = hb[1];
+    if (R->n_ent >= (1ll << 31)) return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: more than 2^31 substrings in one call", R->who);
+    if (n_entries) *n_entries = R->n_ent;
+    if (n_bases) *n_bases = R->n_bases;
+    return MRP_OK;
+}
 
-    /* ---- second half: write the substrings, sort them by entry, gather their bases */
-    EX_HIP(d_entries.alloc((size_t) n_ent));
-    EX_HIP(d_vcnt.alloc((size_t) n_var));
-    EX_HIP(d_vfill.alloc((size_t) n_var));
-    EX_HIP(d_vfirst.alloc((size_t) n_var + 1));
-    EX_HIP(d_bucket.alloc((size_t) n_ent));
-    EX_HIP(d_order.alloc((size_t) n_ent));
-    EX_HIP(d_fread.alloc((size_t) n_ent));
-    EX_HIP(d_flen.alloc((size_t) n_ent));
-    EX_HIP(d_foff.alloc((size_t) n_ent + 1));
-    EX_HIP(d_pool.alloc((size_t) n_bases));
-    EX_HIP(hipEventRecord(ev.e[2], s));
+/* second half: write the substrings, sort them by entry, gather their bases -- into pool + base (a device pool of the caller's, with
+ * room for the total's bases behind base), or with pool NULL into a pool of the run's own */
+int mrp_extract_run_second_half(mrp_extract_run *R, uint8_t *pool, int64_t base) {
+    hipStream_t s = R->s;
+    const int64_t n_reads = R->n_reads, n_var = R->n_var, n_ent = R->n_ent;
+    const ExRead *g_read = (const ExRead *) (R->d_in.p + R->o_read);
+    const ExChunk *g_chunk = (const ExChunk *) (R->d_in.p + R->o_chunk);
+    const ExVar *g_var = (const ExVar *) (R->d_in.p + R->o_var);
+    const uint8_t *g_seq = R->d_in.p + R->o_seq;
+    EX_HIP(R->d_entries.alloc((size_t) n_ent));
+    EX_HIP(R->d_vcnt.alloc((size_t) n_var));
+    EX_HIP(R->d_vfill.alloc((size_t) n_var));
+    EX_HIP(R->d_vfirst.alloc((size_t) n_var + 1));
+    EX_HIP(R->d_bucket.alloc((size_t) n_ent));
+    EX_HIP(R->d_order.alloc((size_t) n_ent));
+    EX_HIP(R->d_fread.alloc((size_t) n_ent));
+    EX_HIP(R->d_flen.alloc((size_t) n_ent));
+    EX_HIP(R->d_foff.alloc((size_t) n_ent + 1));
+    if (!pool) {
+        EX_HIP(R->d_pool.alloc((size_t) R->n_bases));
+        pool = R->d_pool.p;
+        base = 0;
+    }
+    R->g_pool = pool + base;
+    EX_HIP(hipEventRecord(R->ev[2], s));
     if (n_var > 0) {
-        EX_HIP(hipMemsetAsync(d_vcnt.p, 0, sizeof(int64_t) * (size_t) n_var, s));
-        EX_HIP(hipMemsetAsync(d_vfill.p, 0, sizeof(int64_t) * (size_t) n_var, s));
+        EX_HIP(hipMemsetAsync(R->d_vcnt.p, 0, sizeof(int64_t) * (size_t) n_var, s));
+        EX_HIP(hipMemsetAsync(R->d_vfill.p, 0, sizeof(int64_t) * (size_t) n_var, s));
     }
     if (n_ent > 0) {
-        hipLaunchKernelGGL(ex_locate_kernel<true>, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, d_status.p, d_state.p, d_ops.p, g_chunk, g_var,
-                           (int64_t *) nullptr, (unsigned long long *) nullptr, d_eoff.p, d_entries.p);
+        hipLaunchKernelGGL(ex_locate_kernel<true>, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, R->d_status.p, R->d_state.p, R->d_ops.p, g_chunk, g_var,
+                           (int64_t *) nullptr, (unsigned long long *) nullptr, R->d_eoff.p, R->d_entries.p);
         EX_HIP(hipGetLastError());
         const unsigned blocks = (unsigned) ((n_ent + 255) / 256);
-        hipLaunchKernelGGL(ex_var_count_kernel, dim3(blocks), dim3(256), 0, s, d_entries.p, n_ent, (unsigned long long *) d_vcnt.p);
+        hipLaunchKernelGGL(ex_var_count_kernel, dim3(blocks), dim3(256), 0, s, R->d_entries.p, n_ent, (unsigned long long *) R->d_vcnt.p);
         EX_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(ex_scan_i64, dim3(1), dim3(1024), 0, s, d_vcnt.p, n_var, d_vfirst.p);
+    hipLaunchKernelGGL(ex_scan_i64, dim3(1), dim3(1024), 0, s, R->d_vcnt.p, n_var, R->d_vfirst.p);
     EX_HIP(hipGetLastError());
     if (n_ent > 0) {
         const unsigned blocks = (unsigned) ((n_ent + 255) / 256);
-        hipLaunchKernelGGL(ex_bucket_kernel, dim3(blocks), dim3(256), 0, s, d_entries.p, n_ent, d_vfirst.p, (unsigned long long *) d_vfill.p, d_bucket.p);
+        hipLaunchKernelGGL(ex_bucket_kernel, dim3(blocks), dim3(256), 0, s, R->d_entries.p, n_ent, R->d_vfirst.p, (unsigned long long *) R->d_vfill.p, R->d_bucket.p);
         EX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ex_rank_kernel, dim3((unsigned) std::min<int64_t>(n_var, 65536)), dim3(EX_WAVE), 0, s, d_vfirst.p, n_var, d_bucket.p, d_entries.p,
-                           d_order.p, d_flen.p);
+        hipLaunchKernelGGL(ex_rank_kernel, dim3((unsigned) std::min<int64_t>(n_var, 65536)), dim3(EX_WAVE), 0, s, R->d_vfirst.p, n_var, R->d_bucket.p, R->d_entries.p,
+                           R->d_order.p, R->d_flen.p);
         EX_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(ex_scan_i64, dim3(1), dim3(1024), 0, s, d_flen.p, n_ent, d_foff.p);
+    hipLaunchKernelGGL(ex_scan_i64, dim3(1), dim3(1024), 0, s, R->d_flen.p, n_ent, R->d_foff.p);
     EX_HIP(hipGetLastError());
     if (n_ent > 0) {
-        hipLaunchKernelGGL(ex_gather_kernel, dim3((unsigned) std::min<int64_t>(n_ent, 65536)), dim3(EX_WAVE), 0, s, d_order.p, n_ent, d_entries.p, d_foff.p,
-                           g_seq, d_pool.p, d_fread.p);
+        hipLaunchKernelGGL(ex_gather_kernel, dim3((unsigned) std::min<int64_t>(n_ent, 65536)), dim3(EX_WAVE), 0, s, R->d_order.p, n_ent, R->d_entries.p, R->d_foff.p,
+                           g_seq, pool, base, R->d_fread.p);
         EX_HIP(hipGetLastError());
     }
-    EX_HIP(hipEventRecord(ev.e[3], s));
+    EX_HIP(hipEventRecord(R->ev[3], s));
+    R->t_dev2 = R->t_end = ex_now_ms();
+    return MRP_OK;
+}
+
+/* what the second half left on the device (valid until the run is destroyed) */
+void mrp_extract_run_device(const mrp_extract_run *R, mrp_extract_device *D) {
+    D->n_reads = R->n_reads;
+    D->n_variants = R->n_var;
+    D->n_entries = R->n_ent;
+    D->n_bases = R->n_bases;
+    D->read_status = R->d_status.p;
+    D->entry_first = R->d_vfirst.p;
+    D->entry_read = R->d_fread.p;
+    D->entry_len = R->d_flen.p;
+    D->entry_off = R->d_foff.p;
+    D->symbols = R->g_pool;
+    D->read_first = R->rb.data();
+    D->variant_first = R->vb.data();
+}
+
+int64_t mrp_extract_run_allele_bytes(const mrp_extract_run *R) {
+    int64_t n = 0;
+    for (const HostVec<uint8_t> &p : R->apool) n += (int64_t) p.size();
+    return n;
+}
+
+/* every chunk's allele strings one after the other into dst (mrp_extract_run_allele_bytes), and per allele of the call, in chunk
+ * then allele order, where its string lies in dst */
+void mrp_extract_run_alleles(const mrp_extract_run *R, uint8_t *dst, int64_t *allele_off, int32_t *allele_len) {
+    int64_t at = 0, ia = 0;
+    for (int64_t c = 0; c < R->n_chunks; c++) {
+        const std::vector<int64_t> &off = R->aoff[(size_t) c];
+        const HostVec<uint8_t> &p = R->apool[(size_t) c];
+        if (!p.empty()) memcpy(dst + at, p.data(), p.size());
+        for (size_t a = 0; a + 1 < off.size(); a++, ia++) {
+            allele_off[ia] = at + off[a];
+            allele_len[ia] = (int32_t) (off[a + 1] - off[a]);
+        }
+        at += (int64_t) p.size();
+    }
+}
+
+/* the events of the two halves and the counts; after the stream has drained.  total_ms ends where the second half was queued
+ * (a run that stops there) or where the download ended */
+int mrp_extract_run_stats(mrp_extract_run *R) {
+    mrp_extract_stats *stats = R->stats;
+    if (!stats) return MRP_OK;
+    float a = 0.f, b = 0.f;
+    EX_HIP(hipEventElapsedTime(&a, R->ev[0], R->ev[1]));
+    EX_HIP(hipEventElapsedTime(&b, R->ev[2], R->ev[3]));
+    stats->kernel_ms = (double) a + (double) b;
+    stats->bytes_uploaded = (int64_t) R->in_bytes;
+    stats->reads = R->n_reads;
+    stats->cigar_ops = R->n_ops;
+    for (int64_t c = 0; c < R->n_chunks; c++) stats->aligned_bases += R->aligned[(size_t) c];
+    stats->entries = R->n_ent;
+    return MRP_OK;
+}
+
+/* download and the per-chunk outputs */
+int mrp_extract_run_download(mrp_extract_run *R, mrp_extracted_chunk **out) {
+    const char *who = R->who;
+    hipStream_t s = R->s;
+    const int64_t n_chunks = R->n_chunks, n_reads = R->n_reads, n_var = R->n_var, n_ent = R->n_ent, n_bases = R->n_bases;
+    const mrp_aligned_chunk *chunks = R->chunks;
+    const std::vector<int64_t> &rb = R->rb, &vb = R->vb;
     /* back: per read status and count (the scan of the counts), per entry its variant CSR, read, length, pool offset, and the pool */
     const size_t b_status = 0, b_eoff = ex_align<int64_t>((size_t) n_reads), b_vfirst = b_eoff + 8 * ((size_t) n_reads + 1),
                  b_foff = b_vfirst + 8 * ((size_t) n_var + 1), b_flen = b_foff + 8 * ((size_t) n_ent + 1), b_fread = b_flen + 8 * (size_t) n_ent,
                  b_pool = b_fread + 4 * (size_t) n_ent, b_end = b_pool + (size_t) n_bases;
-    EX_HIP(h_back.reserve(b_end));
-    uint8_t *hk = (uint8_t *) h_back.p;
-    if (n_reads) EX_HIP(hipMemcpyAsync(hk + b_status, d_status.p, (size_t) n_reads, hipMemcpyDeviceToHost, s));
-    EX_HIP(hipMemcpyAsync(hk + b_eoff, d_eoff.p, 8 * ((size_t) n_reads + 1), hipMemcpyDeviceToHost, s));
-    EX_HIP(hipMemcpyAsync(hk + b_vfirst, d_vfirst.p, 8 * ((size_t) n_var + 1), hipMemcpyDeviceToHost, s));
-    EX_HIP(hipMemcpyAsync(hk + b_foff, d_foff.p, 8 * ((size_t) n_ent + 1), hipMemcpyDeviceToHost, s));
+    EX_HIP(R->h_back.reserve(b_end));
+    uint8_t *hk = (uint8_t *) R->h_back.p;
+    if (n_reads) EX_HIP(hipMemcpyAsync(hk + b_status, R->d_status.p, (size_t) n_reads, hipMemcpyDeviceToHost, s));
+    EX_HIP(hipMemcpyAsync(hk + b_eoff, R->d_eoff.p, 8 * ((size_t) n_reads + 1), hipMemcpyDeviceToHost, s));
+    EX_HIP(hipMemcpyAsync(hk + b_vfirst, R->d_vfirst.p, 8 * ((size_t) n_var + 1), hipMemcpyDeviceToHost, s));
+    EX_HIP(hipMemcpyAsync(hk + b_foff, R->d_foff.p, 8 * ((size_t) n_ent + 1), hipMemcpyDeviceToHost, s));
     if (n_ent) {
-        EX_HIP(hipMemcpyAsync(hk + b_flen, d_flen.p, 8 * (size_t) n_ent, hipMemcpyDeviceToHost, s));
-        EX_HIP(hipMemcpyAsync(hk + b_fread, d_fread.p, 4 * (size_t) n_ent, hipMemcpyDeviceToHost, s));
+        EX_HIP(hipMemcpyAsync(hk + b_flen, R->d_flen.p, 8 * (size_t) n_ent, hipMemcpyDeviceToHost, s));
+        EX_HIP(hipMemcpyAsync(hk + b_fread, R->d_fread.p, 4 * (size_t) n_ent, hipMemcpyDeviceToHost, s));
     }
-    if (n_bases) EX_HIP(hipMemcpyAsync(hk + b_pool, d_pool.p, (size_t) n_bases, hipMemcpyDeviceToHost, s));
+    if (n_bases) EX_HIP(hipMemcpyAsync(hk + b_pool, R->g_pool, (size_t) n_bases, hipMemcpyDeviceToHost, s));
     EX_HIP(hipStreamSynchronize(s));
-    const double t_dev2 = ex_now_ms();
+    R->t_dev2 = ex_now_ms();
     const uint8_t *k_status = hk + b_status;
     const int64_t *k_eoff = (const int64_t *) (hk + b_eoff), *k_vfirst = (const int64_t *) (hk + b_vfirst), *k_foff = (const int64_t *) (hk + b_foff),
                   *k_flen = (const int64_t *) (hk + b_flen);
     const int32_t *k_fread = (const int32_t *) (hk + b_fread);
     const uint8_t *k_pool = hk + b_pool;
 
-    /* ---- the outputs, per chunk */
     mrp_extracted_chunk *res = (mrp_extracted_chunk *) calloc((size_t) std::max<int64_t>(n_chunks, 1), sizeof(mrp_extracted_chunk));
     if (!res) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
     std::atomic<bool> nomem{false};
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
         const mrp_aligned_chunk &C = chunks[c];
+        const std::vector<ExWindow> &win = R->win[(size_t) c];
+        const std::vector<int64_t> &aoff = R->aoff[(size_t) c];
         mrp_extracted_chunk &X = res[c];
         const int64_t nv = C.n_variants, nr = C.n_reads, na = nv ? C.allele_first[nv] : 0;
         const int64_t e0 = k_vfirst[vb[(size_t) c]], e1 = k_vfirst[vb[(size_t) c + 1]], ne = e1 - e0;
-        const int64_t abytes = aoff[(size_t) c][(size_t) na], sbytes = k_foff[e1] - k_foff[e0];
+        const int64_t abytes = aoff[(size_t) na], sbytes = k_foff[e1] - k_foff[e0];
         auto mk = [&](size_t bytes) { void *p = malloc(bytes ? bytes : 1); if (!p) nomem = true; return p; };
         X.n_variants = nv;
         X.n_reads = nr;
@@ -703,16 +865,16 @@ int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_al
         X.pool = (uint8_t *) mk((size_t) X.pool_bytes);
         if (nomem) return;
         for (int64_t v = 0; v < nv; v++) {
-            X.ref_aln_start[v] = win[(size_t) c][(size_t) v].start;
-            X.ref_aln_stop_incl[v] = win[(size_t) c][(size_t) v].stop;
+            X.ref_aln_start[v] = win[(size_t) v].start;
+            X.ref_aln_stop_incl[v] = win[(size_t) v].stop;
             X.entry_first[v] = k_vfirst[vb[(size_t) c] + v] - e0;
         }
         X.entry_first[nv] = ne;
         if (nv) memcpy(X.allele_first, C.allele_first, 8 * ((size_t) nv + 1));
         else X.allele_first[0] = 0;
         for (int64_t a = 0; a < na; a++) {
-            X.allele_off[a] = aoff[(size_t) c][(size_t) a];
-            X.allele_len[a] = (int32_t) (aoff[(size_t) c][(size_t) a + 1] - aoff[(size_t) c][(size_t) a]);
+            X.allele_off[a] = aoff[(size_t) a];
+            X.allele_len[a] = (int32_t) (aoff[(size_t) a + 1] - aoff[(size_t) a]);
         }
         for (int64_t r = 0; r < nr; r++) {
             const int64_t g = rb[(size_t) c] + r;
@@ -724,39 +886,59 @@ int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_al
             X.entry_off[e] = abytes + k_foff[e0 + e] - k_foff[e0];
             X.entry_len[e] = (int32_t) k_flen[e0 + e];
         }
-        if (abytes) memcpy(X.pool, apool[(size_t) c].data(), (size_t) abytes);
+        if (abytes) memcpy(X.pool, R->apool[(size_t) c].data(), (size_t) abytes);
         if (sbytes) memcpy(X.pool + abytes, k_pool + k_foff[e0], (size_t) sbytes);
     });
     if (nomem) {
-        for (int64_t c = 0; c < n_chunks; c++) {
-            mrp_extracted_chunk &X = res[c];
-            void *ps[] = {X.ref_aln_start, X.ref_aln_stop_incl, X.allele_first, X.allele_off, X.allele_len, X.read_status,
-                          X.read_n_substrings, X.entry_first, X.entry_read, X.entry_off, X.entry_len, X.pool};
-            for (void *p : ps) free(p);
-        }
-        free(res);
+        ex_free_chunks(res, n_chunks);
         return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
     }
-    if (stats) {
-        float a = 0.f, b = 0.f;
-        EX_HIP(hipEventElapsedTime(&a, ev.e[0], ev.e[1]));
-        EX_HIP(hipEventElapsedTime(&b, ev.e[2], ev.e[3]));
-        stats->kernel_ms = (double) a + (double) b;
-        stats->bytes_uploaded = (int64_t) in_bytes;
-        stats->reads = n_reads;
-        stats->cigar_ops = n_ops;
-        for (int64_t c = 0; c < n_chunks; c++) stats->aligned_bases += aligned[(size_t) c];
-        stats->entries = n_ent;
-    }
-    d_in.release(); d_status.release(); d_pool.release(); d_ops.release(); d_state.release(); d_count.release(); d_eoff.release();
-    d_vcnt.release(); d_vfirst.release(); d_vfill.release(); d_flen.release(); d_foff.release(); d_tot.release(); d_entries.release();
-    d_bucket.release(); d_order.release(); d_fread.release();
-    ctx->pool.reclaim();
     *out = res;
-    if (stats) {
-        stats->total_ms = ex_now_ms() - t_begin;
-        stats->host_ms = stats->total_ms - (t_dev1 - t_dev0) - (t_dev2 - t_dev1);
+    return MRP_OK;
+}
+
+/* after the stream has drained: every device array back to the context's pool, at once reusable */
+void mrp_extract_run_release(mrp_extract_run *R) {
+    R->d_in.release(); R->d_status.release(); R->d_pool.release(); R->d_ops.release(); R->d_state.release(); R->d_count.release(); R->d_eoff.release();
+    R->d_vcnt.release(); R->d_vfirst.release(); R->d_vfill.release(); R->d_flen.release(); R->d_foff.release(); R->d_tot.release(); R->d_entries.release();
+    R->d_bucket.release(); R->d_order.release(); R->d_fread.release();
+    R->g_pool = nullptr;
+    if (R->ctx) R->ctx->pool.reclaim();
+}
+
+/* total_ms and host_ms of a run that has ended (t_end: now, or where the second half was queued) */
+void mrp_extract_run_times(mrp_extract_run *R, bool to_now) {
+    if (!R->stats) return;
+    R->stats->total_ms = (to_now ? ex_now_ms() : R->t_end) - R->t_begin;
+    R->stats->host_ms = R->stats->total_ms - (R->t_dev2 - R->t_dev0);
+}
+
+extern "C" {
+
+int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_extract_options *options,
+                                mrp_extracted_chunk **out, mrp_extract_stats *stats) {
+    mrp_extract_run run("mrp_extract_read_substrings", n_chunks, chunks, options, stats);
+    mrp_extract_run *R = &run;
+    int rc = mrp_extract_run_check_args(R, out != nullptr);
+    if (rc == MRP_OK) rc = mrp_extract_run_check_modes(R);
+    if (rc == MRP_OK) rc = mrp_extract_run_check_chunks(R);
+    if (rc != MRP_OK) return rc;
+    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction has no CPU fallback)", R->who);
+    *out = nullptr;
+    mrp_extracted_chunk *res = nullptr;
+    rc = mrp_extract_run_stage(R, ctx);
+    if (rc == MRP_OK) rc = mrp_extract_run_first_half(R);
+    if (rc == MRP_OK) rc = mrp_extract_run_totals(R, nullptr, nullptr);
+    if (rc == MRP_OK) rc = mrp_extract_run_second_half(R, nullptr, 0);
+    if (rc == MRP_OK) rc = mrp_extract_run_download(R, &res);
+    if (rc == MRP_OK) rc = mrp_extract_run_stats(R);
+    if (rc != MRP_OK) { /* (nothing is returned on error) */
+        ex_free_chunks(res, n_chunks);
+        return rc;
     }
+    mrp_extract_run_release(R);
+    *out = res;
+    mrp_extract_run_times(R, true);
     return MRP_OK;
 }
 
@@ -826,6 +1008,82 @@ int mrp_string_chunk_from_extracted(const mrp_extracted_chunk *x, const uint8_t 
     out->read_names = read_names;
     out->read_forward_strand = read_forward_strand;
     *bubble_variant = bv;
+    return MRP_OK;
+}
+
+int mrp_haptag_sites_from_extracted(int64_t n_chunks, const mrp_extracted_chunk *x, const int32_t *const *gt, mrp_haptag_sites *out, int64_t *read_first) {
+    static const char *who = "mrp_haptag_sites_from_extracted";
+    if (n_chunks < 0 || (n_chunks > 0 && (!x || !gt)) || !out || !read_first) return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
+    int64_t ns = 0, na = 0, ne = 0, nb = 0;
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const mrp_extracted_chunk &X = x[c];
+        const int64_t nv = X.n_variants;
+        if (nv < 0 || X.n_reads < 0 || X.pool_bytes < 0) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: bad sizes", who, (long long) c);
+        if (!X.allele_first || !X.entry_first || (X.n_reads > 0 && !X.read_status) || (X.pool_bytes > 0 && !X.pool) ||
+            (nv > 0 && (!gt[c] || !X.allele_off || !X.allele_len || (X.entry_first[nv] > 0 && (!X.entry_read || !X.entry_off || !X.entry_len)))))
+            return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null array", who, (long long) c);
+        for (int64_t v = 0; v < nv; v++) {
+            const int64_t k = X.allele_first[v + 1] - X.allele_first[v];
+            for (int w = 0; w < 2; w++)
+                if (gt[c][2 * v + w] < 0 || gt[c][2 * v + w] >= k)
+                    return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld, variant %lld: genotype %d outside its %lld alleles", who, (long long) c, (long long) v,
+                                         gt[c][2 * v + w], (long long) k);
+        }
+        for (int64_t e = 0; e < X.entry_first[nv]; e++) {
+            if (X.entry_read[e] < 0 || X.entry_read[e] >= X.n_reads)
+                return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: entry %lld names read %d", who, (long long) c, (long long) e, X.entry_read[e]);
+            ne += X.read_status[X.entry_read[e]] == MRP_READ_KEPT;
+        }
+        ns += nv;
+        na += X.allele_first[nv];
+        nb += X.pool_bytes;
+    }
+    /* one block: allele_first, entry_first (ns + 1 each), allele_off (na), entry_read, entry_off (ne each), then the int32 arrays
+     * allele_len (na), compare (2 ns), entry_len (ne), then the pool */
+    const size_t n64 = 2 * ((size_t) ns + 1) + (size_t) na + 2 * (size_t) ne, n32 = (size_t) na + 2 * (size_t) ns + (size_t) ne;
+    uint8_t *blk = (uint8_t *) malloc(8 * n64 + 4 * n32 + (size_t) nb + 8);
+    if (!blk) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
+    int64_t *a_first = (int64_t *) blk, *e_first = a_first + ns + 1, *a_off = e_first + ns + 1, *e_read = a_off + na, *e_off = e_read + ne;
+    int32_t *a_len = (int32_t *) (e_off + ne), *cmp = a_len + na, *e_len = cmp + 2 * ns;
+    uint8_t *pool = (uint8_t *) (e_len + ne);
+    int64_t s = 0, ia = 0, ie = 0, base = 0;
+    a_first[0] = e_first[0] = 0;
+    read_first[0] = 0;
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const mrp_extracted_chunk &X = x[c];
+        for (int64_t v = 0; v < X.n_variants; v++, s++) { /* a variant without entries is a site too: the partition skips it itself */
+            for (int64_t a = X.allele_first[v]; a < X.allele_first[v + 1]; a++, ia++) {
+                a_off[ia] = base + X.allele_off[a];
+                a_len[ia] = X.allele_len[a];
+            }
+            cmp[2 * s] = gt[c][2 * v];
+            cmp[2 * s + 1] = gt[c][2 * v + 1];
+            for (int64_t e = X.entry_first[v]; e < X.entry_first[v + 1]; e++) {
+                if (X.read_status[X.entry_read[e]] != MRP_READ_KEPT) continue; /* filteredReads == NULL: low-mapq reads are skipped (htsIntegration.c:1825) */
+                e_read[ie] = read_first[c] + X.entry_read[e];
+                e_off[ie] = base + X.entry_off[e];
+                e_len[ie] = X.entry_len[e];
+                ie++;
+            }
+            a_first[s + 1] = ia;
+            e_first[s + 1] = ie;
+        }
+        if (X.pool_bytes) memcpy(pool + base, X.pool, (size_t) X.pool_bytes);
+        base += X.pool_bytes;
+        read_first[c + 1] = read_first[c] + X.n_reads;
+    }
+    memset(out, 0, sizeof(*out));
+    out->n_sites = ns;
+    out->pool = pool;
+    out->pool_bytes = nb;
+    out->allele_first = a_first;
+    out->allele_off = a_off;
+    out->allele_len = a_len;
+    out->compare = cmp;
+    out->entry_first = e_first;
+    out->entry_read = e_read;
+    out->entry_off = e_off;
+    out->entry_len = e_len;
     return MRP_OK;
 }
 

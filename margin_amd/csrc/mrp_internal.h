@@ -566,6 +566,49 @@ static inline void mrp_filtered_out_clear(mrp_filtered_out *O) {
     free(O->read_hap); free(O->h1); free(O->h2); free(O->variant_state); free(O->cis); free(O->trans);
     memset(O, 0, sizeof(*O));
 }
+/* mrp_extract_read_substrings as one run taken through steps (mrp_extract.hip), so that a composite (mrp_haplotag_aligned_chunks,
+ * mrp_pairhmm.hip) can stop before the download and read the result where it lies in HBM:
+ *   check_args / check_modes / check_chunks   MRP_ERR_ARG for malformed arguments, MRP_ERR_UNSUPPORTED for the two refused modes, the
+ *                  chunks' own checks and the windows (host only; the entry decides their order);
+ *   stage          the call's reads, ops, bases and variants in one staging block, and its upload on ctx->stream;
+ *   first_half     scan, count; the one total starts on its way back;
+ *   totals         the allele strings on the worker pool beside the first half, then the wait for the total;
+ *   second_half    locate, sort by variant, gather: the symbols go to pool + base (a device pool of the caller's with room for
+ *                  n_bases behind base) or, with pool NULL, to a pool of the run's own;
+ *   download       everything back and the per-chunk outputs (mrp_extract_read_substrings only);
+ *   stats / times  the events and counts (after the stream has drained), then total_ms and host_ms;
+ *   release        every device array back to ctx's pool, which is reclaimed (after the stream has drained).
+ * The run keeps pointers into chunks[] and writes stats (zeroed by create; may be NULL). */
+struct mrp_extract_run;
+struct mrp_extract_device { /* what the second half leaves in HBM; read indices are global to the call */
+    int64_t n_reads, n_variants, n_entries, n_bases;
+    const uint8_t *read_status;  /* n_reads: MRP_READ_* */
+    const int64_t *entry_first;  /* n_variants + 1: the entry CSR by variant, entries in ascending read order */
+    const int32_t *entry_read;   /* per entry */
+    const int64_t *entry_len;
+    const int64_t *entry_off;    /* n_entries + 1: the scan of entry_len, from 0 */
+    const uint8_t *symbols;      /* entry e's symbols: symbols[entry_off[e] .. + entry_len[e]) (= pool + base) */
+    const int64_t *read_first, *variant_first; /* host, n_chunks + 1: chunk c's share of the call's reads / variants */
+};
+mrp_extract_run *mrp_extract_run_create(const char *who, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_extract_options *options,
+                                        mrp_extract_stats *stats);
+void mrp_extract_run_destroy(mrp_extract_run *run);
+int mrp_extract_run_check_args(mrp_extract_run *run, bool have_out);
+int mrp_extract_run_check_modes(mrp_extract_run *run);
+int mrp_extract_run_check_chunks(mrp_extract_run *run);
+int mrp_extract_run_stage(mrp_extract_run *run, mrp_context *ctx);
+int mrp_extract_run_first_half(mrp_extract_run *run);
+int mrp_extract_run_totals(mrp_extract_run *run, int64_t *n_entries, int64_t *n_bases);
+int mrp_extract_run_second_half(mrp_extract_run *run, uint8_t *pool, int64_t base);
+int mrp_extract_run_download(mrp_extract_run *run, mrp_extracted_chunk **out);
+int mrp_extract_run_stats(mrp_extract_run *run);
+void mrp_extract_run_times(mrp_extract_run *run, bool to_now);
+void mrp_extract_run_release(mrp_extract_run *run);
+void mrp_extract_run_device(const mrp_extract_run *run, mrp_extract_device *view);
+/* every chunk's allele strings (prefix + allele + suffix, symbols) one after the other: their bytes; the strings into dst and, per allele
+ * of the call in chunk then allele order, where each lies in dst */
+int64_t mrp_extract_run_allele_bytes(const mrp_extract_run *run);
+void mrp_extract_run_alleles(const mrp_extract_run *run, uint8_t *dst, int64_t *allele_off, int32_t *allele_len);
 extern "C" void mrp_batch_last_launch_ms(struct mrp_batch *b, float *pack, float *emission, float *recursion);
 
 /* development: MRP_DUP=<letters> launches the named kernel families of a resident level TWICE (they are idempotent) -- the slow-down of a

@@ -2,7 +2,9 @@
  * mrp_pairhmm.hip -- read x allele alignment likelihoods: the banded pair-HMM forward probability of the reference
  * (computeForwardProbability, impl/pairwiseAligner.c:849-903) for batches of string pairs, and the alleleReadSupports
  * loop around it (impl/bubbleGraph.c:1421-1464), and the filtered-read / filtered-variant loops after the phasing
- * (:1749-2351: the supports stay on the device, a scoring kernel reduces them).  gfx950 only; compiled with -ffp-contract=off.
+ * (:1749-2351: the supports stay on the device, a scoring kernel reduces them), the string-chunk calls built on them and, at the end
+ * of the file, the haplotagging of aligned reads from a phased VCF over the extraction's result in HBM (ha_owners_kernel,
+ * mrp_haplotag_aligned_chunks).  gfx950 only; compiled with -ffp-contract=off.
  *
  * The recursion (stateMachine3_cellCalculate, impl/stateMachine.c:562-586) gives every dp cell (x, y) three states from
  * its neighbours (x-1, y), (x-1, y-1), (x, y-1); a neighbour outside the band contributes nothing, which is what a
@@ -708,8 +710,10 @@ int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, 
 }
 
 /* The device half: uploads what phm_classify made of n_pairs pairs over pool and queues the kernels on ctx->stream;
- * ctx->ev[0] is recorded before the first kernel. */
-int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64_t n_pairs, const PhmLaunch &H, PhmDev &L, mrp_pairhmm_stats *stats) {
+ * ctx->ev[0] is recorded before the first kernel.  device_pool (optional): the symbols are already on the device, written by work
+ * queued on ctx->stream before this call; nothing is uploaded for them and pool is not read. */
+int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64_t n_pairs, const PhmLaunch &H, PhmDev &L, mrp_pairhmm_stats *stats,
+                const uint8_t *device_pool = nullptr) {
     const int n_models = H.n_models, table_bytes = H.table_bytes;
     const bool has_switch = H.has_switch;
     const HostVec<PhmLanePair> *lane_pairs = H.lane_pairs;
@@ -720,8 +724,11 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
     L.d_models.pool = L.d_pool.pool = L.d_band.pool = L.d_out.pool = &ctx->pool;
     L.s = s; /* from here on the destructor drains the stream */
     PHM_HIP(L.d_models.upload(H.hm, s));
-    PHM_HIP(L.d_pool.alloc((size_t) pool_bytes));
-    if (pool_bytes) PHM_HIP(hipMemcpyAsync(L.d_pool.p, pool, (size_t) pool_bytes, hipMemcpyHostToDevice, s));
+    if (!device_pool) {
+        PHM_HIP(L.d_pool.alloc((size_t) pool_bytes));
+        if (pool_bytes) PHM_HIP(hipMemcpyAsync(L.d_pool.p, pool, (size_t) pool_bytes, hipMemcpyHostToDevice, s));
+        device_pool = L.d_pool.p;
+    }
     PHM_HIP(L.d_band.upload(band, s));
     PHM_HIP(L.d_out.alloc((size_t) n_pairs));
     for (int c = 0; c < 4; c++) {
@@ -751,10 +758,10 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
         const size_t lds = (size_t) table_bytes + (size_t) nw * row_bytes;
         const int64_t per_wg = (int64_t) nw * PHM_WAVE;
         if (has_switch)
-            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, true>), dim3((unsigned) ((n + per_wg - 1) / per_wg)), dim3((unsigned) per_wg), lds, s, L.d_lane[c].p, n, L.d_pool.p,
+            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, true>), dim3((unsigned) ((n + per_wg - 1) / per_wg)), dim3((unsigned) per_wg), lds, s, L.d_lane[c].p, n, device_pool,
                                L.d_models.p, (int) n_models, cap, L.d_out.p);
         else
-            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, false>), dim3((unsigned) ((n + per_wg - 1) / per_wg)), dim3((unsigned) per_wg), lds, s, L.d_lane[c].p, n, L.d_pool.p,
+            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, false>), dim3((unsigned) ((n + per_wg - 1) / per_wg)), dim3((unsigned) per_wg), lds, s, L.d_lane[c].p, n, device_pool,
                                L.d_models.p, (int) n_models, cap, L.d_out.p);
         PHM_HIP(hipGetLastError());
         if (stats) stats->pairs_lane += n;
@@ -764,7 +771,7 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
         if (n == 0) continue;
         const int W = WAVE_CLASS_CAP[c];
         const size_t lds = (size_t) 9 * W * sizeof(double);
-        hipLaunchKernelGGL(phm_wave_kernel, dim3((unsigned) std::min<int64_t>(n, 16384)), dim3(PHM_WAVE), lds, s, L.d_wave[c].p, n, L.d_pool.p,
+        hipLaunchKernelGGL(phm_wave_kernel, dim3((unsigned) std::min<int64_t>(n, 16384)), dim3(PHM_WAVE), lds, s, L.d_wave[c].p, n, device_pool,
                            L.d_models.p, L.d_band.p, W, L.d_out.p);
         PHM_HIP(hipGetLastError());
         if (stats) stats->pairs_wave += n;
@@ -836,6 +843,56 @@ void substring_owners(int64_t n_groups, const int64_t *first, const uint8_t *poo
             i = j;
         }
     });
+}
+
+/* cachedScores of bubbleGraph_partitionFilteredReadsFromPhasedVcfEntries (bubbleGraph.c:2044-2072) on the device, over the arrays the
+ * extraction left in HBM (mrp_extract_device): a wave per site, a lane per entry with a lane stride (a site may hold more entries than
+ * a wave has lanes).  An entry takes part if its read is MRP_READ_KEPT; owner[p] = the LAST entry of the site that takes part and has
+ * p's substring (b->reads is filled by popping, :2012-2014), p itself if none follows, -1 for an entry that takes no part.  Pass one
+ * gives every entry a key (length, hash of the symbols); pass two walks the site from its end and compares symbols wherever the keys
+ * agree: the hash only skips comparisons.  Every loop is bounded by the site's entry count or the substring's length; the barrier
+ * between the passes is the wave's own workgroup's, and both passes of a site are run by the same wave. */
+constexpr uint64_t HA_NO_KEY = ~0ull;
+__global__ void __launch_bounds__(PHM_WAVE) ha_owners_kernel(const int64_t *__restrict__ first, int64_t n_sites, const int32_t *__restrict__ read,
+                                                             const uint8_t *__restrict__ status, const int64_t *__restrict__ len,
+                                                             const int64_t *__restrict__ off, const uint8_t *__restrict__ sym, uint64_t *key,
+                                                             int32_t *__restrict__ owner) {
+    const int lane = threadIdx.x;
+    for (int64_t v = blockIdx.x; v < n_sites; v += gridDim.x) {
+        const int64_t a = first[v], b = first[v + 1];
+        for (int64_t p = a + lane; p < b; p += PHM_WAVE) {
+            uint64_t k = HA_NO_KEY;
+            if (status[read[p]] == MRP_READ_KEPT) {
+                const uint8_t *x = sym + off[p];
+                const int64_t n = len[p];
+                uint32_t h = 2166136261u;
+                for (int64_t i = 0; i < n; i++) h = (h ^ x[i]) * 16777619u;
+                k = (uint64_t) n << 32 | h;
+            }
+            key[p] = k;
+        }
+        __syncthreads();
+        for (int64_t p = a + lane; p < b; p += PHM_WAVE) {
+            const uint64_t k = key[p];
+            int32_t o = -1;
+            if (k != HA_NO_KEY) {
+                o = (int32_t) p;
+                const uint8_t *x = sym + off[p];
+                const int64_t n = len[p];
+                for (int64_t q = b - 1; q > p; q--) {
+                    if (key[q] != k) continue;
+                    const uint8_t *y = sym + off[q];
+                    int64_t i = 0;
+                    while (i < n && x[i] == y[i]) i++;
+                    if (i == n) {
+                        o = (int32_t) q;
+                        break;
+                    }
+                }
+            }
+            owner[p] = o;
+        }
+    }
 }
 
 /* stMath_logAddExact (sonLib), as mrp_kernels.hip and rphmm_frame.c state it */
@@ -2512,3 +2569,289 @@ int mrp_phase_string_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, co
 }
 
 }  // extern "C"
+
+/* ---- mrp_haplotag_aligned_chunks: the staged extraction (mrp_internal.h) with the partition of mrp_partition_reads_by_haplotype reading
+ * its result where it lies in HBM.  One device pool holds the call's allele strings, then the substrings the
+ * gather writes behind them; the owners of equal substrings are found there (ha_owners_kernel); the host gets per entry its read, length
+ * and owner and per read its status, and makes from them what needs no symbol: the pair list (ht_build_pairs' order), the launch classes
+ * (phm_classify reads offsets and lengths only for unanchored pairs) and the per-read entry lists of ht_partition_kernel. */
+namespace {
+
+struct HaRun {
+    static constexpr const char *who = "mrp_haplotag_aligned_chunks";
+    mrp_context *const ctx;
+    const int64_t n_chunks;
+    const mrp_aligned_chunk *const chunks;
+    const int32_t *const *const gt;
+    mrp_haplotag_aligned_stats *const stats;
+    mrp_extract_run *X = nullptr;
+    hipStream_t s = nullptr; /* set once the device is current: from then on the destructor drains it */
+    hipEvent_t ev[2] = {nullptr, nullptr}; /* around the owners kernel */
+    mrp_extract_device D{};
+    int64_t allele_bytes = 0, pool_bytes = 0, n_alleles = 0, downloaded = 0;
+    PinnedBuf h_sym, h_back, h_res;
+    HostVec<int64_t> a_off, y_off, first;
+    HostVec<int32_t> a_len;
+    HostVec<uint8_t> forward;
+    HostVec<HtEntry> ent;
+    HtPairs P;
+    PhmLaunch H;
+    PhmDev L; /* L.d_out holds the log probabilities the partition kernel reads */
+    DevBuf<uint8_t> d_sym;
+    DevBuf<uint64_t> d_key;
+    DevBuf<int32_t> d_owner, d_hap;
+    DevBuf<int64_t> d_first;
+    DevBuf<HtEntry> d_ent;
+    DevBuf<double> d_h;
+    /* what came back after the owners kernel */
+    const uint8_t *k_status = nullptr;
+    const int64_t *k_first = nullptr, *k_len = nullptr;
+    const int32_t *k_read = nullptr, *k_owner = nullptr;
+
+    HaRun(mrp_context *c, int64_t n, const mrp_aligned_chunk *ch, const int32_t *const *g, mrp_haplotag_aligned_stats *st)
+        : ctx(c), n_chunks(n), chunks(ch), gt(g), stats(st) {}
+    ~HaRun() {
+        if (s) (void) hipStreamSynchronize(s);
+        for (hipEvent_t x : ev)
+            if (x) (void) hipEventDestroy(x);
+        mrp_extract_run_destroy(X);
+    }
+    int check(const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+              int8_t *const *hap_out, double *const *h1_out, double *const *h2_out);
+    int extract();
+    int owners();
+    int pairs();
+    int score(const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion);
+    int hand_over(int8_t *const *hap_out, double *const *h1_out, double *const *h2_out);
+};
+
+/* every MRP_ERR_ARG of the call, then the two refused modes: nothing here looks at the context */
+int HaRun::check(const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                 int8_t *const *hap_out, double *const *h1_out, double *const *h2_out) {
+    X = mrp_extract_run_create(who, n_chunks, chunks, options, stats ? &stats->extract : nullptr);
+    if (!X) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
+    int rc = mrp_extract_run_check_args(X, true);
+    if (rc == MRP_OK) rc = mrp_extract_run_check_chunks(X);
+    if (rc != MRP_OK) return rc;
+    if (!forward_model || !reverse_model || (n_chunks > 0 && (!gt || !hap_out))) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const mrp_aligned_chunk &C = chunks[c];
+        if (C.n_reads > 0 && (!hap_out[c] || (h1_out && !h1_out[c]) || (h2_out && !h2_out[c])))
+            return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null output array", who, (long long) c);
+        if (C.n_variants > 0 && !gt[c]) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null genotypes", who, (long long) c);
+        for (int64_t v = 0; v < C.n_variants; v++) {
+            const int64_t k = C.allele_first[v + 1] - C.allele_first[v];
+            for (int w = 0; w < 2; w++)
+                if (gt[c][2 * v + w] < 0 || gt[c][2 * v + w] >= k)
+                    return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld, variant %lld: genotype %d outside its %lld alleles", who, (long long) c, (long long) v,
+                                         gt[c][2 * v + w], (long long) k);
+        }
+    }
+    return mrp_extract_run_check_modes(X);
+}
+
+/* the extraction up to its second half, gathering behind the allele strings in the call's one device pool */
+int HaRun::extract() {
+    int rc = mrp_extract_run_stage(X, ctx);
+    if (rc != MRP_OK) return rc;
+    s = ctx->stream;
+    d_sym.pool = d_key.pool = d_owner.pool = d_hap.pool = d_first.pool = d_ent.pool = d_h.pool = &ctx->pool;
+    for (hipEvent_t &x : ev) PHM_HIP(hipEventCreate(&x));
+    rc = mrp_extract_run_first_half(X);
+    int64_t n_ent = 0, n_bases = 0;
+    if (rc == MRP_OK) rc = mrp_extract_run_totals(X, &n_ent, &n_bases);
+    if (rc != MRP_OK) return rc;
+    downloaded += 16;
+    allele_bytes = mrp_extract_run_allele_bytes(X);
+    pool_bytes = allele_bytes + n_bases;
+    for (int64_t c = 0; c < n_chunks; c++) n_alleles += chunks[c].n_variants ? chunks[c].allele_first[chunks[c].n_variants] : 0;
+    a_off.resize((size_t) n_alleles);
+    a_len.resize((size_t) n_alleles);
+    PHM_HIP(h_sym.reserve(std::max<size_t>((size_t) allele_bytes, 1)));
+    mrp_extract_run_alleles(X, (uint8_t *) h_sym.p, a_off.data(), a_len.data());
+    PHM_HIP(d_sym.alloc((size_t) pool_bytes));
+    if (allele_bytes) PHM_HIP(hipMemcpyAsync(d_sym.p, h_sym.p, (size_t) allele_bytes, hipMemcpyHostToDevice, s));
+    rc = mrp_extract_run_second_half(X, d_sym.p, allele_bytes);
+    if (rc != MRP_OK) return rc;
+    mrp_extract_run_device(X, &D);
+    return MRP_OK;
+}
+
+/* the owners on the device; back come the per-read status and per entry its read, length and owner -- not the symbols */
+int HaRun::owners() {
+    const int64_t n_ent = D.n_entries, n_var = D.n_variants, n_reads = D.n_reads;
+    PHM_HIP(d_key.alloc((size_t) n_ent));
+    PHM_HIP(d_owner.alloc((size_t) n_ent));
+    PHM_HIP(hipEventRecord(ev[0], s));
+    if (n_ent > 0) {
+        hipLaunchKernelGGL(ha_owners_kernel, dim3((unsigned) std::min<int64_t>(n_var, 65536)), dim3(PHM_WAVE), 0, s, D.entry_first, n_var, D.entry_read,
+                           D.read_status, D.entry_len, D.entry_off, D.symbols, d_key.p, d_owner.p);
+        PHM_HIP(hipGetLastError());
+    }
+    PHM_HIP(hipEventRecord(ev[1], s));
+    const size_t b_first = 0, b_len = b_first + 8 * ((size_t) n_var + 1), b_read = b_len + 8 * (size_t) n_ent, b_owner = b_read + 4 * (size_t) n_ent,
+                 b_status = b_owner + 4 * (size_t) n_ent, b_end = b_status + (size_t) n_reads;
+    PHM_HIP(h_back.reserve(b_end));
+    uint8_t *hk = (uint8_t *) h_back.p;
+    PHM_HIP(hipMemcpyAsync(hk + b_first, D.entry_first, 8 * ((size_t) n_var + 1), hipMemcpyDeviceToHost, s));
+    if (n_ent) {
+        PHM_HIP(hipMemcpyAsync(hk + b_len, D.entry_len, 8 * (size_t) n_ent, hipMemcpyDeviceToHost, s));
+        PHM_HIP(hipMemcpyAsync(hk + b_read, D.entry_read, 4 * (size_t) n_ent, hipMemcpyDeviceToHost, s));
+        PHM_HIP(hipMemcpyAsync(hk + b_owner, d_owner.p, 4 * (size_t) n_ent, hipMemcpyDeviceToHost, s));
+    }
+    if (n_reads) PHM_HIP(hipMemcpyAsync(hk + b_status, D.read_status, (size_t) n_reads, hipMemcpyDeviceToHost, s));
+    PHM_HIP(hipStreamSynchronize(s));
+    downloaded += (int64_t) b_end;
+    k_first = (const int64_t *) (hk + b_first);
+    k_len = (const int64_t *) (hk + b_len);
+    k_read = (const int32_t *) (hk + b_read);
+    k_owner = (const int32_t *) (hk + b_owner);
+    k_status = hk + b_status;
+    return MRP_OK;
+}
+
+/* on the host, from indices and lengths alone: the two pairs of every owner at an active site in ht_build_pairs' order (the model from
+ * the owner's strand), and every read's entries in site order */
+int HaRun::pairs() {
+    const int64_t n_ent = D.n_entries, n_var = D.n_variants, n_reads = D.n_reads;
+    y_off.resize((size_t) n_ent);
+    int64_t at = allele_bytes;
+    for (int64_t p = 0; p < n_ent; p++) { y_off[(size_t) p] = at; at += k_len[p]; }
+    forward.resize((size_t) n_reads);
+    for (int64_t c = 0; c < n_chunks; c++)
+        for (int64_t r = 0; r < chunks[c].n_reads; r++) forward[(size_t) (D.read_first[c] + r)] = (chunks[c].flag[r] & 0x10) == 0;
+    std::vector<uint8_t> active((size_t) n_var, 0);
+    P.pair_of.assign((size_t) n_ent, -1);
+    first.assign((size_t) n_reads + 1, 0);
+    int64_t n_active = 0, n_scored = 0, n_owners = 0, abase = 0;
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const mrp_aligned_chunk &C = chunks[c];
+        for (int64_t v = 0; v < C.n_variants; v++) {
+            const int64_t g = D.variant_first[c] + v;
+            if (gt[c][2 * v] == gt[c][2 * v + 1]) continue; /* bubbleGraph.c:1975 */
+            int64_t k = 0;
+            for (int64_t p = k_first[g]; p < k_first[g + 1]; p++)
+                if (k_owner[p] >= 0) { k++; first[(size_t) k_read[p] + 1]++; }
+            if (!k) continue; /* :1989 */
+            active[(size_t) g] = 1;
+            n_active++;
+            n_scored += k;
+            for (int64_t p = k_first[g]; p < k_first[g + 1]; p++) {
+                if (k_owner[p] != p) continue;
+                n_owners++;
+                P.pair_of[(size_t) p] = P.list.size();
+                for (int w = 0; w < 2; w++) { /* never anchored (:2027) */
+                    const int64_t j = abase + C.allele_first[v] + gt[c][2 * v + w];
+                    P.list.add(a_off[(size_t) j], a_len[(size_t) j], y_off[(size_t) p], (int32_t) k_len[p], forward[(size_t) k_read[p]] ? 0 : 1, nullptr);
+                }
+            }
+        }
+        abase += C.n_variants ? C.allele_first[C.n_variants] : 0;
+    }
+    for (int64_t r = 0; r < n_reads; r++) first[(size_t) r + 1] += first[(size_t) r];
+    ent.resize((size_t) first[(size_t) n_reads]);
+    std::vector<int64_t> fill(first.begin(), first.end() - 1);
+    for (int64_t g = 0; g < n_var; g++) {
+        if (!active[(size_t) g]) continue;
+        for (int64_t p = k_first[g + 1] - 1; p >= k_first[g]; p--) { /* b->reads order (:2076) */
+            if (k_owner[p] < 0) continue;
+            const int64_t q = P.pair_of[(size_t) k_owner[p]];
+            ent[(size_t) fill[(size_t) k_read[p]]++] = HtEntry{(int32_t) q, (int32_t) q + 1, 0, 0};
+        }
+    }
+    if (stats) {
+        stats->sites = n_var;
+        stats->active_sites = n_active;
+        stats->entries = n_scored;
+        stats->owners = n_owners;
+    }
+    return MRP_OK;
+}
+
+/* the pair-HMM kernels over the pool that is already on the device, then a lane per read over its entries; the results on their way back */
+int HaRun::score(const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion) {
+    const int64_t n_reads = D.n_reads;
+    mrp_pairhmm_stats *pst = stats ? &stats->pairhmm : nullptr;
+    const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
+    if (P.list.size() > 0) { /* (MRP_ERR_UNSUPPORTED for a diagonal beyond the limit is raised by phm_classify, before anything is launched) */
+        int rc = phm_classify(who, models, 2, pool_bytes, P.list.view(), expansion, 0, 0, H);
+        if (rc == MRP_OK) rc = phm_enqueue(ctx, nullptr, pool_bytes, P.list.size(), H, L, pst, d_sym.p);
+        if (rc != MRP_OK) return rc;
+    } else {
+        if (stats) PHM_HIP(hipStreamSynchronize(s));
+        PHM_HIP(hipEventRecord(ctx->ev[0], s));
+    }
+    PHM_HIP(d_first.upload(first, s));
+    PHM_HIP(d_ent.upload(ent, s));
+    PHM_HIP(d_hap.alloc((size_t) n_reads));
+    PHM_HIP(d_h.alloc(2 * (size_t) n_reads));
+    if (n_reads > 0) {
+        hipLaunchKernelGGL(ht_partition_kernel, dim3((unsigned) ((n_reads + 255) / 256)), dim3(256), 0, s, d_first.p, d_ent.p, L.d_out.p, n_reads, d_hap.p, d_h.p,
+                           d_h.p + n_reads);
+        PHM_HIP(hipGetLastError());
+    }
+    PHM_HIP(hipEventRecord(ctx->ev[1], s));
+    PHM_HIP(h_res.reserve(std::max<size_t>(20 * (size_t) n_reads, 1)));
+    if (n_reads > 0) {
+        PHM_HIP(hipMemcpyAsync(h_res.p, d_h.p, 16 * (size_t) n_reads, hipMemcpyDeviceToHost, s));
+        PHM_HIP(hipMemcpyAsync((uint8_t *) h_res.p + 16 * (size_t) n_reads, d_hap.p, 4 * (size_t) n_reads, hipMemcpyDeviceToHost, s));
+    }
+    PHM_HIP(hipStreamSynchronize(s));
+    downloaded += 20 * n_reads;
+    return MRP_OK;
+}
+
+/* after the stream has drained: the outputs per chunk, the stats, the device arrays back to the pool */
+int HaRun::hand_over(int8_t *const *hap_out, double *const *h1_out, double *const *h2_out) {
+    const int64_t n_reads = D.n_reads;
+    const double *k_h1 = (const double *) h_res.p, *k_h2 = k_h1 + n_reads;
+    const int32_t *k_hap = (const int32_t *) (k_h2 + n_reads);
+    if (stats) {
+        float ms = 0.f;
+        PHM_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        stats->pairhmm.kernel_ms = ms;
+        stats->pairhmm.cells = H.cells;
+        PHM_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        stats->owners_ms = ms;
+        stats->bytes_downloaded = downloaded;
+        const int rc = mrp_extract_run_stats(X);
+        if (rc != MRP_OK) return rc;
+        mrp_extract_run_times(X, false);
+    }
+    for (int64_t c = 0; c < n_chunks; c++)
+        for (int64_t r = 0; r < chunks[c].n_reads; r++) {
+            const int64_t g = D.read_first[c] + r;
+            const bool kept = k_status[g] == MRP_READ_KEPT;
+            hap_out[c][r] = kept ? (int8_t) k_hap[g] : (int8_t) -1;
+            if (h1_out) h1_out[c][r] = kept ? k_h1[g] : 0.0;
+            if (h2_out) h2_out[c][r] = kept ? k_h2[g] : 0.0;
+        }
+    d_sym.release(); d_key.release(); d_owner.release(); d_hap.release(); d_first.release(); d_ent.release(); d_h.release();
+    L.d_models.release(); L.d_band.release(); L.d_out.release();
+    for (int c = 0; c < 4; c++) { L.d_lane[c].release(); L.d_wave[c].release(); }
+    mrp_extract_run_release(X); /* (reclaims the context's pool) */
+    return MRP_OK;
+}
+
+}  // namespace
+
+extern "C" int mrp_haplotag_aligned_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const int32_t *const *gt,
+                                           const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                                           int64_t expansion, int8_t *const *hap_out, double *const *h1_out, double *const *h2_out,
+                                           mrp_haplotag_aligned_stats *stats) {
+    const double t_begin = now_ms();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    HaRun R(ctx, n_chunks, chunks, gt, stats);
+    int rc = R.check(options, forward_model, reverse_model, expansion, hap_out, h1_out, h2_out);
+    if (rc != MRP_OK) return rc;
+    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction and the pair-HMM have no CPU fallback)", HaRun::who);
+    rc = R.extract();
+    if (rc == MRP_OK) rc = R.owners();
+    if (rc == MRP_OK) rc = R.pairs();
+    if (rc == MRP_OK) rc = R.score(forward_model, reverse_model, expansion);
+    if (rc == MRP_OK) rc = R.hand_over(hap_out, h1_out, h2_out);
+    if (rc != MRP_OK) return rc;
+    if (stats) stats->total_ms = now_ms() - t_begin;
+    return MRP_OK;
+}
