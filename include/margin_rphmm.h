@@ -471,6 +471,18 @@ int mrp_band_diagonals(const int64_t *anchors, int64_t n_anchors, int64_t lx, in
 /* getKmerAlignmentAnchors (pairwiseAligner.c:1519-1627, KMER_SIZE = 20): the chain of shared 20-mers the reference anchors
  * long (structural variant) alleles with; out receives at most ly - 19 (x, y) pairs, the count is returned (host only) */
 int64_t mrp_kmer_alignment_anchors(const uint8_t *x, int64_t lx, const uint8_t *y, int64_t ly, int64_t *out);
+/* getKmerAlignmentAnchors (pairwiseAligner.c:1519-1627) for n_pairs pairs on the device, all in one set of launches: pair i is x =
+ * pool[x_off[i] .. + x_len[i]), y likewise.  For every 20-mer of y, in order of y, the first position in x with the same 20 symbols
+ * (byte equality; getKmers :1543-1555 keeps the first occurrence); over these matches the chain with increasing x (:1580-1600: a match
+ * scores 1 + the best earlier match with smaller x, the walk back stops behind the first such match that was a running maximum,
+ * :1592, and a match becomes the running maximum on >=, :1596); the trace back from the last maximum as (x + 10, y + 10), ascending
+ * (:1605-1617).  A pair with lx < 20 or ly < 20 has no anchors (:1567).  anchor_off_out[n_pairs + 1] from 0, *anchors_out malloc'd
+ * (mrp_free) pairs of int64 (x, y); equal, pair by pair, to mrp_kmer_alignment_anchors.  What returns from the device is a count per
+ * pair and the anchors, as diagonal runs (x, y, length) the host expands.  MRP_ERR_ARG (NULL arrays, an offset or length outside the pool) before the context is looked at, then
+ * MRP_ERR_NO_DEVICE; on an error nothing is written.  stats (may be NULL): kernel_ms, total_ms. */
+int mrp_kmer_alignment_anchors_many(mrp_context *ctx, int64_t n_pairs, const uint8_t *pool, int64_t pool_bytes, const int64_t *x_off,
+                                    const int32_t *x_len, const int64_t *y_off, const int32_t *y_len, int64_t *anchor_off_out,
+                                    int64_t **anchors_out, mrp_pairhmm_stats *stats);
 /* computeForwardProbability for n_pairs (x, y) string pairs stored in one pool of symbols.  model_index (NULL: all 0)
  * selects models[i] per pair; anchor_off (NULL: no anchors anywhere) holds n_pairs + 1 offsets into anchors (pairs of
  * int64).  A pair without anchors covers its whole matrix, as in the reference.  out[i] = log probability (0.0 for two
@@ -853,6 +865,53 @@ int mrp_haplotag_aligned_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_al
                                 const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
                                 int64_t expansion, int8_t *const *hap_out, double *const *h1_out, double *const *h2_out,
                                 mrp_haplotag_aligned_stats *stats);
+
+/* ---- from alignments to haplotypes and HP tags of the primary reads -------------------------------------------------------
+ * The front of margin phase's chunk loop (phase.c:337-401) in one call: updateVcfEntriesWithSubstringsAndPositions and
+ * extractReadSubstringsAtVariantPositions (:337-357), the caller's downsampling as a mask (:360-382),
+ * bubbleGraph_constructFromVCFAndBamChunkReadVcfEntrySubstrings (:395, bubbleGraph.c:1338-1464), the phasing and the HP tags
+ * (:396-401).  The substrings' symbols never leave the device: the extraction gathers them behind the allele strings in one device
+ * pool, the owners of equal substrings (bubbleGraph.c:1418,1431-1441) and the k-mer anchors of the pairs with a string longer than
+ * sv_threshold (:1448-1451) are found there, and the pair-HMM reads the pool where it lies. */
+typedef struct mrp_phase_aligned_stats {
+    mrp_extract_stats extract;      /* the extraction's half; total_ms and host_ms end where its second half has been queued */
+    mrp_string_chunks_stats chunks; /* as mrp_phase_string_chunks fills it; total_ms and host_ms cover the whole call */
+    int64_t variants;               /* variants of the call */
+    int64_t bubbles;                /* of these, the ones with an entry that takes part */
+    int64_t entries;                /* substrings the extraction made */
+    int64_t entries_used;           /* of these, the ones of kept reads the mask lets through: the bubbles' substrings */
+    int64_t owners;                 /* of these, the ones that are scored (one pair per allele of the bubble) */
+    int64_t pairs;                  /* pairs in the one pair-HMM launch */
+    int64_t pairs_anchored;         /* of these, the ones with a string longer than sv_threshold: what the anchors kernel ran over */
+    int64_t anchors;                /* anchors it found */
+    int64_t anchor_runs;            /* the diagonal runs (x, y, length) they came back as */
+    int64_t front_bytes_downloaded; /* everything that came back before the pair-HMM launch: 16 B of totals, the entry CSR (8 B per
+                                     * variant + 8), 16 B per entry, 1 B per read, 4 B per anchored pair and 12 B per anchor run */
+    double owners_ms;               /* HIP events around the owners kernel */
+    double anchors_ms;              /* HIP events around the two anchors kernels */
+    double total_ms;                /* host wall time of the call */
+} mrp_phase_aligned_stats;
+
+/* For every chunk exactly what this chain returns: mrp_extract_read_substrings (same options, quirks and refusals) ->
+ * mrp_string_chunk_from_extracted(x, keep[c], read_names[c], strand from flag & 0x10) -> mrp_phase_string_chunks, bit for bit:
+ * out[c], hap_out[c][r] for all n_reads reads of the chunk (-1 for a read that is dropped, filtered, masked out or in no bubble),
+ * phred_out (optional), profiles_out (optional) and bubble_variant_out (optional; per chunk a malloc'd array, mrp_free, of the
+ * variant of each of the chunk's bubbles, vcfEntriesToBubbleIdx, closed by a -1: its length is the bubble count).  keep: NULL, or per chunk NULL / n_reads bytes; a read takes part
+ * if it is MRP_READ_KEPT and its byte is set.  In the extraction's ascending entry order the LAST entry of a variant that takes part
+ * owns the scores of its substring (the bubble lists its substrings popped, :1391-1393, and the first listed owns, :1431-1441); a
+ * variant left without an entry that takes part makes no bubble (:1366-1371).
+ * Errors, in this order: MRP_ERR_ARG before the context is looked at (the extraction's checks; NULL models, params, out, hap_out,
+ * hap_out[c] / phred_out[c] / read_names[c] / a read name for a chunk with reads; an odd or negative expansion);
+ * MRP_ERR_UNSUPPORTED for the SV split mode or run-length encoding, without a context too; MRP_ERR_NO_DEVICE for a NULL context;
+ * MRP_ERR_UNSUPPORTED for a pair whose widest diagonal exceeds 2 048 cells, raised before any pair-HMM kernel is launched (and
+ * MRP_ERR_ARG there for a bubble of more than 65 535 alleles, as the string call).  On an error nothing is returned.  Parameters
+ * outside the resident range take the per-chunk path as in the string call (stats->chunks.phase.resident = 0).  stats may be NULL. */
+int mrp_phase_aligned_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const char *const *const *read_names,
+                             const uint8_t *const *keep, const mrp_extract_options *options, const mrp_pair_hmm *forward_model,
+                             const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
+                             const mrp_params *params, int64_t min_phred, mrp_phase_result **out, int8_t *const *hap_out,
+                             double *const *phred_out, mrp_profile_out *profiles_out, int64_t **bubble_variant_out,
+                             mrp_phase_aligned_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "mrp_extract_read_substrings", "mrp_string_chunk_from_extracted", "mrp_string_chunk_units", "mrp_queue_phase_string_chunks",
     "mrp_phase_string_chunks_on_devices", "mrp_phase_string_chunks_with_filtered", "mrp_queue_phase_string_chunks_with_filtered",
     "mrp_phase_string_chunks_with_filtered_on_devices", "mrp_haptag_sites_from_extracted", "mrp_haplotag_aligned_chunks",
+    "mrp_kmer_alignment_anchors_many", "mrp_phase_aligned_chunks",
 ]
 
 
@@ -289,6 +290,12 @@ class HaplotagAlignedStats(C.Structure):
                 ("owners", C.c_int64), ("bytes_downloaded", C.c_int64), ("owners_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class PhaseAlignedStats(C.Structure):
+    _fields_ = [("extract", ExtractStats), ("chunks", StringChunksStats), ("variants", C.c_int64), ("bubbles", C.c_int64), ("entries", C.c_int64),
+                ("entries_used", C.c_int64), ("owners", C.c_int64), ("pairs", C.c_int64), ("pairs_anchored", C.c_int64), ("anchors", C.c_int64),
+                ("anchor_runs", C.c_int64), ("front_bytes_downloaded", C.c_int64), ("owners_ms", C.c_double), ("anchors_ms", C.c_double), ("total_ms", C.c_double)]
+
+
 def load():
     """dlopen the in-tree library; raises if it has not been built (no fallback)."""
     global _lib
@@ -385,6 +392,9 @@ def load():
     L.mrp_haptag_sites_from_extracted.argtypes = [i64, P(ExtractedChunk), P(vp), P(HaptagSites), vp]
     L.mrp_haplotag_aligned_chunks.argtypes = [vp, i64, P(AlignedChunk), P(vp), P(ExtractOptions), P(PairHmm), P(PairHmm), i64, P(vp), P(vp), P(vp),
                                               P(HaplotagAlignedStats)]
+    L.mrp_phase_aligned_chunks.argtypes = [vp, i64, P(AlignedChunk), P(vp), P(vp), P(ExtractOptions), P(PairHmm), P(PairHmm), i64, i64, C.c_double,
+                                           P(Params), i64, P(P(PhaseResult)), P(vp), P(vp), P(ProfileOut), P(vp), P(PhaseAlignedStats)]
+    L.mrp_kmer_alignment_anchors_many.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, P(vp), P(PairHmmStats)]
     L.mrp_kmer_alignment_anchors.argtypes = [vp, i64, vp, i64, vp]
     L.mrp_kmer_alignment_anchors.restype = i64
     L.mrp_phase_chunks_on_devices.argtypes = [vp, i32, i64, P(ChunkDesc), P(Params), i64, P(P(PhaseResult)), P(QueueStats)]
@@ -1026,6 +1036,29 @@ def kmer_alignment_anchors(sx, sy) -> np.ndarray:
     return out[:n].copy()
 
 
+def kmer_alignment_anchors_many(ctx: Optional[Context], pool, x_off, x_len, y_off, y_len, nulls=()):
+    """mrp_kmer_alignment_anchors_many: getKmerAlignmentAnchors of every pair on the device -> (anchor_off int64 [n + 1], anchors int64
+    [total, 2], PairHmmStats).  ctx None passes a NULL context; nulls names arguments to pass as NULL (for the argument checks)."""
+    L = load()
+    pool = np.ascontiguousarray(pool, dtype=np.uint8)
+    xo, xl, yo, yl = _opt(x_off, np.int64), _opt(x_len, np.int32), _opt(y_off, np.int64), _opt(y_len, np.int32)
+    n = len(xo)
+    off = np.full(n + 1, -7, dtype=np.int64)
+    res = C.c_void_p()
+    st = PairHmmStats()
+    ptr = lambda name, a: None if name in nulls or a.size == 0 else a.ctypes.data
+    rc = L.mrp_kmer_alignment_anchors_many(ctx.h if ctx else None, n, ptr("pool", pool), pool.size, ptr("x_off", xo), ptr("x_len", xl), ptr("y_off", yo),
+                                           ptr("y_len", yl), None if "anchor_off" in nulls else off.ctypes.data,
+                                           None if "anchors" in nulls else C.byref(res), C.byref(st))
+    if rc != MRP_OK:
+        assert res.value is None and (off == -7).all(), "outputs written on an error"
+    _check(rc)
+    total = int(off[n])
+    anchors = _as_np(res, 2 * total, np.int64).reshape(total, 2)
+    L.mrp_free(res)
+    return off, anchors, st
+
+
 def allele_read_supports(ctx: Context, forward_model: PairHmm, reverse_model: PairHmm, bubbles, expansion: int = 4, sv_threshold: int = 512):
     """bubbles: list of (alleles, reads, read_forward_strand) with alleles / reads lists of uint8 symbol arrays.
     Returns ([float32 array [n_alleles, n_reads] per bubble], PairHmmStats): Bubble.alleleReadSupports (bubbleGraph.c:1421-1464)."""
@@ -1594,3 +1627,71 @@ def haplotag_aligned_chunks(ctx: Optional[Context], chunks, gts, forward_model: 
     _check(L.mrp_haplotag_aligned_chunks(ctx.h if ctx else None, n, arr, garr, None if null_options else C.byref(opt), by(forward_model), by(reverse_model),
                                          int(expansion), ptrs(hap), ptrs(h1) if totals else None, ptrs(h2) if totals else None, C.byref(st)))
     return [dict(hap=hap[c], h1=h1[c] if totals else None, h2=h2[c] if totals else None) for c in range(n)], st
+
+
+# ---- from alignments to haplotypes and HP tags in one call (mrp_phase_aligned_chunks) ----
+
+def phase_aligned_chunks(ctx: Optional[Context], chunks, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm], params: Optional[Params],
+                         options: Optional[dict] = None, keeps=None, min_phred: int = 0, expansion: int = 4, sv_threshold: int = 512,
+                         het_substitution_probability: float = 0.0, profiles: bool = False, structs=None, nulls=()):
+    """mrp_phase_aligned_chunks -> (per chunk dict(result, hap int8 [n_reads], phred, bubble_variant int64 [n_bubbles][, profile]),
+    PhaseAlignedStats).  keeps: None, or per chunk None / a uint8 mask over its reads.  ctx / a model / params None pass NULL;
+    nulls names further arguments to pass as NULL ("options", "out", "hap_out", "read_names", "hap_out[0]", "phred_out[0]",
+    "read_names[0]", "read_names[0][0]": for the argument checks).  On an error the output arrays are checked to be untouched."""
+    L = load()
+    n = len(chunks)
+    built = structs if structs is not None else [aligned_chunk_struct(c) for c in chunks]
+    arr = (AlignedChunk * max(n, 1))(*[b[0] for b in built])
+    opt = ExtractOptions.from_dict(options or shipped_extract_options())
+    nr = [int(b[0].n_reads) for b in built]
+    names = [[s.encode() for s in c.read_names] for c in chunks]
+    name_arrs = [(C.c_char_p * max(len(x), 1))(*x) for x in names]
+    if "read_names[0][0]" in nulls:
+        name_arrs[0][0] = None
+    name_ptrs = (C.c_void_p * max(n, 1))(*[C.cast(a, C.c_void_p) if k else None for a, k in zip(name_arrs, nr)])
+    if "read_names[0]" in nulls:
+        name_ptrs[0] = None
+    masks = [None if keeps is None or keeps[c] is None else np.ascontiguousarray(keeps[c], np.uint8) for c in range(n)]
+    mask_ptrs = (C.c_void_p * max(n, 1))(*[None if m is None or m.size == 0 else m.ctypes.data for m in masks])
+    hap = [np.full(k, 99, np.int8) for k in nr]
+    phred = [np.full(k, np.nan) for k in nr]
+    hp = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in hap])
+    pp = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in phred])
+    if "hap_out[0]" in nulls:
+        hp[0] = None
+    if "phred_out[0]" in nulls:
+        pp[0] = None
+    res = (C.POINTER(PhaseResult) * max(n, 1))()
+    prof = (ProfileOut * max(n, 1))() if profiles else None
+    bv = (C.c_void_p * max(n, 1))()
+    st = PhaseAlignedStats()
+    by = lambda m: None if m is None else C.byref(m)
+    rc = L.mrp_phase_aligned_chunks(ctx.h if ctx else None, n, arr, None if "read_names" in nulls else name_ptrs, None if keeps is None else mask_ptrs,
+                                    None if "options" in nulls else C.byref(opt), by(forward_model), by(reverse_model), int(expansion), int(sv_threshold),
+                                    float(het_substitution_probability), by(params), int(min_phred), None if "out" in nulls else res,
+                                    None if "hap_out" in nulls else hp, pp, prof, bv, C.byref(st))
+    if rc != MRP_OK:
+        untouched = all((h == 99).all() for h in hap) and all(np.isnan(p).all() for p in phred) and not any(bool(res[i]) for i in range(n)) and \
+            not any(bv[i] for i in range(n)) and (prof is None or not any(prof[i].seqs or prof[i].pool for i in range(n)))
+        assert untouched, "outputs written on an error"
+    _check(rc)
+    out = []
+    for i in range(n):
+        d = dict(result=_phase_result_dict(res[i].contents), hap=hap[i], phred=phred[i])
+        L.mrp_phase_result_destroy(res[i])
+        nb = 0
+        ends = C.cast(bv[i], C.POINTER(C.c_int64))
+        while ends[nb] != -1:  # the list is closed by a -1
+            nb += 1
+        d["bubble_variant"] = _as_np(bv[i], nb, np.int64)
+        L.mrp_free(bv[i])
+        if profiles:
+            P = prof[i]
+            d["profile"] = _profile_dict(P)
+            an = _as_np(P.allele_number, nb, np.uint32)
+            A = an.astype(np.int64)
+            d["profile"].update(allele_number=an, sub=_as_np(P.substitution, int((A * A).sum()), np.uint16), prior=_as_np(P.prior, int(A.sum()), np.uint16))
+            for f in ("seqs", "read_of_seq", "pool", "allele_number", "substitution", "prior"):
+                L.mrp_free(C.cast(getattr(P, f), C.c_void_p))
+        out.append(d)
+    return out, st

@@ -609,6 +609,14 @@ void mrp_extract_run_device(const mrp_extract_run *run, mrp_extract_device *view
  * of the call in chunk then allele order, where each lies in dst */
 int64_t mrp_extract_run_allele_bytes(const mrp_extract_run *run);
 void mrp_extract_run_alleles(const mrp_extract_run *run, uint8_t *dst, int64_t *allele_off, int32_t *allele_len);
+/* getKmerAlignmentAnchors on the device (mrp_anchors.hip) for n_pairs pairs (host arrays) over a symbol pool that is already in HBM,
+ * written by work queued on ctx->stream before this call: anchor_off[n_pairs + 1] from 0 and the anchors (x, y) in pair order.  Runs on
+ * ctx->stream and returns with the stream drained; its device arrays go back to ctx's pool, which the caller reclaims.  The anchors
+ * come back as diagonal runs (x, y, length) and are expanded here.  kernel_ms (HIP events around the kernels), bytes_downloaded (4 B
+ * per pair, 12 B per run) and n_runs_out may be NULL. */
+int mrp_kmer_anchors_on_device(mrp_context *ctx, const char *who, const uint8_t *device_pool, int64_t n_pairs, const int64_t *x_off,
+                               const int32_t *x_len, const int64_t *y_off, const int32_t *y_len, int64_t *anchor_off, std::vector<int64_t> &anchors,
+                               double *kernel_ms, int64_t *bytes_downloaded, int64_t *n_runs_out);
 extern "C" void mrp_batch_last_launch_ms(struct mrp_batch *b, float *pack, float *emission, float *recursion);
 
 /* development: MRP_DUP=<letters> launches the named kernel families of a resident level TWICE (they are idempotent) -- the slow-down of a

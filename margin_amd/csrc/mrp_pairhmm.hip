@@ -3,8 +3,9 @@
  * (computeForwardProbability, impl/pairwiseAligner.c:849-903) for batches of string pairs, and the alleleReadSupports
  * loop around it (impl/bubbleGraph.c:1421-1464), and the filtered-read / filtered-variant loops after the phasing
  * (:1749-2351: the supports stay on the device, a scoring kernel reduces them), the string-chunk calls built on them and, at the end
- * of the file, the haplotagging of aligned reads from a phased VCF over the extraction's result in HBM (ha_owners_kernel,
- * mrp_haplotag_aligned_chunks).  gfx950 only; compiled with -ffp-contract=off.
+ * of the file, the two composites over the extraction's result in HBM (ha_owners_kernel): the haplotagging of aligned reads from a
+ * phased VCF (mrp_haplotag_aligned_chunks) and the phasing of aligned chunks (mrp_phase_aligned_chunks; its k-mer anchors are made by
+ * mrp_anchors.hip).  gfx950 only; compiled with -ffp-contract=off.
  *
  * The recursion (stateMachine3_cellCalculate, impl/stateMachine.c:562-586) gives every dp cell (x, y) three states from
  * its neighbours (x-1, y), (x-1, y-1), (x, y-1); a neighbour outside the band contributes nothing, which is what a
@@ -847,7 +848,8 @@ void substring_owners(int64_t n_groups, const int64_t *first, const uint8_t *poo
 
 /* cachedScores of bubbleGraph_partitionFilteredReadsFromPhasedVcfEntries (bubbleGraph.c:2044-2072) on the device, over the arrays the
  * extraction left in HBM (mrp_extract_device): a wave per site, a lane per entry with a lane stride (a site may hold more entries than
- * a wave has lanes).  An entry takes part if its read is MRP_READ_KEPT; owner[p] = the LAST entry of the site that takes part and has
+ * a wave has lanes).  An entry takes part if its read is MRP_READ_KEPT and, with a mask, take[read] is set (the caller's downsampling in
+ * mrp_phase_aligned_chunks; NULL: every kept read); owner[p] = the LAST entry of the site that takes part and has
  * p's substring (b->reads is filled by popping, :2012-2014), p itself if none follows, -1 for an entry that takes no part.  Pass one
  * gives every entry a key (length, hash of the symbols); pass two walks the site from its end and compares symbols wherever the keys
  * agree: the hash only skips comparisons.  Every loop is bounded by the site's entry count or the substring's length; the barrier
@@ -855,14 +857,15 @@ void substring_owners(int64_t n_groups, const int64_t *first, const uint8_t *poo
 constexpr uint64_t HA_NO_KEY = ~0ull;
 __global__ void __launch_bounds__(PHM_WAVE) ha_owners_kernel(const int64_t *__restrict__ first, int64_t n_sites, const int32_t *__restrict__ read,
                                                              const uint8_t *__restrict__ status, const int64_t *__restrict__ len,
-                                                             const int64_t *__restrict__ off, const uint8_t *__restrict__ sym, uint64_t *key,
-                                                             int32_t *__restrict__ owner) {
+                                                             const int64_t *__restrict__ off, const uint8_t *__restrict__ sym,
+                                                             const uint8_t *__restrict__ take, uint64_t *key, int32_t *__restrict__ owner) {
     const int lane = threadIdx.x;
     for (int64_t v = blockIdx.x; v < n_sites; v += gridDim.x) {
         const int64_t a = first[v], b = first[v + 1];
         for (int64_t p = a + lane; p < b; p += PHM_WAVE) {
             uint64_t k = HA_NO_KEY;
-            if (status[read[p]] == MRP_READ_KEPT) {
+            const int32_t r = read[p];
+            if (status[r] == MRP_READ_KEPT && (!take || take[r])) {
                 const uint8_t *x = sym + off[p];
                 const int64_t n = len[p];
                 uint32_t h = 2166136261u;
@@ -1616,6 +1619,8 @@ struct mrp_string_front {
     const mrp_string_chunk *chunks = nullptr;          /* the caller's, alive until the run has returned */
     std::vector<int64_t> pool_base, sub_base;          /* n_chunks + 1: chunk c's symbols and substrings in the call's arrays */
     HostVec<uint8_t> gpool;                            /* every chunk's symbols: what the pair-HMM kernels read */
+    const uint8_t *device_pool = nullptr;              /* set (mrp_phase_aligned_chunks): the symbols lie in HBM already, device_pool_bytes of */
+    int64_t device_pool_bytes = 0;                     /* them, written by work queued on the run's stream; gpool is empty and not read */
     std::vector<int64_t> pair_first;                   /* per substring: the pair of its owner with the bubble's allele 0 */
     PhmLaunch L;                                       /* the pairs as phm_classify sorted them; the run adds the device half (PhmDev) */
     /* what only the front itself reads, kept until the front is destroyed: released between front and run, these ~100 bytes per
@@ -2159,7 +2164,8 @@ int ScRun::begin() {
 /* the pair-HMM kernels over the front's launch classes; EV_PAIRS_END behind them */
 int ScRun::enqueue_pairhmm() {
     if (n_pairs > 0) {
-        const int rc = phm_enqueue(ctx, F->gpool.data(), (int64_t) F->gpool.size(), n_pairs, F->L, D, stats ? &stats->pairhmm : nullptr);
+        const int64_t pool_bytes = F->device_pool ? F->device_pool_bytes : (int64_t) F->gpool.size();
+        const int rc = phm_enqueue(ctx, F->gpool.data(), pool_bytes, n_pairs, F->L, D, stats ? &stats->pairhmm : nullptr, F->device_pool);
         if (rc != MRP_OK) return rc;
     } else {
         PHM_HIP(hipEventRecord(ctx->ev[0], s));
@@ -2577,49 +2583,64 @@ int mrp_phase_string_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, co
  * (phm_classify reads offsets and lengths only for unanchored pairs) and the per-read entry lists of ht_partition_kernel. */
 namespace {
 
-struct HaRun {
-    static constexpr const char *who = "mrp_haplotag_aligned_chunks";
+/* What the composites over aligned chunks share (mrp_haplotag_aligned_chunks, mrp_phase_aligned_chunks): the staged extraction gathering
+ * behind the allele strings in the call's one device pool, the owners kernel over it and what comes back from it -- indices, no symbol. */
+struct AlignedFront {
+    const char *const who;
     mrp_context *const ctx;
     const int64_t n_chunks;
     const mrp_aligned_chunk *const chunks;
-    const int32_t *const *const gt;
-    mrp_haplotag_aligned_stats *const stats;
     mrp_extract_run *X = nullptr;
     hipStream_t s = nullptr; /* set once the device is current: from then on the destructor drains it */
     hipEvent_t ev[2] = {nullptr, nullptr}; /* around the owners kernel */
     mrp_extract_device D{};
     int64_t allele_bytes = 0, pool_bytes = 0, n_alleles = 0, downloaded = 0;
-    PinnedBuf h_sym, h_back, h_res;
-    HostVec<int64_t> a_off, y_off, first;
+    PinnedBuf h_sym, h_back;
+    HostVec<int64_t> a_off, y_off;
     HostVec<int32_t> a_len;
     HostVec<uint8_t> forward;
-    HostVec<HtEntry> ent;
-    HtPairs P;
-    PhmLaunch H;
-    PhmDev L; /* L.d_out holds the log probabilities the partition kernel reads */
-    DevBuf<uint8_t> d_sym;
+    DevBuf<uint8_t> d_sym, d_take;
     DevBuf<uint64_t> d_key;
-    DevBuf<int32_t> d_owner, d_hap;
-    DevBuf<int64_t> d_first;
-    DevBuf<HtEntry> d_ent;
-    DevBuf<double> d_h;
+    DevBuf<int32_t> d_owner;
     /* what came back after the owners kernel */
     const uint8_t *k_status = nullptr;
     const int64_t *k_first = nullptr, *k_len = nullptr;
     const int32_t *k_read = nullptr, *k_owner = nullptr;
 
-    HaRun(mrp_context *c, int64_t n, const mrp_aligned_chunk *ch, const int32_t *const *g, mrp_haplotag_aligned_stats *st)
-        : ctx(c), n_chunks(n), chunks(ch), gt(g), stats(st) {}
-    ~HaRun() {
+    AlignedFront(const char *w, mrp_context *c, int64_t n, const mrp_aligned_chunk *ch) : who(w), ctx(c), n_chunks(n), chunks(ch) {}
+    ~AlignedFront() {
         if (s) (void) hipStreamSynchronize(s);
         for (hipEvent_t x : ev)
             if (x) (void) hipEventDestroy(x);
         mrp_extract_run_destroy(X);
     }
+    int extract();
+    int owners(const HostVec<uint8_t> *take);
+    void offsets_and_strands();
+    void release() { d_sym.release(); d_take.release(); d_key.release(); d_owner.release(); }
+};
+
+struct HaRun : AlignedFront {
+    const int32_t *const *const gt;
+    mrp_haplotag_aligned_stats *const stats;
+    PinnedBuf h_res;
+    HostVec<int64_t> first;
+    HostVec<HtEntry> ent;
+    HtPairs P;
+    PhmLaunch H;
+    PhmDev L; /* L.d_out holds the log probabilities the partition kernel reads */
+    DevBuf<int32_t> d_hap;
+    DevBuf<int64_t> d_first;
+    DevBuf<HtEntry> d_ent;
+    DevBuf<double> d_h;
+
+    HaRun(mrp_context *c, int64_t n, const mrp_aligned_chunk *ch, const int32_t *const *g, mrp_haplotag_aligned_stats *st)
+        : AlignedFront("mrp_haplotag_aligned_chunks", c, n, ch), gt(g), stats(st) {}
+    ~HaRun() {
+        if (s) (void) hipStreamSynchronize(s); /* before the pinned result buffer goes */
+    }
     int check(const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
               int8_t *const *hap_out, double *const *h1_out, double *const *h2_out);
-    int extract();
-    int owners();
     int pairs();
     int score(const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion);
     int hand_over(int8_t *const *hap_out, double *const *h1_out, double *const *h2_out);
@@ -2652,11 +2673,11 @@ int HaRun::check(const mrp_extract_options *options, const mrp_pair_hmm *forward
 }
 
 /* the extraction up to its second half, gathering behind the allele strings in the call's one device pool */
-int HaRun::extract() {
+int AlignedFront::extract() {
     int rc = mrp_extract_run_stage(X, ctx);
     if (rc != MRP_OK) return rc;
     s = ctx->stream;
-    d_sym.pool = d_key.pool = d_owner.pool = d_hap.pool = d_first.pool = d_ent.pool = d_h.pool = &ctx->pool;
+    d_sym.pool = d_take.pool = d_key.pool = d_owner.pool = &ctx->pool;
     for (hipEvent_t &x : ev) PHM_HIP(hipEventCreate(&x));
     rc = mrp_extract_run_first_half(X);
     int64_t n_ent = 0, n_bases = 0;
@@ -2678,15 +2699,17 @@ int HaRun::extract() {
     return MRP_OK;
 }
 
-/* the owners on the device; back come the per-read status and per entry its read, length and owner -- not the symbols */
-int HaRun::owners() {
+/* the owners on the device (take: NULL, or per read of the call whether it may take part); back come the per-read status and per entry
+ * its read, length and owner -- not the symbols */
+int AlignedFront::owners(const HostVec<uint8_t> *take) {
     const int64_t n_ent = D.n_entries, n_var = D.n_variants, n_reads = D.n_reads;
     PHM_HIP(d_key.alloc((size_t) n_ent));
     PHM_HIP(d_owner.alloc((size_t) n_ent));
+    if (take) PHM_HIP(d_take.upload(*take, s));
     PHM_HIP(hipEventRecord(ev[0], s));
     if (n_ent > 0) {
         hipLaunchKernelGGL(ha_owners_kernel, dim3((unsigned) std::min<int64_t>(n_var, 65536)), dim3(PHM_WAVE), 0, s, D.entry_first, n_var, D.entry_read,
-                           D.read_status, D.entry_len, D.entry_off, D.symbols, d_key.p, d_owner.p);
+                           D.read_status, D.entry_len, D.entry_off, D.symbols, take ? (const uint8_t *) d_take.p : nullptr, d_key.p, d_owner.p);
         PHM_HIP(hipGetLastError());
     }
     PHM_HIP(hipEventRecord(ev[1], s));
@@ -2711,16 +2734,22 @@ int HaRun::owners() {
     return MRP_OK;
 }
 
+/* where every entry's symbols lie in the device pool (behind the allele strings, in entry order), and every read's strand */
+void AlignedFront::offsets_and_strands() {
+    const int64_t n_ent = D.n_entries;
+    y_off.resize((size_t) n_ent);
+    int64_t at = allele_bytes;
+    for (int64_t p = 0; p < n_ent; p++) { y_off[(size_t) p] = at; at += k_len[p]; }
+    forward.resize((size_t) D.n_reads);
+    for (int64_t c = 0; c < n_chunks; c++)
+        for (int64_t r = 0; r < chunks[c].n_reads; r++) forward[(size_t) (D.read_first[c] + r)] = (chunks[c].flag[r] & 0x10) == 0;
+}
+
 /* on the host, from indices and lengths alone: the two pairs of every owner at an active site in ht_build_pairs' order (the model from
  * the owner's strand), and every read's entries in site order */
 int HaRun::pairs() {
     const int64_t n_ent = D.n_entries, n_var = D.n_variants, n_reads = D.n_reads;
-    y_off.resize((size_t) n_ent);
-    int64_t at = allele_bytes;
-    for (int64_t p = 0; p < n_ent; p++) { y_off[(size_t) p] = at; at += k_len[p]; }
-    forward.resize((size_t) n_reads);
-    for (int64_t c = 0; c < n_chunks; c++)
-        for (int64_t r = 0; r < chunks[c].n_reads; r++) forward[(size_t) (D.read_first[c] + r)] = (chunks[c].flag[r] & 0x10) == 0;
+    offsets_and_strands();
     std::vector<uint8_t> active((size_t) n_var, 0);
     P.pair_of.assign((size_t) n_ent, -1);
     first.assign((size_t) n_reads + 1, 0);
@@ -2772,6 +2801,7 @@ int HaRun::pairs() {
 /* the pair-HMM kernels over the pool that is already on the device, then a lane per read over its entries; the results on their way back */
 int HaRun::score(const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion) {
     const int64_t n_reads = D.n_reads;
+    d_hap.pool = d_first.pool = d_ent.pool = d_h.pool = &ctx->pool;
     mrp_pairhmm_stats *pst = stats ? &stats->pairhmm : nullptr;
     const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
     if (P.list.size() > 0) { /* (MRP_ERR_UNSUPPORTED for a diagonal beyond the limit is raised by phm_classify, before anything is launched) */
@@ -2827,7 +2857,8 @@ int HaRun::hand_over(int8_t *const *hap_out, double *const *h1_out, double *cons
             if (h1_out) h1_out[c][r] = kept ? k_h1[g] : 0.0;
             if (h2_out) h2_out[c][r] = kept ? k_h2[g] : 0.0;
         }
-    d_sym.release(); d_key.release(); d_owner.release(); d_hap.release(); d_first.release(); d_ent.release(); d_h.release();
+    release();
+    d_hap.release(); d_first.release(); d_ent.release(); d_h.release();
     L.d_models.release(); L.d_band.release(); L.d_out.release();
     for (int c = 0; c < 4; c++) { L.d_lane[c].release(); L.d_wave[c].release(); }
     mrp_extract_run_release(X); /* (reclaims the context's pool) */
@@ -2845,12 +2876,264 @@ extern "C" int mrp_haplotag_aligned_chunks(mrp_context *ctx, int64_t n_chunks, c
     HaRun R(ctx, n_chunks, chunks, gt, stats);
     int rc = R.check(options, forward_model, reverse_model, expansion, hap_out, h1_out, h2_out);
     if (rc != MRP_OK) return rc;
-    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction and the pair-HMM have no CPU fallback)", HaRun::who);
+    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction and the pair-HMM have no CPU fallback)", R.who);
     rc = R.extract();
-    if (rc == MRP_OK) rc = R.owners();
+    if (rc == MRP_OK) rc = R.owners(nullptr);
     if (rc == MRP_OK) rc = R.pairs();
     if (rc == MRP_OK) rc = R.score(forward_model, reverse_model, expansion);
     if (rc == MRP_OK) rc = R.hand_over(hap_out, h1_out, h2_out);
+    if (rc != MRP_OK) return rc;
+    if (stats) stats->total_ms = now_ms() - t_begin;
+    return MRP_OK;
+}
+
+/* ---- mrp_phase_aligned_chunks: the staged extraction, the owners kernel with the caller's mask, the k-mer anchors on the device
+ * (mrp_anchors.hip) and the string call's run over the pool where it lies in HBM.  The host makes, from indices
+ * and lengths alone, what mrp_string_chunk_from_extracted and mrp_string_front_create make from the downloaded symbols: every chunk's
+ * mrp_string_chunk index arrays (offsets into the device pool), the owners' pairs in the front's order, and which pairs are anchored. */
+namespace {
+
+struct PaRun : AlignedFront {
+    const char *const *const *const read_names;
+    const uint8_t *const *const keep;
+    mrp_phase_aligned_stats *const stats;
+    struct ChunkArrays { /* what the mrp_string_chunk of a chunk points into */
+        std::vector<int64_t> a_first{0}, a_off, s_first{0}, s_off, bubble_variant;
+        std::vector<int32_t> a_len, s_len, s_read;
+        std::vector<uint8_t> forward;
+    };
+    std::vector<ChunkArrays> arr;
+    std::vector<mrp_string_chunk> sc;
+    std::vector<int64_t> anchored; /* the pairs with a string longer than sv_threshold, ascending */
+    std::vector<int64_t *> bv_out; /* the copies of bubble_variant the caller gets */
+    mrp_string_front F;
+    int64_t n_bubbles = 0, n_used = 0, n_owners = 0, n_anchors = 0, n_anchor_runs = 0;
+    double anchors_ms = 0;
+
+    PaRun(mrp_context *c, int64_t n, const mrp_aligned_chunk *ch, const char *const *const *names, const uint8_t *const *k, mrp_phase_aligned_stats *st)
+        : AlignedFront("mrp_phase_aligned_chunks", c, n, ch), read_names(names), keep(k), stats(st) {}
+    ~PaRun() {
+        for (int64_t *p : bv_out) free(p);
+    }
+    int check(const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+              const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out);
+    int masked_owners();
+    int strings_and_pairs(int64_t sv_threshold);
+    int anchors();
+    int classify(const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion);
+    int hand_over(int64_t **bubble_variant_out);
+};
+
+/* every MRP_ERR_ARG of the call (the extraction's, then the string call's parameter checks), then the two refused modes: nothing
+ * here looks at the context */
+int PaRun::check(const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                 const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out) {
+    X = mrp_extract_run_create(who, n_chunks, chunks, options, stats ? &stats->extract : nullptr);
+    if (!X) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
+    int rc = mrp_extract_run_check_args(X, true);
+    if (rc == MRP_OK) rc = mrp_extract_run_check_chunks(X);
+    if (rc != MRP_OK) return rc;
+    if (!forward_model || !reverse_model || !params || (n_chunks > 0 && (!out || !hap_out || !read_names)))
+        return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const mrp_aligned_chunk &C = chunks[c];
+        if (C.n_reads == 0) continue;
+        if (!hap_out[c] || (phred_out && !phred_out[c])) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null output", who, (long long) c);
+        if (!read_names[c]) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null read names", who, (long long) c);
+        for (int64_t r = 0; r < C.n_reads; r++)
+            if (!read_names[c][r]) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: read %lld has no name", who, (long long) c, (long long) r);
+    }
+    return mrp_extract_run_check_modes(X);
+}
+
+/* the owners among the kept reads the caller's mask lets through (one byte per read of the call; no mask anywhere: none uploaded) */
+int PaRun::masked_owners() {
+    bool any = false;
+    for (int64_t c = 0; keep && c < n_chunks; c++) any = any || (keep[c] && chunks[c].n_reads > 0);
+    if (!any) return owners(nullptr);
+    HostVec<uint8_t> take((size_t) D.n_reads);
+    for (int64_t c = 0; c < n_chunks; c++)
+        for (int64_t r = 0; r < chunks[c].n_reads; r++) take[(size_t) (D.read_first[c] + r)] = keep[c] ? (keep[c][r] != 0) : 1;
+    return owners(&take);
+}
+
+/* bubbleGraph_constructFromVCFAndBamChunkReadVcfEntrySubstrings (bubbleGraph.c:1338-1400) over the device pool: a variant with an entry
+ * that takes part is a bubble, its substrings those entries in descending order (:1391-1393); then mrp_string_front_create's pair list:
+ * chunk by chunk, bubble by bubble, the owners in listing order, an owner's pairs allele by allele, the owner's strand picking the model */
+int PaRun::strings_and_pairs(int64_t sv_threshold) {
+    offsets_and_strands();
+    arr.resize((size_t) n_chunks);
+    sc.assign((size_t) n_chunks, mrp_string_chunk{});
+    std::vector<int64_t> &sub_base = F.sub_base, &pair_first = F.pair_first;
+    sub_base.assign((size_t) n_chunks + 1, 0);
+    pair_first.clear();
+    std::vector<int64_t> sub_of((size_t) D.n_entries, -1); /* entry -> its substring in the call */
+    PhmPairList &pairs = F.scratch.pairs;
+    int64_t abase = 0, n_subs = 0;
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const mrp_aligned_chunk &C = chunks[c];
+        ChunkArrays &A = arr[(size_t) c];
+        A.forward.assign(forward.begin() + D.read_first[c], forward.begin() + D.read_first[c + 1]);
+        for (int64_t v = 0; v < C.n_variants; v++) {
+            const int64_t g = D.variant_first[c] + v;
+            int64_t k = 0;
+            for (int64_t p = k_first[g]; p < k_first[g + 1]; p++) k += k_owner[p] >= 0;
+            if (!k) continue; /* :1366-1371 nothing to phase with */
+            const int64_t na = C.allele_first[v + 1] - C.allele_first[v];
+            if (na > 65535) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: variant %lld has more than 65535 alleles", who, (long long) c, (long long) v);
+            const int64_t a0 = (int64_t) A.a_off.size();
+            for (int64_t a = C.allele_first[v]; a < C.allele_first[v + 1]; a++) {
+                A.a_off.push_back(a_off[(size_t) (abase + a)]);
+                A.a_len.push_back(a_len[(size_t) (abase + a)]);
+            }
+            for (int64_t p = k_first[g + 1] - 1; p >= k_first[g]; p--) {
+                if (k_owner[p] < 0) continue;
+                sub_of[(size_t) p] = n_subs++;
+                /* the pair of the substring's owner with the bubble's allele 0 (the owner is listed before its duplicates) */
+                pair_first.push_back(k_owner[p] == p ? pairs.size() : pair_first[(size_t) sub_of[(size_t) k_owner[p]]]);
+                A.s_off.push_back(y_off[(size_t) p]);
+                A.s_len.push_back((int32_t) k_len[p]);
+                A.s_read.push_back((int32_t) (k_read[p] - D.read_first[c]));
+                if (k_owner[p] != p) continue;
+                n_owners++;
+                const int model = forward[(size_t) k_read[p]] ? 0 : 1;
+                for (int64_t j = 0; j < na; j++) {
+                    const int32_t al = A.a_len[(size_t) (a0 + j)];
+                    if (k_len[p] > sv_threshold || al > sv_threshold) anchored.push_back(pairs.size()); /* bubbleGraph.c:1448-1451 */
+                    pairs.add(A.a_off[(size_t) (a0 + j)], al, y_off[(size_t) p], (int32_t) k_len[p], model, nullptr);
+                }
+            }
+            A.bubble_variant.push_back(v);
+            A.a_first.push_back((int64_t) A.a_off.size());
+            A.s_first.push_back((int64_t) A.s_off.size());
+        }
+        abase += C.n_variants ? C.allele_first[C.n_variants] : 0;
+        sub_base[(size_t) c + 1] = n_subs;
+        mrp_string_chunk &S = sc[(size_t) c];
+        S.n_bubbles = (int64_t) A.bubble_variant.size();
+        S.n_reads = C.n_reads;
+        S.pool = nullptr; /* the symbols are in HBM */
+        S.pool_bytes = pool_bytes;
+        S.allele_first = A.a_first.data();
+        S.allele_off = A.a_off.data();
+        S.allele_len = A.a_len.data();
+        S.sub_first = A.s_first.data();
+        S.sub_off = A.s_off.data();
+        S.sub_len = A.s_len.data();
+        S.sub_read = A.s_read.data();
+        S.read_names = read_names[c];
+        S.read_forward_strand = A.forward.data();
+        n_bubbles += S.n_bubbles;
+    }
+    n_used = n_subs;
+    if (pairs.size() >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
+    F.n_chunks = n_chunks;
+    F.chunks = sc.data();
+    F.n_subs = n_subs;
+    F.n_pairs = pairs.size();
+    F.device_pool = d_sym.p;
+    F.device_pool_bytes = pool_bytes;
+    return MRP_OK;
+}
+
+/* getKmerAlignmentAnchors of the anchored pairs, in the device pool; run counts and the anchors (as diagonal runs) come back and join
+ * the pair list */
+int PaRun::anchors() {
+    PhmPairList &pairs = F.scratch.pairs;
+    const int64_t n = (int64_t) anchored.size();
+    if (n == 0) return MRP_OK;
+    std::vector<int64_t> xo((size_t) n), yo((size_t) n), off((size_t) n + 1, 0), anc;
+    std::vector<int32_t> xl((size_t) n), yl((size_t) n);
+    for (int64_t i = 0; i < n; i++) {
+        const size_t q = (size_t) anchored[(size_t) i];
+        xo[(size_t) i] = pairs.x_off[q]; xl[(size_t) i] = pairs.x_len[q]; yo[(size_t) i] = pairs.y_off[q]; yl[(size_t) i] = pairs.y_len[q];
+    }
+    int64_t bytes = 0;
+    const int rc = mrp_kmer_anchors_on_device(ctx, who, d_sym.p, n, xo.data(), xl.data(), yo.data(), yl.data(), off.data(), anc, &anchors_ms, &bytes, &n_anchor_runs);
+    if (rc != MRP_OK) return rc;
+    downloaded += bytes;
+    n_anchors = off[(size_t) n];
+    for (int64_t i = 0; i < n; i++) pairs.anchor_off[(size_t) anchored[(size_t) i] + 1] = off[(size_t) i + 1] - off[(size_t) i];
+    pairs.counts_to_offsets();
+    pairs.anchors = std::move(anc);
+    return MRP_OK;
+}
+
+/* the launch classes and the bands; raises the 2 048-cell refusal, before any pair-HMM kernel */
+int PaRun::classify(const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion) {
+    if (F.n_pairs == 0) return MRP_OK;
+    const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
+    return phm_classify(who, models, 2, pool_bytes, F.scratch.pairs.view(), expansion, 0, 0, F.L);
+}
+
+/* after the string run has handed its results over: the bubbles' variants, the stats, the device arrays back to the pool */
+int PaRun::hand_over(int64_t **bubble_variant_out) {
+    if (stats) {
+        float ms = 0.f;
+        PHM_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        stats->owners_ms = ms;
+        stats->anchors_ms = anchors_ms;
+        stats->variants = D.n_variants;
+        stats->bubbles = n_bubbles;
+        stats->entries = D.n_entries;
+        stats->entries_used = n_used;
+        stats->owners = n_owners;
+        stats->pairs = F.n_pairs;
+        stats->pairs_anchored = (int64_t) anchored.size();
+        stats->anchors = n_anchors;
+        stats->anchor_runs = n_anchor_runs;
+        stats->front_bytes_downloaded = downloaded;
+        const int rc = mrp_extract_run_stats(X);
+        if (rc != MRP_OK) return rc;
+        mrp_extract_run_times(X, false);
+    }
+    if (bubble_variant_out)
+        for (int64_t c = 0; c < n_chunks; c++) { bubble_variant_out[c] = bv_out[(size_t) c]; bv_out[(size_t) c] = nullptr; }
+    release();
+    mrp_extract_run_release(X); /* (reclaims the context's pool) */
+    return MRP_OK;
+}
+
+}  // namespace
+
+extern "C" int mrp_phase_aligned_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const char *const *const *read_names,
+                                        const uint8_t *const *keep, const mrp_extract_options *options, const mrp_pair_hmm *forward_model,
+                                        const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
+                                        const mrp_params *params, int64_t min_phred, mrp_phase_result **out, int8_t *const *hap_out,
+                                        double *const *phred_out, mrp_profile_out *profiles_out, int64_t **bubble_variant_out,
+                                        mrp_phase_aligned_stats *stats) {
+    const double t_begin = now_ms();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    PaRun R(ctx, n_chunks, chunks, read_names, keep, stats);
+    int rc = R.check(options, forward_model, reverse_model, expansion, params, out, hap_out, phred_out);
+    if (rc != MRP_OK) return rc;
+    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction and the pair-HMM have no CPU fallback)", R.who);
+    rc = R.extract();
+    if (rc == MRP_OK) rc = R.masked_owners();
+    if (rc == MRP_OK) rc = R.strings_and_pairs(sv_threshold);
+    if (rc == MRP_OK) rc = R.anchors();
+    if (rc == MRP_OK) rc = R.classify(forward_model, reverse_model, expansion);
+    if (rc != MRP_OK) return rc;
+    if (bubble_variant_out) { /* (made before anything is handed over: an error returns nothing) */
+        R.bv_out.assign((size_t) n_chunks, nullptr);
+        for (int64_t c = 0; c < n_chunks; c++) {
+            std::vector<int64_t> bv = R.arr[(size_t) c].bubble_variant;
+            bv.push_back(-1); /* the end of the list: the caller has no other way to the bubble count */
+            R.bv_out[(size_t) c] = (int64_t *) sc_dup(bv.data(), sizeof(int64_t) * bv.size());
+            if (!R.bv_out[(size_t) c]) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", R.who);
+        }
+    }
+    for (int64_t c = 0; c < n_chunks; c++) out[c] = nullptr;
+    if (profiles_out && n_chunks > 0) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
+    if (n_chunks > 0) {
+        /* the rest of the string call unchanged: pair-HMM over the device pool, layout beside it, profile bytes, phasing, HP tags */
+        R.F.front_ms = now_ms() - t_begin;
+        rc = mrp_string_front_run(ctx, &R.F, het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out,
+                                  stats ? &stats->chunks : nullptr, nullptr, nullptr);
+        if (rc != MRP_OK) return rc;
+    }
+    rc = R.hand_over(bubble_variant_out);
     if (rc != MRP_OK) return rc;
     if (stats) stats->total_ms = now_ms() - t_begin;
     return MRP_OK;

@@ -1,0 +1,174 @@
+"""mrp_phase_aligned_chunks at margin phase's shape, beside the chain of calls it joins: the 96 chunks of tools/extract_probe.py and
+tools/haplotag_probe.py (100 kb with 10 kb overlaps, 30x, reads of median ~15 kb, a het variant every ~1 kb; a few distinct synthetic
+chunks, repeated).  The chain is mrp_extract_read_substrings -> mrp_string_chunk_from_extracted per chunk -> mrp_phase_string_chunks,
+called through ctypes on the C structs themselves (no numpy copies in between), in the same process and on the same context.  Reports
+the wall time of both (median of --reps, with min and max), their kernel times (HIP events), what the composite downloads before the
+pair-HMM launch against the symbols the chain downloads and uploads again, the owners and anchors kernels -- the latter against the host
+wall time of mrp_kmer_alignment_anchors over the same anchored pairs, which is what the chain's front spends on them -- and whether
+both gave the same results bit for bit.  Prints one JSON line and writes it to --out.
+
+    python tools/phase_aligned_probe.py [--chunks 96] [--distinct 4] [--reps 5] [--cache FILE] [--out profiles/phase_aligned/probe.json]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import pickle
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from margin_amd import capi, synth  # noqa: E402
+
+SV_THRESHOLD = 512
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--chunks", type=int, default=96)
+    ap.add_argument("--distinct", type=int, default=4)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--cache", default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "phase_aligned", "probe.json"))
+    a = ap.parse_args()
+    opts = capi.shipped_extract_options()
+    if a.cache and os.path.exists(a.cache):
+        with open(a.cache, "rb") as f:
+            distinct = pickle.load(f)
+        assert len(distinct) == a.distinct
+    else:
+        t = time.perf_counter()
+        distinct = [synth.make_aligned_chunk(seed, overlap_bp=120_000, margin_bp=10_000, coverage=30.0, read_len=(5_000, 25_000),
+                                             variant_every=1_000, sv_share=0.02, oddities=False) for seed in range(a.distinct)]
+        print(f"generated {a.distinct} chunks in {time.perf_counter() - t:.0f} s", file=sys.stderr)
+        if a.cache:
+            with open(a.cache, "wb") as f:
+                pickle.dump(distinct, f)
+    chunks = [distinct[i % a.distinct] for i in range(a.chunks)]
+    built = [capi.aligned_chunk_struct(c) for c in chunks]
+    n = len(chunks)
+    fwd = capi.PairHmm.from_margin_hmm(*synth.margin_phase_pair_hmm_arrays())
+    rev = fwd.reverse_complement()
+    params = capi.Params.from_reference_names(synth.shipped_phase_params())
+    L = capi.load()
+    arr = (capi.AlignedChunk * n)(*[b[0] for b in built])
+    opt = capi.ExtractOptions.from_dict(opts)
+    names = [[s.encode() for s in c.read_names] for c in chunks]
+    name_arrs = [(C.c_char_p * max(len(x), 1))(*x) for x in names]
+    strands = [np.ascontiguousarray(c.read_forward_strand, np.uint8) for c in chunks]
+
+    def chain(ctx, anchors_too=False):
+        """the calls on the C structs -> (per chunk (hap, phred, hap1, hap2), stats, counts, wall ms[, host anchors ms, pairs, anchors])"""
+        out = C.POINTER(capi.ExtractedChunk)()
+        est, sst = capi.ExtractStats(), capi.StringChunksStats()
+        t0 = time.perf_counter()
+        capi._check(L.mrp_extract_read_substrings(ctx.h, n, arr, C.byref(opt), C.byref(out), C.byref(est)))
+        sc = (capi.StringChunk * n)()
+        bvs = []
+        for i in range(n):
+            bv = C.POINTER(C.c_int64)()
+            capi._check(L.mrp_string_chunk_from_extracted(C.byref(out[i]), None, C.cast(name_arrs[i], C.c_void_p), strands[i].ctypes.data, C.byref(sc[i]), C.byref(bv)))
+            bvs.append(bv)
+        haps = [np.zeros(len(c.read_pos), np.int8) for c in chunks]
+        phreds = [np.zeros(len(c.read_pos)) for c in chunks]
+        hp = (C.c_void_p * n)(*[h.ctypes.data for h in haps])
+        pp = (C.c_void_p * n)(*[p.ctypes.data for p in phreds])
+        res = (C.POINTER(capi.PhaseResult) * n)()
+        capi._check(L.mrp_phase_string_chunks(ctx.h, n, sc, C.byref(fwd), C.byref(rev), 4, SV_THRESHOLD, 0.0, C.byref(params), 0, res, hp, pp, None, C.byref(sst)))
+        wall = (time.perf_counter() - t0) * 1e3
+        results = []
+        for i in range(n):
+            g = res[i].contents
+            results.append((haps[i], phreds[i], capi._as_np(g.haplotype_string1, int(g.length), np.uint64), capi._as_np(g.haplotype_string2, int(g.length), np.uint64)))
+            L.mrp_phase_result_destroy(res[i])
+        n_sym = n_ent = 0
+        host = None
+        if anchors_too:
+            host_ms, n_anchored, n_anchors = 0.0, 0, 0
+            scratch = np.zeros((1 << 16, 2), np.int64)
+        for i in range(n):
+            S = sc[i]
+            nb = int(S.n_bubbles)
+            ne = int(capi._as_np(out[i].entry_first, int(out[i].n_variants) + 1, np.int64)[-1])
+            n_ent += ne
+            n_sym += int(capi._as_np(out[i].entry_len, ne, np.int32).sum())
+            if anchors_too and i < a.distinct:  # the distinct chunks repeat: time each once, count it as often as it occurs
+                times = len(range(i, n, a.distinct))
+                a_first, s_first = capi._as_np(S.allele_first, nb + 1, np.int64), capi._as_np(S.sub_first, nb + 1, np.int64)
+                a_off, a_len = capi._as_np(S.allele_off, int(a_first[nb]), np.int64), capi._as_np(S.allele_len, int(a_first[nb]), np.int32)
+                s_off, s_len = capi._as_np(S.sub_off, int(s_first[nb]), np.int64), capi._as_np(S.sub_len, int(s_first[nb]), np.int32)
+                pool = capi._as_np(S.pool, int(S.pool_bytes), np.uint8)
+                base = pool.ctypes.data
+                for b in range(nb):
+                    seen = set()
+                    for k in range(int(s_first[b]), int(s_first[b + 1])):
+                        key = pool[s_off[k]:s_off[k] + s_len[k]].tobytes()
+                        if key in seen:
+                            continue
+                        seen.add(key)
+                        for j in range(int(a_first[b]), int(a_first[b + 1])):
+                            if s_len[k] <= SV_THRESHOLD and a_len[j] <= SV_THRESHOLD:
+                                continue
+                            t1 = time.perf_counter()
+                            got = L.mrp_kmer_alignment_anchors(base + int(a_off[j]), int(a_len[j]), base + int(s_off[k]), int(s_len[k]), scratch.ctypes.data)
+                            host_ms += (time.perf_counter() - t1) * 1e3 * times
+                            n_anchored += times
+                            n_anchors += int(got) * times
+                host = (host_ms, n_anchored, n_anchors)
+            L.mrp_free(C.cast(S.allele_first, C.c_void_p))
+            for f_, _, _ in capi._EXTRACTED_ARRAYS:
+                L.mrp_free(C.cast(getattr(out[i], f_), C.c_void_p))
+        L.mrp_free(C.cast(out, C.c_void_p))
+        return results, est, sst, (n_ent, n_sym), wall, host
+
+    def joint(ctx, count=None):
+        """-> results, stats, wall ms of the C call (its own clock: the binding's conversions around it are not the library's)"""
+        got, st = capi.phase_aligned_chunks(ctx, chunks[:count], fwd, rev, params, options=opts, structs=built[:count], sv_threshold=SV_THRESHOLD)
+        return got, st, st.total_ms
+
+    with capi.Context(0) as ctx:
+        joint(ctx, 2)  # warm-up: module load, pools
+        ref = chain(ctx, anchors_too=True)
+        host_ms, host_pairs, host_anchors = ref[5]
+        joint(ctx)
+        walls_c, walls_j, stats_c, stats_j = [], [], [], []
+        for _ in range(a.reps):
+            got, st, w = joint(ctx)
+            walls_j.append(w)
+            stats_j.append(st)
+            ref = chain(ctx)
+            walls_c.append(ref[4])
+            stats_c.append(ref)
+    same = all(np.array_equal(g["hap"], r[0]) and g["phred"].tobytes() == r[1].tobytes() and np.array_equal(g["result"]["hap1"], r[2]) and
+               np.array_equal(g["result"]["hap2"], r[3]) for g, r in zip(got, ref[0]))
+    kj, kc = int(np.argsort(walls_j)[len(walls_j) // 2]), int(np.argsort(walls_c)[len(walls_c) // 2])
+    st = stats_j[kj]
+    _, est, sst, (n_ent, n_sym), _, _ = stats_c[kc]
+    assert host_pairs == st.pairs_anchored and host_anchors == st.anchors, (host_pairs, st.pairs_anchored, host_anchors, st.anchors)
+    comp_kernel = st.extract.kernel_ms + st.owners_ms + st.anchors_ms + st.chunks.pairhmm.kernel_ms + st.chunks.profile_ms + st.chunks.assign_ms
+    chain_kernel = est.kernel_ms + sst.pairhmm.kernel_ms + sst.profile_ms + sst.assign_ms
+    res = dict(chunks=a.chunks, distinct=a.distinct, reads=int(st.extract.reads), variants=int(st.variants), bubbles=int(st.bubbles),
+               substrings=int(st.entries), substrings_used=int(st.entries_used), owners=int(st.owners), pairs=int(st.pairs),
+               pairs_wave=int(st.chunks.pairhmm.pairs_wave), pairs_anchored=int(st.pairs_anchored), anchors=int(st.anchors), anchor_runs=int(st.anchor_runs),
+               composite_wall_ms=round(walls_j[kj], 2), composite_walls_ms=[round(x, 2) for x in sorted(walls_j)],
+               chain_wall_ms=round(walls_c[kc], 2), chain_walls_ms=[round(x, 2) for x in sorted(walls_c)],
+               chain_extract_total_ms=round(est.total_ms, 2), chain_string_call_total_ms=round(sst.total_ms, 2),
+               composite_kernel_ms=round(comp_kernel, 3), chain_kernel_ms=round(chain_kernel, 3),
+               extract_kernel_ms=round(st.extract.kernel_ms, 3), owners_kernel_ms=round(st.owners_ms, 3), anchors_kernel_ms=round(st.anchors_ms, 3),
+               host_anchors_ms_single_thread=round(host_ms, 3), pairhmm_kernel_ms=round(st.chunks.pairhmm.kernel_ms, 3),
+               chain_pairhmm_kernel_ms=round(sst.pairhmm.kernel_ms, 3), phase_device_ms=round(st.chunks.phase.device_ms, 2), composite_host_ms=round(st.chunks.host_ms, 2), chain_string_call_host_ms=round(sst.host_ms, 2),
+               composite_front_bytes_downloaded=int(st.front_bytes_downloaded), substring_symbols=int(n_sym),
+               chain_symbol_bytes_down_and_up=int(2 * n_sym), bytes_uploaded=int(st.extract.bytes_uploaded), identical_to_chain=bool(same))
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
