@@ -483,6 +483,15 @@ int64_t mrp_kmer_alignment_anchors(const uint8_t *x, int64_t lx, const uint8_t *
 int mrp_kmer_alignment_anchors_many(mrp_context *ctx, int64_t n_pairs, const uint8_t *pool, int64_t pool_bytes, const int64_t *x_off,
                                     const int32_t *x_len, const int64_t *y_off, const int32_t *y_len, int64_t *anchor_off_out,
                                     int64_t **anchors_out, mrp_pairhmm_stats *stats);
+/* The classes of equal substrings the reference's cachedScores tables are keyed by (bubbleGraph.c:1418,1844,2221: the substring alone),
+ * found on the device: site v owns entries [entry_first[v], entry_first[v + 1]) (n_sites + 1 offsets from 0), entry p is
+ * pool[off[p] .. + len[p]).  rep_out[p] = the lowest entry q <= p of p's site with the same length and the same bytes: the index,
+ * within the call, of the first entry of p's class (p itself for the first of a class).  Every entry gets one; who of a class may own
+ * its scores is the caller's to decide from these indices.  The pool is a host pool and is uploaded; 4 B per entry come back.
+ * MRP_ERR_ARG (NULL arrays, offsets not from 0 or not ascending, 2^31 entries or more, an entry outside the pool) before the context
+ * is looked at, then MRP_ERR_NO_DEVICE; rep_out is written only on success. */
+int mrp_equal_substring_classes(mrp_context *ctx, int64_t n_sites, const int64_t *entry_first, const uint8_t *pool, int64_t pool_bytes,
+                                const int64_t *off, const int32_t *len, int32_t *rep_out);
 /* computeForwardProbability for n_pairs (x, y) string pairs stored in one pool of symbols.  model_index (NULL: all 0)
  * selects models[i] per pair; anchor_off (NULL: no anchors anywhere) holds n_pairs + 1 offsets into anchors (pairs of
  * int64).  A pair without anchors covers its whole matrix, as in the reference.  out[i] = log probability (0.0 for two
@@ -817,6 +826,35 @@ int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_al
 int mrp_string_chunk_from_extracted(const mrp_extracted_chunk *x, const uint8_t *keep, const char *const *read_names,
                                     const uint8_t *read_forward_strand, mrp_string_chunk *out, int64_t **bubble_variant);
 
+/* The rest of an extracted chunk, host only: the mrp_string_chunk_rest margin phase would hand to the back half of its chunk loop
+ * (phase.c:349-365,413,419-432), beside the mrp_string_chunk of mrp_string_chunk_from_extracted(x, keep, ...) and its bubble_variant
+ * (n_bubbles entries).  xf is the extraction of the SAME reads over the chunk's filtered variants: the second call of
+ * extractReadSubstringsAtVariantPositions, phase.c:354-357, an independent walk with its own "starts no earlier than the entry before"
+ * state; fvariant_pos (0-based genome positions) and gt (2 per variant) are those variants'.
+ *   The filtered reads, in list order: (i) the reads x marks MRP_READ_FILTERED, ascending (low mapq, htsIntegration.c:1824-1827); (ii)
+ * the MRP_READ_KEPT reads of x whose keep byte is clear, ascending (the downsampling appends its discards to filteredReads,
+ * phase.c:364-365, htsIntegration.c:1204-1206); (iii) the reads x dropped but xf marks MRP_READ_KEPT, ascending: they are in neither list
+ * of the reference and are never tagged (they have no substring at a bubble), and are listed only so that their entries at filtered
+ * variants have an index.  filtered_read[f] = the chunk's read index of filtered read f; forward_strand[f] = read_forward_strand of it.
+ *   fsub_*: per bubble b the entries of x at variant bubble_variant[b] whose read is of kind (i) or (ii), by ascending filtered index
+ * (phase.c:419-432 tags filteredReads against the primary bubbles).
+ *   Variants: every variant of xf, index for index, with xf's alleles (prefix + allele + suffix) and gt as given (MRP_ERR_ARG for a gt
+ * outside the variant's alleles).  A variant with fvariant_pos outside [chunk_start, chunk_end) is listed with no entries -- the filter
+ * of bubbleGraph.c:2179, which the string rest leaves to the caller -- and comes back MRP_VARIANT_NOT_VISITED.  The others list the
+ * entries of every MRP_READ_KEPT read of xf in xf's ascending read order (buildVcfEntryToReadSubstringsMap, bubbleGraph.c:1281-1323);
+ * ventry_read is the read's own index when the read is primary (x: MRP_READ_KEPT and keep set), else x->n_reads + f.  Entries of reads
+ * xf marks MRP_READ_FILTERED are not listed (filteredReadsForFilteredVcfEntries, phase.c:354-357, is never read).
+ *   One malloc'd block (*block, released by mrp_free) holds every array of out, filtered_read and the rest's own pool: xf's symbols
+ * (valle_off / ventry_off are xf's offsets), then the (i) / (ii) substrings copied from x.  A chunk with no filtered read and no
+ * filtered variant gives the empty rest: every pointer, *filtered_read and *block NULL.
+ *   A consequence: a read of kind (i) or (ii) appears twice in the mrp_filtered_out of mrp_phase_string_chunks_with_filtered -- as
+ * primary index r, with no substrings (read_hap 0, totals 0 / 0), and as x->n_reads + f with its real result.
+ * MRP_ERR_ARG: a NULL argument, extractions over different read counts, a bubble_variant or an entry's read out of range, a bad gt. */
+int mrp_string_chunk_rest_from_extracted(const mrp_extracted_chunk *x, const uint8_t *keep, const uint8_t *read_forward_strand,
+                                         const int64_t *bubble_variant, int64_t n_bubbles, const mrp_extracted_chunk *xf,
+                                         const int64_t *fvariant_pos, const int32_t *gt, int64_t chunk_start, int64_t chunk_end,
+                                         mrp_string_chunk_rest *out, int32_t **filtered_read, void **block);
+
 /* ---- from alignments and a phased VCF to haplotype tags ---------------------------------------------------------------
  * The chunk loop of tools/tagFromPhasedVcf.c (:284-309): updateVcfEntriesWithSubstringsAndPositions,
  * extractReadSubstringsAtVariantPositions with filteredReads = NULL, bubbleGraph_partitionFilteredReadsFromPhasedVcfEntries
@@ -912,6 +950,59 @@ int mrp_phase_aligned_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_align
                              const mrp_params *params, int64_t min_phred, mrp_phase_result **out, int8_t *const *hap_out,
                              double *const *phred_out, mrp_profile_out *profiles_out, int64_t **bubble_variant_out,
                              mrp_phase_aligned_stats *stats);
+
+/* ---- the same with the back half of the chunk loop: from alignments to what margin phase writes for a chunk -------------------
+ * margin phase's whole chunk loop (phase.c:337-436) in one call: mrp_phase_aligned_chunks, then the filtered variants phased from the
+ * tagged primary reads (phase.c:413, bubbleGraph.c:2140-2351) and the filtered reads, with the primary reads the phasing left untagged,
+ * haplotagged against the fragment (phase.c:419-436, bubbleGraph.c:1749-1943).  No substring symbol leaves the device: the reads are
+ * extracted a second time over the rest's variants in the same staged run (phase.c:354-357), the classes of equal substrings are found
+ * on the device (mrp_equal_substring_classes' kernel), and the anchored pairs of heterozygous filtered variants (bubbleGraph.c:2253-2263)
+ * go through the anchors kernel with the front's. */
+typedef struct mrp_aligned_chunk_rest { /* the chunk's filtered variants (filteredChunkVcfEntries, phase.c:331-333), fields as mrp_aligned_chunk's */
+    int64_t n_variants;
+    const int64_t *variant_pos, *allele_first, *allele_off;
+    const int32_t *allele_len;
+    const char *allele_chars; int64_t allele_bytes;
+    const uint8_t *is_sv;
+    const int32_t *gt;                  /* 2 * n_variants: gt1, gt2, allele indices within the variant */
+} mrp_aligned_chunk_rest;
+
+typedef struct mrp_phase_aligned_filtered_stats {
+    mrp_phase_aligned_stats aligned;  /* as mrp_phase_aligned_chunks fills it, over BOTH extractions: extract.reads counts every read twice
+                                       * (the run stages the reads once per variant set), variants and entries are those of both sets,
+                                       * pairs / pairs_anchored / anchors / anchor_runs cover the speculative pairs as well, and
+                                       * front_bytes_downloaded = 16 B of totals + the entry CSR (8 B per variant of both sets + 8) + 20 B per
+                                       * entry of both extractions (length 8, read 4, owner 4, class representative 4) + 1 B per read of
+                                       * extract.reads + 4 B per anchored pair + 12 B per anchor run */
+    int64_t filtered_variants;        /* variants of the rests */
+    int64_t filtered_reads;           /* filtered reads over all chunks (the lengths of filtered_read_out's lists) */
+    int64_t filtered_entries;         /* substrings the second extraction made */
+    int64_t pairs_scored;             /* as mrp_string_filtered_stats */
+    int64_t pairs_speculative;
+    int64_t pairs_read_by_results;
+    double filtered_ms;               /* the back half's kernels, HIP events */
+    double classes_ms;                /* HIP events around the kernel that finds the classes of equal substrings */
+} mrp_phase_aligned_filtered_stats;
+
+/* For every chunk, bit for bit, what this chain returns: mrp_extract_read_substrings over the chunk -> x; the same over the same reads
+ * and the rest's variants -> xf; mrp_string_chunk_from_extracted(x, keep[c], ...); mrp_string_chunk_rest_from_extracted(x, keep[c],
+ * strands, bubble_variant, xf, rest[c].variant_pos, rest[c].gt, chunk_start, chunk_end); mrp_phase_string_chunks_with_filtered.
+ * Returned: everything mrp_phase_aligned_chunks returns; filtered_out[c] in the chain's convention (reads: the chunk's n_reads, then its
+ * filtered reads -- a filtered read of the chunk appears twice, see mrp_string_chunk_rest_from_extracted); filtered_read_out[c]: a
+ * malloc'd array (mrp_free) of the chunk's read index of every filtered read, closed by a -1.
+ * Errors, in this order: MRP_ERR_ARG before the context is looked at (the extraction's checks on both variant sets -- a rest's variants
+ * not ascending or outside the overlap among them; in their messages chunk n_chunks + c is the rest of chunk c --, mrp_phase_aligned_chunks'
+ * own, a NULL rest / filtered_out / filtered_read_out, a gt outside the variant's alleles); MRP_ERR_UNSUPPORTED for the SV split mode or
+ * run-length encoding, without a context too; MRP_ERR_NO_DEVICE; MRP_ERR_UNSUPPORTED for a pair whose widest diagonal exceeds 2 048
+ * cells (with a rest every substring of a bubble may be aligned unanchored, as mrp_phase_string_chunks_with_filtered states).  On an
+ * error nothing is returned and filtered_out is zeroed.  stats may be NULL. */
+int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
+                                           const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
+                                           const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                                           int64_t sv_threshold, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                           mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                                           int64_t **bubble_variant_out, mrp_filtered_out *filtered_out, int32_t **filtered_read_out,
+                                           mrp_phase_aligned_filtered_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -38,7 +38,8 @@ EXPORTED_SYMBOLS = [
     "mrp_extract_read_substrings", "mrp_string_chunk_from_extracted", "mrp_string_chunk_units", "mrp_queue_phase_string_chunks",
     "mrp_phase_string_chunks_on_devices", "mrp_phase_string_chunks_with_filtered", "mrp_queue_phase_string_chunks_with_filtered",
     "mrp_phase_string_chunks_with_filtered_on_devices", "mrp_haptag_sites_from_extracted", "mrp_haplotag_aligned_chunks",
-    "mrp_kmer_alignment_anchors_many", "mrp_phase_aligned_chunks",
+    "mrp_kmer_alignment_anchors_many", "mrp_phase_aligned_chunks", "mrp_string_chunk_rest_from_extracted", "mrp_equal_substring_classes",
+    "mrp_phase_aligned_chunks_with_filtered",
 ]
 
 
@@ -296,6 +297,17 @@ class PhaseAlignedStats(C.Structure):
                 ("anchor_runs", C.c_int64), ("front_bytes_downloaded", C.c_int64), ("owners_ms", C.c_double), ("anchors_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class AlignedChunkRest(C.Structure):
+    _fields_ = [("n_variants", C.c_int64), ("variant_pos", C.c_void_p), ("allele_first", C.c_void_p), ("allele_off", C.c_void_p),
+                ("allele_len", C.c_void_p), ("allele_chars", C.c_void_p), ("allele_bytes", C.c_int64), ("is_sv", C.c_void_p), ("gt", C.c_void_p)]
+
+
+class PhaseAlignedFilteredStats(C.Structure):
+    _fields_ = [("aligned", PhaseAlignedStats), ("filtered_variants", C.c_int64), ("filtered_reads", C.c_int64), ("filtered_entries", C.c_int64),
+                ("pairs_scored", C.c_int64), ("pairs_speculative", C.c_int64), ("pairs_read_by_results", C.c_int64), ("filtered_ms", C.c_double),
+                ("classes_ms", C.c_double)]
+
+
 def load():
     """dlopen the in-tree library; raises if it has not been built (no fallback)."""
     global _lib
@@ -394,7 +406,13 @@ def load():
                                               P(HaplotagAlignedStats)]
     L.mrp_phase_aligned_chunks.argtypes = [vp, i64, P(AlignedChunk), P(vp), P(vp), P(ExtractOptions), P(PairHmm), P(PairHmm), i64, i64, C.c_double,
                                            P(Params), i64, P(P(PhaseResult)), P(vp), P(vp), P(ProfileOut), P(vp), P(PhaseAlignedStats)]
+    L.mrp_phase_aligned_chunks_with_filtered.argtypes = [vp, i64, P(AlignedChunk), P(AlignedChunkRest), P(vp), P(vp), P(ExtractOptions), P(PairHmm),
+                                                         P(PairHmm), i64, i64, C.c_double, P(Params), i64, P(P(PhaseResult)), P(vp), P(vp),
+                                                         P(ProfileOut), P(vp), P(FilteredOut), P(vp), P(PhaseAlignedFilteredStats)]
     L.mrp_kmer_alignment_anchors_many.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, P(vp), P(PairHmmStats)]
+    L.mrp_string_chunk_rest_from_extracted.argtypes = [P(ExtractedChunk), vp, vp, vp, i64, P(ExtractedChunk), vp, vp, i64, i64, P(StringChunkRest),
+                                                       P(vp), P(vp)]
+    L.mrp_equal_substring_classes.argtypes = [vp, i64, vp, vp, i64, vp, vp, vp]
     L.mrp_kmer_alignment_anchors.argtypes = [vp, i64, vp, i64, vp]
     L.mrp_kmer_alignment_anchors.restype = i64
     L.mrp_phase_chunks_on_devices.argtypes = [vp, i32, i64, P(ChunkDesc), P(Params), i64, P(P(PhaseResult)), P(QueueStats)]
@@ -1560,6 +1578,84 @@ def string_chunk_from_extracted(x: dict, read_names, read_forward_strand, keep=N
     return sc, raw["bubble_variant"], raw
 
 
+class ExtractedRest:
+    """What mrp_string_chunk_rest_from_extracted returned for one chunk: struct (the StringChunkRest itself, pointing into the C block: pass
+    it on unchanged), filtered_read (int32, the chunk's read index of every filtered read), raw (numpy copies of every array of the
+    struct, "pool" and "forward_strand" included) and rest (the same as the dict capi.string_chunk_rest_struct takes; None for the empty
+    rest).  The block is released by close()."""
+
+    def __init__(self, struct, block, filtered_read, raw, rest, hold):
+        self.struct, self.block, self.filtered_read, self.raw, self.rest, self._hold = struct, block, filtered_read, raw, rest, hold
+
+    def close(self):
+        if self.block is not None:
+            load().mrp_free(self.block)
+            self.block = None
+
+    def __del__(self):
+        self.close()
+
+
+def string_chunk_rest_from_extracted(x: dict, xf: dict, read_forward_strand, bubble_variant, fvariant_pos, gt, chunk_start: int, chunk_end: int,
+                                     keep=None, nulls=()) -> ExtractedRest:
+    """mrp_string_chunk_rest_from_extracted over two extract_read_substrings results (x: the primary variants, xf: the same reads over the
+    filtered variants); gt: int32 [n, 2] or flat.  nulls names arguments to pass as NULL (for the argument checks)."""
+    L = load()
+    X, hold_x = extracted_struct(x)
+    XF, hold_f = extracted_struct(xf)
+    strand = np.ascontiguousarray(read_forward_strand, np.uint8)
+    km = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+    bv = np.ascontiguousarray(bubble_variant, np.int64)
+    fpos = np.ascontiguousarray(fvariant_pos, np.int64)
+    g = np.ascontiguousarray(gt, np.int32).reshape(-1)
+    ptr = lambda name, a: None if a is None or name in nulls or a.size == 0 else a.ctypes.data
+    R = StringChunkRest()
+    fr, blk = C.c_void_p(), C.c_void_p()
+    _check(L.mrp_string_chunk_rest_from_extracted(None if "x" in nulls else C.byref(X), ptr("keep", km), ptr("strand", strand), ptr("bubble_variant", bv),
+                                                  len(bv), None if "xf" in nulls else C.byref(XF), ptr("fvariant_pos", fpos), ptr("gt", g),
+                                                  int(chunk_start), int(chunk_end), None if "out" in nulls else C.byref(R),
+                                                  None if "filtered_read" in nulls else C.byref(fr), None if "block" in nulls else C.byref(blk)))
+    nf, nv, nb = int(R.n_filtered), int(R.n_variants), len(bv)
+    if blk.value is None:
+        assert nf == 0 and nv == 0 and fr.value is None and bytes(R) == bytes(StringChunkRest()), "an empty rest must be all NULL"
+        return ExtractedRest(R, None, np.zeros(0, np.int32), {}, None, (hold_x, hold_f))
+    f_first = _as_np(R.fsub_first, nb + 1, np.int64)
+    a_first = _as_np(R.valle_first, nv + 1, np.int64)
+    e_first = _as_np(R.ventry_first, nv + 1, np.int64)
+    nfs, na, ne = int(f_first[nb]), int(a_first[nv]), int(e_first[nv])
+    raw = dict(forward_strand=_as_np(R.forward_strand, nf, np.uint8), pool=_as_np(R.pool, int(R.pool_bytes), np.uint8), fsub_first=f_first,
+               fsub_off=_as_np(R.fsub_off, nfs, np.int64), fsub_len=_as_np(R.fsub_len, nfs, np.int32), fsub_read=_as_np(R.fsub_read, nfs, np.int32),
+               valle_first=a_first, valle_off=_as_np(R.valle_off, na, np.int64), valle_len=_as_np(R.valle_len, na, np.int32),
+               gt=_as_np(R.gt, 2 * nv, np.int32), ventry_first=e_first, ventry_read=_as_np(R.ventry_read, ne, np.int32),
+               ventry_off=_as_np(R.ventry_off, ne, np.int64), ventry_len=_as_np(R.ventry_len, ne, np.int32))
+    pool = raw["pool"]
+    cut = lambda o, l: pool[int(o):int(o) + int(l)].copy()
+    fsubs = [[(int(raw["fsub_read"][k]), cut(raw["fsub_off"][k], raw["fsub_len"][k])) for k in range(int(f_first[b]), int(f_first[b + 1]))] for b in range(nb)]
+    variants = [([cut(raw["valle_off"][a], raw["valle_len"][a]) for a in range(int(a_first[v]), int(a_first[v + 1]))],
+                 (int(raw["gt"][2 * v]), int(raw["gt"][2 * v + 1])),
+                 [(int(raw["ventry_read"][k]), cut(raw["ventry_off"][k], raw["ventry_len"][k])) for k in range(int(e_first[v]), int(e_first[v + 1]))])
+                for v in range(nv)]
+    rest = dict(forward_strand=raw["forward_strand"], fsubs=fsubs, variants=variants)
+    return ExtractedRest(R, blk, _as_np(fr, nf, np.int32), raw, rest, (hold_x, hold_f))
+
+
+def equal_substring_classes(ctx: Optional[Context], entry_first, pool, off, length, nulls=()) -> np.ndarray:
+    """mrp_equal_substring_classes -> rep int32 [n_entries]: per entry the first entry of its site with the same substring.  ctx None
+    passes a NULL context; nulls names arguments to pass as NULL (for the argument checks)."""
+    L = load()
+    first = np.ascontiguousarray(entry_first, np.int64)
+    pool = np.ascontiguousarray(pool, np.uint8)
+    off, length = _opt(off, np.int64), _opt(length, np.int32)
+    rep = np.full(len(off), -7, np.int32)
+    ptr = lambda name, a: None if name in nulls or a.size == 0 else a.ctypes.data
+    rc = L.mrp_equal_substring_classes(ctx.h if ctx else None, len(first) - 1, ptr("entry_first", first), ptr("pool", pool), pool.size, ptr("off", off),
+                                       ptr("len", length), ptr("rep_out", rep))
+    if rc != MRP_OK:
+        assert (rep == -7).all(), "outputs written on an error"
+    _check(rc)
+    return rep
+
+
 # ---- haplotagging aligned reads from a phased VCF (mrp_haptag_sites_from_extracted, mrp_haplotag_aligned_chunks) ----
 
 _HAPTAG_SITE_ARRAYS = (("allele_first", np.int64, "s1"), ("allele_off", np.int64, "a"), ("allele_len", np.int32, "a"), ("compare", np.int32, "s2"),
@@ -1631,9 +1727,36 @@ def haplotag_aligned_chunks(ctx: Optional[Context], chunks, gts, forward_model: 
 
 # ---- from alignments to haplotypes and HP tags in one call (mrp_phase_aligned_chunks) ----
 
+def aligned_chunk_rest_struct(filtered_chunk, gt):
+    """mrp_aligned_chunk_rest from a margin_amd.synth.AlignedChunk that holds the filtered variants (its reads are not looked at) and their gt
+    (int32 [n, 2] or flat); returns (AlignedChunkRest, the arrays it points into)"""
+    S, keep = aligned_chunk_struct(filtered_chunk)
+    keep["gt"] = np.ascontiguousarray(gt, np.int32).reshape(-1)
+    assert keep["gt"].size == 2 * int(S.n_variants)
+    R = AlignedChunkRest(S.n_variants, S.variant_pos, S.allele_first, S.allele_off, S.allele_len, S.allele_chars, S.allele_bytes, S.is_sv,
+                         keep["gt"].ctypes.data if keep["gt"].size else None)
+    return R, keep
+
+
+def phase_aligned_chunks_with_filtered(ctx: Optional[Context], chunks, rests, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm],
+                                       params: Optional[Params], **kw):
+    """mrp_phase_aligned_chunks_with_filtered -> (phase_aligned_chunks' list of dicts, each with "filtered" (dict(read_hap, h1, h2 over the
+    chunk's reads then its filtered reads, variant_state, cis, trans)) and "filtered_read" (int32, the chunk's read index of every filtered
+    read), PhaseAlignedFilteredStats).  rests: per chunk (filtered AlignedChunk, gt); or None with rest_structs =
+    [aligned_chunk_rest_struct(...)].  Further nulls: "rest", "filtered_out", "filtered_read_out", "gt[0]"."""
+    return _phase_aligned(ctx, chunks, forward_model, reverse_model, params, rests=rests, with_rest=True, **kw)
+
+
 def phase_aligned_chunks(ctx: Optional[Context], chunks, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm], params: Optional[Params],
-                         options: Optional[dict] = None, keeps=None, min_phred: int = 0, expansion: int = 4, sv_threshold: int = 512,
-                         het_substitution_probability: float = 0.0, profiles: bool = False, structs=None, nulls=()):
+                         **kw):
+    """mrp_phase_aligned_chunks; arguments and results as _phase_aligned states them"""
+    return _phase_aligned(ctx, chunks, forward_model, reverse_model, params, **kw)
+
+
+def _phase_aligned(ctx: Optional[Context], chunks, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm], params: Optional[Params],
+                   options: Optional[dict] = None, keeps=None, min_phred: int = 0, expansion: int = 4, sv_threshold: int = 512,
+                   het_substitution_probability: float = 0.0, profiles: bool = False, structs=None, nulls=(), rests=None, rest_structs=None,
+                   with_rest: bool = False):
     """mrp_phase_aligned_chunks -> (per chunk dict(result, hap int8 [n_reads], phred, bubble_variant int64 [n_bubbles][, profile]),
     PhaseAlignedStats).  keeps: None, or per chunk None / a uint8 mask over its reads.  ctx / a model / params None pass NULL;
     nulls names further arguments to pass as NULL ("options", "out", "hap_out", "read_names", "hap_out[0]", "phred_out[0]",
@@ -1664,12 +1787,29 @@ def phase_aligned_chunks(ctx: Optional[Context], chunks, forward_model: Optional
     res = (C.POINTER(PhaseResult) * max(n, 1))()
     prof = (ProfileOut * max(n, 1))() if profiles else None
     bv = (C.c_void_p * max(n, 1))()
-    st = PhaseAlignedStats()
     by = lambda m: None if m is None else C.byref(m)
-    rc = L.mrp_phase_aligned_chunks(ctx.h if ctx else None, n, arr, None if "read_names" in nulls else name_ptrs, None if keeps is None else mask_ptrs,
-                                    None if "options" in nulls else C.byref(opt), by(forward_model), by(reverse_model), int(expansion), int(sv_threshold),
-                                    float(het_substitution_probability), by(params), int(min_phred), None if "out" in nulls else res,
-                                    None if "hap_out" in nulls else hp, pp, prof, bv, C.byref(st))
+    if not with_rest:
+        st = PhaseAlignedStats()
+        rc = L.mrp_phase_aligned_chunks(ctx.h if ctx else None, n, arr, None if "read_names" in nulls else name_ptrs, None if keeps is None else mask_ptrs,
+                                        None if "options" in nulls else C.byref(opt), by(forward_model), by(reverse_model), int(expansion), int(sv_threshold),
+                                        float(het_substitution_probability), by(params), int(min_phred), None if "out" in nulls else res,
+                                        None if "hap_out" in nulls else hp, pp, prof, bv, C.byref(st))
+    else:
+        rbuilt = rest_structs if rest_structs is not None else [aligned_chunk_rest_struct(f, g) for f, g in rests]
+        rarr = (AlignedChunkRest * max(n, 1))(*[b[0] for b in rbuilt])
+        if "gt[0]" in nulls:
+            rarr[0].gt = None
+        fout = (FilteredOut * max(n, 1))()
+        fout[0].n_reads = 77  # (zeroed whatever the outcome)
+        fr = (C.c_void_p * max(n, 1))()
+        st = PhaseAlignedFilteredStats()
+        rc = L.mrp_phase_aligned_chunks_with_filtered(ctx.h if ctx else None, n, arr, None if "rest" in nulls else rarr, None if "read_names" in nulls else name_ptrs,
+                                                      None if keeps is None else mask_ptrs, None if "options" in nulls else C.byref(opt), by(forward_model),
+                                                      by(reverse_model), int(expansion), int(sv_threshold), float(het_substitution_probability), by(params),
+                                                      int(min_phred), None if "out" in nulls else res, None if "hap_out" in nulls else hp, pp, prof, bv,
+                                                      None if "filtered_out" in nulls else fout, None if "filtered_read_out" in nulls else fr, C.byref(st))
+        if rc != MRP_OK and n > 0 and not {"rest", "filtered_out", "filtered_read_out"} & set(nulls):
+            assert bytes(fout) == bytes((FilteredOut * max(n, 1))()) and not any(fr[i] for i in range(n)), "filtered_out not zeroed on an error"
     if rc != MRP_OK:
         untouched = all((h == 99).all() for h in hap) and all(np.isnan(p).all() for p in phred) and not any(bool(res[i]) for i in range(n)) and \
             not any(bv[i] for i in range(n)) and (prof is None or not any(prof[i].seqs or prof[i].pool for i in range(n)))
@@ -1693,5 +1833,18 @@ def phase_aligned_chunks(ctx: Optional[Context], chunks, forward_model: Optional
             d["profile"].update(allele_number=an, sub=_as_np(P.substitution, int((A * A).sum()), np.uint16), prior=_as_np(P.prior, int(A.sum()), np.uint16))
             for f in ("seqs", "read_of_seq", "pool", "allele_number", "substitution", "prior"):
                 L.mrp_free(C.cast(getattr(P, f), C.c_void_p))
+        if with_rest:
+            O = fout[i]
+            nrd, nv = int(O.n_reads), int(O.n_variants)
+            d["filtered"] = dict(read_hap=_as_np(O.read_hap, nrd, np.int32), h1=_as_np(O.h1, nrd, np.float64), h2=_as_np(O.h2, nrd, np.float64),
+                                 variant_state=_as_np(O.variant_state, nv, np.int32), cis=_as_np(O.cis, nv, np.float64), trans=_as_np(O.trans, nv, np.float64))
+            for f in ("read_hap", "h1", "h2", "variant_state", "cis", "trans"):
+                L.mrp_free(C.cast(getattr(O, f), C.c_void_p))
+            nf = 0
+            ends = C.cast(fr[i], C.POINTER(C.c_int32))
+            while ends[nf] != -1:  # the list is closed by a -1
+                nf += 1
+            d["filtered_read"] = _as_np(fr[i], nf, np.int32)
+            L.mrp_free(fr[i])
         out.append(d)
     return out, st

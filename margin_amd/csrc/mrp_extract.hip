@@ -1011,6 +1011,155 @@ int mrp_string_chunk_from_extracted(const mrp_extracted_chunk *x, const uint8_t 
     return MRP_OK;
 }
 
+int mrp_string_chunk_rest_from_extracted(const mrp_extracted_chunk *x, const uint8_t *keep, const uint8_t *read_forward_strand,
+                                         const int64_t *bubble_variant, int64_t n_bubbles, const mrp_extracted_chunk *xf,
+                                         const int64_t *fvariant_pos, const int32_t *gt, int64_t chunk_start, int64_t chunk_end,
+                                         mrp_string_chunk_rest *out, int32_t **filtered_read, void **block) {
+    static const char *who = "mrp_string_chunk_rest_from_extracted";
+    if (!x || !xf || !out || !filtered_read || !block || x->n_variants < 0 || x->n_reads < 0 || xf->n_variants < 0 || n_bubbles < 0 || xf->pool_bytes < 0 ||
+        x->pool_bytes < 0)
+        return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
+    if (xf->n_reads != x->n_reads)
+        return mrp_set_error(MRP_ERR_ARG, "%s: the two extractions are over %lld and %lld reads: not the same reads", who, (long long) x->n_reads, (long long) xf->n_reads);
+    const int64_t nr = x->n_reads, nv = xf->n_variants;
+    if (nr >= (1ll << 30)) return mrp_set_error(MRP_ERR_ARG, "%s: bad sizes", who);
+    if (nr > 0 && (!read_forward_strand || !x->read_status || !xf->read_status)) return mrp_set_error(MRP_ERR_ARG, "%s: null read array", who);
+    if (!x->entry_first || !xf->entry_first || !xf->allele_first || (n_bubbles > 0 && !bubble_variant) || (nv > 0 && (!fvariant_pos || !gt)))
+        return mrp_set_error(MRP_ERR_ARG, "%s: null array", who);
+    const int64_t ne = x->entry_first[x->n_variants], nef = xf->entry_first[nv], naf = xf->allele_first[nv];
+    if ((ne > 0 && (!x->entry_read || !x->entry_off || !x->entry_len)) || (x->pool_bytes > 0 && !x->pool) || (nef > 0 && (!xf->entry_read || !xf->entry_off || !xf->entry_len)) ||
+        (naf > 0 && (!xf->allele_off || !xf->allele_len)) || (xf->pool_bytes > 0 && !xf->pool))
+        return mrp_set_error(MRP_ERR_ARG, "%s: null array", who);
+    for (int64_t b = 0; b < n_bubbles; b++)
+        if (bubble_variant[b] < 0 || bubble_variant[b] >= x->n_variants)
+            return mrp_set_error(MRP_ERR_ARG, "%s: bubble %lld names variant %lld of %lld", who, (long long) b, (long long) bubble_variant[b], (long long) x->n_variants);
+    for (int64_t e = 0; e < ne; e++)
+        if (x->entry_read[e] < 0 || x->entry_read[e] >= nr || x->entry_len[e] < 0 || x->entry_off[e] < 0 || x->entry_off[e] + x->entry_len[e] > x->pool_bytes)
+            return mrp_set_error(MRP_ERR_ARG, "%s: entry %lld names read %d or lies outside the pool", who, (long long) e, x->entry_read[e]);
+    for (int64_t e = 0; e < nef; e++)
+        if (xf->entry_read[e] < 0 || xf->entry_read[e] >= nr)
+            return mrp_set_error(MRP_ERR_ARG, "%s: entry %lld at the filtered variants names read %d", who, (long long) e, xf->entry_read[e]);
+    for (int64_t v = 0; v < nv; v++) {
+        const int64_t k = xf->allele_first[v + 1] - xf->allele_first[v];
+        for (int w = 0; w < 2; w++)
+            if (gt[2 * v + w] < 0 || gt[2 * v + w] >= k)
+                return mrp_set_error(MRP_ERR_ARG, "%s: filtered variant %lld: genotype %d outside its %lld alleles", who, (long long) v, gt[2 * v + w], (long long) k);
+    }
+    /* the filtered reads: (i) low mapq (htsIntegration.c:1824-1827), (ii) the downsampling's discards (phase.c:364-365,
+     * htsIntegration.c:1204-1206), (iii) reads with a substring at a filtered variant only */
+    auto primary = [&](int64_t r) { return x->read_status[r] == MRP_READ_KEPT && (!keep || keep[r]); };
+    auto kind = [&](int64_t r) {
+        if (x->read_status[r] == MRP_READ_FILTERED) return 0;
+        if (x->read_status[r] == MRP_READ_KEPT) return primary(r) ? -1 : 1;
+        return xf->read_status[r] == MRP_READ_KEPT ? 2 : -1;
+    };
+    int64_t n_kind[3] = {0, 0, 0};
+    for (int64_t r = 0; r < nr; r++) {
+        const int k = kind(r);
+        if (k >= 0) n_kind[k]++;
+    }
+    const int64_t nf = n_kind[0] + n_kind[1] + n_kind[2];
+    memset(out, 0, sizeof(*out));
+    *filtered_read = nullptr;
+    *block = nullptr;
+    if (nf == 0 && nv == 0) return MRP_OK; /* the empty rest */
+    /* sizes: the (i) / (ii) substrings at the bubbles, the kept reads' entries at the filtered variants inside the chunk (bubbleGraph.c:2179) */
+    auto inside = [&](int64_t v) { return fvariant_pos[v] >= chunk_start && fvariant_pos[v] < chunk_end; };
+    int64_t nfs = 0, nve = 0, fs_bytes = 0;
+    for (int64_t b = 0; b < n_bubbles; b++)
+        for (int64_t e = x->entry_first[bubble_variant[b]]; e < x->entry_first[bubble_variant[b] + 1]; e++) {
+            const int k = kind(x->entry_read[e]);
+            if (k == 0 || k == 1) { nfs++; fs_bytes += x->entry_len[e]; }
+        }
+    for (int64_t v = 0; v < nv; v++)
+        if (inside(v))
+            for (int64_t e = xf->entry_first[v]; e < xf->entry_first[v + 1]; e++) nve += xf->read_status[xf->entry_read[e]] == MRP_READ_KEPT;
+    /* one block: int64 fsub_first (n_bubbles + 1), fsub_off (nfs), valle_first, ventry_first (nv + 1 each), valle_off (naf), ventry_off (nve);
+     * int32 fsub_len, fsub_read (nfs each), valle_len (naf), gt (2 nv), ventry_read, ventry_len (nve each), filtered_read, the read -> filtered
+     * index table (nr, scratch); then forward_strand (nf) and the pool */
+    const size_t n64 = (size_t) n_bubbles + 1 + (size_t) nfs + 2 * ((size_t) nv + 1) + (size_t) naf + (size_t) nve;
+    const size_t n32 = 2 * (size_t) nfs + (size_t) naf + 2 * (size_t) nv + 2 * (size_t) nve + (size_t) nf + (size_t) nr;
+    const int64_t pool_bytes = xf->pool_bytes + fs_bytes;
+    uint8_t *blk = (uint8_t *) malloc(8 * n64 + 4 * n32 + (size_t) nf + (size_t) pool_bytes + 8);
+    if (!blk) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
+    int64_t *f_first = (int64_t *) blk, *f_off = f_first + n_bubbles + 1, *va_first = f_off + nfs, *ve_first = va_first + nv + 1, *va_off = ve_first + nv + 1,
+            *ve_off = va_off + naf;
+    int32_t *f_len = (int32_t *) (ve_off + nve), *f_read = f_len + nfs, *va_len = f_read + nfs, *g = va_len + naf, *ve_read = g + 2 * nv, *ve_len = ve_read + nve,
+            *f_of = ve_len + nve, *findex = f_of + nf;
+    uint8_t *strand = (uint8_t *) (findex + nr), *pool = strand + nf;
+    {
+        int64_t at[3] = {0, n_kind[0], n_kind[0] + n_kind[1]};
+        for (int64_t r = 0; r < nr; r++) {
+            const int k = kind(r);
+            findex[r] = k < 0 ? -1 : (int32_t) at[k]++;
+            if (k < 0) continue;
+            f_of[findex[r]] = (int32_t) r;
+            strand[findex[r]] = read_forward_strand[r] != 0;
+        }
+    }
+    if (xf->pool_bytes) memcpy(pool, xf->pool, (size_t) xf->pool_bytes);
+    /* per bubble the substrings of the (i) and (ii) reads in ascending filtered index: x lists a variant's entries in ascending read
+     * order, and every (i) read comes before every (ii) read */
+    int64_t is = 0, pat = xf->pool_bytes;
+    f_first[0] = 0;
+    for (int64_t b = 0; b < n_bubbles; b++) {
+        const int64_t v = bubble_variant[b];
+        for (int pass = 0; pass < 2; pass++)
+            for (int64_t e = x->entry_first[v]; e < x->entry_first[v + 1]; e++) {
+                const int32_t r = x->entry_read[e];
+                if (kind(r) != pass) continue;
+                f_off[is] = pat;
+                f_len[is] = x->entry_len[e];
+                f_read[is] = findex[r];
+                if (x->entry_len[e]) memcpy(pool + pat, x->pool + x->entry_off[e], (size_t) x->entry_len[e]);
+                pat += x->entry_len[e];
+                is++;
+            }
+        f_first[b + 1] = is;
+    }
+    /* every variant of xf, index for index; one outside the chunk keeps its alleles and gt and lists no entry (bubbleGraph.c:2179); the others
+     * list the entries of the reads xf kept, in its ascending read order (buildVcfEntryToReadSubstringsMap, bubbleGraph.c:1281-1323; the
+     * low-mapq reads' entries, filteredReadsForFilteredVcfEntries of phase.c:354-357, are never read) */
+    int64_t ie = 0;
+    ve_first[0] = 0;
+    for (int64_t v = 0; v <= nv; v++) va_first[v] = xf->allele_first[v];
+    for (int64_t a = 0; a < naf; a++) { va_off[a] = xf->allele_off[a]; va_len[a] = xf->allele_len[a]; }
+    for (int64_t v = 0; v < nv; v++) {
+        g[2 * v] = gt[2 * v];
+        g[2 * v + 1] = gt[2 * v + 1];
+        if (inside(v))
+            for (int64_t e = xf->entry_first[v]; e < xf->entry_first[v + 1]; e++) {
+                const int32_t r = xf->entry_read[e];
+                if (xf->read_status[r] != MRP_READ_KEPT) continue;
+                ve_read[ie] = primary(r) ? r : (int32_t) (nr + findex[r]);
+                ve_off[ie] = xf->entry_off[e];
+                ve_len[ie] = xf->entry_len[e];
+                ie++;
+            }
+        ve_first[v + 1] = ie;
+    }
+    out->n_filtered = nf;
+    out->forward_strand = strand;
+    out->pool = pool;
+    out->pool_bytes = pool_bytes;
+    out->fsub_first = f_first;
+    out->fsub_off = f_off;
+    out->fsub_len = f_len;
+    out->fsub_read = f_read;
+    out->n_variants = nv;
+    out->valle_first = va_first;
+    out->valle_off = va_off;
+    out->valle_len = va_len;
+    out->gt = g;
+    out->ventry_first = ve_first;
+    out->ventry_read = ve_read;
+    out->ventry_off = ve_off;
+    out->ventry_len = ve_len;
+    *filtered_read = f_of;
+    *block = blk;
+    return MRP_OK;
+}
+
 int mrp_haptag_sites_from_extracted(int64_t n_chunks, const mrp_extracted_chunk *x, const int32_t *const *gt, mrp_haptag_sites *out, int64_t *read_first) {
     static const char *who = "mrp_haptag_sites_from_extracted";
     if (n_chunks < 0 || (n_chunks > 0 && (!x || !gt)) || !out || !read_first) return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);

@@ -3,9 +3,10 @@
  * (computeForwardProbability, impl/pairwiseAligner.c:849-903) for batches of string pairs, and the alleleReadSupports
  * loop around it (impl/bubbleGraph.c:1421-1464), and the filtered-read / filtered-variant loops after the phasing
  * (:1749-2351: the supports stay on the device, a scoring kernel reduces them), the string-chunk calls built on them and, at the end
- * of the file, the two composites over the extraction's result in HBM (ha_owners_kernel): the haplotagging of aligned reads from a
- * phased VCF (mrp_haplotag_aligned_chunks) and the phasing of aligned chunks (mrp_phase_aligned_chunks; its k-mer anchors are made by
- * mrp_anchors.hip).  gfx950 only; compiled with -ffp-contract=off.
+ * of the file, the composites over the extraction's result in HBM (ha_owners_kernel, ec_classes_kernel): the haplotagging of aligned
+ * reads from a phased VCF (mrp_haplotag_aligned_chunks), the phasing of aligned chunks (mrp_phase_aligned_chunks; its k-mer anchors are
+ * made by mrp_anchors.hip) and the same with the filtered back half (mrp_phase_aligned_chunks_with_filtered).  gfx950 only; compiled
+ * with -ffp-contract=off.
  *
  * The recursion (stateMachine3_cellCalculate, impl/stateMachine.c:562-586) gives every dp cell (x, y) three states from
  * its neighbours (x-1, y), (x-1, y-1), (x, y-1); a neighbour outside the band contributes nothing, which is what a
@@ -898,6 +899,48 @@ __global__ void __launch_bounds__(PHM_WAVE) ha_owners_kernel(const int64_t *__re
     }
 }
 
+/* The classes of equal substrings of every site (what sc_filtered_task finds by sorting host symbols), over symbols that lie in HBM: a wave
+ * per site, lanes striding over the site's entries, waves striding over the sites, as ha_owners_kernel.  Pass one gives EVERY entry of the
+ * site a key (length, FNV-1a of the symbols) -- no mask: who may own is decided later, from indices.  Pass two gives entry p its
+ * representative rep[p]: the lowest entry q <= p of the site with p's length and bytes, found by walking the site from its start and
+ * comparing symbols only where the keys agree (the hash only skips comparisons; two distinct strings with one key are told apart by
+ * their bytes).  Every loop is bounded by the site's entry count or a substring's length; stores are plain vector stores; the barrier
+ * between the passes is the wave's own workgroup's.  LenT: int32 lengths (the public seam) or the extraction's int64 ones. */
+template <typename LenT>
+__global__ void __launch_bounds__(PHM_WAVE) ec_classes_kernel(const int64_t *__restrict__ first, int64_t n_sites, const LenT *__restrict__ len,
+                                                              const int64_t *__restrict__ off, const uint8_t *__restrict__ sym, uint64_t *key,
+                                                              int32_t *__restrict__ rep) {
+    const int lane = threadIdx.x;
+    for (int64_t v = blockIdx.x; v < n_sites; v += gridDim.x) {
+        const int64_t a = first[v], b = first[v + 1];
+        for (int64_t p = a + lane; p < b; p += PHM_WAVE) {
+            const uint8_t *x = sym + off[p];
+            const int64_t n = len[p];
+            uint32_t h = 2166136261u;
+            for (int64_t i = 0; i < n; i++) h = (h ^ x[i]) * 16777619u;
+            key[p] = (uint64_t) n << 32 | h;
+        }
+        __syncthreads();
+        for (int64_t p = a + lane; p < b; p += PHM_WAVE) {
+            const uint64_t k = key[p];
+            const uint8_t *x = sym + off[p];
+            const int64_t n = len[p];
+            int32_t o = (int32_t) p;
+            for (int64_t q = a; q < p; q++) {
+                if (key[q] != k) continue;
+                const uint8_t *y = sym + off[q];
+                int64_t i = 0;
+                while (i < n && x[i] == y[i]) i++;
+                if (i == n) {
+                    o = (int32_t) q;
+                    break;
+                }
+            }
+            rep[p] = o;
+        }
+    }
+}
+
 /* stMath_logAddExact (sonLib), as mrp_kernels.hip and rphmm_frame.c state it */
 static __device__ __forceinline__ double ht_log_add_exact(double x, double y) {
     if (x == -__builtin_inf()) return y;
@@ -1609,6 +1652,52 @@ int mrp_phase_variants_from_tagged_reads(mrp_context *ctx, const mrp_pair_hmm *f
     });
 }
 
+/* ec_classes_kernel over a host pool: upload, one launch, 4 B per entry back */
+int mrp_equal_substring_classes(mrp_context *ctx, int64_t n_sites, const int64_t *entry_first, const uint8_t *pool, int64_t pool_bytes,
+                                const int64_t *off, const int32_t *len, int32_t *rep_out) {
+    static const char *who = "mrp_equal_substring_classes";
+    if (n_sites < 0 || pool_bytes < 0 || !entry_first || (pool_bytes > 0 && !pool)) return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
+    if (entry_first[0] != 0) return mrp_set_error(MRP_ERR_ARG, "%s: entry_first must start at 0", who);
+    for (int64_t v = 0; v < n_sites; v++)
+        if (entry_first[v + 1] < entry_first[v]) return mrp_set_error(MRP_ERR_ARG, "%s: entry_first not ascending at site %lld", who, (long long) v);
+    const int64_t n_ent = entry_first[n_sites];
+    if (n_ent >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 entries in one call", who);
+    if (n_ent > 0 && (!off || !len || !rep_out)) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    for (int64_t p = 0; p < n_ent; p++)
+        if (len[p] < 0 || off[p] < 0 || off[p] + len[p] > pool_bytes) return mrp_set_error(MRP_ERR_ARG, "%s: entry %lld lies outside the symbol pool", who, (long long) p);
+    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the classes are found on the device; there is no CPU fallback)", who);
+    if (n_ent == 0) return MRP_OK;
+    {
+        PHM_HIP(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        DevBuf<uint8_t> d_pool;
+        DevBuf<int64_t> d_first, d_off;
+        DevBuf<int32_t> d_len, d_rep;
+        DevBuf<uint64_t> d_key;
+        d_pool.pool = d_first.pool = d_off.pool = d_len.pool = d_rep.pool = d_key.pool = &ctx->pool;
+        Drain drain{s};
+        PHM_HIP(d_pool.alloc((size_t) pool_bytes));
+        PHM_HIP(d_first.alloc((size_t) n_sites + 1));
+        PHM_HIP(d_off.alloc((size_t) n_ent));
+        PHM_HIP(d_len.alloc((size_t) n_ent));
+        PHM_HIP(d_key.alloc((size_t) n_ent));
+        PHM_HIP(d_rep.alloc((size_t) n_ent));
+        if (pool_bytes) PHM_HIP(hipMemcpyAsync(d_pool.p, pool, (size_t) pool_bytes, hipMemcpyHostToDevice, s));
+        PHM_HIP(hipMemcpyAsync(d_first.p, entry_first, 8 * ((size_t) n_sites + 1), hipMemcpyHostToDevice, s));
+        PHM_HIP(hipMemcpyAsync(d_off.p, off, 8 * (size_t) n_ent, hipMemcpyHostToDevice, s));
+        PHM_HIP(hipMemcpyAsync(d_len.p, len, 4 * (size_t) n_ent, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(ec_classes_kernel<int32_t>, dim3((unsigned) std::min<int64_t>(n_sites, 65536)), dim3(PHM_WAVE), 0, s, d_first.p, n_sites, d_len.p,
+                           d_off.p, d_pool.p, d_key.p, d_rep.p);
+        PHM_HIP(hipGetLastError());
+        HostVec<int32_t> rep((size_t) n_ent); /* (rep_out is written only on success) */
+        PHM_HIP(hipMemcpyAsync(rep.data(), d_rep.p, 4 * (size_t) n_ent, hipMemcpyDeviceToHost, s));
+        PHM_HIP(hipStreamSynchronize(s));
+        memcpy(rep_out, rep.data(), 4 * (size_t) n_ent);
+    }
+    ctx->pool.reclaim();
+    return MRP_OK;
+}
+
 }  // extern "C"
 
 /* ---- mrp_phase_string_chunks in three steps (mrp_internal.h): its own body below, and what a lane of the work queue runs per
@@ -1631,6 +1720,13 @@ struct mrp_string_front {
         std::vector<int32_t> g_sub_len;
         PhmPairList pairs;                             /* the front's own, then the back half's speculative ones */
         std::vector<std::vector<int64_t>> chunk_anchors;
+        /* a front over a device pool with a rest (mrp_phase_aligned_chunks_with_filtered): the host has no symbol, so the classes of equal
+         * substrings come as ids (ec_classes_kernel: equal ids at a site = equal substrings) -- per substring of the call, per chunk per
+         * fsub / ventry of its rest -- and the back half's pairs that want k-mer anchors are listed for the anchors kernel */
+        bool classes_by_id = false;
+        std::vector<int64_t> sub_cls;
+        std::vector<std::vector<int64_t>> fsub_cls, ventry_cls;
+        std::vector<int64_t> anchored_new;
     } scratch;
     double front_ms = 0;                               /* host wall time of the front (the one call adds its checks) */
     /* the back half (a call with rests): the static part of its sites, made with the pairs.  Sites: the bubbles of the chunks
@@ -1753,6 +1849,7 @@ struct FsLocal { /* one task's share; pidx: a pair of the front (>= 0) or ~(inde
     std::vector<int32_t> cbase;
     std::vector<int64_t> pidx;
     PhmPairList pairs;
+    std::vector<int64_t> anchored; /* classes by id: the new pairs past sv_threshold, whose anchors are found on the device */
 };
 /* a task: a run of bubbles or of variants of one chunk (a chunk of 2 000 sites is sixteen tasks, not one) */
 struct FsTask { int64_t c; bool variants; int64_t lo, hi; };
@@ -1765,10 +1862,14 @@ static void sc_filtered_task(const mrp_string_front *F, const mrp_string_chunk_r
     const mrp_string_chunk &S = F->chunks[c];
     const mrp_string_chunk_rest &R = rest[c];
     const int64_t pb = F->pool_base[(size_t) c], rb = rpool_base[(size_t) c], sb = F->sub_base[(size_t) c];
-    struct Item { int64_t off; int32_t len; int64_t prim_sub; bool may_own; };
+    const bool by_id = X.classes_by_id; /* the symbols lie in HBM: equal substrings of a site carry equal ids */
+    struct Item { int64_t off; int32_t len; int64_t prim_sub; bool may_own; int64_t id; };
     std::vector<Item> items;
     std::vector<int32_t> order;
-    auto same = [&](int32_t a, int32_t d) { return items[(size_t) a].len == items[(size_t) d].len && memcmp(gpool + items[(size_t) a].off, gpool + items[(size_t) d].off, (size_t) items[(size_t) a].len) == 0; };
+    auto same = [&](int32_t a, int32_t d) {
+        const Item &x = items[(size_t) a], &y = items[(size_t) d];
+        return by_id ? x.id == y.id : x.len == y.len && memcmp(gpool + x.off, gpool + y.off, (size_t) x.len) == 0;
+    };
     /* classes of the items that may own (entries [e0, e0 + items.size()) of Lc.entries); per class and strand block(cls, rev, rep):
      * adds the (class, strand)'s pairs and returns where its block starts in Lc.pidx */
     auto classes = [&](size_t e0, FsSite &st, auto block) {
@@ -1777,6 +1878,7 @@ static void sc_filtered_task(const mrp_string_front *F, const mrp_string_chunk_r
             if (items[i].may_own) order.push_back((int32_t) i);
         std::sort(order.begin(), order.end(), [&](int32_t a, int32_t d) {
             const Item &x = items[(size_t) a], &y = items[(size_t) d];
+            if (by_id) return x.id != y.id ? x.id < y.id : a < d; /* (another numbering of the classes: only the order of the pairs differs) */
             if (x.len != y.len) return x.len < y.len;
             const int cmp = memcmp(gpool + x.off, gpool + y.off, (size_t) x.len);
             return cmp != 0 ? cmp < 0 : a < d;
@@ -1801,7 +1903,8 @@ static void sc_filtered_task(const mrp_string_front *F, const mrp_string_chunk_r
     };
     auto new_pair = [&](int64_t xo, int32_t xl, int64_t yo, int32_t yl, int rev, bool anchored) {
         Lc.pidx.push_back(~Lc.pairs.size());
-        Lc.pairs.add(xo, xl, yo, yl, rev, anchored ? gpool : nullptr);
+        if (anchored && by_id) Lc.anchored.push_back(Lc.pairs.size());
+        Lc.pairs.add(xo, xl, yo, yl, rev, anchored && !by_id ? gpool : nullptr);
     };
     for (int64_t b = T.variants ? T.hi : T.lo; b < T.hi; b++) {
         FsSite st{};
@@ -1815,12 +1918,12 @@ static void sc_filtered_task(const mrp_string_front *F, const mrp_string_chunk_r
         for (int64_t k = R.fsub_first ? R.fsub_first[b] : 0; k < (R.fsub_first ? R.fsub_first[b + 1] : 0); k++) {
             const int32_t fr = R.fsub_read[k];
             Lc.entries.push_back(FsEntry{0, (int32_t) (S.n_reads + fr), fr, (R.forward_strand[fr] ? 0 : 1) | 2});
-            items.push_back(Item{rb + R.fsub_off[k], R.fsub_len[k], -1, true});
+            items.push_back(Item{rb + R.fsub_off[k], R.fsub_len[k], -1, true, by_id ? X.fsub_cls[(size_t) c][(size_t) k] : -1});
         }
         for (int64_t k = S.sub_first[b]; k < S.sub_first[b + 1]; k++) {
             const int32_t r = S.sub_read[k];
             Lc.entries.push_back(FsEntry{0, r, (int32_t) (R.n_filtered + r), S.read_forward_strand[r] ? 0 : 1});
-            items.push_back(Item{pb + S.sub_off[k], S.sub_len[k], sb + k, true});
+            items.push_back(Item{pb + S.sub_off[k], S.sub_len[k], sb + k, true, by_id ? X.sub_cls[(size_t) (sb + k)] : -1});
         }
         st.n_entries = (int32_t) items.size();
         classes((size_t) st.entry_first, st, [&](int rev, const Item &rep, int64_t prim) {
@@ -1855,7 +1958,7 @@ static void sc_filtered_task(const mrp_string_front *F, const mrp_string_chunk_r
             const bool filtered = r >= S.n_reads;
             const bool fwd = filtered ? R.forward_strand[r - S.n_reads] != 0 : S.read_forward_strand[r] != 0;
             Lc.entries.push_back(FsEntry{0, r, (int32_t) (k - R.ventry_first[v]), (fwd ? 0 : 1) | (filtered ? 2 : 0)});
-            items.push_back(Item{rb + R.ventry_off[k], R.ventry_len[k], -1, st.visited && !filtered});
+            items.push_back(Item{rb + R.ventry_off[k], R.ventry_len[k], -1, st.visited && !filtered, by_id ? X.ventry_cls[(size_t) c][(size_t) k] : -1});
         }
         classes((size_t) st.entry_first, st, [&](int rev, const Item &rep, int64_t) {
             const int64_t at = (int64_t) Lc.pidx.size();
@@ -1920,6 +2023,7 @@ static int sc_filtered_front(mrp_string_front *F, const mrp_string_chunk_rest *r
         for (size_t i = 0; i < Lc.pidx.size(); i++) Q.pidx[(size_t) p0 + i] = (int32_t) (Lc.pidx[i] >= 0 ? Lc.pidx[i] : pair0 + ~Lc.pidx[i]);
         for (const FsSite &st : Lc.bsites) { FsSite g = st; g.entry_first += e0; g.cls_first += c0 / 2; Q.sites[(size_t) b0++] = g; }
         for (const FsSite &st : Lc.vsites) { FsSite g = st; g.entry_first += e0; g.cls_first += c0 / 2; Q.sites[(size_t) v0++] = g; }
+        for (int64_t q : Lc.anchored) X.anchored_new.push_back(pair0 + q);
         X.pairs.append(Lc.pairs);
         e0 += (int64_t) Lc.entries.size(); c0 += (int64_t) Lc.cbase.size(); p0 += (int64_t) Lc.pidx.size(); pair0 += Lc.pairs.size();
     }
@@ -2909,9 +3013,14 @@ struct PaRun : AlignedFront {
     mrp_string_front F;
     int64_t n_bubbles = 0, n_used = 0, n_owners = 0, n_anchors = 0, n_anchor_runs = 0;
     double anchors_ms = 0;
+    /* the chunks of the call: all of the extraction's chunk records, or (with the filtered back half, PfRun) their first half -- the
+     * second half are the same reads over the rests' variants */
+    const int64_t n_front;
+    std::vector<int64_t> entry_of_sub; /* with the back half: substring of the call -> its entry */
 
-    PaRun(mrp_context *c, int64_t n, const mrp_aligned_chunk *ch, const char *const *const *names, const uint8_t *const *k, mrp_phase_aligned_stats *st)
-        : AlignedFront("mrp_phase_aligned_chunks", c, n, ch), read_names(names), keep(k), stats(st) {}
+    PaRun(mrp_context *c, int64_t n, const mrp_aligned_chunk *ch, const char *const *const *names, const uint8_t *const *k, mrp_phase_aligned_stats *st,
+          const char *w = "mrp_phase_aligned_chunks", int64_t front = -1)
+        : AlignedFront(w, c, n, ch), read_names(names), keep(k), stats(st), n_front(front < 0 ? n : front) {}
     ~PaRun() {
         for (int64_t *p : bv_out) free(p);
     }
@@ -2936,7 +3045,7 @@ int PaRun::check(const mrp_extract_options *options, const mrp_pair_hmm *forward
     if (!forward_model || !reverse_model || !params || (n_chunks > 0 && (!out || !hap_out || !read_names)))
         return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
     if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
-    for (int64_t c = 0; c < n_chunks; c++) {
+    for (int64_t c = 0; c < n_front; c++) {
         const mrp_aligned_chunk &C = chunks[c];
         if (C.n_reads == 0) continue;
         if (!hap_out[c] || (phred_out && !phred_out[c])) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null output", who, (long long) c);
@@ -2949,12 +3058,12 @@ int PaRun::check(const mrp_extract_options *options, const mrp_pair_hmm *forward
 
 /* the owners among the kept reads the caller's mask lets through (one byte per read of the call; no mask anywhere: none uploaded) */
 int PaRun::masked_owners() {
-    bool any = false;
-    for (int64_t c = 0; keep && c < n_chunks; c++) any = any || (keep[c] && chunks[c].n_reads > 0);
+    bool any = n_front < n_chunks; /* (the second half's records take no part in the front) */
+    for (int64_t c = 0; keep && c < n_front; c++) any = any || (keep[c] && chunks[c].n_reads > 0);
     if (!any) return owners(nullptr);
     HostVec<uint8_t> take((size_t) D.n_reads);
     for (int64_t c = 0; c < n_chunks; c++)
-        for (int64_t r = 0; r < chunks[c].n_reads; r++) take[(size_t) (D.read_first[c] + r)] = keep[c] ? (keep[c][r] != 0) : 1;
+        for (int64_t r = 0; r < chunks[c].n_reads; r++) take[(size_t) (D.read_first[c] + r)] = c >= n_front ? 0 : (keep && keep[c] ? (keep[c][r] != 0) : 1);
     return owners(&take);
 }
 
@@ -2963,6 +3072,8 @@ int PaRun::masked_owners() {
  * chunk by chunk, bubble by bubble, the owners in listing order, an owner's pairs allele by allele, the owner's strand picking the model */
 int PaRun::strings_and_pairs(int64_t sv_threshold) {
     offsets_and_strands();
+    const int64_t n_chunks = n_front;
+    const bool back = n_front < AlignedFront::n_chunks;
     arr.resize((size_t) n_chunks);
     sc.assign((size_t) n_chunks, mrp_string_chunk{});
     std::vector<int64_t> &sub_base = F.sub_base, &pair_first = F.pair_first;
@@ -2990,6 +3101,10 @@ int PaRun::strings_and_pairs(int64_t sv_threshold) {
             for (int64_t p = k_first[g + 1] - 1; p >= k_first[g]; p--) {
                 if (k_owner[p] < 0) continue;
                 sub_of[(size_t) p] = n_subs++;
+                if (back) { /* what the back half's static front reads: a substring's owner and its entry */
+                    F.scratch.owner.push_back(sub_of[(size_t) k_owner[p]]);
+                    entry_of_sub.push_back(p);
+                }
                 /* the pair of the substring's owner with the bubble's allele 0 (the owner is listed before its duplicates) */
                 pair_first.push_back(k_owner[p] == p ? pairs.size() : pair_first[(size_t) sub_of[(size_t) k_owner[p]]]);
                 A.s_off.push_back(y_off[(size_t) p]);
@@ -3089,7 +3204,7 @@ int PaRun::hand_over(int64_t **bubble_variant_out) {
         mrp_extract_run_times(X, false);
     }
     if (bubble_variant_out)
-        for (int64_t c = 0; c < n_chunks; c++) { bubble_variant_out[c] = bv_out[(size_t) c]; bv_out[(size_t) c] = nullptr; }
+        for (int64_t c = 0; c < n_front; c++) { bubble_variant_out[c] = bv_out[(size_t) c]; bv_out[(size_t) c] = nullptr; }
     release();
     mrp_extract_run_release(X); /* (reclaims the context's pool) */
     return MRP_OK;
@@ -3136,5 +3251,287 @@ extern "C" int mrp_phase_aligned_chunks(mrp_context *ctx, int64_t n_chunks, cons
     rc = R.hand_over(bubble_variant_out);
     if (rc != MRP_OK) return rc;
     if (stats) stats->total_ms = now_ms() - t_begin;
+    return MRP_OK;
+}
+
+/* ---- mrp_phase_aligned_chunks_with_filtered: mrp_phase_aligned_chunks with the back half of the chunk loop.
+ * One staged extraction runs over 2 * n_chunks chunk records: record c is chunk c, record n_chunks + c the same reads over the rest's
+ * variants (extractReadSubstringsAtVariantPositions called the second time, phase.c:354-357).  Both gathers land behind both sets of
+ * allele strings in the call's one device pool.  The front is PaRun's, over the first half; ec_classes_kernel runs over the sites of
+ * both halves, and from its representatives, the statuses and the entry indices the host makes what mrp_string_chunk_rest_from_extracted
+ * makes from downloaded symbols -- every chunk's rest as index arrays into the device pool -- and the back half's static front
+ * (sc_filtered_front, its classes by id).  The anchored pairs of both halves go through the anchors kernel in one launch. */
+namespace {
+
+struct PfRun : PaRun {
+    const int64_t n; /* chunks of the call */
+    const mrp_aligned_chunk_rest *const rest;
+    struct RestArrays { /* what the mrp_string_chunk_rest of a chunk points into */
+        std::vector<uint8_t> forward;
+        std::vector<int64_t> f_first{0}, f_off, va_first{0}, va_off, ve_first{0}, ve_off;
+        std::vector<int32_t> f_len, f_read, va_len, gt, ve_read, ve_len, filtered_read;
+    };
+    std::vector<RestArrays> ra;
+    std::vector<mrp_string_chunk_rest> rs;
+    std::vector<int32_t *> fr_out; /* the copies of filtered_read the caller gets */
+    hipEvent_t cev[2] = {nullptr, nullptr}; /* around the classes kernel */
+    DevBuf<uint64_t> d_ckey;
+    DevBuf<int32_t> d_rep;
+    PinnedBuf h_rep;
+    int64_t n_filtered_reads = 0;
+
+    PfRun(mrp_context *c, int64_t n_, const mrp_aligned_chunk *records, const mrp_aligned_chunk_rest *r, const char *const *const *names,
+          const uint8_t *const *k, mrp_phase_aligned_stats *st)
+        : PaRun(c, 2 * n_, records, names, k, st, "mrp_phase_aligned_chunks_with_filtered", n_), n(n_), rest(r) {}
+    ~PfRun() {
+        if (s) (void) hipStreamSynchronize(s); /* before the pinned buffer goes */
+        for (hipEvent_t x : cev)
+            if (x) (void) hipEventDestroy(x);
+        for (int32_t *p : fr_out) free(p);
+    }
+    int check_rest() const;
+    int classes();
+    int rests();
+    int filtered_front(int64_t sv_threshold);
+};
+
+/* the rest's own MRP_ERR_ARG (its variants have passed the extraction's checks as the second half's records) */
+int PfRun::check_rest() const {
+    for (int64_t c = 0; c < n; c++) {
+        const mrp_aligned_chunk_rest &R = rest[c];
+        if (R.n_variants > 0 && !R.gt) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: null genotypes of the rest", who, (long long) c);
+        for (int64_t v = 0; v < R.n_variants; v++) {
+            const int64_t k = R.allele_first[v + 1] - R.allele_first[v];
+            for (int w = 0; w < 2; w++)
+                if (R.gt[2 * v + w] < 0 || R.gt[2 * v + w] >= k)
+                    return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld, filtered variant %lld: genotype %d outside its %lld alleles", who, (long long) c,
+                                         (long long) v, R.gt[2 * v + w], (long long) k);
+        }
+    }
+    return MRP_OK;
+}
+
+/* the classes of equal substrings at the sites of both halves, queued behind the gather; 4 B per entry start on their way back (the
+ * owners' wait covers them) */
+int PfRun::classes() {
+    const int64_t n_ent = D.n_entries, n_var = D.n_variants;
+    d_ckey.pool = d_rep.pool = &ctx->pool;
+    for (hipEvent_t &x : cev) PHM_HIP(hipEventCreate(&x));
+    PHM_HIP(d_ckey.alloc((size_t) n_ent));
+    PHM_HIP(d_rep.alloc((size_t) n_ent));
+    PHM_HIP(h_rep.reserve(std::max<size_t>(4 * (size_t) n_ent, 1)));
+    PHM_HIP(hipEventRecord(cev[0], s));
+    if (n_ent > 0) {
+        hipLaunchKernelGGL(ec_classes_kernel<int64_t>, dim3((unsigned) std::min<int64_t>(n_var, 65536)), dim3(PHM_WAVE), 0, s, D.entry_first, n_var, D.entry_len,
+                           D.entry_off, D.symbols, d_ckey.p, d_rep.p);
+        PHM_HIP(hipGetLastError());
+    }
+    PHM_HIP(hipEventRecord(cev[1], s));
+    if (n_ent > 0) PHM_HIP(hipMemcpyAsync(h_rep.p, d_rep.p, 4 * (size_t) n_ent, hipMemcpyDeviceToHost, s));
+    downloaded += 4 * n_ent;
+    return MRP_OK;
+}
+
+/* mrp_string_chunk_rest_from_extracted over what came back: statuses, entry indices, lengths and representatives (the rules and their
+ * reference lines are in include/margin_rphmm.h); offsets are into the device pool */
+int PfRun::rests() {
+    const int32_t *k_rep = (const int32_t *) h_rep.p;
+    mrp_string_front::Scratch &X = F.scratch;
+    ra.resize((size_t) n);
+    rs.assign((size_t) n, mrp_string_chunk_rest{});
+    X.fsub_cls.resize((size_t) n);
+    X.ventry_cls.resize((size_t) n);
+    X.sub_cls.resize(entry_of_sub.size());
+    for (size_t k = 0; k < entry_of_sub.size(); k++) X.sub_cls[k] = k_rep[entry_of_sub[k]];
+    int64_t abase = 0;
+    for (int64_t c = 0; c < n; c++) abase += chunks[c].n_variants ? chunks[c].allele_first[chunks[c].n_variants] : 0;
+    for (int64_t c = 0; c < n; c++) {
+        const mrp_aligned_chunk &C = chunks[c];
+        const mrp_aligned_chunk_rest &Rc = rest[c];
+        RestArrays &A = ra[(size_t) c];
+        const int64_t nr = C.n_reads, nv = Rc.n_variants, r1 = D.read_first[c], r2 = D.read_first[n + c];
+        auto primary = [&](int64_t r) { return k_status[r1 + r] == MRP_READ_KEPT && (!keep || !keep[c] || keep[c][r]); };
+        auto kind = [&](int64_t r) {
+            if (k_status[r1 + r] == MRP_READ_FILTERED) return 0;
+            if (k_status[r1 + r] == MRP_READ_KEPT) return primary(r) ? -1 : 1;
+            return k_status[r2 + r] == MRP_READ_KEPT ? 2 : -1;
+        };
+        int64_t n_kind[3] = {0, 0, 0};
+        for (int64_t r = 0; r < nr; r++) {
+            const int k = kind(r);
+            if (k >= 0) n_kind[k]++;
+        }
+        const int64_t nf = n_kind[0] + n_kind[1] + n_kind[2];
+        n_filtered_reads += nf;
+        if (nf == 0 && nv == 0) continue; /* the empty rest */
+        std::vector<int32_t> findex((size_t) nr, -1);
+        A.filtered_read.resize((size_t) nf);
+        A.forward.resize((size_t) nf);
+        int64_t at[3] = {0, n_kind[0], n_kind[0] + n_kind[1]};
+        for (int64_t r = 0; r < nr; r++) {
+            const int k = kind(r);
+            if (k < 0) continue;
+            findex[(size_t) r] = (int32_t) at[k]++;
+            A.filtered_read[(size_t) findex[(size_t) r]] = (int32_t) r;
+            A.forward[(size_t) findex[(size_t) r]] = forward[(size_t) (r1 + r)];
+        }
+        std::vector<int64_t> &fcls = X.fsub_cls[(size_t) c], &vcls = X.ventry_cls[(size_t) c];
+        for (int64_t v : arr[(size_t) c].bubble_variant) {
+            const int64_t g = D.variant_first[c] + v;
+            for (int pass = 0; pass < 2; pass++)
+                for (int64_t p = k_first[g]; p < k_first[g + 1]; p++) {
+                    const int64_t r = k_read[p] - r1;
+                    if (kind(r) != pass) continue;
+                    A.f_off.push_back(y_off[(size_t) p]);
+                    A.f_len.push_back((int32_t) k_len[p]);
+                    A.f_read.push_back(findex[(size_t) r]);
+                    fcls.push_back(k_rep[p]);
+                }
+            A.f_first.push_back((int64_t) A.f_off.size());
+        }
+        for (int64_t v = 0; v < nv; v++) {
+            const int64_t g = D.variant_first[n + c] + v;
+            for (int64_t a = Rc.allele_first[v]; a < Rc.allele_first[v + 1]; a++) {
+                A.va_off.push_back(a_off[(size_t) (abase + a)]);
+                A.va_len.push_back(a_len[(size_t) (abase + a)]);
+            }
+            A.va_first.push_back((int64_t) A.va_off.size());
+            A.gt.push_back(Rc.gt[2 * v]);
+            A.gt.push_back(Rc.gt[2 * v + 1]);
+            if (Rc.variant_pos[v] >= C.chunk_start && Rc.variant_pos[v] < C.chunk_end) /* bubbleGraph.c:2179 */
+                for (int64_t p = k_first[g]; p < k_first[g + 1]; p++) {
+                    const int64_t r = k_read[p] - r2;
+                    if (k_status[r2 + r] != MRP_READ_KEPT) continue;
+                    A.ve_read.push_back(primary(r) ? (int32_t) r : (int32_t) (nr + findex[(size_t) r]));
+                    A.ve_off.push_back(y_off[(size_t) p]);
+                    A.ve_len.push_back((int32_t) k_len[p]);
+                    vcls.push_back(k_rep[p]);
+                }
+            A.ve_first.push_back((int64_t) A.ve_off.size());
+        }
+        abase += nv ? Rc.allele_first[nv] : 0;
+        mrp_string_chunk_rest &R = rs[(size_t) c];
+        R.n_filtered = nf;
+        R.forward_strand = A.forward.data();
+        R.pool = nullptr; /* the symbols are in HBM */
+        R.pool_bytes = pool_bytes;
+        R.fsub_first = A.f_first.data();
+        R.fsub_off = A.f_off.data();
+        R.fsub_len = A.f_len.data();
+        R.fsub_read = A.f_read.data();
+        R.n_variants = nv;
+        R.valle_first = A.va_first.data();
+        R.valle_off = A.va_off.data();
+        R.valle_len = A.va_len.data();
+        R.gt = A.gt.data();
+        R.ventry_first = A.ve_first.data();
+        R.ventry_read = A.ve_read.data();
+        R.ventry_off = A.ve_off.data();
+        R.ventry_len = A.ve_len.data();
+    }
+    return MRP_OK;
+}
+
+/* the back half's static front from indices and classes alone; its pairs past sv_threshold join the front's anchored list */
+int PfRun::filtered_front(int64_t sv_threshold) {
+    F.pool_base.assign((size_t) n + 1, 0); /* every offset is the device pool's already */
+    F.scratch.classes_by_id = true;
+    const std::vector<int64_t> rpool_base((size_t) n, 0);
+    const int rc = sc_filtered_front(&F, rs.data(), sv_threshold, rpool_base);
+    if (rc != MRP_OK) return rc;
+    anchored.insert(anchored.end(), F.scratch.anchored_new.begin(), F.scratch.anchored_new.end());
+    return MRP_OK;
+}
+
+}  // namespace
+
+extern "C" int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
+                                                      const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
+                                                      const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                                                      int64_t sv_threshold, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                      mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                                                      int64_t **bubble_variant_out, mrp_filtered_out *filtered_out, int32_t **filtered_read_out,
+                                                      mrp_phase_aligned_filtered_stats *stats) {
+    static const char *who = "mrp_phase_aligned_chunks_with_filtered";
+    const double t_begin = now_ms();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_chunks < 0 || n_chunks >= (1ll << 30) || (n_chunks > 0 && (!chunks || !rest || !filtered_out || !filtered_read_out)))
+        return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
+    if (n_chunks > 0) memset(filtered_out, 0, sizeof(*filtered_out) * (size_t) n_chunks);
+    /* the extraction's chunk records: the chunks, then the same reads over the rests' variants */
+    std::vector<mrp_aligned_chunk> records((size_t) (2 * n_chunks));
+    for (int64_t c = 0; c < n_chunks; c++) {
+        records[(size_t) c] = chunks[c];
+        mrp_aligned_chunk &R = records[(size_t) (n_chunks + c)];
+        R = chunks[c];
+        R.n_variants = rest[c].n_variants;
+        R.variant_pos = rest[c].variant_pos;
+        R.allele_first = rest[c].allele_first;
+        R.allele_off = rest[c].allele_off;
+        R.allele_len = rest[c].allele_len;
+        R.allele_chars = rest[c].allele_chars;
+        R.allele_bytes = rest[c].allele_bytes;
+        R.is_sv = rest[c].is_sv;
+    }
+    PfRun R(ctx, n_chunks, records.data(), rest, read_names, keep, stats ? &stats->aligned : nullptr);
+    int rc = R.check(options, forward_model, reverse_model, expansion, params, out, hap_out, phred_out);
+    if (rc == MRP_OK || rc == MRP_ERR_UNSUPPORTED) { /* (every MRP_ERR_ARG comes before the refused modes) */
+        const int rc2 = R.check_rest();
+        if (rc2 != MRP_OK) rc = rc2;
+    }
+    if (rc != MRP_OK) return rc;
+    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction and the pair-HMM have no CPU fallback)", who);
+    rc = R.extract();
+    if (rc == MRP_OK) rc = R.classes();
+    if (rc == MRP_OK) rc = R.masked_owners();
+    if (rc == MRP_OK) rc = R.strings_and_pairs(sv_threshold);
+    if (rc == MRP_OK) rc = R.rests();
+    if (rc == MRP_OK) rc = R.filtered_front(sv_threshold);
+    if (rc == MRP_OK) rc = R.anchors();
+    if (rc == MRP_OK) rc = R.classify(forward_model, reverse_model, expansion);
+    if (rc != MRP_OK) return rc;
+    /* (made before anything is handed over: an error returns nothing) */
+    R.fr_out.assign((size_t) n_chunks, nullptr);
+    if (bubble_variant_out) R.bv_out.assign((size_t) n_chunks, nullptr);
+    for (int64_t c = 0; c < n_chunks; c++) {
+        std::vector<int32_t> fr = R.ra[(size_t) c].filtered_read;
+        fr.push_back(-1); /* the end of the list */
+        R.fr_out[(size_t) c] = (int32_t *) sc_dup(fr.data(), sizeof(int32_t) * fr.size());
+        if (!R.fr_out[(size_t) c]) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
+        if (!bubble_variant_out) continue;
+        std::vector<int64_t> bv = R.arr[(size_t) c].bubble_variant;
+        bv.push_back(-1);
+        R.bv_out[(size_t) c] = (int64_t *) sc_dup(bv.data(), sizeof(int64_t) * bv.size());
+        if (!R.bv_out[(size_t) c]) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
+    }
+    for (int64_t c = 0; c < n_chunks; c++) out[c] = nullptr;
+    if (profiles_out && n_chunks > 0) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
+    mrp_string_filtered_stats fst;
+    memset(&fst, 0, sizeof(fst));
+    if (n_chunks > 0) {
+        R.F.front_ms = now_ms() - t_begin;
+        rc = mrp_string_front_run(ctx, &R.F, het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out,
+                                  stats ? &stats->aligned.chunks : nullptr, filtered_out, stats ? &fst : nullptr);
+        if (rc != MRP_OK) return rc;
+    }
+    if (stats) {
+        float ms = 0.f;
+        if (R.cev[1]) PHM_HIP(hipEventElapsedTime(&ms, R.cev[0], R.cev[1]));
+        stats->classes_ms = ms;
+        stats->filtered_ms = fst.filtered_ms;
+        stats->pairs_scored = fst.pairs_scored;
+        stats->pairs_speculative = fst.pairs_speculative;
+        stats->pairs_read_by_results = fst.pairs_read_by_results;
+        stats->filtered_variants = R.D.n_variants - R.D.variant_first[n_chunks];
+        stats->filtered_reads = R.n_filtered_reads;
+        stats->filtered_entries = R.D.n_entries - (n_chunks > 0 ? R.k_first[R.D.variant_first[n_chunks]] : 0);
+    }
+    rc = R.hand_over(bubble_variant_out);
+    if (rc != MRP_OK) return rc;
+    R.d_ckey.release();
+    R.d_rep.release();
+    ctx->pool.reclaim();
+    for (int64_t c = 0; c < n_chunks; c++) { filtered_read_out[c] = R.fr_out[(size_t) c]; R.fr_out[(size_t) c] = nullptr; }
+    if (stats) stats->aligned.total_ms = now_ms() - t_begin;
     return MRP_OK;
 }

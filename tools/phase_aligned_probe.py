@@ -8,9 +8,17 @@ wall time of mrp_kmer_alignment_anchors over the same anchored pairs, which is w
 both gave the same results bit for bit.  Prints one JSON line and writes it to --out.
 
     python tools/phase_aligned_probe.py [--chunks 96] [--distinct 4] [--reps 5] [--cache FILE] [--out profiles/phase_aligned/probe.json]
+
+--filtered: the same shape with one variant in five moved to the filtered set (every fifth, from the third on; gt 0 | 1, every fourth of
+them homozygous), mrp_phase_aligned_chunks_with_filtered beside ITS chain: both extractions in one mrp_extract_read_substrings call,
+mrp_string_chunk_from_extracted and mrp_string_chunk_rest_from_extracted per chunk, mrp_phase_string_chunks_with_filtered.  Both legs in
+one process on one context, a warm-up, the median of --reps; the legs' outputs are compared through a digest.  Writes
+profiles/phase_aligned/filtered.json (or --out).
 """
 import argparse
 import ctypes as C
+import dataclasses
+import hashlib
 import json
 import os
 import pickle
@@ -33,8 +41,10 @@ def main():
     ap.add_argument("--distinct", type=int, default=4)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cache", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "phase_aligned", "probe.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--filtered", action="store_true")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "phase_aligned", "filtered.json" if a.filtered else "probe.json")
     opts = capi.shipped_extract_options()
     if a.cache and os.path.exists(a.cache):
         with open(a.cache, "rb") as f:
@@ -48,6 +58,8 @@ def main():
         if a.cache:
             with open(a.cache, "wb") as f:
                 pickle.dump(distinct, f)
+    if a.filtered:
+        return filtered_legs(a, distinct, opts)
     chunks = [distinct[i % a.distinct] for i in range(a.chunks)]
     built = [capi.aligned_chunk_struct(c) for c in chunks]
     n = len(chunks)
@@ -163,6 +175,142 @@ def main():
                chain_pairhmm_kernel_ms=round(sst.pairhmm.kernel_ms, 3), phase_device_ms=round(st.chunks.phase.device_ms, 2), composite_host_ms=round(st.chunks.host_ms, 2), chain_string_call_host_ms=round(sst.host_ms, 2),
                composite_front_bytes_downloaded=int(st.front_bytes_downloaded), substring_symbols=int(n_sym),
                chain_symbol_bytes_down_and_up=int(2 * n_sym), bytes_uploaded=int(st.extract.bytes_uploaded), identical_to_chain=bool(same))
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+
+
+def split(chunk):
+    """-> (the chunk with four variants in five, the chunk with the fifth ones, their gt)"""
+    n = len(chunk.variant_pos)
+    pick = np.zeros(n, bool)
+    pick[2::5] = True
+    part = lambda m: dataclasses.replace(chunk, variant_pos=np.ascontiguousarray(chunk.variant_pos[m]), alleles=[al for al, k in zip(chunk.alleles, m) if k],
+                                         is_sv=np.ascontiguousarray(chunk.is_sv[m]))
+    filtered = part(pick)
+    gt = np.array([(0, 0) if v % 4 == 3 else (0, 1) for v in range(len(filtered.alleles))], np.int32).reshape(-1, 2)
+    return part(~pick), filtered, gt
+
+
+def filtered_legs(a, distinct, opts):
+    parts = [split(c) for c in distinct]
+    n = a.chunks
+    chunks = [parts[i % a.distinct][0] for i in range(n)]
+    fchunks = [parts[i % a.distinct][1] for i in range(n)]
+    gts = [parts[i % a.distinct][2] for i in range(n)]
+    built = [capi.aligned_chunk_struct(c) for c in chunks]
+    fbuilt = [capi.aligned_chunk_struct(c) for c in fchunks]   # the same reads over the filtered variants: the chain's second n records
+    rbuilt = [capi.aligned_chunk_rest_struct(c, g) for c, g in zip(fchunks, gts)]
+    fwd = capi.PairHmm.from_margin_hmm(*synth.margin_phase_pair_hmm_arrays())
+    rev = fwd.reverse_complement()
+    params = capi.Params.from_reference_names(synth.shipped_phase_params())
+    L = capi.load()
+    arr2 = (capi.AlignedChunk * (2 * n))(*([b[0] for b in built] + [b[0] for b in fbuilt]))
+    opt = capi.ExtractOptions.from_dict(opts)
+    names = [[s.encode() for s in c.read_names] for c in chunks]
+    name_arrs = [(C.c_char_p * max(len(x), 1))(*x) for x in names]
+    strands = [np.ascontiguousarray(c.read_forward_strand, np.uint8) for c in chunks]
+    fpos = [np.ascontiguousarray(c.variant_pos, np.int64) for c in fchunks]
+    gflat = [np.ascontiguousarray(g, np.int32).reshape(-1) for g in gts]
+    ptr = lambda v: v.ctypes.data if v.size else None
+
+    def digest(items):
+        h = hashlib.sha256()
+        for x in items:
+            h.update(np.ascontiguousarray(x).tobytes())
+        return h.hexdigest()
+
+    def chain(ctx):
+        out = C.POINTER(capi.ExtractedChunk)()
+        est, sst = capi.ExtractStats(), capi.StringFilteredStats()
+        t0 = time.perf_counter()
+        capi._check(L.mrp_extract_read_substrings(ctx.h, 2 * n, arr2, C.byref(opt), C.byref(out), C.byref(est)))
+        sc, rs = (capi.StringChunk * n)(), (capi.StringChunkRest * n)()
+        blocks, frs = [], []
+        for i in range(n):
+            bv, fr, blk = C.POINTER(C.c_int64)(), C.c_void_p(), C.c_void_p()
+            capi._check(L.mrp_string_chunk_from_extracted(C.byref(out[i]), None, C.cast(name_arrs[i], C.c_void_p), strands[i].ctypes.data, C.byref(sc[i]), C.byref(bv)))
+            capi._check(L.mrp_string_chunk_rest_from_extracted(C.byref(out[i]), None, strands[i].ctypes.data, C.cast(bv, C.c_void_p), sc[i].n_bubbles,
+                                                               C.byref(out[n + i]), ptr(fpos[i]), ptr(gflat[i]), int(chunks[i].chunk_start),
+                                                               int(chunks[i].chunk_end), C.byref(rs[i]), C.byref(fr), C.byref(blk)))
+            blocks.append(blk)
+            frs.append(fr)
+        haps = [np.zeros(len(c.read_pos), np.int8) for c in chunks]
+        phreds = [np.zeros(len(c.read_pos)) for c in chunks]
+        hp = (C.c_void_p * n)(*[h.ctypes.data for h in haps])
+        pp = (C.c_void_p * n)(*[p.ctypes.data for p in phreds])
+        res = (C.POINTER(capi.PhaseResult) * n)()
+        fout = (capi.FilteredOut * n)()
+        capi._check(L.mrp_phase_string_chunks_with_filtered(ctx.h, n, sc, rs, C.byref(fwd), C.byref(rev), 4, SV_THRESHOLD, 0.0, C.byref(params), 0, res, hp, pp,
+                                                            None, fout, C.byref(sst)))
+        wall = (time.perf_counter() - t0) * 1e3
+        items, n_sym = [], 0
+        for i in range(n):
+            g, O = res[i].contents, fout[i]
+            nr, nv = int(O.n_reads), int(O.n_variants)
+            items += [haps[i], phreds[i], capi._as_np(g.haplotype_string1, int(g.length), np.uint64), capi._as_np(g.haplotype_string2, int(g.length), np.uint64),
+                      capi._as_np(O.read_hap, nr, np.int32), capi._as_np(O.h1, nr, np.float64), capi._as_np(O.h2, nr, np.float64),
+                      capi._as_np(O.variant_state, nv, np.int32), capi._as_np(O.cis, nv, np.float64), capi._as_np(O.trans, nv, np.float64),
+                      capi._as_np(frs[i], int(rs[i].n_filtered), np.int32)]
+            L.mrp_phase_result_destroy(res[i])
+            for f_ in ("read_hap", "h1", "h2", "variant_state", "cis", "trans"):
+                L.mrp_free(C.cast(getattr(O, f_), C.c_void_p))
+            L.mrp_free(C.cast(sc[i].allele_first, C.c_void_p))
+            L.mrp_free(blocks[i])
+        for i in range(2 * n):
+            ne = int(capi._as_np(out[i].entry_first, int(out[i].n_variants) + 1, np.int64)[-1])
+            n_sym += int(capi._as_np(out[i].entry_len, ne, np.int32).sum())
+            for f_, _, _ in capi._EXTRACTED_ARRAYS:
+                L.mrp_free(C.cast(getattr(out[i], f_), C.c_void_p))
+        L.mrp_free(C.cast(out, C.c_void_p))
+        return digest(items), est, sst, n_sym, wall
+
+    def joint(ctx, count=None):
+        got, st = capi.phase_aligned_chunks_with_filtered(ctx, chunks[:count], None, fwd, rev, params, options=opts, structs=built[:count],
+                                                          rest_structs=rbuilt[:count], sv_threshold=SV_THRESHOLD)
+        items = []
+        for g in got:
+            o = g["filtered"]
+            items += [g["hap"], g["phred"], g["result"]["hap1"], g["result"]["hap2"], o["read_hap"], o["h1"], o["h2"], o["variant_state"], o["cis"], o["trans"],
+                      g["filtered_read"]]
+        return digest(items), st, st.aligned.total_ms
+
+    with capi.Context(0) as ctx:
+        joint(ctx, 2)  # warm-up: module load, pools
+        chain(ctx)
+        joint(ctx)
+        walls_c, walls_j, stats_c, stats_j = [], [], [], []
+        for _ in range(a.reps):
+            dj, st, w = joint(ctx)
+            walls_j.append(w)
+            stats_j.append(st)
+            ref = chain(ctx)
+            walls_c.append(ref[4])
+            stats_c.append(ref)
+    kj, kc = int(np.argsort(walls_j)[len(walls_j) // 2]), int(np.argsort(walls_c)[len(walls_c) // 2])
+    st = stats_j[kj]
+    dc, est, sst, n_sym, _ = stats_c[kc]
+    A = st.aligned
+    med_c, med_j, spread_c = walls_c[kc], walls_j[kj], max(walls_c) - min(walls_c)
+    res = dict(chunks=n, distinct=a.distinct, reads=int(A.extract.reads) // 2, variants=int(A.variants - st.filtered_variants), filtered_variants=int(st.filtered_variants),
+               filtered_reads=int(st.filtered_reads), substrings=int(A.entries - st.filtered_entries), filtered_substrings=int(st.filtered_entries),
+               pairs_scored=int(st.pairs_scored), pairs_speculative=int(st.pairs_speculative), pairs_read_by_results=int(st.pairs_read_by_results),
+               chain_pairs_scored=int(sst.pairs_scored), pairs_anchored=int(A.pairs_anchored), anchors=int(A.anchors),
+               composite_wall_ms=round(med_j, 2), composite_walls_ms=[round(x, 2) for x in sorted(walls_j)],
+               chain_wall_ms=round(med_c, 2), chain_walls_ms=[round(x, 2) for x in sorted(walls_c)],
+               condition_composite_not_above_chain_plus_spread=bool(med_j <= med_c + spread_c),
+               chain_extract_total_ms=round(est.total_ms, 2), chain_string_call_total_ms=round(sst.chunks.total_ms, 2),
+               composite_kernel_ms=dict(extract=round(A.extract.kernel_ms, 3), owners=round(A.owners_ms, 3), classes=round(st.classes_ms, 3),
+                                        anchors=round(A.anchors_ms, 3), pairhmm=round(A.chunks.pairhmm.kernel_ms, 3), profile=round(A.chunks.profile_ms, 3),
+                                        assign=round(A.chunks.assign_ms, 3), filtered=round(st.filtered_ms, 3)),
+               chain_kernel_ms=dict(extract=round(est.kernel_ms, 3), pairhmm=round(sst.chunks.pairhmm.kernel_ms, 3), profile=round(sst.chunks.profile_ms, 3),
+                                    assign=round(sst.chunks.assign_ms, 3), filtered=round(sst.filtered_ms, 3)),
+               phase_device_ms=round(A.chunks.phase.device_ms, 2), composite_host_ms=round(A.chunks.host_ms, 2), chain_string_call_host_ms=round(sst.chunks.host_ms, 2),
+               composite_front_bytes_downloaded=int(A.front_bytes_downloaded), substring_symbols_both_extractions=int(n_sym),
+               chain_symbol_bytes_down_and_up=int(2 * n_sym), bytes_uploaded=int(A.extract.bytes_uploaded), chain_bytes_uploaded=int(est.bytes_uploaded),
+               digest=dj, identical_to_chain=bool(dj == dc))
     line = json.dumps(res)
     print(line)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
