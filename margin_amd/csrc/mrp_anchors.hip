@@ -2,7 +2,7 @@
  * mrp_anchors.hip -- getKmerAlignmentAnchors (impl/pairwiseAligner.c:1519-1627, KMER_SIZE 20) for any number of (x, y) string pairs
  * over a symbol pool that lies on the device: the k-mer chain the reference anchors long (structural variant) alleles with.  The
  * host function kmer_anchors() of mrp_pairhmm.hip (mrp_kmer_alignment_anchors) is the specification, quirks included; the public
- * entry is mrp_kmer_alignment_anchors_many, the composite mrp_phase_aligned_chunks calls mrp_kmer_anchors_on_device.  gfx950 only.
+ * entry is mrp_kmer_alignment_anchors_many, the composite mrp_phase_aligned_chunks (mrp_aligned.hip) calls mrp_kmer_anchors_on_device.  gfx950 only.
  *
  * ak_chain_kernel, a wave per pair (the waves stride over the pairs; no wave waits for another):
  *   search   a lane per y position, 64 at a time: the first x whose 20 symbols equal the y k-mer (getKmers :1543-1555 keeps the first

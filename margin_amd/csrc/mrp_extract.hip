@@ -23,7 +23,7 @@
  * device runs.  One total (the substrings and their bases) comes back between the two halves to size the buffers.
  *
  * The call is one mrp_extract_run taken through steps (mrp_internal.h): check, stage and upload, first half, totals, second
- * half, download.  mrp_extract_read_substrings is all of them; mrp_haplotag_aligned_chunks (mrp_pairhmm.hip) stops before the
+ * half, download.  mrp_extract_read_substrings is all of them; mrp_haplotag_aligned_chunks (mrp_aligned.hip) stops before the
  * download and reads the result in HBM.
  */
 #include <hip/hip_runtime.h>

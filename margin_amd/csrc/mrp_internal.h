@@ -535,7 +535,7 @@ void mrp_engine_release_context_cache(mrp_context *ctx);
  * MRP_POOL_TAIL_PAD bytes of the allocation) and descs[i]->profile_pool is the caller's host copy of them; only the site tables are staged */
 int mrp_chunk_block_create(mrp_context *ctx, int64_t n, const mrp_chunk_desc *const *descs, mrp_chunk **out, mrp_chunk_block *blk, int groups = 1,
                            const uint8_t *const *device_pools = nullptr);
-/* mrp_phase_string_chunks in three steps (mrp_pairhmm.hip), so that a work queue can check every chunk before its first lane
+/* mrp_phase_string_chunks in three steps (mrp_string_chunks.hip), so that a work queue can check every chunk before its first lane
  * starts and a lane can make the front of its next batch while the current one is on the device:
  *   check        MRP_ERR_ARG for malformed arguments (host only, the one call's own checks);
  *   check_pairs  MRP_ERR_UNSUPPORTED for a pair whose diagonal exceeds the pair-per-wave kernel's limit (host only);
@@ -567,7 +567,7 @@ static inline void mrp_filtered_out_clear(mrp_filtered_out *O) {
     memset(O, 0, sizeof(*O));
 }
 /* mrp_extract_read_substrings as one run taken through steps (mrp_extract.hip), so that a composite (mrp_haplotag_aligned_chunks,
- * mrp_pairhmm.hip) can stop before the download and read the result where it lies in HBM:
+ * mrp_aligned.hip) can stop before the download and read the result where it lies in HBM:
  *   check_args / check_modes / check_chunks   MRP_ERR_ARG for malformed arguments, MRP_ERR_UNSUPPORTED for the two refused modes, the
  *                  chunks' own checks and the windows (host only; the entry decides their order);
  *   stage          the call's reads, ops, bases and variants in one staging block, and its upload on ctx->stream;

@@ -107,7 +107,7 @@ def main():
     kj, kc = int(np.argsort(walls_j)[len(walls_j) // 2]), int(np.argsort(walls_c)[len(walls_c) // 2])
     st = stats_j[kj]
     _, _, _, est, pst, (n_var, n_ent, n_sym), _ = stats_c[kc]
-    # what the chain's two device calls copy back (mrp_extract.hip, mrp_pairhmm.hip): the extraction's total, the status, the scan of the
+    # what the chain's two device calls copy back (mrp_extract.hip, mrp_aligned.hip): the extraction's total, the status, the scan of the
     # reads' counts, the entry CSR, per entry offset, length and read, every substring's symbols; then hap, h1, h2 per read
     chain_bytes = 16 + (n_reads + 7) // 8 * 8 + 8 * (n_reads + 1) + 8 * (n_var + 1) + 8 * (n_ent + 1) + 12 * n_ent + n_sym + 20 * n_reads
     chain_kernel = est.kernel_ms + pst.kernel_ms
