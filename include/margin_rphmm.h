@@ -1004,6 +1004,58 @@ int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, c
                                            int64_t **bubble_variant_out, mrp_filtered_out *filtered_out, int32_t **filtered_read_out,
                                            mrp_phase_aligned_filtered_stats *stats);
 
+/* ---- the same for a node's worth of aligned chunks over its GPUs --------------------------------------------------------------
+ * The chunk loop of phase.c (:257-279: largest first, schedule(dynamic,1)) around mrp_phase_aligned_chunks /
+ * mrp_phase_aligned_chunks_with_filtered (:337-436), as the work queue gives it to profile-byte and string chunks.
+ *   Units: what a chunk really costs, its (read, variant) substrings, is known only after its extraction has run on the device, so the
+ * queue orders and cuts by the estimate uniform coverage gives, mrp_aligned_chunk_units: floor(B * V / L) with B the sum of l_qseq over
+ * the chunk's reads, V its n_variants (plus the rest's) and L = max(1, overlap_end - overlap_start), computed in 128-bit integers and
+ * clamped to INT64_MAX -- the (read, site) unit MRP_QUEUE_UNITS_PER_CHUNK counts (phase.c:257-263 orders by an estimated depth too).
+ * MRP_ERR_ARG, *units_out left alone, for a NULL chunk or units_out, a negative count, overlap_end < overlap_start, n_reads > 0 with a
+ * NULL l_qseq, a negative l_qseq.  Largest first, ties in input order, batches cut by the rules of mrp_queue_phase_chunks.
+ *   A lane runs a batch as one call on its own context; the part of the lane's NEXT batch that needs no device (its extraction records,
+ * the chunks' checks and windows) is made on a thread beside it.  keep[c] and read_names[c] travel with their chunk.
+ *   Results: out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out, filtered_read_out are, at every chunk's own
+ * position, bit for bit what ONE call of mrp_phase_aligned_chunks / mrp_phase_aligned_chunks_with_filtered over all chunks returns,
+ * whatever the batch size, the lanes, the devices or the hand-out.  Parameters outside the resident range take the per-chunk path
+ * (stats->fallback_chunks counts those chunks).  stats as for string chunks, units_per_device in mrp_aligned_chunk_units.
+ *   Errors: every chunk is checked on the caller's thread before a lane starts, in the one call's order and with its messages (the
+ * rest of chunk c is "chunk n_chunks + c" in the extraction's) -- every MRP_ERR_ARG, then MRP_ERR_UNSUPPORTED for the two refused
+ * extraction modes, both without a device or a queue; then MRP_ERR_NO_DEVICE for a NULL queue (n_chunks == 0 included).  Up to here
+ * nothing is written, stats included.  The 2 048-cell diagonal refusal cannot be raised up front -- the lengths exist only after a
+ * batch's extraction: it arrives as a lane error, like an out-of-memory or a HIP error.  On a lane error the queue stops: remaining
+ * batches are dropped, prefetched ones discarded, the workers joined, every result already made destroyed (bubble_variant_out[c] and
+ * filtered_read_out[c] freed), out[] / bubble_variant_out[] / filtered_read_out[] left NULL, profiles_out[] / filtered_out[] zeroed,
+ * the first error returned (mrp_last_error); the queue stays usable.  n_chunks == 0 returns MRP_OK with zeroed stats. */
+int mrp_aligned_chunk_units(const mrp_aligned_chunk *chunk, const mrp_aligned_chunk_rest *rest /* may be NULL */, int64_t *units_out); /* host only */
+int mrp_queue_phase_aligned_chunks(mrp_queue *q, int64_t n_chunks, const mrp_aligned_chunk *chunks, const char *const *const *read_names,
+                                   const uint8_t *const *keep, const mrp_extract_options *options, const mrp_pair_hmm *forward_model,
+                                   const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
+                                   const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out,
+                                   double *const *phred_out, mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_queue_stats *stats);
+int mrp_queue_phase_aligned_chunks_with_filtered(mrp_queue *q, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
+                                                 const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
+                                                 const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                                                 int64_t sv_threshold, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                 int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                 mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
+                                                 int32_t **filtered_read_out, mrp_queue_stats *stats);
+/* create a queue, run the call above, destroy it */
+int mrp_phase_aligned_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,
+                                        const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
+                                        const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                        double het_substitution_probability, const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch,
+                                        mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                                        int64_t **bubble_variant_out, mrp_queue_stats *stats);
+int mrp_phase_aligned_chunks_with_filtered_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,
+                                                      const mrp_aligned_chunk_rest *rest, const char *const *const *read_names, const uint8_t *const *keep,
+                                                      const mrp_extract_options *options, const mrp_pair_hmm *forward_model,
+                                                      const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                                      double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                      int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                      mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
+                                                      int32_t **filtered_read_out, mrp_queue_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

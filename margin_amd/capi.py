@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import time
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -39,7 +40,8 @@ EXPORTED_SYMBOLS = [
     "mrp_phase_string_chunks_on_devices", "mrp_phase_string_chunks_with_filtered", "mrp_queue_phase_string_chunks_with_filtered",
     "mrp_phase_string_chunks_with_filtered_on_devices", "mrp_haptag_sites_from_extracted", "mrp_haplotag_aligned_chunks",
     "mrp_kmer_alignment_anchors_many", "mrp_phase_aligned_chunks", "mrp_string_chunk_rest_from_extracted", "mrp_equal_substring_classes",
-    "mrp_phase_aligned_chunks_with_filtered",
+    "mrp_phase_aligned_chunks_with_filtered", "mrp_aligned_chunk_units", "mrp_queue_phase_aligned_chunks",
+    "mrp_queue_phase_aligned_chunks_with_filtered", "mrp_phase_aligned_chunks_on_devices", "mrp_phase_aligned_chunks_with_filtered_on_devices",
 ]
 
 
@@ -409,6 +411,13 @@ def load():
     L.mrp_phase_aligned_chunks_with_filtered.argtypes = [vp, i64, P(AlignedChunk), P(AlignedChunkRest), P(vp), P(vp), P(ExtractOptions), P(PairHmm),
                                                          P(PairHmm), i64, i64, C.c_double, P(Params), i64, P(P(PhaseResult)), P(vp), P(vp),
                                                          P(ProfileOut), P(vp), P(FilteredOut), P(vp), P(PhaseAlignedFilteredStats)]
+    pa, pf = L.mrp_phase_aligned_chunks.argtypes, L.mrp_phase_aligned_chunks_with_filtered.argtypes
+    L.mrp_aligned_chunk_units.argtypes = [P(AlignedChunk), P(AlignedChunkRest), P(i64)]
+    # the one call's list with chunks_per_batch behind min_phred and the queue's stats in place of the call's
+    L.mrp_queue_phase_aligned_chunks.argtypes = pa[:13] + [i64] + pa[13:-1] + [P(QueueStats)]
+    L.mrp_queue_phase_aligned_chunks_with_filtered.argtypes = pf[:14] + [i64] + pf[14:-1] + [P(QueueStats)]
+    L.mrp_phase_aligned_chunks_on_devices.argtypes = [vp, i32] + L.mrp_queue_phase_aligned_chunks.argtypes[1:]
+    L.mrp_phase_aligned_chunks_with_filtered_on_devices.argtypes = [vp, i32] + L.mrp_queue_phase_aligned_chunks_with_filtered.argtypes[1:]
     L.mrp_kmer_alignment_anchors_many.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, P(vp), P(PairHmmStats)]
     L.mrp_string_chunk_rest_from_extracted.argtypes = [P(ExtractedChunk), vp, vp, vp, i64, P(ExtractedChunk), vp, vp, i64, i64, P(StringChunkRest),
                                                        P(vp), P(vp)]
@@ -858,6 +867,16 @@ class Queue:
         """mrp_queue_phase_string_chunks -> (phase_string_chunks' list of dicts in input order, QueueStats)"""
         return _queue_phase_string_chunks(self.h, chunks, forward_model, reverse_model, params, min_phred, chunks_per_batch, expansion, sv_threshold,
                                           het_substitution_probability, profiles, structs)
+
+    def phase_aligned_chunks(self, chunks, forward_model: "PairHmm", reverse_model: "PairHmm", params: Params, chunks_per_batch: int = 0, **kw):
+        """mrp_queue_phase_aligned_chunks -> (phase_aligned_chunks' list of dicts in input order, QueueStats); further arguments as there"""
+        return _phase_aligned(None, chunks, forward_model, reverse_model, params, queue=self.h, chunks_per_batch=chunks_per_batch, **kw)
+
+    def phase_aligned_chunks_with_filtered(self, chunks, rests, forward_model: "PairHmm", reverse_model: "PairHmm", params: Params,
+                                           chunks_per_batch: int = 0, **kw):
+        """mrp_queue_phase_aligned_chunks_with_filtered -> (phase_aligned_chunks_with_filtered's list of dicts in input order, QueueStats)"""
+        return _phase_aligned(None, chunks, forward_model, reverse_model, params, rests=rests, with_rest=True, queue=self.h,
+                              chunks_per_batch=chunks_per_batch, **kw)
 
     def close(self):
         if self.h:
@@ -1738,6 +1757,10 @@ def aligned_chunk_rest_struct(filtered_chunk, gt):
     return R, keep
 
 
+_NO_QUEUE = object()  # (None is the NULL queue)
+LAST_ALIGNED_CALL_MS = 0.0  # wall time of the last C call _phase_aligned made, without the binding's conversions around it (tools/)
+
+
 def phase_aligned_chunks_with_filtered(ctx: Optional[Context], chunks, rests, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm],
                                        params: Optional[Params], **kw):
     """mrp_phase_aligned_chunks_with_filtered -> (phase_aligned_chunks' list of dicts, each with "filtered" (dict(read_hap, h1, h2 over the
@@ -1753,15 +1776,50 @@ def phase_aligned_chunks(ctx: Optional[Context], chunks, forward_model: Optional
     return _phase_aligned(ctx, chunks, forward_model, reverse_model, params, **kw)
 
 
+def aligned_chunk_units(chunk, rest=None, struct=None, rest_struct=None) -> int:
+    """mrp_aligned_chunk_units: the (read, variant) units uniform coverage gives one chunk (a margin_amd.synth.AlignedChunk), with rest (the
+    filtered AlignedChunk, or (filtered AlignedChunk, gt)) the rest's variants counted as well -- what the work queue orders and cuts by"""
+    S = struct if struct is not None else aligned_chunk_struct(chunk)
+    R = rest_struct
+    if R is None and rest is not None:
+        f, gt = rest if isinstance(rest, tuple) else (rest, np.zeros((len(rest.alleles), 2), np.int32))
+        R = aligned_chunk_rest_struct(f, gt)
+    u = C.c_int64(-1)
+    _check(load().mrp_aligned_chunk_units(C.byref(S[0]), None if R is None else C.byref(R[0]), C.byref(u)))
+    return int(u.value)
+
+
+def phase_aligned_chunks_on_devices(devices, chunks, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm], params: Optional[Params],
+                                    chunks_per_batch: int = 0, **kw):
+    """mrp_phase_aligned_chunks_on_devices -> (phase_aligned_chunks' list of dicts in input order, QueueStats)"""
+    return _phase_aligned(None, chunks, forward_model, reverse_model, params, devices=list(devices), chunks_per_batch=chunks_per_batch, **kw)
+
+
+def phase_aligned_chunks_with_filtered_on_devices(devices, chunks, rests, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm],
+                                                  params: Optional[Params], chunks_per_batch: int = 0, **kw):
+    """mrp_phase_aligned_chunks_with_filtered_on_devices -> (phase_aligned_chunks_with_filtered's list of dicts in input order, QueueStats)"""
+    return _phase_aligned(None, chunks, forward_model, reverse_model, params, rests=rests, with_rest=True, devices=list(devices),
+                          chunks_per_batch=chunks_per_batch, **kw)
+
+
 def _phase_aligned(ctx: Optional[Context], chunks, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm], params: Optional[Params],
                    options: Optional[dict] = None, keeps=None, min_phred: int = 0, expansion: int = 4, sv_threshold: int = 512,
                    het_substitution_probability: float = 0.0, profiles: bool = False, structs=None, nulls=(), rests=None, rest_structs=None,
-                   with_rest: bool = False):
+                   with_rest: bool = False, queue=_NO_QUEUE, devices=None, chunks_per_batch: int = 0):
     """mrp_phase_aligned_chunks -> (per chunk dict(result, hap int8 [n_reads], phred, bubble_variant int64 [n_bubbles][, profile]),
     PhaseAlignedStats).  keeps: None, or per chunk None / a uint8 mask over its reads.  ctx / a model / params None pass NULL;
     nulls names further arguments to pass as NULL ("options", "out", "hap_out", "read_names", "hap_out[0]", "phred_out[0]",
-    "read_names[0]", "read_names[0][0]": for the argument checks).  On an error the output arrays are checked to be untouched."""
+    "read_names[0]", "read_names[0][0]": for the argument checks).  On an error the output arrays are checked to be untouched.
+    queue (a mrp_queue handle, or None for a NULL queue) or devices (a list) select the work queue's twins, which take
+    chunks_per_batch and return a QueueStats."""
+    global LAST_ALIGNED_CALL_MS
     L = load()
+    queued = queue is not _NO_QUEUE or devices is not None
+    if devices is not None:
+        dev = (C.c_int32 * max(len(devices), 1))(*devices)
+        head = (C.cast(dev, C.c_void_p), len(devices))
+    else:
+        head = (queue,) if queued else (ctx.h if ctx else None,)
     n = len(chunks)
     built = structs if structs is not None else [aligned_chunk_struct(c) for c in chunks]
     arr = (AlignedChunk * max(n, 1))(*[b[0] for b in built])
@@ -1788,12 +1846,15 @@ def _phase_aligned(ctx: Optional[Context], chunks, forward_model: Optional[PairH
     prof = (ProfileOut * max(n, 1))() if profiles else None
     bv = (C.c_void_p * max(n, 1))()
     by = lambda m: None if m is None else C.byref(m)
+    per_batch = (int(chunks_per_batch),) if queued else ()
     if not with_rest:
-        st = PhaseAlignedStats()
-        rc = L.mrp_phase_aligned_chunks(ctx.h if ctx else None, n, arr, None if "read_names" in nulls else name_ptrs, None if keeps is None else mask_ptrs,
-                                        None if "options" in nulls else C.byref(opt), by(forward_model), by(reverse_model), int(expansion), int(sv_threshold),
-                                        float(het_substitution_probability), by(params), int(min_phred), None if "out" in nulls else res,
-                                        None if "hap_out" in nulls else hp, pp, prof, bv, C.byref(st))
+        st = QueueStats() if queued else PhaseAlignedStats()
+        fn = (L.mrp_phase_aligned_chunks_on_devices if devices is not None else L.mrp_queue_phase_aligned_chunks) if queued else L.mrp_phase_aligned_chunks
+        t_call = time.perf_counter()
+        rc = fn(*head, n, arr, None if "read_names" in nulls else name_ptrs, None if keeps is None else mask_ptrs,
+                None if "options" in nulls else C.byref(opt), by(forward_model), by(reverse_model), int(expansion), int(sv_threshold),
+                float(het_substitution_probability), by(params), int(min_phred), *per_batch, None if "out" in nulls else res,
+                None if "hap_out" in nulls else hp, pp, prof, bv, C.byref(st))
     else:
         rbuilt = rest_structs if rest_structs is not None else [aligned_chunk_rest_struct(f, g) for f, g in rests]
         rarr = (AlignedChunkRest * max(n, 1))(*[b[0] for b in rbuilt])
@@ -1802,16 +1863,24 @@ def _phase_aligned(ctx: Optional[Context], chunks, forward_model: Optional[PairH
         fout = (FilteredOut * max(n, 1))()
         fout[0].n_reads = 77  # (zeroed whatever the outcome)
         fr = (C.c_void_p * max(n, 1))()
-        st = PhaseAlignedFilteredStats()
-        rc = L.mrp_phase_aligned_chunks_with_filtered(ctx.h if ctx else None, n, arr, None if "rest" in nulls else rarr, None if "read_names" in nulls else name_ptrs,
-                                                      None if keeps is None else mask_ptrs, None if "options" in nulls else C.byref(opt), by(forward_model),
-                                                      by(reverse_model), int(expansion), int(sv_threshold), float(het_substitution_probability), by(params),
-                                                      int(min_phred), None if "out" in nulls else res, None if "hap_out" in nulls else hp, pp, prof, bv,
-                                                      None if "filtered_out" in nulls else fout, None if "filtered_read_out" in nulls else fr, C.byref(st))
+        st = QueueStats() if queued else PhaseAlignedFilteredStats()
+        fn = (L.mrp_phase_aligned_chunks_with_filtered_on_devices if devices is not None else L.mrp_queue_phase_aligned_chunks_with_filtered) if queued \
+            else L.mrp_phase_aligned_chunks_with_filtered
+        t_call = time.perf_counter()
+        rc = fn(*head, n, arr, None if "rest" in nulls else rarr, None if "read_names" in nulls else name_ptrs,
+                None if keeps is None else mask_ptrs, None if "options" in nulls else C.byref(opt), by(forward_model),
+                by(reverse_model), int(expansion), int(sv_threshold), float(het_substitution_probability), by(params),
+                int(min_phred), *per_batch, None if "out" in nulls else res, None if "hap_out" in nulls else hp, pp, prof, bv,
+                None if "filtered_out" in nulls else fout, None if "filtered_read_out" in nulls else fr, C.byref(st))
+    LAST_ALIGNED_CALL_MS = (time.perf_counter() - t_call) * 1e3
+    if with_rest:
         if rc != MRP_OK and n > 0 and not {"rest", "filtered_out", "filtered_read_out"} & set(nulls):
+            if queued and fout[0].n_reads == 77:  # (the queue writes nothing before its lanes start)
+                fout[0].n_reads = 0
             assert bytes(fout) == bytes((FilteredOut * max(n, 1))()) and not any(fr[i] for i in range(n)), "filtered_out not zeroed on an error"
     if rc != MRP_OK:
-        untouched = all((h == 99).all() for h in hap) and all(np.isnan(p).all() for p in phred) and not any(bool(res[i]) for i in range(n)) and \
+        # (a queue that stops on a lane's error has written hap_out / phred_out of the batches that were done)
+        untouched = (queued or (all((h == 99).all() for h in hap) and all(np.isnan(p).all() for p in phred))) and not any(bool(res[i]) for i in range(n)) and \
             not any(bv[i] for i in range(n)) and (prof is None or not any(prof[i].seqs or prof[i].pool for i in range(n)))
         assert untouched, "outputs written on an error"
     _check(rc)

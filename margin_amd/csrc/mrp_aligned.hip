@@ -163,7 +163,7 @@ namespace {
  * behind the allele strings in the call's one device pool, the owners kernel over it and what comes back from it -- indices, no symbol. */
 struct AlignedFront {
     const char *const who;
-    mrp_context *const ctx;
+    mrp_context *ctx; /* (a front made ahead of its run gets it when it is staged) */
     const int64_t n_chunks;
     const mrp_aligned_chunk *const chunks;
     mrp_extract_run *X = nullptr;
@@ -862,33 +862,104 @@ int PfRun::filtered_front(int64_t sv_threshold) {
 
 }  // namespace
 
-/* What the two entries share: rest, filtered_out, filtered_read_out and fstats are NULL for the plain call, whose records are its chunks */
-static int pa_phase_chunks(const char *who, double t_begin, mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *records, const mrp_aligned_chunk_rest *rest,
-                           const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
-                           const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
-                           double het_substitution_probability, const mrp_params *params, int64_t min_phred, mrp_phase_result **out, int8_t *const *hap_out,
-                           double *const *phred_out, mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
-                           int32_t **filtered_read_out, mrp_phase_aligned_stats *stats, mrp_phase_aligned_filtered_stats *fstats) {
-    PfRun R(who, ctx, n_chunks, records, rest, read_names, keep, stats);
-    int rc = R.check(options, forward_model, reverse_model, expansion, params, out, hap_out, phred_out);
-    if (rest && (rc == MRP_OK || rc == MRP_ERR_UNSUPPORTED)) { /* (every MRP_ERR_ARG comes before the refused modes) */
-        const int rc2 = R.check_rest();
+/* ---- the two entries in steps (mrp_internal.h): the checks, the device steps up to the launch classes, the string run ------------
+ * rest, filtered_out and filtered_read_out are NULL for the plain call, whose extraction records are its chunks. */
+static std::vector<mrp_aligned_chunk> pa_records(const mrp_aligned_args &a) {
+    std::vector<mrp_aligned_chunk> records;
+    if (!a.rest || !a.chunks || a.n_chunks <= 0) return records;
+    const int64_t n_chunks = a.n_chunks;
+    /* the extraction's chunk records: the chunks, then the same reads over the rests' variants */
+    records.resize((size_t) (2 * n_chunks));
+    for (int64_t c = 0; c < n_chunks; c++) {
+        records[(size_t) c] = a.chunks[c];
+        mrp_aligned_chunk &R = records[(size_t) (n_chunks + c)];
+        R = a.chunks[c];
+        R.n_variants = a.rest[c].n_variants;
+        R.variant_pos = a.rest[c].variant_pos;
+        R.allele_first = a.rest[c].allele_first;
+        R.allele_off = a.rest[c].allele_off;
+        R.allele_len = a.rest[c].allele_len;
+        R.allele_chars = a.rest[c].allele_chars;
+        R.allele_bytes = a.rest[c].allele_bytes;
+        R.is_sv = a.rest[c].is_sv;
+    }
+    return records;
+}
+
+struct mrp_aligned_front {
+    const mrp_aligned_args a;
+    const double t_begin;
+    mrp_phase_aligned_stats *const stats;
+    mrp_phase_aligned_filtered_stats *const fstats;
+    const std::vector<mrp_aligned_chunk> records;
+    PfRun R;
+    mrp_aligned_front(const char *who, double t0, const mrp_aligned_args &args, mrp_phase_aligned_stats *st, mrp_phase_aligned_filtered_stats *fst)
+        : a(args), t_begin(t0), stats(st), fstats(fst), records(pa_records(args)),
+          R(who, nullptr, args.n_chunks, args.rest ? records.data() : args.chunks, args.rest, args.read_names, args.keep, st) {}
+};
+
+/* every check of the call that needs no context, in the one call's order (every MRP_ERR_ARG comes before the refused modes); the
+ * extraction's run it leaves holds the windows */
+int mrp_aligned_front_create(const char *who, double t_begin, const mrp_aligned_args *a, mrp_phase_aligned_stats *stats,
+                             mrp_phase_aligned_filtered_stats *fstats, mrp_aligned_front **front_out) {
+    *front_out = nullptr;
+    mrp_aligned_front *A = new (std::nothrow) mrp_aligned_front(who, t_begin, *a, stats, fstats);
+    if (!A) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
+    int rc = A->R.check(a->options, a->forward_model, a->reverse_model, a->expansion, a->params, a->out, a->hap_out, a->phred_out);
+    if (a->rest && (rc == MRP_OK || rc == MRP_ERR_UNSUPPORTED)) {
+        const int rc2 = A->R.check_rest();
         if (rc2 != MRP_OK) rc = rc2;
     }
-    if (rc != MRP_OK) return rc;
-    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction and the pair-HMM have no CPU fallback)", who);
-    rc = R.extract();
+    if (rc != MRP_OK) {
+        delete A;
+        return rc;
+    }
+    *front_out = A;
+    return MRP_OK;
+}
+
+void mrp_aligned_front_destroy(mrp_aligned_front *front) { delete front; }
+
+int mrp_aligned_chunks_check(const char *who, const mrp_aligned_args *a) {
+    mrp_aligned_front *A = nullptr;
+    const int rc = mrp_aligned_front_create(who, now_ms(), a, nullptr, nullptr, &A);
+    mrp_aligned_front_destroy(A);
+    return rc;
+}
+
+/* on ctx, up to the launch classes: extraction, classes, owners, the pair list, the rests, the anchors; raises the 2 048-cell refusal */
+int mrp_aligned_front_stage(mrp_context *ctx, mrp_aligned_front *A) {
+    PfRun &R = A->R;
+    const mrp_aligned_args &a = A->a;
+    const bool rest = a.rest != nullptr;
+    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction and the pair-HMM have no CPU fallback)", R.who);
+    R.ctx = ctx;
+    int rc = R.extract();
     if (rc == MRP_OK && rest) rc = R.classes();
     if (rc == MRP_OK) rc = R.masked_owners();
-    if (rc == MRP_OK) rc = R.strings_and_pairs(sv_threshold);
+    if (rc == MRP_OK) rc = R.strings_and_pairs(a.sv_threshold);
     if (rc == MRP_OK && rest) rc = R.rests();
-    if (rc == MRP_OK && rest) rc = R.filtered_front(sv_threshold);
+    if (rc == MRP_OK && rest) rc = R.filtered_front(a.sv_threshold);
     if (rc == MRP_OK) rc = R.anchors();
-    if (rc == MRP_OK) rc = R.classify(forward_model, reverse_model, expansion);
-    if (rc != MRP_OK) return rc;
+    if (rc == MRP_OK) rc = R.classify(a.forward_model, a.reverse_model, a.expansion);
+    return rc;
+}
+
+/* the string run over a staged front, and the per-chunk lists; chunk_stats: NULL, or where the string run's stats go when the front
+ * has no stats of its own (the work queue counts the per-chunk path's chunks from them) */
+int mrp_aligned_front_run(mrp_aligned_front *A, mrp_string_chunks_stats *chunk_stats) {
+    PfRun &R = A->R;
+    const mrp_aligned_args &a = A->a;
+    const char *who = R.who;
+    mrp_context *ctx = R.ctx;
+    const int64_t n_chunks = a.n_chunks;
+    const bool rest = a.rest != nullptr;
+    mrp_phase_aligned_stats *stats = A->stats;
+    mrp_phase_aligned_filtered_stats *fstats = A->fstats;
+    int rc = MRP_OK;
     /* (made before anything is handed over: an error returns nothing) */
     if (rest) R.fr_out.assign((size_t) n_chunks, nullptr);
-    if (bubble_variant_out) R.bv_out.assign((size_t) n_chunks, nullptr);
+    if (a.bubble_variant_out) R.bv_out.assign((size_t) n_chunks, nullptr);
     for (int64_t c = 0; c < n_chunks; c++) {
         if (rest) {
             std::vector<int32_t> fr = R.ra[(size_t) c].filtered_read;
@@ -896,21 +967,21 @@ static int pa_phase_chunks(const char *who, double t_begin, mrp_context *ctx, in
             R.fr_out[(size_t) c] = (int32_t *) sc_dup(fr.data(), sizeof(int32_t) * fr.size());
             if (!R.fr_out[(size_t) c]) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
         }
-        if (!bubble_variant_out) continue;
+        if (!a.bubble_variant_out) continue;
         std::vector<int64_t> bv = R.arr[(size_t) c].bubble_variant;
         bv.push_back(-1); /* the end of the list: the caller has no other way to the bubble count */
         R.bv_out[(size_t) c] = (int64_t *) sc_dup(bv.data(), sizeof(int64_t) * bv.size());
         if (!R.bv_out[(size_t) c]) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
     }
-    for (int64_t c = 0; c < n_chunks; c++) out[c] = nullptr;
-    if (profiles_out && n_chunks > 0) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
+    for (int64_t c = 0; c < n_chunks; c++) a.out[c] = nullptr;
+    if (a.profiles_out && n_chunks > 0) memset(a.profiles_out, 0, sizeof(*a.profiles_out) * (size_t) n_chunks);
     mrp_string_filtered_stats fst;
     memset(&fst, 0, sizeof(fst));
     if (n_chunks > 0) {
         /* the rest of the string call unchanged: pair-HMM over the device pool, layout beside it, profile bytes, phasing, HP tags */
-        R.F.front_ms = now_ms() - t_begin;
-        rc = mrp_string_front_run(ctx, &R.F, het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out,
-                                  stats ? &stats->chunks : nullptr, filtered_out, fstats ? &fst : nullptr);
+        R.F.front_ms = now_ms() - A->t_begin;
+        rc = mrp_string_front_run(ctx, &R.F, a.het_substitution_probability, a.params, a.min_phred, a.out, a.hap_out, a.phred_out, a.profiles_out,
+                                  stats ? &stats->chunks : chunk_stats, a.filtered_out, fstats ? &fst : nullptr);
         if (rc != MRP_OK) return rc;
     }
     if (fstats) {
@@ -925,15 +996,26 @@ static int pa_phase_chunks(const char *who, double t_begin, mrp_context *ctx, in
         fstats->filtered_reads = R.n_filtered_reads;
         fstats->filtered_entries = R.D.n_entries - (n_chunks > 0 ? R.k_first[R.D.variant_first[n_chunks]] : 0);
     }
-    rc = R.hand_over(bubble_variant_out);
+    rc = R.hand_over(a.bubble_variant_out);
     if (rc != MRP_OK) return rc;
     if (rest) {
         R.class_arrays.release();
         ctx->pool.reclaim();
-        for (int64_t c = 0; c < n_chunks; c++) { filtered_read_out[c] = R.fr_out[(size_t) c]; R.fr_out[(size_t) c] = nullptr; }
+        for (int64_t c = 0; c < n_chunks; c++) { a.filtered_read_out[c] = R.fr_out[(size_t) c]; R.fr_out[(size_t) c] = nullptr; }
     }
-    if (stats) stats->total_ms = now_ms() - t_begin;
+    if (stats) stats->total_ms = now_ms() - A->t_begin;
     return MRP_OK;
+}
+
+/* What the two entries share: front, stage, run, destroy */
+static int pa_phase_chunks(const char *who, double t_begin, mrp_context *ctx, const mrp_aligned_args &a, mrp_phase_aligned_stats *stats,
+                           mrp_phase_aligned_filtered_stats *fstats) {
+    mrp_aligned_front *A = nullptr;
+    int rc = mrp_aligned_front_create(who, t_begin, &a, stats, fstats, &A);
+    if (rc == MRP_OK) rc = mrp_aligned_front_stage(ctx, A);
+    if (rc == MRP_OK) rc = mrp_aligned_front_run(A, nullptr);
+    mrp_aligned_front_destroy(A);
+    return rc;
 }
 
 extern "C" int mrp_phase_aligned_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const char *const *const *read_names,
@@ -944,9 +1026,9 @@ extern "C" int mrp_phase_aligned_chunks(mrp_context *ctx, int64_t n_chunks, cons
                                         mrp_phase_aligned_stats *stats) {
     const double t_begin = now_ms();
     if (stats) memset(stats, 0, sizeof(*stats));
-    return pa_phase_chunks("mrp_phase_aligned_chunks", t_begin, ctx, n_chunks, chunks, nullptr, read_names, keep, options, forward_model, reverse_model, expansion,
-                           sv_threshold, het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr,
-                           nullptr, stats, nullptr);
+    const mrp_aligned_args a{n_chunks, chunks, nullptr, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
+                             het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr};
+    return pa_phase_chunks("mrp_phase_aligned_chunks", t_begin, ctx, a, stats, nullptr);
 }
 
 extern "C" int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
@@ -962,22 +1044,8 @@ extern "C" int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t 
     if (n_chunks < 0 || n_chunks >= (1ll << 30) || (n_chunks > 0 && (!chunks || !rest || !filtered_out || !filtered_read_out)))
         return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
     if (n_chunks > 0) memset(filtered_out, 0, sizeof(*filtered_out) * (size_t) n_chunks);
-    /* the extraction's chunk records: the chunks, then the same reads over the rests' variants */
-    std::vector<mrp_aligned_chunk> records((size_t) (2 * n_chunks));
-    for (int64_t c = 0; c < n_chunks; c++) {
-        records[(size_t) c] = chunks[c];
-        mrp_aligned_chunk &R = records[(size_t) (n_chunks + c)];
-        R = chunks[c];
-        R.n_variants = rest[c].n_variants;
-        R.variant_pos = rest[c].variant_pos;
-        R.allele_first = rest[c].allele_first;
-        R.allele_off = rest[c].allele_off;
-        R.allele_len = rest[c].allele_len;
-        R.allele_chars = rest[c].allele_chars;
-        R.allele_bytes = rest[c].allele_bytes;
-        R.is_sv = rest[c].is_sv;
-    }
-    return pa_phase_chunks(who, t_begin, ctx, n_chunks, records.data(), rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
-                           het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
-                           filtered_read_out, stats ? &stats->aligned : nullptr, stats);
+    const mrp_aligned_args a{n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
+                             het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
+                             filtered_read_out};
+    return pa_phase_chunks(who, t_begin, ctx, a, stats ? &stats->aligned : nullptr, stats);
 }

@@ -617,6 +617,45 @@ void mrp_extract_run_alleles(const mrp_extract_run *run, uint8_t *dst, int64_t *
 int mrp_kmer_anchors_on_device(mrp_context *ctx, const char *who, const uint8_t *device_pool, int64_t n_pairs, const int64_t *x_off,
                                const int32_t *x_len, const int64_t *y_off, const int32_t *y_len, int64_t *anchor_off, std::vector<int64_t> &anchors,
                                double *kernel_ms, int64_t *bytes_downloaded, int64_t *n_runs_out);
+/* mrp_phase_aligned_chunks and mrp_phase_aligned_chunks_with_filtered in steps (mrp_aligned.hip), so that a work queue can check every
+ * chunk before its first lane starts and a lane can make the host part of its next batch's front beside the current batch:
+ *   check    every MRP_ERR_ARG of the call, then MRP_ERR_UNSUPPORTED for the two refused extraction modes, over all chunks and in the
+ *            one call's order (host only, no context; messages name the chunks as the one call does);
+ *   create   the same checks, and the front they leave: the extraction's records and run with the windows (host only; any thread);
+ *   stage    on ctx, on its thread: the extraction, the classes, the owners, the pair list, the rests, the anchors, the launch
+ *            classes -- MRP_ERR_NO_DEVICE for a NULL ctx, MRP_ERR_UNSUPPORTED for a diagonal beyond 2 048 cells;
+ *   run      the string run over the staged front and the per-chunk lists; a front is staged and run once, on one thread;
+ *   destroy  on the thread of ctx once the front was staged (it drains the stream and gives the device arrays back).
+ * rest, filtered_out and filtered_read_out are NULL for the plain call.  The front keeps every pointer of args: the arrays live until it
+ * is destroyed.  stats / filtered_stats (zeroed by the caller) may be NULL; chunk_stats of run: where the string run's stats go when
+ * the front has no stats. */
+struct mrp_aligned_front;
+struct mrp_aligned_args {
+    int64_t n_chunks;
+    const mrp_aligned_chunk *chunks;
+    const mrp_aligned_chunk_rest *rest;
+    const char *const *const *read_names;
+    const uint8_t *const *keep;
+    const mrp_extract_options *options;
+    const mrp_pair_hmm *forward_model, *reverse_model;
+    int64_t expansion, sv_threshold;
+    double het_substitution_probability;
+    const mrp_params *params;
+    int64_t min_phred;
+    mrp_phase_result **out;
+    int8_t *const *hap_out;
+    double *const *phred_out;
+    mrp_profile_out *profiles_out;
+    int64_t **bubble_variant_out;
+    mrp_filtered_out *filtered_out;
+    int32_t **filtered_read_out;
+};
+int mrp_aligned_chunks_check(const char *who, const mrp_aligned_args *args);
+int mrp_aligned_front_create(const char *who, double t_begin_ms, const mrp_aligned_args *args, mrp_phase_aligned_stats *stats,
+                             mrp_phase_aligned_filtered_stats *filtered_stats, mrp_aligned_front **front_out);
+int mrp_aligned_front_stage(mrp_context *ctx, mrp_aligned_front *front);
+int mrp_aligned_front_run(mrp_aligned_front *front, mrp_string_chunks_stats *chunk_stats);
+void mrp_aligned_front_destroy(mrp_aligned_front *front);
 extern "C" void mrp_batch_last_launch_ms(struct mrp_batch *b, float *pack, float *emission, float *recursion);
 
 /* development: MRP_DUP=<letters> launches the named kernel families of a resident level TWICE (they are idempotent) -- the slow-down of a

@@ -700,3 +700,276 @@ int mrp_phase_string_chunks_on_devices(const int32_t *devices, int32_t n_devices
 }
 
 }  /* extern "C" */
+
+/* ---- aligned chunks: mrp_queue_phase_aligned_chunks (rest == NULL) and mrp_queue_phase_aligned_chunks_with_filtered ---------------------- */
+extern "C" int mrp_aligned_chunk_units(const mrp_aligned_chunk *chunk, const mrp_aligned_chunk_rest *rest, int64_t *units_out) {
+    static const char *who = "mrp_aligned_chunk_units";
+    if (!chunk || !units_out) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    const mrp_aligned_chunk &C = *chunk;
+    if (C.n_reads < 0 || C.n_variants < 0 || (rest && rest->n_variants < 0)) return mrp_set_error(MRP_ERR_ARG, "%s: negative count", who);
+    if (C.overlap_end < C.overlap_start) return mrp_set_error(MRP_ERR_ARG, "%s: overlap_end before overlap_start", who);
+    if (C.n_reads > 0 && !C.l_qseq) return mrp_set_error(MRP_ERR_ARG, "%s: null l_qseq", who);
+    unsigned __int128 bases = 0;
+    for (int64_t r = 0; r < C.n_reads; r++) {
+        if (C.l_qseq[r] < 0) return mrp_set_error(MRP_ERR_ARG, "%s: read %lld: negative l_qseq", who, (long long) r);
+        bases += (unsigned __int128) C.l_qseq[r];
+    }
+    /* (B < 2^62 and V < 2^64: the product fits 128 bits) */
+    const unsigned __int128 variants = (unsigned __int128) C.n_variants + (unsigned __int128) (rest ? rest->n_variants : 0);
+    const unsigned __int128 length = (unsigned __int128) std::max<int64_t>(1, C.overlap_end - C.overlap_start);
+    const unsigned __int128 units = bases * variants / length;
+    *units_out = units > (unsigned __int128) INT64_MAX ? INT64_MAX : (int64_t) units;
+    return MRP_OK;
+}
+
+namespace {
+
+/* what a call of either entry carries beside the queue and the batch size */
+struct AlignedQueueArgs {
+    const char *who;
+    mrp_aligned_args a;
+    int64_t chunks_per_batch;
+    mrp_queue_stats *stats;
+};
+
+/* the entry's own null arguments, then every chunk's checks on the caller's thread and in the one call's order: MRP_ERR_ARG, then
+ * MRP_ERR_UNSUPPORTED for the two refused extraction modes; no queue, no device */
+int aligned_queue_check(const AlignedQueueArgs &A, bool with_rest) {
+    const mrp_aligned_args &a = A.a;
+    if (with_rest && (a.n_chunks < 0 || a.n_chunks >= (1ll << 30) || (a.n_chunks > 0 && (!a.chunks || !a.rest || !a.filtered_out || !a.filtered_read_out))))
+        return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", A.who);
+    return mrp_aligned_chunks_check(A.who, &a);
+}
+
+int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool with_rest, bool checked = false) {
+    const char *who = A.who;
+    const mrp_aligned_args &a = A.a;
+    const int64_t n_chunks = a.n_chunks;
+    const mrp_aligned_chunk_rest *rest = with_rest ? a.rest : nullptr;
+    mrp_queue_stats *stats = A.stats;
+    int rc = checked ? (int) MRP_OK : aligned_queue_check(A, with_rest);
+    if (rc != MRP_OK) return rc;
+    if (!q) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no queue (the extraction and the pair-HMM have no CPU fallback)", who);
+    const int n_devices = (int) q->devices.size();
+    if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = n_devices; }
+    for (int64_t i = 0; i < n_chunks; i++) {
+        a.out[i] = nullptr;
+        if (a.bubble_variant_out) a.bubble_variant_out[i] = nullptr;
+        if (rest) a.filtered_read_out[i] = nullptr;
+    }
+    if (a.profiles_out && n_chunks > 0) memset(a.profiles_out, 0, sizeof(*a.profiles_out) * (size_t) n_chunks);
+    if (rest && n_chunks > 0) memset(a.filtered_out, 0, sizeof(*a.filtered_out) * (size_t) n_chunks);
+    if (n_chunks == 0) return MRP_OK;
+    /* phase.c:257-263 orders by estimated depth; here by the (read, variant) substrings uniform coverage gives a chunk (a read the
+     * extraction does not walk, l_qseq <= 0, passes its checks: such a chunk is ordered as if it cost nothing) */
+    std::vector<int64_t> cost((size_t) n_chunks, 0);
+    for (int64_t i = 0; i < n_chunks; i++)
+        if (mrp_aligned_chunk_units(&a.chunks[i], rest ? &rest[i] : nullptr, &cost[(size_t) i]) != MRP_OK) cost[(size_t) i] = 0;
+    const int lanes = q->lanes, n_workers = n_devices * lanes;
+    const QueuePlan plan = plan_queue(n_chunks, cost.data(), A.chunks_per_batch, n_workers, n_devices);
+    const int64_t n_batches = (int64_t) plan.batch_off.size() - 1;
+    if (stats) stats->batches = n_batches;
+    QueueCall call(q, n_batches, active_lanes_of(plan, cost.data(), n_devices, lanes));
+
+    /* a batch as one mrp_phase_aligned_chunks(_with_filtered) call sees it: its chunks in plan order with what travels with them, the
+     * call's outputs, and the front -- its host part (the extraction's records, the chunks' checks and windows) made by the prefetch
+     * beside the lane's current batch, its device part staged on the lane's context when the batch is run */
+    struct Staged {
+        std::atomic<int64_t> batch{-1}; /* (the call's thread looks its batch up while the stager fills the lane's OTHER slot) */
+        int64_t first = 0, count = 0;
+        std::vector<mrp_aligned_chunk> ch;
+        std::vector<mrp_aligned_chunk_rest> rs;
+        std::vector<const char *const *> names;
+        std::vector<const uint8_t *> keep;
+        std::vector<mrp_phase_result *> res;
+        std::vector<int8_t *> hap;
+        std::vector<double *> phred;
+        std::vector<mrp_profile_out> prof;
+        std::vector<int64_t *> bv;
+        std::vector<mrp_filtered_out> fo;
+        std::vector<int32_t *> fr;
+        mrp_aligned_front *front = nullptr;
+    };
+    struct Lane { Staged st[2]; int n_staged = 0; };
+    std::vector<Lane> lane_state((size_t) n_workers);
+    auto staged_of = [&](int w, int64_t b) -> Staged * {
+        Lane &L = lane_state[(size_t) w];
+        return L.st[0].batch.load() == b ? &L.st[0] : (L.st[1].batch.load() == b ? &L.st[1] : nullptr);
+    };
+    /* (a staged front holds arrays of the lane's context: it goes with no other thread of the lane at work, on the lane's thread) */
+    auto drop = [&](Staged *st) { mrp_aligned_front_destroy(st->front); st->front = nullptr; st->batch = -1; };
+    auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    LaneHooks hk;
+    hk.begin = [&](int w) { return call.lane_begin(w, false); };
+    hk.prefetch = [&](int w, int64_t b) { /* host only: never the lane's context, its stream, its events or its pool */
+        const auto t0 = std::chrono::steady_clock::now();
+        mrp_pool_adopt(q->pools[(size_t) (w / lanes)]);
+        Lane &L = lane_state[(size_t) w];
+        Staged *st = &L.st[L.n_staged++ & 1];
+        st->first = plan.batch_off[(size_t) b]; st->count = plan.batch_off[(size_t) b + 1] - st->first;
+        const size_t count = (size_t) st->count;
+        st->ch.resize(count); st->names.resize(count); st->hap.resize(count);
+        st->rs.resize(rest ? count : 0);
+        st->keep.resize(a.keep ? count : 0);
+        st->phred.resize(a.phred_out ? count : 0);
+        st->res.assign(count, nullptr);
+        st->bv.assign(a.bubble_variant_out ? count : 0, nullptr);
+        st->fr.assign(rest ? count : 0, nullptr);
+        st->prof.resize(a.profiles_out ? count : 0);
+        st->fo.resize(rest ? count : 0);
+        if (a.profiles_out) memset(st->prof.data(), 0, sizeof(mrp_profile_out) * count);
+        if (rest) memset(st->fo.data(), 0, sizeof(mrp_filtered_out) * count);
+        for (size_t i = 0; i < count; i++) {
+            const int64_t chunk = plan.order[(size_t) st->first + i];
+            st->ch[i] = a.chunks[chunk];
+            st->names[i] = a.read_names[chunk];
+            st->hap[i] = a.hap_out[chunk];
+            if (rest) st->rs[i] = rest[chunk];
+            if (a.keep) st->keep[i] = a.keep[chunk];
+            if (a.phred_out) st->phred[i] = a.phred_out[chunk];
+        }
+        st->batch.store(b);
+        mrp_aligned_args ba = a;
+        ba.n_chunks = st->count;
+        ba.chunks = st->ch.data();
+        ba.rest = rest ? st->rs.data() : nullptr;
+        ba.read_names = st->names.data();
+        ba.keep = a.keep ? st->keep.data() : nullptr;
+        ba.out = st->res.data();
+        ba.hap_out = st->hap.data();
+        ba.phred_out = a.phred_out ? st->phred.data() : nullptr;
+        ba.profiles_out = a.profiles_out ? st->prof.data() : nullptr;
+        ba.bubble_variant_out = a.bubble_variant_out ? st->bv.data() : nullptr;
+        ba.filtered_out = rest ? st->fo.data() : nullptr;
+        ba.filtered_read_out = rest ? st->fr.data() : nullptr;
+        const double t_begin = std::chrono::duration<double, std::milli>(t0.time_since_epoch()).count();
+        const int r = mrp_aligned_front_create(who, t_begin, &ba, nullptr, nullptr, &st->front);
+        if (r != MRP_OK) call.stage_errs[(size_t) w] = mrp_last_error();
+        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: checks and windows of batch %lld (%lld chunks) in %.1f ms\n", call.since(), w, (long long) b,
+                                 (long long) st->count, ms_since(t0));
+        return r;
+    };
+    hk.discard = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
+    hk.phase = [&](int w, int64_t b) {
+        Staged *cur = staged_of(w, b);
+        if (!cur || !cur->front) { call.errs[(size_t) w] = "work queue: batch has no front"; return (int) MRP_ERR_ARG; }
+        const auto t0 = std::chrono::steady_clock::now();
+        const int64_t count = cur->count;
+        mrp_string_chunks_stats ss;
+        memset(&ss, 0, sizeof(ss));
+        int r = mrp_aligned_front_stage(q->ctx[(size_t) w], cur->front);
+        const double front_ms = ms_since(t0);
+        if (r == MRP_OK) r = mrp_aligned_front_run(cur->front, &ss);
+        QueueCall::PerLane &me = call.per[(size_t) w];
+        if (r != MRP_OK) call.errs[(size_t) w] = mrp_last_error();
+        else {
+            for (int64_t i = 0; i < count; i++) {
+                const int64_t chunk = plan.order[(size_t) (cur->first + i)];
+                a.out[chunk] = cur->res[(size_t) i];
+                if (a.profiles_out) a.profiles_out[chunk] = cur->prof[(size_t) i];
+                if (a.bubble_variant_out) a.bubble_variant_out[chunk] = cur->bv[(size_t) i];
+                if (rest) { a.filtered_out[chunk] = cur->fo[(size_t) i]; a.filtered_read_out[chunk] = cur->fr[(size_t) i]; }
+                me.units += cost[(size_t) chunk];
+            }
+            me.chunks += count;
+            me.fallback += ss.phase.resident ? ss.phase.fallback_chunks : count;
+        }
+        const double all_ms = ms_since(t0);
+        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld: device front in %.1f ms, run in %.1f ms\n", call.since(), w, (long long) b, front_ms,
+                                 all_ms - front_ms);
+        me.busy_ms += all_ms;
+        return r;
+    };
+    hk.retire = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
+    hk.end = [&](int w) { call.lane_end(w); };
+    rc = call.run(hk);
+    call.fill(stats);
+    if (rc != MRP_OK) {
+        for (int64_t i = 0; i < n_chunks; i++) {
+            mrp_phase_result_destroy(a.out[i]);
+            a.out[i] = nullptr;
+            if (a.profiles_out) mrp_profile_out_clear(&a.profiles_out[i]);
+            if (a.bubble_variant_out) { free(a.bubble_variant_out[i]); a.bubble_variant_out[i] = nullptr; }
+            if (rest) {
+                mrp_filtered_out_clear(&a.filtered_out[i]);
+                free(a.filtered_read_out[i]);
+                a.filtered_read_out[i] = nullptr;
+            }
+        }
+        return call.error(rc);
+    }
+    return MRP_OK;
+}
+
+/* create + call + destroy, with the queue's own order of errors: a malformed call and a refused mode need no device */
+int aligned_on_devices(const int32_t *devices, int32_t n_devices, const AlignedQueueArgs &A, bool with_rest) {
+    int rc = aligned_queue_check(A, with_rest);
+    if (rc != MRP_OK) return rc;
+    mrp_queue *q = nullptr;
+    rc = mrp_queue_create(devices, n_devices, &q);
+    if (rc == MRP_OK) rc = queue_phase_aligned_chunks(q, A, with_rest, true);
+    mrp_queue_destroy(q);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrp_queue_phase_aligned_chunks(mrp_queue *q, int64_t n_chunks, const mrp_aligned_chunk *chunks, const char *const *const *read_names,
+                                   const uint8_t *const *keep, const mrp_extract_options *options, const mrp_pair_hmm *forward_model,
+                                   const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
+                                   const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out,
+                                   double *const *phred_out, mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_queue_stats *stats) {
+    const AlignedQueueArgs A{"mrp_queue_phase_aligned_chunks",
+                             {n_chunks, chunks, nullptr, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
+                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr},
+                             chunks_per_batch, stats};
+    return queue_phase_aligned_chunks(q, A, false);
+}
+
+int mrp_queue_phase_aligned_chunks_with_filtered(mrp_queue *q, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
+                                                 const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
+                                                 const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                                                 int64_t sv_threshold, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                 int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                 mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
+                                                 int32_t **filtered_read_out, mrp_queue_stats *stats) {
+    const AlignedQueueArgs A{"mrp_queue_phase_aligned_chunks_with_filtered",
+                             {n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
+                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
+                              filtered_read_out},
+                             chunks_per_batch, stats};
+    return queue_phase_aligned_chunks(q, A, true);
+}
+
+int mrp_phase_aligned_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,
+                                        const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
+                                        const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                        double het_substitution_probability, const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch,
+                                        mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                                        int64_t **bubble_variant_out, mrp_queue_stats *stats) {
+    const AlignedQueueArgs A{"mrp_phase_aligned_chunks_on_devices",
+                             {n_chunks, chunks, nullptr, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
+                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr},
+                             chunks_per_batch, stats};
+    return aligned_on_devices(devices, n_devices, A, false);
+}
+
+int mrp_phase_aligned_chunks_with_filtered_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,
+                                                      const mrp_aligned_chunk_rest *rest, const char *const *const *read_names, const uint8_t *const *keep,
+                                                      const mrp_extract_options *options, const mrp_pair_hmm *forward_model,
+                                                      const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                                      double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                      int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                      mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
+                                                      int32_t **filtered_read_out, mrp_queue_stats *stats) {
+    const AlignedQueueArgs A{"mrp_phase_aligned_chunks_with_filtered_on_devices",
+                             {n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
+                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
+                              filtered_read_out},
+                             chunks_per_batch, stats};
+    return aligned_on_devices(devices, n_devices, A, true);
+}
+
+}  /* extern "C" */

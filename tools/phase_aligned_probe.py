@@ -14,6 +14,12 @@ them homozygous), mrp_phase_aligned_chunks_with_filtered beside ITS chain: both 
 mrp_string_chunk_from_extracted and mrp_string_chunk_rest_from_extracted per chunk, mrp_phase_string_chunks_with_filtered.  Both legs in
 one process on one context, a warm-up, the median of --reps; the legs' outputs are compared through a digest.  Writes
 profiles/phase_aligned/filtered.json (or --out).
+
+--queue (with or without --filtered): the work queue over the same chunks beside the ONE call.  Leg (a) is mrp_phase_aligned_chunks
+(_with_filtered) on one context; leg (b) is mrp_queue_phase_aligned_chunks(_with_filtered) on a queue over device 0, with
+--per-batch chunks per batch (12) and with 0, the library's cut.  One process, a warm-up of every leg, the median of --reps with min and
+max, the wall time of the C call alone; one digest over every output per leg.  Writes (or, when the file holds the other variant's
+record, adds to) profiles/phase_aligned/queue.json (or --out).
 """
 import argparse
 import ctypes as C
@@ -43,8 +49,10 @@ def main():
     ap.add_argument("--cache", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--filtered", action="store_true")
+    ap.add_argument("--queue", action="store_true")
+    ap.add_argument("--per-batch", type=int, default=12)
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "phase_aligned", "filtered.json" if a.filtered else "probe.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "phase_aligned", "queue.json" if a.queue else ("filtered.json" if a.filtered else "probe.json"))
     opts = capi.shipped_extract_options()
     if a.cache and os.path.exists(a.cache):
         with open(a.cache, "rb") as f:
@@ -58,6 +66,8 @@ def main():
         if a.cache:
             with open(a.cache, "wb") as f:
                 pickle.dump(distinct, f)
+    if a.queue:
+        return queue_legs(a, distinct, opts)
     if a.filtered:
         return filtered_legs(a, distinct, opts)
     chunks = [distinct[i % a.distinct] for i in range(a.chunks)]
@@ -316,6 +326,86 @@ def filtered_legs(a, distinct, opts):
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write(line + "\n")
+
+
+def queue_legs(a, distinct, opts):
+    n = a.chunks
+    parts = [split(c) for c in distinct] if a.filtered else [(c, None, None) for c in distinct]
+    chunks = [parts[i % a.distinct][0] for i in range(n)]
+    built = [capi.aligned_chunk_struct(c) for c in chunks]
+    rbuilt = [capi.aligned_chunk_rest_struct(parts[i % a.distinct][1], parts[i % a.distinct][2]) for i in range(n)] if a.filtered else None
+    fwd = capi.PairHmm.from_margin_hmm(*synth.margin_phase_pair_hmm_arrays())
+    rev = fwd.reverse_complement()
+    params = capi.Params.from_reference_names(synth.shipped_phase_params())
+    units = [capi.aligned_chunk_units(None, struct=built[i], rest_struct=rbuilt[i] if a.filtered else None) for i in range(n)]
+    kw = dict(options=opts, structs=built, sv_threshold=SV_THRESHOLD)
+    if a.filtered:
+        kw.update(rest_structs=rbuilt)
+
+    def digest(got):
+        h = hashlib.sha256()
+        for g in got:
+            items = [g["hap"], g["phred"], g["result"]["hap1"], g["result"]["hap2"], g["bubble_variant"]]
+            if a.filtered:
+                o = g["filtered"]
+                items += [o["read_hap"], o["h1"], o["h2"], o["variant_state"], o["cis"], o["trans"], g["filtered_read"]]
+            for x in items:
+                h.update(np.ascontiguousarray(x).tobytes())
+        return h.hexdigest()
+
+    def one_call(ctx):
+        if a.filtered:
+            got, st = capi.phase_aligned_chunks_with_filtered(ctx, chunks, None, fwd, rev, params, **kw)
+            return digest(got), capi.LAST_ALIGNED_CALL_MS, st.aligned
+        got, st = capi.phase_aligned_chunks(ctx, chunks, fwd, rev, params, **kw)
+        return digest(got), capi.LAST_ALIGNED_CALL_MS, st
+
+    def queued(q, per_batch):
+        if a.filtered:
+            got, st = q.phase_aligned_chunks_with_filtered(chunks, None, fwd, rev, params, chunks_per_batch=per_batch, **kw)
+        else:
+            got, st = q.phase_aligned_chunks(chunks, fwd, rev, params, chunks_per_batch=per_batch, **kw)
+        return digest(got), capi.LAST_ALIGNED_CALL_MS, st
+
+    legs = {"one_call": [], f"queue_{a.per_batch}": [], "queue_0": []}
+    digests, qstats = {}, {}
+    q = capi.Queue([0])
+    try:
+        with capi.Context(0) as ctx:
+            one_call(ctx)  # warm-up of every leg: module load, the contexts' pools, the lanes' contexts
+            queued(q, a.per_batch)
+            queued(q, 0)
+            for _ in range(a.reps):
+                d, w, st_a = one_call(ctx)
+                legs["one_call"].append(w)
+                digests.setdefault("one_call", set()).add(d)
+                for per_batch in (a.per_batch, 0):
+                    d, w, st = queued(q, per_batch)
+                    legs[f"queue_{per_batch}"].append(w)
+                    digests.setdefault(f"queue_{per_batch}", set()).add(d)
+                    qstats[f"queue_{per_batch}"] = dict(batches=int(st.batches), busy_ms=round(float(st.busy_ms_per_device[0]), 2),
+                                                        fallback_chunks=int(st.fallback_chunks), units=int(st.units_per_device[0]))
+    finally:
+        q.close()
+    med = {k: float(np.median(v)) for k, v in legs.items()}
+    spread = max(legs["one_call"]) - min(legs["one_call"])
+    best = min(med[f"queue_{a.per_batch}"], med["queue_0"])
+    same = all(len(v) == 1 for v in digests.values()) and len(set.union(*digests.values())) == 1
+    res = dict(filtered=bool(a.filtered), chunks=n, distinct=a.distinct, reps=a.reps, lanes=int(os.environ.get("MRP_QUEUE_LANES", 4)), units_total=int(sum(units)),
+               prefetch_uploads_on_second_context=False,
+               walls_ms={k: dict(median=round(med[k], 2), min=round(min(v), 2), max=round(max(v), 2)) for k, v in legs.items()},
+               one_call_host_ms=round(st_a.chunks.host_ms, 2), one_call_extract_host_ms=round(st_a.extract.host_ms, 2), queue=qstats,
+               condition_best_queue_not_above_one_call_plus_spread=bool(best <= med["one_call"] + spread),
+               digest=sorted(digests["one_call"])[0], identical=bool(same))
+    print(json.dumps(res))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    record = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            record = json.load(f)
+    record["with_filtered" if a.filtered else "plain"] = res
+    with open(a.out, "w") as f:
+        f.write(json.dumps(record, indent=1) + "\n")
 
 
 if __name__ == "__main__":
