@@ -1056,6 +1056,47 @@ int mrp_phase_aligned_chunks_with_filtered_on_devices(const int32_t *devices, in
                                                       mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
                                                       int32_t **filtered_read_out, mrp_queue_stats *stats);
 
+/* ---- haplotagging a node's worth of aligned chunks from a phased VCF over its GPUs ----------------------------------------------
+ * The chunk loop of tools/tagFromPhasedVcf.c (:208-225: the chunks ordered by estimated depth, largest first; :227-235: "#pragma omp
+ * parallel for schedule(dynamic,1)" over them; :284-309: a chunk's body) around mrp_haplotag_aligned_chunks, as the work queue gives it
+ * to the other inputs.
+ *   Units: mrp_haplotag_chunk_units = floor(B * H / L) with B the sum of l_qseq over the chunk's reads, H the number of variants with
+ * gt[2v] != gt[2v + 1] -- only those are scored (bubbleGraph.c:1975): a chunk costs its pair-HMM work, not its variant count -- and
+ * L = max(1, overlap_end - overlap_start), computed in 128-bit integers and clamped to INT64_MAX, as mrp_aligned_chunk_units.  gt: the
+ * chunk's 2 * n_variants genotypes, compared and never range-checked; it may be NULL when n_variants == 0.  MRP_ERR_ARG, *units_out left
+ * alone, for what mrp_aligned_chunk_units refuses and for n_variants > 0 with a NULL gt.  Inside the queue a chunk whose units cannot
+ * be computed costs 0.  Largest first, ties in input order, batches cut by the rules of mrp_queue_phase_chunks (chunks_per_batch = 0:
+ * the library's cut).
+ *   A lane runs a batch as ONE mrp_haplotag_aligned_chunks call on its own context and its device's host pool; the part of the lane's
+ * NEXT batch that needs no device (its extraction records, the argument and chunk checks, the windows) is made on a thread beside it,
+ * which never touches the lane's context.  gt[c], hap_out[c], h1_out[c] and h2_out[c] travel with their chunk.
+ *   Results: hap_out[c], h1_out[c], h2_out[c] are, at every chunk's own position, bit for bit what ONE mrp_haplotag_aligned_chunks call
+ * over all chunks returns, whatever the batch size, the lanes, the devices or the hand-out.  h1_out and h2_out may each be NULL.
+ * stats as for aligned chunks: units_per_device in mrp_haplotag_chunk_units, fallback_chunks always 0 (there is no per-chunk path),
+ * batches set even when a lane fails.  n_chunks == 0 returns MRP_OK with zeroed stats (n_devices set).
+ *   Errors: every chunk is checked on the caller's thread before a lane starts, in the one call's order and with its messages, the chunk
+ * indices the caller's -- every MRP_ERR_ARG (the extraction's own checks; a NULL model, gt or hap_out; a NULL hap_out[c], h1_out[c] or
+ * h2_out[c] for a chunk with reads; a NULL gt[c] for a chunk with variants; a genotype outside its variant's alleles; an odd or
+ * negative expansion; a bad n_chunks), then MRP_ERR_UNSUPPORTED for the two refused extraction modes, both without a queue or a
+ * device; then MRP_ERR_NO_DEVICE for a NULL queue (n_chunks == 0 included).  Up to here nothing is written, stats included.  The
+ * *_on_devices form runs these checks, then mrp_queue_create reports its own error (a device that does not exist: MRP_ERR_ARG), then
+ * the call runs and the queue is destroyed.  The 2 048-cell diagonal refusal is known only after a batch's extraction: it is raised
+ * inside a lane, before any pair-HMM kernel of that batch, and arrives as a lane error, like an out-of-memory or a HIP error.  On a
+ * lane error the queue stops: remaining batches are dropped, prefetched ones discarded, the workers joined, the first error returned
+ * (mrp_last_error); the queue stays usable.  hap_out[c], h1_out[c] and h2_out[c] are then UNSPECIFIED for every chunk: batches that
+ * had finished have written theirs, the others not.  The call allocates nothing the caller has to free. */
+int mrp_haplotag_chunk_units(const mrp_aligned_chunk *chunk, const int32_t *gt /* 2 * n_variants; may be NULL when n_variants == 0 */,
+                             int64_t *units_out); /* host only */
+int mrp_queue_haplotag_aligned_chunks(mrp_queue *q, int64_t n_chunks, const mrp_aligned_chunk *chunks, const int32_t *const *gt,
+                                      const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                                      int64_t expansion, int64_t chunks_per_batch, int8_t *const *hap_out, double *const *h1_out,
+                                      double *const *h2_out, mrp_queue_stats *stats);
+/* create a queue, run the call above, destroy it */
+int mrp_haplotag_aligned_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,
+                                           const int32_t *const *gt, const mrp_extract_options *options, const mrp_pair_hmm *forward_model,
+                                           const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t chunks_per_batch, int8_t *const *hap_out,
+                                           double *const *h1_out, double *const *h2_out, mrp_queue_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

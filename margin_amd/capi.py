@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "mrp_kmer_alignment_anchors_many", "mrp_phase_aligned_chunks", "mrp_string_chunk_rest_from_extracted", "mrp_equal_substring_classes",
     "mrp_phase_aligned_chunks_with_filtered", "mrp_aligned_chunk_units", "mrp_queue_phase_aligned_chunks",
     "mrp_queue_phase_aligned_chunks_with_filtered", "mrp_phase_aligned_chunks_on_devices", "mrp_phase_aligned_chunks_with_filtered_on_devices",
+    "mrp_haplotag_chunk_units", "mrp_queue_haplotag_aligned_chunks", "mrp_haplotag_aligned_chunks_on_devices",
 ]
 
 
@@ -406,6 +407,11 @@ def load():
     L.mrp_haptag_sites_from_extracted.argtypes = [i64, P(ExtractedChunk), P(vp), P(HaptagSites), vp]
     L.mrp_haplotag_aligned_chunks.argtypes = [vp, i64, P(AlignedChunk), P(vp), P(ExtractOptions), P(PairHmm), P(PairHmm), i64, P(vp), P(vp), P(vp),
                                               P(HaplotagAlignedStats)]
+    ha = L.mrp_haplotag_aligned_chunks.argtypes
+    L.mrp_haplotag_chunk_units.argtypes = [P(AlignedChunk), vp, P(i64)]
+    # the one call's list with chunks_per_batch behind the expansion and the queue's stats in place of the call's
+    L.mrp_queue_haplotag_aligned_chunks.argtypes = ha[:8] + [i64] + ha[8:-1] + [P(QueueStats)]
+    L.mrp_haplotag_aligned_chunks_on_devices.argtypes = [vp, i32] + L.mrp_queue_haplotag_aligned_chunks.argtypes[1:]
     L.mrp_phase_aligned_chunks.argtypes = [vp, i64, P(AlignedChunk), P(vp), P(vp), P(ExtractOptions), P(PairHmm), P(PairHmm), i64, i64, C.c_double,
                                            P(Params), i64, P(P(PhaseResult)), P(vp), P(vp), P(ProfileOut), P(vp), P(PhaseAlignedStats)]
     L.mrp_phase_aligned_chunks_with_filtered.argtypes = [vp, i64, P(AlignedChunk), P(AlignedChunkRest), P(vp), P(vp), P(ExtractOptions), P(PairHmm),
@@ -877,6 +883,12 @@ class Queue:
         """mrp_queue_phase_aligned_chunks_with_filtered -> (phase_aligned_chunks_with_filtered's list of dicts in input order, QueueStats)"""
         return _phase_aligned(None, chunks, forward_model, reverse_model, params, rests=rests, with_rest=True, queue=self.h,
                               chunks_per_batch=chunks_per_batch, **kw)
+
+    def haplotag_aligned_chunks(self, chunks, gts, forward_model: "PairHmm", reverse_model: "PairHmm", options: Optional[dict] = None,
+                                totals: bool = True, chunks_per_batch: int = 0, **kw):
+        """mrp_queue_haplotag_aligned_chunks -> (haplotag_aligned_chunks' list of dicts in input order, QueueStats)"""
+        return _haplotag_aligned(None, chunks, gts, forward_model, reverse_model, options=options, totals=totals, queue=self.h,
+                                 chunks_per_batch=chunks_per_batch, **kw)
 
     def close(self):
         if self.h:
@@ -1726,7 +1738,27 @@ def haplotag_aligned_chunks(ctx: Optional[Context], chunks, gts, forward_model: 
     """mrp_haplotag_aligned_chunks -> (per chunk dict(hap int8 [n_reads]: 1 / 2 / 0 / -1, h1, h2 float64 (None without totals)),
     HaplotagAlignedStats).  gts: per chunk int32 [n_variants, 2] (None: NULL).  ctx / a model None pass NULL; structs as
     extract_read_substrings takes them."""
+    return _haplotag_aligned(ctx, chunks, gts, forward_model, reverse_model, options, expansion, totals, structs, null_options)
+
+
+_NO_QUEUE = object()  # (None is the NULL queue)
+LAST_HAPLOTAG_CALL_MS = 0.0  # wall time of the last C call _haplotag_aligned made, without the binding's conversions around it (tools/)
+
+
+def _haplotag_aligned(ctx, chunks, gts, forward_model, reverse_model, options=None, expansion: int = 4, totals: bool = True, structs=None,
+                      null_options: bool = False, queue=_NO_QUEUE, devices=None, chunks_per_batch: int = 0):
+    """mrp_haplotag_aligned_chunks, or with queue (a mrp_queue handle, or None for a NULL queue) or devices (a list) the work queue's
+    twins, which take chunks_per_batch and return a QueueStats"""
+    global LAST_HAPLOTAG_CALL_MS
     L = load()
+    queued = queue is not _NO_QUEUE or devices is not None
+    if devices is not None:
+        dev = (C.c_int32 * max(len(devices), 1))(*devices)
+        head, fn = (C.cast(dev, C.c_void_p), len(devices)), L.mrp_haplotag_aligned_chunks_on_devices
+    elif queued:
+        head, fn = (queue,), L.mrp_queue_haplotag_aligned_chunks
+    else:
+        head, fn = (ctx.h if ctx else None,), L.mrp_haplotag_aligned_chunks
     n = len(chunks)
     built = structs if structs is not None else [aligned_chunk_struct(c) for c in chunks]
     arr = (AlignedChunk * max(n, 1))(*[b[0] for b in built])
@@ -1737,11 +1769,32 @@ def haplotag_aligned_chunks(ctx: Optional[Context], chunks, gts, forward_model: 
     h1 = [np.full(k, np.nan) for k in nr]
     h2 = [np.full(k, np.nan) for k in nr]
     ptrs = lambda arrays: (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrays])
-    st = HaplotagAlignedStats()
+    st = QueueStats() if queued else HaplotagAlignedStats()
     by = lambda m: None if m is None else C.byref(m)
-    _check(L.mrp_haplotag_aligned_chunks(ctx.h if ctx else None, n, arr, garr, None if null_options else C.byref(opt), by(forward_model), by(reverse_model),
-                                         int(expansion), ptrs(hap), ptrs(h1) if totals else None, ptrs(h2) if totals else None, C.byref(st)))
+    per_batch = (int(chunks_per_batch),) if queued else ()
+    t_call = time.perf_counter()
+    rc = fn(*head, n, arr, garr, None if null_options else C.byref(opt), by(forward_model), by(reverse_model), int(expansion), *per_batch, ptrs(hap),
+            ptrs(h1) if totals else None, ptrs(h2) if totals else None, C.byref(st))
+    LAST_HAPLOTAG_CALL_MS = (time.perf_counter() - t_call) * 1e3
+    _check(rc)
     return [dict(hap=hap[c], h1=h1[c] if totals else None, h2=h2[c] if totals else None) for c in range(n)], st
+
+
+def haplotag_chunk_units(chunk, gt, struct=None) -> int:
+    """mrp_haplotag_chunk_units: the (read, het variant) units uniform coverage gives one chunk (a margin_amd.synth.AlignedChunk) with its
+    phased genotypes gt (int32 [n_variants, 2]; None: NULL) -- what the work queue orders and cuts haplotagging by"""
+    S = struct if struct is not None else aligned_chunk_struct(chunk)
+    g = None if gt is None else np.ascontiguousarray(gt, np.int32).reshape(-1)
+    u = C.c_int64(-1)
+    _check(load().mrp_haplotag_chunk_units(C.byref(S[0]), None if g is None or g.size == 0 else g.ctypes.data, C.byref(u)))
+    return int(u.value)
+
+
+def haplotag_aligned_chunks_on_devices(devices, chunks, gts, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm],
+                                       options: Optional[dict] = None, totals: bool = True, chunks_per_batch: int = 0, **kw):
+    """mrp_haplotag_aligned_chunks_on_devices -> (haplotag_aligned_chunks' list of dicts in input order, QueueStats)"""
+    return _haplotag_aligned(None, chunks, gts, forward_model, reverse_model, options=options, totals=totals, devices=list(devices),
+                             chunks_per_batch=chunks_per_batch, **kw)
 
 
 # ---- from alignments to haplotypes and HP tags in one call (mrp_phase_aligned_chunks) ----
@@ -1757,7 +1810,6 @@ def aligned_chunk_rest_struct(filtered_chunk, gt):
     return R, keep
 
 
-_NO_QUEUE = object()  # (None is the NULL queue)
 LAST_ALIGNED_CALL_MS = 0.0  # wall time of the last C call _phase_aligned made, without the binding's conversions around it (tools/)
 
 

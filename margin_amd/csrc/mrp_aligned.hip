@@ -438,21 +438,67 @@ int HaRun::hand_over(int8_t *const *hap_out, double *const *h1_out, double *cons
 
 }  // namespace
 
+/* ---- the call in steps (mrp_internal.h): the checks, the device steps up to the owners, the scoring and the outputs */
+struct mrp_haplotag_front {
+    const mrp_haplotag_args a;
+    HaRun R;
+    mrp_haplotag_front(const mrp_haplotag_args &args, mrp_haplotag_aligned_stats *st) : a(args), R(nullptr, args.n_chunks, args.chunks, args.gt, st) {}
+};
+
+/* every check of the call that needs no context, in the one call's order; the extraction's run it leaves holds the windows */
+int mrp_haplotag_front_create(const mrp_haplotag_args *a, mrp_haplotag_aligned_stats *stats, mrp_haplotag_front **front_out) {
+    *front_out = nullptr;
+    mrp_haplotag_front *A = new (std::nothrow) mrp_haplotag_front(*a, stats);
+    if (!A) return mrp_set_error(MRP_ERR_NOMEM, "mrp_haplotag_aligned_chunks: out of host memory");
+    const int rc = A->R.check(a->options, a->forward_model, a->reverse_model, a->expansion, a->hap_out, a->h1_out, a->h2_out);
+    if (rc != MRP_OK) {
+        delete A;
+        return rc;
+    }
+    *front_out = A;
+    return MRP_OK;
+}
+
+void mrp_haplotag_front_destroy(mrp_haplotag_front *front) { delete front; }
+
+int mrp_haplotag_chunks_check(const mrp_haplotag_args *a) {
+    mrp_haplotag_front *A = nullptr;
+    const int rc = mrp_haplotag_front_create(a, nullptr, &A);
+    mrp_haplotag_front_destroy(A);
+    return rc;
+}
+
+/* on ctx: the extraction gathering behind the allele strings, the owners of equal substrings; indices and lengths come back */
+int mrp_haplotag_front_stage(mrp_context *ctx, mrp_haplotag_front *A) {
+    HaRun &R = A->R;
+    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction and the pair-HMM have no CPU fallback)", R.who);
+    R.ctx = ctx;
+    const int rc = R.extract();
+    return rc == MRP_OK ? R.owners(nullptr) : rc;
+}
+
+/* the pair list, the pair-HMM (which raises the 2 048-cell refusal before it launches) and the scoring over a staged front, the outputs */
+int mrp_haplotag_front_run(mrp_haplotag_front *A) {
+    HaRun &R = A->R;
+    const mrp_haplotag_args &a = A->a;
+    int rc = R.pairs();
+    if (rc == MRP_OK) rc = R.score(a.forward_model, a.reverse_model, a.expansion);
+    if (rc == MRP_OK) rc = R.hand_over(a.hap_out, a.h1_out, a.h2_out);
+    return rc;
+}
+
 extern "C" int mrp_haplotag_aligned_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const int32_t *const *gt,
                                            const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
                                            int64_t expansion, int8_t *const *hap_out, double *const *h1_out, double *const *h2_out,
                                            mrp_haplotag_aligned_stats *stats) {
     const double t_begin = now_ms();
     if (stats) memset(stats, 0, sizeof(*stats));
-    HaRun R(ctx, n_chunks, chunks, gt, stats);
-    int rc = R.check(options, forward_model, reverse_model, expansion, hap_out, h1_out, h2_out);
-    if (rc != MRP_OK) return rc;
-    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction and the pair-HMM have no CPU fallback)", R.who);
-    rc = R.extract();
-    if (rc == MRP_OK) rc = R.owners(nullptr);
-    if (rc == MRP_OK) rc = R.pairs();
-    if (rc == MRP_OK) rc = R.score(forward_model, reverse_model, expansion);
-    if (rc == MRP_OK) rc = R.hand_over(hap_out, h1_out, h2_out);
+    const mrp_haplotag_args a{n_chunks, chunks, gt, options, forward_model, reverse_model, expansion, hap_out, h1_out, h2_out};
+    mrp_haplotag_front *A = nullptr;
+    int rc = mrp_haplotag_front_create(&a, stats, &A);
+    if (rc == MRP_OK) rc = mrp_haplotag_front_stage(ctx, A);
+    if (rc == MRP_OK) rc = mrp_haplotag_front_run(A);
+    mrp_haplotag_front_destroy(A);
     if (rc != MRP_OK) return rc;
     if (stats) stats->total_ms = now_ms() - t_begin;
     return MRP_OK;

@@ -656,6 +656,31 @@ int mrp_aligned_front_create(const char *who, double t_begin_ms, const mrp_align
 int mrp_aligned_front_stage(mrp_context *ctx, mrp_aligned_front *front);
 int mrp_aligned_front_run(mrp_aligned_front *front, mrp_string_chunks_stats *chunk_stats);
 void mrp_aligned_front_destroy(mrp_aligned_front *front);
+
+/* mrp_haplotag_aligned_chunks in the same steps (mrp_aligned.hip):
+ *   check    create + destroy over all chunks: every MRP_ERR_ARG of the call, then the two refused modes (host only, no context);
+ *   create   HaRun::check and the front it leaves: the extraction's run with the windows (host only; any thread);
+ *   stage    on ctx, on its thread: the extraction and the owners -- MRP_ERR_NO_DEVICE for a NULL ctx;
+ *   run      the pair list, the pair-HMM and the scoring, the outputs -- MRP_ERR_UNSUPPORTED for a diagonal beyond 2 048 cells, raised
+ *            before any pair-HMM kernel; a front is staged and run once, on one thread;
+ *   destroy  on the thread of ctx once the front was staged.
+ * The front keeps every pointer of args: the arrays live until it is destroyed.  stats (zeroed by the caller) may be NULL. */
+struct mrp_haplotag_front;
+struct mrp_haplotag_args {
+    int64_t n_chunks;
+    const mrp_aligned_chunk *chunks;
+    const int32_t *const *gt;
+    const mrp_extract_options *options;
+    const mrp_pair_hmm *forward_model, *reverse_model;
+    int64_t expansion;
+    int8_t *const *hap_out;
+    double *const *h1_out, *const *h2_out;
+};
+int mrp_haplotag_chunks_check(const mrp_haplotag_args *args);
+int mrp_haplotag_front_create(const mrp_haplotag_args *args, mrp_haplotag_aligned_stats *stats, mrp_haplotag_front **front_out);
+int mrp_haplotag_front_stage(mrp_context *ctx, mrp_haplotag_front *front);
+int mrp_haplotag_front_run(mrp_haplotag_front *front);
+void mrp_haplotag_front_destroy(mrp_haplotag_front *front);
 extern "C" void mrp_batch_last_launch_ms(struct mrp_batch *b, float *pack, float *emission, float *recursion);
 
 /* development: MRP_DUP=<letters> launches the named kernel families of a resident level TWICE (they are idempotent) -- the slow-down of a

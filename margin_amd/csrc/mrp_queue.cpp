@@ -10,6 +10,9 @@
  * worker's next batch run on a second stream while the current batch is phased; every worker has its own host thread pool.
  * The same queue takes the chunks as read and allele strings (mrp_queue_phase_string_chunks): a batch is then what one
  * mrp_phase_string_chunks call phases, and what runs beside the current batch is the host front of the next one.
+ * Aligned chunks come the same way, to be phased (mrp_queue_phase_aligned_chunks, with or without the filtered back half) or haplotagged
+ * from a phased VCF (mrp_queue_haplotag_aligned_chunks: the chunk loop of tools/tagFromPhasedVcf.c:227-309); beside a batch run the checks
+ * and windows of the next one.
  */
 #include <hip/hip_runtime.h>
 
@@ -387,6 +390,30 @@ struct QueueCall {
     }
 };
 
+/* What the bodies whose prefetch makes a host front share (string chunks, aligned chunks phased and haplotagged): a lane's two staged batches -- the one it runs and the one its
+ * prefetch makes beside it -- and the create + call + destroy of the *_on_devices forms. */
+template <typename Staged>
+struct LaneSlots {
+    Staged st[2];
+    int n_staged = 0;
+    Staged *next() { return &st[n_staged++ & 1]; } /* (the stager fills the slot the call's thread is not running) */
+    Staged *find(int64_t b) { return st[0].batch.load() == b ? &st[0] : (st[1].batch.load() == b ? &st[1] : nullptr); }
+};
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+/* the queue's own order of errors: a malformed call and a refused mode need no device; then mrp_queue_create's own error */
+template <typename Check, typename Run>
+static int checked_on_devices(const int32_t *devices, int32_t n_devices, Check check, Run run) {
+    int rc = check();
+    if (rc != MRP_OK) return rc;
+    mrp_queue *q = nullptr;
+    rc = mrp_queue_create(devices, n_devices, &q);
+    if (rc == MRP_OK) rc = run(q);
+    mrp_queue_destroy(q);
+    return rc;
+}
+
 extern "C" {
 
 int mrp_queue_phase_chunks(mrp_queue *q, int64_t n_chunks, const mrp_chunk_desc *chunks, const mrp_params *params, int64_t chunks_per_batch,
@@ -557,21 +584,15 @@ static int queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_s
         std::vector<mrp_string_chunk_rest> sr;
         mrp_string_front *front = nullptr;
     };
-    struct Lane { Staged st[2]; int n_staged = 0; };
-    std::vector<Lane> lane_state((size_t) n_workers);
-    auto staged_of = [&](int w, int64_t b) -> Staged * {
-        Lane &L = lane_state[(size_t) w];
-        return L.st[0].batch.load() == b ? &L.st[0] : (L.st[1].batch.load() == b ? &L.st[1] : nullptr);
-    };
+    std::vector<LaneSlots<Staged>> lane_state((size_t) n_workers);
+    auto staged_of = [&](int w, int64_t b) { return lane_state[(size_t) w].find(b); };
     auto drop = [&](Staged *st) { mrp_string_front_destroy(st->front); st->front = nullptr; st->batch = -1; };
-    auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     LaneHooks hk;
     hk.begin = [&](int w) { return call.lane_begin(w, false); };
     hk.prefetch = [&](int w, int64_t b) {
         const auto t0 = std::chrono::steady_clock::now();
         mrp_pool_adopt(q->pools[(size_t) (w / lanes)]);
-        Lane &L = lane_state[(size_t) w];
-        Staged *st = &L.st[L.n_staged++ & 1];
+        Staged *st = lane_state[(size_t) w].next();
         st->first = plan.batch_off[(size_t) b]; st->count = plan.batch_off[(size_t) b + 1] - st->first;
         st->sc.resize((size_t) st->count);
         for (int64_t i = 0; i < st->count; i++) st->sc[(size_t) i] = chunks[plan.order[(size_t) (st->first + i)]];
@@ -790,22 +811,16 @@ int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool wit
         std::vector<int32_t *> fr;
         mrp_aligned_front *front = nullptr;
     };
-    struct Lane { Staged st[2]; int n_staged = 0; };
-    std::vector<Lane> lane_state((size_t) n_workers);
-    auto staged_of = [&](int w, int64_t b) -> Staged * {
-        Lane &L = lane_state[(size_t) w];
-        return L.st[0].batch.load() == b ? &L.st[0] : (L.st[1].batch.load() == b ? &L.st[1] : nullptr);
-    };
+    std::vector<LaneSlots<Staged>> lane_state((size_t) n_workers);
+    auto staged_of = [&](int w, int64_t b) { return lane_state[(size_t) w].find(b); };
     /* (a staged front holds arrays of the lane's context: it goes with no other thread of the lane at work, on the lane's thread) */
     auto drop = [&](Staged *st) { mrp_aligned_front_destroy(st->front); st->front = nullptr; st->batch = -1; };
-    auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
     LaneHooks hk;
     hk.begin = [&](int w) { return call.lane_begin(w, false); };
     hk.prefetch = [&](int w, int64_t b) { /* host only: never the lane's context, its stream, its events or its pool */
         const auto t0 = std::chrono::steady_clock::now();
         mrp_pool_adopt(q->pools[(size_t) (w / lanes)]);
-        Lane &L = lane_state[(size_t) w];
-        Staged *st = &L.st[L.n_staged++ & 1];
+        Staged *st = lane_state[(size_t) w].next();
         st->first = plan.batch_off[(size_t) b]; st->count = plan.batch_off[(size_t) b + 1] - st->first;
         const size_t count = (size_t) st->count;
         st->ch.resize(count); st->names.resize(count); st->hap.resize(count);
@@ -903,13 +918,8 @@ int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool wit
 
 /* create + call + destroy, with the queue's own order of errors: a malformed call and a refused mode need no device */
 int aligned_on_devices(const int32_t *devices, int32_t n_devices, const AlignedQueueArgs &A, bool with_rest) {
-    int rc = aligned_queue_check(A, with_rest);
-    if (rc != MRP_OK) return rc;
-    mrp_queue *q = nullptr;
-    rc = mrp_queue_create(devices, n_devices, &q);
-    if (rc == MRP_OK) rc = queue_phase_aligned_chunks(q, A, with_rest, true);
-    mrp_queue_destroy(q);
-    return rc;
+    return checked_on_devices(devices, n_devices, [&] { return aligned_queue_check(A, with_rest); },
+                              [&](mrp_queue *q) { return queue_phase_aligned_chunks(q, A, with_rest, true); });
 }
 
 }  // namespace
@@ -970,6 +980,159 @@ int mrp_phase_aligned_chunks_with_filtered_on_devices(const int32_t *devices, in
                               filtered_read_out},
                              chunks_per_batch, stats};
     return aligned_on_devices(devices, n_devices, A, true);
+}
+
+}  /* extern "C" */
+
+/* ---- haplotagging aligned chunks from a phased VCF: mrp_queue_haplotag_aligned_chunks ------------------------------------------------ */
+extern "C" int mrp_haplotag_chunk_units(const mrp_aligned_chunk *chunk, const int32_t *gt, int64_t *units_out) {
+    static const char *who = "mrp_haplotag_chunk_units";
+    if (!chunk || !units_out) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    const mrp_aligned_chunk &C = *chunk;
+    if (C.n_reads < 0 || C.n_variants < 0) return mrp_set_error(MRP_ERR_ARG, "%s: negative count", who);
+    if (C.overlap_end < C.overlap_start) return mrp_set_error(MRP_ERR_ARG, "%s: overlap_end before overlap_start", who);
+    if (C.n_reads > 0 && !C.l_qseq) return mrp_set_error(MRP_ERR_ARG, "%s: null l_qseq", who);
+    if (C.n_variants > 0 && !gt) return mrp_set_error(MRP_ERR_ARG, "%s: null genotypes", who);
+    unsigned __int128 bases = 0;
+    for (int64_t r = 0; r < C.n_reads; r++) {
+        if (C.l_qseq[r] < 0) return mrp_set_error(MRP_ERR_ARG, "%s: read %lld: negative l_qseq", who, (long long) r);
+        bases += (unsigned __int128) C.l_qseq[r];
+    }
+    /* only a heterozygous variant is scored (bubbleGraph.c:1975): the chunk's pair-HMM work, not its variant count */
+    unsigned __int128 het = 0;
+    for (int64_t v = 0; v < C.n_variants; v++) het += gt[2 * v] != gt[2 * v + 1];
+    /* (B < 2^62 and H < 2^63: the product fits 128 bits) */
+    const unsigned __int128 length = (unsigned __int128) std::max<int64_t>(1, C.overlap_end - C.overlap_start);
+    const unsigned __int128 units = bases * het / length;
+    *units_out = units > (unsigned __int128) INT64_MAX ? INT64_MAX : (int64_t) units;
+    return MRP_OK;
+}
+
+namespace {
+
+struct HaplotagQueueArgs {
+    mrp_haplotag_args a;
+    int64_t chunks_per_batch;
+    mrp_queue_stats *stats;
+};
+
+int queue_haplotag_aligned_chunks(mrp_queue *q, const HaplotagQueueArgs &A, bool checked = false) {
+    static const char *who = "mrp_queue_haplotag_aligned_chunks";
+    const mrp_haplotag_args &a = A.a;
+    const int64_t n_chunks = a.n_chunks;
+    mrp_queue_stats *stats = A.stats;
+    /* every chunk's checks on the caller's thread, in the one call's order and with its messages: MRP_ERR_ARG, then the refused modes */
+    int rc = checked ? (int) MRP_OK : mrp_haplotag_chunks_check(&a);
+    if (rc != MRP_OK) return rc;
+    if (!q) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no queue (the extraction and the pair-HMM have no CPU fallback)", who);
+    const int n_devices = (int) q->devices.size();
+    if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = n_devices; }
+    if (n_chunks == 0) return MRP_OK;
+    /* tools/tagFromPhasedVcf.c:208-225 orders the chunks largest first; here by the (read, het variant) substrings uniform coverage gives */
+    std::vector<int64_t> cost((size_t) n_chunks, 0);
+    for (int64_t i = 0; i < n_chunks; i++)
+        if (mrp_haplotag_chunk_units(&a.chunks[i], a.gt[i], &cost[(size_t) i]) != MRP_OK) cost[(size_t) i] = 0;
+    const int lanes = q->lanes, n_workers = n_devices * lanes;
+    const QueuePlan plan = plan_queue(n_chunks, cost.data(), A.chunks_per_batch, n_workers, n_devices);
+    const int64_t n_batches = (int64_t) plan.batch_off.size() - 1;
+    if (stats) stats->batches = n_batches;
+    QueueCall call(q, n_batches, active_lanes_of(plan, cost.data(), n_devices, lanes));
+
+    /* a batch as one mrp_haplotag_aligned_chunks call sees it: its chunks in plan order with their genotypes and output arrays, and the
+     * front -- its host part (the extraction's records, the checks, the windows) made by the prefetch beside the lane's current batch,
+     * its device part staged on the lane's context when the batch is run */
+    struct Staged {
+        std::atomic<int64_t> batch{-1}; /* (the call's thread looks its batch up while the stager fills the lane's OTHER slot) */
+        int64_t first = 0, count = 0;
+        std::vector<mrp_aligned_chunk> ch;
+        std::vector<const int32_t *> gt;
+        std::vector<int8_t *> hap;
+        std::vector<double *> h1, h2;
+        mrp_haplotag_front *front = nullptr;
+    };
+    std::vector<LaneSlots<Staged>> lane_state((size_t) n_workers);
+    auto staged_of = [&](int w, int64_t b) { return lane_state[(size_t) w].find(b); };
+    /* (a staged front holds arrays of the lane's context: it goes with no other thread of the lane at work, on the lane's thread) */
+    auto drop = [&](Staged *st) { mrp_haplotag_front_destroy(st->front); st->front = nullptr; st->batch = -1; };
+    LaneHooks hk;
+    hk.begin = [&](int w) { return call.lane_begin(w, false); };
+    hk.prefetch = [&](int w, int64_t b) { /* host only: never the lane's context, its stream, its events or its pool */
+        const auto t0 = std::chrono::steady_clock::now();
+        mrp_pool_adopt(q->pools[(size_t) (w / lanes)]);
+        Staged *st = lane_state[(size_t) w].next();
+        st->first = plan.batch_off[(size_t) b]; st->count = plan.batch_off[(size_t) b + 1] - st->first;
+        const size_t count = (size_t) st->count;
+        st->ch.resize(count); st->gt.resize(count); st->hap.resize(count);
+        st->h1.resize(a.h1_out ? count : 0);
+        st->h2.resize(a.h2_out ? count : 0);
+        for (size_t i = 0; i < count; i++) {
+            const int64_t chunk = plan.order[(size_t) st->first + i];
+            st->ch[i] = a.chunks[chunk];
+            st->gt[i] = a.gt[chunk];
+            st->hap[i] = a.hap_out[chunk];
+            if (a.h1_out) st->h1[i] = a.h1_out[chunk];
+            if (a.h2_out) st->h2[i] = a.h2_out[chunk];
+        }
+        st->batch.store(b);
+        mrp_haplotag_args ba = a;
+        ba.n_chunks = st->count;
+        ba.chunks = st->ch.data();
+        ba.gt = st->gt.data();
+        ba.hap_out = st->hap.data();
+        ba.h1_out = a.h1_out ? st->h1.data() : nullptr;
+        ba.h2_out = a.h2_out ? st->h2.data() : nullptr;
+        const int r = mrp_haplotag_front_create(&ba, nullptr, &st->front);
+        if (r != MRP_OK) call.stage_errs[(size_t) w] = mrp_last_error();
+        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: checks and windows of batch %lld (%lld chunks) in %.1f ms\n", call.since(), w, (long long) b,
+                                 (long long) st->count, ms_since(t0));
+        return r;
+    };
+    hk.discard = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
+    hk.phase = [&](int w, int64_t b) {
+        Staged *cur = staged_of(w, b);
+        if (!cur || !cur->front) { call.errs[(size_t) w] = "work queue: batch has no front"; return (int) MRP_ERR_ARG; }
+        const auto t0 = std::chrono::steady_clock::now();
+        int r = mrp_haplotag_front_stage(q->ctx[(size_t) w], cur->front);
+        const double front_ms = ms_since(t0);
+        if (r == MRP_OK) r = mrp_haplotag_front_run(cur->front); /* (writes the batch's outputs at the chunks' own arrays) */
+        QueueCall::PerLane &me = call.per[(size_t) w];
+        if (r != MRP_OK) call.errs[(size_t) w] = mrp_last_error();
+        else {
+            for (int64_t i = 0; i < cur->count; i++) me.units += cost[(size_t) plan.order[(size_t) (cur->first + i)]];
+            me.chunks += cur->count;
+        }
+        const double all_ms = ms_since(t0);
+        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld: extraction and owners in %.1f ms, pairs and scoring in %.1f ms\n", call.since(), w,
+                                 (long long) b, front_ms, all_ms - front_ms);
+        me.busy_ms += all_ms;
+        return r;
+    };
+    hk.retire = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
+    hk.end = [&](int w) { call.lane_end(w); };
+    rc = call.run(hk);
+    call.fill(stats);
+    return rc != MRP_OK ? call.error(rc) : (int) MRP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrp_queue_haplotag_aligned_chunks(mrp_queue *q, int64_t n_chunks, const mrp_aligned_chunk *chunks, const int32_t *const *gt,
+                                      const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                                      int64_t expansion, int64_t chunks_per_batch, int8_t *const *hap_out, double *const *h1_out,
+                                      double *const *h2_out, mrp_queue_stats *stats) {
+    const HaplotagQueueArgs A{{n_chunks, chunks, gt, options, forward_model, reverse_model, expansion, hap_out, h1_out, h2_out}, chunks_per_batch, stats};
+    return queue_haplotag_aligned_chunks(q, A);
+}
+
+int mrp_haplotag_aligned_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,
+                                           const int32_t *const *gt, const mrp_extract_options *options, const mrp_pair_hmm *forward_model,
+                                           const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t chunks_per_batch, int8_t *const *hap_out,
+                                           double *const *h1_out, double *const *h2_out, mrp_queue_stats *stats) {
+    const HaplotagQueueArgs A{{n_chunks, chunks, gt, options, forward_model, reverse_model, expansion, hap_out, h1_out, h2_out}, chunks_per_batch, stats};
+    return checked_on_devices(devices, n_devices, [&] { return mrp_haplotag_chunks_check(&A.a); },
+                              [&](mrp_queue *q) { return queue_haplotag_aligned_chunks(q, A, true); });
 }
 
 }  /* extern "C" */

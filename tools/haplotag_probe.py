@@ -9,9 +9,15 @@ both gave the same tags and totals bit for bit.  Prints one JSON line and writes
     python tools/haplotag_probe.py [--chunks 96] [--distinct 4] [--reps 5] [--cache FILE] [--out profiles/haplotag/probe.json]
 
 --cache keeps the generated chunks (pickle) so that a later run skips their generation.
+
+--queue N: the work queue over the same chunks beside the ONE call.  Leg (a) is mrp_haplotag_aligned_chunks on one context; leg (b) is
+mrp_queue_haplotag_aligned_chunks on a queue over device 0 with N chunks per batch.  One process, a warm-up of both legs, the median of
+--reps with min and max, the wall time of the C call alone; one digest over every output per leg, which must be equal.  Writes
+profiles/haplotag/queue.json (or --out).  MRP_TIMING=1 prints the lanes' lines.
 """
 import argparse
 import ctypes as C
+import hashlib
 import json
 import os
 import pickle
@@ -33,8 +39,10 @@ def main():
     ap.add_argument("--distinct", type=int, default=4)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--cache", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "haplotag", "probe.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--queue", type=int, default=None, metavar="N")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "haplotag", "probe.json" if a.queue is None else "queue.json")
     opts = capi.shipped_extract_options()
     if a.cache and os.path.exists(a.cache):
         with open(a.cache, "rb") as f:
@@ -52,6 +60,8 @@ def main():
     chunks = [distinct[i % a.distinct] for i in range(a.chunks)]
     gts = [dgt[i % a.distinct] for i in range(a.chunks)]
     built = [capi.aligned_chunk_struct(c) for c in chunks]
+    if a.queue is not None:
+        return queue_legs(a, chunks, gts, built, opts)
     n = len(chunks)
     n_reads = sum(len(c.read_pos) for c in chunks)
     strand = np.ascontiguousarray(np.concatenate([c.read_forward_strand for c in chunks]), np.uint8)
@@ -128,6 +138,54 @@ def main():
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write(line + "\n")
+
+
+def queue_legs(a, chunks, gts, built, opts):
+    fwd = capi.PairHmm.from_margin_hmm(*synth.margin_phase_pair_hmm_arrays())
+    rev = fwd.reverse_complement()
+    units = [capi.haplotag_chunk_units(c, g, struct=b) for c, g, b in zip(chunks, gts, built)]
+
+    def digest(got):
+        h = hashlib.sha256()
+        for g in got:
+            for k in ("hap", "h1", "h2"):
+                h.update(np.ascontiguousarray(g[k]).tobytes())
+        return h.hexdigest()
+
+    def one_call(ctx):
+        got, _ = capi.haplotag_aligned_chunks(ctx, chunks, gts, fwd, rev, opts, structs=built)
+        return digest(got), capi.LAST_HAPLOTAG_CALL_MS
+
+    def queued(q):
+        got, st = q.haplotag_aligned_chunks(chunks, gts, fwd, rev, opts, chunks_per_batch=a.queue, structs=built)
+        return digest(got), capi.LAST_HAPLOTAG_CALL_MS, st
+
+    legs, digests = {"one_call": [], f"queue_{a.queue}": []}, {"one_call": set(), f"queue_{a.queue}": set()}
+    q = capi.Queue([0])
+    try:
+        with capi.Context(0) as ctx:
+            one_call(ctx)  # warm-up of both legs: module load, the contexts' pools, the lanes' contexts
+            queued(q)
+            for _ in range(a.reps):
+                d, w = one_call(ctx)
+                legs["one_call"].append(w)
+                digests["one_call"].add(d)
+                d, w, st = queued(q)
+                legs[f"queue_{a.queue}"].append(w)
+                digests[f"queue_{a.queue}"].add(d)
+    finally:
+        q.close()
+    same = all(len(v) == 1 for v in digests.values()) and len(set.union(*digests.values())) == 1
+    res = dict(chunks=a.chunks, distinct=a.distinct, reps=a.reps, chunks_per_batch=a.queue, lanes=int(os.environ.get("MRP_QUEUE_LANES", 4)),
+               units_total=int(sum(units)), walls_ms={k: dict(median=round(float(np.median(v)), 2), min=round(min(v), 2), max=round(max(v), 2)) for k, v in legs.items()},
+               queue=dict(batches=int(st.batches), busy_ms=round(float(st.busy_ms_per_device[0]), 2), fallback_chunks=int(st.fallback_chunks),
+                          units=int(st.units_per_device[0])),
+               digest=sorted(digests["one_call"])[0], identical=bool(same))
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(json.dumps(res, indent=1) + "\n")
 
 
 if __name__ == "__main__":
