@@ -88,7 +88,9 @@ int mrp_context_set_phase_groups(mrp_context *ctx, int groups);
  * a resident call must survive by redoing itself in two halves.  Bit 3: the prune kernel's general chain (one entry per cell) instead
  * of the chain on complement pairs that includeInvertedPartitions with even column limits selects, for A/B parity.  Bit 4: one
  * array entry per cell on unit levels (the chain on complement pairs over per-cell arrays) instead of one per complement pair.
- * Bit 5: no merge level is launched deferred -- every launch waits for its totals, as the large levels' do. */
+ * Bit 5: no merge level is launched deferred -- every launch waits for its totals, as the large levels' do.  Bit 6: the grid of
+ * the pair-per-workgroup pair-HMM kernel (mrp_context_set_wide_pairs) is one workgroup, so consecutive wide pairs of a call reuse
+ * one workspace slice. */
 int mrp_context_set_test_hooks(mrp_context *ctx, int hooks);
 /* size of the host worker pool (structure of the merge levels, descriptors, classification of alignment pairs): the
  * process-wide pool of contexts used directly, and EACH worker's own pool of a work queue (mrp_queue_*: one pool per device).
@@ -363,6 +365,13 @@ typedef struct mrp_queue_stats {
 typedef struct mrp_queue mrp_queue; /* the workers' contexts (device allocator caches, staging), kept from call to call */
 int mrp_queue_create(const int32_t *devices, int32_t n_devices, mrp_queue **out);
 void mrp_queue_destroy(mrp_queue *q);
+/* mrp_context_set_wide_pairs (below, with the pair-HMM entries) for every lane's context, present and future, and for the queue's
+ * up-front checks: with it on, the string queues no longer refuse a pair beyond 2 048 cells up front and the aligned and haplotag
+ * queues no longer meet that refusal as a lane error, up to MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS.  Between calls of the queue
+ * only.  The *_on_devices forms make a queue of their own with the setting off: a caller who wants wide pairs makes a queue. */
+int mrp_queue_set_wide_pairs(mrp_queue *q, int on);
+/* mrp_context_wide_pair_count summed over the lanes' contexts (either pointer may be NULL) */
+int mrp_queue_wide_pair_count(mrp_queue *q, int64_t *pairs_out, int64_t *cells_out);
 int mrp_queue_phase_chunks(mrp_queue *q, int64_t n_chunks, const mrp_chunk_desc *chunks, const mrp_params *params, int64_t chunks_per_batch,
                            mrp_phase_result **out, mrp_queue_stats *stats);
 /* create + phase + destroy */
@@ -440,7 +449,8 @@ double mrp_binomial_coefficient(int64_t n, int64_t k, uint64_t *hi, uint64_t *lo
 /* ---------------------------------------------------------------------------------------------------------------
  * Read x allele alignment likelihoods: the banded pair-HMM forward probability that fills
  * Bubble.alleleReadSupports (bubbleGraph.c:1421-1464 -> computeForwardProbability, pairwiseAligner.c:849-903).
- * Device work: one kernel with a pair per lane for short x strings, one with a pair per wave for everything else.
+ * Device work: one kernel with a pair per lane for short x strings, one with a pair per wave for everything else up to a
+ * diagonal of 2 048 cells, and -- once wide pairs are on for the context (below) -- one with a pair per workgroup beyond that.
  * The arithmetic is the reference's: fp64 + and * only (logAdd is a cubic interpolation, pairwiseAligner.c:279-299),
  * evaluated without fused multiply-add, so results are bit-identical to a strict IEEE build of the reference.
  * Symbols: 0..3 = A C G T, >= 4 = N (convertNucleotideCharToSymbol, stateMachine.c:25-42).  Nucleotide emissions
@@ -454,7 +464,9 @@ typedef struct mrp_pair_hmm { /* struct _StateMachine3 (stateMachine.c:507-519) 
 } mrp_pair_hmm;
 
 typedef struct mrp_pairhmm_stats {
-    int64_t pairs_lane, pairs_wave; /* pairs handled by the pair-per-lane / pair-per-wave kernel */
+    int64_t pairs_lane, pairs_wave; /* pairs handled by the pair-per-lane / pair-per-wave kernel; with wide pairs on (below) pairs_wave
+                                     * counts the pairs of the pair-per-workgroup kernel too, so pairs_lane + pairs_wave stays the number
+                                     * of pairs scored (their own count: mrp_context_wide_pair_count) */
     int64_t cells;                  /* dp cells inside the bands, (0,0) included */
     double kernel_ms;               /* HIP events around the launches */
     double total_ms;                /* host wall time of the call */
@@ -468,6 +480,30 @@ void mrp_pair_hmm_reverse_complement(mrp_pair_hmm *m);
  * sequence coordinates, strictly increasing in both.  MRP_ERR_ARG where the reference asserts / throws. */
 int mrp_band_diagonals(const int64_t *anchors, int64_t n_anchors, int64_t lx, int64_t ly, int64_t expansion, int32_t *xmy_l,
                        int32_t *xmy_r);
+/* Wide pairs.  The pair-per-wave kernel keeps three diagonals in LDS, so every entry below that scores pairs refuses a pair whose
+ * widest diagonal holds more than 2 048 cells (MRP_ERR_UNSUPPORTED).  The reference has no such limit (computeForwardProbability
+ * walks whatever band it is given), and the shipped parameters reach it: referenceExpansionForStructuralVariants = 512 on each
+ * side of a 1 kb SV allele gives strings beyond 2 048 symbols, and the loops over filtered reads are never anchored.  With wide
+ * pairs ON for the context such a pair is aligned by a third kernel, a pair per WORKGROUP with its diagonals in a device
+ * workspace, bit-identical to the other two; pairs of up to 2 048 cells keep their kernel.  Two refusals remain
+ * (MRP_ERR_UNSUPPORTED, raised before anything is launched; the message names the limit), because one launch on a shared card
+ * must stay bounded: */
+#define MRP_WIDE_MAX_WIDTH 32768                /* cells on a pair's widest diagonal: 2.25 MB of workspace per workgroup */
+#define MRP_WIDE_MAX_CELLS ((int64_t) 1 << 31)  /* dp cells inside one pair's band: 5 s of one workgroup at the measured 4.3e8 cells/s */
+/* off (default): a pair whose widest diagonal exceeds 2 048 cells is refused, as documented at every entry.
+ * on: such a pair is aligned by the pair-per-workgroup kernel, up to MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS.
+ * Honoured by every entry that takes the context and scores pairs: mrp_forward_probabilities, mrp_allele_read_supports,
+ * mrp_partition_reads_by_haplotype, mrp_phase_variants_from_tagged_reads, mrp_phase_string_chunks(_with_filtered),
+ * mrp_haplotag_aligned_chunks, mrp_phase_aligned_chunks(_with_filtered). */
+int mrp_context_set_wide_pairs(mrp_context *ctx, int on);
+/* pairs / dp cells the wide kernel has taken on this context since it was created (either pointer may be NULL) */
+int mrp_context_wide_pair_count(mrp_context *ctx, int64_t *pairs_out, int64_t *cells_out);
+/* host only, no device: the widest diagonal and the cells of one pair's band, i.e. what decides its kernel (the band of
+ * mrp_band_diagonals; min(lx, ly) + 1 and (lx + 1)(ly + 1) without anchors).  Either output may be NULL.  MRP_ERR_ARG as
+ * mrp_band_diagonals.  A caller pre-checks a batch with it: width <= 2 048 always runs, width <= MRP_WIDE_MAX_WIDTH and cells <=
+ * MRP_WIDE_MAX_CELLS runs with wide pairs on. */
+int mrp_pair_diagonal_width(const int64_t *anchors, int64_t n_anchors, int64_t lx, int64_t ly, int64_t expansion,
+                            int32_t *width_out, int64_t *cells_out);
 /* getKmerAlignmentAnchors (pairwiseAligner.c:1519-1627, KMER_SIZE = 20): the chain of shared 20-mers the reference anchors
  * long (structural variant) alleles with; out receives at most ly - 19 (x, y) pairs, the count is returned (host only) */
 int64_t mrp_kmer_alignment_anchors(const uint8_t *x, int64_t lx, const uint8_t *y, int64_t ly, int64_t *out);
@@ -496,7 +532,8 @@ int mrp_equal_substring_classes(mrp_context *ctx, int64_t n_sites, const int64_t
  * selects models[i] per pair; anchor_off (NULL: no anchors anywhere) holds n_pairs + 1 offsets into anchors (pairs of
  * int64).  A pair without anchors covers its whole matrix, as in the reference.  out[i] = log probability (0.0 for two
  * empty strings, :860-862).  Limits: a diagonal of at most 2 048 cells for pairs that go to the pair-per-wave kernel
- * (x longer than 100 symbols, or anchored); beyond that MRP_ERR_UNSUPPORTED.  stats may be NULL. */
+ * (x longer than 100 symbols, or anchored); beyond that MRP_ERR_UNSUPPORTED -- unless wide pairs are on for the context, mrp_context_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS.
+ * stats may be NULL. */
 int mrp_forward_probabilities(mrp_context *ctx, const mrp_pair_hmm *models, int32_t n_models, int64_t n_pairs, const uint8_t *pool,
                               int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len, const int64_t *y_off,
                               const int32_t *y_len, const uint8_t *model_index, const int64_t *anchor_off, const int64_t *anchors,
@@ -543,7 +580,7 @@ typedef struct mrp_haptag_sites {
  * machine for every duplicate.  Supports are rounded to float (:1869); per read, in site order, in fp64:
  * h1 += s1 - logAddExact(s1, s2), h2 += s2 - logAddExact(s2, s1) (:1879-1888).  Out per read: hap = 1 (h1 > h2), 2
  * (h2 > h1) or 0 (unclassified, :1913-1925), h1, h2.  A pair whose widest diagonal exceeds 2 048 cells is refused
- * (MRP_ERR_UNSUPPORTED, as mrp_forward_probabilities) before anything is launched.  stats may be NULL; kernel_ms covers
+ * (MRP_ERR_UNSUPPORTED, as mrp_forward_probabilities) before anything is launched (unless wide pairs are on for the context, mrp_context_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS).  stats may be NULL; kernel_ms covers
  * the pair-HMM and the scoring kernels. */
 int mrp_partition_reads_by_haplotype(mrp_context *ctx, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
                                      const mrp_haptag_sites *sites, int64_t n_reads, const uint8_t *read_forward_strand,
@@ -616,7 +653,7 @@ typedef struct mrp_string_chunks_stats {
  * that reads1 / reads2 name the CALLER's reads (through read_of_seq); hap_out[c][r] (n_reads entries per chunk) = 1 / 2,
  * 0 below min_phred, -1 for a read not in the fragment or in no bubble; phred_out (optional) the score of
  * genomeFragment.c:260, 0 for -1 reads; profiles_out (optional) as above.  A pair whose diagonal exceeds 2 048 cells gives
- * MRP_ERR_UNSUPPORTED before anything is launched; parameters outside the resident range take mrp_phase_reads_many's
+ * MRP_ERR_UNSUPPORTED before anything is launched (unless wide pairs are on for the context, mrp_context_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS); parameters outside the resident range take mrp_phase_reads_many's
  * per-chunk path (stats->phase.resident = 0).  Arguments are checked before the context: MRP_ERR_ARG, then
  * MRP_ERR_NO_DEVICE for a NULL context.  On an error nothing is returned in out / profiles_out. */
 int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model,
@@ -636,7 +673,7 @@ int mrp_phase_string_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_string
  *   Results: out[c], hap_out[c], phred_out[c], profiles_out[c] are, at the chunk's own position, bit for bit what one
  * mrp_phase_string_chunks call over all chunks returns, whatever the batch size, the lanes, the devices or the hand-out.
  *   Errors: every chunk is checked on the caller's thread before a lane starts, in that call's order -- MRP_ERR_ARG, then
- * MRP_ERR_NO_DEVICE for a NULL queue, then MRP_ERR_UNSUPPORTED for a pair of ANY chunk whose diagonal exceeds 2 048 cells.
+ * MRP_ERR_NO_DEVICE for a NULL queue, then MRP_ERR_UNSUPPORTED for a pair of ANY chunk whose diagonal exceeds 2 048 cells (unless wide pairs are on for the queue, mrp_queue_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS).
  * An error inside a lane (HIP, out of memory) stops the queue as in mrp_queue_phase_chunks: the remaining batches are
  * dropped, the workers joined, every result already made destroyed, out[] / profiles_out[] left NULL / zeroed, the first
  * error returned (mrp_last_error); the queue stays usable.
@@ -647,7 +684,8 @@ int mrp_queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_stri
                                   const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
                                   const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out,
                                   double *const *phred_out, mrp_profile_out *profiles_out, mrp_queue_stats *stats);
-/* create a queue, run the call above, destroy it: the string twin of mrp_phase_chunks_on_devices */
+/* create a queue, run the call above, destroy it: the string twin of mrp_phase_chunks_on_devices (a queue of its own, wide pairs off:
+ * the 2 048-cell refusal stays; a caller who wants wide pairs makes a queue) */
 int mrp_phase_string_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_string_chunk *chunks,
                                        const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
                                        double het_substitution_probability, const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch,
@@ -715,7 +753,7 @@ typedef struct mrp_string_filtered_stats {
  * Checks in the existing order: MRP_ERR_ARG (the rest's included: NULL arrays, offsets not ascending, a read index out of range,
  * a filtered read twice in a bubble or not ascending, gt naming an allele the variant lacks) before the context, then
  * MRP_ERR_NO_DEVICE, then MRP_ERR_UNSUPPORTED for a pair -- the back half's included: with a rest every substring of a bubble
- * may be aligned unanchored -- beyond the 2 048-cell diagonal.  On an error filtered_out is left zeroed.  stats may be NULL. */
+ * may be aligned unanchored -- beyond the 2 048-cell diagonal (unless wide pairs are on for the context, mrp_context_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS).  On an error filtered_out is left zeroed.  stats may be NULL. */
 int mrp_phase_string_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest,
                                           const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
                                           double het_substitution_probability, const mrp_params *params, int64_t min_phred, mrp_phase_result **out,
@@ -897,7 +935,7 @@ typedef struct mrp_haplotag_aligned_stats {
  * a NULL gt[c] for a chunk with variants, a genotype outside the variant's alleles, an odd or negative expansion) before the
  * context is looked at; MRP_ERR_UNSUPPORTED for the SV split mode or run-length encoding, as the extraction reports them:
  * without a context too; MRP_ERR_NO_DEVICE for a NULL context; MRP_ERR_UNSUPPORTED for a pair whose widest diagonal exceeds
- * 2 048 cells, known once the extraction's device half has given the lengths and raised before any pair-HMM kernel is launched.
+ * 2 048 cells, known once the extraction's device half has given the lengths and raised before any pair-HMM kernel is launched (unless wide pairs are on for the context, mrp_context_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS).
  * stats may be NULL. */
 int mrp_haplotag_aligned_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const int32_t *const *gt,
                                 const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
@@ -941,7 +979,7 @@ typedef struct mrp_phase_aligned_stats {
  * Errors, in this order: MRP_ERR_ARG before the context is looked at (the extraction's checks; NULL models, params, out, hap_out,
  * hap_out[c] / phred_out[c] / read_names[c] / a read name for a chunk with reads; an odd or negative expansion);
  * MRP_ERR_UNSUPPORTED for the SV split mode or run-length encoding, without a context too; MRP_ERR_NO_DEVICE for a NULL context;
- * MRP_ERR_UNSUPPORTED for a pair whose widest diagonal exceeds 2 048 cells, raised before any pair-HMM kernel is launched (and
+ * MRP_ERR_UNSUPPORTED for a pair whose widest diagonal exceeds 2 048 cells, raised before any pair-HMM kernel is launched (unless wide pairs are on for the context, mrp_context_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS) (and
  * MRP_ERR_ARG there for a bubble of more than 65 535 alleles, as the string call).  On an error nothing is returned.  Parameters
  * outside the resident range take the per-chunk path as in the string call (stats->chunks.phase.resident = 0).  stats may be NULL. */
 int mrp_phase_aligned_chunks(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const char *const *const *read_names,
@@ -994,7 +1032,7 @@ typedef struct mrp_phase_aligned_filtered_stats {
  * not ascending or outside the overlap among them; in their messages chunk n_chunks + c is the rest of chunk c --, mrp_phase_aligned_chunks'
  * own, a NULL rest / filtered_out / filtered_read_out, a gt outside the variant's alleles); MRP_ERR_UNSUPPORTED for the SV split mode or
  * run-length encoding, without a context too; MRP_ERR_NO_DEVICE; MRP_ERR_UNSUPPORTED for a pair whose widest diagonal exceeds 2 048
- * cells (with a rest every substring of a bubble may be aligned unanchored, as mrp_phase_string_chunks_with_filtered states).  On an
+ * cells (with a rest every substring of a bubble may be aligned unanchored, as mrp_phase_string_chunks_with_filtered states) (unless wide pairs are on for the context, mrp_context_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS).  On an
  * error nothing is returned and filtered_out is zeroed.  stats may be NULL. */
 int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
                                            const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
@@ -1023,7 +1061,7 @@ int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, c
  * rest of chunk c is "chunk n_chunks + c" in the extraction's) -- every MRP_ERR_ARG, then MRP_ERR_UNSUPPORTED for the two refused
  * extraction modes, both without a device or a queue; then MRP_ERR_NO_DEVICE for a NULL queue (n_chunks == 0 included).  Up to here
  * nothing is written, stats included.  The 2 048-cell diagonal refusal cannot be raised up front -- the lengths exist only after a
- * batch's extraction: it arrives as a lane error, like an out-of-memory or a HIP error.  On a lane error the queue stops: remaining
+ * batch's extraction: it arrives as a lane error, like an out-of-memory or a HIP error (unless wide pairs are on for the queue, mrp_queue_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS).  The *_on_devices forms make their own queue and keep the 2 048-cell refusal.  On a lane error the queue stops: remaining
  * batches are dropped, prefetched ones discarded, the workers joined, every result already made destroyed (bubble_variant_out[c] and
  * filtered_read_out[c] freed), out[] / bubble_variant_out[] / filtered_read_out[] left NULL, profiles_out[] / filtered_out[] zeroed,
  * the first error returned (mrp_last_error); the queue stays usable.  n_chunks == 0 returns MRP_OK with zeroed stats. */
@@ -1081,7 +1119,7 @@ int mrp_phase_aligned_chunks_with_filtered_on_devices(const int32_t *devices, in
  * device; then MRP_ERR_NO_DEVICE for a NULL queue (n_chunks == 0 included).  Up to here nothing is written, stats included.  The
  * *_on_devices form runs these checks, then mrp_queue_create reports its own error (a device that does not exist: MRP_ERR_ARG), then
  * the call runs and the queue is destroyed.  The 2 048-cell diagonal refusal is known only after a batch's extraction: it is raised
- * inside a lane, before any pair-HMM kernel of that batch, and arrives as a lane error, like an out-of-memory or a HIP error.  On a
+ * inside a lane, before any pair-HMM kernel of that batch, and arrives as a lane error, like an out-of-memory or a HIP error (unless wide pairs are on for the queue, mrp_queue_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS); the *_on_devices form makes its own queue and keeps the 2 048-cell refusal.  On a
  * lane error the queue stops: remaining batches are dropped, prefetched ones discarded, the workers joined, the first error returned
  * (mrp_last_error); the queue stays usable.  hap_out[c], h1_out[c] and h2_out[c] are then UNSPECIFIED for every chunk: batches that
  * had finished have written theirs, the others not.  The call allocates nothing the caller has to free. */

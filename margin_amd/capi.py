@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MRP_LIB_OVERRIDE") or os.path.join(_HERE, "lib", "lib
 
 MRP_OK = 0
 MRP_ERR_ARG, MRP_ERR_NO_DEVICE, MRP_ERR_HIP, MRP_ERR_NOMEM, MRP_ERR_UNSUPPORTED, MRP_ERR_LOOKUP = 1, 2, 3, 4, 5, 6
+WIDE_MAX_WIDTH, WIDE_MAX_CELLS = 32768, 1 << 31  # MRP_WIDE_MAX_WIDTH, MRP_WIDE_MAX_CELLS
 FLAG_MAX_NOT_SUM = 1
 FLAG_INCLUDE_ANCESTOR_SUB_PROB = 2
 
@@ -43,6 +44,7 @@ EXPORTED_SYMBOLS = [
     "mrp_phase_aligned_chunks_with_filtered", "mrp_aligned_chunk_units", "mrp_queue_phase_aligned_chunks",
     "mrp_queue_phase_aligned_chunks_with_filtered", "mrp_phase_aligned_chunks_on_devices", "mrp_phase_aligned_chunks_with_filtered_on_devices",
     "mrp_haplotag_chunk_units", "mrp_queue_haplotag_aligned_chunks", "mrp_haplotag_aligned_chunks_on_devices",
+    "mrp_context_set_wide_pairs", "mrp_context_wide_pair_count", "mrp_queue_set_wide_pairs", "mrp_queue_wide_pair_count", "mrp_pair_diagonal_width",
 ]
 
 
@@ -387,6 +389,11 @@ def load():
     L.mrp_pair_hmm_reverse_complement.argtypes = [P(PairHmm)]
     L.mrp_pair_hmm_reverse_complement.restype = None
     L.mrp_band_diagonals.argtypes = [vp, i64, i64, i64, i64, vp, vp]
+    L.mrp_pair_diagonal_width.argtypes = [vp, i64, i64, i64, i64, P(i32), P(i64)]
+    L.mrp_context_set_wide_pairs.argtypes = [vp, C.c_int]
+    L.mrp_context_wide_pair_count.argtypes = [vp, P(i64), P(i64)]
+    L.mrp_queue_set_wide_pairs.argtypes = [vp, C.c_int]
+    L.mrp_queue_wide_pair_count.argtypes = [vp, P(i64), P(i64)]
     L.mrp_forward_probabilities.argtypes = [vp, vp, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, P(PairHmmStats)]
     L.mrp_allele_read_supports.argtypes = [vp, P(PairHmm), P(PairHmm), i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, P(PairHmmStats)]
     L.mrp_partition_reads_by_haplotype.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, i64, vp, vp, vp, P(PairHmmStats)]
@@ -464,8 +471,19 @@ class Context:
 
     def set_test_hooks(self, hooks: int):
         """test suite only: bit 0 fault injection, bit 1 separate cross product / emission kernels, bit 2 one refused device
-        allocation, bit 3 general prune chain, bit 4 one array entry per cell on unit levels, bit 5 no level is launched deferred (include/margin_rphmm.h)"""
+        allocation, bit 3 general prune chain, bit 4 one array entry per cell on unit levels, bit 5 no level is launched deferred, bit 6 the
+        wide pair-HMM kernel's grid is one workgroup (include/margin_rphmm.h)"""
         _check(load().mrp_context_set_test_hooks(self.h, hooks))
+
+    def set_wide_pairs(self, on):
+        """mrp_context_set_wide_pairs: pairs whose widest diagonal exceeds 2 048 cells are aligned, not refused (up to WIDE_MAX_WIDTH / WIDE_MAX_CELLS)"""
+        _check(load().mrp_context_set_wide_pairs(self.h, int(bool(on))))
+
+    def wide_pair_count(self):
+        """mrp_context_wide_pair_count -> (pairs, dp cells) the wide kernel has taken on this context"""
+        pairs, cells = C.c_int64(), C.c_int64()
+        _check(load().mrp_context_wide_pair_count(self.h, C.byref(pairs), C.byref(cells)))
+        return pairs.value, cells.value
 
     def close(self):
         if self.h:
@@ -890,6 +908,16 @@ class Queue:
         return _haplotag_aligned(None, chunks, gts, forward_model, reverse_model, options=options, totals=totals, queue=self.h,
                                  chunks_per_batch=chunks_per_batch, **kw)
 
+    def set_wide_pairs(self, on):
+        """mrp_queue_set_wide_pairs: Context.set_wide_pairs for every lane's context and the queue's up-front checks"""
+        _check(load().mrp_queue_set_wide_pairs(self.h, int(bool(on))))
+
+    def wide_pair_count(self):
+        """mrp_queue_wide_pair_count -> (pairs, dp cells), summed over the lanes"""
+        pairs, cells = C.c_int64(), C.c_int64()
+        _check(load().mrp_queue_wide_pair_count(self.h, C.byref(pairs), C.byref(cells)))
+        return pairs.value, cells.value
+
     def close(self):
         if self.h:
             load().mrp_queue_destroy(self.h)
@@ -1053,6 +1081,14 @@ def band_diagonals(anchors, lx: int, ly: int, expansion: int):
     lo, hi = np.zeros(lx + ly + 1, dtype=np.int32), np.zeros(lx + ly + 1, dtype=np.int32)
     _check(load().mrp_band_diagonals(a.ctypes.data if len(a) else None, len(a), lx, ly, expansion, lo.ctypes.data, hi.ctypes.data))
     return lo, hi
+
+
+def pair_diagonal_width(anchors, lx: int, ly: int, expansion: int):
+    """mrp_pair_diagonal_width (host only) -> (cells on the widest diagonal, dp cells inside the band): what decides a pair's kernel"""
+    a = np.ascontiguousarray(np.asarray(anchors if anchors is not None else [], dtype=np.int64).reshape(-1, 2))
+    width, cells = C.c_int32(), C.c_int64()
+    _check(load().mrp_pair_diagonal_width(a.ctypes.data if len(a) else None, len(a), lx, ly, expansion, C.byref(width), C.byref(cells)))
+    return width.value, cells.value
 
 
 def _opt(a, dtype):

@@ -385,7 +385,7 @@ int HaRun::score(const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_
     mrp_pairhmm_stats *pst = stats ? &stats->pairhmm : nullptr;
     const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
     if (P.list.size() > 0) { /* (MRP_ERR_UNSUPPORTED for a diagonal beyond the limit is raised by phm_classify, before anything is launched) */
-        int rc = phm_classify(who, models, 2, pool_bytes, P.list.view(), expansion, 0, 0, H);
+        int rc = phm_classify(who, models, 2, pool_bytes, P.list.view(), expansion, 0, 0, ctx->wide_pairs, H);
         if (rc == MRP_OK) rc = phm_enqueue(ctx, nullptr, pool_bytes, P.list.size(), H, L, pst, d_sym.p);
         if (rc != MRP_OK) return rc;
     } else {
@@ -683,11 +683,12 @@ int PaRun::anchors() {
     return MRP_OK;
 }
 
-/* the launch classes and the bands; raises the 2 048-cell refusal, before any pair-HMM kernel */
+/* the launch classes and the bands; raises the 2 048-cell refusal (wide pairs on for the context: the wide kernel's caps), before any
+ * pair-HMM kernel */
 int PaRun::classify(const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion) {
     if (F.n_pairs == 0) return MRP_OK;
     const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
-    return phm_classify(who, models, 2, pool_bytes, F.scratch.pairs.view(), expansion, 0, 0, F.L);
+    return phm_classify(who, models, 2, pool_bytes, F.scratch.pairs.view(), expansion, 0, 0, ctx->wide_pairs, F.L);
 }
 
 /* after the string run has handed its results over: the bubbles' variants, the stats, the device arrays back to the pool */

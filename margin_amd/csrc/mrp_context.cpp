@@ -160,7 +160,7 @@ int mrp_context_set_phase_groups(mrp_context *ctx, int groups) {
 }
 int mrp_context_phase_groups(const mrp_context *ctx) { return ctx->phase_groups; }
 int mrp_context_set_test_hooks(mrp_context *ctx, int hooks) {
-    if (!ctx || hooks < 0 || hooks > 63) return mrp_set_error(MRP_ERR_ARG, "mrp_context_set_test_hooks: bad arguments");
+    if (!ctx || hooks < 0 || hooks > 127) return mrp_set_error(MRP_ERR_ARG, "mrp_context_set_test_hooks: bad arguments");
     if ((hooks & 4) && ctx->pool.device >= 0) DevPoolRegistry::get().inject_oom[ctx->pool.device].store(1);
     hooks &= ~4;
     ctx->test_hooks = hooks;
@@ -168,5 +168,16 @@ int mrp_context_set_test_hooks(mrp_context *ctx, int hooks) {
     return MRP_OK;
 }
 int mrp_context_test_hooks(const mrp_context *ctx) { return ctx->test_hooks; }
+int mrp_context_set_wide_pairs(mrp_context *ctx, int on) {
+    if (!ctx) return mrp_set_error(MRP_ERR_ARG, "mrp_context_set_wide_pairs: context is NULL");
+    ctx->wide_pairs = on != 0;
+    return MRP_OK;
+}
+int mrp_context_wide_pair_count(mrp_context *ctx, int64_t *pairs_out, int64_t *cells_out) {
+    if (!ctx) return mrp_set_error(MRP_ERR_ARG, "mrp_context_wide_pair_count: context is NULL");
+    if (pairs_out) *pairs_out = ctx->wide_pair_count;
+    if (cells_out) *cells_out = ctx->wide_cell_count;
+    return MRP_OK;
+}
 
 }  /* extern "C" */

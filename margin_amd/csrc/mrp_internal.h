@@ -367,6 +367,8 @@ struct mrp_context {
     }
     DevPool pool;
     int test_hooks = 0;   /* mrp_context_set_test_hooks (test suite only) */
+    int wide_pairs = 0;   /* mrp_context_set_wide_pairs: pairs beyond the pair-per-wave kernel's 2 048 cells go to the pair-per-workgroup kernel */
+    int64_t wide_pair_count = 0, wide_cell_count = 0; /* what that kernel has taken on this context (mrp_context_wide_pair_count) */
     int phase_groups = 0; /* concurrent batches of mrp_phase_reads_many (mrp_context_set_phase_groups); 0: chosen by batch size */
     std::vector<mrp_context *> siblings; /* further contexts on the same device (concurrent batches of mrp_phase_reads_many) */
     std::mutex sibling_mu;
@@ -549,10 +551,11 @@ struct mrp_string_front;
 int mrp_string_chunks_check(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
                             int64_t expansion, const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
                             const mrp_string_chunk_rest *rest, const char *who);
+/* wide_pairs: the caller's setting (a context's or a queue's): check_pairs and the front then refuse only beyond the wide kernel's caps */
 int mrp_string_chunks_check_pairs(int64_t n_chunks, const mrp_string_chunk *chunks, int64_t expansion, int64_t sv_threshold, const mrp_string_chunk_rest *rest,
-                                  const char *who);
+                                  const char *who, int wide_pairs);
 int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest, const mrp_pair_hmm *forward_model,
-                            const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, mrp_string_front **front_out);
+                            const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, int wide_pairs, mrp_string_front **front_out);
 void mrp_string_front_destroy(mrp_string_front *front);
 int mrp_string_front_run(mrp_context *ctx, mrp_string_front *front, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
                          mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,

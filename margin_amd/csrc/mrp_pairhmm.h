@@ -1,5 +1,5 @@
 /*
- * mrp_pairhmm.h -- what crosses the seams between the three units of the pair-HMM family: mrp_pairhmm.hip (the two kernels, the
+ * mrp_pairhmm.h -- what crosses the seams between the three units of the pair-HMM family: mrp_pairhmm.hip (the three kernels, the
  * launch scaffold, the small entries), mrp_string_chunks.hip (the string-chunk calls) and mrp_aligned.hip (the composites over the
  * extraction's result in HBM).  Internal; every unit that includes it is compiled with -ffp-contract=off.
  */
@@ -12,6 +12,7 @@
 
 constexpr int PHM_WAVE = 64;
 constexpr int PHM_WAVE_MAX_WIDTH = 2048; /* 3 diagonals * 2 048 cells * 3 states * 8 B = 144 KB */
+constexpr int64_t PHM_WIDE_WORKSPACE_BYTES = (int64_t) 256 << 20; /* pair-per-workgroup kernel: what the slices of one launch may hold together */
 
 struct PhmModelDev {
     double t[9];     /* order of mrp_pair_hmm */
@@ -115,6 +116,9 @@ struct PhmLaunch {
     std::vector<PhmModelDev> hm;
     HostVec<PhmLanePair> lane_pairs[4];
     HostVec<PhmPair> wave_pairs[4];
+    HostVec<PhmPair> wide_pairs; /* wide pairs on: the pairs beyond PHM_WAVE_MAX_WIDTH, for the pair-per-workgroup kernel */
+    int wide_width = 0;          /* the widest diagonal among them: the cells of a workgroup's slice per diagonal and state */
+    int64_t wide_cells = 0;      /* their share of cells */
     HostVec<int32_t> band;
     HostVec<uint32_t> key; /* phm_classify's sort keys (released with the launch, not between its two halves) */
 };
@@ -127,13 +131,18 @@ struct PhmDev {
     DevBuf<double> d_out{arrays};
     DevBuf<PhmLanePair> d_lane[4]{DevBuf<PhmLanePair>{arrays}, DevBuf<PhmLanePair>{arrays}, DevBuf<PhmLanePair>{arrays}, DevBuf<PhmLanePair>{arrays}};
     DevBuf<PhmPair> d_wave[4]{DevBuf<PhmPair>{arrays}, DevBuf<PhmPair>{arrays}, DevBuf<PhmPair>{arrays}, DevBuf<PhmPair>{arrays}};
+    DevBuf<PhmPair> d_wide{arrays};
+    DevBuf<double> d_wide_ws{arrays}; /* [workgroup][diagonal being written, xay - 1, xay - 2][state][wide_width] */
     ~PhmDev() {
         if (s) (void) hipStreamSynchronize(s);
     }
 };
 
+/* wide_pairs: the caller's setting (mrp_context_set_wide_pairs / mrp_queue_set_wide_pairs); 0 is the refusal beyond PHM_WAVE_MAX_WIDTH */
 int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, int64_t pool_bytes, const PhmPairs &P, int64_t expansion,
-                 int ragged_left, int ragged_right, PhmLaunch &L);
+                 int ragged_left, int ragged_right, int wide_pairs, PhmLaunch &L);
+/* wide pairs on: MRP_OK, or the message of the cap a pair of this width and these cells exceeds (what: "pair 12", "chunk 3: a pair of bubble 7") */
+int phm_wide_caps(const char *who, const char *what, int64_t width, int64_t cells);
 int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64_t n_pairs, const PhmLaunch &H, PhmDev &L, mrp_pairhmm_stats *stats,
                 const uint8_t *device_pool = nullptr);
 
@@ -152,7 +161,7 @@ int phm_call(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, int3
         PhmLaunch H;
         PhmDev L;
         if (P.n > 0) { /* (the host's errors first, then the device: phm_enqueue makes it current) */
-            int rc = phm_classify(who, models, n_models, pool_bytes, P, expansion, ragged_left, ragged_right, H);
+            int rc = phm_classify(who, models, n_models, pool_bytes, P, expansion, ragged_left, ragged_right, ctx->wide_pairs, H);
             if (rc == MRP_OK) rc = phm_enqueue(ctx, pool, pool_bytes, P.n, H, L, stats);
             if (rc != MRP_OK) return rc;
         } else {

@@ -10,7 +10,7 @@
  * its neighbours (x-1, y), (x-1, y-1), (x, y-1); a neighbour outside the band contributes nothing, which is what a
  * neighbour holding LOG_ZERO contributes, so the kernels keep -inf where the reference keeps NULL.  Each state is a
  * chain of three logAdd (pairwiseAligner.c:279-299: cubic interpolation in fp64, float literals, no exp / log) in the
- * reference's order.  Two mappings:
+ * reference's order.  Three mappings:
  *
  *   phm_lane_kernel   a pair per LANE, for pairs whose x string has at most 100 symbols and no anchors (their band is
  *                     the whole matrix): the lane walks its matrix row by row, the previous row lives in LDS as
@@ -20,7 +20,9 @@
  *                     10^5 pairs per 1 Mb chunk.  LDS per wave = 1 536 B x (longest x string of the launch class):
  *                     25 symbols -> 4 waves per CU, one per SIMD.
  *   phm_wave_kernel   a pair per WAVE for everything else (long strings, anchored bands): x+y diagonal by diagonal, a
- *                     lane per cell of the diagonal, the last two diagonals in LDS.
+ *                     lane per cell of the diagonal, the last two diagonals in LDS -- up to 2 048 cells on a diagonal.
+ *   phm_wide_kernel   a pair per WORKGROUP for the pairs beyond that, when the caller has turned wide pairs on (else they are
+ *                     refused): the same walk with the diagonals in a device workspace.
  *
  * Bound: fp64 VALU issue (six logAdd per cell); the kernels move ~0.1 B per flop.
  */
@@ -344,6 +346,85 @@ __global__ void __launch_bounds__(PHM_WAVE) phm_wave_kernel(const PhmPair *__res
     }
 }
 
+/* A pair per WORKGROUP, for the pairs whose widest diagonal does not fit the LDS of phm_wave_kernel (wide pairs on): the same walk,
+ * x+y diagonal by diagonal with the threads striding over the diagonal's cells, the same limits(), the same phm_cell / phm_log_add /
+ * phm_dot -- a cell's value does not depend on which thread computes it.  The three live diagonals lie in the workgroup's slice of a
+ * device workspace, ws[workgroup][diagonal][state][W] (W = the widest diagonal of the launch; an array per state, so a wave's loads
+ * and stores are consecutive 8-byte accesses), and rotate by pointer.  A workgroup reads only what it wrote itself and runs on one CU:
+ * one __syncthreads() between diagonals is the only synchronisation.  The next pair of the grid-stride loop reuses the slice; every
+ * cell read lies inside [l1, r1] / [l2, r2] of the pair's own diagonals, which that pair wrote. */
+template <int T>
+__global__ void __launch_bounds__(T) phm_wide_kernel(const PhmPair *__restrict__ pairs, int64_t n_pairs, const uint8_t *__restrict__ pool,
+                                                     const PhmModelDev *__restrict__ models, const int32_t *__restrict__ band, int W, double *ws,
+                                                     double *__restrict__ out) {
+    double *slice = ws + (size_t) blockIdx.x * 9 * (size_t) W;
+    const int tid = threadIdx.x;
+    for (int64_t pi = blockIdx.x; pi < n_pairs; pi += gridDim.x) {
+        const PhmPair p = pairs[pi];
+        const int lx = p.lx, ly = p.ly, n = lx + ly;
+        const PhmModelDev *__restrict__ M = models + p.model;
+        double t[9];
+#pragma unroll
+        for (int i = 0; i < 9; i++) t[i] = M->t[i];
+        const uint8_t *__restrict__ sx = pool + p.x_off;
+        const uint8_t *__restrict__ sy = pool + p.y_off;
+        double *d0 = slice, *d1 = slice + 3 * (size_t) W, *d2 = slice + 6 * (size_t) W; /* being written, xay - 1, xay - 2 */
+        auto limits = [&](int d, int &l, int &r) {
+            if (p.band_off >= 0) {
+                l = band[2 * (p.band_off + d)];
+                r = band[2 * (p.band_off + d) + 1];
+            } else {
+                const int xlo = d - ly > 0 ? d - ly : 0, xhi = d < lx ? d : lx;
+                l = 2 * xlo - d;
+                r = 2 * xhi - d;
+            }
+        };
+        int l1, r1, l2 = 1, r2 = 0;
+        limits(0, l1, r1);
+        for (int i = tid; i <= (r1 - l1) / 2; i += T) {
+            d1[i] = M->start[0];
+            d1[W + i] = M->start[1];
+            d1[2 * W + i] = M->start[2];
+        }
+        __syncthreads();
+        for (int d = 1; d <= n; d++) {
+            int l, r;
+            limits(d, l, r);
+            const int width = (r - l) / 2 + 1;
+            for (int i = tid; i < width; i += T) {
+                const int xmy = l + 2 * i;
+                const int x = (d + xmy) >> 1, y = (d - xmy) >> 1;
+                St lower{PHM_NEG, PHM_NEG, PHM_NEG}, middle = lower, upper = lower;
+                if (xmy - 1 >= l1 && xmy - 1 <= r1) { const double *c = d1 + ((xmy - 1 - l1) >> 1); lower = St{c[0], c[W], c[2 * W]}; }
+                if (xmy + 1 >= l1 && xmy + 1 <= r1) { const double *c = d1 + ((xmy + 1 - l1) >> 1); upper = St{c[0], c[W], c[2 * W]}; }
+                if (xmy >= l2 && xmy <= r2) { const double *c = d2 + ((xmy - l2) >> 1); middle = St{c[0], c[W], c[2 * W]}; }
+                int cx = 4, cy = 4;
+                if (x > 0) { cx = sx[x - 1]; cx = cx > 4 ? 4 : cx; }
+                if (y > 0) { cy = sy[y - 1]; cy = cy > 4 ? 4 : cy; }
+                const double eY = M->ey[cy];
+                const PhmRowT ty{eY + t[4], eY + t[6], eY + t[8]};
+                const St cur = phm_cell(lower, middle, upper, t, M->ex[cx], M->em[cx * 5 + cy], ty);
+                d0[i] = cur.m;
+                d0[W + i] = cur.x;
+                d0[2 * W + i] = cur.y;
+            }
+            __syncthreads();
+            double *tmp = d2;
+            d2 = d1; d1 = d0; d0 = tmp;
+            l2 = l1; r2 = r1; l1 = l; r1 = r;
+        }
+        /* the total on the last diagonal, serially in index order as phm_wave_kernel does: phm_log_add is not associative */
+        if (tid == 0) {
+            const double e_end[3] = {M->end[0], M->end[1], M->end[2]};
+            double tot = PHM_NEG;
+            for (int i = 0; i <= (r1 - l1) / 2; i++) tot = phm_log_add(tot, phm_dot(St{d1[i], d1[W + i], d1[2 * W + i]}, e_end));
+            out[p.out] = tot;
+        }
+        __syncthreads();
+    }
+}
+constexpr int PHM_WIDE_THREADS = 1024; /* workgroup of phm_wide_kernel (measured against 256 and 512: DESIGN.md 9.10) */
+
 }  // namespace
 
 /* ---------------- host ---------------- */
@@ -459,11 +540,23 @@ int64_t kmer_anchors(const uint8_t *sx, int64_t lx, const uint8_t *sy, int64_t l
     return n;
 }
 
+/* wide pairs on: the two refusals that remain (what: "pair 12", "chunk 3: a pair of bubble 7") */
+int phm_wide_caps(const char *who, const char *what, int64_t width, int64_t cells) {
+    if (width > MRP_WIDE_MAX_WIDTH)
+        return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: %s has a diagonal of %lld cells (limit %d with wide pairs on, MRP_WIDE_MAX_WIDTH)", who, what,
+                             (long long) width, (int) MRP_WIDE_MAX_WIDTH);
+    if (cells > MRP_WIDE_MAX_CELLS)
+        return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: %s has %lld dp cells inside its band, its widest diagonal %lld (limit %lld cells with wide pairs on, MRP_WIDE_MAX_CELLS)",
+                             who, what, (long long) cells, (long long) width, (long long) MRP_WIDE_MAX_CELLS);
+    return MRP_OK;
+}
+
 /* The host half of a pair-HMM batch of n_pairs > 0 pairs, no device needed: the pairs sorted into the launch classes of
  * the two kernels, the bands of the anchored ones, the models as the kernels read them.  Every error of the batch (prefixed
- * with who) is raised here, MRP_ERR_UNSUPPORTED for a diagonal beyond PHM_WAVE_MAX_WIDTH cells among them. */
+ * with who) is raised here, MRP_ERR_UNSUPPORTED for a diagonal beyond PHM_WAVE_MAX_WIDTH cells among them -- or, with wide_pairs,
+ * beyond the caps of the pair-per-workgroup kernel, which then takes the pairs beyond PHM_WAVE_MAX_WIDTH (L.wide_pairs). */
 int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, int64_t pool_bytes, const PhmPairs &P, int64_t expansion,
-                 int ragged_left, int ragged_right, PhmLaunch &L) {
+                 int ragged_left, int ragged_right, int wide_pairs, PhmLaunch &L) {
     const int64_t n_pairs = P.n;
     const int64_t *x_off = P.x_off, *y_off = P.y_off, *anchor_off = P.anchor_off, *anchors = P.anchors;
     const int32_t *x_len = P.x_len, *y_len = P.y_len;
@@ -559,9 +652,11 @@ int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, 
         p.model = model_index ? model_index[i] : 0;
         p.out = (int32_t) i;
         int width;
+        int64_t pair_cells;
         if (na == 0) {
             width = (int) std::min(lx, ly) + 1;
-            cells += (lx + 1) * (ly + 1);
+            pair_cells = (lx + 1) * (ly + 1);
+            cells += pair_cells;
         } else {
             if (lx + ly >= (1ll << 30)) return mrp_set_error(MRP_ERR_ARG, "%s: strings too long", who);
             Lb.resize((size_t) (lx + ly + 1));
@@ -570,20 +665,32 @@ int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, 
             const int rc = band_closed_form(anchors + 2 * anchor_off[i], na, lx, ly, expansion, Lb.data(), Rb.data(), &c, &width);
             if (rc != MRP_OK) return mrp_set_error(rc, "%s: pair %lld has invalid anchors (pairwiseAligner.c:206-211)", who, (long long) i);
             cells += c;
+            pair_cells = c;
             p.band_off = (int64_t) band.size() / 2;
             for (int64_t d = 0; d <= lx + ly; d++) { band.push_back(Lb[(size_t) d]); band.push_back(Rb[(size_t) d]); }
         }
-        if (width > PHM_WAVE_MAX_WIDTH)
-            return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: pair %lld has a diagonal of %d cells (limit %d)", who, (long long) i, width, PHM_WAVE_MAX_WIDTH);
+        if (width > PHM_WAVE_MAX_WIDTH) {
+            if (!wide_pairs)
+                return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: pair %lld has a diagonal of %d cells (limit %d)", who, (long long) i, width, PHM_WAVE_MAX_WIDTH);
+            char what[48];
+            snprintf(what, sizeof(what), "pair %lld", (long long) i);
+            const int rc = phm_wide_caps(who, what, width, pair_cells);
+            if (rc != MRP_OK) return rc;
+            L.wide_pairs.push_back(p);
+            L.wide_width = std::max(L.wide_width, width);
+            L.wide_cells += pair_cells;
+            continue;
+        }
         int c = 0;
         while (width > WAVE_CLASS_CAP[c]) c++;
         wave_pairs[c].push_back(p);
     }
-    for (int c = 0; c < 4; c++)
-        std::sort(wave_pairs[c].begin(), wave_pairs[c].end(), [](const PhmPair &a, const PhmPair &b) {
-            const int64_t ca = (int64_t) a.lx * a.ly, cb = (int64_t) b.lx * b.ly;
-            return ca != cb ? ca > cb : a.out < b.out;
-        });
+    const auto largest_first = [](const PhmPair &a, const PhmPair &b) {
+        const int64_t ca = (int64_t) a.lx * a.ly, cb = (int64_t) b.lx * b.ly;
+        return ca != cb ? ca > cb : a.out < b.out;
+    };
+    for (int c = 0; c < 4; c++) std::sort(wave_pairs[c].begin(), wave_pairs[c].end(), largest_first);
+    std::sort(L.wide_pairs.begin(), L.wide_pairs.end(), largest_first);
     L.cells = cells;
     L.n_models = n_models;
     L.table_bytes = table_bytes;
@@ -621,6 +728,16 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
     for (int c = 0; c < 4; c++) {
         PHM_HIP(L.d_lane[c].upload(lane_pairs[c], s));
         PHM_HIP(L.d_wave[c].upload(wave_pairs[c], s));
+    }
+    /* the pair-per-workgroup kernel: as many workgroups as the workspace bound holds slices of 9 x (widest diagonal) doubles */
+    const int64_t n_wide = (int64_t) H.wide_pairs.size();
+    int64_t wide_grid = 0;
+    if (n_wide > 0) {
+        const int64_t slice_bytes = 9 * (int64_t) H.wide_width * (int64_t) sizeof(double);
+        wide_grid = std::min(n_wide, std::max<int64_t>(1, PHM_WIDE_WORKSPACE_BYTES / slice_bytes));
+        if (ctx->test_hooks & 64) wide_grid = 1; /* test hook: consecutive pairs reuse one slice */
+        PHM_HIP(L.d_wide.upload(H.wide_pairs, s));
+        PHM_HIP(L.d_wide_ws.alloc((size_t) wide_grid * 9 * (size_t) H.wide_width));
     }
     /* once per device (contexts of several host threads may call concurrently) */
     static PerDeviceOnce once;
@@ -661,6 +778,14 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
                            L.d_models.p, L.d_band.p, W, L.d_out.p);
         PHM_HIP(hipGetLastError());
         if (stats) stats->pairs_wave += n;
+    }
+    if (n_wide > 0) {
+        hipLaunchKernelGGL(phm_wide_kernel<PHM_WIDE_THREADS>, dim3((unsigned) wide_grid), dim3(PHM_WIDE_THREADS), 0, s, L.d_wide.p, n_wide, device_pool, L.d_models.p,
+                           L.d_band.p, H.wide_width, L.d_wide_ws.p, L.d_out.p);
+        PHM_HIP(hipGetLastError());
+        if (stats) stats->pairs_wave += n_wide;
+        ctx->wide_pair_count += n_wide;
+        ctx->wide_cell_count += H.wide_cells;
     }
     return MRP_OK;
 }
@@ -822,6 +947,24 @@ int mrp_band_diagonals(const int64_t *anchors, int64_t n_anchors, int64_t lx, in
     if (lx + ly >= (1ll << 30)) return fail(MRP_ERR_ARG, "mrp_band_diagonals: strings too long");
     const int rc = band_closed_form(anchors, n_anchors, lx, ly, expansion, xmy_l, xmy_r, nullptr, nullptr);
     return rc == MRP_OK ? rc : fail(rc, "mrp_band_diagonals: invalid anchors or expansion (pairwiseAligner.c:179,206-211)");
+}
+
+int mrp_pair_diagonal_width(const int64_t *anchors, int64_t n_anchors, int64_t lx, int64_t ly, int64_t expansion, int32_t *width_out,
+                            int64_t *cells_out) {
+    if ((n_anchors > 0 && !anchors) || n_anchors < 0) return fail(MRP_ERR_ARG, "mrp_pair_diagonal_width: null argument");
+    if (lx < 0 || ly < 0 || expansion < 0 || expansion % 2 != 0)
+        return fail(MRP_ERR_ARG, "mrp_pair_diagonal_width: invalid anchors or expansion (pairwiseAligner.c:179,206-211)");
+    if (lx + ly >= (1ll << 30)) return fail(MRP_ERR_ARG, "mrp_pair_diagonal_width: strings too long");
+    int width = (int) std::min(lx, ly) + 1; /* no anchors: the whole matrix, as phm_classify counts it */
+    int64_t cells = (lx + 1) * (ly + 1);
+    if (n_anchors > 0) {
+        std::vector<int32_t> Lb((size_t) (lx + ly + 1)), Rb((size_t) (lx + ly + 1));
+        const int rc = band_closed_form(anchors, n_anchors, lx, ly, expansion, Lb.data(), Rb.data(), &cells, &width);
+        if (rc != MRP_OK) return fail(rc, "mrp_pair_diagonal_width: invalid anchors or expansion (pairwiseAligner.c:179,206-211)");
+    }
+    if (width_out) *width_out = width;
+    if (cells_out) *cells_out = cells;
+    return MRP_OK;
 }
 
 int mrp_forward_probabilities(mrp_context *ctx, const mrp_pair_hmm *models, int32_t n_models, int64_t n_pairs, const uint8_t *pool,

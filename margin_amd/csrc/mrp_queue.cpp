@@ -241,6 +241,7 @@ struct mrp_queue {
     /* Calls of a device in flight at a time ("lanes", each a host thread with its own contexts); see plan_queue.  A short
      * queue uses one of them.  MRP_QUEUE_LANES=1..4 overrides. */
     int lanes = 4;
+    int wide_pairs = 0; /* mrp_queue_set_wide_pairs: every lane's context gets it when the lane begins a call; the up-front checks read it */
 };
 
 int mrp_queue_create(const int32_t *devices, int32_t n_devices, mrp_queue **out) {
@@ -271,6 +272,26 @@ void mrp_queue_destroy(mrp_queue *q) {
     for (auto *c : q->ctx) mrp_context_destroy(c);
     for (auto *p : q->pools) mrp_host_pool_destroy(p);
     delete q;
+}
+
+int mrp_queue_set_wide_pairs(mrp_queue *q, int on) {
+    if (!q) return mrp_set_error(MRP_ERR_ARG, "mrp_queue_set_wide_pairs: queue is NULL");
+    q->wide_pairs = on != 0;
+    for (mrp_context *c : q->ctx)
+        if (c) (void) mrp_context_set_wide_pairs(c, q->wide_pairs);
+    return MRP_OK;
+}
+
+int mrp_queue_wide_pair_count(mrp_queue *q, int64_t *pairs_out, int64_t *cells_out) {
+    if (!q) return mrp_set_error(MRP_ERR_ARG, "mrp_queue_wide_pair_count: queue is NULL");
+    int64_t pairs = 0, cells = 0;
+    for (mrp_context *c : q->ctx) {
+        int64_t p = 0, n = 0;
+        if (c && mrp_context_wide_pair_count(c, &p, &n) == MRP_OK) { pairs += p; cells += n; }
+    }
+    if (pairs_out) *pairs_out = pairs;
+    if (cells_out) *cells_out = cells;
+    return MRP_OK;
 }
 
 }  /* extern "C" */
@@ -346,6 +367,7 @@ struct QueueCall {
         }
         if (r != MRP_OK) { errs[(size_t) w] = mrp_last_error(); return r; }
         if (lanes > 1) (void) mrp_context_set_grouped(q->ctx[(size_t) w], 1); /* the lanes of a device are concurrent batches of it */
+        (void) mrp_context_set_wide_pairs(q->ctx[(size_t) w], q->wide_pairs);
         q->ctx[(size_t) w]->calls_sharing_device = n_batches > (int64_t) n_devices ? active_lanes : 1;
         caller_pool[(size_t) w] = mrp_pool_current();
         mrp_pool_adopt(q->pools[(size_t) d]);
@@ -557,7 +579,7 @@ static int queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_s
     if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = n_devices; }
     for (int64_t i = 0; i < n_chunks; i++) out[i] = nullptr;
     if (profiles_out) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
-    rc = mrp_string_chunks_check_pairs(n_chunks, chunks, expansion, sv_threshold, rest, who);
+    rc = mrp_string_chunks_check_pairs(n_chunks, chunks, expansion, sv_threshold, rest, who, q->wide_pairs);
     if (rc != MRP_OK) return rc;
     if (n_chunks == 0) return MRP_OK;
     /* phase.c:257-263 orders by estimated depth; here a chunk costs its (read, bubble) units, the unit the batches are cut by, and
@@ -600,7 +622,7 @@ static int queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_s
         for (int64_t i = 0; rest && i < st->count; i++) st->sr[(size_t) i] = rest[plan.order[(size_t) (st->first + i)]];
         st->batch.store(b);
         const int r = mrp_string_front_create(st->count, st->sc.data(), rest ? st->sr.data() : nullptr, forward_model, reverse_model, expansion, sv_threshold,
-                                              &st->front);
+                                              q->wide_pairs, &st->front);
         if (r != MRP_OK) call.stage_errs[(size_t) w] = mrp_last_error();
         if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: front of batch %lld (%lld chunks) in %.1f ms\n", call.since(), w, (long long) b, (long long) st->count, ms_since(t0));
         return r;

@@ -386,9 +386,10 @@ int mrp_string_chunks_check(int64_t n_chunks, const mrp_string_chunk *chunks, co
 /* MRP_ERR_UNSUPPORTED as phm_classify raises it, from the strings alone -- without the owners, the pair list or the sort (a
  * duplicate substring has its owner's strings, so looking at every substring changes nothing).  A diagonal of a pair holds at
  * most min(lx, ly) + 1 cells, band or not: only pairs with BOTH strings at the limit are looked at, their anchors (above
- * sv_threshold, bubbleGraph.c:1448-1451) and bands made as the front makes them. */
+ * sv_threshold, bubbleGraph.c:1448-1451) and bands made as the front makes them.  wide_pairs (mrp_queue_set_wide_pairs): such a pair
+ * is refused only beyond the caps of the pair-per-workgroup kernel. */
 int mrp_string_chunks_check_pairs(int64_t n_chunks, const mrp_string_chunk *chunks, int64_t expansion, int64_t sv_threshold,
-                                  const mrp_string_chunk_rest *rest, const char *who) {
+                                  const mrp_string_chunk_rest *rest, const char *who, int wide_pairs) {
     std::vector<int> rcs((size_t) n_chunks, MRP_OK);
     std::vector<std::string> msgs((size_t) n_chunks);
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
@@ -402,17 +403,22 @@ int mrp_string_chunks_check_pairs(int64_t n_chunks, const mrp_string_chunk *chun
             anc.clear();
             if (anchored) kmer_anchors(x, lx, y, ly, anc);
             int width = (int) std::min<int64_t>(std::min(lx, ly) + 1, INT32_MAX);
+            int64_t cells = (lx + 1) * (ly + 1);
             if (!anc.empty()) {
                 if (lx + ly >= (1ll << 30)) { rcc = mrp_set_error(MRP_ERR_ARG, "%s: strings too long", who); return; }
                 Lb.resize((size_t) (lx + ly + 1));
                 Rb.resize((size_t) (lx + ly + 1));
-                const int rc = band_closed_form(anc.data(), (int64_t) anc.size() / 2, lx, ly, expansion, Lb.data(), Rb.data(), nullptr, &width);
+                const int rc = band_closed_form(anc.data(), (int64_t) anc.size() / 2, lx, ly, expansion, Lb.data(), Rb.data(), &cells, &width);
                 if (rc != MRP_OK) {
                     rcc = mrp_set_error(rc, "%s: chunk %lld: a pair of %s %lld has invalid anchors (pairwiseAligner.c:206-211)", who, (long long) c, what, (long long) idx);
                     return;
                 }
             }
-            if (width > PHM_WAVE_MAX_WIDTH)
+            if (width > PHM_WAVE_MAX_WIDTH && wide_pairs) {
+                char which[96];
+                snprintf(which, sizeof(which), "chunk %lld: a pair of %s %lld", (long long) c, what, (long long) idx);
+                rcc = phm_wide_caps(who, which, width, cells);
+            } else if (width > PHM_WAVE_MAX_WIDTH)
                 rcc = mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: chunk %lld: a pair of %s %lld has a diagonal of %d cells (limit %d)", who, (long long) c, what,
                                     (long long) idx, width, PHM_WAVE_MAX_WIDTH);
         };
@@ -660,7 +666,7 @@ int sc_filtered_front(mrp_string_front *F, const mrp_string_chunk_rest *rest, in
 }
 
 int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest, const mrp_pair_hmm *forward_model,
-                            const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, mrp_string_front **front_out) {
+                            const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, int wide_pairs, mrp_string_front **front_out) {
     const char *who = rest ? "mrp_phase_string_chunks_with_filtered" : "mrp_phase_string_chunks";
     const double t_begin = now_ms();
     *front_out = nullptr;
@@ -761,7 +767,7 @@ int mrp_string_front_create(int64_t n_chunks, const mrp_string_chunk *chunks, co
     }
     if (F->n_pairs > 0) {
         const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
-        const int rc = phm_classify(who, models, 2, (int64_t) gpool.size(), pairs.view(), expansion, 0, 0, F->L);
+        const int rc = phm_classify(who, models, 2, (int64_t) gpool.size(), pairs.view(), expansion, 0, 0, wide_pairs, F->L);
         if (rc != MRP_OK) return rc;
     }
     F->front_ms = now_ms() - t_begin;
@@ -1244,7 +1250,7 @@ static int sc_phase_chunks(const char *who, double t_begin, mrp_context *ctx, in
     if (profiles_out) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
     if (n_chunks == 0) return MRP_OK;
     mrp_string_front *F = nullptr;
-    rc = mrp_string_front_create(n_chunks, chunks, rest, forward_model, reverse_model, expansion, sv_threshold, &F);
+    rc = mrp_string_front_create(n_chunks, chunks, rest, forward_model, reverse_model, expansion, sv_threshold, ctx->wide_pairs, &F);
     if (rc != MRP_OK) return rc;
     F->front_ms = now_ms() - t_begin;
     rc = mrp_string_front_run(ctx, F, het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, stats, filtered_out, filtered_stats);
