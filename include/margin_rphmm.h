@@ -370,6 +370,11 @@ void mrp_queue_destroy(mrp_queue *q);
  * queues no longer meet that refusal as a lane error, up to MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS.  Between calls of the queue
  * only.  The *_on_devices forms make a queue of their own with the setting off: a caller who wants wide pairs makes a queue. */
 int mrp_queue_set_wide_pairs(mrp_queue *q, int on);
+/* mrp_context_set_sv_split (below, with the extraction) for every lane's context, present and future, and for the up-front mode check
+ * of the aligned and haplotag queues: with it on, indel_size_for_sv_handling > 0 runs the split walk instead of stopping the queue with
+ * MRP_ERR_UNSUPPORTED before its first batch.  Between calls of the queue only.  The *_on_devices forms make a queue of their own with
+ * the setting off and keep the refusal: a caller who wants the SV split makes a queue. */
+int mrp_queue_set_sv_split(mrp_queue *q, int on);
 /* mrp_context_wide_pair_count summed over the lanes' contexts (either pointer may be NULL) */
 int mrp_queue_wide_pair_count(mrp_queue *q, int64_t *pairs_out, int64_t *cells_out);
 int mrp_queue_phase_chunks(mrp_queue *q, int64_t n_chunks, const mrp_chunk_desc *chunks, const mrp_params *params, int64_t chunks_per_batch,
@@ -777,7 +782,7 @@ int mrp_phase_string_chunks_with_filtered_on_devices(const int32_t *devices, int
 /* ---- from alignments to read substrings at variant sites --------------------------------------------------------------
  * The step of margin phase's chunk loop that makes the strings above (phase.c:337-357): updateVcfEntriesWithSubstringsAndPositions
  * (impl/vcf.c:476-486, getAlleleSubstrings2 :394-462) and extractReadSubstringsAtVariantPositions (impl/htsIntegration.c:1722-1989)
- * with indelSizeForSVHandling = 0.  One chunk's inputs in the layout htslib holds them; coordinates are 0-based genome
+ * with indelSizeForSVHandling = 0, or > 0 on a context that admits it (mrp_context_set_sv_split below).  One chunk's inputs in the layout htslib holds them; coordinates are 0-based genome
  * positions (bamChunk's chunkOverlapStart / chunkOverlapEnd / chunkStart / chunkEnd). */
 #define MRP_READ_DROPPED 0  /* not listed: filtered out (:1816-1842) or no variant at or after its start (:1855) */
 #define MRP_READ_KEPT 1     /* in `reads` */
@@ -792,7 +797,7 @@ typedef struct mrp_aligned_chunk {
     const int64_t *allele_off;    /* per allele: its chars in allele_chars; allele 0 = REF */
     const int32_t *allele_len;
     const char *allele_chars; int64_t allele_bytes;
-    const uint8_t *is_sv;         /* n_variants: nonzero selects expansion_sv (isStructuralVariant, vcf.c:405-410) */
+    const uint8_t *is_sv;         /* n_variants: nonzero selects expansion_sv (isStructuralVariant, vcf.c:405-410) and, in the SV split, the variant's walk; mrp_mark_structural_variants makes it */
     int64_t n_reads;
     const int64_t *pos;           /* bam1_core_t.pos */
     const uint16_t *flag;         /* bam1_core_t.flag */
@@ -810,7 +815,9 @@ typedef struct mrp_extract_options {
     int64_t min_mapq;                /* filterAlignmentsWithMapQBelowThisThreshold (5 shipped) */
     int32_t include_secondary;       /* includeSecondaryAlignments (0 shipped) */
     int32_t include_supplementary;   /* includeSupplementaryAlignments (0 shipped) */
-    int32_t indel_size_for_sv_handling; /* indelSizeForSVHandling: only 0 (shipped) is supported (:1724-1755) */
+    int32_t indel_size_for_sv_handling; /* indelSizeForSVHandling (0 in the shipped small-variant configurations, 50 in allParams.phase_vcf.ont.sv.json): 0 is
+                                         * the one-list walk; > 0 is the SV split (:1724-1755), refused unless mrp_context_set_sv_split is on -- only the sign
+                                         * is read, the threshold was applied when is_sv was made; < 0 is refused */
     int32_t use_run_length_encoding; /* useRunLengthEncoding: only 0 (shipped) is supported */
 } mrp_extract_options;
 
@@ -850,9 +857,28 @@ typedef struct mrp_extract_stats {
  * variant without alleles, a REF allele that disagrees with an A/C/G/T reference base (vcf.c:423), a reference slice of the
  * wrong length, a CIGAR op code above 8, and for a read with bases and a CIGAR: an M/I/D/N/=/X op of length 0 (the
  * reference's walk never leaves it) or a CIGAR whose query length is not l_qseq.  MRP_ERR_UNSUPPORTED for the SV split
- * mode or run-length encoding.  Nothing is returned on error.  stats may be NULL. */
+ * mode (unless the context admits it, mrp_context_set_sv_split) or run-length encoding.  Nothing is returned on error.  stats may be NULL. */
 int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_extract_options *options,
                                 mrp_extracted_chunk **out, mrp_extract_stats *stats);
+
+/* The SV split of the extraction (indelSizeForSVHandling > 0, htsIntegration.c:1722-1759), per context.
+ * off (default): a nonzero indel_size_for_sv_handling is refused (MRP_ERR_UNSUPPORTED), as documented at every entry; a NULL context
+ *   counts as off, so the order MRP_ERR_ARG, MRP_ERR_UNSUPPORTED, MRP_ERR_NO_DEVICE holds.
+ * on: indel_size_for_sv_handling > 0 runs the split walk; 0 the one-list walk, bit for bit; < 0 is still refused.
+ * The split walk: the walk of mrp_extract_read_substrings runs over the chunk's small variants (is_sv == 0) alone and over its
+ * structural ones alone -- each with its own first-entry search (a read with no variant of the class at or after its start is not
+ * listed by that walk), its own "starts no earlier than the entry before" state, dropping rules and step bound -- and the two results
+ * are merged per read (mergeVariantTypeSeparatedReadLists, :1675-1719): read_status is MRP_READ_DROPPED only if both walks dropped the
+ * read, read_n_substrings is the sum, a variant's entries are those of its class's walk in ascending read index.  Windows, allele
+ * strings and the output layout (the caller's variant order) do not change.  Two assumptions: the reference
+ * lists the merged reads in the iteration order of a hash over read names, here they stay in ascending read index; the reference merges
+ * by read name (at most two records a name), here by read index.
+ * Honoured by mrp_extract_read_substrings, mrp_haplotag_aligned_chunks, mrp_phase_aligned_chunks and
+ * mrp_phase_aligned_chunks_with_filtered (where the primary and the filtered variant set are split each on its own, phase.c:353-357). */
+int mrp_context_set_sv_split(mrp_context *ctx, int on);
+/* host only, no device: isStructuralVariant as loadVcfEntries sets it (vcf.c:173-185) -- is_sv_out[v] = 1 if any allele of variant v is
+ * longer than indel_size, else 0; every byte 0 for indel_size <= 0.  Reads chunk->n_variants, allele_first and allele_len only. */
+int mrp_mark_structural_variants(const mrp_aligned_chunk *chunk, int64_t indel_size, uint8_t *is_sv_out);
 
 /* bubbleGraph_constructFromVCFAndBamChunkReadVcfEntrySubstrings (bubbleGraph.c:1338-1400), host only: the mrp_string_chunk
  * of one extracted chunk over its MRP_READ_KEPT reads r with keep[r] set (keep NULL: all; the seam for the caller's
@@ -933,7 +959,7 @@ typedef struct mrp_haplotag_aligned_stats {
  * `reads`: dropped or low mapq); h1_out / h2_out (NULL, or one array per chunk) the totals, 0 for reads that are not kept.
  * Outputs are written only on success.  Errors, in this order: MRP_ERR_ARG (the extraction's own checks, a NULL model or output,
  * a NULL gt[c] for a chunk with variants, a genotype outside the variant's alleles, an odd or negative expansion) before the
- * context is looked at; MRP_ERR_UNSUPPORTED for the SV split mode or run-length encoding, as the extraction reports them:
+ * context is looked at; MRP_ERR_UNSUPPORTED for the SV split mode (unless the context admits it, mrp_context_set_sv_split) or run-length encoding, as the extraction reports them:
  * without a context too; MRP_ERR_NO_DEVICE for a NULL context; MRP_ERR_UNSUPPORTED for a pair whose widest diagonal exceeds
  * 2 048 cells, known once the extraction's device half has given the lengths and raised before any pair-HMM kernel is launched (unless wide pairs are on for the context, mrp_context_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS).
  * stats may be NULL. */
@@ -978,7 +1004,7 @@ typedef struct mrp_phase_aligned_stats {
  * variant left without an entry that takes part makes no bubble (:1366-1371).
  * Errors, in this order: MRP_ERR_ARG before the context is looked at (the extraction's checks; NULL models, params, out, hap_out,
  * hap_out[c] / phred_out[c] / read_names[c] / a read name for a chunk with reads; an odd or negative expansion);
- * MRP_ERR_UNSUPPORTED for the SV split mode or run-length encoding, without a context too; MRP_ERR_NO_DEVICE for a NULL context;
+ * MRP_ERR_UNSUPPORTED for the SV split mode (unless the context admits it, mrp_context_set_sv_split) or run-length encoding, without a context too; MRP_ERR_NO_DEVICE for a NULL context;
  * MRP_ERR_UNSUPPORTED for a pair whose widest diagonal exceeds 2 048 cells, raised before any pair-HMM kernel is launched (unless wide pairs are on for the context, mrp_context_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS) (and
  * MRP_ERR_ARG there for a bubble of more than 65 535 alleles, as the string call).  On an error nothing is returned.  Parameters
  * outside the resident range take the per-chunk path as in the string call (stats->chunks.phase.resident = 0).  stats may be NULL. */
@@ -1030,7 +1056,7 @@ typedef struct mrp_phase_aligned_filtered_stats {
  * malloc'd array (mrp_free) of the chunk's read index of every filtered read, closed by a -1.
  * Errors, in this order: MRP_ERR_ARG before the context is looked at (the extraction's checks on both variant sets -- a rest's variants
  * not ascending or outside the overlap among them; in their messages chunk n_chunks + c is the rest of chunk c --, mrp_phase_aligned_chunks'
- * own, a NULL rest / filtered_out / filtered_read_out, a gt outside the variant's alleles); MRP_ERR_UNSUPPORTED for the SV split mode or
+ * own, a NULL rest / filtered_out / filtered_read_out, a gt outside the variant's alleles); MRP_ERR_UNSUPPORTED for the SV split mode (unless the context admits it, mrp_context_set_sv_split: then the primary and the filtered variant set are split, each on its own) or
  * run-length encoding, without a context too; MRP_ERR_NO_DEVICE; MRP_ERR_UNSUPPORTED for a pair whose widest diagonal exceeds 2 048
  * cells (with a rest every substring of a bubble may be aligned unanchored, as mrp_phase_string_chunks_with_filtered states) (unless wide pairs are on for the context, mrp_context_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS).  On an
  * error nothing is returned and filtered_out is zeroed.  stats may be NULL. */
@@ -1058,7 +1084,7 @@ int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, c
  * whatever the batch size, the lanes, the devices or the hand-out.  Parameters outside the resident range take the per-chunk path
  * (stats->fallback_chunks counts those chunks).  stats as for string chunks, units_per_device in mrp_aligned_chunk_units.
  *   Errors: every chunk is checked on the caller's thread before a lane starts, in the one call's order and with its messages (the
- * rest of chunk c is "chunk n_chunks + c" in the extraction's) -- every MRP_ERR_ARG, then MRP_ERR_UNSUPPORTED for the two refused
+ * rest of chunk c is "chunk n_chunks + c" in the extraction's) -- every MRP_ERR_ARG, then MRP_ERR_UNSUPPORTED for the two refused (the SV split unless mrp_queue_set_sv_split is on)
  * extraction modes, both without a device or a queue; then MRP_ERR_NO_DEVICE for a NULL queue (n_chunks == 0 included).  Up to here
  * nothing is written, stats included.  The 2 048-cell diagonal refusal cannot be raised up front -- the lengths exist only after a
  * batch's extraction: it arrives as a lane error, like an out-of-memory or a HIP error (unless wide pairs are on for the queue, mrp_queue_set_wide_pairs: then only beyond MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS).  The *_on_devices forms make their own queue and keep the 2 048-cell refusal.  On a lane error the queue stops: remaining
@@ -1115,7 +1141,7 @@ int mrp_phase_aligned_chunks_with_filtered_on_devices(const int32_t *devices, in
  *   Errors: every chunk is checked on the caller's thread before a lane starts, in the one call's order and with its messages, the chunk
  * indices the caller's -- every MRP_ERR_ARG (the extraction's own checks; a NULL model, gt or hap_out; a NULL hap_out[c], h1_out[c] or
  * h2_out[c] for a chunk with reads; a NULL gt[c] for a chunk with variants; a genotype outside its variant's alleles; an odd or
- * negative expansion; a bad n_chunks), then MRP_ERR_UNSUPPORTED for the two refused extraction modes, both without a queue or a
+ * negative expansion; a bad n_chunks), then MRP_ERR_UNSUPPORTED for the two refused extraction modes (the SV split unless mrp_queue_set_sv_split is on), both without a queue or a
  * device; then MRP_ERR_NO_DEVICE for a NULL queue (n_chunks == 0 included).  Up to here nothing is written, stats included.  The
  * *_on_devices form runs these checks, then mrp_queue_create reports its own error (a device that does not exist: MRP_ERR_ARG), then
  * the call runs and the queue is destroyed.  The 2 048-cell diagonal refusal is known only after a batch's extraction: it is raised

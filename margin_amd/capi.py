@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "mrp_queue_phase_aligned_chunks_with_filtered", "mrp_phase_aligned_chunks_on_devices", "mrp_phase_aligned_chunks_with_filtered_on_devices",
     "mrp_haplotag_chunk_units", "mrp_queue_haplotag_aligned_chunks", "mrp_haplotag_aligned_chunks_on_devices",
     "mrp_context_set_wide_pairs", "mrp_context_wide_pair_count", "mrp_queue_set_wide_pairs", "mrp_queue_wide_pair_count", "mrp_pair_diagonal_width",
+    "mrp_context_set_sv_split", "mrp_queue_set_sv_split", "mrp_mark_structural_variants",
 ]
 
 
@@ -394,6 +395,9 @@ def load():
     L.mrp_context_wide_pair_count.argtypes = [vp, P(i64), P(i64)]
     L.mrp_queue_set_wide_pairs.argtypes = [vp, C.c_int]
     L.mrp_queue_wide_pair_count.argtypes = [vp, P(i64), P(i64)]
+    L.mrp_context_set_sv_split.argtypes = [vp, C.c_int]
+    L.mrp_queue_set_sv_split.argtypes = [vp, C.c_int]
+    L.mrp_mark_structural_variants.argtypes = [P(AlignedChunk), i64, vp]
     L.mrp_forward_probabilities.argtypes = [vp, vp, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, P(PairHmmStats)]
     L.mrp_allele_read_supports.argtypes = [vp, P(PairHmm), P(PairHmm), i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, P(PairHmmStats)]
     L.mrp_partition_reads_by_haplotype.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, i64, vp, vp, vp, P(PairHmmStats)]
@@ -478,6 +482,10 @@ class Context:
     def set_wide_pairs(self, on):
         """mrp_context_set_wide_pairs: pairs whose widest diagonal exceeds 2 048 cells are aligned, not refused (up to WIDE_MAX_WIDTH / WIDE_MAX_CELLS)"""
         _check(load().mrp_context_set_wide_pairs(self.h, int(bool(on))))
+
+    def set_sv_split(self, on):
+        """mrp_context_set_sv_split: indel_size_for_sv_handling > 0 runs the extraction's walk per class of variant (small, structural), not refused"""
+        _check(load().mrp_context_set_sv_split(self.h, int(bool(on))))
 
     def wide_pair_count(self):
         """mrp_context_wide_pair_count -> (pairs, dp cells) the wide kernel has taken on this context"""
@@ -911,6 +919,10 @@ class Queue:
     def set_wide_pairs(self, on):
         """mrp_queue_set_wide_pairs: Context.set_wide_pairs for every lane's context and the queue's up-front checks"""
         _check(load().mrp_queue_set_wide_pairs(self.h, int(bool(on))))
+
+    def set_sv_split(self, on):
+        """mrp_queue_set_sv_split: Context.set_sv_split for every lane's context and the queue's up-front mode check"""
+        _check(load().mrp_queue_set_sv_split(self.h, int(bool(on))))
 
     def wide_pair_count(self):
         """mrp_queue_wide_pair_count -> (pairs, dp cells), summed over the lanes"""
@@ -1577,6 +1589,14 @@ def aligned_chunk_struct(chunk):
                      ptr(keep["pos"]), ptr(keep["flag"]), ptr(keep["mapq"]), ptr(keep["l_qseq"]), keep["cigar_first"].ctypes.data,
                      ptr(keep["cigar"]), keep["seq_first"].ctypes.data, ptr(keep["seq"]))
     return S, keep
+
+
+def mark_structural_variants(chunk, indel_size: int, struct=None) -> np.ndarray:
+    """mrp_mark_structural_variants -> is_sv [n_variants] (uint8): any allele longer than indel_size; none for indel_size <= 0"""
+    S, keep = struct if struct is not None else aligned_chunk_struct(chunk)
+    out = np.zeros(int(S.n_variants), np.uint8)
+    _check(load().mrp_mark_structural_variants(C.byref(S), int(indel_size), out.ctypes.data if out.size else None))
+    return out
 
 
 def extract_read_substrings(ctx: Optional[Context], chunks, options: Optional[dict] = None, structs=None):

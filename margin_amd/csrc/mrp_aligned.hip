@@ -214,7 +214,7 @@ struct HaRun : AlignedFront {
         if (s) (void) hipStreamSynchronize(s); /* before the pinned result buffer goes */
     }
     int check(const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
-              int8_t *const *hap_out, double *const *h1_out, double *const *h2_out);
+              int8_t *const *hap_out, double *const *h1_out, double *const *h2_out, int sv_split);
     int pairs();
     int score(const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion);
     int hand_over(int8_t *const *hap_out, double *const *h1_out, double *const *h2_out);
@@ -232,9 +232,9 @@ int AlignedFront::check_front(const mrp_extract_options *options, mrp_extract_st
     return MRP_OK;
 }
 
-/* every MRP_ERR_ARG of the call, then the two refused modes: nothing here looks at the context */
+/* every MRP_ERR_ARG of the call, then the two refused modes: nothing here looks at the context (sv_split: its setting, 0 for none) */
 int HaRun::check(const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
-                 int8_t *const *hap_out, double *const *h1_out, double *const *h2_out) {
+                 int8_t *const *hap_out, double *const *h1_out, double *const *h2_out, int sv_split) {
     const int rc = check_front(options, stats ? &stats->extract : nullptr, !forward_model || !reverse_model || (n_chunks > 0 && (!gt || !hap_out)), expansion);
     if (rc != MRP_OK) return rc;
     for (int64_t c = 0; c < n_chunks; c++) {
@@ -250,7 +250,7 @@ int HaRun::check(const mrp_extract_options *options, const mrp_pair_hmm *forward
                                          gt[c][2 * v + w], (long long) k);
         }
     }
-    return mrp_extract_run_check_modes(X);
+    return mrp_extract_run_check_modes(X, sv_split);
 }
 
 /* the extraction up to its second half, gathering behind the allele strings in the call's one device pool */
@@ -450,7 +450,7 @@ int mrp_haplotag_front_create(const mrp_haplotag_args *a, mrp_haplotag_aligned_s
     *front_out = nullptr;
     mrp_haplotag_front *A = new (std::nothrow) mrp_haplotag_front(*a, stats);
     if (!A) return mrp_set_error(MRP_ERR_NOMEM, "mrp_haplotag_aligned_chunks: out of host memory");
-    const int rc = A->R.check(a->options, a->forward_model, a->reverse_model, a->expansion, a->hap_out, a->h1_out, a->h2_out);
+    const int rc = A->R.check(a->options, a->forward_model, a->reverse_model, a->expansion, a->hap_out, a->h1_out, a->h2_out, a->sv_split);
     if (rc != MRP_OK) {
         delete A;
         return rc;
@@ -493,7 +493,8 @@ extern "C" int mrp_haplotag_aligned_chunks(mrp_context *ctx, int64_t n_chunks, c
                                            mrp_haplotag_aligned_stats *stats) {
     const double t_begin = now_ms();
     if (stats) memset(stats, 0, sizeof(*stats));
-    const mrp_haplotag_args a{n_chunks, chunks, gt, options, forward_model, reverse_model, expansion, hap_out, h1_out, h2_out};
+    const mrp_haplotag_args a{n_chunks, chunks, gt, options, forward_model, reverse_model, expansion, hap_out, h1_out, h2_out,
+                              ctx ? ctx->sv_split : 0}; /* (a NULL context counts as off) */
     mrp_haplotag_front *A = nullptr;
     int rc = mrp_haplotag_front_create(&a, stats, &A);
     if (rc == MRP_OK) rc = mrp_haplotag_front_stage(ctx, A);
@@ -538,7 +539,7 @@ struct PaRun : AlignedFront {
         for (int64_t *p : bv_out) free(p);
     }
     int check(const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
-              const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out);
+              const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, int sv_split);
     int masked_owners();
     int strings_and_pairs(int64_t sv_threshold);
     int anchors();
@@ -547,9 +548,9 @@ struct PaRun : AlignedFront {
 };
 
 /* every MRP_ERR_ARG of the call (the extraction's, then the string call's parameter checks), then the two refused modes: nothing
- * here looks at the context */
+ * here looks at the context (sv_split: its setting, 0 for none) */
 int PaRun::check(const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
-                 const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out) {
+                 const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, int sv_split) {
     const int rc = check_front(options, stats ? &stats->extract : nullptr,
                                !forward_model || !reverse_model || !params || (n_chunks > 0 && (!out || !hap_out || !read_names)), expansion);
     if (rc != MRP_OK) return rc;
@@ -561,7 +562,7 @@ int PaRun::check(const mrp_extract_options *options, const mrp_pair_hmm *forward
         for (int64_t r = 0; r < C.n_reads; r++)
             if (!read_names[c][r]) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: read %lld has no name", who, (long long) c, (long long) r);
     }
-    return mrp_extract_run_check_modes(X);
+    return mrp_extract_run_check_modes(X, sv_split);
 }
 
 /* the owners among the kept reads the caller's mask lets through (one byte per read of the call; no mask anywhere: none uploaded) */
@@ -952,7 +953,7 @@ int mrp_aligned_front_create(const char *who, double t_begin, const mrp_aligned_
     *front_out = nullptr;
     mrp_aligned_front *A = new (std::nothrow) mrp_aligned_front(who, t_begin, *a, stats, fstats);
     if (!A) return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
-    int rc = A->R.check(a->options, a->forward_model, a->reverse_model, a->expansion, a->params, a->out, a->hap_out, a->phred_out);
+    int rc = A->R.check(a->options, a->forward_model, a->reverse_model, a->expansion, a->params, a->out, a->hap_out, a->phred_out, a->sv_split);
     if (a->rest && (rc == MRP_OK || rc == MRP_ERR_UNSUPPORTED)) {
         const int rc2 = A->R.check_rest();
         if (rc2 != MRP_OK) rc = rc2;
@@ -1074,7 +1075,8 @@ extern "C" int mrp_phase_aligned_chunks(mrp_context *ctx, int64_t n_chunks, cons
     const double t_begin = now_ms();
     if (stats) memset(stats, 0, sizeof(*stats));
     const mrp_aligned_args a{n_chunks, chunks, nullptr, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
-                             het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr};
+                             het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr,
+                             ctx ? ctx->sv_split : 0}; /* (a NULL context counts as off) */
     return pa_phase_chunks("mrp_phase_aligned_chunks", t_begin, ctx, a, stats, nullptr);
 }
 
@@ -1093,6 +1095,6 @@ extern "C" int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t 
     if (n_chunks > 0) memset(filtered_out, 0, sizeof(*filtered_out) * (size_t) n_chunks);
     const mrp_aligned_args a{n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
-                             filtered_read_out};
+                             filtered_read_out, ctx ? ctx->sv_split : 0};
     return pa_phase_chunks(who, t_begin, ctx, a, stats ? &stats->aligned : nullptr, stats);
 }

@@ -168,6 +168,12 @@ int mrp_context_set_test_hooks(mrp_context *ctx, int hooks) {
     return MRP_OK;
 }
 int mrp_context_test_hooks(const mrp_context *ctx) { return ctx->test_hooks; }
+int mrp_context_set_sv_split(mrp_context *ctx, int on) {
+    if (!ctx) return mrp_set_error(MRP_ERR_ARG, "mrp_context_set_sv_split: context is NULL");
+    ctx->sv_split = on != 0;
+    return MRP_OK;
+}
+
 int mrp_context_set_wide_pairs(mrp_context *ctx, int on) {
     if (!ctx) return mrp_set_error(MRP_ERR_ARG, "mrp_context_set_wide_pairs: context is NULL");
     ctx->wide_pairs = on != 0;

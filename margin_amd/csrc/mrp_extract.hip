@@ -19,6 +19,12 @@
  *                      does not depend on the order of the atomics;
  *   ex_gather_kernel   a wave per substring: read bases (seq_nt16_str codes) to symbols into the output pool.
  *
+ * With indelSizeForSVHandling > 0 (on a context that admits it, mrp_context_set_sv_split) the reference makes the walk twice, over the
+ * small entries and over the structural ones, and merges the two per read (:1725-1755).  Here the entries are staged class-major and
+ * the scan and locate kernels are instantiated for two classes: a first-entry search and a running maximum per class, one count and
+ * one run of write offsets per read over both; an entry carries its original index, so the sort gives the caller's variant order
+ * (DESIGN.md section 9.11).  Without the split the one-class instantiations run: the launches and the bytes of before.
+ *
  * The windows are computed on the host while checking the arguments; the allele strings on the worker pool while the
  * device runs.  One total (the substrings and their bases) comes back between the two halves to size the buffers.
  *
@@ -61,8 +67,13 @@ struct ExChunk {
     int64_t ovl, cs, ce;
     int64_t var0; /* first variant of the chunk in the call */
     int64_t n_var;
+    /* the two classes of the split walk (indelSizeForSVHandling > 0, :1725-1755): records [0, n_small) are the chunk's small variants,
+     * [n_small, n_var) its structural ones; without the split one class holds everything (n_small = n_var) */
+    int64_t n_small;
 };
 
+/* staged in the caller's order -- or, for the split walk, class-major (small ascending, then structural ascending) beside a table of
+ * every record's original index in the call */
 struct ExVar {
     int64_t pos;          /* 0-based genome */
     int64_t start, stop;  /* refAlnStart / refAlnStopIncl, 0-based in the overlap slice */
@@ -78,8 +89,8 @@ struct ExState {
     int64_t limit;       /* alnReadLength + 1 reference steps at most (:1901) */
     int64_t tot_ref, tot_seq;
     int32_t clip;        /* start soft clip */
-    int32_t var_first;   /* global index of the first entry at or after the read */
-    int32_t s1, r1;      /* sequence / reference advance of the first step */
+    int32_t var_first[2]; /* per class: record of the call's first entry at or after the read (the class's end: none) */
+    int16_t s1, r1;      /* sequence / reference advance of the first step */
 };
 
 struct ExOp {
@@ -118,6 +129,8 @@ __device__ inline int64_t wave_sum(int64_t v) {
     return v;
 }
 
+/* NCLS: 1, or 2 for the split walk -- one first-entry search per class (each walk's own, :1852-1855) */
+template <int NCLS>
 __global__ __launch_bounds__(64) void ex_scan_kernel(const ExRead *__restrict__ reads, const uint32_t *__restrict__ cigar,
                                                      const ExChunk *__restrict__ chunks, const ExVar *__restrict__ vars, ExOpt o,
                                                      ExOp *__restrict__ ops, ExState *__restrict__ state, uint8_t *__restrict__ status) {
@@ -173,13 +186,21 @@ __global__ __launch_bounds__(64) void ex_scan_kernel(const ExRead *__restrict__ 
         return;
     }
     /* binarySearchVcfListForFirstIndexAtOrAfterRefPos on refPos = pos - overlap + 1: the first entry with pos >= read pos */
-    int64_t lo = 0, hi = ch.n_var;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) / 2;
-        if (vars[ch.var0 + mid].pos < rd.pos) lo = mid + 1;
-        else hi = mid;
+    int32_t first[2] = {0, 0};
+    bool listed = false;
+#pragma unroll
+    for (int c = 0; c < NCLS; c++) {
+        const int64_t end = (c == NCLS - 1) ? ch.n_var : ch.n_small;
+        int64_t lo = c ? ch.n_small : 0, hi = end;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) / 2;
+            if (vars[ch.var0 + mid].pos < rd.pos) lo = mid + 1;
+            else hi = mid;
+        }
+        first[c] = (int32_t) (ch.var0 + lo);
+        listed = listed || lo < end;
     }
-    if (lo == ch.n_var) { /* :1855 all entries before the read: not listed */
+    if (!listed) { /* :1855 all entries before the read: not listed (split: by neither walk) */
         if (lane == 0) status[r] = st;
         return;
     }
@@ -191,7 +212,8 @@ __global__ __launch_bounds__(64) void ex_scan_kernel(const ExRead *__restrict__ 
         s.tot_ref = cr;
         s.tot_seq = cs;
         s.clip = (int32_t) clip;
-        s.var_first = (int32_t) (ch.var0 + lo);
+        s.var_first[0] = first[0];
+        s.var_first[1] = first[1];
         s.s1 = ex_seq_op(op0) ? 1 : 0;
         s.r1 = ex_ref_op(op0) ? 1 : 0;
         state[r] = s;
@@ -211,11 +233,13 @@ __device__ inline int64_t ex_seq_after(const ExOp *__restrict__ op, int n, int64
     return (int64_t) o.sb + (ex_seq_op(o.word & 15u) ? t - o.rb : 0);
 }
 
-template <bool WRITE>
+/* NCLS: 1, or 2 for the split walk -- one pass per class, each with its own running maximum; vorig (NCLS == 2): a record's original
+ * index in the call, which the entry carries, so that the sort and the gather below see the caller's variant order */
+template <bool WRITE, int NCLS>
 __global__ __launch_bounds__(64) void ex_locate_kernel(const ExRead *__restrict__ reads, const uint8_t *__restrict__ status,
                                                        const ExState *__restrict__ state, const ExOp *__restrict__ ops,
                                                        const ExChunk *__restrict__ chunks, const ExVar *__restrict__ vars,
-                                                       int64_t *__restrict__ count, unsigned long long *__restrict__ total_bases,
+                                                       const int32_t *__restrict__ vorig, int64_t *__restrict__ count, unsigned long long *__restrict__ total_bases,
                                                        const int64_t *__restrict__ entry_off, ExEntry *__restrict__ entries) {
     const int64_t r = blockIdx.x;
     const int lane = threadIdx.x;
@@ -231,44 +255,48 @@ __global__ __launch_bounds__(64) void ex_locate_kernel(const ExRead *__restrict_
     const bool cut = s.tot_ref >= s.limit; /* the loop bound ends the walk before the CIGAR does */
     const int64_t r0 = s.r0, r_end = r0 + (cut ? s.limit : s.tot_ref);
     const int64_t seq_end = cut ? ex_seq_after(op, n, s.limit) : s.tot_seq;
-    const int64_t vend = ch.var0 + ch.n_var;
-    int64_t run_max = LLONG_MIN, kept = 0, bases = 0;
-    for (int64_t j0 = s.var_first; j0 < vend; j0 += EX_WAVE) {
-        const int64_t j = j0 + lane;
-        const bool in = j < vend;
-        ExVar v{0, LLONG_MAX, 0};
-        if (in) v = vars[j];
-        const int64_t m = max(run_max, wave_incl_max(v.start)); /* the entry starts once every earlier one has */
-        const bool cand = in && m <= r_end;
-        bool keep = false;
-        int64_t ss = 0, len = 0;
-        if (cand) {
-            const bool pre = m <= r0 && s.clip == 0; /* started before the first step (:1895-1899), checked after it */
-            int64_t rs;
-            if (m <= r0) { rs = r0; ss = 0; }
-            else { rs = m; ss = ex_seq_after(op, n, m - r0); }
-            bool decided = false;
-            if (pre && v.stop <= r0 + s.r1) { len = s.s1; keep = len != 0; decided = true; }
-            else if (!pre && v.stop <= rs) { decided = true; } /* finished in the step that started it: no base */
-            if (!decided) {
-                if (v.stop <= r_end) {
-                    len = ex_seq_after(op, n, v.stop - r0) - ss;
-                    keep = len != 0;
-                } else { /* open at the end of the read (:1961-1962) */
-                    len = seq_end - ss;
-                    keep = len != 0 && !(r_end < v.pos - ch.ovl + 1);
+    int64_t kept = 0, bases = 0;
+#pragma unroll
+    for (int c = 0; c < NCLS; c++) {
+        const int64_t vend = ch.var0 + ((c == NCLS - 1) ? ch.n_var : ch.n_small);
+        int64_t run_max = LLONG_MIN;
+        for (int64_t j0 = s.var_first[c]; j0 < vend; j0 += EX_WAVE) {
+            const int64_t j = j0 + lane;
+            const bool in = j < vend;
+            ExVar v{0, LLONG_MAX, 0};
+            if (in) v = vars[j];
+            const int64_t m = max(run_max, wave_incl_max(v.start)); /* the entry starts once every earlier one has */
+            const bool cand = in && m <= r_end;
+            bool keep = false;
+            int64_t ss = 0, len = 0;
+            if (cand) {
+                const bool pre = m <= r0 && s.clip == 0; /* started before the first step (:1895-1899), checked after it */
+                int64_t rs;
+                if (m <= r0) { rs = r0; ss = 0; }
+                else { rs = m; ss = ex_seq_after(op, n, m - r0); }
+                bool decided = false;
+                if (pre && v.stop <= r0 + s.r1) { len = s.s1; keep = len != 0; decided = true; }
+                else if (!pre && v.stop <= rs) { decided = true; } /* finished in the step that started it: no base */
+                if (!decided) {
+                    if (v.stop <= r_end) {
+                        len = ex_seq_after(op, n, v.stop - r0) - ss;
+                        keep = len != 0;
+                    } else { /* open at the end of the read (:1961-1962) */
+                        len = seq_end - ss;
+                        keep = len != 0 && !(r_end < v.pos - ch.ovl + 1);
+                    }
                 }
             }
+            const uint64_t kb = __ballot(keep);
+            if (WRITE && keep) {
+                const int rank = __popcll(kb & ((1ull << lane) - 1ull));
+                entries[entry_off[r] + kept + rank] = ExEntry{rd.seq_nib + s.clip + ss, NCLS == 2 ? vorig[j] : (int32_t) j, (int32_t) r, (int32_t) len, 0};
+            }
+            kept += __popcll(kb);
+            bases += wave_sum(keep ? len : 0);
+            run_max = __shfl(m, EX_WAVE - 1, EX_WAVE);
+            if (__ballot(!cand)) break; /* the running maximum only grows: no later entry starts either */
         }
-        const uint64_t kb = __ballot(keep);
-        if (WRITE && keep) {
-            const int rank = __popcll(kb & ((1ull << lane) - 1ull));
-            entries[entry_off[r] + kept + rank] = ExEntry{rd.seq_nib + s.clip + ss, (int32_t) j, (int32_t) r, (int32_t) len, 0};
-        }
-        kept += __popcll(kb);
-        bases += wave_sum(keep ? len : 0);
-        run_max = __shfl(m, EX_WAVE - 1, EX_WAVE);
-        if (__ballot(!cand)) break; /* the running maximum only grows: no later entry starts either */
     }
     if (!WRITE && lane == 0) {
         count[r] = kept;
@@ -482,7 +510,8 @@ struct mrp_extract_run {
     std::vector<int64_t> aligned;
     std::vector<int64_t> rb, vb, cb, sb; /* n_chunks + 1: chunk c's share of the call's reads, variants, CIGAR words, packed bases */
     int64_t n_reads = 0, n_var = 0, n_ops = 0, n_seq = 0, n_ent = 0, n_bases = 0;
-    size_t o_cig = 0, o_read = 0, o_chunk = 0, o_var = 0, o_seq = 0, in_bytes = 0;
+    size_t o_cig = 0, o_read = 0, o_chunk = 0, o_var = 0, o_vorig = 0, o_seq = 0, in_bytes = 0;
+    bool split = false; /* check_modes: the walk runs per class of variant (indelSizeForSVHandling > 0 on a context that admits it) */
     mrp_context *ctx = nullptr;
     hipStream_t s = nullptr; /* set once the device is current: from then on the destructor drains it */
     DevBuf<uint8_t> d_in, d_status, d_pool;
@@ -534,8 +563,10 @@ int mrp_extract_run_check_args(mrp_extract_run *R, bool have_out) {
     return MRP_OK;
 }
 
-int mrp_extract_run_check_modes(mrp_extract_run *R) {
-    if (R->o.indel_size_for_sv_handling != 0)
+int mrp_extract_run_check_modes(mrp_extract_run *R, int sv_split) {
+    /* only the sign is read: the threshold was applied when is_sv was made (mrp_mark_structural_variants) */
+    R->split = sv_split && R->o.indel_size_for_sv_handling > 0;
+    if (R->o.indel_size_for_sv_handling != 0 && !R->split)
         return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: indelSizeForSVHandling > 0 (htsIntegration.c:1724-1755) is not supported", R->who);
     if (R->o.use_run_length_encoding != 0) return mrp_set_error(MRP_ERR_UNSUPPORTED, "%s: run-length encoding is not supported", R->who);
     return MRP_OK;
@@ -576,6 +607,8 @@ int mrp_extract_run_stage(mrp_extract_run *R, mrp_context *ctx) {
     const size_t o_read = R->o_read = at; at = ex_align<ExChunk>(at + sizeof(ExRead) * (size_t) n_reads);
     const size_t o_chunk = R->o_chunk = at; at = ex_align<ExVar>(at + sizeof(ExChunk) * (size_t) n_chunks);
     const size_t o_var = R->o_var = at; at += sizeof(ExVar) * (size_t) n_var;
+    const bool split = R->split;
+    const size_t o_vorig = R->o_vorig = at; at += split ? sizeof(int32_t) * (size_t) n_var : 0; /* (then bytes: no alignment to keep) */
     const size_t o_seq = R->o_seq = at; at += (size_t) n_seq;
     const size_t in_bytes = R->in_bytes = at;
 
@@ -591,9 +624,24 @@ int mrp_extract_run_stage(mrp_extract_run *R, mrp_context *ctx) {
     const std::vector<std::vector<ExWindow>> &win = R->win;
     mrp_parallel_for(n_chunks, 1, [&](int64_t c) {
         const mrp_aligned_chunk &C = chunks[c];
-        hch[c] = ExChunk{C.overlap_start, C.chunk_start, C.chunk_end, vb[(size_t) c], C.n_variants};
         ExVar *hv = (ExVar *) (hin + o_var) + vb[(size_t) c];
-        for (int64_t v = 0; v < C.n_variants; v++) hv[v] = ExVar{C.variant_pos[v], win[(size_t) c][(size_t) v].start, win[(size_t) c][(size_t) v].stop};
+        int64_t n_small = C.n_variants;
+        if (!split) {
+            for (int64_t v = 0; v < C.n_variants; v++) hv[v] = ExVar{C.variant_pos[v], win[(size_t) c][(size_t) v].start, win[(size_t) c][(size_t) v].stop};
+        } else { /* class-major, each class ascending as the caller's list is (:1727-1732) */
+            int32_t *ho = (int32_t *) (hin + o_vorig) + vb[(size_t) c];
+            int64_t k = 0;
+            for (int cls = 0; cls < 2; cls++) {
+                for (int64_t v = 0; v < C.n_variants; v++) {
+                    if ((C.is_sv[v] != 0) != (cls != 0)) continue;
+                    hv[k] = ExVar{C.variant_pos[v], win[(size_t) c][(size_t) v].start, win[(size_t) c][(size_t) v].stop};
+                    ho[k] = (int32_t) (vb[(size_t) c] + v);
+                    k++;
+                }
+                if (cls == 0) n_small = k;
+            }
+        }
+        hch[c] = ExChunk{C.overlap_start, C.chunk_start, C.chunk_end, vb[(size_t) c], C.n_variants, n_small};
         ExRead *hr = (ExRead *) (hin + o_read) + rb[(size_t) c];
         for (int64_t r = 0; r < C.n_reads; r++) {
             ExRead &x = hr[r];
@@ -638,10 +686,14 @@ int mrp_extract_run_first_half(mrp_extract_run *R) {
     EX_HIP(hipEventRecord(R->ev[0], s));
     EX_HIP(hipMemsetAsync(R->d_tot.p, 0, sizeof(unsigned long long), s));
     if (n_reads > 0) {
-        hipLaunchKernelGGL(ex_scan_kernel, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, g_cig, g_chunk, g_var, eo, R->d_ops.p, R->d_state.p, R->d_status.p);
+        const int32_t *g_vorig = R->split ? (const int32_t *) (R->d_in.p + R->o_vorig) : nullptr;
+        const auto scan = R->split ? ex_scan_kernel<2> : ex_scan_kernel<1>;
+        const auto locate = R->split ? ex_locate_kernel<false, 2> : ex_locate_kernel<false, 1>;
+        hipLaunchKernelGGL(scan, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, g_cig, g_chunk, g_var, eo,
+                           R->d_ops.p, R->d_state.p, R->d_status.p);
         EX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(ex_locate_kernel<false>, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, R->d_status.p, R->d_state.p, R->d_ops.p, g_chunk, g_var,
-                           R->d_count.p, R->d_tot.p, (const int64_t *) nullptr, (ExEntry *) nullptr);
+        hipLaunchKernelGGL(locate, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, R->d_status.p,
+                           R->d_state.p, R->d_ops.p, g_chunk, g_var, g_vorig, R->d_count.p, R->d_tot.p, (const int64_t *) nullptr, (ExEntry *) nullptr);
         EX_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(ex_scan_i64, dim3(1), dim3(1024), 0, s, R->d_count.p, n_reads, R->d_eoff.p);
@@ -722,8 +774,10 @@ int mrp_extract_run_second_half(mrp_extract_run *R, uint8_t *pool, int64_t base)
         EX_HIP(hipMemsetAsync(R->d_vfill.p, 0, sizeof(int64_t) * (size_t) n_var, s));
     }
     if (n_ent > 0) {
-        hipLaunchKernelGGL(ex_locate_kernel<true>, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, R->d_status.p, R->d_state.p, R->d_ops.p, g_chunk, g_var,
-                           (int64_t *) nullptr, (unsigned long long *) nullptr, R->d_eoff.p, R->d_entries.p);
+        const int32_t *g_vorig = R->split ? (const int32_t *) (R->d_in.p + R->o_vorig) : nullptr;
+        const auto locate = R->split ? ex_locate_kernel<true, 2> : ex_locate_kernel<true, 1>;
+        hipLaunchKernelGGL(locate, dim3((unsigned) n_reads), dim3(EX_WAVE), 0, s, g_read, R->d_status.p,
+                           R->d_state.p, R->d_ops.p, g_chunk, g_var, g_vorig, (int64_t *) nullptr, (unsigned long long *) nullptr, R->d_eoff.p, R->d_entries.p);
         EX_HIP(hipGetLastError());
         const unsigned blocks = (unsigned) ((n_ent + 255) / 256);
         hipLaunchKernelGGL(ex_var_count_kernel, dim3(blocks), dim3(256), 0, s, R->d_entries.p, n_ent, (unsigned long long *) R->d_vcnt.p);
@@ -915,12 +969,27 @@ void mrp_extract_run_times(mrp_extract_run *R, bool to_now) {
 
 extern "C" {
 
+/* vcf.c:173-185: an entry is structural if any of its alleles is longer than indelSizeForSVHandling, and none is at a threshold <= 0 */
+int mrp_mark_structural_variants(const mrp_aligned_chunk *chunk, int64_t indel_size, uint8_t *is_sv_out) {
+    static const char *who = "mrp_mark_structural_variants";
+    if (!chunk || chunk->n_variants < 0 || (chunk->n_variants > 0 && (!is_sv_out || !chunk->allele_first || !chunk->allele_len)))
+        return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
+    for (int64_t v = 0; v < chunk->n_variants; v++) {
+        if (chunk->allele_first[v] < 0 || chunk->allele_first[v + 1] < chunk->allele_first[v])
+            return mrp_set_error(MRP_ERR_ARG, "%s: allele offsets not ascending at variant %lld", who, (long long) v);
+        uint8_t sv = 0;
+        for (int64_t a = chunk->allele_first[v]; a < chunk->allele_first[v + 1]; a++) sv |= indel_size > 0 && (int64_t) chunk->allele_len[a] > indel_size;
+        is_sv_out[v] = sv;
+    }
+    return MRP_OK;
+}
+
 int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_extract_options *options,
                                 mrp_extracted_chunk **out, mrp_extract_stats *stats) {
     mrp_extract_run run("mrp_extract_read_substrings", n_chunks, chunks, options, stats);
     mrp_extract_run *R = &run;
     int rc = mrp_extract_run_check_args(R, out != nullptr);
-    if (rc == MRP_OK) rc = mrp_extract_run_check_modes(R);
+    if (rc == MRP_OK) rc = mrp_extract_run_check_modes(R, ctx ? ctx->sv_split : 0); /* (a NULL context counts as off) */
     if (rc == MRP_OK) rc = mrp_extract_run_check_chunks(R);
     if (rc != MRP_OK) return rc;
     if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the extraction has no CPU fallback)", R->who);

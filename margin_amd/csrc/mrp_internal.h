@@ -368,6 +368,7 @@ struct mrp_context {
     DevPool pool;
     int test_hooks = 0;   /* mrp_context_set_test_hooks (test suite only) */
     int wide_pairs = 0;   /* mrp_context_set_wide_pairs: pairs beyond the pair-per-wave kernel's 2 048 cells go to the pair-per-workgroup kernel */
+    int sv_split = 0;     /* mrp_context_set_sv_split: indel_size_for_sv_handling > 0 splits the extraction's walk by class of variant */
     int64_t wide_pair_count = 0, wide_cell_count = 0; /* what that kernel has taken on this context (mrp_context_wide_pair_count) */
     int phase_groups = 0; /* concurrent batches of mrp_phase_reads_many (mrp_context_set_phase_groups); 0: chosen by batch size */
     std::vector<mrp_context *> siblings; /* further contexts on the same device (concurrent batches of mrp_phase_reads_many) */
@@ -597,7 +598,9 @@ mrp_extract_run *mrp_extract_run_create(const char *who, int64_t n_chunks, const
                                         mrp_extract_stats *stats);
 void mrp_extract_run_destroy(mrp_extract_run *run);
 int mrp_extract_run_check_args(mrp_extract_run *run, bool have_out);
-int mrp_extract_run_check_modes(mrp_extract_run *run);
+/* sv_split: the caller's setting (a context's or a queue's; 0 for none): indel_size_for_sv_handling > 0 then runs the walk per class
+ * of variant instead of being refused */
+int mrp_extract_run_check_modes(mrp_extract_run *run, int sv_split);
 int mrp_extract_run_check_chunks(mrp_extract_run *run);
 int mrp_extract_run_stage(mrp_extract_run *run, mrp_context *ctx);
 int mrp_extract_run_first_half(mrp_extract_run *run);
@@ -652,6 +655,7 @@ struct mrp_aligned_args {
     int64_t **bubble_variant_out;
     mrp_filtered_out *filtered_out;
     int32_t **filtered_read_out;
+    int sv_split; /* the context's or the queue's setting at the call (mrp_context_set_sv_split); the checks need no context */
 };
 int mrp_aligned_chunks_check(const char *who, const mrp_aligned_args *args);
 int mrp_aligned_front_create(const char *who, double t_begin_ms, const mrp_aligned_args *args, mrp_phase_aligned_stats *stats,
@@ -678,6 +682,7 @@ struct mrp_haplotag_args {
     int64_t expansion;
     int8_t *const *hap_out;
     double *const *h1_out, *const *h2_out;
+    int sv_split; /* the context's or the queue's setting at the call (mrp_context_set_sv_split); the checks need no context */
 };
 int mrp_haplotag_chunks_check(const mrp_haplotag_args *args);
 int mrp_haplotag_front_create(const mrp_haplotag_args *args, mrp_haplotag_aligned_stats *stats, mrp_haplotag_front **front_out);

@@ -242,6 +242,7 @@ struct mrp_queue {
      * queue uses one of them.  MRP_QUEUE_LANES=1..4 overrides. */
     int lanes = 4;
     int wide_pairs = 0; /* mrp_queue_set_wide_pairs: every lane's context gets it when the lane begins a call; the up-front checks read it */
+    int sv_split = 0;   /* mrp_queue_set_sv_split: likewise */
 };
 
 int mrp_queue_create(const int32_t *devices, int32_t n_devices, mrp_queue **out) {
@@ -279,6 +280,14 @@ int mrp_queue_set_wide_pairs(mrp_queue *q, int on) {
     q->wide_pairs = on != 0;
     for (mrp_context *c : q->ctx)
         if (c) (void) mrp_context_set_wide_pairs(c, q->wide_pairs);
+    return MRP_OK;
+}
+
+int mrp_queue_set_sv_split(mrp_queue *q, int on) {
+    if (!q) return mrp_set_error(MRP_ERR_ARG, "mrp_queue_set_sv_split: queue is NULL");
+    q->sv_split = on != 0;
+    for (mrp_context *c : q->ctx)
+        if (c) (void) mrp_context_set_sv_split(c, q->sv_split);
     return MRP_OK;
 }
 
@@ -368,6 +377,7 @@ struct QueueCall {
         if (r != MRP_OK) { errs[(size_t) w] = mrp_last_error(); return r; }
         if (lanes > 1) (void) mrp_context_set_grouped(q->ctx[(size_t) w], 1); /* the lanes of a device are concurrent batches of it */
         (void) mrp_context_set_wide_pairs(q->ctx[(size_t) w], q->wide_pairs);
+        (void) mrp_context_set_sv_split(q->ctx[(size_t) w], q->sv_split);
         q->ctx[(size_t) w]->calls_sharing_device = n_batches > (int64_t) n_devices ? active_lanes : 1;
         caller_pool[(size_t) w] = mrp_pool_current();
         mrp_pool_adopt(q->pools[(size_t) d]);
@@ -955,7 +965,8 @@ int mrp_queue_phase_aligned_chunks(mrp_queue *q, int64_t n_chunks, const mrp_ali
                                    double *const *phred_out, mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_queue_stats *stats) {
     const AlignedQueueArgs A{"mrp_queue_phase_aligned_chunks",
                              {n_chunks, chunks, nullptr, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
-                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr},
+                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr,
+                              q ? q->sv_split : 0}, /* (a NULL queue counts as off) */
                              chunks_per_batch, stats};
     return queue_phase_aligned_chunks(q, A, false);
 }
@@ -970,7 +981,7 @@ int mrp_queue_phase_aligned_chunks_with_filtered(mrp_queue *q, int64_t n_chunks,
     const AlignedQueueArgs A{"mrp_queue_phase_aligned_chunks_with_filtered",
                              {n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
                               het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
-                              filtered_read_out},
+                              filtered_read_out, q ? q->sv_split : 0},
                              chunks_per_batch, stats};
     return queue_phase_aligned_chunks(q, A, true);
 }
@@ -1144,7 +1155,8 @@ int mrp_queue_haplotag_aligned_chunks(mrp_queue *q, int64_t n_chunks, const mrp_
                                       const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
                                       int64_t expansion, int64_t chunks_per_batch, int8_t *const *hap_out, double *const *h1_out,
                                       double *const *h2_out, mrp_queue_stats *stats) {
-    const HaplotagQueueArgs A{{n_chunks, chunks, gt, options, forward_model, reverse_model, expansion, hap_out, h1_out, h2_out}, chunks_per_batch, stats};
+    const HaplotagQueueArgs A{{n_chunks, chunks, gt, options, forward_model, reverse_model, expansion, hap_out, h1_out, h2_out, q ? q->sv_split : 0},
+                              chunks_per_batch, stats};
     return queue_haplotag_aligned_chunks(q, A);
 }
 
