@@ -499,7 +499,7 @@ int mrp_band_diagonals(const int64_t *anchors, int64_t n_anchors, int64_t lx, in
  * on: such a pair is aligned by the pair-per-workgroup kernel, up to MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS.
  * Honoured by every entry that takes the context and scores pairs: mrp_forward_probabilities, mrp_allele_read_supports,
  * mrp_partition_reads_by_haplotype, mrp_phase_variants_from_tagged_reads, mrp_phase_string_chunks(_with_filtered),
- * mrp_haplotag_aligned_chunks, mrp_phase_aligned_chunks(_with_filtered). */
+ * mrp_haplotag_aligned_chunks, mrp_phase_aligned_chunks(_with_filtered, _with_records). */
 int mrp_context_set_wide_pairs(mrp_context *ctx, int on);
 /* pairs / dp cells the wide kernel has taken on this context since it was created (either pointer may be NULL) */
 int mrp_context_wide_pair_count(mrp_context *ctx, int64_t *pairs_out, int64_t *cells_out);
@@ -874,7 +874,7 @@ int mrp_extract_read_substrings(mrp_context *ctx, int64_t n_chunks, const mrp_al
  * lists the merged reads in the iteration order of a hash over read names, here they stay in ascending read index; the reference merges
  * by read name (at most two records a name), here by read index.
  * Honoured by mrp_extract_read_substrings, mrp_haplotag_aligned_chunks, mrp_phase_aligned_chunks and
- * mrp_phase_aligned_chunks_with_filtered (where the primary and the filtered variant set are split each on its own, phase.c:353-357). */
+ * mrp_phase_aligned_chunks_with_filtered / _with_records (where the primary and the filtered variant set are split each on its own, phase.c:353-357). */
 int mrp_context_set_sv_split(mrp_context *ctx, int on);
 /* host only, no device: isStructuralVariant as loadVcfEntries sets it (vcf.c:173-185) -- is_sv_out[v] = 1 if any allele of variant v is
  * longer than indel_size, else 0; every byte 0 for indel_size <= 0.  Reads chunk->n_variants, allele_first and allele_len only. */
@@ -1067,6 +1067,98 @@ int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, c
                                            mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
                                            int64_t **bubble_variant_out, mrp_filtered_out *filtered_out, int32_t **filtered_read_out,
                                            mrp_phase_aligned_filtered_stats *stats);
+
+/* ---- the same with what writePhasedVcf reads for every variant: the phased variant records ------------------------------------
+ * The last per-chunk statement of margin phase's chunk loop, updateOriginalVcfEntriesWithBubbleData (phase.c:446, vcf.c:511-592), and
+ * the matching update that ends bubbleGraph_phaseVcfEntriesFromHaplotaggedReads (bubbleGraph.c:2298-2343), as arrays: per variant the
+ * genotype written to the root VCF entry, its three probabilities, wasUpdated, and alleleIdxToReads -- the tagged reads under each of
+ * the two called alleles.  Sites: the chunk's (primary) variants in the caller's order, then its rest's.
+ *   A primary variant v is MRP_RECORD_UPDATED when it has a bubble b (bubble_variant, vcf.c:533), b lies inside the fragment
+ * [ref_start, ref_start + length) (the loop of :520) and variant_pos[v] lies in [chunk_start, chunk_end) (:538-540); otherwise it is
+ * MRP_RECORD_UNTOUCHED.  (A bubble has a substring by construction, bubbleGraph.c:1366-1371, so the "nothing to phase with" branch of
+ * :546-555 is never taken.)  gt = the fragment's hap1 / hap2 allele at b (:558-559); the three log values are the fragment's floats at b,
+ * bit for bit -- the caller applies fromLog / toPhred (:560-562, :882-884), no exp is evaluated here.  The listed reads are the reads of
+ * b's substrings (entryBCRs of :543: kept, and let through by keep): hap1 those with hap_out == 1, hap2 those with hap_out == 2
+ * (:572-582); a read whose tag is 0 or -1 is listed nowhere.  Only the phasing's own tags count: readsBelongingToHap1/2 are pointer sets
+ * (genomeFragment.c:237-238) and the primary reads the back half tags later are copies (phase.c:423, bubbleGraph.c:1914-1917), so the
+ * lookup of :576-578 never finds them.  A homozygous call keeps its two lists: mrp_variants_from_records unions them.
+ *   A filtered variant follows its state (mrp_filtered_out.variant_state): MRP_VARIANT_NOT_VISITED -> UNTOUCHED (gt -2, -2);
+ * MRP_VARIANT_TIE -> CLEARED: gt -1 | -1 and zero probabilities written, wasUpdated not set (bubbleGraph.c:2298-2321); MRP_VARIANT_CIS ->
+ * UPDATED with gt1, gt2; MRP_VARIANT_TRANS -> UPDATED with gt2, gt1 (:2303-2309).  The reference writes probability 0 (:2300-2302, :2314-2316):
+ * the log values of a CLEARED or UPDATED filtered record are -INFINITY.  The lists of a CIS / TRANS record hold the primary reads among
+ * the variant's entries with tag 1, and those with tag 2 (:2330-2343); hap1 always belongs to gt[0] of the record.
+ *   An UNTOUCHED record has gt -2, -2, log values 0 and no reads. */
+#define MRP_RECORD_UNTOUCHED 0 /* the reference leaves the root entry alone */
+#define MRP_RECORD_UPDATED   1 /* gt and probabilities written, wasUpdated = TRUE */
+#define MRP_RECORD_CLEARED   2 /* gt = -1 | -1 and zero probabilities written, wasUpdated not set (bubbleGraph.c:2313-2321) */
+
+typedef struct mrp_variant_records {   /* one chunk; every array malloc'd, mrp_free */
+    int64_t n_primary, n_filtered;     /* sites: the chunk's variants in the caller's order, then its rest's */
+    uint8_t *state;                    /* MRP_RECORD_* per site */
+    int32_t *gt;                       /* 2 per site: gt1, gt2 as written to the root entry; untouched: -2, -2 */
+    float *genotype_log_prob, *hap1_log_prob, *hap2_log_prob; /* LOG values, see above */
+    int64_t *read_first;               /* n_sites + 1, from 0 */
+    int32_t *n_hap1, *n_hap2;          /* read_first[v+1] - read_first[v] == n_hap1[v] + n_hap2[v] */
+    int32_t *reads;                    /* the chunk's read indices: the site's hap1 reads ascending, then its hap2 reads ascending */
+} mrp_variant_records;
+
+/* The records of one chunk, host only: what a caller who chains the single calls gets from their outputs.  x / xf: the extractions over
+ * the chunk's variants and over its rest's (the same reads); keep: the caller's mask (NULL: every read); bubble_variant / n_bubbles: from
+ * mrp_string_chunk_from_extracted(x, keep, ...); result / hap_out (x->n_reads entries): the chunk's phasing and HP tags; variant_pos
+ * (x->n_variants) and fvariant_pos (xf->n_variants): 0-based genome positions; gt (2 per filtered variant) and variant_state: the rest's
+ * genotypes and mrp_filtered_out.variant_state.  A filtered variant outside [chunk_start, chunk_end) lists no reads (bubbleGraph.c:2179).
+ * MRP_ERR_ARG: a NULL argument (keep excepted), extractions over different read counts, a bubble_variant or an entry's read out of range,
+ * a fragment that leaves the bubbles, a fragment allele the variant lacks, a gt outside the variant's alleles, a state outside 0..3.
+ * Nothing is written on error. */
+int mrp_variant_records_from_extracted(const mrp_extracted_chunk *x, const mrp_extracted_chunk *xf, const uint8_t *keep,
+                                       const int64_t *bubble_variant, int64_t n_bubbles, const mrp_phase_result *result, const int8_t *hap_out,
+                                       const int64_t *variant_pos, const int64_t *fvariant_pos, int64_t chunk_start, int64_t chunk_end,
+                                       const int32_t *gt, const int32_t *variant_state, mrp_variant_records *out);
+
+typedef struct mrp_phase_aligned_records_stats {
+    mrp_phase_aligned_filtered_stats filtered; /* as mrp_phase_aligned_chunks_with_filtered fills it */
+    int64_t records_sites;            /* sites of the call: the variants of both sets */
+    int64_t records_updated;          /* of these, MRP_RECORD_UPDATED */
+    int64_t reads_listed;             /* reads in the lists of the call */
+    int64_t records_bytes_downloaded; /* what came back for the records: 20 B per site (state, gt, the two counts) and 4 B per list slot -- a
+                                       * slot per entry of a primary read at the site, the hap1 reads from the front, the hap2 reads from the back */
+    double records_ms;                /* the records kernel, HIP events */
+} mrp_phase_aligned_records_stats;
+
+/* mrp_phase_aligned_chunks_with_filtered plus records_out[n_chunks] (zeroed on an error): every other output is what that call returns,
+ * and records_out[c] is, array for array, what mrp_variant_records_from_extracted makes from the chain that call documents.  A chunk
+ * whose rest is empty (phasePrimaryVariantsOnly, the SV configuration) gets its primary records all the same.  One kernel behind the
+ * back half's reads the tags, the haplotype strings and the variants' states where they lie in HBM, a wave per site, and builds the two
+ * lists as stable compactions of the extraction's entry list; the per-site scalars and the lists come back, no entry list does.  The
+ * log values are the fragment's own floats, copied on the host where the phasing left them.
+ * Checks, their order and their messages are mrp_phase_aligned_chunks_with_filtered's, a NULL records_out among its null arguments.
+ * mrp_context_set_wide_pairs and mrp_context_set_sv_split are honoured as there.  stats may be NULL. */
+int mrp_phase_aligned_chunks_with_records(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
+                                          const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
+                                          const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                                          int64_t sv_threshold, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                          mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                                          int64_t **bubble_variant_out, mrp_filtered_out *filtered_out, int32_t **filtered_read_out,
+                                          mrp_variant_records *records_out, mrp_phase_aligned_records_stats *stats);
+
+/* From the records of a contig's chunks (in genome order) to what mrp_phase_sets takes, host only.  Per chunk c: records[c]; variant_pos[c]
+ * / n_alleles[c] (records[c].n_primary entries) and fvariant_pos[c] / fn_alleles[c] (n_filtered entries): positions and allele counts of
+ * its two variant sets; switched[c]: what mrp_stitch_chunk decided; read_id[c][r]: the caller's global id of the chunk's read r
+ * (readIdToIdx).  updateHaplotypeSwitchingInVcfEntries (vcf.c:595-650): in a switched chunk gt1 <-> gt2 and the hap1 <-> hap2 log values
+ * trade places; the lists stay with their allele (alleleIdxToReads is indexed by allele).  Only MRP_RECORD_UPDATED records are kept
+ * (wasUpdated, vcf.c:863-868), ordered by position; ties by chunk, then primary before filtered, then site (an assumption, DESIGN.md 9.12:
+ * the reference keeps the VCF's own order).  A variant's allele_reads: under allele gt[0] of the record its hap1 reads, under gt[1] its
+ * hap2 reads, as read ids, ascending and without repeats; equal alleles hold the union.
+ * out->variants is ONE malloc'd block (mrp_free) that holds the mrp_variant array, the arrays it points into and the arrays below. */
+typedef struct mrp_record_variants {
+    int64_t n_variants;
+    mrp_variant *variants;  /* the block */
+    int32_t *chunk, *site;  /* per kept variant: its chunk and its site among the chunk's records */
+    float *genotype_log_prob, *hap1_log_prob, *hap2_log_prob; /* after switching */
+} mrp_record_variants;
+int mrp_variants_from_records(int64_t n_chunks, const mrp_variant_records *records, const int64_t *const *variant_pos, const int32_t *const *n_alleles,
+                              const int64_t *const *fvariant_pos, const int32_t *const *fn_alleles, const int32_t *switched,
+                              const int32_t *const *read_id, mrp_record_variants *out);
 
 /* ---- the same for a node's worth of aligned chunks over its GPUs --------------------------------------------------------------
  * The chunk loop of phase.c (:257-279: largest first, schedule(dynamic,1)) around mrp_phase_aligned_chunks /

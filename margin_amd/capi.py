@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "mrp_haplotag_chunk_units", "mrp_queue_haplotag_aligned_chunks", "mrp_haplotag_aligned_chunks_on_devices",
     "mrp_context_set_wide_pairs", "mrp_context_wide_pair_count", "mrp_queue_set_wide_pairs", "mrp_queue_wide_pair_count", "mrp_pair_diagonal_width",
     "mrp_context_set_sv_split", "mrp_queue_set_sv_split", "mrp_mark_structural_variants",
+    "mrp_variant_records_from_extracted", "mrp_phase_aligned_chunks_with_records", "mrp_variants_from_records",
 ]
 
 
@@ -314,6 +315,27 @@ class PhaseAlignedFilteredStats(C.Structure):
                 ("classes_ms", C.c_double)]
 
 
+RECORD_UNTOUCHED, RECORD_UPDATED, RECORD_CLEARED = 0, 1, 2
+
+_RECORD_ARRAYS = (("state", np.uint8, "s"), ("gt", np.int32, "s2"), ("genotype_log_prob", np.float32, "s"), ("hap1_log_prob", np.float32, "s"),
+                  ("hap2_log_prob", np.float32, "s"), ("read_first", np.int64, "s1"), ("n_hap1", np.int32, "s"), ("n_hap2", np.int32, "s"),
+                  ("reads", np.int32, "r"))
+
+
+class VariantRecords(C.Structure):
+    _fields_ = [("n_primary", C.c_int64), ("n_filtered", C.c_int64)] + [(f, C.c_void_p) for f, _, _ in _RECORD_ARRAYS]
+
+
+class PhaseAlignedRecordsStats(C.Structure):
+    _fields_ = [("filtered", PhaseAlignedFilteredStats), ("records_sites", C.c_int64), ("records_updated", C.c_int64), ("reads_listed", C.c_int64),
+                ("records_bytes_downloaded", C.c_int64), ("records_ms", C.c_double)]
+
+
+class RecordVariants(C.Structure):
+    _fields_ = [("n_variants", C.c_int64), ("variants", C.POINTER(Variant)), ("chunk", C.c_void_p), ("site", C.c_void_p),
+                ("genotype_log_prob", C.c_void_p), ("hap1_log_prob", C.c_void_p), ("hap2_log_prob", C.c_void_p)]
+
+
 def load():
     """dlopen the in-tree library; raises if it has not been built (no fallback)."""
     global _lib
@@ -429,6 +451,10 @@ def load():
                                                          P(PairHmm), i64, i64, C.c_double, P(Params), i64, P(P(PhaseResult)), P(vp), P(vp),
                                                          P(ProfileOut), P(vp), P(FilteredOut), P(vp), P(PhaseAlignedFilteredStats)]
     pa, pf = L.mrp_phase_aligned_chunks.argtypes, L.mrp_phase_aligned_chunks_with_filtered.argtypes
+    L.mrp_phase_aligned_chunks_with_records.argtypes = pf[:-1] + [P(VariantRecords), P(PhaseAlignedRecordsStats)]
+    L.mrp_variant_records_from_extracted.argtypes = [P(ExtractedChunk), P(ExtractedChunk), vp, vp, i64, P(PhaseResult), vp, vp, vp, i64, i64, vp, vp,
+                                                     P(VariantRecords)]
+    L.mrp_variants_from_records.argtypes = [i64, P(VariantRecords), P(vp), P(vp), P(vp), P(vp), vp, P(vp), P(RecordVariants)]
     L.mrp_aligned_chunk_units.argtypes = [P(AlignedChunk), P(AlignedChunkRest), P(i64)]
     # the one call's list with chunks_per_batch behind min_phred and the queue's stats in place of the call's
     L.mrp_queue_phase_aligned_chunks.argtypes = pa[:13] + [i64] + pa[13:-1] + [P(QueueStats)]
@@ -1743,6 +1769,101 @@ def equal_substring_classes(ctx: Optional[Context], entry_first, pool, off, leng
     return rep
 
 
+# ---- the phased variant records (mrp_variant_records_from_extracted, mrp_variants_from_records) ----
+
+def _records_dict(R, free: bool = True) -> dict:
+    """the arrays of one mrp_variant_records as numpy copies (gt as [n_sites, 2]); the C arrays are released"""
+    ns = int(R.n_primary) + int(R.n_filtered)
+    first = _as_np(R.read_first, ns + 1, np.int64)
+    size = dict(s=ns, s1=ns + 1, s2=2 * ns, r=int(first[ns]))
+    d = {f: _as_np(getattr(R, f), size[k], t) for f, t, k in _RECORD_ARRAYS}
+    d["gt"] = d["gt"].reshape(ns, 2)
+    d["n_primary"], d["n_filtered"] = int(R.n_primary), int(R.n_filtered)
+    if free:
+        for f, _, _ in _RECORD_ARRAYS:
+            load().mrp_free(C.cast(getattr(R, f), C.c_void_p))
+    return d
+
+
+def records_struct(rec: dict):
+    """mrp_variant_records over the numpy arrays of a records dict; returns (VariantRecords, the arrays it points into)"""
+    keep = {f: np.ascontiguousarray(rec[f], t).reshape(-1) for f, t, _ in _RECORD_ARRAYS}
+    ptr = lambda a: a.ctypes.data if a.size else None
+    return VariantRecords(int(rec["n_primary"]), int(rec["n_filtered"]), *[ptr(keep[f]) for f, _, _ in _RECORD_ARRAYS]), keep
+
+
+def phase_result_struct(g: dict):
+    """mrp_phase_result over a dict _phase_result_dict made (the arrays a record reads); returns (PhaseResult, the arrays)"""
+    keep = dict(h1=np.ascontiguousarray(g["hap1"], np.uint64), h2=np.ascontiguousarray(g["hap2"], np.uint64),
+                gp=np.ascontiguousarray(g["genotype_probs"], np.float32), p1=np.ascontiguousarray(g["hap_probs1"], np.float32),
+                p2=np.ascontiguousarray(g["hap_probs2"], np.float32))
+    R = PhaseResult()
+    R.ref_start, R.length = int(g["ref_start"]), int(g["length"])
+    as_p = lambda a, t: C.cast(a.ctypes.data if a.size else None, C.POINTER(t))
+    R.haplotype_string1, R.haplotype_string2 = as_p(keep["h1"], C.c_uint64), as_p(keep["h2"], C.c_uint64)
+    R.genotype_probs, R.haplotype_probs1, R.haplotype_probs2 = as_p(keep["gp"], C.c_float), as_p(keep["p1"], C.c_float), as_p(keep["p2"], C.c_float)
+    return R, keep
+
+
+def variant_records_from_extracted(x: dict, xf: dict, keep, bubble_variant, result: dict, hap, variant_pos, fvariant_pos, chunk_start: int,
+                                   chunk_end: int, gt, variant_state, nulls=()) -> dict:
+    """mrp_variant_records_from_extracted -> dict of the record arrays (numpy; gt as [n_sites, 2]; n_primary, n_filtered).  result: a dict
+    as _phase_result_dict makes it; nulls names arguments to pass as NULL (for the argument checks).  On an error the output struct is
+    checked to be unwritten."""
+    L = load()
+    X, hold_x = extracted_struct(x)
+    XF, hold_f = extracted_struct(xf)
+    G, hold_g = phase_result_struct(result)
+    km = None if keep is None else np.ascontiguousarray(keep, np.uint8)
+    arrs = dict(bubble_variant=np.ascontiguousarray(bubble_variant, np.int64), hap=np.ascontiguousarray(hap, np.int8),
+                variant_pos=np.ascontiguousarray(variant_pos, np.int64), fvariant_pos=np.ascontiguousarray(fvariant_pos, np.int64),
+                gt=np.ascontiguousarray(gt, np.int32).reshape(-1), variant_state=np.ascontiguousarray(variant_state, np.int32))
+    ptr = lambda name: None if name in nulls or arrs[name].size == 0 else arrs[name].ctypes.data
+    R = VariantRecords()
+    R.n_primary = -7
+    rc = L.mrp_variant_records_from_extracted(None if "x" in nulls else C.byref(X), None if "xf" in nulls else C.byref(XF),
+                                              None if km is None or km.size == 0 else km.ctypes.data, ptr("bubble_variant"), len(arrs["bubble_variant"]),
+                                              None if "result" in nulls else C.byref(G), ptr("hap"), ptr("variant_pos"), ptr("fvariant_pos"),
+                                              int(chunk_start), int(chunk_end), ptr("gt"), ptr("variant_state"), None if "out" in nulls else C.byref(R))
+    if rc != MRP_OK:
+        assert R.n_primary == -7 and not any(getattr(R, f) for f, _, _ in _RECORD_ARRAYS), "outputs written on an error"
+    _check(rc)
+    return _records_dict(R)
+
+
+def variants_from_records(records, variant_pos, n_alleles, fvariant_pos, fn_alleles, switched, read_id):
+    """mrp_variants_from_records over per-chunk lists (records: dicts as variant_records_from_extracted returns) -> (variants as the dicts
+    capi.phase_sets takes, each with "chunk", "site" and the three log values after switching)"""
+    L = load()
+    n = len(records)
+    built = [records_struct(r) for r in records]
+    arr = (VariantRecords * max(n, 1))(*[b[0] for b in built])
+
+    def table(rows, t):
+        keep = [np.ascontiguousarray(r, t) for r in rows]
+        return (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in keep]), keep
+    vp_, k1 = table(variant_pos, np.int64)
+    na_, k2 = table(n_alleles, np.int32)
+    fp_, k3 = table(fvariant_pos, np.int64)
+    fa_, k4 = table(fn_alleles, np.int32)
+    id_, k5 = table(read_id, np.int32)
+    sw = np.ascontiguousarray(switched, np.int32)
+    out = RecordVariants()
+    _check(L.mrp_variants_from_records(n, arr, vp_, na_, fp_, fa_, sw.ctypes.data if sw.size else None, id_, C.byref(out)))
+    m = int(out.n_variants)
+    chunk, site = _as_np(out.chunk, m, np.int32), _as_np(out.site, m, np.int32)
+    logs = [_as_np(getattr(out, f), m, np.float32) for f in ("genotype_log_prob", "hap1_log_prob", "hap2_log_prob")]
+    res = []
+    for i in range(m):
+        V = out.variants[i]
+        off = _as_np(V.allele_read_off, V.n_alleles + 1, np.int64)
+        ids = _as_np(V.allele_reads, int(off[V.n_alleles]), np.int32)
+        res.append(dict(pos=int(V.pos), gt1=int(V.gt1), gt2=int(V.gt2), alleleIdxToReads=[ids[off[a]:off[a + 1]].tolist() for a in range(V.n_alleles)],
+                        chunk=int(chunk[i]), site=int(site[i]), genotype_log_prob=logs[0][i], hap1_log_prob=logs[1][i], hap2_log_prob=logs[2][i]))
+    L.mrp_free(C.cast(out.variants, C.c_void_p))
+    return res
+
+
 # ---- haplotagging aligned reads from a phased VCF (mrp_haptag_sites_from_extracted, mrp_haplotag_aligned_chunks) ----
 
 _HAPTAG_SITE_ARRAYS = (("allele_first", np.int64, "s1"), ("allele_off", np.int64, "a"), ("allele_len", np.int32, "a"), ("compare", np.int32, "s2"),
@@ -1878,6 +1999,13 @@ def phase_aligned_chunks_with_filtered(ctx: Optional[Context], chunks, rests, fo
     return _phase_aligned(ctx, chunks, forward_model, reverse_model, params, rests=rests, with_rest=True, **kw)
 
 
+def phase_aligned_chunks_with_records(ctx: Optional[Context], chunks, rests, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm],
+                                      params: Optional[Params], **kw):
+    """mrp_phase_aligned_chunks_with_records -> (phase_aligned_chunks_with_filtered's list of dicts, each with "records" (the record arrays as
+    variant_records_from_extracted returns them), PhaseAlignedRecordsStats).  A further null: "records_out"."""
+    return _phase_aligned(ctx, chunks, forward_model, reverse_model, params, rests=rests, with_rest=True, with_records=True, **kw)
+
+
 def phase_aligned_chunks(ctx: Optional[Context], chunks, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm], params: Optional[Params],
                          **kw):
     """mrp_phase_aligned_chunks; arguments and results as _phase_aligned states them"""
@@ -1913,7 +2041,7 @@ def phase_aligned_chunks_with_filtered_on_devices(devices, chunks, rests, forwar
 def _phase_aligned(ctx: Optional[Context], chunks, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm], params: Optional[Params],
                    options: Optional[dict] = None, keeps=None, min_phred: int = 0, expansion: int = 4, sv_threshold: int = 512,
                    het_substitution_probability: float = 0.0, profiles: bool = False, structs=None, nulls=(), rests=None, rest_structs=None,
-                   with_rest: bool = False, queue=_NO_QUEUE, devices=None, chunks_per_batch: int = 0):
+                   with_rest: bool = False, queue=_NO_QUEUE, devices=None, chunks_per_batch: int = 0, with_records: bool = False):
     """mrp_phase_aligned_chunks -> (per chunk dict(result, hap int8 [n_reads], phred, bubble_variant int64 [n_bubbles][, profile]),
     PhaseAlignedStats).  keeps: None, or per chunk None / a uint8 mask over its reads.  ctx / a model / params None pass NULL;
     nulls names further arguments to pass as NULL ("options", "out", "hap_out", "read_names", "hap_out[0]", "phred_out[0]",
@@ -1971,21 +2099,26 @@ def _phase_aligned(ctx: Optional[Context], chunks, forward_model: Optional[PairH
         fout = (FilteredOut * max(n, 1))()
         fout[0].n_reads = 77  # (zeroed whatever the outcome)
         fr = (C.c_void_p * max(n, 1))()
-        st = QueueStats() if queued else PhaseAlignedFilteredStats()
+        st = QueueStats() if queued else (PhaseAlignedRecordsStats() if with_records else PhaseAlignedFilteredStats())
         fn = (L.mrp_phase_aligned_chunks_with_filtered_on_devices if devices is not None else L.mrp_queue_phase_aligned_chunks_with_filtered) if queued \
-            else L.mrp_phase_aligned_chunks_with_filtered
+            else (L.mrp_phase_aligned_chunks_with_records if with_records else L.mrp_phase_aligned_chunks_with_filtered)
+        recs = (VariantRecords * max(n, 1))()
+        recs[0].n_primary = 77  # (zeroed whatever the outcome)
+        tail = (None if "records_out" in nulls else recs,) if with_records else ()
         t_call = time.perf_counter()
         rc = fn(*head, n, arr, None if "rest" in nulls else rarr, None if "read_names" in nulls else name_ptrs,
                 None if keeps is None else mask_ptrs, None if "options" in nulls else C.byref(opt), by(forward_model),
                 by(reverse_model), int(expansion), int(sv_threshold), float(het_substitution_probability), by(params),
                 int(min_phred), *per_batch, None if "out" in nulls else res, None if "hap_out" in nulls else hp, pp, prof, bv,
-                None if "filtered_out" in nulls else fout, None if "filtered_read_out" in nulls else fr, C.byref(st))
+                None if "filtered_out" in nulls else fout, None if "filtered_read_out" in nulls else fr, *tail, C.byref(st))
     LAST_ALIGNED_CALL_MS = (time.perf_counter() - t_call) * 1e3
     if with_rest:
-        if rc != MRP_OK and n > 0 and not {"rest", "filtered_out", "filtered_read_out"} & set(nulls):
+        if rc != MRP_OK and n > 0 and not {"rest", "filtered_out", "filtered_read_out", "records_out"} & set(nulls):
             if queued and fout[0].n_reads == 77:  # (the queue writes nothing before its lanes start)
                 fout[0].n_reads = 0
             assert bytes(fout) == bytes((FilteredOut * max(n, 1))()) and not any(fr[i] for i in range(n)), "filtered_out not zeroed on an error"
+            if with_records and "records_out" not in nulls:
+                assert bytes(recs) == bytes((VariantRecords * max(n, 1))()), "records_out not zeroed on an error"
     if rc != MRP_OK:
         # (a queue that stops on a lane's error has written hap_out / phred_out of the batches that were done)
         untouched = (queued or (all((h == 99).all() for h in hap) and all(np.isnan(p).all() for p in phred))) and not any(bool(res[i]) for i in range(n)) and \
@@ -2023,5 +2156,7 @@ def _phase_aligned(ctx: Optional[Context], chunks, forward_model: Optional[PairH
                 nf += 1
             d["filtered_read"] = _as_np(fr[i], nf, np.int32)
             L.mrp_free(fr[i])
+            if with_records:
+                d["records"] = _records_dict(recs[i])
         out.append(d)
     return out, st

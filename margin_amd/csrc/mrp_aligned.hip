@@ -758,6 +758,8 @@ struct PfRun : PaRun {
     int classes();
     int rests();
     int filtered_front(int64_t sv_threshold);
+    int record_sites();
+    int records(mrp_phase_result *const *out, mrp_variant_records *records_out, mrp_phase_aligned_records_stats *rstats);
 };
 
 /* the rest's own MRP_ERR_ARG (its variants have passed the extraction's checks as the second half's records) */
@@ -908,6 +910,124 @@ int PfRun::filtered_front(int64_t sv_threshold) {
     return MRP_OK;
 }
 
+/* the records' site table: every variant of both halves, with a slot per entry of a primary read where the
+ * site can be updated at all -- a primary variant with a bubble and a position inside the chunk (vcf.c:538-540), a filtered variant
+ * inside the chunk (bubbleGraph.c:2179); the kernel reads the entries where the extraction left them */
+int PfRun::record_sites() {
+    mrp_string_front::Records &Q = F.rec;
+    Q.on = true;
+    Q.read_first.assign(D.read_first, D.read_first + n + 1);
+    Q.entry_first = D.entry_first;
+    Q.entry_read = D.entry_read;
+    Q.read_status = D.read_status;
+    Q.take = d_take.p;
+    Q.sites.resize((size_t) D.n_variants);
+    int64_t slots = 0;
+    for (int64_t c = 0; c < n; c++) {
+        const mrp_aligned_chunk &C = chunks[c];
+        const mrp_aligned_chunk_rest &Rc = rest[c];
+        const int64_t r1 = D.read_first[c], r2 = D.read_first[n + c];
+        auto primary = [&](int64_t r) { return k_status[r1 + r] == MRP_READ_KEPT && (!keep || !keep[c] || keep[c][r]); };
+        std::vector<int32_t> bubble_of((size_t) C.n_variants, -1);
+        const std::vector<int64_t> &bv = arr[(size_t) c].bubble_variant;
+        for (size_t b = 0; b < bv.size(); b++) bubble_of[(size_t) bv[b]] = (int32_t) b;
+        for (int64_t v = 0; v < C.n_variants; v++) {
+            const int64_t g = D.variant_first[c] + v;
+            const bool inside = C.variant_pos[v] >= C.chunk_start && C.variant_pos[v] < C.chunk_end;
+            RcSite st{g, slots, 0, (int32_t) c, inside ? bubble_of[(size_t) v] : -1, -1, 0, 0, 0, (int32_t) r1};
+            if (st.bubble >= 0)
+                for (int64_t p = k_first[g]; p < k_first[g + 1]; p++) st.n_slots += primary(k_read[p] - r1);
+            slots += st.n_slots;
+            Q.sites[(size_t) g] = st;
+        }
+        for (int64_t v = 0; v < Rc.n_variants; v++) {
+            const int64_t g = D.variant_first[n + c] + v;
+            RcSite st{g, slots, 0, (int32_t) c, -1, (int32_t) (F.fil.var_base[(size_t) c] + v), Rc.gt[2 * v], Rc.gt[2 * v + 1], (int32_t) (r2 - r1), (int32_t) r1};
+            if (Rc.variant_pos[v] >= C.chunk_start && Rc.variant_pos[v] < C.chunk_end)
+                for (int64_t p = k_first[g]; p < k_first[g + 1]; p++) st.n_slots += k_status[k_read[p]] == MRP_READ_KEPT && primary(k_read[p] - r2);
+            slots += st.n_slots;
+            Q.sites[(size_t) g] = st;
+        }
+    }
+    Q.n_slots = slots;
+    if (slots >= (1ll << 31) || D.n_reads >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 reads or list slots in one call", who);
+    return MRP_OK;
+}
+
+/* the records per chunk from what the kernel brought back; the log values are the fragment's own floats (vcf.c:527-529), a filtered
+ * record's -INFINITY (probability 0, bubbleGraph.c:2300-2302) */
+int PfRun::records(mrp_phase_result *const *out, mrp_variant_records *records_out, mrp_phase_aligned_records_stats *rstats) {
+    const mrp_string_front::Records &Q = F.rec;
+    int64_t n_updated = 0, n_listed = 0;
+    bool ok = true;
+    for (size_t g = 0; g < Q.sites.size(); g++) { /* (before anything is handed over) */
+        const RcOut &o = Q.out[g];
+        if (o.n_hap1 < 0 || o.n_hap2 < 0 || (int64_t) o.n_hap1 + o.n_hap2 > Q.sites[g].n_slots)
+            return mrp_set_error(MRP_ERR_HIP, "%s: site %lld: the records kernel listed %d + %d reads in %d slots", who, (long long) g, o.n_hap1, o.n_hap2,
+                                 Q.sites[g].n_slots);
+    }
+    for (int64_t c = 0; c < n && ok; c++) {
+        const int64_t np = chunks[c].n_variants, nv = rest[c].n_variants, ns = np + nv;
+        int64_t listed = 0;
+        for (int64_t i = 0; i < ns; i++) {
+            const RcOut &o = Q.out[(size_t) (i < np ? D.variant_first[c] + i : D.variant_first[n + c] + (i - np))];
+            listed += o.n_hap1 + o.n_hap2;
+        }
+        mrp_variant_records &R = records_out[c];
+        const size_t m = (size_t) std::max<int64_t>(ns, 1);
+        R.n_primary = np;
+        R.n_filtered = nv;
+        R.state = (uint8_t *) calloc(m, 1);
+        R.gt = (int32_t *) calloc(2 * m, 4);
+        R.genotype_log_prob = (float *) calloc(m, 4);
+        R.hap1_log_prob = (float *) calloc(m, 4);
+        R.hap2_log_prob = (float *) calloc(m, 4);
+        R.read_first = (int64_t *) calloc((size_t) ns + 1, 8);
+        R.n_hap1 = (int32_t *) calloc(m, 4);
+        R.n_hap2 = (int32_t *) calloc(m, 4);
+        R.reads = (int32_t *) calloc((size_t) std::max<int64_t>(listed, 1), 4);
+        ok = R.state && R.gt && R.genotype_log_prob && R.hap1_log_prob && R.hap2_log_prob && R.read_first && R.n_hap1 && R.n_hap2 && R.reads;
+        if (!ok) break;
+        const mrp_phase_result *gf = out[c];
+        int64_t at = 0;
+        for (int64_t i = 0; i < ns; i++) {
+            const int64_t g = i < np ? D.variant_first[c] + i : D.variant_first[n + c] + (i - np);
+            const RcOut &o = Q.out[(size_t) g];
+            const RcSite &st = Q.sites[(size_t) g];
+            R.state[i] = (uint8_t) o.state;
+            R.gt[2 * i] = o.gt1;
+            R.gt[2 * i + 1] = o.gt2;
+            R.n_hap1[i] = o.n_hap1;
+            R.n_hap2[i] = o.n_hap2;
+            if (i >= np && o.state != MRP_RECORD_UNTOUCHED) R.genotype_log_prob[i] = R.hap1_log_prob[i] = R.hap2_log_prob[i] = -INFINITY;
+            if (i < np && o.state == MRP_RECORD_UPDATED) {
+                const int64_t j = st.bubble - gf->ref_start;
+                R.genotype_log_prob[i] = gf->genotype_probs[j];
+                R.hap1_log_prob[i] = gf->haplotype_probs1[j];
+                R.hap2_log_prob[i] = gf->haplotype_probs2[j];
+            }
+            const int32_t *sl = Q.slots.data() + st.slot_first;
+            for (int32_t q = 0; q < o.n_hap1; q++) R.reads[at++] = sl[q];
+            for (int32_t q = 0; q < o.n_hap2; q++) R.reads[at++] = sl[st.n_slots - o.n_hap2 + q];
+            R.read_first[i + 1] = at;
+            n_updated += o.state == MRP_RECORD_UPDATED;
+        }
+        n_listed += listed;
+    }
+    if (!ok) {
+        for (int64_t c = 0; c < n; c++) mrp_variant_records_clear(&records_out[c]);
+        return mrp_set_error(MRP_ERR_NOMEM, "%s: out of host memory", who);
+    }
+    if (rstats) {
+        rstats->records_sites = (int64_t) Q.sites.size();
+        rstats->records_updated = n_updated;
+        rstats->reads_listed = n_listed;
+        rstats->records_bytes_downloaded = (int64_t) (sizeof(RcOut) * Q.sites.size()) + 4 * Q.n_slots;
+        rstats->records_ms = Q.ms;
+    }
+    return MRP_OK;
+}
+
 }  // namespace
 
 /* ---- the two entries in steps (mrp_internal.h): the checks, the device steps up to the launch classes, the string run ------------
@@ -988,6 +1108,7 @@ int mrp_aligned_front_stage(mrp_context *ctx, mrp_aligned_front *A) {
     if (rc == MRP_OK) rc = R.strings_and_pairs(a.sv_threshold);
     if (rc == MRP_OK && rest) rc = R.rests();
     if (rc == MRP_OK && rest) rc = R.filtered_front(a.sv_threshold);
+    if (rc == MRP_OK && rest && a.records_out) rc = R.record_sites();
     if (rc == MRP_OK) rc = R.anchors();
     if (rc == MRP_OK) rc = R.classify(a.forward_model, a.reverse_model, a.expansion);
     return rc;
@@ -1031,6 +1152,18 @@ int mrp_aligned_front_run(mrp_aligned_front *A, mrp_string_chunks_stats *chunk_s
         rc = mrp_string_front_run(ctx, &R.F, a.het_substitution_probability, a.params, a.min_phred, a.out, a.hap_out, a.phred_out, a.profiles_out,
                                   stats ? &stats->chunks : chunk_stats, a.filtered_out, fstats ? &fst : nullptr);
         if (rc != MRP_OK) return rc;
+        if (a.records_out) {
+            rc = R.records(a.out, a.records_out, a.records_stats);
+            if (rc != MRP_OK) { /* an error returns nothing: what the string run handed over goes back */
+                for (int64_t c = 0; c < n_chunks; c++) {
+                    mrp_phase_result_destroy(a.out[c]);
+                    a.out[c] = nullptr;
+                    if (a.profiles_out) mrp_profile_out_clear(&a.profiles_out[c]);
+                    mrp_filtered_out_clear(&a.filtered_out[c]);
+                }
+                return rc;
+            }
+        }
     }
     if (fstats) {
         float ms = 0.f;
@@ -1078,6 +1211,28 @@ extern "C" int mrp_phase_aligned_chunks(mrp_context *ctx, int64_t n_chunks, cons
                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr,
                              ctx ? ctx->sv_split : 0}; /* (a NULL context counts as off) */
     return pa_phase_chunks("mrp_phase_aligned_chunks", t_begin, ctx, a, stats, nullptr);
+}
+
+extern "C" int mrp_phase_aligned_chunks_with_records(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
+                                                     const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
+                                                     const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                                                     int64_t sv_threshold, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                     mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                                                     int64_t **bubble_variant_out, mrp_filtered_out *filtered_out, int32_t **filtered_read_out,
+                                                     mrp_variant_records *records_out, mrp_phase_aligned_records_stats *stats) {
+    static const char *who = "mrp_phase_aligned_chunks_with_records";
+    const double t_begin = now_ms();
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_chunks < 0 || n_chunks >= (1ll << 30) || (n_chunks > 0 && (!chunks || !rest || !filtered_out || !filtered_read_out || !records_out)))
+        return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
+    if (n_chunks > 0) {
+        memset(filtered_out, 0, sizeof(*filtered_out) * (size_t) n_chunks);
+        memset(records_out, 0, sizeof(*records_out) * (size_t) n_chunks);
+    }
+    const mrp_aligned_args a{n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
+                             het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
+                             filtered_read_out, ctx ? ctx->sv_split : 0, records_out, stats};
+    return pa_phase_chunks(who, t_begin, ctx, a, stats ? &stats->filtered.aligned : nullptr, stats ? &stats->filtered : nullptr);
 }
 
 extern "C" int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,

@@ -570,6 +570,11 @@ static inline void mrp_filtered_out_clear(mrp_filtered_out *O) {
     free(O->read_hap); free(O->h1); free(O->h2); free(O->variant_state); free(O->cis); free(O->trans);
     memset(O, 0, sizeof(*O));
 }
+static inline void mrp_variant_records_clear(mrp_variant_records *R) {
+    free(R->state); free(R->gt); free(R->genotype_log_prob); free(R->hap1_log_prob); free(R->hap2_log_prob); free(R->read_first); free(R->n_hap1);
+    free(R->n_hap2); free(R->reads);
+    memset(R, 0, sizeof(*R));
+}
 /* mrp_extract_read_substrings as one run taken through steps (mrp_extract.hip), so that a composite (mrp_haplotag_aligned_chunks,
  * mrp_aligned.hip) can stop before the download and read the result where it lies in HBM:
  *   check_args / check_modes / check_chunks   MRP_ERR_ARG for malformed arguments, MRP_ERR_UNSUPPORTED for the two refused modes, the
@@ -656,6 +661,9 @@ struct mrp_aligned_args {
     mrp_filtered_out *filtered_out;
     int32_t **filtered_read_out;
     int sv_split; /* the context's or the queue's setting at the call (mrp_context_set_sv_split); the checks need no context */
+    /* mrp_phase_aligned_chunks_with_records only (NULL otherwise): the records and their share of the stats */
+    mrp_variant_records *records_out;
+    mrp_phase_aligned_records_stats *records_stats;
 };
 int mrp_aligned_chunks_check(const char *who, const mrp_aligned_args *args);
 int mrp_aligned_front_create(const char *who, double t_begin_ms, const mrp_aligned_args *args, mrp_phase_aligned_stats *stats,

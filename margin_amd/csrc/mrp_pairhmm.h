@@ -260,6 +260,24 @@ struct FsSite {
     int32_t n_alleles, visited; /* variants: gt1 != gt2 and entries (bubbleGraph.c:2174, :2186-2192) */
 };
 
+/* ---- the phased variant records behind the back half (mrp_phase_aligned_chunks_with_records) -------------------
+ * A site is a variant of the call: the chunks' primary variants, then the rests'.  Its entries are the extraction's, read where the
+ * extraction left them in HBM; its two lists go into its own slots of one array, hap1 from the front, hap2 from the back. */
+struct RcSite {
+    int64_t var;        /* the site's variant in the extraction's entry CSR */
+    int64_t slot_first; /* its slots */
+    int32_t n_slots;    /* one per entry of a primary read; 0 for a site that cannot be updated */
+    int32_t chunk;
+    int32_t bubble;     /* primary: its bubble, -1 without one or with a position outside [chunk_start, chunk_end); filtered: -1 */
+    int32_t state;      /* filtered: where its state lies among the back half's variants; primary: -1 */
+    int32_t gt1, gt2;   /* filtered: the rest's genotype */
+    int32_t read_shift; /* entry_read - read_shift = the read among the call's primary reads (the rest's extraction numbers the same reads again) */
+    int32_t read_base;  /* the chunk's first read among the call's primary reads */
+};
+struct RcOut {
+    int32_t state, gt1, gt2, n_hap1, n_hap2;
+};
+
 /* the front of a string-chunk call: what mrp_string_front_create (or PaRun, over a device pool) makes and mrp_string_front_run reads */
 struct mrp_string_front {
     int64_t n_chunks = 0, n_subs = 0, n_pairs = 0;
@@ -300,6 +318,21 @@ struct mrp_string_front {
         HostVec<int64_t> cand_first;                   /* per read of the call: its entries at bubbles, in bubble order */
         HostVec<int32_t> cand;
     } fil;
+    /* the records (a front over a device pool made for mrp_phase_aligned_chunks_with_records): the site table, the extraction's device
+     * arrays the kernel reads (alive until the run has returned), and what the run brings back */
+    struct Records {
+        bool on = false;
+        HostVec<RcSite> sites;
+        std::vector<int64_t> read_first;               /* n_chunks + 1: chunk c's reads among the call's primary reads */
+        int64_t n_slots = 0;
+        const int64_t *entry_first = nullptr;          /* device: the entry CSR by variant of the call */
+        const int32_t *entry_read = nullptr;           /* device: per entry its read of the call */
+        const uint8_t *read_status = nullptr;          /* device: per read of the call MRP_READ_* */
+        const uint8_t *take = nullptr;                 /* device: per read of the call the caller's mask (NULL: none) */
+        std::vector<RcOut> out;                        /* filled by the run: per site */
+        std::vector<int32_t> slots;                    /* the chunk's read index per slot that was written */
+        float ms = 0.f;                                /* the kernel, HIP events */
+    } rec;
 };
 
 int sc_filtered_front(mrp_string_front *F, const mrp_string_chunk_rest *rest, int64_t sv_threshold, const std::vector<int64_t> &rpool_base);

@@ -301,6 +301,79 @@ __global__ void __launch_bounds__(256) fs_phase_kernel(const FsSite *__restrict_
     trans[v] = t;
 }
 
+/* The phased variant records (updateOriginalVcfEntriesWithBubbleData, vcf.c:511-592; the update that ends
+ * bubbleGraph_phaseVcfEntriesFromHaplotaggedReads, bubbleGraph.c:2298-2343), behind fs_phase_kernel.  A wave per site; lanes run over
+ * the site's entries where the extraction left them, 64 a pass.  A primary site is updated when its bubble lies inside the fragment
+ * (its gt: the fragment's hap1 / hap2 allele there); a filtered site follows its state.  An entry is listed when its read is a primary
+ * read of the chunk (kept, let through by the mask; at a filtered site kept by the rest's extraction too) that the HP kernel tagged 1 or
+ * 2.  The two lists are stable compactions (ballot + prefix popcount, a running base across the passes): a count pass, then hap1 fills
+ * the site's slots from the front and hap2 ends at their end.  n_slots counts the site's entries of primary reads, so n1 + n2 <=
+ * n_slots; a store outside the site's slots is skipped all the same.  Plain vector stores only; every loop is bounded by the site's
+ * entry count and uniform across the wave. */
+static __device__ __forceinline__ int rc_entry_tag(const RcSite &st, bool variant, int32_t g, const uint8_t *__restrict__ status,
+                                                   const uint8_t *__restrict__ take, const int32_t *__restrict__ read_seq,
+                                                   const int8_t *__restrict__ tags, int32_t &read) {
+    if (variant && status[g] != MRP_READ_KEPT) return 0; /* (entries of reads the rest's extraction did not keep are not listed) */
+    const int32_t p = g - st.read_shift;
+    read = p - st.read_base;
+    if (status[p] != MRP_READ_KEPT || (take && !take[p])) return 0;
+    const int tag = fs_tag(read_seq, tags, p);
+    return tag == 1 || tag == 2 ? tag : 0;
+}
+
+__global__ void __launch_bounds__(64) rc_records_kernel(const RcSite *__restrict__ sites, const int64_t *__restrict__ entry_first,
+                                                        const int32_t *__restrict__ entry_read, const uint8_t *__restrict__ status,
+                                                        const uint8_t *__restrict__ take, const int32_t *__restrict__ read_seq,
+                                                        const int8_t *__restrict__ tags, const FsChunk *__restrict__ chunks,
+                                                        const uint64_t *__restrict__ haps, const int32_t *__restrict__ var_state,
+                                                        RcOut *__restrict__ out, int32_t *__restrict__ slots) {
+    const RcSite st = sites[blockIdx.x];
+    const int lane = (int) threadIdx.x;
+    const bool variant = st.state >= 0;
+    int32_t state = MRP_RECORD_UNTOUCHED, g1 = -2, g2 = -2;
+    if (!variant) {
+        if (st.bubble >= 0) {
+            const FsChunk ch = chunks[st.chunk];
+            const int32_t j = st.bubble - ch.frag_start;
+            if (j >= 0 && j < ch.frag_length) { /* vcf.c:520, :558-563 */
+                state = MRP_RECORD_UPDATED;
+                g1 = (int32_t) haps[ch.hap + j];
+                g2 = (int32_t) haps[ch.hap + ch.frag_length + j];
+            }
+        }
+    } else {
+        const int32_t vs = var_state[st.state];
+        if (vs == MRP_VARIANT_TIE) { state = MRP_RECORD_CLEARED; g1 = -1; g2 = -1; }      /* bubbleGraph.c:2298-2321 */
+        else if (vs == MRP_VARIANT_CIS) { state = MRP_RECORD_UPDATED; g1 = st.gt1; g2 = st.gt2; }   /* :2303-2305 */
+        else if (vs == MRP_VARIANT_TRANS) { state = MRP_RECORD_UPDATED; g1 = st.gt2; g2 = st.gt1; } /* :2306-2309 */
+    }
+    int32_t n1 = 0, n2 = 0;
+    if (state == MRP_RECORD_UPDATED && st.n_slots > 0) { /* (the same for every lane of the wave) */
+        const int64_t a = entry_first[st.var], b = entry_first[st.var + 1];
+        for (int64_t p0 = a; p0 < b; p0 += 64) {
+            const int64_t p = p0 + lane;
+            int32_t read = 0;
+            const int tag = p < b ? rc_entry_tag(st, variant, entry_read[p], status, take, read_seq, tags, read) : 0;
+            n1 += (int32_t) __popcll(__ballot(tag == 1));
+            n2 += (int32_t) __popcll(__ballot(tag == 2));
+        }
+        const uint64_t below = (1ull << lane) - 1;
+        int32_t b1 = 0, b2 = st.n_slots - n2;
+        int32_t *dst = slots + st.slot_first;
+        for (int64_t p0 = a; p0 < b; p0 += 64) {
+            const int64_t p = p0 + lane;
+            int32_t read = 0;
+            const int tag = p < b ? rc_entry_tag(st, variant, entry_read[p], status, take, read_seq, tags, read) : 0;
+            const uint64_t m1 = __ballot(tag == 1), m2 = __ballot(tag == 2);
+            const int32_t at = tag == 1 ? b1 + (int32_t) __popcll(m1 & below) : b2 + (int32_t) __popcll(m2 & below);
+            if (tag != 0 && at >= 0 && at < st.n_slots) dst[at] = read;
+            b1 += (int32_t) __popcll(m1);
+            b2 += (int32_t) __popcll(m2);
+        }
+    }
+    if (lane == 0) out[blockIdx.x] = RcOut{state, g1, g2, n1, n2};
+}
+
 bool sc_rest_empty(const mrp_string_chunk_rest &R) { return R.n_filtered == 0 && R.n_variants == 0; }
 
 /* MRP_ERR_ARG for a malformed rest of chunk c (the chunk itself has passed sc_check_chunk) */
@@ -791,7 +864,7 @@ struct ScRun {
     const int64_t n_chunks, n_subs, n_pairs;
     const mrp_string_chunk *const chunks;
     hipStream_t s = nullptr; /* set once the device is current: from then on the destructor drains it */
-    enum { EV_PAIRS_END, EV_BYTES_BEGIN, EV_BYTES_END, EV_POOL_HOME, EV_TAGS_BEGIN, EV_BACK_BEGIN, EV_BACK_END, N_EV };
+    enum { EV_PAIRS_END, EV_BYTES_BEGIN, EV_BYTES_END, EV_POOL_HOME, EV_TAGS_BEGIN, EV_BACK_BEGIN, EV_BACK_END, EV_REC_BEGIN, EV_REC_END, N_EV };
     hipEvent_t ev[N_EV] = {};
     PhmDev D; /* the pair-HMM's device half: D.d_out holds the log probabilities every later kernel reads */
     DevBufGroup arrays;
@@ -848,12 +921,34 @@ struct ScRun {
         int hand_over(ScRun &R, mrp_profile_out *profiles_out);
     } back;
 
+    /* The records' share: the site table and the tags' index go up with the static tables, the kernel follows the back
+     * half's, 20 B per site and 4 B per slot come back.  `on` false makes each method a no-op. */
+    struct Rec {
+        mrp_string_front::Records &Q;
+        const bool on;
+        size_t n_sites = 0;
+        DevBufGroup arrays;
+        DevBuf<RcSite> d_sites{arrays};
+        DevBuf<int32_t> d_read_seq{arrays}, d_slots{arrays};
+        DevBuf<FsChunk> d_chunks{arrays};
+        DevBuf<RcOut> d_out{arrays};
+        HostVec<int32_t> read_seq;
+        HostVec<FsChunk> fchunks;
+        PinnedBuf h_res;
+        explicit Rec(mrp_string_front::Records &q) : Q(q), on(q.on) {}
+        int upload_static(ScRun &R);
+        int alloc_results(ScRun &R);
+        int launch(ScRun &R);
+        int hand_over(ScRun &R);
+    } rec;
+
     ScRun(mrp_context *c, mrp_string_front *f, mrp_string_chunks_stats *st, mrp_filtered_out *filtered_out, mrp_string_filtered_stats *fst)
         : ctx(c), F(f), stats(st), filtered_stats(fst), n_chunks(f->n_chunks), n_subs(f->n_subs), n_pairs(f->n_pairs), chunks(f->chunks),
-          dch((size_t) f->n_chunks, nullptr), res((size_t) f->n_chunks, nullptr), back(f->fil, filtered_out, fst != nullptr) {
+          dch((size_t) f->n_chunks, nullptr), res((size_t) f->n_chunks, nullptr), back(f->fil, filtered_out, fst != nullptr), rec(f->rec) {
         /* the one place that binds the run's device buffers to the context's pool (D: phm_enqueue) */
         arrays.bind(&ctx->pool);
         back.arrays.bind(&ctx->pool);
+        rec.arrays.bind(&ctx->pool);
     }
     ~ScRun() {
         if (s) (void) hipStreamSynchronize(s);
@@ -931,7 +1026,8 @@ int ScRun::layout_and_items(double het_substitution_probability) {
 int ScRun::profile_bytes() {
     PHM_HIP(d_items.upload(items, s));
     PHM_HIP(d_aoff.upload(aoff_all, s));
-    const int rc = back.upload_static(*this); /* the static tables of the back half go up with the rest */
+    int rc = back.upload_static(*this); /* the static tables of the back half go up with the rest */
+    if (rc == MRP_OK) rc = rec.upload_static(*this);
     if (rc != MRP_OK) return rc;
     PHM_HIP(d_pool.alloc((size_t) dpool_bytes));
     PHM_HIP(hipMemsetAsync(d_pool.p, 0, (size_t) dpool_bytes, s)); /* sites a read skips stay 0 */
@@ -1022,6 +1118,7 @@ int ScRun::hp_tags(int64_t min_phred) {
     h_phred = (double *) ((char *) h_res.p + (((size_t) n_seqs_all + 7) & ~(size_t) 7));
     /* the back half's buffers, device and pinned, before the HP kernel is queued: no allocation between it and the back half */
     int rc = back.alloc_results(*this);
+    if (rc == MRP_OK) rc = rec.alloc_results(*this);
     if (rc != MRP_OK) return rc;
     PHM_HIP(hipEventRecord(ev[EV_TAGS_BEGIN], s));
     if (n_seqs_all > 0) {
@@ -1034,7 +1131,8 @@ int ScRun::hp_tags(int64_t min_phred) {
         PHM_HIP(hipMemcpyAsync(h_hap, d_hap.p, (size_t) n_seqs_all, hipMemcpyDeviceToHost, s));
         PHM_HIP(hipMemcpyAsync(h_phred, d_phred.p, (size_t) n_seqs_all * sizeof(double), hipMemcpyDeviceToHost, s));
     }
-    return back.launch(*this);
+    rc = back.launch(*this);
+    return rc == MRP_OK ? rec.launch(*this) : rc;
 }
 
 /* the downloads queued behind their kernels have landed once the stream has drained */
@@ -1042,6 +1140,7 @@ int ScRun::download() {
     PHM_HIP(hipStreamSynchronize(s));
     /* (read before anything is handed over: an error leaves profiles_out / filtered_out zeroed) */
     if (back.on && filtered_stats) PHM_HIP(hipEventElapsedTime(&back.ms, ev[EV_BACK_BEGIN], ev[EV_BACK_END]));
+    if (rec.on) PHM_HIP(hipEventElapsedTime(&rec.Q.ms, ev[EV_REC_BEGIN], ev[EV_REC_END]));
     return MRP_OK;
 }
 
@@ -1079,7 +1178,8 @@ int ScRun::hand_over(mrp_phase_result **out, int8_t *const *hap_out, double *con
                 return fail(MRP_ERR_NOMEM, "mrp_phase_string_chunks: out of host memory");
             }
         }
-    const int rc = back.hand_over(*this, profiles_out);
+    int rc = rec.hand_over(*this); /* (into the front: nothing of the caller's is written) */
+    if (rc == MRP_OK) rc = back.hand_over(*this, profiles_out);
     if (rc != MRP_OK) return rc;
     if (stats) {
         float ms = 0.f;
@@ -1204,6 +1304,60 @@ int ScRun::Back::hand_over(ScRun &R, mrp_profile_out *profiles_out) {
         T.pairs_speculative += R.n_pairs - Q.n_primary_pairs;
         for (int64_t p = Q.n_primary_pairs; p < R.n_pairs; p++) T.pairs_read_by_results += h_used[p] ? 1 : 0;
     }
+    return MRP_OK;
+}
+
+/* the records: the site table and, per primary read of the call, where the HP kernel writes its tag */
+int ScRun::Rec::upload_static(ScRun &R) {
+    if (!on) return MRP_OK;
+    n_sites = Q.sites.size();
+    read_seq.resize((size_t) Q.read_first[(size_t) R.n_chunks]);
+    for (int64_t c = 0; c < R.n_chunks; c++)
+        for (int64_t r = 0; r < R.chunks[c].n_reads; r++) {
+            const int32_t q = R.lay[(size_t) c].seq_of[(size_t) r];
+            read_seq[(size_t) (Q.read_first[(size_t) c] + r)] = q < 0 ? -1 : (int32_t) (R.seq_base[(size_t) c] + q);
+        }
+    PHM_HIP(d_sites.upload(Q.sites, R.s));
+    PHM_HIP(d_read_seq.upload(read_seq, R.s));
+    return MRP_OK;
+}
+
+/* where the fragments' haplotype strings lie goes up; the results' buffers, device and pinned, before the HP kernel is queued */
+int ScRun::Rec::alloc_results(ScRun &R) {
+    if (!on) return MRP_OK;
+    fchunks.resize((size_t) R.n_chunks);
+    for (int64_t c = 0; c < R.n_chunks; c++)
+        fchunks[(size_t) c] = FsChunk{R.hap_base[(size_t) c], (int32_t) R.res[(size_t) c]->ref_start, (int32_t) R.res[(size_t) c]->length};
+    PHM_HIP(d_chunks.upload(fchunks, R.s));
+    PHM_HIP(d_out.alloc(n_sites));
+    PHM_HIP(d_slots.alloc((size_t) Q.n_slots));
+    PHM_HIP(h_res.reserve(n_sites * sizeof(RcOut) + (size_t) Q.n_slots * sizeof(int32_t) + 16));
+    return MRP_OK;
+}
+
+int ScRun::Rec::launch(ScRun &R) {
+    if (!on) return MRP_OK;
+    hipStream_t s = R.s;
+    if (!R.back.on) return fail(MRP_ERR_ARG, "mrp_phase_aligned_chunks_with_records: the records follow the back half");
+    PHM_HIP(hipEventRecord(R.ev[EV_REC_BEGIN], s));
+    if (n_sites > 0) {
+        hipLaunchKernelGGL(rc_records_kernel, dim3((unsigned) n_sites), dim3(64), 0, s, d_sites.p, Q.entry_first, Q.entry_read, Q.read_status, Q.take,
+                           d_read_seq.p, R.d_hap.p, d_chunks.p, R.d_haps.p, R.back.d_hap.p + R.back.n_reads, d_out.p, d_slots.p);
+        PHM_HIP(hipGetLastError());
+    }
+    PHM_HIP(hipEventRecord(R.ev[EV_REC_END], s));
+    if (n_sites > 0) PHM_HIP(hipMemcpyAsync(h_res.p, d_out.p, n_sites * sizeof(RcOut), hipMemcpyDeviceToHost, s));
+    if (Q.n_slots > 0)
+        PHM_HIP(hipMemcpyAsync((uint8_t *) h_res.p + n_sites * sizeof(RcOut), d_slots.p, (size_t) Q.n_slots * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    return MRP_OK;
+}
+
+int ScRun::Rec::hand_over(ScRun &R) {
+    if (!on) return MRP_OK;
+    const RcOut *o = (const RcOut *) h_res.p;
+    const int32_t *sl = (const int32_t *) ((const uint8_t *) h_res.p + n_sites * sizeof(RcOut));
+    Q.out.assign(o, o + n_sites);
+    Q.slots.assign(sl, sl + Q.n_slots);
     return MRP_OK;
 }
 
