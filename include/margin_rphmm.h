@@ -375,6 +375,7 @@ int mrp_queue_set_wide_pairs(mrp_queue *q, int on);
  * MRP_ERR_UNSUPPORTED before its first batch.  Between calls of the queue only.  The *_on_devices forms make a queue of their own with
  * the setting off and keep the refusal: a caller who wants the SV split makes a queue. */
 int mrp_queue_set_sv_split(mrp_queue *q, int on);
+/* (mrp_queue_set_downsampling, the downsampling to maxDepth for every lane's context, is declared with mrp_context_set_downsampling below) */
 /* mrp_context_wide_pair_count summed over the lanes' contexts (either pointer may be NULL) */
 int mrp_queue_wide_pair_count(mrp_queue *q, int64_t *pairs_out, int64_t *cells_out);
 int mrp_queue_phase_chunks(mrp_queue *q, int64_t n_chunks, const mrp_chunk_desc *chunks, const mrp_params *params, int64_t chunks_per_batch,
@@ -988,7 +989,8 @@ typedef struct mrp_phase_aligned_stats {
     int64_t anchors;                /* anchors it found */
     int64_t anchor_runs;            /* the diagonal runs (x, y, length) they came back as */
     int64_t front_bytes_downloaded; /* everything that came back before the pair-HMM launch: 16 B of totals, the entry CSR (8 B per
-                                     * variant + 8), 16 B per entry, 1 B per read, 4 B per anchored pair and 12 B per anchor run */
+                                     * variant + 8), 16 B per entry, 1 B per read, 4 B per anchored pair and 12 B per anchor run; with
+                                     * mrp_context_set_downsampling on, exactly 1 B per read of the call's chunks and 4 B per chunk more */
     double owners_ms;               /* HIP events around the owners kernel */
     double anchors_ms;              /* HIP events around the two anchors kernels */
     double total_ms;                /* host wall time of the call */
@@ -999,7 +1001,7 @@ typedef struct mrp_phase_aligned_stats {
  * out[c], hap_out[c][r] for all n_reads reads of the chunk (-1 for a read that is dropped, filtered, masked out or in no bubble),
  * phred_out (optional), profiles_out (optional) and bubble_variant_out (optional; per chunk a malloc'd array, mrp_free, of the
  * variant of each of the chunk's bubbles, vcfEntriesToBubbleIdx, closed by a -1: its length is the bubble count).  keep: NULL, or per chunk NULL / n_reads bytes; a read takes part
- * if it is MRP_READ_KEPT and its byte is set.  In the extraction's ascending entry order the LAST entry of a variant that takes part
+ * if it is MRP_READ_KEPT and its byte is set (with mrp_context_set_downsampling on, below, the mask is made on the device instead and a non-NULL keep[c] is MRP_ERR_ARG).  In the extraction's ascending entry order the LAST entry of a variant that takes part
  * owns the scores of its substring (the bubble lists its substrings popped, :1391-1393, and the first listed owns, :1431-1441); a
  * variant left without an entry that takes part makes no bubble (:1366-1371).
  * Errors, in this order: MRP_ERR_ARG before the context is looked at (the extraction's checks; NULL models, params, out, hap_out,
@@ -1140,6 +1142,68 @@ int mrp_phase_aligned_chunks_with_records(mrp_context *ctx, int64_t n_chunks, co
                                           mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
                                           int64_t **bubble_variant_out, mrp_filtered_out *filtered_out, int32_t **filtered_read_out,
                                           mrp_variant_records *records_out, mrp_phase_aligned_records_stats *stats);
+
+/* ---- downsampling to maxDepth inside the aligned one-call path -----------------------------------------
+ * The step of phase.c:360-382, downsampleBamChunkReadWithVcfEntrySubstringsViaFullReadLengthLikelihood (htsIntegration.c:1141-1216),
+ * which the composites otherwise take from the caller as `keep`.
+ *   The definition, for one chunk.  V = n_variants (stList_length(chunkVcfEntries), :1162: every variant, with or without substrings);
+ * per MRP_READ_KEPT read, in ascending read index (the order of `reads`), l = read_n_substrings (:1157-1158; in the SV split the one
+ * count over both classes) and h = alnReadLength (fullReadLength, :1160, :1859; getAlignedReadLength3 with boundaryAtMatch = FALSE,
+ * :37-120, both taken as the reference's (int)); total = sum of l; D = max_depth > 0.
+ *   - shallow chunk: the reference's own fp64 test 1.0 * total / V < D (:1163-1170) holds: nobody is discarded, p = 1, no draw is used
+ *     (V > 0 and total == 0 is shallow; V == 0 never is: the quotient is inf or nan);
+ *   - no variants, V == 0 (:1174-1186): every read is discarded, p = 0 (vacuous for an extraction's result: no read is kept in a
+ *     chunk without variants, :1855);
+ *   - downsampled chunk: T = D * V and p is the optimum of the LP of computeReadProbsByLengthAndSecondMetric (:957-1011), maximise
+ *     sum p h subject to sum p l = T, 0 <= p <= 1 -- a fractional knapsack, taken in closed form: a read with l == 0 has p = 1 if h > 0,
+ *     else 0; the others are ordered by h / l descending (h_i l_j against h_j l_i in 64-bit integers; equal ratios by ascending read
+ *     index -- an assumption: the optimum is not unique among equal ratios and lp_solve picks some vertex), and with B_i the sum of l
+ *     over the reads ordered before read i, p_i = 1 if B_i + l_i <= T, (T - B_i) / l_i if B_i < T (one correctly rounded fp64
+ *     division of two exact integers), else 0; if total <= T every p is 1.
+ *   A kept read stays iff u_k < p (:1201), k its rank among the chunk's kept reads (the order the reference draws in) and
+ * u_k = mrp_downsample_draw(seed, overlap_start, overlap_end, k): sonLib's st_random cannot be reproduced (and under OpenMP the
+ * reference's own stream depends on thread timing), so the draw is counter based and a chunk's draws depend on the chunk alone.
+ *   keep_out[r] = 1 iff read r is MRP_READ_KEPT and stays; prob_out[r] = p, 0.0 for a read that is not MRP_READ_KEPT. */
+typedef struct mrp_downsampling_stats {
+    int64_t chunks;             /* chunks the decision was made for */
+    int64_t chunks_downsampled; /* of these, the ones that were not shallow */
+    int64_t reads_discarded;    /* MRP_READ_KEPT reads whose mask byte is clear */
+    int64_t bytes_downloaded;   /* what came back for it: 1 B per read and 4 B per chunk (the seam: 9 B per read, prob_out too) */
+    double downsample_ms;       /* HIP events around the kernel */
+} mrp_downsampling_stats;
+/* the draw: z = mix(mix(mix(seed ^ overlap_start) ^ overlap_end) ^ k), mix the splitmix64 finaliser (z += 0x9E3779B97F4A7C15;
+ * z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31), u = (z >> 11) * 2^-53: in [0, 1),
+ * integer work and one exact conversion -- host and device agree bit for bit */
+double mrp_downsample_draw(uint64_t seed, int64_t overlap_start, int64_t overlap_end, int64_t k);
+/* host only: h of every read of the chunk from its CIGAR as the extraction's walk bound computes it (l_qseq - start clip - end clip
+ * + deletions - insertions, N ops left out), cast to int32; 0 for a read without bases or CIGAR.  MRP_ERR_ARG for NULL arguments. */
+int mrp_aln_read_lengths(const mrp_aligned_chunk *chunk, int32_t *out);
+/* host only: the definition above over one extracted chunk (the primary extraction: the one over the rest's variants takes no part,
+ * phase.c:364-365), for a caller who chains the single calls -- and the contract the composites are held to.  keep_out (n_reads
+ * bytes) is required; prob_out (n_reads) and downsampled_out (1: the chunk was not shallow) may be NULL.  MRP_ERR_ARG: a NULL x,
+ * keep_out or array, max_depth <= 0, a negative read_n_substrings. */
+int mrp_downsample_keep_from_extracted(const mrp_extracted_chunk *x, const int32_t *aln_read_length, int64_t max_depth, uint64_t seed,
+                                       int64_t overlap_start, int64_t overlap_end, uint8_t *keep_out, double *prob_out, int32_t *downsampled_out);
+/* The kernel's public seam: the definition for n_chunks chunks in one launch, a workgroup per chunk.  Chunk c owns reads
+ * [first[c], first[c] + n_reads[c]) of l, h and status (ranges inside [0, n_total), n_total = the largest first[c] + n_reads[c]);
+ * V[c], overlap_start[c], overlap_end[c] per chunk.  prob_out and keep_out (n_total each; prob_out may be NULL) are written for the
+ * reads of the chunks and are bit for bit the host definition's; stats may be NULL.  MRP_ERR_ARG (before the context is looked at)
+ * for NULL arrays, negative sizes, l or V, max_depth <= 0, overlapping or descending chunk ranges; MRP_ERR_NO_DEVICE for a NULL context. */
+int mrp_downsample_reads(mrp_context *ctx, int64_t n_chunks, const int64_t *n_reads, const int64_t *first, const int32_t *l, const int32_t *h,
+                         const uint8_t *status, const int64_t *V, int64_t max_depth, uint64_t seed, const int64_t *overlap_start,
+                         const int64_t *overlap_end, double *prob_out, uint8_t *keep_out, mrp_downsampling_stats *stats);
+/* max_depth > 0 (polish.maxDepth; 32 or 64 in every shipped parameter file): mrp_phase_aligned_chunks, _with_filtered and
+ * _with_records make the mask on the device, between the extraction and the owners kernel, from the extraction's per-read state where
+ * it lies in HBM, and give bit for bit what the same call gives when keep[c] comes from mrp_downsample_keep_from_extracted over chunk
+ * c's primary extraction; the discards become filtered reads of kind (ii).  A non-NULL keep[c] is then MRP_ERR_ARG (among the
+ * argument checks, before the context is looked at).  front_bytes_downloaded grows by exactly 1 B per read of the call's chunks and
+ * 4 B per chunk.  0 (default): off, every launch, byte and output as before; negative: MRP_ERR_ARG.  mrp_haplotag_aligned_chunks
+ * (no downsampling in tagFromPhasedVcf.c) and the *_on_devices forms ignore the setting. */
+int mrp_context_set_downsampling(mrp_context *ctx, int64_t max_depth, uint64_t seed);
+/* the same for every lane's context, present and future, of a queue: honoured by mrp_queue_phase_aligned_chunks(_with_filtered) */
+int mrp_queue_set_downsampling(mrp_queue *q, int64_t max_depth, uint64_t seed);
+/* what the last composite call on ctx (or mrp_downsample_reads) did for the downsampling; zeros when the setting was off */
+int mrp_context_last_downsampling(mrp_context *ctx, mrp_downsampling_stats *out);
 
 /* From the records of a contig's chunks (in genome order) to what mrp_phase_sets takes, host only.  Per chunk c: records[c]; variant_pos[c]
  * / n_alleles[c] (records[c].n_primary entries) and fvariant_pos[c] / fn_alleles[c] (n_filtered entries): positions and allele counts of

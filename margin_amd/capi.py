@@ -47,6 +47,8 @@ EXPORTED_SYMBOLS = [
     "mrp_context_set_wide_pairs", "mrp_context_wide_pair_count", "mrp_queue_set_wide_pairs", "mrp_queue_wide_pair_count", "mrp_pair_diagonal_width",
     "mrp_context_set_sv_split", "mrp_queue_set_sv_split", "mrp_mark_structural_variants",
     "mrp_variant_records_from_extracted", "mrp_phase_aligned_chunks_with_records", "mrp_variants_from_records",
+    "mrp_context_set_downsampling", "mrp_queue_set_downsampling", "mrp_context_last_downsampling", "mrp_downsample_draw", "mrp_aln_read_lengths",
+    "mrp_downsample_keep_from_extracted", "mrp_downsample_reads",
 ]
 
 
@@ -293,6 +295,11 @@ class ExtractStats(C.Structure):
                 ("bytes_uploaded", C.c_int64), ("host_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class DownsamplingStats(C.Structure):
+    _fields_ = [("chunks", C.c_int64), ("chunks_downsampled", C.c_int64), ("reads_discarded", C.c_int64), ("bytes_downloaded", C.c_int64),
+                ("downsample_ms", C.c_double)]
+
+
 class HaplotagAlignedStats(C.Structure):
     _fields_ = [("extract", ExtractStats), ("pairhmm", PairHmmStats), ("sites", C.c_int64), ("active_sites", C.c_int64), ("entries", C.c_int64),
                 ("owners", C.c_int64), ("bytes_downloaded", C.c_int64), ("owners_ms", C.c_double), ("total_ms", C.c_double)]
@@ -420,6 +427,14 @@ def load():
     L.mrp_context_set_sv_split.argtypes = [vp, C.c_int]
     L.mrp_queue_set_sv_split.argtypes = [vp, C.c_int]
     L.mrp_mark_structural_variants.argtypes = [P(AlignedChunk), i64, vp]
+    L.mrp_context_set_downsampling.argtypes = [vp, i64, C.c_uint64]
+    L.mrp_queue_set_downsampling.argtypes = [vp, i64, C.c_uint64]
+    L.mrp_context_last_downsampling.argtypes = [vp, P(DownsamplingStats)]
+    L.mrp_downsample_draw.argtypes = [C.c_uint64, i64, i64, i64]
+    L.mrp_downsample_draw.restype = C.c_double
+    L.mrp_aln_read_lengths.argtypes = [P(AlignedChunk), vp]
+    L.mrp_downsample_keep_from_extracted.argtypes = [P(ExtractedChunk), vp, i64, C.c_uint64, i64, i64, vp, vp, P(i32)]
+    L.mrp_downsample_reads.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, C.c_uint64, vp, vp, vp, vp, P(DownsamplingStats)]
     L.mrp_forward_probabilities.argtypes = [vp, vp, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, P(PairHmmStats)]
     L.mrp_allele_read_supports.argtypes = [vp, P(PairHmm), P(PairHmm), i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, P(PairHmmStats)]
     L.mrp_partition_reads_by_haplotype.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, i64, vp, vp, vp, P(PairHmmStats)]
@@ -512,6 +527,16 @@ class Context:
     def set_sv_split(self, on):
         """mrp_context_set_sv_split: indel_size_for_sv_handling > 0 runs the extraction's walk per class of variant (small, structural), not refused"""
         _check(load().mrp_context_set_sv_split(self.h, int(bool(on))))
+
+    def set_downsampling(self, max_depth: int, seed: int = 0):
+        """mrp_context_set_downsampling: max_depth > 0 makes the aligned composites' downsampling mask on the device (0: off); keeps=... is then refused"""
+        _check(load().mrp_context_set_downsampling(self.h, int(max_depth), int(seed) & (2**64 - 1)))
+
+    def last_downsampling(self) -> "DownsamplingStats":
+        """mrp_context_last_downsampling: what the last composite call (or downsample_reads) on this context did for the downsampling"""
+        st = DownsamplingStats()
+        _check(load().mrp_context_last_downsampling(self.h, C.byref(st)))
+        return st
 
     def wide_pair_count(self):
         """mrp_context_wide_pair_count -> (pairs, dp cells) the wide kernel has taken on this context"""
@@ -949,6 +974,10 @@ class Queue:
     def set_sv_split(self, on):
         """mrp_queue_set_sv_split: Context.set_sv_split for every lane's context and the queue's up-front mode check"""
         _check(load().mrp_queue_set_sv_split(self.h, int(bool(on))))
+
+    def set_downsampling(self, max_depth: int, seed: int = 0):
+        """mrp_queue_set_downsampling: Context.set_downsampling for every lane's context and the queue's up-front checks"""
+        _check(load().mrp_queue_set_downsampling(self.h, int(max_depth), int(seed) & (2**64 - 1)))
 
     def wide_pair_count(self):
         """mrp_queue_wide_pair_count -> (pairs, dp cells), summed over the lanes"""
@@ -1649,6 +1678,49 @@ def extract_read_substrings(ctx: Optional[Context], chunks, options: Optional[di
         res.append(d)
     L.mrp_free(C.cast(out, C.c_void_p))
     return res, st
+
+
+def downsample_draw(seed: int, overlap_start: int, overlap_end: int, k: int) -> float:
+    """mrp_downsample_draw: the counter-based u_k of a chunk, in [0, 1)"""
+    return float(load().mrp_downsample_draw(int(seed) & (2**64 - 1), int(overlap_start), int(overlap_end), int(k)))
+
+
+def aln_read_lengths(chunk, struct=None) -> np.ndarray:
+    """mrp_aln_read_lengths -> alnReadLength per read of the chunk (int32), as the extraction's walk bound computes it"""
+    S, keep = struct if struct is not None else aligned_chunk_struct(chunk)
+    out = np.zeros(int(S.n_reads), np.int32)
+    _check(load().mrp_aln_read_lengths(C.byref(S), out.ctypes.data if out.size else None))
+    return out
+
+
+def downsample_keep_from_extracted(x: dict, aln_read_length, max_depth: int, seed: int, overlap_start: int, overlap_end: int):
+    """mrp_downsample_keep_from_extracted -> (keep uint8 [n_reads], prob float64 [n_reads], downsampled bool): the host definition of the
+    downsampling to maxDepth over one extract_read_substrings result"""
+    X, hold = extracted_struct(x)
+    h = np.ascontiguousarray(aln_read_length, np.int32)
+    n = int(X.n_reads)
+    assert h.size == n
+    keep, prob, did = np.zeros(n, np.uint8), np.zeros(n, np.float64), C.c_int32(0)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    _check(load().mrp_downsample_keep_from_extracted(C.byref(X), ptr(h), int(max_depth), int(seed) & (2**64 - 1), int(overlap_start), int(overlap_end),
+                                                     ptr(keep), ptr(prob), C.byref(did)))
+    return keep, prob, bool(did.value)
+
+
+def downsample_reads(ctx: Optional[Context], n_reads, first, l, h, status, V, max_depth: int, seed: int, overlap_start, overlap_end):
+    """mrp_downsample_reads, the kernel's seam: many chunks in one launch -> (keep uint8, prob float64, DownsamplingStats), the arrays over
+    the n_total = max(first + n_reads) reads of the call.  ctx None passes a NULL context (MRP_ERR_NO_DEVICE)."""
+    a64 = lambda a: np.ascontiguousarray(a, np.int64)
+    n_reads, first, V, os_, oe = a64(n_reads), a64(first), a64(V), a64(overlap_start), a64(overlap_end)
+    l, h, status = np.ascontiguousarray(l, np.int32), np.ascontiguousarray(h, np.int32), np.ascontiguousarray(status, np.uint8)
+    n = int(n_reads.size)
+    n_total = max(int((first + n_reads).max()), 0) if n else 0
+    assert l.size >= n_total and h.size >= n_total and status.size >= n_total
+    keep, prob, st = np.zeros(n_total, np.uint8), np.zeros(n_total, np.float64), DownsamplingStats()
+    ptr = lambda a: a.ctypes.data if a.size else None
+    _check(load().mrp_downsample_reads(ctx.h if ctx else None, n, ptr(n_reads), ptr(first), ptr(l), ptr(h), ptr(status), ptr(V), int(max_depth),
+                                       int(seed) & (2**64 - 1), ptr(os_), ptr(oe), ptr(prob), ptr(keep), C.byref(st)))
+    return keep, prob, st
 
 
 def extracted_struct(x: dict):

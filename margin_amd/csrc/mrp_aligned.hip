@@ -183,6 +183,11 @@ struct AlignedFront {
     const uint8_t *k_status = nullptr;
     const int64_t *k_first = nullptr, *k_len = nullptr;
     const int32_t *k_read = nullptr, *k_owner = nullptr;
+    /* a mask made on the device (the downsampling, PaRun::downsampled_owners): d_take holds it before the owners kernel; its first
+     * mask_reads bytes and the mask_chunks per-chunk flags behind d_mask_flag come back with the rest (k_flag is not aligned) */
+    int64_t mask_reads = -1, mask_chunks = 0;
+    const int32_t *d_mask_flag = nullptr;
+    const uint8_t *k_take = nullptr, *k_flag = nullptr;
 
     AlignedFront(const char *w, mrp_context *c, int64_t n, const mrp_aligned_chunk *ch) : who(w), ctx(c), n_chunks(n), chunks(ch) {}
     ~AlignedFront() {
@@ -280,22 +285,25 @@ int AlignedFront::extract() {
     return MRP_OK;
 }
 
-/* the owners on the device (take: NULL, or per read of the call whether it may take part); back come the per-read status and per entry
- * its read, length and owner -- not the symbols */
+/* the owners on the device (take: NULL, or per read of the call whether it may take part; mask_reads >= 0: the mask is in d_take
+ * already); back come the per-read status and per entry its read, length and owner -- not the symbols -- and of a mask made on the
+ * device its first mask_reads bytes and the chunks' flags */
 int AlignedFront::owners(const HostVec<uint8_t> *take) {
     const int64_t n_ent = D.n_entries, n_var = D.n_variants, n_reads = D.n_reads;
+    const bool device_mask = mask_reads >= 0;
     PHM_HIP(d_key.alloc((size_t) n_ent));
     PHM_HIP(d_owner.alloc((size_t) n_ent));
     if (take) PHM_HIP(d_take.upload(*take, s));
     PHM_HIP(hipEventRecord(ev[0], s));
     if (n_ent > 0) {
         hipLaunchKernelGGL(ha_owners_kernel, dim3((unsigned) std::min<int64_t>(n_var, 65536)), dim3(PHM_WAVE), 0, s, D.entry_first, n_var, D.entry_read,
-                           D.read_status, D.entry_len, D.entry_off, D.symbols, take ? (const uint8_t *) d_take.p : nullptr, d_key.p, d_owner.p);
+                           D.read_status, D.entry_len, D.entry_off, D.symbols, take || device_mask ? (const uint8_t *) d_take.p : nullptr, d_key.p, d_owner.p);
         PHM_HIP(hipGetLastError());
     }
     PHM_HIP(hipEventRecord(ev[1], s));
     const size_t b_first = 0, b_len = b_first + 8 * ((size_t) n_var + 1), b_read = b_len + 8 * (size_t) n_ent, b_owner = b_read + 4 * (size_t) n_ent,
-                 b_status = b_owner + 4 * (size_t) n_ent, b_end = b_status + (size_t) n_reads;
+                 b_status = b_owner + 4 * (size_t) n_ent, b_take = b_status + (size_t) n_reads, b_flag = b_take + (device_mask ? (size_t) mask_reads : 0),
+                 b_end = b_flag + 4 * (size_t) mask_chunks;
     PHM_HIP(h_back.reserve(b_end));
     uint8_t *hk = (uint8_t *) h_back.p;
     PHM_HIP(hipMemcpyAsync(hk + b_first, D.entry_first, 8 * ((size_t) n_var + 1), hipMemcpyDeviceToHost, s));
@@ -305,8 +313,11 @@ int AlignedFront::owners(const HostVec<uint8_t> *take) {
         PHM_HIP(hipMemcpyAsync(hk + b_owner, d_owner.p, 4 * (size_t) n_ent, hipMemcpyDeviceToHost, s));
     }
     if (n_reads) PHM_HIP(hipMemcpyAsync(hk + b_status, D.read_status, (size_t) n_reads, hipMemcpyDeviceToHost, s));
+    if (device_mask && mask_reads) PHM_HIP(hipMemcpyAsync(hk + b_take, d_take.p, (size_t) mask_reads, hipMemcpyDeviceToHost, s));
+    if (mask_chunks) PHM_HIP(hipMemcpyAsync(hk + b_flag, d_mask_flag, 4 * (size_t) mask_chunks, hipMemcpyDeviceToHost, s));
     PHM_HIP(hipStreamSynchronize(s));
     downloaded += (int64_t) b_end;
+    if (device_mask) { k_take = hk + b_take; k_flag = hk + b_flag; }
     k_first = (const int64_t *) (hk + b_first);
     k_len = (const int64_t *) (hk + b_len);
     k_read = (const int32_t *) (hk + b_read);
@@ -531,16 +542,29 @@ struct PaRun : AlignedFront {
      * second half are the same reads over the rests' variants */
     const int64_t n_front;
     std::vector<int64_t> entry_of_sub; /* with the back half: substring of the call -> its entry */
+    /* the downsampling to maxDepth (mrp_context_set_downsampling): > 0 makes the mask on the device */
+    int64_t max_depth = 0;
+    uint64_t downsampling_seed = 0;
+    hipEvent_t dev[2] = {nullptr, nullptr}; /* around its kernel */
+    HostVec<MrpDsChunk> ds_chunks;
+    DevBuf<MrpDsChunk> d_ds_chunks{arrays};
+    DevBuf<int32_t> d_ds_flag{arrays};
 
     PaRun(const char *w, mrp_context *c, int64_t n, const mrp_aligned_chunk *ch, const char *const *const *names, const uint8_t *const *k,
           mrp_phase_aligned_stats *st, int64_t front)
         : AlignedFront(w, c, n, ch), read_names(names), keep(k), stats(st), n_front(front) {}
     ~PaRun() {
+        if (s) (void) hipStreamSynchronize(s); /* before ds_chunks goes */
+        for (hipEvent_t x : dev)
+            if (x) (void) hipEventDestroy(x);
         for (int64_t *p : bv_out) free(p);
     }
+    /* read r of chunk c passes the mask: the one made on the device, or the caller's */
+    bool taken(int64_t c, int64_t r) const { return k_take ? k_take[D.read_first[c] + r] != 0 : (!keep || !keep[c] || keep[c][r]); }
     int check(const mrp_extract_options *options, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
               const mrp_params *params, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, int sv_split);
     int masked_owners();
+    int downsampled_owners();
     int strings_and_pairs(int64_t sv_threshold);
     int anchors();
     int classify(const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion);
@@ -562,11 +586,16 @@ int PaRun::check(const mrp_extract_options *options, const mrp_pair_hmm *forward
         for (int64_t r = 0; r < C.n_reads; r++)
             if (!read_names[c][r]) return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: read %lld has no name", who, (long long) c, (long long) r);
     }
+    for (int64_t c = 0; max_depth > 0 && keep && c < n_front; c++)
+        if (keep[c])
+            return mrp_set_error(MRP_ERR_ARG, "%s: chunk %lld: a keep mask while the downsampling is on (mrp_context_set_downsampling): the mask is made on the device",
+                                 who, (long long) c);
     return mrp_extract_run_check_modes(X, sv_split);
 }
 
 /* the owners among the kept reads the caller's mask lets through (one byte per read of the call; no mask anywhere: none uploaded) */
 int PaRun::masked_owners() {
+    if (max_depth > 0) return downsampled_owners();
     bool any = n_front < n_chunks; /* (the second half's records take no part in the front) */
     for (int64_t c = 0; keep && c < n_front; c++) any = any || (keep[c] && chunks[c].n_reads > 0);
     if (!any) return owners(nullptr);
@@ -574,6 +603,29 @@ int PaRun::masked_owners() {
     for (int64_t c = 0; c < n_chunks; c++)
         for (int64_t r = 0; r < chunks[c].n_reads; r++) take[(size_t) (D.read_first[c] + r)] = c >= n_front ? 0 : (keep && keep[c] ? (keep[c][r] != 0) : 1);
     return owners(&take);
+}
+
+/* the mask of phase.c:360-382 made on the device, between the gather and the owners kernel: a workgroup per chunk of the front reads the
+ * statuses, the per-read entry counts and the walk bounds where the extraction left them (nothing per read is uploaded: 40 B per chunk
+ * are) and writes the bytes the owners kernel reads as `take`; the second half's records take no part and get 0 */
+int PaRun::downsampled_owners() {
+    const int64_t n_mask = D.read_first[n_front];
+    ds_chunks.resize((size_t) n_front);
+    for (int64_t c = 0; c < n_front; c++)
+        ds_chunks[(size_t) c] = MrpDsChunk{D.read_first[c], chunks[c].n_reads, chunks[c].n_variants, chunks[c].overlap_start, chunks[c].overlap_end};
+    for (hipEvent_t &x : dev) PHM_HIP(hipEventCreate(&x));
+    PHM_HIP(d_ds_chunks.upload(ds_chunks, s));
+    PHM_HIP(d_ds_flag.alloc((size_t) n_front));
+    PHM_HIP(d_take.alloc((size_t) D.n_reads));
+    if (D.n_reads > n_mask) PHM_HIP(hipMemsetAsync(d_take.p + n_mask, 0, (size_t) (D.n_reads - n_mask), s));
+    PHM_HIP(hipEventRecord(dev[0], s));
+    PHM_HIP(mrp_downsample_launch(s, n_front, d_ds_chunks.p, MrpDsIn{nullptr, nullptr, D.read_entry_first, D.read_limit, D.read_limit_stride}, D.read_status,
+                                  max_depth, downsampling_seed, nullptr, d_take.p, d_ds_flag.p));
+    PHM_HIP(hipEventRecord(dev[1], s));
+    mask_reads = n_mask;
+    mask_chunks = n_front;
+    d_mask_flag = d_ds_flag.p;
+    return owners(nullptr);
 }
 
 /* bubbleGraph_constructFromVCFAndBamChunkReadVcfEntrySubstrings (bubbleGraph.c:1338-1400) over the device pool: a variant with an entry
@@ -694,6 +746,21 @@ int PaRun::classify(const mrp_pair_hmm *forward_model, const mrp_pair_hmm *rever
 
 /* after the string run has handed its results over: the bubbles' variants, the stats, the device arrays back to the pool */
 int PaRun::hand_over(int64_t **bubble_variant_out) {
+    mrp_downsampling_stats &ds = ctx->last_downsampling;
+    ds = mrp_downsampling_stats{};
+    if (max_depth > 0) {
+        float ms = 0.f;
+        PHM_HIP(hipEventElapsedTime(&ms, dev[0], dev[1]));
+        ds.downsample_ms = ms;
+        ds.chunks = n_front;
+        for (int64_t c = 0; c < n_front; c++) {
+            int32_t flag = 0;
+            memcpy(&flag, k_flag + 4 * c, 4);
+            ds.chunks_downsampled += flag != 0;
+            for (int64_t r = 0; r < chunks[c].n_reads; r++) ds.reads_discarded += k_status[D.read_first[c] + r] == MRP_READ_KEPT && !taken(c, r);
+        }
+        ds.bytes_downloaded = mask_reads + 4 * mask_chunks;
+    }
     if (stats) {
         float ms = 0.f;
         PHM_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
@@ -817,7 +884,7 @@ int PfRun::rests() {
         const mrp_aligned_chunk_rest &Rc = rest[c];
         RestArrays &A = ra[(size_t) c];
         const int64_t nr = C.n_reads, nv = Rc.n_variants, r1 = D.read_first[c], r2 = D.read_first[n + c];
-        auto primary = [&](int64_t r) { return k_status[r1 + r] == MRP_READ_KEPT && (!keep || !keep[c] || keep[c][r]); };
+        auto primary = [&](int64_t r) { return k_status[r1 + r] == MRP_READ_KEPT && taken(c, r); };
         auto kind = [&](int64_t r) {
             if (k_status[r1 + r] == MRP_READ_FILTERED) return 0;
             if (k_status[r1 + r] == MRP_READ_KEPT) return primary(r) ? -1 : 1;
@@ -927,7 +994,7 @@ int PfRun::record_sites() {
         const mrp_aligned_chunk &C = chunks[c];
         const mrp_aligned_chunk_rest &Rc = rest[c];
         const int64_t r1 = D.read_first[c], r2 = D.read_first[n + c];
-        auto primary = [&](int64_t r) { return k_status[r1 + r] == MRP_READ_KEPT && (!keep || !keep[c] || keep[c][r]); };
+        auto primary = [&](int64_t r) { return k_status[r1 + r] == MRP_READ_KEPT && taken(c, r); };
         std::vector<int32_t> bubble_of((size_t) C.n_variants, -1);
         const std::vector<int64_t> &bv = arr[(size_t) c].bubble_variant;
         for (size_t b = 0; b < bv.size(); b++) bubble_of[(size_t) bv[b]] = (int32_t) b;
@@ -1063,7 +1130,10 @@ struct mrp_aligned_front {
     PfRun R;
     mrp_aligned_front(const char *who, double t0, const mrp_aligned_args &args, mrp_phase_aligned_stats *st, mrp_phase_aligned_filtered_stats *fst)
         : a(args), t_begin(t0), stats(st), fstats(fst), records(pa_records(args)),
-          R(who, nullptr, args.n_chunks, args.rest ? records.data() : args.chunks, args.rest, args.read_names, args.keep, st) {}
+          R(who, nullptr, args.n_chunks, args.rest ? records.data() : args.chunks, args.rest, args.read_names, args.keep, st) {
+        R.max_depth = args.max_depth;
+        R.downsampling_seed = args.downsampling_seed;
+    }
 };
 
 /* every check of the call that needs no context, in the one call's order (every MRP_ERR_ARG comes before the refused modes); the
@@ -1209,7 +1279,7 @@ extern "C" int mrp_phase_aligned_chunks(mrp_context *ctx, int64_t n_chunks, cons
     if (stats) memset(stats, 0, sizeof(*stats));
     const mrp_aligned_args a{n_chunks, chunks, nullptr, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr,
-                             ctx ? ctx->sv_split : 0}; /* (a NULL context counts as off) */
+                             ctx ? ctx->sv_split : 0, nullptr, nullptr, ctx ? ctx->max_depth : 0, ctx ? ctx->downsampling_seed : 0}; /* (a NULL context counts as off) */
     return pa_phase_chunks("mrp_phase_aligned_chunks", t_begin, ctx, a, stats, nullptr);
 }
 
@@ -1231,7 +1301,7 @@ extern "C" int mrp_phase_aligned_chunks_with_records(mrp_context *ctx, int64_t n
     }
     const mrp_aligned_args a{n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
-                             filtered_read_out, ctx ? ctx->sv_split : 0, records_out, stats};
+                             filtered_read_out, ctx ? ctx->sv_split : 0, records_out, stats, ctx ? ctx->max_depth : 0, ctx ? ctx->downsampling_seed : 0};
     return pa_phase_chunks(who, t_begin, ctx, a, stats ? &stats->filtered.aligned : nullptr, stats ? &stats->filtered : nullptr);
 }
 
@@ -1250,6 +1320,6 @@ extern "C" int mrp_phase_aligned_chunks_with_filtered(mrp_context *ctx, int64_t 
     if (n_chunks > 0) memset(filtered_out, 0, sizeof(*filtered_out) * (size_t) n_chunks);
     const mrp_aligned_args a{n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
-                             filtered_read_out, ctx ? ctx->sv_split : 0};
+                             filtered_read_out, ctx ? ctx->sv_split : 0, nullptr, nullptr, ctx ? ctx->max_depth : 0, ctx ? ctx->downsampling_seed : 0};
     return pa_phase_chunks(who, t_begin, ctx, a, stats ? &stats->aligned : nullptr, stats);
 }

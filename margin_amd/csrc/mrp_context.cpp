@@ -174,6 +174,19 @@ int mrp_context_set_sv_split(mrp_context *ctx, int on) {
     return MRP_OK;
 }
 
+int mrp_context_set_downsampling(mrp_context *ctx, int64_t max_depth, uint64_t seed) {
+    if (!ctx) return mrp_set_error(MRP_ERR_ARG, "mrp_context_set_downsampling: context is NULL");
+    if (max_depth < 0) return mrp_set_error(MRP_ERR_ARG, "mrp_context_set_downsampling: negative max_depth");
+    ctx->max_depth = max_depth;
+    ctx->downsampling_seed = seed;
+    return MRP_OK;
+}
+int mrp_context_last_downsampling(mrp_context *ctx, mrp_downsampling_stats *out) {
+    if (!ctx || !out) return mrp_set_error(MRP_ERR_ARG, "mrp_context_last_downsampling: null argument");
+    *out = ctx->last_downsampling;
+    return MRP_OK;
+}
+
 int mrp_context_set_wide_pairs(mrp_context *ctx, int on) {
     if (!ctx) return mrp_set_error(MRP_ERR_ARG, "mrp_context_set_wide_pairs: context is NULL");
     ctx->wide_pairs = on != 0;

@@ -38,6 +38,7 @@
 #include <atomic>
 #include <chrono>
 #include <climits>
+#include <cstddef>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -817,6 +818,10 @@ void mrp_extract_run_device(const mrp_extract_run *R, mrp_extract_device *D) {
     D->entry_len = R->d_flen.p;
     D->entry_off = R->d_foff.p;
     D->symbols = R->g_pool;
+    D->read_entry_first = R->d_eoff.p;
+    static_assert(sizeof(ExState) % sizeof(int64_t) == 0 && offsetof(ExState, limit) % sizeof(int64_t) == 0, "the limit is read as a strided int64 array");
+    D->read_limit = (const int64_t *) ((const uint8_t *) R->d_state.p + offsetof(ExState, limit));
+    D->read_limit_stride = (int64_t) (sizeof(ExState) / sizeof(int64_t));
     D->read_first = R->rb.data();
     D->variant_first = R->vb.data();
 }

@@ -369,6 +369,9 @@ struct mrp_context {
     int test_hooks = 0;   /* mrp_context_set_test_hooks (test suite only) */
     int wide_pairs = 0;   /* mrp_context_set_wide_pairs: pairs beyond the pair-per-wave kernel's 2 048 cells go to the pair-per-workgroup kernel */
     int sv_split = 0;     /* mrp_context_set_sv_split: indel_size_for_sv_handling > 0 splits the extraction's walk by class of variant */
+    int64_t max_depth = 0;   /* mrp_context_set_downsampling: > 0 makes the aligned composites' mask on the device (0: off) */
+    uint64_t downsampling_seed = 0;
+    mrp_downsampling_stats last_downsampling{}; /* mrp_context_last_downsampling */
     int64_t wide_pair_count = 0, wide_cell_count = 0; /* what that kernel has taken on this context (mrp_context_wide_pair_count) */
     int phase_groups = 0; /* concurrent batches of mrp_phase_reads_many (mrp_context_set_phase_groups); 0: chosen by batch size */
     std::vector<mrp_context *> siblings; /* further contexts on the same device (concurrent batches of mrp_phase_reads_many) */
@@ -597,6 +600,11 @@ struct mrp_extract_device { /* what the second half leaves in HBM; read indices 
     const int64_t *entry_len;
     const int64_t *entry_off;    /* n_entries + 1: the scan of entry_len, from 0 */
     const uint8_t *symbols;      /* entry e's symbols: symbols[entry_off[e] .. + entry_len[e]) (= pool + base) */
+    /* per read, as the first half left them (what the downsampling reads, mrp_downsample.hip): read r saved
+     * read_entry_first[r + 1] - read_entry_first[r] substrings (n_reads + 1, from 0), and the walk bound alnReadLength + 1 of a read that
+     * is not MRP_READ_DROPPED is read_limit[r * read_limit_stride] (never written for a dropped read) */
+    const int64_t *read_entry_first, *read_limit;
+    int64_t read_limit_stride;
     const int64_t *read_first, *variant_first; /* host, n_chunks + 1: chunk c's share of the call's reads / variants */
 };
 mrp_extract_run *mrp_extract_run_create(const char *who, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_extract_options *options,
@@ -664,6 +672,9 @@ struct mrp_aligned_args {
     /* mrp_phase_aligned_chunks_with_records only (NULL otherwise): the records and their share of the stats */
     mrp_variant_records *records_out;
     mrp_phase_aligned_records_stats *records_stats;
+    /* the context's or the queue's setting at the call (mrp_context_set_downsampling; 0: off): the checks need no context */
+    int64_t max_depth;
+    uint64_t downsampling_seed;
 };
 int mrp_aligned_chunks_check(const char *who, const mrp_aligned_args *args);
 int mrp_aligned_front_create(const char *who, double t_begin_ms, const mrp_aligned_args *args, mrp_phase_aligned_stats *stats,
@@ -697,6 +708,18 @@ int mrp_haplotag_front_create(const mrp_haplotag_args *args, mrp_haplotag_aligne
 int mrp_haplotag_front_stage(mrp_context *ctx, mrp_haplotag_front *front);
 int mrp_haplotag_front_run(mrp_haplotag_front *front);
 void mrp_haplotag_front_destroy(mrp_haplotag_front *front);
+/* The downsampling to maxDepth on the device (mrp_downsample.hip): one workgroup per chunk over device arrays,
+ * queued on s.  A chunk owns reads [first, first + n_reads) of the call; the per-read inputs are either the seam's (l, h) or the
+ * extraction's own (entry_first, limit: mrp_extract_device's read_entry_first / read_limit).  d_keep gets a byte per read of the chunks,
+ * d_prob (may be NULL) its probability, d_downsampled per chunk whether it was not shallow. */
+struct MrpDsChunk { int64_t first, n_reads, V, overlap_start, overlap_end; };
+struct MrpDsIn {
+    const int32_t *l, *h;                    /* NULL: read the extraction's */
+    const int64_t *entry_first, *limit;
+    int64_t limit_stride;
+};
+hipError_t mrp_downsample_launch(hipStream_t s, int64_t n_chunks, const MrpDsChunk *d_chunks, const MrpDsIn &in, const uint8_t *d_status, int64_t max_depth,
+                                 uint64_t seed, double *d_prob, uint8_t *d_keep, int32_t *d_downsampled);
 extern "C" void mrp_batch_last_launch_ms(struct mrp_batch *b, float *pack, float *emission, float *recursion);
 
 /* development: MRP_DUP=<letters> launches the named kernel families of a resident level TWICE (they are idempotent) -- the slow-down of a

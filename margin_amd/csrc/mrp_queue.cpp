@@ -243,6 +243,8 @@ struct mrp_queue {
     int lanes = 4;
     int wide_pairs = 0; /* mrp_queue_set_wide_pairs: every lane's context gets it when the lane begins a call; the up-front checks read it */
     int sv_split = 0;   /* mrp_queue_set_sv_split: likewise */
+    int64_t max_depth = 0; /* mrp_queue_set_downsampling: likewise */
+    uint64_t downsampling_seed = 0;
 };
 
 int mrp_queue_create(const int32_t *devices, int32_t n_devices, mrp_queue **out) {
@@ -288,6 +290,16 @@ int mrp_queue_set_sv_split(mrp_queue *q, int on) {
     q->sv_split = on != 0;
     for (mrp_context *c : q->ctx)
         if (c) (void) mrp_context_set_sv_split(c, q->sv_split);
+    return MRP_OK;
+}
+
+int mrp_queue_set_downsampling(mrp_queue *q, int64_t max_depth, uint64_t seed) {
+    if (!q) return mrp_set_error(MRP_ERR_ARG, "mrp_queue_set_downsampling: queue is NULL");
+    if (max_depth < 0) return mrp_set_error(MRP_ERR_ARG, "mrp_queue_set_downsampling: negative max_depth");
+    q->max_depth = max_depth;
+    q->downsampling_seed = seed;
+    for (mrp_context *c : q->ctx)
+        if (c) (void) mrp_context_set_downsampling(c, max_depth, seed);
     return MRP_OK;
 }
 
@@ -378,6 +390,7 @@ struct QueueCall {
         if (lanes > 1) (void) mrp_context_set_grouped(q->ctx[(size_t) w], 1); /* the lanes of a device are concurrent batches of it */
         (void) mrp_context_set_wide_pairs(q->ctx[(size_t) w], q->wide_pairs);
         (void) mrp_context_set_sv_split(q->ctx[(size_t) w], q->sv_split);
+        (void) mrp_context_set_downsampling(q->ctx[(size_t) w], q->max_depth, q->downsampling_seed);
         q->ctx[(size_t) w]->calls_sharing_device = n_batches > (int64_t) n_devices ? active_lanes : 1;
         caller_pool[(size_t) w] = mrp_pool_current();
         mrp_pool_adopt(q->pools[(size_t) d]);
@@ -966,7 +979,7 @@ int mrp_queue_phase_aligned_chunks(mrp_queue *q, int64_t n_chunks, const mrp_ali
     const AlignedQueueArgs A{"mrp_queue_phase_aligned_chunks",
                              {n_chunks, chunks, nullptr, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
                               het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr,
-                              q ? q->sv_split : 0}, /* (a NULL queue counts as off) */
+                              q ? q->sv_split : 0, nullptr, nullptr, q ? q->max_depth : 0, q ? q->downsampling_seed : 0}, /* (a NULL queue counts as off) */
                              chunks_per_batch, stats};
     return queue_phase_aligned_chunks(q, A, false);
 }
@@ -981,7 +994,7 @@ int mrp_queue_phase_aligned_chunks_with_filtered(mrp_queue *q, int64_t n_chunks,
     const AlignedQueueArgs A{"mrp_queue_phase_aligned_chunks_with_filtered",
                              {n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
                               het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
-                              filtered_read_out, q ? q->sv_split : 0},
+                              filtered_read_out, q ? q->sv_split : 0, nullptr, nullptr, q ? q->max_depth : 0, q ? q->downsampling_seed : 0},
                              chunks_per_batch, stats};
     return queue_phase_aligned_chunks(q, A, true);
 }
