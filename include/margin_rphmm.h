@@ -92,6 +92,13 @@ int mrp_context_set_phase_groups(mrp_context *ctx, int groups);
  * the pair-per-workgroup pair-HMM kernel (mrp_context_set_wide_pairs) is one workgroup, so consecutive wide pairs of a call reuse
  * one workspace slice. */
 int mrp_context_set_test_hooks(mrp_context *ctx, int hooks);
+/* Test suite and probes only: the launch census of the device-resident path.  Every kernel the path picks by size class (the prune
+ * kernel's instantiations by chain mode, the prune-back kernel, the cross product + emission plans, the two-kernel cross product, the
+ * recursion's classes, the single-wave kernel, compaction, trace back, fragments) has a slot that counts how often the context and
+ * its sibling contexts launched it with work.  mrp_launch_class_name(slot) names slot 0, 1, ... and returns NULL behind the last.
+ * counts[0 .. n_counts) receives the slots' counts; n_counts must be the number of slots.  reset != 0 zeroes them after the read. */
+int mrp_context_launch_census(mrp_context *ctx, uint64_t *counts, int n_counts, int reset);
+const char *mrp_launch_class_name(int slot);
 /* size of the host worker pool (structure of the merge levels, descriptors, classification of alignment pairs): the
  * process-wide pool of contexts used directly, and EACH worker's own pool of a work queue (mrp_queue_*: one pool per device).
  * Default: min(16, hardware threads) for the process-wide pool, hardware threads / devices (2..16) per queue worker.

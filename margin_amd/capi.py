@@ -27,7 +27,7 @@ ABI_VERSION = 6  # MRP_ABI_VERSION of include/margin_rphmm.h as transcribed here
 
 EXPORTED_SYMBOLS = [
     "mrp_last_error", "mrp_version", "mrp_abi_version", "mrp_runtime_init", "mrp_device_count", "mrp_context_create", "mrp_context_destroy",
-    "mrp_context_synchronize", "mrp_context_trim", "mrp_hmm_split", "mrp_hmm_split_where_phasing_is_uncertain", "mrp_context_set_phase_groups", "mrp_context_set_test_hooks", "mrp_set_host_threads", "mrp_chunk_create", "mrp_chunk_destroy", "mrp_fb_run", "mrp_batch_create",
+    "mrp_context_synchronize", "mrp_context_trim", "mrp_hmm_split", "mrp_hmm_split_where_phasing_is_uncertain", "mrp_context_set_phase_groups", "mrp_context_set_test_hooks", "mrp_context_launch_census", "mrp_launch_class_name", "mrp_set_host_threads", "mrp_chunk_create", "mrp_chunk_destroy", "mrp_fb_run", "mrp_batch_create",
     "mrp_batch_add", "mrp_batch_upload", "mrp_batch_launch", "mrp_batch_download", "mrp_batch_destroy",
     "mrp_batch_stats", "mrp_count_bit_vectors", "mrp_emissions", "mrp_get_rp_hmms", "mrp_hmm_destroy", "mrp_free",
     "mrp_hmm_view", "mrp_hmm_forward_backward", "mrp_hmm_prune", "mrp_hmm_forward_trace_back", "mrp_phase_reads",
@@ -368,6 +368,9 @@ def load():
     L.mrp_context_trim.argtypes = [vp]
     L.mrp_context_set_phase_groups.argtypes = [vp, C.c_int]
     L.mrp_context_set_test_hooks.argtypes = [vp, C.c_int]
+    L.mrp_context_launch_census.argtypes = [vp, P(C.c_uint64), C.c_int, C.c_int]
+    L.mrp_launch_class_name.argtypes = [C.c_int]
+    L.mrp_launch_class_name.restype = C.c_char_p
     L.mrp_set_host_threads.argtypes = [C.c_int]
     L.mrp_chunk_create.argtypes = [vp, i64, vp, vp, vp, vp, i64, P(vp)]
     L.mrp_chunk_destroy.argtypes = [vp]
@@ -498,6 +501,15 @@ def _check(rc: int):
         raise MrpError(rc, load().mrp_last_error().decode())
 
 
+def launch_class_names() -> list:
+    """the launch classes of the device-resident path, as the library names them (mrp_launch_class_name: slot 0, 1, ... until NULL)"""
+    L = load()
+    names = []
+    while (name := L.mrp_launch_class_name(len(names))) is not None:
+        names.append(name.decode())
+    return names
+
+
 class Context:
     def __init__(self, device: int = 0):
         L = load()
@@ -519,6 +531,14 @@ class Context:
         allocation, bit 3 general prune chain, bit 4 one array entry per cell on unit levels, bit 5 no level is launched deferred, bit 6 the
         wide pair-HMM kernel's grid is one workgroup (include/margin_rphmm.h)"""
         _check(load().mrp_context_set_test_hooks(self.h, hooks))
+
+    def launch_census(self, reset: bool = False) -> dict:
+        """test suite and probes only: how often this context and its siblings launched each launch class of the device-resident
+        path, by the library's own slot names (mrp_launch_class_name); reset zeroes the counts after the read"""
+        names = launch_class_names()
+        counts = (C.c_uint64 * len(names))()
+        _check(load().mrp_context_launch_census(self.h, counts, len(names), int(bool(reset))))
+        return dict(zip(names, (int(c) for c in counts)))
 
     def set_wide_pairs(self, on):
         """mrp_context_set_wide_pairs: pairs whose widest diagonal exceeds 2 048 cells are aligned, not refused (up to WIDE_MAX_WIDTH / WIDE_MAX_CELLS)"""

@@ -476,6 +476,11 @@ int mrp_batch_launch(mrp_batch *b) {
     HIP_TRY(mrp_launch_sweep_i32(d, b->d_order_wide.p, (int64_t) b->order_wide.size(), t_wide, b->max_merge_wide, s));
     HIP_TRY(mrp_launch_sweep_i32(d, b->d_order_mid.p, (int64_t) b->order_mid.size(), t_mid, b->max_merge_mid, a0));
     HIP_TRY(mrp_launch_sweep_i32(d, b->d_order_narrow.p, (int64_t) b->order_narrow.size(), t_narrow, b->max_merge_narrow, a1));
+    if (b->resident) { /* the launch census counts the resident path's classes (a class without hmms is not launched) */
+        if (!b->order_wide.empty()) ctx->census.bump(census_sweep_slot(SWEEP_WIDE));
+        if (!b->order_mid.empty()) ctx->census.bump(census_sweep_slot(SWEEP_MID));
+        if (!b->order_narrow.empty()) ctx->census.bump(census_sweep_slot(SWEEP_NARROW));
+    }
     if (b->resident && mrp_dup('s')) {
         HIP_TRY(mrp_launch_sweep_i32(d, b->d_order_wide.p, (int64_t) b->order_wide.size(), t_wide, b->max_merge_wide, s));
         HIP_TRY(mrp_launch_sweep_i32(d, b->d_order_mid.p, (int64_t) b->order_mid.size(), t_mid, b->max_merge_mid, a0));

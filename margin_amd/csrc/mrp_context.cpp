@@ -168,6 +168,19 @@ int mrp_context_set_test_hooks(mrp_context *ctx, int hooks) {
     return MRP_OK;
 }
 int mrp_context_test_hooks(const mrp_context *ctx) { return ctx->test_hooks; }
+int mrp_context_launch_census(mrp_context *ctx, uint64_t *counts, int n_counts, int reset) {
+    if (!ctx || !counts || n_counts != CENSUS_SLOTS) return mrp_set_error(MRP_ERR_ARG, "mrp_context_launch_census: bad arguments (%d slots)", (int) CENSUS_SLOTS);
+    std::lock_guard<std::mutex> lock(ctx->sibling_mu);
+    for (int q = 0; q < CENSUS_SLOTS; q++) counts[q] = 0;
+    auto take = [&](mrp_context *c) {
+        for (int q = 0; q < CENSUS_SLOTS; q++)
+            counts[q] += reset ? c->census.n[q].exchange(0, std::memory_order_relaxed) : c->census.n[q].load(std::memory_order_relaxed);
+    };
+    take(ctx);
+    for (mrp_context *s_ : ctx->siblings) take(s_);
+    return MRP_OK;
+}
+const char *mrp_launch_class_name(int slot) { return census_slot_name(slot); }
 int mrp_context_set_sv_split(mrp_context *ctx, int on) {
     if (!ctx) return mrp_set_error(MRP_ERR_ARG, "mrp_context_set_sv_split: context is NULL");
     ctx->sv_split = on != 0;

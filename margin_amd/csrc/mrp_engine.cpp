@@ -941,6 +941,7 @@ static int launch_kernels(mrp_engine *e, mrp_engine_level_state *L, hipStream_t 
     mrp_batch *b = L->b;
     const int64_t n = L->n, total_cols = L->ix.total_cols;
     const size_t kept = L->final_level ? 0 : (size_t) total_cols * (size_t) e->pp.S;
+    LaunchCensus *const census = &e->ctx->census;
     if (!L->final_level) {
         ENG_TRY(L->d_kept.alloc(kept)); ENG_TRY(L->d_keptm.alloc(kept)); ENG_TRY(L->d_kept_np.alloc(kept));
         ENG_TRY(L->d_nkept.alloc((size_t) total_cols)); ENG_TRY(L->d_nkeptm.alloc((size_t) total_cols));
@@ -954,14 +955,14 @@ static int launch_kernels(mrp_engine *e, mrp_engine_level_state *L, hipStream_t 
          * partitions, the batch's own emission launch finds nothing to do */
         ENG_TRY(hipEventRecord(L->ev[0], s));
         ENG_TRY(hipEventRecord(L->ev[1], s));
-        b->pre_sweep = [L](hipStream_t st) -> hipError_t {
-            return mrp_launch_cross_emit(L->d_cc.p, L->b->dev, L->d_err.p, L->d_col_hmm.p, L->d_err_hmm.p, L->pp.max_cells, 2 * L->order.n_mini > L->n, st);
+        b->pre_sweep = [L, census](hipStream_t st) -> hipError_t {
+            return mrp_launch_cross_emit(L->d_cc.p, L->b->dev, L->d_err.p, L->d_col_hmm.p, L->d_err_hmm.p, L->pp.max_cells, 2 * L->order.n_mini > L->n, st, census);
         };
     } else {
         b->pre_sweep = nullptr;
         ENG_TRY(mrp_launch_tiles(b->d_cols.p, b->d_tilecols.p, total_cols, b->d_tiles.p, s));
         ENG_TRY(hipEventRecord(L->ev[0], s));
-        ENG_TRY(mrp_launch_cross(L->d_cc.p, total_cols, b->d_partition.p, b->d_np.p, L->d_err.p, L->d_col_hmm.p, L->d_err_hmm.p, s));
+        ENG_TRY(mrp_launch_cross(L->d_cc.p, total_cols, b->d_partition.p, b->d_np.p, L->d_err.p, L->d_col_hmm.p, L->d_err_hmm.p, s, census));
         ENG_TRY(hipEventRecord(L->ev[1], s));
     }
     const int rc = mrp_batch_launch(b);
@@ -969,14 +970,14 @@ static int launch_kernels(mrp_engine *e, mrp_engine_level_state *L, hipStream_t 
     if (rc != MRP_OK) return rc;
     ENG_TRY(hipEventRecord(L->ev[2], s));
     if (L->final_level) {
-        ENG_TRY_DUP('b', mrp_launch_traceback(b->dev, L->d_ph.p, n, L->d_err.p, L->d_err_hmm.p, s));
-        if (L->frag.on) ENG_TRY(mrp_launch_fragments(b->dev, L->d_ph.p, n, L->frag.device_arrays(), L->d_err.p, L->d_err_hmm.p, s));
+        ENG_TRY_DUP('b', mrp_launch_traceback(b->dev, L->d_ph.p, n, L->d_err.p, L->d_err_hmm.p, s, census));
+        if (L->frag.on) ENG_TRY(mrp_launch_fragments(b->dev, L->d_ph.p, n, L->frag.device_arrays(), L->d_err.p, L->d_err_hmm.p, s, census));
     } else {
         const int64_t n_mini = L->order.n_mini, n_reg = n - n_mini;
-        ENG_TRY_DUP('m', mrp_launch_mini(b->dev, L->d_cc.p, L->d_ph.p + n_reg, n_mini, n_reg, L->pp, sc, s));
-        ENG_TRY_DUP('r', mrp_launch_prune(b->dev, L->d_cc.p, L->d_ph.p, n_reg, L->pp, sc, s));
+        ENG_TRY_DUP('m', mrp_launch_mini(b->dev, L->d_cc.p, L->d_ph.p + n_reg, n_mini, n_reg, L->pp, sc, s, census));
+        ENG_TRY_DUP('r', mrp_launch_prune(b->dev, L->d_cc.p, L->d_ph.p, n_reg, L->pp, sc, s, census));
         ENG_TRY(hipEventRecord(L->ev[4], s));
-        ENG_TRY_DUP('c', mrp_launch_compact(b->dev, L->d_cc.p, L->d_ph.p, L->d_col_hmm.p, total_cols, n_reg, L->pp, sc, s));
+        ENG_TRY_DUP('c', mrp_launch_compact(b->dev, L->d_cc.p, L->d_ph.p, L->d_col_hmm.p, total_cols, n_reg, L->pp, sc, s, census));
     }
     ENG_TRY(hipEventRecord(L->ev[3], s));
     return MRP_OK;

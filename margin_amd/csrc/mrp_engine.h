@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mrp_census.h" /* LaunchCensus: every launcher below counts the class it launches, where it is given one */
 #include "mrp_kernels.h"
 
 #include "rphmm_host.h" /* MRP_CONN_*: connector kinds between consecutive aligned pieces */
@@ -214,7 +215,7 @@ struct FragArrays {
     int32_t *col_cnt;           /* scratch: per column 2 x first-sighting counts */
 };
 hipError_t mrp_launch_fragments(const MrpBatchDev &d, const PruneHmm *hmms_dev, int64_t n_hmms, FragArrays fa, int32_t *err, int32_t *err_hmm,
-                                hipStream_t stream);
+                                hipStream_t stream, LaunchCensus *census = nullptr);
 
 #define MRP_ENGINE_ERR_STRUCTURE 1 /* a parent is not in complement-pair order: closed-form cross product not valid */
 #define MRP_ENGINE_ERR_POSTERIOR 2 /* f + b > total (column.c:183 "invalid prob") */
@@ -226,27 +227,28 @@ hipError_t mrp_launch_fragments(const MrpBatchDev &d, const PruneHmm *hmms_dev, 
 #define MRP_PRUNE_MAX_S 116 /* 116 * 116 cells per cross product column <= MRP_PRUNE_MAX_CELLS */
 
 hipError_t mrp_launch_cross(const CrossCol *cols_dev, int64_t n_cols, uint64_t *partition, uint32_t *cell_np, int32_t *err,
-                            const int32_t *col_hmm_dev, int32_t *err_hmm, hipStream_t stream);
+                            const int32_t *col_hmm_dev, int32_t *err_hmm, hipStream_t stream, LaunchCensus *census = nullptr);
 /* Cross product and emission in one pass (merge levels without the ancestor substitution model): writes d.cell_np and
  * d.cell_cost from the parents' cells and the packed profile bytes (d.slot_bytes, d.slot_total); no partition array. */
 hipError_t mrp_launch_cross_emit(const CrossCol *cols_dev, const MrpBatchDev &d, int32_t *err, const int32_t *col_hmm_dev, int32_t *err_hmm,
                                  int32_t level_max_cells /* largest column of the level by the static bounds: sizes the kernel's tables */,
-                                 bool mostly_narrow /* most hmms of the level hold at most 64 array entries per column */, hipStream_t stream);
+                                 bool mostly_narrow /* most hmms of the level hold at most 64 array entries per column */, hipStream_t stream,
+                                 LaunchCensus *census = nullptr);
 /* ccols_dev: the level's cross product descriptors, indexed like the batch's columns (the prune kernel enumerates the
  * cells linked to a kept merge cell from the parents' transition arrays) */
 hipError_t mrp_launch_prune(const MrpBatchDev &d, const CrossCol *ccols_dev, const PruneHmm *hmms_dev, int64_t n_hmms, PruneParams p,
-                            PruneScratch s, hipStream_t stream);
+                            PruneScratch s, hipStream_t stream, LaunchCensus *census = nullptr);
 /* stRPHmm_forwardTraceBack (hmm.c:165-219) for every hmm of the level: out_n_cells[k] = cell index,
  * out_part[k] = its partition */
 hipError_t mrp_launch_traceback(const MrpBatchDev &d, const PruneHmm *hmms_dev, int64_t n_hmms, int32_t *err, int32_t *err_hmm,
-                                hipStream_t stream);
+                                hipStream_t stream, LaunchCensus *census = nullptr);
 /* d.partition == NULL: the level was produced by mrp_launch_cross_emit, partitions of the kept cells come from the parents */
 hipError_t mrp_launch_compact(const MrpBatchDev &d, const CrossCol *ccols_dev, const PruneHmm *hmms_dev, const int32_t *col_hmm_dev, int64_t n_cols,
-                              int64_t n_hmms_here, PruneParams p, PruneScratch s, hipStream_t stream); /* columns of hmms at positions >= n_hmms_here are skipped */
+                              int64_t n_hmms_here, PruneParams p, PruneScratch s, hipStream_t stream, LaunchCensus *census = nullptr); /* columns of hmms at positions >= n_hmms_here are skipped */
 /* Recursion, prune and compaction of hmms whose columns hold at most 64 units and 64 merge units (MRP_XF_UNITS levels) by one wave
  * each: hmms_dev[0 .. n_hmms) are the level's PruneHmm records from position hmm0 on (the error flags are indexed by position). */
 #define MRP_MINI_MAX_UNITS 64
 hipError_t mrp_launch_mini(const MrpBatchDev &d, const CrossCol *ccols_dev, const PruneHmm *hmms_dev, int64_t n_hmms, int64_t hmm0, PruneParams p,
-                           PruneScratch s, hipStream_t stream);
+                           PruneScratch s, hipStream_t stream, LaunchCensus *census = nullptr);
 
 #endif

@@ -32,6 +32,7 @@
 
 #include "mrp_engine.h"
 #include "mrp_internal.h"
+#include "mrp_level_order.h" /* prune_class, cross_emit_plan, the census slots */
 #include "../../include/margin_rphmm.h"
 
 #define WAVE 64
@@ -181,8 +182,9 @@ __global__ void __launch_bounds__(256) mrp_cross_kernel(const CrossCol *__restri
 }
 
 hipError_t mrp_launch_cross(const CrossCol *cols_dev, int64_t n_cols, uint64_t *partition, uint32_t *cell_np, int32_t *err,
-                            const int32_t *col_hmm_dev, int32_t *err_hmm, hipStream_t stream) {
+                            const int32_t *col_hmm_dev, int32_t *err_hmm, hipStream_t stream, LaunchCensus *census) {
     if (n_cols <= 0) return hipSuccess;
+    if (census) census->bump(CENSUS_CROSS_TWO_KERNELS);
     const int64_t grid = n_cols < 65536 ? n_cols : 65536;
     hipLaunchKernelGGL(mrp_cross_kernel, dim3((unsigned) grid), dim3(256), 0, stream, cols_dev, n_cols, partition, cell_np, err, col_hmm_dev,
                        err_hmm);
@@ -943,19 +945,18 @@ __global__ void __launch_bounds__(XE_WAVES * WAVE, MODE == 1 ? 8 : XE_MIN_WAVES)
 }
 
 hipError_t mrp_launch_cross_emit(const CrossCol *cols_dev, const MrpBatchDev &d, int32_t *err, const int32_t *col_hmm_dev, int32_t *err_hmm,
-                                 int32_t level_max_cells, bool mostly_narrow, hipStream_t stream) {
+                                 int32_t level_max_cells, bool mostly_narrow, hipStream_t stream, LaunchCensus *census) {
     if (d.n_cols <= 0) return hipSuccess;
     int64_t wgs = (d.n_cols + XE_WAVES - 1) / XE_WAVES;
-    /* level_max_cells: the level's largest cross product column by the host's static bounds; up to 128 cells (64 array entries of a
-     * unit level) every column has a lane per entry */
-    const uint32_t cap = level_max_cells > 2 * WAVE && !mostly_narrow ? XE_CAP_WIDE : XE_CAP_NARROW;
+    const CrossEmitPlan plan = cross_emit_plan(level_max_cells, mostly_narrow); /* (mrp_level_order.h) */
+    if (census) census->bump(plan.census_slot);
+    const uint32_t cap = plan.wide_cap ? XE_CAP_WIDE : XE_CAP_NARROW;
     const size_t lds = (size_t) XE_WAVES * (cap + XE_ROWS * 16 + XE_ROWS + 512) * sizeof(uint32_t);
     const dim3 grid((unsigned) (wgs < (1 << 20) ? wgs : (1 << 20)));
-    if (mostly_narrow) {
+    if (plan.mode1) {
         hipLaunchKernelGGL(mrp_cross_emit_kernel<1>, grid, dim3(XE_WAVES * WAVE), 0, stream, cols_dev, d.cols, d.chunks, d.n_cols, d.slot_bytes, d.slot_total,
                            const_cast<uint32_t *>(d.cell_np), d.cell_cost, err, col_hmm_dev, err_hmm, cap);
-        /* (a column of at most 64 cells is narrow whatever its parents: they have no more cells than it has) */
-        if (level_max_cells > WAVE)
+        if (plan.mode2)
             hipLaunchKernelGGL(mrp_cross_emit_kernel<2>, grid, dim3(XE_WAVES * WAVE), lds, stream, cols_dev, d.cols, d.chunks, d.n_cols, d.slot_bytes, d.slot_total,
                                const_cast<uint32_t *>(d.cell_np), d.cell_cost, err, col_hmm_dev, err_hmm, cap);
     } else
@@ -1538,8 +1539,7 @@ static __device__ __forceinline__ __amdgpu_buffer_rsrc_t prune_rsrc(const void *
 #define SEC_DONE() do { } while (0)
 #endif
 
-#define PRUNE_SP 128  /* slots of the selection buffers (S <= MRP_PRUNE_MAX_S) */
-#define PRUNE_TAB 5   /* per side and buffer: cnt, start, list, nx, pv, 128 entries each */
+/* (PRUNE_SP, PRUNE_TAB and the size of the LDS layout below: mrp_level_order.h, prune_lds_bytes) */
 
 /* T threads; the bin-streaming waves (all but the first four) form NGRP groups (2: alternating over the columns, a column's f and
  * b sit in a group's registers for two column times; 1: one group, requested one column ahead) and hold CPT loads of VEC cells
@@ -3105,19 +3105,12 @@ __global__ void __launch_bounds__(256) mrp_prune_back_kernel(const PruneHmm *__r
     }
 }
 
-static size_t prune_lds_bytes(const PruneParams &p) {
-    const size_t cap = p.pairs ? (size_t) (((p.max_cells + 1) / 2 + 3) & ~3) : (size_t) ((p.max_cells + 3) & ~3);
-    const size_t dwords = 4 * PRUNE_SP + PRUNE_SP + 4 * PRUNE_SP + 64 + 2 * 1024 + 512 + 512 + 2 * PRUNE_SP + 2 * PRUNE_SP + 512 + 512 + 4 * PRUNE_TAB * 128 + 512;
-    return dwords * 4 + (size_t) (((p.max_merge + 127) >> 7) << 2) * 4 + 2 * cap * 2 + 16;
-}
-
-/* columns of up to this many cells: one group of four bin-streaming waves, ten 16-byte loads per lane and array */
-#define MRP_PRUNE_MID_CELLS (4 * WAVE * 10 * 4)
-
 hipError_t mrp_launch_prune(const MrpBatchDev &d, const CrossCol *ccols_dev, const PruneHmm *hmms_dev, int64_t n_hmms, PruneParams p,
-                            PruneScratch s, hipStream_t stream) {
+                            PruneScratch s, hipStream_t stream, LaunchCensus *census) {
     if (n_hmms <= 0) return hipSuccess;
-    if (p.S > MRP_PRUNE_MAX_S || p.max_cells > MRP_PRUNE_MAX_CELLS || p.max_merge > MRP_PRUNE_MAX_CELLS || p.n_bins > 1024) return hipErrorInvalidValue;
+    /* what the bin-streaming waves hold per column decides the instantiation (prune_class, mrp_level_order.h) */
+    const PruneClass cls = prune_class(p.pairs, p.max_cells);
+    if (p.S > MRP_PRUNE_MAX_S || cls == PRUNE_TOO_LARGE || p.max_merge > MRP_PRUNE_MAX_CELLS || p.n_bins > 1024) return hipErrorInvalidValue;
     /* once per device (thread-safe: the concurrent halves of a call launch from two host threads) */
     static PerDeviceOnce once;
     const hipError_t configured = once.run([] {
@@ -3131,14 +3124,16 @@ hipError_t mrp_launch_prune(const MrpBatchDev &d, const CrossCol *ccols_dev, con
         return e;
     });
     if (configured != hipSuccess) return configured;
-    const size_t lds = prune_lds_bytes(p);
+    const size_t lds = prune_lds_bytes(p.pairs, p.max_cells, p.max_merge); /* (mrp_level_order.h; within the budget at every reachable level) */
     if (lds > (size_t) MRP_LDS_BUDGET) return hipErrorInvalidValue;
     const dim3 grid((unsigned) (n_hmms < 65536 ? n_hmms : 65536));
     const PruneIn in{d.scols, ccols_dev, d.cell_f32, d.cell_b32, d.merge_f32, d.merge_b32, d.hmm_fb};
     /* The bin-streaming waves hold a column's f and b in registers: two groups of 2 waves x 32 cells per lane at 512 threads;
      * one group of 4 waves x 40 cells per lane (16-byte loads) at 512 threads for columns of up to 10 240 cells -- the
      * 100 x 100 cells of the shipped parameters: half the waves and 77 KB of LDS let two workgroups share a CU where the
-     * 1 024-thread variant (two groups of 6 waves x 36 cells, up to 13 824 cells) fills it alone.
+     * 1 024-thread variant (two groups of 6 waves x 36 cells) fills it alone.  That variant holds up to 13 824 cells
+     * (MRP_PRUNE_MAX_CELLS); the largest bound a level can have is 116 x 116 = 13 456 (MRP_PRUNE_MAX_S), so 13 457..13 824 is
+     * covered only by the CPU check of the selector (tests/level_order_check.cpp), never by a launch.
      * p.pairs (includeInvertedPartitions and even column limits): the chain runs on complement pairs. */
     const bool pairs = p.pairs != 0;
 #define PRUNE_LAUNCH(T_, CPT_, NGRP_, VEC_)                                                                                               \
@@ -3146,17 +3141,18 @@ hipError_t mrp_launch_prune(const MrpBatchDev &d, const CrossCol *ccols_dev, con
         if (pairs) hipLaunchKernelGGL((mrp_prune_kernel<T_, CPT_, NGRP_, VEC_, true>), grid, dim3(T_), lds, stream, in, hmms_dev, n_hmms, p, s);  \
         else hipLaunchKernelGGL((mrp_prune_kernel<T_, CPT_, NGRP_, VEC_, false>), grid, dim3(T_), lds, stream, in, hmms_dev, n_hmms, p, s);       \
     } while (0)
-    /* what the bin-streaming waves hold per column: cells, or units when the level's arrays hold units (p.pairs == 2) */
-    const int held = p.pairs == 2 ? (p.max_cells + 1) / 2 : p.max_cells;
+    if (census) census->bump(census_prune_slot(cls, p.pairs));
+    switch (cls) {
     /* columns of at most 256 entries (the first merge levels: a few reads per hmm): four waves, the table wave writes the bins */
-    if (held <= 4 * WAVE) PRUNE_LAUNCH(256, 4, 1, 1);
-    else if (held <= 2 * WAVE * 32) PRUNE_LAUNCH(512, 32, 2, 1);
+    case PRUNE_256: PRUNE_LAUNCH(256, 4, 1, 1); break;
+    case PRUNE_512X32: PRUNE_LAUNCH(512, 32, 2, 1); break;
     /* up to 5 120 entries -- the unit levels of the shipped parameters (100 x 100 cells = 5 000 units): the same four streaming waves as
      * two groups that alternate over the columns, so that a column's f and b have TWO column times to arrive (one group: 1 ms per
      * step slower) */
-    else if (held <= 2 * WAVE * 10 * 4) PRUNE_LAUNCH(512, 10, 2, 4);
-    else if (held <= MRP_PRUNE_MID_CELLS) PRUNE_LAUNCH(512, 10, 1, 4);
-    else PRUNE_LAUNCH(1024, 36, 2, 1);
+    case PRUNE_512X10_TWO_GROUPS: PRUNE_LAUNCH(512, 10, 2, 4); break;
+    case PRUNE_512X10_ONE_GROUP: PRUNE_LAUNCH(512, 10, 1, 4); break;
+    default: PRUNE_LAUNCH(1024, 36, 2, 1); break;
+    }
 #undef PRUNE_LAUNCH
     {
         const hipError_t fe = hipGetLastError();
@@ -3166,6 +3162,7 @@ hipError_t mrp_launch_prune(const MrpBatchDev &d, const CrossCol *ccols_dev, con
         const size_t back_lds = (size_t) 4 * ((size_t) (((p.max_merge + 127) >> 7) << 2)) * sizeof(uint32_t);
         const int64_t wgs = (n_hmms + 3) / 4;
         const dim3 bgrid((unsigned) (wgs < 65536 ? wgs : 65536));
+        if (census) census->bump(pairs ? CENSUS_PRUNE_BACK_PAIRS : CENSUS_PRUNE_BACK_GENERAL);
         if (pairs) hipLaunchKernelGGL((mrp_prune_back_kernel<true>), bgrid, dim3(256), back_lds, stream, hmms_dev, n_hmms, p, s);
         else hipLaunchKernelGGL((mrp_prune_back_kernel<false>), bgrid, dim3(256), back_lds, stream, hmms_dev, n_hmms, p, s);
     }
@@ -3463,9 +3460,10 @@ __global__ void __launch_bounds__(256) mrp_mini_kernel(MrpBatchDev d, const Cros
 }
 
 hipError_t mrp_launch_mini(const MrpBatchDev &d, const CrossCol *ccols_dev, const PruneHmm *hmms_dev, int64_t n_hmms, int64_t hmm0, PruneParams p,
-                           PruneScratch s, hipStream_t stream) {
+                           PruneScratch s, hipStream_t stream, LaunchCensus *census) {
     if (n_hmms <= 0) return hipSuccess;
     if (p.pairs != 2 || p.n_bins > 1024) return hipErrorInvalidValue;
+    if (census) census->bump(CENSUS_MINI);
     const int64_t wgs = (n_hmms + 3) / 4;
     hipLaunchKernelGGL(mrp_mini_kernel, dim3((unsigned) (wgs < (1 << 20) ? wgs : (1 << 20))), dim3(256), 0, stream, d, ccols_dev, hmms_dev, n_hmms, hmm0, p, s);
     return hipGetLastError();
@@ -3876,23 +3874,26 @@ __global__ void __launch_bounds__(FRAG_T) mrp_fragment_kernel(MrpBatchDev d, con
 }
 
 hipError_t mrp_launch_fragments(const MrpBatchDev &d, const PruneHmm *hmms_dev, int64_t n_hmms, FragArrays fa, int32_t *err, int32_t *err_hmm,
-                                hipStream_t stream) {
+                                hipStream_t stream, LaunchCensus *census) {
     if (n_hmms <= 0) return hipSuccess;
+    if (census) census->bump(CENSUS_FRAGMENTS);
     hipLaunchKernelGGL(mrp_fragment_kernel, dim3((unsigned) (n_hmms < 65536 ? n_hmms : 65536)), dim3(FRAG_T), 0, stream, d, hmms_dev, n_hmms, fa, err, err_hmm);
     return hipGetLastError();
 }
 
 hipError_t mrp_launch_traceback(const MrpBatchDev &d, const PruneHmm *hmms_dev, int64_t n_hmms, int32_t *err, int32_t *err_hmm,
-                                hipStream_t stream) {
+                                hipStream_t stream, LaunchCensus *census) {
     if (n_hmms <= 0) return hipSuccess;
+    if (census) census->bump(CENSUS_TRACEBACK);
     hipLaunchKernelGGL(mrp_traceback_kernel, dim3((unsigned) (n_hmms < 65536 ? n_hmms : 65536)), dim3(64), 0, stream, d, hmms_dev,
                        n_hmms, err, err_hmm);
     return hipGetLastError();
 }
 
 hipError_t mrp_launch_compact(const MrpBatchDev &d, const CrossCol *ccols_dev, const PruneHmm *hmms_dev, const int32_t *col_hmm_dev, int64_t n_cols,
-                              int64_t n_hmms_here, PruneParams p, PruneScratch s, hipStream_t stream) {
+                              int64_t n_hmms_here, PruneParams p, PruneScratch s, hipStream_t stream, LaunchCensus *census) {
     if (n_cols <= 0 || n_hmms_here <= 0) return hipSuccess;
+    if (census) census->bump(CENSUS_COMPACT);
     const int64_t wgs = (n_cols + 3) / 4;
     hipLaunchKernelGGL(mrp_compact_kernel, dim3((unsigned) (wgs < 65536 ? wgs : 65536)), dim3(256), 0, stream, d, ccols_dev, hmms_dev,
                        col_hmm_dev, n_cols, (int32_t) n_hmms_here, p, s);

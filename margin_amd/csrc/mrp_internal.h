@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/margin_rphmm.h"
+#include "mrp_census.h"
 #include "mrp_device.h"
 #include "mrp_host_pool.h"
 #include "mrp_kernels.h"
@@ -367,6 +368,7 @@ struct mrp_context {
     }
     DevPool pool;
     int test_hooks = 0;   /* mrp_context_set_test_hooks (test suite only) */
+    LaunchCensus census;  /* launches of the resident path by class, this context's own (mrp_context_launch_census sums the siblings') */
     int wide_pairs = 0;   /* mrp_context_set_wide_pairs: pairs beyond the pair-per-wave kernel's 2 048 cells go to the pair-per-workgroup kernel */
     int sv_split = 0;     /* mrp_context_set_sv_split: indel_size_for_sv_handling > 0 splits the extraction's walk by class of variant */
     int64_t max_depth = 0;   /* mrp_context_set_downsampling: > 0 makes the aligned composites' mask on the device (0: off) */

@@ -1,6 +1,7 @@
 /*
  * mrp_level_order.h -- what staging a resident level (mrp_engine.cpp) decides by host arithmetic alone: the order of the level's
- * hmms, their launch classes, and the layout of its page-locked blocks; also the layout of a work queue's chunk block
+ * hmms, their launch classes (the recursion's, the prune kernel's, the cross product + emission plan) and their census slots, and the
+ * layout of its page-locked blocks; also the layout of a work queue's chunk block
  * (mrp_chunk.cpp).  No HIP call: tests/level_order_check.cpp runs it on the CPU.
  */
 #ifndef MRP_LEVEL_ORDER_H_
@@ -12,7 +13,8 @@
 #include <utility>
 #include <vector>
 
-#include "mrp_engine.h" /* MRP_MINI_MAX_UNITS */
+#include "mrp_census.h"
+#include "mrp_engine.h" /* MRP_MINI_MAX_UNITS, MRP_PRUNE_MAX_CELLS */
 #include "rphmm_host.h" /* mrp_xhmm */
 
 /* Hands out consecutive aligned regions of one block (64 bytes unless told otherwise; a power of two).  Run the same code twice:
@@ -91,6 +93,61 @@ enum SweepClass { SWEEP_NARROW, SWEEP_MID, SWEEP_WIDE };
 static inline SweepClass sweep_class(int64_t max_cells, int64_t max_merge) {
     return max_cells <= 256 ? SWEEP_NARROW : max_merge <= 4096 ? SWEEP_MID : SWEEP_WIDE;
 }
+
+/* The instantiation of the prune kernel for a level (mrp_launch_prune), by what its bin-streaming waves hold per column -- cells, or
+ * units where the level's arrays hold units (pairs == 2) -- in registers:
+ *   up to   256  four waves, the table wave writes the bins (the first merge levels: a few reads per hmm)
+ *   up to 4 096  two groups of 2 waves x 32 entries per lane
+ *   up to 5 120  two groups of 2 waves x 10 16-byte loads per lane, alternating over the columns
+ *   up to 10 240 one group of 4 waves x 10 16-byte loads per lane
+ *   beyond       1 024 threads: two groups of 6 waves x 36 entries; a level of more than MRP_PRUNE_MAX_CELLS cells is refused */
+#define MRP_PRUNE_HELD_256 (4 * 64)
+#define MRP_PRUNE_HELD_512X32 (2 * 64 * 32)
+#define MRP_PRUNE_HELD_TWO_GROUPS (2 * 64 * 10 * 4)
+#define MRP_PRUNE_HELD_ONE_GROUP (4 * 64 * 10 * 4)
+static inline int prune_held(int pairs, int max_cells) { return pairs == 2 ? (max_cells + 1) / 2 : max_cells; }
+static inline PruneClass prune_class(int pairs, int max_cells) {
+    if (max_cells > MRP_PRUNE_MAX_CELLS) return PRUNE_TOO_LARGE;
+    const int held = prune_held(pairs, max_cells);
+    return held <= MRP_PRUNE_HELD_256 ? PRUNE_256 : held <= MRP_PRUNE_HELD_512X32 ? PRUNE_512X32 :
+           held <= MRP_PRUNE_HELD_TWO_GROUPS ? PRUNE_512X10_TWO_GROUPS : held <= MRP_PRUNE_HELD_ONE_GROUP ? PRUNE_512X10_ONE_GROUP : PRUNE_1024;
+}
+/* The prune kernel's dynamic LDS (its layout: mrp_prune_kernel), the same for every class: the selection, stage and list buffers
+ * of PRUNE_SP slots, counters, two histograms of 1 024 bins, two bitmaps, range marks and prefixes, the inverse tables, the
+ * merge-cell hash, a kept flag per merge cell and two columns of 16-bit posterior bins -- one per cell, or per complement pair
+ * where the chain runs on pairs.  The largest request of the path is the per-cell level of 116 x 116 cells under the general
+ * chain: 91 120 bytes, within MRP_LDS_BUDGET (tests/level_order_check.cpp), so no reachable level is refused for its LDS. */
+#define PRUNE_SP 128  /* slots of the selection buffers (S <= MRP_PRUNE_MAX_S) */
+#define PRUNE_TAB 5   /* per side and buffer: cnt, start, list, nx, pv, 128 entries each */
+static inline size_t prune_lds_bytes(int pairs, int max_cells, int max_merge) {
+    const size_t cap = pairs ? (size_t) (((max_cells + 1) / 2 + 3) & ~3) : (size_t) ((max_cells + 3) & ~3);
+    const size_t dwords = 4 * PRUNE_SP + PRUNE_SP + 4 * PRUNE_SP + 64 + 2 * 1024 + 512 + 512 + 2 * PRUNE_SP + 2 * PRUNE_SP + 512 + 512 + 4 * PRUNE_TAB * 128 + 512;
+    return dwords * 4 + (size_t) (((max_merge + 127) >> 7) << 2) * 4 + 2 * cap * 2 + 16;
+}
+
+static inline int census_prune_slot(PruneClass k, int pairs) { return CENSUS_PRUNE + (int) k * PRUNE_CHAIN_MODES + pairs; }
+
+/* What mrp_launch_cross_emit launches for a level: the modes of the one-pass cross product + emission kernel and the table dwords
+ * per wave.  level_max_cells: the level's largest column by the static bounds; up to 128 cells (64 array entries of a unit level)
+ * every column has a lane per entry.  mostly_narrow: most hmms of the level are the single-wave kernel's -- mode 1 takes the
+ * table-free columns, mode 2 the rest (a column of at most 64 cells is narrow whatever its parents: they have no more cells than
+ * it has, so mode 1 runs alone). */
+struct CrossEmitPlan {
+    bool mode0, mode1, mode2;
+    bool wide_cap; /* XE_CAP_WIDE, not XE_CAP_NARROW */
+    int census_slot;
+};
+static inline CrossEmitPlan cross_emit_plan(int32_t level_max_cells, bool mostly_narrow) {
+    CrossEmitPlan p{};
+    p.wide_cap = level_max_cells > 2 * 64 && !mostly_narrow;
+    p.mode0 = !mostly_narrow;
+    p.mode1 = mostly_narrow;
+    p.mode2 = mostly_narrow && level_max_cells > 64;
+    p.census_slot = p.mode0 ? (p.wide_cap ? CENSUS_XE_MODE0_WIDE_CAP : CENSUS_XE_MODE0_NARROW_CAP) : p.mode2 ? CENSUS_XE_MODES_1_2 : CENSUS_XE_MODE1_ALONE;
+    return p;
+}
+
+static inline int census_sweep_slot(SweepClass k) { return k == SWEEP_NARROW ? CENSUS_SWEEP_NARROW : k == SWEEP_MID ? CENSUS_SWEEP_MID : CENSUS_SWEEP_WIDE; }
 
 /* the launch classes, from the static bounds; largest first inside a class.  Also the level's maxima and bound sums. */
 static inline void level_classes(const mrp_xhmm *x, int64_t n, bool units, LevelOrder &o) {

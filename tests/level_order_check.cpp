@@ -1,7 +1,8 @@
 /*
  * level_order_check.cpp -- the host arithmetic of staging a resident level (margin_amd/csrc/mrp_level_order.h) without a device:
- * the order and launch classes of random levels against a plain restatement, the block carver's two passes against each other, and
- * the layout of a work queue's chunk block.
+ * the order and launch classes of random levels against a plain restatement, the prune kernel's class and the cross product + emission
+ * plan on both sides of every threshold, the census slots, the block carver's two passes against each other, and the layout of a work
+ * queue's chunk block.
  * Built and run by tests/test_level_order.py with the address and undefined-behaviour sanitizers; prints "level order ok".
  */
 #include <algorithm>
@@ -88,6 +89,92 @@ static void check_level(const std::vector<mrp_xhmm> &x, bool units) {
     }
     CHECK(o.max_cells == max_cells && o.max_merge == max_merge);
     CHECK(o.bound_cells == bound_cells && o.bound_merge == bound_merge);
+}
+
+/* The prune kernel's instantiation for (pairs, max_cells), restated as a table: the largest number of entries a class holds, by what
+ * its bin-streaming waves keep in registers (waves x lanes x entries per lane).  A unit level (pairs == 2) holds one entry per
+ * complement pair, half the cells rounded up.  More than 13 824 cells: no class, the launcher refuses. */
+static int prune_class_restated(int pairs, int max_cells) {
+    static const int HOLDS[5] = {256 /* 4 x 64 x 1 */, 4096 /* 2 x 64 x 32 */, 5120 /* 2 x 64 x 40 */, 10240 /* 4 x 64 x 40 */, 13824 /* 6 x 64 x 36 */};
+    if (max_cells > 13824) return -1;
+    const int held = pairs == 2 ? max_cells / 2 + max_cells % 2 : max_cells;
+    for (int k = 0; k < 5; k++)
+        if (held <= HOLDS[k]) return k;
+    return -1;
+}
+
+static void check_prune_selector() {
+    CHECK(PRUNE_256 == 0 && PRUNE_512X32 == 1 && PRUNE_512X10_TWO_GROUPS == 2 && PRUNE_512X10_ONE_GROUP == 3 && PRUNE_1024 == 4 && PRUNE_CLASSES == 5);
+    CHECK(PRUNE_TOO_LARGE == -1 && MRP_PRUNE_MAX_CELLS == 13824 && MRP_PRUNE_MAX_S * MRP_PRUNE_MAX_S == 13456);
+    /* both sides of every threshold, named: cell levels (general chain, pairs over per-cell arrays) ... */
+    struct { int max_cells, want; } const CELL_EDGES[] = {{1, 0}, {256, 0}, {257, 1}, {4096, 1}, {4097, 2}, {5120, 2}, {5121, 3}, {10240, 3}, {10241, 4},
+                                                          {13456, 4}, {13457, 4}, {13824, 4}, {13825, -1}};
+    for (const auto &e : CELL_EDGES)
+        for (int pairs = 0; pairs < 2; pairs++) CHECK((int) prune_class(pairs, e.max_cells) == e.want);
+    /* ... and unit levels: held = (max_cells + 1) / 2, so a threshold t sits between 2 t and 2 t + 1 cells; the range still ends at
+     * 13 824 CELLS (6 912 units: the 1 024-thread class is never reached on units) */
+    struct { int max_cells, want; } const UNIT_EDGES[] = {{1, 0}, {511, 0}, {512, 0}, {513, 1}, {8191, 1}, {8192, 1}, {8193, 2}, {10239, 2}, {10240, 2}, {10241, 3},
+                                                          {13456, 3}, {13824, 3}, {13825, -1}};
+    for (const auto &e : UNIT_EDGES) CHECK((int) prune_class(2, e.max_cells) == e.want);
+    /* every size against the restatement, every mode; the census slot is class-major, mode-minor and inside the prune block */
+    for (int pairs = 0; pairs < 3; pairs++)
+        for (int max_cells = 1; max_cells <= 13824 + 300; max_cells++) {
+            const int want = prune_class_restated(pairs, max_cells);
+            CHECK((int) prune_class(pairs, max_cells) == want);
+            CHECK(prune_held(pairs, max_cells) == (pairs == 2 ? (max_cells + 1) / 2 : max_cells));
+            if (want >= 0) {
+                const int slot = census_prune_slot((PruneClass) want, pairs);
+                CHECK(slot == CENSUS_PRUNE + 3 * want + pairs && slot >= CENSUS_PRUNE && slot < CENSUS_PRUNE_BACK_GENERAL);
+            }
+        }
+}
+
+/* The prune kernel's LDS request never exceeds the budget at a level the selector accepts (so the launcher's refusal for LDS is
+ * unreachable): largest at the largest per-cell level under the general chain; monotone in both sizes; halved bins on pairs. */
+static void check_prune_lds() {
+    CHECK(prune_lds_bytes(0, 13456, 13456) == 91120);
+    CHECK(prune_lds_bytes(0, MRP_PRUNE_MAX_CELLS, MRP_PRUNE_MAX_CELLS) <= (size_t) MRP_LDS_BUDGET);
+    for (int pairs = 0; pairs < 3; pairs++)
+        for (int cells = 1; cells <= MRP_PRUNE_MAX_CELLS; cells += 97) {
+            CHECK(prune_lds_bytes(pairs, cells, cells) <= prune_lds_bytes(0, MRP_PRUNE_MAX_CELLS, MRP_PRUNE_MAX_CELLS));
+            CHECK(prune_lds_bytes(pairs, cells, cells) <= prune_lds_bytes(pairs, cells + 1, cells + 1));
+            CHECK(prune_lds_bytes(pairs, cells, cells) % 4 == 0);
+        }
+    CHECK(prune_lds_bytes(1, 13456, 13456) == prune_lds_bytes(2, 13456, 13456) && prune_lds_bytes(1, 13456, 13456) == 91120 - 2 * 13456);
+}
+
+/* The cross product + emission plan, restated: a level that is mostly the single-wave kernel's runs the table-free mode 1 and, if any
+ * column can exceed a wave (64 cells), mode 2 for the rest, with the narrow table; any other level runs mode 0, with the wide table
+ * once a column can exceed two waves (128 cells). */
+static void check_cross_emit_plan() {
+    for (int32_t max_cells : {1, 63, 64, 65, 127, 128, 129, 256, 4096, 13456})
+        for (int narrow = 0; narrow < 2; narrow++) {
+            const CrossEmitPlan p = cross_emit_plan(max_cells, narrow != 0);
+            if (narrow) {
+                CHECK(!p.mode0 && p.mode1 && p.mode2 == (max_cells >= 65) && !p.wide_cap);
+                CHECK(p.census_slot == (max_cells >= 65 ? CENSUS_XE_MODES_1_2 : CENSUS_XE_MODE1_ALONE));
+            } else {
+                CHECK(p.mode0 && !p.mode1 && !p.mode2 && p.wide_cap == (max_cells >= 129));
+                CHECK(p.census_slot == (max_cells >= 129 ? CENSUS_XE_MODE0_WIDE_CAP : CENSUS_XE_MODE0_NARROW_CAP));
+            }
+        }
+}
+
+/* the census: every slot has a name, the names are distinct, there is none outside the table; the sweep classes have their slots */
+static void check_census_slots() {
+    for (int q = 0; q < CENSUS_SLOTS; q++) {
+        CHECK(census_slot_name(q) != nullptr && census_slot_name(q)[0] != 0);
+        for (int r = 0; r < q; r++) CHECK(strcmp(census_slot_name(q), census_slot_name(r)) != 0);
+    }
+    CHECK(census_slot_name(-1) == nullptr && census_slot_name(CENSUS_SLOTS) == nullptr);
+    CHECK(strcmp(census_slot_name(census_prune_slot(PRUNE_1024, 1)), "prune_1024_pairs_over_cells") == 0);
+    CHECK(strcmp(census_slot_name(census_prune_slot(PRUNE_512X10_TWO_GROUPS, 0)), "prune_512x10_two_groups_general") == 0);
+    CHECK(strcmp(census_slot_name(census_prune_slot(PRUNE_256, 2)), "prune_256_units") == 0);
+    CHECK(census_sweep_slot(sweep_class(256, 9000)) == CENSUS_SWEEP_NARROW && census_sweep_slot(sweep_class(257, 4096)) == CENSUS_SWEEP_MID &&
+          census_sweep_slot(sweep_class(257, 4097)) == CENSUS_SWEEP_WIDE);
+    LaunchCensus c;
+    c.bump(CENSUS_MINI); c.bump(CENSUS_MINI); c.bump(CENSUS_SLOTS - 1);
+    for (int q = 0; q < CENSUS_SLOTS; q++) CHECK(c.n[q].load() == (q == CENSUS_MINI ? 2u : q == CENSUS_SLOTS - 1 ? 1u : 0u));
 }
 
 struct Twenty { char b[20]; }; /* the size of a FragSite */
@@ -177,6 +264,10 @@ int main() {
         for (int mode = 0; mode < 4; mode++)
             for (int units = 0; units < 2; units++)
                 for (int rep = 0; rep < (n <= 63 ? 20 : 2); rep++) check_level(random_level(rng, n, mode), units != 0);
+    check_prune_selector();
+    check_prune_lds();
+    check_cross_emit_plan();
+    check_census_slots();
     for (int rep = 0; rep < 2000; rep++) check_carver(rng);
     for (int with_pool = 0; with_pool < 2; with_pool++)
         for (size_t last_pool : {0, 1, 255, 256, 257})
