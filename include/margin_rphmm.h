@@ -1207,7 +1207,7 @@ int mrp_downsample_reads(mrp_context *ctx, int64_t n_chunks, const int64_t *n_re
  * 4 B per chunk.  0 (default): off, every launch, byte and output as before; negative: MRP_ERR_ARG.  mrp_haplotag_aligned_chunks
  * (no downsampling in tagFromPhasedVcf.c) and the *_on_devices forms ignore the setting. */
 int mrp_context_set_downsampling(mrp_context *ctx, int64_t max_depth, uint64_t seed);
-/* the same for every lane's context, present and future, of a queue: honoured by mrp_queue_phase_aligned_chunks(_with_filtered) */
+/* the same for every lane's context, present and future, of a queue: honoured by mrp_queue_phase_aligned_chunks(_with_filtered, _with_records) */
 int mrp_queue_set_downsampling(mrp_queue *q, int64_t max_depth, uint64_t seed);
 /* what the last composite call on ctx (or mrp_downsample_reads) did for the downsampling; zeros when the setting was off */
 int mrp_context_last_downsampling(mrp_context *ctx, mrp_downsampling_stats *out);
@@ -1282,6 +1282,125 @@ int mrp_phase_aligned_chunks_with_filtered_on_devices(const int32_t *devices, in
                                                       int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
                                                       mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
                                                       int32_t **filtered_read_out, mrp_queue_stats *stats);
+
+/* ---- the same with the phased variant records: what a whole contig needs to reach writePhasedVcf ------
+ * mrp_queue_phase_aligned_chunks_with_filtered plus records_out[n_chunks] and an optional mrp_queue_records_stats: a batch is then
+ * what one mrp_phase_aligned_chunks_with_records call phases, and records_out[c] travels with its chunk like filtered_out[c].
+ *   Results: at every chunk's own position every output, records_out[c] array for array and float bits included, is what ONE
+ * mrp_phase_aligned_chunks_with_records call over all chunks returns, whatever the batch size, the lanes, the devices or the hand-out.
+ * mrp_queue_set_downsampling, mrp_queue_set_sv_split and mrp_queue_set_wide_pairs are honoured exactly as by ..._with_filtered.
+ *   Checks, their order and their messages are mrp_queue_phase_aligned_chunks_with_filtered's, a NULL records_out among its null
+ * arguments (MRP_ERR_ARG, before the queue is looked at); then MRP_ERR_UNSUPPORTED for the refused modes; then MRP_ERR_NO_DEVICE for a
+ * NULL queue.  Up to there nothing is written.  n_chunks == 0 returns MRP_OK with zeroed stats (both).  On a lane error every record
+ * already handed out is released, records_out[] is left zeroed as are the other outputs, records_stats stays zeroed, and the queue
+ * stays usable.  records_stats sums what the batches' calls report (mrp_phase_aligned_records_stats); records_ms is the sum of the
+ * batches' kernel times, not a wall time: batches of different lanes run beside each other. */
+typedef struct mrp_queue_records_stats {
+    int64_t records_sites;            /* sites of all batches: the variants of both sets */
+    int64_t records_updated;          /* of these, MRP_RECORD_UPDATED */
+    int64_t reads_listed;             /* reads in the lists */
+    int64_t records_bytes_downloaded; /* what came back for the records, as mrp_phase_aligned_records_stats counts it */
+    double records_ms;                /* the records kernel, HIP events, summed over the batches */
+} mrp_queue_records_stats;
+int mrp_queue_phase_aligned_chunks_with_records(mrp_queue *q, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
+                                                const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
+                                                const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                                                int64_t sv_threshold, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
+                                                int32_t **filtered_read_out, mrp_variant_records *records_out, mrp_queue_stats *stats,
+                                                mrp_queue_records_stats *records_stats);
+/* create a queue (every queue setting off), run the call above, destroy it */
+int mrp_phase_aligned_chunks_with_records_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,
+                                                     const mrp_aligned_chunk_rest *rest, const char *const *const *read_names, const uint8_t *const *keep,
+                                                     const mrp_extract_options *options, const mrp_pair_hmm *forward_model,
+                                                     const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                                     double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                     int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                     mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
+                                                     int32_t **filtered_read_out, mrp_variant_records *records_out, mrp_queue_stats *stats,
+                                                     mrp_queue_records_stats *records_stats);
+
+/* ---- closing a contig on the host: what follows the chunk loop (phase.c:475-535), DESIGN.md section 9.14 -------------------------
+ * outputChunkers_stitchAndTrackExtraData (stitching.c:1558-1693), updateHaplotypeSwitchingInVcfEntries, the phase set rules of
+ * writePhasedVcf and the final read sets writeHaplotaggedBam takes, over the per-chunk outputs of the calls above.  Host only, no
+ * device, no context.  Three rules a caller would otherwise re-derive are defined here.
+ *
+ * mrp_final_read_tags: one tag (1 / 2 / 0) per read of one chunk.
+ *   Phasing form (filtered_out != NULL; hap_out, filtered_out[c], filtered_read_out[c] of mrp_phase_aligned_chunks_with_filtered and
+ * its kin).  The tag is the phasing's own tag where hap_out[r] is 1 or 2 (the reads of phase.c:413).  Otherwise it is what the back
+ * half gave the read (phase.c:419-436): a chunk's reads in filtered_out->read_hap are its n_reads primary indices, then
+ * its filtered reads in list order, and a read of kind (i) or (ii) appears twice -- at its primary index r with no
+ * substrings (0) and at n_reads + k with its result, k its place in filtered_read_out.  So for a read named in filtered_read_out[k]
+ * the tag is read_hap[n_reads + k]; for every other read it is read_hap[r] (a primary read the phasing left untagged takes part in the
+ * partition under its own index; for a chunk with an empty rest read_hap are the tags, 0 for an untagged read).  filtered_read_out is
+ * closed by a -1 and may be NULL when filtered_out->n_reads == n_reads.
+ *   Haplotag form (filtered_out == NULL, filtered_read_out ignored): hap_out is mrp_haplotag_aligned_chunks', -1 mapped to 0.
+ *   MRP_ERR_ARG: NULL arrays, n_reads < 0, a hap_out outside -1..2, a read_hap outside 0..2, filtered_out->n_reads below n_reads or
+ * not n_reads + the length of filtered_read_out, a filtered_read_out entry outside [0, n_reads) or named twice.
+ *
+ * mrp_stitch_values: the value every tagged read carries into chunkToStitch_phaseAdjacentChunks.  The reference prints a read of the
+ * genome fragment's own partition with its phred score and "%f" (genomeFragment.c:101-122, stitching.c:896, :909), every other read of
+ * the two sets -- the ones the back half tagged -- with -1.0 (stitching.c:887-917), and getReadNames parses the field back with strtof
+ * into a double (stitching.c:288-303).  So value_out[r] = (double) strtof(the "%f" text of phred_out[r]) when hap_out[r] is 1 or 2,
+ * -1.0 for every other read whose final tag is 1 or 2, and 0.0 (never read) where the final tag is 0.  A NULL hap_out (the haplotag
+ * tool, tagFromPhasedVcf.c:340-348: no fragment) gives -1.0 for every tagged read; phred_out may then be NULL.
+ *   MRP_ERR_ARG: NULL final_tag or value_out, n_reads < 0, hap_out without phred_out, a tag outside its range, hap_out[r] 1 or 2
+ * with another final tag.
+ *
+ * mrp_close_contig: the chunks of ONE contig in genome order.  Steps, in order: the two functions above per chunk; mrp_stitch_chunk
+ * chunk by chunk over (read_names, values) of the reads with final tag 1 and of those with final tag 2, with rules->primary_reads_only
+ * (stitchWithPrimaryReadsOnly), the first chunk never switched (mergeContigChunkz stitches from the second chunk on) and no chunk
+ * switched when rules->prevent_switching (stitching.c:1586); mrp_variants_from_records over the chunks' records with those switches
+ * and read_id; mrp_phase_sets with the three parameters.  A chunk whose records is NULL has no sites; when every chunk's is NULL no
+ * variants and no phase sets come out.  Out (mrp_contig_out, released by mrp_contig_out_clear, which zeroes it):
+ *   switched[c], counts[4 c .. 4 c + 3] (cisH1, cisH2, transH1, transH2 as mrp_stitch_chunk counts them; zeros for the first chunk);
+ *   final_hap[c][r]: 1 / 2 when read r's NAME is in the stitcher's hap1 / hap2 set after the last chunk (stitching.c:1664-1671, the
+ *     sets writeHaplotaggedBam takes), 0 otherwise -- the same name in two chunks gets the same value;
+ *   variants: the mrp_record_variants block (variants.variants: mrp_free, done by mrp_contig_out_clear);
+ *   phase_set[i], reason[i] per kept variant (MRP_PS_*).
+ *   MRP_ERR_ARG: NULL arguments or arrays, negative counts, a NULL read name, what the two functions above refuse, records whose
+ * n_primary / n_filtered disagree with n_variants / n_fvariants, what mrp_variants_from_records and mrp_phase_sets refuse.  Nothing is
+ * written on error.
+ *
+ * mrp_close_contigs: n_contigs contigs in one call; contig k is chunks[first_chunk[k] .. first_chunk[k + 1]) with first_chunk[0] == 0,
+ * first_chunk ascending (n_contigs + 1 entries, the last = n_chunks).  Contigs are closed independently and in parallel
+ * (stitching.c:1635) on the library's host threads (mrp_set_host_threads); out[k] equals mrp_close_contig over contig k alone,
+ * whatever the thread count.  Every contig is checked before anything is written. */
+typedef struct mrp_contig_chunk {
+    int64_t n_reads;
+    const char *const *read_names;        /* n_reads */
+    const int32_t *read_id;               /* n_reads: the caller's global read ids (readIdToIdx); needed only with records */
+    const int8_t *hap_out;                /* n_reads: the phasing's tags; haplotag form: mrp_haplotag_aligned_chunks' tags */
+    const double *phred_out;              /* n_reads; haplotag form: ignored, may be NULL */
+    const mrp_filtered_out *filtered_out; /* the chunk's; NULL: haplotag form */
+    const int32_t *filtered_read_out;     /* the chunk's, closed by -1 */
+    const mrp_variant_records *records;   /* may be NULL */
+    int64_t n_variants, n_fvariants;      /* sizes of the arrays below = records->n_primary, records->n_filtered */
+    const int64_t *variant_pos; const int32_t *n_alleles;
+    const int64_t *fvariant_pos; const int32_t *fn_alleles;
+} mrp_contig_chunk;
+typedef struct mrp_contig_rules {
+    int32_t primary_reads_only;  /* phaseParams->stitchWithPrimaryReadsOnly */
+    int32_t prevent_switching;   /* preventSwitching of outputChunkers_stitchAndTrackExtraData */
+    int64_t min_spanning_reads;  /* the three parameters of mrp_phase_sets */
+    double min_binomial_read_split_likelihood, max_discordant_ratio;
+} mrp_contig_rules;
+typedef struct mrp_contig_out {
+    int64_t n_chunks;
+    int32_t *switched;           /* n_chunks */
+    int64_t *counts;             /* 4 per chunk */
+    int8_t **final_hap;          /* n_chunks pointers into one block: final_hap[c][r] */
+    mrp_record_variants variants;
+    int32_t *phase_set, *reason; /* variants.n_variants each */
+} mrp_contig_out;
+int mrp_final_read_tags(int64_t n_reads, const int8_t *hap_out, const mrp_filtered_out *filtered_out, const int32_t *filtered_read_out,
+                        int8_t *tag_out);
+int mrp_stitch_values(int64_t n_reads, const int8_t *hap_out, const double *phred_out, const int8_t *final_tag, double *value_out);
+int mrp_close_contig(int64_t n_chunks, const mrp_contig_chunk *chunks, const mrp_contig_rules *rules, mrp_contig_out *out);
+int mrp_close_contigs(int64_t n_contigs, const int64_t *first_chunk, const mrp_contig_chunk *chunks, const mrp_contig_rules *rules,
+                      mrp_contig_out *out);
+void mrp_contig_out_clear(mrp_contig_out *out);
 
 /* ---- haplotagging a node's worth of aligned chunks from a phased VCF over its GPUs ----------------------------------------------
  * The chunk loop of tools/tagFromPhasedVcf.c (:208-225: the chunks ordered by estimated depth, largest first; :227-235: "#pragma omp

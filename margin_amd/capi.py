@@ -49,6 +49,8 @@ EXPORTED_SYMBOLS = [
     "mrp_variant_records_from_extracted", "mrp_phase_aligned_chunks_with_records", "mrp_variants_from_records",
     "mrp_context_set_downsampling", "mrp_queue_set_downsampling", "mrp_context_last_downsampling", "mrp_downsample_draw", "mrp_aln_read_lengths",
     "mrp_downsample_keep_from_extracted", "mrp_downsample_reads",
+    "mrp_queue_phase_aligned_chunks_with_records", "mrp_phase_aligned_chunks_with_records_on_devices", "mrp_final_read_tags", "mrp_stitch_values",
+    "mrp_close_contig", "mrp_close_contigs", "mrp_contig_out_clear",
 ]
 
 
@@ -338,9 +340,31 @@ class PhaseAlignedRecordsStats(C.Structure):
                 ("records_bytes_downloaded", C.c_int64), ("records_ms", C.c_double)]
 
 
+class QueueRecordsStats(C.Structure):
+    _fields_ = [("records_sites", C.c_int64), ("records_updated", C.c_int64), ("reads_listed", C.c_int64), ("records_bytes_downloaded", C.c_int64),
+                ("records_ms", C.c_double)]
+
+
+class ContigChunk(C.Structure):
+    _fields_ = [("n_reads", C.c_int64), ("read_names", C.c_void_p), ("read_id", C.c_void_p), ("hap_out", C.c_void_p), ("phred_out", C.c_void_p),
+                ("filtered_out", C.POINTER(FilteredOut)), ("filtered_read_out", C.c_void_p), ("records", C.POINTER(VariantRecords)),
+                ("n_variants", C.c_int64), ("n_fvariants", C.c_int64), ("variant_pos", C.c_void_p), ("n_alleles", C.c_void_p),
+                ("fvariant_pos", C.c_void_p), ("fn_alleles", C.c_void_p)]
+
+
+class ContigRules(C.Structure):
+    _fields_ = [("primary_reads_only", C.c_int32), ("prevent_switching", C.c_int32), ("min_spanning_reads", C.c_int64),
+                ("min_binomial_read_split_likelihood", C.c_double), ("max_discordant_ratio", C.c_double)]
+
+
 class RecordVariants(C.Structure):
     _fields_ = [("n_variants", C.c_int64), ("variants", C.POINTER(Variant)), ("chunk", C.c_void_p), ("site", C.c_void_p),
                 ("genotype_log_prob", C.c_void_p), ("hap1_log_prob", C.c_void_p), ("hap2_log_prob", C.c_void_p)]
+
+
+class ContigOut(C.Structure):
+    _fields_ = [("n_chunks", C.c_int64), ("switched", C.c_void_p), ("counts", C.c_void_p), ("final_hap", C.POINTER(C.c_void_p)), ("variants", RecordVariants),
+                ("phase_set", C.c_void_p), ("reason", C.c_void_p)]
 
 
 def load():
@@ -479,6 +503,15 @@ def load():
     L.mrp_queue_phase_aligned_chunks_with_filtered.argtypes = pf[:14] + [i64] + pf[14:-1] + [P(QueueStats)]
     L.mrp_phase_aligned_chunks_on_devices.argtypes = [vp, i32] + L.mrp_queue_phase_aligned_chunks.argtypes[1:]
     L.mrp_phase_aligned_chunks_with_filtered_on_devices.argtypes = [vp, i32] + L.mrp_queue_phase_aligned_chunks_with_filtered.argtypes[1:]
+    L.mrp_queue_phase_aligned_chunks_with_records.argtypes = L.mrp_queue_phase_aligned_chunks_with_filtered.argtypes[:-1] + \
+        [P(VariantRecords), P(QueueStats), P(QueueRecordsStats)]
+    L.mrp_phase_aligned_chunks_with_records_on_devices.argtypes = [vp, i32] + L.mrp_queue_phase_aligned_chunks_with_records.argtypes[1:]
+    L.mrp_final_read_tags.argtypes = [i64, vp, P(FilteredOut), vp, vp]
+    L.mrp_stitch_values.argtypes = [i64, vp, vp, vp, vp]
+    L.mrp_close_contig.argtypes = [i64, P(ContigChunk), P(ContigRules), P(ContigOut)]
+    L.mrp_close_contigs.argtypes = [i64, vp, P(ContigChunk), P(ContigRules), P(ContigOut)]
+    L.mrp_contig_out_clear.argtypes = [P(ContigOut)]
+    L.mrp_contig_out_clear.restype = None
     L.mrp_kmer_alignment_anchors_many.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, P(vp), P(PairHmmStats)]
     L.mrp_string_chunk_rest_from_extracted.argtypes = [P(ExtractedChunk), vp, vp, vp, i64, P(ExtractedChunk), vp, vp, i64, i64, P(StringChunkRest),
                                                        P(vp), P(vp)]
@@ -979,6 +1012,13 @@ class Queue:
                                            chunks_per_batch: int = 0, **kw):
         """mrp_queue_phase_aligned_chunks_with_filtered -> (phase_aligned_chunks_with_filtered's list of dicts in input order, QueueStats)"""
         return _phase_aligned(None, chunks, forward_model, reverse_model, params, rests=rests, with_rest=True, queue=self.h,
+                              chunks_per_batch=chunks_per_batch, **kw)
+
+    def phase_aligned_chunks_with_records(self, chunks, rests, forward_model: "PairHmm", reverse_model: "PairHmm", params: Params,
+                                          chunks_per_batch: int = 0, **kw):
+        """mrp_queue_phase_aligned_chunks_with_records -> (phase_aligned_chunks_with_records' list of dicts in input order, QueueStats with
+        the QueueRecordsStats as its attribute `records`)"""
+        return _phase_aligned(None, chunks, forward_model, reverse_model, params, rests=rests, with_rest=True, with_records=True, queue=self.h,
                               chunks_per_batch=chunks_per_batch, **kw)
 
     def haplotag_aligned_chunks(self, chunks, gts, forward_model: "PairHmm", reverse_model: "PairHmm", options: Optional[dict] = None,
@@ -1942,6 +1982,13 @@ def variants_from_records(records, variant_pos, n_alleles, fvariant_pos, fn_alle
     sw = np.ascontiguousarray(switched, np.int32)
     out = RecordVariants()
     _check(L.mrp_variants_from_records(n, arr, vp_, na_, fp_, fa_, sw.ctypes.data if sw.size else None, id_, C.byref(out)))
+    res = _record_variants_list(out)
+    L.mrp_free(C.cast(out.variants, C.c_void_p))
+    return res
+
+
+def _record_variants_list(out) -> list:
+    """the variants of a mrp_record_variants block as the dicts capi.phase_sets takes (copies; the block is the caller's to free)"""
     m = int(out.n_variants)
     chunk, site = _as_np(out.chunk, m, np.int32), _as_np(out.site, m, np.int32)
     logs = [_as_np(getattr(out, f), m, np.float32) for f in ("genotype_log_prob", "hap1_log_prob", "hap2_log_prob")]
@@ -1952,8 +1999,143 @@ def variants_from_records(records, variant_pos, n_alleles, fvariant_pos, fn_alle
         ids = _as_np(V.allele_reads, int(off[V.n_alleles]), np.int32)
         res.append(dict(pos=int(V.pos), gt1=int(V.gt1), gt2=int(V.gt2), alleleIdxToReads=[ids[off[a]:off[a + 1]].tolist() for a in range(V.n_alleles)],
                         chunk=int(chunk[i]), site=int(site[i]), genotype_log_prob=logs[0][i], hap1_log_prob=logs[1][i], hap2_log_prob=logs[2][i]))
-    L.mrp_free(C.cast(out.variants, C.c_void_p))
     return res
+
+
+# ---- closing a contig on the host (mrp_final_read_tags, mrp_stitch_values, mrp_close_contig, mrp_close_contigs) ----
+
+def filtered_out_struct(filtered: dict):
+    """mrp_filtered_out over the numpy arrays of a "filtered" dict as phase_aligned_chunks_with_filtered returns it (only read_hap and
+    variant_state are required); returns (FilteredOut, the arrays it points into)"""
+    keep = dict(read_hap=np.ascontiguousarray(filtered["read_hap"], np.int32), variant_state=np.ascontiguousarray(filtered.get("variant_state", []), np.int32))
+    for f in ("h1", "h2", "cis", "trans"):
+        if f in filtered:
+            keep[f] = np.ascontiguousarray(filtered[f], np.float64)
+    ptr = lambda f: keep[f].ctypes.data if f in keep and keep[f].size else None
+    return FilteredOut(len(keep["read_hap"]), ptr("read_hap"), ptr("h1"), ptr("h2"), len(keep["variant_state"]), ptr("variant_state"), ptr("cis"), ptr("trans")), keep
+
+
+def _closed_list(a):
+    """an int32 list closed by -1, as filtered_read_out is"""
+    return np.ascontiguousarray(list(np.asarray(a, np.int64).reshape(-1)) + [-1], np.int32)
+
+
+def final_read_tags(hap, filtered: Optional[dict] = None, filtered_read=None, nulls=()) -> np.ndarray:
+    """mrp_final_read_tags -> int8 [n_reads]: 1 / 2 / 0.  hap: the call's hap_out; filtered / filtered_read: the chunk's "filtered" dict and
+    "filtered_read" (None: the haplotag form).  nulls ("hap", "out") pass NULL.  On an error the output is checked to be unwritten."""
+    h = np.ascontiguousarray(hap, np.int8)
+    out = np.full(max(len(h), 1), 77, np.int8)
+    F = fr = None
+    if filtered is not None:
+        F, _keep = filtered_out_struct(filtered)
+        fr = _closed_list([] if filtered_read is None else filtered_read)
+    rc = load().mrp_final_read_tags(len(h), None if "hap" in nulls or not h.size else h.ctypes.data, None if F is None else C.byref(F),
+                                    None if fr is None else fr.ctypes.data, None if "out" in nulls else out.ctypes.data)
+    if rc != MRP_OK:
+        assert (out == 77).all(), "outputs written on an error"
+    _check(rc)
+    return out[:len(h)]
+
+
+def stitch_values(hap, phred, final_tag, nulls=()) -> np.ndarray:
+    """mrp_stitch_values -> float64 [n_reads]; hap None: the haplotag form (-1.0 for every tagged read)"""
+    t = np.ascontiguousarray(final_tag, np.int8)
+    h = None if hap is None else np.ascontiguousarray(hap, np.int8)
+    p = None if phred is None else np.ascontiguousarray(phred, np.float64)
+    out = np.full(max(len(t), 1), 77.0)
+    ptr = lambda a, name: None if a is None or name in nulls or not a.size else a.ctypes.data
+    rc = load().mrp_stitch_values(len(t), ptr(h, "hap"), ptr(p, "phred"), ptr(t, "final_tag"), None if "out" in nulls else out.ctypes.data)
+    if rc != MRP_OK:
+        assert (out == 77.0).all(), "outputs written on an error"
+    _check(rc)
+    return out[:len(t)]
+
+
+def contig_chunk_struct(ch: dict, nulls=()):
+    """mrp_contig_chunk over one chunk's results: dict(read_names, read_id, hap, phred, filtered, filtered_read, records, variant_pos, n_alleles,
+    fvariant_pos, fn_alleles).  filtered None: the haplotag form; records None: no sites.  nulls names fields to pass as NULL.  Returns
+    (ContigChunk, what it points into)."""
+    nr = len(ch["read_names"])
+    names = [s.encode() for s in ch["read_names"]]
+    keep = dict(names=names, name_arr=(C.c_char_p * max(nr, 1))(*names), read_id=np.ascontiguousarray(ch.get("read_id", np.zeros(nr)), np.int32),
+                hap=np.ascontiguousarray(ch["hap"], np.int8))
+    if "read_names[0]" in nulls:
+        keep["name_arr"][0] = None
+    K = ContigChunk()
+    K.n_reads = nr
+    K.read_names = None if "read_names" in nulls else C.cast(keep["name_arr"], C.c_void_p)
+    K.read_id = None if "read_id" in nulls or not nr else keep["read_id"].ctypes.data
+    K.hap_out = None if "hap" in nulls or not nr else keep["hap"].ctypes.data
+    if ch.get("phred") is not None and "phred" not in nulls:
+        keep["phred"] = np.ascontiguousarray(ch["phred"], np.float64)
+        K.phred_out = keep["phred"].ctypes.data if nr else None
+    if ch.get("filtered") is not None:
+        keep["F"], keep["F_arrays"] = filtered_out_struct(ch["filtered"])
+        K.filtered_out = C.pointer(keep["F"])
+        keep["fr"] = _closed_list(ch.get("filtered_read", []))
+        K.filtered_read_out = keep["fr"].ctypes.data
+    if ch.get("records") is not None:
+        keep["R"], keep["R_arrays"] = records_struct(ch["records"])
+        K.records = C.pointer(keep["R"])
+        for f, t in (("variant_pos", np.int64), ("n_alleles", np.int32), ("fvariant_pos", np.int64), ("fn_alleles", np.int32)):
+            keep[f] = np.ascontiguousarray(ch[f], t)
+            setattr(K, f, keep[f].ctypes.data if keep[f].size and f not in nulls else None)
+        K.n_variants, K.n_fvariants = len(keep["variant_pos"]), len(keep["fvariant_pos"])
+    return K, keep
+
+
+def _contig_out_dict(O) -> dict:
+    """a mrp_contig_out as Python values (copies); the struct is released"""
+    n = int(O.n_chunks)
+    switched = _as_np(O.switched, n, np.int32)
+    d = dict(switched=[int(x) for x in switched], counts=[tuple(int(x) for x in row) for row in _as_np(O.counts, 4 * n, np.int64).reshape(n, 4)])
+    d["variants"] = _record_variants_list(O.variants)
+    m = len(d["variants"])
+    ps, why = _as_np(O.phase_set, m, np.int32), _as_np(O.reason, m, np.int32)
+    d["phase_sets"] = [(int(ps[i]), int(why[i])) for i in range(m)]
+    return d
+
+
+def _contig_rules(primary_reads_only, prevent_switching, rules):
+    return ContigRules(int(bool(primary_reads_only)), int(bool(prevent_switching)), int(rules[0]), float(rules[1]), float(rules[2]))
+
+
+def close_contigs(contigs, primary_reads_only: bool = False, prevent_switching: bool = False, rules=(2, 0.05, 0.5), nulls=(), one: bool = False):
+    """mrp_close_contigs over a list of contigs, each a list of chunk dicts in genome order (contig_chunk_struct) -> per contig
+    dict(switched, counts [(cisH1, cisH2, transH1, transH2)], final_hap [int8 array per chunk], variants (the dicts capi.phase_sets takes),
+    phase_sets [(phase set, reason code)]).  one: mrp_close_contig over the single contig given.  On an error the outputs are checked to
+    be unwritten."""
+    L = load()
+    flat = [ch for contig in contigs for ch in contig]
+    built = [contig_chunk_struct(ch, nulls if i == 0 else ()) for i, ch in enumerate(flat)]
+    arr = (ContigChunk * max(len(flat), 1))(*[b[0] for b in built])
+    first = np.ascontiguousarray(np.cumsum([0] + [len(c) for c in contigs]), np.int64)
+    R = _contig_rules(primary_reads_only, prevent_switching, rules)
+    outs = (ContigOut * max(len(contigs), 1))()
+    for O in outs:
+        O.n_chunks = -7
+    if one:
+        assert len(contigs) == 1
+        rc = L.mrp_close_contig(len(flat), None if "chunks" in nulls else arr, None if "rules" in nulls else C.byref(R), None if "out" in nulls else outs)
+    else:
+        rc = L.mrp_close_contigs(len(contigs), None if "first_chunk" in nulls else first.ctypes.data, None if "chunks" in nulls else arr,
+                                 None if "rules" in nulls else C.byref(R), None if "out" in nulls else outs)
+    if rc != MRP_OK:
+        assert all(O.n_chunks == -7 and not O.switched and not O.final_hap and not O.variants.variants for O in outs), "outputs written on an error"
+    _check(rc)
+    res = []
+    for k, contig in enumerate(contigs):
+        O = outs[k]
+        d = _contig_out_dict(O)
+        d["final_hap"] = [_as_np(O.final_hap[c], len(ch["read_names"]), np.int8) for c, ch in enumerate(contig)]
+        L.mrp_contig_out_clear(C.byref(O))
+        res.append(d)
+    return res
+
+
+def close_contig(chunks, **kw) -> dict:
+    """mrp_close_contig over the chunk dicts of one contig -> the dict close_contigs returns per contig"""
+    return close_contigs([list(chunks)], one=True, **kw)[0]
 
 
 # ---- haplotagging aligned reads from a phased VCF (mrp_haptag_sites_from_extracted, mrp_haplotag_aligned_chunks) ----
@@ -2130,6 +2312,14 @@ def phase_aligned_chunks_with_filtered_on_devices(devices, chunks, rests, forwar
                           chunks_per_batch=chunks_per_batch, **kw)
 
 
+def phase_aligned_chunks_with_records_on_devices(devices, chunks, rests, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm],
+                                                 params: Optional[Params], chunks_per_batch: int = 0, **kw):
+    """mrp_phase_aligned_chunks_with_records_on_devices -> (phase_aligned_chunks_with_records' list of dicts in input order, QueueStats with the
+    QueueRecordsStats as its attribute `records`)"""
+    return _phase_aligned(None, chunks, forward_model, reverse_model, params, rests=rests, with_rest=True, with_records=True, devices=list(devices),
+                          chunks_per_batch=chunks_per_batch, **kw)
+
+
 def _phase_aligned(ctx: Optional[Context], chunks, forward_model: Optional[PairHmm], reverse_model: Optional[PairHmm], params: Optional[Params],
                    options: Optional[dict] = None, keeps=None, min_phred: int = 0, expansion: int = 4, sv_threshold: int = 512,
                    het_substitution_probability: float = 0.0, profiles: bool = False, structs=None, nulls=(), rests=None, rest_structs=None,
@@ -2192,22 +2382,31 @@ def _phase_aligned(ctx: Optional[Context], chunks, forward_model: Optional[PairH
         fout[0].n_reads = 77  # (zeroed whatever the outcome)
         fr = (C.c_void_p * max(n, 1))()
         st = QueueStats() if queued else (PhaseAlignedRecordsStats() if with_records else PhaseAlignedFilteredStats())
-        fn = (L.mrp_phase_aligned_chunks_with_filtered_on_devices if devices is not None else L.mrp_queue_phase_aligned_chunks_with_filtered) if queued \
-            else (L.mrp_phase_aligned_chunks_with_records if with_records else L.mrp_phase_aligned_chunks_with_filtered)
+        if queued and with_records:
+            fn = L.mrp_phase_aligned_chunks_with_records_on_devices if devices is not None else L.mrp_queue_phase_aligned_chunks_with_records
+        else:
+            fn = (L.mrp_phase_aligned_chunks_with_filtered_on_devices if devices is not None else L.mrp_queue_phase_aligned_chunks_with_filtered) if queued \
+                else (L.mrp_phase_aligned_chunks_with_records if with_records else L.mrp_phase_aligned_chunks_with_filtered)
         recs = (VariantRecords * max(n, 1))()
         recs[0].n_primary = 77  # (zeroed whatever the outcome)
         tail = (None if "records_out" in nulls else recs,) if with_records else ()
+        after = ()
+        if queued and with_records:  # the queue's stats, then the records' own (kept as st.records)
+            st.records = QueueRecordsStats()
+            after = (C.byref(st.records),)
         t_call = time.perf_counter()
         rc = fn(*head, n, arr, None if "rest" in nulls else rarr, None if "read_names" in nulls else name_ptrs,
                 None if keeps is None else mask_ptrs, None if "options" in nulls else C.byref(opt), by(forward_model),
                 by(reverse_model), int(expansion), int(sv_threshold), float(het_substitution_probability), by(params),
                 int(min_phred), *per_batch, None if "out" in nulls else res, None if "hap_out" in nulls else hp, pp, prof, bv,
-                None if "filtered_out" in nulls else fout, None if "filtered_read_out" in nulls else fr, *tail, C.byref(st))
+                None if "filtered_out" in nulls else fout, None if "filtered_read_out" in nulls else fr, *tail, C.byref(st), *after)
     LAST_ALIGNED_CALL_MS = (time.perf_counter() - t_call) * 1e3
     if with_rest:
         if rc != MRP_OK and n > 0 and not {"rest", "filtered_out", "filtered_read_out", "records_out"} & set(nulls):
             if queued and fout[0].n_reads == 77:  # (the queue writes nothing before its lanes start)
                 fout[0].n_reads = 0
+                if recs[0].n_primary == 77:
+                    recs[0].n_primary = 0
             assert bytes(fout) == bytes((FilteredOut * max(n, 1))()) and not any(fr[i] for i in range(n)), "filtered_out not zeroed on an error"
             if with_records and "records_out" not in nulls:
                 assert bytes(recs) == bytes((VariantRecords * max(n, 1))()), "records_out not zeroed on an error"

@@ -10,7 +10,7 @@
  * worker's next batch run on a second stream while the current batch is phased; every worker has its own host thread pool.
  * The same queue takes the chunks as read and allele strings (mrp_queue_phase_string_chunks): a batch is then what one
  * mrp_phase_string_chunks call phases, and what runs beside the current batch is the host front of the next one.
- * Aligned chunks come the same way, to be phased (mrp_queue_phase_aligned_chunks, with or without the filtered back half) or haplotagged
+ * Aligned chunks come the same way, to be phased (mrp_queue_phase_aligned_chunks, with or without the filtered back half and the phased variant records) or haplotagged
  * from a phased VCF (mrp_queue_haplotag_aligned_chunks: the chunk loop of tools/tagFromPhasedVcf.c:227-309); beside a batch run the checks
  * and windows of the next one.
  */
@@ -767,7 +767,8 @@ int mrp_phase_string_chunks_on_devices(const int32_t *devices, int32_t n_devices
 
 }  /* extern "C" */
 
-/* ---- aligned chunks: mrp_queue_phase_aligned_chunks (rest == NULL) and mrp_queue_phase_aligned_chunks_with_filtered ---------------------- */
+/* ---- aligned chunks: mrp_queue_phase_aligned_chunks (rest == NULL), mrp_queue_phase_aligned_chunks_with_filtered and
+ * mrp_queue_phase_aligned_chunks_with_records (records_out beside filtered_out) -------------------------------------------------------- */
 extern "C" int mrp_aligned_chunk_units(const mrp_aligned_chunk *chunk, const mrp_aligned_chunk_rest *rest, int64_t *units_out) {
     static const char *who = "mrp_aligned_chunk_units";
     if (!chunk || !units_out) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
@@ -796,13 +797,15 @@ struct AlignedQueueArgs {
     mrp_aligned_args a;
     int64_t chunks_per_batch;
     mrp_queue_stats *stats;
+    bool with_records = false;                     /* a.records_out is the caller's array: required, and travels with its chunk */
+    mrp_queue_records_stats *records_stats = nullptr; /* may be NULL */
 };
 
 /* the entry's own null arguments, then every chunk's checks on the caller's thread and in the one call's order: MRP_ERR_ARG, then
  * MRP_ERR_UNSUPPORTED for the two refused extraction modes; no queue, no device */
 int aligned_queue_check(const AlignedQueueArgs &A, bool with_rest) {
     const mrp_aligned_args &a = A.a;
-    if (with_rest && (a.n_chunks < 0 || a.n_chunks >= (1ll << 30) || (a.n_chunks > 0 && (!a.chunks || !a.rest || !a.filtered_out || !a.filtered_read_out))))
+    if (with_rest && (a.n_chunks < 0 || a.n_chunks >= (1ll << 30) || (a.n_chunks > 0 && (!a.chunks || !a.rest || !a.filtered_out || !a.filtered_read_out || (A.with_records && !a.records_out)))))
         return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", A.who);
     return mrp_aligned_chunks_check(A.who, &a);
 }
@@ -813,6 +816,7 @@ int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool wit
     const int64_t n_chunks = a.n_chunks;
     const mrp_aligned_chunk_rest *rest = with_rest ? a.rest : nullptr;
     mrp_queue_stats *stats = A.stats;
+    const bool records = with_rest && A.with_records;
     int rc = checked ? (int) MRP_OK : aligned_queue_check(A, with_rest);
     if (rc != MRP_OK) return rc;
     if (!q) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no queue (the extraction and the pair-HMM have no CPU fallback)", who);
@@ -825,6 +829,8 @@ int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool wit
     }
     if (a.profiles_out && n_chunks > 0) memset(a.profiles_out, 0, sizeof(*a.profiles_out) * (size_t) n_chunks);
     if (rest && n_chunks > 0) memset(a.filtered_out, 0, sizeof(*a.filtered_out) * (size_t) n_chunks);
+    if (records && n_chunks > 0) memset(a.records_out, 0, sizeof(*a.records_out) * (size_t) n_chunks);
+    if (records && A.records_stats) memset(A.records_stats, 0, sizeof(*A.records_stats));
     if (n_chunks == 0) return MRP_OK;
     /* phase.c:257-263 orders by estimated depth; here by the (read, variant) substrings uniform coverage gives a chunk (a read the
      * extraction does not walk, l_qseq <= 0, passes its checks: such a chunk is ordered as if it cost nothing) */
@@ -854,9 +860,13 @@ int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool wit
         std::vector<int64_t *> bv;
         std::vector<mrp_filtered_out> fo;
         std::vector<int32_t *> fr;
+        std::vector<mrp_variant_records> rec;                /* with records: the batch's records ... */
+        std::vector<mrp_phase_aligned_records_stats> rst;    /* ... and, in one entry, its share of the records' stats */
         mrp_aligned_front *front = nullptr;
     };
     std::vector<LaneSlots<Staged>> lane_state((size_t) n_workers);
+    std::vector<mrp_queue_records_stats> rec_per((size_t) n_workers); /* what each lane's batches added to the records' stats */
+    memset(rec_per.data(), 0, sizeof(mrp_queue_records_stats) * rec_per.size());
     auto staged_of = [&](int w, int64_t b) { return lane_state[(size_t) w].find(b); };
     /* (a staged front holds arrays of the lane's context: it goes with no other thread of the lane at work, on the lane's thread) */
     auto drop = [&](Staged *st) { mrp_aligned_front_destroy(st->front); st->front = nullptr; st->batch = -1; };
@@ -879,6 +889,12 @@ int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool wit
         st->fo.resize(rest ? count : 0);
         if (a.profiles_out) memset(st->prof.data(), 0, sizeof(mrp_profile_out) * count);
         if (rest) memset(st->fo.data(), 0, sizeof(mrp_filtered_out) * count);
+        st->rec.resize(records ? count : 0);
+        st->rst.resize(records ? 1 : 0);
+        if (records) {
+            memset(st->rec.data(), 0, sizeof(mrp_variant_records) * count);
+            memset(st->rst.data(), 0, sizeof(mrp_phase_aligned_records_stats));
+        }
         for (size_t i = 0; i < count; i++) {
             const int64_t chunk = plan.order[(size_t) st->first + i];
             st->ch[i] = a.chunks[chunk];
@@ -902,6 +918,8 @@ int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool wit
         ba.bubble_variant_out = a.bubble_variant_out ? st->bv.data() : nullptr;
         ba.filtered_out = rest ? st->fo.data() : nullptr;
         ba.filtered_read_out = rest ? st->fr.data() : nullptr;
+        ba.records_out = records ? st->rec.data() : nullptr;
+        ba.records_stats = records ? st->rst.data() : nullptr;
         const double t_begin = std::chrono::duration<double, std::milli>(t0.time_since_epoch()).count();
         const int r = mrp_aligned_front_create(who, t_begin, &ba, nullptr, nullptr, &st->front);
         if (r != MRP_OK) call.stage_errs[(size_t) w] = mrp_last_error();
@@ -921,11 +939,23 @@ int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool wit
         const double front_ms = ms_since(t0);
         if (r == MRP_OK) r = mrp_aligned_front_run(cur->front, &ss);
         QueueCall::PerLane &me = call.per[(size_t) w];
-        if (r != MRP_OK) call.errs[(size_t) w] = mrp_last_error();
-        else {
+        if (r != MRP_OK) {
+            call.errs[(size_t) w] = mrp_last_error();
+            for (mrp_variant_records &R : cur->rec) mrp_variant_records_clear(&R); /* (a batch that failed behind its records hands none over) */
+        } else {
+            if (records) {
+                mrp_queue_records_stats &mine = rec_per[(size_t) w];
+                const mrp_phase_aligned_records_stats &b = cur->rst[0];
+                mine.records_sites += b.records_sites;
+                mine.records_updated += b.records_updated;
+                mine.reads_listed += b.reads_listed;
+                mine.records_bytes_downloaded += b.records_bytes_downloaded;
+                mine.records_ms += b.records_ms;
+            }
             for (int64_t i = 0; i < count; i++) {
                 const int64_t chunk = plan.order[(size_t) (cur->first + i)];
                 a.out[chunk] = cur->res[(size_t) i];
+                if (records) { a.records_out[chunk] = cur->rec[(size_t) i]; memset(&cur->rec[(size_t) i], 0, sizeof(mrp_variant_records)); }
                 if (a.profiles_out) a.profiles_out[chunk] = cur->prof[(size_t) i];
                 if (a.bubble_variant_out) a.bubble_variant_out[chunk] = cur->bv[(size_t) i];
                 if (rest) { a.filtered_out[chunk] = cur->fo[(size_t) i]; a.filtered_read_out[chunk] = cur->fr[(size_t) i]; }
@@ -955,9 +985,18 @@ int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool wit
                 free(a.filtered_read_out[i]);
                 a.filtered_read_out[i] = nullptr;
             }
+            if (records) mrp_variant_records_clear(&a.records_out[i]);
         }
         return call.error(rc);
     }
+    if (records && A.records_stats)
+        for (const mrp_queue_records_stats &b : rec_per) { /* in lane order: the sum of records_ms does not depend on which lane finished first */
+            A.records_stats->records_sites += b.records_sites;
+            A.records_stats->records_updated += b.records_updated;
+            A.records_stats->reads_listed += b.reads_listed;
+            A.records_stats->records_bytes_downloaded += b.records_bytes_downloaded;
+            A.records_stats->records_ms += b.records_ms;
+        }
     return MRP_OK;
 }
 
@@ -997,6 +1036,39 @@ int mrp_queue_phase_aligned_chunks_with_filtered(mrp_queue *q, int64_t n_chunks,
                               filtered_read_out, q ? q->sv_split : 0, nullptr, nullptr, q ? q->max_depth : 0, q ? q->downsampling_seed : 0},
                              chunks_per_batch, stats};
     return queue_phase_aligned_chunks(q, A, true);
+}
+
+int mrp_queue_phase_aligned_chunks_with_records(mrp_queue *q, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
+                                                const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
+                                                const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion,
+                                                int64_t sv_threshold, double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
+                                                int32_t **filtered_read_out, mrp_variant_records *records_out, mrp_queue_stats *stats,
+                                                mrp_queue_records_stats *records_stats) {
+    const AlignedQueueArgs A{"mrp_queue_phase_aligned_chunks_with_records",
+                             {n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
+                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
+                              filtered_read_out, q ? q->sv_split : 0, records_out, nullptr, q ? q->max_depth : 0, q ? q->downsampling_seed : 0},
+                             chunks_per_batch, stats, true, records_stats};
+    return queue_phase_aligned_chunks(q, A, true);
+}
+
+int mrp_phase_aligned_chunks_with_records_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,
+                                                     const mrp_aligned_chunk_rest *rest, const char *const *const *read_names, const uint8_t *const *keep,
+                                                     const mrp_extract_options *options, const mrp_pair_hmm *forward_model,
+                                                     const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                                     double het_substitution_probability, const mrp_params *params, int64_t min_phred,
+                                                     int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
+                                                     mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
+                                                     int32_t **filtered_read_out, mrp_variant_records *records_out, mrp_queue_stats *stats,
+                                                     mrp_queue_records_stats *records_stats) {
+    const AlignedQueueArgs A{"mrp_phase_aligned_chunks_with_records_on_devices",
+                             {n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
+                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
+                              filtered_read_out, 0, records_out},
+                             chunks_per_batch, stats, true, records_stats};
+    return aligned_on_devices(devices, n_devices, A, true);
 }
 
 int mrp_phase_aligned_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,

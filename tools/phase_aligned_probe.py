@@ -20,6 +20,11 @@ profiles/phase_aligned/filtered.json (or --out).
 --per-batch chunks per batch (12) and with 0, the library's cut.  One process, a warm-up of every leg, the median of --reps with min and
 max, the wall time of the C call alone; one digest over every output per leg.  Writes (or, when the file holds the other variant's
 record, adds to) profiles/phase_aligned/queue.json (or --out).
+
+--queue --filtered --records: the queue with the phased variant records (mrp_queue_phase_aligned_chunks_with_records) beside the queue
+without (mrp_queue_phase_aligned_chunks_with_filtered), the same chunks and --per-batch on one queue over device 0, a warm-up of both,
+the median of --reps with min and max; then the wall time of mrp_close_contigs over the result, cut into contigs of --contig-chunks (8)
+chunks, with the library's default number of host threads and with one.  Adds its record ("with_records") to the same file.
 """
 import argparse
 import ctypes as C
@@ -51,6 +56,8 @@ def main():
     ap.add_argument("--filtered", action="store_true")
     ap.add_argument("--queue", action="store_true")
     ap.add_argument("--per-batch", type=int, default=12)
+    ap.add_argument("--records", action="store_true")
+    ap.add_argument("--contig-chunks", type=int, default=8)
     a = ap.parse_args()
     a.out = a.out or os.path.join(ROOT, "profiles", "phase_aligned", "queue.json" if a.queue else ("filtered.json" if a.filtered else "probe.json"))
     opts = capi.shipped_extract_options()
@@ -66,6 +73,10 @@ def main():
         if a.cache:
             with open(a.cache, "wb") as f:
                 pickle.dump(distinct, f)
+    if a.queue and a.records:
+        if not a.filtered:
+            ap.error("--records needs --queue --filtered")
+        return records_legs(a, distinct, opts)
     if a.queue:
         return queue_legs(a, distinct, opts)
     if a.filtered:
@@ -404,6 +415,91 @@ def queue_legs(a, distinct, opts):
         with open(a.out) as f:
             record = json.load(f)
     record["with_filtered" if a.filtered else "plain"] = res
+    with open(a.out, "w") as f:
+        f.write(json.dumps(record, indent=1) + "\n")
+
+
+def records_legs(a, distinct, opts):
+    """--queue --filtered --records: the queue with the records beside the queue without, then the closing of the result"""
+    n = a.chunks
+    parts = [split(c) for c in distinct]
+    chunks = [parts[i % a.distinct][0] for i in range(n)]
+    fchunks = [parts[i % a.distinct][1] for i in range(n)]
+    built = [capi.aligned_chunk_struct(c) for c in chunks]
+    rbuilt = [capi.aligned_chunk_rest_struct(parts[i % a.distinct][1], parts[i % a.distinct][2]) for i in range(n)]
+    fwd = capi.PairHmm.from_margin_hmm(*synth.margin_phase_pair_hmm_arrays())
+    rev = fwd.reverse_complement()
+    params = capi.Params.from_reference_names(synth.shipped_phase_params())
+    kw = dict(options=opts, structs=built, rest_structs=rbuilt, sv_threshold=SV_THRESHOLD, chunks_per_batch=a.per_batch)
+
+    def digest(got):
+        h = hashlib.sha256()
+        for g in got:
+            o = g["filtered"]
+            for x in (g["hap"], g["phred"], g["result"]["hap1"], g["result"]["hap2"], g["bubble_variant"], o["read_hap"], o["h1"], o["h2"], o["variant_state"],
+                      o["cis"], o["trans"], g["filtered_read"]):
+                h.update(np.ascontiguousarray(x).tobytes())
+        return h.hexdigest()
+
+    legs = {"queue_with_filtered": [], "queue_with_records": []}
+    digests = set()
+    q = capi.Queue([0])
+    try:
+        q.phase_aligned_chunks_with_filtered(chunks, None, fwd, rev, params, **kw)  # warm-up of both legs: module load, the lanes' contexts and pools
+        q.phase_aligned_chunks_with_records(chunks, None, fwd, rev, params, **kw)
+        for _ in range(a.reps):
+            got, _ = q.phase_aligned_chunks_with_filtered(chunks, None, fwd, rev, params, **kw)
+            legs["queue_with_filtered"].append(capi.LAST_ALIGNED_CALL_MS)
+            digests.add(digest(got))
+            got, st = q.phase_aligned_chunks_with_records(chunks, None, fwd, rev, params, **kw)
+            legs["queue_with_records"].append(capi.LAST_ALIGNED_CALL_MS)
+            digests.add(digest(got))
+    finally:
+        q.close()
+    rs = st.records
+    # ---- the closing: the chunks in contigs of --contig-chunks, read ids = a read's index among the distinct chunk's reads
+    na = lambda c: np.array([len(al) for al in c.alleles], np.int32)
+    dicts = [dict(read_names=list(c.read_names), read_id=np.arange(len(c.read_names), dtype=np.int32), hap=g["hap"], phred=g["phred"], filtered=g["filtered"],
+                  filtered_read=g["filtered_read"], records=g["records"], variant_pos=c.variant_pos, n_alleles=na(c), fvariant_pos=f.variant_pos, fn_alleles=na(f))
+             for g, c, f in zip(got, chunks, fchunks)]
+    cbuilt = [capi.contig_chunk_struct(d) for d in dicts]
+    arr = (capi.ContigChunk * n)(*[b[0] for b in cbuilt])
+    first = np.ascontiguousarray(list(range(0, n, a.contig_chunks)) + [n], np.int64)
+    n_contigs = len(first) - 1
+    rules = capi.ContigRules(0, 0, 2, 0.05, 0.5)
+    L = capi.load()
+
+    def close_ms():
+        walls, seen = [], None
+        for _ in range(a.reps + 1):  # (the first is a warm-up: the pool's threads)
+            outs = (capi.ContigOut * n_contigs)()
+            t0 = time.perf_counter()
+            capi._check(L.mrp_close_contigs(n_contigs, first.ctypes.data, arr, C.byref(rules), outs))
+            walls.append((time.perf_counter() - t0) * 1e3)
+            seen = dict(variants=sum(int(O.variants.n_variants) for O in outs), switched=sum(int(x) for O in outs for x in capi._as_np(O.switched, int(O.n_chunks), np.int32)))
+            for O in outs:
+                L.mrp_contig_out_clear(C.byref(O))
+        walls = walls[1:]
+        return dict(median=round(float(np.median(walls)), 3), min=round(min(walls), 3), max=round(max(walls), 3)), seen
+    close_default, seen = close_ms()  # the library's own number of host threads: never set in this process
+    capi._check(L.mrp_set_host_threads(1))
+    close_one, seen_one = close_ms()
+    assert seen == seen_one
+    med = {k: float(np.median(v)) for k, v in legs.items()}
+    res = dict(chunks=n, distinct=a.distinct, reps=a.reps, per_batch=a.per_batch, lanes=int(os.environ.get("MRP_QUEUE_LANES", 4)), batches=int(st.batches),
+               walls_ms={k: dict(median=round(med[k], 2), min=round(min(v), 2), max=round(max(v), 2)) for k, v in legs.items()},
+               records=dict(sites=int(rs.records_sites), updated=int(rs.records_updated), reads_listed=int(rs.reads_listed),
+                            bytes_downloaded=int(rs.records_bytes_downloaded), kernel_ms_summed_over_batches=round(float(rs.records_ms), 3)),
+               close_contigs=dict(contigs=n_contigs, chunks_per_contig=a.contig_chunks, reads=sum(len(d["read_names"]) for d in dicts), kept_variants=seen["variants"],
+                                  chunks_switched=seen["switched"], wall_ms_default_threads=close_default, wall_ms_one_thread=close_one),
+               identical_outputs_with_and_without_records=bool(len(digests) == 1))
+    print(json.dumps(res))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    record = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            record = json.load(f)
+    record["with_records"] = res
     with open(a.out, "w") as f:
         f.write(json.dumps(record, indent=1) + "\n")
 
