@@ -33,6 +33,7 @@
 
 #include "../../include/margin_rphmm.h"
 #include "mrp_internal.h"
+#include "mrp_wave.h"
 
 namespace {
 
@@ -45,13 +46,6 @@ struct AkPair {
     int32_t lx, ly;
 };
 
-static __device__ __forceinline__ int ak_wave_max(int v) {
-    for (int o = 32; o >= 1; o >>= 1) {
-        const int w = __shfl_xor(v, o, AK_WAVE);
-        v = w > v ? w : v;
-    }
-    return v;
-}
 static __device__ __forceinline__ uint32_t ak_dword(const uint8_t *p) {
     return (uint32_t) p[0] | (uint32_t) p[1] << 8 | (uint32_t) p[2] << 16 | (uint32_t) p[3] << 24;
 }
@@ -122,7 +116,7 @@ __global__ void __launch_bounds__(AK_WAVE) ak_chain_kernel(const AkPair *__restr
                 const uint64_t stops = ak_by_distance(__ballot(chainable && (ring_s & 1)), r);
                 const int d_stop = stops ? (int) __builtin_ctzll(stops) : 64;
                 const bool in_walk = chainable && d <= d_stop;
-                const int best = ak_wave_max(in_walk ? ring_s >> 1 : -1);
+                const int best = wave_max_i32(in_walk ? ring_s >> 1 : -1);
                 if (best >= 0) {
                     const uint64_t who = ak_by_distance(__ballot(in_walk && (ring_s >> 1) == best), r);
                     score = best + 1;
@@ -140,7 +134,7 @@ __global__ void __launch_bounds__(AK_WAVE) ak_chain_kernel(const AkPair *__restr
                         const uint64_t st = __ballot(ch && (gs & 1));
                         const int l_stop = st ? (int) __builtin_ctzll(st) : 64;
                         const bool in = ch && lane <= l_stop;
-                        const int b = ak_wave_max(in ? gs >> 1 : -1);
+                        const int b = wave_max_i32(in ? gs >> 1 : -1);
                         if (b >= 0 && b + 1 > score) {
                             score = b + 1;
                             back = top - (int) __builtin_ctzll(__ballot(in && (gs >> 1) == b));

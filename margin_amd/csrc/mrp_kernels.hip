@@ -26,45 +26,14 @@
 #include "mrp_device.h"
 #include "mrp_internal.h"
 #include "mrp_kernels.h"
+#include "mrp_wave.h"
 #include "../../include/margin_rphmm.h"
-
-#define WAVE 64
-
-/* Read-only data that is uniform across a wave (column descriptors, bit planes, site tables) is
- * loaded through the constant address space so that hipcc emits s_load (scalar cache, SGPR
- * operands) instead of 64 identical vector loads.  None of it is written by the kernel reading it. */
-#define K_AS(T) const __attribute__((address_space(4))) T *
-#define K_PTR(T, p) ((K_AS(T)) (p))
-/* whole-struct load through the scalar path (dword copies; SROA turns them into s_load_dwordxN) */
-template <typename T>
-static __device__ __forceinline__ T k_load(const T *p) {
-    static_assert(sizeof(T) % 4 == 0, "dword sized");
-    T v;
-    K_AS(uint32_t) s = K_PTR(uint32_t, p);
-    uint32_t *dst = reinterpret_cast<uint32_t *>(&v);
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(T) / 4; i++) dst[i] = s[i];
-    return v;
-}
 
 static __device__ __forceinline__ double i32_to_log(int32_t v) {
     return v == MRP_NEG_I32 ? -__builtin_inf() : (double) v;
 }
 static __device__ __forceinline__ int32_t add_i32(int32_t a, int32_t b) {
     return a == MRP_NEG_I32 ? MRP_NEG_I32 : a + b;
-}
-/* Workgroup barrier that orders LDS traffic only.  __syncthreads() also emits s_waitcnt vmcnt(0),
- * which would drain the prefetched global loads (and wait for every store) at each column. */
-static __device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-static __device__ __forceinline__ int32_t wave_max_i32(int32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        int32_t t = __shfl_xor(v, o, WAVE);
-        v = t > v ? t : v;
-    }
-    return v;
 }
 
 /* ------------------------------------------------------------------------------------------ */

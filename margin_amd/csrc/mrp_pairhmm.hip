@@ -39,6 +39,7 @@
 #include "../../include/margin_rphmm.h"
 #include "mrp_internal.h"
 #include "mrp_pairhmm.h"
+#include "mrp_wave.h"
 #include "rphmm_host.h"
 
 #pragma clang fp contract(off)
@@ -126,13 +127,6 @@ static __device__ __forceinline__ double phm_dot(const St &f, const double *e) {
     tot = phm_log_add(tot, f.x + e[1]);
     return phm_log_add(tot, f.y + e[2]);
 }
-static __device__ __forceinline__ int phm_wave_max(int v) {
-    for (int o = 32; o >= 1; o >>= 1) {
-        const int w = __shfl_xor(v, o, PHM_WAVE);
-        v = w > v ? w : v;
-    }
-    return v;
-}
 
 /* LDS: coef[16] | etab[n_models][cx][cy][6] = eX + {open, extend, switch to x}, eM + {continue, from x, from y} |
  * rows[wave][x - 1][state][lane].  The waves of a workgroup share the tables and nothing else.
@@ -173,7 +167,7 @@ __global__ void __launch_bounds__(256) phm_lane_kernel(const PhmLanePair *__rest
     if (have) p = pairs[pi];
     else { p.x_off = 0; p.y_off = 0; p.lx = -1; p.ly = -1; p.model = 0; p.out = 0; }
     const int lx = p.lx, ly = p.ly;
-    const int mx = phm_wave_max(lx), my = phm_wave_max(ly);
+    const int mx = wave_max_i32(lx), my = wave_max_i32(ly);
     const int mx1 = mx > 1 ? mx : 1;
     const PhmModelDev *__restrict__ M = models + p.model;
     const double t_open_y = M->t[4], t_extend_y = M->t[6], t_switch_y = M->t[8];

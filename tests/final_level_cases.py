@@ -6,7 +6,7 @@ what the case must exhibit, computed from the oracle alone (OracleChunk.phase wi
 chunk's arrays.  tests/test_final_level_cases.py asserts the facts without a device, tests/test_gpu_final_level.py runs the rows on
 one.  Builders, oracle chunks and oracle runs are cached: each is made once per process, whichever module asks first.
 
-The edges (mrp_engine_kernels.hip):
+The edges (mrp_engine_final.hip):
   rounds        the refinement stops at max_iterations or at the first round that moves nothing; the lists swap between two buffers
                 every moving round and are copied back after an odd number of them.  Six chunks whose last moving round m is
                 0, 1, 2, 3, 4 and 5, each at the limits 0, m - 1, m, m + 1 and 10.
