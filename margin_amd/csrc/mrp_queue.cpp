@@ -22,9 +22,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
-#include <system_error>
 #include <mutex>
-#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -34,164 +32,9 @@
 #include <cctype>
 
 #include "mrp_internal.h"
+#include "mrp_queue_lanes.h" /* the plan and the hand-out: plan_queue, active_lanes_of, run_lanes + LaneHooks */
 
 int mrp_queue_threads_per_device(int n_devices);
-
-namespace {
-
-struct QueuePlan {
-    std::vector<int64_t> order;     /* chunk indices, largest estimated cost first (ties: input order) */
-    std::vector<int64_t> batch_off; /* batch b = order[batch_off[b] .. batch_off[b + 1]) */
-};
-
-/* phase.c:257-263: sort by estimated size, largest first; then cut into batches of consecutive chunks.
- * chunks_per_batch >= 1: batches of that many chunks.  0: the library's choice for n_workers pulling threads on n_devices
- * devices.  A batch is one mrp_phase_reads_many call; a call begins and ends with host work and walks its merge levels one
- * after the other, the top ones bound by per-column latency whatever the number of chunks.  A short queue (up to 1 280 chunks
- * of the 1 Mb kind per device -- 640 through round 3, when a device held twice as much per chunk; sizes are counted in units, below) is ONE batch per device: the call runs it as eight concurrent batches of its own (576 chunks: 170-182 ms).  A
- * longer one is handed out in batches of MRP_QUEUE_DEFAULT_BATCH chunks to the lanes of the devices (four per device, each
- * call two concurrent batches: the same eight in flight, but at different levels -- while one lane is in its host-bound
- * head or its latency-bound top levels the others stream; measured on 2 304 chunks: 153-160 ms per 576 against 174-177 for
- * one lane of 576-chunk calls), shrinking towards the end (several devices: "guided" schedule, remaining / workers, at least 96) so that the
- * devices finish within two percent of each other (tests/test_work_queue.py: 8 devices, 31 000 chunks) without the tail of
- * the queue dissolving into small, latency-bound calls. */
-QueuePlan plan_queue(int64_t n, const int64_t *cost, int64_t chunks_per_batch, int n_workers = 1, int n_devices = 1) {
-    QueuePlan p;
-    p.order.resize((size_t) n);
-    std::iota(p.order.begin(), p.order.end(), (int64_t) 0);
-    std::stable_sort(p.order.begin(), p.order.end(), [&](int64_t a, int64_t b) { return cost[a] > cost[b]; });
-    /* Sizes are counted in UNITS (a chunk's cost: its reads x the het sites they span), with the 1 Mb, 30x chunk of
-     * BASELINE.json configs[1] (60 000 units) as the yardstick the policy was measured on: what a call costs the device and
-     * what it keeps there grow with its units, not with its chunks -- 192 chunks of 130 sites would be a call of 9 ms. */
-    const int64_t unit_chunk = MRP_QUEUE_UNITS_PER_CHUNK;
-    const int64_t big = MRP_QUEUE_DEFAULT_BATCH * unit_chunk, short_queue = MRP_QUEUE_SHORT_CHUNKS * unit_chunk;
-    auto units = [&](int64_t pos) { return std::max<int64_t>(1, cost[p.order[(size_t) pos]]); };
-    int64_t total = 0;
-    for (int64_t i = 0; i < n; i++) total += units(i);
-    if (chunks_per_batch >= 1) {
-        for (int64_t o = 0; o < n; o += chunks_per_batch) p.batch_off.push_back(o);
-    } else if (total <= (int64_t) n_devices * short_queue) {
-        /* up to MRP_QUEUE_SHORT_CHUNKS yardstick chunks per device ONE call per device is the fastest */
-        const int64_t parts = std::min<int64_t>(n, n_devices);
-        /* these batches all start at once: deal the chunks out in stripes (batch b takes the b-th, (b + parts)-th, ... of the
-         * cost order), so that every batch gets its share of the expensive ones -- consecutive runs of a largest-first order
-         * would make the first batch the slowest by a third */
-        std::vector<int64_t> striped;
-        striped.reserve((size_t) n);
-        for (int64_t b = 0; b < parts; b++) {
-            p.batch_off.push_back((int64_t) striped.size());
-            for (int64_t i = b; i < n; i += parts) striped.push_back(p.order[(size_t) i]);
-        }
-        p.order.swap(striped);
-    } else {
-        int64_t left = total;
-        /* one device: its lanes share it, so there is nothing to even out between them towards the end -- but they should all be
-         * busy to the end: as many equal batches as fill whole rounds of the lanes (1 152 chunks on four lanes: 8 batches of 144
-         * rather than 6 of 192, of which the last two would run on half the lanes) */
-        const int64_t lanes_of_device = std::max(1, n_workers / std::max(1, n_devices));
-        const int64_t rounds = (total + lanes_of_device * big - 1) / (lanes_of_device * big);
-        const int64_t even = (total + rounds * lanes_of_device - 1) / (rounds * lanes_of_device);
-        for (int64_t o = 0; o < n;) { /* several devices: full batches while every lane can still get two, then shrinking, at least a quarter batch */
-            p.batch_off.push_back(o);
-            /* (a lane holds two batches, the one it phases and the one it took ahead: what is left is shared out as if there were
-             * twice the lanes; the floor of a quarter batch keeps the tail from dissolving into latency-bound calls) */
-            const int64_t target = n_devices > 1 ? std::max<int64_t>(big / 4, std::min<int64_t>(big, left / (2 * (int64_t) std::max(1, n_workers)))) : even;
-            int64_t got = 0;
-            do { got += units(o); o++; } while (o < n && got + units(o) / 2 < target);
-            if (left - got < target / 2) /* (what would be left is no batch of its own) */
-                while (o < n) { got += units(o); o++; }
-            left -= got;
-        }
-    }
-    p.batch_off.push_back(n);
-    return p;
-}
-
-/* How many calls of a device run at a time: a device holds what its calls in flight need (some 170 MB per 1 Mb chunk = 60 000 units,
- * DevPool): four lanes for batches of up to 288 such chunks, two up to 576, one beyond; a queue of no more batches than
- * devices needs one lane each. */
-int active_lanes_of(const QueuePlan &plan, const int64_t *cost, int n_devices, int lanes) {
-    const int64_t n_batches = (int64_t) plan.batch_off.size() - 1;
-    int64_t max_batch = 0;
-    for (int64_t b = 0; b < n_batches; b++) {
-        int64_t u = 0;
-        for (int64_t i = plan.batch_off[(size_t) b]; i < plan.batch_off[(size_t) b + 1]; i++) u += cost[(size_t) plan.order[(size_t) i]];
-        max_batch = std::max(max_batch, u);
-    }
-    const int64_t yard = MRP_QUEUE_UNITS_PER_CHUNK;
-    return n_batches <= (int64_t) n_devices ? 1 : (max_batch <= 288 * yard ? lanes : (max_batch <= 576 * yard ? std::min(lanes, 2) : 1));
-}
-
-/* The hand-out of the queue, shared by the real workers and the dry run: lane w = device w / lanes; a lane that is active takes
- * its first batch (fixed, below), then -- schedule(dynamic,1), one batch ahead -- takes its NEXT batch when it starts on the current one
- * (`prefetch(w, next batch)` runs beside `phase(w, current batch)`: the real worker uploads there) and goes on until the shared
- * counter runs out.  A lane without a first batch does nothing (no contexts, no streams).  begin(w) / end(w) bracket a lane that
- * got work; any non-zero status stops the queue.  Every lane is a host thread; lane 0 runs on the caller's thread unless
- * `own_thread_for_lane0`. */
-struct LaneHooks {
-    std::function<int(int)> begin;                     /* lane */
-    std::function<int(int, int64_t)> prefetch;         /* lane, batch: may run on another thread than phase */
-    std::function<int(int, int64_t)> phase;            /* lane, batch */
-    std::function<void(int, int64_t)> retire;          /* lane, batch: after phase AND after the prefetch that ran beside it has ended */
-    std::function<void(int, int64_t)> discard;         /* lane, batch: a prefetched batch that will not be phased */
-    std::function<void(int)> end;
-};
-int run_lanes(int n_devices, int lanes, int active_lanes, int64_t n_batches, const LaneHooks &hk, bool own_thread_for_lane0,
-              const std::function<void(int)> &on_thread_start) {
-    const int n_workers = n_devices * lanes;
-    /* The FIRST batch of a lane is fixed: batch (lane of device) * n_devices + device, so the largest batches start on different
-     * devices and no lane that starts early can take (and, one ahead, reserve) the work of a device whose thread is not up yet --
-     * with as many batches as devices every device gets exactly one.  From there on the hand-out is dynamic. */
-    std::atomic<int64_t> next{std::min<int64_t>(n_batches, (int64_t) n_devices * active_lanes)};
-    std::atomic<int> status{MRP_OK};
-    auto fail = [&](int rc) { int expect = MRP_OK; status.compare_exchange_strong(expect, rc); };
-    auto work = [&](int w) {
-        if (on_thread_start) on_thread_start(w);
-        if (w % lanes >= active_lanes) return; /* (large caller-chosen batches: fewer calls of a device in flight) */
-        const int64_t first = (int64_t) (w % lanes) * n_devices + w / lanes;
-        if (first >= n_batches) return;
-        int rc = hk.begin ? hk.begin(w) : MRP_OK;
-        if (rc != MRP_OK) { fail(rc); return; }
-        rc = hk.prefetch ? hk.prefetch(w, first) : MRP_OK;
-        int64_t cur = first;
-        while (cur >= 0) {
-            if (rc != MRP_OK) { fail(rc); if (hk.discard) hk.discard(w, cur); break; }
-            if (status.load() != MRP_OK) { if (hk.discard) hk.discard(w, cur); break; }
-            const int64_t nb = next.fetch_add(1);
-            int prc = MRP_OK;
-            std::thread stager;
-            bool inline_stage = false;
-            if (nb < n_batches && hk.prefetch) {
-                try { stager = std::thread([&, nb] { prc = hk.prefetch(w, nb); }); }
-                catch (const std::system_error &) { inline_stage = true; } /* no thread to be had: stage after the call instead */
-            }
-            rc = hk.phase(w, cur);
-            if (stager.joinable()) stager.join();
-            if (hk.retire) hk.retire(w, cur); /* (what the batch held goes back with no other thread of the lane at work) */
-            if (inline_stage) prc = hk.prefetch(w, nb);
-            if (rc != MRP_OK) { fail(rc); if (nb < n_batches && hk.discard) hk.discard(w, nb); break; }
-            cur = nb < n_batches ? nb : -1;
-            rc = prc;
-        }
-        if (hk.end) hk.end(w);
-    };
-    std::vector<std::thread> th;
-    std::vector<int> inline_lanes; /* lanes whose thread could not be created run on the caller's thread, after lane 0 */
-    for (int w = 1; w < n_workers; w++) {
-        try { th.emplace_back(work, w); }
-        catch (const std::system_error &) { inline_lanes.push_back(w); }
-    }
-    if (own_thread_for_lane0) {
-        bool started = false;
-        try { std::thread t0(work, 0); started = true; t0.join(); }
-        catch (const std::system_error &) { if (!started) work(0); }
-    } else work(0);
-    for (int w : inline_lanes) work(w);
-    for (auto &t : th) t.join();
-    return status.load();
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -401,21 +244,6 @@ struct QueueCall {
     }
     void lane_end(int w) { mrp_pool_adopt(caller_pool[(size_t) w]); }
 
-    /* runs the lanes; when the queue drives more than one device, each on the CPUs next to its device */
-    int run(const LaneHooks &hk) {
-        const int n_devices = (int) q->devices.size(), lanes = q->lanes;
-        const char *aff_env = getenv("MRP_QUEUE_AFFINITY");
-        const bool bind = n_devices > 1 && !(aff_env && aff_env[0] == '0');
-        /* before the first thread of a worker is created (they inherit it): the CPUs next to its device */
-        std::function<void(int)> on_start;
-        if (bind) on_start = [this, lanes](int w) {
-            cpu_set_t set;
-            if (device_cpuset(q->devices[(size_t) (w / lanes)], &set)) (void) pthread_setaffinity_np(pthread_self(), sizeof(set), &set);
-        };
-        const int rc = run_lanes(n_devices, lanes, active_lanes, n_batches, hk, /* the caller's own affinity is left alone */ bind, on_start);
-        if (timing) fprintf(stderr, "  [%7.1f] queue: workers joined\n", since());
-        return rc;
-    }
     void fill(mrp_queue_stats *stats) const {
         if (!stats) return;
         for (size_t w = 0; w < per.size(); w++) {
@@ -435,18 +263,118 @@ struct QueueCall {
     }
 };
 
-/* What the bodies whose prefetch makes a host front share (string chunks, aligned chunks phased and haplotagged): a lane's two staged batches -- the one it runs and the one its
- * prefetch makes beside it -- and the create + call + destroy of the *_on_devices forms. */
+/* runs the lanes; when the queue drives more than one device, each on the CPUs next to its device */
+static int run_call(QueueCall &call, const LaneHooks &hk) {
+    mrp_queue *q = call.q;
+    const int n_devices = (int) q->devices.size(), lanes = q->lanes;
+    const char *aff_env = getenv("MRP_QUEUE_AFFINITY");
+    const bool bind = n_devices > 1 && !(aff_env && aff_env[0] == '0');
+    /* before the first thread of a worker is created (they inherit it): the CPUs next to its device */
+    std::function<void(int)> on_start;
+    if (bind) on_start = [q, lanes](int w) {
+        cpu_set_t set;
+        if (device_cpuset(q->devices[(size_t) (w / lanes)], &set)) (void) pthread_setaffinity_np(pthread_self(), sizeof(set), &set);
+    };
+    const int rc = run_lanes(n_devices, lanes, call.active_lanes, call.n_batches, hk, /* the caller's own affinity is left alone */ bind, on_start);
+    if (call.timing) fprintf(stderr, "  [%7.1f] queue: workers joined\n", call.since());
+    return rc;
+}
+
+/* What every chunk kind's batches share: the head of a staged batch, a lane's two of them -- the one it runs and the one its
+ * prefetch makes beside it --, the one driver that takes a kind's batches through the lanes, and the create + call + destroy of the
+ * *_on_devices forms. */
+struct StagedBatch {
+    std::atomic<int64_t> batch{-1}; /* (the call's thread looks its batch up while the stager fills the lane's OTHER slot) */
+    int64_t first = 0, count = 0;   /* the batch is plan.order[first .. first + count) */
+};
 template <typename Staged>
 struct LaneSlots {
     Staged st[2];
     int n_staged = 0;
-    Staged *next() { return &st[n_staged++ & 1]; } /* (the stager fills the slot the call's thread is not running) */
+    Staged *next(int *slot) { *slot = n_staged++ & 1; return &st[*slot]; } /* (the stager fills the slot the call's thread is not running) */
     Staged *find(int64_t b) { return st[0].batch.load() == b ? &st[0] : (st[1].batch.load() == b ? &st[1] : nullptr); }
 };
 static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
+/* (the three phasing kinds: a batch the resident path did not take went through the per-chunk path as a whole) */
+static void count_fallback(QueueCall::PerLane &me, const mrp_phase_many_stats &ps, int64_t count) {
+    me.fallback += ps.resident ? ps.fallback_chunks : count;
+}
+
+/* The queue for one chunk kind: the plan, the lanes, the two slots of each, the accounting and the MRP_TIMING lines; on an error
+ * `clear_outputs()` and the first error text.  The preamble (the checks, zeroing the outputs, the costs) is the entry's.  A Body has
+ *   Staged                   what it keeps of a staged batch, derived from StagedBatch;
+ *   on_stage_ctx             the batch is made on, and lives on, a second context of the lane (uploads beside the call): the lane gets
+ *                            one, and giving the batch back is device work that counts as the lane's busy time;
+ *   staged_line, not_ready   the MRP_TIMING line of a prefetch; the error text of a batch that reaches its call unstaged;
+ *   stage(w, slot, st, order)        gather the batch (chunks order[0 .. st.count)) and make its front or upload it: runs beside the
+ *                                    lane's current call, from the second batch on on a thread of its own; MRP_OK: it can be run;
+ *   run(w, st, order, me, &split_ms) the call, then the results to the caller's arrays at the positions order[i]; split_ms is what
+ *                                    print_run wants beside the time of the whole;
+ *   print_run(since, w, b, all_ms, split_ms)  the MRP_TIMING line of a call;
+ *   drop(st)                         give back what the staged batch holds. */
+template <typename Body, typename Clear>
+static int run_queue(mrp_queue *q, int64_t n_chunks, const std::vector<int64_t> &cost, int64_t chunks_per_batch, mrp_queue_stats *stats, Body &body,
+                     Clear clear_outputs) {
+    using Staged = typename Body::Staged;
+    const int n_devices = (int) q->devices.size(), lanes = q->lanes, n_workers = n_devices * lanes;
+    const QueuePlan plan = plan_queue(n_chunks, cost.data(), chunks_per_batch, n_workers, n_devices);
+    const int64_t n_batches = (int64_t) plan.batch_off.size() - 1;
+    if (stats) stats->batches = n_batches;
+    QueueCall call(q, n_batches, active_lanes_of(plan, cost.data(), n_devices, lanes));
+    std::vector<LaneSlots<Staged>> lane_state((size_t) n_workers);
+    auto staged_of = [&](int w, int64_t b) { return lane_state[(size_t) w].find(b); };
+    auto drop = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) { body.drop(*st); st->batch = -1; } };
+    LaneHooks hk;
+    hk.begin = [&](int w) { return call.lane_begin(w, Body::on_stage_ctx); };
+    hk.prefetch = [&](int w, int64_t b) { /* (the first batch on the lane's thread, the later ones on a thread beside the call) */
+        const auto t0 = std::chrono::steady_clock::now();
+        mrp_pool_adopt(q->pools[(size_t) (w / lanes)]);
+        int slot = 0;
+        Staged *st = lane_state[(size_t) w].next(&slot);
+        st->first = plan.batch_off[(size_t) b]; st->count = plan.batch_off[(size_t) b + 1] - st->first;
+        st->batch.store(b);
+        const int r = body.stage(w, slot, *st, plan.order.data() + st->first);
+        if (r != MRP_OK) call.stage_errs[(size_t) w] = mrp_last_error();
+        if (call.timing) fprintf(stderr, Body::staged_line, call.since(), w, (long long) b, (long long) st->count, ms_since(t0));
+        return r;
+    };
+    hk.discard = drop;
+    hk.phase = [&](int w, int64_t b) {
+        Staged *cur = staged_of(w, b);
+        if (!cur) { call.errs[(size_t) w] = Body::not_ready; return (int) MRP_ERR_ARG; }
+        const auto t0 = std::chrono::steady_clock::now();
+        const int64_t *order = plan.order.data() + cur->first;
+        QueueCall::PerLane &me = call.per[(size_t) w];
+        double split_ms = 0;
+        const int r = body.run(w, *cur, order, me, &split_ms);
+        if (r != MRP_OK) call.errs[(size_t) w] = mrp_last_error();
+        else {
+            for (int64_t i = 0; i < cur->count; i++) me.units += cost[(size_t) order[i]];
+            me.chunks += cur->count;
+        }
+        const double all_ms = ms_since(t0);
+        if (call.timing) body.print_run(call.since(), w, b, all_ms, split_ms);
+        me.busy_ms += all_ms;
+        return r;
+    };
+    /* (a batch on the lane's STAGING context, on which the stager thread makes the next batch while the call runs, goes after that
+     * thread has ended: one host thread per context, include/margin_rphmm.h; a staged front holds arrays of the lane's context and
+     * goes on the lane's thread with no other thread of the lane at work) */
+    hk.retire = [&](int w, int64_t b) {
+        const auto t0 = std::chrono::steady_clock::now();
+        drop(w, b);
+        if (Body::on_stage_ctx) call.per[(size_t) w].busy_ms += ms_since(t0);
+    };
+    hk.end = [&](int w) { call.lane_end(w); };
+    const int rc = run_call(call, hk);
+    call.fill(stats);
+    if (rc == MRP_OK) return MRP_OK;
+    clear_outputs();
+    return call.error(rc);
+}
+
 /* the queue's own order of errors: a malformed call and a refused mode need no device; then mrp_queue_create's own error */
 template <typename Check, typename Run>
 static int checked_on_devices(const int32_t *devices, int32_t n_devices, Check check, Run run) {
@@ -459,13 +387,64 @@ static int checked_on_devices(const int32_t *devices, int32_t n_devices, Check c
     return rc;
 }
 
+namespace {
+
+/* chunks as profile bytes: a batch is what one mrp_phase_reads_many call phases; its chunks are on the device before the call (uploads
+ * queued on the staging context's stream; the chunks carry the event that ends the upload, the first device work that reads one waits
+ * for it) */
+struct ProfileBody {
+    struct Staged : StagedBatch { std::vector<mrp_chunk *> dch; };
+    static constexpr bool on_stage_ctx = true;
+    static constexpr const char *staged_line = "  [%7.1f] queue lane %d: batch %lld (%lld chunks) staged in %.1f ms\n";
+    static constexpr const char *not_ready = "work queue: batch was not staged";
+    mrp_queue *q;
+    const mrp_chunk_desc *chunks;
+    const mrp_params *params;
+    mrp_phase_result **out;
+
+    int stage(int w, int slot, Staged &st, const int64_t *order) {
+        st.dch.assign((size_t) st.count, nullptr);
+        mrp_context *sc = q->stage_ctx[(size_t) w];
+        sc->pool.reclaim(); /* the block of the batch before last was emptied after its call returned */
+        mrp_chunk_block *&blk = q->blocks[(size_t) w * 2 + (size_t) slot]; /* (the block of the slot: the other one's is in use) */
+        if (!blk) blk = new (std::nothrow) mrp_chunk_block();
+        if (!blk) return mrp_set_error(MRP_ERR_NOMEM, "out of host memory");
+        std::vector<const mrp_chunk_desc *> dl((size_t) st.count);
+        for (int64_t i = 0; i < st.count; i++) dl[(size_t) i] = &chunks[order[i]];
+        /* (uploaded in the groups the call will deal the chunks to: its first batch starts on the device when an eighth of the bytes is there) */
+        return mrp_chunk_block_create(sc, st.count, dl.data(), st.dch.data(), blk, mrp_phase_groups_for(q->ctx[(size_t) w], st.count));
+    }
+    int run(int w, Staged &st, const int64_t *order, QueueCall::PerLane &me, double *) {
+        const size_t count = (size_t) st.count;
+        std::vector<const mrp_chunk *> cch(st.dch.begin(), st.dch.end());
+        std::vector<const mrp_read *> rd(count);
+        std::vector<int64_t> nr(count);
+        std::vector<mrp_phase_result *> res(count, nullptr);
+        for (size_t i = 0; i < count; i++) { rd[i] = chunks[order[i]].reads; nr[i] = chunks[order[i]].n_reads; }
+        mrp_phase_many_stats ps{};
+        const int r = mrp_phase_reads_many(q->ctx[(size_t) w], st.count, cch.data(), rd.data(), nr.data(), params, res.data(), &ps);
+        if (r != MRP_OK) return r;
+        for (size_t i = 0; i < count; i++) out[order[i]] = res[i];
+        count_fallback(me, ps, st.count);
+        return r;
+    }
+    void print_run(double since, int w, int64_t b, double all_ms, double) const {
+        fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld phased in %.1f ms\n", since, w, (long long) b, all_ms);
+    }
+    void drop(Staged &st) { /* (a thousand chunks of a one-call queue: on the lane's pool, not one after the other) */
+        mrp_parallel_for((int64_t) st.dch.size(), 8, [&](int64_t i) { if (st.dch[(size_t) i]) mrp_chunk_destroy(st.dch[(size_t) i]); });
+        st.dch.clear();
+    }
+};
+
+}  // namespace
+
 extern "C" {
 
 int mrp_queue_phase_chunks(mrp_queue *q, int64_t n_chunks, const mrp_chunk_desc *chunks, const mrp_params *params, int64_t chunks_per_batch,
                            mrp_phase_result **out, mrp_queue_stats *stats) {
     if (!q || n_chunks < 0 || !params || (n_chunks > 0 && (!chunks || !out))) return mrp_set_error(MRP_ERR_ARG, "mrp_queue_phase_chunks: bad arguments");
-    const int n_devices = (int) q->devices.size();
-    if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = n_devices; }
+    if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = (int) q->devices.size(); }
     for (int64_t i = 0; i < n_chunks; i++) out[i] = nullptr;
     if (n_chunks == 0) return MRP_OK;
     /* estimated cost of a chunk: its het-sites x reads (what the depth estimate of phase.c:259 stands for) */
@@ -476,115 +455,83 @@ int mrp_queue_phase_chunks(mrp_queue *q, int64_t n_chunks, const mrp_chunk_desc 
             return mrp_set_error(MRP_ERR_ARG, "chunk %lld: bad description", (long long) i);
         for (int64_t r = 0; r < c.n_reads; r++) cost[(size_t) i] += c.reads[r].length;
     }
-    const int lanes = q->lanes, n_workers = n_devices * lanes;
-    const QueuePlan plan = plan_queue(n_chunks, cost.data(), chunks_per_batch, n_workers, n_devices);
-    const int64_t n_batches = (int64_t) plan.batch_off.size() - 1;
-    if (stats) stats->batches = n_batches;
-
-    QueueCall call(q, n_batches, active_lanes_of(plan, cost.data(), n_devices, lanes));
-    std::vector<std::string> &errs = call.errs, &stage_errs = call.stage_errs;
-    std::vector<QueueCall::PerLane> &per = call.per;
-
-    /* the chunks of one batch on the device (uploads queued on the staging context's stream; the chunks carry the event that
-     * ends the upload, the first device work that reads one waits for it) */
-    struct Staged {
-        std::atomic<int64_t> batch{-1}; /* (the call's thread looks its batch up while the stager fills the lane's OTHER slot) */
-        int64_t first = 0, count = 0;
-        std::vector<mrp_chunk *> dch;
-    };
-    struct Lane { Staged st[2]; int n_staged = 0; };
-    std::vector<Lane> lane_state((size_t) n_workers);
-    const bool timing = call.timing;
-    auto since = [&]() { return call.since(); };
-    auto drop = [&](Staged *st) { /* (a thousand chunks of a one-call queue: on the lane's pool, not one after the other) */
-        mrp_parallel_for((int64_t) st->dch.size(), 8, [&](int64_t i) { if (st->dch[(size_t) i]) mrp_chunk_destroy(st->dch[(size_t) i]); });
-        st->dch.clear();
-        st->batch = -1;
-    };
-    auto staged_of = [&](int w, int64_t b) -> Staged * {
-        Lane &L = lane_state[(size_t) w];
-        return L.st[0].batch.load() == b ? &L.st[0] : (L.st[1].batch.load() == b ? &L.st[1] : nullptr);
-    };
-    LaneHooks hk;
-    hk.begin = [&](int w) { return call.lane_begin(w, true); };
-    hk.prefetch = [&](int w, int64_t b) { /* (the first batch on the lane's thread, the later ones on a thread beside the call) */
-        const auto ts0 = std::chrono::steady_clock::now();
-        const int d = w / lanes;
-        mrp_pool_adopt(q->pools[(size_t) d]);
-        Lane &L = lane_state[(size_t) w];
-        const int parity = L.n_staged++ & 1;
-        Staged *st = &L.st[parity];
-        st->first = plan.batch_off[(size_t) b]; st->count = plan.batch_off[(size_t) b + 1] - st->first;
-        st->dch.assign((size_t) st->count, nullptr);
-        st->batch.store(b);
-        mrp_context *sc = q->stage_ctx[(size_t) w];
-        sc->pool.reclaim(); /* the block of the batch before last was emptied after its call returned */
-        mrp_chunk_block *&blk = q->blocks[(size_t) w * 2 + (size_t) parity];
-        if (!blk) blk = new (std::nothrow) mrp_chunk_block();
-        std::vector<const mrp_chunk_desc *> dl((size_t) st->count);
-        for (int64_t i = 0; i < st->count; i++) dl[(size_t) i] = &chunks[plan.order[(size_t) (st->first + i)]];
-        /* (uploaded in the groups the call will deal the chunks to: its first batch starts on the device when an eighth of the bytes is there) */
-        const int rc = blk ? mrp_chunk_block_create(sc, st->count, dl.data(), st->dch.data(), blk, mrp_phase_groups_for(q->ctx[(size_t) w], st->count))
-                           : mrp_set_error(MRP_ERR_NOMEM, "out of host memory");
-        if (rc != MRP_OK) stage_errs[(size_t) w] = mrp_last_error();
-        if (timing) fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld (%lld chunks) staged in %.1f ms\n", since(), w, (long long) b, (long long) st->count,
-                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts0).count());
-        return rc;
-    };
-    hk.discard = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
-    hk.phase = [&](int w, int64_t b) {
-        Staged *cur = staged_of(w, b);
-        if (!cur) { errs[(size_t) w] = "work queue: batch was not staged"; return (int) MRP_ERR_ARG; }
-        auto t0 = std::chrono::steady_clock::now();
-        const int64_t count = cur->count;
-        std::vector<const mrp_chunk *> cch((size_t) count);
-        std::vector<const mrp_read *> rd((size_t) count);
-        std::vector<int64_t> nr((size_t) count);
-        std::vector<mrp_phase_result *> res((size_t) count, nullptr);
-        for (int64_t i = 0; i < count; i++) {
-            const mrp_chunk_desc &c = chunks[plan.order[(size_t) (cur->first + i)]];
-            cch[(size_t) i] = cur->dch[(size_t) i]; rd[(size_t) i] = c.reads; nr[(size_t) i] = c.n_reads;
-        }
-        mrp_phase_many_stats ps{};
-        const int r = mrp_phase_reads_many(q->ctx[(size_t) w], count, cch.data(), rd.data(), nr.data(), params, res.data(), &ps);
-        if (r != MRP_OK) errs[(size_t) w] = mrp_last_error();
-        for (int64_t i = 0; i < count; i++) {
-            const int64_t chunk = plan.order[(size_t) (cur->first + i)];
-            if (r == MRP_OK) { out[chunk] = res[(size_t) i]; per[(size_t) w].units += cost[(size_t) chunk]; }
-        }
-        if (r == MRP_OK) { per[(size_t) w].chunks += count; per[(size_t) w].fallback += ps.resident ? ps.fallback_chunks : count; }
-        if (timing) fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld phased in %.1f ms\n", since(), w, (long long) b,
-                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        per[(size_t) w].busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return r;
-    };
-    /* the batch's chunks live on the lane's STAGING context, on which the stager thread makes the next batch's block while the call
-     * runs: they are destroyed after that thread has ended (one host thread per context, include/margin_rphmm.h) */
-    hk.retire = [&](int w, int64_t b) {
-        const auto t0 = std::chrono::steady_clock::now();
-        if (Staged *st = staged_of(w, b)) drop(st);
-        per[(size_t) w].busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    };
-    hk.end = [&](int w) { call.lane_end(w); };
-    const int rc = call.run(hk);
-    call.fill(stats);
-    if (rc != MRP_OK) {
+    ProfileBody body{q, chunks, params, out};
+    return run_queue(q, n_chunks, cost, chunks_per_batch, stats, body, [&] {
         for (int64_t i = 0; i < n_chunks; i++) { mrp_phase_result_destroy(out[i]); out[i] = nullptr; }
-        return call.error(rc);
-    }
-    return MRP_OK;
+    });
 }
 
 int mrp_phase_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_chunk_desc *chunks,
                                 const mrp_params *params, int64_t chunks_per_batch, mrp_phase_result **out, mrp_queue_stats *stats) {
-    mrp_queue *q = nullptr;
-    int rc = mrp_queue_create(devices, n_devices, &q);
-    if (rc == MRP_OK) rc = mrp_queue_phase_chunks(q, n_chunks, chunks, params, chunks_per_batch, out, stats);
-    mrp_queue_destroy(q);
-    return rc;
+    /* (this form has no checks that come before the queue's own: mrp_queue_phase_chunks makes them) */
+    return checked_on_devices(devices, n_devices, [] { return (int) MRP_OK; },
+                              [&](mrp_queue *q) { return mrp_queue_phase_chunks(q, n_chunks, chunks, params, chunks_per_batch, out, stats); });
 }
 
 }  /* extern "C" */
+
+namespace {
+
+/* chunks as strings: a batch as one mrp_phase_string_chunks call sees it: its chunks side by side, and the host front made of them
+ * (prefetch: beside the device work of the lane's current batch; the uploads follow on the lane's own stream when the batch is run) */
+struct StringBody {
+    struct Staged : StagedBatch {
+        std::vector<mrp_string_chunk> sc;
+        std::vector<mrp_string_chunk_rest> sr;
+        mrp_string_front *front = nullptr;
+    };
+    static constexpr bool on_stage_ctx = false;
+    static constexpr const char *staged_line = "  [%7.1f] queue lane %d: front of batch %lld (%lld chunks) in %.1f ms\n";
+    static constexpr const char *not_ready = "work queue: batch has no front";
+    mrp_queue *q;
+    const mrp_string_chunk *chunks;
+    const mrp_string_chunk_rest *rest; /* NULL: without the filtered half */
+    const mrp_pair_hmm *forward_model, *reverse_model;
+    int64_t expansion, sv_threshold;
+    double het_substitution_probability;
+    const mrp_params *params;
+    int64_t min_phred;
+    mrp_phase_result **out; int8_t *const *hap_out; double *const *phred_out; mrp_profile_out *profiles_out; mrp_filtered_out *filtered_out;
+
+    int stage(int, int, Staged &st, const int64_t *order) {
+        st.sc.resize((size_t) st.count);
+        for (int64_t i = 0; i < st.count; i++) st.sc[(size_t) i] = chunks[order[i]];
+        st.sr.resize(rest ? (size_t) st.count : 0);
+        for (int64_t i = 0; rest && i < st.count; i++) st.sr[(size_t) i] = rest[order[i]];
+        return mrp_string_front_create(st.count, st.sc.data(), rest ? st.sr.data() : nullptr, forward_model, reverse_model, expansion, sv_threshold,
+                                       q->wide_pairs, &st.front);
+    }
+    int run(int w, Staged &st, const int64_t *order, QueueCall::PerLane &me, double *call_ms) {
+        const size_t count = (size_t) st.count;
+        std::vector<mrp_phase_result *> res(count, nullptr);
+        std::vector<int8_t *> hap(count);
+        std::vector<double *> phred(count);
+        std::vector<mrp_profile_out> prof(profiles_out ? count : 0); /* (zeroed, as the next) */
+        std::vector<mrp_filtered_out> fo(rest ? count : 0);
+        for (size_t i = 0; i < count; i++) {
+            hap[i] = hap_out[order[i]];
+            if (phred_out) phred[i] = phred_out[order[i]];
+        }
+        mrp_string_chunks_stats ss{};
+        const int r = mrp_string_front_run(q->ctx[(size_t) w], st.front, het_substitution_probability, params, min_phred, res.data(), hap.data(),
+                                           phred_out ? phred.data() : nullptr, profiles_out ? prof.data() : nullptr, &ss, rest ? fo.data() : nullptr, nullptr);
+        *call_ms = ss.total_ms;
+        if (r != MRP_OK) return r;
+        for (size_t i = 0; i < count; i++) {
+            out[order[i]] = res[i];
+            if (profiles_out) profiles_out[order[i]] = prof[i];
+            if (rest) filtered_out[order[i]] = fo[i];
+        }
+        count_fallback(me, ss.phase, st.count);
+        return r;
+    }
+    void print_run(double since, int w, int64_t b, double all_ms, double call_ms) const { /* (the call's own time counts its front) */
+        fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld run in %.1f ms, its front took %.1f ms\n", since, w, (long long) b, all_ms, call_ms - all_ms);
+    }
+    void drop(Staged &st) { mrp_string_front_destroy(st.front); st.front = nullptr; }
+};
+
+}  // namespace
 
 /* mrp_queue_phase_string_chunks (rest == NULL) and mrp_queue_phase_string_chunks_with_filtered: the rest travels with its chunk */
 static int queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_string_chunk *chunks, const mrp_string_chunk_rest *rest,
@@ -598,8 +545,7 @@ static int queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_s
     int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out, rest, who);
     if (rc != MRP_OK) return rc;
     if (!q) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no queue (the pair-HMM path has no CPU fallback)", rest ? who : "mrp_queue_phase_string_chunks");
-    const int n_devices = (int) q->devices.size();
-    if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = n_devices; }
+    if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = (int) q->devices.size(); }
     for (int64_t i = 0; i < n_chunks; i++) out[i] = nullptr;
     if (profiles_out) memset(profiles_out, 0, sizeof(*profiles_out) * (size_t) n_chunks);
     rc = mrp_string_chunks_check_pairs(n_chunks, chunks, expansion, sv_threshold, rest, who, q->wide_pairs);
@@ -614,97 +560,16 @@ static int queue_phase_string_chunks(mrp_queue *q, int64_t n_chunks, const mrp_s
         if (rest[i].fsub_first && chunks[i].n_bubbles > 0) cost[(size_t) i] += rest[i].fsub_first[chunks[i].n_bubbles];
         if (rest[i].n_variants > 0) cost[(size_t) i] += rest[i].ventry_first[rest[i].n_variants];
     }
-    const int lanes = q->lanes, n_workers = n_devices * lanes;
-    const QueuePlan plan = plan_queue(n_chunks, cost.data(), chunks_per_batch, n_workers, n_devices);
-    const int64_t n_batches = (int64_t) plan.batch_off.size() - 1;
-    if (stats) stats->batches = n_batches;
-    QueueCall call(q, n_batches, active_lanes_of(plan, cost.data(), n_devices, lanes));
-
-    /* a batch as one mrp_phase_string_chunks call sees it: its chunks side by side, and the host front made of them (prefetch:
-     * beside the device work of the lane's current batch; the uploads follow on the lane's own stream when the batch is run) */
-    struct Staged {
-        std::atomic<int64_t> batch{-1}; /* (the call's thread looks its batch up while the stager fills the lane's OTHER slot) */
-        int64_t first = 0, count = 0;
-        std::vector<mrp_string_chunk> sc;
-        std::vector<mrp_string_chunk_rest> sr;
-        mrp_string_front *front = nullptr;
-    };
-    std::vector<LaneSlots<Staged>> lane_state((size_t) n_workers);
-    auto staged_of = [&](int w, int64_t b) { return lane_state[(size_t) w].find(b); };
-    auto drop = [&](Staged *st) { mrp_string_front_destroy(st->front); st->front = nullptr; st->batch = -1; };
-    LaneHooks hk;
-    hk.begin = [&](int w) { return call.lane_begin(w, false); };
-    hk.prefetch = [&](int w, int64_t b) {
-        const auto t0 = std::chrono::steady_clock::now();
-        mrp_pool_adopt(q->pools[(size_t) (w / lanes)]);
-        Staged *st = lane_state[(size_t) w].next();
-        st->first = plan.batch_off[(size_t) b]; st->count = plan.batch_off[(size_t) b + 1] - st->first;
-        st->sc.resize((size_t) st->count);
-        for (int64_t i = 0; i < st->count; i++) st->sc[(size_t) i] = chunks[plan.order[(size_t) (st->first + i)]];
-        st->sr.resize(rest ? (size_t) st->count : 0);
-        for (int64_t i = 0; rest && i < st->count; i++) st->sr[(size_t) i] = rest[plan.order[(size_t) (st->first + i)]];
-        st->batch.store(b);
-        const int r = mrp_string_front_create(st->count, st->sc.data(), rest ? st->sr.data() : nullptr, forward_model, reverse_model, expansion, sv_threshold,
-                                              q->wide_pairs, &st->front);
-        if (r != MRP_OK) call.stage_errs[(size_t) w] = mrp_last_error();
-        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: front of batch %lld (%lld chunks) in %.1f ms\n", call.since(), w, (long long) b, (long long) st->count, ms_since(t0));
-        return r;
-    };
-    hk.discard = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
-    hk.phase = [&](int w, int64_t b) {
-        Staged *cur = staged_of(w, b);
-        if (!cur || !cur->front) { call.errs[(size_t) w] = "work queue: batch has no front"; return (int) MRP_ERR_ARG; }
-        const auto t0 = std::chrono::steady_clock::now();
-        const int64_t count = cur->count;
-        std::vector<mrp_phase_result *> res((size_t) count, nullptr);
-        std::vector<int8_t *> hap((size_t) count);
-        std::vector<double *> phred((size_t) count);
-        std::vector<mrp_profile_out> prof(profiles_out ? (size_t) count : 0);
-        if (profiles_out) memset(prof.data(), 0, sizeof(mrp_profile_out) * prof.size());
-        for (int64_t i = 0; i < count; i++) {
-            const int64_t chunk = plan.order[(size_t) (cur->first + i)];
-            hap[(size_t) i] = hap_out[chunk];
-            if (phred_out) phred[(size_t) i] = phred_out[chunk];
-        }
-        std::vector<mrp_filtered_out> fo(rest ? (size_t) count : 0);
-        if (rest) memset(fo.data(), 0, sizeof(mrp_filtered_out) * fo.size());
-        mrp_string_chunks_stats ss;
-        memset(&ss, 0, sizeof(ss));
-        const int r = mrp_string_front_run(q->ctx[(size_t) w], cur->front, het_substitution_probability, params, min_phred, res.data(), hap.data(),
-                                           phred_out ? phred.data() : nullptr, profiles_out ? prof.data() : nullptr, &ss, rest ? fo.data() : nullptr, nullptr);
-        QueueCall::PerLane &me = call.per[(size_t) w];
-        if (r != MRP_OK) call.errs[(size_t) w] = mrp_last_error();
-        else {
-            for (int64_t i = 0; i < count; i++) {
-                const int64_t chunk = plan.order[(size_t) (cur->first + i)];
-                out[chunk] = res[(size_t) i];
-                if (profiles_out) profiles_out[chunk] = prof[(size_t) i];
-                if (rest) filtered_out[chunk] = fo[(size_t) i];
-                me.units += cost[(size_t) chunk];
-            }
-            me.chunks += count;
-            me.fallback += ss.phase.resident ? ss.phase.fallback_chunks : count;
-        }
-        const double run_ms = ms_since(t0);
-        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld run in %.1f ms, its front took %.1f ms\n", call.since(), w, (long long) b, run_ms,
-                                 ss.total_ms - run_ms);
-        me.busy_ms += run_ms;
-        return r;
-    };
-    hk.retire = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
-    hk.end = [&](int w) { call.lane_end(w); };
-    rc = call.run(hk);
-    call.fill(stats);
-    if (rc != MRP_OK) {
+    StringBody body{q, chunks, rest, forward_model, reverse_model, expansion, sv_threshold, het_substitution_probability, params, min_phred,
+                    out, hap_out, phred_out, profiles_out, filtered_out};
+    return run_queue(q, n_chunks, cost, chunks_per_batch, stats, body, [&] {
         for (int64_t i = 0; i < n_chunks; i++) {
             mrp_phase_result_destroy(out[i]);
             out[i] = nullptr;
             if (profiles_out) mrp_profile_out_clear(&profiles_out[i]);
             if (rest) mrp_filtered_out_clear(&filtered_out[i]);
         }
-        return call.error(rc);
-    }
-    return MRP_OK;
+    });
 }
 
 extern "C" {
@@ -734,18 +599,16 @@ int mrp_phase_string_chunks_with_filtered_on_devices(const int32_t *devices, int
                                                      double het_substitution_probability, const mrp_params *params, int64_t min_phred,
                                                      int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
                                                      mrp_profile_out *profiles_out, mrp_filtered_out *filtered_out, mrp_queue_stats *stats) {
-    if (n_chunks > 0 && (!rest || !filtered_out)) return mrp_set_error(MRP_ERR_ARG, "mrp_phase_string_chunks_with_filtered_on_devices: null argument or bad sizes");
-    if (filtered_out && n_chunks > 0) memset(filtered_out, 0, sizeof(*filtered_out) * (size_t) n_chunks);
-    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out, rest, "mrp_phase_string_chunks_with_filtered_on_devices");
-    if (rc != MRP_OK) return rc;
-    mrp_queue *q = nullptr;
-    rc = mrp_queue_create(devices, n_devices, &q);
-    if (rc == MRP_OK)
-        rc = mrp_queue_phase_string_chunks_with_filtered(q, n_chunks, chunks, rest, forward_model, reverse_model, expansion, sv_threshold,
-                                                         het_substitution_probability, params, min_phred, chunks_per_batch, out, hap_out, phred_out, profiles_out,
-                                                         filtered_out, stats);
-    mrp_queue_destroy(q);
-    return rc;
+    static const char *who = "mrp_phase_string_chunks_with_filtered_on_devices";
+    return checked_on_devices(devices, n_devices, [&] {
+        if (n_chunks > 0 && (!rest || !filtered_out)) return mrp_set_error(MRP_ERR_ARG, "%s: null argument or bad sizes", who);
+        if (filtered_out && n_chunks > 0) memset(filtered_out, 0, sizeof(*filtered_out) * (size_t) n_chunks);
+        return mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out, rest, who);
+    }, [&](mrp_queue *q) {
+        return mrp_queue_phase_string_chunks_with_filtered(q, n_chunks, chunks, rest, forward_model, reverse_model, expansion, sv_threshold,
+                                                           het_substitution_probability, params, min_phred, chunks_per_batch, out, hap_out, phred_out,
+                                                           profiles_out, filtered_out, stats);
+    });
 }
 
 int mrp_phase_string_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_string_chunk *chunks,
@@ -754,39 +617,44 @@ int mrp_phase_string_chunks_on_devices(const int32_t *devices, int32_t n_devices
                                        mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
                                        mrp_queue_stats *stats) {
     /* (the queue's own order of errors: a malformed call is MRP_ERR_ARG with or without a device) */
-    int rc = mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out, nullptr, "mrp_phase_string_chunks");
-    if (rc != MRP_OK) return rc;
-    mrp_queue *q = nullptr;
-    rc = mrp_queue_create(devices, n_devices, &q);
-    if (rc == MRP_OK)
-        rc = mrp_queue_phase_string_chunks(q, n_chunks, chunks, forward_model, reverse_model, expansion, sv_threshold, het_substitution_probability, params,
-                                           min_phred, chunks_per_batch, out, hap_out, phred_out, profiles_out, stats);
-    mrp_queue_destroy(q);
-    return rc;
+    return checked_on_devices(devices, n_devices, [&] {
+        return mrp_string_chunks_check(n_chunks, chunks, forward_model, reverse_model, expansion, params, out, hap_out, phred_out, nullptr, "mrp_phase_string_chunks");
+    }, [&](mrp_queue *q) {
+        return mrp_queue_phase_string_chunks(q, n_chunks, chunks, forward_model, reverse_model, expansion, sv_threshold, het_substitution_probability, params,
+                                             min_phred, chunks_per_batch, out, hap_out, phred_out, profiles_out, stats);
+    });
 }
 
 }  /* extern "C" */
 
 /* ---- aligned chunks: mrp_queue_phase_aligned_chunks (rest == NULL), mrp_queue_phase_aligned_chunks_with_filtered and
  * mrp_queue_phase_aligned_chunks_with_records (records_out beside filtered_out) -------------------------------------------------------- */
-extern "C" int mrp_aligned_chunk_units(const mrp_aligned_chunk *chunk, const mrp_aligned_chunk_rest *rest, int64_t *units_out) {
-    static const char *who = "mrp_aligned_chunk_units";
+/* The (read, site) substrings uniform coverage gives a chunk: its bases x sites() / the length of its overlap, at most INT64_MAX
+ * (B < 2^62 and the sites < 2^64: the product fits 128 bits).  The checks in the order of both entries: `negative_too` and
+ * `no_genotypes` are what the entry's own second argument adds to them.  An error leaves *units_out alone. */
+template <typename Sites>
+static int aligned_units(const char *who, const mrp_aligned_chunk *chunk, int64_t *units_out, bool negative_too, bool no_genotypes, Sites sites) {
     if (!chunk || !units_out) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
     const mrp_aligned_chunk &C = *chunk;
-    if (C.n_reads < 0 || C.n_variants < 0 || (rest && rest->n_variants < 0)) return mrp_set_error(MRP_ERR_ARG, "%s: negative count", who);
+    if (C.n_reads < 0 || C.n_variants < 0 || negative_too) return mrp_set_error(MRP_ERR_ARG, "%s: negative count", who);
     if (C.overlap_end < C.overlap_start) return mrp_set_error(MRP_ERR_ARG, "%s: overlap_end before overlap_start", who);
     if (C.n_reads > 0 && !C.l_qseq) return mrp_set_error(MRP_ERR_ARG, "%s: null l_qseq", who);
+    if (C.n_variants > 0 && no_genotypes) return mrp_set_error(MRP_ERR_ARG, "%s: null genotypes", who);
     unsigned __int128 bases = 0;
     for (int64_t r = 0; r < C.n_reads; r++) {
         if (C.l_qseq[r] < 0) return mrp_set_error(MRP_ERR_ARG, "%s: read %lld: negative l_qseq", who, (long long) r);
         bases += (unsigned __int128) C.l_qseq[r];
     }
-    /* (B < 2^62 and V < 2^64: the product fits 128 bits) */
-    const unsigned __int128 variants = (unsigned __int128) C.n_variants + (unsigned __int128) (rest ? rest->n_variants : 0);
     const unsigned __int128 length = (unsigned __int128) std::max<int64_t>(1, C.overlap_end - C.overlap_start);
-    const unsigned __int128 units = bases * variants / length;
+    const unsigned __int128 units = bases * (unsigned __int128) sites(C) / length;
     *units_out = units > (unsigned __int128) INT64_MAX ? INT64_MAX : (int64_t) units;
     return MRP_OK;
+}
+
+extern "C" int mrp_aligned_chunk_units(const mrp_aligned_chunk *chunk, const mrp_aligned_chunk_rest *rest, int64_t *units_out) {
+    return aligned_units("mrp_aligned_chunk_units", chunk, units_out, rest && rest->n_variants < 0, false, [&](const mrp_aligned_chunk &C) {
+        return (unsigned __int128) C.n_variants + (unsigned __int128) (rest ? rest->n_variants : 0);
+    });
 }
 
 namespace {
@@ -810,45 +678,21 @@ int aligned_queue_check(const AlignedQueueArgs &A, bool with_rest) {
     return mrp_aligned_chunks_check(A.who, &a);
 }
 
-int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool with_rest, bool checked = false) {
-    const char *who = A.who;
-    const mrp_aligned_args &a = A.a;
-    const int64_t n_chunks = a.n_chunks;
-    const mrp_aligned_chunk_rest *rest = with_rest ? a.rest : nullptr;
-    mrp_queue_stats *stats = A.stats;
-    const bool records = with_rest && A.with_records;
-    int rc = checked ? (int) MRP_OK : aligned_queue_check(A, with_rest);
-    if (rc != MRP_OK) return rc;
-    if (!q) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no queue (the extraction and the pair-HMM have no CPU fallback)", who);
-    const int n_devices = (int) q->devices.size();
-    if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = n_devices; }
-    for (int64_t i = 0; i < n_chunks; i++) {
-        a.out[i] = nullptr;
-        if (a.bubble_variant_out) a.bubble_variant_out[i] = nullptr;
-        if (rest) a.filtered_read_out[i] = nullptr;
-    }
-    if (a.profiles_out && n_chunks > 0) memset(a.profiles_out, 0, sizeof(*a.profiles_out) * (size_t) n_chunks);
-    if (rest && n_chunks > 0) memset(a.filtered_out, 0, sizeof(*a.filtered_out) * (size_t) n_chunks);
-    if (records && n_chunks > 0) memset(a.records_out, 0, sizeof(*a.records_out) * (size_t) n_chunks);
-    if (records && A.records_stats) memset(A.records_stats, 0, sizeof(*A.records_stats));
-    if (n_chunks == 0) return MRP_OK;
-    /* phase.c:257-263 orders by estimated depth; here by the (read, variant) substrings uniform coverage gives a chunk (a read the
-     * extraction does not walk, l_qseq <= 0, passes its checks: such a chunk is ordered as if it cost nothing) */
-    std::vector<int64_t> cost((size_t) n_chunks, 0);
-    for (int64_t i = 0; i < n_chunks; i++)
-        if (mrp_aligned_chunk_units(&a.chunks[i], rest ? &rest[i] : nullptr, &cost[(size_t) i]) != MRP_OK) cost[(size_t) i] = 0;
-    const int lanes = q->lanes, n_workers = n_devices * lanes;
-    const QueuePlan plan = plan_queue(n_chunks, cost.data(), A.chunks_per_batch, n_workers, n_devices);
-    const int64_t n_batches = (int64_t) plan.batch_off.size() - 1;
-    if (stats) stats->batches = n_batches;
-    QueueCall call(q, n_batches, active_lanes_of(plan, cost.data(), n_devices, lanes));
+/* (a batch's share of the records' stats to a lane's, the lanes' to the call's) */
+template <typename Stats>
+void add_records_stats(mrp_queue_records_stats &to, const Stats &b) {
+    to.records_sites += b.records_sites;
+    to.records_updated += b.records_updated;
+    to.reads_listed += b.reads_listed;
+    to.records_bytes_downloaded += b.records_bytes_downloaded;
+    to.records_ms += b.records_ms;
+}
 
-    /* a batch as one mrp_phase_aligned_chunks(_with_filtered) call sees it: its chunks in plan order with what travels with them, the
-     * call's outputs, and the front -- its host part (the extraction's records, the chunks' checks and windows) made by the prefetch
-     * beside the lane's current batch, its device part staged on the lane's context when the batch is run */
-    struct Staged {
-        std::atomic<int64_t> batch{-1}; /* (the call's thread looks its batch up while the stager fills the lane's OTHER slot) */
-        int64_t first = 0, count = 0;
+/* aligned chunks to be phased: a batch as one mrp_phase_aligned_chunks(_with_filtered) call sees it: its chunks in plan order with what
+ * travels with them, the call's outputs, and the front -- its host part (the extraction's records, the chunks' checks and windows) made
+ * by the prefetch beside the lane's current batch, its device part staged on the lane's context when the batch is run */
+struct AlignedBody {
+    struct Staged : StagedBatch {
         std::vector<mrp_aligned_chunk> ch;
         std::vector<mrp_aligned_chunk_rest> rs;
         std::vector<const char *const *> names;
@@ -864,117 +708,107 @@ int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool wit
         std::vector<mrp_phase_aligned_records_stats> rst;    /* ... and, in one entry, its share of the records' stats */
         mrp_aligned_front *front = nullptr;
     };
-    std::vector<LaneSlots<Staged>> lane_state((size_t) n_workers);
-    std::vector<mrp_queue_records_stats> rec_per((size_t) n_workers); /* what each lane's batches added to the records' stats */
-    memset(rec_per.data(), 0, sizeof(mrp_queue_records_stats) * rec_per.size());
-    auto staged_of = [&](int w, int64_t b) { return lane_state[(size_t) w].find(b); };
-    /* (a staged front holds arrays of the lane's context: it goes with no other thread of the lane at work, on the lane's thread) */
-    auto drop = [&](Staged *st) { mrp_aligned_front_destroy(st->front); st->front = nullptr; st->batch = -1; };
-    LaneHooks hk;
-    hk.begin = [&](int w) { return call.lane_begin(w, false); };
-    hk.prefetch = [&](int w, int64_t b) { /* host only: never the lane's context, its stream, its events or its pool */
-        const auto t0 = std::chrono::steady_clock::now();
-        mrp_pool_adopt(q->pools[(size_t) (w / lanes)]);
-        Staged *st = lane_state[(size_t) w].next();
-        st->first = plan.batch_off[(size_t) b]; st->count = plan.batch_off[(size_t) b + 1] - st->first;
-        const size_t count = (size_t) st->count;
-        st->ch.resize(count); st->names.resize(count); st->hap.resize(count);
-        st->rs.resize(rest ? count : 0);
-        st->keep.resize(a.keep ? count : 0);
-        st->phred.resize(a.phred_out ? count : 0);
-        st->res.assign(count, nullptr);
-        st->bv.assign(a.bubble_variant_out ? count : 0, nullptr);
-        st->fr.assign(rest ? count : 0, nullptr);
-        st->prof.resize(a.profiles_out ? count : 0);
-        st->fo.resize(rest ? count : 0);
-        if (a.profiles_out) memset(st->prof.data(), 0, sizeof(mrp_profile_out) * count);
-        if (rest) memset(st->fo.data(), 0, sizeof(mrp_filtered_out) * count);
-        st->rec.resize(records ? count : 0);
-        st->rst.resize(records ? 1 : 0);
-        if (records) {
-            memset(st->rec.data(), 0, sizeof(mrp_variant_records) * count);
-            memset(st->rst.data(), 0, sizeof(mrp_phase_aligned_records_stats));
-        }
+    static constexpr bool on_stage_ctx = false;
+    static constexpr const char *staged_line = "  [%7.1f] queue lane %d: checks and windows of batch %lld (%lld chunks) in %.1f ms\n";
+    static constexpr const char *not_ready = "work queue: batch has no front";
+    mrp_queue *q;
+    const char *who;
+    const mrp_aligned_args &a;
+    const mrp_aligned_chunk_rest *rest; /* NULL: without the filtered half */
+    bool records;
+    std::vector<mrp_queue_records_stats> rec_per; /* [lane] what each lane's batches added to the records' stats */
+
+    int stage(int, int, Staged &st, const int64_t *order) { /* host only: never the lane's context, its stream, its events or its pool */
+        const double t_begin = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+        const size_t count = (size_t) st.count;
+        const size_t n_rest = rest ? count : 0; /* (every array the call gets is as long as the batch or empty, its outputs zeroed) */
+        st.ch.resize(count); st.names.resize(count); st.hap.resize(count); st.res.assign(count, nullptr);
+        st.rs.resize(n_rest); st.fo.assign(n_rest, mrp_filtered_out{}); st.fr.assign(n_rest, nullptr);
+        st.keep.resize(a.keep ? count : 0); st.phred.resize(a.phred_out ? count : 0);
+        st.prof.assign(a.profiles_out ? count : 0, mrp_profile_out{}); st.bv.assign(a.bubble_variant_out ? count : 0, nullptr);
+        st.rec.assign(records ? count : 0, mrp_variant_records{}); st.rst.assign(records ? 1 : 0, mrp_phase_aligned_records_stats{});
         for (size_t i = 0; i < count; i++) {
-            const int64_t chunk = plan.order[(size_t) st->first + i];
-            st->ch[i] = a.chunks[chunk];
-            st->names[i] = a.read_names[chunk];
-            st->hap[i] = a.hap_out[chunk];
-            if (rest) st->rs[i] = rest[chunk];
-            if (a.keep) st->keep[i] = a.keep[chunk];
-            if (a.phred_out) st->phred[i] = a.phred_out[chunk];
+            const int64_t chunk = order[i];
+            st.ch[i] = a.chunks[chunk];
+            st.names[i] = a.read_names[chunk];
+            st.hap[i] = a.hap_out[chunk];
+            if (rest) st.rs[i] = rest[chunk];
+            if (a.keep) st.keep[i] = a.keep[chunk];
+            if (a.phred_out) st.phred[i] = a.phred_out[chunk];
         }
-        st->batch.store(b);
         mrp_aligned_args ba = a;
-        ba.n_chunks = st->count;
-        ba.chunks = st->ch.data();
-        ba.rest = rest ? st->rs.data() : nullptr;
-        ba.read_names = st->names.data();
-        ba.keep = a.keep ? st->keep.data() : nullptr;
-        ba.out = st->res.data();
-        ba.hap_out = st->hap.data();
-        ba.phred_out = a.phred_out ? st->phred.data() : nullptr;
-        ba.profiles_out = a.profiles_out ? st->prof.data() : nullptr;
-        ba.bubble_variant_out = a.bubble_variant_out ? st->bv.data() : nullptr;
-        ba.filtered_out = rest ? st->fo.data() : nullptr;
-        ba.filtered_read_out = rest ? st->fr.data() : nullptr;
-        ba.records_out = records ? st->rec.data() : nullptr;
-        ba.records_stats = records ? st->rst.data() : nullptr;
-        const double t_begin = std::chrono::duration<double, std::milli>(t0.time_since_epoch()).count();
-        const int r = mrp_aligned_front_create(who, t_begin, &ba, nullptr, nullptr, &st->front);
-        if (r != MRP_OK) call.stage_errs[(size_t) w] = mrp_last_error();
-        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: checks and windows of batch %lld (%lld chunks) in %.1f ms\n", call.since(), w, (long long) b,
-                                 (long long) st->count, ms_since(t0));
-        return r;
-    };
-    hk.discard = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
-    hk.phase = [&](int w, int64_t b) {
-        Staged *cur = staged_of(w, b);
-        if (!cur || !cur->front) { call.errs[(size_t) w] = "work queue: batch has no front"; return (int) MRP_ERR_ARG; }
+        ba.n_chunks = st.count;
+        ba.chunks = st.ch.data();
+        ba.rest = rest ? st.rs.data() : nullptr;
+        ba.read_names = st.names.data();
+        ba.keep = a.keep ? st.keep.data() : nullptr;
+        ba.out = st.res.data();
+        ba.hap_out = st.hap.data();
+        ba.phred_out = a.phred_out ? st.phred.data() : nullptr;
+        ba.profiles_out = a.profiles_out ? st.prof.data() : nullptr;
+        ba.bubble_variant_out = a.bubble_variant_out ? st.bv.data() : nullptr;
+        ba.filtered_out = rest ? st.fo.data() : nullptr;
+        ba.filtered_read_out = rest ? st.fr.data() : nullptr;
+        ba.records_out = records ? st.rec.data() : nullptr;
+        ba.records_stats = records ? st.rst.data() : nullptr;
+        return mrp_aligned_front_create(who, t_begin, &ba, nullptr, nullptr, &st.front);
+    }
+    int run(int w, Staged &st, const int64_t *order, QueueCall::PerLane &me, double *front_ms) {
         const auto t0 = std::chrono::steady_clock::now();
-        const int64_t count = cur->count;
-        mrp_string_chunks_stats ss;
-        memset(&ss, 0, sizeof(ss));
-        int r = mrp_aligned_front_stage(q->ctx[(size_t) w], cur->front);
-        const double front_ms = ms_since(t0);
-        if (r == MRP_OK) r = mrp_aligned_front_run(cur->front, &ss);
-        QueueCall::PerLane &me = call.per[(size_t) w];
+        mrp_string_chunks_stats ss{};
+        int r = mrp_aligned_front_stage(q->ctx[(size_t) w], st.front);
+        *front_ms = ms_since(t0);
+        if (r == MRP_OK) r = mrp_aligned_front_run(st.front, &ss);
         if (r != MRP_OK) {
-            call.errs[(size_t) w] = mrp_last_error();
-            for (mrp_variant_records &R : cur->rec) mrp_variant_records_clear(&R); /* (a batch that failed behind its records hands none over) */
-        } else {
-            if (records) {
-                mrp_queue_records_stats &mine = rec_per[(size_t) w];
-                const mrp_phase_aligned_records_stats &b = cur->rst[0];
-                mine.records_sites += b.records_sites;
-                mine.records_updated += b.records_updated;
-                mine.reads_listed += b.reads_listed;
-                mine.records_bytes_downloaded += b.records_bytes_downloaded;
-                mine.records_ms += b.records_ms;
-            }
-            for (int64_t i = 0; i < count; i++) {
-                const int64_t chunk = plan.order[(size_t) (cur->first + i)];
-                a.out[chunk] = cur->res[(size_t) i];
-                if (records) { a.records_out[chunk] = cur->rec[(size_t) i]; memset(&cur->rec[(size_t) i], 0, sizeof(mrp_variant_records)); }
-                if (a.profiles_out) a.profiles_out[chunk] = cur->prof[(size_t) i];
-                if (a.bubble_variant_out) a.bubble_variant_out[chunk] = cur->bv[(size_t) i];
-                if (rest) { a.filtered_out[chunk] = cur->fo[(size_t) i]; a.filtered_read_out[chunk] = cur->fr[(size_t) i]; }
-                me.units += cost[(size_t) chunk];
-            }
-            me.chunks += count;
-            me.fallback += ss.phase.resident ? ss.phase.fallback_chunks : count;
+            for (mrp_variant_records &R : st.rec) mrp_variant_records_clear(&R); /* (a batch that failed behind its records hands none over) */
+            return r;
         }
-        const double all_ms = ms_since(t0);
-        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld: device front in %.1f ms, run in %.1f ms\n", call.since(), w, (long long) b, front_ms,
-                                 all_ms - front_ms);
-        me.busy_ms += all_ms;
+        if (records) add_records_stats(rec_per[(size_t) w], st.rst[0]);
+        for (size_t i = 0; i < (size_t) st.count; i++) {
+            const int64_t chunk = order[i];
+            a.out[chunk] = st.res[i];
+            if (records) { a.records_out[chunk] = st.rec[i]; memset(&st.rec[i], 0, sizeof(mrp_variant_records)); }
+            if (a.profiles_out) a.profiles_out[chunk] = st.prof[i];
+            if (a.bubble_variant_out) a.bubble_variant_out[chunk] = st.bv[i];
+            if (rest) { a.filtered_out[chunk] = st.fo[i]; a.filtered_read_out[chunk] = st.fr[i]; }
+        }
+        count_fallback(me, ss.phase, st.count);
         return r;
-    };
-    hk.retire = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
-    hk.end = [&](int w) { call.lane_end(w); };
-    rc = call.run(hk);
-    call.fill(stats);
-    if (rc != MRP_OK) {
+    }
+    void print_run(double since, int w, int64_t b, double all_ms, double front_ms) const {
+        fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld: device front in %.1f ms, run in %.1f ms\n", since, w, (long long) b, front_ms, all_ms - front_ms);
+    }
+    void drop(Staged &st) { mrp_aligned_front_destroy(st.front); st.front = nullptr; }
+};
+
+int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool with_rest, bool checked = false) {
+    const char *who = A.who;
+    const mrp_aligned_args &a = A.a;
+    const int64_t n_chunks = a.n_chunks;
+    const mrp_aligned_chunk_rest *rest = with_rest ? a.rest : nullptr;
+    mrp_queue_stats *stats = A.stats;
+    const bool records = with_rest && A.with_records;
+    int rc = checked ? (int) MRP_OK : aligned_queue_check(A, with_rest);
+    if (rc != MRP_OK) return rc;
+    if (!q) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no queue (the extraction and the pair-HMM have no CPU fallback)", who);
+    if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = (int) q->devices.size(); }
+    for (int64_t i = 0; i < n_chunks; i++) {
+        a.out[i] = nullptr;
+        if (a.bubble_variant_out) a.bubble_variant_out[i] = nullptr;
+        if (rest) a.filtered_read_out[i] = nullptr;
+    }
+    if (a.profiles_out && n_chunks > 0) memset(a.profiles_out, 0, sizeof(*a.profiles_out) * (size_t) n_chunks);
+    if (rest && n_chunks > 0) memset(a.filtered_out, 0, sizeof(*a.filtered_out) * (size_t) n_chunks);
+    if (records && n_chunks > 0) memset(a.records_out, 0, sizeof(*a.records_out) * (size_t) n_chunks);
+    if (records && A.records_stats) memset(A.records_stats, 0, sizeof(*A.records_stats));
+    if (n_chunks == 0) return MRP_OK;
+    /* phase.c:257-263 orders by estimated depth; here by the (read, variant) substrings uniform coverage gives a chunk (a read the
+     * extraction does not walk, l_qseq <= 0, passes its checks: such a chunk is ordered as if it cost nothing) */
+    std::vector<int64_t> cost((size_t) n_chunks, 0);
+    for (int64_t i = 0; i < n_chunks; i++)
+        if (mrp_aligned_chunk_units(&a.chunks[i], rest ? &rest[i] : nullptr, &cost[(size_t) i]) != MRP_OK) cost[(size_t) i] = 0;
+    AlignedBody body{q, who, a, rest, records, std::vector<mrp_queue_records_stats>(q->ctx.size(), mrp_queue_records_stats{})};
+    rc = run_queue(q, n_chunks, cost, A.chunks_per_batch, stats, body, [&] {
         for (int64_t i = 0; i < n_chunks; i++) {
             mrp_phase_result_destroy(a.out[i]);
             a.out[i] = nullptr;
@@ -987,23 +821,32 @@ int queue_phase_aligned_chunks(mrp_queue *q, const AlignedQueueArgs &A, bool wit
             }
             if (records) mrp_variant_records_clear(&a.records_out[i]);
         }
-        return call.error(rc);
-    }
-    if (records && A.records_stats)
-        for (const mrp_queue_records_stats &b : rec_per) { /* in lane order: the sum of records_ms does not depend on which lane finished first */
-            A.records_stats->records_sites += b.records_sites;
-            A.records_stats->records_updated += b.records_updated;
-            A.records_stats->reads_listed += b.reads_listed;
-            A.records_stats->records_bytes_downloaded += b.records_bytes_downloaded;
-            A.records_stats->records_ms += b.records_ms;
-        }
-    return MRP_OK;
+    });
+    if (rc == MRP_OK && records && A.records_stats) /* in lane order: the sum of records_ms does not depend on which lane finished first */
+        for (const mrp_queue_records_stats &b : body.rec_per) add_records_stats(*A.records_stats, b);
+    return rc;
 }
 
 /* create + call + destroy, with the queue's own order of errors: a malformed call and a refused mode need no device */
 int aligned_on_devices(const int32_t *devices, int32_t n_devices, const AlignedQueueArgs &A, bool with_rest) {
     return checked_on_devices(devices, n_devices, [&] { return aligned_queue_check(A, with_rest); },
                               [&](mrp_queue *q) { return queue_phase_aligned_chunks(q, A, with_rest, true); });
+}
+
+/* The arguments of the longest entry (with records); a shorter one passes NULL for what it has not.  q: the queue whose settings the
+ * up-front checks read -- NULL (no queue, or none yet: *_on_devices) counts as all off, which is what a new queue has. */
+AlignedQueueArgs aligned_queue_args(const char *who, const mrp_queue *q, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
+                                    const char *const *const *read_names, const uint8_t *const *keep, const mrp_extract_options *options,
+                                    const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold,
+                                    double het_substitution_probability, const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch,
+                                    mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
+                                    int64_t **bubble_variant_out, mrp_filtered_out *filtered_out, int32_t **filtered_read_out, mrp_queue_stats *stats,
+                                    bool with_records = false, mrp_variant_records *records_out = nullptr, mrp_queue_records_stats *records_stats = nullptr) {
+    return {who,
+            {n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold, het_substitution_probability, params,
+             min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out, filtered_read_out, q ? q->sv_split : 0, records_out,
+             /* records_stats: a batch's own */ nullptr, q ? q->max_depth : 0, q ? q->downsampling_seed : 0},
+            chunks_per_batch, stats, with_records, records_stats};
 }
 
 }  // namespace
@@ -1015,12 +858,9 @@ int mrp_queue_phase_aligned_chunks(mrp_queue *q, int64_t n_chunks, const mrp_ali
                                    const mrp_pair_hmm *reverse_model, int64_t expansion, int64_t sv_threshold, double het_substitution_probability,
                                    const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out,
                                    double *const *phred_out, mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_queue_stats *stats) {
-    const AlignedQueueArgs A{"mrp_queue_phase_aligned_chunks",
-                             {n_chunks, chunks, nullptr, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
-                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr,
-                              q ? q->sv_split : 0, nullptr, nullptr, q ? q->max_depth : 0, q ? q->downsampling_seed : 0}, /* (a NULL queue counts as off) */
-                             chunks_per_batch, stats};
-    return queue_phase_aligned_chunks(q, A, false);
+    return queue_phase_aligned_chunks(q, aligned_queue_args("mrp_queue_phase_aligned_chunks", q, n_chunks, chunks, nullptr, read_names, keep, options, forward_model,
+                                                            reverse_model, expansion, sv_threshold, het_substitution_probability, params, min_phred, chunks_per_batch,
+                                                            out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr, stats), false);
 }
 
 int mrp_queue_phase_aligned_chunks_with_filtered(mrp_queue *q, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
@@ -1030,12 +870,10 @@ int mrp_queue_phase_aligned_chunks_with_filtered(mrp_queue *q, int64_t n_chunks,
                                                  int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
                                                  mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
                                                  int32_t **filtered_read_out, mrp_queue_stats *stats) {
-    const AlignedQueueArgs A{"mrp_queue_phase_aligned_chunks_with_filtered",
-                             {n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
-                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
-                              filtered_read_out, q ? q->sv_split : 0, nullptr, nullptr, q ? q->max_depth : 0, q ? q->downsampling_seed : 0},
-                             chunks_per_batch, stats};
-    return queue_phase_aligned_chunks(q, A, true);
+    return queue_phase_aligned_chunks(q, aligned_queue_args("mrp_queue_phase_aligned_chunks_with_filtered", q, n_chunks, chunks, rest, read_names, keep, options,
+                                                            forward_model, reverse_model, expansion, sv_threshold, het_substitution_probability, params, min_phred,
+                                                            chunks_per_batch, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
+                                                            filtered_read_out, stats), true);
 }
 
 int mrp_queue_phase_aligned_chunks_with_records(mrp_queue *q, int64_t n_chunks, const mrp_aligned_chunk *chunks, const mrp_aligned_chunk_rest *rest,
@@ -1046,12 +884,10 @@ int mrp_queue_phase_aligned_chunks_with_records(mrp_queue *q, int64_t n_chunks, 
                                                 mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
                                                 int32_t **filtered_read_out, mrp_variant_records *records_out, mrp_queue_stats *stats,
                                                 mrp_queue_records_stats *records_stats) {
-    const AlignedQueueArgs A{"mrp_queue_phase_aligned_chunks_with_records",
-                             {n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
-                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
-                              filtered_read_out, q ? q->sv_split : 0, records_out, nullptr, q ? q->max_depth : 0, q ? q->downsampling_seed : 0},
-                             chunks_per_batch, stats, true, records_stats};
-    return queue_phase_aligned_chunks(q, A, true);
+    return queue_phase_aligned_chunks(q, aligned_queue_args("mrp_queue_phase_aligned_chunks_with_records", q, n_chunks, chunks, rest, read_names, keep, options,
+                                                            forward_model, reverse_model, expansion, sv_threshold, het_substitution_probability, params, min_phred,
+                                                            chunks_per_batch, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
+                                                            filtered_read_out, stats, true, records_out, records_stats), true);
 }
 
 int mrp_phase_aligned_chunks_with_records_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,
@@ -1063,12 +899,11 @@ int mrp_phase_aligned_chunks_with_records_on_devices(const int32_t *devices, int
                                                      mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
                                                      int32_t **filtered_read_out, mrp_variant_records *records_out, mrp_queue_stats *stats,
                                                      mrp_queue_records_stats *records_stats) {
-    const AlignedQueueArgs A{"mrp_phase_aligned_chunks_with_records_on_devices",
-                             {n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
-                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
-                              filtered_read_out, 0, records_out},
-                             chunks_per_batch, stats, true, records_stats};
-    return aligned_on_devices(devices, n_devices, A, true);
+    return aligned_on_devices(devices, n_devices, aligned_queue_args("mrp_phase_aligned_chunks_with_records_on_devices", nullptr, n_chunks, chunks, rest, read_names,
+                                                                     keep, options, forward_model, reverse_model, expansion, sv_threshold,
+                                                                     het_substitution_probability, params, min_phred, chunks_per_batch, out, hap_out, phred_out,
+                                                                     profiles_out, bubble_variant_out, filtered_out, filtered_read_out, stats, true, records_out,
+                                                                     records_stats), true);
 }
 
 int mrp_phase_aligned_chunks_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,
@@ -1077,11 +912,10 @@ int mrp_phase_aligned_chunks_on_devices(const int32_t *devices, int32_t n_device
                                         double het_substitution_probability, const mrp_params *params, int64_t min_phred, int64_t chunks_per_batch,
                                         mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out, mrp_profile_out *profiles_out,
                                         int64_t **bubble_variant_out, mrp_queue_stats *stats) {
-    const AlignedQueueArgs A{"mrp_phase_aligned_chunks_on_devices",
-                             {n_chunks, chunks, nullptr, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
-                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr, nullptr},
-                             chunks_per_batch, stats};
-    return aligned_on_devices(devices, n_devices, A, false);
+    return aligned_on_devices(devices, n_devices, aligned_queue_args("mrp_phase_aligned_chunks_on_devices", nullptr, n_chunks, chunks, nullptr, read_names, keep, options,
+                                                                     forward_model, reverse_model, expansion, sv_threshold, het_substitution_probability, params,
+                                                                     min_phred, chunks_per_batch, out, hap_out, phred_out, profiles_out, bubble_variant_out, nullptr,
+                                                                     nullptr, stats), false);
 }
 
 int mrp_phase_aligned_chunks_with_filtered_on_devices(const int32_t *devices, int32_t n_devices, int64_t n_chunks, const mrp_aligned_chunk *chunks,
@@ -1092,38 +926,22 @@ int mrp_phase_aligned_chunks_with_filtered_on_devices(const int32_t *devices, in
                                                       int64_t chunks_per_batch, mrp_phase_result **out, int8_t *const *hap_out, double *const *phred_out,
                                                       mrp_profile_out *profiles_out, int64_t **bubble_variant_out, mrp_filtered_out *filtered_out,
                                                       int32_t **filtered_read_out, mrp_queue_stats *stats) {
-    const AlignedQueueArgs A{"mrp_phase_aligned_chunks_with_filtered_on_devices",
-                             {n_chunks, chunks, rest, read_names, keep, options, forward_model, reverse_model, expansion, sv_threshold,
-                              het_substitution_probability, params, min_phred, out, hap_out, phred_out, profiles_out, bubble_variant_out, filtered_out,
-                              filtered_read_out},
-                             chunks_per_batch, stats};
-    return aligned_on_devices(devices, n_devices, A, true);
+    return aligned_on_devices(devices, n_devices, aligned_queue_args("mrp_phase_aligned_chunks_with_filtered_on_devices", nullptr, n_chunks, chunks, rest, read_names,
+                                                                     keep, options, forward_model, reverse_model, expansion, sv_threshold,
+                                                                     het_substitution_probability, params, min_phred, chunks_per_batch, out, hap_out, phred_out,
+                                                                     profiles_out, bubble_variant_out, filtered_out, filtered_read_out, stats), true);
 }
 
 }  /* extern "C" */
 
 /* ---- haplotagging aligned chunks from a phased VCF: mrp_queue_haplotag_aligned_chunks ------------------------------------------------ */
 extern "C" int mrp_haplotag_chunk_units(const mrp_aligned_chunk *chunk, const int32_t *gt, int64_t *units_out) {
-    static const char *who = "mrp_haplotag_chunk_units";
-    if (!chunk || !units_out) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
-    const mrp_aligned_chunk &C = *chunk;
-    if (C.n_reads < 0 || C.n_variants < 0) return mrp_set_error(MRP_ERR_ARG, "%s: negative count", who);
-    if (C.overlap_end < C.overlap_start) return mrp_set_error(MRP_ERR_ARG, "%s: overlap_end before overlap_start", who);
-    if (C.n_reads > 0 && !C.l_qseq) return mrp_set_error(MRP_ERR_ARG, "%s: null l_qseq", who);
-    if (C.n_variants > 0 && !gt) return mrp_set_error(MRP_ERR_ARG, "%s: null genotypes", who);
-    unsigned __int128 bases = 0;
-    for (int64_t r = 0; r < C.n_reads; r++) {
-        if (C.l_qseq[r] < 0) return mrp_set_error(MRP_ERR_ARG, "%s: read %lld: negative l_qseq", who, (long long) r);
-        bases += (unsigned __int128) C.l_qseq[r];
-    }
     /* only a heterozygous variant is scored (bubbleGraph.c:1975): the chunk's pair-HMM work, not its variant count */
-    unsigned __int128 het = 0;
-    for (int64_t v = 0; v < C.n_variants; v++) het += gt[2 * v] != gt[2 * v + 1];
-    /* (B < 2^62 and H < 2^63: the product fits 128 bits) */
-    const unsigned __int128 length = (unsigned __int128) std::max<int64_t>(1, C.overlap_end - C.overlap_start);
-    const unsigned __int128 units = bases * het / length;
-    *units_out = units > (unsigned __int128) INT64_MAX ? INT64_MAX : (int64_t) units;
-    return MRP_OK;
+    return aligned_units("mrp_haplotag_chunk_units", chunk, units_out, false, !gt, [&](const mrp_aligned_chunk &C) {
+        unsigned __int128 het = 0;
+        for (int64_t v = 0; v < C.n_variants; v++) het += gt[2 * v] != gt[2 * v + 1];
+        return het;
+    });
 }
 
 namespace {
@@ -1132,6 +950,59 @@ struct HaplotagQueueArgs {
     mrp_haplotag_args a;
     int64_t chunks_per_batch;
     mrp_queue_stats *stats;
+};
+
+/* aligned chunks to be haplotagged: a batch as one mrp_haplotag_aligned_chunks call sees it: its chunks in plan order with their
+ * genotypes and output arrays, and the front -- its host part (the extraction's records, the checks, the windows) made by the prefetch
+ * beside the lane's current batch, its device part staged on the lane's context when the batch is run */
+struct HaplotagBody {
+    struct Staged : StagedBatch {
+        std::vector<mrp_aligned_chunk> ch;
+        std::vector<const int32_t *> gt;
+        std::vector<int8_t *> hap;
+        std::vector<double *> h1, h2;
+        mrp_haplotag_front *front = nullptr;
+    };
+    static constexpr bool on_stage_ctx = false;
+    static constexpr const char *staged_line = "  [%7.1f] queue lane %d: checks and windows of batch %lld (%lld chunks) in %.1f ms\n";
+    static constexpr const char *not_ready = "work queue: batch has no front";
+    mrp_queue *q;
+    const mrp_haplotag_args &a;
+
+    int stage(int, int, Staged &st, const int64_t *order) { /* host only: never the lane's context, its stream, its events or its pool */
+        const size_t count = (size_t) st.count;
+        st.ch.resize(count); st.gt.resize(count); st.hap.resize(count);
+        st.h1.resize(a.h1_out ? count : 0);
+        st.h2.resize(a.h2_out ? count : 0);
+        for (size_t i = 0; i < count; i++) {
+            const int64_t chunk = order[i];
+            st.ch[i] = a.chunks[chunk];
+            st.gt[i] = a.gt[chunk];
+            st.hap[i] = a.hap_out[chunk];
+            if (a.h1_out) st.h1[i] = a.h1_out[chunk];
+            if (a.h2_out) st.h2[i] = a.h2_out[chunk];
+        }
+        mrp_haplotag_args ba = a;
+        ba.n_chunks = st.count;
+        ba.chunks = st.ch.data();
+        ba.gt = st.gt.data();
+        ba.hap_out = st.hap.data();
+        ba.h1_out = a.h1_out ? st.h1.data() : nullptr;
+        ba.h2_out = a.h2_out ? st.h2.data() : nullptr;
+        return mrp_haplotag_front_create(&ba, nullptr, &st.front);
+    }
+    int run(int w, Staged &st, const int64_t *, QueueCall::PerLane &, double *front_ms) { /* (no fallback to count: nothing is phased) */
+        const auto t0 = std::chrono::steady_clock::now();
+        int r = mrp_haplotag_front_stage(q->ctx[(size_t) w], st.front);
+        *front_ms = ms_since(t0);
+        if (r == MRP_OK) r = mrp_haplotag_front_run(st.front); /* (writes the batch's outputs at the chunks' own arrays) */
+        return r;
+    }
+    void print_run(double since, int w, int64_t b, double all_ms, double front_ms) const {
+        fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld: extraction and owners in %.1f ms, pairs and scoring in %.1f ms\n", since, w, (long long) b,
+                front_ms, all_ms - front_ms);
+    }
+    void drop(Staged &st) { mrp_haplotag_front_destroy(st.front); st.front = nullptr; }
 };
 
 int queue_haplotag_aligned_chunks(mrp_queue *q, const HaplotagQueueArgs &A, bool checked = false) {
@@ -1143,93 +1014,14 @@ int queue_haplotag_aligned_chunks(mrp_queue *q, const HaplotagQueueArgs &A, bool
     int rc = checked ? (int) MRP_OK : mrp_haplotag_chunks_check(&a);
     if (rc != MRP_OK) return rc;
     if (!q) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no queue (the extraction and the pair-HMM have no CPU fallback)", who);
-    const int n_devices = (int) q->devices.size();
-    if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = n_devices; }
+    if (stats) { memset(stats, 0, sizeof(*stats)); stats->n_devices = (int) q->devices.size(); }
     if (n_chunks == 0) return MRP_OK;
     /* tools/tagFromPhasedVcf.c:208-225 orders the chunks largest first; here by the (read, het variant) substrings uniform coverage gives */
     std::vector<int64_t> cost((size_t) n_chunks, 0);
     for (int64_t i = 0; i < n_chunks; i++)
         if (mrp_haplotag_chunk_units(&a.chunks[i], a.gt[i], &cost[(size_t) i]) != MRP_OK) cost[(size_t) i] = 0;
-    const int lanes = q->lanes, n_workers = n_devices * lanes;
-    const QueuePlan plan = plan_queue(n_chunks, cost.data(), A.chunks_per_batch, n_workers, n_devices);
-    const int64_t n_batches = (int64_t) plan.batch_off.size() - 1;
-    if (stats) stats->batches = n_batches;
-    QueueCall call(q, n_batches, active_lanes_of(plan, cost.data(), n_devices, lanes));
-
-    /* a batch as one mrp_haplotag_aligned_chunks call sees it: its chunks in plan order with their genotypes and output arrays, and the
-     * front -- its host part (the extraction's records, the checks, the windows) made by the prefetch beside the lane's current batch,
-     * its device part staged on the lane's context when the batch is run */
-    struct Staged {
-        std::atomic<int64_t> batch{-1}; /* (the call's thread looks its batch up while the stager fills the lane's OTHER slot) */
-        int64_t first = 0, count = 0;
-        std::vector<mrp_aligned_chunk> ch;
-        std::vector<const int32_t *> gt;
-        std::vector<int8_t *> hap;
-        std::vector<double *> h1, h2;
-        mrp_haplotag_front *front = nullptr;
-    };
-    std::vector<LaneSlots<Staged>> lane_state((size_t) n_workers);
-    auto staged_of = [&](int w, int64_t b) { return lane_state[(size_t) w].find(b); };
-    /* (a staged front holds arrays of the lane's context: it goes with no other thread of the lane at work, on the lane's thread) */
-    auto drop = [&](Staged *st) { mrp_haplotag_front_destroy(st->front); st->front = nullptr; st->batch = -1; };
-    LaneHooks hk;
-    hk.begin = [&](int w) { return call.lane_begin(w, false); };
-    hk.prefetch = [&](int w, int64_t b) { /* host only: never the lane's context, its stream, its events or its pool */
-        const auto t0 = std::chrono::steady_clock::now();
-        mrp_pool_adopt(q->pools[(size_t) (w / lanes)]);
-        Staged *st = lane_state[(size_t) w].next();
-        st->first = plan.batch_off[(size_t) b]; st->count = plan.batch_off[(size_t) b + 1] - st->first;
-        const size_t count = (size_t) st->count;
-        st->ch.resize(count); st->gt.resize(count); st->hap.resize(count);
-        st->h1.resize(a.h1_out ? count : 0);
-        st->h2.resize(a.h2_out ? count : 0);
-        for (size_t i = 0; i < count; i++) {
-            const int64_t chunk = plan.order[(size_t) st->first + i];
-            st->ch[i] = a.chunks[chunk];
-            st->gt[i] = a.gt[chunk];
-            st->hap[i] = a.hap_out[chunk];
-            if (a.h1_out) st->h1[i] = a.h1_out[chunk];
-            if (a.h2_out) st->h2[i] = a.h2_out[chunk];
-        }
-        st->batch.store(b);
-        mrp_haplotag_args ba = a;
-        ba.n_chunks = st->count;
-        ba.chunks = st->ch.data();
-        ba.gt = st->gt.data();
-        ba.hap_out = st->hap.data();
-        ba.h1_out = a.h1_out ? st->h1.data() : nullptr;
-        ba.h2_out = a.h2_out ? st->h2.data() : nullptr;
-        const int r = mrp_haplotag_front_create(&ba, nullptr, &st->front);
-        if (r != MRP_OK) call.stage_errs[(size_t) w] = mrp_last_error();
-        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: checks and windows of batch %lld (%lld chunks) in %.1f ms\n", call.since(), w, (long long) b,
-                                 (long long) st->count, ms_since(t0));
-        return r;
-    };
-    hk.discard = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
-    hk.phase = [&](int w, int64_t b) {
-        Staged *cur = staged_of(w, b);
-        if (!cur || !cur->front) { call.errs[(size_t) w] = "work queue: batch has no front"; return (int) MRP_ERR_ARG; }
-        const auto t0 = std::chrono::steady_clock::now();
-        int r = mrp_haplotag_front_stage(q->ctx[(size_t) w], cur->front);
-        const double front_ms = ms_since(t0);
-        if (r == MRP_OK) r = mrp_haplotag_front_run(cur->front); /* (writes the batch's outputs at the chunks' own arrays) */
-        QueueCall::PerLane &me = call.per[(size_t) w];
-        if (r != MRP_OK) call.errs[(size_t) w] = mrp_last_error();
-        else {
-            for (int64_t i = 0; i < cur->count; i++) me.units += cost[(size_t) plan.order[(size_t) (cur->first + i)]];
-            me.chunks += cur->count;
-        }
-        const double all_ms = ms_since(t0);
-        if (call.timing) fprintf(stderr, "  [%7.1f] queue lane %d: batch %lld: extraction and owners in %.1f ms, pairs and scoring in %.1f ms\n", call.since(), w,
-                                 (long long) b, front_ms, all_ms - front_ms);
-        me.busy_ms += all_ms;
-        return r;
-    };
-    hk.retire = [&](int w, int64_t b) { if (Staged *st = staged_of(w, b)) drop(st); };
-    hk.end = [&](int w) { call.lane_end(w); };
-    rc = call.run(hk);
-    call.fill(stats);
-    return rc != MRP_OK ? call.error(rc) : (int) MRP_OK;
+    HaplotagBody body{q, a};
+    return run_queue(q, n_chunks, cost, A.chunks_per_batch, stats, body, [] {}); /* (an error leaves the outputs unspecified) */
 }
 
 }  // namespace
