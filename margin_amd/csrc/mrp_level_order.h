@@ -15,6 +15,7 @@
 
 #include "mrp_census.h"
 #include "mrp_engine.h" /* MRP_MINI_MAX_UNITS, MRP_PRUNE_MAX_CELLS */
+#include "mrp_prune_lds.h"
 #include "rphmm_host.h" /* mrp_xhmm */
 
 /* Hands out consecutive aligned regions of one block (64 bytes unless told otherwise; a power of two).  Run the same code twice:
@@ -112,18 +113,9 @@ static inline PruneClass prune_class(int pairs, int max_cells) {
     return held <= MRP_PRUNE_HELD_256 ? PRUNE_256 : held <= MRP_PRUNE_HELD_512X32 ? PRUNE_512X32 :
            held <= MRP_PRUNE_HELD_TWO_GROUPS ? PRUNE_512X10_TWO_GROUPS : held <= MRP_PRUNE_HELD_ONE_GROUP ? PRUNE_512X10_ONE_GROUP : PRUNE_1024;
 }
-/* The prune kernel's dynamic LDS (its layout: mrp_prune_kernel), the same for every class: the selection, stage and list buffers
- * of PRUNE_SP slots, counters, two histograms of 1 024 bins, two bitmaps, range marks and prefixes, the inverse tables, the
- * merge-cell hash, a kept flag per merge cell and two columns of 16-bit posterior bins -- one per cell, or per complement pair
- * where the chain runs on pairs.  The largest request of the path is the per-cell level of 116 x 116 cells under the general
- * chain: 91 120 bytes, within MRP_LDS_BUDGET (tests/level_order_check.cpp), so no reachable level is refused for its LDS. */
-#define PRUNE_SP 128  /* slots of the selection buffers (S <= MRP_PRUNE_MAX_S) */
-#define PRUNE_TAB 5   /* per side and buffer: cnt, start, list, nx, pv, 128 entries each */
-static inline size_t prune_lds_bytes(int pairs, int max_cells, int max_merge) {
-    const size_t cap = pairs ? (size_t) (((max_cells + 1) / 2 + 3) & ~3) : (size_t) ((max_cells + 3) & ~3);
-    const size_t dwords = 4 * PRUNE_SP + PRUNE_SP + 4 * PRUNE_SP + 64 + 2 * 1024 + 512 + 512 + 2 * PRUNE_SP + 2 * PRUNE_SP + 512 + 512 + 4 * PRUNE_TAB * 128 + 512;
-    return dwords * 4 + (size_t) (((max_merge + 127) >> 7) << 2) * 4 + 2 * cap * 2 + 16;
-}
+/* The prune kernel's dynamic LDS, the same for every class: prune_lds_bytes and the layout it is the size of, mrp_prune_lds.h (PRUNE_SP,
+ * PRUNE_TAB).  The largest request of the path is the per-cell level of 116 x 116 cells under the general chain: 89 424 bytes, within
+ * MRP_LDS_BUDGET (tests/level_order_check.cpp), so no reachable level is refused for its LDS. */
 
 static inline int census_prune_slot(PruneClass k, int pairs) { return CENSUS_PRUNE + (int) k * PRUNE_CHAIN_MODES + pairs; }
 

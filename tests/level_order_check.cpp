@@ -130,17 +130,60 @@ static void check_prune_selector() {
 }
 
 /* The prune kernel's LDS request never exceeds the budget at a level the selector accepts (so the launcher's refusal for LDS is
- * unreachable): largest at the largest per-cell level under the general chain; monotone in both sizes; halved bins on pairs. */
+ * unreachable): largest at the largest per-cell level under the general chain; monotone in the size; halved bins on pairs. */
 static void check_prune_lds() {
-    CHECK(prune_lds_bytes(0, 13456, 13456) == 91120);
-    CHECK(prune_lds_bytes(0, MRP_PRUNE_MAX_CELLS, MRP_PRUNE_MAX_CELLS) <= (size_t) MRP_LDS_BUDGET);
+    CHECK(prune_lds_bytes(0, 13456) == 89424);
+    CHECK(prune_lds_bytes(0, MRP_PRUNE_MAX_CELLS) <= (size_t) MRP_LDS_BUDGET);
     for (int pairs = 0; pairs < 3; pairs++)
         for (int cells = 1; cells <= MRP_PRUNE_MAX_CELLS; cells += 97) {
-            CHECK(prune_lds_bytes(pairs, cells, cells) <= prune_lds_bytes(0, MRP_PRUNE_MAX_CELLS, MRP_PRUNE_MAX_CELLS));
-            CHECK(prune_lds_bytes(pairs, cells, cells) <= prune_lds_bytes(pairs, cells + 1, cells + 1));
-            CHECK(prune_lds_bytes(pairs, cells, cells) % 4 == 0);
+            CHECK(prune_lds_bytes(pairs, cells) <= prune_lds_bytes(0, MRP_PRUNE_MAX_CELLS));
+            CHECK(prune_lds_bytes(pairs, cells) <= prune_lds_bytes(pairs, cells + 1));
+            CHECK(prune_lds_bytes(pairs, cells) % 4 == 0);
         }
-    CHECK(prune_lds_bytes(1, 13456, 13456) == prune_lds_bytes(2, 13456, 13456) && prune_lds_bytes(1, 13456, 13456) == 91120 - 2 * 13456);
+    CHECK(prune_lds_bytes(1, 13456) == prune_lds_bytes(2, 13456) && prune_lds_bytes(1, 13456) == 89424 - 2 * 13456 && prune_lds_bytes(1, 13456) == 62512);
+}
+
+/* the request as it was written out by hand before the layout had one definition; it then held a kept flag per merge cell, which only the
+ * backward kernel uses: the forward kernel's request is smaller by those words */
+static size_t prune_lds_bytes_by_hand(int pairs, int max_cells, int max_merge) {
+    const size_t cap = pairs ? (size_t) (((max_cells + 1) / 2 + 3) & ~3) : (size_t) ((max_cells + 3) & ~3);
+    const size_t dwords = 4 * 128 + 128 + 4 * 128 + 64 + 2 * 1024 + 512 + 512 + 2 * 128 + 2 * 128 + 512 + 512 + 4 * 5 * 128 + 512;
+    return dwords * 4 + (size_t) (((max_merge + 127) >> 7) << 2) * 4 + 2 * cap * 2 + 16;
+}
+
+/* The regions of the prune kernel's LDS (mrp_prune_lds.h): in order, without overlap, aligned as the kernel reads them, and the request
+ * is their end plus the tail slack; the pointers handed out are the offsets. */
+static void check_prune_lds_layout() {
+    CHECK(PRUNE_SP == 128 && PRUNE_TAB == 5 && PRUNE_HIST == 1024 && PRUNE_SIDE == 128 && PRUNE_BMP == 512 && PRUNE_CHUNK == 512 && PRUNE_HTAB == 256 &&
+          PRUNE_LDS_TAIL_SLACK == 16);
+    CHECK(prune_flag_words(1) == 4 && prune_flag_words(128) == 4 && prune_flag_words(129) == 8 && prune_flag_words(13456) == 424);
+    std::vector<uint32_t> block(prune_lds_bytes(0, MRP_PRUNE_MAX_CELLS) / 4);
+    for (int pairs = 0; pairs < 3; pairs++)
+        for (int cells = 1; cells <= MRP_PRUNE_MAX_CELLS; cells += 97) {
+            const PruneLdsOff o = prune_lds_offsets(pairs != 0, cells);
+            /* (dwords) every region with the size the kernel uses of it; the bins: two columns of 16-bit entries */
+            const struct { int at, size, align; } R[] = {
+                {o.sel, 4 * PRUNE_SP, 2}, {o.um, PRUNE_SP, 1}, {o.s1, 4 * PRUNE_SP, 2}, {o.sh, 64, 4}, {o.hist, 2 * PRUNE_HIST, 1}, {o.bmp_c, PRUNE_BMP, 1},
+                {o.bmp_m, PRUNE_BMP, 1}, {o.kml, 2 * PRUNE_SP, 1}, {o.minfo, 2 * PRUNE_SP, 4}, {o.heads, PRUNE_CHUNK, 1}, {o.pref, PRUNE_BMP, 1},
+                {o.tab, 2 * 2 * PRUNE_TAB * PRUNE_SIDE, 1}, {o.htab_key, PRUNE_HTAB, 1}, {o.htab_val, PRUNE_HTAB, 1}, {o.bins, o.cap_c, 4}};
+            int at = 0;
+            for (const auto &r : R) {
+                CHECK(r.at == at && r.size > 0 && r.at % r.align == 0);
+                at += r.size;
+            }
+            CHECK(o.end == at && (size_t) o.end * 4 + PRUNE_LDS_TAIL_SLACK == prune_lds_bytes(pairs, cells));
+            CHECK((o.sh + MB_COL) % 4 == 0 && MB_COL + 8 <= MB_HIST_USED && MB_HIST_USED + 2 <= 64);
+            CHECK(o.cap_c == prune_bins_cap(pairs != 0, cells) && o.cap_c % 4 == 0 && o.cap_c >= (pairs ? (cells + 1) / 2 : cells));
+            for (int merge : {1, cells, MRP_PRUNE_MAX_CELLS})
+                CHECK(prune_lds_bytes(pairs, cells) == prune_lds_bytes_by_hand(pairs, cells, merge) - 4 * (size_t) prune_flag_words(merge));
+            const PruneLds l = prune_lds_carve(block.data(), pairs != 0, cells);
+            CHECK(l.sel == block.data() + o.sel && l.um == block.data() + o.um && l.s1 == block.data() + o.s1 && l.sh == block.data() + o.sh);
+            CHECK(l.hist == block.data() + o.hist && l.bmp_c == block.data() + o.bmp_c && l.bmp_m == block.data() + o.bmp_m && l.kml == block.data() + o.kml);
+            CHECK(l.minfo == block.data() + o.minfo && l.heads == block.data() + o.heads && l.pref == block.data() + o.pref && l.tab == block.data() + o.tab);
+            CHECK(l.htab_key == block.data() + o.htab_key && l.htab_val == block.data() + o.htab_val);
+            CHECK(l.bins == reinterpret_cast<uint16_t *>(block.data() + o.bins) && l.cap_c == o.cap_c);
+            CHECK((size_t) (reinterpret_cast<uint32_t *>(l.bins + 2 * l.cap_c) - block.data()) * 4 + PRUNE_LDS_TAIL_SLACK == prune_lds_bytes(pairs, cells));
+        }
 }
 
 /* The cross product + emission plan, restated: a level that is mostly the single-wave kernel's runs the table-free mode 1 and, if any
@@ -266,6 +309,7 @@ int main() {
                 for (int rep = 0; rep < (n <= 63 ? 20 : 2); rep++) check_level(random_level(rng, n, mode), units != 0);
     check_prune_selector();
     check_prune_lds();
+    check_prune_lds_layout();
     check_cross_emit_plan();
     check_census_slots();
     for (int rep = 0; rep < 2000; rep++) check_carver(rng);

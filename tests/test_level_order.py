@@ -4,7 +4,8 @@ launch classes on seeded random levels (n in {0, 1, 2, 63, 4 096, 4 097, 6 000};
 common; bounds on both sides of every threshold; unit and cell levels) against a plain restatement; the prune kernel's class from (chain mode, largest column) on both sides of every threshold
 (256/257, 4 096/4 097, 5 120/5 121, 10 240/10 241, the end of the range at 13 824/13 825; cell levels and unit levels) and at every size
 up to there against a table of what each class holds; the prune kernel's LDS request within the budget at every size the selector
-accepts (91 120 bytes at 116 x 116 cells, its largest reachable level); the cross product + emission plan at 64/65 and 128/129 cells with the level mostly
+accepts (89 424 bytes at 116 x 116 cells, its largest reachable level) and the layout behind it (mrp_prune_lds.h: regions in order, disjoint,
+aligned as the kernel reads them; the request is their end plus the tail slack, and the hand-written sum of before minus the flag words); the cross product + emission plan at 64/65 and 128/129 cells with the level mostly
 single-wave or not; the census slots (named, distinct, class-major); and the block carver's sizing
 pass against its pointer pass (64-byte aligned, inside the block, disjoint regions; a zero count takes nothing), and the chunk block of
 a work queue's batch (chunks of 0, 1 and 5 sites with slot totals not divisible by 4, profile pools of 0, 1, 255, 256 and 257 bytes, with
