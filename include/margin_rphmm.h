@@ -507,7 +507,8 @@ int mrp_band_diagonals(const int64_t *anchors, int64_t n_anchors, int64_t lx, in
  * on: such a pair is aligned by the pair-per-workgroup kernel, up to MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS.
  * Honoured by every entry that takes the context and scores pairs: mrp_forward_probabilities, mrp_allele_read_supports,
  * mrp_partition_reads_by_haplotype, mrp_phase_variants_from_tagged_reads, mrp_phase_string_chunks(_with_filtered),
- * mrp_haplotag_aligned_chunks, mrp_phase_aligned_chunks(_with_filtered, _with_records). */
+ * mrp_haplotag_aligned_chunks, mrp_phase_aligned_chunks(_with_filtered, _with_records).  NOT extended to
+ * mrp_posterior_aligned_pairs, which refuses a pair beyond 2 048 cells whatever this setting. */
 int mrp_context_set_wide_pairs(mrp_context *ctx, int on);
 /* pairs / dp cells the wide kernel has taken on this context since it was created (either pointer may be NULL) */
 int mrp_context_wide_pair_count(mrp_context *ctx, int64_t *pairs_out, int64_t *cells_out);
@@ -551,6 +552,86 @@ int mrp_forward_probabilities(mrp_context *ctx, const mrp_pair_hmm *models, int3
                               int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len, const int64_t *y_off,
                               const int32_t *y_len, const uint8_t *model_index, const int64_t *anchor_off, const int64_t *anchors,
                               int64_t expansion, int ragged_left, int ragged_right, double *out, mrp_pairhmm_stats *stats);
+/* ---- the posterior half of the pairwise aligner: aligned pairs from banded tracebacks -------------------------
+ * getPosteriorProbsWithBanding (pairwiseAligner.c:706-844) for n_pairs string pairs: the banded forward recursion of
+ * mrp_forward_probabilities, a backward pass at every traceback point of the band (:746-749), the total recomputed at every tenth
+ * diagonal of a traceback (:788-803, :578-596), and per band cell exp((forward + backward) - total) tested against the threshold
+ * (addPosteriorProb, :598-608).  with_gaps = 0 is diagonalCalculationPosteriorMatchProbs (:610-635), what getAlignedPairsUsingAnchors
+ * (:1125-1146) is built from; with_gaps = 1 is diagonalCalculationPosteriorProbs (:637-681), what
+ * getAlignedPairsWithIndelsUsingAnchors (:1148-1171) is built from.  Bit for bit the reference's arithmetic, exp() included: the
+ * device compacts the cells near or above the threshold and the host applies the rule with the C library's exp.
+ *
+ * ORDER.  A pair's lists come in the order the reference generates them: tracebacks ascending, diagonals descending inside a
+ * traceback, x - y ascending inside a diagonal.  getAlignedPairsUsingAnchors hands its callers the REVERSE of that list
+ * (stList_reverse, :1109-1111): a caller who wants that order walks a pair's range backwards.
+ *
+ * Out of scope: getPosteriorProbsWithBandingSplittingAlignmentsByLargeGaps and getSplitPoints (:913-1040; a caller passes each
+ * sub-region as a pair of its own with its ragged flags), dynamicAnchorExpansion (band_constructDynamic),
+ * diagonalCalculationExpectations (:683-696), run-length emissions, reweightAlignedPairs, leftShiftAlignment and POA construction,
+ * pairs whose widest diagonal exceeds 2 048 cells, and any leg of the benchmark. */
+typedef struct mrp_posterior_options {
+    double  threshold;                    /* in (0, 1]; PairwiseAlignmentParameters.threshold (reference default 0.01) */
+    int64_t expansion;                    /* diagonalExpansion: even, >= 0 (default 20) */
+    int64_t min_diags_between_traceback;  /* minDiagsBetweenTraceBack: >= 2 (default 1000) */
+    int64_t traceback_diagonals;          /* traceBackDiagonals: >= 1 and + 1 < min_diags_between_traceback (default 40) */
+    int32_t ragged_left, ragged_right;    /* alignmentHasRaggedLeftEnd / RightEnd (stateMachine.c:521-560) */
+    int32_t with_gaps;                    /* 0: match list only; 1: match, gap-x, gap-y */
+    int32_t reserved;                     /* 0 */
+} mrp_posterior_options;
+
+typedef struct mrp_posterior_pairs {      /* pair i owns [first[i], first[i+1]); n_pairs + 1 offsets from 0 */
+    int64_t *first;
+    int32_t *x, *y, *weight;              /* sequence coordinates (x - 1, y - 1 of the cell: -1 in a gap list for the gap before the first
+                                           * symbol); weight = floor(min(p, 1) * 1e7), PAIR_ALIGNMENT_PROB_1 */
+    double  *log_posterior;               /* the v = (forward + backward) - total whose exp() was tested */
+} mrp_posterior_pairs;
+
+/* Host only, no device: the tracebacks of one pair, (d, tracedBackTo, tracedBackFrom) triples in ascending order (:746-749, :768,
+ * :819): a traceback at diagonal d = x + y when d == lx + ly, or when d >= tracedBackTo + min_diags_between_traceback and the band's
+ * diagonal d has at most 2 * expansion + 1 cells; it takes the posteriors of the diagonals (tracedBackTo, tracedBackFrom],
+ * tracedBackFrom = d - (traceback_diagonals + 1), or d at the end.  The band is mrp_band_diagonals'.  *n_out = the count (0 for two empty
+ * strings); the first min(count, capacity) triples are written to triples_out (3 int64 each; may be NULL with capacity 0).  The list depends
+ * on the band alone, which is why the device entry runs a pair's tracebacks side by side.  MRP_ERR_ARG for NULL arguments, options
+ * the reference asserts against (:714-718; threshold and reserved are checked as by the device entry), invalid anchors. */
+int mrp_posterior_tracebacks(const int64_t *anchors, int64_t n_anchors, int64_t lx, int64_t ly, const mrp_posterior_options *opt,
+                             int64_t *triples_out, int64_t capacity, int64_t *n_out);
+/* Inputs as mrp_forward_probabilities.  match_out (and, exactly when opt->with_gaps is set, gap_x_out and gap_y_out: gap-x holds the
+ * cells with x > 0, gap-y those with y > 0) receive malloc'd arrays, released with mrp_posterior_pairs_free.  total_out (n_pairs, may
+ * be NULL): the total taken at diagonal lx + ly in the pair's last traceback, bit for bit mrp_forward_probabilities' value for the same
+ * pair and raggedness.  A pair of two empty strings has empty lists and a total of 0.0 (:721-723).
+ *   The call runs its pairs in groups, in input order; a group's forward diagonals (24 B per band cell) fit the context's posterior
+ * workspace, MRP_POSTERIOR_DEFAULT_WORKSPACE unless mrp_context_set_posterior_workspace changed it.  Beside it a group holds up to
+ * 16 B per band cell and list for the candidates.  16 B per candidate, 12 B per traceback and 8 B per pair return from the device.
+ *   Errors, in this order; on an error nothing is written.  MRP_ERR_ARG: NULL arguments; reserved != 0; a threshold outside (0, 1]
+ * (0 would return every cell of the band and is refused with a message that says so); an odd or negative expansion; the preconditions
+ * of :714-718; gap outputs that do not match with_gaps; an offset outside the pool; a model index >= n_models; invalid anchors, as
+ * mrp_band_diagonals rejects them.  MRP_ERR_UNSUPPORTED: a pair whose widest diagonal exceeds 2 048 cells (wide pairs,
+ * mrp_context_set_wide_pairs, are NOT extended to this entry); a single pair whose forward diagonals exceed the workspace (the message
+ * names the limit) or whose band holds 2^31 cells or more.  MRP_ERR_NO_DEVICE for a NULL context.  stats may be NULL: pairs_wave = the pairs that ran, cells, kernel_ms = the
+ * forward and the traceback kernels (mrp_context_last_posterior has them apart), total_ms. */
+int mrp_posterior_aligned_pairs(mrp_context *ctx, const mrp_pair_hmm *models, int32_t n_models, int64_t n_pairs, const uint8_t *pool,
+                                int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len, const int64_t *y_off, const int32_t *y_len,
+                                const uint8_t *model_index, const int64_t *anchor_off, const int64_t *anchors, const mrp_posterior_options *opt,
+                                mrp_posterior_pairs *match_out, mrp_posterior_pairs *gap_x_out, mrp_posterior_pairs *gap_y_out,
+                                double *total_out /* [n_pairs], may be NULL */, mrp_pairhmm_stats *stats);
+void mrp_posterior_pairs_free(mrp_posterior_pairs *p); /* frees the five arrays and zeroes *p; NULL is fine */
+/* Bytes of forward diagonals the pairs of one group of mrp_posterior_aligned_pairs may keep together on the device (24 B per band
+ * cell).  Default: 1 GiB, 4.4e7 band cells -- four thousand 100 x 100 matrices, or three hundred 2 kb pairs in a band of 37.  A pair
+ * is a wave and its steps are latency bound, so a group should hold enough pairs to fill the device: groups run one after the other
+ * (DESIGN.md 9.15).  0 restores the default; negative: MRP_ERR_ARG.  A single pair beyond it is refused (MRP_ERR_UNSUPPORTED). */
+#define MRP_POSTERIOR_DEFAULT_WORKSPACE ((int64_t) 1 << 30)
+int mrp_context_set_posterior_workspace(mrp_context *ctx, int64_t bytes);
+typedef struct mrp_posterior_stats { /* the context's most recent successful mrp_posterior_aligned_pairs */
+    double forward_ms, traceback_ms; /* HIP events around the launches of the two kernels, summed over the groups */
+    double total_ms;                 /* host wall time of the call */
+    int64_t cells;                   /* band cells of the call's pairs: what the forward kernel walks */
+    int64_t traceback_cells;         /* band cells the tracebacks walk: the diagonals (tracedBackTo, d] of each */
+    int64_t candidates;              /* records that crossed from the device, 16 B each */
+    int64_t downloaded_bytes;        /* candidates, counts and totals */
+    int64_t groups;
+} mrp_posterior_stats;
+int mrp_context_last_posterior(mrp_context *ctx, mrp_posterior_stats *out);
+
 /* The alleleReadSupports loop of bubbleGraph.c:1421-1464 for n_bubbles bubbles.  Bubble b owns alleles
  * [allele_first[b], allele_first[b+1]) and read substrings [read_first[b], read_first[b+1]); x = allele, y = read
  * substring, the read's strand picks the state machine -- except that, as in the reference (cachedScores is keyed by the

@@ -51,6 +51,8 @@ EXPORTED_SYMBOLS = [
     "mrp_downsample_keep_from_extracted", "mrp_downsample_reads",
     "mrp_queue_phase_aligned_chunks_with_records", "mrp_phase_aligned_chunks_with_records_on_devices", "mrp_final_read_tags", "mrp_stitch_values",
     "mrp_close_contig", "mrp_close_contigs", "mrp_contig_out_clear",
+    "mrp_posterior_tracebacks", "mrp_posterior_aligned_pairs", "mrp_posterior_pairs_free", "mrp_context_set_posterior_workspace",
+    "mrp_context_last_posterior",
 ]
 
 
@@ -213,6 +215,38 @@ class PairHmm(C.Structure):
 
 class PairHmmStats(C.Structure):
     _fields_ = [("pairs_lane", C.c_int64), ("pairs_wave", C.c_int64), ("cells", C.c_int64), ("kernel_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+POSTERIOR_DEFAULT_WORKSPACE = 1 << 30  # MRP_POSTERIOR_DEFAULT_WORKSPACE
+
+
+class PosteriorOptions(C.Structure):
+    """mrp_posterior_options; the defaults are pairwiseAlignmentBandingParameters_construct's (impl/pairwiseAligner.c:1048-1060)"""
+    _fields_ = [("threshold", C.c_double), ("expansion", C.c_int64), ("min_diags_between_traceback", C.c_int64), ("traceback_diagonals", C.c_int64),
+                ("ragged_left", C.c_int32), ("ragged_right", C.c_int32), ("with_gaps", C.c_int32), ("reserved", C.c_int32)]
+
+    def __init__(self, threshold=0.01, expansion=20, min_diags_between_traceback=1000, traceback_diagonals=40, ragged_left=False, ragged_right=False,
+                 with_gaps=False, reserved=0):
+        super().__init__(float(threshold), int(expansion), int(min_diags_between_traceback), int(traceback_diagonals), int(ragged_left), int(ragged_right),
+                         int(with_gaps), int(reserved))
+
+
+class PosteriorPairs(C.Structure):
+    """mrp_posterior_pairs: pair i owns [first[i], first[i + 1])"""
+    _fields_ = [("first", C.POINTER(C.c_int64)), ("x", C.POINTER(C.c_int32)), ("y", C.POINTER(C.c_int32)), ("weight", C.POINTER(C.c_int32)),
+                ("log_posterior", C.POINTER(C.c_double))]
+
+    def to_numpy(self, n_pairs: int) -> dict:
+        first = np.ctypeslib.as_array(self.first, shape=(n_pairs + 1,)).copy()
+        n = int(first[-1])
+        take = lambda p, dt: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype=dt)
+        return {"first": first, "x": take(self.x, np.int32), "y": take(self.y, np.int32), "weight": take(self.weight, np.int32),
+                "log_posterior": take(self.log_posterior, np.float64)}
+
+
+class PosteriorStats(C.Structure):
+    _fields_ = [("forward_ms", C.c_double), ("traceback_ms", C.c_double), ("total_ms", C.c_double), ("cells", C.c_int64), ("traceback_cells", C.c_int64),
+                ("candidates", C.c_int64), ("downloaded_bytes", C.c_int64), ("groups", C.c_int64)]
 
 
 class HaptagSites(C.Structure):
@@ -463,6 +497,13 @@ def load():
     L.mrp_downsample_keep_from_extracted.argtypes = [P(ExtractedChunk), vp, i64, C.c_uint64, i64, i64, vp, vp, P(i32)]
     L.mrp_downsample_reads.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, C.c_uint64, vp, vp, vp, vp, P(DownsamplingStats)]
     L.mrp_forward_probabilities.argtypes = [vp, vp, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, P(PairHmmStats)]
+    L.mrp_posterior_tracebacks.argtypes = [vp, i64, i64, i64, P(PosteriorOptions), vp, i64, P(i64)]
+    L.mrp_posterior_aligned_pairs.argtypes = [vp, vp, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, P(PosteriorOptions), P(PosteriorPairs), P(PosteriorPairs),
+                                              P(PosteriorPairs), vp, P(PairHmmStats)]
+    L.mrp_posterior_pairs_free.argtypes = [P(PosteriorPairs)]
+    L.mrp_posterior_pairs_free.restype = None
+    L.mrp_context_set_posterior_workspace.argtypes = [vp, i64]
+    L.mrp_context_last_posterior.argtypes = [vp, P(PosteriorStats)]
     L.mrp_allele_read_supports.argtypes = [vp, P(PairHmm), P(PairHmm), i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, P(PairHmmStats)]
     L.mrp_partition_reads_by_haplotype.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, i64, vp, vp, vp, P(PairHmmStats)]
     L.mrp_phase_variants_from_tagged_reads.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, vp, i64, i64, vp, vp, vp, P(PairHmmStats)]
@@ -572,6 +613,15 @@ class Context:
         counts = (C.c_uint64 * len(names))()
         _check(load().mrp_context_launch_census(self.h, counts, len(names), int(bool(reset))))
         return dict(zip(names, (int(c) for c in counts)))
+
+    def set_posterior_workspace(self, n_bytes: int):
+        """mrp_context_set_posterior_workspace: bytes of forward diagonals a group of posterior_aligned_pairs keeps on the device (0: the default)"""
+        _check(load().mrp_context_set_posterior_workspace(self.h, int(n_bytes)))
+
+    def last_posterior(self) -> "PosteriorStats":
+        st = PosteriorStats()
+        _check(load().mrp_context_last_posterior(self.h, C.byref(st)))
+        return st
 
     def set_wide_pairs(self, on):
         """mrp_context_set_wide_pairs: pairs whose widest diagonal exceeds 2 048 cells are aligned, not refused (up to WIDE_MAX_WIDTH / WIDE_MAX_CELLS)"""
@@ -1237,6 +1287,40 @@ def forward_probabilities(ctx: Context, models, pool, x_off, x_len, y_off, y_len
                                             ptr(mi), None if ao is None else ao.ctypes.data, ptr(an), int(expansion), int(ragged_left),
                                             int(ragged_right), ptr(out), C.byref(st)))
     return out, st
+
+
+def posterior_tracebacks(anchors, lx: int, ly: int, options: PosteriorOptions) -> np.ndarray:
+    """mrp_posterior_tracebacks (host only): int64 [n, 3] (d, tracedBackTo, tracedBackFrom), impl/pairwiseAligner.c:746-749,768,819"""
+    a = np.ascontiguousarray(np.asarray(anchors if anchors is not None else [], dtype=np.int64).reshape(-1, 2))
+    out = np.zeros((lx + ly + 1, 3), dtype=np.int64)
+    n = C.c_int64()
+    _check(load().mrp_posterior_tracebacks(a.ctypes.data if len(a) else None, len(a), lx, ly, C.byref(options), out.ctypes.data, len(out), C.byref(n)))
+    return out[:n.value].copy()
+
+
+def posterior_aligned_pairs(ctx, models, pool, x_off, x_len, y_off, y_len, model_index=None, anchor_off=None, anchors=None,
+                            options: PosteriorOptions = None, want_total: bool = True):
+    """getPosteriorProbsWithBanding for a batch of pairs (mrp_posterior_aligned_pairs) -> (match, gap_x, gap_y, total, PairHmmStats):
+    each list a dict of first / x / y / weight / log_posterior in the reference's order of generation, gap_x and gap_y None without
+    options.with_gaps.  ctx may be None (the checks that need no device)."""
+    options = options if options is not None else PosteriorOptions()
+    arr = (PairHmm * len(models))(*models)
+    pool = np.ascontiguousarray(pool, dtype=np.uint8)
+    xo, xl, yo, yl = _opt(x_off, np.int64), _opt(x_len, np.int32), _opt(y_off, np.int64), _opt(y_len, np.int32)
+    mi, ao, an = _opt(model_index, np.uint8), _opt(anchor_off, np.int64), _opt(anchors, np.int64)
+    n = len(xo)
+    total = np.zeros(n, dtype=np.float64) if want_total else None
+    st = PairHmmStats()
+    lists = [PosteriorPairs() for _ in range(3 if options.with_gaps else 1)]
+    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+    _check(load().mrp_posterior_aligned_pairs(ctx.h if ctx is not None else None, C.cast(arr, C.c_void_p), len(models), n, ptr(pool), pool.size, ptr(xo), ptr(xl),
+                                              ptr(yo), ptr(yl), ptr(mi), None if ao is None else ao.ctypes.data, ptr(an), C.byref(options), C.byref(lists[0]),
+                                              C.byref(lists[1]) if options.with_gaps else None, C.byref(lists[2]) if options.with_gaps else None,
+                                              ptr(total), C.byref(st)))
+    out = [l.to_numpy(n) for l in lists]
+    for l in lists:
+        load().mrp_posterior_pairs_free(C.byref(l))
+    return out[0], (out[1] if options.with_gaps else None), (out[2] if options.with_gaps else None), total, st
 
 
 def kmer_alignment_anchors(sx, sy) -> np.ndarray:

@@ -374,6 +374,8 @@ struct mrp_context {
     int64_t max_depth = 0;   /* mrp_context_set_downsampling: > 0 makes the aligned composites' mask on the device (0: off) */
     uint64_t downsampling_seed = 0;
     mrp_downsampling_stats last_downsampling{}; /* mrp_context_last_downsampling */
+    int64_t posterior_workspace = 0; /* mrp_context_set_posterior_workspace: bytes of forward diagonals a group of mrp_posterior_aligned_pairs keeps (0: the default) */
+    mrp_posterior_stats last_posterior{}; /* mrp_context_last_posterior */
     int64_t wide_pair_count = 0, wide_cell_count = 0; /* what that kernel has taken on this context (mrp_context_wide_pair_count) */
     int phase_groups = 0; /* concurrent batches of mrp_phase_reads_many (mrp_context_set_phase_groups); 0: chosen by batch size */
     std::vector<mrp_context *> siblings; /* further contexts on the same device (concurrent batches of mrp_phase_reads_many) */

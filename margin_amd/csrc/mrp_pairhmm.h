@@ -51,6 +51,8 @@ const int WAVE_CLASS_CAP[4] = {64, 256, 1024, PHM_WAVE_MAX_WIDTH};
 int band_closed_form(const int64_t *anchors, int64_t n_anchors, int64_t lx, int64_t ly, int64_t expansion, int32_t *L, int32_t *R,
                      int64_t *cells, int *max_width);
 int64_t kmer_anchors(const uint8_t *sx, int64_t lx, const uint8_t *sy, int64_t ly, std::vector<int64_t> &out);
+/* (mrp_pairhmm.hip) a model as the kernels read it: the N rows of the emissions, the start and end states of stateMachine.c:521-560 */
+void model_to_device(const mrp_pair_hmm &m, int ragged_left, int ragged_right, PhmModelDev &d);
 
 /* A batch's pairs as phm_classify reads them, in the order of the output: pair i aligns x (an allele) to y (a read substring), both
  * in one symbol pool, with model model[i] (NULL: model 0), inside the band of the anchors (x, y) anchors[2 * anchor_off[i]] up to

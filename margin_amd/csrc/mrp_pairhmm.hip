@@ -39,6 +39,7 @@
 #include "../../include/margin_rphmm.h"
 #include "mrp_internal.h"
 #include "mrp_pairhmm.h"
+#include "mrp_pairhmm_dev.h" /* St, phm_log_add, phm_cell, phm_dot */
 #include "mrp_wave.h"
 #include "rphmm_host.h"
 
@@ -52,28 +53,6 @@ constexpr int PHM_LDS_BYTES = 160 * 1024;
 constexpr int PHM_LANE_BYTES_PER_X = 3 * 64 * 8 + 64; /* LDS per wave and x position: three states per lane + the lane's symbol */
 constexpr int PHM_ETAB = 25 * 6;       /* doubles per model in the emission + transition table */
 
-struct St {
-    double m, x, y;
-};
-
-#define PHM_NEG (-__builtin_inf())
-
-/* lookup(), pairwiseAligner.c:282-293: the float literals are rounded to float first, as the C compiler does */
-static __device__ __forceinline__ double phm_lookup(double x) {
-    const bool a = x <= 1.0, b = x <= 2.5, c = x <= 4.5;
-    const double c3 = a ? (double) -0.009350833524763f : b ? (double) -0.014532321752540f : c ? (double) -0.004605031767994f : (double) -0.000458661602210f;
-    const double c2 = a ? (double) 0.130659527668286f : b ? (double) 0.139942324101744f : c ? (double) 0.063427417320019f : (double) 0.009695946122598f;
-    const double c1 = a ? (double) 0.498799810682272f : b ? (double) 0.495635523139337f : c ? (double) 0.695956496475118f : (double) 0.930734667215156f;
-    const double c0 = a ? (double) 0.693203116424741f : b ? (double) 0.692140569840976f : c ? (double) 0.514272634594009f : (double) 0.168037164329057f;
-    return ((c3 * x + c2) * x + c1) * x + c0;
-}
-/* logAdd(), pairwiseAligner.c:295-299 */
-static __device__ __forceinline__ double phm_log_add(double x, double y) {
-    const bool lt = x < y;
-    const double hi = lt ? y : x, lo = lt ? x : y;
-    const double d = hi - lo; /* NaN for two LOG_ZEROs: not used, lo == LOG_ZERO decides first */
-    return (lo == PHM_NEG || d >= 7.5) ? hi : phm_lookup(d) + lo;
-}
 /* The same two functions with the coefficients of the interval read from LDS (coef[interval][c3, c2, c1, c0]) instead
  * of selected with 24 v_cndmask: the pair-per-lane kernel is bound by VALU issue, its LDS pipe is mostly idle */
 __device__ const float PHM_COEF[16] = {-0.009350833524763f, 0.130659527668286f, 0.498799810682272f, 0.693203116424741f,
@@ -105,27 +84,6 @@ template <bool THIRD>
 static __device__ __forceinline__ double phm_chain_t(double a, double b, double c, const double *coef) {
     const double ab = phm_log_add_t(a, b, coef);
     return THIRD ? phm_log_add_t(ab, c, coef) : ab;
-}
-
-/* toCells[to] = logAdd(toCells[to], from + (eP + tP)) three times, starting from LOG_ZERO (logAdd(LOG_ZERO, a) == a) */
-static __device__ __forceinline__ double phm_chain(double a, double b, double c) { return phm_log_add(phm_log_add(a, b), c); }
-
-struct PhmRowT { /* eP + tP of the gap-y transitions of a row (y fixed) */
-    double open, extend, sw;
-};
-static __device__ __forceinline__ St phm_cell(const St &lower, const St &middle, const St &upper, const double *t, double eX, double eM,
-                                              const PhmRowT &ty) {
-    St cur;
-    cur.x = phm_chain(lower.m + (eX + t[3]), lower.x + (eX + t[5]), lower.y + (eX + t[7]));
-    cur.m = phm_chain(middle.m + (eM + t[0]), middle.x + (eM + t[1]), middle.y + (eM + t[2]));
-    cur.y = phm_chain(upper.m + ty.open, upper.y + ty.extend, upper.x + ty.sw);
-    return cur;
-}
-/* cell_dotProduct, pairwiseAligner.c:333-339 */
-static __device__ __forceinline__ double phm_dot(const St &f, const double *e) {
-    double tot = f.m + e[0];
-    tot = phm_log_add(tot, f.x + e[1]);
-    return phm_log_add(tot, f.y + e[2]);
 }
 
 /* LDS: coef[16] | etab[n_models][cx][cy][6] = eX + {open, extend, switch to x}, eM + {continue, from x, from y} |
@@ -471,7 +429,7 @@ int band_closed_form(const int64_t *anchors, int64_t n_anchors, int64_t lx, int6
     return MRP_OK;
 }
 
-static void model_to_device(const mrp_pair_hmm &m, int ragged_left, int ragged_right, PhmModelDev &d) {
+void model_to_device(const mrp_pair_hmm &m, int ragged_left, int ragged_right, PhmModelDev &d) {
     const double *t = &m.match_continue;
     for (int i = 0; i < 9; i++) d.t[i] = t[i];
     for (int x = 0; x < 5; x++)

@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Timing probe of mrp_posterior_aligned_pairs: kernel time (HIP events) of its forward and traceback kernels, pairs/s and band cells/s
+of each, the bytes that return per pair, and beside them mrp_forward_probabilities on the same pairs in the same run.
+Two shapes: --short N pairs of 100 x ~97 with the reference's default parameters (one traceback each), --long N pairs of
+--long-len x --long-len anchored on the diagonal every 16 symbols (a band of 37 cells; a traceback every 1 000 diagonals)."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+
+from margin_amd import capi, synth  # noqa: E402
+
+
+def short_pairs(n, seed):
+    rng = np.random.default_rng(seed)
+    pairs = []
+    for _ in range(n):
+        sx = synth.random_sequence(rng, 100)
+        pairs.append((sx, synth.evolve_sequence(rng, sx, 0.05, 0.05, 0.05), []))
+    return pairs
+
+
+def long_pairs(n, length, seed):
+    rng = np.random.default_rng(seed)
+    anchors = [(i, i) for i in range(8, length - 8, 16)]
+    pairs = []
+    for _ in range(n):
+        sx = synth.random_sequence(rng, length)
+        sy = sx.copy()
+        hit = rng.random(length) < 0.15  # substitutions only: the diagonal anchors stay valid
+        sy[hit] = rng.integers(0, 4, size=int(hit.sum()))
+        pairs.append((sx, sy, anchors))
+    return pairs
+
+
+def pack(pairs):
+    pool, xo, xl, yo, yl, ao, an, at = [], [], [], [], [], [0], [], 0
+    for sx, sy, anchors in pairs:
+        xo.append(at); xl.append(len(sx)); at += len(sx)
+        yo.append(at); yl.append(len(sy)); at += len(sy)
+        pool += [sx, sy]
+        an += [v for a in anchors for v in a]
+        ao.append(len(an) // 2)
+    return (np.concatenate(pool), np.array(xo, np.int64), np.array(xl, np.int32), np.array(yo, np.int64), np.array(yl, np.int32),
+            np.array(ao, np.int64), np.array(an, np.int64))
+
+
+def probe(ctx, models, name, pairs, opt, repeat):
+    pool, xo, xl, yo, yl, ao, an = pack(pairs)
+    n = len(pairs)
+    rows = []
+    for r in range(repeat + 1):  # the first run warms the code objects and the context's pool
+        match, _gx, _gy, total, st = capi.posterior_aligned_pairs(ctx, models, pool, xo, xl, yo, yl, None, ao, an, opt)
+        ps = ctx.last_posterior()
+        fwd, fst = capi.forward_probabilities(ctx, models, pool, xo, xl, yo, yl, None, ao, an, expansion=opt.expansion)
+        if r:
+            rows.append((ps.forward_ms, ps.traceback_ms, ps.total_ms, fst.kernel_ms, fst.total_ms))
+    assert (total == fwd).all()
+    f_ms, t_ms, call_ms, y_ms, ycall_ms = (float(np.median([row[k] for row in rows])) for k in range(5))
+    print(f"{name}: {n} pairs, {ps.cells} band cells, {ps.traceback_cells} walked back, {ps.groups} group(s), with_gaps={int(opt.with_gaps)}, "
+          f"{int(match['first'][-1])} match pairs", flush=True)
+    print(f"  forward kernel   {f_ms:9.3f} ms  {n / f_ms * 1e3:.3e} pairs/s  {ps.cells / f_ms * 1e3:.3e} band cells/s", flush=True)
+    print(f"  traceback kernel {t_ms:9.3f} ms  {n / t_ms * 1e3:.3e} pairs/s  {ps.traceback_cells / t_ms * 1e3:.3e} band cells/s", flush=True)
+    print(f"  call             {call_ms:9.3f} ms  {n / call_ms * 1e3:.3e} pairs/s; {ps.downloaded_bytes / n:.1f} B downloaded per pair "
+          f"({ps.candidates} candidates)", flush=True)
+    print(f"  mrp_forward_probabilities on the same pairs: kernel {y_ms:.3f} ms  {fst.cells / y_ms * 1e3:.3e} cells/s, call {ycall_ms:.3f} ms "
+          f"(lane {fst.pairs_lane}, wave {fst.pairs_wave})", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--short", type=int, default=4096)
+    ap.add_argument("--long", type=int, default=256)
+    ap.add_argument("--long-len", type=int, default=2000)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--with-gaps", type=int, default=0)
+    args = ap.parse_args()
+    models = [capi.PairHmm.default_nucleotide()]
+    opt = capi.PosteriorOptions(with_gaps=bool(args.with_gaps))  # threshold 0.01, expansion 20, 1 000 / 40
+    with capi.Context(0) as ctx:
+        if args.short:
+            probe(ctx, models, "short", short_pairs(args.short, 5), opt, args.repeat)
+        if args.long:
+            probe(ctx, models, "long", long_pairs(args.long, args.long_len, 6), opt, args.repeat)
+
+
+if __name__ == "__main__":
+    main()
