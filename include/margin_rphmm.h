@@ -90,7 +90,9 @@ int mrp_context_set_phase_groups(mrp_context *ctx, int groups);
  * array entry per cell on unit levels (the chain on complement pairs over per-cell arrays) instead of one per complement pair.
  * Bit 5: no merge level is launched deferred -- every launch waits for its totals, as the large levels' do.  Bit 6: the grid of
  * the pair-per-workgroup pair-HMM kernel (mrp_context_set_wide_pairs) is one workgroup, so consecutive wide pairs of a call reuse
- * one workspace slice. */
+ * one workspace slice.  Bit 7: every pair of a posterior call (mrp_posterior_aligned_pairs, _dynamic) takes the two pair-per-workgroup
+ * kernels of mrp_context_set_posterior_wide_pairs, at 128 threads and on a grid of one workgroup each, so consecutive pairs and
+ * tracebacks reuse one slice; the refusal beyond 2 048 cells with that switch off stays. */
 int mrp_context_set_test_hooks(mrp_context *ctx, int hooks);
 /* Test suite and probes only: the launch census of the device-resident path.  Every kernel the path picks by size class (the prune
  * kernel's instantiations by chain mode, the prune-back kernel, the cross product + emission plans, the two-kernel cross product, the
@@ -507,8 +509,9 @@ int mrp_band_diagonals(const int64_t *anchors, int64_t n_anchors, int64_t lx, in
  * on: such a pair is aligned by the pair-per-workgroup kernel, up to MRP_WIDE_MAX_WIDTH / MRP_WIDE_MAX_CELLS.
  * Honoured by every entry that takes the context and scores pairs: mrp_forward_probabilities, mrp_allele_read_supports,
  * mrp_partition_reads_by_haplotype, mrp_phase_variants_from_tagged_reads, mrp_phase_string_chunks(_with_filtered),
- * mrp_haplotag_aligned_chunks, mrp_phase_aligned_chunks(_with_filtered, _with_records).  NOT extended to
- * mrp_posterior_aligned_pairs, which refuses a pair beyond 2 048 cells whatever this setting. */
+ * mrp_haplotag_aligned_chunks, mrp_phase_aligned_chunks(_with_filtered, _with_records).  NOT read by
+ * mrp_posterior_aligned_pairs(_dynamic), which have a switch of their own for their own kernels, mrp_context_set_posterior_wide_pairs
+ * (below): with that one off they refuse a pair beyond 2 048 cells whatever this setting. */
 int mrp_context_set_wide_pairs(mrp_context *ctx, int on);
 /* pairs / dp cells the wide kernel has taken on this context since it was created (either pointer may be NULL) */
 int mrp_context_wide_pair_count(mrp_context *ctx, int64_t *pairs_out, int64_t *cells_out);
@@ -566,9 +569,11 @@ int mrp_forward_probabilities(mrp_context *ctx, const mrp_pair_hmm *models, int3
  * (stList_reverse, :1109-1111): a caller who wants that order walks a pair's range backwards.
  *
  * Out of scope: getPosteriorProbsWithBandingSplittingAlignmentsByLargeGaps and getSplitPoints (:913-1040; a caller passes each
- * sub-region as a pair of its own with its ragged flags), dynamicAnchorExpansion (band_constructDynamic),
- * diagonalCalculationExpectations (:683-696), run-length emissions, reweightAlignedPairs, leftShiftAlignment and POA construction,
- * pairs whose widest diagonal exceeds 2 048 cells, and any leg of the benchmark. */
+ * sub-region as a pair of its own with its ragged flags; with splitMatrixBiggerThanThis = 250 M cells, as shipped, a region is split
+ * only beyond 15 811 symbols on a side), cropping the reference, diagonalCalculationExpectations (:683-696), run-length emissions,
+ * reweightAlignedPairs, the MEA alignment, leftShiftAlignment and POA construction, and any leg of the benchmark.
+ * dynamicAnchorExpansion (band_constructDynamic) is mrp_posterior_aligned_pairs_dynamic; pairs whose widest diagonal exceeds 2 048
+ * cells run once mrp_context_set_posterior_wide_pairs is on (both below). */
 typedef struct mrp_posterior_options {
     double  threshold;                    /* in (0, 1]; PairwiseAlignmentParameters.threshold (reference default 0.01) */
     int64_t expansion;                    /* diagonalExpansion: even, >= 0 (default 20) */
@@ -605,8 +610,9 @@ int mrp_posterior_tracebacks(const int64_t *anchors, int64_t n_anchors, int64_t 
  *   Errors, in this order; on an error nothing is written.  MRP_ERR_ARG: NULL arguments; reserved != 0; a threshold outside (0, 1]
  * (0 would return every cell of the band and is refused with a message that says so); an odd or negative expansion; the preconditions
  * of :714-718; gap outputs that do not match with_gaps; an offset outside the pool; a model index >= n_models; invalid anchors, as
- * mrp_band_diagonals rejects them.  MRP_ERR_UNSUPPORTED: a pair whose widest diagonal exceeds 2 048 cells (wide pairs,
- * mrp_context_set_wide_pairs, are NOT extended to this entry); a single pair whose forward diagonals exceed the workspace (the message
+ * mrp_band_diagonals rejects them.  MRP_ERR_UNSUPPORTED: a pair whose widest diagonal exceeds 2 048 cells (mrp_context_set_wide_pairs
+ * does not reach this entry; with mrp_context_set_posterior_wide_pairs on, below, only beyond MRP_WIDE_MAX_WIDTH; a NULL context
+ * counts as off); a single pair whose forward diagonals exceed the workspace (the message
  * names the limit) or whose band holds 2^31 cells or more.  MRP_ERR_NO_DEVICE for a NULL context.  stats may be NULL: pairs_wave = the pairs that ran, cells, kernel_ms = the
  * forward and the traceback kernels (mrp_context_last_posterior has them apart), total_ms. */
 int mrp_posterior_aligned_pairs(mrp_context *ctx, const mrp_pair_hmm *models, int32_t n_models, int64_t n_pairs, const uint8_t *pool,
@@ -615,6 +621,41 @@ int mrp_posterior_aligned_pairs(mrp_context *ctx, const mrp_pair_hmm *models, in
                                 mrp_posterior_pairs *match_out, mrp_posterior_pairs *gap_x_out, mrp_posterior_pairs *gap_y_out,
                                 double *total_out /* [n_pairs], may be NULL */, mrp_pairhmm_stats *stats);
 void mrp_posterior_pairs_free(mrp_posterior_pairs *p); /* frees the five arrays and zeroes *p; NULL is fine */
+/* ---- the dynamic anchor band: band_constructDynamic (pairwiseAligner.c:120-173), what getPosteriorProbsWithBanding builds when
+ * PairwiseAlignmentParameters.dynamicAnchorExpansion is set (:726), as every shipped parameter file has it.  An anchor is (x, y,
+ * expansion): anchors as everywhere (n_anchors pairs), anchor_expansion a parallel array with one int64 per anchor (NULL with no
+ * anchors).  The stretch of diagonals that ends at anchor i is bounded with anchor i's expansion; the stretch behind the last anchor keeps
+ * the last anchor's; a pair without anchors has expansion 0, which still is its whole matrix.  With every expansion equal to e the band
+ * is mrp_band_diagonals' for e.  MRP_ERR_ARG where the reference asserts: the anchor checks of mrp_band_diagonals, and an odd or negative
+ * expansion (:157-158).  Host only, no device; each function is its sibling above with anchor_expansion in the scalar's place. */
+int mrp_band_diagonals_dynamic(const int64_t *anchors, int64_t n_anchors, int64_t lx, int64_t ly, const int64_t *anchor_expansion,
+                               int32_t *xmy_l, int32_t *xmy_r);
+int mrp_pair_diagonal_width_dynamic(const int64_t *anchors, int64_t n_anchors, int64_t lx, int64_t ly, const int64_t *anchor_expansion,
+                                    int32_t *width_out, int64_t *cells_out);
+/* mrp_posterior_tracebacks over the dynamic band.  The width rule (:748, at most diagonalExpansion * 2 + 1 cells) reads
+ * p->diagonalExpansion in dynamic mode too, so it keeps reading opt->expansion here, and opt->expansion keeps its checks. */
+int mrp_posterior_tracebacks_dynamic(const int64_t *anchors, const int64_t *anchor_expansion, int64_t n_anchors, int64_t lx, int64_t ly,
+                                     const mrp_posterior_options *opt, int64_t *triples_out, int64_t capacity, int64_t *n_out);
+/* mrp_posterior_aligned_pairs over the dynamic band: anchor_expansion[k] belongs to the anchor (anchors[2k], anchors[2k + 1]), so pair
+ * i's expansions are anchor_expansion[anchor_off[i] .. anchor_off[i + 1]).  Everything else -- outputs, order, groups, workspace,
+ * stats, the order of the errors -- is that entry's; anchors without anchor_expansion, or an odd or negative value in it, are
+ * MRP_ERR_ARG where that entry reports invalid anchors.  total_out is bit for bit the forward value over the same band. */
+int mrp_posterior_aligned_pairs_dynamic(mrp_context *ctx, const mrp_pair_hmm *models, int32_t n_models, int64_t n_pairs, const uint8_t *pool,
+                                        int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len, const int64_t *y_off,
+                                        const int32_t *y_len, const uint8_t *model_index, const int64_t *anchor_off, const int64_t *anchors,
+                                        const int64_t *anchor_expansion, const mrp_posterior_options *opt, mrp_posterior_pairs *match_out,
+                                        mrp_posterior_pairs *gap_x_out, mrp_posterior_pairs *gap_y_out,
+                                        double *total_out /* [n_pairs], may be NULL */, mrp_pairhmm_stats *stats);
+/* Posterior wide pairs.  off (default, and for a NULL context): both posterior entries refuse a pair whose widest diagonal exceeds
+ * 2 048 cells.  on: such a pair runs on two kernels of its own, a pair per workgroup forward and a (pair, traceback) per workgroup
+ * backward, bit-identical to the pair-per-wave ones; pairs of up to 2 048 cells keep their kernels and launch classes,
+ * and a call without such a pair is what it is with the switch off.  Refusals that remain (MRP_ERR_UNSUPPORTED, before anything is
+ * launched): a diagonal beyond MRP_WIDE_MAX_WIDTH cells; 2^31 band cells or more; forward diagonals (24 B per band cell) beyond the
+ * posterior workspace.  The traceback kernel keeps 88 B per cell of the launch's widest diagonal and workgroup in a second workspace of
+ * at most 256 MB.  Separate from mrp_context_set_wide_pairs, which these entries do not read. */
+int mrp_context_set_posterior_wide_pairs(mrp_context *ctx, int on);
+/* pairs / band cells those two kernels have taken on this context since it was created (either pointer may be NULL) */
+int mrp_context_posterior_wide_count(mrp_context *ctx, int64_t *pairs_out, int64_t *cells_out);
 /* Bytes of forward diagonals the pairs of one group of mrp_posterior_aligned_pairs may keep together on the device (24 B per band
  * cell).  Default: 1 GiB, 4.4e7 band cells -- four thousand 100 x 100 matrices, or three hundred 2 kb pairs in a band of 37.  A pair
  * is a wave and its steps are latency bound, so a group should hold enough pairs to fill the device: groups run one after the other

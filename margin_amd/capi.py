@@ -53,6 +53,8 @@ EXPORTED_SYMBOLS = [
     "mrp_close_contig", "mrp_close_contigs", "mrp_contig_out_clear",
     "mrp_posterior_tracebacks", "mrp_posterior_aligned_pairs", "mrp_posterior_pairs_free", "mrp_context_set_posterior_workspace",
     "mrp_context_last_posterior",
+    "mrp_band_diagonals_dynamic", "mrp_pair_diagonal_width_dynamic", "mrp_posterior_tracebacks_dynamic", "mrp_posterior_aligned_pairs_dynamic",
+    "mrp_context_set_posterior_wide_pairs", "mrp_context_posterior_wide_count",
 ]
 
 
@@ -504,6 +506,13 @@ def load():
     L.mrp_posterior_pairs_free.restype = None
     L.mrp_context_set_posterior_workspace.argtypes = [vp, i64]
     L.mrp_context_last_posterior.argtypes = [vp, P(PosteriorStats)]
+    L.mrp_band_diagonals_dynamic.argtypes = [vp, i64, i64, i64, vp, vp, vp]
+    L.mrp_pair_diagonal_width_dynamic.argtypes = [vp, i64, i64, i64, vp, P(i32), P(i64)]
+    L.mrp_posterior_tracebacks_dynamic.argtypes = [vp, vp, i64, i64, i64, P(PosteriorOptions), vp, i64, P(i64)]
+    L.mrp_posterior_aligned_pairs_dynamic.argtypes = [vp, vp, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, P(PosteriorOptions), P(PosteriorPairs),
+                                                      P(PosteriorPairs), P(PosteriorPairs), vp, vp]
+    L.mrp_context_set_posterior_wide_pairs.argtypes = [vp, C.c_int]
+    L.mrp_context_posterior_wide_count.argtypes = [vp, P(i64), P(i64)]
     L.mrp_allele_read_supports.argtypes = [vp, P(PairHmm), P(PairHmm), i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, P(PairHmmStats)]
     L.mrp_partition_reads_by_haplotype.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, i64, vp, vp, vp, P(PairHmmStats)]
     L.mrp_phase_variants_from_tagged_reads.argtypes = [vp, P(PairHmm), P(PairHmm), P(HaptagSites), i64, vp, vp, i64, i64, vp, vp, vp, P(PairHmmStats)]
@@ -603,7 +612,8 @@ class Context:
     def set_test_hooks(self, hooks: int):
         """test suite only: bit 0 fault injection, bit 1 separate cross product / emission kernels, bit 2 one refused device
         allocation, bit 3 general prune chain, bit 4 one array entry per cell on unit levels, bit 5 no level is launched deferred, bit 6 the
-        wide pair-HMM kernel's grid is one workgroup (include/margin_rphmm.h)"""
+        wide pair-HMM kernel's grid is one workgroup, bit 7 every pair of a posterior call takes the pair-per-workgroup kernels at 128 threads on a
+        grid of one workgroup (include/margin_rphmm.h)"""
         _check(load().mrp_context_set_test_hooks(self.h, hooks))
 
     def launch_census(self, reset: bool = False) -> dict:
@@ -622,6 +632,16 @@ class Context:
         st = PosteriorStats()
         _check(load().mrp_context_last_posterior(self.h, C.byref(st)))
         return st
+
+    def set_posterior_wide_pairs(self, on):
+        """mrp_context_set_posterior_wide_pairs: the posterior entries run a pair whose widest diagonal exceeds 2 048 cells (up to WIDE_MAX_WIDTH)"""
+        _check(load().mrp_context_set_posterior_wide_pairs(self.h, int(bool(on))))
+
+    def posterior_wide_count(self):
+        """mrp_context_posterior_wide_count -> (pairs, band cells) the posterior entries' pair-per-workgroup kernels have taken on this context"""
+        pairs, cells = C.c_int64(), C.c_int64()
+        _check(load().mrp_context_posterior_wide_count(self.h, C.byref(pairs), C.byref(cells)))
+        return pairs.value, cells.value
 
     def set_wide_pairs(self, on):
         """mrp_context_set_wide_pairs: pairs whose widest diagonal exceeds 2 048 cells are aligned, not refused (up to WIDE_MAX_WIDTH / WIDE_MAX_CELLS)"""
@@ -1298,12 +1318,50 @@ def posterior_tracebacks(anchors, lx: int, ly: int, options: PosteriorOptions) -
     return out[:n.value].copy()
 
 
+def _anchor_arrays(anchors, anchor_expansion):
+    a = np.ascontiguousarray(np.asarray(anchors if anchors is not None else [], dtype=np.int64).reshape(-1, 2))
+    e = np.ascontiguousarray(np.asarray(anchor_expansion if anchor_expansion is not None else [], dtype=np.int64).reshape(-1))
+    if len(a) != len(e):
+        raise ValueError("one expansion per anchor")
+    return a, e
+
+
+def band_diagonals_dynamic(anchors, lx: int, ly: int, anchor_expansion):
+    """mrp_band_diagonals_dynamic (host only): band_constructDynamic, impl/pairwiseAligner.c:120-173, one expansion per anchor"""
+    a, e = _anchor_arrays(anchors, anchor_expansion)
+    lo, hi = np.zeros(lx + ly + 1, dtype=np.int32), np.zeros(lx + ly + 1, dtype=np.int32)
+    _check(load().mrp_band_diagonals_dynamic(a.ctypes.data if len(a) else None, len(a), lx, ly, e.ctypes.data if len(e) else None, lo.ctypes.data, hi.ctypes.data))
+    return lo, hi
+
+
+def pair_diagonal_width_dynamic(anchors, lx: int, ly: int, anchor_expansion):
+    """mrp_pair_diagonal_width_dynamic (host only) -> (cells on the widest diagonal, cells inside the dynamic band)"""
+    a, e = _anchor_arrays(anchors, anchor_expansion)
+    width, cells = C.c_int32(), C.c_int64()
+    _check(load().mrp_pair_diagonal_width_dynamic(a.ctypes.data if len(a) else None, len(a), lx, ly, e.ctypes.data if len(e) else None, C.byref(width),
+                                                  C.byref(cells)))
+    return width.value, cells.value
+
+
+def posterior_tracebacks_dynamic(anchors, anchor_expansion, lx: int, ly: int, options: PosteriorOptions) -> np.ndarray:
+    """mrp_posterior_tracebacks_dynamic (host only): posterior_tracebacks over the dynamic band; options.expansion stays the scalar of :748"""
+    a, e = _anchor_arrays(anchors, anchor_expansion)
+    out = np.zeros((lx + ly + 1, 3), dtype=np.int64)
+    n = C.c_int64()
+    _check(load().mrp_posterior_tracebacks_dynamic(a.ctypes.data if len(a) else None, e.ctypes.data if len(e) else None, len(a), lx, ly, C.byref(options),
+                                                   out.ctypes.data, len(out), C.byref(n)))
+    return out[:n.value].copy()
+
+
 def posterior_aligned_pairs(ctx, models, pool, x_off, x_len, y_off, y_len, model_index=None, anchor_off=None, anchors=None,
-                            options: PosteriorOptions = None, want_total: bool = True):
+                            options: PosteriorOptions = None, want_total: bool = True, anchor_expansion=None, dynamic: bool = False):
     """getPosteriorProbsWithBanding for a batch of pairs (mrp_posterior_aligned_pairs) -> (match, gap_x, gap_y, total, PairHmmStats):
     each list a dict of first / x / y / weight / log_posterior in the reference's order of generation, gap_x and gap_y None without
-    options.with_gaps.  ctx may be None (the checks that need no device)."""
+    options.with_gaps.  ctx may be None (the checks that need no device).  dynamic (or anchor_expansion given):
+    mrp_posterior_aligned_pairs_dynamic, the band of band_constructDynamic with one expansion per anchor."""
     options = options if options is not None else PosteriorOptions()
+    dynamic = dynamic or anchor_expansion is not None
+    ae = _opt(anchor_expansion if anchor_expansion is not None else [], np.int64)
     arr = (PairHmm * len(models))(*models)
     pool = np.ascontiguousarray(pool, dtype=np.uint8)
     xo, xl, yo, yl = _opt(x_off, np.int64), _opt(x_len, np.int32), _opt(y_off, np.int64), _opt(y_len, np.int32)
@@ -1313,10 +1371,14 @@ def posterior_aligned_pairs(ctx, models, pool, x_off, x_len, y_off, y_len, model
     st = PairHmmStats()
     lists = [PosteriorPairs() for _ in range(3 if options.with_gaps else 1)]
     ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
-    _check(load().mrp_posterior_aligned_pairs(ctx.h if ctx is not None else None, C.cast(arr, C.c_void_p), len(models), n, ptr(pool), pool.size, ptr(xo), ptr(xl),
-                                              ptr(yo), ptr(yl), ptr(mi), None if ao is None else ao.ctypes.data, ptr(an), C.byref(options), C.byref(lists[0]),
-                                              C.byref(lists[1]) if options.with_gaps else None, C.byref(lists[2]) if options.with_gaps else None,
-                                              ptr(total), C.byref(st)))
+    front = [ctx.h if ctx is not None else None, C.cast(arr, C.c_void_p), len(models), n, ptr(pool), pool.size, ptr(xo), ptr(xl), ptr(yo), ptr(yl), ptr(mi),
+             None if ao is None else ao.ctypes.data, ptr(an)]
+    back = [C.byref(options), C.byref(lists[0]), C.byref(lists[1]) if options.with_gaps else None, C.byref(lists[2]) if options.with_gaps else None,
+            ptr(total), C.byref(st)]
+    if dynamic:  # anchor_expansion behind anchors
+        _check(load().mrp_posterior_aligned_pairs_dynamic(*front, ptr(ae), *back))
+    else:
+        _check(load().mrp_posterior_aligned_pairs(*front, *back))
     out = [l.to_numpy(n) for l in lists]
     for l in lists:
         load().mrp_posterior_pairs_free(C.byref(l))

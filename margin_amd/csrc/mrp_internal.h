@@ -385,6 +385,8 @@ struct mrp_context {
      * page-locked memory takes milliseconds and synchronizes the device (owned here, managed by mrp_engine.cpp) */
     std::vector<struct mrp_engine_level_state *> spare_levels;
     std::vector<struct mrp_batch *> spare_batches;
+    int posterior_wide_pairs = 0; /* mrp_context_set_posterior_wide_pairs: the posterior entries run pairs beyond 2 048 cells on their pair-per-workgroup kernels */
+    int64_t posterior_wide_count = 0, posterior_wide_cells = 0; /* what those kernels have taken on this context (mrp_context_posterior_wide_count) */
 };
 
 struct mrp_chunk {

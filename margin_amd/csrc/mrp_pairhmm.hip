@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/margin_rphmm.h"
+#include "mrp_band.h"
 #include "mrp_internal.h"
 #include "mrp_pairhmm.h"
 #include "mrp_pairhmm_dev.h" /* St, phm_log_add, phm_cell, phm_dot */
@@ -381,52 +382,10 @@ constexpr int PHM_WIDE_THREADS = 1024; /* workgroup of phm_wide_kernel (measured
 
 /* ---------------- host ---------------- */
 
-/* band_construct in closed form.  Between two consecutive anchor points P = (px, py) and N = (nx, ny) (matrix
- * coordinates; the first P is (0, 0), the last N is (lx, ly)) the reference bounds the diagonals xay in (px + py,
- * nx + ny] by xL = px - e/2, yL = ny + e/2, xU = nx + e/2, yU = py - e/2 (clamped to the matrix), :218-221; on such a
- * diagonal band_setCurrentDiagonal (:96-114) yields the smallest xmy of the right parity with xmy >= xL - yL, x >= xL,
- * y <= yL and the largest with xmy <= (xU - yU rounded UP to the parity), x <= xU, y >= yU. */
+/* band_construct in closed form (mrp_band.h, which also states band_constructDynamic) */
 int band_closed_form(const int64_t *anchors, int64_t n_anchors, int64_t lx, int64_t ly, int64_t expansion, int32_t *L, int32_t *R,
                      int64_t *cells, int *max_width) {
-    if (lx < 0 || ly < 0 || expansion < 0 || expansion % 2 != 0) return MRP_ERR_ARG;
-    const int64_t e2 = expansion / 2;
-    auto clamp = [](int64_t z, int64_t hi) { return z < 0 ? (int64_t) 0 : (z > hi ? hi : z); };
-    L[0] = 0;
-    R[0] = 0;
-    int64_t total = 1;
-    int mw = 1;
-    int64_t px = 0, py = 0, ai = 0;
-    while (px + py < lx + ly) {
-        int64_t nx = lx, ny = ly;
-        if (ai < n_anchors) {
-            nx = anchors[2 * ai] + 1;
-            ny = anchors[2 * ai + 1] + 1;
-            ai++;
-            if (!(nx > px && ny > py && nx <= lx && ny <= ly)) return MRP_ERR_ARG; /* asserts :206-211 */
-        }
-        const int64_t xL = clamp(px - e2, lx), yL = clamp(ny + e2, ly), xU = clamp(nx + e2, lx), yU = clamp(py - e2, ly);
-        for (int64_t d = px + py + 1; d <= nx + ny; d++) {
-            int64_t l = xL - yL, r = xU - yU;
-            if ((d + l) % 2 != 0) l++;
-            if ((d + r) % 2 != 0) r++;
-            l = std::max(l, std::max(2 * xL - d, d - 2 * yL));
-            r = std::min(r, std::min(2 * xU - d, d - 2 * yU));
-            if (l > r) return MRP_ERR_ARG; /* diagonal_construct :22-27 throws */
-            L[d] = (int32_t) l;
-            R[d] = (int32_t) r;
-            const int64_t w = (r - l) / 2 + 1;
-            total += w;
-            if (w > mw) mw = (int) w;
-        }
-        px = nx;
-        py = ny;
-    }
-    /* the reference ignores anchors left over once (lx, ly) has been reached only if there are none: an anchor list that
-     * runs past the end fails its asserts, an anchor exactly at (lx - 1, ly - 1) followed by nothing is fine */
-    if (ai < n_anchors) return MRP_ERR_ARG;
-    if (cells) *cells = total;
-    if (max_width) *max_width = mw;
-    return MRP_OK;
+    return band_closed_form_any(anchors, nullptr, false, n_anchors, lx, ly, expansion, L, R, cells, max_width);
 }
 
 void model_to_device(const mrp_pair_hmm &m, int ragged_left, int ragged_right, PhmModelDev &d) {

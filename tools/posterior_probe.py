@@ -2,7 +2,10 @@
 """Timing probe of mrp_posterior_aligned_pairs: kernel time (HIP events) of its forward and traceback kernels, pairs/s and band cells/s
 of each, the bytes that return per pair, and beside them mrp_forward_probabilities on the same pairs in the same run.
 Two shapes: --short N pairs of 100 x ~97 with the reference's default parameters (one traceback each), --long N pairs of
---long-len x --long-len anchored on the diagonal every 16 symbols (a band of 37 cells; a traceback every 1 000 diagonals)."""
+--long-len x --long-len anchored on the diagonal every 16 symbols (a band of 37 cells; a traceback every 1 000 diagonals).
+--wide adds a third: unanchored pairs of --wide-len x --wide-len (2 500: a widest diagonal of 2 501 cells, one traceback over the whole
+matrix), as many as the default posterior workspace holds, on the pair-per-workgroup kernels (posterior wide pairs on), with
+mrp_forward_probabilities' pair-per-workgroup kernel (wide pairs on) beside them."""
 import argparse
 import os
 import sys
@@ -33,6 +36,20 @@ def long_pairs(n, length, seed):
         hit = rng.random(length) < 0.15  # substitutions only: the diagonal anchors stay valid
         sy[hit] = rng.integers(0, 4, size=int(hit.sum()))
         pairs.append((sx, sy, anchors))
+    return pairs
+
+
+def wide_pairs(length, seed):
+    """as many as fit MRP_POSTERIOR_DEFAULT_WORKSPACE together (24 B per cell of the whole matrix): one group, one launch"""
+    n = max(1, (1 << 30) // (24 * (length + 1) ** 2))
+    rng = np.random.default_rng(seed)
+    pairs = []
+    for _ in range(n):
+        sx = synth.random_sequence(rng, length)
+        sy = sx.copy()
+        hit = rng.random(length) < 0.15  # substitutions only: every pair has the same cells
+        sy[hit] = rng.integers(0, 4, size=int(hit.sum()))
+        pairs.append((sx, sy, []))
     return pairs
 
 
@@ -75,6 +92,8 @@ def main():
     ap.add_argument("--short", type=int, default=4096)
     ap.add_argument("--long", type=int, default=256)
     ap.add_argument("--long-len", type=int, default=2000)
+    ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--wide-len", type=int, default=2500)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--with-gaps", type=int, default=0)
     args = ap.parse_args()
@@ -85,6 +104,13 @@ def main():
             probe(ctx, models, "short", short_pairs(args.short, 5), opt, args.repeat)
         if args.long:
             probe(ctx, models, "long", long_pairs(args.long, args.long_len, 6), opt, args.repeat)
+        if args.wide:
+            ctx.set_posterior_wide_pairs(True)
+            ctx.set_wide_pairs(True)  # the yardstick's own switch
+            before = ctx.posterior_wide_count()
+            probe(ctx, models, "wide", wide_pairs(args.wide_len, 7), opt, args.repeat)
+            after = ctx.posterior_wide_count()
+            print(f"  the pair-per-workgroup kernels took {after[0] - before[0]} pairs, {after[1] - before[1]} band cells over {args.repeat + 1} runs", flush=True)
 
 
 if __name__ == "__main__":
