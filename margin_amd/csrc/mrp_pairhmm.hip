@@ -22,7 +22,7 @@
  *   phm_wave_kernel   a pair per WAVE for everything else (long strings, anchored bands): x+y diagonal by diagonal, a
  *                     lane per cell of the diagonal, the last two diagonals in LDS -- up to 2 048 cells on a diagonal.
  *   phm_wide_kernel   a pair per WORKGROUP for the pairs beyond that, when the caller has turned wide pairs on (else they are
- *                     refused): the same walk with the diagonals in a device workspace.
+ *                     refused): the diagonals in a device workspace.  Both are the walk of mrp_pairhmm_walk.h.
  *
  * Bound: fp64 VALU issue (six logAdd per cell); the kernels move ~0.1 B per flop.
  */
@@ -40,7 +40,7 @@
 #include "mrp_band.h"
 #include "mrp_internal.h"
 #include "mrp_pairhmm.h"
-#include "mrp_pairhmm_dev.h" /* St, phm_log_add, phm_cell, phm_dot */
+#include "mrp_pairhmm_walk.h" /* St, phm_log_add, phm_dot; the walk of the two diagonal kernels */
 #include "mrp_wave.h"
 #include "rphmm_host.h"
 
@@ -225,154 +225,47 @@ __global__ void __launch_bounds__(256) phm_lane_kernel(const PhmLanePair *__rest
     }
 }
 
+/* A pair per WAVE (a workgroup of one wave): the walk of mrp_pairhmm_walk.h with the three live diagonals in LDS, 3 diagonals x W
+ * cells x 3 states, then the total on the last diagonal. */
 __global__ void __launch_bounds__(PHM_WAVE) phm_wave_kernel(const PhmPair *__restrict__ pairs, int64_t n_pairs, const uint8_t *__restrict__ pool,
                                                               const PhmModelDev *__restrict__ models, const int32_t *__restrict__ band, int W,
                                                               double *__restrict__ out) {
-    extern __shared__ double phm_diag[]; /* 3 diagonals x W cells x 3 states */
-    const int lane = threadIdx.x;
+    extern __shared__ double phm_diag[];
     for (int64_t pi = blockIdx.x; pi < n_pairs; pi += gridDim.x) {
         const PhmPair p = pairs[pi];
-        const int lx = p.lx, ly = p.ly, n = lx + ly;
+        const int n = p.lx + p.ly;
         if (n == 0) {
-            if (lane == 0) out[p.out] = 0.0;
+            if (threadIdx.x == 0) out[p.out] = 0.0; /* :860-862 */
             continue;
         }
-        const PhmModelDev *__restrict__ M = models + p.model;
-        double t[9];
-#pragma unroll
-        for (int i = 0; i < 9; i++) t[i] = M->t[i];
-        const uint8_t *__restrict__ sx = pool + p.x_off;
-        const uint8_t *__restrict__ sy = pool + p.y_off;
-        double *d0 = phm_diag, *d1 = phm_diag + 3 * W, *d2 = phm_diag + 6 * W; /* being written, xay - 1, xay - 2 */
-        auto limits = [&](int d, int &l, int &r) {
-            if (p.band_off >= 0) {
-                l = band[2 * (p.band_off + d)];
-                r = band[2 * (p.band_off + d) + 1];
-            } else {
-                const int xlo = d - ly > 0 ? d - ly : 0, xhi = d < lx ? d : lx;
-                l = 2 * xlo - d;
-                r = 2 * xhi - d;
-            }
-        };
-        int l1, r1, l2 = 1, r2 = 0;
-        limits(0, l1, r1);
-        for (int i = lane; i <= (r1 - l1) / 2; i += PHM_WAVE) {
-            d1[3 * i] = M->start[0];
-            d1[3 * i + 1] = M->start[1];
-            d1[3 * i + 2] = M->start[2];
-        }
-        __syncthreads();
-        for (int d = 1; d <= n; d++) {
-            int l, r;
-            limits(d, l, r);
-            const int width = (r - l) / 2 + 1;
-            for (int i = lane; i < width; i += PHM_WAVE) {
-                const int xmy = l + 2 * i;
-                const int x = (d + xmy) >> 1, y = (d - xmy) >> 1;
-                St lower{PHM_NEG, PHM_NEG, PHM_NEG}, middle = lower, upper = lower;
-                if (xmy - 1 >= l1 && xmy - 1 <= r1) { const double *c = d1 + 3 * ((xmy - 1 - l1) >> 1); lower = St{c[0], c[1], c[2]}; }
-                if (xmy + 1 >= l1 && xmy + 1 <= r1) { const double *c = d1 + 3 * ((xmy + 1 - l1) >> 1); upper = St{c[0], c[1], c[2]}; }
-                if (xmy >= l2 && xmy <= r2) { const double *c = d2 + 3 * ((xmy - l2) >> 1); middle = St{c[0], c[1], c[2]}; }
-                int cx = 4, cy = 4;
-                if (x > 0) { cx = sx[x - 1]; cx = cx > 4 ? 4 : cx; }
-                if (y > 0) { cy = sy[y - 1]; cy = cy > 4 ? 4 : cy; }
-                const double eY = M->ey[cy];
-                const PhmRowT ty{eY + t[4], eY + t[6], eY + t[8]};
-                const St cur = phm_cell(lower, middle, upper, t, M->ex[cx], M->em[cx * 5 + cy], ty);
-                d0[3 * i] = cur.m;
-                d0[3 * i + 1] = cur.x;
-                d0[3 * i + 2] = cur.y;
-            }
-            __syncthreads();
-            double *tmp = d2;
-            d2 = d1; d1 = d0; d0 = tmp;
-            l2 = l1; r2 = r1; l1 = l; r1 = r;
-        }
-        /* diagonalCalculationTotalProbability on the last diagonal (:578-596, no diagonal beyond it): dpDiagonal_dotProduct */
-        if (lane == 0) {
-            const double e_end[3] = {M->end[0], M->end[1], M->end[2]};
-            double tot = PHM_NEG;
-            for (int i = 0; i <= (r1 - l1) / 2; i++) tot = phm_log_add(tot, phm_dot(St{d1[3 * i], d1[3 * i + 1], d1[3 * i + 2]}, e_end));
-            out[p.out] = tot;
-        }
-        __syncthreads();
+        const PhmPairCtx c = phm_pair_ctx(models, p.model, pool, p.x_off, p.y_off);
+        PhmDiagonals<PhmInterleaved, PHM_KEEP_NONE> diag{PhmInterleaved::at(phm_diag, W, 0), PhmInterleaved::at(phm_diag, W, 1), PhmInterleaved::at(phm_diag, W, 2)};
+        const PhmBandOrMatrixLimits limits{band, p.band_off, p.lx, p.ly};
+        phm_forward_walk<PhmTeam<PHM_WAVE, false>>(n, diag, limits, c);
+        if (threadIdx.x == 0) out[p.out] = phm_last_diagonal_total(diag.d1, (diag.r1 - diag.l1) / 2, c.M);
+        __syncthreads(); /* the next pair starts over in the diagonals that thread 0 has just read */
     }
 }
 
-/* A pair per WORKGROUP, for the pairs whose widest diagonal does not fit the LDS of phm_wave_kernel (wide pairs on): the same walk,
- * x+y diagonal by diagonal with the threads striding over the diagonal's cells, the same limits(), the same phm_cell / phm_log_add /
- * phm_dot -- a cell's value does not depend on which thread computes it.  The three live diagonals lie in the workgroup's slice of a
- * device workspace, ws[workgroup][diagonal][state][W] (W = the widest diagonal of the launch; an array per state, so a wave's loads
- * and stores are consecutive 8-byte accesses), and rotate by pointer.  A workgroup reads only what it wrote itself and runs on one CU:
- * one __syncthreads() between diagonals is the only synchronisation.  The next pair of the grid-stride loop reuses the slice; every
- * cell read lies inside [l1, r1] / [l2, r2] of the pair's own diagonals, which that pair wrote. */
+/* A pair per WORKGROUP, for the pairs whose widest diagonal does not fit the LDS of phm_wave_kernel (wide pairs on): the same walk by
+ * T threads.  The three live diagonals lie in the workgroup's slice of a device workspace, ws[workgroup][diagonal][state][W] (W = the
+ * widest diagonal of the launch), and rotate by pointer.  A workgroup reads only what it wrote itself and runs on one CU: one
+ * __syncthreads() between diagonals is the only synchronisation.  The next pair of the grid-stride loop reuses the slice; every
+ * cell read lies inside [l1, r1] / [l2, r2] of the pair's own diagonals, which that pair wrote.  (No pair with an empty matrix
+ * reaches this kernel; the walk would give it its start cell's total.) */
 template <int T>
 __global__ void __launch_bounds__(T) phm_wide_kernel(const PhmPair *__restrict__ pairs, int64_t n_pairs, const uint8_t *__restrict__ pool,
                                                      const PhmModelDev *__restrict__ models, const int32_t *__restrict__ band, int W, double *ws,
                                                      double *__restrict__ out) {
     double *slice = ws + (size_t) blockIdx.x * 9 * (size_t) W;
-    const int tid = threadIdx.x;
     for (int64_t pi = blockIdx.x; pi < n_pairs; pi += gridDim.x) {
         const PhmPair p = pairs[pi];
-        const int lx = p.lx, ly = p.ly, n = lx + ly;
-        const PhmModelDev *__restrict__ M = models + p.model;
-        double t[9];
-#pragma unroll
-        for (int i = 0; i < 9; i++) t[i] = M->t[i];
-        const uint8_t *__restrict__ sx = pool + p.x_off;
-        const uint8_t *__restrict__ sy = pool + p.y_off;
-        double *d0 = slice, *d1 = slice + 3 * (size_t) W, *d2 = slice + 6 * (size_t) W; /* being written, xay - 1, xay - 2 */
-        auto limits = [&](int d, int &l, int &r) {
-            if (p.band_off >= 0) {
-                l = band[2 * (p.band_off + d)];
-                r = band[2 * (p.band_off + d) + 1];
-            } else {
-                const int xlo = d - ly > 0 ? d - ly : 0, xhi = d < lx ? d : lx;
-                l = 2 * xlo - d;
-                r = 2 * xhi - d;
-            }
-        };
-        int l1, r1, l2 = 1, r2 = 0;
-        limits(0, l1, r1);
-        for (int i = tid; i <= (r1 - l1) / 2; i += T) {
-            d1[i] = M->start[0];
-            d1[W + i] = M->start[1];
-            d1[2 * W + i] = M->start[2];
-        }
-        __syncthreads();
-        for (int d = 1; d <= n; d++) {
-            int l, r;
-            limits(d, l, r);
-            const int width = (r - l) / 2 + 1;
-            for (int i = tid; i < width; i += T) {
-                const int xmy = l + 2 * i;
-                const int x = (d + xmy) >> 1, y = (d - xmy) >> 1;
-                St lower{PHM_NEG, PHM_NEG, PHM_NEG}, middle = lower, upper = lower;
-                if (xmy - 1 >= l1 && xmy - 1 <= r1) { const double *c = d1 + ((xmy - 1 - l1) >> 1); lower = St{c[0], c[W], c[2 * W]}; }
-                if (xmy + 1 >= l1 && xmy + 1 <= r1) { const double *c = d1 + ((xmy + 1 - l1) >> 1); upper = St{c[0], c[W], c[2 * W]}; }
-                if (xmy >= l2 && xmy <= r2) { const double *c = d2 + ((xmy - l2) >> 1); middle = St{c[0], c[W], c[2 * W]}; }
-                int cx = 4, cy = 4;
-                if (x > 0) { cx = sx[x - 1]; cx = cx > 4 ? 4 : cx; }
-                if (y > 0) { cy = sy[y - 1]; cy = cy > 4 ? 4 : cy; }
-                const double eY = M->ey[cy];
-                const PhmRowT ty{eY + t[4], eY + t[6], eY + t[8]};
-                const St cur = phm_cell(lower, middle, upper, t, M->ex[cx], M->em[cx * 5 + cy], ty);
-                d0[i] = cur.m;
-                d0[W + i] = cur.x;
-                d0[2 * W + i] = cur.y;
-            }
-            __syncthreads();
-            double *tmp = d2;
-            d2 = d1; d1 = d0; d0 = tmp;
-            l2 = l1; r2 = r1; l1 = l; r1 = r;
-        }
-        /* the total on the last diagonal, serially in index order as phm_wave_kernel does: phm_log_add is not associative */
-        if (tid == 0) {
-            const double e_end[3] = {M->end[0], M->end[1], M->end[2]};
-            double tot = PHM_NEG;
-            for (int i = 0; i <= (r1 - l1) / 2; i++) tot = phm_log_add(tot, phm_dot(St{d1[i], d1[W + i], d1[2 * W + i]}, e_end));
-            out[p.out] = tot;
-        }
+        const PhmPairCtx c = phm_pair_ctx(models, p.model, pool, p.x_off, p.y_off);
+        PhmDiagonals<PhmSlice, PHM_KEEP_NONE> diag{PhmSlice::at(slice, W, 0), PhmSlice::at(slice, W, 1), PhmSlice::at(slice, W, 2)};
+        const int n = p.lx + p.ly;
+        const PhmBandOrMatrixLimits limits{band, p.band_off, p.lx, p.ly};
+        phm_forward_walk<PhmTeam<T, false>>(n, diag, limits, c);
+        if (threadIdx.x == 0) out[p.out] = phm_last_diagonal_total(diag.d1, (diag.r1 - diag.l1) / 2, c.M);
         __syncthreads();
     }
 }

@@ -1,7 +1,8 @@
 /*
- * mrp_pairhmm_dev.h -- the device arithmetic the pair-HMM kernels share: logAdd, the forward cell, the dot product of a cell.
- * Moved verbatim out of mrp_pairhmm.hip so that mrp_posterior.hip evaluates the very same expressions.  Device code only; every unit
- * that includes it is compiled with -ffp-contract=off.
+ * mrp_pairhmm_dev.h -- the device arithmetic the pair-HMM kernels share: logAdd, the forward cell, the dot product of a cell.  It began
+ * as text taken out of mrp_pairhmm.hip when mrp_posterior.hip needed the very same expressions; the walk over the diagonals and the
+ * cells of a traceback, built on it, are in mrp_pairhmm_walk.h.  Device code only; every unit that includes it is compiled with
+ * -ffp-contract=off.
  */
 #ifndef MRP_PAIRHMM_DEV_H_
 #define MRP_PAIRHMM_DEV_H_
