@@ -468,8 +468,9 @@ double mrp_binomial_coefficient(int64_t n, int64_t k, uint64_t *hi, uint64_t *lo
  * diagonal of 2 048 cells, and -- once wide pairs are on for the context (below) -- one with a pair per workgroup beyond that.
  * The arithmetic is the reference's: fp64 + and * only (logAdd is a cubic interpolation, pairwiseAligner.c:279-299),
  * evaluated without fused multiply-add, so results are bit-identical to a strict IEEE build of the reference.
- * Symbols: 0..3 = A C G T, >= 4 = N (convertNucleotideCharToSymbol, stateMachine.c:25-42).  Nucleotide emissions
- * only; the run-length (repeat count) emissions of margin polish (stateMachine.c:722-753) are out of scope.
+ * Symbols: 0..3 = A C G T, >= 4 = N (convertNucleotideCharToSymbol, stateMachine.c:25-42).  Nucleotide emissions;
+ * the run-length (repeat count) emissions of margin polish (stateMachine.c:716-752) are mrp_forward_probabilities_rle and
+ * mrp_posterior_aligned_pairs_rle (below).  The composites (string chunks, aligned chunks, queues) keep the nucleotide emissions.
  * ------------------------------------------------------------------------------------------------------------- */
 typedef struct mrp_pair_hmm { /* struct _StateMachine3 (stateMachine.c:507-519) + NucleotideEmissions, all in log space */
     double match_continue, match_from_gap_x, match_from_gap_y, gap_open_x, gap_open_y, gap_extend_x, gap_extend_y,
@@ -570,7 +571,7 @@ int mrp_forward_probabilities(mrp_context *ctx, const mrp_pair_hmm *models, int3
  *
  * Out of scope: getPosteriorProbsWithBandingSplittingAlignmentsByLargeGaps and getSplitPoints (:913-1040; a caller passes each
  * sub-region as a pair of its own with its ragged flags; with splitMatrixBiggerThanThis = 250 M cells, as shipped, a region is split
- * only beyond 15 811 symbols on a side), cropping the reference, diagonalCalculationExpectations (:683-696), run-length emissions,
+ * only beyond 15 811 symbols on a side), cropping the reference, diagonalCalculationExpectations (:683-696),
  * reweightAlignedPairs, the MEA alignment, leftShiftAlignment and POA construction, and any leg of the benchmark.
  * dynamicAnchorExpansion (band_constructDynamic) is mrp_posterior_aligned_pairs_dynamic; pairs whose widest diagonal exceeds 2 048
  * cells run once mrp_context_set_posterior_wide_pairs is on (both below). */
@@ -646,6 +647,45 @@ int mrp_posterior_aligned_pairs_dynamic(mrp_context *ctx, const mrp_pair_hmm *mo
                                         const int64_t *anchor_expansion, const mrp_posterior_options *opt, mrp_posterior_pairs *match_out,
                                         mrp_posterior_pairs *gap_x_out, mrp_posterior_pairs *gap_y_out,
                                         double *total_out /* [n_pairs], may be NULL */, mrp_pairhmm_stats *stats);
+/* ---- run-length emissions: rleNucleotideEmissions_construct (stateMachine.c:716-752), what polishParams_finishParsing gives both
+ * read-to-reference state machines when useRepeatCountsInAlignment is set (parser.c:510-524), as every shipped polish parameter file
+ * but one has it.  A symbol carries a repeat count (symbol_addRepeatCount, :124-131): here a byte per symbol in `counts`, an array parallel
+ * to the symbol pool with the same offsets.  The match emission of x against y becomes
+ *     getNucleotideMatchProb(x's base, y's base) + 2.3025 * log_prob[b][count(x)][count(y)],  b = strand ? x's base : 3 - x's base,
+ * an N counting as A (repeatSubMatrix.c:16-29); the gap emissions strip the count and stay (:722-731); the symbol before the first is N
+ * with count 0.  The host takes the product once per table entry, the device adds it: bit for bit the reference's value in a build
+ * without fused multiply-add. */
+typedef struct mrp_repeat_model {
+    int32_t max_repeat;     /* R, exclusive: counts are 0..R-1; RepeatSubMatrix.maximumRepeatLength, 2 <= R <= 256 (the reference: 51) */
+    int32_t strand;         /* 1 or 0, RleNucleotideEmissions.strand */
+    const double *log_prob; /* [4][R][R]: base A..T, underlying count (x), observed count (y); RepeatSubMatrix.logProbabilities in the
+                             * layout of the parameter file's repeatCountLogProbabilities arrays */
+} mrp_repeat_model;
+/* Host only, no device: rleString_construct (rle.c:7-38) followed by the clamp of rleString_constructSymbolString / symbol_addRepeatCount
+ * (stateMachine.c:124-146).  n chars in; a run is a stretch of equal chars ("aA" is two runs, as there); one symbol (mrp_symbols_from_chars' mapping) and one count, min(run
+ * length, max_repeat - 1), per run out; both outputs hold up to n bytes.  Returns the compressed length, -1 for a NULL array with n > 0,
+ * n < 0 or max_repeat outside [2, 256]. */
+int64_t mrp_rle_compress(const char *s, int64_t n, int32_t max_repeat, uint8_t *symbols_out, uint8_t *counts_out);
+/* mrp_forward_probabilities with run-length emissions: repeat[i] belongs to models[i], counts is parallel to pool (pool_bytes bytes).
+ * Honours mrp_context_set_wide_pairs.  Every pair runs on the pair-per-wave kernel (or, wide, the pair-per-workgroup one): stats counts
+ * none in pairs_lane.  MRP_ERR_ARG, before the context is looked at and with nothing written: what mrp_forward_probabilities checks of its
+ * arrays; a NULL repeat, counts or log_prob; max_repeat outside [2, 256]; a strand that is neither 0 nor 1; a count >= the max_repeat of
+ * its pair's model (the message names the pair).  Then MRP_ERR_NO_DEVICE for a NULL context; the rest as mrp_forward_probabilities. */
+int mrp_forward_probabilities_rle(mrp_context *ctx, const mrp_pair_hmm *models, const mrp_repeat_model *repeat, int32_t n_models, int64_t n_pairs,
+                                  const uint8_t *pool, const uint8_t *counts, int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len,
+                                  const int64_t *y_off, const int32_t *y_len, const uint8_t *model_index, const int64_t *anchor_off,
+                                  const int64_t *anchors, int64_t expansion, int ragged_left, int ragged_right, double *out,
+                                  mrp_pairhmm_stats *stats);
+/* The posterior entries with run-length emissions.  anchor_expansion == NULL: the band of mrp_posterior_aligned_pairs (band_construct over
+ * opt->expansion); else that of mrp_posterior_aligned_pairs_dynamic.  Honours mrp_context_set_posterior_wide_pairs.  Outputs, order,
+ * groups, workspace, stats and mrp_context_last_posterior are those entries'; total_out equals mrp_forward_probabilities_rle on the same
+ * pair.  The run-length MRP_ERR_ARG (as above) come with the other argument errors, before the bands are built. */
+int mrp_posterior_aligned_pairs_rle(mrp_context *ctx, const mrp_pair_hmm *models, const mrp_repeat_model *repeat, int32_t n_models, int64_t n_pairs,
+                                    const uint8_t *pool, const uint8_t *counts, int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len,
+                                    const int64_t *y_off, const int32_t *y_len, const uint8_t *model_index, const int64_t *anchor_off,
+                                    const int64_t *anchors, const int64_t *anchor_expansion, const mrp_posterior_options *opt,
+                                    mrp_posterior_pairs *match_out, mrp_posterior_pairs *gap_x_out, mrp_posterior_pairs *gap_y_out,
+                                    double *total_out /* [n_pairs], may be NULL */, mrp_pairhmm_stats *stats);
 /* Posterior wide pairs.  off (default, and for a NULL context): both posterior entries refuse a pair whose widest diagonal exceeds
  * 2 048 cells.  on: such a pair runs on two kernels of its own, a pair per workgroup forward and a (pair, traceback) per workgroup
  * backward, bit-identical to the pair-per-wave ones; pairs of up to 2 048 cells keep their kernels and launch classes,

@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "mrp_context_last_posterior",
     "mrp_band_diagonals_dynamic", "mrp_pair_diagonal_width_dynamic", "mrp_posterior_tracebacks_dynamic", "mrp_posterior_aligned_pairs_dynamic",
     "mrp_context_set_posterior_wide_pairs", "mrp_context_posterior_wide_count",
+    "mrp_rle_compress", "mrp_forward_probabilities_rle", "mrp_posterior_aligned_pairs_rle",
 ]
 
 
@@ -244,6 +245,24 @@ class PosteriorPairs(C.Structure):
         take = lambda p, dt: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype=dt)
         return {"first": first, "x": take(self.x, np.int32), "y": take(self.y, np.int32), "weight": take(self.weight, np.int32),
                 "log_posterior": take(self.log_posterior, np.float64)}
+
+
+class RepeatModelStruct(C.Structure):
+    """mrp_repeat_model"""
+    _fields_ = [("max_repeat", C.c_int32), ("strand", C.c_int32), ("log_prob", C.POINTER(C.c_double))]
+
+
+class RepeatModel:
+    """The run-length emissions of one model: log_prob float64 [4, R, R] (base A..T, underlying count, observed count:
+    RepeatSubMatrix.logProbabilities), strand 1 or 0 (RleNucleotideEmissions.strand).  Nothing is checked here: the entries do."""
+
+    def __init__(self, log_prob, strand=1, max_repeat=None):
+        self.log_prob = None if log_prob is None else np.ascontiguousarray(log_prob, dtype=np.float64)
+        self.max_repeat = int(max_repeat if max_repeat is not None else self.log_prob.shape[-1])
+        self.strand = int(strand)
+
+    def struct(self) -> RepeatModelStruct:
+        return RepeatModelStruct(self.max_repeat, self.strand, None if self.log_prob is None else self.log_prob.ctypes.data_as(C.POINTER(C.c_double)))
 
 
 class PosteriorStats(C.Structure):
@@ -511,6 +530,11 @@ def load():
     L.mrp_posterior_tracebacks_dynamic.argtypes = [vp, vp, i64, i64, i64, P(PosteriorOptions), vp, i64, P(i64)]
     L.mrp_posterior_aligned_pairs_dynamic.argtypes = [vp, vp, i32, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, P(PosteriorOptions), P(PosteriorPairs),
                                                       P(PosteriorPairs), P(PosteriorPairs), vp, vp]
+    L.mrp_rle_compress.argtypes = [C.c_char_p, i64, i32, vp, vp]
+    L.mrp_rle_compress.restype = i64
+    L.mrp_forward_probabilities_rle.argtypes = [vp, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, P(PairHmmStats)]
+    L.mrp_posterior_aligned_pairs_rle.argtypes = [vp, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, P(PosteriorOptions), P(PosteriorPairs),
+                                                  P(PosteriorPairs), P(PosteriorPairs), vp, P(PairHmmStats)]
     L.mrp_context_set_posterior_wide_pairs.argtypes = [vp, C.c_int]
     L.mrp_context_posterior_wide_count.argtypes = [vp, P(i64), P(i64)]
     L.mrp_allele_read_supports.argtypes = [vp, P(PairHmm), P(PairHmm), i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, P(PairHmmStats)]
@@ -1379,6 +1403,74 @@ def posterior_aligned_pairs(ctx, models, pool, x_off, x_len, y_off, y_len, model
         _check(load().mrp_posterior_aligned_pairs_dynamic(*front, ptr(ae), *back))
     else:
         _check(load().mrp_posterior_aligned_pairs(*front, *back))
+    out = [l.to_numpy(n) for l in lists]
+    for l in lists:
+        load().mrp_posterior_pairs_free(C.byref(l))
+    return out[0], (out[1] if options.with_gaps else None), (out[2] if options.with_gaps else None), total, st
+
+
+# ---- run-length emissions (rleNucleotideEmissions_construct, impl/stateMachine.c:716-752) ----
+
+def rle_compress(seq, max_repeat: int):
+    """mrp_rle_compress (host only): rleString_construct + the count clamp -> (symbols uint8, counts uint8), one entry per run"""
+    b = seq.encode() if isinstance(seq, str) else bytes(seq)
+    sym, cnt = np.zeros(len(b), dtype=np.uint8), np.zeros(len(b), dtype=np.uint8)
+    n = load().mrp_rle_compress(b, len(b), int(max_repeat), sym.ctypes.data, cnt.ctypes.data)
+    if n < 0:
+        raise ValueError("mrp_rle_compress: bad arguments")
+    return sym[:n].copy(), cnt[:n].copy()
+
+
+def _repeat_array(repeat):
+    """the mrp_repeat_model array of a list of RepeatModel (None: a NULL array); the caller keeps `repeat` alive during the call"""
+    if repeat is None:
+        return None
+    return (RepeatModelStruct * len(repeat))(*[r.struct() for r in repeat])
+
+
+def forward_probabilities_rle(ctx, models, repeat, pool, counts, x_off, x_len, y_off, y_len, model_index=None, anchor_off=None, anchors=None,
+                              expansion: int = 4, ragged_left: bool = False, ragged_right: bool = False):
+    """mrp_forward_probabilities_rle: forward_probabilities with run-length emissions; repeat one RepeatModel per model, counts uint8
+    parallel to pool (None: a NULL array).  ctx may be None (the checks that need no device)."""
+    arr = (PairHmm * len(models))(*models)
+    rarr = _repeat_array(repeat)
+    pool = np.ascontiguousarray(pool, dtype=np.uint8)
+    cnt = _opt(counts, np.uint8)
+    xo, xl, yo, yl = _opt(x_off, np.int64), _opt(x_len, np.int32), _opt(y_off, np.int64), _opt(y_len, np.int32)
+    mi, ao, an = _opt(model_index, np.uint8), _opt(anchor_off, np.int64), _opt(anchors, np.int64)
+    n = len(xo)
+    out = np.zeros(n, dtype=np.float64)
+    st = PairHmmStats()
+    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+    _check(load().mrp_forward_probabilities_rle(ctx.h if ctx is not None else None, C.cast(arr, C.c_void_p), None if rarr is None else C.cast(rarr, C.c_void_p),
+                                                len(models), n, ptr(pool), None if cnt is None else cnt.ctypes.data, pool.size, ptr(xo), ptr(xl), ptr(yo), ptr(yl),
+                                                ptr(mi), None if ao is None else ao.ctypes.data, ptr(an), int(expansion), int(ragged_left), int(ragged_right),
+                                                out.ctypes.data, C.byref(st)))
+    return out, st
+
+
+def posterior_aligned_pairs_rle(ctx, models, repeat, pool, counts, x_off, x_len, y_off, y_len, model_index=None, anchor_off=None, anchors=None,
+                                options: PosteriorOptions = None, want_total: bool = True, anchor_expansion=None):
+    """mrp_posterior_aligned_pairs_rle -> as posterior_aligned_pairs; anchor_expansion None: the band of band_construct over
+    options.expansion, else the dynamic band"""
+    options = options if options is not None else PosteriorOptions()
+    ae = _opt(anchor_expansion, np.int64)
+    arr = (PairHmm * len(models))(*models)
+    rarr = _repeat_array(repeat)
+    pool = np.ascontiguousarray(pool, dtype=np.uint8)
+    cnt = _opt(counts, np.uint8)
+    xo, xl, yo, yl = _opt(x_off, np.int64), _opt(x_len, np.int32), _opt(y_off, np.int64), _opt(y_len, np.int32)
+    mi, ao, an = _opt(model_index, np.uint8), _opt(anchor_off, np.int64), _opt(anchors, np.int64)
+    n = len(xo)
+    total = np.zeros(n, dtype=np.float64) if want_total else None
+    st = PairHmmStats()
+    lists = [PosteriorPairs() for _ in range(3 if options.with_gaps else 1)]
+    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+    _check(load().mrp_posterior_aligned_pairs_rle(
+        ctx.h if ctx is not None else None, C.cast(arr, C.c_void_p), None if rarr is None else C.cast(rarr, C.c_void_p), len(models), n, ptr(pool),
+        None if cnt is None else cnt.ctypes.data, pool.size, ptr(xo), ptr(xl), ptr(yo), ptr(yl), ptr(mi), None if ao is None else ao.ctypes.data, ptr(an),
+        None if ae is None else ae.ctypes.data, C.byref(options), C.byref(lists[0]), C.byref(lists[1]) if options.with_gaps else None,
+        C.byref(lists[2]) if options.with_gaps else None, ptr(total), C.byref(st)))
     out = [l.to_numpy(n) for l in lists]
     for l in lists:
         load().mrp_posterior_pairs_free(C.byref(l))

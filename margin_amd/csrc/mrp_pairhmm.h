@@ -22,6 +22,45 @@ struct PhmModelDev {
     double end[3];   /* stateMachine3_endStateProb / raggedEndStateProb */
 };
 
+/* The run-length emissions of one model (RleNucleotideEmissions, stateMachine.c:716-752) as the kernels read them:
+ * rep[(cx * R + u) * R + o] = 2.3025 * logProbabilities[b(cx)][u][o], cx 0..4 the x symbol, b(cx) = strand ? cx : 3 - cx with N
+ * mapped to A first (repeatSubMatrix.c:16-29), u the count of the x symbol (underlying), o that of the y symbol (observed) */
+struct PhmRepeatDev {
+    const double *rep;
+    int32_t R;
+};
+/* The host half of a run-length batch: the counts (the caller's, parallel to the pool), every model's table back to back */
+struct PhmRle {
+    const uint8_t *counts = nullptr;
+    HostVec<double> rep;
+    std::vector<int64_t> rep_first; /* model i's table in rep */
+    std::vector<int32_t> R;
+};
+/* (mrp_pairhmm.hip) every MRP_ERR_ARG of the two run-length entries; builds the tables.  The count check is what keeps every table
+ * index of the kernels in range. */
+struct PhmPairs;
+int phm_rle_check_and_build(const char *who, const mrp_repeat_model *repeat, int32_t n_models, const uint8_t *counts, const PhmPairs &P,
+                            PhmRle &out);
+/* the device half: counts and tables uploaded on s; d_counts and d_models are what the run-length instantiations of the kernels are
+ * handed (PhmRunLength::Args) */
+struct PhmRleDev {
+    DevBufGroup arrays;
+    DevBuf<uint8_t> d_counts{arrays};
+    DevBuf<double> d_rep{arrays};
+    DevBuf<PhmRepeatDev> d_models{arrays};
+    hipError_t upload(DevPool *pool, const PhmRle &H, int64_t pool_bytes, hipStream_t s) {
+        arrays.bind(pool);
+        hipError_t e = d_counts.alloc((size_t) pool_bytes);
+        if (e == hipSuccess && pool_bytes) e = hipMemcpyAsync(d_counts.p, H.counts, (size_t) pool_bytes, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = d_rep.upload(H.rep, s);
+        if (e != hipSuccess) return e;
+        models.resize(H.R.size());
+        for (size_t i = 0; i < H.R.size(); i++) models[i] = PhmRepeatDev{d_rep.p + H.rep_first[i], H.R[i]};
+        return d_models.upload(models, s);
+    }
+    HostVec<PhmRepeatDev> models; /* the source of a queued copy: lives as long as the buffers */
+};
+
 struct PhmPair {
     int64_t x_off, y_off;
     int64_t band_off; /* first diagonal in the band array, -1: whole matrix */
@@ -123,6 +162,7 @@ struct PhmLaunch {
     int64_t wide_cells = 0;      /* their share of cells */
     HostVec<int32_t> band;
     HostVec<uint32_t> key; /* phm_classify's sort keys (released with the launch, not between its two halves) */
+    const PhmRle *rle = nullptr; /* set before phm_classify: run-length emissions; no pair goes to the pair-per-lane kernel */
 };
 struct PhmDev {
     hipStream_t s = nullptr;
@@ -135,6 +175,7 @@ struct PhmDev {
     DevBuf<PhmPair> d_wave[4]{DevBuf<PhmPair>{arrays}, DevBuf<PhmPair>{arrays}, DevBuf<PhmPair>{arrays}, DevBuf<PhmPair>{arrays}};
     DevBuf<PhmPair> d_wide{arrays};
     DevBuf<double> d_wide_ws{arrays}; /* [workgroup][diagonal being written, xay - 1, xay - 2][state][wide_width] */
+    PhmRleDev rle;                    /* a run-length batch: counts and tables */
     ~PhmDev() {
         if (s) (void) hipStreamSynchronize(s);
     }
@@ -157,10 +198,12 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
  * copies (and, on a cold pool, their hipMalloc) beside the kernels. */
 template <class Reduce>
 int phm_call(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, int32_t n_models, const uint8_t *pool, int64_t pool_bytes,
-             const PhmPairs &P, int64_t expansion, int ragged_left, int ragged_right, mrp_pairhmm_stats *stats, double t_begin, Reduce reduce) {
+             const PhmPairs &P, int64_t expansion, int ragged_left, int ragged_right, mrp_pairhmm_stats *stats, double t_begin, Reduce reduce,
+             const PhmRle *rle = nullptr) {
     hipStream_t s = ctx->stream;
     {
         PhmLaunch H;
+        H.rle = rle;
         PhmDev L;
         if (P.n > 0) { /* (the host's errors first, then the device: phm_enqueue makes it current) */
             int rc = phm_classify(who, models, n_models, pool_bytes, P, expansion, ragged_left, ragged_right, ctx->wide_pairs, H);

@@ -22,7 +22,9 @@
  *   phm_wave_kernel   a pair per WAVE for everything else (long strings, anchored bands): x+y diagonal by diagonal, a
  *                     lane per cell of the diagonal, the last two diagonals in LDS -- up to 2 048 cells on a diagonal.
  *   phm_wide_kernel   a pair per WORKGROUP for the pairs beyond that, when the caller has turned wide pairs on (else they are
- *                     refused): the diagonals in a device workspace.  Both are the walk of mrp_pairhmm_walk.h.
+ *                     refused): the diagonals in a device workspace.  Both are the walk of mrp_pairhmm_walk.h, and
+ *                     both exist a second time with the run-length emissions of margin polish (mrp_forward_probabilities_rle,
+ *                     DESIGN.md 9.16), whose pairs never take the pair-per-lane kernel.
  *
  * Bound: fp64 VALU issue (six logAdd per cell); the kernels move ~0.1 B per flop.
  */
@@ -226,10 +228,11 @@ __global__ void __launch_bounds__(256) phm_lane_kernel(const PhmLanePair *__rest
 }
 
 /* A pair per WAVE (a workgroup of one wave): the walk of mrp_pairhmm_walk.h with the three live diagonals in LDS, 3 diagonals x W
- * cells x 3 states, then the total on the last diagonal. */
+ * cells x 3 states, then the total on the last diagonal.  Em: the match emission (PhmNucleotide, PhmRunLength), ea what it reads. */
+template <class Em>
 __global__ void __launch_bounds__(PHM_WAVE) phm_wave_kernel(const PhmPair *__restrict__ pairs, int64_t n_pairs, const uint8_t *__restrict__ pool,
                                                               const PhmModelDev *__restrict__ models, const int32_t *__restrict__ band, int W,
-                                                              double *__restrict__ out) {
+                                                              double *__restrict__ out, typename Em::Args ea) {
     extern __shared__ double phm_diag[];
     for (int64_t pi = blockIdx.x; pi < n_pairs; pi += gridDim.x) {
         const PhmPair p = pairs[pi];
@@ -238,7 +241,7 @@ __global__ void __launch_bounds__(PHM_WAVE) phm_wave_kernel(const PhmPair *__res
             if (threadIdx.x == 0) out[p.out] = 0.0; /* :860-862 */
             continue;
         }
-        const PhmPairCtx c = phm_pair_ctx(models, p.model, pool, p.x_off, p.y_off);
+        const PhmPairCtxT<Em> c = phm_pair_ctx<Em>(models, p.model, pool, p.x_off, p.y_off, ea);
         PhmDiagonals<PhmInterleaved, PHM_KEEP_NONE> diag{PhmInterleaved::at(phm_diag, W, 0), PhmInterleaved::at(phm_diag, W, 1), PhmInterleaved::at(phm_diag, W, 2)};
         const PhmBandOrMatrixLimits limits{band, p.band_off, p.lx, p.ly};
         phm_forward_walk<PhmTeam<PHM_WAVE, false>>(n, diag, limits, c);
@@ -253,14 +256,14 @@ __global__ void __launch_bounds__(PHM_WAVE) phm_wave_kernel(const PhmPair *__res
  * __syncthreads() between diagonals is the only synchronisation.  The next pair of the grid-stride loop reuses the slice; every
  * cell read lies inside [l1, r1] / [l2, r2] of the pair's own diagonals, which that pair wrote.  (No pair with an empty matrix
  * reaches this kernel; the walk would give it its start cell's total.) */
-template <int T>
+template <int T, class Em>
 __global__ void __launch_bounds__(T) phm_wide_kernel(const PhmPair *__restrict__ pairs, int64_t n_pairs, const uint8_t *__restrict__ pool,
                                                      const PhmModelDev *__restrict__ models, const int32_t *__restrict__ band, int W, double *ws,
-                                                     double *__restrict__ out) {
+                                                     double *__restrict__ out, typename Em::Args ea) {
     double *slice = ws + (size_t) blockIdx.x * 9 * (size_t) W;
     for (int64_t pi = blockIdx.x; pi < n_pairs; pi += gridDim.x) {
         const PhmPair p = pairs[pi];
-        const PhmPairCtx c = phm_pair_ctx(models, p.model, pool, p.x_off, p.y_off);
+        const PhmPairCtxT<Em> c = phm_pair_ctx<Em>(models, p.model, pool, p.x_off, p.y_off, ea);
         PhmDiagonals<PhmSlice, PHM_KEEP_NONE> diag{PhmSlice::at(slice, W, 0), PhmSlice::at(slice, W, 1), PhmSlice::at(slice, W, 2)};
         const int n = p.lx + p.ly;
         const PhmBandOrMatrixLimits limits{band, p.band_off, p.lx, p.ly};
@@ -372,7 +375,9 @@ int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, 
      * launch classes by x length (4, 3, 2, 1 waves per workgroup = per CU). */
     const int table_bytes = (16 + n_models * PHM_ETAB) * (int) sizeof(double);
     /* (-1: the tables of this many models leave no room for a row, every pair goes to the pair-per-wave kernel) */
-    const int lane_max_x = PHM_LDS_BYTES - table_bytes < PHM_LANE_BYTES_PER_X ? -1 : std::min(PHM_LANE_MAX_X, (PHM_LDS_BYTES - table_bytes) / PHM_LANE_BYTES_PER_X);
+    /* (-1 as well for run-length emissions, L.rle: phm_lane_kernel is not instantiated for them) */
+    const int lane_max_x =
+        L.rle || PHM_LDS_BYTES - table_bytes < PHM_LANE_BYTES_PER_X ? -1 : std::min(PHM_LANE_MAX_X, (PHM_LDS_BYTES - table_bytes) / PHM_LANE_BYTES_PER_X);
     int lane_cap[4];
     for (int c = 0; c < 4; c++) lane_cap[c] = std::min(lane_max_x, (PHM_LDS_BYTES - table_bytes) / ((4 - c) * PHM_LANE_BYTES_PER_X));
     constexpr uint32_t WAVE_KEY = 0xFFFFFFFFu;
@@ -529,6 +534,7 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
     }
     PHM_HIP(L.d_band.upload(band, s));
     PHM_HIP(L.d_out.alloc((size_t) n_pairs));
+    if (H.rle) PHM_HIP(L.rle.upload(&ctx->pool, *H.rle, pool_bytes, s));
     for (int c = 0; c < 4; c++) {
         PHM_HIP(L.d_lane[c].upload(lane_pairs[c], s));
         PHM_HIP(L.d_wave[c].upload(wave_pairs[c], s));
@@ -548,7 +554,8 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
     const hipError_t configured = once.run([] {
         hipError_t e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *) phm_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *) phm_wave_kernel<PhmNucleotide>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *) phm_wave_kernel<PhmRunLength>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
         return e;
     });
     PHM_HIP(configured);
@@ -578,18 +585,67 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
         if (n == 0) continue;
         const int W = WAVE_CLASS_CAP[c];
         const size_t lds = (size_t) 9 * W * sizeof(double);
-        hipLaunchKernelGGL(phm_wave_kernel, dim3((unsigned) std::min<int64_t>(n, 16384)), dim3(PHM_WAVE), lds, s, L.d_wave[c].p, n, device_pool,
-                           L.d_models.p, L.d_band.p, W, L.d_out.p);
+        const dim3 grid((unsigned) std::min<int64_t>(n, 16384));
+        if (H.rle)
+            hipLaunchKernelGGL(phm_wave_kernel<PhmRunLength>, grid, dim3(PHM_WAVE), lds, s, L.d_wave[c].p, n, device_pool, L.d_models.p, L.d_band.p, W, L.d_out.p,
+                               PhmRunLength::Args{L.rle.d_counts.p, L.rle.d_models.p});
+        else
+            hipLaunchKernelGGL(phm_wave_kernel<PhmNucleotide>, grid, dim3(PHM_WAVE), lds, s, L.d_wave[c].p, n, device_pool, L.d_models.p, L.d_band.p, W, L.d_out.p,
+                               PhmNucleotide::Args{});
         PHM_HIP(hipGetLastError());
         if (stats) stats->pairs_wave += n;
     }
     if (n_wide > 0) {
-        hipLaunchKernelGGL(phm_wide_kernel<PHM_WIDE_THREADS>, dim3((unsigned) wide_grid), dim3(PHM_WIDE_THREADS), 0, s, L.d_wide.p, n_wide, device_pool, L.d_models.p,
-                           L.d_band.p, H.wide_width, L.d_wide_ws.p, L.d_out.p);
+        if (H.rle)
+            hipLaunchKernelGGL((phm_wide_kernel<PHM_WIDE_THREADS, PhmRunLength>), dim3((unsigned) wide_grid), dim3(PHM_WIDE_THREADS), 0, s, L.d_wide.p, n_wide, device_pool,
+                               L.d_models.p, L.d_band.p, H.wide_width, L.d_wide_ws.p, L.d_out.p, PhmRunLength::Args{L.rle.d_counts.p, L.rle.d_models.p});
+        else
+            hipLaunchKernelGGL((phm_wide_kernel<PHM_WIDE_THREADS, PhmNucleotide>), dim3((unsigned) wide_grid), dim3(PHM_WIDE_THREADS), 0, s, L.d_wide.p, n_wide, device_pool,
+                               L.d_models.p, L.d_band.p, H.wide_width, L.d_wide_ws.p, L.d_out.p, PhmNucleotide::Args{});
         PHM_HIP(hipGetLastError());
         if (stats) stats->pairs_wave += n_wide;
         ctx->wide_pair_count += n_wide;
         ctx->wide_cell_count += H.wide_cells;
+    }
+    return MRP_OK;
+}
+
+/* The MRP_ERR_ARG of the run-length entries, raised with the other argument errors, and the tables: rep = 2.3025 * log_prob, one IEEE
+ * multiply per entry (getRleNucleotideMatchProb, stateMachine.c:733-738), rows by x symbol with the strand and N rules of
+ * repeatSubMatrix_setLogProb (repeatSubMatrix.c:16-29).  P's offsets and model indices have been checked by the caller. */
+int phm_rle_check_and_build(const char *who, const mrp_repeat_model *repeat, int32_t n_models, const uint8_t *counts, const PhmPairs &P, PhmRle &out) {
+    if (!repeat) return mrp_set_error(MRP_ERR_ARG, "%s: repeat is NULL", who);
+    for (int32_t m = 0; m < n_models; m++) {
+        if (!repeat[m].log_prob) return mrp_set_error(MRP_ERR_ARG, "%s: repeat model %d has no log_prob", who, (int) m);
+        if (repeat[m].max_repeat < 2 || repeat[m].max_repeat > 256)
+            return mrp_set_error(MRP_ERR_ARG, "%s: repeat model %d: max_repeat %d outside [2, 256]", who, (int) m, (int) repeat[m].max_repeat);
+        if (repeat[m].strand != 0 && repeat[m].strand != 1) return mrp_set_error(MRP_ERR_ARG, "%s: repeat model %d: strand must be 0 or 1", who, (int) m);
+    }
+    bool any = false;
+    for (int64_t i = 0; i < P.n && !any; i++) any = P.x_len[i] > 0 || P.y_len[i] > 0;
+    if (any && !counts) return mrp_set_error(MRP_ERR_ARG, "%s: counts is NULL", who);
+    for (int64_t i = 0; i < P.n; i++) {
+        const int R = repeat[P.model ? P.model[i] : 0].max_repeat;
+        const int64_t off[2] = {P.x_off[i], P.y_off[i]}, len[2] = {P.x_len[i], P.y_len[i]};
+        for (int q = 0; q < 2; q++)
+            for (int64_t k = 0; k < len[q]; k++)
+                if (counts[off[q] + k] >= R)
+                    return mrp_set_error(MRP_ERR_ARG, "%s: pair %lld: the count %d of %c symbol %lld is not below max_repeat %d of its model", who, (long long) i,
+                                         (int) counts[off[q] + k], q ? 'y' : 'x', (long long) k, R);
+    }
+    out.counts = counts;
+    out.rep.clear();
+    out.rep_first.clear();
+    out.R.clear();
+    for (int32_t m = 0; m < n_models; m++) {
+        const int64_t R = repeat[m].max_repeat;
+        out.rep_first.push_back((int64_t) out.rep.size());
+        out.R.push_back((int32_t) R);
+        for (int cx = 0; cx < 5; cx++) {
+            const int base = cx >= 4 ? 0 : cx;
+            const double *src = repeat[m].log_prob + (repeat[m].strand ? base : 3 - base) * R * R;
+            for (int64_t k = 0; k < R * R; k++) out.rep.push_back(2.3025 * src[k]);
+        }
     }
     return MRP_OK;
 }
@@ -788,6 +844,50 @@ int mrp_forward_probabilities(mrp_context *ctx, const mrp_pair_hmm *models, int3
                         PHM_HIP(hipMemcpyAsync(out, lp, (size_t) n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
                         return (int) MRP_OK;
                     });
+}
+
+int64_t mrp_rle_compress(const char *s, int64_t n, int32_t max_repeat, uint8_t *symbols_out, uint8_t *counts_out) {
+    if (n < 0 || (n > 0 && (!s || !symbols_out || !counts_out)) || max_repeat < 2 || max_repeat > 256) return -1;
+    int64_t m = 0;
+    for (int64_t i = 0; i < n;) { /* rleString_construct, rle.c:7-38: a run of one character, compared as chars ("aA" is two runs) */
+        int64_t j = i + 1;
+        while (j < n && s[j] == s[i]) j++;
+        mrp_symbols_from_chars(s + i, 1, symbols_out + m);
+        const int64_t run = j - i;
+        counts_out[m++] = (uint8_t) (run >= max_repeat ? max_repeat - 1 : run); /* symbol_addRepeatCount, stateMachine.c:124-131 */
+        i = j;
+    }
+    return m;
+}
+
+int mrp_forward_probabilities_rle(mrp_context *ctx, const mrp_pair_hmm *models, const mrp_repeat_model *repeat, int32_t n_models, int64_t n_pairs,
+                                  const uint8_t *pool, const uint8_t *counts, int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len,
+                                  const int64_t *y_off, const int32_t *y_len, const uint8_t *model_index, const int64_t *anchor_off, const int64_t *anchors,
+                                  int64_t expansion, int ragged_left, int ragged_right, double *out, mrp_pairhmm_stats *stats) {
+    static const char *who = "mrp_forward_probabilities_rle";
+    const double t_begin = now_ms();
+    /* the argument errors first, before the context is looked at; nothing is written on an error */
+    if (n_pairs < 0 || n_models <= 0 || !models || pool_bytes < 0) return mrp_set_error(MRP_ERR_ARG, "%s: bad sizes", who);
+    if (n_pairs > 0 && (!x_off || !x_len || !y_off || !y_len || !out || (pool_bytes > 0 && !pool))) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    const PhmPairs P{n_pairs, x_off, x_len, y_off, y_len, model_index, anchor_off, anchors};
+    for (int64_t i = 0; i < n_pairs; i++)
+        if (x_len[i] < 0 || y_len[i] < 0 || x_off[i] < 0 || y_off[i] < 0 || x_off[i] + x_len[i] > pool_bytes || y_off[i] + y_len[i] > pool_bytes ||
+            (model_index && model_index[i] >= n_models))
+            return mrp_set_error(MRP_ERR_ARG, "%s: pair %lld lies outside the symbol pool or names a model >= %d", who, (long long) i, (int) n_models);
+    PhmRle rle;
+    const int rc = phm_rle_check_and_build(who, repeat, n_models, counts, P, rle);
+    if (rc != MRP_OK) return rc;
+    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the pair-HMM path has no CPU fallback)", who);
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_pairs == 0) return MRP_OK;
+    return phm_call(
+        ctx, who, models, n_models, pool, pool_bytes, P, expansion, ragged_left, ragged_right, stats, t_begin,
+        [&](hipStream_t s, const double *lp) {
+            PHM_HIP(hipEventRecord(ctx->ev[1], s));
+            PHM_HIP(hipMemcpyAsync(out, lp, (size_t) n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+            return (int) MRP_OK;
+        },
+        &rle);
 }
 
 int mrp_allele_read_supports(mrp_context *ctx, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t n_bubbles,

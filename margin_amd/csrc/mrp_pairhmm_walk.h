@@ -8,6 +8,10 @@
  *   one walk       phm_forward_walk: the start diagonal, then diagonal after diagonal from the two before it, a barrier after each
  *   two teams      T threads with __syncthreads (phm_wave_kernel's one wave too, as ever), or a wave with the LDS-only lds_barrier
  *   three storages three rotating buffers; the same with every cell also kept in the workspace; the kept workspace alone (PhmKeep)
+ *   two emissions  the match emission of a cell is a policy of the pair's context: the model's table (PhmNucleotide, the default, which
+ *                  costs the kernels nothing) or the same + the repeat counts' term from a table in device memory (PhmRunLength,
+ *                  DESIGN.md 9.16); the three places that take a match emission -- the forward cell, the match branch of the backward
+ *                  cell, the second term of a total -- ask the policy
  */
 #ifndef MRP_PAIRHMM_WALK_H_
 #define MRP_PAIRHMM_WALK_H_
@@ -28,14 +32,48 @@ static __device__ __forceinline__ int phm_sym(const uint8_t *s, int i) {
     return c > 4 ? 4 : c;
 }
 
-/* what every cell of a pair reads: the pair's model, the model's transitions in registers, the two strings */
-struct PhmPairCtx {
+/* ---- the match emission of a cell: a policy the pair's context carries.  match(M, cx, cy, xi, yi): the symbols cx, cy (0..4) that
+ * stand at positions xi, yi of the two strings, -1 for the symbol before the first.  Args: what a kernel is handed for the policy ---- */
+struct PhmNucleotide { /* getNucleotideMatchProb, stateMachine.c:378-383: the model's table */
+    struct Args {};
+    static __device__ __forceinline__ PhmNucleotide of(const Args &, int, int64_t, int64_t) { return PhmNucleotide{}; }
+    __device__ __forceinline__ double match(const PhmModelDev *M, int cx, int cy, int, int) const { return M->em[cx * 5 + cy]; }
+};
+/* getRleNucleotideMatchProb, stateMachine.c:733-738: the same + 2.3025 * repeatSubMatrix_getLogProb(x's base, strand, observed = y's
+ * count, underlying = x's count), the product taken from the host's table (PhmRepeatDev).  The symbol before the first has count 0
+ * (pairwiseAligner.c:535-545).  The host has checked every count against the R of its pair's model, so the index stays inside the table;
+ * the table is read through the caches, never from LDS. */
+struct PhmRunLength {
+    struct Args {
+        const uint8_t *counts;      /* parallel to the symbol pool */
+        const PhmRepeatDev *models; /* one per model */
+    };
+    const uint8_t *rx, *ry;
+    const double *rep;
+    int R;
+    static __device__ __forceinline__ PhmRunLength of(const Args &a, int model, int64_t x_off, int64_t y_off) {
+        const PhmRepeatDev m = a.models[model];
+        return PhmRunLength{a.counts + x_off, a.counts + y_off, m.rep, m.R};
+    }
+    __device__ __forceinline__ double match(const PhmModelDev *M, int cx, int cy, int xi, int yi) const {
+        const int u = xi >= 0 ? rx[xi] : 0, o = yi >= 0 ? ry[yi] : 0;
+        return M->em[cx * 5 + cy] + rep[(cx * R + u) * R + o];
+    }
+};
+
+/* what every cell of a pair reads: the pair's model, the model's transitions in registers, the two strings, the match emission */
+template <class Em>
+struct PhmPairCtxT {
     const PhmModelDev *M;
     double t[9];
     const uint8_t *sx, *sy;
+    Em em;
 };
-static __device__ __forceinline__ PhmPairCtx phm_pair_ctx(const PhmModelDev *models, int model, const uint8_t *pool, int64_t x_off, int64_t y_off) {
-    PhmPairCtx c{models + model, {}, pool + x_off, pool + y_off};
+using PhmPairCtx = PhmPairCtxT<PhmNucleotide>;
+template <class Em = PhmNucleotide>
+static __device__ __forceinline__ PhmPairCtxT<Em> phm_pair_ctx(const PhmModelDev *models, int model, const uint8_t *pool, int64_t x_off, int64_t y_off,
+                                                               const typename Em::Args &ea = {}) {
+    PhmPairCtxT<Em> c{models + model, {}, pool + x_off, pool + y_off, Em::of(ea, model, x_off, y_off)};
 #pragma unroll
     for (int i = 0; i < 9; i++) c.t[i] = c.M->t[i];
     return c;
@@ -153,9 +191,9 @@ struct PhmDiagonals {
 /* The cell x - y = xmy of diagonal d from its neighbours on d - 1 (limits l1, r1) and d - 2 (l2, r2): stateMachine3_cellCalculate
  * (impl/stateMachine.c:562-586) as diagonalCalculation applies it (pairwiseAligner.c:547-570; the symbol before the first is N,
  * :535-545).  A neighbour outside the band contributes what one holding LOG_ZERO contributes. */
-template <class V>
+template <class V, class Ctx>
 static __device__ __forceinline__ St phm_forward_cell(int d, int xmy, int l1, int r1, int l2, int r2, const V &prev1, const V &prev2,
-                                                      const PhmPairCtx &c) {
+                                                      const Ctx &c) {
     const PhmModelDev *M = c.M;
     const double *t = c.t;
     const int x = (d + xmy) >> 1, y = (d - xmy) >> 1;
@@ -168,14 +206,14 @@ static __device__ __forceinline__ St phm_forward_cell(int d, int xmy, int l1, in
     if (y > 0) cy = phm_sym(c.sy, y - 1);
     const double eY = M->ey[cy];
     const PhmRowT ty{eY + t[4], eY + t[6], eY + t[8]};
-    return phm_cell(lower, middle, upper, t, M->ex[cx], M->em[cx * 5 + cy], ty);
+    return phm_cell(lower, middle, upper, t, M->ex[cx], c.em.match(M, cx, cy, x - 1, y - 1), ty);
 }
 
 /* The forward diagonals 0 .. n of a pair (pairwiseAligner.c:849-903 without its total): the team strides over a diagonal's cells, a
  * cell's value does not depend on which thread computes it, and one barrier separates a diagonal from the next.  A team reads only
  * what it wrote itself.  Diagonal n is left in s.d1, its limits in s.l1, s.r1. */
-template <class Team, class Storage, class Limits>
-static __device__ __forceinline__ void phm_forward_walk(int n, Storage &s, const Limits &limits, const PhmPairCtx &c) {
+template <class Team, class Storage, class Limits, class Ctx>
+static __device__ __forceinline__ void phm_forward_walk(int n, Storage &s, const Limits &limits, const Ctx &c) {
     const int tid = threadIdx.x;
     int l, r, l2 = 1, r2 = 0; /* the limits of the diagonal being written and of d - 2 */
     limits(0, l, r);
@@ -232,17 +270,20 @@ static __device__ __forceinline__ void pst_end_states(const double *t, bool at_e
 }
 
 /* What a traceback knows before its first diagonal */
-struct PstTbStart {
-    PhmPairCtx c;
+template <class Em>
+struct PstTbStartT {
+    PhmPairCtxT<Em> c;
     int n, slot;          /* the pair's last diagonal; where its total goes */
     const int32_t *bnd;   /* the pair's band from its diagonal 0 */
     const int64_t *first; /* and its cell_first */
     double e_end[3];
 };
-static __device__ __forceinline__ PstTbStart pst_tb_start(const PstTb &tb, const PstPair *pairs, const PhmModelDev *models, const uint8_t *pool,
-                                                          const int32_t *band, const int64_t *cell_first, int ragged_right) {
+template <class Em = PhmNucleotide>
+static __device__ __forceinline__ PstTbStartT<Em> pst_tb_start(const PstTb &tb, const PstPair *pairs, const PhmModelDev *models, const uint8_t *pool,
+                                                               const int32_t *band, const int64_t *cell_first, int ragged_right,
+                                                               const typename Em::Args &ea = {}) {
     const PstPair p = pairs[tb.pair];
-    PstTbStart s{phm_pair_ctx(models, p.model, pool, p.x_off, p.y_off), p.lx + p.ly, p.slot, band + 2 * p.diag0, cell_first + p.diag0, {}};
+    PstTbStartT<Em> s{phm_pair_ctx<Em>(models, p.model, pool, p.x_off, p.y_off, ea), p.lx + p.ly, p.slot, band + 2 * p.diag0, cell_first + p.diag0, {}};
     pst_end_states(s.c.t, tb.d == s.n, ragged_right, s.e_end);
     return s;
 }
@@ -255,16 +296,16 @@ static __device__ __forceinline__ PstTbStart pst_tb_start(const PstTb &tb, const
  * walked, the gap-y transition of (dd + 1, z - 1), whose `upper` this cell is; then the gap-x transition of (dd + 1, z + 1), whose
  * `lower` it is.  A state of the receiving cell gets one term from each, b_successor[to] + (eP + tP) with the successor's symbols; a
  * successor outside the band or beyond the traceback's first diagonal gives none. */
-template <class V>
+template <class V, class Ctx>
 static __device__ __forceinline__ St pst_backward_cell(int dd, int z, int l1, int r1, int l2, int r2, const V &b1, const V &b2,
-                                                       const PhmPairCtx &c) {
+                                                       const Ctx &c) {
     const PhmModelDev *M = c.M;
     const double *t = c.t;
     const int x = (dd + z) >> 1, y = (dd - z) >> 1;
     St b{PHM_NEG, PHM_NEG, PHM_NEG};
     if (z >= l2 && z <= r2) { /* (x + 1, y + 1) */
         const double sm = b2.load((z - l2) >> 1).m;
-        const double eM = M->em[phm_sym(c.sx, x) * 5 + phm_sym(c.sy, y)];
+        const double eM = c.em.match(M, phm_sym(c.sx, x), phm_sym(c.sy, y), x, y);
         b.m = phm_log_add(b.m, sm + (eM + t[0]));
         b.x = phm_log_add(b.x, sm + (eM + t[1]));
         b.y = phm_log_add(b.y, sm + (eM + t[2]));
@@ -293,9 +334,9 @@ static __device__ __forceinline__ double pst_total_term_here(const St &f, const 
 }
 /* ... and of its second: the match state of a forward step from diagonal dd - 1 (fwd; limits lm, rm) onto the cell x - y = z of
  * dd + 1, whose backward cell is b; the step's gap states stay LOG_ZERO */
-template <class V>
+template <class V, class Ctx>
 static __device__ __forceinline__ double pst_total_term_next(int dd, int z, int lm, int rm, const V &fwd, const St &b,
-                                                             const PhmPairCtx &c) {
+                                                             const Ctx &c) {
     const double *t = c.t;
     const int x = (dd + 1 + z) >> 1, y = (dd + 1 - z) >> 1;
     St mid{PHM_NEG, PHM_NEG, PHM_NEG};
@@ -303,7 +344,7 @@ static __device__ __forceinline__ double pst_total_term_next(int dd, int z, int 
     int cx = 4, cy = 4;
     if (x > 0) cx = phm_sym(c.sx, x - 1);
     if (y > 0) cy = phm_sym(c.sy, y - 1);
-    const double eM = c.M->em[cx * 5 + cy];
+    const double eM = c.em.match(c.M, cx, cy, x - 1, y - 1);
     const St f{phm_chain(mid.m + (eM + t[0]), mid.x + (eM + t[1]), mid.y + (eM + t[2])), PHM_NEG, PHM_NEG};
     return pst_total_term_here(f, b);
 }

@@ -24,6 +24,9 @@
  * lds_barrier(), which orders LDS traffic only: nothing in them reads what it stored to the workspace or to the lists.
  *
  * The host applies the reference's rule (addPosteriorProb, :598-608) with the C library's exp and keeps the order of generation.
+ *
+ * The four walking kernels are templates over the match emission (mrp_pairhmm_walk.h): mrp_posterior_aligned_pairs_rle runs their
+ * PhmRunLength instantiations over the same plan, groups and lists.
  */
 #include <hip/hip_runtime.h>
 
@@ -56,14 +59,15 @@ static_assert(sizeof(PstCand) == 16, "a candidate is 16 bytes");
 
 /* A pair per wave: the walk with the live diagonals in LDS (3 diagonals x W cells x 3 states) and every cell kept,
  * ws_m / ws_x / ws_y [cell_first[diag0 + d] + i] = cell i of diagonal d.  Nothing here reads what it stored to the workspace. */
+template <class Em>
 __global__ void __launch_bounds__(PHM_WAVE) pst_forward_kernel(const PstPair *__restrict__ pairs, int64_t n_pairs, const uint8_t *__restrict__ pool,
                                                                  const PhmModelDev *__restrict__ models, const int32_t *__restrict__ band,
                                                                  const int64_t *__restrict__ cell_first, int W, double *__restrict__ ws_m,
-                                                                 double *__restrict__ ws_x, double *__restrict__ ws_y) {
+                                                                 double *__restrict__ ws_x, double *__restrict__ ws_y, typename Em::Args ea) {
     extern __shared__ double pst_lds[];
     for (int64_t pi = blockIdx.x; pi < n_pairs; pi += gridDim.x) {
         const PstPair p = pairs[pi];
-        const PhmPairCtx c = phm_pair_ctx(models, p.model, pool, p.x_off, p.y_off);
+        const PhmPairCtxT<Em> c = phm_pair_ctx<Em>(models, p.model, pool, p.x_off, p.y_off, ea);
         PhmDiagonals<PhmInterleaved, PHM_KEEP_ALSO> diag{PhmInterleaved::at(pst_lds, W, 0), PhmInterleaved::at(pst_lds, W, 1), PhmInterleaved::at(pst_lds, W, 2), {ws_m, ws_x, ws_y, cell_first + p.diag0}};
         phm_forward_walk<PhmTeam<PHM_WAVE, true>>(p.lx + p.ly, diag, PhmBandLimits{band + 2 * p.diag0}, c);
     }
@@ -81,6 +85,7 @@ static __device__ __forceinline__ void pst_emit(PstCand *__restrict__ list, int 
 
 /* One traceback of one pair (pairwiseAligner.c:752-829), a wave.  b0 / b1 / b2: the backward diagonals d', d' + 1, d' + 2, each gathered
  * from the two behind it (pst_backward_cell, which says in what order). */
+template <class Em>
 __global__ void __launch_bounds__(PHM_WAVE) pst_traceback_kernel(const PstPair *__restrict__ pairs, const PstTb *__restrict__ tbs,
                                                                    const uint8_t *__restrict__ pool, const PhmModelDev *__restrict__ models,
                                                                    const int32_t *__restrict__ band, const int64_t *__restrict__ cell_first, int W,
@@ -88,11 +93,11 @@ __global__ void __launch_bounds__(PHM_WAVE) pst_traceback_kernel(const PstPair *
                                                                    const double *__restrict__ ws_y, double cut, int with_gaps, int ragged_right,
                                                                    int64_t n_tb_group, PstCand *__restrict__ cand_m, PstCand *__restrict__ cand_x,
                                                                    PstCand *__restrict__ cand_y, int32_t *__restrict__ counts,
-                                                                   double *__restrict__ total_out) {
+                                                                   double *__restrict__ total_out, typename Em::Args ea) {
     extern __shared__ double pst_lds[]; /* 3 diagonals x W cells x 3 states */
     const int lane = threadIdx.x;
     const PstTb tb = tbs[blockIdx.x];
-    const PstTbStart s = pst_tb_start(tb, pairs, models, pool, band, cell_first, ragged_right);
+    const PstTbStartT<Em> s = pst_tb_start<Em>(tb, pairs, models, pool, band, cell_first, ragged_right, ea);
     const int d = tb.d;
     using View = PhmInterleaved;
     View b0 = View::at(pst_lds, W, 0), b1 = View::at(pst_lds, W, 1), b2 = View::at(pst_lds, W, 2);
@@ -181,13 +186,14 @@ __global__ void __launch_bounds__(PHM_WAVE) pst_traceback_kernel(const PstPair *
 
 /* pst_forward_kernel with a pair per workgroup.  Every band cell is stored to the pair's slice of ws_m / ws_x / ws_y anyway, so the
  * diagonals d - 1 and d - 2 are read back from there: no copy in LDS, no second slice. */
-template <int T>
+template <int T, class Em>
 __global__ void __launch_bounds__(T) pst_forward_wide_kernel(const PstPair *__restrict__ pairs, int64_t n_pairs, const uint8_t *__restrict__ pool,
                                                              const PhmModelDev *__restrict__ models, const int32_t *__restrict__ band,
-                                                             const int64_t *__restrict__ cell_first, double *ws_m, double *ws_x, double *ws_y) {
+                                                             const int64_t *__restrict__ cell_first, double *ws_m, double *ws_x, double *ws_y,
+                                                             typename Em::Args ea) {
     for (int64_t pi = blockIdx.x; pi < n_pairs; pi += gridDim.x) {
         const PstPair p = pairs[pi];
-        const PhmPairCtx c = phm_pair_ctx(models, p.model, pool, p.x_off, p.y_off);
+        const PhmPairCtxT<Em> c = phm_pair_ctx<Em>(models, p.model, pool, p.x_off, p.y_off, ea);
         PhmDiagonals<PhmPlanar, PHM_KEEP_ONLY> diag{{}, {}, {}, {ws_m, ws_x, ws_y, cell_first + p.diag0}};
         phm_forward_walk<PhmTeam<T, false>>(p.lx + p.ly, diag, PhmBandLimits{band + 2 * p.diag0}, c);
     }
@@ -217,7 +223,7 @@ static __device__ __forceinline__ double pst_fold_row(const double *row, int cou
     return acc;
 }
 
-template <int T>
+template <int T, class Em>
 __global__ void __launch_bounds__(T) pst_traceback_wide_kernel(const PstPair *__restrict__ pairs, const PstTb *__restrict__ tbs, int64_t n_tbs,
                                                                const uint8_t *__restrict__ pool, const PhmModelDev *__restrict__ models,
                                                                const int32_t *__restrict__ band, const int64_t *__restrict__ cell_first, int W,
@@ -225,7 +231,7 @@ __global__ void __launch_bounds__(T) pst_traceback_wide_kernel(const PstPair *__
                                                                const double *__restrict__ ws_y, double *ws_back, double cut, int with_gaps,
                                                                int ragged_right, int64_t n_tb_group, PstCand *__restrict__ cand_m,
                                                                PstCand *__restrict__ cand_x, PstCand *__restrict__ cand_y,
-                                                               int32_t *__restrict__ counts, double *__restrict__ total_out) {
+                                                               int32_t *__restrict__ counts, double *__restrict__ total_out, typename Em::Args ea) {
     constexpr int NW = T / PHM_WAVE;
     static_assert(NW >= 2, "the two rows of a total are folded by two waves");
     __shared__ int wave_count[2][3][NW];
@@ -236,7 +242,7 @@ __global__ void __launch_bounds__(T) pst_traceback_wide_kernel(const PstPair *__
     int flip = 0;
     for (int64_t k = blockIdx.x; k < n_tbs; k += gridDim.x) {
         const PstTb tb = tbs[k];
-        const PstTbStart s = pst_tb_start(tb, pairs, models, pool, band, cell_first, ragged_right);
+        const PstTbStartT<Em> s = pst_tb_start<Em>(tb, pairs, models, pool, band, cell_first, ragged_right, ea);
         const int d = tb.d;
         using View = PhmSlice;
         View b0 = View::at(slice, W, 0), b1 = View::at(slice, W, 1), b2 = View::at(slice, W, 2);
@@ -572,9 +578,21 @@ void pst_with_wide_threads(bool wide_hook, F launch) {
     else launch(std::integral_constant<int, PST_WIDE_THREADS>{});
 }
 
+/* launch(PstEmission<Em>{}, args): the match emission of the call, the nucleotide one or (rle) the run-length one */
+template <class Em>
+struct PstEmission {
+    using type = Em;
+};
+template <class F>
+void pst_with_emission(const PhmRunLength::Args *rle, F launch) {
+    if (rle) launch(PstEmission<PhmRunLength>{}, *rle);
+    else launch(PstEmission<PhmNucleotide>{}, PhmNucleotide::Args{});
+}
+
 /* The device half of a group with at least one scored pair: uploads, the forward and traceback launches between the context's events,
  * the counts, the pack and the download of the dense candidates into H.dense */
-int pst_group_run(mrp_context *ctx, const uint8_t *d_pool, const PhmModelDev *d_models, const mrp_posterior_options *opt, PstGroup &H, mrp_posterior_stats &ps) {
+int pst_group_run(mrp_context *ctx, const uint8_t *d_pool, const PhmModelDev *d_models, const PhmRunLength::Args *rle, const mrp_posterior_options *opt, PstGroup &H,
+                  mrp_posterior_stats &ps) {
     hipStream_t s = ctx->stream;
     const int n_lists = opt->with_gaps ? 3 : 1;
     const int with_gaps = (int) opt->with_gaps, ragged_right = (int) (opt->ragged_right != 0);
@@ -616,15 +634,21 @@ int pst_group_run(mrp_context *ctx, const uint8_t *d_pool, const PhmModelDev *d_
         const int64_t n = pair0[c + 1] - pair0[c];
         if (n == 0) continue;
         const int W = WAVE_CLASS_CAP[c];
-        hipLaunchKernelGGL(pst_forward_kernel, dim3((unsigned) std::min<int64_t>(n, 1 << 20)), dim3(PHM_WAVE), (size_t) 9 * W * sizeof(double), s,
-                           G.d_pairs.p + pair0[c], n, d_pool, d_models, G.d_band.p, G.d_cell_first.p, W, ws_m, ws_x, ws_y);
+        pst_with_emission(rle, [&](auto em, auto ea) {
+            using Em = typename decltype(em)::type;
+            hipLaunchKernelGGL(pst_forward_kernel<Em>, dim3((unsigned) std::min<int64_t>(n, 1 << 20)), dim3(PHM_WAVE), (size_t) 9 * W * sizeof(double), s,
+                               G.d_pairs.p + pair0[c], n, d_pool, d_models, G.d_band.p, G.d_cell_first.p, W, ws_m, ws_x, ws_y, ea);
+        });
         PHM_HIP(hipGetLastError());
     }
     if (n_wide > 0) {
         pst_with_wide_threads(H.wide_hook, [&](auto threads) {
             constexpr int T = decltype(threads)::value;
-            hipLaunchKernelGGL((pst_forward_wide_kernel<T>), dim3((unsigned) wide_fgrid), dim3(T), 0, s, G.d_pairs.p + pair0[4], n_wide, d_pool, d_models,
-                               G.d_band.p, G.d_cell_first.p, ws_m, ws_x, ws_y);
+            pst_with_emission(rle, [&](auto em, auto ea) {
+                using Em = typename decltype(em)::type;
+                hipLaunchKernelGGL((pst_forward_wide_kernel<T, Em>), dim3((unsigned) wide_fgrid), dim3(T), 0, s, G.d_pairs.p + pair0[4], n_wide, d_pool, d_models,
+                                   G.d_band.p, G.d_cell_first.p, ws_m, ws_x, ws_y, ea);
+            });
         });
         PHM_HIP(hipGetLastError());
     }
@@ -633,17 +657,23 @@ int pst_group_run(mrp_context *ctx, const uint8_t *d_pool, const PhmModelDev *d_
         const int64_t n = tb0[c + 1] - tb0[c];
         if (n == 0) continue;
         const int W = WAVE_CLASS_CAP[c];
-        hipLaunchKernelGGL(pst_traceback_kernel, dim3((unsigned) n), dim3(PHM_WAVE), (size_t) 9 * W * sizeof(double), s, G.d_pairs.p + pair0[c],
-                           G.d_tbs.p + tb0[c], d_pool, d_models, G.d_band.p, G.d_cell_first.p, W, ws_m, ws_x, ws_y, cut, with_gaps, ragged_right, n_tb, G.d_cand.p,
-                           G.d_cand.p + cand, G.d_cand.p + 2 * cand, G.d_counts.p, G.d_total.p);
+        pst_with_emission(rle, [&](auto em, auto ea) {
+            using Em = typename decltype(em)::type;
+            hipLaunchKernelGGL(pst_traceback_kernel<Em>, dim3((unsigned) n), dim3(PHM_WAVE), (size_t) 9 * W * sizeof(double), s, G.d_pairs.p + pair0[c],
+                               G.d_tbs.p + tb0[c], d_pool, d_models, G.d_band.p, G.d_cell_first.p, W, ws_m, ws_x, ws_y, cut, with_gaps, ragged_right, n_tb, G.d_cand.p,
+                               G.d_cand.p + cand, G.d_cand.p + 2 * cand, G.d_counts.p, G.d_total.p, ea);
+        });
         PHM_HIP(hipGetLastError());
     }
     if (n_wide_tb > 0) {
         pst_with_wide_threads(H.wide_hook, [&](auto threads) {
             constexpr int T = decltype(threads)::value;
-            hipLaunchKernelGGL((pst_traceback_wide_kernel<T>), dim3((unsigned) wide_tgrid), dim3(T), 0, s, G.d_pairs.p + pair0[4], G.d_tbs.p + tb0[4], n_wide_tb,
-                               d_pool, d_models, G.d_band.p, G.d_cell_first.p, H.wide_width, ws_m, ws_x, ws_y, G.d_ws_back.p, cut, with_gaps, ragged_right, n_tb,
-                               G.d_cand.p, G.d_cand.p + cand, G.d_cand.p + 2 * cand, G.d_counts.p, G.d_total.p);
+            pst_with_emission(rle, [&](auto em, auto ea) {
+                using Em = typename decltype(em)::type;
+                hipLaunchKernelGGL((pst_traceback_wide_kernel<T, Em>), dim3((unsigned) wide_tgrid), dim3(T), 0, s, G.d_pairs.p + pair0[4], G.d_tbs.p + tb0[4],
+                                   n_wide_tb, d_pool, d_models, G.d_band.p, G.d_cell_first.p, H.wide_width, ws_m, ws_x, ws_y, G.d_ws_back.p, cut, with_gaps,
+                                   ragged_right, n_tb, G.d_cand.p, G.d_cand.p + cand, G.d_cand.p + 2 * cand, G.d_counts.p, G.d_total.p, ea);
+            });
         });
         PHM_HIP(hipGetLastError());
     }
@@ -759,17 +789,22 @@ int mrp_context_posterior_wide_count(mrp_context *ctx, int64_t *pairs_out, int64
     return MRP_OK;
 }
 
-/* The two entries.  dynamic: the band is band_constructDynamic's over anchor_expansion (one per anchor, indexed as the anchors are);
+/* The entries.  repeat: run-length emissions (the two arguments of the _rle entry), else the nucleotide ones.  dynamic: the band is band_constructDynamic's over anchor_expansion (one per anchor, indexed as the anchors are);
  * else band_construct's over opt->expansion.  Everything behind the band is the same call.  The order of the error classes is part of
  * the contract: MRP_ERR_ARG, then MRP_ERR_UNSUPPORTED, then MRP_ERR_NO_DEVICE. */
 static int pst_aligned_pairs(const char *who, bool dynamic, mrp_context *ctx, const mrp_pair_hmm *models, int32_t n_models, const PhmPairs &P,
                              const uint8_t *pool, int64_t pool_bytes, const int64_t *anchor_expansion, const mrp_posterior_options *opt,
                              mrp_posterior_pairs *match_out, mrp_posterior_pairs *gap_x_out, mrp_posterior_pairs *gap_y_out, double *total_out,
-                             mrp_pairhmm_stats *stats) {
+                             mrp_pairhmm_stats *stats, bool run_length = false, const mrp_repeat_model *repeat = nullptr, const uint8_t *counts = nullptr) {
     const double t_begin = now_ms();
     const int64_t n_pairs = P.n;
     int rc = pst_check_arguments(who, dynamic, models, n_models, P, pool, pool_bytes, anchor_expansion, opt, match_out, gap_x_out, gap_y_out);
     if (rc != MRP_OK) return rc;
+    PhmRle rle;
+    if (run_length) {
+        rc = phm_rle_check_and_build(who, repeat, n_models, counts, P, rle);
+        if (rc != MRP_OK) return rc;
+    }
     PstPlan plan;
     mrp_posterior_stats ps;
     memset(&ps, 0, sizeof(ps));
@@ -791,19 +826,24 @@ static int pst_aligned_pairs(const char *who, bool dynamic, mrp_context *ctx, co
         hipStream_t s = ctx->stream;
         static PerDeviceOnce once;
         const hipError_t configured = once.run([] {
-            hipError_t e = hipFuncSetAttribute((const void *) pst_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 9 * PHM_WAVE_MAX_WIDTH * (int) sizeof(double));
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute((const void *) pst_traceback_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 9 * PHM_WAVE_MAX_WIDTH * (int) sizeof(double));
+            constexpr int lds = 9 * PHM_WAVE_MAX_WIDTH * (int) sizeof(double);
+            const void *kernels[4] = {(const void *) pst_forward_kernel<PhmNucleotide>, (const void *) pst_traceback_kernel<PhmNucleotide>,
+                                      (const void *) pst_forward_kernel<PhmRunLength>, (const void *) pst_traceback_kernel<PhmRunLength>};
+            hipError_t e = hipSuccess;
+            for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, lds);
             return e;
         });
         PHM_HIP(configured);
         DevBuf<PhmModelDev> d_models;
         DevBuf<uint8_t> d_pool;
         d_models.pool = d_pool.pool = &ctx->pool;
+        PhmRleDev d_rle; /* the counts and tables of a run-length call */
         Drain drain{s};
         PHM_HIP(d_models.upload(hm, s));
         PHM_HIP(d_pool.alloc((size_t) pool_bytes));
         if (pool_bytes) PHM_HIP(hipMemcpyAsync(d_pool.p, pool, (size_t) pool_bytes, hipMemcpyHostToDevice, s));
+        if (run_length) PHM_HIP(d_rle.upload(&ctx->pool, rle, pool_bytes, s));
+        const PhmRunLength::Args rle_args{d_rle.d_counts.p, d_rle.d_models.p};
 
         /* the groups: consecutive pairs whose forward diagonals fit the workspace together */
         PstGroup G;
@@ -814,7 +854,7 @@ static int pst_aligned_pairs(const char *who, bool dynamic, mrp_context *ctx, co
             ps.groups++;
             n_scored += G.n_slot;
             if (G.n_slot > 0) {
-                rc = pst_group_run(ctx, d_pool.p, d_models.p, opt, G, ps);
+                rc = pst_group_run(ctx, d_pool.p, d_models.p, run_length ? &rle_args : nullptr, opt, G, ps);
                 if (rc != MRP_OK) return rc;
             }
             ctx->pool.reclaim(); /* the group's arrays are idle: the next group takes them */
@@ -869,6 +909,16 @@ int mrp_posterior_aligned_pairs_dynamic(mrp_context *ctx, const mrp_pair_hmm *mo
     return pst_aligned_pairs("mrp_posterior_aligned_pairs_dynamic", true, ctx, models, n_models,
                              PhmPairs{n_pairs, x_off, x_len, y_off, y_len, model_index, anchor_off, anchors}, pool, pool_bytes, anchor_expansion, opt, match_out,
                              gap_x_out, gap_y_out, total_out, stats);
+}
+
+int mrp_posterior_aligned_pairs_rle(mrp_context *ctx, const mrp_pair_hmm *models, const mrp_repeat_model *repeat, int32_t n_models, int64_t n_pairs,
+                                    const uint8_t *pool, const uint8_t *counts, int64_t pool_bytes, const int64_t *x_off, const int32_t *x_len,
+                                    const int64_t *y_off, const int32_t *y_len, const uint8_t *model_index, const int64_t *anchor_off, const int64_t *anchors,
+                                    const int64_t *anchor_expansion, const mrp_posterior_options *opt, mrp_posterior_pairs *match_out,
+                                    mrp_posterior_pairs *gap_x_out, mrp_posterior_pairs *gap_y_out, double *total_out, mrp_pairhmm_stats *stats) {
+    return pst_aligned_pairs("mrp_posterior_aligned_pairs_rle", anchor_expansion != nullptr, ctx, models, n_models,
+                             PhmPairs{n_pairs, x_off, x_len, y_off, y_len, model_index, anchor_off, anchors}, pool, pool_bytes, anchor_expansion, opt, match_out,
+                             gap_x_out, gap_y_out, total_out, stats, true, repeat, counts);
 }
 
 }  // extern "C"

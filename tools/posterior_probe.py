@@ -5,7 +5,12 @@ Two shapes: --short N pairs of 100 x ~97 with the reference's default parameters
 --long-len x --long-len anchored on the diagonal every 16 symbols (a band of 37 cells; a traceback every 1 000 diagonals).
 --wide adds a third: unanchored pairs of --wide-len x --wide-len (2 500: a widest diagonal of 2 501 cells, one traceback over the whole
 matrix), as many as the default posterior workspace holds, on the pair-per-workgroup kernels (posterior wide pairs on), with
-mrp_forward_probabilities' pair-per-workgroup kernel (wide pairs on) beside them."""
+mrp_forward_probabilities' pair-per-workgroup kernel (wide pairs on) beside them.
+--rle runs every shape a second time in the same run with run-length emissions (mrp_posterior_aligned_pairs_rle,
+mrp_forward_probabilities_rle): the same strings with counts 1 + geometric and the shipped repeat matrix of
+tests/golden/repeat_matrix_r94_g507.npz, and prints the run-length kernels' times with their ratio to the nucleotide ones.
+--tiny N (with --rle) adds what the pair-per-lane kernel is for, N unanchored pairs of 25 x ~25, to the forward entries alone: run-length
+pairs never take that kernel, so this is what a batch of short pairs pays for the pair-per-wave kernel in its place."""
 import argparse
 import os
 import sys
@@ -65,16 +70,30 @@ def pack(pairs):
             np.array(ao, np.int64), np.array(an, np.int64))
 
 
-def probe(ctx, models, name, pairs, opt, repeat):
+def shipped_repeat_model():
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "repeat_matrix_r94_g507.npz")
+    return capi.RepeatModel(np.load(path)["log_prob_F"], strand=1)
+
+
+def probe(ctx, models, name, pairs, opt, repeat, rle=False):
     pool, xo, xl, yo, yl, ao, an = pack(pairs)
     n = len(pairs)
-    rows = []
+    rows, rle_rows = [], []
+    if rle:
+        rm = [shipped_repeat_model()]
+        counts = np.minimum(np.random.default_rng(8).geometric(0.5, size=pool.size), rm[0].max_repeat - 1).astype(np.uint8)
     for r in range(repeat + 1):  # the first run warms the code objects and the context's pool
         match, _gx, _gy, total, st = capi.posterior_aligned_pairs(ctx, models, pool, xo, xl, yo, yl, None, ao, an, opt)
         ps = ctx.last_posterior()
         fwd, fst = capi.forward_probabilities(ctx, models, pool, xo, xl, yo, yl, None, ao, an, expansion=opt.expansion)
         if r:
             rows.append((ps.forward_ms, ps.traceback_ms, ps.total_ms, fst.kernel_ms, fst.total_ms))
+        if rle:  # the same strings, in the same run
+            rmatch, _gx, _gy, rtotal, _ = capi.posterior_aligned_pairs_rle(ctx, models, rm, pool, counts, xo, xl, yo, yl, None, ao, an, opt)
+            rps = ctx.last_posterior()
+            rfwd, rfst = capi.forward_probabilities_rle(ctx, models, rm, pool, counts, xo, xl, yo, yl, None, ao, an, expansion=opt.expansion)
+            if r:
+                rle_rows.append((rps.forward_ms, rps.traceback_ms, rps.total_ms, rfst.kernel_ms, rfst.total_ms))
     assert (total == fwd).all()
     f_ms, t_ms, call_ms, y_ms, ycall_ms = (float(np.median([row[k] for row in rows])) for k in range(5))
     print(f"{name}: {n} pairs, {ps.cells} band cells, {ps.traceback_cells} walked back, {ps.groups} group(s), with_gaps={int(opt.with_gaps)}, "
@@ -85,6 +104,36 @@ def probe(ctx, models, name, pairs, opt, repeat):
           f"({ps.candidates} candidates)", flush=True)
     print(f"  mrp_forward_probabilities on the same pairs: kernel {y_ms:.3f} ms  {fst.cells / y_ms * 1e3:.3e} cells/s, call {ycall_ms:.3f} ms "
           f"(lane {fst.pairs_lane}, wave {fst.pairs_wave})", flush=True)
+    if rle:
+        assert (rtotal == rfwd).all()
+        rf_ms, rt_ms, rcall_ms, ry_ms, _ = (float(np.median([row[k] for row in rle_rows])) for k in range(5))
+        print(f"  run-length emissions on the same strings ({int(rmatch['first'][-1])} match pairs; lane {rfst.pairs_lane}, wave {rfst.pairs_wave}):", flush=True)
+        print(f"    forward kernel   {rf_ms:9.3f} ms  x{rf_ms / f_ms:.3f} of the nucleotide kernel", flush=True)
+        print(f"    traceback kernel {rt_ms:9.3f} ms  x{rt_ms / t_ms:.3f}", flush=True)
+        print(f"    call             {rcall_ms:9.3f} ms  x{rcall_ms / call_ms:.3f}", flush=True)
+        print(f"    mrp_forward_probabilities_rle kernel {ry_ms:.3f} ms  x{ry_ms / y_ms:.3f} of mrp_forward_probabilities' (which runs {fst.pairs_lane} pairs a lane)",
+              flush=True)
+
+
+def tiny_forward(ctx, models, n, repeat):
+    """N pairs of 25 x ~25: mrp_forward_probabilities (a pair per lane) against mrp_forward_probabilities_rle (a pair per wave, class 64)"""
+    rng = np.random.default_rng(9)
+    pairs = []
+    for _ in range(n):
+        sx = synth.random_sequence(rng, 25)
+        pairs.append((sx, synth.evolve_sequence(rng, sx, 0.05, 0.05, 0.05), []))
+    pool, xo, xl, yo, yl, ao, an = pack(pairs)
+    rm = [shipped_repeat_model()]
+    counts = np.minimum(rng.geometric(0.5, size=pool.size), rm[0].max_repeat - 1).astype(np.uint8)
+    rows = []
+    for r in range(repeat + 1):
+        _, a = capi.forward_probabilities(ctx, models, pool, xo, xl, yo, yl, expansion=20)
+        _, b = capi.forward_probabilities_rle(ctx, models, rm, pool, counts, xo, xl, yo, yl, expansion=20)
+        if r:
+            rows.append((a.kernel_ms, b.kernel_ms))
+    lane_ms, wave_ms = (float(np.median([row[k] for row in rows])) for k in range(2))
+    print(f"tiny: {n} pairs of 25 x ~25, {a.cells} cells: mrp_forward_probabilities kernel {lane_ms:.3f} ms (lane {a.pairs_lane}, wave {a.pairs_wave}), "
+          f"mrp_forward_probabilities_rle kernel {wave_ms:.3f} ms (lane {b.pairs_lane}, wave {b.pairs_wave})  x{wave_ms / lane_ms:.3f}", flush=True)
 
 
 def main():
@@ -96,19 +145,23 @@ def main():
     ap.add_argument("--wide-len", type=int, default=2500)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--with-gaps", type=int, default=0)
+    ap.add_argument("--rle", action="store_true")
+    ap.add_argument("--tiny", type=int, default=0)
     args = ap.parse_args()
     models = [capi.PairHmm.default_nucleotide()]
     opt = capi.PosteriorOptions(with_gaps=bool(args.with_gaps))  # threshold 0.01, expansion 20, 1 000 / 40
     with capi.Context(0) as ctx:
         if args.short:
-            probe(ctx, models, "short", short_pairs(args.short, 5), opt, args.repeat)
+            probe(ctx, models, "short", short_pairs(args.short, 5), opt, args.repeat, args.rle)
         if args.long:
-            probe(ctx, models, "long", long_pairs(args.long, args.long_len, 6), opt, args.repeat)
+            probe(ctx, models, "long", long_pairs(args.long, args.long_len, 6), opt, args.repeat, args.rle)
+        if args.tiny and args.rle:
+            tiny_forward(ctx, models, args.tiny, args.repeat)
         if args.wide:
             ctx.set_posterior_wide_pairs(True)
             ctx.set_wide_pairs(True)  # the yardstick's own switch
             before = ctx.posterior_wide_count()
-            probe(ctx, models, "wide", wide_pairs(args.wide_len, 7), opt, args.repeat)
+            probe(ctx, models, "wide", wide_pairs(args.wide_len, 7), opt, args.repeat, args.rle)
             after = ctx.posterior_wide_count()
             print(f"  the pair-per-workgroup kernels took {after[0] - before[0]} pairs, {after[1] - before[1]} band cells over {args.repeat + 1} runs", flush=True)
 
