@@ -667,8 +667,9 @@ typedef struct mrp_repeat_model {
  * n < 0 or max_repeat outside [2, 256]. */
 int64_t mrp_rle_compress(const char *s, int64_t n, int32_t max_repeat, uint8_t *symbols_out, uint8_t *counts_out);
 /* mrp_forward_probabilities with run-length emissions: repeat[i] belongs to models[i], counts is parallel to pool (pool_bytes bytes).
- * Honours mrp_context_set_wide_pairs.  Every pair runs on the pair-per-wave kernel (or, wide, the pair-per-workgroup one): stats counts
- * none in pairs_lane.  MRP_ERR_ARG, before the context is looked at and with nothing written: what mrp_forward_probabilities checks of its
+ * Honours mrp_context_set_wide_pairs.  By default every pair runs on the pair-per-wave kernel (or, wide, the pair-per-workgroup one) and
+ * stats counts none in pairs_lane; with mrp_context_set_rle_lane_pairs on (below) the eligible pairs run a pair per lane, bit for bit
+ * the same values.  MRP_ERR_ARG, before the context is looked at and with nothing written: what mrp_forward_probabilities checks of its
  * arrays; a NULL repeat, counts or log_prob; max_repeat outside [2, 256]; a strand that is neither 0 nor 1; a count >= the max_repeat of
  * its pair's model (the message names the pair).  Then MRP_ERR_NO_DEVICE for a NULL context; the rest as mrp_forward_probabilities. */
 int mrp_forward_probabilities_rle(mrp_context *ctx, const mrp_pair_hmm *models, const mrp_repeat_model *repeat, int32_t n_models, int64_t n_pairs,
@@ -686,6 +687,41 @@ int mrp_posterior_aligned_pairs_rle(mrp_context *ctx, const mrp_pair_hmm *models
                                     const int64_t *anchors, const int64_t *anchor_expansion, const mrp_posterior_options *opt,
                                     mrp_posterior_pairs *match_out, mrp_posterior_pairs *gap_x_out, mrp_posterior_pairs *gap_y_out,
                                     double *total_out /* [n_pairs], may be NULL */, mrp_pairhmm_stats *stats);
+/* Run-length lane pairs.  off (default): mrp_forward_probabilities_rle is what it was, every pair on the pair-per-wave
+ * (or pair-per-workgroup) kernel, pairs_lane == 0.  on: the pairs of a call that are eligible run on the run-length instantiation of the
+ * pair-per-lane kernel and are counted in pairs_lane; the others keep their kernel, so one call may mix both.  Eligible: no anchors, an x
+ * string within the caps of mrp_rle_lane_caps, and every count of both strings below that function's count bound.  The values are bit
+ * for bit those of the switch off.  The posterior entries do not read it.  MRP_ERR_ARG for a NULL context. */
+int mrp_context_set_rle_lane_pairs(mrp_context *ctx, int on);
+/* Host only, no device: for a run-length batch of n_models models, cap_out[c] = the longest x string (in run-length symbols) of launch
+ * class c of the pair-per-lane kernel (4, 3, 2, 1 waves per workgroup: non-decreasing, at most 100), -1 throughout where the tables of
+ * that many models leave no room for a row (no pair is eligible then); *count_bound_out = the bound every count of an eligible pair lies
+ * below.  Either output may be NULL.  MRP_ERR_ARG for n_models <= 0. */
+int mrp_rle_lane_caps(int32_t n_models, int32_t cap_out[4], int32_t *count_bound_out);
+/* Bubble.alleleReadSupports with run-length emissions: the two polish loops of bubbleGraph.c:1028-1075 and :1193-1244 as one call.
+ * Bubbles, alleles, reads, offsets and the layout of support are those of mrp_allele_read_supports (x = allele, y = read substring; entry
+ * j * readNo + k of a bubble, bubbles concatenated); counts is parallel to pool.  A read on the forward strand takes forward_model with
+ * forward_repeat, else reverse_model with reverse_repeat.  Both loops pass an empty anchor list, so no pair is anchored and there is no
+ * sv_threshold.  The first read of a bubble with a given substring owns the scores (:1045-1055) and later equal ones copy them, whatever
+ * their strand; equal means equal symbols and equal counts as given.  Every support is rounded to float (:1069).  Eligible pairs always
+ * run a pair per lane (mrp_rle_lane_caps), whatever mrp_context_set_rle_lane_pairs says; mrp_context_set_wide_pairs is honoured for a pair
+ * beyond 2 048 cells.
+ *   One corner differs from the reference.  Its cache is keyed by the EXPANDED string (rleString_expandedStringEqualKey), so two
+ * substrings that differ only in runs of max_repeat - 1 or more are distinct there, while here, after the caller's clamp
+ * (mrp_rle_compress), they are equal and the later one copies.  Their scores agree all the same, the emissions read the clamped counts,
+ * unless the two reads lie on different strands: then the reference scores the later read with its own strand's model and this call
+ * copies the earlier one's.
+ *   MRP_ERR_ARG, before the context is looked at and with nothing written: n_bubbles < 0 or pool_bytes < 0; a NULL model, repeat model,
+ * array or (with any symbol) counts; offsets not from 0 or not ascending; an allele or read substring outside the pool; the checks of
+ * mrp_forward_probabilities_rle on the two repeat models; a count >= the max_repeat of the model its pair is scored with (the message
+ * names bubble, allele or read, and symbol); an odd or negative expansion.  Then MRP_ERR_NO_DEVICE for a NULL context; the rest as
+ * mrp_forward_probabilities_rle.  stats may be NULL: pairs_lane + pairs_wave = the owners' pairs. */
+int mrp_allele_read_supports_rle(mrp_context *ctx, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                                 const mrp_repeat_model *forward_repeat, const mrp_repeat_model *reverse_repeat, int64_t n_bubbles,
+                                 const int64_t *allele_first, const int64_t *read_first, const uint8_t *pool, const uint8_t *counts,
+                                 int64_t pool_bytes, const int64_t *allele_off, const int32_t *allele_len, const int64_t *read_off,
+                                 const int32_t *read_len, const uint8_t *read_forward_strand, int64_t expansion, float *support,
+                                 mrp_pairhmm_stats *stats);
 /* Posterior wide pairs.  off (default, and for a NULL context): both posterior entries refuse a pair whose widest diagonal exceeds
  * 2 048 cells.  on: such a pair runs on two kernels of its own, a pair per workgroup forward and a (pair, traceback) per workgroup
  * backward, bit-identical to the pair-per-wave ones; pairs of up to 2 048 cells keep their kernels and launch classes,

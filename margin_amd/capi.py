@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "mrp_band_diagonals_dynamic", "mrp_pair_diagonal_width_dynamic", "mrp_posterior_tracebacks_dynamic", "mrp_posterior_aligned_pairs_dynamic",
     "mrp_context_set_posterior_wide_pairs", "mrp_context_posterior_wide_count",
     "mrp_rle_compress", "mrp_forward_probabilities_rle", "mrp_posterior_aligned_pairs_rle",
+    "mrp_context_set_rle_lane_pairs", "mrp_rle_lane_caps", "mrp_allele_read_supports_rle",
 ]
 
 
@@ -535,6 +536,10 @@ def load():
     L.mrp_forward_probabilities_rle.argtypes = [vp, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, P(PairHmmStats)]
     L.mrp_posterior_aligned_pairs_rle.argtypes = [vp, vp, vp, i32, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, P(PosteriorOptions), P(PosteriorPairs),
                                                   P(PosteriorPairs), P(PosteriorPairs), vp, P(PairHmmStats)]
+    L.mrp_context_set_rle_lane_pairs.argtypes = [vp, C.c_int]
+    L.mrp_rle_lane_caps.argtypes = [i32, vp, P(i32)]
+    L.mrp_allele_read_supports_rle.argtypes = [vp, P(PairHmm), P(PairHmm), P(RepeatModelStruct), P(RepeatModelStruct), i64, vp, vp, vp, vp, i64, vp, vp, vp, vp,
+                                               vp, i64, vp, P(PairHmmStats)]
     L.mrp_context_set_posterior_wide_pairs.argtypes = [vp, C.c_int]
     L.mrp_context_posterior_wide_count.argtypes = [vp, P(i64), P(i64)]
     L.mrp_allele_read_supports.argtypes = [vp, P(PairHmm), P(PairHmm), i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, P(PairHmmStats)]
@@ -666,6 +671,10 @@ class Context:
         pairs, cells = C.c_int64(), C.c_int64()
         _check(load().mrp_context_posterior_wide_count(self.h, C.byref(pairs), C.byref(cells)))
         return pairs.value, cells.value
+
+    def set_rle_lane_pairs(self, on):
+        """mrp_context_set_rle_lane_pairs: forward_probabilities_rle runs its eligible pairs (unanchored, within rle_lane_caps) a pair per lane"""
+        _check(load().mrp_context_set_rle_lane_pairs(self.h, int(bool(on))))
 
     def set_wide_pairs(self, on):
         """mrp_context_set_wide_pairs: pairs whose widest diagonal exceeds 2 048 cells are aligned, not refused (up to WIDE_MAX_WIDTH / WIDE_MAX_CELLS)"""
@@ -1535,6 +1544,54 @@ def allele_read_supports(ctx: Context, forward_model: PairHmm, reverse_model: Pa
     ptr = lambda a: None if a.size == 0 else a.ctypes.data
     _check(load().mrp_allele_read_supports(ctx.h, C.byref(forward_model), C.byref(reverse_model), len(bubbles), af.ctypes.data, rf.ctypes.data,
                                            ptr(pool), pool.size, ptr(ao), ptr(al), ptr(ro), ptr(rl), ptr(sd), int(expansion), int(sv_threshold), ptr(sup), C.byref(st)))
+    out, p = [], 0
+    for b, sz in enumerate(sizes):
+        out.append(sup[p:p + int(sz)].reshape(int(af[b + 1] - af[b]), int(rf[b + 1] - rf[b])))
+        p += int(sz)
+    return out, st
+
+
+def rle_lane_caps(n_models: int):
+    """mrp_rle_lane_caps (host only) -> ([cap of launch class 0..3], count bound): the longest x string of the pair-per-lane kernel's launch
+    classes for a run-length batch of n_models models (-1: no row fits) and the bound every count of an eligible pair lies below"""
+    cap = np.zeros(4, dtype=np.int32)
+    bound = C.c_int32(0)
+    _check(load().mrp_rle_lane_caps(int(n_models), cap.ctypes.data, C.byref(bound)))
+    return [int(c) for c in cap], int(bound.value)
+
+
+def allele_read_supports_rle(ctx, forward_model: PairHmm, reverse_model: PairHmm, forward_repeat, reverse_repeat, bubbles, expansion: int = 4):
+    """mrp_allele_read_supports_rle: bubbles a list of (alleles, allele_counts, reads, read_counts, read_forward_strand), alleles / reads lists
+    of uint8 symbol arrays and the counts lists of uint8 arrays parallel to them; forward_repeat / reverse_repeat a RepeatModel each.
+    Returns ([float32 array [n_alleles, n_reads] per bubble], PairHmmStats): Bubble.alleleReadSupports of the polish loops
+    (bubbleGraph.c:1028-1075, :1193-1244).  ctx may be None (the checks that need no device)."""
+    strings, cnts, a_first, r_first, a_len, r_len, strand = [], [], [0], [0], [], [], []
+    a_off, r_off, pos = [], [], 0
+    for alleles, allele_counts, reads, read_counts, fwd in bubbles:
+        for a, c in zip(alleles, allele_counts):
+            a = np.ascontiguousarray(a, dtype=np.uint8)
+            strings.append(a); cnts.append(np.ascontiguousarray(c, dtype=np.uint8)); a_off.append(pos); a_len.append(len(a)); pos += len(a)
+        for r, c in zip(reads, read_counts):
+            r = np.ascontiguousarray(r, dtype=np.uint8)
+            strings.append(r); cnts.append(np.ascontiguousarray(c, dtype=np.uint8)); r_off.append(pos); r_len.append(len(r)); pos += len(r)
+        strand.extend(int(bool(x)) for x in fwd)
+        a_first.append(len(a_off))
+        r_first.append(len(r_off))
+    pool = np.concatenate(strings) if strings else np.zeros(0, dtype=np.uint8)
+    counts = np.concatenate(cnts) if cnts else np.zeros(0, dtype=np.uint8)
+    assert counts.size == pool.size, "counts must be parallel to the symbols"
+    af, rf = np.array(a_first, dtype=np.int64), np.array(r_first, dtype=np.int64)
+    ao, al = np.array(a_off, dtype=np.int64), np.array(a_len, dtype=np.int32)
+    ro, rl = np.array(r_off, dtype=np.int64), np.array(r_len, dtype=np.int32)
+    sd = np.array(strand, dtype=np.uint8)
+    sizes = [(af[b + 1] - af[b]) * (rf[b + 1] - rf[b]) for b in range(len(bubbles))]
+    sup = np.zeros(int(sum(sizes)), dtype=np.float32)
+    st = PairHmmStats()
+    fr, rr = forward_repeat.struct(), reverse_repeat.struct()
+    ptr = lambda a: None if a.size == 0 else a.ctypes.data
+    _check(load().mrp_allele_read_supports_rle(ctx.h if ctx is not None else None, C.byref(forward_model), C.byref(reverse_model), C.byref(fr), C.byref(rr),
+                                               len(bubbles), af.ctypes.data, rf.ctypes.data, ptr(pool), ptr(counts), pool.size, ptr(ao), ptr(al), ptr(ro), ptr(rl),
+                                               ptr(sd), int(expansion), ptr(sup), C.byref(st)))
     out, p = [], 0
     for b, sz in enumerate(sizes):
         out.append(sup[p:p + int(sz)].reshape(int(af[b + 1] - af[b]), int(rf[b + 1] - rf[b])))

@@ -205,6 +205,11 @@ int mrp_context_set_wide_pairs(mrp_context *ctx, int on) {
     ctx->wide_pairs = on != 0;
     return MRP_OK;
 }
+int mrp_context_set_rle_lane_pairs(mrp_context *ctx, int on) {
+    if (!ctx) return mrp_set_error(MRP_ERR_ARG, "mrp_context_set_rle_lane_pairs: context is NULL");
+    ctx->rle_lane_pairs = on != 0;
+    return MRP_OK;
+}
 int mrp_context_wide_pair_count(mrp_context *ctx, int64_t *pairs_out, int64_t *cells_out) {
     if (!ctx) return mrp_set_error(MRP_ERR_ARG, "mrp_context_wide_pair_count: context is NULL");
     if (pairs_out) *pairs_out = ctx->wide_pair_count;

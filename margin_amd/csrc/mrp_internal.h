@@ -387,6 +387,7 @@ struct mrp_context {
     std::vector<struct mrp_batch *> spare_batches;
     int posterior_wide_pairs = 0; /* mrp_context_set_posterior_wide_pairs: the posterior entries run pairs beyond 2 048 cells on their pair-per-workgroup kernels */
     int64_t posterior_wide_count = 0, posterior_wide_cells = 0; /* what those kernels have taken on this context (mrp_context_posterior_wide_count) */
+    int rle_lane_pairs = 0; /* mrp_context_set_rle_lane_pairs: mrp_forward_probabilities_rle runs its eligible pairs on the pair-per-lane kernel */
 };
 
 struct mrp_chunk {

@@ -35,6 +35,7 @@ struct PhmRle {
     HostVec<double> rep;
     std::vector<int64_t> rep_first; /* model i's table in rep */
     std::vector<int32_t> R;
+    HostVec<double> rep_lane; /* [model][cx][u][o], u, o below the count bound of the pair-per-lane kernel: what that kernel stages in LDS */
 };
 /* (mrp_pairhmm.hip) every MRP_ERR_ARG of the two run-length entries; builds the tables.  The count check is what keeps every table
  * index of the kernels in range. */
@@ -48,6 +49,7 @@ struct PhmRleDev {
     DevBuf<uint8_t> d_counts{arrays};
     DevBuf<double> d_rep{arrays};
     DevBuf<PhmRepeatDev> d_models{arrays};
+    DevBuf<double> d_rep_lane{arrays}; /* phm_enqueue uploads it when the batch has lane pairs */
     hipError_t upload(DevPool *pool, const PhmRle &H, int64_t pool_bytes, hipStream_t s) {
         arrays.bind(pool);
         hipError_t e = d_counts.alloc((size_t) pool_bytes);
@@ -162,7 +164,9 @@ struct PhmLaunch {
     int64_t wide_cells = 0;      /* their share of cells */
     HostVec<int32_t> band;
     HostVec<uint32_t> key; /* phm_classify's sort keys (released with the launch, not between its two halves) */
-    const PhmRle *rle = nullptr; /* set before phm_classify: run-length emissions; no pair goes to the pair-per-lane kernel */
+    const PhmRle *rle = nullptr; /* set before phm_classify: run-length emissions */
+    bool rle_lane = false;       /* set before phm_classify: a run-length batch's eligible pairs (unanchored, x within the cap, every count
+                                  * below the kernel's bound) go to the pair-per-lane kernel; off: none does */
 };
 struct PhmDev {
     hipStream_t s = nullptr;
@@ -181,6 +185,8 @@ struct PhmDev {
     }
 };
 
+/* (mrp_pairhmm.hip) the x-length caps of the pair-per-lane kernel's four launch classes, -1 where no row fits; returns the tables' bytes */
+int phm_lane_caps(int n_models, bool rle, int cap[4]);
 /* wide_pairs: the caller's setting (mrp_context_set_wide_pairs / mrp_queue_set_wide_pairs); 0 is the refusal beyond PHM_WAVE_MAX_WIDTH */
 int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, int64_t pool_bytes, const PhmPairs &P, int64_t expansion,
                  int ragged_left, int ragged_right, int wide_pairs, PhmLaunch &L);
@@ -199,11 +205,12 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
 template <class Reduce>
 int phm_call(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, int32_t n_models, const uint8_t *pool, int64_t pool_bytes,
              const PhmPairs &P, int64_t expansion, int ragged_left, int ragged_right, mrp_pairhmm_stats *stats, double t_begin, Reduce reduce,
-             const PhmRle *rle = nullptr) {
+             const PhmRle *rle = nullptr, bool rle_lane = false) {
     hipStream_t s = ctx->stream;
     {
         PhmLaunch H;
         H.rle = rle;
+        H.rle_lane = rle_lane;
         PhmDev L;
         if (P.n > 0) { /* (the host's errors first, then the device: phm_enqueue makes it current) */
             int rc = phm_classify(who, models, n_models, pool_bytes, P, expansion, ragged_left, ragged_right, ctx->wide_pairs, H);
@@ -231,7 +238,7 @@ int phm_call(mrp_context *ctx, const char *who, const mrp_pair_hmm *models, int3
 }
 
 void substring_owners(int64_t n_groups, const int64_t *first, const uint8_t *pool, const int64_t *off, const int32_t *len,
-                      const uint8_t *may_own, bool last, std::vector<int64_t> &owner);
+                      const uint8_t *may_own, bool last, std::vector<int64_t> &owner, const uint8_t *counts = nullptr);
 
 /* stMath_logAddExact (sonLib), as mrp_kernels.hip and rphmm_frame.c state it */
 static __device__ __forceinline__ double ht_log_add_exact(double x, double y) {

@@ -24,7 +24,9 @@
  *   phm_wide_kernel   a pair per WORKGROUP for the pairs beyond that, when the caller has turned wide pairs on (else they are
  *                     refused): the diagonals in a device workspace.  Both are the walk of mrp_pairhmm_walk.h, and
  *                     both exist a second time with the run-length emissions of margin polish (mrp_forward_probabilities_rle,
- *                     DESIGN.md 9.16), whose pairs never take the pair-per-lane kernel.
+ *                     DESIGN.md 9.16).  So does phm_lane_kernel, for the unanchored pairs whose counts are all
+ *                     below PHM_LANE_RLE_COUNTS: mrp_allele_read_supports_rle always sends them there, mrp_forward_probabilities_rle
+ *                     once mrp_context_set_rle_lane_pairs is on; every other run-length pair keeps the two kernels above.
  *
  * Bound: fp64 VALU issue (six logAdd per cell); the kernels move ~0.1 B per flop.
  */
@@ -55,6 +57,31 @@ constexpr int PHM_LDS_BYTES = 160 * 1024;
 #define PHM_ROWS 2 /* rows a lane of the pair-per-lane kernel advances together (measured: 1 -> 2.49 ms, 2 -> 2.11, 3 -> 2.75, 4 -> 2.61, 6 -> 3.23 for 4.8e5 pairs) */
 constexpr int PHM_LANE_BYTES_PER_X = 3 * 64 * 8 + 64; /* LDS per wave and x position: three states per lane + the lane's symbol */
 constexpr int PHM_ETAB = 25 * 6;       /* doubles per model in the emission + transition table */
+/* The run-length instantiation of the pair-per-lane kernel: a pair is eligible only if every count of both its strings
+ * is below this bound, so that the part of the models' repeat tables a wave can ask for, rep_c[model][cx][u][o] with u, o below the
+ * bound, lies in LDS beside the other tables (5 * 16 * 16 * 8 B = 10 240 B per model) and a symbol (0..4) with its count fits the byte
+ * the row keeps per x position. */
+constexpr int PHM_LANE_RLE_COUNTS = 16;
+constexpr int PHM_LANE_RLE_REP = 5 * PHM_LANE_RLE_COUNTS * PHM_LANE_RLE_COUNTS; /* doubles per model in the compact repeat table */
+static_assert(4 + ((PHM_LANE_RLE_COUNTS - 1) << 3) < 256, "a symbol and its count share a byte");
+
+/* The tables of the pair-per-lane kernel in LDS, in doubles: coef | etab, and for run-length emissions em | rep_c behind them */
+constexpr int phm_lane_table_doubles(int n_models, bool rle) { return 16 + n_models * (PHM_ETAB + (rle ? 25 + PHM_LANE_RLE_REP : 0)); }
+
+/* The match emission of the pair-per-lane kernel, a policy as in the diagonal kernels (mrp_pairhmm_walk.h).  PhmLaneNucleotide: the
+ * model's table, already summed with the three match transitions in etab.  PhmLaneRunLength: em[cx * 5 + cy] + rep_c[cx][u][o] added per
+ * cell, then the transition (getRleNucleotideMatchProb, stateMachine.c:733-738; the association of phm_cell), both tables in LDS. */
+struct PhmLaneNucleotide {
+    static constexpr bool RLE = false;
+    struct Args {};
+};
+struct PhmLaneRunLength {
+    static constexpr bool RLE = true;
+    struct Args {
+        const uint8_t *counts; /* parallel to the symbol pool; every count of a lane pair is below PHM_LANE_RLE_COUNTS */
+        const double *rep_c;   /* [model][cx][u][o], u, o < PHM_LANE_RLE_COUNTS: PhmRle::rep_lane */
+    };
+};
 
 /* The same two functions with the coefficients of the interval read from LDS (coef[interval][c3, c2, c1, c0]) instead
  * of selected with 24 v_cndmask: the pair-per-lane kernel is bound by VALU issue, its LDS pipe is mostly idle */
@@ -90,7 +117,10 @@ static __device__ __forceinline__ double phm_chain_t(double a, double b, double 
 }
 
 /* LDS: coef[16] | etab[n_models][cx][cy][6] = eX + {open, extend, switch to x}, eM + {continue, from x, from y} |
- * rows[wave][x - 1][state][lane].  The waves of a workgroup share the tables and nothing else.
+ * (run-length emissions only: em[n_models][cx][cy] | rep_c[n_models][cx][u][o]) | rows[wave][x - 1][state][lane].  The waves of a
+ * workgroup share the tables and nothing else.  With run-length emissions the byte a row keeps per x position and the int a lane
+ * keeps per y position hold symbol | count << 3; a slot that stands for no symbol holds 4 (N, count 0), so every table index of a
+ * padding lane and of a cell beyond a lane's own strings is in range as well.
  *
  * A lane walks its matrix R rows at a time, row r one column behind row r - 1 (x_r = k - r in step k), so the R cells
  * of a step depend only on cells of earlier steps: left = the row's own cell of step k - 1, up / diagonal = the cells
@@ -98,14 +128,17 @@ static __device__ __forceinline__ double phm_chain_t(double a, double b, double 
  * row of the previous pass) and only the last row writes it.  With one wave per SIMD this is what hides the latency of
  * the dependent fp64 chains and of the table reads: R * 3 independent chains per step instead of 3.
  * Cells beyond a lane's own strings are computed and ignored: nothing flows from larger x or y to smaller. */
-template <int R, bool HAS_SWITCH>
+template <int R, bool HAS_SWITCH, class Em>
 __global__ void __launch_bounds__(256) phm_lane_kernel(const PhmLanePair *__restrict__ pairs, int64_t n_pairs, const uint8_t *__restrict__ pool,
-                                                       const PhmModelDev *__restrict__ models, int n_models, int cap, double *__restrict__ out) {
+                                                       const PhmModelDev *__restrict__ models, int n_models, int cap, double *__restrict__ out,
+                                                       typename Em::Args ea) {
     extern __shared__ double phm_lds[];
     double *coef = phm_lds;
     double *etab = phm_lds + 16;
     const int lane = threadIdx.x & (PHM_WAVE - 1), wave = threadIdx.x / PHM_WAVE, n_waves = blockDim.x / PHM_WAVE;
-    uint8_t *wave_base = reinterpret_cast<uint8_t *>(etab + (size_t) n_models * PHM_ETAB) + (size_t) wave * cap * PHM_LANE_BYTES_PER_X;
+    [[maybe_unused]] double *em_l = etab + (size_t) n_models * PHM_ETAB; /* run-length emissions: em | rep_c */
+    [[maybe_unused]] double *rep_l = em_l + (size_t) n_models * 25;
+    uint8_t *wave_base = reinterpret_cast<uint8_t *>(phm_lds + phm_lane_table_doubles(n_models, Em::RLE)) + (size_t) wave * cap * PHM_LANE_BYTES_PER_X;
     double *row = reinterpret_cast<double *>(wave_base) + lane;          /* [x - 1][state][lane] */
     uint8_t *symx = wave_base + (size_t) cap * 3 * PHM_WAVE * sizeof(double) + lane; /* [x - 1][lane]: the lane's x string */
     if (threadIdx.x < 16) coef[threadIdx.x] = (double) PHM_COEF[threadIdx.x];
@@ -120,7 +153,10 @@ __global__ void __launch_bounds__(256) phm_lane_kernel(const PhmLanePair *__rest
         e[3] = eM + Mi->t[0];
         e[4] = eM + Mi->t[1];
         e[5] = eM + Mi->t[2];
+        if constexpr (Em::RLE) em_l[i] = eM;
     }
+    if constexpr (Em::RLE)
+        for (int i = threadIdx.x; i < n_models * PHM_LANE_RLE_REP; i += blockDim.x) rep_l[i] = ea.rep_c[i];
     __syncthreads();
     const int64_t pi = ((int64_t) blockIdx.x * n_waves + wave) * PHM_WAVE + lane;
     const bool have = pi < n_pairs;
@@ -134,10 +170,19 @@ __global__ void __launch_bounds__(256) phm_lane_kernel(const PhmLanePair *__rest
     const double t_open_y = M->t[4], t_extend_y = M->t[6], t_switch_y = M->t[8];
     const uint8_t *__restrict__ sx = pool + p.x_off;
     const uint8_t *__restrict__ sy = pool + p.y_off;
+    /* symbol i of a string, with run-length emissions | its count << 3 */
+    const auto sym_of = [&](const uint8_t *__restrict__ str, int64_t off, int i) {
+        int c = str[i];
+        c = c > 4 ? 4 : c;
+        if constexpr (Em::RLE) c |= (int) ea.counts[off + i] << 3;
+        return c;
+    };
+    [[maybe_unused]] double t_match[3] = {0.0, 0.0, 0.0};
+    if constexpr (Em::RLE) { t_match[0] = M->t[0]; t_match[1] = M->t[1]; t_match[2] = M->t[2]; }
     /* no global loads inside the step loop (the compiler waits for each one on the spot): the x string goes to LDS */
     for (int x = 1; x <= mx1; x++) {
         int c = 4;
-        if (x <= lx) { c = sx[x - 1]; c = c > 4 ? 4 : c; }
+        if (x <= lx) c = sym_of(sx, p.x_off, x - 1);
         symx[(x - 1) * PHM_WAVE] = (uint8_t) c;
 #pragma unroll
         for (int s = 0; s < 3; s++) row[((x - 1) * 3 + s) * PHM_WAVE] = PHM_NEG;
@@ -146,23 +191,30 @@ __global__ void __launch_bounds__(256) phm_lane_kernel(const PhmLanePair *__rest
     St b_prev = neg; /* cell (0, y0 - 1) */
     St fin = neg;    /* cell (lx, ly) */
     const double *__restrict__ etab_m = etab + (size_t) p.model * PHM_ETAB;
+    [[maybe_unused]] const double *__restrict__ em_m = em_l + (size_t) p.model * 25;
+    [[maybe_unused]] const double *__restrict__ rep_m = rep_l + (size_t) p.model * PHM_LANE_RLE_REP;
     int cy_next[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
         cy_next[r] = 4;
-        if (r >= 1 && r <= ly) { cy_next[r] = sy[r - 1]; cy_next[r] = cy_next[r] > 4 ? 4 : cy_next[r]; }
+        if (r >= 1 && r <= ly) cy_next[r] = sym_of(sy, p.y_off, r - 1);
     }
     for (int y0 = 0; y0 <= my; y0 += R) {
         const double *etab_r[R];
+        [[maybe_unused]] const double *em_r[R], *rep_r[R]; /* run-length emissions: the row's column of em and of rep_c */
         double ty_open[R], ty_extend[R], ty_switch[R];
         St b0[R]; /* cell (0, y0 + r): only the gap-y state can be reached */
 #pragma unroll
         for (int r = 0; r < R; r++) {
             const int y = y0 + r;
-            const int cy = cy_next[r];
+            const int cy = Em::RLE ? cy_next[r] & 7 : cy_next[r];
+            if constexpr (Em::RLE) {
+                em_r[r] = em_m + cy;
+                rep_r[r] = rep_m + (cy_next[r] >> 3);
+            }
             /* the y symbols of the next pass are requested now and waited for after the step loop */
             cy_next[r] = 4;
-            if (y + R <= ly) { cy_next[r] = sy[y + R - 1]; cy_next[r] = cy_next[r] > 4 ? 4 : cy_next[r]; }
+            if (y + R <= ly) cy_next[r] = sym_of(sy, p.y_off, y + R - 1);
             const double eY = M->ey[cy];
             ty_open[r] = eY + t_open_y;
             ty_extend[r] = eY + t_extend_y;
@@ -194,11 +246,21 @@ __global__ void __launch_bounds__(256) phm_lane_kernel(const PhmLanePair *__rest
                 const St left = c1[r];
                 const St up = r == 0 ? up0 : c1[r > 0 ? r - 1 : 0];
                 const St diag = r == 0 ? up0_prev : c2[r > 0 ? r - 1 : 0];
-                const double2 *__restrict__ e = reinterpret_cast<const double2 *>(etab_r[r] + cxs[r] * 30);
-                const double2 e01 = e[0], e23 = e[1], e45 = e[2];
                 St cur;
-                cur.x = phm_chain_t<HAS_SWITCH>(left.m + e01.x, left.x + e01.y, left.y + e23.x, coef);
-                cur.m = phm_chain_t<true>(diag.m + e23.y, diag.x + e45.x, diag.y + e45.y, coef);
+                if constexpr (Em::RLE) {
+                    const int cx = cxs[r] & 7, u = cxs[r] >> 3;
+                    const double2 *__restrict__ e = reinterpret_cast<const double2 *>(etab_r[r] + cx * 30);
+                    const double2 e01 = e[0];
+                    const double e2 = etab_r[r][cx * 30 + 2];
+                    const double eM = em_r[r][cx * 5] + rep_r[r][(cx * PHM_LANE_RLE_COUNTS + u) * PHM_LANE_RLE_COUNTS];
+                    cur.x = phm_chain_t<HAS_SWITCH>(left.m + e01.x, left.x + e01.y, left.y + e2, coef);
+                    cur.m = phm_chain_t<true>(diag.m + (eM + t_match[0]), diag.x + (eM + t_match[1]), diag.y + (eM + t_match[2]), coef);
+                } else {
+                    const double2 *__restrict__ e = reinterpret_cast<const double2 *>(etab_r[r] + cxs[r] * 30);
+                    const double2 e01 = e[0], e23 = e[1], e45 = e[2];
+                    cur.x = phm_chain_t<HAS_SWITCH>(left.m + e01.x, left.x + e01.y, left.y + e23.x, coef);
+                    cur.m = phm_chain_t<true>(diag.m + e23.y, diag.x + e45.x, diag.y + e45.y, coef);
+                }
                 cur.y = phm_chain_t<HAS_SWITCH>(up.m + ty_open[r], up.y + ty_extend[r], up.x + ty_switch[r], coef);
                 const bool last = x == lx && y0 + r == ly && lx >= 1;
                 fin.m = last ? cur.m : fin.m;
@@ -358,6 +420,17 @@ int phm_wide_caps(const char *who, const char *what, int64_t width, int64_t cell
     return MRP_OK;
 }
 
+/* The x-length caps of the four launch classes of the pair-per-lane kernel (4, 3, 2, 1 waves per workgroup) for n_models models, from
+ * the LDS its tables leave; -1 throughout where they leave no room for a row (every pair then goes to the pair-per-wave kernel).  rle:
+ * the tables of the run-length instantiation.  Returns the bytes of the tables. */
+int phm_lane_caps(int n_models, bool rle, int cap[4]) {
+    const int64_t table_bytes = (int64_t) phm_lane_table_doubles(n_models, rle) * (int64_t) sizeof(double);
+    const int64_t left = PHM_LDS_BYTES - table_bytes;
+    const int lane_max_x = left < PHM_LANE_BYTES_PER_X ? -1 : (int) std::min<int64_t>(PHM_LANE_MAX_X, left / PHM_LANE_BYTES_PER_X);
+    for (int c = 0; c < 4; c++) cap[c] = lane_max_x < 0 ? -1 : (int) std::min<int64_t>(lane_max_x, left / ((4 - c) * PHM_LANE_BYTES_PER_X));
+    return (int) std::min<int64_t>(table_bytes, INT32_MAX);
+}
+
 /* The host half of a pair-HMM batch of n_pairs > 0 pairs, no device needed: the pairs sorted into the launch classes of
  * the two kernels, the bands of the anchored ones, the models as the kernels read them.  Every error of the batch (prefixed
  * with who) is raised here, MRP_ERR_UNSUPPORTED for a diagonal beyond PHM_WAVE_MAX_WIDTH cells among them -- or, with wide_pairs,
@@ -372,14 +445,20 @@ int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, 
     if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
 
     /* classify.  The pair-per-lane kernel takes the unanchored pairs whose x string fits its LDS row next to the tables;
-     * launch classes by x length (4, 3, 2, 1 waves per workgroup = per CU). */
-    const int table_bytes = (16 + n_models * PHM_ETAB) * (int) sizeof(double);
-    /* (-1: the tables of this many models leave no room for a row, every pair goes to the pair-per-wave kernel) */
-    /* (-1 as well for run-length emissions, L.rle: phm_lane_kernel is not instantiated for them) */
-    const int lane_max_x =
-        L.rle || PHM_LDS_BYTES - table_bytes < PHM_LANE_BYTES_PER_X ? -1 : std::min(PHM_LANE_MAX_X, (PHM_LDS_BYTES - table_bytes) / PHM_LANE_BYTES_PER_X);
+     * launch classes by x length (4, 3, 2, 1 waves per workgroup = per CU).  A run-length batch (L.rle) has lane classes only
+     * if L.rle_lane is on, and then for the pairs whose counts are all below PHM_LANE_RLE_COUNTS. */
+    const bool rle = L.rle != nullptr;
     int lane_cap[4];
-    for (int c = 0; c < 4; c++) lane_cap[c] = std::min(lane_max_x, (PHM_LDS_BYTES - table_bytes) / ((4 - c) * PHM_LANE_BYTES_PER_X));
+    const int table_bytes = phm_lane_caps(n_models, rle, lane_cap);
+    if (rle && !L.rle_lane)
+        for (int c = 0; c < 4; c++) lane_cap[c] = -1;
+    const int lane_max_x = lane_cap[3];
+    const uint8_t *rle_counts = rle ? L.rle->counts : nullptr;
+    const auto counts_below_bound = [rle_counts](int64_t off, int64_t len) {
+        for (int64_t k = 0; k < len; k++)
+            if (rle_counts[off + k] >= PHM_LANE_RLE_COUNTS) return false;
+        return true;
+    };
     constexpr uint32_t WAVE_KEY = 0xFFFFFFFFu;
     constexpr int LY_CLIP = 4095;
     HostVec<uint32_t> &key = L.key;
@@ -398,7 +477,7 @@ int phm_classify(const char *who, const mrp_pair_hmm *models, int32_t n_models, 
                 key[(size_t) i] = WAVE_KEY;
                 continue;
             }
-            if (na == 0 && lx <= lane_max_x) {
+            if (na == 0 && lx <= lane_max_x && (!rle || (counts_below_bound(x_off[i], lx) && counts_below_bound(y_off[i], ly)))) {
                 key[(size_t) i] = (uint32_t) (std::min<int64_t>(ly, LY_CLIP) << 7 | lx);
                 c_local += (lx + 1) * (ly + 1);
             } else {
@@ -535,6 +614,9 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
     PHM_HIP(L.d_band.upload(band, s));
     PHM_HIP(L.d_out.alloc((size_t) n_pairs));
     if (H.rle) PHM_HIP(L.rle.upload(&ctx->pool, *H.rle, pool_bytes, s));
+    bool rle_lane_pairs = false;
+    for (int c = 0; c < 4; c++) rle_lane_pairs = rle_lane_pairs || (H.rle && !lane_pairs[c].empty());
+    if (rle_lane_pairs) PHM_HIP(L.rle.d_rep_lane.upload(H.rle->rep_lane, s)); /* (no lane pair: nothing beyond what the pair-per-wave kernel reads goes up) */
     for (int c = 0; c < 4; c++) {
         PHM_HIP(L.d_lane[c].upload(lane_pairs[c], s));
         PHM_HIP(L.d_wave[c].upload(wave_pairs[c], s));
@@ -552,8 +634,13 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
     /* once per device (contexts of several host threads may call concurrently) */
     static PerDeviceOnce once;
     const hipError_t configured = once.run([] {
-        hipError_t e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
+        hipError_t e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, true, PhmLaneNucleotide>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, false, PhmLaneNucleotide>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, true, PhmLaneRunLength>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void *) phm_lane_kernel<PHM_ROWS, false, PhmLaneRunLength>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *) phm_wave_kernel<PhmNucleotide>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *) phm_wave_kernel<PhmRunLength>, hipFuncAttributeMaxDynamicSharedMemorySize, PHM_LDS_BYTES);
         return e;
@@ -571,12 +658,21 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
         const int nw = std::max(1, std::min(4, (PHM_LDS_BYTES - table_bytes) / row_bytes));
         const size_t lds = (size_t) table_bytes + (size_t) nw * row_bytes;
         const int64_t per_wg = (int64_t) nw * PHM_WAVE;
-        if (has_switch)
-            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, true>), dim3((unsigned) ((n + per_wg - 1) / per_wg)), dim3((unsigned) per_wg), lds, s, L.d_lane[c].p, n, device_pool,
-                               L.d_models.p, (int) n_models, cap, L.d_out.p);
+        const dim3 grid((unsigned) ((n + per_wg - 1) / per_wg)), block((unsigned) per_wg);
+        if (H.rle) {
+            const PhmLaneRunLength::Args ea{L.rle.d_counts.p, L.rle.d_rep_lane.p};
+            if (has_switch)
+                hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, true, PhmLaneRunLength>), grid, block, lds, s, L.d_lane[c].p, n, device_pool, L.d_models.p, (int) n_models,
+                                   cap, L.d_out.p, ea);
+            else
+                hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, false, PhmLaneRunLength>), grid, block, lds, s, L.d_lane[c].p, n, device_pool, L.d_models.p, (int) n_models,
+                                   cap, L.d_out.p, ea);
+        } else if (has_switch)
+            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, true, PhmLaneNucleotide>), grid, block, lds, s, L.d_lane[c].p, n, device_pool, L.d_models.p, (int) n_models, cap,
+                               L.d_out.p, PhmLaneNucleotide::Args{});
         else
-            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, false>), dim3((unsigned) ((n + per_wg - 1) / per_wg)), dim3((unsigned) per_wg), lds, s, L.d_lane[c].p, n, device_pool,
-                               L.d_models.p, (int) n_models, cap, L.d_out.p);
+            hipLaunchKernelGGL((phm_lane_kernel<PHM_ROWS, false, PhmLaneNucleotide>), grid, block, lds, s, L.d_lane[c].p, n, device_pool, L.d_models.p, (int) n_models, cap,
+                               L.d_out.p, PhmLaneNucleotide::Args{});
         PHM_HIP(hipGetLastError());
         if (stats) stats->pairs_lane += n;
     }
@@ -613,7 +709,7 @@ int phm_enqueue(mrp_context *ctx, const uint8_t *pool, int64_t pool_bytes, int64
 /* The MRP_ERR_ARG of the run-length entries, raised with the other argument errors, and the tables: rep = 2.3025 * log_prob, one IEEE
  * multiply per entry (getRleNucleotideMatchProb, stateMachine.c:733-738), rows by x symbol with the strand and N rules of
  * repeatSubMatrix_setLogProb (repeatSubMatrix.c:16-29).  P's offsets and model indices have been checked by the caller. */
-int phm_rle_check_and_build(const char *who, const mrp_repeat_model *repeat, int32_t n_models, const uint8_t *counts, const PhmPairs &P, PhmRle &out) {
+static int phm_rle_check_models(const char *who, const mrp_repeat_model *repeat, int32_t n_models) {
     if (!repeat) return mrp_set_error(MRP_ERR_ARG, "%s: repeat is NULL", who);
     for (int32_t m = 0; m < n_models; m++) {
         if (!repeat[m].log_prob) return mrp_set_error(MRP_ERR_ARG, "%s: repeat model %d has no log_prob", who, (int) m);
@@ -621,6 +717,11 @@ int phm_rle_check_and_build(const char *who, const mrp_repeat_model *repeat, int
             return mrp_set_error(MRP_ERR_ARG, "%s: repeat model %d: max_repeat %d outside [2, 256]", who, (int) m, (int) repeat[m].max_repeat);
         if (repeat[m].strand != 0 && repeat[m].strand != 1) return mrp_set_error(MRP_ERR_ARG, "%s: repeat model %d: strand must be 0 or 1", who, (int) m);
     }
+    return MRP_OK;
+}
+int phm_rle_check_and_build(const char *who, const mrp_repeat_model *repeat, int32_t n_models, const uint8_t *counts, const PhmPairs &P, PhmRle &out) {
+    const int rc = phm_rle_check_models(who, repeat, n_models);
+    if (rc != MRP_OK) return rc;
     bool any = false;
     for (int64_t i = 0; i < P.n && !any; i++) any = P.x_len[i] > 0 || P.y_len[i] > 0;
     if (any && !counts) return mrp_set_error(MRP_ERR_ARG, "%s: counts is NULL", who);
@@ -647,24 +748,42 @@ int phm_rle_check_and_build(const char *who, const mrp_repeat_model *repeat, int
             for (int64_t k = 0; k < R * R; k++) out.rep.push_back(2.3025 * src[k]);
         }
     }
+    /* what the pair-per-lane kernel keeps in LDS: the same products for the counts below its bound (0 where the model has none) */
+    out.rep_lane.assign((size_t) n_models * PHM_LANE_RLE_REP, 0.0);
+    for (int32_t m = 0; m < n_models; m++) {
+        const int64_t R = repeat[m].max_repeat, B = std::min<int64_t>(R, PHM_LANE_RLE_COUNTS);
+        const double *full = out.rep.data() + out.rep_first[(size_t) m];
+        double *compact = out.rep_lane.data() + (size_t) m * PHM_LANE_RLE_REP;
+        for (int cx = 0; cx < 5; cx++)
+            for (int64_t u = 0; u < B; u++)
+                for (int64_t o = 0; o < B; o++) compact[(cx * PHM_LANE_RLE_COUNTS + u) * PHM_LANE_RLE_COUNTS + o] = full[(cx * R + u) * R + o];
+    }
     return MRP_OK;
 }
 
 /* cachedScores of the reference's bubble loops (bubbleGraph.c:1418,1844,2221, keyed by the substring alone): for every
  * entry k of every group g (entries [first[g], first[g + 1])), owner[k] = the entry of the group whose scores k takes,
  * itself if it is scored.  Only entries with may_own[k] != 0 (NULL: all) take part; the others get owner -1 (not scored,
- * not cached).  last: among the entries of a group with equal substrings the last one owns the scores, else the first. */
+ * not cached).  last: among the entries of a group with equal substrings the last one owns the scores, else the first.
+ * counts (NULL: none): an array parallel to pool; substrings are equal only if their counts are equal too (the run-length loops,
+ * bubbleGraph.c:1042-1055). */
 void substring_owners(int64_t n_groups, const int64_t *first, const uint8_t *pool, const int64_t *off, const int32_t *len,
-                      const uint8_t *may_own, bool last, std::vector<int64_t> &owner) {
+                      const uint8_t *may_own, bool last, std::vector<int64_t> &owner, const uint8_t *counts) {
     owner.assign((size_t) first[n_groups], -1);
     mrp_parallel_for(n_groups, 64, [&](int64_t g) {
         std::vector<int64_t> order;
         for (int64_t k = first[g]; k < first[g + 1]; k++)
             if (!may_own || may_own[k]) order.push_back(k);
-        auto same = [&](int64_t a, int64_t c) { return len[a] == len[c] && memcmp(pool + off[a], pool + off[c], (size_t) len[a]) == 0; };
+        /* (a substring of no symbols reads nothing: its offset may stand where the arrays end, or the arrays be NULL) */
+        auto compare = [&](int64_t a, int64_t c) {
+            if (len[a] == 0) return 0;
+            const int cmp = memcmp(pool + off[a], pool + off[c], (size_t) len[a]);
+            return cmp != 0 || !counts ? cmp : memcmp(counts + off[a], counts + off[c], (size_t) len[a]);
+        };
+        auto same = [&](int64_t a, int64_t c) { return len[a] == len[c] && compare(a, c) == 0; };
         std::sort(order.begin(), order.end(), [&](int64_t a, int64_t c) {
             if (len[a] != len[c]) return len[a] < len[c];
-            const int cmp = memcmp(pool + off[a], pool + off[c], (size_t) len[a]);
+            const int cmp = compare(a, c);
             return cmp != 0 ? cmp < 0 : a < c;
         });
         for (size_t i = 0; i < order.size();) {
@@ -887,7 +1006,126 @@ int mrp_forward_probabilities_rle(mrp_context *ctx, const mrp_pair_hmm *models, 
             PHM_HIP(hipMemcpyAsync(out, lp, (size_t) n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
             return (int) MRP_OK;
         },
-        &rle);
+        &rle, ctx->rle_lane_pairs != 0);
+}
+
+int mrp_rle_lane_caps(int32_t n_models, int32_t cap_out[4], int32_t *count_bound_out) {
+    if (n_models <= 0) return fail(MRP_ERR_ARG, "mrp_rle_lane_caps: n_models must be positive");
+    int cap[4];
+    (void) phm_lane_caps(n_models, true, cap);
+    if (cap_out)
+        for (int c = 0; c < 4; c++) cap_out[c] = cap[c];
+    if (count_bound_out) *count_bound_out = PHM_LANE_RLE_COUNTS;
+    return MRP_OK;
+}
+
+int mrp_allele_read_supports_rle(mrp_context *ctx, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model,
+                                 const mrp_repeat_model *forward_repeat, const mrp_repeat_model *reverse_repeat, int64_t n_bubbles,
+                                 const int64_t *allele_first, const int64_t *read_first, const uint8_t *pool, const uint8_t *counts, int64_t pool_bytes,
+                                 const int64_t *allele_off, const int32_t *allele_len, const int64_t *read_off, const int32_t *read_len,
+                                 const uint8_t *read_forward_strand, int64_t expansion, float *support, mrp_pairhmm_stats *stats) {
+    static const char *who = "mrp_allele_read_supports_rle";
+    const double t_begin = now_ms();
+    /* the argument errors first, before the context is looked at; nothing is written on an error */
+    if (n_bubbles < 0 || pool_bytes < 0) return mrp_set_error(MRP_ERR_ARG, "%s: bad sizes", who);
+    if (!forward_model || !reverse_model || !forward_repeat || !reverse_repeat || (pool_bytes > 0 && !pool))
+        return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    if (n_bubbles > 0 && (!allele_first || !read_first)) return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    if (n_bubbles > 0 && (allele_first[0] != 0 || read_first[0] != 0)) return mrp_set_error(MRP_ERR_ARG, "%s: offsets must start at 0", who);
+    std::vector<int64_t> support_first((size_t) n_bubbles + 1, 0);
+    for (int64_t b = 0; b < n_bubbles; b++) {
+        const int64_t na = allele_first[b + 1] - allele_first[b], nr = read_first[b + 1] - read_first[b];
+        if (na < 0 || nr < 0) return mrp_set_error(MRP_ERR_ARG, "%s: offsets not ascending at bubble %lld", who, (long long) b);
+        support_first[(size_t) b + 1] = support_first[(size_t) b] + na * nr;
+    }
+    const int64_t n_alleles = n_bubbles ? allele_first[n_bubbles] : 0, n_reads = n_bubbles ? read_first[n_bubbles] : 0;
+    if ((n_alleles > 0 && (!allele_off || !allele_len)) || (n_reads > 0 && (!read_off || !read_len || !read_forward_strand)) ||
+        (support_first[(size_t) n_bubbles] > 0 && !support))
+        return mrp_set_error(MRP_ERR_ARG, "%s: null argument", who);
+    bool any_symbol = false;
+    for (int64_t j = 0; j < n_alleles; j++) {
+        if (allele_len[j] < 0 || allele_off[j] < 0 || allele_off[j] + allele_len[j] > pool_bytes)
+            return mrp_set_error(MRP_ERR_ARG, "%s: allele %lld lies outside the pool", who, (long long) j);
+        any_symbol = any_symbol || allele_len[j] > 0;
+    }
+    for (int64_t k = 0; k < n_reads; k++) {
+        if (read_len[k] < 0 || read_off[k] < 0 || read_off[k] + read_len[k] > pool_bytes)
+            return mrp_set_error(MRP_ERR_ARG, "%s: read substring %lld lies outside the pool", who, (long long) k);
+        any_symbol = any_symbol || read_len[k] > 0;
+    }
+    if (any_symbol && !counts) return mrp_set_error(MRP_ERR_ARG, "%s: counts is NULL", who);
+    if (expansion < 0 || expansion % 2 != 0) return mrp_set_error(MRP_ERR_ARG, "%s: diagonalExpansion must be even (pairwiseAligner.c:855)", who);
+    const mrp_pair_hmm models[2] = {*forward_model, *reverse_model};
+    const mrp_repeat_model repeat[2] = {*forward_repeat, *reverse_repeat}; /* model 0: forward strand reads, model 1: reverse */
+    int rc = phm_rle_check_models(who, repeat, 2);
+    if (rc != MRP_OK) return rc;
+    /* cachedScores (:1042-1065): the first read of the bubble with a given substring, symbols and counts, owns the scores */
+    std::vector<int64_t> owner;
+    if (n_bubbles > 0) substring_owners(n_bubbles, read_first, pool, read_off, read_len, nullptr, false, owner, counts);
+    /* a count is checked against the model its string is scored with: a read's own strand's, an allele's for every strand among its
+     * bubble's owners */
+    const auto bad_count = [&](int64_t off, int64_t len, int R) {
+        for (int64_t i = 0; i < len; i++)
+            if (counts[off + i] >= R) return i;
+        return (int64_t) -1;
+    };
+    PhmPairList pairs;
+    std::vector<int64_t> where;
+    for (int64_t b = 0; b < n_bubbles; b++) {
+        const int64_t nr = read_first[b + 1] - read_first[b];
+        bool strand_owns[2] = {false, false};
+        for (int64_t k = read_first[b]; k < read_first[b + 1]; k++) {
+            if (owner[(size_t) k] != k) continue;
+            const int mi = read_forward_strand[k] ? 0 : 1;
+            strand_owns[mi] = true;
+            const int64_t i = bad_count(read_off[k], read_len[k], repeat[mi].max_repeat);
+            if (i >= 0)
+                return mrp_set_error(MRP_ERR_ARG, "%s: bubble %lld: the count %d of symbol %lld of read %lld is not below max_repeat %d of its strand's model", who,
+                                     (long long) b, (int) counts[read_off[k] + i], (long long) i, (long long) (k - read_first[b]), (int) repeat[mi].max_repeat);
+            for (int64_t j = allele_first[b]; j < allele_first[b + 1]; j++) {
+                where.push_back(support_first[(size_t) b] + (j - allele_first[b]) * nr + (k - read_first[b]));
+                pairs.add(allele_off[j], allele_len[j], read_off[k], read_len[k], mi, nullptr);
+            }
+        }
+        for (int mi = 0; mi < 2; mi++) {
+            if (!strand_owns[mi]) continue;
+            for (int64_t j = allele_first[b]; j < allele_first[b + 1]; j++) {
+                const int64_t i = bad_count(allele_off[j], allele_len[j], repeat[mi].max_repeat);
+                if (i >= 0)
+                    return mrp_set_error(MRP_ERR_ARG, "%s: bubble %lld: the count %d of symbol %lld of allele %lld is not below max_repeat %d of the %s strand's model",
+                                         who, (long long) b, (int) counts[allele_off[j] + i], (long long) i, (long long) (j - allele_first[b]),
+                                         (int) repeat[mi].max_repeat, mi ? "reverse" : "forward");
+            }
+        }
+    }
+    if (pairs.size() >= (1ll << 31)) return mrp_set_error(MRP_ERR_ARG, "%s: more than 2^31 pairs in one call", who);
+    const PhmPairs P = pairs.view();
+    PhmRle rle;
+    rc = phm_rle_check_and_build(who, repeat, 2, counts, P, rle);
+    if (rc != MRP_OK) return rc;
+    if (!ctx) return mrp_set_error(MRP_ERR_NO_DEVICE, "%s: no context (the pair-HMM path has no CPU fallback)", who);
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (P.n == 0) return MRP_OK;
+    std::vector<double> lp((size_t) P.n);
+    rc = phm_call(
+        ctx, who, models, 2, pool, pool_bytes, P, expansion, 0, 0, stats, t_begin,
+        [&](hipStream_t s, const double *d_lp) {
+            PHM_HIP(hipEventRecord(ctx->ev[1], s));
+            PHM_HIP(hipMemcpyAsync(lp.data(), d_lp, (size_t) P.n * sizeof(double), hipMemcpyDeviceToHost, s));
+            return (int) MRP_OK;
+        },
+        &rle, true); /* eligible pairs always run a pair per lane */
+    if (rc != MRP_OK) return rc;
+    for (size_t i = 0; i < lp.size(); i++) support[where[i]] = (float) lp[i];
+    for (int64_t b = 0; b < n_bubbles; b++) {
+        const int64_t na = allele_first[b + 1] - allele_first[b], nr = read_first[b + 1] - read_first[b];
+        for (int64_t k = 0; k < nr; k++) {
+            const int64_t o = owner[(size_t) (read_first[b] + k)] - read_first[b];
+            if (o == k) continue;
+            for (int64_t j = 0; j < na; j++) support[support_first[(size_t) b] + j * nr + k] = support[support_first[(size_t) b] + j * nr + o];
+        }
+    }
+    return MRP_OK;
 }
 
 int mrp_allele_read_supports(mrp_context *ctx, const mrp_pair_hmm *forward_model, const mrp_pair_hmm *reverse_model, int64_t n_bubbles,

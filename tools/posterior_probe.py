@@ -9,8 +9,10 @@ mrp_forward_probabilities' pair-per-workgroup kernel (wide pairs on) beside them
 --rle runs every shape a second time in the same run with run-length emissions (mrp_posterior_aligned_pairs_rle,
 mrp_forward_probabilities_rle): the same strings with counts 1 + geometric and the shipped repeat matrix of
 tests/golden/repeat_matrix_r94_g507.npz, and prints the run-length kernels' times with their ratio to the nucleotide ones.
---tiny N (with --rle) adds what the pair-per-lane kernel is for, N unanchored pairs of 25 x ~25, to the forward entries alone: run-length
-pairs never take that kernel, so this is what a batch of short pairs pays for the pair-per-wave kernel in its place."""
+--tiny N (with --rle) adds what the pair-per-lane kernel is for, N unanchored pairs of 25 x ~25, to the forward entries alone, three
+times: the nucleotide entry (a pair per lane), the run-length entry as it is by default (a pair per wave), and the run-length entry with
+mrp_context_set_rle_lane_pairs on (a pair per lane where every count is below the kernel's bound).  --tiny-len L: x strings of L symbols
+in place of 25."""
 import argparse
 import os
 import sys
@@ -115,12 +117,14 @@ def probe(ctx, models, name, pairs, opt, repeat, rle=False):
               flush=True)
 
 
-def tiny_forward(ctx, models, n, repeat):
-    """N pairs of 25 x ~25: mrp_forward_probabilities (a pair per lane) against mrp_forward_probabilities_rle (a pair per wave, class 64)"""
+def tiny_forward(ctx, models, n, repeat, length=25):
+    """N pairs of 25 x ~25: mrp_forward_probabilities (a pair per lane) against mrp_forward_probabilities_rle with run-length lane pairs
+    off (a pair per wave, class 64) and on (a pair per lane for the pairs whose counts are all below the bound), the same strings in
+    one run.  length: the x strings' (--tiny-len; the launch class of the lane kernels depends on it, mrp_rle_lane_caps)"""
     rng = np.random.default_rng(9)
     pairs = []
     for _ in range(n):
-        sx = synth.random_sequence(rng, 25)
+        sx = synth.random_sequence(rng, length)
         pairs.append((sx, synth.evolve_sequence(rng, sx, 0.05, 0.05, 0.05), []))
     pool, xo, xl, yo, yl, ao, an = pack(pairs)
     rm = [shipped_repeat_model()]
@@ -128,12 +132,20 @@ def tiny_forward(ctx, models, n, repeat):
     rows = []
     for r in range(repeat + 1):
         _, a = capi.forward_probabilities(ctx, models, pool, xo, xl, yo, yl, expansion=20)
-        _, b = capi.forward_probabilities_rle(ctx, models, rm, pool, counts, xo, xl, yo, yl, expansion=20)
+        off, b = capi.forward_probabilities_rle(ctx, models, rm, pool, counts, xo, xl, yo, yl, expansion=20)
+        ctx.set_rle_lane_pairs(True)
+        try:
+            on, c = capi.forward_probabilities_rle(ctx, models, rm, pool, counts, xo, xl, yo, yl, expansion=20)
+        finally:
+            ctx.set_rle_lane_pairs(False)
+        assert np.array_equal(on.view(np.int64), off.view(np.int64))
         if r:
-            rows.append((a.kernel_ms, b.kernel_ms))
-    lane_ms, wave_ms = (float(np.median([row[k] for row in rows])) for k in range(2))
-    print(f"tiny: {n} pairs of 25 x ~25, {a.cells} cells: mrp_forward_probabilities kernel {lane_ms:.3f} ms (lane {a.pairs_lane}, wave {a.pairs_wave}), "
+            rows.append((a.kernel_ms, b.kernel_ms, c.kernel_ms))
+    lane_ms, wave_ms, rle_lane_ms = (float(np.median([row[k] for row in rows])) for k in range(3))
+    print(f"tiny: {n} pairs of {length} x ~{length}, {a.cells} cells: mrp_forward_probabilities kernel {lane_ms:.3f} ms (lane {a.pairs_lane}, wave {a.pairs_wave}), "
           f"mrp_forward_probabilities_rle kernel {wave_ms:.3f} ms (lane {b.pairs_lane}, wave {b.pairs_wave})  x{wave_ms / lane_ms:.3f}", flush=True)
+    print(f"      with run-length lane pairs on: kernel {rle_lane_ms:.3f} ms (lane {c.pairs_lane}, wave {c.pairs_wave})  x{rle_lane_ms / wave_ms:.3f} of the switch off "
+          f"(x{wave_ms / rle_lane_ms:.2f} faster), x{rle_lane_ms / lane_ms:.3f} of the nucleotide lane kernel", flush=True)
 
 
 def main():
@@ -147,6 +159,7 @@ def main():
     ap.add_argument("--with-gaps", type=int, default=0)
     ap.add_argument("--rle", action="store_true")
     ap.add_argument("--tiny", type=int, default=0)
+    ap.add_argument("--tiny-len", type=int, default=25)
     args = ap.parse_args()
     models = [capi.PairHmm.default_nucleotide()]
     opt = capi.PosteriorOptions(with_gaps=bool(args.with_gaps))  # threshold 0.01, expansion 20, 1 000 / 40
@@ -156,7 +169,7 @@ def main():
         if args.long:
             probe(ctx, models, "long", long_pairs(args.long, args.long_len, 6), opt, args.repeat, args.rle)
         if args.tiny and args.rle:
-            tiny_forward(ctx, models, args.tiny, args.repeat)
+            tiny_forward(ctx, models, args.tiny, args.repeat, args.tiny_len)
         if args.wide:
             ctx.set_posterior_wide_pairs(True)
             ctx.set_wide_pairs(True)  # the yardstick's own switch
