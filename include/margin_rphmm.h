@@ -749,6 +749,69 @@ typedef struct mrp_posterior_stats { /* the context's most recent successful mrp
 } mrp_posterior_stats;
 int mrp_context_last_posterior(mrp_context *ctx, mrp_posterior_stats *out);
 
+/* ---- ML repeat counts of a run-length consensus from the posterior matches: polish's last step before it writes a
+ * sequence.  poa_estimateRepeatCountsUsingBayesianModel (impl/poa.c:1715-1727) over repeatSubMatrix_getMLRepeatCount
+ * (impl/repeatSubMatrix.c:65-143), and, with read_in_hap, poa_estimatePhasedRepeatCountsUsingBayesianModel (poa.c:1729-1756) over
+ * repeatSubMatrix_getPhasedMLRepeatCount (repeatSubMatrix.c:169-238), for any number of consensus strings in one call.
+ *   A node's observations are the matches of poa_augment's match loop (poa.c:324-340): a match (x, y, weight) of read r is an observation
+ * (r, y, weight) of node x + x_shift[r] of the read's consensus (x_shift: the crop of getAlignedPairsWithIndelsCroppingReference,
+ * :621-665).  Reads ascend; inside a read the matches are taken in the order of `matches`, or, with walk_backwards, in the reverse of it:
+ * the posterior entries produce the reverse of what poa_augment receives (pairwiseAligner.c:1109-1123), so a caller who passes their
+ * match_out sets walk_backwards = 1.  The order decides the bits of the fp64 sums and is kept exactly.
+ *   Unphased: min and max over the node's observed counts (min starts at R: a count >= R never lowers it; a max >= R becomes R - 1; no
+ * count below R: 0 with log probability -inf); for u = min..max, lp = 0.0, then for every observation lp = lp + log_prob[b][u][min(o, R - 1)]
+ * * weight (two IEEE operations), then lp / 1e7 (PAIR_ALIGNMENT_PROB_1); b = strand of the observation's read ? base : 3 - base, the
+ * node's symbol with N as A.  The first u that is strictly greater wins (getMax, :153-167).  Phased: the same min and max over all
+ * observations; lp1 over the observations whose read is in the haplotype, lp2 over the others (an empty list: 0.0 / 1e7); ml2 = getMax of
+ * lp2; p(u) = lp1[u] + (lp2[u] > ml2 + s ? lp2[u] : ml2 + s), s = log_het_substitution = log(hetRunLengthSubstitutionProbability) as the
+ * caller's C library gives it (shipped: log(0.0001)); the LAST u with p(u) >= the best wins (:212-220).  A result of 0 is stored as 1
+ * (poa.c:1721-1723); non_rle_length is the sum of the stored counts.
+ *   COUNTS.  Unlike the alignment entries this one accepts counts >= R and treats them as the reference does, so max_repeat lies in
+ * [2, 255] and a caller keeps exactness by passing run lengths saturated at 255 (mrp_rle_compress with max_repeat 256), not the array
+ * clamped for the alignment.  With the clamped array one result differs: a node all of whose observations were overlong gets R - 1 where
+ * the reference gives 1 (log probability -inf).
+ *   Out of scope: getRunLengthMode (repeatSubMatrix == NULL, "for an experiment", poa.c:1703-1706), poaNode_getPhasedMLBase (never
+ * called), and the base weights, inserts and deletes of poa_augment. */
+typedef struct mrp_repeat_count_options {
+    int32_t walk_backwards;       /* 0: a read's matches in the order given; 1: in reverse (the posterior entries' match_out) */
+    int32_t reserved;             /* 0 */
+    double  log_het_substitution; /* s; read only with read_in_hap; -inf is allowed, NaN is not */
+    int64_t reserved2;            /* 0 */
+} mrp_repeat_count_options;
+typedef struct mrp_repeat_count_stats {
+    int64_t observations;    /* matches of the call */
+    int64_t nodes_observed;  /* nodes with at least one observation */
+    int64_t candidates;      /* sum over the nodes with a count below R of max - min + 1 */
+    double  upload_ms, ordering_ms, estimate_ms; /* HIP events: the copies in; counting, scan, claim and rank; estimate and sums */
+    double  total_ms;        /* host wall time of the call, the checks included */
+    int64_t bytes_uploaded, bytes_downloaded;
+} mrp_repeat_count_stats;
+/* log_prob: [4][R][R] in mrp_repeat_model's layout (base, underlying, observed), R = max_repeat.  Consensus c owns the nodes
+ * [node_first[c], node_first[c+1]) of `symbols` (0..4, a byte per node) and the reads [read_first[c], read_first[c+1]); both arrays hold
+ * n_consensus + 1 offsets from 0.  Read r's run lengths are counts[y_off[r] .. + y_len[r]) (counts_bytes bytes in all: the layout of the
+ * posterior entries' counts and y_off), read_forward_strand[r] its strand, x_shift[r] its crop (x_shift NULL: 0), read_in_hap[r] != 0 puts
+ * it on the haplotype's side (read_in_hap NULL: the unphased estimate).  matches: pair i is read i, as mrp_posterior_aligned_pairs_rle
+ * returned it for the same reads; log_posterior is not read.
+ *   Outputs, written only on success: repeat_count_out[node] the stored count (>= 1); log_prob_out[node] (may be NULL) the winning value,
+ * -inf for a node without a count below R; non_rle_length_out[c]; stats (may be NULL).  A table entry of -inf under a weight of 0 is NaN
+ * here as there; which NaN is not promised.
+ *   MRP_ERR_ARG, before the context is looked at: a NULL argument; n_consensus < 0 or counts_bytes < 0; max_repeat outside [2, 255]; a table
+ * entry that is NaN or +inf; offsets not from 0 or not ascending; 2^31 or more nodes, reads or matches; a symbol above 4; a read outside
+ * counts; matches->first not from 0, not ascending over the reads; a y outside its read; x + x_shift outside its consensus; a negative
+ * weight; walk_backwards neither 0 nor 1; a NaN log_het_substitution with read_in_hap; reserved != 0.  The message names consensus, read
+ * and match.  Then MRP_ERR_NO_DEVICE for a NULL context.  These checks are what keep every device index in range. */
+int mrp_ml_repeat_counts(mrp_context *ctx, const double *log_prob, int32_t max_repeat, int64_t n_consensus, const int64_t *node_first,
+                         const uint8_t *symbols, const int64_t *read_first, const uint8_t *counts, int64_t counts_bytes, const int64_t *y_off,
+                         const int32_t *y_len, const uint8_t *read_forward_strand, const int32_t *x_shift, const uint8_t *read_in_hap,
+                         const mrp_posterior_pairs *matches, const mrp_repeat_count_options *opt, int32_t *repeat_count_out,
+                         double *log_prob_out /* may be NULL */, int64_t *non_rle_length_out, mrp_repeat_count_stats *stats);
+/* Host only, no device: rleString_expand (impl/rle.c:145-155).  n symbols (0..4 -> "ACGTN") with their counts, given either as bytes
+ * (counts8, mrp_rle_compress' output) or as int32 (counts32, repeat_count_out): exactly one of the two is not NULL.  Returns the expanded
+ * length; with out != NULL the characters are written (no terminator; capacity bytes are available), with out == NULL nothing is (a
+ * sizing call).  -1 for n < 0, a NULL symbols with n > 0, both or neither counts array, a symbol above 4, a negative count, or an out that
+ * is too small. */
+int64_t mrp_rle_expand(const uint8_t *symbols, const uint8_t *counts8, const int32_t *counts32, int64_t n, char *out, int64_t capacity);
+
 /* The alleleReadSupports loop of bubbleGraph.c:1421-1464 for n_bubbles bubbles.  Bubble b owns alleles
  * [allele_first[b], allele_first[b+1]) and read substrings [read_first[b], read_first[b+1]); x = allele, y = read
  * substring, the read's strand picks the state machine -- except that, as in the reference (cachedScores is keyed by the

@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "mrp_context_set_posterior_wide_pairs", "mrp_context_posterior_wide_count",
     "mrp_rle_compress", "mrp_forward_probabilities_rle", "mrp_posterior_aligned_pairs_rle",
     "mrp_context_set_rle_lane_pairs", "mrp_rle_lane_caps", "mrp_allele_read_supports_rle",
+    "mrp_ml_repeat_counts", "mrp_rle_expand",
 ]
 
 
@@ -264,6 +265,18 @@ class RepeatModel:
 
     def struct(self) -> RepeatModelStruct:
         return RepeatModelStruct(self.max_repeat, self.strand, None if self.log_prob is None else self.log_prob.ctypes.data_as(C.POINTER(C.c_double)))
+
+
+class RepeatCountOptions(C.Structure):
+    """mrp_repeat_count_options"""
+    _fields_ = [("walk_backwards", C.c_int32), ("reserved", C.c_int32), ("log_het_substitution", C.c_double), ("reserved2", C.c_int64)]
+
+
+class RepeatCountStats(C.Structure):
+    """mrp_repeat_count_stats"""
+    _fields_ = [("observations", C.c_int64), ("nodes_observed", C.c_int64), ("candidates", C.c_int64), ("upload_ms", C.c_double),
+                ("ordering_ms", C.c_double), ("estimate_ms", C.c_double), ("total_ms", C.c_double), ("bytes_uploaded", C.c_int64),
+                ("bytes_downloaded", C.c_int64)]
 
 
 class PosteriorStats(C.Structure):
@@ -540,6 +553,10 @@ def load():
     L.mrp_rle_lane_caps.argtypes = [i32, vp, P(i32)]
     L.mrp_allele_read_supports_rle.argtypes = [vp, P(PairHmm), P(PairHmm), P(RepeatModelStruct), P(RepeatModelStruct), i64, vp, vp, vp, vp, i64, vp, vp, vp, vp,
                                                vp, i64, vp, P(PairHmmStats)]
+    L.mrp_ml_repeat_counts.argtypes = [vp, vp, i32, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, P(PosteriorPairs), P(RepeatCountOptions), vp, vp, vp,
+                                       P(RepeatCountStats)]
+    L.mrp_rle_expand.argtypes = [vp, vp, vp, i64, vp, i64]
+    L.mrp_rle_expand.restype = i64
     L.mrp_context_set_posterior_wide_pairs.argtypes = [vp, C.c_int]
     L.mrp_context_posterior_wide_count.argtypes = [vp, P(i64), P(i64)]
     L.mrp_allele_read_supports.argtypes = [vp, P(PairHmm), P(PairHmm), i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, P(PairHmmStats)]
@@ -1484,6 +1501,54 @@ def posterior_aligned_pairs_rle(ctx, models, repeat, pool, counts, x_off, x_len,
     for l in lists:
         load().mrp_posterior_pairs_free(C.byref(l))
     return out[0], (out[1] if options.with_gaps else None), (out[2] if options.with_gaps else None), total, st
+
+
+def rle_expand(symbols, counts) -> str:
+    """mrp_rle_expand (host only): rleString_expand; counts uint8 (mrp_rle_compress') or int32 (repeat_count_out)"""
+    sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+    cnt = np.ascontiguousarray(counts)
+    if cnt.dtype != np.uint8:
+        cnt = cnt.astype(np.int32)
+    c8, c32 = (cnt.ctypes.data, None) if cnt.dtype == np.uint8 else (None, cnt.ctypes.data)
+    n = load().mrp_rle_expand(sym.ctypes.data, c8, c32, len(sym), None, 0)
+    if n < 0:
+        raise ValueError("mrp_rle_expand: bad arguments")
+    out = C.create_string_buffer(max(int(n), 1))
+    if load().mrp_rle_expand(sym.ctypes.data, c8, c32, len(sym), out, n) != n:
+        raise ValueError("mrp_rle_expand: bad arguments")
+    return out.raw[:n].decode()
+
+
+def ml_repeat_counts(ctx, log_prob, node_first, symbols, read_first, counts, y_off, y_len, read_forward_strand, matches, x_shift=None, read_in_hap=None,
+                     walk_backwards=False, log_het_substitution=0.0, max_repeat=None, want_log_prob=True, reserved=0, reserved2=0, nulls=()):
+    """mrp_ml_repeat_counts -> (repeat_count int32 [nodes], log_prob float64 [nodes] or None, non_rle_length int64 [consensus],
+    RepeatCountStats).  log_prob float64 [4, R, R]; matches a dict with first, x, y, weight as posterior_aligned_pairs_rle returns it (pair
+    i is read i).  ctx may be None (the checks that need no device); nulls names arguments to pass as NULL (for those checks).  The
+    outputs are pre-filled with -7 and must come back untouched from an error."""
+    table = np.ascontiguousarray(log_prob, dtype=np.float64)
+    R = int(max_repeat if max_repeat is not None else table.shape[-1])
+    nf, rf = np.ascontiguousarray(node_first, dtype=np.int64), np.ascontiguousarray(read_first, dtype=np.int64)
+    sym, cnt = np.ascontiguousarray(symbols, dtype=np.uint8), np.ascontiguousarray(counts, dtype=np.uint8)
+    yo, yl, sd = np.ascontiguousarray(y_off, dtype=np.int64), np.ascontiguousarray(y_len, dtype=np.int32), np.ascontiguousarray(read_forward_strand, dtype=np.uint8)
+    xs, hap = _opt(x_shift, np.int32), _opt(read_in_hap, np.uint8)
+    first = np.ascontiguousarray(matches["first"], dtype=np.int64)
+    mx, my, mw = (np.ascontiguousarray(matches[k], dtype=np.int32) for k in ("x", "y", "weight"))
+    ip = lambda a, t: a.ctypes.data_as(C.POINTER(t)) if a.size else None
+    pairs = PosteriorPairs(None if "first" in nulls else ip(first, C.c_int64), None if "x" in nulls else ip(mx, C.c_int32), ip(my, C.c_int32), ip(mw, C.c_int32), None)
+    opt = RepeatCountOptions(int(walk_backwards), int(reserved), float(log_het_substitution), int(reserved2))
+    n_cons, n_nodes = len(nf) - 1, len(sym)
+    rc_out, lp_out, len_out = np.full(n_nodes, -7, np.int32), np.full(n_nodes, -7.0), np.full(n_cons, -7, np.int64)
+    st = RepeatCountStats()
+    ptr = lambda name, a: None if a is None or name in nulls else a.ctypes.data
+    rc = load().mrp_ml_repeat_counts(ctx.h if ctx is not None else None, ptr("log_prob", table), R, n_cons, ptr("node_first", nf), ptr("symbols", sym),
+                                     ptr("read_first", rf), ptr("counts", cnt), cnt.size, ptr("y_off", yo), ptr("y_len", yl), ptr("read_forward_strand", sd),
+                                     ptr("x_shift", xs), ptr("read_in_hap", hap), None if "matches" in nulls else C.byref(pairs),
+                                     None if "opt" in nulls else C.byref(opt), ptr("repeat_count_out", rc_out), lp_out.ctypes.data if want_log_prob else None,
+                                     ptr("non_rle_length_out", len_out), C.byref(st))
+    if rc != MRP_OK:
+        assert (rc_out == -7).all() and (lp_out == -7.0).all() and (len_out == -7).all() and st.observations == 0, "outputs written on an error"
+    _check(rc)
+    return rc_out, (lp_out if want_log_prob else None), len_out, st
 
 
 def kmer_alignment_anchors(sx, sy) -> np.ndarray:
