@@ -812,6 +812,109 @@ int mrp_ml_repeat_counts(mrp_context *ctx, const double *log_prob, int32_t max_r
  * is too small. */
 int64_t mrp_rle_expand(const uint8_t *symbols, const uint8_t *counts8, const int32_t *counts32, int64_t n, char *out, int64_t capacity);
 
+/* ---- POA weights, inserts and deletes from the three posterior lists ----
+ * poa_augment (impl/poa.c:317-543) for every read of every consensus of a call, as poa_realign (:668-716) runs it over a reference graph
+ * (poa_getReferenceGraph, :112-127), then getMaxWeight (:1335-1348) per node and the four totals of :794-839.  The definition is
+ * tests/poa_oracle.py.  Consensus c owns the POA nodes [node_first[c] + c, node_first[c+1] + c + 1): its reference length + 1, the first
+ * being the prefix node ('N', count 1); "node" below is this index.
+ *   LISTS.  Pair i of each list is read i.  matches: (x, y) adds weight to baseWeights[read symbol y] and repeatCountWeights[min(count,
+ * R - 1)] of node x + 1.  deletes = the gap-x list of mrp_posterior_aligned_pairs_rle: reference x deleted after read y, y may be -1.
+ * inserts = its gap-y list: read y inserted after reference x, x may be -1 (pairwiseAligner.c:637-681, poa.c:651-653).  x_shift[r] is
+ * added to every x of read r first (:662-665, NULL: 0); the alignment-end tests then compare against the whole read and the whole
+ * reference (:399, :497).  The order of a read's entries does not matter; an (x, y) twice in one list of one read is MRP_ERR_ARG, found on
+ * the device (the reference asserts).  log_posterior is not read.
+ *   EXACTNESS.  Every accumulator is a sum of integer weights (a complete indel's: a minimum of them), accumulated as int64 and converted
+ * at the end: the reference's doubles bit for bit while they stay below 2^53.  An accumulator or total of 2^53 or more: MRP_ERR_UNSUPPORTED,
+ * nothing written.  inserts and deletes of a node come in the reference's order of creation: by the smallest (read, x, y_first, y_last)
+ * -- deletes (read, y, x_first, x_last) -- among the complete indels that equal it.
+ *   DEVIATIONS.  Strings are compared as symbols, so 'a' equals 'A' (the reference compares chars in getShift and rleString_eq).  Read
+ * counts are bytes saturated at 255 as for mrp_ml_repeat_counts: a run beyond 255 differs from the reference's unbounded count.
+ *   Out of scope: poa_getAnchorAlignments (:545-599, the one step left to close the realignment loop), poa_polish and the bubble graph,
+ * lists that stay on the device between the posterior call and this one, the observation lists (counted in n_observations, not returned). */
+typedef struct mrp_poa_options {
+    int32_t compare_repeat_counts;    /* poaConstructCompareRepeatCounts: 0 or 1 */
+    int32_t merge_ends;               /* useRunLengthEncoding as rleString_rotateString receives it: 0 or 1 */
+    double  reference_base_penalty;   /* referenceBasePenalty of getMaxWeight: not NaN, not negative */
+    int32_t want_repeat_count_weight; /* 1: repeat_count_weight is returned (nodes * max_repeat doubles); 0: it is NULL */
+    int32_t reserved;                 /* 0 */
+    int64_t reserved2;                /* 0 */
+} mrp_poa_options;
+typedef struct mrp_poa {              /* every array malloc'd; released by mrp_poa_free */
+    int64_t  n_nodes;                 /* node_first[n_consensus] + n_consensus */
+    int64_t  n_consensus;
+    int32_t  max_repeat, pad;
+    double  *base_weight;             /* [node][5] */
+    double  *repeat_count_weight;     /* [node][max_repeat], or NULL */
+    int32_t *base_pick;               /* getMaxWeight over base_weight, reference index = the node's symbol (4 for a prefix node) */
+    int32_t *repeat_count_pick;       /* getMaxWeight over the repeat count weights, reference index = the node's count (1 for a prefix
+                                       * node): the raw result, the consensus applies the 0 -> 1 rule */
+    int64_t *insert_first;            /* n_nodes + 1: node k owns the inserts [insert_first[k], insert_first[k+1]) */
+    int64_t  n_inserts;
+    int64_t *insert_str_off;          /* per insert: its string is pool_symbols / pool_counts [str_off, str_off + str_len) */
+    int32_t *insert_str_len;
+    double  *insert_weight_forward, *insert_weight_reverse;
+    int64_t *insert_n_observations;
+    int64_t  pool_len;
+    uint8_t *pool_symbols;            /* 0..4 */
+    int32_t *pool_counts;             /* int32: a merged end adds two counts */
+    int64_t *delete_first;            /* n_nodes + 1 */
+    int64_t  n_deletes;
+    int32_t *delete_length;
+    double  *delete_weight_forward, *delete_weight_reverse;
+    int64_t *delete_n_observations;
+    double  *totals;                  /* [consensus][4]: reference match weight, disagreement, insert total, delete total (:794-839) */
+} mrp_poa;
+typedef struct mrp_poa_stats {
+    int64_t matches, deletes, inserts;             /* entries per list */
+    int64_t complete_inserts, complete_deletes;    /* enumerated */
+    int64_t distinct_inserts, distinct_deletes;
+    int64_t longest_run;                           /* entries of the longest maximal run of either gap list */
+    int64_t table_slots;                           /* slots of the call's open-addressing tables */
+    int64_t bytes_uploaded, bytes_downloaded;
+    double  upload_ms, sets_ms, enumerate_ms, group_ms, picks_ms; /* HIP events: copies in; tables, match weights and the counting pass;
+                                                                   * the emitting pass; regrouping, leaders, CSR and pool; picks, totals */
+    double  check_ms;                              /* host: the argument checks and the table sizing */
+    double  total_ms;                              /* host wall time of the call */
+} mrp_poa_stats;
+/* symbols / ref_counts: a byte per reference position of every consensus (node_first as for mrp_ml_repeat_counts: n_consensus + 1 offsets
+ * from 0 into them).  Read r is read_symbols / read_counts [y_off[r], y_off[r] + y_len[r]) of pools of pool_bytes bytes each.
+ *   Outputs are written only on success; on an error *out and *stats are untouched.
+ *   MRP_ERR_ARG, before the context is looked at, in this order: a NULL argument (an array that only a count makes necessary: where the
+ * count is known); n_consensus < 0 or pool_bytes < 0; max_repeat outside [2, 255]; compare_repeat_counts, merge_ends or
+ * want_repeat_count_weight neither 0 nor 1; a penalty that is NaN or negative; reserved != 0; node_first or read_first not from 0 or not
+ * ascending; 2^31 or more nodes or reads; a reference symbol above 4; a reference count of 0 or >= max_repeat (the reference indexes
+ * repeatCountWeights[node->repeatCount] out of bounds there); a read outside the pools; a read symbol above 4; a list whose first is NULL,
+ * not from 0 or not ascending over the reads, that holds 2^31 or more entries, or whose arrays are NULL; then read by read, its matches,
+ * deletes and inserts entry by entry: a match with y outside its read or x + x_shift outside [0, L - 1]; a delete with y outside
+ * [-1, len - 1] or x + x_shift outside [0, L - 1]; an insert with y outside its read or x + x_shift outside [-1, L - 1]; a negative weight.
+ * The message names consensus, read and entry.
+ * Then MRP_ERR_NO_DEVICE for a NULL context.  These checks are what keep every device index in range.  Then, from the device:
+ * MRP_ERR_ARG for a duplicate (x, y); MRP_ERR_UNSUPPORTED for 2^31 or more complete indels of a kind or symbols of their strings, or an
+ * accumulator or total of 2^53 or more. */
+int mrp_poa_augment(mrp_context *ctx, int32_t max_repeat, int64_t n_consensus, const int64_t *node_first, const uint8_t *symbols,
+                    const uint8_t *ref_counts, const int64_t *read_first, const uint8_t *read_symbols, const uint8_t *read_counts,
+                    int64_t pool_bytes, const int64_t *y_off, const int32_t *y_len, const uint8_t *read_forward_strand,
+                    const int32_t *x_shift /* may be NULL */, const mrp_posterior_pairs *matches, const mrp_posterior_pairs *deletes,
+                    const mrp_posterior_pairs *inserts, const mrp_poa_options *opt, mrp_poa *out, mrp_poa_stats *stats /* may be NULL */);
+void mrp_poa_free(mrp_poa *p); /* frees the arrays and zeroes *p; NULL is fine */
+/* Host only, no device: poa_getConsensus (impl/poa.c:1350-1588) for ONE consensus of L reference positions (L + 1 nodes): the forward
+ * pass with logAdd (pairwiseAligner.c:282-299) and the C library's log, then the greedy trace back.  The arrays are mrp_poa's, each
+ * pointing at the consensus' first node (base_weight + 5 * k, base_pick + k, repeat_count_pick + k, insert_first + k, delete_first + k for
+ * k = node_first[c] + c; the per-insert, per-delete and pool arrays as they are: the CSR offsets are absolute).  use_rle:
+ * useRunLengthEncoding, both branches of :1486-1506 and :1550-1557.  Returns the new consensus as run-length symbols and int32 counts
+ * (rleString_construct of the expanded string with use_rle, so equal neighbours merge; one count of 1 per expanded character without),
+ * its length, and poa_to_consensus_map[L] (-1 where the reference leaves -1, mirrored as at :1573-1578); the three arrays are malloc'd and
+ * released with mrp_free (one byte each for length 0).  MRP_ERR_ARG, nothing written: a NULL argument, L < 0 or L + 1 >= 2^31, CSR offsets
+ * that descend, a string outside the pool, a symbol above 4 or a count below 0 in a string that is used, a delete whose length is below 1
+ * or that ends beyond the last node, a pick outside 0..4 / below 0 -- and a step where the reference would dereference a NULL maxInsert
+ * or maxDelete (a NaN weight gets there); the message names the node. */
+int mrp_poa_consensus(int64_t L, const double *base_weight, const int32_t *base_pick, const int32_t *repeat_count_pick,
+                      const int64_t *insert_first, const int64_t *insert_str_off, const int32_t *insert_str_len,
+                      const double *insert_weight_forward, const double *insert_weight_reverse, const uint8_t *pool_symbols,
+                      const int32_t *pool_counts, int64_t pool_len, const int64_t *delete_first, const int32_t *delete_length,
+                      const double *delete_weight_forward, const double *delete_weight_reverse, int32_t use_rle, uint8_t **symbols_out,
+                      int32_t **counts_out, int64_t *length_out, int64_t **poa_to_consensus_map_out);
+
 /* The alleleReadSupports loop of bubbleGraph.c:1421-1464 for n_bubbles bubbles.  Bubble b owns alleles
  * [allele_first[b], allele_first[b+1]) and read substrings [read_first[b], read_first[b+1]); x = allele, y = read
  * substring, the read's strand picks the state machine -- except that, as in the reference (cachedScores is keyed by the

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "mrp_rle_compress", "mrp_forward_probabilities_rle", "mrp_posterior_aligned_pairs_rle",
     "mrp_context_set_rle_lane_pairs", "mrp_rle_lane_caps", "mrp_allele_read_supports_rle",
     "mrp_ml_repeat_counts", "mrp_rle_expand",
+    "mrp_poa_augment", "mrp_poa_free", "mrp_poa_consensus",
 ]
 
 
@@ -277,6 +278,31 @@ class RepeatCountStats(C.Structure):
     _fields_ = [("observations", C.c_int64), ("nodes_observed", C.c_int64), ("candidates", C.c_int64), ("upload_ms", C.c_double),
                 ("ordering_ms", C.c_double), ("estimate_ms", C.c_double), ("total_ms", C.c_double), ("bytes_uploaded", C.c_int64),
                 ("bytes_downloaded", C.c_int64)]
+
+
+class PoaOptions(C.Structure):
+    """mrp_poa_options"""
+    _fields_ = [("compare_repeat_counts", C.c_int32), ("merge_ends", C.c_int32), ("reference_base_penalty", C.c_double),
+                ("want_repeat_count_weight", C.c_int32), ("reserved", C.c_int32), ("reserved2", C.c_int64)]
+
+
+class Poa(C.Structure):
+    """mrp_poa"""
+    _fields_ = [("n_nodes", C.c_int64), ("n_consensus", C.c_int64), ("max_repeat", C.c_int32), ("pad", C.c_int32),
+                ("base_weight", C.POINTER(C.c_double)), ("repeat_count_weight", C.POINTER(C.c_double)), ("base_pick", C.POINTER(C.c_int32)),
+                ("repeat_count_pick", C.POINTER(C.c_int32)), ("insert_first", C.POINTER(C.c_int64)), ("n_inserts", C.c_int64),
+                ("insert_str_off", C.POINTER(C.c_int64)), ("insert_str_len", C.POINTER(C.c_int32)), ("insert_weight_forward", C.POINTER(C.c_double)),
+                ("insert_weight_reverse", C.POINTER(C.c_double)), ("insert_n_observations", C.POINTER(C.c_int64)), ("pool_len", C.c_int64),
+                ("pool_symbols", C.POINTER(C.c_uint8)), ("pool_counts", C.POINTER(C.c_int32)), ("delete_first", C.POINTER(C.c_int64)),
+                ("n_deletes", C.c_int64), ("delete_length", C.POINTER(C.c_int32)), ("delete_weight_forward", C.POINTER(C.c_double)),
+                ("delete_weight_reverse", C.POINTER(C.c_double)), ("delete_n_observations", C.POINTER(C.c_int64)), ("totals", C.POINTER(C.c_double))]
+
+
+class PoaStats(C.Structure):
+    """mrp_poa_stats"""
+    _fields_ = [(k, C.c_int64) for k in ("matches", "deletes", "inserts", "complete_inserts", "complete_deletes", "distinct_inserts", "distinct_deletes",
+                                         "longest_run", "table_slots", "bytes_uploaded", "bytes_downloaded")] + \
+               [(k, C.c_double) for k in ("upload_ms", "sets_ms", "enumerate_ms", "group_ms", "picks_ms", "check_ms", "total_ms")]
 
 
 class PosteriorStats(C.Structure):
@@ -557,6 +583,13 @@ def load():
                                        P(RepeatCountStats)]
     L.mrp_rle_expand.argtypes = [vp, vp, vp, i64, vp, i64]
     L.mrp_rle_expand.restype = i64
+    L.mrp_poa_augment.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, P(PosteriorPairs), P(PosteriorPairs), P(PosteriorPairs),
+                                  P(PoaOptions), P(Poa), P(PoaStats)]
+    L.mrp_poa_augment.restype = C.c_int
+    L.mrp_poa_free.argtypes = [P(Poa)]
+    L.mrp_poa_free.restype = None
+    L.mrp_poa_consensus.argtypes = [i64] + [vp] * 10 + [i64] + [vp] * 4 + [i32, P(C.POINTER(C.c_uint8)), P(C.POINTER(C.c_int32)), P(i64), P(C.POINTER(C.c_int64))]
+    L.mrp_poa_consensus.restype = C.c_int
     L.mrp_context_set_posterior_wide_pairs.argtypes = [vp, C.c_int]
     L.mrp_context_posterior_wide_count.argtypes = [vp, P(i64), P(i64)]
     L.mrp_allele_read_supports.argtypes = [vp, P(PairHmm), P(PairHmm), i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, P(PairHmmStats)]
@@ -1549,6 +1582,82 @@ def ml_repeat_counts(ctx, log_prob, node_first, symbols, read_first, counts, y_o
         assert (rc_out == -7).all() and (lp_out == -7.0).all() and (len_out == -7).all() and st.observations == 0, "outputs written on an error"
     _check(rc)
     return rc_out, (lp_out if want_log_prob else None), len_out, st
+
+
+def _pairs_struct(lst, nulls=(), name=""):
+    """a PosteriorPairs over a dict's first / x / y / weight -> (struct, the arrays it points into)"""
+    first = np.ascontiguousarray(lst["first"], dtype=np.int64)
+    x, y, w = (np.ascontiguousarray(lst[k], dtype=np.int32) for k in ("x", "y", "weight"))
+    ip = lambda a, t, k: a.ctypes.data_as(C.POINTER(t)) if a.size and f"{name}.{k}" not in nulls else None
+    return PosteriorPairs(ip(first, C.c_int64, "first"), ip(x, C.c_int32, "x"), ip(y, C.c_int32, "y"), ip(w, C.c_int32, "weight"), None), (first, x, y, w)
+
+
+def poa_augment(ctx, max_repeat, node_first, symbols, ref_counts, read_first, read_symbols, read_counts, y_off, y_len, read_forward_strand, matches, deletes,
+                inserts, x_shift=None, compare_repeat_counts=True, merge_ends=True, reference_base_penalty=0.5, want_repeat_count_weight=False, reserved=0,
+                reserved2=0, pool_bytes=None, nulls=()):
+    """mrp_poa_augment -> a dict of numpy arrays named as mrp_poa's fields (repeat_count_weight None unless asked for) plus n_nodes,
+    n_consensus, max_repeat and stats (PoaStats).  The three lists are dicts with first, x, y, weight as posterior_aligned_pairs_rle returns
+    them (deletes = its gap-x list, inserts = its gap-y list; pair i is read i).  ctx may be None (the checks that need no device); nulls
+    names arguments to pass as NULL ("matches", "matches.first", "deletes.x", ...).  The outputs are pre-filled and must come back
+    untouched from an error."""
+    nf, rf = np.ascontiguousarray(node_first, dtype=np.int64), np.ascontiguousarray(read_first, dtype=np.int64)
+    sym, rcn = np.ascontiguousarray(symbols, dtype=np.uint8), np.ascontiguousarray(ref_counts, dtype=np.uint8)
+    rs, rc_ = np.ascontiguousarray(read_symbols, dtype=np.uint8), np.ascontiguousarray(read_counts, dtype=np.uint8)
+    yo, yl, sd = np.ascontiguousarray(y_off, dtype=np.int64), np.ascontiguousarray(y_len, dtype=np.int32), np.ascontiguousarray(read_forward_strand, dtype=np.uint8)
+    xs = _opt(x_shift, np.int32)
+    structs = [_pairs_struct(l, nulls, k) for l, k in ((matches, "matches"), (deletes, "deletes"), (inserts, "inserts"))]
+    opt = PoaOptions(int(compare_repeat_counts), int(merge_ends), float(reference_base_penalty), int(want_repeat_count_weight), int(reserved), int(reserved2))
+    out, st = Poa(), PoaStats()
+    out.n_nodes, st.matches = -7, -7
+    ptr = lambda name, a: None if a is None or name in nulls or a.size == 0 else a.ctypes.data
+    lp = lambda k, name: None if name in nulls else C.byref(structs[k][0])
+    rc = load().mrp_poa_augment(ctx.h if ctx is not None else None, int(max_repeat), len(nf) - 1, None if "node_first" in nulls else nf.ctypes.data,
+                                ptr("symbols", sym), ptr("ref_counts", rcn), None if "read_first" in nulls else rf.ctypes.data, ptr("read_symbols", rs),
+                                ptr("read_counts", rc_), rs.size if pool_bytes is None else int(pool_bytes), ptr("y_off", yo), ptr("y_len", yl),
+                                ptr("read_forward_strand", sd), ptr("x_shift", xs), lp(0, "matches"), lp(1, "deletes"), lp(2, "inserts"),
+                                None if "opt" in nulls else C.byref(opt), None if "out" in nulls else C.byref(out), C.byref(st))
+    if rc != MRP_OK:
+        assert out.n_nodes == -7 and not out.base_weight and not out.totals and st.matches == -7, "outputs written on an error"
+    _check(rc)
+    n, R, ni, nd, nc = int(out.n_nodes), int(out.max_repeat), int(out.n_inserts), int(out.n_deletes), int(out.n_consensus)
+    take = lambda p, k, dt: np.ctypeslib.as_array(p, shape=(k,)).copy() if k else np.zeros(0, dtype=dt)
+    res = dict(n_nodes=n, n_consensus=nc, max_repeat=R, stats=st,
+               base_weight=take(out.base_weight, 5 * n, np.float64).reshape(n, 5),
+               repeat_count_weight=take(out.repeat_count_weight, R * n, np.float64).reshape(n, R) if out.repeat_count_weight else None,
+               base_pick=take(out.base_pick, n, np.int32), repeat_count_pick=take(out.repeat_count_pick, n, np.int32),
+               insert_first=take(out.insert_first, n + 1, np.int64), insert_str_off=take(out.insert_str_off, ni, np.int64),
+               insert_str_len=take(out.insert_str_len, ni, np.int32), insert_weight_forward=take(out.insert_weight_forward, ni, np.float64),
+               insert_weight_reverse=take(out.insert_weight_reverse, ni, np.float64), insert_n_observations=take(out.insert_n_observations, ni, np.int64),
+               pool_symbols=take(out.pool_symbols, int(out.pool_len), np.uint8), pool_counts=take(out.pool_counts, int(out.pool_len), np.int32),
+               delete_first=take(out.delete_first, n + 1, np.int64), delete_length=take(out.delete_length, nd, np.int32),
+               delete_weight_forward=take(out.delete_weight_forward, nd, np.float64), delete_weight_reverse=take(out.delete_weight_reverse, nd, np.float64),
+               delete_n_observations=take(out.delete_n_observations, nd, np.int64), totals=take(out.totals, 4 * nc, np.float64).reshape(nc, 4))
+    load().mrp_poa_free(C.byref(out))
+    assert not out.base_weight and out.n_nodes == 0
+    return res
+
+
+def poa_consensus(poa: dict, first_node: int, L: int, use_rle: bool = True, nulls=()):
+    """mrp_poa_consensus (host only) for the consensus whose prefix node is first_node (node_first[c] + c) and that has L reference
+    positions, over poa_augment's dict (or any dict with those arrays) -> (symbols uint8, counts int32, poa_to_consensus_map int64 [L])"""
+    k = int(first_node)
+    a = {f: np.ascontiguousarray(poa[f]) for f in ("base_weight", "base_pick", "repeat_count_pick", "insert_first", "insert_str_off", "insert_str_len",
+                                                    "insert_weight_forward", "insert_weight_reverse", "pool_symbols", "pool_counts", "delete_first",
+                                                    "delete_length", "delete_weight_forward", "delete_weight_reverse")}
+    at = lambda f, off=0: None if f in nulls else a[f].ctypes.data + off * a[f].itemsize * (5 if f == "base_weight" else 1)
+    so, co, mo, n = C.POINTER(C.c_uint8)(), C.POINTER(C.c_int32)(), C.POINTER(C.c_int64)(), C.c_int64(-7)
+    rc = load().mrp_poa_consensus(int(L), at("base_weight", k), at("base_pick", k), at("repeat_count_pick", k), at("insert_first", k), at("insert_str_off"),
+                                  at("insert_str_len"), at("insert_weight_forward"), at("insert_weight_reverse"), at("pool_symbols"), at("pool_counts"),
+                                  a["pool_symbols"].size, at("delete_first", k), at("delete_length"), at("delete_weight_forward"), at("delete_weight_reverse"),
+                                  int(use_rle), C.byref(so), C.byref(co), C.byref(n), C.byref(mo))
+    if rc != MRP_OK:
+        assert not so and not co and not mo and n.value == -7, "outputs written on an error"
+    _check(rc)
+    take = lambda p, cnt, dt: np.ctypeslib.as_array(p, shape=(cnt,)).copy() if cnt else np.zeros(0, dtype=dt)
+    res = take(so, n.value, np.uint8), take(co, n.value, np.int32), take(mo, int(L), np.int64)
+    for p in (so, co, mo):
+        load().mrp_free(C.cast(p, C.c_void_p))
+    return res
 
 
 def kmer_alignment_anchors(sx, sy) -> np.ndarray:
